@@ -6,7 +6,14 @@ Workload (BASELINE.json configs[1] / configs[2]): synthetic 3.0 Gb human-scale a
 the contigs, 0.1 % soft-masked bases; flags -c TTAGGG -p TTAGGG,TCAGGG,TGAGGG,TTGGGG -x 1 -w 1000 -s 500
 -r -g -e -m -i  (124 patterns, k = 6).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--gbases G]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--gbases G] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`value`, `ms_per_step` = milliseconds of one
+timed step).  --full adds everything else the line can carry: at N = 1 the launch protocol, the box probe, the CPU
+baseline, the scan + block calling and reads sub-records and the PCIe-inclusive legs (each still subject to its --no-*
+option).  --dump-outputs DIR (N = 1) writes what the last timed step computed to DIR/<name>.npy (float64; seeded samples of
+the window and match records, every per-segment count): two builds run with the same arguments can be compared array
+for array.
 
 N = 1: one "step" = one full scan of the resident assembly: window records (8 x u32 per window) and the packed
 match stream are produced in HBM.

@@ -34,6 +34,29 @@ SETTLE_LAUNCHES = 96            # untimed scans before the warm-up steps, see ru
 
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together stay under this
+DUMP_SEED = 20261015            # the seeded samples of --dump-outputs: the same rows in every run of the same arguments
+
+
+def dump_sample_index(n, k):
+    """Sorted indices of a fixed, seeded sample of k of n rows (all n when n <= k)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def write_dump(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> numpy array of float32 / float64) as path/<name>.npy."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes is over the limit of %d" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class Watchdog:
     """A deadline around a step that may never return (first contact of N ranks over RCCL: a rank that never posts its send leaves
     rank 0's grouped receive waiting for ever, and the driver's clock with it).  When `seconds` pass before cancel(), the process
@@ -63,4 +86,4 @@ class Watchdog:
 
 
 __all__ = ["Watchdog", "argparse", "C", "json", "os", "socket", "subprocess", "sys", "time", "ROOT", "HBM_PEAK_GBS", "FLAGS", "LIB", "ORACLE",
-           "READ_FLAGS", "READ_CHUNK", "SETTLE_LAUNCHES"]
+           "READ_FLAGS", "READ_CHUNK", "SETTLE_LAUNCHES", "dump_sample_index", "write_dump"]

@@ -375,6 +375,67 @@ def pcie_inclusive(L, K, tel, buf, offsets, lens, total):
 
 
 # ------------------------------------------------------------------------------------------- the assembly scan
+DUMP_WINDOWS = 400_000          # window records in the --dump-outputs sample (9 columns of float64: 28.8 MB)
+DUMP_MATCHES = 500_000          # match records in it (5 columns: 20 MB)
+
+
+def dump_scan_outputs(path, L, K, tel, plan, batch, dev, sptr):
+    """--dump-outputs of the assembly scan: what a caller of the timed scan reads back from its last step, as float64
+      segment_summary.npy  [segments, 4]  windows, matches, canonical, forward per segment (ts_batch_segment_summary)
+      windows.npy          [k, 9]  a seeded sample of the window records: window index, then A, C, G, T and the canonical /
+                                   non-canonical / forward / reverse covered bases (ts_batch_windows_ptr)
+      matches.npy          [k, 5]  a seeded sample of the match records in position order (ts_batch_export): record index,
+                                   segment, position in the segment, forward, canonical
+    Untimed; the batch must have been synced after its last scan."""
+    import numpy as np
+    import torch
+    info = K.BatchInfo()
+    L.ts_batch_get_info(batch, C.byref(info))
+    n_seg, n_win, n_tiles = int(info.n_segments), int(info.n_windows), int(info.n_tiles)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+
+    def device_copy(src_ptr, n_u32):
+        t = torch.empty(max(1, n_u32), dtype=torch.int32, device=dev)
+        if n_u32:
+            assert hip.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(src_ptr), C.c_size_t(4 * n_u32), 3) == 0
+            # (a device-to-device hipMemcpy may return before the copy is done, and torch's stream does not wait for it)
+            torch.cuda.synchronize()
+        return t[:n_u32]
+
+    torch.cuda.synchronize()
+    summ = torch.zeros(n_seg * 4, dtype=torch.int64, device=dev)
+    dense = torch.empty(int(info.n_matches) + 1024, dtype=torch.int32, device=dev)
+    total = torch.zeros(2, dtype=torch.int64, device=dev)
+    if (L.ts_batch_segment_summary(batch, C.c_void_p(summ.data_ptr()), sptr) != 0
+            or L.ts_batch_export(batch, C.c_void_p(dense.data_ptr()), dense.numel(), C.c_void_p(total.data_ptr()), sptr) != 0):
+        raise RuntimeError(tel._ctx.error())
+    torch.cuda.synchronize()
+    n_rec, incomplete = (int(x) for x in total.tolist())
+    if incomplete or n_rec != int(info.n_matches):
+        raise RuntimeError("--dump-outputs: the exported match stream holds %d of %d records (incomplete: %d)"
+                           % (n_rec, int(info.n_matches), incomplete))
+
+    wins = device_copy(L.ts_batch_windows_ptr(batch), 8 * n_win).view(-1, 8)
+    wi = dump_sample_index(n_win, DUMP_WINDOWS)
+    w = wins[torch.from_numpy(wi).to(dev)].cpu().numpy().view(np.uint32)
+    windows = np.concatenate([wi[:, None].astype(np.float64), w.astype(np.float64)], axis=1)
+    del wins
+
+    stats = device_copy(L.ts_batch_tile_stats_ptr(batch), 4 * n_tiles).view(-1, 4).cpu().numpy().view(np.uint32)
+    offs = np.concatenate(([0], np.cumsum(stats[:, 0].astype(np.int64))))
+    assert int(offs[-1]) == n_rec, (int(offs[-1]), n_rec)
+    mi = dump_sample_index(n_rec, DUMP_MATCHES)
+    rec = dense[torch.from_numpy(mi).to(dev)].cpu().numpy().view(np.uint32).astype(np.int64)
+    del dense
+    tiles = plan.tiles
+    tile = np.searchsorted(offs, mi, side="right") - 1
+    matches = np.stack([mi, tiles["seg_index"][tile].astype(np.int64), tiles["seg_offset"][tile].astype(np.int64) + (rec >> 2),
+                        (rec >> 1) & 1, rec & 1], axis=1).astype(np.float64)
+    write_dump(path, {"segment_summary": summ.view(n_seg, 4).cpu().numpy().astype(np.float64),
+                      "windows": windows, "matches": matches})
+
+
 def run_scan(args, rank, local_rank, world, dev, backend):
     import numpy as np
     import torch
@@ -390,6 +451,8 @@ def run_scan(args, rank, local_rank, world, dev, backend):
     L = K.lib()
     forced_strong = world == 1 and bool(os.environ.get("TS_BENCH_FORCE_STRONG"))
     strong = (world > 1 or forced_strong) and not args.weak
+    if args.dump_outputs and strong:
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the single-GPU scan, not of the sharded path")
     total = int(args.gbases * 1e9)
     lens = contig_lengths(total, args.contigs, 42 + (rank if args.weak else 0))
     n = len(lens)
@@ -497,7 +560,13 @@ def run_scan(args, rank, local_rank, world, dev, backend):
         # loaded), the second (a single shot on a warm library), and the contract's own protocol without the settling scans
         # below (W warm-ups, then K steps) are measured before the steady state that `value` reports.
         protocol = {}
-        if world == 1:
+        if world == 1 and not args.full:
+            # a plain run skips those figures; its first scan is still followed by a sync, as theirs is
+            step(0)
+            drain()
+            if L.ts_batch_sync(batch) != 0:      # (grows the match buffer and rescans if the first scan overflowed)
+                raise RuntimeError(tel._ctx.error())
+        elif world == 1:
             def one():
                 torch.cuda.synchronize()
                 c0 = time.perf_counter()
@@ -526,13 +595,15 @@ def run_scan(args, rank, local_rank, world, dev, backend):
         if L.ts_batch_sync(batch) != 0:          # also grows the match buffer if it overflowed
             raise RuntimeError(tel._ctx.error())
         tmax, dev_ms = timed(step, drain, args.steps)
-        if world == 1:
+        if protocol:
             protocol["settled_ms_per_step"] = round(tmax / args.steps * 1e3, 4)
             protocol["value_is"] = "settled_ms_per_step: the steady state after %d untimed scans; a genome scanned once costs single_shot_ms" % SETTLE_LAUNCHES
         if L.ts_batch_sync(batch) != 0:
             raise RuntimeError(tel._ctx.error())
         L.ts_batch_get_info(batch, C.byref(info))
         kern_ms, launches = float(info.avg_kernel_ms), int(info.kernel_launches)
+        if args.dump_outputs:
+            dump_scan_outputs(args.dump_outputs, L, K, tel, plan, batch, dev, sptr)
         alg_bytes, n_matches, n_windows, n_tiles = int(info.algorithmic_bytes), int(info.n_matches), int(info.n_windows), int(info.n_tiles)
         result_batch = batch
         extra_cfg = {"timed_region": "resident ASCII in HBM -> window records + packed match stream in HBM"
@@ -944,7 +1015,7 @@ def run_scan(args, rank, local_rank, world, dev, backend):
                          "kernel": "ts_scan_tiles" + (" (rank 0's range)" if strong else ""), "kernel_ms": round(kern_ms, 4),
                          "launches_timed": launches, "algorithmic_bytes": alg_bytes},
         }
-        if world == 1 and not os.environ.get("TS_BENCH_NO_BOX_PROBE"):
+        if world == 1 and args.full and not os.environ.get("TS_BENCH_NO_BOX_PROBE"):
             # what THIS box issues and streams (ts_box_probe: hand-written independent integer instructions at four waves per SIMD;
             # a 1 GiB copy), measured right after the timed steps, for context: the boxes of this pool differ by up to 7 % on one
             # kernel hash (0.705 .. 0.758 ms per step).  The short probes do not explain that spread (0.720 / 0.727 / 0.739 / 0.758 ms
@@ -959,7 +1030,7 @@ def run_scan(args, rank, local_rank, world, dev, backend):
                 if fast:
                     out["roofline"]["box"]["kernel_ms_over_fastest_box_seen"] = round(kern_ms / fast, 3)
                     out["roofline"]["box"]["fastest_box_seen_kernel_ms"] = fast
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, opts, buf, offsets, lens)
         if args.verify and sharded is not None:
             # shard results: a single-GPU scan of the whole assembly on rank 0 is (a) checked against the independent torch
@@ -996,12 +1067,12 @@ def run_scan(args, rank, local_rank, world, dev, backend):
                 "terminal_blocks": int(sum(seg_out[i].n_terminal_blocks for i in range(n))),
                 "interstitial_blocks": int(sum(seg_out[i].n_interstitial_blocks for i in range(n)))}
             L.ts_free_segments(seg_out, n)
-        if world == 1 and not forced_strong and not os.environ.get("TS_BENCH_NO_BLOCKS_RECORD"):
+        if world == 1 and args.full and not forced_strong and not os.environ.get("TS_BENCH_NO_BLOCKS_RECORD"):
             out["scan_plus_block_calling"] = scan_plus_block_calling_record(args, tel, lens, buf, dev, out["ms_per_step"], stream)
-        if world == 1 and not args.no_reads and not forced_strong:
+        if world == 1 and args.full and not args.no_reads and not forced_strong:
             from .reads import reads_sub_record
             out["reads"] = reads_sub_record(args, dev)
-        if world == 1 and not args.no_e2e:
+        if world == 1 and args.full and not args.no_e2e:
             out["pcie_inclusive"] = pcie_inclusive(L, K, tel, buf, offsets, lens, total)
             out["pcie_inclusive"]["host_placement"] = ("process and library threads on NUMA node %d, the GPU's" % common.HOST_NUMA_NODE
                                                        if common.HOST_NUMA_NODE is not None else "not bound to a NUMA node")

@@ -10,8 +10,8 @@ def parse_args():
                          "bit-equality of the assembled arrays with a single-GPU scan of the whole assembly on rank 0)")
     ap.add_argument("--blocks", action="store_true", help="also time device block calling (untimed in value)")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the PCIe-inclusive leg (host buffers through the C-ABI entry points; never in value)")
-    ap.add_argument("--e2e", action="store_true", help="(kept for compatibility: the PCIe-inclusive leg is on by default at N = 1)")
+                    help="with --full: skip the PCIe-inclusive leg (host buffers through the C-ABI entry points; never in value)")
+    ap.add_argument("--e2e", action="store_true", help="(kept for compatibility: the PCIe-inclusive leg is on at N = 1 with --full)")
     ap.add_argument("--flags", default=FLAGS, help="Teloscope flags of the workload (default: configs[1])")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -23,12 +23,22 @@ def parse_args():
                          "the shard results (blocks called per rank; packed windows, writer-visible records and blocks travel)")
     ap.add_argument("--weak", action="store_true", help="N > 1: every rank scans its own --gbases assembly (weak scaling; "
                                                           "only per-segment hit summaries are gathered)")
-    ap.add_argument("--no-reads", action="store_true", help="skip the `reads` sub-record of the default line (configs[3] at 500 k reads)")
+    ap.add_argument("--no-reads", action="store_true", help="with --full: skip the `reads` sub-record (configs[3] at 500 k reads)")
     ap.add_argument("--cpu-sample-mb", type=float, default=384.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--reads", action="store_true", help="benchmark the read filter (configs[3]) instead of the assembly scan")
     ap.add_argument("--n-reads", type=float, default=5e6, help="--reads: reads filtered per step across all GPUs")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the launch protocol, the box probe, the CPU baseline, "
+                         "the scan + block calling and reads sub-records, the PCIe-inclusive legs (each still subject to its --no-* "
+                         "option); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of the larger arrays, under 64 MB in all); --gpus 1 only")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the outputs of a single-GPU run: use it with --gpus 1")
+    return args
 
 
 def free_port():
@@ -115,6 +125,9 @@ def main():
     common.ORIG_AFFINITY = os.sched_getaffinity(0)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("bench.py: --dump-outputs writes the outputs of a single-GPU run, not of a rank of %s"
+                 % os.environ["WORLD_SIZE"])
     ensure_built()                                              # before any GPU / torch.distributed call
 
     import torch  # noqa: E402  (imported before libteloscan so both share one HIP runtime)

@@ -301,11 +301,12 @@ def run_reads(args, rank, local_rank, world, dev, backend):
     for e in batches:
         if L.ts_batch_sync(e["b"]) != 0:
             raise RuntimeError(rf._ctx.error())
-    overlap[0] = False
-    torch.cuda.synchronize()
-    step()
-    torch.cuda.synchronize()
-    overlap[0] = True
+    if args.full:
+        overlap[0] = False
+        torch.cuda.synchronize()
+        step()
+        torch.cuda.synchronize()
+        overlap[0] = True
     kern_ms = alg = nm = launches = 0
     for e in batches:
         if L.ts_batch_sync(e["b"]) != 0:
@@ -332,7 +333,6 @@ def run_reads(args, rank, local_rank, world, dev, backend):
             np.concatenate([gathered[r][:shard_sizes[r]].cpu().numpy() for r in range(world)])
         kept = int(all_pass.sum())
         sec = tmax / args.steps
-        achieved = alg / (kern_ms * 1e-3) / 1e9
         out = {
             "metric": "Gbases/s filtered (whole node), --fastq-subset -l 42 on synthetic ~15 kb HiFi reads",
             "value": round(total_bases / sec / 1e9, 3), "unit": "Gbases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -346,11 +346,20 @@ def run_reads(args, rank, local_rank, world, dev, backend):
                                        "per read in HBM" + (" -> one gather of the pass bytes to rank 0" if world > 1 else "")
                                        + "; the predicate of sub-batch i runs beside the scan of sub-batch i + 1 (two streams); roofline.kernel_ms is "
                                          "the tips kernel alone, from a pass without that overlap"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                         "kernel": "ts_scan_tiles (tips mode, rank 0's reads)", "kernel_ms": round(kern_ms, 4), "launches_timed": launches,
-                         "algorithmic_bytes": alg},
         }
+        if args.full:
+            achieved = alg / (kern_ms * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                               "kernel": "ts_scan_tiles (tips mode, rank 0's reads)", "kernel_ms": round(kern_ms, 4), "launches_timed": launches,
+                               "algorithmic_bytes": alg}
+        if args.dump_outputs:
+            # the pass byte of every read (0 / 1) up to 12 M reads; beyond that a seeded sample of 4 M and their indices
+            if len(all_pass) <= 12_000_000:
+                write_dump(args.dump_outputs, {"pass": all_pass.astype(np.float32)})
+            else:
+                pick = dump_sample_index(len(all_pass), 4_000_000)
+                write_dump(args.dump_outputs, {"read_index": pick.astype(np.float64), "pass": all_pass[pick].astype(np.float32)})
         import hashlib
         out["config"]["pass_bytes_sha1"] = hashlib.sha1(all_pass.tobytes()).hexdigest()     # (the same for any number of ranks)
         if args.verify:
@@ -370,33 +379,34 @@ def run_reads(args, rank, local_rank, world, dev, backend):
                 assert [bool(all_pass[g0 + i]) for i in pick] == orf.filter(seqs), "oracle and the gathered pass bytes disagree"
                 checked += len(pick)
             out["verify"] = {"reads_checked_against_oracle": checked, "where": "the first and the last 3000 reads of the set (every 40th + every carrier)"}
-        # streaming, PCIe-inclusive: host reads through ts_filter_reads (groups pipelined through upload / scan / predicate);
-        # a pool of 200 k host reads is cycled, so that any read count streams through bounded host memory
-        e = batches[0]
-        npool = min(200_000, e["n"])
-        host = e["buf"][:int(e["offs"][npool - 1] + e["lens"][npool - 1])].cpu().numpy()
-        ptrs = (C.c_char_p * npool)()
-        base = host.ctypes.data
-        for i in range(npool):
-            ptrs[i] = C.cast(C.c_void_p(base + int(e["offs"][i])), C.c_char_p)
-        hl = (C.c_uint64 * npool)(*[int(x) for x in e["lens"][:npool]])
-        hp = (C.c_uint8 * npool)()
-        pool_bases = int(e["lens"][:npool].sum())
-        rounds = max(1, min(25, int(round(n_total / world / npool))))
-        assert L.ts_filter_reads(rf._ctx.ptr, ptrs, hl, npool, hp) == 0, rf._ctx.error()        # warm: pool, pinned rings
-        assert bytes(hp) == bytes(e["d_pass"][:npool].cpu().numpy().tobytes()), "streaming and resident filters disagree"
-        c0 = time.perf_counter()
-        for _ in range(rounds):
-            if L.ts_filter_reads(rf._ctx.ptr, ptrs, hl, npool, hp) != 0:
-                raise RuntimeError(rf._ctx.error())
-        dt = time.perf_counter() - c0
-        out["pcie_inclusive"] = {"host_placement": ("process and library threads on NUMA node %d, the GPU's" % common.HOST_NUMA_NODE
-                                                    if common.HOST_NUMA_NODE is not None else "not bound to a NUMA node"),
-                                 "entry_point": "ts_filter_reads (pageable host reads in, pass bytes out; groups of ~256 MB pipelined)",
-                                 "reads": rounds * npool, "seconds": round(dt, 4), "reads_per_s": round(rounds * npool / dt, 1),
-                                 "gbases_per_s": round(rounds * pool_bases / dt / 1e9, 3),
-                                 "note": "a pool of %d host reads filtered %d times on one GPU" % (npool, rounds)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # streaming, PCIe-inclusive: host reads through ts_filter_reads (groups pipelined through upload / scan / predicate);
+            # a pool of 200 k host reads is cycled, so that any read count streams through bounded host memory
+            e = batches[0]
+            npool = min(200_000, e["n"])
+            host = e["buf"][:int(e["offs"][npool - 1] + e["lens"][npool - 1])].cpu().numpy()
+            ptrs = (C.c_char_p * npool)()
+            base = host.ctypes.data
+            for i in range(npool):
+                ptrs[i] = C.cast(C.c_void_p(base + int(e["offs"][i])), C.c_char_p)
+            hl = (C.c_uint64 * npool)(*[int(x) for x in e["lens"][:npool]])
+            hp = (C.c_uint8 * npool)()
+            pool_bases = int(e["lens"][:npool].sum())
+            rounds = max(1, min(25, int(round(n_total / world / npool))))
+            assert L.ts_filter_reads(rf._ctx.ptr, ptrs, hl, npool, hp) == 0, rf._ctx.error()        # warm: pool, pinned rings
+            assert bytes(hp) == bytes(e["d_pass"][:npool].cpu().numpy().tobytes()), "streaming and resident filters disagree"
+            c0 = time.perf_counter()
+            for _ in range(rounds):
+                if L.ts_filter_reads(rf._ctx.ptr, ptrs, hl, npool, hp) != 0:
+                    raise RuntimeError(rf._ctx.error())
+            dt = time.perf_counter() - c0
+            out["pcie_inclusive"] = {"host_placement": ("process and library threads on NUMA node %d, the GPU's" % common.HOST_NUMA_NODE
+                                                        if common.HOST_NUMA_NODE is not None else "not bound to a NUMA node"),
+                                     "entry_point": "ts_filter_reads (pageable host reads in, pass bytes out; groups of ~256 MB pipelined)",
+                                     "reads": rounds * npool, "seconds": round(dt, 4), "reads_per_s": round(rounds * npool / dt, 1),
+                                     "gbases_per_s": round(rounds * pool_bases / dt / 1e9, 3),
+                                     "note": "a pool of %d host reads filtered %d times on one GPU" % (npool, rounds)}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from concurrent.futures import ThreadPoolExecutor
             from tests.backends import OracleReadFilter
             cores = max(1, os.cpu_count() or 1)

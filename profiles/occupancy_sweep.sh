@@ -13,7 +13,7 @@ run() {   # geometry label [flags]
 }
 rr() {
   if [ "$1" = auto ]; then unset TS_GEOMETRY; else export TS_GEOMETRY=$1; fi
-  timeout -k 10 200 python3 bench.py --reads --no-cpu-baseline 2> /tmp/occ.err \
+  timeout -k 10 200 python3 bench.py --reads --full --no-cpu-baseline 2> /tmp/occ.err \
     | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-5s reads     value %.0f Gbases/s  ms_per_step %.3f  scan kernel %.3f ms' % ('$1', d['value'], d['ms_per_step'], d['roofline']['kernel_ms']))" || tail -n 2 /tmp/occ.err
 }
 for r in $(seq 1 ${ROUNDS:-2}); do

@@ -8,7 +8,7 @@ O=gpurun_out/pcie_ab_$TAG.txt
 : > $O
 for SETTING in "$@"; do
   echo "$SETTING" >> $O
-  env $SETTING timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-reads --no-cpu-baseline 2>/dev/null | python3 -c "
+  env $SETTING timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-reads --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 p=d['pcie_inclusive']

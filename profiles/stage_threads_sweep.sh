@@ -8,7 +8,7 @@ O=gpurun_out/stage_threads_$TAG.txt
 echo "nproc $(nproc), cpu.max $(cat /sys/fs/cgroup/cpu.max 2>/dev/null || echo n/a)" > $O
 for T in 8 12 16 24; do
   echo "TS_STAGE_THREADS=$T" >> $O
-  TS_STAGE_THREADS=$T timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-reads --no-cpu-baseline 2>/dev/null | python3 -c "
+  TS_STAGE_THREADS=$T timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-reads --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 p=d['pcie_inclusive']

@@ -617,14 +617,14 @@ def test_bench_full_size_properties_small():
 
 
 def test_bench_line_contract_and_host_entry_points_small():
-    """The bench line's contract fields, and the PCIe-inclusive (default at N = 1) / --blocks legs (the host-buffer entry points and the
+    """The bench line's contract fields, and the PCIe-inclusive (at N = 1 with --full) / --blocks legs (the host-buffer entry points and the
     device block calling on the bench workload): both entry points must see the matches the resident scan counted."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gbases", "0.1", "--contigs", "9",
-                        "--steps", "2", "--warmup", "1", "--cpu-sample-mb", "8", "--blocks"],
+                        "--steps", "2", "--warmup", "1", "--cpu-sample-mb", "8", "--blocks", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -160,8 +160,8 @@ def test_bench_read_shard_over_two_ranks_equals_one_rank_and_the_oracle():
     processes sharing this GPU, the pass bytes gathered over gloo in input order) against `--reads` on one rank — the same
     pass bytes (the reference pins -j 1 == -j 8 the same way: validateFiles/fastq_subset_large_j1.tst / _j8.tst) — and both
     against the oracle's ReadTelomereFilter::matches on a sample from both ends of the read set (--verify)."""
-    one = _bench("--reads", "--n-reads", "5e5", "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline")
-    two = _bench("--reads", "--n-reads", "5e5", "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline", "--gpus", "2")
+    one = _bench("--reads", "--n-reads", "5e5", "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline", "--full")
+    two = _bench("--reads", "--n-reads", "5e5", "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline", "--gpus", "2", "--full")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert one["config"]["pass_bytes_sha1"] == two["config"]["pass_bytes_sha1"]
     assert one["config"]["kept"] == two["config"]["kept"] > 2000
@@ -174,7 +174,7 @@ def test_bench_reads_at_five_million_reads():
     """configs[3] at a tenth of its size — 5 M reads, 75 Gbases resident in HBM (BASELINE: "may be scaled to 5 M reads for
     CI") — through bench.py --reads on one GPU with --verify: every planted carrier kept, a sample from both ends of the read
     set equal to the oracle's ReadTelomereFilter::matches, and the roofline figure over the whole step (scan + predicate)."""
-    out = _bench("--reads", "--n-reads", "5e6", "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline", timeout=1200)
+    out = _bench("--reads", "--n-reads", "5e6", "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline", "--full", timeout=1200)
     assert out["n_gpus"] == 1 and out["config"]["reads"] == 5_000_000
     assert out["config"]["bases"] > 70e9 and out["config"]["kept"] > 20_000
     assert out["verify"]["reads_checked_against_oracle"] > 100
@@ -215,10 +215,10 @@ def test_bench_two_ranks_configs4_plant_equals_single_gpu():
 
 
 def test_default_line_carries_the_read_filter_and_the_launch_protocol():
-    """What the driver's plain `python bench.py` prints, minus the slow CPU leg: the `reads` sub-record (configs[3] at
+    """What `python bench.py --full` prints, minus the slow CPU leg: the `reads` sub-record (configs[3] at
     500 k reads, roofline over the whole step by 1 B/base + 1 bit/read, oracle-checked sample), the single-shot figures
     beside the settled value, and the PCIe-inclusive legs incl. ts_scan_segments_multi."""
-    out = _bench("--steps", "5", "--warmup", "2", "--no-cpu-baseline")
+    out = _bench("--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full")
     lp = out["config"]["launch_protocol"]
     assert lp["single_shot_ms"] > 0 and lp["first_scan_ms_incl_module_load_and_allocation"] >= lp["single_shot_ms"] and lp["settled_ms_per_step"] == out["ms_per_step"]
     r = out["reads"]
@@ -227,6 +227,70 @@ def test_default_line_carries_the_read_filter_and_the_launch_protocol():
     pc = out["pcie_inclusive"]
     assert pc["writer_view_multi"]["n_ctx"] >= 1 and pc["writer_view_multi"]["matches"] == out["config"]["matches"]
     assert 0 < pc["writer_view_multi"]["visible_matches"] < 0.05 * out["config"]["matches"]
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the sub-records --full adds, and --dump-outputs writes what
+    the timed scan computed in its last step: the same arrays in two runs of the same arguments, float64, under 64 MB, the
+    per-segment counts of the line, and window / match records that agree with the bases bench.py generated."""
+    import torch
+    import bench
+    import teloscope_amd as ta
+    from teloscope_amd import distributed as D
+    from teloscope_amd.cli import parse_cli, user_input
+    args = ("--gbases", "0.1", "--contigs", "9", "--steps", "3", "--warmup", "1")
+    a = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    b = _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    for out in (a, b):
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        assert out["unit"] == "Gbases/s" and out["higher_is_better"] is True and out["dtype"] == "u8" and out["value"] > 0
+        for key in ("cpu_baseline", "reads", "pcie_inclusive", "scan_plus_block_calling"):
+            assert key not in out, key
+        assert "launch_protocol" not in out["config"] and "box" not in out["roofline"]
+    got, nbytes = {}, 0
+    for name in ("segment_summary", "windows", "matches"):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == np.float64 and x.shape == y.shape and np.array_equal(x, y), name
+        got[name] = x.astype(np.int64)
+        nbytes += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert nbytes <= 64 << 20
+    summ, wins, mats = got["segment_summary"], got["windows"], got["matches"]
+    assert summ.shape == (9, 4) and summ[:, 0].sum() == a["config"]["windows"] and summ[:, 1].sum() == a["config"]["matches"]
+    assert len(wins) == a["config"]["windows"] and 0 < len(mats) <= a["config"]["matches"]
+    # the bases of the run, generated again the way bench.py lays them out
+    opts = parse_cli("x.fa " + bench.FLAGS)
+    ui = user_input(opts, device=0)
+    lens = bench.contig_lengths(int(0.1e9), 9, 42)
+    plan = D.ShardPlan(ta.Teloscope(ui), lens)
+    offs = plan.segment_offsets()
+    dev = torch.device("cuda", 0)
+    buf = torch.zeros(int(plan.info.input_bytes), dtype=torch.uint8, device=dev)
+    bench.fill_synthetic(buf, offs, lens, 42, dev)
+    host = buf.cpu().numpy() & 0xDF                                   # upper case
+    plan.close()
+    # matches: in (segment, position) order, each the k-mer of a pattern of the right strand / canonical kind
+    k = len(ui.patternInfo[0][0])
+    code = np.full(256, -1, dtype=np.int64)
+    for i, ch in enumerate(b"ACGT"):
+        code[ch] = i
+    kind = {}
+    for pat, fwd in ui.patternInfo:
+        kind[sum(int(code[ord(ch)]) << (2 * i) for i, ch in enumerate(pat))] = (int(bool(fwd)), int(pat in (ui.canonicalFwd, ui.canonicalRev)))
+    seg, pos = mats[:, 1], mats[:, 2]
+    assert np.all(np.diff(mats[:, 0]) > 0) and np.all((np.diff(seg) > 0) | ((np.diff(seg) == 0) & (np.diff(pos) > 0)))
+    at = np.asarray(offs, dtype=np.int64)[seg] + pos
+    c = code[host[at[:, None] + np.arange(k)]]
+    assert (c >= 0).all()
+    kmer = (c << (2 * np.arange(k))).sum(axis=1)
+    assert [kind.get(int(x)) for x in kmer] == [(int(f), int(cn)) for f, cn in mats[:, 3:5]]
+    # windows: A, C, G, T of a spread of the records, counted from the bases
+    step, window = ui.step, ui.windowSize
+    first = np.concatenate(([0], np.cumsum([-(-n // step) for n in lens])))
+    for row in wins[::max(1, len(wins) // 1500)]:
+        si = int(np.searchsorted(first, row[0], side="right") - 1)
+        s0 = int(row[0] - first[si]) * step
+        bases = host[offs[si] + s0:offs[si] + min(lens[si], s0 + window)]
+        assert [int((bases == ch).sum()) for ch in b"ACGT"] == row[1:5].tolist(), int(row[0])
 
 
 def test_bench_verify_full_size_configs1():
