@@ -304,6 +304,12 @@ typedef struct ts_segment_counts {
 int ts_scan_segments_blocks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out,
                             ts_segment_counts *counts);
 
+/* ---- GFA annotation (src/input.cpp:625-716).  For every segment (tips_only must be 1), ends[2*i] / ends[2*i+1]: the
+ *      longest terminal block (blockLen) at the start / end side of segs[i], 0 if none (walkSegment's distToStart <= distToEnd
+ *      rule, src/input.cpp:835-881; positions relative to abs_pos).  Host in, host out, any context; the same numbers as
+ *      ts_scan_segments_blocks' terminal blocks reduced per side, but only 8 bytes per segment leave the device. */
+int ts_terminal_ends(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, uint32_t *ends);
+
 /* ---- device-resident batches: the same scan with inputs and outputs kept in HBM.
  *      Used by bench.py and the multi-GPU driver; ts_scan_segments is built on it. ----- */
 typedef struct ts_batch_info {

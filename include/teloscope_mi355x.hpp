@@ -420,6 +420,19 @@ public:
         return res;
     }
 
+    // The GFA annotation's numbers (ts_terminal_ends): for every segment (tipsOnly is implied), {longest terminal block at
+    // the start side, at the end side} of scanSegment(seq, absPos, true) — walkSegment's rule, src/input.cpp:849-853; 0 = none
+    std::vector<std::pair<uint32_t, uint32_t>> terminalEnds(const std::vector<Segment> &segs) {
+        std::vector<ts_segment_in> in(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) { in[i] = segs[i].in(); in[i].tips_only = 1; }
+        std::vector<uint32_t> ends(2 * segs.size());
+        if (ts_terminal_ends(ctx.get(), in.data(), in.size(), ends.data()) != TS_OK)
+            throw std::runtime_error(ts_last_error(ctx.get()));
+        std::vector<std::pair<uint32_t, uint32_t>> res(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) res[i] = {ends[2 * i], ends[2 * i + 1]};
+        return res;
+    }
+
     // SegmentData Teloscope::scanSegment(std::string &sequence, uint64_t absPos, bool tipsOnly)
     SegmentData scanSegment(std::string &sequence, uint64_t absPos, bool tipsOnly) {
         return std::move(scanSegments({Segment{&sequence, absPos, tipsOnly}})[0]);

@@ -1,0 +1,353 @@
+// teloscope_mi355x_gfa.hpp — the reference's fourth input mode: a GFA assembly graph annotated with telomere caps for
+// BandageNG (README "Annotate a graph for BandageNG"; src/input.cpp:625-716, walkSegment / walkSegmentForPath :835-939).
+//
+//   GfaGraph g = readGfa("asm.gfa");                           // plain or gzip; .gfa, .gfa.gz, .gfa2, .gfa2.gz
+//   std::vector<GfaEnd> jobs = gfaTerminalJobs(g);             // the terminal ends the reference queues a job for
+//   GfaEnds e = gfaScanEnds(teloscope, g, jobs);               // ONE Teloscope::terminalEnds call, each segment once
+//   writeAnnotatedGfa(g, jobs, e.ends, "out/asm.gfa.telo.annotated.gfa", "out/asm.gfa.telo.annotated.colors.csv");
+//
+// or annotateGfa(teloscope, file, outDir) for all four.  The device reduces a segment to {longest terminal block at its start
+// side, at its end side} (ts_terminal_ends): 8 bytes per segment, whatever the number of blocks.
+//
+// Input lines are written back verbatim (line ends as read) with two exceptions: the header says VN:Z:1.2 (added when the input
+// has none, replacing a VN:Z:2.0), and a GFA 2 segment `S name len seq [tags]` loses its length field.  Other GFA 2 records are
+// refused.  GFA 1.1 W lines are copied through and are not read as paths.
+#pragma once
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <tuple>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "teloscope_mi355x_io.hpp"
+
+namespace teloscope_mi355x {
+
+struct GfaSegment {
+    std::string name;
+    const char *seq = nullptr;        // the sequence field where it lies in GfaGraph::data (nullptr: '*')
+    uint64_t len = 0;
+};
+
+struct GfaPath {                      // a P line: its components as written (name, orientation)
+    std::string name;
+    std::vector<std::pair<std::string, char>> comps;
+};
+
+struct GfaEdit { size_t off, len; std::string text; };   // input bytes [off, off + len) written as `text`
+
+struct GfaGraph {
+    std::string file, baseName;       // baseName: the output files' stem (userInput.inSequenceName)
+    std::string data;                 // the whole input, decompressed
+    int version = 1;                  // 2 when the header says VN:Z:2.x
+    bool hasVersion = false;          // some H line carries VN:Z
+    std::vector<GfaSegment> segments; // S records in input order
+    std::unordered_map<std::string, uint32_t> index;
+    std::vector<GfaPath> paths;
+    std::vector<GfaEdit> edits;       // ascending offsets, disjoint
+};
+
+// One terminal end the reference queues a scan job for (src/input.cpp:637-674)
+struct GfaEnd {
+    uint32_t seg;
+    char orient;                      // path orientation ('+' for a pathless graph)
+    bool isFirst;                     // path mode: the path's first (true) or last segment
+    bool pathAware;                   // walkSegmentForPath (true) or walkSegment
+};
+
+struct GfaEnds {
+    std::vector<std::pair<uint32_t, uint32_t>> ends;    // per graph segment: {start side, end side}, 0 = none / not scanned
+    size_t scanned = 0, noSeq = 0;                       // distinct segments scanned; ends whose segment has no sequence
+};
+
+struct GfaAnnotateStats {
+    size_t segments = 0, ends = 0, scanned = 0, noSeq = 0, nodes = 0;
+    double parseMs = 0, scanMs = 0, writeMs = 0;
+};
+
+namespace detail {
+
+inline std::string gfaReadAll(const std::string &file) {
+    gzFile in = gzopen(file.c_str(), "rb");                     // (zlib reads plain files through the same calls)
+    if (!in) throw std::runtime_error("Could not open assembly input '" + file + "'.");
+    gzbuffer(in, 1u << 20);
+    std::string data;
+    size_t used = 0;
+    for (;;) {
+        if (data.size() - used < (size_t(16) << 20)) data.resize(std::max<size_t>(data.size() * 2, size_t(32) << 20));
+        const int n = gzread(in, &data[used], static_cast<unsigned>(std::min<size_t>(data.size() - used, size_t(1) << 30)));
+        if (n < 0) { gzclose(in); throw std::runtime_error("Could not read assembly input '" + file + "'."); }
+        if (n == 0) break;
+        used += static_cast<size_t>(n);
+    }
+    gzclose(in);
+    data.resize(used);
+    return data;
+}
+
+struct GfaField { size_t off, len; };
+
+// the tab-separated fields of the line [b, e) ('\r' before the line feed already cut), offsets relative to `base`
+inline void gfaFields(const char *base, const char *b, const char *e, std::vector<GfaField> &f, size_t maxFields) {
+    f.clear();
+    const char *p = b;
+    while (f.size() + 1 < maxFields) {
+        const char *t = static_cast<const char *>(std::memchr(p, '\t', static_cast<size_t>(e - p)));
+        if (!t) break;
+        f.push_back({static_cast<size_t>(p - base), static_cast<size_t>(t - p)});
+        p = t + 1;
+    }
+    f.push_back({static_cast<size_t>(p - base), static_cast<size_t>(e - p)});
+}
+
+// what a chunk of lines holds (parsed side by side, joined in input order)
+struct GfaChunk {
+    struct S { size_t line, lineEnd, f1, f1len, f2, f2len, f3, f3len; bool has3; };   // offsets into data
+    std::vector<S> segs;
+    std::vector<GfaPath> paths;
+    std::vector<std::pair<size_t, size_t>> headers;   // H lines carrying VN:Z: line start, content end
+    std::vector<std::string> versions;
+    std::string foreign;                                // first record type other than H / S / '#' (for a GFA 2 input)
+};
+
+}  // namespace detail
+
+// Reads a GFA 1.x or 2.0 graph (plain or gzip).  Throws on an unreadable file, a GFA 2 record other than H / S, or a
+// segment named twice.
+inline GfaGraph readGfa(const std::string &file) {
+    GfaGraph g;
+    g.file = file;
+    const size_t slash = file.find_last_of('/');
+    g.baseName = slash == std::string::npos ? file : file.substr(slash + 1);
+    g.data = detail::gfaReadAll(file);
+    const char *const base = g.data.data();
+    const size_t n = g.data.size();
+    // chunks of ~16 MB cut at line starts, parsed on the host threads
+    std::vector<size_t> cuts{0};
+    for (size_t at = size_t(16) << 20; at < n;) {
+        const char *nl = static_cast<const char *>(std::memchr(base + at, '\n', n - at));
+        if (!nl) break;
+        const size_t c = static_cast<size_t>(nl - base) + 1;
+        if (c >= n) break;
+        cuts.push_back(c);
+        at = c + (size_t(16) << 20);
+    }
+    cuts.push_back(n);
+    std::vector<detail::GfaChunk> chunks(cuts.size() - 1);
+    detail::onThreads(chunks.size(), [&](size_t ci) {
+        detail::GfaChunk &ch = chunks[ci];
+        std::vector<detail::GfaField> f;
+        for (size_t ls = cuts[ci]; ls < cuts[ci + 1];) {
+            const char *nl = static_cast<const char *>(std::memchr(base + ls, '\n', cuts[ci + 1] - ls));
+            const size_t next = nl ? static_cast<size_t>(nl - base) + 1 : cuts[ci + 1];
+            size_t le = nl ? static_cast<size_t>(nl - base) : cuts[ci + 1];
+            if (le > ls && base[le - 1] == '\r') --le;
+            const char *b = base + ls, *e = base + le;
+            if (e > b) {
+                const char type = *b;
+                const bool single = e - b == 1 || b[1] == '\t';
+                if (type == 'S' && single) {
+                    detail::gfaFields(base, b, e, f, 5);
+                    if (f.size() >= 3)
+                        ch.segs.push_back({ls, le, f[1].off, f[1].len, f[2].off, f[2].len, f.size() >= 4 ? f[3].off : 0,
+                                           f.size() >= 4 ? f[3].len : 0, f.size() >= 4});
+                } else if (type == 'P' && single) {
+                    detail::gfaFields(base, b, e, f, 4);
+                    if (f.size() >= 3) {
+                        GfaPath p;
+                        p.name.assign(base + f[1].off, f[1].len);
+                        const char *c = base + f[2].off, *ce = c + f[2].len;
+                        while (c < ce) {
+                            const char *d = c;
+                            while (d < ce && *d != ',' && *d != ';') ++d;
+                            if (d - c >= 2) p.comps.emplace_back(std::string(c, static_cast<size_t>(d - c - 1)), d[-1]);
+                            c = d + 1;
+                        }
+                        ch.paths.push_back(std::move(p));
+                    }
+                } else if (type == 'H' && single) {
+                    detail::gfaFields(base, b, e, f, size_t(-1));
+                    for (size_t i = 1; i < f.size(); ++i)
+                        if (f[i].len >= 5 && std::memcmp(base + f[i].off, "VN:Z:", 5) == 0) {
+                            ch.headers.emplace_back(ls, le);
+                            ch.versions.emplace_back(base + f[i].off + 5, f[i].len - 5);
+                        }
+                }
+                if (ch.foreign.empty() && !(single && (type == 'H' || type == 'S')) && type != '#') {
+                    const char *t = static_cast<const char *>(std::memchr(b, '\t', static_cast<size_t>(e - b)));
+                    ch.foreign.assign(b, t ? t : e);
+                }
+            }
+            ls = next;
+        }
+    });
+    for (const detail::GfaChunk &ch : chunks)
+        for (const std::string &v : ch.versions) { g.hasVersion = true; g.version = (!v.empty() && v[0] == '2') ? 2 : 1; }
+    size_t nseg = 0;
+    for (const detail::GfaChunk &ch : chunks) nseg += ch.segs.size();
+    g.segments.reserve(nseg);
+    g.index.reserve(nseg);
+    for (detail::GfaChunk &ch : chunks) {
+        if (g.version == 2 && !ch.foreign.empty())
+            throw std::runtime_error("GFA 2 record type '" + ch.foreign + "' in '" + file +
+                                     "' is not supported: only H and S records of a GFA 2 graph are read.");
+        for (const auto &h : ch.headers) {
+            const std::string line(base + h.first, h.second - h.first);
+            if (line.find("VN:Z:2") != std::string::npos) g.edits.push_back({h.first, h.second - h.first, "H\tVN:Z:1.2"});
+        }
+        for (const detail::GfaChunk::S &s : ch.segs) {
+            GfaSegment seg;
+            seg.name.assign(base + s.f1, s.f1len);
+            size_t so = s.f2, sl = s.f2len;
+            if (g.version == 2 && s.has3) {                          // S name len seq [tags]: the length goes
+                so = s.f3; sl = s.f3len;
+                g.edits.push_back({s.f2, s.f3 - s.f2, std::string()});
+            }
+            if (!(sl == 1 && base[so] == '*')) { seg.seq = base + so; seg.len = sl; }
+            if (!g.index.emplace(seg.name, static_cast<uint32_t>(g.segments.size())).second)
+                throw std::runtime_error("segment '" + seg.name + "' is defined twice in '" + file + "'.");
+            g.segments.push_back(std::move(seg));
+        }
+        for (GfaPath &p : ch.paths) g.paths.push_back(std::move(p));
+    }
+    std::sort(g.edits.begin(), g.edits.end(), [](const GfaEdit &a, const GfaEdit &b) { return a.off < b.off; });
+    return g;
+}
+
+// The ends the reference scans (src/input.cpp:637-674).  With P lines: per path, the first and the last component that
+// names an S record with orientation '+' / '-', as unique (segment, orientation, isFirst) ends in that order.  Without:
+// every segment, '+'.
+inline std::vector<GfaEnd> gfaTerminalJobs(const GfaGraph &g) {
+    std::vector<GfaEnd> jobs;
+    if (!g.paths.empty()) {
+        std::set<std::tuple<uint32_t, char, bool>> ends;
+        for (const GfaPath &p : g.paths) {
+            std::vector<std::pair<uint32_t, char>> comps;
+            for (const auto &c : p.comps) {
+                if (c.second != '+' && c.second != '-') continue;
+                const auto it = g.index.find(c.first);
+                if (it != g.index.end()) comps.emplace_back(it->second, c.second);
+            }
+            if (comps.empty()) continue;
+            ends.emplace(comps.front().first, comps.front().second, true);
+            ends.emplace(comps.back().first, comps.back().second, false);
+        }
+        for (const auto &e : ends) jobs.push_back({std::get<0>(e), std::get<1>(e), std::get<2>(e), true});
+    } else {
+        jobs.reserve(g.segments.size());
+        for (uint32_t i = 0; i < g.segments.size(); ++i) jobs.push_back({i, '+', false, false});
+    }
+    return jobs;
+}
+
+// The distinct segments with a sequence that the ends use, in one Teloscope::terminalEnds call (each segment once, scanned
+// where it lies in the input buffer; the library folds case as unmaskSequence does).  Warns on `log` about ends whose
+// segment has no sequence, in the reference's words.
+inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::vector<GfaEnd> &jobs, std::ostream &log = std::cerr) {
+    GfaEnds r;
+    r.ends.assign(g.segments.size(), {0u, 0u});
+    std::vector<char> want(g.segments.size(), 0);
+    for (const GfaEnd &j : jobs) {
+        if (!g.segments[j.seg].seq) ++r.noSeq;
+        else want[j.seg] = 1;
+    }
+    if (r.noSeq)
+        log << "Warning: " << r.noSeq << " of " << jobs.size()
+            << " GFA segment(s) had no sequence (*); skipped for telomere annotation.\n";
+    std::vector<uint32_t> which;
+    std::vector<Teloscope::Segment> segs;
+    for (uint32_t i = 0; i < g.segments.size(); ++i)
+        if (want[i]) { which.push_back(i); segs.emplace_back(g.segments[i].seq, g.segments[i].len, 0, true); }
+    r.scanned = which.size();
+    if (segs.empty()) return r;
+    const std::vector<std::pair<uint32_t, uint32_t>> e = teloscope.terminalEnds(segs);
+    for (size_t k = 0; k < which.size(); ++k) r.ends[which[k]] = e[k];
+    return r;
+}
+
+// Writes the annotated graph and its colours file; returns the number of telomere nodes.  ends: per graph segment (GfaEnds).
+// Node rules of walkSegment / walkSegmentForPath (src/input.cpp:835-939): a path end keeps the block on the physical side
+// isFirst == (orient == '+'), edge orientation orient at a start, its flip at an end; a pathless segment gets a node per side
+// that has a block, '+' in the name, edge '+' at the start and '-' at the end.
+inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jobs,
+                                const std::vector<std::pair<uint32_t, uint32_t>> &ends,
+                                const std::string &outGfa, const std::string &outColors) {
+    struct Node { std::string name; uint32_t seg, len; char edge; };
+    std::vector<Node> nodes;
+    for (const GfaEnd &j : jobs) {
+        const std::string &seg = g.segments[j.seg].name;
+        const auto &e = ends[j.seg];
+        if (j.pathAware) {
+            const bool atStart = j.isFirst == (j.orient == '+');
+            const uint32_t len = atStart ? e.first : e.second;
+            if (!len) continue;
+            const char edge = j.isFirst ? j.orient : (j.orient == '+' ? '-' : '+');
+            nodes.push_back({"telomere_" + seg + j.orient + (j.isFirst ? "_start" : "_end"), j.seg, len, edge});
+        } else {
+            if (e.first) nodes.push_back({"telomere_" + seg + "+_start", j.seg, e.first, '+'});
+            if (e.second) nodes.push_back({"telomere_" + seg + "+_end", j.seg, e.second, '-'});
+        }
+    }
+    std::ofstream out(outGfa, std::ios::binary);
+    if (!out) throw std::runtime_error("could not write " + outGfa);
+    if (!g.hasVersion) out << "H\tVN:Z:1.2\n";
+    size_t at = 0;
+    for (const GfaEdit &ed : g.edits) {
+        out.write(g.data.data() + at, static_cast<std::streamsize>(ed.off - at));
+        out << ed.text;
+        at = ed.off + ed.len;
+    }
+    out.write(g.data.data() + at, static_cast<std::streamsize>(g.data.size() - at));
+    if (!g.data.empty() && g.data.back() != '\n') out << '\n';
+    std::string tail;
+    for (const Node &nd : nodes) {
+        tail += "S\t" + nd.name + "\t*\tLN:i:6\tRC:i:6000\tTL:i:" + std::to_string(nd.len) + "\n";
+        tail += "L\t" + nd.name + "\t+\t" + g.segments[nd.seg].name + "\t" + nd.edge + "\t0M\tRC:i:0\n";
+    }
+    out << tail;
+    out.close();
+    if (!out) throw std::runtime_error("could not write " + outGfa);
+    std::ofstream colors(outColors, std::ios::binary);
+    if (!colors) throw std::runtime_error("could not write " + outColors);
+    colors << "node\tcolor\n";
+    for (const Node &nd : nodes) colors << nd.name << "\t#008000\n";
+    colors.close();
+    if (!colors) throw std::runtime_error("could not write " + outColors);
+    return nodes.size();
+}
+
+// teloscope asm.gfa -o outDir: outDir/<name>.telo.annotated.gfa and outDir/<name>.telo.annotated.colors.csv
+inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                    std::ostream &log = std::cerr) {
+    using Clock = std::chrono::steady_clock;
+    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    GfaAnnotateStats st;
+    const auto t0 = Clock::now();
+    const GfaGraph g = readGfa(file);
+    const std::vector<GfaEnd> jobs = gfaTerminalJobs(g);
+    const auto t1 = Clock::now();
+    const GfaEnds e = gfaScanEnds(teloscope, g, jobs, log);
+    const auto t2 = Clock::now();
+    const std::string stem = outDir + "/" + g.baseName + ".telo.annotated";
+    st.nodes = writeAnnotatedGfa(g, jobs, e.ends, stem + ".gfa", stem + ".colors.csv");
+    const auto t3 = Clock::now();
+    st.segments = g.segments.size();
+    st.ends = jobs.size();
+    st.scanned = e.scanned;
+    st.noSeq = e.noSeq;
+    st.parseMs = ms(t0, t1);
+    st.scanMs = ms(t1, t2);
+    st.writeMs = ms(t2, t3);
+    return st;
+}
+
+}  // namespace teloscope_mi355x

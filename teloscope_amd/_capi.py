@@ -187,6 +187,7 @@ SYMBOLS = [
     "ts_shard_peek", "ts_shards_finalize", "ts_scan_segments_multi", "ts_batch_read_pass_status", "ts_pack_bases",
     "ts_batch_set_emit", "ts_exchange_unique_id", "ts_exchange_last_error", "ts_exchange_create", "ts_exchange_destroy",
     "ts_exchange_gather", "ts_box_probe", "ts_batch_bind_shard_message", "ts_refresh_env", "ts_streams_concurrent", "ts_batch_wait_scan", "ts_batch_set_timing", "ts_batch_set_record_bits",
+    "ts_terminal_ends",
 ]
 
 
@@ -264,6 +265,8 @@ def lib():
     L.ts_scan_segments_blocks.argtypes = [C.c_void_p, C.POINTER(SegmentIn), C.c_size_t, C.POINTER(SegmentOut),
                                           C.POINTER(SegmentCounts)]
     L.ts_free_segments.argtypes = [C.POINTER(SegmentOut), C.c_size_t]
+    L.ts_terminal_ends.argtypes = [C.c_void_p, C.POINTER(SegmentIn), C.c_size_t, C.POINTER(C.c_uint32)]
+    L.ts_terminal_ends.restype = C.c_int
     L.ts_filter_reads.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64),
                                   C.c_size_t, C.POINTER(C.c_uint8)]
     L.ts_label_terminal_blocks.argtypes = [C.POINTER(Block), C.c_size_t, C.c_uint16, C.c_uint64,

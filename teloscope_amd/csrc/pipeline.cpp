@@ -1,5 +1,5 @@
 // pipeline.cpp — the host-buffer entry points of libteloscan: ts_scan_segments, ts_scan_segments_blocks,
-// ts_filter_reads(_multi).  Host memory in, host results out.
+// ts_filter_reads(_multi), ts_terminal_ends.  Host memory in, host results out.
 //
 // A call's segments (or reads) are cut into GROUPS of about 256 MB of input and the groups flow through three
 // stages that run concurrently, each on its own host thread and HIP stream:
@@ -83,7 +83,7 @@ private:
     int n_;
 };
 
-enum class Mode { Matches, Blocks, ReadPass };
+enum class Mode { Matches, Blocks, ReadPass, Ends };   // Ends: ts_terminal_ends, 8 bytes per segment back
 
 struct Item { const char *seq; uint64_t len, abs_pos; uint8_t format; uint32_t n_pieces; };     // format: TS_INPUT_BASES / TS_INPUT_TEXT_PIECES (seq = ts_text_piece[])
 
@@ -608,7 +608,9 @@ int upload_batch(ts_batch *b, const Item *items, int &slot, bool used[]) {
 // The terminal-block predicate of a scanned tips batch on the device: one byte per read
 // (ReadTelomereFilter::matches, src/read-filter.cpp:37-45, reduced to !terminalBlocks.empty()), written to
 // d_pass (device).  The per-read table the kernel walks is built once per batch.
-int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st) {
+// d_ends (instead of a predicate): the same walks reduced to the longest terminal block per side, two u32 per segment
+// (ts_terminal_ends); the overflow flag is then left for the caller to read.
+int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, uint32_t *d_ends = nullptr) {
     ts_ctx *c = b->ctx;
     const size_t ns = b->segs.size();
     if (!ns) return TS_OK;
@@ -639,6 +641,17 @@ int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st) {
     Q.k = c->k;
     Q.long_list = 128;                                        // floor of the per-wave threshold, see ts_terminal_predicate
     const bool canon = b->emitted && b->kp.emit == 2u && !b->dense && b->all_terminal && b->d_chain.p && b->d_vis.p && !b->kp.vis_wide;
+    if (d_ends) {
+        const int e = ts_k_launch_terminal_ends((const TsTile *)b->d_tiles.p, (const unsigned long long *)b->d_tile_off.p,
+                                                b->stats_ptr(), b->records_ptr(), b->records_limit(), (const uint32_t *)dt,
+                                                (const unsigned long long *)(dt + off_in), (const unsigned long long *)(dt + off_len),
+                                                (uint32_t)ns, &Q, d_ends, (uint32_t *)(dt + off_long), (uint32_t *)(dt + off_count),
+                                                (b->all_terminal && !b->dense && ((uintptr_t)b->records_ptr() & 15u) == 0) ? 1 : 0,
+                                                (const uint32_t *)b->d_fill.p, b->dense ? 0xFFFFFFFFu : b->region_cap, b->dense ? 0u : b->total_waves,
+                                                (uint32_t *)(dt + off_flag), b->records16() ? 1 : 0, st);
+        if (e != 0) return c->fail(TS_ERR_HIP, "terminal-ends kernel launch failed");
+        return TS_OK;
+    }
     int e = ts_k_launch_predicate((const TsTile *)b->d_tiles.p, (const unsigned long long *)b->d_tile_off.p,
                                   b->stats_ptr(), b->records_ptr(), b->records_limit(), (const uint32_t *)dt,
                                   (const unsigned long long *)(dt + off_in), (const unsigned long long *)(dt + off_len),
@@ -669,6 +682,46 @@ int batch_read_pass(ts_batch *b, uint8_t *pass_out, hipStream_t st) {
     return TS_OK;
 }
 
+// the longest terminal block at either side of a segment, from its terminal blocks (start: absolute position)
+void reduce_terminal_ends(const ts_segment_out &o, uint64_t len, uint64_t abs_pos, uint32_t *two) {
+    two[0] = two[1] = 0u;
+    for (uint64_t j = 0; j < o.n_terminal_blocks; ++j) {
+        const ts_block &blk = o.terminal_blocks[j];
+        const uint64_t rel = blk.start - abs_pos;
+        uint32_t &side = two[rel <= len - (rel + blk.block_len) ? 0 : 1];      // walkSegment, src/input.cpp:849-853
+        side = std::max(side, blk.block_len);
+    }
+}
+
+// ts_terminal_ends of a scanned tips batch: the per-side maxima of every segment to ends_out (2 x u32 per segment).  After a
+// region overflow in the scan (the guard's flag: the kernel judged nothing) the group's blocks are called and reduced instead.
+int batch_terminal_ends(ts_batch *b, uint32_t *ends_out, int slot, hipStream_t st) {
+    ts_ctx *c = b->ctx;
+    const size_t ns = b->segs.size();
+    if (!ns) return TS_OK;
+    DevBuf d_ends;
+    struct Return { ts_ctx *c; DevBuf &a; ~Return() { c->pool.give(std::move(a)); } } give_back{c, d_ends};
+    HIP_TRY(c, c->pool.take(ns * 8 + 16, d_ends));
+    int rc = batch_read_pass_device(b, nullptr, st, (uint32_t *)d_ends.p);
+    if (rc != TS_OK) return rc;
+    const size_t off_in = (((ns + 1) * 4 + 15) & ~(size_t)15), off_len = off_in + ns * 8, off_long = off_len + ns * 8,
+                 off_count = (off_long + ns * 4 + 15) & ~(size_t)15, off_flag = off_count + 16;      // (batch_read_pass_device's table)
+    char *const dt = (char *)b->d_readtab.p;
+    uint32_t flag = 0;
+    HIP_TRY(c, hipMemcpyAsync(ends_out, d_ends.p, ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&flag, dt + off_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (!flag) return TS_OK;
+    HIP_TRY(c, hipMemsetAsync(dt + off_flag, 0, 4, st));
+    ts_fetched *f = ts_batch_fetch(b, false, slot, &rc);
+    std::vector<ts_segment_out> tmp(ns);
+    if (rc == TS_OK) rc = ts_batch_finalize(b, f, tmp.data());
+    if (rc == TS_OK)
+        for (size_t i = 0; i < ns; ++i) reduce_terminal_ends(tmp[i], b->segs[i].len, b->segs[i].abs_pos, ends_out + 2 * i);
+    ts_free_segments(tmp.data(), ns);
+    return rc;
+}
+
 int batch_counts(ts_batch *b, ts_segment_counts *counts, bool tips, hipStream_t st) {
     ts_ctx *c = b->ctx;
     const size_t ns = b->segs.size();
@@ -688,7 +741,7 @@ int batch_counts(ts_batch *b, ts_segment_counts *counts, bool tips, hipStream_t 
 // The three-stage pipeline over the groups of one call.  items: the call's segments or reads in input order;
 // results go to out / counts / pass at the same indices.
 int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, ts_segment_out *out,
-                 ts_segment_counts *counts, uint8_t *pass) {
+                 ts_segment_counts *counts, uint8_t *pass, uint32_t *ends = nullptr) {
     if (items.empty()) return TS_OK;
     if (ctx->device == kNoDevice) return ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it");
     const auto t_begin = Clock::now();
@@ -802,6 +855,8 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
             if (rc == TS_OK) gr->b->last_stream = ctx->down_stream;   // the scan is complete (synced): later work runs on this stage's stream
             if (rc == TS_OK && mode == Mode::ReadPass) {
                 rc = batch_read_pass(gr->b, pass + gr->first, ctx->down_stream);
+            } else if (rc == TS_OK && mode == Mode::Ends) {
+                rc = batch_terminal_ends(gr->b, ends + 2 * gr->first, slot, ctx->down_stream);
             } else if (rc == TS_OK) {
                 // device work + D2H of this group while the previous group's records are expanded on the host threads
                 ts_fetched *f = ts_batch_fetch(gr->b, mode == Mode::Matches, slot, &rc);
@@ -836,7 +891,8 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
     if (timing) {
         double p = 0, u = 0, s = 0, d = 0, f = 0, z = 0;
         for (const Group &gr : groups) { p += gr.t_plan; u += gr.t_upload; s += gr.t_scan; d += gr.t_down; f += gr.t_fetch; z += gr.t_final; }
-        const char *name = mode == Mode::Matches ? "ts_scan_segments" : mode == Mode::Blocks ? "ts_scan_segments_blocks" : "ts_filter_reads";
+        const char *name = mode == Mode::Matches ? "ts_scan_segments" : mode == Mode::Blocks ? "ts_scan_segments_blocks"
+                         : mode == Mode::Ends ? "ts_terminal_ends" : "ts_filter_reads";
         fprintf(stderr, "%s: %zu items in %zu groups, wall %.1f ms; stage sums (concurrent): plan %.1f ms, stage+upload %.1f ms, "
                         "scan (incl. waiting for the upload) %.1f ms, download + host post-processing %.1f ms (device work + D2H %.1f ms, host expansion %.1f ms)\n",
                 name, items.size(), groups.size(), ms_between(t_begin, Clock::now()), p, u, s, d, f, z);
@@ -849,7 +905,7 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
 struct SubmitReq {
     int mode; bool tips;
     const std::vector<Item> *items;
-    ts_segment_out *out; ts_segment_counts *counts; uint8_t *pass;
+    ts_segment_out *out; ts_segment_counts *counts; uint8_t *pass; uint32_t *ends;
     int rc = TS_OK; bool done = false;
     std::string error;
 };
@@ -864,7 +920,7 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
     const bool tips = group[0]->tips;
     if (group.size() == 1) {
         SubmitReq &r = *group[0];
-        r.rc = run_pipeline(ctx, mode, tips, *r.items, r.out, r.counts, r.pass);
+        r.rc = run_pipeline(ctx, mode, tips, *r.items, r.out, r.counts, r.pass, r.ends);
         if (r.rc != TS_OK) r.error = ctx->error;
         return;
     }
@@ -876,8 +932,9 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
     std::vector<ts_segment_out> out(mode == Mode::ReadPass ? 0 : total);
     std::vector<ts_segment_counts> counts(mode == Mode::Blocks ? total : 0);
     std::vector<uint8_t> pass(mode == Mode::ReadPass ? total : 0);
+    std::vector<uint32_t> ends(mode == Mode::Ends ? 2 * total : 0);
     const int rc = run_pipeline(ctx, mode, tips, items, out.empty() ? nullptr : out.data(), counts.empty() ? nullptr : counts.data(),
-                                pass.empty() ? nullptr : pass.data());
+                                pass.empty() ? nullptr : pass.data(), ends.empty() ? nullptr : ends.data());
     if (rc == TS_OK) {
         size_t at = 0;
         for (SubmitReq *r : group) {
@@ -885,6 +942,7 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
             if (r->out) std::memcpy(r->out, out.data() + at, n * sizeof(ts_segment_out));
             if (r->counts) std::memcpy(r->counts, counts.data() + at, n * sizeof(ts_segment_counts));
             if (r->pass) std::memcpy(r->pass, pass.data() + at, n);
+            if (r->ends) std::memcpy(r->ends, ends.data() + 2 * at, n * 8);
             r->rc = TS_OK;
             at += n;
         }
@@ -892,7 +950,7 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
     }
     if (!out.empty()) ts_free_segments(out.data(), out.size());
     for (SubmitReq *r : group) {
-        r->rc = run_pipeline(ctx, mode, tips, *r->items, r->out, r->counts, r->pass);
+        r->rc = run_pipeline(ctx, mode, tips, *r->items, r->out, r->counts, r->pass, r->ends);
         if (r->rc != TS_OK) r->error = ctx->error;
     }
 }
@@ -900,9 +958,9 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
 // run_pipeline for a caller that does not hold the context's call lock: alone, it runs at once; beside others, it is merged
 // with them.  (A merged run is capped at ~8 GB of input: what is left waits for the next one.)
 int submit_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, ts_segment_out *out,
-                    ts_segment_counts *counts, uint8_t *pass) {
+                    ts_segment_counts *counts, uint8_t *pass, uint32_t *ends = nullptr) {
     if (items.empty()) return TS_OK;
-    SubmitReq req{(int)mode, tips, &items, out, counts, pass, TS_OK, false, std::string()};
+    SubmitReq req{(int)mode, tips, &items, out, counts, pass, ends, TS_OK, false, std::string()};
     std::unique_lock<std::mutex> lk(ctx->sq_mtx);
     ctx->sq.push_back(&req);
     while (!req.done) {
@@ -1606,6 +1664,31 @@ int ts_filter_reads(ts_ctx *ctx, const char *const *seqs, const uint64_t *lens, 
     // tiled path: whole-read tips scan, then the terminal-block predicate on the device; only one
     // byte per read comes back
     return submit_pipeline(ctx, Mode::ReadPass, true, items, nullptr, nullptr, pass);
+}
+
+// =========================================================================== GFA annotation: per-end terminal lengths
+// ends[2i] / ends[2i+1]: the longest terminal block at the start / end side of segs[i] (walkSegment's rule,
+// src/input.cpp:835-881).  Tiled sets: a tips-only batch, the scan, the predicate's walks in their ENDS form
+// (predicate.hip) and 8 bytes per segment back.  Other sets: the general kernels' blocks-only form, reduced here.
+int ts_terminal_ends(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, uint32_t *ends) {
+    if (!ctx || (n_segs && (!segs || !ends))) return TS_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n_segs; ++i) {
+        ends[2 * i] = ends[2 * i + 1] = 0u;
+        if (!segs[i].tips_only) return ctx->fail(TS_ERR_INVALID_ARG, "ts_terminal_ends: every segment must be tips_only");
+        if (segs[i].len && !segs[i].seq) return ctx->fail(TS_ERR_INVALID_ARG, "null sequence pointer");
+        if (segs[i].input_format > TS_INPUT_PACKED2) return ctx->fail(TS_ERR_INVALID_ARG, "unknown input_format");
+    }
+    if (n_segs == 0) return TS_OK;
+    std::vector<size_t> all(n_segs);
+    for (size_t i = 0; i < n_segs; ++i) all[i] = i;
+    if (ctx->fast_ok) return submit_pipeline(ctx, Mode::Ends, true, items_of(segs, all), nullptr, nullptr, nullptr, ends);
+    std::vector<ts_segment_out> out(n_segs);
+    for (size_t i = 0; i < n_segs; ++i) std::memset(&out[i], 0, sizeof out[i]);
+    const int rc = generic_locked(ctx, segs, all, true, out.data(), false, true, nullptr);
+    if (rc == TS_OK)
+        for (size_t i = 0; i < n_segs; ++i) reduce_terminal_ends(out[i], segs[i].len, segs[i].abs_pos, ends + 2 * i);
+    ts_free_segments(out.data(), n_segs);
+    return rc;
 }
 
 // ReadTelomereFilter::matches over a device-resident tips-only batch (reads already in HBM, scanned on `stream`):

@@ -26,7 +26,29 @@ struct PredState {
     u64 cstart, clen;                       // running merged block
 };
 
-__device__ __forceinline__ void pred_close_sub(PredState &st, const TsPredParams &Q, bool from_start) {
+// ENDS (ts_terminal_ends, the GFA annotation): the same walks, but a merged block of >= -l does not end them — its length goes
+// into the maximum of the side it lies on, and the result is 8 bytes per segment: the longest terminal block at the start and
+// at the end side.  The state of that lives apart (SideMax) and is only touched under `if constexpr (ENDS)`, and `pass` is
+// never raised (so the walks' "stop at the first block" conditions never fire): with ENDS false every walk below compiles to
+// what it was before.
+struct SideMax { u64 n; uint32_t s, e; };   // segment length; longest block so far at the start / end side
+
+// A merged block of >= -l is complete (finalizeExtended, src/teloscope.cpp:129-145; the caller checked the length).
+// Predicate: pass.  ENDS: its length into its side's maximum — walkSegment's rule (src/input.cpp:849-853) on
+// segment-relative positions: the start side when distToStart <= distToEnd.
+template <bool ENDS, typename P>
+__device__ __forceinline__ void pred_fold(bool &pass, SideMax &sm, P cstart, P clen) {
+    if constexpr (!ENDS) {
+        pass = true;
+    } else {
+        const uint32_t len = (uint32_t)clen;
+        if ((u64)cstart <= sm.n - ((u64)cstart + (u64)clen)) sm.s = sm.s > len ? sm.s : len;
+        else sm.e = sm.e > len ? sm.e : len;
+    }
+}
+
+template <bool ENDS = false>
+__device__ __forceinline__ void pred_close_sub(PredState &st, const TsPredParams &Q, bool from_start, SideMax &sm) {
     const float need = Q.min_block_density * (float)(st.bend - st.bstart);
     if (st.counts >= Q.min_block_counts && st.canon > 0u && (float)st.can_cov >= need) {
         const u64 sstart = st.bstart, slen = (uint32_t)(st.bend - st.bstart);
@@ -38,7 +60,7 @@ __device__ __forceinline__ void pred_close_sub(PredState &st, const TsPredParams
                 if (from_start) st.clen = (uint32_t)((sstart + slen) - st.cstart);
                 else { st.clen = (uint32_t)((st.cstart + st.clen) - sstart); st.cstart = sstart; }
             } else {
-                if (st.clen >= Q.min_block_len) st.pass = true;
+                if (st.clen >= Q.min_block_len) pred_fold<ENDS>(st.pass, sm, st.cstart, st.clen);
                 st.cstart = sstart; st.clen = slen;
             }
         }
@@ -47,8 +69,9 @@ __device__ __forceinline__ void pred_close_sub(PredState &st, const TsPredParams
 }
 
 // returns false when the walk must stop (a match outside the terminal zone while no chain is open)
+template <bool ENDS = false>
 __device__ __forceinline__ bool pred_feed(PredState &st, const TsPredParams &Q, bool from_start, u64 pos,
-                                          bool canonical, u64 seg_len) {
+                                          bool canonical, u64 seg_len, SideMax &sm) {
     if (st.in_block) {
         const u64 gap = from_start ? pos - st.prev : st.prev - pos;
         if (gap <= Q.max_match_dist) {
@@ -57,7 +80,7 @@ __device__ __forceinline__ bool pred_feed(PredState &st, const TsPredParams &Q, 
             st.prev = pos;
             return true;
         }
-        pred_close_sub(st, Q, from_start);
+        pred_close_sub<ENDS>(st, Q, from_start, sm);
     }
     const bool in_zone = seg_len <= Q.terminal_limit ? true
                        : (from_start ? pos < Q.terminal_limit : pos >= seg_len - Q.terminal_limit);
@@ -75,10 +98,11 @@ __device__ __forceinline__ bool pred_feed(PredState &st, const TsPredParams &Q, 
 // masked — two blocks at a time with the next two already requested (round 2; dword loads before: 4x the instructions).
 // A block that would reach outside [matches, matches + nrec_limit) is read record by record.
 constexpr uint32_t kPredBlocks = 2;      // 16-byte blocks a thread requests at a time (and as many again in flight; four measured the same)
-template <bool FROM_START, typename REC = uint32_t>
+// (ENDS: the blocks into sm, which the caller set up with the segment's length; pass stays down, so the walk runs to its zone's end)
+template <bool FROM_START, typename REC = uint32_t, bool ENDS = false>
 __device__ __forceinline__ bool pred_walk(const TsTile *tiles, const u64 *tile_off, const uint32_t *tile_stats,
                                           const uint32_t *matches, u64 nrec_limit, uint32_t t0, uint32_t t1, u64 base, u64 n,
-                                          const TsPredParams &Q) {
+                                          const TsPredParams &Q, SideMax &sm) {
     constexpr uint32_t RPB = 16u / (uint32_t)sizeof(REC);     // records per 16-byte block (REC: see pred_walk_read)
     PredState st = {};
     bool go = true;
@@ -116,7 +140,7 @@ __device__ __forceinline__ bool pred_walk(const TsTile *tiles, const u64 *tile_o
                 const uint32_t ej = sizeof(REC) == 4 ? w[j & 3u] : (w[j >> 1] >> (16u * (j & 1u))) & 0xFFFFu;
                 const uint32_t i = RPB * q + j - m;
                 if (i < cnt && go && ((ej & 2u) != 0u) == FROM_START)
-                    go = pred_feed(st, Q, FROM_START, rel0 + (ej >> 2), ej & 1u, n);
+                    go = pred_feed<ENDS>(st, Q, FROM_START, rel0 + (ej >> 2), ej & 1u, n, sm);
             }
         };
         uint4 v[kPredBlocks], w[kPredBlocks];
@@ -131,8 +155,8 @@ __device__ __forceinline__ bool pred_walk(const TsTile *tiles, const u64 *tile_o
             for (uint32_t j = 0; j < kPredBlocks; ++j) v[j] = w[j];
         }
     }
-    if (st.in_block) pred_close_sub(st, Q, FROM_START);
-    if (st.have_cur && st.clen >= Q.min_block_len) st.pass = true;
+    if (st.in_block) pred_close_sub<ENDS>(st, Q, FROM_START, sm);
+    if (st.have_cur && st.clen >= Q.min_block_len) pred_fold<ENDS>(st.pass, sm, st.cstart, st.clen);
     return st.pass;
 }
 
@@ -149,10 +173,11 @@ struct ReadChain { uint32_t first, last, counts, canon; };            // the ope
 struct ReadBlock { uint32_t cstart, clen; bool have_cur, pass; };      // the running merged block of one list
 
 // a kept chain [sstart, sstart + slen) into its list's running block: pred_close_sub's merge, same u32 expressions
-__device__ __forceinline__ void read_block_merge(ReadBlock &b, const TsPredParams &Q, uint32_t sstart, uint32_t slen) {
+template <bool ENDS = false>
+__device__ __forceinline__ void read_block_merge(ReadBlock &b, const TsPredParams &Q, uint32_t sstart, uint32_t slen, SideMax &sm) {
     if (!b.have_cur) { b.cstart = sstart; b.clen = slen; b.have_cur = true; }
     else if (sstart - (b.cstart + b.clen) <= Q.max_block_dist) b.clen = sstart + slen - b.cstart;   // (wraps to "far" when chains overlap)
-    else { if (b.clen >= Q.min_block_len) b.pass = true; b.cstart = sstart; b.clen = slen; }
+    else { if (b.clen >= Q.min_block_len) pred_fold<ENDS>(b.pass, sm, b.cstart, b.clen); b.cstart = sstart; b.clen = slen; }
 }
 
 // is the chain kept when it closes?  enough matches, a canonical one, the density (pred_close_sub's float expression)
@@ -166,8 +191,9 @@ __device__ __forceinline__ bool read_chain_kept(const ReadChain &c, const TsPred
 // predicate of 500 k reads as many wave-instructions as two thirds of a 3 Gb scan).  The record's list is selected by
 // v_cndmask (four chain fields in, four out per list); only a chain that is KEPT when it closes takes a branch, into
 // the merge: one record in a few thousand outside telomeres.
+template <bool ENDS = false>
 __device__ __forceinline__ void read_feed(ReadChain &cf, ReadChain &cr, ReadBlock &bf, ReadBlock &br, const TsPredParams &Q,
-                                          bool sel, bool fwd, uint32_t pos, uint32_t canonical) {
+                                          bool sel, bool fwd, uint32_t pos, uint32_t canonical, SideMax &sm) {
     ReadChain c;
     c.first = fwd ? cf.first : cr.first; c.last = fwd ? cf.last : cr.last;
     c.counts = fwd ? cf.counts : cr.counts; c.canon = fwd ? cf.canon : cr.canon;
@@ -176,7 +202,7 @@ __device__ __forceinline__ void read_feed(ReadChain &cf, ReadChain &cr, ReadBloc
     const bool kept = sel & open & !ext & read_chain_kept(c, Q);
     if (kept) {
         const uint32_t slen = c.last + Q.k - c.first;
-        if (fwd) read_block_merge(bf, Q, c.first, slen); else read_block_merge(br, Q, c.first, slen);
+        if (fwd) read_block_merge<ENDS>(bf, Q, c.first, slen, sm); else read_block_merge<ENDS>(br, Q, c.first, slen, sm);
     }
     c.first = ext ? c.first : pos;
     c.counts = ext ? c.counts + 1u : 1u;
@@ -186,13 +212,16 @@ __device__ __forceinline__ void read_feed(ReadChain &cf, ReadChain &cr, ReadBloc
     cr.first = wr ? c.first : cr.first; cr.last = wr ? pos : cr.last; cr.counts = wr ? c.counts : cr.counts; cr.canon = wr ? c.canon : cr.canon;
 }
 
-template <uint32_t NB, bool PADDED, typename REC = uint32_t>   // NB: 16-byte blocks a thread requests at a time (and as many again in flight);
+template <uint32_t NB, bool PADDED, typename REC = uint32_t, bool ENDS = false>
+                                                // NB: 16-byte blocks a thread requests at a time (and as many again in flight);
                                                 // PADDED: the records lie in a 16-byte aligned buffer with 16 bytes of slack;
                                                 // REC: uint16_t for a read batch whose scan left 16-bit records (TsScanParams.rec16):
-                                                // a block then holds eight records — half the load instructions, half the bytes
+                                                // a block then holds eight records — half the load instructions, half the bytes;
+                                                // ENDS: both lists' blocks into sm (sides by position: which list a block came from
+                                                // does not matter), no early end
 __device__ __forceinline__ bool pred_walk_read(const TsTile *tiles, const u64 *tile_off, const uint32_t *tile_stats,
                                                const uint32_t *matches, u64 nrec_limit, uint32_t t0, uint32_t t1, u64 base,
-                                               const TsPredParams &Q, bool walk_fwd, bool walk_rev) {
+                                               const TsPredParams &Q, bool walk_fwd, bool walk_rev, SideMax &sm) {
     constexpr uint32_t RPB = 16u / (uint32_t)sizeof(REC);     // records per 16-byte block
     ReadChain cf = {}, cr = {};                 // (a list of fewer than two matches is not walked: walk_fwd / walk_rev)
     ReadBlock bf = {}, br = {};
@@ -226,7 +255,7 @@ __device__ __forceinline__ bool pred_walk_read(const TsTile *tiles, const u64 *t
                 const uint32_t i = RPB * bi + j - m;         // wraps below the first record, runs past the last one
                 const bool valid = i < cnt, fwd = (ej & 2u) != 0u;
                 const uint32_t pos = rel0 + (ej >> 2), can = ej & 1u;
-                read_feed(cf, cr, bf, br, Q, valid & (fwd ? walk_fwd : walk_rev), fwd, pos, can);
+                read_feed<ENDS>(cf, cr, bf, br, Q, valid & (fwd ? walk_fwd : walk_rev), fwd, pos, can, sm);
             }
         };
         uint4 v[NB], w[NB];
@@ -241,10 +270,10 @@ __device__ __forceinline__ bool pred_walk_read(const TsTile *tiles, const u64 *t
             for (uint32_t j = 0; j < NB; ++j) v[j] = w[j];
         }
     }
-    if (cf.counts != 0u && read_chain_kept(cf, Q)) read_block_merge(bf, Q, cf.first, cf.last + Q.k - cf.first);
-    if (bf.have_cur && bf.clen >= Q.min_block_len) bf.pass = true;
-    if (cr.counts != 0u && read_chain_kept(cr, Q)) read_block_merge(br, Q, cr.first, cr.last + Q.k - cr.first);
-    if (br.have_cur && br.clen >= Q.min_block_len) br.pass = true;
+    if (cf.counts != 0u && read_chain_kept(cf, Q)) read_block_merge<ENDS>(bf, Q, cf.first, cf.last + Q.k - cf.first, sm);
+    if (bf.have_cur && bf.clen >= Q.min_block_len) pred_fold<ENDS>(bf.pass, sm, bf.cstart, bf.clen);
+    if (cr.counts != 0u && read_chain_kept(cr, Q)) read_block_merge<ENDS>(br, Q, cr.first, cr.last + Q.k - cr.first, sm);
+    if (br.have_cur && br.clen >= Q.min_block_len) pred_fold<ENDS>(br.pass, sm, br.cstart, br.clen);
     return bf.pass || br.pass;
 }
 
@@ -272,10 +301,10 @@ __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {
 // predecessor, a ballot marks the records that start a new sub-block (gap > -k), and the scalar state machine
 // then steps once per SUB-BLOCK (counts by popcount of ballots) instead of once per record — a telomeric read
 // is one sub-block of thousands of matches.
-template <bool FWD_LIST, typename REC = uint32_t>
+template <bool FWD_LIST, typename REC = uint32_t, bool ENDS = false>
 __device__ __forceinline__ bool pred_scan_wave(const TsTile *tiles, const u64 *tile_off, const uint32_t *tile_stats,
                                const uint32_t *matches, uint32_t t0, uint32_t t1, u64 base,
-                               const TsPredParams &Q, uint32_t lane) {
+                               const TsPredParams &Q, uint32_t lane, SideMax &sm) {
     PredState st = {};
     bool have_prev = false;
     u64 prev = 0;                                            // last selected position so far
@@ -302,7 +331,7 @@ __device__ __forceinline__ bool pred_scan_wave(const TsTile *tiles, const u64 *t
             while (rem) {                                    // one step per run of chained records
                 const uint32_t l0 = (uint32_t)__builtin_ctzll(rem);
                 if ((heads >> l0) & 1ull) {
-                    if (st.in_block) { st.can_cov = st.canon * Q.k; pred_close_sub(st, Q, true); }
+                    if (st.in_block) { st.can_cov = st.canon * Q.k; pred_close_sub<ENDS>(st, Q, true, sm); }
                     st.bstart = rel0 + (uint32_t)__builtin_amdgcn_readlane((int)p32, (int)l0);
                     st.counts = 0; st.canon = 0; st.in_block = true;
                 }
@@ -318,8 +347,8 @@ __device__ __forceinline__ bool pred_scan_wave(const TsTile *tiles, const u64 *t
             }
         }
     }
-    if (st.in_block) { st.can_cov = st.canon * Q.k; pred_close_sub(st, Q, true); }
-    if (st.have_cur && st.clen >= Q.min_block_len) st.pass = true;
+    if (st.in_block) { st.can_cov = st.canon * Q.k; pred_close_sub<ENDS>(st, Q, true, sm); }
+    if (st.have_cur && st.clen >= Q.min_block_len) pred_fold<ENDS>(st.pass, sm, st.cstart, st.clen);
     return st.pass;
 }
 
@@ -344,12 +373,18 @@ __device__ __forceinline__ bool pred_scan_wave(const TsTile *tiles, const u64 *t
 #ifndef TS_PRED_NB
 #define TS_PRED_NB 4u
 #endif
-template <bool READS, typename REC = uint32_t>
+// ENDS (ts_terminal_ends): out is one uint2 per segment, {longest block at the start side, at the end side}; the walks do not
+// stop at the first block, and segments longer than the terminal limit — the usual case in a graph — take pred_walk<>.
+// Every segment is written by exactly one thread: by its lane here, or by the wave of ts_terminal_ends_long when listed.
+template <bool ENDS> struct PredOut { typedef unsigned char T; };
+template <> struct PredOut<true> { typedef uint2 T; };
+
+template <bool READS, typename REC = uint32_t, bool ENDS = false>
 __global__ __launch_bounds__(64, TS_PRED_WAVES)
 void ts_terminal_predicate(const TsTile *tiles, const u64 *tile_off, const uint32_t *tile_stats,
                            const uint32_t *matches, const u64 nrec_limit, const uint32_t *seg_first_tile,
                            const u64 *seg_in_off, const u64 *seg_len, uint32_t nseg,
-                           const TsPredParams Q, unsigned char *pass, uint32_t *long_list, uint32_t *long_count,
+                           const TsPredParams Q, typename PredOut<ENDS>::T *pass, uint32_t *long_list, uint32_t *long_count,
                            const uint32_t *overflow) {
     // a wave's record region overflowed in the scan (ts_pred_guard): the directory promises records that were never
     // stored — nothing is judged, the flag stays up for ts_batch_read_pass_status
@@ -373,16 +408,19 @@ void ts_terminal_predicate(const TsTile *tiles, const u64 *tile_off, const uint3
         return;
     }
     bool ok = false;
+    SideMax sm = {n, 0u, 0u};
     if (READS || n <= Q.terminal_limit) {
         if (nfwd >= 2 || total - nfwd >= 2)
-            ok = pred_walk_read<READS ? TS_PRED_NB : 2u, READS, REC>(tiles, tile_off, tile_stats, matches, nrec_limit, t0, t1, base, Q, nfwd >= 2, total - nfwd >= 2);
+            ok = pred_walk_read<READS ? TS_PRED_NB : 2u, READS, REC, ENDS>(tiles, tile_off, tile_stats, matches, nrec_limit, t0, t1, base, Q,
+                                                                          nfwd >= 2, total - nfwd >= 2, sm);
     } else if (!READS) {
         if (nfwd >= 2)                                      // forward list, from the segment start
-            ok = pred_walk<true, REC>(tiles, tile_off, tile_stats, matches, nrec_limit, t0, t1, base, n, Q);
+            ok = pred_walk<true, REC, ENDS>(tiles, tile_off, tile_stats, matches, nrec_limit, t0, t1, base, n, Q, sm);
         if (!ok && total - nfwd >= 2)                       // reverse list, from the segment end
-            ok = pred_walk<false, REC>(tiles, tile_off, tile_stats, matches, nrec_limit, t0, t1, base, n, Q);
+            ok = pred_walk<false, REC, ENDS>(tiles, tile_off, tile_stats, matches, nrec_limit, t0, t1, base, n, Q, sm);
     }
-    pass[si] = ok ? 1 : 0;
+    if constexpr (ENDS) pass[si] = make_uint2(sm.s, sm.e);
+    else pass[si] = ok ? 1 : 0;
 }
 
 
@@ -424,6 +462,7 @@ void ts_read_predicate_canon(const TsTile *tiles, const u64 *tile_off, const uin
     }
     const bool walk_list[2] = {total - nfwd >= 2, nfwd >= 2};           // [reverse, forward]: a list of fewer than two matches is not walked
     ReadBlock blk[2] = {};
+    SideMax unused = {};
     ReadCursor covered[2] = {{t0, 0u}, {t0, 0u}};                         // per list: the first record no evaluated chain has reached
     auto rec_at = [&](ReadCursor c) -> uint32_t { return matches[tile_off[c.t] + c.i]; };
     auto pos_of = [&](ReadCursor c, uint32_t r) -> uint32_t { return (uint32_t)(tiles[c.t].in_off - base) + (r >> 2); };
@@ -527,7 +566,7 @@ void ts_read_predicate_canon(const TsTile *tiles, const u64 *tile_off, const uin
             }
             covered[o] = e_after;
             if (read_chain_kept(ch, Q)) {
-                read_block_merge(blk[o], Q, ch.first, ch.last + Q.k - ch.first);
+                read_block_merge(blk[o], Q, ch.first, ch.last + Q.k - ch.first, unused);
                 ok = blk[o].pass;
             }
         }
@@ -551,11 +590,35 @@ void ts_terminal_predicate_long(const TsTile *tiles, const u64 *tile_off, const 
         u64 total = 0, nfwd = 0;
         for (uint32_t t = t0; t < t1; ++t) { total += tile_stats[4u * t]; nfwd += tile_stats[4u * t + 2u]; }
         bool ok = false;
+        SideMax sm = {};                                     // (not read: ENDS is false)
         if (nfwd >= 2)
-            ok = pred_scan_wave<true, REC>(tiles, tile_off, tile_stats, matches, t0, t1, base, Q, lane);
+            ok = pred_scan_wave<true, REC>(tiles, tile_off, tile_stats, matches, t0, t1, base, Q, lane, sm);
         if (!ok && total - nfwd >= 2)
-            ok = pred_scan_wave<false, REC>(tiles, tile_off, tile_stats, matches, t0, t1, base, Q, lane);
+            ok = pred_scan_wave<false, REC>(tiles, tile_off, tile_stats, matches, t0, t1, base, Q, lane, sm);
         if (lane == 0) pass[si] = ok ? 1 : 0;
+    }
+}
+
+// The same waves for ts_terminal_ends: both lists walked to their ends, the per-side maxima to ends[si] (the listed segment is
+// terminal zone as a whole; seg_len decides the sides).  Its own kernel rather than a shared body with the one above: sharing
+// it changed the predicate's register assignment, and the predicate is on the read filter's hot path.
+template <typename REC>
+__global__ __launch_bounds__(64)
+void ts_terminal_ends_long(const TsTile *tiles, const u64 *tile_off, const uint32_t *tile_stats,
+                           const uint32_t *matches, const uint32_t *seg_first_tile, const u64 *seg_in_off, const u64 *seg_len,
+                           const TsPredParams Q, uint2 *ends, const uint32_t *long_list, const uint32_t *long_count) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t count = *long_count;
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        const uint32_t si = long_list[i];                    // wave-uniform
+        const uint32_t t0 = seg_first_tile[si], t1 = seg_first_tile[si + 1];
+        const u64 base = seg_in_off[si];
+        u64 total = 0, nfwd = 0;
+        for (uint32_t t = t0; t < t1; ++t) { total += tile_stats[4u * t]; nfwd += tile_stats[4u * t + 2u]; }
+        SideMax sm = {seg_len[si], 0u, 0u};
+        if (nfwd >= 2) (void)pred_scan_wave<true, REC, true>(tiles, tile_off, tile_stats, matches, t0, t1, base, Q, lane, sm);
+        if (total - nfwd >= 2) (void)pred_scan_wave<false, REC, true>(tiles, tile_off, tile_stats, matches, t0, t1, base, Q, lane, sm);
+        if (lane == 0) ends[si] = make_uint2(sm.s, sm.e);
     }
 }
 
@@ -614,3 +677,40 @@ int ts_k_launch_predicate(const TsTile *tiles, const unsigned long long *tile_of
     return (int)hipGetLastError();
 }
 
+// The per-end maxima (ts_terminal_ends): the predicate's launches with ENDS set — ends[2 si] / ends[2 si + 1] are the longest
+// terminal block at the start / end side of segment si, 0 where there is none.  No canonical-index form: the pipeline's
+// scans leave no index (emit 1).
+int ts_k_launch_terminal_ends(const TsTile *tiles, const unsigned long long *tile_off, const uint32_t *tile_stats,
+                              const uint32_t *matches, unsigned long long nrec_limit, const uint32_t *seg_first_tile,
+                              const unsigned long long *seg_in_off, const unsigned long long *seg_len, uint32_t nseg,
+                              const TsPredParams *Q, uint32_t *ends, uint32_t *long_list, uint32_t *long_count, int all_terminal,
+                              const uint32_t *wave_fill, uint32_t region_cap, uint32_t nwaves, uint32_t *overflow, int rec16,
+                              void *stream) {
+    if (nseg == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(long_count, 0, 4, st);
+    if (e != hipSuccess) return (int)e;
+    uint2 *out = (uint2 *)ends;
+    hipLaunchKernelGGL(ts_pred_guard, dim3(8), dim3(256), 0, st, wave_fill, region_cap, nwaves, overflow, 0u);
+    const dim3 grid1((nseg + 63u) / 64u);
+    if (all_terminal && rec16)
+        hipLaunchKernelGGL((ts_terminal_predicate<true, uint16_t, true>), grid1, dim3(64), 0, st, tiles, tile_off, tile_stats, matches,
+                           (u64)nrec_limit, seg_first_tile, seg_in_off, seg_len, nseg, *Q, out, long_list, long_count, (const uint32_t *)overflow);
+    else if (rec16)
+        hipLaunchKernelGGL((ts_terminal_predicate<false, uint16_t, true>), grid1, dim3(64), 0, st, tiles, tile_off, tile_stats, matches,
+                           (u64)nrec_limit, seg_first_tile, seg_in_off, seg_len, nseg, *Q, out, long_list, long_count, (const uint32_t *)overflow);
+    else if (all_terminal)
+        hipLaunchKernelGGL((ts_terminal_predicate<true, uint32_t, true>), grid1, dim3(64), 0, st, tiles, tile_off, tile_stats, matches,
+                           (u64)nrec_limit, seg_first_tile, seg_in_off, seg_len, nseg, *Q, out, long_list, long_count, (const uint32_t *)overflow);
+    else
+        hipLaunchKernelGGL((ts_terminal_predicate<false, uint32_t, true>), grid1, dim3(64), 0, st, tiles, tile_off, tile_stats, matches,
+                           (u64)nrec_limit, seg_first_tile, seg_in_off, seg_len, nseg, *Q, out, long_list, long_count, (const uint32_t *)overflow);
+    const uint32_t grid = nseg < 8192u ? nseg : 8192u;
+    if (rec16)
+        hipLaunchKernelGGL(ts_terminal_ends_long<uint16_t>, dim3(grid), dim3(64), 0, st, tiles, tile_off, tile_stats, matches,
+                           seg_first_tile, seg_in_off, (const u64 *)seg_len, *Q, out, (const uint32_t *)long_list, (const uint32_t *)long_count);
+    else
+        hipLaunchKernelGGL(ts_terminal_ends_long<uint32_t>, dim3(grid), dim3(64), 0, st, tiles, tile_off, tile_stats, matches,
+                           seg_first_tile, seg_in_off, (const u64 *)seg_len, *Q, out, (const uint32_t *)long_list, (const uint32_t *)long_count);
+    return (int)hipGetLastError();
+}

@@ -348,6 +348,14 @@ int  ts_k_launch_predicate(const TsTile *tiles, const unsigned long long *tile_o
                            //  long_list: nseg entries of scratch + long_count: one counter, for the reads a whole wave walks;
                            //  all_terminal: no segment is longer than the terminal limit — every read batch — the lean kernel;
                            //  wave_fill / region_cap / nwaves -> *overflow: raised, and nothing judged, when the scan overflowed a wave's region)
+int  ts_k_launch_terminal_ends(const TsTile *tiles, const unsigned long long *tile_off, const uint32_t *tile_stats,
+                               const uint32_t *matches, unsigned long long nrec_limit, const uint32_t *seg_first_tile,
+                               const unsigned long long *seg_in_off, const unsigned long long *seg_len, uint32_t nseg,
+                               const TsPredParams *Q, uint32_t *ends, uint32_t *long_list, uint32_t *long_count, int all_terminal,
+                               const uint32_t *wave_fill, uint32_t region_cap, uint32_t nwaves, uint32_t *overflow, int rec16,
+                               void *stream);
+                           // the predicate's walks reduced to the longest terminal block per side: ends[2 i] start side, ends[2 i + 1]
+                           // end side of segment i (predicate.hip, ENDS); arguments as above
 // blockcall.hip: terminal walks per segment of `segs` (nseg entries; bounds: 2 x u64 per segment), then the interstitial
 // search over the batch's ntiles (range-local) tiles; seg_base = plan index of segs[0]'s segment; seg_out (nullable):
 // what a shard reports per segment

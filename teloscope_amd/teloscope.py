@@ -245,6 +245,27 @@ class Teloscope:
             return res, [(int(c.n_windows), int(c.n_matches), int(c.n_canonical), int(c.n_forward)) for c in cnt[:n]]
         return res
 
+    def terminalEnds(self, sequences, absPos=0):
+        """The GFA annotation's per-segment numbers (ts_terminal_ends): for every sequence, the longest terminal block of a
+        tips-only scanSegment at its start side and at its end side (walkSegment's distToStart <= distToEnd rule), 0 where
+        there is none.  absPos: one position for all, or one per sequence.  Returns an (n, 2) uint32 array."""
+        n = len(sequences)
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+        abs_pos = list(absPos) if hasattr(absPos, "__len__") else [absPos] * n
+        if len(abs_pos) != n:
+            raise ValueError("absPos: one position, or one per sequence")
+        arr = (K.SegmentIn * max(1, n))()
+        for i, s in enumerate(seqs):
+            arr[i].seq = s
+            arr[i].len = len(s)
+            arr[i].abs_pos = int(abs_pos[i])
+            arr[i].tips_only = 1
+        ends = np.zeros((n, 2), dtype=np.uint32)
+        rc = K.lib().ts_terminal_ends(self._ctx.ptr, arr, n, ends.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if rc != K.TS_OK:
+            raise K.TeloscanError(rc, self._ctx.error())
+        return ends
+
     def scanSegment(self, sequence, absPos=0, tipsOnly=False):
         """SegmentData Teloscope::scanSegment(std::string&, uint64_t absPos, bool tipsOnly)."""
         return self.scanSegments([(sequence, absPos, tipsOnly)])[0]
