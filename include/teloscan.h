@@ -234,8 +234,7 @@ int     ts_box_probe(ts_ctx *ctx, double *valu_wave_instr_per_ns, double *copy_b
  * set the library scans (until ABI 3 the general kernels wanted the bases joined). */
 int     ts_takes_text_input(const ts_ctx *ctx, int tips_only);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
- * TS_PACKED_MIN_BYTES, TS_STAGE_THREADS, TS_GEN_HOST_BLOCKS, TS_GEN_PREFETCH, TS_GEN_LIST, TS_GEN_ABL) ONCE, when the context
- * is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
+ * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
  * No counterpart in the reference (its options are fixed by main, /root/reference/src/main.cpp:149-184). */
 int     ts_refresh_env(ts_ctx *ctx);
 /* HIP puts the streams of a process on a few hardware queues (four unless GPU_MAX_HW_QUEUES says otherwise) and does not say which;

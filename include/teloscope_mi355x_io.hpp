@@ -596,13 +596,11 @@ inline bool splitFastqRecords(const char *data, size_t size, std::vector<FastqRe
 namespace detail {
 // The library's first call in a process pays for its streams, its kernels' code, the device pool and the pinned staging (about
 // 75 ms, whatever the size of the call).  The subset tools make it here, on one dummy read and a thread of its own, while their
-// first block of input is still being read and parsed; joined before the first real batch.  TS_MIRROR_WARMUP=0 leaves it out.
+// first block of input is still being read and parsed; joined before the first real batch.
 class FilterWarmUp {
     std::thread th;
 public:
     explicit FilterWarmUp(ReadTelomereFilter &filter) {
-        const char *wu = std::getenv("TS_MIRROR_WARMUP");
-        if (wu && wu[0] == '0') return;
         th = std::thread([&filter] {
             try {
                 const std::string seq(4096, 'A');
@@ -1910,8 +1908,8 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
             detail::FastaGroup g;
             // The library's first call in a process pays for its streams, its kernels' code, the device pool and the pinned staging
             // (81-115 ms against 12-15 ms for a later group of 256 MB): made here, on a dummy record, while the reader is still
-            // parsing its first group.  TS_MIRROR_WARMUP=0 leaves it out (A/B).
-            if (const char *wu = std::getenv("TS_MIRROR_WARMUP"); !(wu && wu[0] == '0')) {
+            // parsing its first group.
+            {
                 const auto tw = Clock::now();
                 const std::string hdr = "warm-up", seq(size_t(1) << 20, 'A');
                 std::vector<RecordView> one{RecordView{&hdr, seq.data(), seq.size(), nullptr, 0, nullptr}};

@@ -1,16 +1,14 @@
 #!/bin/bash
-# pcie_inclusive legs of bench.py with the packed upload on and off, staging thread counts
+# pcie_inclusive legs of bench.py with the packed upload on and off
 set -e
 make -s -C teloscope_amd/csrc && make -s -C oracle
 mkdir -p gpurun_out
 OUT=gpurun_out/packed_${1:-a}.txt
 ERR=${OUT%.txt}_err.txt
 : > $OUT
-IFS=";" read -ra LIST <<< "${CFGS:-0 8;1 8;1 12;1 16}"
-for cfg in "${LIST[@]}"; do
-  IFS=" " read -r a b g <<< "$cfg"; set -- $a $b; export TS_GROUP_MB=${g:-256}; echo "TS_GROUP_MB=$TS_GROUP_MB" >> $OUT
-  echo "TS_PACKED_UPLOAD=$1 TS_STAGE_THREADS=$2" >> $OUT
-  TS_TIMING=1 TS_PACKED_UPLOAD=$1 TS_STAGE_THREADS=$2 python3 bench.py --full --no-cpu-baseline --no-reads --steps 5 --warmup 2 2> "$ERR" | python3 -c "
+for p in ${PACKED:-0 1}; do
+  echo "TS_PACKED_UPLOAD=$p" >> $OUT
+  TS_TIMING=1 TS_PACKED_UPLOAD=$p python3 bench.py --full --no-cpu-baseline --no-reads --steps 5 --warmup 2 2> "$ERR" | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -4,6 +4,6 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2 3; do
   for lib in old new; do
     if [ $lib = old ]; then export TELOSCAN_LIB=$PWD/teloscope_amd/libteloscan_old.so; else unset TELOSCAN_LIB; fi
-    echo -n "$lib: "; timeout -k 10 200 python profiles/pack_abl_time.py 60 2>/dev/null | tail -1 | cut -c1-300
+    echo -n "$lib: "; timeout -k 10 200 python profiles/shard_step_time.py 60 2>/dev/null | tail -1 | cut -c1-300
   done
 done

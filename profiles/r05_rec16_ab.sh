@@ -11,6 +11,6 @@ for i in 1 2 3; do
   LABEL=rec32 TS_REC32=1 python3 profiles/emit_time.py 2>/dev/null
 done
 for i in 1 2; do
-  LABEL=rec16 STREAMS=probe EV=lib TIME_EVERY=0 python3 profiles/pack_abl_time.py 60 2>/dev/null
-  LABEL=rec32 TS_REC32=1 STREAMS=probe EV=lib TIME_EVERY=0 python3 profiles/pack_abl_time.py 60 2>/dev/null
+  LABEL=rec16 STREAMS=probe EV=lib TIME_EVERY=0 python3 profiles/shard_step_time.py 60 2>/dev/null
+  LABEL=rec32 TS_REC32=1 STREAMS=probe EV=lib TIME_EVERY=0 python3 profiles/shard_step_time.py 60 2>/dev/null
 done

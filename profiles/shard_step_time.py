@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The sharded step of bench.py's scan_plus_block_calling (emitting scan + pack beside the next scan, four slots) with the pack
-left out (PACK=0) or with a library variant whose pack skips kernels (-DTS_PACK_ABL, TELOSCAN_LIB): what each of the pack's kernels
-costs the scan it runs beside.  No result is checked here (the variants' results are wrong).  python3 profiles/pack_abl_time.py [steps]"""
+"""The sharded step of bench.py's scan_plus_block_calling (emitting scan + pack beside the next scan, four slots), with the pack
+and without it (PACK=0), or for a library variant (TELOSCAN_LIB): what the pack costs the scan it runs beside.  No result is
+checked here.  python3 profiles/shard_step_time.py [steps]"""
 import ctypes as C
 import os
 import sys

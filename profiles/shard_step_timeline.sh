@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel timeline of the sharded step (profiles/pack_abl_time.py: emitting scan + pack beside the next scan, four slots) under
+# kernel timeline of the sharded step (profiles/shard_step_time.py: emitting scan + pack beside the next scan, four slots) under
 # rocprofv3 --kernel-trace: start, duration, hardware queue and stream of every kernel of three steps, for each of the script's passes
 # usage: bash profiles/shard_step_timeline.sh <tag> [ENV=val ...]  -> gpurun_out/shardtl_<tag>.txt
 TAG=$1; shift
@@ -9,7 +9,7 @@ mkdir -p $OUT
 for e in "$@"; do export "$e"; done
 export PACK=${PACK:-1}
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $REPO/profiles/pack_abl_time.py 24 > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $REPO/profiles/shard_step_time.py 24 > $OUT/trace.log 2>&1
 python3 - $OUT > $REPO/gpurun_out/shardtl_$TAG.txt <<'PY'
 import csv, glob, os, re, sys
 root = sys.argv[1]

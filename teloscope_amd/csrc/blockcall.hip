@@ -401,9 +401,6 @@ __device__ __forceinline__ bool view_has_two(const TsBlockCallParams &Q, const S
     return acc >= 2u;
 }
 
-#ifndef TS_TERMINAL_PRIO
-#define TS_TERMINAL_PRIO 0
-#endif
 template <int MODE>
 __global__ __launch_bounds__(kSideWg)
 void ts_terminal_blocks(const TsBlockCallParams Q, const TsShardSegIn *segs, uint32_t nseg, u64 *bounds, TsShardSeg *seg_out) {
@@ -416,9 +413,6 @@ void ts_terminal_blocks(const TsBlockCallParams Q, const TsShardSegIn *segs, uin
     // (the per-segment counts of a shard's message are added up elsewhere: ts_chain_screen / ts_segment_sums)
     const uint32_t si = blockIdx.x >> 1;
     if (si >= nseg) return;
-#if TS_TERMINAL_PRIO
-    __builtin_amdgcn_s_setprio(TS_TERMINAL_PRIO);
-#endif
     const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x & 1u;
     const TsShardSegIn S = segs[si];
     const SegView V = seg_view(Q, S);
@@ -833,7 +827,7 @@ __device__ __forceinline__ void its_tile(const TsBlockCallParams &Q, const TsSha
     if (seg_out && ooc && lane == 0) atomicOr(&seg_out[si].flags, TS_SEG_F_CONTEXT);
 }
 
-// every tile of the range: results that carry no chain summaries (adopted from elsewhere, TS_EMIT=0), and the shard pack
+// every tile of the range: results that carry no chain summaries (adopted from elsewhere), and the shard pack
 // that takes the visible records from the match stream
 template <int MODE>
 __global__ __launch_bounds__(kSideWg)

@@ -87,18 +87,10 @@ void read_env_knobs(ts_ctx *c) {
     auto is = [](const char *name, char v) { const char *e = getenv(name); return e && e[0] == v; };
     ts_ctx::Knobs k;
     k.timing = getenv("TS_TIMING") != nullptr;
-    k.gen_host_blocks = is("TS_GEN_HOST_BLOCKS", '1');
-    k.gen_compact_always = is("TS_GEN_COMPACT", '1');     // (A/B: the dense stream made even where nothing reads it)
-    k.gen_prefetch = !is("TS_GEN_PREFETCH", '0');
     k.gen_list = !is("TS_GEN_LIST", '0');
-    if (const char *e = getenv("TS_GEN_ABL")) k.gen_abl = (uint32_t)atoi(e);
     k.packed_upload = !is("TS_PACKED_UPLOAD", '0');
     if (const char *e = getenv("TS_PACKED_MIN_BYTES")) k.packed_min_bytes = strtoull(e, nullptr, 10);
-    if (const char *e = getenv("TS_STAGE_THREADS")) { const int n = atoi(e); if (n > 0) k.stage_threads = (uint32_t)std::min(n, 64); }
-    if (const char *e = getenv("TS_SIDE_PRIORITY")) k.side_priority = atoi(e);
-    k.side_probe = !is("TS_SIDE_PROBE", '0');
     k.rec16 = !is("TS_REC32", '1');
-    if (const char *e = getenv("TS_SCAN_EVENTS")) k.scan_events = atoi(e);
     c->knobs = k;
 }
 
@@ -139,12 +131,8 @@ std::vector<int> device_node_cpus(int dev) {
     return cpus;
 }
 
-// groups of workgroups that share a ticket counter (TS_TICKET_GROUPS overrides, for measurements)
-uint32_t ticket_groups_wanted() {
-    uint32_t g = 32;
-    if (const char *e = getenv("TS_TICKET_GROUPS")) { const int n = atoi(e); if (n > 0) g = (uint32_t)n; }
-    return std::min<uint32_t>(g, TS_MAX_TICKET_GROUPS);
-}
+// groups of workgroups that share a ticket counter
+constexpr uint32_t kTicketGroups = std::min<uint32_t>(32, TS_MAX_TICKET_GROUPS);
 
 // Chooses waves per workgroup, chunks per tile and windows per tile so that the match table plus
 // one LDS slice per wave fit in 160 KB; false if even one wave cannot hold one window.
@@ -346,7 +334,6 @@ static int ensure_emit_buffers(ts_batch *b) {
     {
         HIP_TRY(c, c->pool.take(std::max<uint64_t>((uint64_t)b->vis_cap * b->total_waves, 4) * (b->kp.vis_wide ? 4 : 2) + 16, b->d_vis));
         HIP_TRY(c, c->pool.take((nt + 1) * 16, b->d_chain));
-        if (b->kp.emit == 2u) return TS_OK;                 // (a read batch: no terminal-zone words, every record is in the zone)
         HIP_TRY(c, c->pool.take((nt + 1) * 4, b->d_zone));
         // terminal zone of a segment (isTerminal, src/teloscope.cpp:451-459): rel <= t || rel >= N - t, the whole of a
         // segment no longer than t; per tile as two 16-bit thresholds on the tile-relative position
@@ -414,31 +401,16 @@ void size_launch(ts_batch *b) {
     const uint64_t want = b->match_cap_request ? b->match_cap_request : b->range_bases / 4 + 4096;
     uint64_t cap = ceil_div(want, b->total_waves);
     // Tiles are taken on demand by the waves (see ts_scan_tiles); dealt round-robin to small ranges, whose regions are
-    // sized for the worst case of the tiles a wave is dealt, and to the rescans after an overflow.  (TS_DEALT_TIPS=1
-    // deals the tiles of tips / read batches: the read predicate's sensitivity to the record placement was measured with it,
-    // profiles/r02/reads_taken_vs_dealt.txt.)
-    b->dealt_tiles = b->tips && ts_env_flag("TS_DEALT_TIPS");
-    if (b->range_bases <= (64ull << 20) && !b->match_cap_request) { cap = worst; b->dealt_tiles = true; }
+    // sized for the worst case of the tiles a wave is dealt, and to the rescans after an overflow.
+    b->dealt_tiles = b->range_bases <= (64ull << 20) && !b->match_cap_request;
+    if (b->dealt_tiles) cap = worst;
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 256), worst);
     b->region_cap = (uint32_t)((cap + 3) & ~3ull);
     b->match_cap = (uint64_t)b->region_cap * b->total_waves;
     // visible records (kp.emit): canonical matches at their density on random sequence, every match of a terminal zone
     // (a few per cent of its bases; every k-th base inside a telomere), twice the even share per wave, grown on overflow
     b->vis_cap = 0;
-    if (b->tips && b->kp.emit == 2u) {
-        // a read batch: the canonical records' indices — their density on random sequence, twice the even share per wave, and
-        // room for a few telomeric reads (a canonical record every k bases over thousands of bases); grown on overflow
-        const ts_ctx *c = b->ctx;
-        uint64_t ncanon = 0;
-        for (const ts::Pattern &p : c->patterns) ncanon += p.is_canonical ? 1 : 0;
-        const double d_canon = (double)std::max<uint64_t>(ncanon, 1) / (double)(1ull << (2 * std::min<uint32_t>(c->k, 16)));
-        const uint64_t vwant = (uint64_t)((double)b->range_bases * d_canon * 1.5);
-        uint64_t vcap = 2 * ceil_div(vwant, b->total_waves) + 8192;
-        if (b->dealt_tiles && !b->match_cap_request) vcap = worst;
-        vcap = std::min<uint64_t>(vcap, std::max<uint64_t>(worst, 256));
-        if (const char *e = getenv("TS_VIS_CAP")) { const long v = atol(e); if (v > 0) vcap = (uint64_t)v; }
-        b->vis_cap = (uint32_t)((vcap + 7) & ~7ull);
-    } else if (!b->tips) {
+    if (!b->tips) {
         const ts_ctx *c = b->ctx;
         uint64_t zone_bases = 0;
         const uint64_t tl = c->params.terminal_limit;
@@ -605,13 +577,7 @@ static ts_ctx *create_impl(const ts_params *params, const ts_pattern *patterns, 
     }
     c->longest = kmax;
     if (c->params.out_entropy && c->params.window_size && c->params.window_size <= (1u << 22)) ts::entropy_terms(c->params.window_size, c->entropy_term);
-    c->bp.terminal_limit = c->params.terminal_limit;
-    c->bp.max_match_dist = c->params.max_match_dist;
-    c->bp.min_block_len = c->params.min_block_len;
-    c->bp.max_block_dist = c->params.max_block_dist;
-    c->bp.min_block_counts = c->params.min_block_counts;
-    c->bp.min_block_density = c->params.min_block_density;
-    c->bp.first_pattern_len = n_patterns ? patterns[0].len : 0;
+    c->first_pattern_len = n_patterns ? patterns[0].len : 0;
 
     // tables of the general kernels: usable for any set with <= 8 distinct lengths <= 32
     if (n_patterns) {
@@ -933,18 +899,8 @@ ts_batch *ts_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t 
         return nullptr;
     }
     b->lds_bytes = (uint32_t)ts_k_lds_bytes(&b->kp);
-    // TS_READ_EMIT=1 (an experiment of round 5, off by default): a read filter's batches (ReadTelomereFilter::matches,
-    // /root/reference/src/read-filter.cpp:10-45: tips-only, every read terminal zone as a whole) have their scans leave the indices of
-    // the canonical records (kp.emit = 2), and the predicate visits only the chains that hold one (predicate.hip:
-    // ts_read_predicate_canon) — a twentieth of the records, but each visit is a scattered 32-byte look at the match stream, a
-    // 128-byte line of HBM traffic: 0.35 ms per 5e5 reads against the streaming walk's 0.31, and the scan pays 5 % for the indices
-    // (profiles/r05/reads_canonical_index_experiment.txt).  The same pass bytes on the read-filter fuzz either way.
-    if (b->tips && ctx->read_filter && b->kp.stage_u16) {
-        const char *e = getenv("TS_READ_EMIT");
-        if (e && e[0] == '1' && ts_k_read_index_built()) b->kp.emit = 2u;     // (only a library built with -DTS_READ_INDEX_BUILD=1 has it)
-    }
     // records leave as the stage holds them: 16 bits each where tile positions fit 14 bits (TS_REC32=1 / ts_batch_set_record_bits: 32)
-    b->kp.rec16 = (b->kp.stage_u16 && ctx->knobs.rec16 && b->kp.emit != 2u) ? 1u : 0u;
+    b->kp.rec16 = (b->kp.stage_u16 && ctx->knobs.rec16) ? 1u : 0u;
     set_range(b, 0, b->tiles.size());
     return b;
 }
@@ -1007,15 +963,11 @@ int ts_batch_restrict(ts_batch *b, uint64_t tile_begin, uint64_t tile_end) {
     return TS_OK;
 }
 
-// TS_EMIT=0 keeps every batch from emitting (A/B measurements: the interstitial search then reads every record again, as it
-// does for results adopted from elsewhere)
-static bool emit_allowed() { const char *e = getenv("TS_EMIT"); return !(e && e[0] == '0'); }
-
 int ts_batch_set_emit(ts_batch *b, int on) {
     if (!b) return TS_ERR_INVALID_ARG;
     if (b->dense) return b->ctx->fail(TS_ERR_STATE, "ts_batch_set_emit on a batch that adopted results");
-    if (b->tips) return TS_OK;                           // (a tips-only batch ignores it: a read batch keeps its own form, see ts_batch_create)
-    b->kp.emit = (on && emit_allowed()) ? 1u : 0u;
+    if (b->tips) return TS_OK;                           // (a tips-only batch ignores it)
+    b->kp.emit = on ? 1u : 0u;
     return TS_OK;
 }
 
@@ -1090,7 +1042,7 @@ int ts_batch_scan(ts_batch *b, const void *d_input, void *stream) {
     // small ranges, whose regions are sized for the worst case of the tiles a wave is DEALT, and the rescans after
     // an overflow, which size the regions from the counts of the scan before.
     kp.tile_tickets = (uint32_t *)b->d_tickets.p;
-    kp.ticket_groups = std::min<uint32_t>(b->grid, ticket_groups_wanted());
+    kp.ticket_groups = std::min<uint32_t>(b->grid, kTicketGroups);
     kp.dynamic_tiles = (b->dealt_tiles || ts_env_flag("TS_DEALT_TILES")) ? 0u : 1u;
     kp.ticket_slot = (uint32_t)(b->ticket_seq & 1u);
     kp.region_cap = b->region_cap;
@@ -1116,7 +1068,7 @@ int ts_batch_scan(ts_batch *b, const void *d_input, void *stream) {
 
     const size_t slot = (size_t)(b->scan_seq % kEventRing);
     static_assert(kEventRing == 64, "timed_mask holds one bit per ring slot");
-    const bool timed = c->knobs.scan_events >= 2 && b->time_every && (b->scan_seq % b->time_every) == 0;
+    const bool timed = b->time_every && (b->scan_seq % b->time_every) == 0;
     if (timed) { HIP_TRY(c, hipEventRecord(b->evs[2 * slot], st)); b->timed_mask |= 1ull << slot; }
     else b->timed_mask &= ~(1ull << slot);
     {
@@ -1125,7 +1077,7 @@ int ts_batch_scan(ts_batch *b, const void *d_input, void *stream) {
         if (e != 0) return c->fail(TS_ERR_HIP, std::string("scan kernel launch: ") + hipGetErrorString((hipError_t)e));
     }
     if (kp.dynamic_tiles) ++b->ticket_seq;        // the launch is enqueued: it zeroes the other counter for the next one
-    if (c->knobs.scan_events >= 1) HIP_TRY(c, hipEventRecord(b->evs[2 * slot + 1], st));
+    HIP_TRY(c, hipEventRecord(b->evs[2 * slot + 1], st));
     ++b->scan_seq;
     return TS_OK;
 }
@@ -1142,7 +1094,7 @@ int ts_batch_set_record_bits(ts_batch *b, int bits) {
     if (b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_set_record_bits: before the first scan");
     if (bits == 32) { b->kp.rec16 = 0u; return TS_OK; }
     // 16-bit records are the stage's own entries: tile positions below 2^14 (every geometry the planner picks for w <= 8192)
-    if (!b->kp.stage_u16 || b->kp.emit == 2u || b->dense)
+    if (!b->kp.stage_u16 || b->dense)
         return c->fail(TS_ERR_UNSUPPORTED, "16-bit records need 16-bit stage entries (tile positions below 2^14)");
     b->kp.rec16 = 1u;
     return TS_OK;
@@ -1153,7 +1105,6 @@ int ts_batch_wait_scan(ts_batch *b, void *stream) {
     ts_ctx *c = b->ctx;
     if (!b->scanned || b->dense || b->scan_seq == 0) return c->fail(TS_ERR_STATE, "ts_batch_wait_scan needs a scanned batch");
     if (stream == b->last_stream) return TS_OK;                 // (the same stream: in order already)
-    if (c->knobs.scan_events < 1) return c->fail(TS_ERR_STATE, "ts_batch_wait_scan: the scan's events are switched off (TS_SCAN_EVENTS=0)");
     DEVICE_TRY(c);
     const size_t last = (size_t)((b->scan_seq - 1) % kEventRing);
     HIP_TRY(c, hipStreamWaitEvent((hipStream_t)stream, b->evs[2 * last + 1], 0));
@@ -1169,7 +1120,7 @@ int ts_batch_sync(ts_batch *b) {
     for (int attempt = 0; attempt < 4; ++attempt) {
         {   // kernel times of the scans since the previous sync (the ring keeps the latest kEventRing)
             const size_t last = (size_t)((b->scan_seq - 1) % kEventRing);
-            if (c->knobs.scan_events >= 1) HIP_TRY(c, hipEventSynchronize(b->evs[2 * last + 1]));
+            HIP_TRY(c, hipEventSynchronize(b->evs[2 * last + 1]));
             const uint64_t from = std::max(b->harvested, b->scan_seq > kEventRing ? b->scan_seq - kEventRing : 0);
             double sum = 0.0;
             float ms = 0.f;
@@ -1339,13 +1290,13 @@ int ts_batch_segment_summary(ts_batch *b, void *d_out, void *stream) {
 
 // --------------------------------------------------------------- shared host post-processing
 // Turns one segment's raw results into SegmentData: window records (float metrics evaluated on
-// the host from the integer counts, as the reference does), terminal flags, block calling
-// (src/teloscope.cpp:642-657).  `matches` arrive with absolute positions and FORWARD/CANONICAL set.
-// `matches` (malloc'd by the caller, position-ordered, terminal flags not yet set; may be null when nm == 0)
+// the host from the integer counts, as the reference does), terminal flags, and the blocks called on the
+// device (pre_blocks).  `matches` arrive with absolute positions and FORWARD/CANONICAL set.
+// `matches` (malloc'd by the caller, in push order, terminal flags not yet set; may be null when nm == 0)
 // becomes the segment's match array.
 int ts_finalize_segment(ts_ctx *c, bool tips, uint64_t seg_len, uint64_t abs_pos,
                         const uint32_t *win_raw, uint64_t n_windows, ts_match *matches, uint64_t nm,
-                        ts_segment_out &o, unsigned spare_threads, const TsDevBlock *pre_blocks, size_t n_pre, bool have_pre) {
+                        ts_segment_out &o, unsigned spare_threads, const TsDevBlock *pre_blocks, size_t n_pre) {
     const ts_params &P = c->params;
     std::memset(&o, 0, sizeof o);
     if (!tips && n_windows) {
@@ -1388,49 +1339,31 @@ int ts_finalize_segment(ts_ctx *c, bool tips, uint64_t seg_len, uint64_t abs_pos
     o.n_matches = nm;
     if (!nm) std::free(matches);
     const uint64_t term_end = seg_len > P.terminal_limit ? seg_len - P.terminal_limit : 0;
-    uint64_t nfwd = 0;
     {
-        auto flag = [&](uint64_t i0, uint64_t i1, uint64_t *fwd_out) {
-            uint64_t f = 0;
+        auto flag = [&](uint64_t i0, uint64_t i1) {
             for (uint64_t i = i0; i < i1; ++i) {                    // isTerminal, src/teloscope.cpp:451-459
                 ts_match &m = o.matches[i];
                 const uint64_t rel = m.position - abs_pos;
                 if (rel <= P.terminal_limit || rel >= term_end) m.flags |= TS_MATCH_TERMINAL;
-                f += (m.flags & TS_MATCH_FORWARD) ? 1u : 0u;
             }
-            *fwd_out = f;
         };
         const unsigned nth = nm >= (1u << 20) ? std::max(1u, std::min<unsigned>(spare_threads, (unsigned)(nm >> 18))) : 1u;
-        std::vector<uint64_t> f(nth, 0);
-        if (nth <= 1u) flag(0, nm, &f[0]);
+        if (nth <= 1u) flag(0, nm);
         else {
             std::vector<std::thread> pool;
             const uint64_t share = (nm + nth - 1) / nth;
             for (unsigned t = 0; t < nth; ++t)
-                pool.emplace_back(flag, std::min<uint64_t>(nm, t * share), std::min<uint64_t>(nm, (t + 1) * share), &f[t]);
+                pool.emplace_back(flag, std::min<uint64_t>(nm, t * share), std::min<uint64_t>(nm, (t + 1) * share));
             for (std::thread &th : pool) th.join();
         }
-        for (uint64_t v : f) nfwd += v;
     }
-    // the two walks take their orientation's records out of the one position-ordered array (they leave the
-    // terminal zone after a few thousand records: no per-orientation index lists of the whole segment)
+    // the blocks were called on the device (sorted: terminal blocks in push order, then interstitial blocks by start)
     std::vector<ts_block> term, its;
-    if (have_pre) {
-        // the blocks were called on the device (sorted: terminal blocks in push order, then interstitial blocks by start)
-        for (size_t q = 0; q < n_pre; ++q) {
-            ts_block b;
-            std::memcpy(&b, &pre_blocks[q], sizeof b);
-            (pre_blocks[q].kind == 2 ? its : term).push_back(b);
-        }
+    for (size_t q = 0; q < n_pre; ++q) {
+        ts_block b;
+        std::memcpy(&b, &pre_blocks[q], sizeof b);
+        (pre_blocks[q].kind == 2 ? its : term).push_back(b);
     }
-    uint64_t fwd_boundary = abs_pos, rev_boundary = abs_pos + seg_len;
-    if (have_pre) {
-    } else if (nfwd >= 2)
-        fwd_boundary = ts::terminal_blocks(c->bp, o.matches, nullptr, nm, term, seg_len, abs_pos, true, 1);
-    if (!have_pre && nm - nfwd >= 2)
-        rev_boundary = ts::terminal_blocks(c->bp, o.matches, nullptr, nm, term, seg_len, abs_pos, false, 0);
-    if (!have_pre && !tips && fwd_boundary < rev_boundary && nm >= 2)
-        ts::interstitial_blocks(c->bp, o.matches, nm, its, fwd_boundary, rev_boundary);
     auto copy_blocks = [&](const std::vector<ts_block> &v, ts_block *&dst, uint64_t &n) -> bool {
         n = v.size();
         dst = nullptr;
@@ -1602,7 +1535,7 @@ int ts_device_block_call_raw(ts_ctx *c, const TsTile *d_tiles, const unsigned lo
         Q.terminal_limit = P.terminal_limit; Q.max_match_dist = P.max_match_dist;
         Q.min_block_len = P.min_block_len; Q.max_block_dist = P.max_block_dist;
         Q.min_block_counts = P.min_block_counts; Q.min_block_density = P.min_block_density;
-        Q.k = c->k; Q.its_min_len = (uint32_t)(uint16_t)(2 * c->bp.first_pattern_len);
+        Q.k = c->k; Q.its_min_len = (uint32_t)(uint16_t)(2 * c->first_pattern_len);
         Q.gen_lens = gen_lens;
         Q.rec16 = rec16 ? 1u : 0u;
         // (the general path's wide records and push-ordered streams: blockcall.hip, MODE 1)

@@ -103,7 +103,7 @@ private:
 struct ts_ctx {
     ts_params params{};
     std::vector<ts::Pattern> patterns;
-    ts::BlockParams bp{};
+    uint16_t first_pattern_len = 0; // userInput.patterns.front().size(): interstitial blocks are at least twice as long
     uint32_t k = 0;                 // uniform pattern length (0 = mixed)
     uint32_t longest = 0;
     bool fast_ok = false;           // table-driven tiled kernel usable for the pattern set
@@ -126,16 +126,11 @@ struct ts_ctx {
     mutable std::string error;
     bool read_filter = false;
     // measurement / test knobs of the host entry points, read from the environment ONCE, when the context is made (never per call):
-    // TS_TIMING (stage times to stderr), TS_GEN_HOST_BLOCKS=1 (general path: block calling on the host), TS_GEN_PREFETCH=0,
-    // TS_GEN_LIST=0 (general path: the strided form), TS_GEN_ABL (profiling mask of the general kernels)
-    // TS_PACKED_UPLOAD=0 (bases cross PCIe as ASCII), TS_PACKED_MIN_BYTES (calls below it go plain), TS_STAGE_THREADS
+    // TS_TIMING (stage times to stderr), TS_GEN_LIST=0 (general path: the strided form), TS_PACKED_UPLOAD=0 (bases cross PCIe
+    // as ASCII), TS_PACKED_MIN_BYTES (calls below it go plain), TS_REC32=1 (32-bit records)
     struct Knobs {
-        bool timing = false, gen_host_blocks = false, gen_prefetch = true, gen_list = true, packed_upload = true, gen_compact_always = false;
-        uint32_t gen_abl = 0, stage_threads = 0;
-        int side_priority = 0;                                // stream priority of the pack's side stream (0: the default priority)
-        int scan_events = 2;                                  // events ts_batch_scan records around a scan: 2 both (kernel times), 1 the one behind it, 0 none (measurements)
-        bool rec16 = true;                                    // read-filter batches keep 16-bit records where they can (TS_REC32=1: 32-bit, for A/B)
-        bool side_probe = true;                               // try the side stream against the scan / pack streams it meets (shard.cpp)
+        bool timing = false, gen_list = true, packed_upload = true;
+        bool rec16 = true;                                    // scans keep 16-bit records where they can (TS_REC32=1: 32-bit)
         uint64_t packed_min_bytes = 1u << 20;                 // small calls are latency, not link time: they go plain
     } knobs;
     BufferPool pool;
@@ -299,7 +294,7 @@ bool ts_full_scan_supported(const ts_ctx *c, std::string &why);
 void *ts_alloc_large(size_t bytes);     // malloc-compatible; many-MB arrays on 2 MB pages when the kernel grants them
 int  ts_finalize_segment(ts_ctx *c, bool tips, uint64_t seg_len, uint64_t abs_pos, const uint32_t *win_raw,
                          uint64_t n_windows, ts_match *matches, uint64_t nm, ts_segment_out &o, unsigned spare_threads,
-                         const TsDevBlock *pre_blocks = nullptr, size_t n_pre = 0, bool have_pre = false);   // have_pre: blocks called on the device
+                         const TsDevBlock *pre_blocks, size_t n_pre);   // pre_blocks: the segment's blocks, called on the device
 int  ts_batch_ensure_device(ts_batch *b);        // allocates the range's device state (idempotent)
 // block calling on the device over a resident match stream + tile directory (a batch's, or the general kernels' dense stream)
 int  ts_device_block_call_raw(ts_ctx *c, const TsTile *d_tiles, const unsigned long long *d_tile_off, const uint32_t *d_stats,

@@ -210,7 +210,6 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
     if (lds_lists)
         for (uint32_t i = tid; i < npat; i += 256u) { pcode[i] = G.codes[i]; pflag[i] = G.flags[i]; }
     const TsGeneralTile T = tiles[blockIdx.x];
-    if (Q.abl & 8u) { if (tid == 0u) *(uint4 *)&tile_stats[4ull * blockIdx.x] = make_uint4(0u, 0u, 0u, 0u); return; }
     // 1. stage: bases [0, avail) of the tile (avail = what lies between its start and the region end, at most
     // kTile + kHalo); layout offsets are 16-byte aligned per segment, tiles start at multiples of kTile inside it.
     // Thread t packs bases [16 t, 16 t + 16) (and the halo's); positions beyond avail are invalid.
@@ -254,7 +253,6 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
     __syncthreads();
     // 2. matches
     for (uint32_t j = tid; j < T.n; j += 256u) {
-        if (Q.abl & 1u) { mask[j] = 0; continue; }
         // the next 32 bases of position j: three plane dwords funnelled by 2 (j mod 16) bits; their validity bits alike
         const uint32_t wd = j >> 4, sh = 2u * (j & 15u);
         const uint32_t c0 = codes2[wd], c1 = codes2[wd + 1u], c2 = codes2[wd + 2u];
@@ -286,7 +284,7 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
     const u64 n = seg_len[T.seg];
     const u64 P0 = T.seg_rel;
     // 3. window records (full scans)
-    if (!tips && T.n && !(Q.abl & 2u)) {
+    if (!tips && T.n) {
         const u64 nwin = (n + Q.s - 1u) / Q.s;
         const u64 kw_lo = P0 >= Q.w ? (P0 - Q.w) / Q.s + 1u : 0u;             // first call whose window reaches the tile
         u64 kw_hi = (P0 + T.n - 1u) / Q.s;                                    // last call that starts inside it
@@ -320,7 +318,6 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
         }
     }
     // 4. match records: wave v owns the 1024 consecutive positions [1024 v, 1024 v + 1024)
-    if (Q.abl & 4u) { if (tid == 0u) *(uint4 *)&tile_stats[4ull * blockIdx.x] = make_uint4(0u, 0u, 0u, 0u); return; }
     const PushGeom pg = push_geom(P0, n, Q);
     uint32_t wave_cnt = 0;
     for (uint32_t r = 0; r < 16u; ++r) {
@@ -448,10 +445,7 @@ __device__ __forceinline__ void gen_or(uint32_t *p, uint32_t v) { asm volatile("
 // Taken when a tile adds to at most kWaccMax window records (decided on the host from w and s) and the pattern lists fit
 // LDS; a wave whose list overflows (more than one candidate per position: dense repeats under a mixed-length set) raises
 // overflow bit 1 and the group runs again with the kernel above.
-#ifndef TS_GEN_WAVES
-#define TS_GEN_WAVES 5
-#endif
-__global__ __launch_bounds__(256, TS_GEN_WAVES)        // waves per SIMD = workgroups per CU.  74 VGPRs and nothing spilled since round 5 (scalar descriptor loads); five per CU still measure best: six +1.5 %, seven +8 % (profiles/r05/general_list_waits.txt; round 4, at 96 VGPRs with two spilled: profiles/r04/general_occupancy.txt)
+__global__ __launch_bounds__(256, 5)        // waves per SIMD = workgroups per CU.  74 VGPRs and nothing spilled since round 5 (scalar descriptor loads); five per CU still measure best: six +1.5 %, seven +8 % (profiles/r05/general_list_waits.txt; round 4, at 96 VGPRs with two spilled: profiles/r04/general_occupancy.txt)
 void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, uint32_t ntiles, const u64 *seg_len,
                            const u64 *seg_win_base, const u64 *seg_nwin, const TsGenericPatterns G, const TsGenericGeom Q, int tips, uint32_t slot_cap,
                            uint32_t lds_patterns, uint32_t nshort, uint32_t *tile_stats, uint32_t *records, uint32_t *win_out, uint32_t *overflow) {
@@ -606,7 +600,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
         // 2'. candidates: wave v owns the 1024 consecutive positions [1024 v, 1024 v + 1024), lane L the sixteen from 16 L on
         uint32_t ncand = 0;                                                    // (wave-uniform)
         bool spilled = false;
-        if (!(Q.abl & 16u)) {
+        {
             const uint32_t wd0 = wave * 64u + lane, j0 = wd0 * 16u;
             const uint32_t c0 = codes2[wd0], c1 = codes2[wd0 + 1u];
             uint32_t acc[4] = {0u, 0u, 0u, 0u};                                // a byte of length bits per position
@@ -693,7 +687,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
         uint32_t npush = 0;
         __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
-        for (uint32_t e0 = 0; e0 < ncand && !spilled && !(Q.abl & 32u); e0 += 64u) {
+        for (uint32_t e0 = 0; e0 < ncand && !spilled; e0 += 64u) {
             const uint32_t e = e0 + lane;
             bool pushed = false;
             if (e < ncand) {
@@ -766,7 +760,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
         }
         // 4'. window records: thread r takes record kw_lo + r.  Positions relative to the tile's first base, 32-bit signed (the
         // host keeps w below 2^28 on this path; a segment end farther away than that is as good as infinitely far)
-        if (win_on && !any_spill && !(Q.abl & 64u) && (u64)tid <= rec_hi - kw_lo) {
+        if (win_on && !any_spill && (u64)tid <= rec_hi - kw_lo) {
             const u64 R = kw_lo + tid;
             const int32_t rel = (int32_t)((long long)(kw_lo * Q.s) - (long long)P0) + (int32_t)(tid * Q.s);   // R s - P0
             const int32_t N1c = N1 > 0x3FFF0000ull ? 0x3FFF0000 : (int32_t)N1;
@@ -1071,7 +1065,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
     uint32_t ncand = 0;
     for (uint32_t i = tid; i < kTile * (uint32_t)sizeof(M) / 16u; i += 256u) ((uint4 *)hit)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid < 128u) hitmap[tid] = 0u;
-    if (!(Q.abl & 128u)) {
+    {
         const uint32_t wd0 = wave * 64u + lane, j0 = wd0 * 16u;
         const uint32_t c0 = codes2[wd0], c1 = codes2[wd0 + 1u];
         uint32_t mask16 = 0;
@@ -1137,7 +1131,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
     const u64 n = seg_len[T.seg];
     const u64 P0 = T.seg_rel;
     // 3. window records (full scans): as in ts_general_fused
-    if (!tips && T.n && !(Q.abl & 256u)) {
+    if (!tips && T.n) {
         // (no 64-bit division: the host hands over P0 = k_p0 s + r_p0 per tile, w = cw s + rw per call and the segments' window counts)
         const u64 nwin = seg_nwin[T.seg];
         const u64 kw_lo = P0 >= Q.w ? T.k_p0 + 1u - Q.cw - (Q.rw > T.r_p0 ? 1u : 0u) : 0u;     // first call whose window reaches the tile: (P0 - w) / s + 1
@@ -1469,7 +1463,6 @@ int ts_k_launch_general_fused(const unsigned char *in, const TsGeneralTile *tile
         const unsigned long long lds2 = 4ull * kListWave * 2u + (((unsigned long long)lp * 8u + 15u) & ~15ull) + 4096u + nshort * 1024u + kWaccMax * 16u + 32u + 48u + 32u + 64u +
                                         kCodeWords * 4u + kInvalWords * 4u + kCodeWords * 4u + 2u * kCumWords * 4u + ((lp + 15u) & ~15u);
         // persistent workgroups: as many as the device holds at once (LDS bound), each strides over the tiles
-        static const uint32_t wg_override = [] { const char *e = getenv("TS_GEN_WGS"); return e ? (uint32_t)atoi(e) : 0u; }();
         // (what the runtime says fits: a grid of more workgroups than are resident at once ends in a round of stragglers —
         // 1280 workgroups where 1024 fit measured 7.0 ms against 6.0, profiles/r04/general_occupancy.txt)
         int per_cu = 0;
@@ -1478,7 +1471,6 @@ int ts_k_launch_general_fused(const unsigned char *in, const TsGeneralTile *tile
             per_cu = (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>(8ull, (128ull << 10) / lds2));
         }
         uint32_t grid = (uint32_t)(num_cu > 0 ? num_cu : 256) * (uint32_t)per_cu;
-        if (wg_override) grid = wg_override;
         if (grid > ntiles) grid = ntiles;
         hipLaunchKernelGGL(ts_general_fused_list, dim3(grid), dim3(256), (size_t)lds2, (hipStream_t)stream, in, tiles, ntiles,
                            (const u64 *)seg_len, (const u64 *)seg_win_base, (const u64 *)seg_nwin, *G, *Q, tips, slot_cap, lp, nshort, tile_stats, records, win_out, overflow);

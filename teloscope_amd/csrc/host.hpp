@@ -26,21 +26,7 @@ int  base_code(char c);
 bool build_match_table(const std::vector<Pattern> &pats, uint32_t k, uint32_t max_byte_k, std::vector<uint32_t> &table,
                        uint32_t &rows, uint32_t &fc_bytes, bool &fc_byte_table, bool &pair_byte_table);
 
-// blocks.cpp — block calling on the match stream (src/teloscope.cpp:29-383)
-struct BlockParams {
-    uint32_t terminal_limit;
-    uint16_t max_match_dist, min_block_len, max_block_dist, min_block_counts;
-    float    min_block_density;
-    uint16_t first_pattern_len;     // userInput.patterns.front().size()
-};
-
-// Matches are passed as parallel views over ts_match records; `idx` selects a subsequence
-// (fwdMatches / revMatches) without copying, nullptr = all.
-uint64_t terminal_blocks(const BlockParams &bp, const ts_match *m, const uint32_t *idx, size_t n,
-                         std::vector<ts_block> &out, uint64_t seg_size, uint64_t abs_pos, bool from_start,
-                         int only_forward = -1);
-void interstitial_blocks(const BlockParams &bp, const ts_match *m, size_t n, std::vector<ts_block> &out,
-                         uint64_t fwd_boundary, uint64_t rev_boundary);
+// blocks.cpp
 int  label_terminal_blocks(ts_block *blocks, size_t n, uint16_t gaps, uint64_t path_size,
                            uint32_t terminal_limit, std::string &label);
 

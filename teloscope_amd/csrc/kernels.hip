@@ -35,57 +35,16 @@
 
 #include "ts_internal.h"
 
-// Profiling only: -DTS_ABL=<mask> builds a kernel with one stage removed (results are then wrong)
-// so that stage costs can be measured under real overlap; see profiles/ablate.sh.
-//   1 record flush to global  2 nucleotide window sums  4 window match accumulation
-//   8 window record stores  16 the whole per-match pass  32 table probes  64 code plane stores
-//   128 the consumption of the match queue (compaction still runs)
-#ifndef TS_ABL
-#define TS_ABL 0
-#endif
-// Experiments and diagnostics (profiles/abx.sh): -DTS_EXP=<mask>.  8: every tile leaves the 100 MHz timestamp of its end
-// (20 bits) and the wave that scanned it (12 bits) in the spare word of its tile_stats row (profiles/tile_timeline.py
-// reads the waves' timelines from them).
-// 1: no wave priorities (every phase at priority 0, as before they were introduced).
-#ifndef TS_EXP
-#define TS_EXP 0
-#endif
-// 1: the emitting build requests its next tile at the start of phase 2 instead of ahead of the tile's last passes (-0.4 % on configs[1]: profiles/r05/emit_ab_plain_emit_r04_r05_late_ffirst.txt; 0 for A/B)
-// whole rows of 64 records take a copy of the row code without the mask of live lanes (0: one copy for every row)
-#ifndef TS_EMIT_FULL_ROWS
-#define TS_EMIT_FULL_ROWS 1
-#endif
-#ifndef TS_EMIT_LATE_REQUEST
-#define TS_EMIT_LATE_REQUEST 1
-#endif
-// (measurement: results are then wrong) 1: the rows are not looked at, 2: no visible records, 4: no chain summary
-#ifndef TS_EMIT_ABL
-#define TS_EMIT_ABL 0
-#endif
-#ifndef TS_EMIT_FINISH_LAST
-#define TS_EMIT_FINISH_LAST 1
-#endif
-#ifndef TS_PLAIN_FINISH_LAST
-#define TS_PLAIN_FINISH_LAST 0
-#endif
-
 // Wave priorities (s_setprio; the SIMD's arbiter picks the ready wave of the highest priority, the oldest among equals).
 // The dense per-chunk work (decode, probes: long runs of independent vector instructions) stays at 0; the phases that are
 // chains of dependent LDS / memory operations with a few instructions between the waits run above it, so that those few
 // instructions issue as soon as their operand arrives instead of queueing behind another wave's dense run, and the wave
 // is back in dense work sooner: configs[1] -2.8 .. -3.8 %, the k = 7 and default-flag configurations -1.5 %
 // (profiles/r02/kernel_experiments_ab.txt, "wave priorities").
-#ifndef TS_PRIO_PASS
-#define TS_PRIO_PASS 3          // the per-match pass over 64 queued matches
-#endif
-#ifndef TS_PRIO_APPEND
-#define TS_PRIO_APPEND 2        // prefix sum of a chunk pair's match counts + the queue writes
-#endif
-#ifndef TS_PRIO_WINDOWS
-#define TS_PRIO_WINDOWS 2       // phase 2: record flush, nucleotide counts, window records, tile directory
-#endif
-#define set_prio(p) do { if (!(TS_EXP & 1)) __builtin_amdgcn_s_setprio(p); } while (0)
-constexpr int kPrioPass = TS_PRIO_PASS, kPrioAppend = TS_PRIO_APPEND, kPrioWindows = TS_PRIO_WINDOWS;
+#define set_prio(p) __builtin_amdgcn_s_setprio(p)
+constexpr int kPrioPass = 3;          // the per-match pass over 64 queued matches
+constexpr int kPrioAppend = 2;        // prefix sum of a chunk pair's match counts + the queue writes
+constexpr int kPrioWindows = 2;       // phase 2: record flush, nucleotide counts, window records, tile directory
 
 namespace {
 
@@ -102,7 +61,7 @@ typedef LDS uint32_t lds_u32;
 __device__ __forceinline__ lds_u16 *lds_at16(uint32_t addr) { return (lds_u16 *)(uintptr_t)addr; }
 __device__ __forceinline__ lds_u8 *lds_at8(uint32_t addr) { return (lds_u8 *)(uintptr_t)addr; }
 
-// Global stores the compiler does not see (TS_ASM_STORES, default on).  On gfx9 loads and stores share one counter (vmcnt) and may
+// Global stores the compiler does not see.  On gfx9 loads and stores share one counter (vmcnt) and may
 // retire out of order with respect to each other, so once a store is pending the compiler can only wait for a LOAD with vmcnt(0) —
 // and it does so early: in front of every loop that holds a store and no load it empties the counter ("flush in the preheader").
 // In this kernel that meant an s_waitcnt vmcnt(0) right behind the request of the next tile's first chunk (the last drain of the
@@ -110,74 +69,33 @@ __device__ __forceinline__ lds_u8 *lds_at8(uint32_t addr) { return (lds_u8 *)(ui
 // The stores never feed a load of this kernel (the one place that reads records back waits for vmcnt(0) itself), so they are issued
 // by inline asm: the compiler counts only its loads, whose waits stay counted, and a pending store can only make such a wait longer,
 // never too short (loads retire in order among themselves).  Measurements: profiles/r05/asm_stores.txt.
-// -DTS_READ_INDEX_BUILD=1: the emitting build also knows kp.emit == 2 (canonical-record indices for ts_read_predicate_canon, the read
-// filter experiment of profiles/r05/reads_canonical_index_experiment.txt); without it ts_k_read_index_built() says no and
-// TS_READ_EMIT=1 is ignored.
-#ifndef TS_READ_INDEX_BUILD
-#define TS_READ_INDEX_BUILD 0
-#endif
-#ifndef TS_ASM_STORES
-#define TS_ASM_STORES 1
-#endif
 __device__ __forceinline__ void gstore(uint32_t *p, uint32_t v) {
-#if TS_ASM_STORES
     asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void gstore(uint16_t *p, uint16_t v) {
-#if TS_ASM_STORES
     asm volatile("global_store_short %0, %1, off" :: "v"(p), "v"((uint32_t)v));
-#else
-    *p = v;
-#endif
 }
 // (the low 16 bits of v: the store takes them itself)
 __device__ __forceinline__ void gstore_lo16(uint16_t *p, uint32_t v) {
-#if TS_ASM_STORES
     asm volatile("global_store_short %0, %1, off" :: "v"(p), "v"(v));
-#else
-    *p = (uint16_t)v;
-#endif
 }
 __device__ __forceinline__ void gstore(unsigned char *p, unsigned char v) {
-#if TS_ASM_STORES
     asm volatile("global_store_byte %0, %1, off" :: "v"(p), "v"((uint32_t)v));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void gstore(u64 *p, u64 v) {
-#if TS_ASM_STORES
     asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(v));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void gstore(uint4 *p, uint4 v) {
-#if TS_ASM_STORES
     const u32x4 d = {v.x, v.y, v.z, v.w};
     // (s_nop: a store of more than 8 bytes reads its data a cycle late, and the hazard recogniser does not look into asm)
     asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 0" :: "v"(p), "v"(d));
-#else
-    *p = v;
-#endif
 }
 // (possibly unaligned: the bit-packed window records)
 __device__ __forceinline__ void gstore_unaligned(unsigned char *p, u64 v) {
-#if TS_ASM_STORES
     asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(v));
-#else
-    __builtin_memcpy(p, &v, 8);
-#endif
 }
 __device__ __forceinline__ void gstore_unaligned(unsigned char *p, uint32_t v) {
-#if TS_ASM_STORES
     asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v));
-#else
-    __builtin_memcpy(p, &v, 4);
-#endif
 }
 
 // Wave-wide inclusive prefix sum in 6 DPP adds (row_shr 1/2/4/8 inside each row of 16,
@@ -436,7 +354,7 @@ void ts_scan_tiles(const TsScanParams P) {
             const bool rec16 = Q->rec16 != 0u;                       // (16-bit records: the stage's entries as they are, see TsScanParams)
             for (uint32_t i = lane; i < n; i += 64u) {
                 const uint32_t o = cursor + flushed + i;
-                if (o < cap && !(TS_ABL & 1)) {
+                if (o < cap) {
                     if (rec16) gstore_lo16((uint16_t *)Q->matches_out + (u64)gw * cap + o, stage_at(i));
                     else gstore(wave_out + o, stage_at(i));
                 }
@@ -473,13 +391,13 @@ void ts_scan_tiles(const TsScanParams P) {
                     uint16_t *const dst = wave_out16 + cursor + flushed;
                     for (uint32_t i = 4u * ln; i < n4; i += 256u) {
                         const u32x2 q = *(const LDS u32x2 *)((lds_u16 *)stage + i);
-                        if (!(TS_ABL & 1)) gstore_unaligned((unsigned char *)(dst + i), (u64)q.x | ((u64)q.y << 32));
+                        gstore_unaligned((unsigned char *)(dst + i), (u64)q.x | ((u64)q.y << 32));
                     }
-                    if (ln < n - n4 && !(TS_ABL & 1)) gstore_lo16(dst + n4 + ln, stage_at(n4 + ln));
+                    if (ln < n - n4) gstore_lo16(dst + n4 + ln, stage_at(n4 + ln));
                 } else
                 for (uint32_t i = ln; i < n; i += 64u) {
                     const uint32_t o = cursor + flushed + i;
-                    if (o < cap && !(TS_ABL & 1)) {
+                    if (o < cap) {
                         if (rec16) gstore_lo16(wave_out16 + o, stage_at(i));
                         else gstore(wave_out + o, stage_at(i));
                     }
@@ -498,12 +416,8 @@ void ts_scan_tiles(const TsScanParams P) {
             const uint32_t vbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)park[4]);   // the wave's visible cursor
             // (a scalar load — the table is written by the host only — not a vector one, whose wait (vmcnt) is also a wait for the next
             // tile's first chunk, in flight since the end of phase 1, and for every store ahead of it)
-            // P.emit == 2 (a read batch: tips-only, every segment terminal zone as a whole): what leaves is the INDEX, among the
-            // tile's records, of every canonical record — the read predicate (predicate.hip: ts_read_predicate_canon) then looks
-            // only at the chains that hold one, a twentieth of the records — and no chain summary.
-            const bool idx_mode = TS_READ_INDEX_BUILD ? Q->emit == 2u : false;     // (a build flag: two vector instructions per row otherwise)
             typedef const uint32_t __attribute__((address_space(4))) *ConstU32;
-            const uint32_t zone = idx_mode ? TS_ZONE_NONE : ((ConstU32)(uintptr_t)Q->tile_zone)[tile];
+            const uint32_t zone = ((ConstU32)(uintptr_t)Q->tile_zone)[tile];
             const uint32_t vis_cap = Q->vis_cap;
             const bool wide = FAST ? false : Q->vis_wide != 0u;        // (16-bit stage entries = tile positions below 2^14 = 16-bit visible records)
             void *const vis_out = Q->vis_out;
@@ -523,12 +437,11 @@ void ts_scan_tiles(const TsScanParams P) {
                 {
                     u64 vm = canm;
                     if (zone != TS_ZONE_NONE) vm = live_m & (canm | ballot64(u < (zone & 0xFFFFu)) | ballot64(u >= (zone >> 16)));
-                    if (vm != 0ull && !(TS_EMIT_ABL & 2)) {
+                    if (vm != 0ull) {
                         const uint32_t at = vbase + vout + __builtin_amdgcn_mbcnt_hi((uint32_t)(vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vm, 0u));
                         if (__builtin_amdgcn_inverse_ballot_w64(vm) && (vis_fit || at < vis_cap)) {
-                            const uint32_t what = idx_mode ? base + i0 + ln : r;
-                            if (wide) gstore((uint32_t *)vis_out + (vwave + at), what);
-                            else gstore((uint16_t *)vis_out + (vwave + at), (uint16_t)what);
+                            if (wide) gstore((uint32_t *)vis_out + (vwave + at), r);
+                            else gstore((uint16_t *)vis_out + (vwave + at), (uint16_t)r);
                         }
                         vout += (uint32_t)__popcll(vm);
                     }
@@ -538,7 +451,7 @@ void ts_scan_tiles(const TsScanParams P) {
                 // third of them) changes neither.
                 const uint32_t ncan = (uint32_t)__popcll(canm);
                 const uint32_t t = ch_cc + ncan;
-                if ((t | (~ch_w1 & TS_CHAIN_HEADS)) != 0u && !idx_mode && !(TS_EMIT_ABL & 4)) {            // (integer logic: a uniform bool costs three scalar instructions to combine)
+                if ((t | (~ch_w1 & TS_CHAIN_HEADS)) != 0u) {            // (integer logic: a uniform bool costs three scalar instructions to combine)
                     // the lane below holds the record before, lane 0 gets the last record of the row before
                     uint32_t below = (uint32_t)__builtin_amdgcn_update_dpp((int)ch_last, (int)u, 0x138, 0xf, 0xf, false);   // wave_shr:1, lane 0 keeps ch_last
                     asm volatile("" : "+v"(below));            // (kept a v_mov_b32_dpp: see lane_below)
@@ -603,16 +516,14 @@ void ts_scan_tiles(const TsScanParams P) {
             // loads with vmcnt(0), which also waits for the row stores before them and for the next tile's first chunk (in flight
             // since the end of phase 1) — six memory round trips per tile in the first version of this code.
             if (!redo) {
-                const uint32_t nfull = TS_EMIT_FULL_ROWS ? n & ~63u : 0u;
+                const uint32_t nfull = n & ~63u;
                 for (uint32_t i0 = 0; i0 < nfull; i0 += 64u) {             // whole rows
                     const uint32_t o = cursor + base + i0 + ln;
                     const uint32_t r = stage_at(i0 + ln);
-                    if (!(TS_ABL & 1)) {
-                        auto put = [&]() { if (rec16) gstore_lo16(wave_out16 + o, r); else gstore(wave_out + o, r); };
-                        if (rec_fit) put();                                // (whole-tile bound, scalar)
-                        else if (o < cap) put();
-                    }
-                    if (!(TS_EMIT_ABL & 1)) look(r, 64u, i0, std::true_type{});
+                    auto put = [&]() { if (rec16) gstore_lo16(wave_out16 + o, r); else gstore(wave_out + o, r); };
+                    if (rec_fit) put();                                    // (whole-tile bound, scalar)
+                    else if (o < cap) put();
+                    look(r, 64u, i0, std::true_type{});
                 }
                 for (uint32_t i0 = nfull; i0 < n; i0 += 64u) {              // the tile's last, partial row
                     const uint32_t nrow = n - i0 < 64u ? n - i0 : 64u;
@@ -620,12 +531,12 @@ void ts_scan_tiles(const TsScanParams P) {
                     uint32_t r = 0u;
                     if (ln < nrow) {
                         r = stage_at(i0 + ln);
-                        if (o < cap && !(TS_ABL & 1)) {
+                        if (o < cap) {
                             if (rec16) gstore_lo16(wave_out16 + o, r);
                             else gstore(wave_out + o, r);
                         }
                     }
-                    if (!(TS_EMIT_ABL & 1)) look(r, nrow, i0, std::false_type{});
+                    look(r, nrow, i0, std::false_type{});
                 }
             } else {
                 for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
@@ -662,7 +573,6 @@ void ts_scan_tiles(const TsScanParams P) {
         // runs on 64 queued matches (fewer when the tile ends or the queue must make room).
         uint32_t qhead = 0, qcount = 0;                            // head as a byte offset into the ring, entries queued
         auto drain_queue = [&](const uint32_t threshold) {
-            if (TS_ABL & 128) { qcount = 0; return; }           // profiling: compaction only, nothing consumed
             if (qcount >= threshold && qcount > 0u) set_prio(kPrioPass);
             while (qcount >= threshold && qcount > 0u) {
                 const uint32_t n = qcount < 64u ? qcount : 64u;
@@ -716,7 +626,7 @@ void ts_scan_tiles(const TsScanParams P) {
                 const u64 inc = (u64)(is_can ? 1u : 0x10000u) | ((u64)(is_fwd ? 1u : 0x10000u) << 32);
                 // windows q, q-1, ... contain the match as long as it ends inside them.  Window q always does:
                 // o + k <= w holds for every valid match (w == s: the straddle rule above; w > s: k <= w - s)
-                if (P.windows_on && accb && !(TS_ABL & 4)) {
+                if (P.windows_on && accb) {
                     // per step block: block q takes the match, and the row of run-overs takes it too when it ends behind the block's
                     // end (o + k > s: k - 1 offsets of s) — a window is the sum of its blocks minus the run-overs of its last one
                     if (valid && q < nblk) atomicAdd((unsigned long long *)(wacc + acc_off + q), inc);
@@ -724,7 +634,7 @@ void ts_scan_tiles(const TsScanParams P) {
                     if (over != 0ull) {
                         if (__builtin_amdgcn_inverse_ballot_w64(over) && q < nblk) atomicAdd((unsigned long long *)(wacc + P.acc_copies * acc_rows + q), inc);
                     }
-                } else if (P.windows_on && !(TS_ABL & 4)) {
+                } else if (P.windows_on) {
                     for (uint32_t j = 0; j < nwper; ++j) {
                         const uint32_t wi = q - j;            // wraps past window 0
                         const bool in = valid && wi < T.nwin && o + k + j * P.s <= P.w;
@@ -789,7 +699,6 @@ void ts_scan_tiles(const TsScanParams P) {
             // starts at an even position and holds {match at p, match at p+1} (16 entries per dword:
             // row = index >> 4, bit = 2 * (index & 15)).  All sixteen ds_read_b32 are issued back to
             // back (inline asm) and consumed behind one counted wait.
-#if !(TS_ABL & 32)
             uint32_t tmp[16], ent[16];
             // bases 16..31 of a code dword followed by bases 0..15 of the next one: the (k+1)-mers that start
             // at bases 10, 12, 14 lie inside it (k <= 6)
@@ -814,25 +723,18 @@ void ts_scan_tiles(const TsScanParams P) {
                     asm volatile("ds_read_b32 %0, %1" : "=v"(ent[j]) : "v"(addr));
                 }
             }
-#endif
             // (issued while the probes are in flight: the stores and the counting need nothing from them)
             // the lane's bases go to the tile's code plane (lane 63's first dword is the look-ahead of lane 62's
             // last k-mers; the next chunk's lane 0 rewrites the same slot with the same value)
-            if (!(TS_ABL & 64)) {
-                const uint32_t h = ch + lane;                     // index of the lane's 32 positions in the plane
-                *(LDS u32x2 *)(codes + 2u * h) = (u32x2){wa, wb};
-            }
+            const uint32_t h = ch + lane;                         // index of the lane's 32 positions in the plane
+            *(LDS u32x2 *)(codes + 2u * h) = (u32x2){wa, wb};
 
-#if TS_ABL & 32
-            uint32_t M32 = wa & wb & (wa >> 7) & (nx >> 3) & (wb >> 11);
-#else
             uint32_t M32 = 0;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 16; ++j)
                 M32 = __builtin_amdgcn_alignbit(PAIR_BYTES ? ent[j] : ent[j] >> ((tmp[j] << 1) & 31u), M32, 2);
-#endif
 
             if (slow) {                                           // k-mers touching an invalid base
                 const uint32_t inv_next = (uint32_t)__builtin_amdgcn_mov_dpp((int)inv, 0x130, 0xf, 0xf, false);
@@ -842,9 +744,6 @@ void ts_scan_tiles(const TsScanParams P) {
                 M32 &= ~kb;
             }
 
-#if TS_ABL & 16
-            M32 = 0;
-#endif
             if (lane == 63u) M32 = 0;                             // lane 63 only looks ahead for lane 62
             return M32;
         };
@@ -946,7 +845,7 @@ void ts_scan_tiles(const TsScanParams P) {
         {                                                                                                                        \
             /* the chunk loop's last loads re-read the final chunk and are never used: told complete here (they are a chunk old),  \
                or every register of theirs that is written below waits for them AND for the loads requested here */               \
-            if (TS_ASM_STORES) __builtin_amdgcn_s_waitcnt(0x0F70);                                                                \
+            __builtin_amdgcn_s_waitcnt(0x0F70);                                                                                  \
             KernArgs Q = tail_params();                                                                                          \
             const bool dyn = Q->dynamic_tiles != 0u;                                                                             \
             tile_next = dyn ? group + Q->ticket_groups * (group_waves + (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket))   \
@@ -957,7 +856,9 @@ void ts_scan_tiles(const TsScanParams P) {
                 if (dyn && lane == 0) ticket = take_ticket(Q);      /* and the ticket for the tile after it */                   \
             }                                                                                                                    \
         }
-        if (!(EMIT && TS_EMIT_LATE_REQUEST)) TS_REQUEST_NEXT_TILE()
+        // (the emitting build requests its next tile at the start of phase 2 instead: -0.4 % on configs[1],
+        // profiles/r05/emit_ab_plain_emit_r04_r05_late_ffirst.txt)
+        if (!EMIT) TS_REQUEST_NEXT_TILE()
         drain_queue(1u);                          // the matches still queued when the tile ends
         __builtin_amdgcn_wave_barrier();          // planes written above are read by other lanes below
 
@@ -966,8 +867,8 @@ void ts_scan_tiles(const TsScanParams P) {
         // The match fields of the tile's window records are complete (accumulated above).
         // (the emitting build flushes — and looks at — the records BEHIND the window phase: its rows want thirty scalars of their own,
         // and between the chunk loop and the window phase they competed with both for registers: 110 more spill moves per tile)
-        if (EMIT ? !TS_EMIT_FINISH_LAST : !TS_PLAIN_FINISH_LAST) finish_records();
-        if (EMIT && TS_EMIT_LATE_REQUEST) TS_REQUEST_NEXT_TILE()
+        if (!EMIT) finish_records();
+        if (EMIT) TS_REQUEST_NEXT_TILE()
         if (P.windows_on) {
             // Nucleotides.  Counted here, from the tile's code plane, not per chunk: a row (a step block when w is a
             // multiple of s — a window is then the sum of w / s of them and overlapping windows share them — else a
@@ -1003,7 +904,7 @@ void ts_scan_tiles(const TsScanParams P) {
             // When w is a multiple of s rec[] holds one row per step block (the tile's windows + halo), otherwise one
             // per window.
             const bool by_blocks = P.block_sums != 0u;
-            if (P.nuc_on && !(TS_ABL & 2)) {
+            if (P.nuc_on) {
                 const uint32_t rows = by_blocks ? T.nwin + P.halo_blocks : T.nwin;
                 const uint32_t len = by_blocks ? P.s : P.w;
                 for (uint32_t it = lane; it < rows * 4u; it += 64u) rec[it] = 0u;
@@ -1060,7 +961,7 @@ void ts_scan_tiles(const TsScanParams P) {
                 // its own) — and nothing is written for the context tiles' windows, which nobody reads.  A lane per window.
                 KernArgs Q = tail_params();
                 const u64 T_win_out = const_tiles[tile].win_out;
-                if (T_win_out >= Q->win_pack_lo && T_win_out < Q->win_pack_hi && !(TS_ABL & 8)) {
+                if (T_win_out >= Q->win_pack_lo && T_win_out < Q->win_pack_hi) {
                     const uint32_t wb = Q->win_pack_bytes, B = Q->win_field_bits;
                     unsigned char *const dst0 = Q->win_packed + T_win_out * (u64)wb;
                     uint32_t ln = lane;
@@ -1103,7 +1004,7 @@ void ts_scan_tiles(const TsScanParams P) {
                         for (; b < wb; ++b) gstore(d + b, (unsigned char)(b < 8u ? lo >> (8u * b) : hi >> (8u * (b - 8u))));
                     }
                 }
-            } else if (!(TS_ABL & 8)) {
+            } else {
                 uint4 *wout = (uint4 *)(tail_params()->windows_out + const_tiles[tile].win_out * 8ull);
                 for (uint32_t it = lane; it < T.nwin * 2u; it += 64u) {
                     const uint32_t i = it >> 1;
@@ -1126,7 +1027,7 @@ void ts_scan_tiles(const TsScanParams P) {
             }
         }
 
-        if (EMIT ? TS_EMIT_FINISH_LAST : TS_PLAIN_FINISH_LAST) finish_records();
+        if (EMIT) finish_records();
         // ------------------------------------------------------- tile directory
         {
             const uint32_t tcan = ccan, tfwd = cfwd;
@@ -1134,7 +1035,7 @@ void ts_scan_tiles(const TsScanParams P) {
                 KernArgs Q = tail_params();
                 gstore((u64 *)&Q->tile_off[tile], (u64)gw * Q->region_cap + cursor);
                 const uint32_t vout = EMIT ? tile_vis : 0u;       // (the tile's chain summary left with its records: finish_records)
-                gstore((uint4 *)&Q->tile_stats[4ull * tile], make_uint4(done, tcan, tfwd, (TS_EXP & 8) ? (((uint32_t)wall_clock64() & 0xFFFFFu) | (gw << 20)) : vout));
+                gstore((uint4 *)&Q->tile_stats[4ull * tile], make_uint4(done, tcan, tfwd, vout));
             }
             cursor += done;
         }
@@ -1212,9 +1113,6 @@ const void *scan_variant_e(const TsScanParams *p) {
 }
 const void *scan_variant(const TsScanParams *p) { return p->emit ? scan_variant_e<true>(p) : scan_variant_e<false>(p); }
 }  // namespace
-
-// 1 when the emitting build knows kp.emit == 2 (see TS_READ_INDEX_BUILD)
-int ts_k_read_index_built(void) { return TS_READ_INDEX_BUILD; }
 
 int ts_k_prepare(uint32_t lds_bytes) {
     const void *fns[] = {(const void *)ts_scan_tiles<true, true, 4, false, false>, (const void *)ts_scan_tiles<true, false, 4, false, false>,

@@ -43,7 +43,6 @@ double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono
 
 uint64_t group_target_bytes() {
     static const uint64_t v = [] {
-        if (const char *e = getenv("TS_GROUP_MB")) { const long mb = atol(e); if (mb > 0) return (uint64_t)mb << 20; }
         // (with the packed upload a group's bases are staged in 128 MB chunks: larger groups, fewer hand-overs between the
         // stages — profiles/r03/packed_upload_rate.txt)
         const char *pk = getenv("TS_PACKED_UPLOAD");
@@ -257,7 +256,6 @@ int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, u
     }
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     unsigned nthr = std::min(8u, std::max(1u, hw / 2u));
-    if (c->knobs.stage_threads) nthr = c->knobs.stage_threads;
     // The staging threads live for the whole call, not for one 32 MB chunk (a chunk is staged in ~0.6 ms: spawning and
     // joining eight threads for each cost a tenth of the upload): job(t) runs on worker t, the caller is worker 0.
     struct StagePool {
@@ -640,7 +638,6 @@ int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, u
     Q.min_block_density = c->params.min_block_density;
     Q.k = c->k;
     Q.long_list = 128;                                        // floor of the per-wave threshold, see ts_terminal_predicate
-    const bool canon = b->emitted && b->kp.emit == 2u && !b->dense && b->all_terminal && b->d_chain.p && b->d_vis.p && !b->kp.vis_wide;
     if (d_ends) {
         const int e = ts_k_launch_terminal_ends((const TsTile *)b->d_tiles.p, (const unsigned long long *)b->d_tile_off.p,
                                                 b->stats_ptr(), b->records_ptr(), b->records_limit(), (const uint32_t *)dt,
@@ -660,10 +657,7 @@ int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, u
                                   // regions (16-byte aligned, 16 bytes of slack behind them: whole aligned blocks can be fetched)
                                   (b->all_terminal && !b->dense && ((uintptr_t)b->records_ptr() & 15u) == 0) ? 1 : 0,
                                   (const uint32_t *)b->d_fill.p, b->dense ? 0xFFFFFFFFu : b->region_cap, b->dense ? 0u : b->total_waves,
-                                  (uint32_t *)(dt + off_flag),
-                                  // (the scan left the canonical records' indices: the predicate visits only the chains that hold one)
-                                  canon ? (const uint32_t *)b->d_chain.p : nullptr, canon ? b->d_vis.p : nullptr, canon ? b->vis_cap : 0u,
-                                  b->records16() ? 1 : 0, st);
+                                  (uint32_t *)(dt + off_flag), b->records16() ? 1 : 0, st);
     if (e != 0) return c->fail(TS_ERR_HIP, "predicate kernel launch failed");
     return TS_OK;
 }
@@ -1008,12 +1002,12 @@ int submit_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &
 // Parameter sets outside the tiled kernel's closed form (mixed-length pattern sets, pattern lengths above 8, or a
 // longest pattern exceeding min(step, window-step) where the reference's uint32 start index wraps): the general
 // kernels of generic.hip over groups of ~256 MB of regions at a time — match masks, the records the reference pushes
-// and the window records all come off the device; the host orders the records by the window that pushes them (only
-// mixed-length sets can be out of position order at all), expands them and calls blocks (ts_finalize_segment).
+// and the window records all come off the device, and blocks are called on the device; the host expands the records and
+// converts the window records (ts_finalize_segment).
 std::atomic<uint64_t> ts_gen_ns[2];       // TS_TIMING: job time in record expansion / in ts_finalize_segment
 
-// blocks_only: the caller reads no match vectors (ts_scan_segments_blocks) — where the blocks can be called on the device
-// the match records then never leave it; counts (nullable): the sizes the vectors would have had.
+// blocks_only: the caller reads no match vectors (ts_scan_segments_blocks) — the match records then never leave the device;
+// counts (nullable): the sizes the vectors would have had.
 int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<size_t> &which,
                        bool tips, ts_segment_out *out, bool blocks_only = false, ts_segment_counts *counts = nullptr) {
     if (which.empty()) return TS_OK;
@@ -1029,7 +1023,6 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
     Q.s = s; Q.w = w; Q.longest = L; Q.nuc_on = (P.out_gc || P.out_entropy) ? 1u : 0u; Q.fold = P.fold_case;
     Q.s_magic = s >= 2u ? (uint32_t)((1ull << 32) / s + 1ull) : 0u;
     Q.cw = w / s; Q.rw = w - Q.cw * s;
-    Q.abl = c->knobs.gen_abl;
     const bool timing = c->knobs.timing;
     const auto t_begin = Clock::now();
     double t_dbg[3] = {0, 0, 0};
@@ -1043,16 +1036,15 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
     // smaller groups, because a tile's slot may have to grow to a record per position AND length
     const bool wide = c->gen_wide;
     const uint32_t rec_shift = wide ? 8u : 5u, rec_li_mask = wide ? 63u : 7u;
-    static const uint64_t wide_cap = []() -> uint64_t { if (const char *e = getenv("TS_WIDE_GROUP_MB")) { const long mb = atol(e); if (mb > 0) return (uint64_t)mb << 20; } return 256ull << 20; }();
-    const uint64_t target = wide ? std::min<uint64_t>(group_target_bytes(), wide_cap) : group_target_bytes();   // (16 - 64 KB of slot per tile: 4 - 17 GB per group)
+    const uint64_t target = wide ? std::min<uint64_t>(group_target_bytes(), 256ull << 20) : group_target_bytes();   // (16 - 64 KB of slot per tile: 4 - 17 GB per group)
     int slot = 0;
     bool used[ts_ctx::kUpSlots] = {false, false, false};
     size_t wi = 0;
-    // The host stage of group g (ordering + block calling on the host threads) runs on a background thread while the
+    // The host stage of group g (record expansion + window records on the host threads) runs on a background thread while the
     // device stage of group g + 1 (upload, kernels, D2H) runs here: what a group's host stage reads lives in a GroupHost.
     struct GroupHost { std::vector<SegL> G; std::vector<TsGeneralTile> tiles; std::vector<unsigned long long> tile_off;
                        std::vector<uint32_t> recs_heap, wins_heap; const uint32_t *recs = nullptr, *wins = nullptr;
-                       bool dev_blocks = false; std::vector<TsDevBlock> blocks; std::vector<unsigned long long> sums; };
+                       std::vector<TsDevBlock> blocks; std::vector<unsigned long long> sums; };
     // Block calling on the device (blockcall.hip with the general record formats).  The reference calls blocks over allMatches
     // as pushed (src/teloscope.cpp:485-509, :642-657): position order for tips-only scans, for w == s, and under w > s when the
     // pattern lengths differ by at most one (the record that ends later is never pushed earlier: end positions are monotone
@@ -1060,8 +1052,7 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
     // quite in position order: for those the compaction writes the dense stream IN PUSH ORDER
     // (ts_general_compact_push) and block calling walks it as the reference does (blockcall.hip, MODE 1: the predecessor as
     // the stream lies, the search range by stream index from a bisection restated probe by probe).  The host's expansion
-    // of such a stream needs no ordering pass either.  TS_GEN_HOST_BLOCKS=1 forces the round-4 route — position-ordered
-    // stream, ordering and block calling on the host — for A/B and tests.
+    // of such a stream needs no ordering pass either.
     const uint32_t len_spread = c->gen_wide ? (c->wide_lens.empty() ? 0u : c->wide_lens.back() - c->wide_lens.front())
                                             : (c->gpat.nlen ? c->gpat.len[c->gpat.nlen - 1] - c->gpat.len[0] : 0u);
     const bool position_order = tips || ov == 0 || len_spread <= 1u;      // position order IS push order
@@ -1069,10 +1060,7 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
     for (uint32_t li = 0; li < c->gpat.nlen && li < 8u; ++li) gen_lens |= (unsigned long long)(c->gpat.len[li] & 63u) << (6u * li);
     if (c->gpat.nlen && c->gpat.len[c->gpat.nlen - 1] > 63u) gen_lens = 0;
     if (c->gen_wide) gen_lens = 1ull;                                      // (wide records: the lengths come from wpat.len; non-zero = "general format")
-    const bool dev_blocks_ok = !c->knobs.gen_host_blocks && gen_lens != 0 && (c->gen_wide ? c->wpat.nlen >= 1 : c->gpat.nlen >= 1);
-    const bool push_compact = dev_blocks_ok && !position_order;           // the device orders the stream
-    const bool known_order = position_order || push_compact;               // what the host stage receives is in push order
-    const bool skip_records = blocks_only && dev_blocks_ok;
+    const bool push_compact = !position_order;                             // the device orders the stream
     size_t group_no = 0;
     std::thread host_job;
     std::atomic<int> host_err{TS_OK};
@@ -1087,7 +1075,6 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         int rc = TS_OK;
         double ms = 0;
     };
-    const bool prefetch = c->knobs.gen_prefetch;
     auto prepare = [&](Prepared &PR) -> int {
         // ---- a group of consecutive segments, ~256 MB of regions; layout = the regions back to back, 16-byte aligned
         PR.gh = std::make_shared<GroupHost>();
@@ -1168,7 +1155,7 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
             nxt.reset(new Prepared);
             Prepared *np = nxt.get();
             // (an exception on the thread — std::bad_alloc while planning a group — must come back as an error code, not end the process)
-            if (prefetch) pf = std::thread([&, np] {
+            pf = std::thread([&, np] {
                 try { c->bind_this_thread(); DeviceGuard g2(c->device); np->rc = prepare(*np); }
                 catch (const std::exception &e) { np->rc = c->fail(TS_ERR_ALLOC, std::string("general path: planning / upload of a group failed: ") + e.what()); }
             });
@@ -1259,7 +1246,7 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         // blocks only, over a stream in position order: block calling reads the records where the fused pass wrote them (it
         // addresses them through the tile directory), so there is no dense stream to make — every record used to be read and
         // written once more for nothing
-        const bool in_place = skip_records && !push_compact && !c->knobs.gen_compact_always;
+        const bool in_place = blocks_only && !push_compact;
         if (!in_place) HIP_TRY(c, c->pool.take(std::max<uint64_t>(nrec, 1) * 4, d_rec));
         const uint32_t *const d_records = in_place ? (const uint32_t *)d_slots.p : (const uint32_t *)d_rec.p;
         {
@@ -1275,14 +1262,14 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
                                                      w, s, len_spread, wide ? 1 : 0, gen_lens, wide ? c->wpat.len : nullptr, (uint32_t *)d_rec.p, st) != 0)
                     return c->fail(TS_ERR_HIP, "general push-order compact kernel launch failed");
                 // (records moved across tile borders: the host stage reads the offsets as they are now)
-                if (!skip_records) HIP_TRY(c, hipMemcpyAsync(tile_off.data(), d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
+                if (!blocks_only) HIP_TRY(c, hipMemcpyAsync(tile_off.data(), d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
             } else
             if (ts_k_launch_general_compact((const uint32_t *)d_stats.p, (const unsigned long long *)d_off.p, (const uint32_t *)d_slots.p,
                                             slot_cap, (uint32_t)nt, (uint32_t *)d_rec.p, st) != 0)
                 return c->fail(TS_ERR_HIP, "general compact kernel launch failed");
             if (timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
         }
-        if (dev_blocks_ok) {
+        {
             // ---- blocks on the device: the tiles as blockcall.hip addresses them, the canonical / forward counts, then the walks
             DevBuf d_bct, d_sbase;
             struct Ret2 { ts_ctx *c; DevBuf &a, &b2; ~Ret2() { c->pool.give(std::move(a)); c->pool.give(std::move(b2)); } } give2{c, d_bct, d_sbase};
@@ -1310,14 +1297,13 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
                                               d_records, nrec, segtab, nt, tips, gen_lens, nullptr, nullptr, st, gh->blocks, &gh->sums, 0,
                                               wide ? c->wpat.len : nullptr, push_compact);
             if (rc != TS_OK) return rc;
-            gh->dev_blocks = true;
         }
         const auto t_b = Clock::now();
         t_blk += ms_between(t_f, t_b);
         // landing area: the context's pinned download buffers, alternating by group (the host stage of group g reads
         // its buffer while group g + 1 lands in the other; it has been joined before group g + 2 arrives)
         {
-            const uint64_t nrec_dl = skip_records ? 0 : nrec;
+            const uint64_t nrec_dl = blocks_only ? 0 : nrec;
             const size_t rec_bytes = ((size_t)nrec_dl * 4 + 255) & ~(size_t)255, win_bytes = (size_t)nwin_total * 32;
             PinBuf &pb = c->pin_down[group_no & 1];
             ++group_no;
@@ -1342,10 +1328,10 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         const auto t2 = Clock::now();
         t_d2h += ms_between(t_b, t2);
         t_dev += ms_between(t1, t2);
-        // ---- host: records -> MatchInfo in the reference's push order, then block calling; one job per segment
+        // ---- host: records -> MatchInfo in the reference's push order, window records, the device's blocks; one job per segment
         if (host_job.joinable()) host_job.join();                     // (one host stage at a time: it takes all the host threads)
         if (host_err.load() != TS_OK) return host_err.load();
-        host_job = std::thread([c, gh, ns, tips, s, w, ov, out, counts, skip_records, timing, wide, rec_shift, rec_li_mask, known_order, &host_err, &t_host]() {
+        host_job = std::thread([c, gh, ns, tips, out, counts, blocks_only, timing, wide, rec_shift, rec_li_mask, &host_err, &t_host]() {
         try {
         const auto th0 = Clock::now();
         const std::vector<SegL> &G = gh->G;
@@ -1358,7 +1344,7 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         const unsigned spare = std::max(1u, std::min(16u, hw_threads) / (unsigned)std::max<size_t>(1, std::min<size_t>(ns, 16)));
         // the device-called blocks of the group, sorted by segment: where each segment's begin
         std::vector<size_t> blk_at(ns + 1, 0);
-        if (gh->dev_blocks) {
+        {
             size_t q = 0;
             for (size_t gi = 0; gi < ns; ++gi) {
                 blk_at[gi] = q;
@@ -1369,27 +1355,22 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         auto worker = [&]() {
             for (size_t gi; (gi = next.fetch_add(1)) < ns && first_err.load() == TS_OK;) {
                 const SegL &sl = G[gi];
-                const TsDevBlock *pre = gh->dev_blocks ? gh->blocks.data() + blk_at[gi] : nullptr;
-                const size_t n_pre = gh->dev_blocks ? blk_at[gi + 1] - blk_at[gi] : 0;
-                if (counts && gh->dev_blocks)
+                const TsDevBlock *pre = gh->blocks.data() + blk_at[gi];
+                const size_t n_pre = blk_at[gi + 1] - blk_at[gi];
+                if (counts)
                     counts[sl.idx] = ts_segment_counts{tips ? 0 : sl.n_windows, gh->sums[5 * gi + 2], gh->sums[5 * gi + 3], gh->sums[5 * gi + 4]};
-                if (skip_records) {
+                if (blocks_only) {
                     // windows + the device's blocks; the match records stayed on the device
                     const int rc = ts_finalize_segment(c, tips, sl.len, sl.abs_pos, sl.n_windows ? &wins[sl.win_base * 8] : nullptr,
-                                                       tips ? 0 : sl.n_windows, nullptr, 0, out[sl.idx], spare, pre, n_pre, true);
+                                                       tips ? 0 : sl.n_windows, nullptr, 0, out[sl.idx], spare, pre, n_pre);
                     if (rc != TS_OK) { int e = TS_OK; first_err.compare_exchange_strong(e, rc); return; }
                     continue;
                 }
                 const uint64_t r0 = tile_off[sl.first_tile], r1 = tile_off[sl.first_tile + sl.n_tiles], nm = r1 - r0;
                 ts_match *arr = nm ? (ts_match *)ts_alloc_large(nm * sizeof(ts_match)) : nullptr;
                 if (nm && !arr) { int e = TS_OK; first_err.compare_exchange_strong(e, c->fail(TS_ERR_ALLOC, "out of host memory")); return; }
-                // the window that pushes a match (src/teloscope.cpp:485): records must be in that order
-                auto push_window = [&](uint64_t p, uint32_t len) -> uint64_t {
-                    const uint64_t e = p + len - 1;
-                    return ov == 0 ? p / s : (e < std::min<uint64_t>(w, sl.len) ? 0 : (e - ov) / s);
-                };
                 // a segment's records are expanded by all the threads its job can spare (a group that holds ONE 250 Mb
-                // contig has one job): tile ranges of equal records, each thread checks the push order inside its range
+                // contig has one job): tile ranges of equal records, one per thread
                 const unsigned nth = nm >= (1u << 18) ? std::max(1u, std::min<unsigned>(spare, (unsigned)(nm >> 17))) : 1u;
                 std::vector<uint64_t> cut(nth + 1, sl.n_tiles);
                 cut[0] = 0;
@@ -1397,15 +1378,7 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
                     cut[q] = (uint64_t)(std::lower_bound(tile_off.begin() + sl.first_tile, tile_off.begin() + sl.first_tile + sl.n_tiles,
                                                          r0 + nm * q / nth) - (tile_off.begin() + sl.first_tile));
                 const auto tw0 = Clock::now();
-                std::vector<char> part_sorted(nth, 1);
-                std::vector<uint64_t> first_key(nth, 0), last_key(nth, 0);
-                // (a stream that is in the reference's push order by construction — tips-only scans, w == s, pattern lengths that
-                // differ by at most one: what device block calling relies on as well — is not checked at all)
-                const bool check_order = !tips && !known_order;
-                const uint64_t head_end = std::min<uint64_t>(w, sl.len);
                 auto expand = [&](unsigned q) {
-                    bool ok = true, any = false, have_base = false;
-                    uint64_t prev_k = 0, cur_k = 0, cur_base = 0;
                     for (uint64_t t = cut[q]; t < cut[q + 1]; ++t) {
                         const TsGeneralTile &T = tiles[sl.first_tile + t];
                         uint64_t at = tile_off[sl.first_tile + t] - r0;
@@ -1418,27 +1391,8 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
                             m.position = sl.abs_pos + p;
                             m.match_size = (uint16_t)len;
                             m.flags = (uint8_t)(((rec & 1u) ? TS_MATCH_FORWARD : 0u) | ((rec & 2u) ? TS_MATCH_CANONICAL : 0u));   // (general records: forward is bit 0)
-                            if (check_order) {
-                                // the pushing window without a division per record: the stream is in position order, so the quotient
-                                // of the record before is at most a step or two away
-                                uint64_t k = 0;
-                                const uint64_t e = p + len - 1;
-                                if (ov == 0 || e >= head_end) {
-                                    const uint64_t x = ov == 0 ? p : e - ov;
-                                    if (!have_base) { cur_k = x / s; cur_base = cur_k * s; have_base = true; }
-                                    while (x >= cur_base + s) { ++cur_k; cur_base += s; }
-                                    while (x < cur_base) { --cur_k; cur_base -= s; }
-                                    k = cur_k;
-                                }
-                                if (!any) { first_key[q] = k; any = true; }
-                                else if (k < prev_k) ok = false;
-                                prev_k = k;
-                            }
                         }
                     }
-                    part_sorted[q] = ok ? 1 : 0;
-                    last_key[q] = prev_k;
-                    if (!any) part_sorted[q] = 2;                                     // (an empty part)
                 };
                 if (nth <= 1) expand(0);
                 else {
@@ -1446,38 +1400,9 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
                     for (unsigned q = 0; q < nth; ++q) ex.emplace_back(expand, q);
                     for (std::thread &th : ex) th.join();
                 }
-                bool sorted = true;
-                {
-                    bool have_prev = false;
-                    uint64_t prev_last = 0;
-                    for (unsigned q = 0; q < nth; ++q) {                                 // (and the order across the parts' seams)
-                        if (part_sorted[q] == 2) continue;
-                        if (!part_sorted[q] || (have_prev && first_key[q] < prev_last)) sorted = false;
-                        prev_last = last_key[q];
-                        have_prev = true;
-                    }
-                }
-                if (!tips && !sorted) {
-                    // mixed-length sets: a long match near a window start is pushed by the NEXT window, after shorter
-                    // matches that begin behind it — order by pushing window, position order within it
-                    // The stream is in position order and a record's pushing window grows with its END position, so a record is
-                    // out of place by at most the few records that start within (longest - shortest) bases ahead of it: one
-                    // insertion pass, stable by construction (a record only moves behind records with a LARGER key), instead
-                    // of a stable_sort over an index array and a gather (0.7 s per 3 Gb on a nine-length set).
-                    std::vector<uint64_t> key(nm);
-                    for (uint64_t i = 0; i < nm; ++i) key[i] = push_window(arr[i].position - sl.abs_pos, arr[i].match_size);
-                    for (uint64_t i = 1; i < nm; ++i) {
-                        if (key[i] >= key[i - 1]) continue;
-                        const ts_match t = arr[i];
-                        const uint64_t kk = key[i];
-                        uint64_t j = i;
-                        while (j > 0 && key[j - 1] > kk) { arr[j] = arr[j - 1]; key[j] = key[j - 1]; --j; }
-                        arr[j] = t; key[j] = kk;
-                    }
-                }
                 const auto tw1 = Clock::now();
                 const int rc = ts_finalize_segment(c, tips, sl.len, sl.abs_pos, sl.n_windows ? &wins[sl.win_base * 8] : nullptr,
-                                                   tips ? 0 : sl.n_windows, arr, nm, out[sl.idx], spare, pre, n_pre, gh->dev_blocks);
+                                                   tips ? 0 : sl.n_windows, arr, nm, out[sl.idx], spare, pre, n_pre);
                 if (timing) { ts_gen_ns[0] += (uint64_t)(ms_between(tw0, tw1) * 1e6); ts_gen_ns[1] += (uint64_t)(ms_between(tw1, Clock::now()) * 1e6); }
                 if (rc != TS_OK) { int e = TS_OK; first_err.compare_exchange_strong(e, rc); return; }
             }
@@ -1493,11 +1418,10 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         t_host += ms_between(th0, Clock::now());
         } catch (...) { int e = TS_OK; host_err.compare_exchange_strong(e, c->fail(TS_ERR_ALLOC, "general path: the host stage ran out of memory")); }
         });
-        // ---- next group: already uploaded by the prefetch thread (or planned and uploaded here)
+        // ---- next group: already uploaded by the prefetch thread
         const auto t_w = Clock::now();
         if (pf.joinable()) pf.join();
         t_wait_next += ms_between(t_w, Clock::now());
-        if (nxt && !prefetch) nxt->rc = prepare(*nxt);
         cur = std::move(nxt);
     }
     if (host_job.joinable()) host_job.join();
@@ -1506,10 +1430,10 @@ int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<s
         fprintf(stderr, "general path: device stage: buffers %.1f ms, fused pass + tile offsets (synced) %.1f ms, compaction + block calling %.1f ms, D2H %.1f ms, waiting for the next group's upload %.1f ms (fused stage: enqueue %.1f, copies enqueue %.1f, sync %.1f)\n",
                 t_take, t_fused, t_blk, t_d2h, t_wait_next, t_dbg[0], t_dbg[1], t_dbg[2]);
     if (timing)
-        fprintf(stderr, "general path: route: %s form, blocks called on the %s, stream %s\n", wide ? "wide" : "table",
-                dev_blocks_ok ? "device" : "host", position_order ? "in position order" : push_compact ? "written in push order by the device" : "ordered on the host");
+        fprintf(stderr, "general path: route: %s form, blocks called on the device, stream %s\n", wide ? "wide" : "table",
+                position_order ? "in position order" : "written in push order by the device");
     if (timing)
-        fprintf(stderr, "general path: %zu segments, wall %.1f ms: upload %.1f ms, kernels + D2H %.1f ms (kernels alone, HIP events: %.2f ms), host ordering + block calling %.1f ms (on a thread of its own, one group behind; job time: expansion %.1f ms, windows + block calling %.1f ms)\n",
+        fprintf(stderr, "general path: %zu segments, wall %.1f ms: upload %.1f ms, kernels + D2H %.1f ms (kernels alone, HIP events: %.2f ms), host stage %.1f ms (on a thread of its own, one group behind; job time: expansion %.1f ms, windows + blocks %.1f ms)\n",
                 which.size(), ms_between(t_begin, Clock::now()), t_up, t_dev, (double)t_kern, t_host, ts_gen_ns[0].exchange(0) / 1e6, ts_gen_ns[1].exchange(0) / 1e6);
     return TS_OK;
 }

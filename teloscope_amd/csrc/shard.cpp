@@ -30,12 +30,6 @@
 
 #include "capi_internal.hpp"
 
-// Measurement only (-DTS_PACK_ABL=bits: results are wrong): 1 no terminal walks, 2 no visible-record copy, 8 no interstitial search,
-// 32 no header kernel — which of the pack's kernels costs the scan beside it what (profiles/r05_pack_abl.sh).
-#ifndef TS_PACK_ABL
-#define TS_PACK_ABL 0
-#endif
-
 namespace {
 
 uint32_t bit_width_u32(uint32_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b ? b : 1u; }
@@ -111,11 +105,10 @@ ShardRange shard_range(const ts_batch *b, uint32_t n_parts, uint32_t part) {
 // i + 1 — 0.95 ms per 3 Gb step instead of 0.85 (profiles/r05/shard_step_queues.txt); on a pack stream's queue it costs less.
 // So every stream a pack meets (the batch's scan stream, the pack's own) is tried once against the side stream
 // (ts_k_streams_concurrent: ~1 ms, and it waits for the work those streams hold); when they share a queue, up to eight fresh
-// streams are tried for one that runs beside every stream seen so far.  TS_SIDE_PROBE=0 keeps the first stream.
+// streams are tried for one that runs beside every stream seen so far.
 int side_stream_for(ts_ctx *c, void *scan_stream, void *pack_stream) {
     std::lock_guard<std::mutex> lk(c->side_mtx);
-    if (!c->side_stream) HIP_TRY(c, hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, c->knobs.side_priority));
-    if (!c->knobs.side_probe) return TS_OK;
+    if (!c->side_stream) HIP_TRY(c, hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, 0));
     for (void *s : {scan_stream, pack_stream}) {
         if (!s || std::find(c->side_tried.begin(), c->side_tried.end(), s) != c->side_tried.end()) continue;
         c->side_tried.push_back(s);                          // (tried once, whatever comes of it)
@@ -126,7 +119,7 @@ int side_stream_for(ts_ctx *c, void *scan_stream, void *pack_stream) {
         hipStream_t found = nullptr;
         for (int i = 0; i < 8 && !found; ++i) {
             hipStream_t cand = nullptr;
-            if (hipStreamCreateWithPriority(&cand, hipStreamNonBlocking, c->knobs.side_priority) != hipSuccess) break;
+            if (hipStreamCreateWithPriority(&cand, hipStreamNonBlocking, 0) != hipSuccess) break;
             fresh.push_back(cand);
             bool all = true;
             for (void *t : c->side_tried) {
@@ -354,7 +347,7 @@ int ts_batch_pack_shard(ts_batch *b, void *d_msg, uint64_t msg_bytes, void *stre
     Q.terminal_limit = P.terminal_limit; Q.max_match_dist = P.max_match_dist;
     Q.min_block_len = P.min_block_len; Q.max_block_dist = P.max_block_dist;
     Q.min_block_counts = P.min_block_counts; Q.min_block_density = P.min_block_density;
-    Q.k = c->k; Q.its_min_len = (uint32_t)(uint16_t)(2 * c->bp.first_pattern_len);
+    Q.k = c->k; Q.its_min_len = (uint32_t)(uint16_t)(2 * c->first_pattern_len);
     TsShardPackParams K{};
     K.tiles = Q.tiles; K.tile_off = Q.tile_off; K.tile_stats = Q.tile_stats; K.matches = Q.matches; K.rec16 = Q.rec16;
     K.windows = b->windows_ptr();
@@ -399,13 +392,13 @@ int ts_batch_pack_shard(ts_batch *b, void *d_msg, uint64_t msg_bytes, void *stre
     // where every tile's visible records go) and joins them.
     HIP_TRY(c, hipEventRecord(b->ev_fork, st));
     HIP_TRY(c, hipStreamWaitEvent(c->side_stream, b->ev_fork, 0));
-    if (!(TS_PACK_ABL & 1) && ts_k_launch_terminal(&Q, (const TsShardSegIn *)b->d_shard_segs.p, ns, (uint32_t)r.seg_begin, (uint32_t)b->range_tiles(),
+    if (ts_k_launch_terminal(&Q, (const TsShardSegIn *)b->d_shard_segs.p, ns, (uint32_t)r.seg_begin, (uint32_t)b->range_tiles(),
                              (unsigned long long *)b->d_shard_bounds.p, (TsShardSeg *)(msg + L.off_segs), c->side_stream) != 0)
         return c->fail(TS_ERR_HIP, "terminal block kernel launch failed");
     HIP_TRY(c, hipEventRecord(b->ev_join, c->side_stream));
     TsVisibleOut vis{};
     if (from_scan) {
-        if (!(TS_PACK_ABL & 2) && ts_k_launch_shard_visible(&K, &H, b->d_shard_tmp.p, 1, stream) != 0)
+        if (ts_k_launch_shard_visible(&K, &H, b->d_shard_tmp.p, 1, stream) != 0)
             return c->fail(TS_ERR_HIP, "visible-record kernel launch failed");
     } else if (ts_k_launch_shard_count(&K, &H, b->d_shard_tmp.p, b->tips ? 0 : 1, &vis, stream) != 0)
         return c->fail(TS_ERR_HIP, "shard count kernel launch failed");
@@ -419,11 +412,11 @@ int ts_batch_pack_shard(ts_batch *b, void *d_msg, uint64_t msg_bytes, void *stre
                                                nullptr, (TsShardSeg *)(msg + L.off_segs), 1, stream) != 0)
         return c->fail(TS_ERR_HIP, "segment sums kernel launch failed");
     HIP_TRY(c, hipStreamWaitEvent(st, b->ev_join, 0));
-    if (!(TS_PACK_ABL & 8) && !b->tips && ts_k_launch_interstitial(&Q, (const TsShardSegIn *)b->d_shard_segs.p, ns, (uint32_t)r.seg_begin, (uint32_t)b->range_tiles(),
+    if (!b->tips && ts_k_launch_interstitial(&Q, (const TsShardSegIn *)b->d_shard_segs.p, ns, (uint32_t)r.seg_begin, (uint32_t)b->range_tiles(),
                                              (const unsigned long long *)b->d_shard_bounds.p, (TsShardSeg *)(msg + L.off_segs), &vis,
                                              from_scan ? K.chain : nullptr, from_scan ? (uint32_t *)b->d_scan_tmp.p : nullptr, 1, stream) != 0)
         return c->fail(TS_ERR_HIP, "interstitial block kernel launch failed");
-    if (!(TS_PACK_ABL & 32) && ts_k_launch_shard_pack(&K, &H, b->d_shard_tmp.p, b->tips ? 0 : 1, stream) != 0)
+    if (ts_k_launch_shard_pack(&K, &H, b->d_shard_tmp.p, b->tips ? 0 : 1, stream) != 0)
         return c->fail(TS_ERR_HIP, "shard pack kernel launch failed");
     return TS_OK;
 }

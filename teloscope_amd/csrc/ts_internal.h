@@ -70,8 +70,7 @@ struct TsScanParams {
     uint32_t        ticket_groups;  // groups of workgroups with a counter each (<= 64; group g owns the tiles t = g mod groups)
     uint32_t        wgs_per_cu;     // host side: workgroups that share a CU (1, or 2 of 10 waves: selects the 80-VGPR build)
     // ---- what the scan hands to block calling and to a shard's message (window scans only; emit == 0: none of it)
-    uint32_t        emit;           // 1: visible records + per-tile chain summaries are produced; 2 (tips-only read batches): the indices of the
-                                    // canonical records among every tile's records instead, no summaries (vis_out, tile_chain words 2-3, tile_stats word 3 as for 1)
+    uint32_t        emit;           // 1: visible records + per-tile chain summaries are produced
     uint32_t        kdist;          // -k (maxMatchDistance): matches farther apart than this start a new chain
     uint32_t        vis_wide;       // 0: visible records are u16 (tile positions < 2^14), 1: u32
     uint32_t        vis_cap;        // visible records per wave region
@@ -275,8 +274,6 @@ struct TsWidePatterns {
 struct TsGenericGeom {
     uint32_t s, w, longest;
     uint32_t nuc_on, fold;
-    uint32_t abl;                       // TS_GEN_ABL (profiling): strided form: 1 no matching, 2 no window records, 4 no match records, 8 nothing
-                                        // after the table load; list form: 16 no candidates, 32 no per-candidate pass, 64 no window records
     uint32_t s_magic;                   // floor(2^32 / s) + 1 (s >= 2): x / s == umulhi(x, s_magic) for x < 2^32 / s (the list form, s <= 8192)
     uint32_t cw, rw;                    // w / s and w - cw s
 };
@@ -340,10 +337,7 @@ int  ts_k_launch_predicate(const TsTile *tiles, const unsigned long long *tile_o
                            const unsigned long long *seg_in_off, const unsigned long long *seg_len,
                            uint32_t nseg, const TsPredParams *Q, unsigned char *pass, uint32_t *long_list,
                            uint32_t *long_count, int all_terminal, const uint32_t *wave_fill, uint32_t region_cap,
-                           uint32_t nwaves, uint32_t *overflow, const uint32_t *chain, const void *canon_idx, uint32_t vis_cap, int rec16, void *stream);
-                           // (chain + canon_idx, both or neither: a read batch's scan left the indices of the canonical records — u16 each,
-                           //  per-wave regions of vis_cap, TsTileChain words 2-3 say where a tile's are, tile_stats word 3 how many — and
-                           //  the predicate visits only the chains that hold one)
+                           uint32_t nwaves, uint32_t *overflow, int rec16, void *stream);
                            // (nrec_limit: records that may be READ behind `matches` — the predicate fetches aligned 16-byte blocks;
                            //  long_list: nseg entries of scratch + long_count: one counter, for the reads a whole wave walks;
                            //  all_terminal: no segment is longer than the terminal limit — every read batch — the lean kernel;
@@ -406,7 +400,6 @@ int  ts_k_launch_tile_order_export(const uint32_t *tile_stats, const unsigned lo
 int  ts_k_launch_unpack(const void *packed, uint32_t first, void *dst, unsigned long long n, const void *runs, uint32_t nruns,
                         void *runs_base, void *stream);
 // exchange.hip: box calibration (see there)
-int  ts_k_read_index_built(void);      // kernels.hip: built with -DTS_READ_INDEX_BUILD=1 (the read filter's canonical-index experiment)
 int  ts_k_box_probe(void *scratch, unsigned long long bytes, int num_cu, double *issue_per_ns, double *copy_bytes_per_ns, void *stream);
 int  ts_k_launch_widen_u16(const uint16_t *src, uint32_t *dst, unsigned long long n, void *stream);
 int  ts_k_launch_compact(const uint32_t *regions, const uint32_t *wave_fill,

@@ -648,19 +648,21 @@ BLOCKCALL_GRID = ["-r -g -e -m -i", "-w 1000 -s 500 -r -g -e -m -i",
 
 # ... and through the general kernels (generic.hip): mixed pattern lengths — the match stream carries a length per record —
 # where the blocks are called on the device too (lengths at most one apart, w == s, tips-only), and a set with lengths 6 and
-# 14 under w > s, whose stream is not in the reference's calling order and keeps the host path
+# 14 under w > s, whose stream is not in position order (the device writes it in the reference's push order)
 GENERIC_BLOCKCALL_GRID = ["-p TTAGGG,TTAGG -w 1000 -s 500 -r -g -e -m -i", "-p TTAGGG,TTAGG,TTTAGGGTTTAGGG -x 1 -w 500 -s 500 -g -i",
                           "-p TTAGGG,TTAGG -t 400", "-c TTTAGGGTTTAGGG -x 1 -w 1000 -s 500 -r -g -i -k 80",
                           "-p TTAGGG,TTTAGGGTTTAGGG -x 0 -w 1000 -s 500 -r -g -i", "-w 1000 -s 997 -r -g -e -i"]
 
 
-@pytest.mark.parametrize("host_blocks", [False, True])
-@pytest.mark.parametrize("cli", GENERIC_BLOCKCALL_GRID)
-def test_general_path_block_calling_matches_oracle(cli, host_blocks, monkeypatch):
-    """The same through ts_scan_segments_blocks on parameter sets the general kernels take; host_blocks pins the host's block
-    calling (TS_GEN_HOST_BLOCKS=1) so that both ways are compared with the oracle on the same input."""
-    if host_blocks:
-        monkeypatch.setenv("TS_GEN_HOST_BLOCKS", "1")
+def kept_ids(grid):
+    """The ids these cases had while a host_blocks parameter also ran each set through the host's block calling (removed):
+    the device cases keep them."""
+    return [c + "-False" for c in grid]
+
+
+@pytest.mark.parametrize("cli", GENERIC_BLOCKCALL_GRID, ids=kept_ids(GENERIC_BLOCKCALL_GRID))
+def test_general_path_block_calling_matches_oracle(cli):
+    """The same through ts_scan_segments_blocks on parameter sets the general kernels take."""
     test_device_block_calling_matches_oracle(cli)
 
 
@@ -681,21 +683,16 @@ PUSH_ORDER_GRID = [
 ]
 
 
-@pytest.mark.parametrize("host_blocks", [False, True])
-@pytest.mark.parametrize("cli", PUSH_ORDER_GRID)
-def test_push_ordered_streams_blocks_match_oracle(cli, host_blocks, monkeypatch):
-    if host_blocks:
-        monkeypatch.setenv("TS_GEN_HOST_BLOCKS", "1")
+@pytest.mark.parametrize("cli", PUSH_ORDER_GRID, ids=kept_ids(PUSH_ORDER_GRID))
+def test_push_ordered_streams_blocks_match_oracle(cli):
     test_device_block_calling_matches_oracle(cli)
 
 
-def test_push_ordered_sets_take_the_device_route(monkeypatch, capfd):
-    """No parameter set is sent to the host's block calling any more unless TS_GEN_HOST_BLOCKS=1 asks for it (the library says
-    which route a general-path call took under TS_TIMING=1)."""
+def test_general_path_calls_blocks_on_the_device(monkeypatch, capfd):
+    """Every parameter set has its blocks called on the device (the library says which route a general-path call took under
+    TS_TIMING=1)."""
     monkeypatch.setenv("TS_TIMING", "1")
-    for cli, host in ((PUSH_ORDER_GRID[0], False), (PUSH_ORDER_GRID[5], False), (WIDE_GRID[3], False), (PUSH_ORDER_GRID[0], True)):
-        if host:
-            monkeypatch.setenv("TS_GEN_HOST_BLOCKS", "1")
+    for cli in (PUSH_ORDER_GRID[0], PUSH_ORDER_GRID[5], WIDE_GRID[3]):
         opts = H.parse_cli("x.fa " + cli)
         prod = ProductBackend(opts)
         rng = np.random.default_rng(3)
@@ -703,8 +700,8 @@ def test_push_ordered_sets_take_the_device_route(monkeypatch, capfd):
         capfd.readouterr()
         prod.teloscope.scanSegmentsBlocksOnly([(s, 0)], tipsOnly=False, with_counts=True)
         err = capfd.readouterr().err
-        assert ("blocks called on the host" in err) == host and ("blocks called on the device" in err) != host, err
-        if not host and cli in PUSH_ORDER_GRID:
+        assert "blocks called on the host" not in err and "blocks called on the device" in err, err
+        if cli in PUSH_ORDER_GRID:
             assert "written in push order by the device" in err, err
 
 
