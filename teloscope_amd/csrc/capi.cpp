@@ -9,6 +9,7 @@
 #include <atomic>
 #include <thread>
 #include <cstdio>
+#include <cstddef>
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
@@ -1288,95 +1289,45 @@ int ts_batch_segment_summary(ts_batch *b, void *d_out, void *stream) {
 
 }  // extern "C"
 
-// --------------------------------------------------------------- shared host post-processing
-// Turns one segment's raw results into SegmentData: window records (float metrics evaluated on
-// the host from the integer counts, as the reference does), terminal flags, and the blocks called on the
-// device (pre_blocks).  `matches` arrive with absolute positions and FORWARD/CANONICAL set.
-// `matches` (malloc'd by the caller, in push order, terminal flags not yet set; may be null when nm == 0)
-// becomes the segment's match array.
-int ts_finalize_segment(ts_ctx *c, bool tips, uint64_t seg_len, uint64_t abs_pos,
-                        const uint32_t *win_raw, uint64_t n_windows, ts_match *matches, uint64_t nm,
-                        ts_segment_out &o, unsigned spare_threads, const TsDevBlock *pre_blocks, size_t n_pre) {
-    const ts_params &P = c->params;
+// --------------------------------------------------------------- SegmentData assembly, shared by every route
+bool ts_alloc_segment(ts_segment_out &o, uint64_t n_windows, uint64_t n_matches) {
     std::memset(&o, 0, sizeof o);
-    if (!tips && n_windows) {
+    if (n_windows) {
         o.windows = (ts_window *)std::malloc(n_windows * sizeof(ts_window));
-        if (!o.windows) return c->fail(TS_ERR_ALLOC, "out of host memory");
+        if (!o.windows) return false;
         o.n_windows = n_windows;
-        const bool nuc = P.out_gc || P.out_entropy;
-        // windows are independent: a segment with very many of them (a multi-gigabase contig) is split over the
-        // host threads its job can spare
-        auto convert = [&](uint64_t k0, uint64_t k1) {
-        for (uint64_t kwin = k0; kwin < k1; ++kwin) {
-            const uint32_t *r = &win_raw[kwin * 8];
-            ts_window &w = o.windows[kwin];
-            std::memset(&w, 0, sizeof w);
-            const uint64_t ws = kwin * P.step;
-            w.window_start = abs_pos + ws;
-            w.current_window_size = (uint32_t)std::min<uint64_t>(P.window_size, seg_len - ws);
-            if (nuc) for (int i = 0; i < 4; ++i) w.nucleotide_counts[i] = r[i];
-            if (P.out_gc) w.gc_content = ts::gc_content(w.nucleotide_counts, w.current_window_size);
-            if (P.out_entropy) w.shannon_entropy = ts::shannon_entropy_memo(w.nucleotide_counts, w.current_window_size, c->entropy_term);
-            w.canonical_covered = r[4];
-            w.non_canonical_covered = r[5];
-            w.fwd_covered = r[6];
-            w.rev_covered = r[7];
-        }
+    }
+    if (n_matches) {
+        o.matches = (ts_match *)ts_alloc_large(n_matches * sizeof(ts_match));
+        if (!o.matches) return false;
+        o.n_matches = n_matches;
+    }
+    return true;
+}
+
+bool ts_split_blocks(const TsDevBlock *blocks, size_t n, ts_segment_out *out, size_t ns, size_t &placed) {
+    static_assert(offsetof(TsDevBlock, seg) == sizeof(ts_block), "a TsDevBlock begins with its ts_block");
+    size_t bi = 0;
+    for (size_t si = 0; si < ns; ++si) {
+        const size_t b0 = bi;
+        size_t nits = 0;
+        for (; bi < n && blocks[bi].seg == si; ++bi) nits += blocks[bi].kind == 2;
+        auto fill = [&](ts_block *&dst, uint64_t &count, size_t want, bool its) -> bool {
+            count = want; dst = nullptr;
+            if (!want) return true;
+            dst = (ts_block *)std::malloc(want * sizeof(ts_block));
+            if (!dst) return false;
+            size_t at = 0;
+            for (size_t q = b0; q < bi; ++q)
+                if ((blocks[q].kind == 2) == its) std::memcpy(&dst[at++], &blocks[q], sizeof(ts_block));
+            return true;
         };
-        const unsigned nth = n_windows >= (1u << 16) ? std::min<unsigned>(spare_threads, (unsigned)(n_windows >> 14)) : 1u;
-        if (nth <= 1u) {
-            convert(0, n_windows);
-        } else {
-            std::vector<std::thread> pool;
-            const uint64_t share = (n_windows + nth - 1) / nth;
-            for (unsigned t = 0; t < nth; ++t)
-                pool.emplace_back(convert, std::min<uint64_t>(n_windows, t * share), std::min<uint64_t>(n_windows, (t + 1) * share));
-            for (std::thread &th : pool) th.join();
-        }
+        if (!fill(out[si].terminal_blocks, out[si].n_terminal_blocks, bi - b0 - nits, false) ||
+            !fill(out[si].interstitial_blocks, out[si].n_interstitial_blocks, nits, true))
+            return false;
     }
-    if (nm > 0xFFFFFFFFull) { std::free(matches); return c->fail(TS_ERR_UNSUPPORTED, "more than 2^32 matches in one segment"); }
-    o.matches = nm ? matches : nullptr;
-    o.n_matches = nm;
-    if (!nm) std::free(matches);
-    const uint64_t term_end = seg_len > P.terminal_limit ? seg_len - P.terminal_limit : 0;
-    {
-        auto flag = [&](uint64_t i0, uint64_t i1) {
-            for (uint64_t i = i0; i < i1; ++i) {                    // isTerminal, src/teloscope.cpp:451-459
-                ts_match &m = o.matches[i];
-                const uint64_t rel = m.position - abs_pos;
-                if (rel <= P.terminal_limit || rel >= term_end) m.flags |= TS_MATCH_TERMINAL;
-            }
-        };
-        const unsigned nth = nm >= (1u << 20) ? std::max(1u, std::min<unsigned>(spare_threads, (unsigned)(nm >> 18))) : 1u;
-        if (nth <= 1u) flag(0, nm);
-        else {
-            std::vector<std::thread> pool;
-            const uint64_t share = (nm + nth - 1) / nth;
-            for (unsigned t = 0; t < nth; ++t)
-                pool.emplace_back(flag, std::min<uint64_t>(nm, t * share), std::min<uint64_t>(nm, (t + 1) * share));
-            for (std::thread &th : pool) th.join();
-        }
-    }
-    // the blocks were called on the device (sorted: terminal blocks in push order, then interstitial blocks by start)
-    std::vector<ts_block> term, its;
-    for (size_t q = 0; q < n_pre; ++q) {
-        ts_block b;
-        std::memcpy(&b, &pre_blocks[q], sizeof b);
-        (pre_blocks[q].kind == 2 ? its : term).push_back(b);
-    }
-    auto copy_blocks = [&](const std::vector<ts_block> &v, ts_block *&dst, uint64_t &n) -> bool {
-        n = v.size();
-        dst = nullptr;
-        if (v.empty()) return true;
-        dst = (ts_block *)std::malloc(v.size() * sizeof(ts_block));
-        if (!dst) return false;
-        std::memcpy(dst, v.data(), v.size() * sizeof(ts_block));
-        return true;
-    };
-    if (!copy_blocks(term, o.terminal_blocks, o.n_terminal_blocks) ||
-        !copy_blocks(its, o.interstitial_blocks, o.n_interstitial_blocks))
-        return c->fail(TS_ERR_ALLOC, "out of host memory");
-    return TS_OK;
+    placed = bi;
+    return true;
 }
 
 namespace {
@@ -1423,7 +1374,7 @@ static void expand_records_avx2(const uint32_t *recs, uint32_t cnt, ts_match *m,
     for (; i + 4 <= cnt; i += 4) {
         const __m256i r = _mm256_cvtepu32_epi64(_mm_loadu_si128((const __m128i *)(recs + i)));
         const __m256i rel = _mm256_add_epi64(vrel0, _mm256_srli_epi64(r, 2));
-        // terminal: rel <= limit or rel >= term_end  (positions are far below 2^63: signed compares)
+        // ts_is_terminal, four at a time: rel <= limit or rel >= term_end  (positions are far below 2^63: signed compares)
         const __m256i interior = _mm256_and_si256(_mm256_cmpgt_epi64(rel, vtl), _mm256_cmpgt_epi64(vte, _mm256_sub_epi64(rel, one)));
         // flags: forward (record bit 1) -> bit 0, canonical (record bit 0) -> bit 1, terminal -> bit 2; all shifted to bit 16
         const __m256i fwd = _mm256_slli_epi64(_mm256_and_si256(_mm256_srli_epi64(r, 1), one), 16);
@@ -1439,7 +1390,7 @@ static void expand_records_avx2(const uint32_t *recs, uint32_t cnt, ts_match *m,
         const uint32_t rec = recs[i];
         const uint64_t rel = rel0 + (rec >> 2);
         const uint64_t fl = ((rec & 2u) ? TS_MATCH_FORWARD : 0u) | ((rec & 1u) ? TS_MATCH_CANONICAL : 0u) |
-                            ((rel <= terminal_limit || rel >= term_end) ? TS_MATCH_TERMINAL : 0u);
+                            (ts_is_terminal(rel, terminal_limit, term_end) ? TS_MATCH_TERMINAL : 0u);
         _mm_stream_si128((__m128i *)&m[i], _mm_set_epi64x((long long)((uint64_t)klen | (fl << 16)), (long long)(abs_pos + rel)));
     }
 }
@@ -1451,7 +1402,7 @@ static void expand_records(const uint32_t *recs, uint32_t cnt, ts_match *m, uint
         const uint32_t rec = recs[i];
         const uint64_t rel = rel0 + (rec >> 2);
         const uint64_t fl = ((rec & 2u) ? TS_MATCH_FORWARD : 0u) | ((rec & 1u) ? TS_MATCH_CANONICAL : 0u) |
-                            ((rel <= terminal_limit || rel >= term_end) ? TS_MATCH_TERMINAL : 0u);
+                            (ts_is_terminal(rel, terminal_limit, term_end) ? TS_MATCH_TERMINAL : 0u);
         _mm_stream_si128((__m128i *)&m[i], _mm_set_epi64x((long long)((uint64_t)klen | (fl << 16)), (long long)(abs_pos + rel)));
     };
     uint32_t i = 0;
@@ -1473,26 +1424,6 @@ void *ts_alloc_large(size_t bytes) {
     (void)madvise(p, (bytes + kHuge - 1) & ~(kHuge - 1), MADV_HUGEPAGE);
     return p;
 }
-
-namespace {
-
-// f(i) for i in [0, n) on up to max_threads host threads (dynamic: an atomic counter hands out the indices)
-template <typename F>
-void parallel_for(size_t n, unsigned max_threads, F &&f) {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned nt = (unsigned)std::min<size_t>({(size_t)max_threads, (size_t)hw, n});
-    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < nt; ++t)
-        pool.emplace_back([&] { for (size_t i; (i = next.fetch_add(1)) < n;) f(i); });
-    for (std::thread &th : pool) th.join();
-}
-
-// Block calling ON THE DEVICE (getTerminalBlocks / getInterstitialBlocks, src/teloscope.cpp:29-256) over the
-// batch's resident match stream: the blocks of all segments, sorted by (segment; terminal blocks in push order:
-// forward walk then reverse walk; interstitial blocks by start).
-}  // namespace
 
 // Block calling on the device over ANY resident match stream addressed by a tile directory: the tiled kernel's (a batch) or the
 // general kernels' dense stream (gen_lens != 0: their record format and pattern lengths, ts_internal.h).  tab: the kernels'
@@ -1602,14 +1533,6 @@ int device_block_call(ts_batch *b, hipStream_t st, std::vector<TsDevBlock> &bloc
                                     b->records16() ? 1 : 0);
 }
 
-unsigned finalize_threads() {
-    static const unsigned v = [] {
-        if (const char *e = getenv("TS_HOST_THREADS")) { const int n = atoi(e); if (n > 0) return (unsigned)n; }
-        return 16u;
-    }();
-    return v;
-}
-
 // What a download leaves in host memory before post-processing.
 struct Fetched {
     std::unique_ptr<HostLanding> land;
@@ -1680,117 +1603,117 @@ int batch_fetch(ts_batch *b, bool with_matches, PinBuf &pin, Fetched &F) {
     return TS_OK;
 }
 
-// Host post-processing of a fetched batch: SegmentData per segment.  Everything is independent per window, per
-// tile and per block, so the work is cut into pieces of a few ten thousand records and spread over the host
-// threads whatever the segment sizes are (one 250 Mb contig keeps all threads busy): window records with their
-// float metrics (evaluated on the host from the integer counts, as the reference does), packed records ->
-// MatchInfo with absolute position and the terminal flag (isTerminal, src/teloscope.cpp:451-459), and the
-// device-called blocks.
-int batch_finalize(ts_batch *b, const Fetched &F, ts_segment_out *out) {
-    ts_ctx *c = b->ctx;
+// Record decoders of the assembler: a tile's cnt records -> m[0, cnt), at abs_pos + rel0 + the record's offset, the terminal
+// flag set.  The tiled kernel's: rec = (tile-relative position << 2) | forward << 1 | canonical, one pattern length.
+struct TiledRecords {
+    uint16_t klen;
+    void operator()(const uint32_t *recs, uint32_t cnt, ts_match *m, uint64_t abs_pos, uint64_t rel0, uint64_t terminal_limit,
+                    uint64_t term_end) const {
+        expand_records(recs, cnt, m, abs_pos, rel0, terminal_limit, term_end, klen);
+    }
+};
+
+// The general kernels': rec = (tile-relative position << shift) | length index << 2 | canonical << 1 | forward, the index into
+// gpat.len (shift 5, 3 bits) or, in the wide form, wide_lens (shift 8, 6 bits).
+struct GeneralRecords {
+    const uint32_t *lens;
+    uint32_t shift, li_mask;
+    void operator()(const uint32_t *recs, uint32_t cnt, ts_match *m, uint64_t abs_pos, uint64_t rel0, uint64_t terminal_limit,
+                    uint64_t term_end) const {
+        for (uint32_t i = 0; i < cnt; ++i) {
+            const uint32_t rec = recs[i];
+            const uint64_t rel = rel0 + (rec >> shift);
+            ts_match &o = m[i];
+            std::memset(&o, 0, sizeof o);
+            o.position = abs_pos + rel;
+            o.match_size = (uint16_t)lens[(rec >> 2) & li_mask];
+            o.flags = (uint8_t)(((rec & 1u) ? TS_MATCH_FORWARD : 0u) | ((rec & 2u) ? TS_MATCH_CANONICAL : 0u) |
+                                (ts_is_terminal(rel, terminal_limit, term_end) ? TS_MATCH_TERMINAL : 0u));
+        }
+    }
+};
+
+// SegmentData of every segment of a HostView.  Everything is independent per window, per tile and per block, so the work is
+// cut into pieces of a few ten thousand records and spread over the host threads whatever the segment sizes are (one 250 Mb
+// contig keeps all threads busy): window records, records -> MatchInfo with absolute position and the terminal flag, and
+// the device-called blocks.
+template <typename Decode>
+int assemble(ts_ctx *c, const HostView &v, const Decode &decode, ts_segment_out *out) {
     const ts_params &P = c->params;
-    const size_t ns = b->segs.size();
+    const size_t ns = v.segs.size();
     for (size_t i = 0; i < ns; ++i) std::memset(&out[i], 0, sizeof out[i]);
-    const bool nuc = P.out_gc || P.out_entropy;
-    // per-segment arrays
     std::vector<uint64_t> seg_nm(ns, 0);
-    std::vector<uint64_t> tile_out;                              // output index (within its segment's array) of a tile's first record
-    if (F.with_matches) {
-        tile_out.resize(b->tiles.size());
+    std::vector<uint64_t> tile_out(v.tiles.size());              // output index (within its segment's array) of a tile's first record
+    if (!v.tiles.empty()) {
         for (size_t si = 0; si < ns; ++si) {
-            const SegPlan &sp = b->segs[si];
+            const HostView::Seg &sg = v.segs[si];
             uint64_t nm = 0;
-            for (uint32_t t = 0; t < sp.n_tiles; ++t) { tile_out[sp.first_tile + t] = nm; nm += F.tile_stats[4ull * (sp.first_tile + t)]; }
+            for (uint64_t t = sg.first_tile; t < sg.first_tile + sg.n_tiles; ++t) { tile_out[t] = nm; nm += v.tiles[t].count; }
             if (nm > 0xFFFFFFFFull) return c->fail(TS_ERR_UNSUPPORTED, "more than 2^32 matches in one segment");
             seg_nm[si] = nm;
         }
     }
-    int rc = TS_OK;
-    for (size_t si = 0; si < ns && rc == TS_OK; ++si) {
-        const SegPlan &sp = b->segs[si];
-        if (!b->tips && sp.n_windows) {
-            out[si].windows = (ts_window *)std::malloc(sp.n_windows * sizeof(ts_window));
-            if (!out[si].windows) rc = c->fail(TS_ERR_ALLOC, "out of host memory");
-            out[si].n_windows = sp.n_windows;
+    for (size_t si = 0; si < ns; ++si)
+        if (!ts_alloc_segment(out[si], v.tips ? 0 : v.segs[si].n_windows, seg_nm[si])) {
+            ts_free_segments(out, ns);
+            return c->fail(TS_ERR_ALLOC, "out of host memory");
         }
-        if (rc == TS_OK && seg_nm[si]) {
-            out[si].matches = (ts_match *)ts_alloc_large(seg_nm[si] * sizeof(ts_match));
-            if (!out[si].matches) rc = c->fail(TS_ERR_ALLOC, "out of host memory");
-            out[si].n_matches = seg_nm[si];
-        }
-    }
-    if (rc != TS_OK) { ts_free_segments(out, ns); return rc; }
 
     struct Piece { uint32_t seg; bool windows; uint64_t a, z; };     // windows [a, z) of a segment, or its tiles [a, z)
     std::vector<Piece> pieces;
-    constexpr uint64_t kWinPiece = 1u << 13, kTilePiece = 64;
+    // (a piece fills about 2 MB of output: threads that fill the same huge page wait for each other's first touch of it)
+    constexpr uint64_t kWinPiece = 1u << 15, kRecPiece = 1u << 17;
     for (size_t si = 0; si < ns; ++si) {
-        const SegPlan &sp = b->segs[si];
-        if (!b->tips)
-            for (uint64_t a = 0; a < sp.n_windows; a += kWinPiece) pieces.push_back({(uint32_t)si, true, a, std::min<uint64_t>(sp.n_windows, a + kWinPiece)});
+        const HostView::Seg &sg = v.segs[si];
+        if (!v.tips)
+            for (uint64_t a = 0; a < sg.n_windows; a += kWinPiece) pieces.push_back({(uint32_t)si, true, a, std::min<uint64_t>(sg.n_windows, a + kWinPiece)});
         if (seg_nm[si])
-            for (uint64_t a = 0; a < sp.n_tiles; a += kTilePiece) pieces.push_back({(uint32_t)si, false, a, std::min<uint64_t>(sp.n_tiles, a + kTilePiece)});
+            for (uint64_t a = 0, z = 0; a < sg.n_tiles; a = z) {
+                uint64_t nrec = 0;
+                for (z = a; z < sg.n_tiles && nrec < kRecPiece; ++z) nrec += v.tiles[sg.first_tile + z].count;
+                pieces.push_back({(uint32_t)si, false, a, z});
+            }
     }
-    const uint16_t klen = (uint16_t)c->k;
     std::atomic<int> bad{0};
-    parallel_for(pieces.size(), finalize_threads(), [&](size_t pi) {
+    ts_parallel_for(pieces.size(), ts_host_threads(), [&](size_t pi) {
         const Piece &pc = pieces[pi];
-        const SegPlan &sp = b->segs[pc.seg];
+        const HostView::Seg &sg = v.segs[pc.seg];
         ts_segment_out &o = out[pc.seg];
         if (pc.windows) {
-            for (uint64_t kwin = pc.a; kwin < pc.z; ++kwin) {
-                const uint32_t *r = &F.wins[(sp.win_base + kwin) * 8];
-                ts_window &w = o.windows[kwin];
-                std::memset(&w, 0, sizeof w);
-                const uint64_t ws = kwin * P.step;
-                w.window_start = sp.abs_pos + ws;
-                w.current_window_size = (uint32_t)std::min<uint64_t>(P.window_size, sp.len - ws);
-                if (nuc) for (int i = 0; i < 4; ++i) w.nucleotide_counts[i] = r[i];
-                if (P.out_gc) w.gc_content = ts::gc_content(w.nucleotide_counts, w.current_window_size);
-                if (P.out_entropy) w.shannon_entropy = ts::shannon_entropy_memo(w.nucleotide_counts, w.current_window_size, c->entropy_term);
-                w.canonical_covered = r[4];
-                w.non_canonical_covered = r[5];
-                w.fwd_covered = r[6];
-                w.rev_covered = r[7];
-            }
+            for (uint64_t kwin = pc.a; kwin < pc.z; ++kwin) ts_fill_window(c, kwin, sg.len, sg.abs_pos, &v.wins[(sg.win_base + kwin) * 8], o.windows[kwin]);
             return;
         }
-        const uint64_t term_end = sp.len > P.terminal_limit ? sp.len - P.terminal_limit : 0;
+        const uint64_t term_end = ts_terminal_end(sg.len, P.terminal_limit);
         for (uint64_t t = pc.a; t < pc.z; ++t) {
-            const size_t ti = sp.first_tile + t;
-            const uint32_t cnt = F.tile_stats[4ull * ti];
-            if (!cnt) continue;
-            const uint64_t r0 = F.tile_off[ti];
-            if (r0 + cnt > F.nrecs) { bad.store(1); return; }
-            const uint64_t rel0 = b->tiles[ti].in_off - sp.in_off;          // segment-relative position of the tile
-            expand_records(F.recs + r0, cnt, o.matches + tile_out[ti], sp.abs_pos, rel0, P.terminal_limit, term_end, klen);
+            const size_t ti = sg.first_tile + t;
+            const HostView::Tile &T = v.tiles[ti];
+            if (!T.count) continue;
+            if (T.rec_off + T.count > v.nrecs) { bad.store(1); return; }
+            decode(v.recs + T.rec_off, T.count, o.matches + tile_out[ti], sg.abs_pos, T.rel, P.terminal_limit, term_end);
         }
         _mm_sfence();
     });
     if (bad.load()) { ts_free_segments(out, ns); return c->fail(TS_ERR_STATE, "tile directory out of range"); }
-    // blocks: the sorted list's slice of every segment
-    size_t bi = 0;
-    for (size_t si = 0; si < ns; ++si) {
-        size_t nterm = 0, nits = 0;
-        const size_t b0 = bi;
-        while (bi < F.blocks.size() && F.blocks[bi].seg == si) { (F.blocks[bi].kind == 2 ? nits : nterm)++; ++bi; }
-        auto fill = [&](ts_block *&dst, uint64_t &n, size_t count, bool its) -> bool {
-            n = count; dst = nullptr;
-            if (!count) return true;
-            dst = (ts_block *)std::malloc(count * sizeof(ts_block));
-            if (!dst) return false;
-            size_t at = 0;
-            for (size_t q = b0; q < bi; ++q)
-                if ((F.blocks[q].kind == 2) == its) std::memcpy(&dst[at++], &F.blocks[q], sizeof(ts_block));
-            return true;
-        };
-        if (!fill(out[si].terminal_blocks, out[si].n_terminal_blocks, nterm, false) ||
-            !fill(out[si].interstitial_blocks, out[si].n_interstitial_blocks, nits, true)) {
-            ts_free_segments(out, ns);
-            return c->fail(TS_ERR_ALLOC, "out of host memory");
-        }
-    }
+    size_t placed = 0;
+    if (!ts_split_blocks(v.blocks, v.n_blocks, out, ns, placed)) { ts_free_segments(out, ns); return c->fail(TS_ERR_ALLOC, "out of host memory"); }
     return TS_OK;
+}
+
+// Host post-processing of a fetched batch: its view, the tiled kernel's records.
+int batch_finalize(ts_batch *b, const Fetched &F, ts_segment_out *out) {
+    HostView v;
+    v.tips = b->tips;
+    v.wins = F.wins; v.recs = F.recs; v.nrecs = F.nrecs;
+    v.blocks = F.blocks.data(); v.n_blocks = F.blocks.size();
+    v.segs.reserve(b->segs.size());
+    for (const SegPlan &sp : b->segs) v.segs.push_back({sp.len, sp.abs_pos, sp.win_base, sp.n_windows, sp.first_tile, sp.n_tiles});
+    if (F.with_matches) {
+        v.tiles.resize(b->tiles.size());
+        for (const SegPlan &sp : b->segs)
+            for (uint64_t ti = sp.first_tile; ti < sp.first_tile + sp.n_tiles; ++ti)      // (rel: the segment-relative position of the tile)
+                v.tiles[ti] = {F.tile_off[ti], b->tiles[ti].in_off - sp.in_off, F.tile_stats[4 * ti]};
+    }
+    return assemble(b->ctx, v, TiledRecords{(uint16_t)b->ctx->k}, out);
 }
 
 int download_impl(ts_batch *b, ts_segment_out *out, bool with_matches) {
@@ -1807,6 +1730,19 @@ int download_impl(ts_batch *b, ts_segment_out *out, bool with_matches) {
 }
 
 }  // namespace
+
+unsigned ts_host_threads() {
+    static const unsigned v = [] {
+        if (const char *e = getenv("TS_HOST_THREADS")) { const int n = atoi(e); if (n > 0) return (unsigned)n; }
+        return 16u;
+    }();
+    return v;
+}
+
+int ts_assemble_general(ts_ctx *c, const HostView &v, ts_segment_out *out) {
+    const GeneralRecords decode = c->gen_wide ? GeneralRecords{c->wide_lens.data(), 8u, 63u} : GeneralRecords{c->gpat.len, 5u, 7u};
+    return assemble(c, v, decode, out);
+}
 
 // the two phases of a download, for the host entry points' pipeline (pipeline.cpp): device work + D2H into the
 // pinned landing area `slot` of the context, then host post-processing (which may run while the next group's

@@ -5,11 +5,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
 #include <deque>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -292,9 +296,66 @@ int  ts_pipeline_upload_batch(ts_batch *b, const ts_segment_in *segs, int *slot,
 // capi.cpp internals used by pipeline.cpp
 bool ts_full_scan_supported(const ts_ctx *c, std::string &why);
 void *ts_alloc_large(size_t bytes);     // malloc-compatible; many-MB arrays on 2 MB pages when the kernel grants them
-int  ts_finalize_segment(ts_ctx *c, bool tips, uint64_t seg_len, uint64_t abs_pos, const uint32_t *win_raw,
-                         uint64_t n_windows, ts_match *matches, uint64_t nm, ts_segment_out &o, unsigned spare_threads,
-                         const TsDevBlock *pre_blocks, size_t n_pre);   // pre_blocks: the segment's blocks, called on the device
+
+// --------------------------------------------------------------- SegmentData assembly (capi.cpp), shared by every route
+unsigned ts_host_threads();             // host threads of a download's post-processing: TS_HOST_THREADS, default 16
+
+// f(i) for i in [0, n) on up to max_threads host threads (dynamic: an atomic counter hands out the indices)
+template <typename F>
+void ts_parallel_for(size_t n, unsigned max_threads, F &&f) {
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const unsigned nt = (unsigned)std::min<size_t>({(size_t)max_threads, (size_t)hw, n});
+    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
+    std::atomic<size_t> next{0};
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < nt; ++t)
+        pool.emplace_back([&] { for (size_t i; (i = next.fetch_add(1)) < n;) f(i); });
+    for (std::thread &th : pool) th.join();
+}
+
+// isTerminal (src/teloscope.cpp:451-459) of a segment-relative position; term_end = ts_terminal_end(segment length, limit)
+inline uint64_t ts_terminal_end(uint64_t seg_len, uint64_t terminal_limit) { return seg_len > terminal_limit ? seg_len - terminal_limit : 0; }
+inline bool ts_is_terminal(uint64_t rel, uint64_t terminal_limit, uint64_t term_end) { return rel <= terminal_limit || rel >= term_end; }
+
+// Window kwin of a segment from its eight counts {A, C, G, T, canonical, non-canonical, forward, reverse covered}: the float
+// metrics are evaluated on the host from the integer counts, as the reference does
+inline void ts_fill_window(const ts_ctx *c, uint64_t kwin, uint64_t seg_len, uint64_t abs_pos, const uint32_t r[8], ts_window &w) {
+    const ts_params &P = c->params;
+    std::memset(&w, 0, sizeof w);
+    const uint64_t ws = kwin * P.step;
+    w.window_start = abs_pos + ws;
+    w.current_window_size = (uint32_t)std::min<uint64_t>(P.window_size, seg_len - ws);
+    if (P.out_gc || P.out_entropy) for (int i = 0; i < 4; ++i) w.nucleotide_counts[i] = r[i];
+    if (P.out_gc) w.gc_content = ts::gc_content(w.nucleotide_counts, w.current_window_size);
+    if (P.out_entropy) w.shannon_entropy = ts::shannon_entropy_memo(w.nucleotide_counts, w.current_window_size, c->entropy_term);
+    w.canonical_covered = r[4];
+    w.non_canonical_covered = r[5];
+    w.fwd_covered = r[6];
+    w.rev_covered = r[7];
+}
+
+// A segment's windows / matches arrays (o zeroed first); false when out of host memory
+bool ts_alloc_segment(ts_segment_out &o, uint64_t n_windows, uint64_t n_matches);
+// The blocks of segments [0, ns), sorted by segment and within one terminal blocks before interstitial ones, into each
+// segment's two arrays.  placed: the blocks consumed (fewer than n when one names a segment >= ns).  false when out of memory.
+bool ts_split_blocks(const TsDevBlock *blocks, size_t n, ts_segment_out *out, size_t ns, size_t &placed);
+
+// What landed on the host for piece-parallel assembly: per segment its windows (8 x u32 each, at win_base of `wins`) and a
+// range of tiles; per tile its records (rec_off, count: a run of `recs`) and the segment-relative position they are relative to.
+struct HostView {
+    struct Seg { uint64_t len, abs_pos, win_base, n_windows, first_tile, n_tiles; };
+    struct Tile { uint64_t rec_off, rel; uint32_t count; };
+    std::vector<Seg> segs;
+    std::vector<Tile> tiles;                 // empty: no match vectors
+    const uint32_t *wins = nullptr, *recs = nullptr;
+    uint64_t nrecs = 0;
+    bool tips = false;
+    const TsDevBlock *blocks = nullptr;      // sorted as ts_split_blocks reads them
+    size_t n_blocks = 0;
+};
+// SegmentData from the general kernels' records (pipeline.cpp's general path) to out[0, v.segs.size()); frees it on failure
+int  ts_assemble_general(ts_ctx *c, const HostView &v, ts_segment_out *out);
+
 int  ts_batch_ensure_device(ts_batch *b);        // allocates the range's device state (idempotent)
 // block calling on the device over a resident match stream + tile directory (a batch's, or the general kernels' dense stream)
 int  ts_device_block_call_raw(ts_ctx *c, const TsTile *d_tiles, const unsigned long long *d_tile_off, const uint32_t *d_stats,

@@ -86,6 +86,18 @@ enum class Mode { Matches, Blocks, ReadPass, Ends };   // Ends: ts_terminal_ends
 
 struct Item { const char *seq; uint64_t len, abs_pos; uint8_t format; uint32_t n_pieces; };     // format: TS_INPUT_BASES / TS_INPUT_TEXT_PIECES (seq = ts_text_piece[])
 
+// Where a call's results go, at the items' indices; null = not asked for.  out: Matches / Blocks; counts: Blocks (optional);
+// pass: ReadPass; ends: Ends (two per item).
+struct Outputs {
+    ts_segment_out *out = nullptr;
+    ts_segment_counts *counts = nullptr;
+    uint8_t *pass = nullptr;
+    uint32_t *ends = nullptr;
+    Outputs slice(size_t at) const {
+        return {out ? out + at : nullptr, counts ? counts + at : nullptr, pass ? pass + at : nullptr, ends ? ends + 2 * at : nullptr};
+    }
+};
+
 struct Group {
     size_t first = 0, count = 0;                  // items [first, first + count) of the call's item list
     ts_batch *b = nullptr;
@@ -603,6 +615,14 @@ int upload_batch(ts_batch *b, const Item *items, int &slot, bool used[]) {
     return upload_pieces(c, pieces, din, b->in_lo, slot, used);
 }
 
+// Layout of a tips batch's per-read table (d_readtab): the first tile of every read (and the end), in_off and len per read, then
+// the list of long reads, its counter and the overflow flag
+struct ReadTab {
+    size_t in, len, long_list, count, flag, bytes;
+    explicit ReadTab(size_t ns) : in(((ns + 1) * 4 + 15) & ~(size_t)15), len(in + ns * 8), long_list(len + ns * 8),
+                                  count((long_list + ns * 4 + 15) & ~(size_t)15), flag(count + 16), bytes(flag + 16) {}
+};
+
 // The terminal-block predicate of a scanned tips batch on the device: one byte per read
 // (ReadTelomereFilter::matches, src/read-filter.cpp:37-45, reduced to !terminalBlocks.empty()), written to
 // d_pass (device).  The per-read table the kernel walks is built once per batch.
@@ -612,20 +632,19 @@ int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, u
     ts_ctx *c = b->ctx;
     const size_t ns = b->segs.size();
     if (!ns) return TS_OK;
-    const size_t off_in = (((ns + 1) * 4 + 15) & ~(size_t)15), off_len = off_in + ns * 8, off_long = off_len + ns * 8,
-                 off_count = (off_long + ns * 4 + 15) & ~(size_t)15, off_flag = off_count + 16, bytes = off_flag + 16;   // + the list of long reads, its counter, the overflow flag
+    const ReadTab T(ns);
     if (!b->d_readtab.p) {
-        std::vector<char> tab(bytes);
+        std::vector<char> tab(T.bytes);
         for (size_t i = 0; i < ns; ++i) {
             ((uint32_t *)tab.data())[i] = b->segs[i].first_tile;
-            ((unsigned long long *)(tab.data() + off_in))[i] = b->segs[i].in_off;
-            ((unsigned long long *)(tab.data() + off_len))[i] = b->segs[i].len;
+            ((unsigned long long *)(tab.data() + T.in))[i] = b->segs[i].in_off;
+            ((unsigned long long *)(tab.data() + T.len))[i] = b->segs[i].len;
         }
         ((uint32_t *)tab.data())[ns] = (uint32_t)b->tiles.size();
         b->all_terminal = true;                                   // every segment terminal zone as a whole: the lean predicate kernel
         for (size_t i = 0; i < ns; ++i) if (b->segs[i].len > c->params.terminal_limit) b->all_terminal = false;
-        HIP_TRY(c, c->pool.take(bytes, b->d_readtab));
-        HIP_TRY(c, hipMemcpyAsync(b->d_readtab.p, tab.data(), bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, c->pool.take(T.bytes, b->d_readtab));
+        HIP_TRY(c, hipMemcpyAsync(b->d_readtab.p, tab.data(), T.bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipStreamSynchronize(st));                    // (tab is a local)
     }
     char *const dt = (char *)b->d_readtab.p;
@@ -638,27 +657,20 @@ int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, u
     Q.min_block_density = c->params.min_block_density;
     Q.k = c->k;
     Q.long_list = 128;                                        // floor of the per-wave threshold, see ts_terminal_predicate
-    if (d_ends) {
-        const int e = ts_k_launch_terminal_ends((const TsTile *)b->d_tiles.p, (const unsigned long long *)b->d_tile_off.p,
-                                                b->stats_ptr(), b->records_ptr(), b->records_limit(), (const uint32_t *)dt,
-                                                (const unsigned long long *)(dt + off_in), (const unsigned long long *)(dt + off_len),
-                                                (uint32_t)ns, &Q, d_ends, (uint32_t *)(dt + off_long), (uint32_t *)(dt + off_count),
-                                                (b->all_terminal && !b->dense && ((uintptr_t)b->records_ptr() & 15u) == 0) ? 1 : 0,
-                                                (const uint32_t *)b->d_fill.p, b->dense ? 0xFFFFFFFFu : b->region_cap, b->dense ? 0u : b->total_waves,
-                                                (uint32_t *)(dt + off_flag), b->records16() ? 1 : 0, st);
-        if (e != 0) return c->fail(TS_ERR_HIP, "terminal-ends kernel launch failed");
-        return TS_OK;
-    }
-    int e = ts_k_launch_predicate((const TsTile *)b->d_tiles.p, (const unsigned long long *)b->d_tile_off.p,
-                                  b->stats_ptr(), b->records_ptr(), b->records_limit(), (const uint32_t *)dt,
-                                  (const unsigned long long *)(dt + off_in), (const unsigned long long *)(dt + off_len),
-                                  (uint32_t)ns, &Q, d_pass, (uint32_t *)(dt + off_long), (uint32_t *)(dt + off_count),
-                                  // the lean kernel: every segment terminal zone as a whole, and the records in the batch's own
-                                  // regions (16-byte aligned, 16 bytes of slack behind them: whole aligned blocks can be fetched)
-                                  (b->all_terminal && !b->dense && ((uintptr_t)b->records_ptr() & 15u) == 0) ? 1 : 0,
-                                  (const uint32_t *)b->d_fill.p, b->dense ? 0xFFFFFFFFu : b->region_cap, b->dense ? 0u : b->total_waves,
-                                  (uint32_t *)(dt + off_flag), b->records16() ? 1 : 0, st);
-    if (e != 0) return c->fail(TS_ERR_HIP, "predicate kernel launch failed");
+    // the predicate's or the ends' launcher: the same walks and arguments, one byte or two u32 per segment out
+    auto launch = [&](auto launcher, auto *dst) {
+        return launcher((const TsTile *)b->d_tiles.p, (const unsigned long long *)b->d_tile_off.p,
+                        b->stats_ptr(), b->records_ptr(), b->records_limit(), (const uint32_t *)dt,
+                        (const unsigned long long *)(dt + T.in), (const unsigned long long *)(dt + T.len),
+                        (uint32_t)ns, &Q, dst, (uint32_t *)(dt + T.long_list), (uint32_t *)(dt + T.count),
+                        // the lean kernel: every segment terminal zone as a whole, and the records in the batch's own
+                        // regions (16-byte aligned, 16 bytes of slack behind them: whole aligned blocks can be fetched)
+                        (b->all_terminal && !b->dense && ((uintptr_t)b->records_ptr() & 15u) == 0) ? 1 : 0,
+                        (const uint32_t *)b->d_fill.p, b->dense ? 0xFFFFFFFFu : b->region_cap, b->dense ? 0u : b->total_waves,
+                        (uint32_t *)(dt + T.flag), b->records16() ? 1 : 0, st);
+    };
+    if ((d_ends ? launch(ts_k_launch_terminal_ends, d_ends) : launch(ts_k_launch_predicate, d_pass)) != 0)
+        return c->fail(TS_ERR_HIP, d_ends ? "terminal-ends kernel launch failed" : "predicate kernel launch failed");
     return TS_OK;
 }
 
@@ -698,15 +710,13 @@ int batch_terminal_ends(ts_batch *b, uint32_t *ends_out, int slot, hipStream_t s
     HIP_TRY(c, c->pool.take(ns * 8 + 16, d_ends));
     int rc = batch_read_pass_device(b, nullptr, st, (uint32_t *)d_ends.p);
     if (rc != TS_OK) return rc;
-    const size_t off_in = (((ns + 1) * 4 + 15) & ~(size_t)15), off_len = off_in + ns * 8, off_long = off_len + ns * 8,
-                 off_count = (off_long + ns * 4 + 15) & ~(size_t)15, off_flag = off_count + 16;      // (batch_read_pass_device's table)
-    char *const dt = (char *)b->d_readtab.p;
+    char *const flag_at = (char *)b->d_readtab.p + ReadTab(ns).flag;
     uint32_t flag = 0;
     HIP_TRY(c, hipMemcpyAsync(ends_out, d_ends.p, ns * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&flag, dt + off_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&flag, flag_at, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (!flag) return TS_OK;
-    HIP_TRY(c, hipMemsetAsync(dt + off_flag, 0, 4, st));
+    HIP_TRY(c, hipMemsetAsync(flag_at, 0, 4, st));
     ts_fetched *f = ts_batch_fetch(b, false, slot, &rc);
     std::vector<ts_segment_out> tmp(ns);
     if (rc == TS_OK) rc = ts_batch_finalize(b, f, tmp.data());
@@ -733,9 +743,8 @@ int batch_counts(ts_batch *b, ts_segment_counts *counts, bool tips, hipStream_t 
 }
 
 // The three-stage pipeline over the groups of one call.  items: the call's segments or reads in input order;
-// results go to out / counts / pass at the same indices.
-int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, ts_segment_out *out,
-                 ts_segment_counts *counts, uint8_t *pass, uint32_t *ends = nullptr) {
+// results go to o at the same indices.
+int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, Outputs o) {
     if (items.empty()) return TS_OK;
     if (ctx->device == kNoDevice) return ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it");
     const auto t_begin = Clock::now();
@@ -847,22 +856,23 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
             const auto t0 = Clock::now();
             int rc = first_err.load();
             if (rc == TS_OK) gr->b->last_stream = ctx->down_stream;   // the scan is complete (synced): later work runs on this stage's stream
+            const Outputs go = o.slice(gr->first);
             if (rc == TS_OK && mode == Mode::ReadPass) {
-                rc = batch_read_pass(gr->b, pass + gr->first, ctx->down_stream);
+                rc = batch_read_pass(gr->b, go.pass, ctx->down_stream);
             } else if (rc == TS_OK && mode == Mode::Ends) {
-                rc = batch_terminal_ends(gr->b, ends + 2 * gr->first, slot, ctx->down_stream);
+                rc = batch_terminal_ends(gr->b, go.ends, slot, ctx->down_stream);
             } else if (rc == TS_OK) {
                 // device work + D2H of this group while the previous group's records are expanded on the host threads
                 ts_fetched *f = ts_batch_fetch(gr->b, mode == Mode::Matches, slot, &rc);
-                if (rc == TS_OK && mode == Mode::Blocks && counts) rc = batch_counts(gr->b, counts + gr->first, tips, ctx->down_stream);
+                if (rc == TS_OK && mode == Mode::Blocks && go.counts) rc = batch_counts(gr->b, go.counts, tips, ctx->down_stream);
                 gr->t_fetch = ms_between(t0, Clock::now());
                 if (post.joinable()) post.join();
                 if (rc == TS_OK) {
                     Group *g2 = gr;
-                    post = std::thread([&, g2, f] {
+                    post = std::thread([&, g2, f, go] {
                         DeviceGuard g3(ctx->device);
                         const auto p0 = Clock::now();
-                        const int prc = ts_batch_finalize(g2->b, f, out + g2->first);
+                        const int prc = ts_batch_finalize(g2->b, f, go.out);
                         if (prc != TS_OK) set_err(prc);
                         g2->t_final = ms_between(p0, Clock::now());
                         retire(g2, g2->t_final);
@@ -899,7 +909,7 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
 struct SubmitReq {
     int mode; bool tips;
     const std::vector<Item> *items;
-    ts_segment_out *out; ts_segment_counts *counts; uint8_t *pass; uint32_t *ends;
+    Outputs o;
     int rc = TS_OK; bool done = false;
     std::string error;
 };
@@ -914,7 +924,7 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
     const bool tips = group[0]->tips;
     if (group.size() == 1) {
         SubmitReq &r = *group[0];
-        r.rc = run_pipeline(ctx, mode, tips, *r.items, r.out, r.counts, r.pass, r.ends);
+        r.rc = run_pipeline(ctx, mode, tips, *r.items, r.o);
         if (r.rc != TS_OK) r.error = ctx->error;
         return;
     }
@@ -923,20 +933,22 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
     std::vector<Item> items;
     items.reserve(total);
     for (SubmitReq *r : group) items.insert(items.end(), r->items->begin(), r->items->end());
-    std::vector<ts_segment_out> out(mode == Mode::ReadPass ? 0 : total);
+    std::vector<ts_segment_out> out(mode == Mode::ReadPass || mode == Mode::Ends ? 0 : total);
     std::vector<ts_segment_counts> counts(mode == Mode::Blocks ? total : 0);
     std::vector<uint8_t> pass(mode == Mode::ReadPass ? total : 0);
     std::vector<uint32_t> ends(mode == Mode::Ends ? 2 * total : 0);
-    const int rc = run_pipeline(ctx, mode, tips, items, out.empty() ? nullptr : out.data(), counts.empty() ? nullptr : counts.data(),
-                                pass.empty() ? nullptr : pass.data(), ends.empty() ? nullptr : ends.data());
+    const Outputs merged{out.empty() ? nullptr : out.data(), counts.empty() ? nullptr : counts.data(),
+                         pass.empty() ? nullptr : pass.data(), ends.empty() ? nullptr : ends.data()};
+    const int rc = run_pipeline(ctx, mode, tips, items, merged);
     if (rc == TS_OK) {
         size_t at = 0;
         for (SubmitReq *r : group) {
             const size_t n = r->items->size();
-            if (r->out) std::memcpy(r->out, out.data() + at, n * sizeof(ts_segment_out));
-            if (r->counts) std::memcpy(r->counts, counts.data() + at, n * sizeof(ts_segment_counts));
-            if (r->pass) std::memcpy(r->pass, pass.data() + at, n);
-            if (r->ends) std::memcpy(r->ends, ends.data() + 2 * at, n * 8);
+            const Outputs from = merged.slice(at);
+            if (r->o.out) std::memcpy(r->o.out, from.out, n * sizeof(ts_segment_out));
+            if (r->o.counts) std::memcpy(r->o.counts, from.counts, n * sizeof(ts_segment_counts));
+            if (r->o.pass) std::memcpy(r->o.pass, from.pass, n);
+            if (r->o.ends) std::memcpy(r->o.ends, from.ends, n * 8);
             r->rc = TS_OK;
             at += n;
         }
@@ -944,17 +956,16 @@ void run_group(ts_ctx *ctx, std::vector<SubmitReq *> &group) {
     }
     if (!out.empty()) ts_free_segments(out.data(), out.size());
     for (SubmitReq *r : group) {
-        r->rc = run_pipeline(ctx, mode, tips, *r->items, r->out, r->counts, r->pass, r->ends);
+        r->rc = run_pipeline(ctx, mode, tips, *r->items, r->o);
         if (r->rc != TS_OK) r->error = ctx->error;
     }
 }
 
 // run_pipeline for a caller that does not hold the context's call lock: alone, it runs at once; beside others, it is merged
 // with them.  (A merged run is capped at ~8 GB of input: what is left waits for the next one.)
-int submit_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, ts_segment_out *out,
-                    ts_segment_counts *counts, uint8_t *pass, uint32_t *ends = nullptr) {
+int submit_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, Outputs o) {
     if (items.empty()) return TS_OK;
-    SubmitReq req{(int)mode, tips, &items, out, counts, pass, ends, TS_OK, false, std::string()};
+    SubmitReq req{(int)mode, tips, &items, o, TS_OK, false, std::string()};
     std::unique_lock<std::mutex> lk(ctx->sq_mtx);
     ctx->sq.push_back(&req);
     while (!req.done) {
@@ -1002,508 +1013,510 @@ int submit_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &
 // Parameter sets outside the tiled kernel's closed form (mixed-length pattern sets, pattern lengths above 8, or a
 // longest pattern exceeding min(step, window-step) where the reference's uint32 start index wraps): the general
 // kernels of generic.hip over groups of ~256 MB of regions at a time — match masks, the records the reference pushes
-// and the window records all come off the device, and blocks are called on the device; the host expands the records and
-// converts the window records (ts_finalize_segment).
-std::atomic<uint64_t> ts_gen_ns[2];       // TS_TIMING: job time in record expansion / in ts_finalize_segment
+// and the window records all come off the device, and blocks are called on the device; the host assembles SegmentData
+// from them (ts_assemble_general).  Group g + 1 is planned, staged and uploaded on a thread of its own while group g's
+// kernels, block calling and download run on the calling thread, and group g - 1's host stage runs on a third.
 
-// blocks_only: the caller reads no match vectors (ts_scan_segments_blocks) — the match records then never leave the device;
-// counts (nullable): the sizes the vectors would have had.
-int scan_group_generic(ts_ctx *c, const ts_segment_in *segs, const std::vector<size_t> &which,
-                       bool tips, ts_segment_out *out, bool blocks_only = false, ts_segment_counts *counts = nullptr) {
-    if (which.empty()) return TS_OK;
+struct GenRegion { uint64_t seg_start, len, layout_off; };                  // a scanned region and where it lies in the layout
+struct GenSeg { uint64_t len, abs_pos, layout_off; std::vector<GenRegion> regions; uint64_t first_tile = 0, n_tiles = 0, win_base = 0, n_windows = 0; };
+
+// What a group's host stage reads (it runs while the next group is on the device)
+struct GenHost {
+    size_t first = 0;                                     // the group's items: [first, first + G.size())
+    std::vector<GenSeg> G;
+    std::vector<TsGeneralTile> tiles;
+    std::vector<unsigned long long> tile_off;
+    std::vector<uint32_t> recs_heap, wins_heap;
+    const uint32_t *recs = nullptr, *wins = nullptr;      // the landing area: pinned, or the heap vectors
+    uint64_t nrecs = 0;                                   // records downloaded
+    std::vector<TsDevBlock> blocks;
+    std::vector<unsigned long long> sums;
+};
+
+// One group on the device: planned and uploaded by gen_prepare, its other buffers taken by gen_fused; all go back to the pool
+struct GenGroup {
+    ts_ctx *c;
+    std::shared_ptr<GenHost> gh;
+    DevBuf d_in, d_tiles, d_tab, d_slots, d_stats, d_off, d_tmp, d_rec, d_win;
+    uint64_t nwin_total = 0, nrec = 0;
+    uint32_t slot_cap = 0;
+    const uint32_t *d_records = nullptr;                  // the stream block calling reads: d_rec, or the slots themselves
+    Clock::time_point t_dev0;
+    double ms_up = 0;
+    int rc = TS_OK;
+    explicit GenGroup(ts_ctx *c_) : c(c_) {}
+    ~GenGroup() { for (DevBuf *d : {&d_in, &d_tiles, &d_tab, &d_slots, &d_stats, &d_off, &d_tmp, &d_rec, &d_win}) c->pool.give(std::move(*d)); }
+    // the segment table: len, layout offset, window base, window count per segment (4 x ns u64), the window total, the overflow flag
+    size_t tab_win() const { return 2 * gh->G.size() * 8; }
+    size_t tab_nwin() const { return 3 * gh->G.size() * 8; }
+    size_t tab_flag() const { return 4 * gh->G.size() * 8 + 8; }
+};
+
+// The state of one call that its steps share
+struct GenCall {
+    ts_ctx *c;
+    const ts_params &P;
+    Mode mode;
+    bool tips, blocks_only, wide;
+    const std::vector<Item> &items;
+    Outputs o;
+    TsGenericGeom Q{};
+    uint64_t target;                                      // bytes of regions per group
+    uint32_t len_spread;
+    bool position_order, push_compact;
+    unsigned long long gen_lens = 0;
+    // a tile's slot at the start of a group: what the groups before needed (a telomeric tile under a many-length set holds more
+    // than a record per position; finding that out again for every group ran half the groups of a call twice)
+    uint32_t slot_cap_call;
+    // the upload (one group at a time, on the calling thread or the prefetch thread)
+    size_t next_item = 0;
+    int slot = 0;
+    bool used[ts_ctx::kUpSlots] = {false, false, false};
+    size_t group_no = 0;
+    std::thread host_job;                                 // the host stage of the group before
+    std::atomic<int> host_err{TS_OK};
+    // TS_TIMING
+    bool timing;
+    Clock::time_point t_begin = Clock::now();
+    double t_up = 0, t_dev = 0, t_host = 0, t_take = 0, t_fused = 0, t_blk = 0, t_d2h = 0, t_wait_next = 0, t_dbg[3] = {0, 0, 0};
+    float t_kern = 0;
+
+    GenCall(ts_ctx *c_, Mode m, bool t, const std::vector<Item> &it, Outputs out)
+        : c(c_), P(c_->params), mode(m), tips(t), blocks_only(m != Mode::Matches), wide(c_->gen_wide), items(it), o(out),
+          timing(c_->knobs.timing) {
+        const uint32_t s = P.step, w = P.window_size;
+        Q.s = s; Q.w = w; Q.longest = c->longest; Q.nuc_on = (P.out_gc || P.out_entropy) ? 1u : 0u; Q.fold = P.fold_case;
+        Q.s_magic = s >= 2u ? (uint32_t)((1ull << 32) / s + 1ull) : 0u;
+        Q.cw = w / s; Q.rw = w - Q.cw * s;
+        // the wide form (sets beyond 8 lengths / 32 bases): its own kernel, a 64-base halo, records with six bits of length index;
+        // smaller groups, because a tile's slot may have to grow to a record per position AND length
+        target = wide ? std::min<uint64_t>(group_target_bytes(), 256ull << 20) : group_target_bytes();   // (16 - 64 KB of slot per tile: 4 - 17 GB per group)
+        // Block calling on the device (blockcall.hip with the general record formats).  The reference calls blocks over allMatches
+        // as pushed (src/teloscope.cpp:485-509, :642-657): position order for tips-only scans, for w == s, and under w > s when the
+        // pattern lengths differ by at most one (the record that ends later is never pushed earlier: end positions are monotone
+        // in stream order, hence so is the pushing window).  Sets with a length gap of two or more under w > s are pushed not
+        // quite in position order: for those the compaction writes the dense stream IN PUSH ORDER
+        // (ts_general_compact_push) and block calling walks it as the reference does (blockcall.hip, MODE 1: the predecessor as
+        // the stream lies, the search range by stream index from a bisection restated probe by probe).  The host's expansion
+        // of such a stream needs no ordering pass either.
+        len_spread = wide ? (c->wide_lens.empty() ? 0u : c->wide_lens.back() - c->wide_lens.front())
+                          : (c->gpat.nlen ? c->gpat.len[c->gpat.nlen - 1] - c->gpat.len[0] : 0u);
+        position_order = tips || w == s || len_spread <= 1u;                   // position order IS push order
+        push_compact = !position_order;                                         // the device orders the stream
+        for (uint32_t li = 0; li < c->gpat.nlen && li < 8u; ++li) gen_lens |= (unsigned long long)(c->gpat.len[li] & 63u) << (6u * li);
+        if (c->gpat.nlen && c->gpat.len[c->gpat.nlen - 1] > 63u) gen_lens = 0;
+        if (wide) gen_lens = 1ull;                                              // (wide records: the lengths come from wpat.len; non-zero = "general format")
+        slot_cap_call = wide ? TS_GENERAL_TILE * std::min<uint32_t>(4u, std::max<uint32_t>(1u, c->wpat.nlen)) : TS_GENERAL_TILE;
+    }
+    ~GenCall() { if (host_job.joinable()) host_job.join(); }
+};
+
+// Plans a group of consecutive items, ~256 MB of regions (layout = the regions back to back, 16-byte aligned), and uploads its
+// bases, tile list and segment table.
+int gen_prepare(GenCall &g, GenGroup &gr) {
+    ts_ctx *c = g.c;
+    const ts_params &P = g.P;
+    const uint32_t s = P.step;
+    gr.gh = std::make_shared<GenHost>();
+    GenHost &h = *gr.gh;
+    h.first = g.next_item;
+    std::vector<GenSeg> &G = h.G;
+    std::vector<TsGeneralTile> &tiles = h.tiles;
+    std::vector<UpPiece> pieces;
+    uint64_t off = 0, nwin_total = 0;
+    while (g.next_item < g.items.size() && (G.empty() || off < g.target)) {
+        const Item &it = g.items[g.next_item];
+        GenSeg sl{it.len, it.abs_pos, off, {}};
+        // regions exactly as scanSegment picks them (src/teloscope.cpp:576-583; uint32 product)
+        if (g.tips) {
+            const uint32_t twice = 2u * P.terminal_limit;
+            if (it.len > twice) { sl.regions.push_back({0, P.terminal_limit, 0}); sl.regions.push_back({it.len - P.terminal_limit, P.terminal_limit, 0}); }
+            else if (it.len) sl.regions.push_back({0, it.len, 0});
+        } else if (it.len) {
+            sl.regions.push_back({0, it.len, 0});
+            sl.n_windows = ceil_div(it.len, s);
+        }
+        sl.first_tile = tiles.size();
+        for (GenRegion &rg : sl.regions) {
+            rg.layout_off = off;
+            const int rc = region_pieces(c, it, it.len, rg.seg_start, rg.len, off, 0, ~0ull, pieces);
+            if (rc != TS_OK) return rc;
+            uint64_t kq = rg.seg_start / s, kr = rg.seg_start - kq * s;          // P0 = kq s + kr, walked from tile to tile
+            for (uint64_t a = 0; a < rg.len; a += TS_GENERAL_TILE) {
+                TsGeneralTile T{};
+                T.in_off = off + a;
+                T.seg_rel = rg.seg_start + a;
+                T.k_p0 = kq; T.r_p0 = (uint32_t)kr;
+                T.n = (uint32_t)std::min<uint64_t>(TS_GENERAL_TILE, rg.len - a);
+                T.avail = (uint32_t)std::min<uint64_t>(rg.len - a, (uint64_t)T.n + (g.wide ? (uint32_t)TS_WIDE_HALO : 32u));
+                T.seg = (uint32_t)G.size();
+                tiles.push_back(T);
+                kr += TS_GENERAL_TILE;
+                if (kr >= s) { const uint64_t d = kr / s; kq += d; kr -= d * s; }
+            }
+            off += (rg.len + 15) & ~15ull;
+        }
+        sl.n_tiles = tiles.size() - sl.first_tile;
+        sl.win_base = nwin_total;
+        nwin_total += sl.n_windows;
+        G.push_back(std::move(sl));
+        ++g.next_item;
+    }
+    gr.nwin_total = nwin_total;
+    const uint64_t span = off + 64;
+    const size_t ns = G.size(), nt = tiles.size();
+    if (nt >= 0x7FFFFFFFull) return c->fail(TS_ERR_UNSUPPORTED, "too many tiles in one group");
+    const size_t tab_bytes = 4 * ns * 8 + 8 + 16;
+    HIP_TRY(c, c->pool.take(span, gr.d_in));
+    HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * sizeof(TsGeneralTile), gr.d_tiles));
+    HIP_TRY(c, c->pool.take(tab_bytes, gr.d_tab));
+    std::vector<unsigned long long> tab(4 * ns + 3, 0ull);
+    for (size_t i = 0; i < ns; ++i) { tab[i] = G[i].len; tab[ns + i] = G[i].layout_off; tab[2 * ns + i] = G[i].win_base; tab[3 * ns + i] = G[i].n_windows; }
+    tab[4 * ns] = nwin_total;
+    const auto t0 = Clock::now();
+    { int rc = upload_pieces(c, pieces, gr.d_in.p, 0, g.slot, g.used); if (rc != TS_OK) return rc; }
+    HIP_TRY(c, hipMemcpyAsync(gr.d_tiles.p, tiles.data(), nt * sizeof(TsGeneralTile), hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(c, hipMemcpyAsync(gr.d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(c, hipStreamSynchronize(c->up_stream));
+    gr.ms_up = ms_between(t0, Clock::now());
+    return TS_OK;
+}
+
+// The fused pass (match masks, records into per-tile slots, window records) and the tile offsets (a prefix sum over the tile
+// counts).  A tile's slot holds one record per position — all a single-length set can produce; a mixed-length tile that holds
+// more says so, and the group runs again with slots that cannot overflow.
+int gen_fused(GenCall &g, GenGroup &gr) {
+    ts_ctx *c = g.c;
+    GenHost &h = *gr.gh;
+    const size_t nt = h.tiles.size();
+    const uint32_t s = g.P.step, w = g.P.window_size;
+    hipStream_t st = c->scan_stream;
+    const auto t0 = Clock::now();
+    gr.slot_cap = g.slot_cap_call;
+    // the list form of the fused pass (per-candidate work on full wavefronts) when a tile adds to few enough window
+    // records for the accumulators it keeps in LDS; a tile dense enough to overflow a wave's candidate list sends the
+    // group through the position-strided form instead
+    bool use_list = !g.wide && c->knobs.gen_list && s >= 2u && w < (1u << 28) &&
+                    (g.tips || ((uint64_t)TS_GENERAL_TILE + w) / s + 3 <= ts_k_general_list_max_records());
+    HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)gr.slot_cap * 4, gr.d_slots));
+    HIP_TRY(c, c->pool.take((nt + 1) * 16, gr.d_stats));
+    HIP_TRY(c, c->pool.take((nt + 1) * 8, gr.d_off));
+    HIP_TRY(c, c->pool.take((size_t)ts_k_scan_tmp_bytes((uint32_t)nt), gr.d_tmp));
+    if (gr.nwin_total) HIP_TRY(c, c->pool.take(gr.nwin_total * 32, gr.d_win));
+    const auto t1 = Clock::now();
+    gr.t_dev0 = t1;
+    g.t_up += gr.ms_up;
+    g.t_take += ms_between(t0, t1);
+    char *const dt = (char *)gr.d_tab.p;
+    const unsigned long long *const tab_len = (const unsigned long long *)dt, *const tab_win = (const unsigned long long *)(dt + gr.tab_win()),
+                             *const tab_nwin = (const unsigned long long *)(dt + gr.tab_nwin());
+    uint32_t *const d_flag = (uint32_t *)(dt + gr.tab_flag());
+    std::vector<unsigned long long> &tile_off = h.tile_off;
+    tile_off.assign(nt + 1, 0);
+    for (int attempt = 0;; ++attempt) {
+        uint32_t flag = 0;
+        {
+            std::lock_guard<std::mutex> lk(c->mtx);
+            if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[0], st));
+            HIP_TRY(c, hipMemsetAsync(d_flag, 0, 16, st));
+            if (gr.nwin_total) HIP_TRY(c, hipMemsetAsync(gr.d_win.p, 0, gr.nwin_total * 32, st));
+            if (g.wide) {
+                if (ts_k_launch_general_wide((const unsigned char *)gr.d_in.p, (const TsGeneralTile *)gr.d_tiles.p, (uint32_t)nt,
+                                             tab_len, tab_win, tab_nwin, &c->wpat, &g.Q, g.tips ? 1 : 0, gr.slot_cap, (uint32_t *)gr.d_stats.p,
+                                             (uint32_t *)gr.d_slots.p, (uint32_t *)gr.d_win.p, d_flag, st) != 0)
+                    return c->fail(TS_ERR_HIP, "general wide kernel launch failed");
+            } else
+            if (ts_k_launch_general_fused((const unsigned char *)gr.d_in.p, (const TsGeneralTile *)gr.d_tiles.p, (uint32_t)nt,
+                                          tab_len, tab_win, tab_nwin, &c->gpat, &g.Q, g.tips ? 1 : 0, gr.slot_cap, (uint32_t *)gr.d_stats.p,
+                                          (uint32_t *)gr.d_slots.p, (uint32_t *)gr.d_win.p, d_flag, use_list ? 1 : 0, c->num_cu, st) != 0)
+                return c->fail(TS_ERR_HIP, "general fused kernel launch failed");
+            if (ts_k_launch_tile_offsets((const uint32_t *)gr.d_stats.p, (uint32_t)nt, (unsigned long long *)gr.d_off.p, gr.d_tmp.p, st) != 0)
+                return c->fail(TS_ERR_HIP, "tile-offset kernel launch failed");
+            if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
+        }
+        const auto te0 = Clock::now();
+        // (pinned landing: asynchronous for real, then one memcpy into the group's own vector)
+        unsigned long long *land = nullptr;
+        if (nt && c->pin_off.ensure(std::max<size_t>((nt + 1) * 8 + 64, 1u << 20)) == hipSuccess) land = (unsigned long long *)c->pin_off.p;
+        else (void)hipGetLastError();
+        uint32_t *flag_land = land ? (uint32_t *)(land + nt + 1) : &flag;
+        if (nt) HIP_TRY(c, hipMemcpyAsync(land ? land : tile_off.data(), gr.d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(flag_land, d_flag, 4, hipMemcpyDeviceToHost, st));
+        const auto te1 = Clock::now();
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (land) { std::memcpy(tile_off.data(), land, (nt + 1) * 8); flag = *flag_land; }
+        if (g.timing) { g.t_dbg[0] += ms_between(t1, te0); g.t_dbg[1] += ms_between(te0, te1); g.t_dbg[2] += ms_between(te1, Clock::now()); }
+        if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
+        if (!flag) break;
+        const uint32_t slot_max = TS_GENERAL_TILE * std::max<uint32_t>(1u, g.wide ? c->wpat.nlen : c->gpat.nlen);
+        if (attempt > (g.wide ? 4 : 1) || (gr.slot_cap >= slot_max && !(flag & 2u)))
+            return c->fail(TS_ERR_STATE, "general path: a tile overflowed a slot that holds every match it can have");
+        if (flag & 2u) { use_list = false; continue; }            // a candidate list spilled: the strided form takes this group
+        // (the wide form grows by fours: a slot for every position AND length — 63 of them — is 1 MB per tile)
+        gr.slot_cap = g.wide ? std::min<uint32_t>(slot_max, gr.slot_cap * 4u) : slot_max;
+        g.slot_cap_call = gr.slot_cap;
+        c->pool.give(std::move(gr.d_slots));
+        HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)gr.slot_cap * 4, gr.d_slots));
+    }
+    gr.nrec = tile_off[nt];
+    g.t_fused += ms_between(t1, Clock::now());
+    return TS_OK;
+}
+
+// The slots into one dense stream (in push order where it is not position order), then blocks on the device: the tiles as
+// blockcall.hip addresses them, the canonical / forward counts, then the walks.
+int gen_blocks(GenCall &g, GenGroup &gr) {
+    ts_ctx *c = g.c;
+    GenHost &h = *gr.gh;
+    const size_t ns = h.G.size(), nt = h.tiles.size();
+    hipStream_t st = c->scan_stream;
+    const auto t0 = Clock::now();
+    // blocks only, over a stream in position order: block calling reads the records where the fused pass wrote them (it
+    // addresses them through the tile directory), so there is no dense stream to make — every record used to be read and
+    // written once more for nothing
+    const bool in_place = g.blocks_only && !g.push_compact;
+    if (!in_place) HIP_TRY(c, c->pool.take(std::max<uint64_t>(gr.nrec, 1) * 4, gr.d_rec));
+    gr.d_records = in_place ? (const uint32_t *)gr.d_slots.p : (const uint32_t *)gr.d_rec.p;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[0], st));
+        if (in_place) {
+            if (ts_k_launch_general_slot_offsets((unsigned long long *)gr.d_off.p, (uint32_t)nt, gr.slot_cap, st) != 0)
+                return c->fail(TS_ERR_HIP, "slot-offset kernel launch failed");
+        } else
+        if (g.push_compact) {
+            if (ts_k_launch_general_compact_push((const TsGeneralTile *)gr.d_tiles.p, (const uint32_t *)gr.d_stats.p, (unsigned long long *)gr.d_off.p,
+                                                 (const uint32_t *)gr.d_slots.p, gr.slot_cap, (uint32_t)nt, (const unsigned long long *)gr.d_tab.p,
+                                                 g.P.window_size, g.P.step, g.len_spread, g.wide ? 1 : 0, g.gen_lens, g.wide ? c->wpat.len : nullptr,
+                                                 (uint32_t *)gr.d_rec.p, st) != 0)
+                return c->fail(TS_ERR_HIP, "general push-order compact kernel launch failed");
+            // (records moved across tile borders: the host stage reads the offsets as they are now)
+            if (!g.blocks_only) HIP_TRY(c, hipMemcpyAsync(h.tile_off.data(), gr.d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
+        } else
+        if (ts_k_launch_general_compact((const uint32_t *)gr.d_stats.p, (const unsigned long long *)gr.d_off.p, (const uint32_t *)gr.d_slots.p,
+                                        gr.slot_cap, (uint32_t)nt, (uint32_t *)gr.d_rec.p, st) != 0)
+            return c->fail(TS_ERR_HIP, "general compact kernel launch failed");
+        if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
+    }
+    DevBuf d_bct, d_sbase;
+    struct Return { ts_ctx *c; DevBuf &a, &b2; ~Return() { c->pool.give(std::move(a)); c->pool.give(std::move(b2)); } } give_back{c, d_bct, d_sbase};
+    HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * sizeof(TsTile), d_bct));
+    HIP_TRY(c, c->pool.take(std::max<size_t>(ns, 1) * 8, d_sbase));
+    std::vector<unsigned long long> sbase(std::max<size_t>(ns, 1), 0ull);
+    std::vector<TsShardSegIn> segtab(ns);
+    unsigned long long X = 0;
+    for (size_t i = 0; i < ns; ++i) {
+        sbase[i] = X;
+        TsShardSegIn &S = segtab[i];
+        S = TsShardSegIn{};
+        S.in_off = X; S.len = h.G[i].len; S.abs_pos = h.G[i].abs_pos;
+        S.t0 = S.o0 = (uint32_t)h.G[i].first_tile; S.t1 = S.o1 = (uint32_t)(h.G[i].first_tile + h.G[i].n_tiles);
+        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
+        S.lo_rel = 0; S.hi_rel = h.G[i].len; S.seg = (uint32_t)i;
+        X += h.G[i].len + 64;
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_sbase.p, sbase.data(), sbase.size() * 8, hipMemcpyHostToDevice, st));
+    if (ts_k_launch_general_block_inputs((const TsGeneralTile *)gr.d_tiles.p, (const unsigned long long *)gr.d_off.p, gr.d_records,
+                                         (const unsigned long long *)d_sbase.p, (uint32_t)nt, (TsTile *)d_bct.p, (uint32_t *)gr.d_stats.p,
+                                         g.push_compact ? 1 : 0, st) != 0)
+        return c->fail(TS_ERR_HIP, "general block-input kernel launch failed");
+    const int rc = ts_device_block_call_raw(c, (const TsTile *)d_bct.p, (const unsigned long long *)gr.d_off.p, (const uint32_t *)gr.d_stats.p,
+                                            gr.d_records, gr.nrec, segtab, nt, g.tips, g.gen_lens, nullptr, nullptr, st, h.blocks, &h.sums, 0,
+                                            g.wide ? c->wpat.len : nullptr, g.push_compact);
+    g.t_blk += ms_between(t0, Clock::now());
+    return rc;
+}
+
+// The records (unless the mode reads none) and the window records to the landing area: the context's pinned download
+// buffers, alternating by group (the host stage of group g reads its buffer while group g + 1 lands in the other; it has been
+// joined before group g + 2 arrives)
+int gen_download(GenCall &g, GenGroup &gr) {
+    ts_ctx *c = g.c;
+    GenHost &h = *gr.gh;
+    hipStream_t st = c->scan_stream;
+    const auto t0 = Clock::now();
+    h.nrecs = g.blocks_only ? 0 : gr.nrec;
+    const size_t rec_bytes = ((size_t)h.nrecs * 4 + 255) & ~(size_t)255, win_bytes = (size_t)gr.nwin_total * 32;
+    PinBuf &pb = c->pin_down[g.group_no & 1];
+    ++g.group_no;
+    uint32_t *hrec, *hwin;
+    if (rec_bytes + win_bytes + 256 <= (768ull << 20) && pb.ensure(std::max<size_t>(rec_bytes + win_bytes + 256, 32u << 20)) == hipSuccess) {
+        hrec = (uint32_t *)pb.p;
+        hwin = (uint32_t *)((char *)pb.p + rec_bytes);
+    } else {
+        (void)hipGetLastError();
+        h.recs_heap.resize(h.nrecs + 1);
+        h.wins_heap.resize(gr.nwin_total * 8 + 1);
+        hrec = h.recs_heap.data();
+        hwin = h.wins_heap.data();
+    }
+    if (h.nrecs) HIP_TRY(c, hipMemcpyAsync(hrec, gr.d_rec.p, h.nrecs * 4, hipMemcpyDeviceToHost, st));
+    if (gr.nwin_total) HIP_TRY(c, hipMemcpyAsync(hwin, gr.d_win.p, gr.nwin_total * 32, hipMemcpyDeviceToHost, st));
+    h.recs = hrec;
+    h.wins = hwin;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
+    const auto t1 = Clock::now();
+    g.t_d2h += ms_between(t0, t1);
+    g.t_dev += ms_between(gr.t_dev0, t1);
+    return TS_OK;
+}
+
+// The host stage of a group: SegmentData from what landed (ts_assemble_general), then the mode's outputs — Matches: the
+// segments; Blocks: the segments and the counts from the device sums; ReadPass: whether a read has a terminal block; Ends:
+// the longest terminal block per side.
+int gen_host(GenCall &g, const GenHost &h) {
+    const size_t ns = h.G.size();
+    HostView v;
+    v.tips = g.tips;
+    v.wins = h.wins; v.recs = h.recs; v.nrecs = h.nrecs;
+    v.blocks = h.blocks.data(); v.n_blocks = h.blocks.size();
+    v.segs.reserve(ns);
+    for (const GenSeg &sg : h.G) v.segs.push_back({sg.len, sg.abs_pos, sg.win_base, sg.n_windows, sg.first_tile, sg.n_tiles});
+    if (!g.blocks_only) {
+        v.tiles.resize(h.tiles.size());
+        for (size_t t = 0; t < h.tiles.size(); ++t) v.tiles[t] = {h.tile_off[t], h.tiles[t].seg_rel, (uint32_t)(h.tile_off[t + 1] - h.tile_off[t])};
+    }
+    const Outputs o = g.o.slice(h.first);
+    std::vector<ts_segment_out> tmp(o.out ? 0 : ns);
+    ts_segment_out *const out = o.out ? o.out : tmp.data();
+    const int rc = ts_assemble_general(g.c, v, out);
+    if (rc != TS_OK) return rc;
+    for (size_t i = 0; i < ns; ++i) {
+        if (o.counts) o.counts[i] = ts_segment_counts{g.tips ? 0 : h.G[i].n_windows, h.sums[5 * i + 2], h.sums[5 * i + 3], h.sums[5 * i + 4]};
+        if (o.pass) o.pass[i] = out[i].n_terminal_blocks != 0;
+        if (o.ends) reduce_terminal_ends(out[i], h.G[i].len, h.G[i].abs_pos, o.ends + 2 * i);
+    }
+    ts_free_segments(tmp.data(), tmp.size());
+    return TS_OK;
+}
+
+int scan_general(ts_ctx *c, Mode mode, bool tips, const std::vector<Item> &items, Outputs o) {
+    if (items.empty()) return TS_OK;
     if (!c->generic_ok)
         return c->fail(TS_ERR_UNSUPPORTED, "unsupported parameter set: a non-ACGT pattern, or more than 63 pattern lengths / a pattern "
                                            "longer than 63 bases (more than a ts_pattern holds)");
     DEVICE_TRY(c);
     { int rc = ensure_streams(c); if (rc != TS_OK) return rc; }
-    const ts_params &P = c->params;
-    const uint32_t s = P.step, w = P.window_size, ov = w - s, L = c->longest;
-    hipStream_t st = c->scan_stream;
-    TsGenericGeom Q{};
-    Q.s = s; Q.w = w; Q.longest = L; Q.nuc_on = (P.out_gc || P.out_entropy) ? 1u : 0u; Q.fold = P.fold_case;
-    Q.s_magic = s >= 2u ? (uint32_t)((1ull << 32) / s + 1ull) : 0u;
-    Q.cw = w / s; Q.rw = w - Q.cw * s;
-    const bool timing = c->knobs.timing;
-    const auto t_begin = Clock::now();
-    double t_dbg[3] = {0, 0, 0};
-    double t_up = 0, t_dev = 0, t_host = 0, t_take = 0, t_fused = 0, t_blk = 0, t_d2h = 0, t_wait_next = 0;
-    float t_kern = 0;
-    if (timing && !c->gen_ev[0]) { HIP_TRY(c, hipEventCreate(&c->gen_ev[0])); HIP_TRY(c, hipEventCreate(&c->gen_ev[1])); }
-
-    struct RegionL { uint64_t seg_start, len, layout_off; };                   // a scanned region and where it lies in the layout
-    struct SegL { size_t idx; uint64_t len, abs_pos, layout_off; std::vector<RegionL> regions; uint64_t first_tile = 0, n_tiles = 0, win_base = 0, n_windows = 0; };
-    // the wide form (sets beyond 8 lengths / 32 bases): its own kernel, a 64-base halo, records with six bits of length index;
-    // smaller groups, because a tile's slot may have to grow to a record per position AND length
-    const bool wide = c->gen_wide;
-    const uint32_t rec_shift = wide ? 8u : 5u, rec_li_mask = wide ? 63u : 7u;
-    const uint64_t target = wide ? std::min<uint64_t>(group_target_bytes(), 256ull << 20) : group_target_bytes();   // (16 - 64 KB of slot per tile: 4 - 17 GB per group)
-    int slot = 0;
-    bool used[ts_ctx::kUpSlots] = {false, false, false};
-    size_t wi = 0;
-    // The host stage of group g (record expansion + window records on the host threads) runs on a background thread while the
-    // device stage of group g + 1 (upload, kernels, D2H) runs here: what a group's host stage reads lives in a GroupHost.
-    struct GroupHost { std::vector<SegL> G; std::vector<TsGeneralTile> tiles; std::vector<unsigned long long> tile_off;
-                       std::vector<uint32_t> recs_heap, wins_heap; const uint32_t *recs = nullptr, *wins = nullptr;
-                       std::vector<TsDevBlock> blocks; std::vector<unsigned long long> sums; };
-    // Block calling on the device (blockcall.hip with the general record formats).  The reference calls blocks over allMatches
-    // as pushed (src/teloscope.cpp:485-509, :642-657): position order for tips-only scans, for w == s, and under w > s when the
-    // pattern lengths differ by at most one (the record that ends later is never pushed earlier: end positions are monotone
-    // in stream order, hence so is the pushing window).  Sets with a length gap of two or more under w > s are pushed not
-    // quite in position order: for those the compaction writes the dense stream IN PUSH ORDER
-    // (ts_general_compact_push) and block calling walks it as the reference does (blockcall.hip, MODE 1: the predecessor as
-    // the stream lies, the search range by stream index from a bisection restated probe by probe).  The host's expansion
-    // of such a stream needs no ordering pass either.
-    const uint32_t len_spread = c->gen_wide ? (c->wide_lens.empty() ? 0u : c->wide_lens.back() - c->wide_lens.front())
-                                            : (c->gpat.nlen ? c->gpat.len[c->gpat.nlen - 1] - c->gpat.len[0] : 0u);
-    const bool position_order = tips || ov == 0 || len_spread <= 1u;      // position order IS push order
-    unsigned long long gen_lens = 0;
-    for (uint32_t li = 0; li < c->gpat.nlen && li < 8u; ++li) gen_lens |= (unsigned long long)(c->gpat.len[li] & 63u) << (6u * li);
-    if (c->gpat.nlen && c->gpat.len[c->gpat.nlen - 1] > 63u) gen_lens = 0;
-    if (c->gen_wide) gen_lens = 1ull;                                      // (wide records: the lengths come from wpat.len; non-zero = "general format")
-    const bool push_compact = !position_order;                             // the device orders the stream
-    size_t group_no = 0;
-    std::thread host_job;
-    std::atomic<int> host_err{TS_OK};
-    struct JoinJob { std::thread &t; ~JoinJob() { if (t.joinable()) t.join(); } } join_job{host_job};
-    // What the upload stage hands the device stage: a group planned, its input buffer, tile list and segment table on the device.
-    // Group g + 1 is planned, staged and uploaded on a thread of its own while group g's kernels, block calling and
-    // download run here (round 4: the two used to run one after the other, 32 + 22 ms per 3 Gb).
-    struct Prepared {
-        std::shared_ptr<GroupHost> gh;
-        DevBuf d_in, d_tiles, d_tab;
-        uint64_t nwin_total = 0;
-        int rc = TS_OK;
-        double ms = 0;
-    };
-    auto prepare = [&](Prepared &PR) -> int {
-        // ---- a group of consecutive segments, ~256 MB of regions; layout = the regions back to back, 16-byte aligned
-        PR.gh = std::make_shared<GroupHost>();
-        std::vector<SegL> &G = PR.gh->G;
-        std::vector<TsGeneralTile> &tiles = PR.gh->tiles;
-        std::vector<UpPiece> pieces;
-        uint64_t off = 0, nwin_total = 0;
-        while (wi < which.size() && (G.empty() || off < target)) {
-            const ts_segment_in &sg = segs[which[wi]];
-            const Item it{sg.seq, sg.len, sg.abs_pos, sg.input_format, sg.n_pieces};
-            SegL sl{which[wi], sg.len, sg.abs_pos, off, {}};
-            // regions exactly as scanSegment picks them (src/teloscope.cpp:576-583; uint32 product)
-            if (tips) {
-                const uint32_t twice = 2u * P.terminal_limit;
-                if (sg.len > twice) { sl.regions.push_back({0, P.terminal_limit, 0}); sl.regions.push_back({sg.len - P.terminal_limit, P.terminal_limit, 0}); }
-                else if (sg.len) sl.regions.push_back({0, sg.len, 0});
-            } else if (sg.len) {
-                sl.regions.push_back({0, sg.len, 0});
-                sl.n_windows = ceil_div(sg.len, s);
-            }
-            sl.first_tile = tiles.size();
-            for (RegionL &rg : sl.regions) {
-                rg.layout_off = off;
-                const int rc = region_pieces(c, it, sg.len, rg.seg_start, rg.len, off, 0, ~0ull, pieces);
-                if (rc != TS_OK) return rc;
-                uint64_t kq = rg.seg_start / s, kr = rg.seg_start - kq * s;          // P0 = kq s + kr, walked from tile to tile
-                for (uint64_t a = 0; a < rg.len; a += TS_GENERAL_TILE) {
-                    TsGeneralTile T{};
-                    T.in_off = off + a;
-                    T.seg_rel = rg.seg_start + a;
-                    T.k_p0 = kq; T.r_p0 = (uint32_t)kr;
-                    T.n = (uint32_t)std::min<uint64_t>(TS_GENERAL_TILE, rg.len - a);
-                    T.avail = (uint32_t)std::min<uint64_t>(rg.len - a, (uint64_t)T.n + (wide ? (uint32_t)TS_WIDE_HALO : 32u));
-                    T.seg = (uint32_t)G.size();
-                    tiles.push_back(T);
-                    kr += TS_GENERAL_TILE;
-                    if (kr >= s) { const uint64_t d = kr / s; kq += d; kr -= d * s; }
-                }
-                off += (rg.len + 15) & ~15ull;
-            }
-            sl.n_tiles = tiles.size() - sl.first_tile;
-            sl.win_base = nwin_total;
-            nwin_total += sl.n_windows;
-            G.push_back(std::move(sl));
-            ++wi;
-        }
-        PR.nwin_total = nwin_total;
-        const uint64_t span = off + 64;
-        const size_t ns = G.size(), nt = tiles.size();
-        if (nt >= 0x7FFFFFFFull) return c->fail(TS_ERR_UNSUPPORTED, "too many tiles in one group");
-        const size_t tab_bytes = 4 * ns * 8 + 8 + 16;
-        HIP_TRY(c, c->pool.take(span, PR.d_in));
-        HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * sizeof(TsGeneralTile), PR.d_tiles));
-        HIP_TRY(c, c->pool.take(tab_bytes, PR.d_tab));
-        std::vector<unsigned long long> tab(4 * ns + 3, 0ull);
-        for (size_t i = 0; i < ns; ++i) { tab[i] = G[i].len; tab[ns + i] = G[i].layout_off; tab[2 * ns + i] = G[i].win_base; tab[3 * ns + i] = G[i].n_windows; }
-        tab[4 * ns] = nwin_total;
-        const auto t0 = Clock::now();
-        { int rc = upload_pieces(c, pieces, PR.d_in.p, 0, slot, used); if (rc != TS_OK) return rc; }
-        HIP_TRY(c, hipMemcpyAsync(PR.d_tiles.p, tiles.data(), nt * sizeof(TsGeneralTile), hipMemcpyHostToDevice, c->up_stream));
-        HIP_TRY(c, hipMemcpyAsync(PR.d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->up_stream));
-        HIP_TRY(c, hipStreamSynchronize(c->up_stream));
-        PR.ms = ms_between(t0, Clock::now());
-        return TS_OK;
-    };
-    // a tile's slot at the start of a group: what the groups before needed (a telomeric tile under a many-length set holds more
-    // than a record per position; finding that out again for every group ran half the groups of a call twice)
-    uint32_t slot_cap_call = wide ? TS_GENERAL_TILE * std::min<uint32_t>(4u, std::max<uint32_t>(1u, c->wpat.nlen)) : TS_GENERAL_TILE;
-    std::unique_ptr<Prepared> cur(new Prepared), nxt;
-    std::thread pf;
-    struct JoinJob join_pf{pf};
-    cur->rc = prepare(*cur);
+    if (c->knobs.timing && !c->gen_ev[0]) { HIP_TRY(c, hipEventCreate(&c->gen_ev[0])); HIP_TRY(c, hipEventCreate(&c->gen_ev[1])); }
+    GenCall g(c, mode, tips, items, o);
+    std::unique_ptr<GenGroup> cur(new GenGroup(c)), nxt;
+    std::thread pf;                                               // prefetch: plans and uploads the next group
+    struct JoinPf { std::thread &t; ~JoinPf() { if (t.joinable()) t.join(); } } join_pf{pf};
+    cur->rc = gen_prepare(g, *cur);
     while (cur) {
         if (cur->rc != TS_OK) return cur->rc;
-        if (pf.joinable()) pf.join();
-        nxt.reset();
-        if (wi < which.size()) {
-            nxt.reset(new Prepared);
-            Prepared *np = nxt.get();
+        if (g.next_item < items.size()) {
+            nxt.reset(new GenGroup(c));
+            GenGroup *np = nxt.get();
             // (an exception on the thread — std::bad_alloc while planning a group — must come back as an error code, not end the process)
-            pf = std::thread([&, np] {
-                try { c->bind_this_thread(); DeviceGuard g2(c->device); np->rc = prepare(*np); }
+            pf = std::thread([&g, c, np] {
+                try { c->bind_this_thread(); DeviceGuard g2(c->device); np->rc = gen_prepare(g, *np); }
                 catch (const std::exception &e) { np->rc = c->fail(TS_ERR_ALLOC, std::string("general path: planning / upload of a group failed: ") + e.what()); }
             });
         }
-        const auto t_iter0 = Clock::now();
-        std::shared_ptr<GroupHost> gh = cur->gh;
-        std::vector<SegL> &G = gh->G;
-        std::vector<TsGeneralTile> &tiles = gh->tiles;
-        const uint64_t nwin_total = cur->nwin_total;
-        const size_t ns = G.size(), nt = tiles.size();
-        // ---- device buffers from the pool
-        DevBuf &d_in = cur->d_in, &d_tiles = cur->d_tiles, &d_tab = cur->d_tab;
-        DevBuf d_slots, d_stats, d_off, d_tmp, d_rec, d_win;
-        struct Return { ts_ctx *c; std::vector<DevBuf *> v; ~Return() { for (DevBuf *d : v) c->pool.give(std::move(*d)); } }
-            give_back{c, {&d_in, &d_slots, &d_tiles, &d_tab, &d_stats, &d_off, &d_tmp, &d_rec, &d_win}};
-        const size_t tab_len = 0, tab_win = 2 * ns * 8, tab_nwin = 3 * ns * 8, tab_flag = 4 * ns * 8 + 8;
-        // a tile's slot: one record per position — all a single-length set can produce; a mixed-length tile that holds
-        // more says so, and the group runs again with slots that cannot overflow
-        uint32_t slot_cap = slot_cap_call;
-        // the list form of the fused pass (per-candidate work on full wavefronts) when a tile adds to few enough window
-        // records for the accumulators it keeps in LDS; a tile dense enough to overflow a wave's candidate list sends the
-        // group through the position-strided form instead
-        bool use_list = !wide && c->knobs.gen_list && s >= 2u && w < (1u << 28) &&
-                        (tips || ((uint64_t)TS_GENERAL_TILE + w) / s + 3 <= ts_k_general_list_max_records());
-        HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)slot_cap * 4, d_slots));
-        HIP_TRY(c, c->pool.take((nt + 1) * 16, d_stats));
-        HIP_TRY(c, c->pool.take((nt + 1) * 8, d_off));
-        HIP_TRY(c, c->pool.take((size_t)ts_k_scan_tmp_bytes((uint32_t)nt), d_tmp));
-        if (nwin_total) HIP_TRY(c, c->pool.take(nwin_total * 32, d_win));
-        const auto t1 = Clock::now();
-        t_up += cur->ms;
-        t_take += ms_between(t_iter0, t1);
-        // ---- kernels: the fused pass, a prefix sum over the tile counts, the slots into one dense stream
-        char *const dt = (char *)d_tab.p;
-        std::vector<unsigned long long> &tile_off = gh->tile_off;
-        tile_off.assign(nt + 1, 0);
-        for (int attempt = 0;; ++attempt) {
-            uint32_t flag = 0;
-            {
-                std::lock_guard<std::mutex> lk(c->mtx);
-                if (timing) HIP_TRY(c, hipEventRecord(c->gen_ev[0], st));
-                HIP_TRY(c, hipMemsetAsync(dt + tab_flag, 0, 16, st));
-                if (nwin_total) HIP_TRY(c, hipMemsetAsync(d_win.p, 0, nwin_total * 32, st));
-                if (wide) {
-                    if (ts_k_launch_general_wide((const unsigned char *)d_in.p, (const TsGeneralTile *)d_tiles.p, (uint32_t)nt,
-                                                 (const unsigned long long *)(dt + tab_len), (const unsigned long long *)(dt + tab_win),
-                                                 (const unsigned long long *)(dt + tab_nwin), &c->wpat, &Q,
-                                                 tips ? 1 : 0, slot_cap, (uint32_t *)d_stats.p, (uint32_t *)d_slots.p, (uint32_t *)d_win.p,
-                                                 (uint32_t *)(dt + tab_flag), st) != 0)
-                        return c->fail(TS_ERR_HIP, "general wide kernel launch failed");
-                } else
-                if (ts_k_launch_general_fused((const unsigned char *)d_in.p, (const TsGeneralTile *)d_tiles.p, (uint32_t)nt,
-                                              (const unsigned long long *)(dt + tab_len), (const unsigned long long *)(dt + tab_win),
-                                              (const unsigned long long *)(dt + tab_nwin), &c->gpat, &Q, tips ? 1 : 0, slot_cap, (uint32_t *)d_stats.p, (uint32_t *)d_slots.p,
-                                              (uint32_t *)d_win.p, (uint32_t *)(dt + tab_flag), use_list ? 1 : 0, c->num_cu, st) != 0)
-                    return c->fail(TS_ERR_HIP, "general fused kernel launch failed");
-                if (ts_k_launch_tile_offsets((const uint32_t *)d_stats.p, (uint32_t)nt, (unsigned long long *)d_off.p, d_tmp.p, st) != 0)
-                    return c->fail(TS_ERR_HIP, "tile-offset kernel launch failed");
-                if (timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
-            }
-            const auto te0 = Clock::now();
-            // (pinned landing: asynchronous for real, then one memcpy into the group's own vector)
-            unsigned long long *land = nullptr;
-            if (nt && c->pin_off.ensure(std::max<size_t>((nt + 1) * 8 + 64, 1u << 20)) == hipSuccess) land = (unsigned long long *)c->pin_off.p;
-            else (void)hipGetLastError();
-            uint32_t *flag_land = land ? (uint32_t *)(land + nt + 1) : &flag;
-            if (nt) HIP_TRY(c, hipMemcpyAsync(land ? land : tile_off.data(), d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipMemcpyAsync(flag_land, dt + tab_flag, 4, hipMemcpyDeviceToHost, st));
-            const auto te1 = Clock::now();
-            HIP_TRY(c, hipStreamSynchronize(st));
-            if (land) { std::memcpy(tile_off.data(), land, (nt + 1) * 8); flag = *flag_land; }
-            if (timing) { t_dbg[0] += ms_between(t1, te0); t_dbg[1] += ms_between(te0, te1); t_dbg[2] += ms_between(te1, Clock::now()); }
-            if (timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) t_kern += ms; }
-            if (!flag) break;
-            const uint32_t slot_max = TS_GENERAL_TILE * std::max<uint32_t>(1u, wide ? c->wpat.nlen : c->gpat.nlen);
-            if (attempt > (wide ? 4 : 1) || (slot_cap >= slot_max && !(flag & 2u)))
-                return c->fail(TS_ERR_STATE, "general path: a tile overflowed a slot that holds every match it can have");
-            if (flag & 2u) { use_list = false; continue; }            // a candidate list spilled: the strided form takes this group
-            // (the wide form grows by fours: a slot for every position AND length — 63 of them — is 1 MB per tile)
-            slot_cap = wide ? std::min<uint32_t>(slot_max, slot_cap * 4u) : slot_max;
-            slot_cap_call = slot_cap;
-            c->pool.give(std::move(d_slots));
-            HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)slot_cap * 4, d_slots));
-        }
-        const uint64_t nrec = tile_off[nt];
-        const auto t_f = Clock::now();
-        t_fused += ms_between(t1, t_f);
-        // blocks only, over a stream in position order: block calling reads the records where the fused pass wrote them (it
-        // addresses them through the tile directory), so there is no dense stream to make — every record used to be read and
-        // written once more for nothing
-        const bool in_place = blocks_only && !push_compact;
-        if (!in_place) HIP_TRY(c, c->pool.take(std::max<uint64_t>(nrec, 1) * 4, d_rec));
-        const uint32_t *const d_records = in_place ? (const uint32_t *)d_slots.p : (const uint32_t *)d_rec.p;
-        {
-            std::lock_guard<std::mutex> lk(c->mtx);
-            if (timing) HIP_TRY(c, hipEventRecord(c->gen_ev[0], st));
-            if (in_place) {
-                if (ts_k_launch_general_slot_offsets((unsigned long long *)d_off.p, (uint32_t)nt, slot_cap, st) != 0)
-                    return c->fail(TS_ERR_HIP, "slot-offset kernel launch failed");
-            } else
-            if (push_compact) {
-                if (ts_k_launch_general_compact_push((const TsGeneralTile *)d_tiles.p, (const uint32_t *)d_stats.p, (unsigned long long *)d_off.p,
-                                                     (const uint32_t *)d_slots.p, slot_cap, (uint32_t)nt, (const unsigned long long *)(dt + tab_len),
-                                                     w, s, len_spread, wide ? 1 : 0, gen_lens, wide ? c->wpat.len : nullptr, (uint32_t *)d_rec.p, st) != 0)
-                    return c->fail(TS_ERR_HIP, "general push-order compact kernel launch failed");
-                // (records moved across tile borders: the host stage reads the offsets as they are now)
-                if (!blocks_only) HIP_TRY(c, hipMemcpyAsync(tile_off.data(), d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
-            } else
-            if (ts_k_launch_general_compact((const uint32_t *)d_stats.p, (const unsigned long long *)d_off.p, (const uint32_t *)d_slots.p,
-                                            slot_cap, (uint32_t)nt, (uint32_t *)d_rec.p, st) != 0)
-                return c->fail(TS_ERR_HIP, "general compact kernel launch failed");
-            if (timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
-        }
-        {
-            // ---- blocks on the device: the tiles as blockcall.hip addresses them, the canonical / forward counts, then the walks
-            DevBuf d_bct, d_sbase;
-            struct Ret2 { ts_ctx *c; DevBuf &a, &b2; ~Ret2() { c->pool.give(std::move(a)); c->pool.give(std::move(b2)); } } give2{c, d_bct, d_sbase};
-            HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * sizeof(TsTile), d_bct));
-            HIP_TRY(c, c->pool.take(std::max<size_t>(ns, 1) * 8, d_sbase));
-            std::vector<unsigned long long> sbase(std::max<size_t>(ns, 1), 0ull);
-            std::vector<TsShardSegIn> segtab(ns);
-            unsigned long long X = 0;
-            for (size_t i = 0; i < ns; ++i) {
-                sbase[i] = X;
-                TsShardSegIn &S = segtab[i];
-                S = TsShardSegIn{};
-                S.in_off = X; S.len = G[i].len; S.abs_pos = G[i].abs_pos;
-                S.t0 = S.o0 = (uint32_t)G[i].first_tile; S.t1 = S.o1 = (uint32_t)(G[i].first_tile + G[i].n_tiles);
-                S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-                S.lo_rel = 0; S.hi_rel = G[i].len; S.seg = (uint32_t)i;
-                X += G[i].len + 64;
-            }
-            HIP_TRY(c, hipMemcpyAsync(d_sbase.p, sbase.data(), sbase.size() * 8, hipMemcpyHostToDevice, st));
-            if (ts_k_launch_general_block_inputs((const TsGeneralTile *)d_tiles.p, (const unsigned long long *)d_off.p, d_records,
-                                                 (const unsigned long long *)d_sbase.p, (uint32_t)nt, (TsTile *)d_bct.p, (uint32_t *)d_stats.p,
-                                                 push_compact ? 1 : 0, st) != 0)
-                return c->fail(TS_ERR_HIP, "general block-input kernel launch failed");
-            int rc = ts_device_block_call_raw(c, (const TsTile *)d_bct.p, (const unsigned long long *)d_off.p, (const uint32_t *)d_stats.p,
-                                              d_records, nrec, segtab, nt, tips, gen_lens, nullptr, nullptr, st, gh->blocks, &gh->sums, 0,
-                                              wide ? c->wpat.len : nullptr, push_compact);
-            if (rc != TS_OK) return rc;
-        }
-        const auto t_b = Clock::now();
-        t_blk += ms_between(t_f, t_b);
-        // landing area: the context's pinned download buffers, alternating by group (the host stage of group g reads
-        // its buffer while group g + 1 lands in the other; it has been joined before group g + 2 arrives)
-        {
-            const uint64_t nrec_dl = blocks_only ? 0 : nrec;
-            const size_t rec_bytes = ((size_t)nrec_dl * 4 + 255) & ~(size_t)255, win_bytes = (size_t)nwin_total * 32;
-            PinBuf &pb = c->pin_down[group_no & 1];
-            ++group_no;
-            uint32_t *hrec, *hwin;
-            if (rec_bytes + win_bytes + 256 <= (768ull << 20) && pb.ensure(std::max<size_t>(rec_bytes + win_bytes + 256, 32u << 20)) == hipSuccess) {
-                hrec = (uint32_t *)pb.p;
-                hwin = (uint32_t *)((char *)pb.p + rec_bytes);
-            } else {
-                (void)hipGetLastError();
-                gh->recs_heap.resize(nrec_dl + 1);
-                gh->wins_heap.resize(nwin_total * 8 + 1);
-                hrec = gh->recs_heap.data();
-                hwin = gh->wins_heap.data();
-            }
-            if (nrec_dl) HIP_TRY(c, hipMemcpyAsync(hrec, d_rec.p, nrec_dl * 4, hipMemcpyDeviceToHost, st));
-            if (nwin_total) HIP_TRY(c, hipMemcpyAsync(hwin, d_win.p, nwin_total * 32, hipMemcpyDeviceToHost, st));
-            gh->recs = hrec;
-            gh->wins = hwin;
-        }
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) t_kern += ms; }
-        const auto t2 = Clock::now();
-        t_d2h += ms_between(t_b, t2);
-        t_dev += ms_between(t1, t2);
-        // ---- host: records -> MatchInfo in the reference's push order, window records, the device's blocks; one job per segment
-        if (host_job.joinable()) host_job.join();                     // (one host stage at a time: it takes all the host threads)
-        if (host_err.load() != TS_OK) return host_err.load();
-        host_job = std::thread([c, gh, ns, tips, out, counts, blocks_only, timing, wide, rec_shift, rec_li_mask, &host_err, &t_host]() {
-        try {
-        const auto th0 = Clock::now();
-        const std::vector<SegL> &G = gh->G;
-        const std::vector<TsGeneralTile> &tiles = gh->tiles;
-        const std::vector<unsigned long long> &tile_off = gh->tile_off;
-        const uint32_t *const recs = gh->recs, *const wins = gh->wins;
-        std::atomic<size_t> next{0};
-        std::atomic<int> first_err{TS_OK};
-        const unsigned hw_threads = std::max(1u, std::thread::hardware_concurrency());
-        const unsigned spare = std::max(1u, std::min(16u, hw_threads) / (unsigned)std::max<size_t>(1, std::min<size_t>(ns, 16)));
-        // the device-called blocks of the group, sorted by segment: where each segment's begin
-        std::vector<size_t> blk_at(ns + 1, 0);
-        {
-            size_t q = 0;
-            for (size_t gi = 0; gi < ns; ++gi) {
-                blk_at[gi] = q;
-                while (q < gh->blocks.size() && gh->blocks[q].seg == gi) ++q;
-            }
-            blk_at[ns] = q;
-        }
-        auto worker = [&]() {
-            for (size_t gi; (gi = next.fetch_add(1)) < ns && first_err.load() == TS_OK;) {
-                const SegL &sl = G[gi];
-                const TsDevBlock *pre = gh->blocks.data() + blk_at[gi];
-                const size_t n_pre = blk_at[gi + 1] - blk_at[gi];
-                if (counts)
-                    counts[sl.idx] = ts_segment_counts{tips ? 0 : sl.n_windows, gh->sums[5 * gi + 2], gh->sums[5 * gi + 3], gh->sums[5 * gi + 4]};
-                if (blocks_only) {
-                    // windows + the device's blocks; the match records stayed on the device
-                    const int rc = ts_finalize_segment(c, tips, sl.len, sl.abs_pos, sl.n_windows ? &wins[sl.win_base * 8] : nullptr,
-                                                       tips ? 0 : sl.n_windows, nullptr, 0, out[sl.idx], spare, pre, n_pre);
-                    if (rc != TS_OK) { int e = TS_OK; first_err.compare_exchange_strong(e, rc); return; }
-                    continue;
-                }
-                const uint64_t r0 = tile_off[sl.first_tile], r1 = tile_off[sl.first_tile + sl.n_tiles], nm = r1 - r0;
-                ts_match *arr = nm ? (ts_match *)ts_alloc_large(nm * sizeof(ts_match)) : nullptr;
-                if (nm && !arr) { int e = TS_OK; first_err.compare_exchange_strong(e, c->fail(TS_ERR_ALLOC, "out of host memory")); return; }
-                // a segment's records are expanded by all the threads its job can spare (a group that holds ONE 250 Mb
-                // contig has one job): tile ranges of equal records, one per thread
-                const unsigned nth = nm >= (1u << 18) ? std::max(1u, std::min<unsigned>(spare, (unsigned)(nm >> 17))) : 1u;
-                std::vector<uint64_t> cut(nth + 1, sl.n_tiles);
-                cut[0] = 0;
-                for (unsigned q = 1; q < nth; ++q)
-                    cut[q] = (uint64_t)(std::lower_bound(tile_off.begin() + sl.first_tile, tile_off.begin() + sl.first_tile + sl.n_tiles,
-                                                         r0 + nm * q / nth) - (tile_off.begin() + sl.first_tile));
-                const auto tw0 = Clock::now();
-                auto expand = [&](unsigned q) {
-                    for (uint64_t t = cut[q]; t < cut[q + 1]; ++t) {
-                        const TsGeneralTile &T = tiles[sl.first_tile + t];
-                        uint64_t at = tile_off[sl.first_tile + t] - r0;
-                        for (uint64_t ri = tile_off[sl.first_tile + t]; ri < tile_off[sl.first_tile + t + 1]; ++ri, ++at) {
-                            const uint32_t rec = recs[ri];
-                            const uint64_t p = T.seg_rel + (rec >> rec_shift);
-                            const uint32_t len = wide ? c->wide_lens[(rec >> 2) & rec_li_mask] : c->gpat.len[(rec >> 2) & rec_li_mask];
-                            ts_match &m = arr[at];
-                            std::memset(&m, 0, sizeof m);
-                            m.position = sl.abs_pos + p;
-                            m.match_size = (uint16_t)len;
-                            m.flags = (uint8_t)(((rec & 1u) ? TS_MATCH_FORWARD : 0u) | ((rec & 2u) ? TS_MATCH_CANONICAL : 0u));   // (general records: forward is bit 0)
-                        }
-                    }
-                };
-                if (nth <= 1) expand(0);
-                else {
-                    std::vector<std::thread> ex;
-                    for (unsigned q = 0; q < nth; ++q) ex.emplace_back(expand, q);
-                    for (std::thread &th : ex) th.join();
-                }
-                const auto tw1 = Clock::now();
-                const int rc = ts_finalize_segment(c, tips, sl.len, sl.abs_pos, sl.n_windows ? &wins[sl.win_base * 8] : nullptr,
-                                                   tips ? 0 : sl.n_windows, arr, nm, out[sl.idx], spare, pre, n_pre);
-                if (timing) { ts_gen_ns[0] += (uint64_t)(ms_between(tw0, tw1) * 1e6); ts_gen_ns[1] += (uint64_t)(ms_between(tw1, Clock::now()) * 1e6); }
-                if (rc != TS_OK) { int e = TS_OK; first_err.compare_exchange_strong(e, rc); return; }
-            }
-        };
-        const unsigned nthreads = (unsigned)std::min<size_t>({(size_t)16, ns, (size_t)hw_threads});
-        if (nthreads <= 1) worker();
-        else {
-            std::vector<std::thread> pool;
-            for (unsigned i = 0; i < nthreads; ++i) pool.emplace_back(worker);
-            for (std::thread &th : pool) th.join();
-        }
-        if (first_err.load() != TS_OK) { int e = TS_OK; host_err.compare_exchange_strong(e, first_err.load()); }
-        t_host += ms_between(th0, Clock::now());
-        } catch (...) { int e = TS_OK; host_err.compare_exchange_strong(e, c->fail(TS_ERR_ALLOC, "general path: the host stage ran out of memory")); }
+        int rc = gen_fused(g, *cur);
+        if (rc == TS_OK) rc = gen_blocks(g, *cur);
+        if (rc == TS_OK) rc = gen_download(g, *cur);
+        if (rc != TS_OK) return rc;
+        if (g.host_job.joinable()) g.host_job.join();             // (one host stage at a time: it takes all the host threads)
+        if (g.host_err.load() != TS_OK) return g.host_err.load();
+        g.host_job = std::thread([&g, gh = cur->gh] {
+            int rc2;
+            const auto t0 = Clock::now();
+            try { rc2 = gen_host(g, *gh); }
+            catch (...) { rc2 = g.c->fail(TS_ERR_ALLOC, "general path: the host stage ran out of memory"); }
+            if (rc2 != TS_OK) { int e = TS_OK; g.host_err.compare_exchange_strong(e, rc2); }
+            g.t_host += ms_between(t0, Clock::now());
         });
-        // ---- next group: already uploaded by the prefetch thread
         const auto t_w = Clock::now();
         if (pf.joinable()) pf.join();
-        t_wait_next += ms_between(t_w, Clock::now());
+        g.t_wait_next += ms_between(t_w, Clock::now());
         cur = std::move(nxt);
     }
-    if (host_job.joinable()) host_job.join();
-    if (host_err.load() != TS_OK) return host_err.load();
-    if (timing)
+    if (g.host_job.joinable()) g.host_job.join();
+    if (g.host_err.load() != TS_OK) return g.host_err.load();
+    if (g.timing) {
         fprintf(stderr, "general path: device stage: buffers %.1f ms, fused pass + tile offsets (synced) %.1f ms, compaction + block calling %.1f ms, D2H %.1f ms, waiting for the next group's upload %.1f ms (fused stage: enqueue %.1f, copies enqueue %.1f, sync %.1f)\n",
-                t_take, t_fused, t_blk, t_d2h, t_wait_next, t_dbg[0], t_dbg[1], t_dbg[2]);
-    if (timing)
-        fprintf(stderr, "general path: route: %s form, blocks called on the device, stream %s\n", wide ? "wide" : "table",
-                position_order ? "in position order" : "written in push order by the device");
-    if (timing)
-        fprintf(stderr, "general path: %zu segments, wall %.1f ms: upload %.1f ms, kernels + D2H %.1f ms (kernels alone, HIP events: %.2f ms), host stage %.1f ms (on a thread of its own, one group behind; job time: expansion %.1f ms, windows + blocks %.1f ms)\n",
-                which.size(), ms_between(t_begin, Clock::now()), t_up, t_dev, (double)t_kern, t_host, ts_gen_ns[0].exchange(0) / 1e6, ts_gen_ns[1].exchange(0) / 1e6);
-    return TS_OK;
-}
-
-std::vector<Item> items_of(const ts_segment_in *segs, const std::vector<size_t> &which) {
-    std::vector<Item> v(which.size());
-    for (size_t i = 0; i < which.size(); ++i) v[i] = Item{segs[which[i]].seq, segs[which[i]].len, segs[which[i]].abs_pos, segs[which[i]].input_format, segs[which[i]].n_pieces};
-    return v;
-}
-
-// scanSegment over the subset `which` (all full scans or all tips-only) on the tiled kernel
-int scan_subset(ts_ctx *ctx, Mode mode, const ts_segment_in *segs, const std::vector<size_t> &which, bool tips,
-                ts_segment_out *out, ts_segment_counts *counts, bool have_lock) {
-    if (which.empty()) return TS_OK;
-    const std::vector<Item> items = items_of(segs, which);
-    // results land in arrays parallel to `which`, then move to their places
-    std::vector<ts_segment_out> tmp(which.size());
-    std::vector<ts_segment_counts> cnt(counts ? which.size() : 0);
-    int rc = have_lock ? run_pipeline(ctx, mode, tips, items, tmp.data(), counts ? cnt.data() : nullptr, nullptr)
-                       : submit_pipeline(ctx, mode, tips, items, tmp.data(), counts ? cnt.data() : nullptr, nullptr);
-    if (rc != TS_OK) { ts_free_segments(tmp.data(), tmp.size()); return rc; }
-    for (size_t i = 0; i < which.size(); ++i) {
-        out[which[i]] = tmp[i];
-        if (counts) counts[which[i]] = cnt[i];
+                g.t_take, g.t_fused, g.t_blk, g.t_d2h, g.t_wait_next, g.t_dbg[0], g.t_dbg[1], g.t_dbg[2]);
+        fprintf(stderr, "general path: route: %s form, blocks called on the device, stream %s\n", g.wide ? "wide" : "table",
+                g.position_order ? "in position order" : "written in push order by the device");
+        fprintf(stderr, "general path: %zu segments, wall %.1f ms: upload %.1f ms, kernels + D2H %.1f ms (kernels alone, HIP events: %.2f ms), host stage %.1f ms (on a thread of its own, one group behind)\n",
+                items.size(), ms_between(g.t_begin, Clock::now()), g.t_up, g.t_dev, (double)g.t_kern, g.t_host);
     }
     return TS_OK;
 }
 
-// the general kernels run one call at a time (their groups are not merged across callers)
-int generic_locked(ts_ctx *ctx, const ts_segment_in *segs, const std::vector<size_t> &which, bool tips, ts_segment_out *out, bool have_lock,
-                   bool blocks_only = false, ts_segment_counts *counts = nullptr) {
+// =========================================================================== routing of the entry points
+Item item_of(const ts_segment_in &s) { return Item{s.seq, s.len, s.abs_pos, s.input_format, s.n_pieces}; }
+
+// A call's items of one kind (all full scans or all tips-only) to the tiled pipeline — merged with concurrent callers unless
+// the caller holds the context's call lock — or, for parameter sets the tiled kernel does not take, to the general kernels,
+// one call at a time (their groups are not merged across callers).  Results to o at the items' indices.
+int route(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, Outputs o, bool have_lock) {
+    if (items.empty()) return TS_OK;
+    std::string why;
+    if (tips ? ctx->fast_ok : ts_full_scan_supported(ctx, why))
+        return have_lock ? run_pipeline(ctx, mode, tips, items, o) : submit_pipeline(ctx, mode, tips, items, o);
     // (an exception — std::bad_alloc while a multi-GB group is planned — must leave as an error code: this is a C boundary)
     try {
-        if (have_lock) return scan_group_generic(ctx, segs, which, tips, out, blocks_only, counts);
+        if (have_lock) return scan_general(ctx, mode, tips, items, o);
         std::lock_guard<std::mutex> api(ctx->api_mtx);
-        return scan_group_generic(ctx, segs, which, tips, out, blocks_only, counts);
+        return scan_general(ctx, mode, tips, items, o);
     } catch (const std::exception &e) {
         return ctx->fail(TS_ERR_ALLOC, std::string("general path: ") + e.what());
     }
 }
 
-// ts_scan_segments; have_lock: the caller holds the context's call lock (ts_filter_reads's general path, ts_scan_segments_multi)
-int scan_segments_impl(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out, bool have_lock) {
+// The checks of the segment entry points; every segment's outputs are cleared before its checks.  tips_only: every segment
+// must be a tips-only one (ts_terminal_ends).
+int check_segments(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, Outputs o, bool tips_only) {
     for (size_t i = 0; i < n_segs; ++i) {
-        std::memset(&out[i], 0, sizeof out[i]);
+        if (o.out) std::memset(&o.out[i], 0, sizeof o.out[i]);
+        if (o.counts) o.counts[i] = ts_segment_counts{0, 0, 0, 0};
+        if (o.ends) o.ends[2 * i] = o.ends[2 * i + 1] = 0u;
+        if (tips_only && !segs[i].tips_only) return ctx->fail(TS_ERR_INVALID_ARG, "ts_terminal_ends: every segment must be tips_only");
         if (segs[i].len && !segs[i].seq) return ctx->fail(TS_ERR_INVALID_ARG, "null sequence pointer");
         if (segs[i].input_format > TS_INPUT_PACKED2) return ctx->fail(TS_ERR_INVALID_ARG, "unknown input_format");
     }
-    std::vector<size_t> full, tips;
-    for (size_t i = 0; i < n_segs; ++i) (segs[i].tips_only ? tips : full).push_back(i);
-    std::string why;
-    int rc = ts_full_scan_supported(ctx, why) ? scan_subset(ctx, Mode::Matches, segs, full, false, out, nullptr, have_lock)
-                                              : generic_locked(ctx, segs, full, false, out, have_lock);
-    if (rc == TS_OK) rc = ctx->fast_ok ? scan_subset(ctx, Mode::Matches, segs, tips, true, out, nullptr, have_lock)
-                                       : generic_locked(ctx, segs, tips, true, out, have_lock);
-    if (rc != TS_OK) ts_free_segments(out, n_segs);
+    return TS_OK;
+}
+
+// ts_scan_segments (Matches) and ts_scan_segments_blocks (Blocks): the full scans, then the tips-only scans, each routed on its
+// own into arrays of their own and moved to the segments' places.  have_lock: the caller holds the context's call lock
+// (ts_scan_segments_multi).
+int scan_segments_impl(ts_ctx *ctx, Mode mode, const ts_segment_in *segs, size_t n_segs, Outputs o, bool have_lock) {
+    int rc = check_segments(ctx, segs, n_segs, o, false);
+    if (rc != TS_OK) return rc;
+    for (const bool tips : {false, true}) {
+        std::vector<size_t> which;
+        for (size_t i = 0; i < n_segs; ++i) if ((segs[i].tips_only != 0) == tips) which.push_back(i);
+        std::vector<Item> items(which.size());
+        for (size_t i = 0; i < which.size(); ++i) items[i] = item_of(segs[which[i]]);
+        std::vector<ts_segment_out> out(which.size());
+        std::vector<ts_segment_counts> counts(o.counts ? which.size() : 0);
+        rc = route(ctx, mode, tips, items, Outputs{out.data(), o.counts ? counts.data() : nullptr, nullptr, nullptr}, have_lock);
+        if (rc != TS_OK) { ts_free_segments(out.data(), out.size()); break; }
+        for (size_t i = 0; i < which.size(); ++i) {
+            o.out[which[i]] = out[i];
+            if (o.counts) o.counts[which[i]] = counts[i];
+        }
+    }
+    if (rc != TS_OK) ts_free_segments(o.out, n_segs);
     return rc;
 }
 
 }  // namespace
 
 int ts_scan_segments_unlocked(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out) {
-    return scan_segments_impl(ctx, segs, n_segs, out, true);
+    return scan_segments_impl(ctx, Mode::Matches, segs, n_segs, Outputs{out}, true);
 }
 
 // the pieces of the pipeline that ts_scan_segments_multi (multi.cpp) runs per context
 int ts_pipeline_ensure_streams(ts_ctx *c) { return ensure_streams(c); }
 int ts_pipeline_upload_batch(ts_batch *b, const ts_segment_in *segs, int *slot, bool used[]) {
     std::vector<Item> items(b->segs.size());
-    for (size_t i = 0; i < items.size(); ++i) items[i] = Item{segs[i].seq, segs[i].len, segs[i].abs_pos, segs[i].input_format, segs[i].n_pieces};
+    for (size_t i = 0; i < items.size(); ++i) items[i] = item_of(segs[i]);
     return upload_batch(b, items.data(), *slot, used);
 }
 
@@ -1512,7 +1525,7 @@ extern "C" {
 
 int ts_scan_segments(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out) {
     if (!ctx || (n_segs && (!segs || !out))) return TS_ERR_INVALID_ARG;
-    return scan_segments_impl(ctx, segs, n_segs, out, false);
+    return scan_segments_impl(ctx, Mode::Matches, segs, n_segs, Outputs{out}, false);
 }
 
 // scanSegment for callers that do not read the match vectors: scan, block calling and the per-segment
@@ -1520,44 +1533,12 @@ int ts_scan_segments(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_s
 int ts_scan_segments_blocks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out,
                             ts_segment_counts *counts) {
     if (!ctx || (n_segs && (!segs || !out))) return TS_ERR_INVALID_ARG;
-    for (size_t i = 0; i < n_segs; ++i) {
-        std::memset(&out[i], 0, sizeof out[i]);
-        if (counts) counts[i] = ts_segment_counts{0, 0, 0, 0};
-        if (segs[i].len && !segs[i].seq) return ctx->fail(TS_ERR_INVALID_ARG, "null sequence pointer");
-        if (segs[i].input_format > TS_INPUT_PACKED2) return ctx->fail(TS_ERR_INVALID_ARG, "unknown input_format");
-    }
-    std::vector<size_t> full, tips;
-    for (size_t i = 0; i < n_segs; ++i) (segs[i].tips_only ? tips : full).push_back(i);
-    // parameter sets outside the tiled kernel take the general path and drop the match vectors afterwards
-    auto via_matches = [&](const std::vector<size_t> &which, bool tips_mode) -> int {
-        // (blocks on the device and no record download where the match stream is in calling order; else the host path, whose
-        // match vectors are counted and dropped here)
-        if (counts) for (size_t i : which) counts[i] = ts_segment_counts{~0ull, 0, 0, 0};
-        int rc = generic_locked(ctx, segs, which, tips_mode, out, false, true, counts);
-        if (rc != TS_OK) return rc;
-        for (size_t i : which) {
-            if (counts && counts[i].n_windows == ~0ull) {
-                ts_segment_counts cnt{tips_mode ? 0 : out[i].n_windows, out[i].n_matches, 0, 0};
-                for (uint64_t m = 0; m < out[i].n_matches; ++m) {
-                    cnt.n_canonical += (out[i].matches[m].flags & TS_MATCH_CANONICAL) ? 1 : 0;
-                    cnt.n_forward += (out[i].matches[m].flags & TS_MATCH_FORWARD) ? 1 : 0;
-                }
-                counts[i] = cnt;
-            }
-            std::free(out[i].matches);
-            out[i].matches = nullptr;
-            out[i].n_matches = 0;
-        }
-        return TS_OK;
-    };
-    std::string why;
-    int rc = ts_full_scan_supported(ctx, why) ? scan_subset(ctx, Mode::Blocks, segs, full, false, out, counts, false) : via_matches(full, false);
-    if (rc == TS_OK) rc = ctx->fast_ok ? scan_subset(ctx, Mode::Blocks, segs, tips, true, out, counts, false) : via_matches(tips, true);
-    if (rc != TS_OK) ts_free_segments(out, n_segs);
-    return rc;
+    return scan_segments_impl(ctx, Mode::Blocks, segs, n_segs, Outputs{out, counts}, false);
 }
 
 // =========================================================================== ReadTelomereFilter
+// Whole-read tips-only scans.  Tiled sets: the terminal-block predicate on the device, one byte per read back.  Other sets
+// (mixed lengths, k > 8): the general kernels' blocks; a read passes with a terminal block.
 int ts_filter_reads(ts_ctx *ctx, const char *const *seqs, const uint64_t *lens, size_t n_reads,
                     uint8_t *pass) {
     if (!ctx || (n_reads && (!seqs || !lens || !pass))) return TS_ERR_INVALID_ARG;
@@ -1570,49 +1551,21 @@ int ts_filter_reads(ts_ctx *ctx, const char *const *seqs, const uint64_t *lens, 
         if (n && seqs[i][n - 1] == '\r') --n;             // src/read-filter.cpp:38-40
         items[i] = Item{seqs[i], n, 0, TS_INPUT_BASES, 0};
     }
-    if (!ctx->fast_ok) {
-        // pattern sets outside the tiled kernel (mixed lengths, k > 8): the general kernels in their blocks-only form — a
-        // tips-only scan's stream is in calling order, so the blocks are called on the device and no match record leaves it
-        // (the wide form alone keeps host block calling); all the filter reads is whether a read has a terminal block
-        std::vector<ts_segment_in> in(n_reads);
-        std::vector<size_t> all(n_reads);
-        for (size_t i = 0; i < n_reads; ++i) { in[i] = ts_segment_in{}; in[i].seq = items[i].seq; in[i].len = items[i].len; in[i].abs_pos = 0; in[i].tips_only = 1; all[i] = i; }
-        std::vector<ts_segment_out> out(n_reads);
-        for (size_t i = 0; i < n_reads; ++i) std::memset(&out[i], 0, sizeof out[i]);
-        int rc = generic_locked(ctx, in.data(), all, true, out.data(), false, true, nullptr);
-        if (rc != TS_OK) { ts_free_segments(out.data(), n_reads); return rc; }
-        for (size_t i = 0; i < n_reads; ++i) pass[i] = out[i].n_terminal_blocks != 0;
-        ts_free_segments(out.data(), n_reads);
-        return TS_OK;
-    }
-    // tiled path: whole-read tips scan, then the terminal-block predicate on the device; only one
-    // byte per read comes back
-    return submit_pipeline(ctx, Mode::ReadPass, true, items, nullptr, nullptr, pass);
+    return route(ctx, Mode::ReadPass, true, items, Outputs{nullptr, nullptr, pass}, false);
 }
 
 // =========================================================================== GFA annotation: per-end terminal lengths
 // ends[2i] / ends[2i+1]: the longest terminal block at the start / end side of segs[i] (walkSegment's rule,
 // src/input.cpp:835-881).  Tiled sets: a tips-only batch, the scan, the predicate's walks in their ENDS form
-// (predicate.hip) and 8 bytes per segment back.  Other sets: the general kernels' blocks-only form, reduced here.
+// (predicate.hip) and 8 bytes per segment back.  Other sets: the general kernels' blocks, reduced on the host.
 int ts_terminal_ends(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, uint32_t *ends) {
     if (!ctx || (n_segs && (!segs || !ends))) return TS_ERR_INVALID_ARG;
-    for (size_t i = 0; i < n_segs; ++i) {
-        ends[2 * i] = ends[2 * i + 1] = 0u;
-        if (!segs[i].tips_only) return ctx->fail(TS_ERR_INVALID_ARG, "ts_terminal_ends: every segment must be tips_only");
-        if (segs[i].len && !segs[i].seq) return ctx->fail(TS_ERR_INVALID_ARG, "null sequence pointer");
-        if (segs[i].input_format > TS_INPUT_PACKED2) return ctx->fail(TS_ERR_INVALID_ARG, "unknown input_format");
-    }
-    if (n_segs == 0) return TS_OK;
-    std::vector<size_t> all(n_segs);
-    for (size_t i = 0; i < n_segs; ++i) all[i] = i;
-    if (ctx->fast_ok) return submit_pipeline(ctx, Mode::Ends, true, items_of(segs, all), nullptr, nullptr, nullptr, ends);
-    std::vector<ts_segment_out> out(n_segs);
-    for (size_t i = 0; i < n_segs; ++i) std::memset(&out[i], 0, sizeof out[i]);
-    const int rc = generic_locked(ctx, segs, all, true, out.data(), false, true, nullptr);
-    if (rc == TS_OK)
-        for (size_t i = 0; i < n_segs; ++i) reduce_terminal_ends(out[i], segs[i].len, segs[i].abs_pos, ends + 2 * i);
-    ts_free_segments(out.data(), n_segs);
-    return rc;
+    const Outputs o{nullptr, nullptr, nullptr, ends};
+    const int rc = check_segments(ctx, segs, n_segs, o, true);
+    if (rc != TS_OK) return rc;
+    std::vector<Item> items(n_segs);
+    for (size_t i = 0; i < n_segs; ++i) items[i] = item_of(segs[i]);
+    return route(ctx, Mode::Ends, true, items, o, false);
 }
 
 // ReadTelomereFilter::matches over a device-resident tips-only batch (reads already in HBM, scanned on `stream`):
@@ -1631,14 +1584,11 @@ int ts_batch_read_pass_status(ts_batch *b, int *overflowed) {
     DEVICE_TRY(c);
     *overflowed = 0;
     if (!b->d_readtab.p) return TS_OK;                            // no pass was ever enqueued
-    const size_t ns = b->segs.size();
-    const size_t off_in = (((ns + 1) * 4 + 15) & ~(size_t)15), off_len = off_in + ns * 8, off_long = off_len + ns * 8,
-                 off_count = (off_long + ns * 4 + 15) & ~(size_t)15, off_flag = off_count + 16;
+    char *const flag_at = (char *)b->d_readtab.p + ReadTab(b->segs.size()).flag;
     uint32_t flag = 0;
-    char *const dt = (char *)b->d_readtab.p;
     HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(&flag, dt + off_flag, 4, hipMemcpyDeviceToHost));
-    if (flag) HIP_TRY(c, hipMemset(dt + off_flag, 0, 4));
+    HIP_TRY(c, hipMemcpy(&flag, flag_at, 4, hipMemcpyDeviceToHost));
+    if (flag) HIP_TRY(c, hipMemset(flag_at, 0, 4));
     *overflowed = flag ? 1 : 0;
     return TS_OK;
 }

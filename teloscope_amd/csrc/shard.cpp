@@ -207,19 +207,6 @@ void fill_shard_info(const ts_batch *b, uint32_t n_parts, uint32_t part, uint32_
     o.context_tiles = shard_geom(b).ctx;
 }
 
-// f(i) for i in [0, n) on up to max_threads host threads
-template <typename F>
-void parallel_for(size_t n, unsigned max_threads, F &&f) {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned nt = (unsigned)std::min<size_t>({(size_t)max_threads, (size_t)hw, n});
-    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < nt; ++t)
-        pool.emplace_back([&] { for (size_t i; (i = next.fetch_add(1)) < n;) f(i); });
-    for (std::thread &th : pool) th.join();
-}
-
 }  // namespace
 
 void ts_shard_boundaries(const ts_batch *b, uint32_t n_parts, std::vector<uint64_t> &out) { shard_boundaries(b, n_parts, out); }
@@ -563,21 +550,11 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
         if (!b->tips && pv.vis_off[nown] != pv.H->n_visible)
             return c->fail(TS_ERR_STATE, "ts_shards_finalize: a message's per-tile counts do not add up to its record count");
     }
-    int rc = TS_OK;
-    for (size_t si = 0; si < ns && rc == TS_OK; ++si) {
-        const SegPlan &sp = b->segs[si];
-        if (!b->tips && sp.n_windows) {
-            out[si].windows = (ts_window *)std::malloc(sp.n_windows * sizeof(ts_window));
-            if (!out[si].windows) rc = c->fail(TS_ERR_ALLOC, "out of host memory");
-            out[si].n_windows = sp.n_windows;
+    for (size_t si = 0; si < ns; ++si)
+        if (!ts_alloc_segment(out[si], b->tips ? 0 : b->segs[si].n_windows, seg_nvis[si])) {
+            ts_free_segments(out, ns);
+            return c->fail(TS_ERR_ALLOC, "out of host memory");
         }
-        if (rc == TS_OK && seg_nvis[si]) {
-            out[si].matches = (ts_match *)std::malloc(seg_nvis[si] * sizeof(ts_match));
-            if (!out[si].matches) rc = c->fail(TS_ERR_ALLOC, "out of host memory");
-            out[si].n_matches = seg_nvis[si];
-        }
-    }
-    if (rc != TS_OK) { ts_free_segments(out, ns); return rc; }
     // index (within its segment's array) of the first visible record of the first owned tile of every (part, segment)
     // = the visible records of the segment's tiles owned by earlier parts
     std::vector<std::vector<uint64_t>> seg_base(n_parts);
@@ -603,9 +580,7 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
     }
     const bool nuc = P.out_gc || P.out_entropy;
     const uint16_t klen = (uint16_t)c->k;
-    unsigned nthreads = 16;
-    if (const char *e = getenv("TS_HOST_THREADS")) { const int n = atoi(e); if (n > 0) nthreads = (unsigned)n; }
-    parallel_for(pieces.size(), nthreads, [&](size_t pi) {
+    ts_parallel_for(pieces.size(), ts_host_threads(), [&](size_t pi) {
         const Piece &pc = pieces[pi];
         const PartView &pv = parts[pc.p];
         if (pc.windows) {
@@ -626,18 +601,9 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
                 uint32_t f[7] = {0, 0, 0, 0, 0, 0, 0};
                 const uint32_t nf = nuc ? 7u : 3u;
                 for (uint32_t q = 0; q < nf; ++q) f[nuc ? q : q + 4u] = (uint32_t)((uint64_t)(v >> (q * B)) & mask);
-                ts_window &w = out[si].windows[kwin];
-                std::memset(&w, 0, sizeof w);
-                const uint64_t ws = kwin * P.step;
-                w.window_start = sp.abs_pos + ws;
-                w.current_window_size = (uint32_t)std::min<uint64_t>(P.window_size, sp.len - ws);
-                if (nuc) for (int q = 0; q < 4; ++q) w.nucleotide_counts[q] = f[q];
-                if (P.out_gc) w.gc_content = ts::gc_content(w.nucleotide_counts, w.current_window_size);
-                if (P.out_entropy) w.shannon_entropy = ts::shannon_entropy_memo(w.nucleotide_counts, w.current_window_size, c->entropy_term);
-                w.canonical_covered = f[4] * klen;
-                w.non_canonical_covered = f[5] * klen;
-                w.fwd_covered = f[6] * klen;
-                w.rev_covered = (f[4] + f[5] - f[6]) * klen;
+                // covered bases from the match counts: every match is klen long, and rev = canonical + non-canonical - forward
+                const uint32_t r[8] = {f[0], f[1], f[2], f[3], f[4] * klen, f[5] * klen, f[6] * klen, (f[4] + f[5] - f[6]) * klen};
+                ts_fill_window(c, kwin, sp.len, sp.abs_pos, r, out[si].windows[kwin]);
             }
             return;
         }
@@ -647,7 +613,7 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
             const TsTile &T = b->tiles[pv.r.own_lo + i];
             const SegPlan &sp = b->segs[T.seg];
             const uint64_t rel0 = T.in_off - sp.in_off;
-            const uint64_t term_end = sp.len > P.terminal_limit ? sp.len - P.terminal_limit : 0;
+            const uint64_t term_end = ts_terminal_end(sp.len, P.terminal_limit);
             // where the tile's records go: records of the segment's earlier tiles of this part precede them
             uint64_t at = seg_base[pc.p][T.seg - pv.r.seg_begin];
             const uint64_t first_own = std::max<uint64_t>(sp.first_tile, pv.r.own_lo);
@@ -660,7 +626,7 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
                 m[q].position = sp.abs_pos + rel;
                 m[q].match_size = klen;
                 m[q].flags = (uint8_t)(((rec & 2u) ? TS_MATCH_FORWARD : 0u) | ((rec & 1u) ? TS_MATCH_CANONICAL : 0u) |
-                                       ((rel <= P.terminal_limit || rel >= term_end) ? TS_MATCH_TERMINAL : 0u));
+                                       (ts_is_terminal(rel, P.terminal_limit, term_end) ? TS_MATCH_TERMINAL : 0u));
             }
         }
     });
@@ -676,6 +642,7 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
             }
         blocks.insert(blocks.end(), src, src + pv.H->n_blocks);
     }
+    // (not ts_device_block_call_raw's comparator: that one orders interstitial blocks by their stream index before their start)
     std::sort(blocks.begin(), blocks.end(), [](const TsDevBlock &x, const TsDevBlock &y) {
         if (x.seg != y.seg) return x.seg < y.seg;
         const uint32_t kx = x.kind == 2 ? 1 : 0, ky = y.kind == 2 ? 1 : 0;
@@ -684,26 +651,7 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
         return x.kind != y.kind ? x.kind < y.kind : x.seq < y.seq;
     });
     size_t bi = 0;
-    for (size_t si = 0; si < ns; ++si) {
-        size_t nterm = 0, nits = 0;
-        const size_t b0 = bi;
-        while (bi < blocks.size() && blocks[bi].seg == si) { (blocks[bi].kind == 2 ? nits : nterm)++; ++bi; }
-        auto fill = [&](ts_block *&dst, uint64_t &n, size_t count, bool its) -> bool {
-            n = count; dst = nullptr;
-            if (!count) return true;
-            dst = (ts_block *)std::malloc(count * sizeof(ts_block));
-            if (!dst) return false;
-            size_t at = 0;
-            for (size_t q = b0; q < bi; ++q)
-                if ((blocks[q].kind == 2) == its) std::memcpy(&dst[at++], &blocks[q], sizeof(ts_block));
-            return true;
-        };
-        if (!fill(out[si].terminal_blocks, out[si].n_terminal_blocks, nterm, false) ||
-            !fill(out[si].interstitial_blocks, out[si].n_interstitial_blocks, nits, true)) {
-            ts_free_segments(out, ns);
-            return c->fail(TS_ERR_ALLOC, "out of host memory");
-        }
-    }
+    if (!ts_split_blocks(blocks.data(), blocks.size(), out, ns, bi)) { ts_free_segments(out, ns); return c->fail(TS_ERR_ALLOC, "out of host memory"); }
     if (bi != blocks.size()) { ts_free_segments(out, ns); return c->fail(TS_ERR_STATE, "ts_shards_finalize: a block names a segment outside the batch"); }
     return TS_OK;
 }
