@@ -509,7 +509,12 @@ int ts_batch_pack_shard(ts_batch *b, void *d_msg, uint64_t msg_bytes, void *stre
  * that ts_batch_pack_shard then packs in a pass of its own: the pack has one kernel fewer and the scan stores a quarter of
  * the bytes.  The 8 x uint32 records of such a scan are NOT produced (ts_batch_windows_ptr / ts_batch_download see none), and
  * ts_batch_pack_shard must be given the same buffer (TS_ERR_STATE otherwise).  The message's bytes do not depend on it.
- * d_msg == NULL unbinds; ts_batch_set_shard_scale unbinds (the message's size changes with the scale). */
+ * d_msg == NULL unbinds; ts_batch_set_shard_scale unbinds (the message's size changes with the scale).
+ * Ordering: every scan of the batch writes the bound message, not only its pack.  A bound message must therefore not be in
+ * flight — sent, copied, read by any stream — when the next scan of that batch is enqueued: make the scan's stream wait for
+ * the reader first (an event recorded behind the send or copy).  An event recorded behind the pack is not enough: the next
+ * scan would overwrite the window section of a message whose transfer has not finished, and the receiver would get the
+ * window records of two different scans in one message (teloscope_amd/distributed.py: PackedShard.release). */
 int ts_batch_bind_shard_message(ts_batch *b, void *d_msg, uint64_t msg_bytes);
 #define TS_SHARD_OVERFLOW_VISIBLE 0x1u   /* ts_shard_status.flags */
 #define TS_SHARD_OVERFLOW_BLOCKS  0x2u

@@ -1196,7 +1196,7 @@ int ts_batch_get_info(const ts_batch *b, ts_batch_info *info) {
 }
 
 const void *ts_batch_windows_ptr(const ts_batch *b) { return b ? b->windows_ptr() : nullptr; }
-const void *ts_batch_matches_ptr(const ts_batch *b) { return b && !b->kp.rec16 ? b->records_ptr() : nullptr; }   // (16-bit records: no raw view)
+const void *ts_batch_matches_ptr(const ts_batch *b) { return b && !b->records16() ? b->records_ptr() : nullptr; }   // (16-bit regions: no raw view; a dense stream is 32-bit)
 const void *ts_batch_tile_stats_ptr(const ts_batch *b) { return b ? b->stats_ptr() : nullptr; }
 
 int ts_batch_export(ts_batch *b, void *d_dense, uint64_t dense_capacity, void *d_total, void *stream) {

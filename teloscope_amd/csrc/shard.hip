@@ -122,8 +122,11 @@ void ts_shard_copy_visible(const TsShardPackParams P, const u64 *vis_off, u64 ca
         dst0 = vis_off[i];
         // A wave whose visible region overflowed in the scan (wave_fill[nwaves + w] > vis_cap; ts_overflow_flag reports it and the
         // caller rescans) did not store the records it promises here: src0 = wave * vis_cap + the wave's cursor, and a cursor past
-        // the region's end would be read out of the next waves' regions — for the last waves, past the end of vis_src.
-        if (P.vis_cap == 0u || (src0 % P.vis_cap) + n > P.vis_cap) n = 0;
+        // the region's end would be read out of the next waves' regions — for the last waves, past the end of vis_src.  The
+        // modulo test catches the tile that straddles a region's end; a later tile of the same wave starts past it and wraps
+        // back into range, so the copy is also bounded by the whole buffer (what it reads then lies in a message whose header
+        // says SCAN_OVERFLOW, and is not trusted).
+        if (P.vis_cap == 0u || (src0 % P.vis_cap) + n > P.vis_cap || src0 + n > (u64)P.vis_cap * P.nwaves) n = 0;
     }
     if (vis_off[nown] > capacity) return;                     // does not fit: nothing is written, the header reports it
     if (n <= kVisOwn) {

@@ -473,7 +473,11 @@ def concurrent_streams(teloscope, device, n, first=None, tries=24):
 class PackedShard:
     """One rank's shard on its GPU (ts_batch_restrict_shard): scan + device block calling + packed message, all
     asynchronous on the caller's stream.  `slots` message buffers (each with its own batch object) let the
-    transfer of one scan's message overlap the next scan."""
+    transfer of one scan's message overlap the next scan.
+
+    A slot's message is written by its scan (a bound message: the window section) and by its pack, so whatever reads
+    it — the transfer ShardExchange.post enqueues, a copy to the host — must be done before the slot is scanned
+    again: hand that reader to `release(slot, ...)` and the slot's next scan waits for it on the device."""
 
     def __init__(self, plan: ShardPlan, part: int, device, slots: int = 1, scale: int = 1):
         import torch
@@ -481,6 +485,7 @@ class PackedShard:
         self.L = plan.L
         self.info = shard_info(plan, part, scale)
         self.batches, self.msgs = [], []
+        self._readers = [[] for _ in range(slots)]             # per slot: what the next scan waits for (see release)
         for _ in range(slots):
             b = plan.new_batch()
             rc = self.L.ts_batch_restrict_shard(b, plan.world, part, scale)
@@ -499,8 +504,36 @@ class PackedShard:
         if rc != K.TS_OK:
             raise K.TeloscanError(rc, self.plan.teloscope._ctx.error())
 
+    def release(self, slot, reader):
+        """The slot's message is being read by `reader`: a torch.cuda.Event recorded behind the read, a torch stream the
+        read was enqueued on (an event is recorded on it now), or the works ShardExchange.post returned.  The slot's next
+        scan is ordered behind it (its stream waits on the device; a work of a host-side backend is waited for on the
+        host), so that neither that scan nor the pack after it writes the message while it is still in flight."""
+        import torch
+        if isinstance(reader, torch.cuda.Stream):
+            ev = torch.cuda.Event()
+            ev.record(reader)
+            reader = ev
+        self._readers[slot].extend(reader if isinstance(reader, (list, tuple)) else [reader])
+
+    def _wait_readers(self, stream_ptr, slot):
+        import torch
+        readers, self._readers[slot] = self._readers[slot], []
+        if not readers:
+            return
+        ptr = int(getattr(stream_ptr, "value", stream_ptr) or 0)
+        stream = torch.cuda.ExternalStream(ptr, device=self.device) if ptr else torch.cuda.default_stream(self.device)
+        for r in readers:
+            if isinstance(r, torch.cuda.Event):
+                stream.wait_event(r)
+            else:                                              # a torch.distributed work: wait() orders the current stream
+                with torch.cuda.stream(stream):
+                    r.wait()
+
     def scan(self, d_input, stream_ptr, slot=0):
-        """Enqueue the scan of the shard's tiles.  d_input: device address of byte `info.input_begin` of the input layout."""
+        """Enqueue the scan of the shard's tiles, behind the slot's released readers (release).  d_input: device address
+        of byte `info.input_begin` of the input layout."""
+        self._wait_readers(stream_ptr, slot)
         rc = self.L.ts_batch_scan(self.batches[slot], C.c_void_p(d_input), stream_ptr)
         if rc != K.TS_OK:
             raise K.TeloscanError(rc, self.plan.teloscope._ctx.error())
@@ -607,7 +640,8 @@ class ShardExchange:
 
     def post(self, msg, slot=0):
         """Enqueue the transfer of this rank's message (`msg`: its device tensor, packed on the current stream);
-        returns the works to wait for before the slot's buffers are reused."""
+        returns the works to wait for before the slot's buffers are reused (PackedShard.release(slot, works) orders the
+        slot's next scan behind them)."""
         import torch.distributed as dist
         if self.world == 1:
             return []
