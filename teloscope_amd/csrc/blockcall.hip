@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ts_device.h"
 #include "ts_internal.h"
 
 // ONE-WAVE WORKGROUPS.  These kernels run beside the persistent scan kernel of the next batch, whose two workgroups of ten
@@ -64,14 +65,7 @@ __device__ __forceinline__ uint32_t rec_len(const TsBlockCallParams &Q, uint32_t
 }
 // sum of v over the lanes of `mask` (wave-uniform result)
 __device__ __forceinline__ uint32_t masked_sum(uint32_t v, u64 mask) {
-    uint32_t x = ((mask >> (threadIdx.x & 63u)) & 1ull) ? v : 0u;
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+    return wave_total(((mask >> (threadIdx.x & 63u)) & 1ull) ? v : 0u);
 }
 
 struct SegView {
@@ -107,23 +101,6 @@ __device__ __forceinline__ void emit_block(const TsBlockCallParams &Q, TsDevBloc
     b.start += abs_pos;
     b.seg = seg; b.kind = kind; b.seq = seq; b.pad = seq_hi;
     Q.blocks[slot] = b;
-}
-
-// Wave-wide inclusive prefix maximum in 6 DPP steps (row_shr 1/2/4/8 inside each row of 16, then row_bcast:15
-// into rows 1,3 and row_bcast:31 into rows 2,3); lanes outside a shift read 0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_max(uint32_t v) {
-    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-    return v > o ? v : o;
-}
-__device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {
-    v = dpp_max<0x111, 0xf>(v);
-    v = dpp_max<0x112, 0xf>(v);
-    v = dpp_max<0x114, 0xf>(v);
-    v = dpp_max<0x118, 0xf>(v);
-    v = dpp_max<0x142, 0xa>(v);
-    v = dpp_max<0x143, 0xc>(v);
-    return v;
 }
 
 // One direction of getTerminalBlocks for one segment; returns the boundary.  Run by a whole wave, 64 records
@@ -234,7 +211,7 @@ __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, co
                 before = below_me ? v : 0u;
             } else {
                 const uint32_t incl = wave_scan_max(sel ? (from_start ? p32 + 1u : ~p32) : 0u);
-                before = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x138, 0xf, 0xf, false);   // wave_shr:1
+                before = lane_below(incl);
             }
             const uint32_t gap_in = from_start ? p32 - (before - 1u) : ~before - p32;
             const uint32_t first_lane = (uint32_t)__builtin_ctzll(rem);
@@ -455,16 +432,6 @@ __device__ char its_label(uint32_t fwd_count, uint32_t counts) {
     if (ratio < 33.3f) return 'q';
     return 'b';
 }
-
-// The value of the lane below (lane 0: 0) by DPP wave_shr:1.  The empty asm keeps it a v_mov_b32_dpp: folded into the
-// subtraction that follows (v_subrev_u32_dpp v, x, x wave_shr:1, what the DPP combiner makes of it) it came back wrong on gfx950.
-__device__ __forceinline__ uint32_t lane_below(uint32_t v) {
-    uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);
-    asm volatile("" : "+v"(r));
-    return r;
-}
-
-__device__ __forceinline__ u64 low_bits(uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }
 
 // The chain that starts at record i0 of tile t0, walked record by record (64 per step) to its end — the first record more
 // than -k behind its predecessor, the first at or behind rb, or the end of the view — and, if it passes the reference's

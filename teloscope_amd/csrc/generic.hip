@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "ts_device.h"
 #include "ts_internal.h"
 
 namespace {
@@ -41,16 +42,6 @@ constexpr uint32_t kMaxLdsPatterns = 4096;       // (9 bytes of LDS each: the li
 // traffic per 3 Gb); then canonical, non-canonical, forward, reverse covered
 struct Acc { uint32_t nuc, can, non, fwd, rev; };
 
-__device__ __forceinline__ uint32_t wave_total(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 // Inclusive prefix sum over the wave's lanes.
 __device__ __forceinline__ uint32_t wave_inclusive(uint32_t v, uint32_t lane) {
 #pragma unroll
@@ -60,6 +51,17 @@ __device__ __forceinline__ uint32_t wave_inclusive(uint32_t v, uint32_t lane) {
     }
     return v;
 }
+
+// analyzeWindow's start index of a call that is not window 0 of a segment with overlapping windows: uint32 arithmetic on
+// purpose, as there (src/teloscope.cpp:413-415; it wraps when the longest pattern exceeds step or overlap)
+// (ov: the overlap w - s)
+__device__ __forceinline__ uint32_t inner_start_index(const TsGenericGeom &Q, uint32_t ov) {
+    const uint32_t t1 = Q.s - Q.longest, t2 = ov - Q.longest;
+    return t1 < t2 ? t1 : t2;
+}
+// the start index of call kw (always_main: window 0, or windows that do not overlap), and that of its carry: i >= step
+__device__ __forceinline__ uint32_t call_start(bool always_main, uint32_t inner) { return always_main ? 0u : inner; }
+__device__ __forceinline__ uint32_t carry_start(uint32_t start, uint32_t s) { return start < s ? s : start; }
 
 // Per tile, what the push test needs of the segment's geometry — computed once (two 64-bit divisions), so that the
 // test itself is 32-bit arithmetic relative to the tile.
@@ -79,8 +81,7 @@ struct PushGeom {
 __device__ __forceinline__ PushGeom push_geom(u64 P0, u64 n, const TsGenericGeom &Q) {
     PushGeom g{};
     g.P0 = P0; g.n = n; g.s = Q.s; g.w = Q.w; g.ov = Q.w - Q.s;
-    const uint32_t t1 = Q.s - Q.longest, t2 = g.ov - Q.longest;       // uint32 on purpose (src/teloscope.cpp:413-415)
-    g.start_index = t1 < t2 ? t1 : t2;
+    g.start_index = inner_start_index(Q, g.ov);
     if (g.ov == 0u) {
         const u64 k0 = P0 / Q.s;
         g.r0 = (uint32_t)(P0 - k0 * Q.s);
@@ -99,56 +100,114 @@ __device__ __forceinline__ PushGeom push_geom(u64 P0, u64 n, const TsGenericGeom
     return g;
 }
 
+// The same from the host's quotients (P0 = k_p0 s + r_p0 per tile, w = cw s + rw per call): sums and compares, no 64-bit division.
+__device__ __forceinline__ PushGeom push_geom_tile(const TsGeneralTile &T, u64 n, const TsGenericGeom &Q) {
+    PushGeom g{};
+    const u64 P0 = T.seg_rel;
+    const uint32_t ov = Q.w - Q.s;
+    g.P0 = P0; g.n = n; g.s = Q.s; g.w = Q.w; g.ov = ov;
+    g.start_index = inner_start_index(Q, g.ov);
+    g.kP0 = T.k_p0; g.rP0 = T.r_p0;
+    if (ov == 0u) {
+        g.k0 = T.k_p0; g.r0 = T.r_p0;
+        g.N0 = (n - P0) + T.r_p0;                                     // n - k0 s
+    } else if (P0 > ov) {
+        // P0 - ov = (k_p0 - cw + 1) s + (r_p0 - rw)
+        const bool borrow = T.r_p0 < Q.rw;
+        g.k1 = T.k_p0 + 1u - Q.cw - (borrow ? 1u : 0u);
+        g.r1 = T.r_p0 - Q.rw + (borrow ? Q.s : 0u);
+        g.D1 = g.r1 + ov;                                             // P0 - k1 s
+        g.dsub = 0u;
+    } else {
+        g.k1 = 0u; g.r1 = 0u; g.D1 = (uint32_t)P0; g.dsub = (uint32_t)(ov - P0);
+    }
+    return g;
+}
+
 // Is the match (tile-relative position j, length l) pushed to the reference's match vectors by a full scan?
 // (src/teloscope.cpp:485: by the window whose own scan sees it with j >= overlap, or always in window 0 / when
 // windows do not overlap; restated from the window loop's index arithmetic, uint32 wrap included.)
-// (*rec: the window whose own scan pushes it — the record its covered bases are added to as well)
-__device__ __forceinline__ bool full_scan_pushes(uint32_t j, uint32_t l, const PushGeom &g, u64 *rec) {
+// (*rec: the window whose own scan pushes it — the record its covered bases are added to as well; div_s(x): x / s)
+template <typename DivS>
+__device__ __forceinline__ bool full_scan_pushes(uint32_t j, uint32_t l, const PushGeom &g, DivS div_s, u64 *rec) {
     if (g.ov == 0u) {
         const uint32_t x = g.r0 + j;
-        const uint32_t dk = x / g.s;
-        const u64 left = g.N0 - (u64)dk * g.s;
+        const uint32_t dk = div_s(x), dks = dk * g.s;       // (dk s <= x: no wrap)
+        const u64 left = g.N0 - dks;
         const uint32_t cws = left < g.w ? (uint32_t)left : g.w;
         *rec = g.k0 + dk;
-        return (x - dk * g.s) + l <= cws;                   // may not cross its only window's end
+        return (x - dks) + l <= cws;                        // may not cross its only window's end
     }
     const u64 e = g.P0 + j + l - 1u;
     *rec = 0;
     if (e < (g.n < g.w ? g.n : (u64)g.w)) return true;      // window 0 scans everything it holds
     const uint32_t xr = g.r1 + (j + l - 1u - g.dsub);       // (e - ov) relative to k1 s   [e >= w here]
-    const uint32_t dk = xr / g.s;                           // the one window with j >= overlap: k = k1 + dk
+    const uint32_t dk = div_s(xr);                          // the one window with j >= overlap: k = k1 + dk
     const long long diff = (long long)g.D1 + (long long)j - (long long)((u64)dk * g.s);
     *rec = g.k1 + dk;
     return diff >= 0 && (u64)diff >= g.start_index;
+}
+
+// Does the tile [P0, P0 + ntile) hold the whole span [R s, min(R s + w, n)) window record R collects?  Then its writer is the only one.
+__device__ __forceinline__ bool record_in_tile(u64 R, const TsGenericGeom &Q, u64 n, u64 P0, uint32_t ntile) {
+    const u64 span_lo = R * Q.s;
+    const u64 span_hi = span_lo + Q.w < n ? span_lo + Q.w : n;
+    return span_lo >= P0 && span_hi <= P0 + ntile;
+}
+
+// A wave's share of window record R (wrec: the segment's records): nucleotides {A | T << 16, C | G << 16} (wave-uniform) and the
+// lanes' covered counters, summed; lane f < 8 writes field f (A C G T, then the four covered counters), stored when the tile holds
+// the whole record, added otherwise
+__device__ __forceinline__ void put_record_wave(uint32_t *wrec, u64 R, uint32_t tAT, uint32_t tCG, const Acc &a, uint32_t lane, bool sole) {
+    const uint32_t tcan = wave_total(a.can), tnon = wave_total(a.non), tfwd = wave_total(a.fwd), trev = wave_total(a.rev);
+    const uint32_t mine = lane == 0u ? (tAT & 0xFFFFu) : lane == 1u ? (tCG & 0xFFFFu) : lane == 2u ? (tCG >> 16) : lane == 3u ? (tAT >> 16)
+                        : lane == 4u ? tcan : lane == 5u ? tnon : lane == 6u ? tfwd : trev;
+    if (lane < 8u) {
+        if (sole) wrec[R * 8ull + lane] = mine;
+        else if (mine) atomicAdd(&wrec[R * 8ull + lane], mine);
+    }
 }
 
 // code (0..3) and validity of tile position q from the packed planes
 __device__ __forceinline__ uint32_t plane_code(const uint32_t *codes2, uint32_t q) { return (codes2[q >> 4] >> (2u * (q & 15u))) & 3u; }
 __device__ __forceinline__ uint32_t plane_invalid(const uint32_t *inval, uint32_t q) { return (inval[q >> 5] >> (q & 31u)) & 1u; }
 
+// Where one analyzeWindow() call over window `kw` (carry: the part it carries into the next window's record, i >= step) meets
+// the tile's positions [P0, P0 + ntile): the tile positions [qlo, qhi) it visits, window index i = q + ioff.  False: it visits
+// nothing at all.  (src/teloscope.cpp:387-534, the index arithmetic in uint32 as there.)
+struct WindowCall {
+    u64 wstart;
+    uint32_t cws, ov, qlo, qhi, ioff;
+    bool always_main;
+};
+__device__ __forceinline__ bool window_call(const TsGenericGeom &Q, u64 n, u64 kw, bool carry, u64 P0, uint32_t ntile, WindowCall &c) {
+    c.wstart = kw * Q.s;
+    c.cws = (uint32_t)((n - c.wstart) < Q.w ? (n - c.wstart) : Q.w);
+    c.ov = Q.w - Q.s;
+    c.always_main = (c.ov == 0 || c.wstart == 0);
+    uint32_t start_index = call_start(c.always_main, inner_start_index(Q, c.ov));
+    if (carry) start_index = carry_start(start_index, Q.s);
+    if (start_index >= c.cws) return false;
+    const u64 lo = c.wstart + start_index, hi = c.wstart + c.cws;     // segment-relative positions the call visits
+    c.qlo = lo > P0 ? (uint32_t)(lo - P0 < ntile ? lo - P0 : ntile) : 0u;
+    c.qhi = hi > P0 ? (uint32_t)(hi - P0 < ntile ? hi - P0 : ntile) : 0u;
+    c.ioff = (uint32_t)(P0 - c.wstart);                               // i = q + ioff (mod 2^32: i < cws fits)
+    return true;
+}
+
 // What one analyzeWindow() call over window `kw` adds either to its own record (carry == false: bases with
 // i >= overlap, matches with j >= overlap, or everything for window 0 / overlap == 0) or to the NEXT window's record
 // (carry == true: i >= step) — restricted to the positions [P0, P0 + ntile) the tile holds in LDS; the wave's lanes
-// stride over them.  (src/teloscope.cpp:387-534, the index arithmetic in uint32 as there.)
+// stride over them.
 __device__ __forceinline__ void window_tile_part(const uint32_t *codes2, const uint32_t *inval, const uint32_t *mask,
                                                  const TsGenericPatterns &G, const TsGenericGeom &Q, u64 n, u64 kw, bool carry,
                                                  u64 P0, uint32_t ntile, uint32_t lane, Acc &a) {
-    const u64 wstart = kw * Q.s;
-    const uint32_t cws = (uint32_t)((n - wstart) < Q.w ? (n - wstart) : Q.w);
-    const uint32_t ov = Q.w - Q.s;
-    const bool always_main = (ov == 0 || wstart == 0);
-    // uint32 arithmetic on purpose (wraps when the longest pattern exceeds step or overlap)
-    const uint32_t t1 = Q.s - Q.longest, t2 = ov - Q.longest;
-    uint32_t start_index = always_main ? 0u : (t1 < t2 ? t1 : t2);
-    if (carry && start_index < Q.s) start_index = Q.s;               // the carry only takes i >= step
-    if (start_index >= cws) return;
-    const u64 lo = wstart + start_index, hi = wstart + cws;           // segment-relative positions the call visits
-    const uint32_t qlo = lo > P0 ? (uint32_t)(lo - P0 < ntile ? lo - P0 : ntile) : 0u;
-    const uint32_t qhi = hi > P0 ? (uint32_t)(hi - P0 < ntile ? hi - P0 : ntile) : 0u;
-    const uint32_t ioff = (uint32_t)(P0 - wstart);                    // i = q + ioff (mod 2^32: i < cws fits)
-    const bool all_nuc = carry || always_main;
-    for (uint32_t q = qlo + lane; q < qhi; q += 64u) {
-        const uint32_t i = q + ioff;
+    WindowCall c;
+    if (!window_call(Q, n, kw, carry, P0, ntile, c)) return;
+    const uint32_t cws = c.cws, ov = c.ov;
+    const bool always_main = c.always_main, all_nuc = carry || always_main;
+    for (uint32_t q = c.qlo + lane; q < c.qhi; q += 64u) {
+        const uint32_t i = q + c.ioff;
         if (Q.nuc_on) {
             if (plane_invalid(inval, q)) continue;
             if (all_nuc || i >= ov) a.nuc += 1u << (8u * plane_code(codes2, q));
@@ -170,6 +229,25 @@ __device__ __forceinline__ void window_tile_part(const uint32_t *codes2, const u
 
 constexpr uint32_t kCodeWords = (kTile + kHalo) / 16u + 4u;          // 2-bit plane, dwords (+ slack: three are read per position)
 constexpr uint32_t kInvalWords = (kTile + kHalo) / 32u + 3u;         // validity plane
+constexpr uint32_t kCumWords = 260;                                  // per-dword nucleotide prefix sums of a tile (256 + the end sentinel)
+
+__host__ __device__ inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
+
+// LDS of ts_general_fused (byte offsets; lp: patterns whose lists are copied in, 0: none):
+//   mask u32[kTile] | pcode u64[lp] | bitmap u32[8][128] | part u32[8] | codes2 | inval | pflag u8[lp]
+struct FusedLayout { uint32_t pcode, bitmap, part, codes2, inval, pflag, bytes; };
+__host__ __device__ inline FusedLayout fused_layout(uint32_t lp) {
+    FusedLayout L;
+    uint32_t o = kTile * 4u;
+    L.pcode = o; o += lp * 8u;
+    L.bitmap = o; o += 8u * 128u * 4u;
+    L.part = o; o += 8u * 4u;
+    L.codes2 = o; o += kCodeWords * 4u;
+    L.inval = o; o += kInvalWords * 4u;
+    L.pflag = o; o += align16(lp);
+    L.bytes = o;
+    return L;
+}
 
 // ONE pass per tile of 4096 positions of one scanned region (round 3; rounds 1-2 wrote a 4 B/base match mask to HBM
 // and read it back three times).  The workgroup
@@ -194,14 +272,14 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
                       const u64 *seg_win_base, const TsGenericPatterns G, const TsGenericGeom Q, int tips, uint32_t slot_cap,
                       uint32_t lds_patterns, uint32_t *tile_stats, uint32_t *records, uint32_t *win_out, uint32_t *overflow) {
     extern __shared__ __align__(16) unsigned char lds[];
-    // layout: mask u32[kTile] | pcode u64[lds_patterns] | bitmap u32[8][128] | part u32[8] | codes2 | inval | pflag u8[lds_patterns]
+    const FusedLayout L = fused_layout(lds_patterns);
     uint32_t *mask = (uint32_t *)lds;
-    u64 *pcode = (u64 *)(lds + kTile * 4u);
-    uint32_t *bitmap = (uint32_t *)(lds + kTile * 4u + (size_t)lds_patterns * 8u);
-    uint32_t *part = bitmap + 8u * 128u;
-    uint32_t *codes2 = part + 8;
-    uint32_t *inval = codes2 + kCodeWords;
-    unsigned char *pflag = (unsigned char *)(inval + kInvalWords);
+    u64 *pcode = (u64 *)(lds + L.pcode);
+    uint32_t *bitmap = (uint32_t *)(lds + L.bitmap);
+    uint32_t *part = (uint32_t *)(lds + L.part);
+    uint32_t *codes2 = (uint32_t *)(lds + L.codes2);
+    uint32_t *inval = (uint32_t *)(lds + L.inval);
+    unsigned char *pflag = lds + L.pflag;
     if (blockIdx.x >= ntiles) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t npat = G.first[G.nlen];
@@ -304,21 +382,12 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
             // two fields per reduction (a tile's share of a window is at most 4096 bases: 16 bits hold it)
             const uint32_t tAT = wave_total((a.nuc & 0xFFu) | ((a.nuc >> 16) & 0xFFu) << 16);        // A | T << 16
             const uint32_t tCG = wave_total(((a.nuc >> 8) & 0xFFu) | ((a.nuc >> 24) & 0xFFu) << 16);  // C | G << 16
-            const uint32_t tcan = wave_total(a.can), tnon = wave_total(a.non), tfwd = wave_total(a.fwd), trev = wave_total(a.rev);
-            // A C G T, then the four covered counters
-            const uint32_t mine = lane == 0u ? (tAT & 0xFFFFu) : lane == 1u ? (tCG & 0xFFFFu) : lane == 2u ? (tCG >> 16) : lane == 3u ? (tAT >> 16)
-                                : lane == 4u ? tcan : lane == 5u ? tnon : lane == 6u ? tfwd : trev;
-            const u64 span_lo = R * Q.s;
-            const u64 span_hi = span_lo + Q.w < n ? span_lo + Q.w : n;
-            const bool sole = span_lo >= P0 && span_hi <= P0 + T.n;
-            if (lane < 8u) {
-                if (sole) wrec[R * 8ull + lane] = mine;
-                else if (mine) atomicAdd(&wrec[R * 8ull + lane], mine);
-            }
+            put_record_wave(wrec, R, tAT, tCG, a, lane, record_in_tile(R, Q, n, P0, T.n));
         }
     }
     // 4. match records: wave v owns the 1024 consecutive positions [1024 v, 1024 v + 1024)
     const PushGeom pg = push_geom(P0, n, Q);
+    const auto div_s = [&](uint32_t x) { return x / pg.s; };
     uint32_t wave_cnt = 0;
     for (uint32_t r = 0; r < 16u; ++r) {
         const uint32_t j = wave * 1024u + r * 64u + lane;
@@ -327,7 +396,7 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
         if (v) {
             u64 unused_rec;
             for (uint32_t li = 0; li < G.nlen; ++li)
-                if (((v >> (3u * li)) & 1u) && (tips || full_scan_pushes(j, G.len[li], pg, &unused_rec))) keep |= 1u << li;
+                if (((v >> (3u * li)) & 1u) && (tips || full_scan_pushes(j, G.len[li], pg, div_s, &unused_rec))) keep |= 1u << li;
             mask[j] = v | (keep << 24);
         }
         wave_cnt += (uint32_t)__popc(keep);
@@ -360,27 +429,89 @@ void ts_general_fused(const unsigned char *in, const TsGeneralTile *tiles, uint3
 constexpr uint32_t kWaccMax = 256;          // window records a tile may add to on the list path
 constexpr uint32_t kListWave = 1024;        // candidate entries a wave's 1024 positions may produce on the list path (u16 each:
                                             // position in the wave's range << 6 | length index << 3 | pushed << 2 | canonical << 1 | forward)
-constexpr uint32_t kCumWords = 260;         // per-dword nucleotide prefix sums of a tile (256 + the end sentinel), list path
 constexpr uint32_t kShortLen = 6;           // pattern lengths up to this have exact tables in LDS (their l-mers index them)
 
-// Inclusive prefix sum over the wave's lanes by DPP (row shifts, then the two row broadcasts: lane 63 holds the total).
-__device__ __forceinline__ uint32_t wave_inclusive_dpp(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
+// LDS of ts_general_fused_list (byte offsets; lp: patterns in LDS, nshort: lengths up to kShortLen):
+//   list u16[4][kListWave] | pcode u64[lp] | cand6 u8[4096] | sflag u8[nshort][1024] | wacc u32[kWaccMax][4] | part u32[8] |
+//   first u32[12] | wtot u32[2][4] | wbase u32[2][8] | codes2 | inval | valid2 | cum u32[2][kCumWords] | pflag u8[lp]
+struct ListLayout { uint32_t pcode, cand6, sflag, wacc, part, first, wtot, wbase, codes2, inval, valid2, cum, pflag, bytes; };
+__host__ __device__ inline ListLayout list_layout(uint32_t lp, uint32_t nshort) {
+    ListLayout L;
+    uint32_t o = 4u * kListWave * 2u;
+    L.pcode = o; o += align16(lp * 8u);                 // (16-byte aligned: wacc is zeroed and read as uint4)
+    L.cand6 = o; o += 4096u;
+    L.sflag = o; o += nshort * 1024u;
+    L.wacc = o; o += kWaccMax * 4u * 4u;
+    L.part = o; o += 8u * 4u;
+    L.first = o; o += 12u * 4u;
+    L.wtot = o; o += 8u * 4u;
+    L.wbase = o; o += 16u * 4u;
+    L.codes2 = o; o += kCodeWords * 4u;
+    L.inval = o; o += kInvalWords * 4u;
+    L.valid2 = o; o += kCodeWords * 4u;
+    L.cum = o; o += 2u * kCumWords * 4u;
+    L.pflag = o; o += align16(lp);
+    L.bytes = o;
+    return L;
 }
 
-// sixteen doubled 2-bit codes (ASCII & 6), one per byte of t[0..3] -> one dword, base i at bits 2i..2i+1
-__device__ __forceinline__ uint32_t pack16(const uint32_t t[4]) {
-    const uint32_t b0 = __builtin_amdgcn_udot4(t[0], 0x40100401u, 0u, false);
-    const uint32_t b1 = __builtin_amdgcn_udot4(t[1], 0x40100401u, 0u, false);
-    const uint32_t b2 = __builtin_amdgcn_udot4(t[2], 0x40100401u, 0u, false);
-    const uint32_t b3 = __builtin_amdgcn_udot4(t[3], 0x40100401u, 0u, false);
-    return ((b0 | (b1 << 8)) >> 1) | ((b2 | (b3 << 8)) << 15);
+// Plane dword i / 16 of a tile from its sixteen bases v (positions from avail on are invalid), for the list and wide forms: the
+// 2-bit codes, the validity bits and valid2 (the low bit of each base's pair set: valid), and the dword's nucleotide counts
+// vg = {valid | G << 16}, ct = {C | T << 16}.  ASCII & 6 = twice the code (A 0, C 2, T 4, G 6) and the v_perm selector of the
+// letter that code stands for; a byte that is not that letter (up to case folding) is invalid.
+__device__ __forceinline__ void stage16(const uint4 v, uint32_t i, uint32_t avail, uint32_t fold_mask, uint32_t *codes2, uint32_t *inval,
+                                        uint32_t *valid2, uint32_t &vg, uint32_t &ct) {
+    uint32_t cw = 0, iv = 0xFFFFu;
+    if (i < avail) {
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+        uint32_t t[4], b4[4];
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            t[q] = d[q] & 0x06060606u;
+            const uint32_t e = __builtin_amdgcn_perm(0xFF47FF54u, 0xFF43FF41u, t[q]);
+            const uint32_t dd = (d[q] & fold_mask) ^ e;
+            const uint32_t nz = ((((dd & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | dd) & 0x80808080u) >> 7;
+            b4[q] = __builtin_amdgcn_udot4(nz, 0x08040201u, 0u, false);
+        }
+        cw = pack16(t);
+        iv = b4[0] | (b4[1] << 4) | (b4[2] << 8) | (b4[3] << 12);
+        if (i + 16u > avail) iv = (iv | (~0u << (avail - i))) & 0xFFFFu;       // bases behind the region's end
+    }
+    codes2[i >> 4] = cw;
+    ((unsigned short *)inval)[i >> 4] = (unsigned short)iv;
+    uint32_t ok = ~iv & 0xFFFFu;
+    ok = (ok | (ok << 8)) & 0x00FF00FFu; ok = (ok | (ok << 4)) & 0x0F0F0F0Fu;
+    ok = (ok | (ok << 2)) & 0x33333333u; ok = (ok | (ok << 1)) & 0x55555555u;
+    valid2[i >> 4] = ok;
+    const uint32_t lo = cw & ok, hi = (cw >> 1) & ok, g = (uint32_t)__popc(lo & hi);
+    vg = (uint32_t)__popc(ok) | (g << 16);
+    ct = ((uint32_t)__popc(lo) - g) | (((uint32_t)__popc(hi) - g) << 16);
+}
+
+// The prefix sums behind prefix_counts, staged by plane dword tid (each field <= 4096: the 16-bit halves do not carry into each
+// other): cum[tid] and cum[kCumWords + tid] the counts of the dwords before it in its wave, wtot the wave's totals ...
+__device__ __forceinline__ void stage_cum(uint32_t vg, uint32_t ct, uint32_t tid, uint32_t lane, uint32_t wave, uint32_t *cum, uint32_t *wtot) {
+    const uint32_t ivg = wave_scan_add(vg), ict = wave_scan_add(ct);
+    cum[tid] = ivg - vg; cum[kCumWords + tid] = ict - ct;
+    if (lane == 63u) { wtot[wave] = ivg; wtot[4u + wave] = ict; }
+}
+// ... and, once they are all in (behind a barrier), wbase: the totals of the waves before (entry 4: the whole tile), twice
+__device__ __forceinline__ void stage_wave_bases(uint32_t tid, const uint32_t *wtot, uint32_t *wbase) {
+    if (tid < 5u) {
+        uint32_t a = 0, b = 0;
+        for (uint32_t v = 0; v < tid; ++v) { a += wtot[v]; b += wtot[4u + v]; }
+        wbase[tid] = a; wbase[8u + tid] = b;
+    }
+}
+
+// nucleotide counts of the tile positions [0, q), q <= 4096: {V | G << 16, C | T << 16} (V: valid bases)
+__device__ __forceinline__ void prefix_counts(const uint32_t *codes2, const uint32_t *valid2, const uint32_t *cum, const uint32_t *wbase,
+                                              uint32_t q, uint32_t &VG, uint32_t &CT) {
+    const uint32_t d = q >> 4, m = (1u << (2u * (q & 15u))) - 1u;
+    const uint32_t v = valid2[d] & m, w = codes2[d], lo = w & v, hi = (w >> 1) & v;
+    const uint32_t g = (uint32_t)__popc(lo & hi);
+    VG = cum[d] + wbase[d >> 6] + ((uint32_t)__popc(v) | (g << 16));
+    CT = cum[kCumWords + d] + wbase[8u + (d >> 6)] + (((uint32_t)__popc(lo) - g) | (((uint32_t)__popc(hi) - g) << 16));
 }
 
 // x / s for the x this kernel divides (x < s + 4200): one multiply by ceil-ish(2^32 / s) when s <= 8192 (exact for
@@ -388,39 +519,6 @@ __device__ __forceinline__ uint32_t pack16(const uint32_t t[4]) {
 __device__ __forceinline__ uint32_t div_step(uint32_t x, uint32_t s, uint32_t magic) {
     return s > 8192u ? (x >= s ? 1u : 0u) : __umulhi(x, magic);
 }
-
-// full_scan_pushes with the division above (same arithmetic otherwise)
-__device__ __forceinline__ bool full_scan_pushes_m(uint32_t j, uint32_t l, const PushGeom &g, uint32_t magic, u64 *rec) {
-    if (g.ov == 0u) {
-        const uint32_t x = g.r0 + j;
-        const uint32_t dk = div_step(x, g.s, magic), dks = dk * g.s;
-        const u64 left = g.N0 - dks;
-        const uint32_t cws = left < g.w ? (uint32_t)left : g.w;
-        *rec = g.k0 + dk;
-        return (x - dks) + l <= cws;                        // may not cross its only window's end
-    }
-    const u64 e = g.P0 + j + l - 1u;
-    *rec = 0;
-    if (e < (g.n < g.w ? g.n : (u64)g.w)) return true;      // window 0 scans everything it holds
-    const uint32_t xr = g.r1 + (j + l - 1u - g.dsub);       // (e - ov) relative to k1 s   [e >= w here]
-    const uint32_t dk = div_step(xr, g.s, magic);           // the one window with j >= overlap: k = k1 + dk
-    const long long diff = (long long)g.D1 + (long long)j - (long long)((u64)dk * g.s);
-    *rec = g.k1 + dk;
-    return diff >= 0 && (u64)diff >= g.start_index;
-}
-
-// Global stores and return-less atomics the compiler does not see (round 5; kernels.hip has the same helpers and the full story):
-// on gfx9 loads and stores share vmcnt, so with a store pending the compiler waits for the NEXT TILE'S PREFETCH with vmcnt(0) at the
-// first register it reuses — in the list kernel a few instructions behind the prefetch's issue.  Nothing in the kernel loads what it
-// stored.
-__device__ __forceinline__ void gen_store(uint32_t *p, uint32_t v) { asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v)); }
-__device__ __forceinline__ void gen_store(uint4 *p, uint4 v) {
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    const u32x4_t d = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 0" :: "v"(p), "v"(d));       // (s_nop: the data of a store of more than 8 bytes is read a cycle late)
-}
-__device__ __forceinline__ void gen_add(uint32_t *p, uint32_t v) { asm volatile("global_atomic_add %0, %1, off" :: "v"(p), "v"(v)); }
-__device__ __forceinline__ void gen_or(uint32_t *p, uint32_t v) { asm volatile("global_atomic_or %0, %1, off" :: "v"(p), "v"(v)); }
 
 // The same pass in its LIST form (round 3; restructured in round 4): what the kernel above does per position — flag
 // lookup, push test, window shares — is done here per CANDIDATE, on full wavefronts, and a position costs ONE LDS probe.
@@ -450,24 +548,22 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
                            const u64 *seg_win_base, const u64 *seg_nwin, const TsGenericPatterns G, const TsGenericGeom Q, int tips, uint32_t slot_cap,
                            uint32_t lds_patterns, uint32_t nshort, uint32_t *tile_stats, uint32_t *records, uint32_t *win_out, uint32_t *overflow) {
     extern __shared__ __align__(16) unsigned char lds[];
-    // layout: list u16[4][kListWave] | pcode u64[lds_patterns] | cand6 u8[4096] | sflag u8[nshort][1024] | wacc u32[kWaccMax][4] |
-    //         part u32[8] | first u32[12] | wtot u32[2][4] | wbase u32[2][8] | codes2 | inval | valid2 | cum u32[2][kCumWords] | pflag
+    const ListLayout L = list_layout(lds_patterns, nshort);
     unsigned short *list_all = (unsigned short *)lds;
-    u64 *pcode = (u64 *)(lds + 4u * kListWave * 2u);
-    uint32_t *cand6w = (uint32_t *)(lds + 4u * kListWave * 2u + (((size_t)lds_patterns * 8u + 15u) & ~(size_t)15u));   // (16-byte aligned: wacc is zeroed and read as uint4)
+    u64 *pcode = (u64 *)(lds + L.pcode);
+    uint32_t *cand6w = (uint32_t *)(lds + L.cand6);
     const unsigned char *cand6 = (const unsigned char *)cand6w;
-    uint32_t *sflagw = cand6w + 1024u;
-    uint32_t *wacc = sflagw + nshort * 256u;                               // [kWaccMax][4]: canonical, non-canonical, forward, reverse covered
-    uint32_t *part = wacc + kWaccMax * 4u;
-    uint32_t *firstl = part + 8;
-    uint32_t *wtot = firstl + 12;                                          // per wave: nucleotide totals of its 64 plane dwords {V | G << 16, C | T << 16}
-    uint32_t *wbase = wtot + 8;                                            // the same summed over the waves before (entries 0..4, twice)
-    uint32_t *codes2 = wbase + 16;
-    uint32_t *inval = codes2 + kCodeWords;
-    uint32_t *valid2 = inval + kInvalWords;
-    uint32_t *cumVG = valid2 + kCodeWords;                                 // per plane dword: counts of the dwords before it IN ITS WAVE
-    uint32_t *cumCT = cumVG + kCumWords;
-    unsigned char *pflag = (unsigned char *)(cumCT + kCumWords);
+    uint32_t *sflagw = (uint32_t *)(lds + L.sflag);
+    uint32_t *wacc = (uint32_t *)(lds + L.wacc);                           // [kWaccMax][4]: canonical, non-canonical, forward, reverse covered
+    uint32_t *part = (uint32_t *)(lds + L.part);
+    uint32_t *firstl = (uint32_t *)(lds + L.first);
+    uint32_t *wtot = (uint32_t *)(lds + L.wtot);                           // per wave: nucleotide totals of its 64 plane dwords {V | G << 16, C | T << 16}
+    uint32_t *wbase = (uint32_t *)(lds + L.wbase);                         // the same summed over the waves before (entries 0..4, twice)
+    uint32_t *codes2 = (uint32_t *)(lds + L.codes2);
+    uint32_t *inval = (uint32_t *)(lds + L.inval);
+    uint32_t *valid2 = (uint32_t *)(lds + L.valid2);
+    uint32_t *cum = (uint32_t *)(lds + L.cum);                             // per plane dword: counts of the dwords before it IN ITS WAVE
+    unsigned char *pflag = lds + L.pflag;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     unsigned short *const list = list_all + wave * kListWave;
@@ -479,7 +575,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
     if (tid == 0u) {
 #pragma unroll
         for (uint32_t q = 0; q < 9u; ++q) firstl[q] = G.first[q];
-        cumVG[256] = 0u; cumCT[256] = 0u;
+        cum[256] = 0u; cum[kCumWords + 256] = 0u;
     }
     // the pattern lengths as six bits each (uniform), for the per-candidate pass
     u64 lens64 = 0;
@@ -510,48 +606,11 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
         const uint32_t c0 = codes2[wd], c1 = codes2[wd + 1u], c2 = codes2[wd + 2u];
         return (u64)__funnelshift_r(c0, c1, sh) | ((u64)__funnelshift_r(c1, c2, sh) << 32);
     };
-    // nucleotide counts of the tile positions [0, q), q <= 4096: {V | G << 16, C | T << 16} (V: valid bases)
-    auto prefix_counts = [&](uint32_t q, uint32_t &VG, uint32_t &CT) {
-        const uint32_t d = q >> 4, m = (1u << (2u * (q & 15u))) - 1u;
-        const uint32_t v = valid2[d] & m, w = codes2[d], lo = w & v, hi = (w >> 1) & v;
-        const uint32_t g = (uint32_t)__popc(lo & hi);
-        VG = cumVG[d] + wbase[d >> 6] + ((uint32_t)__popc(v) | (g << 16));
-        CT = cumCT[d] + wbase[8u + (d >> 6)] + (((uint32_t)__popc(lo) - g) | (((uint32_t)__popc(hi) - g) << 16));
-    };
     // a thread stages the plane dword tid (bases [16 tid, 16 tid + 16)); threads 0..5 also the halo's dwords 256 + tid.  The
     // layout's regions start on 16-byte boundaries and tiles at multiples of 4096 inside them (the host checks): aligned loads;
     // the layout keeps 64 readable bytes behind the last region.
     auto load16 = [&](const TsGeneralTile &T, uint32_t i) -> uint4 {
         return i < T.avail ? *(const uint4 *)(in + T.in_off + i) : make_uint4(0u, 0u, 0u, 0u);
-    };
-    auto stage16 = [&](const uint4 v, uint32_t i, uint32_t avail, uint32_t &vg, uint32_t &ct) {
-        uint32_t cw = 0, iv = 0xFFFFu;
-        if (i < avail) {
-            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-            // ASCII & 6 = twice the code (A 0, C 2, T 4, G 6) and the v_perm selector of the letter that code stands for; a byte
-            // that is not that letter (up to case folding) is invalid
-            uint32_t t[4], b4[4];
-#pragma unroll
-            for (uint32_t q = 0; q < 4u; ++q) {
-                t[q] = d[q] & 0x06060606u;
-                const uint32_t e = __builtin_amdgcn_perm(0xFF47FF54u, 0xFF43FF41u, t[q]);
-                const uint32_t dd = (d[q] & fold_mask) ^ e;
-                const uint32_t nz = ((((dd & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | dd) & 0x80808080u) >> 7;
-                b4[q] = __builtin_amdgcn_udot4(nz, 0x08040201u, 0u, false);
-            }
-            cw = pack16(t);
-            iv = b4[0] | (b4[1] << 4) | (b4[2] << 8) | (b4[3] << 12);
-            if (i + 16u > avail) iv = (iv | (~0u << (avail - i))) & 0xFFFFu;       // bases behind the region's end
-        }
-        codes2[i >> 4] = cw;
-        ((unsigned short *)inval)[i >> 4] = (unsigned short)iv;
-        uint32_t ok = ~iv & 0xFFFFu;
-        ok = (ok | (ok << 8)) & 0x00FF00FFu; ok = (ok | (ok << 4)) & 0x0F0F0F0Fu;
-        ok = (ok | (ok << 2)) & 0x33333333u; ok = (ok | (ok << 1)) & 0x55555555u;
-        valid2[i >> 4] = ok;
-        const uint32_t lo = cw & ok, hi = (cw >> 1) & ok, g = (uint32_t)__popc(lo & hi);
-        vg = (uint32_t)__popc(ok) | (g << 16);
-        ct = ((uint32_t)__popc(lo) - g) | (((uint32_t)__popc(hi) - g) << 16);
     };
     // tile descriptors by scalar loads (the table is written by the host only): as vector loads they sat behind a vmcnt wait in
     // front of the very prefetch they address
@@ -574,13 +633,9 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
         {
             uint32_t vg, ct, hv = 0, hc = 0;
             for (uint32_t i = tid; i < kWaccMax; i += 256u) *(uint4 *)&wacc[4u * i] = make_uint4(0u, 0u, 0u, 0u);
-            stage16(v_main, tid * 16u, avail, vg, ct);
-            if (tid < kCodeWords - 256u) stage16(v_halo, 4096u + tid * 16u, avail, hv, hc);
-            (void)hv; (void)hc;
-            // the wave's prefix sums of the counts (each field <= 4096: the 16-bit halves do not carry into each other)
-            const uint32_t ivg = wave_inclusive_dpp(vg), ict = wave_inclusive_dpp(ct);
-            cumVG[tid] = ivg - vg; cumCT[tid] = ict - ct;
-            if (lane == 63u) { wtot[wave] = ivg; wtot[4u + wave] = ict; }
+            stage16(v_main, tid * 16u, avail, fold_mask, codes2, inval, valid2, vg, ct);
+            if (tid < kCodeWords - 256u) stage16(v_halo, 4096u + tid * 16u, avail, fold_mask, codes2, inval, valid2, hv, hc);
+            stage_cum(vg, ct, tid, lane, wave, cum, wtot);
         }
         // the next tile's bases are on their way while this one is worked on
         const uint32_t tile_next = tile + gridDim.x;
@@ -592,11 +647,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
             if (tid < kCodeWords - 256u) v_halo = load16(Tn, 4096u + tid * 16u);
         }
         __syncthreads();
-        if (tid < 5u) {                                                    // sums over the waves before (entry 4: the whole tile)
-            uint32_t a = 0, b = 0;
-            for (uint32_t v = 0; v < tid; ++v) { a += wtot[v]; b += wtot[4u + v]; }
-            wbase[tid] = a; wbase[8u + tid] = b;
-        }
+        stage_wave_bases(tid, wtot, wbase);
         // 2'. candidates: wave v owns the 1024 consecutive positions [1024 v, 1024 v + 1024), lane L the sixteen from 16 L on
         uint32_t ncand = 0;                                                    // (wave-uniform)
         bool spilled = false;
@@ -612,7 +663,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
             // non-ACGT bases within reach of the wave's positions, or the region's end: lengths that do not fit are dropped
             const unsigned short *inval16 = (const unsigned short *)inval;
             const u64 iv48 = (u64)inval16[wd0] | ((u64)inval16[wd0 + 1u] << 16) | ((u64)inval16[wd0 + 2u] << 32);
-            const bool slow = wave * 1024u + 1024u + 32u > avail || __builtin_amdgcn_ballot_w64(iv48 != 0ull) != 0ull;
+            const bool slow = wave * 1024u + 1024u + 32u > avail || ballot64(iv48 != 0ull) != 0ull;
             if (slow) {
 #pragma unroll 1
                 for (uint32_t i = 0; i < 16u; ++i) {
@@ -633,7 +684,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
                 }
             }
             const uint32_t c = (uint32_t)(__popc(acc[0]) + __popc(acc[1]) + __popc(acc[2]) + __popc(acc[3]));
-            const uint32_t incl = wave_inclusive_dpp(c);
+            const uint32_t incl = wave_scan_add(c);
             ncand = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             if (ncand > kListWave) { spilled = true; ncand = 0; }
             else {
@@ -646,7 +697,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
                     }
             }
         }
-        if (spilled && lane == 0u) gen_or(overflow, 2u);
+        if (spilled && lane == 0u) gatomic_or(overflow, 2u);
         const u64 n = c_seg_len[T.seg];
         const u64 P0 = T.seg_rel;
         const u64 N1 = n - P0;                                                  // bases from the tile's first to the segment's end
@@ -661,28 +712,9 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
             if (kw_hi >= nwin) kw_hi = nwin - 1u;
             rec_hi = kw_hi + (carries ? 1u : 0u);
             if (rec_hi >= nwin) rec_hi = nwin - 1u;
-            if (rec_hi - kw_lo >= kWaccMax) { if (tid == 0u) gen_or(overflow, 2u); spilled = true; }     // (the host sizes this out: never)
+            if (rec_hi - kw_lo >= kWaccMax) { if (tid == 0u) gatomic_or(overflow, 2u); spilled = true; }     // (the host sizes this out: never)
         }
-        PushGeom pg{};
-        {
-            pg.P0 = P0; pg.n = n; pg.s = Q.s; pg.w = Q.w; pg.ov = ov;
-            const uint32_t t1 = Q.s - Q.longest, t2 = ov - Q.longest;        // uint32 on purpose (src/teloscope.cpp:413-415)
-            pg.start_index = t1 < t2 ? t1 : t2;
-            pg.kP0 = T.k_p0; pg.rP0 = T.r_p0;
-            if (ov == 0u) {
-                pg.k0 = T.k_p0; pg.r0 = T.r_p0;
-                pg.N0 = N1 + T.r_p0;                                          // n - k0 s
-            } else if (P0 > ov) {
-                // P0 - ov = (k_p0 - cw + 1) s + (r_p0 - rw)
-                const bool borrow = T.r_p0 < Q.rw;
-                pg.k1 = T.k_p0 + 1u - Q.cw - (borrow ? 1u : 0u);
-                pg.r1 = T.r_p0 - Q.rw + (borrow ? Q.s : 0u);
-                pg.D1 = pg.r1 + ov;                                           // P0 - k1 s
-                pg.dsub = 0u;
-            } else {
-                pg.k1 = 0u; pg.r1 = 0u; pg.D1 = (uint32_t)P0; pg.dsub = (uint32_t)(ov - P0);
-            }
-        }
+        const PushGeom pg = push_geom_tile(T, n, Q);
         // 3'. a lane per candidate
         uint32_t npush = 0;
         __builtin_amdgcn_wave_barrier();
@@ -712,7 +744,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
                 }
                 if (found) {
                     u64 rec = 0;
-                    pushed = tips || full_scan_pushes_m(j, l, pg, magic, &rec);
+                    pushed = tips || full_scan_pushes(j, l, pg, [&](uint32_t x) { return div_step(x, Q.s, magic); }, &rec);
                     if (win_on) {
                         const uint32_t f_can = (fl & 2u) ? 0u : 1u, f_fwd = (fl & 1u) ? 2u : 3u;
                         // the window that pushes a match counts it in its own record (analyzeWindow's main part) ...
@@ -746,7 +778,7 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
                 }
                 list[e] = (unsigned short)(pushed ? (ent | 4u) : 0u);
             }
-            npush += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(pushed));
+            npush += (uint32_t)__popcll(ballot64(pushed));
         }
         if (lane == 0u) { part[wave] = npush; part[4u + wave] = spilled ? 1u : 0u; }
         __syncthreads();
@@ -755,8 +787,8 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
         // did any wave's list spill?  then nothing of this tile counts: the group runs again with the kernel above
         const bool any_spill = (part[4] | part[5] | part[6] | part[7]) != 0u;
         if (tid == 0u) {
-            gen_store((uint4 *)&tile_stats[4ull * tile], make_uint4(total, 0u, 0u, 0u));
-            if (total > slot_cap) gen_or(overflow, 1u);
+            gstore((uint4 *)&tile_stats[4ull * tile], make_uint4(total, 0u, 0u, 0u));
+            if (total > slot_cap) gatomic_or(overflow, 1u);
         }
         // 4'. window records: thread r takes record kw_lo + r.  Positions relative to the tile's first base, 32-bit signed (the
         // host keeps w below 2^28 on this path; a segment end farther away than that is as good as infinitely far)
@@ -771,22 +803,21 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
                 const uint32_t qa = (uint32_t)(a < 0 ? 0 : (a > tn ? tn : a)), qb = (uint32_t)(b < 0 ? 0 : (b > tn ? tn : b));
                 if (qa >= qb) return;
                 uint32_t va, ca, vb, cb;
-                prefix_counts(qa, va, ca);
-                prefix_counts(qb, vb, cb);
+                prefix_counts(codes2, valid2, cum, wbase, qa, va, ca);
+                prefix_counts(codes2, valid2, cum, wbase, qb, vb, cb);
                 VG += vb - va; CT += cb - ca;
             };
             if (Q.nuc_on) {
                 {                                                           // main part of call R
                     const uint32_t cws = left < (int32_t)Q.w ? (uint32_t)left : Q.w;
                     const bool always_main = ov == 0u || R == 0u;
-                    const uint32_t from = always_main ? 0u : (pg.start_index > ov ? pg.start_index : ov);
+                    const uint32_t from = always_main ? 0u : (pg.start_index > ov ? pg.start_index : ov);   // (nucleotides: i >= overlap too)
                     if (from < cws) add_range(rel + (int32_t)from, rel + (int32_t)cws);
                 }
                 if (carries && R > 0u) {                                    // carry of call R - 1: i >= max(its start index, step)
                     const int32_t left1 = left + (int32_t)Q.s;
                     const uint32_t cws = left1 < (int32_t)Q.w ? (uint32_t)left1 : Q.w;
-                    const uint32_t si = R - 1u == 0u ? 0u : pg.start_index;
-                    const uint32_t from = si > Q.s ? si : Q.s;
+                    const uint32_t from = carry_start(call_start(R - 1u == 0u, pg.start_index), Q.s);
                     if (from < cws) add_range(rel - (int32_t)Q.s + (int32_t)from, rel - (int32_t)Q.s + (int32_t)cws);
                 }
             }
@@ -795,17 +826,17 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
             uint32_t *const wr = win_out + (c_seg_win_base[T.seg] + R) * 8ull;
             const int32_t span_hi = rel + (left < (int32_t)Q.w ? left : (int32_t)Q.w);
             if (rel >= 0 && span_hi <= tn) {                                 // the tile holds the whole record: this thread is its only writer
-                gen_store((uint4 *)wr, make_uint4(tA, tC, tG, tT));
-                gen_store((uint4 *)(wr + 4), cov);
+                gstore((uint4 *)wr, make_uint4(tA, tC, tG, tT));
+                gstore((uint4 *)(wr + 4), cov);
             } else {
-                if (tA) gen_add(wr + 0, tA);
-                if (tC) gen_add(wr + 1, tC);
-                if (tG) gen_add(wr + 2, tG);
-                if (tT) gen_add(wr + 3, tT);
-                if (cov.x) gen_add(wr + 4, cov.x);
-                if (cov.y) gen_add(wr + 5, cov.y);
-                if (cov.z) gen_add(wr + 6, cov.z);
-                if (cov.w) gen_add(wr + 7, cov.w);
+                if (tA) gatomic_add(wr + 0, tA);
+                if (tC) gatomic_add(wr + 1, tC);
+                if (tG) gatomic_add(wr + 2, tG);
+                if (tT) gatomic_add(wr + 3, tT);
+                if (cov.x) gatomic_add(wr + 4, cov.x);
+                if (cov.y) gatomic_add(wr + 5, cov.y);
+                if (cov.z) gatomic_add(wr + 6, cov.z);
+                if (cov.w) gatomic_add(wr + 7, cov.w);
             }
         }
         // 5'. match records
@@ -815,11 +846,11 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
             for (uint32_t e0 = 0; e0 < ncand; e0 += 64u) {
                 const uint32_t e = e0 + lane;
                 const uint32_t ent = e < ncand ? list[e] : 0u;
-                const u64 m = __builtin_amdgcn_ballot_w64((ent & 4u) != 0u);
+                const u64 m = ballot64((ent & 4u) != 0u);
                 if (m == 0ull) continue;
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                 // the stream's record: tile position << 5 | length index << 2 | canonical << 1 | forward
-                if (ent & 4u) gen_store(dst + (base + rank), ((wave * 1024u + (ent >> 6)) << 5) | (((ent >> 3) & 7u) << 2) | (ent & 3u));
+                if (ent & 4u) gstore(dst + (base + rank), ((wave * 1024u + (ent >> 6)) << 5) | (((ent >> 3) & 7u) << 2) | (ent & 3u));
                 base += (uint32_t)__popcll(m);
             }
         }
@@ -852,10 +883,37 @@ void ts_general_fused_list(const unsigned char *in, const TsGeneralTile *tiles, 
 // profiles/r05/general_unordered_device_blocks.txt has every step with its time: 41.75 -> 12.78 ms per 3 Gb on a nine-length set.
 constexpr uint32_t kWideCodeWords = (kTile + TS_WIDE_HALO) / 16u + 6u;     // 2-bit plane, dwords (five are read per position)
 constexpr uint32_t kWideInvalWords = (kTile + TS_WIDE_HALO) / 32u + 4u;    // validity plane (three are read per position)
-constexpr uint32_t kWideCumWords = 260;                                     // per-dword nucleotide prefix sums (256 + the end sentinel)
 constexpr uint32_t kWideWacc = 64;                                          // window records a tile may add to with a lane per record (more: a wave per record part)
 
-struct WideAcc { uint32_t nuc, can, non, fwd, rev; };
+// LDS of ts_general_wide (byte offsets; mask_bytes / pre_bytes: sizeof M / P, lds_pat: patterns in LDS, 0: none):
+//   hit M[kTile] | fwd M[kTile] | can M[kTile] | pre6 P[4096] | plo u64[lds_pat] | phi u64[lds_pat] | lens u32[64] | first u32[68] |
+//   part u32[8] | wtot u32[8] | wbase u32[16] | hitmap u32[128] | cum u32[2][kCumWords] | codes2 | inval | valid2 | lists u16[4][1024] |
+//   wacc u32[kWideWacc][4] | pfl u8[lds_pat]
+struct WideLayout { uint32_t fwd, can, pre6, plo, phi, lens, first, part, wtot, wbase, hitmap, cum, codes2, inval, valid2, lists, wacc, pfl, bytes; };
+__host__ __device__ inline WideLayout wide_layout(uint32_t mask_bytes, uint32_t pre_bytes, uint32_t lds_pat) {
+    WideLayout L;
+    uint32_t o = kTile * mask_bytes;
+    L.fwd = o; o += kTile * mask_bytes;
+    L.can = o; o += kTile * mask_bytes;
+    L.pre6 = o; o += 4096u * pre_bytes;
+    L.plo = o; o += lds_pat * 8u;
+    L.phi = o; o += lds_pat * 8u;
+    L.lens = o; o += 64u * 4u;
+    L.first = o; o += 68u * 4u;
+    L.part = o; o += 8u * 4u;
+    L.wtot = o; o += 8u * 4u;
+    L.wbase = o; o += 16u * 4u;
+    L.hitmap = o; o += 128u * 4u;
+    L.cum = o; o += 2u * kCumWords * 4u;
+    L.codes2 = o; o += kWideCodeWords * 4u;
+    L.inval = o; o += kWideInvalWords * 4u;
+    L.valid2 = o; o += kWideCodeWords * 4u;
+    L.lists = o; o += 4u * 1024u * 2u;
+    L.wacc = o; o += kWideWacc * 4u * 4u;
+    L.pfl = o; o += align16(lds_pat);
+    L.bytes = o + 16u;                                  // (and 16 bytes of slack)
+    return L;
+}
 
 // The part of window call kw that lies in a tile, for the wide form: covered bases of its matches into `a` (per lane, summed by
 // the caller), the nucleotide counts of the part as a wave-uniform pair {A | T << 16, C | G << 16} added to nAT / nCG.
@@ -865,33 +923,24 @@ struct WideAcc { uint32_t nuc, can, non, fwd, rev; };
 template <typename M, typename PC, bool NUC_ONLY = false>
 __device__ __forceinline__ void window_tile_part_wide(const uint32_t *hitmap, const M *hit, const M *fwdm, const M *canm,
                                                       const uint32_t *lens, const TsGenericGeom &Q, u64 n, u64 kw, bool carry,
-                                                      u64 P0, uint32_t ntile, uint32_t lane, WideAcc &a, PC prefix_counts,
+                                                      u64 P0, uint32_t ntile, uint32_t lane, Acc &a, PC counts,
                                                       uint32_t &nAT, uint32_t &nCG) {
-    const u64 wstart = kw * Q.s;
-    const uint32_t cws = (uint32_t)((n - wstart) < Q.w ? (n - wstart) : Q.w);
-    const uint32_t ov = Q.w - Q.s;
-    const bool always_main = (ov == 0 || wstart == 0);
-    const uint32_t t1 = Q.s - Q.longest, t2 = ov - Q.longest;           // uint32 on purpose (src/teloscope.cpp:413-415)
-    uint32_t start_index = always_main ? 0u : (t1 < t2 ? t1 : t2);
-    if (carry && start_index < Q.s) start_index = Q.s;               // the carry only takes i >= step
-    if (start_index >= cws) return;
-    const u64 lo = wstart + start_index, hi = wstart + cws;
-    const uint32_t qlo = lo > P0 ? (uint32_t)(lo - P0 < ntile ? lo - P0 : ntile) : 0u;
-    const uint32_t qhi = hi > P0 ? (uint32_t)(hi - P0 < ntile ? hi - P0 : ntile) : 0u;
+    WindowCall c;
+    if (!window_call(Q, n, kw, carry, P0, ntile, c)) return;
+    const uint32_t cws = c.cws, ov = c.ov, qlo = c.qlo, qhi = c.qhi;
     if (qlo >= qhi) return;
-    const uint32_t ioff = (uint32_t)(P0 - wstart);
-    const bool all_nuc = carry || always_main;
+    const bool always_main = c.always_main, all_nuc = carry || always_main;
     if (Q.nuc_on) {
         // valid bases at window indices i >= ov (all of the part for a carry or a first window): tile positions [nlo, qhi)
         uint32_t nlo = qlo;
         if (!all_nuc) {
-            const long long b = (long long)ov + (long long)wstart - (long long)P0;      // i >= ov  <=>  q >= b
+            const long long b = (long long)ov + (long long)c.wstart - (long long)P0;    // i >= ov  <=>  q >= b
             if (b > (long long)qlo) nlo = b >= (long long)qhi ? qhi : (uint32_t)b;
         }
         if (nlo < qhi) {
             uint32_t vg1, ct1, vg0, ct0;
-            prefix_counts(qhi, vg1, ct1);
-            prefix_counts(nlo, vg0, ct0);
+            counts(qhi, vg1, ct1);
+            counts(nlo, vg0, ct0);
             const uint32_t vg = vg1 - vg0, ct = ct1 - ct0;               // {valid | G << 16}, {C | T << 16}: fields never borrow
             const uint32_t G_ = vg >> 16, C_ = ct & 0xFFFFu, T_ = ct >> 16, A_ = (vg & 0xFFFFu) - G_ - C_ - T_;
             nAT += A_ | (T_ << 16);
@@ -906,16 +955,16 @@ __device__ __forceinline__ void window_tile_part_wide(const uint32_t *hitmap, co
         if (q0 + 32u > qhi) bits &= ~0u >> (q0 + 32u - qhi);
         for (; bits; bits &= bits - 1u) {
             const uint32_t q = q0 + (uint32_t)__builtin_ctz(bits);
-            const uint32_t i = q + ioff;
+            const uint32_t i = q + c.ioff;
             u64 m = hit[q];
-            const u64 f = fwdm[q], c = canm[q];
+            const u64 f = fwdm[q], cn = canm[q];
             for (; m; m &= m - 1ull) {
                 const uint32_t li = (uint32_t)__builtin_ctzll(m);
                 const uint32_t l = lens[li];
                 const uint32_t j = i + l - 1u;
                 if (j >= cws) continue;                                 // scanLimit: may not cross the window end
                 if (!carry && !(always_main || j >= ov)) continue;
-                if ((c >> li) & 1ull) a.can += l; else a.non += l;
+                if ((cn >> li) & 1ull) a.can += l; else a.non += l;
                 if ((f >> li) & 1ull) a.fwd += l; else a.rev += l;
             }
         }
@@ -930,30 +979,28 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
                      const u64 *seg_win_base, const u64 *seg_nwin, const TsWidePatterns W, const TsGenericGeom Q, int tips, uint32_t slot_cap, uint32_t lds_pat,
                      uint32_t *tile_stats, uint32_t *records, uint32_t *win_out, uint32_t *overflow) {
     extern __shared__ __align__(16) unsigned char lds[];
-    // layout: hit M[kTile] | fwd M[kTile] | can M[kTile] | pre6 P[4096] | plo u64[lds_pat] | phi u64[lds_pat] | lens u32[64] | first u32[68] |
-    //         part u32[8] | wtot u32[8] | wbase u32[16] | hitmap u32[128] | cumVG u32[260] | cumCT u32[260] | codes2 | inval | valid2 | lists u16[4][1024] | wacc u32[64][4] | pfl u8[lds_pat]
-    //         (lds_pat: the pattern lists in LDS when they fit — a search step is then an LDS read; out of device memory the searches of the
-    //         few lanes that hold a candidate were 80 % of the kernel's time)
+    // (lds_pat: the pattern lists in LDS when they fit — a search step is then an LDS read; out of device memory the searches of the
+    // few lanes that hold a candidate were 80 % of the kernel's time)
+    const WideLayout L = wide_layout(sizeof(M), sizeof(P), lds_pat);
     M *hit = (M *)lds;
-    M *fwdm = hit + kTile;
-    M *canm = fwdm + kTile;
-    P *pre6 = (P *)(canm + kTile);
-    u64 *plo = (u64 *)(pre6 + 4096u);
-    u64 *phi = plo + lds_pat;
-    uint32_t *lens = (uint32_t *)(phi + lds_pat);
-    uint32_t *first = lens + 64;
-    uint32_t *part = first + 68;
-    uint32_t *wtot = part + 8;                       // per wave: nucleotide totals of its 64 plane dwords {valid | G << 16, C | T << 16}
-    uint32_t *wbase = wtot + 8;                      // the same summed over the waves before (entries 0..4, twice)
-    uint32_t *hitmap = wbase + 16;                   // a bit per tile position that holds a match
-    uint32_t *cumVG = hitmap + 128;                  // per plane dword: counts of the dwords before it in its wave
-    uint32_t *cumCT = cumVG + kWideCumWords;
-    uint32_t *codes2 = cumCT + kWideCumWords;
-    uint32_t *inval = codes2 + kWideCodeWords;
-    uint32_t *valid2 = inval + kWideInvalWords;      // the low bit of each base's pair set: valid (the 2-bit plane's layout)
-    unsigned short *lists = (unsigned short *)(valid2 + kWideCodeWords);   // per wave: its candidate positions (of 1024), ascending
-    uint32_t *wacc = (uint32_t *)(lists + 4u * 1024u);                     // [kWideWacc][4]: canonical, non-canonical, forward, reverse covered, per window record of the tile
-    unsigned char *pfl = (unsigned char *)(wacc + kWideWacc * 4u);
+    M *fwdm = (M *)(lds + L.fwd);
+    M *canm = (M *)(lds + L.can);
+    P *pre6 = (P *)(lds + L.pre6);
+    u64 *plo = (u64 *)(lds + L.plo);
+    u64 *phi = (u64 *)(lds + L.phi);
+    uint32_t *lens = (uint32_t *)(lds + L.lens);
+    uint32_t *first = (uint32_t *)(lds + L.first);
+    uint32_t *part = (uint32_t *)(lds + L.part);
+    uint32_t *wtot = (uint32_t *)(lds + L.wtot);       // per wave: nucleotide totals of its 64 plane dwords {valid | G << 16, C | T << 16}
+    uint32_t *wbase = (uint32_t *)(lds + L.wbase);     // the same summed over the waves before (entries 0..4, twice)
+    uint32_t *hitmap = (uint32_t *)(lds + L.hitmap);   // a bit per tile position that holds a match
+    uint32_t *cum = (uint32_t *)(lds + L.cum);         // per plane dword: counts of the dwords before it in its wave
+    uint32_t *codes2 = (uint32_t *)(lds + L.codes2);
+    uint32_t *inval = (uint32_t *)(lds + L.inval);
+    uint32_t *valid2 = (uint32_t *)(lds + L.valid2);   // the low bit of each base's pair set: valid (the 2-bit plane's layout)
+    unsigned short *lists = (unsigned short *)(lds + L.lists);   // per wave: its candidate positions (of 1024), ascending
+    uint32_t *wacc = (uint32_t *)(lds + L.wacc);       // [kWideWacc][4]: canonical, non-canonical, forward, reverse covered, per window record of the tile
+    unsigned char *pfl = lds + L.pfl;
     if (blockIdx.x >= ntiles) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const bool in_lds = lds_pat != 0u;
@@ -961,15 +1008,8 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
     for (uint32_t i = tid; i < 4096u; i += 256u) pre6[i] = (P)0;
     if (tid < 64u) lens[tid] = tid < W.nlen ? W.len[tid] : 0xFFFFFFFFu;
     if (tid <= W.nlen && tid < 68u) first[tid] = W.first[tid];
-    if (tid == 0u) { cumVG[256] = 0u; cumCT[256] = 0u; }
-    // nucleotide counts of the tile positions [0, q), q <= 4096: {valid | G << 16, C | T << 16}
-    auto prefix_counts = [&](uint32_t q, uint32_t &VG, uint32_t &CT) {
-        const uint32_t d = q >> 4, m = (1u << (2u * (q & 15u))) - 1u;
-        const uint32_t v = valid2[d] & m & 0x55555555u, w = codes2[d], lo = w & v, hi = (w >> 1) & v;
-        const uint32_t g = (uint32_t)__popc(lo & hi);
-        VG = cumVG[d] + wbase[d >> 6] + ((uint32_t)__popc(v) | (g << 16));
-        CT = cumCT[d] + wbase[8u + (d >> 6)] + (((uint32_t)__popc(lo) - g) | (((uint32_t)__popc(hi) - g) << 16));
-    };
+    if (tid == 0u) { cum[256] = 0u; cum[kCumWords + 256] = 0u; }
+    auto counts_to = [&](uint32_t q, uint32_t &VG, uint32_t &CT) { prefix_counts(codes2, valid2, cum, wbase, q, VG, CT); };
     bool tables_built = false;
     const uint32_t fold_mask = Q.fold ? 0xDFDFDFDFu : 0xFFFFFFFFu;
     // sixteen bases of a tile (the layout keeps 64 readable bytes behind the last region; regions start on 16-byte boundaries and
@@ -986,40 +1026,6 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
         }
         return make_uint4(d[0], d[1], d[2], d[3]);
     };
-    // plane dword i / 16 from sixteen bases (ASCII & 6 = twice the code: A 0, C 2, T 4, G 6, and the v_perm selector of the letter
-    // that code stands for; a byte that is not that letter, up to case folding, is invalid)
-    auto stage16 = [&](const uint4 v, uint32_t i, uint32_t avail, bool counts) {
-        uint32_t cw = 0, iv = 0xFFFFu;
-        if (i < avail) {
-            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-            uint32_t t[4], b4[4];
-#pragma unroll
-            for (uint32_t q = 0; q < 4u; ++q) {
-                t[q] = d[q] & 0x06060606u;
-                const uint32_t e = __builtin_amdgcn_perm(0xFF47FF54u, 0xFF43FF41u, t[q]);
-                const uint32_t dd = (d[q] & fold_mask) ^ e;
-                const uint32_t nz = ((((dd & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | dd) & 0x80808080u) >> 7;
-                b4[q] = __builtin_amdgcn_udot4(nz, 0x08040201u, 0u, false);
-            }
-            cw = pack16(t);
-            iv = b4[0] | (b4[1] << 4) | (b4[2] << 8) | (b4[3] << 12);
-            if (i + 16u > avail) iv = (iv | (~0u << (avail - i))) & 0xFFFFu;       // bases behind the region's end
-        }
-        codes2[i >> 4] = cw;
-        ((unsigned short *)inval)[i >> 4] = (unsigned short)iv;
-        uint32_t ok = ~iv & 0xFFFFu;
-        ok = (ok | (ok << 8)) & 0x00FF00FFu; ok = (ok | (ok << 4)) & 0x0F0F0F0Fu;
-        ok = (ok | (ok << 2)) & 0x33333333u; ok = (ok | (ok << 1)) & 0x55555555u;
-        valid2[i >> 4] = ok;                            // (the low bit of each base's pair)
-        if (counts) {                                   // (plane dword tid; every thread is here)
-            const uint32_t lo1 = cw & ok, hi1 = (cw >> 1) & ok, g = (uint32_t)__popc(lo1 & hi1);
-            const uint32_t vg = (uint32_t)__popc(ok) | (g << 16);
-            const uint32_t ct = ((uint32_t)__popc(lo1) - g) | (((uint32_t)__popc(hi1) - g) << 16);
-            const uint32_t ivg = wave_inclusive_dpp(vg), ict = wave_inclusive_dpp(ct);
-            cumVG[tid] = ivg - vg; cumCT[tid] = ict - ct;
-            if (lane == 63u) { wtot[wave] = ivg; wtot[4u + wave] = ict; }
-        }
-    };
     TsGeneralTile T = tiles[blockIdx.x];
     uint4 v_main = load16(T, tid * 16u), v_halo = tid < kWideCodeWords - 256u ? load16(T, 4096u + tid * 16u) : make_uint4(0u, 0u, 0u, 0u);
   TsGeneralTile Tn = T;
@@ -1027,8 +1033,12 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
     if (tables_built) __syncthreads();               // (the tile before is done with the planes and the masks)
     // 1. stage: bases [0, avail) of the tile, avail <= kTile + 64; positions beyond avail are invalid
     const uint32_t avail = T.avail;
-    stage16(v_main, tid * 16u, avail, true);
-    if (tid < kWideCodeWords - 256u) stage16(v_halo, 4096u + tid * 16u, avail, false);
+    {
+        uint32_t vg, ct, hv, hc;
+        stage16(v_main, tid * 16u, avail, fold_mask, codes2, inval, valid2, vg, ct);
+        stage_cum(vg, ct, tid, lane, wave, cum, wtot);
+        if (tid < kWideCodeWords - 256u) stage16(v_halo, 4096u + tid * 16u, avail, fold_mask, codes2, inval, valid2, hv, hc);
+    }
     // the next tile's bases are on their way while this one is worked on
     if (tile + gridDim.x < ntiles) {
         Tn = tiles[tile + gridDim.x];
@@ -1036,11 +1046,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
         if (tid < kWideCodeWords - 256u) v_halo = load16(Tn, 4096u + tid * 16u);
     }
     __syncthreads();
-    if (tid < 5u) {                                  // sums over the waves before (entry 4: the whole tile)
-        uint32_t a = 0, b = 0;
-        for (uint32_t v = 0; v < tid; ++v) { a += wtot[v]; b += wtot[4u + v]; }
-        wbase[tid] = a; wbase[8u + tid] = b;
-    }
+    stage_wave_bases(tid, wtot, wbase);
     // the prefix table: every pattern's first min(l, 6) bases under every extension to six (once per workgroup)
     if (!tables_built)
     for (uint32_t li = 0; li < W.nlen; ++li) {
@@ -1076,7 +1082,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
         }
         if (j0 + 16u > T.n) mask16 &= j0 < T.n ? (1u << (T.n - j0)) - 1u : 0u;     // positions behind the tile's last
         const uint32_t cnt = (uint32_t)__popc(mask16);
-        const uint32_t incl = wave_inclusive_dpp(cnt);
+        const uint32_t incl = wave_scan_add(cnt);
         ncand = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         uint32_t at = incl - cnt;
         for (uint32_t m = mask16; m; m &= m - 1u) list[at++] = (unsigned short)(lane * 16u + (uint32_t)__builtin_ctz(m));
@@ -1151,8 +1157,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
             if (tid < kWideWacc) *(uint4 *)&wacc[4u * tid] = make_uint4(0u, 0u, 0u, 0u);
             __syncthreads();
             const uint32_t ov = Q.w - Q.s;
-            const uint32_t t1 = Q.s - Q.longest, t2 = ov - Q.longest;        // uint32 on purpose (src/teloscope.cpp:413-415)
-            const uint32_t si_inner = t1 < t2 ? t1 : t2;
+            const uint32_t si_inner = inner_start_index(Q, ov);
             for (uint32_t e0 = 0; e0 < ncand; e0 += 64u) {
                 const uint32_t e = e0 + lane;
                 if (e >= ncand) continue;
@@ -1171,9 +1176,9 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
                     const uint32_t i = (uint32_t)(p - wstart);
                     const uint32_t cws = (uint32_t)((n - wstart) < Q.w ? (n - wstart) : Q.w);
                     const bool always_main = (ov == 0u || kw == 0u);
-                    const uint32_t start_index = always_main ? 0u : si_inner;
+                    const uint32_t start_index = call_start(always_main, si_inner);
                     const bool main_i = i >= start_index && i < cws;
-                    const bool carry_i = carries && kw + 1u <= rec_hi && i >= (start_index < Q.s ? Q.s : start_index) && i < cws;
+                    const bool carry_i = carries && kw + 1u <= rec_hi && i >= carry_start(start_index, Q.s) && i < cws;
                     if (!main_i && !carry_i) continue;
                     uint32_t mc = 0, mn = 0, mf = 0, mr = 0, cc = 0, cn = 0, cf = 0, cr = 0;
                     for (u64 mm = m; mm; mm &= mm - 1ull) {
@@ -1193,17 +1198,14 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
             __syncthreads();
             if (tid < nrec) {
                 const u64 R = kw_lo + tid;
-                WideAcc unused = {0, 0, 0, 0, 0};
+                Acc unused = {0, 0, 0, 0, 0};
                 uint32_t tAT = 0, tCG = 0;                                       // A | T << 16, C | G << 16
-                window_tile_part_wide<M, decltype(prefix_counts), true>(hitmap, hit, fwdm, canm, lens, Q, n, R, false, P0, T.n, lane, unused, prefix_counts, tAT, tCG);
-                if (carries && R > 0u) window_tile_part_wide<M, decltype(prefix_counts), true>(hitmap, hit, fwdm, canm, lens, Q, n, R - 1u, true, P0, T.n, lane, unused, prefix_counts, tAT, tCG);
+                window_tile_part_wide<M, decltype(counts_to), true>(hitmap, hit, fwdm, canm, lens, Q, n, R, false, P0, T.n, lane, unused, counts_to, tAT, tCG);
+                if (carries && R > 0u) window_tile_part_wide<M, decltype(counts_to), true>(hitmap, hit, fwdm, canm, lens, Q, n, R - 1u, true, P0, T.n, lane, unused, counts_to, tAT, tCG);
                 const uint4 acc = *(const uint4 *)&wacc[4u * tid];
                 const uint4 lo4 = make_uint4(tAT & 0xFFFFu, tCG & 0xFFFFu, tCG >> 16, tAT >> 16);      // A, C, G, T
-                const u64 span_lo = R * Q.s;
-                const u64 span_hi = span_lo + Q.w < n ? span_lo + Q.w : n;
-                const bool sole = span_lo >= P0 && span_hi <= P0 + T.n;
                 uint32_t *const out = wrec + R * 8ull;
-                if (sole) { *(uint4 *)out = lo4; *(uint4 *)(out + 4) = acc; }
+                if (record_in_tile(R, Q, n, P0, T.n)) { *(uint4 *)out = lo4; *(uint4 *)(out + 4) = acc; }
                 else {
                     if (lo4.x) atomicAdd(out + 0, lo4.x); if (lo4.y) atomicAdd(out + 1, lo4.y); if (lo4.z) atomicAdd(out + 2, lo4.z); if (lo4.w) atomicAdd(out + 3, lo4.w);
                     if (acc.x) atomicAdd(out + 4, acc.x); if (acc.y) atomicAdd(out + 5, acc.y); if (acc.z) atomicAdd(out + 6, acc.z); if (acc.w) atomicAdd(out + 7, acc.w);
@@ -1211,47 +1213,19 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
             }
         } else
         for (u64 R = kw_lo + wave; R <= rec_hi; R += 4u) {
-            WideAcc a = {0, 0, 0, 0, 0};
+            Acc a = {0, 0, 0, 0, 0};
             uint32_t tAT = 0, tCG = 0;                                       // A | T << 16, C | G << 16 (wave-uniform)
-            window_tile_part_wide(hitmap, hit, fwdm, canm, lens, Q, n, R, false, P0, T.n, lane, a, prefix_counts, tAT, tCG);
-            if (carries && R > 0u) window_tile_part_wide(hitmap, hit, fwdm, canm, lens, Q, n, R - 1u, true, P0, T.n, lane, a, prefix_counts, tAT, tCG);
-            const uint32_t tcan = wave_total(a.can), tnon = wave_total(a.non), tfwd = wave_total(a.fwd), trev = wave_total(a.rev);
-            const uint32_t mine = lane == 0u ? (tAT & 0xFFFFu) : lane == 1u ? (tCG & 0xFFFFu) : lane == 2u ? (tCG >> 16) : lane == 3u ? (tAT >> 16)
-                                : lane == 4u ? tcan : lane == 5u ? tnon : lane == 6u ? tfwd : trev;
-            const u64 span_lo = R * Q.s;
-            const u64 span_hi = span_lo + Q.w < n ? span_lo + Q.w : n;
-            const bool sole = span_lo >= P0 && span_hi <= P0 + T.n;
-            if (lane < 8u) {
-                if (sole) wrec[R * 8ull + lane] = mine;
-                else if (mine) atomicAdd(&wrec[R * 8ull + lane], mine);
-            }
+            window_tile_part_wide(hitmap, hit, fwdm, canm, lens, Q, n, R, false, P0, T.n, lane, a, counts_to, tAT, tCG);
+            if (carries && R > 0u) window_tile_part_wide(hitmap, hit, fwdm, canm, lens, Q, n, R - 1u, true, P0, T.n, lane, a, counts_to, tAT, tCG);
+            put_record_wave(wrec, R, tAT, tCG, a, lane, record_in_tile(R, Q, n, P0, T.n));
         }
     }
     __syncthreads();                                   // (the masks are rewritten below)
     // 4. match records: the matches the reference pushes, position then length order; wave v owns positions [1024 v, 1024 v + 1024).
     // A lane per LISTED position (the list is in position order): round 4 walked all 4096 positions twice, and the push test — 64-bit
     // divisions — ran under divergence for every group of 64 positions that held a match.
-    PushGeom pg{};                                     // (as the list form derives it: sums and compares of the host's quotients)
-    {
-        const uint32_t ov = Q.w - Q.s;
-        pg.P0 = P0; pg.n = n; pg.s = Q.s; pg.w = Q.w; pg.ov = ov;
-        const uint32_t t1 = Q.s - Q.longest, t2 = ov - Q.longest;        // uint32 on purpose (src/teloscope.cpp:413-415)
-        pg.start_index = t1 < t2 ? t1 : t2;
-        pg.kP0 = T.k_p0; pg.rP0 = T.r_p0;
-        if (ov == 0u) {
-            pg.k0 = T.k_p0; pg.r0 = T.r_p0;
-            pg.N0 = (n - P0) + T.r_p0;                                    // n - k0 s
-        } else if (P0 > ov) {
-            // P0 - ov = (k_p0 - cw + 1) s + (r_p0 - rw)
-            const bool borrow = T.r_p0 < Q.rw;
-            pg.k1 = T.k_p0 + 1u - Q.cw - (borrow ? 1u : 0u);
-            pg.r1 = T.r_p0 - Q.rw + (borrow ? Q.s : 0u);
-            pg.D1 = pg.r1 + ov;                                           // P0 - k1 s
-            pg.dsub = 0u;
-        } else {
-            pg.k1 = 0u; pg.r1 = 0u; pg.D1 = (uint32_t)P0; pg.dsub = (uint32_t)(ov - P0);
-        }
-    }
+    const PushGeom pg = push_geom_tile(T, n, Q);
+    const auto div_s = [&](uint32_t x) { return x / pg.s; };
     uint32_t wave_cnt = 0;
     for (uint32_t e0 = 0; e0 < ncand; e0 += 64u) {
         const uint32_t e = e0 + lane;
@@ -1261,7 +1235,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
             for (u64 m = hit[j]; m; m &= m - 1ull) {
                 const uint32_t li = (uint32_t)__builtin_ctzll(m);
                 u64 unused_rec;
-                if (tips || full_scan_pushes(j, lens[li], pg, &unused_rec)) keep |= 1ull << li;
+                if (tips || full_scan_pushes(j, lens[li], pg, div_s, &unused_rec)) keep |= 1ull << li;
             }
             hit[j] = (M)keep;
         }
@@ -1282,7 +1256,7 @@ void ts_general_wide(const unsigned char *in, const TsGeneralTile *tiles, uint32
         const uint32_t e = e0 + lane;
         const uint32_t j = e < ncand ? wave * 1024u + list[e] : 0u;
         const u64 keep = e < ncand ? (u64)hit[j] : 0ull;
-        if (__builtin_amdgcn_ballot_w64(keep != 0ull) == 0ull) continue;
+        if (ballot64(keep != 0ull) == 0ull) continue;
         const uint32_t c = (uint32_t)__popcll(keep);
         const uint32_t incl = wave_inclusive(c, lane);
         uint32_t at = base + incl - c;
@@ -1442,8 +1416,7 @@ unsigned long long ts_k_general_lds_bytes(const TsGenericPatterns *G, uint32_t *
     const uint32_t npat = G->first[G->nlen];
     const uint32_t lp = npat <= kMaxLdsPatterns ? (npat ? npat : 1u) : 0u;
     *lds_patterns = lp;
-    return (unsigned long long)kTile * 4u + (unsigned long long)lp * 8u + 8u * 128u * 4u + 32u + kCodeWords * 4u + kInvalWords * 4u +
-           ((lp + 15u) & ~15u);
+    return fused_layout(lp).bytes;
 }
 
 // list != 0: the list form of the pass (see ts_general_fused_list: the caller has checked that a tile adds to at most
@@ -1460,8 +1433,7 @@ int ts_k_launch_general_fused(const unsigned char *in, const TsGeneralTile *tile
     if (list && lp) {
         uint32_t nshort = 0;
         for (uint32_t li = 0; li < G->nlen; ++li) nshort += G->len[li] <= kShortLen ? 1u : 0u;
-        const unsigned long long lds2 = 4ull * kListWave * 2u + (((unsigned long long)lp * 8u + 15u) & ~15ull) + 4096u + nshort * 1024u + kWaccMax * 16u + 32u + 48u + 32u + 64u +
-                                        kCodeWords * 4u + kInvalWords * 4u + kCodeWords * 4u + 2u * kCumWords * 4u + ((lp + 15u) & ~15u);
+        const unsigned long long lds2 = list_layout(lp, nshort).bytes;
         // persistent workgroups: as many as the device holds at once (LDS bound), each strides over the tiles
         // (what the runtime says fits: a grid of more workgroups than are resident at once ends in a round of stragglers —
         // 1280 workgroups where 1024 fit measured 7.0 ms against 6.0, profiles/r04/general_occupancy.txt)
@@ -1565,14 +1537,12 @@ int ts_k_launch_general_wide(const unsigned char *in, const TsGeneralTile *tiles
                              const TsWidePatterns *W, const TsGenericGeom *Q, int tips, uint32_t slot_cap,
                              uint32_t *tile_stats, uint32_t *records, uint32_t *win_out, uint32_t *overflow, void *stream) {
     if (ntiles == 0) return 0;
-    const size_t fixed = 64u * 4u + 68u * 4u + 32u + 32u + 64u + 128u * 4u + 2u * kWideCumWords * 4u + 2u * kWideCodeWords * 4u + kWideInvalWords * 4u + 4u * 1024u * 2u + (kWideWacc + 1u) * 16u;
     static const int cus = [] { int v = 0, dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; return v; }();
-    auto launch = [&](auto kernel, size_t mask_bytes, size_t pre_bytes) -> hipError_t {
-        const size_t tables = 3u * (size_t)kTile * mask_bytes + 4096u * pre_bytes + fixed;
+    auto launch = [&](auto kernel, uint32_t mask_bytes, uint32_t pre_bytes) -> hipError_t {
         // the pattern lists in LDS (17 bytes per pattern) when they fit beside the tables
         uint32_t lds_pat = W->npat <= 2048u ? W->npat : 0u;
-        if (tables + (size_t)lds_pat * 16u + ((lds_pat + 15u) & ~15u) > (160u << 10)) lds_pat = 0u;
-        const size_t lds = tables + (size_t)lds_pat * 16u + ((lds_pat + 15u) & ~15u);
+        if (wide_layout(mask_bytes, pre_bytes, lds_pat).bytes > (160u << 10)) lds_pat = 0u;
+        const size_t lds = wide_layout(mask_bytes, pre_bytes, lds_pat).bytes;
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // (up to 160 KB: above the default limit)
         if (e != hipSuccess) return e;
         // persistent workgroups: as many as fit beside each other (LDS), each takes the tiles blockIdx.x, + gridDim.x, ...

@@ -33,6 +33,7 @@
 
 #include <type_traits>
 
+#include "ts_device.h"
 #include "ts_internal.h"
 
 // Wave priorities (s_setprio; the SIMD's arbiter picks the ready wave of the highest priority, the oldest among equals).
@@ -52,7 +53,6 @@ typedef unsigned long long u64;
 // LDS pointers are declared in their own address space so that indexing stays 32-bit arithmetic
 #define LDS __attribute__((address_space(3)))
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef LDS unsigned char lds_u8;
 typedef LDS uint16_t lds_u16;
 typedef LDS uint32_t lds_u32;
@@ -60,81 +60,6 @@ typedef LDS uint32_t lds_u32;
 // an LDS byte address (the dynamic-LDS base is 0) as a pointer
 __device__ __forceinline__ lds_u16 *lds_at16(uint32_t addr) { return (lds_u16 *)(uintptr_t)addr; }
 __device__ __forceinline__ lds_u8 *lds_at8(uint32_t addr) { return (lds_u8 *)(uintptr_t)addr; }
-
-// Global stores the compiler does not see.  On gfx9 loads and stores share one counter (vmcnt) and may
-// retire out of order with respect to each other, so once a store is pending the compiler can only wait for a LOAD with vmcnt(0) —
-// and it does so early: in front of every loop that holds a store and no load it empties the counter ("flush in the preheader").
-// In this kernel that meant an s_waitcnt vmcnt(0) right behind the request of the next tile's first chunk (the last drain of the
-// match queue is such a loop: its overflow path stores), i.e. the prefetch was waited for on the spot, and two more in phase 2.
-// The stores never feed a load of this kernel (the one place that reads records back waits for vmcnt(0) itself), so they are issued
-// by inline asm: the compiler counts only its loads, whose waits stay counted, and a pending store can only make such a wait longer,
-// never too short (loads retire in order among themselves).  Measurements: profiles/r05/asm_stores.txt.
-__device__ __forceinline__ void gstore(uint32_t *p, uint32_t v) {
-    asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v));
-}
-__device__ __forceinline__ void gstore(uint16_t *p, uint16_t v) {
-    asm volatile("global_store_short %0, %1, off" :: "v"(p), "v"((uint32_t)v));
-}
-// (the low 16 bits of v: the store takes them itself)
-__device__ __forceinline__ void gstore_lo16(uint16_t *p, uint32_t v) {
-    asm volatile("global_store_short %0, %1, off" :: "v"(p), "v"(v));
-}
-__device__ __forceinline__ void gstore(unsigned char *p, unsigned char v) {
-    asm volatile("global_store_byte %0, %1, off" :: "v"(p), "v"((uint32_t)v));
-}
-__device__ __forceinline__ void gstore(u64 *p, u64 v) {
-    asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(v));
-}
-__device__ __forceinline__ void gstore(uint4 *p, uint4 v) {
-    const u32x4 d = {v.x, v.y, v.z, v.w};
-    // (s_nop: a store of more than 8 bytes reads its data a cycle late, and the hazard recogniser does not look into asm)
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 0" :: "v"(p), "v"(d));
-}
-// (possibly unaligned: the bit-packed window records)
-__device__ __forceinline__ void gstore_unaligned(unsigned char *p, u64 v) {
-    asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(v));
-}
-__device__ __forceinline__ void gstore_unaligned(unsigned char *p, uint32_t v) {
-    asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v));
-}
-
-// Wave-wide inclusive prefix sum in 6 DPP adds (row_shr 1/2/4/8 inside each row of 16,
-// then row_bcast:15 into rows 1,3 and row_bcast:31 into rows 2,3); no LDS traffic.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
-    v = dpp_add<0x111, 0xf>(v);
-    v = dpp_add<0x112, 0xf>(v);
-    v = dpp_add<0x114, 0xf>(v);
-    v = dpp_add<0x118, 0xf>(v);
-    v = dpp_add<0x142, 0xa>(v);
-    v = dpp_add<0x143, 0xc>(v);
-    return v;
-}
-
-// (a DPP move folded into the subtraction that follows it came back wrong on gfx950 — see blockcall.hip — so the places that take the
-// lane below's value keep it a v_mov_b32_dpp behind an empty asm)
-__device__ __forceinline__ unsigned long long low_bits(uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }
-
-// the lanes for which `p` holds, as a mask: on a bool this is one scalar AND of the compare's result with exec (__ballot takes
-// an int: the bool is first materialised per lane and compared again, two vector instructions per ballot)
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-
-
-// sixteen 2-bit codes, held doubled (2 * code = ASCII & 6) one per byte of t[0..3] -> one dword, base i at
-// bits 2i..2i+1; four independent v_dot4_u32_u8 (weights 1,4,16,64: twice the packed byte, 9 bits) and four
-// shift/or, no dependent dot chain
-__device__ __forceinline__ uint32_t pack16(const uint32_t t[4]) {
-    const uint32_t b0 = __builtin_amdgcn_udot4(t[0], 0x40100401u, 0u, false);
-    const uint32_t b1 = __builtin_amdgcn_udot4(t[1], 0x40100401u, 0u, false);
-    const uint32_t b2 = __builtin_amdgcn_udot4(t[2], 0x40100401u, 0u, false);
-    const uint32_t b3 = __builtin_amdgcn_udot4(t[3], 0x40100401u, 0u, false);
-    return ((b0 | (b1 << 8)) >> 1) | ((b2 | (b3 << 8)) << 15);
-}
-
 
 __host__ __device__ inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
 
@@ -453,8 +378,7 @@ void ts_scan_tiles(const TsScanParams P) {
                 const uint32_t t = ch_cc + ncan;
                 if ((t | (~ch_w1 & TS_CHAIN_HEADS)) != 0u) {            // (integer logic: a uniform bool costs three scalar instructions to combine)
                     // the lane below holds the record before, lane 0 gets the last record of the row before
-                    uint32_t below = (uint32_t)__builtin_amdgcn_update_dpp((int)ch_last, (int)u, 0x138, 0xf, 0xf, false);   // wave_shr:1, lane 0 keeps ch_last
-                    asm volatile("" : "+v"(below));            // (kept a v_mov_b32_dpp: see lane_below)
+                    const uint32_t below = lane_below(u, ch_last);
                     const u64 H = FULL ? ballot64(u - below > kdist) : live_m & ballot64(u - below > kdist);
                     if (__builtin_expect(t >= 4u, 0)) {
                         // a chain that ends in this row may hold the four canonical records a block needs: the exact look
@@ -760,7 +684,7 @@ void ts_scan_tiles(const TsScanParams P) {
                 if (dense) {
                     m = (lane / kGroup == gi) ? M32 : 0u;
                     nm = __popc(m);
-                    incl = wave_scan_incl(nm);
+                    incl = wave_scan_add(nm);
                     total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 }
                 // the queue keeps whatever is short of a full pass; it is emptied first if these
@@ -782,7 +706,7 @@ void ts_scan_tiles(const TsScanParams P) {
             if (!__any((mA | mB) != 0u)) return;
             set_prio(kPrioAppend);
             const uint32_t nA = __popc(mA), nB = __popc(mB);
-            const uint32_t incl = wave_scan_incl(nA | (nB << 16));
+            const uint32_t incl = wave_scan_add(nA | (nB << 16));
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             const uint32_t totA = tot & 0xFFFFu, totB = tot >> 16;
             if (totA + totB + 63u > TS_LIST) {                    // rare: does not fit behind what a pass may leave

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ts_device.h"
 #include "ts_internal.h"
 
 namespace {
@@ -277,23 +278,6 @@ __device__ __forceinline__ bool pred_walk_read(const TsTile *tiles, const u64 *t
     return bf.pass || br.pass;
 }
 
-// Wave-wide inclusive prefix maximum in 6 DPP steps (row_shr 1/2/4/8 inside each row of 16, then row_bcast:15 into rows
-// 1,3 and row_bcast:31 into rows 2,3); lanes outside a shift read 0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_max(uint32_t v) {
-    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-    return v > o ? v : o;
-}
-__device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {
-    v = dpp_max<0x111, 0xf>(v);
-    v = dpp_max<0x112, 0xf>(v);
-    v = dpp_max<0x114, 0xf>(v);
-    v = dpp_max<0x118, 0xf>(v);
-    v = dpp_max<0x142, 0xa>(v);
-    v = dpp_max<0x143, 0xc>(v);
-    return v;
-}
-
 // A long match list walked by a whole wave, 64 records per step IN PARALLEL (all arguments wave-uniform).
 // Valid when the whole segment is terminal zone (n <= terminal_limit: every read): then the walk never stops
 // early, and the two-phase state machine gives the same answer in either direction, so both lists are taken in
@@ -322,6 +306,8 @@ __device__ __forceinline__ bool pred_scan_wave(const TsTile *tiles, const u64 *t
             const uint32_t p32 = rec >> 2;                   // tile-relative position (a batch lies in one tile)
             // predecessor among the selected records of this batch: prefix maximum of (position + 1), one lane down
             const uint32_t incl = wave_scan_max(sel ? p32 + 1u : 0u);
+            // (not lane_below: its empty asm reorders this kernel's scalar code and costs an SGPR; here the compiler emits a plain
+            // v_mov_b32_dpp without it)
             const uint32_t before = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x138, 0xf, 0xf, false);   // wave_shr:1
             const uint32_t first_lane = (uint32_t)__builtin_ctzll(rem);
             const u64 first_pos = rel0 + (uint32_t)__builtin_amdgcn_readlane((int)p32, (int)first_lane);
