@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -195,7 +196,11 @@ extern "C" int ts_scan_segments_multi(ts_ctx *const *ctxs, size_t n_ctx, const t
         if (which.empty()) continue;
         std::string why;
         const bool tiled = mode ? c0->fast_ok : ts_full_scan_supported(c0, why);
-        if (!tiled) { rc = whole_segments(which); continue; }
+        if (!tiled) {
+            if (c0->knobs.timing) fprintf(stderr, "multi: whole segments per context (%s)\n", why.c_str());
+            rc = whole_segments(which);
+            continue;
+        }
         std::vector<uint64_t> lens(which.size()), abs(which.size());
         std::vector<ts_segment_in> in(which.size());
         for (size_t i = 0; i < which.size(); ++i) { in[i] = segs[which[i]]; lens[i] = in[i].len; abs[i] = in[i].abs_pos; }
@@ -222,10 +227,12 @@ extern "C" int ts_scan_segments_multi(ts_ctx *const *ctxs, size_t n_ctx, const t
         for (PartJob &j : jobs) if (j.landing.owns_lock()) j.landing.unlock();
         if (frc == TS_SHARD_NEED_FULL || frc == TS_SHARD_RETRY_SYNC || frc == TS_SHARD_RETRY_GROW) {
             // (the parts synced and regrew by themselves; what is left is an input the shards' assumptions do not hold for)
+            if (c0->knobs.timing) fprintf(stderr, "multi: the shards' results were not final: scanned again on one context\n");
             rc = single(which);
             continue;
         }
         if (frc != TS_OK) { rc = frc; break; }
+        if (c0->knobs.timing) fprintf(stderr, "multi: %u shards merged\n", n_parts);
         for (size_t i = 0; i < which.size(); ++i) { out[which[i]] = tmp[i]; if (counts) counts[which[i]] = cnt[i]; }
     }
     if (rc != TS_OK) ts_free_segments(out, n_segs);

@@ -1080,6 +1080,7 @@ struct GenCall {
     Clock::time_point t_begin = Clock::now();
     double t_up = 0, t_dev = 0, t_host = 0, t_take = 0, t_fused = 0, t_blk = 0, t_d2h = 0, t_wait_next = 0, t_dbg[3] = {0, 0, 0};
     float t_kern = 0;
+    uint32_t n_list = 0, n_strided = 0;                   // groups whose fused pass took the list / the position-strided form
 
     GenCall(ts_ctx *c_, Mode m, bool t, const std::vector<Item> &it, Outputs out)
         : c(c_), P(c_->params), mode(m), tips(t), blocks_only(m != Mode::Matches), wide(c_->gen_wide), items(it), o(out),
@@ -1258,6 +1259,7 @@ int gen_fused(GenCall &g, GenGroup &gr) {
         c->pool.give(std::move(gr.d_slots));
         HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)gr.slot_cap * 4, gr.d_slots));
     }
+    ++(use_list ? g.n_list : g.n_strided);
     gr.nrec = tile_off[nt];
     g.t_fused += ms_between(t1, Clock::now());
     return TS_OK;
@@ -1441,6 +1443,7 @@ int scan_general(ts_ctx *c, Mode mode, bool tips, const std::vector<Item> &items
                 g.t_take, g.t_fused, g.t_blk, g.t_d2h, g.t_wait_next, g.t_dbg[0], g.t_dbg[1], g.t_dbg[2]);
         fprintf(stderr, "general path: route: %s form, blocks called on the device, stream %s\n", g.wide ? "wide" : "table",
                 g.position_order ? "in position order" : "written in push order by the device");
+        fprintf(stderr, "general path: fused pass: %u groups in the list form, %u in the strided form\n", g.n_list, g.n_strided);
         fprintf(stderr, "general path: %zu segments, wall %.1f ms: upload %.1f ms, kernels + D2H %.1f ms (kernels alone, HIP events: %.2f ms), host stage %.1f ms (on a thread of its own, one group behind)\n",
                 items.size(), ms_between(g.t_begin, Clock::now()), g.t_up, g.t_dev, (double)g.t_kern, g.t_host);
     }
