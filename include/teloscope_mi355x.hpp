@@ -58,6 +58,10 @@ struct UserInputTeloscope {                    // include/input.h:15-64 (fields 
     bool outWinRepeats = false, outGC = false, outEntropy = false, outMatches = false, outITS = false;
     bool ultraFastMode = true;
     int device = -1;                           // HIP device ordinal (-1 = current); not in the reference
+    // assembly record filters (include/input.h:21-27; include/teloscope_mi355x_filter.hpp): off by default
+    std::vector<std::string> includeBedFiles, excludeBedFiles, includePrefixes, excludePrefixes;
+    bool sequenceFilterActive = false;
+    uint64_t filterInputCount = 0, filterSelectedCount = 0;
 };
 
 struct MatchInfo {                             // include/teloscope.h:89-95

@@ -12,6 +12,15 @@
 // Input lines are written back verbatim (line ends as read) with two exceptions: the header says VN:Z:1.2 (added when the input
 // has none, replacing a VN:Z:2.0), and a GFA 2 segment `S name len seq [tags]` loses its length field.  Other GFA 2 records are
 // refused.  GFA 1.1 W lines are copied through and are not read as paths.
+//
+// Assembly record filters (include/teloscope_mi355x_filter.hpp) select paths, or the segments of a pathless graph:
+//
+//   validateFilteredGfa(file);                                  // GFA 1 with P paths or none; throws SequenceFilterError
+//   GfaGraph g = readGfa(file);
+//   SequenceSelection sel = selectGfa(g, selector);             // candidates: path names, or segment names without paths
+//   ... Teloscope t(ui); annotateGfa(t, g, &sel, outDir);       // ends of selected paths / selected segments only
+//
+// or annotateGfa(teloscope, file, outDir, selector) for all of it.  Every input line, unselected P lines included, is written back.
 #pragma once
 
 #include <algorithm>
@@ -28,6 +37,7 @@
 #include <utility>
 #include <vector>
 
+#include "teloscope_mi355x_filter.hpp"
 #include "teloscope_mi355x_io.hpp"
 
 namespace teloscope_mi355x {
@@ -225,12 +235,14 @@ inline GfaGraph readGfa(const std::string &file) {
 
 // The ends the reference scans (src/input.cpp:637-674).  With P lines: per path, the first and the last component that
 // names an S record with orientation '+' / '-', as unique (segment, orientation, isFirst) ends in that order.  Without:
-// every segment, '+'.
-inline std::vector<GfaEnd> gfaTerminalJobs(const GfaGraph &g) {
+// every segment, '+'.  keep (a selection, selectGfa): per path — or per segment of a pathless graph — whether it takes part.
+inline std::vector<GfaEnd> gfaTerminalJobs(const GfaGraph &g, const std::vector<char> *keep = nullptr) {
     std::vector<GfaEnd> jobs;
     if (!g.paths.empty()) {
         std::set<std::tuple<uint32_t, char, bool>> ends;
-        for (const GfaPath &p : g.paths) {
+        for (size_t pi = 0; pi < g.paths.size(); ++pi) {
+            if (keep && !(*keep)[pi]) continue;
+            const GfaPath &p = g.paths[pi];
             std::vector<std::pair<uint32_t, char>> comps;
             for (const auto &c : p.comps) {
                 if (c.second != '+' && c.second != '-') continue;
@@ -244,7 +256,8 @@ inline std::vector<GfaEnd> gfaTerminalJobs(const GfaGraph &g) {
         for (const auto &e : ends) jobs.push_back({std::get<0>(e), std::get<1>(e), std::get<2>(e), true});
     } else {
         jobs.reserve(g.segments.size());
-        for (uint32_t i = 0; i < g.segments.size(); ++i) jobs.push_back({i, '+', false, false});
+        for (uint32_t i = 0; i < g.segments.size(); ++i)
+            if (!keep || (*keep)[i]) jobs.push_back({i, '+', false, false});
     }
     return jobs;
 }
@@ -325,16 +338,68 @@ inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jo
     return nodes.size();
 }
 
-// teloscope asm.gfa -o outDir: outDir/<name>.telo.annotated.gfa and outDir/<name>.telo.annotated.colors.csv
-inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &file, const std::string &outDir,
-                                    std::ostream &log = std::cerr) {
+// With assembly record filters the input must be a GFA 1 graph with P paths or none (src/input.cpp:206-283): throws a
+// SequenceFilterError naming the first line that is not, before the graph is read.  Blank and '#' lines are skipped.
+inline void validateFilteredGfa(const std::string &file) {
+    const std::string gfa2 = "; use GFA1 P paths or a pathless GFA1 graph.";
+    if (detail::caseInsensitiveSuffix(file, ".gfa2") || detail::caseInsensitiveSuffix(file, ".gfa2.gz"))
+        throw SequenceFilterError("Assembly record filters do not support GFA2" + gfa2);
+    std::string data;
+    try {
+        data = detail::gfaReadAll(file);
+    } catch (const std::exception &e) {
+        throw SequenceFilterError(e.what());
+    }
+    uint64_t lineNo = 0;
+    for (size_t ls = 0; ls < data.size();) {
+        const size_t nl = data.find('\n', ls);
+        std::string line = data.substr(ls, (nl == std::string::npos ? data.size() : nl) - ls);
+        ls = nl == std::string::npos ? data.size() : nl + 1;
+        ++lineNo;
+        line.erase(std::remove(line.begin(), line.end(), '\r'), line.end());
+        if (line.empty() || line[0] == '#') continue;
+        const std::string at = " at line " + std::to_string(lineNo);
+        if (line.compare(0, 2, "H\t") == 0 && line.find("\tVN:Z:2") != std::string::npos)
+            throw SequenceFilterError("Assembly record filters do not support GFA2" + at + gfa2);
+        if (line.size() < 2 || line[1] != '\t')
+            throw SequenceFilterError("Assembly record filters found a malformed or unsupported GFA record" + at + ".");
+        const char type = line[0];
+        if (std::strchr("OUEGF", type))
+            throw SequenceFilterError(std::string("Assembly record filters do not support GFA2 record type '") + type + "'" + at + gfa2);
+        if (type == 'W') throw SequenceFilterError("Assembly record filters do not support GFA1 W walks" + at + gfa2);
+        if (type == 'C') throw SequenceFilterError("Assembly record filters do not support GFA1 C containment records" + at + ".");
+        if (type == 'S') {                                         // S name LEN seq: a GFA 2 segment
+            const size_t t2 = line.find('\t', 2), t3 = t2 == std::string::npos ? t2 : line.find('\t', t2 + 1);
+            if (t3 != std::string::npos && t3 > t2 + 1 &&
+                std::all_of(line.begin() + static_cast<long>(t2) + 1, line.begin() + static_cast<long>(t3),
+                            [](char c) { return c >= '0' && c <= '9'; }))
+                throw SequenceFilterError("Assembly record filters do not support GFA2 segment records" + at + gfa2);
+        }
+        if (!std::strchr("HSLJP", type))
+            throw SequenceFilterError(std::string("Assembly record filters do not support GFA record type '") + type + "'" + at + ".");
+    }
+}
+
+// The selection of a graph (src/input.cpp:596-623): its P lines' names, or — a pathless graph — its segments' names, each up
+// to its first whitespace.  sel.keep is indexed like g.paths, or like g.segments.
+inline SequenceSelection selectGfa(const GfaGraph &g, const SequenceSelector &selector) {
+    std::vector<std::string> names;
+    if (!g.paths.empty())
+        for (const GfaPath &p : g.paths) names.push_back(sequenceFilterId(p.name));
+    else
+        for (const GfaSegment &sg : g.segments) names.push_back(sequenceFilterId(sg.name));
+    return selector.select(names, g.paths.empty() ? "segments" : "paths");
+}
+
+// teloscope asm.gfa -o outDir on a graph already read: outDir/<name>.telo.annotated.gfa and .colors.csv.  selection: selectGfa's
+// (nullptr: every path / segment)
+inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const GfaGraph &g, const SequenceSelection *selection,
+                                    const std::string &outDir, std::ostream &log = std::cerr) {
     using Clock = std::chrono::steady_clock;
     auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     GfaAnnotateStats st;
-    const auto t0 = Clock::now();
-    const GfaGraph g = readGfa(file);
-    const std::vector<GfaEnd> jobs = gfaTerminalJobs(g);
     const auto t1 = Clock::now();
+    const std::vector<GfaEnd> jobs = gfaTerminalJobs(g, selection ? &selection->keep : nullptr);
     const GfaEnds e = gfaScanEnds(teloscope, g, jobs, log);
     const auto t2 = Clock::now();
     const std::string stem = outDir + "/" + g.baseName + ".telo.annotated";
@@ -344,9 +409,35 @@ inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &fil
     st.ends = jobs.size();
     st.scanned = e.scanned;
     st.noSeq = e.noSeq;
-    st.parseMs = ms(t0, t1);
     st.scanMs = ms(t1, t2);
     st.writeMs = ms(t2, t3);
+    return st;
+}
+
+// teloscope asm.gfa -o outDir: outDir/<name>.telo.annotated.gfa and outDir/<name>.telo.annotated.colors.csv
+inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                    std::ostream &log = std::cerr) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const GfaGraph g = readGfa(file);
+    const double parseMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    GfaAnnotateStats st = annotateGfa(teloscope, g, nullptr, outDir, log);
+    st.parseMs += parseMs;
+    return st;
+}
+
+// the same with assembly record filters: validateFilteredGfa (when the selector is active), readGfa, selectGfa — whose line
+// goes to `log` — and the annotation of the selected paths / segments.  (A caller that must not touch the device before the
+// selection is known runs these steps itself, as the overview above shows.)
+inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                    const SequenceSelector &selector, std::ostream &log = std::cerr) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (selector.active()) validateFilteredGfa(file);
+    const GfaGraph g = readGfa(file);
+    const SequenceSelection sel = selectGfa(g, selector);
+    if (selector.active()) log << selectionMessage(sel) << "\n";
+    const double parseMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    GfaAnnotateStats st = annotateGfa(teloscope, g, &sel, outDir, log);
+    st.parseMs += parseMs;
     return st;
 }
 

@@ -45,6 +45,7 @@
 #include <zlib.h>
 
 #include "teloscope_mi355x.hpp"
+#include "teloscope_mi355x_filter.hpp"
 
 namespace teloscope_mi355x {
 
@@ -374,9 +375,11 @@ inline std::vector<PathComponents> splitPaths(const std::vector<RecordView> &rec
     return comps;
 }
 
-// walkPath for every record, with one batched scan (result order = record order; seqPos = seqPosBase + index).
+// walkPath for every record, with one batched scan (result order = record order; seqPos = seqPosBase + index, or
+// (*seqPositions)[index] when given: the records' indices in the whole input, which a record filter leaves with gaps).
 inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::vector<RecordView> &records, size_t seqPosBase = 0,
-                                             const std::vector<PathComponents> *precomputed = nullptr) {
+                                             const std::vector<PathComponents> *precomputed = nullptr,
+                                             const std::vector<size_t> *seqPositions = nullptr) {
     const UserInputTeloscope &ui = teloscope.input();
     // (the streaming reader finds the N-runs while the freshly joined bases are still in cache)
     const std::vector<PathComponents> split = precomputed ? std::vector<PathComponents>() : splitPaths(records);
@@ -451,7 +454,7 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
     size_t si = 0;
     for (size_t pi = 0; pi < records.size(); ++pi) {
         PathData &pd = paths[pi];
-        pd.seqPos = static_cast<unsigned int>(seqPosBase + pi);
+        pd.seqPos = static_cast<unsigned int>(seqPositions ? (*seqPositions)[pi] : seqPosBase + pi);
         pd.header = *records[pi].header;
         pd.pathSize = records[pi].size;
         pd.gapInfos = comps[pi].gaps;
@@ -1310,6 +1313,9 @@ struct AssemblySummary {
     uint32_t byType[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t scaffoldN50 = 0, contigN50 = 0;
     float teloMean = 0.0f, teloMedian = 0.0f, teloMin = 0.0f, teloMax = 0.0f;
+    // assembly record filters (src/teloscope.cpp:1007-1012): the two counts are printed only when filtering was on
+    bool filterActive = false;
+    uint64_t filterInputCount = 0, filterSelectedCount = 0;
 };
 
 namespace detail {
@@ -1606,7 +1612,10 @@ inline void writeBEDFiles(const std::string &outBase, const std::vector<PathData
 inline void printSummary(std::ostream &console, const AssemblySummary &s, bool ultraFastMode, const std::string &reportFile = "") {
     using detail::line;
     std::string t;
-    line(t, "\n+++ Assembly Summary Report +++\n", "Total paths:\t", uint64_t(s.totalPaths), '\n', "Total gaps:\t", uint64_t(s.totalGaps), '\n',
+    line(t, "\n+++ Assembly Summary Report +++\n", "Total paths:\t", uint64_t(s.totalPaths), '\n');
+    if (s.filterActive)
+        line(t, "Filter input paths:\t", s.filterInputCount, '\n', "Filter selected paths:\t", s.filterSelectedCount, '\n');
+    line(t, "Total gaps:\t", uint64_t(s.totalGaps), '\n',
          "Scaffold N50:\t", s.scaffoldN50, '\n', "Contig N50:\t", s.contigN50, '\n', "Total telomeres:\t", uint64_t(s.totalTelomeres), '\n');
     if (!ultraFastMode)
         line(t, "Total ITS blocks:\t", uint64_t(s.totalITS), '\n', "Total canonical matches:\t", uint64_t(s.totalCanMatches), '\n',
@@ -1697,6 +1706,7 @@ struct RawRecord {                                              // a record of a
 
 struct FastaGroup {
     size_t firstRecord = 0;
+    std::vector<size_t> seqPos;                                 // per record: its index in the whole input
     std::vector<RawRecord> records;
     std::vector<PathComponents> comps;                          // of `records`, found while their bases were copied
     std::shared_ptr<void> mapping;                              // text mode: the records' pieces point into the mapped file
@@ -1706,30 +1716,76 @@ struct FastaGroup {
 }  // namespace detail
 
 // Groups of consecutive records of a FASTA file, each with its records' lines joined.
+//
+// Assembly record filters: the reader is made with strict = true (the filtered loader's rules, src/input.cpp:285-361, are
+// checked while the records are located; a SequenceFilterError names the first offence), its primaryIds() go through
+// SequenceSelector::select, and keep(sel.keep) before the first next() leaves the dropped records out of every group: they are
+// never joined, split or handed to the library, and group sizes count kept bytes only.  Each group carries its records' input
+// indices (FastaGroup::seqPos).  A strict reader of input that cannot be mapped (gzip, a FIFO) decompresses it into memory
+// first and then works as on a mapped file.
 class FastaGroupReader {
     struct Span { const char *head, *body, *stop; };
     int fd = -1;
     void *map = nullptr;
     size_t mapSize = 0;
     std::shared_ptr<void> mapping;                              // unmaps when the reader AND every group that points into it are gone
+    const char *text = nullptr;                                 // the records' text: the mapped file, or (strict) the decompressed input
+    size_t textSize = 0;
     std::vector<Span> spans;
     size_t nextSpan = 0;
     size_t groupBytes, pieceBytes;
     bool textPieces;                                            // records as text pieces (line ends skipped by the library's staging)
     std::vector<FastaRecord> all;                               // not a mapped plain file: everything was read up front
     bool mapped = false;
+    bool strict = false;
+    std::vector<std::string> ids;                               // primary IDs (strict: found while checking)
+    std::vector<char> kept;                                     // empty = every record
+    uint64_t nKept = 0;
+
+    size_t records() const { return mapped ? spans.size() : all.size(); }
+    bool isKept(size_t i) const { return kept.empty() || kept[i]; }
+    static std::string idOf(const Span &sp) {                   // the header up to its first whitespace
+        const char *e = sp.body > sp.head && sp.body[-1] == '\n' ? sp.body - 1 : sp.body, *w = sp.head;
+        while (w < e && !std::strchr(" \t\r\n\f\v", *w)) ++w;
+        return std::string(sp.head, w);
+    }
+
+    // the filtered loader's rules over the located records, in the order the reference meets them while reading line by line
+    void checkStrict(const char *data, const char *first) {
+        if (!spans.empty() ? spans[0].head - 1 > first : first < data + textSize)
+            throw SequenceFilterError("Assembly record filters require FASTA input or a recognized GFA file.");
+        auto hasBases = [](const Span &sp) {
+            for (const char *p = sp.body; p < sp.stop; ++p)
+                if (*p != '\n' && *p != '\r') return true;
+            return false;
+        };
+        std::unordered_set<std::string> seen;
+        ids.resize(spans.size());
+        for (size_t i = 0; i < spans.size(); ++i) {
+            if (i && !hasBases(spans[i - 1])) throw SequenceFilterError("FASTA record '" + ids[i - 1] + "' has no sequence.");
+            ids[i] = idOf(spans[i]);
+            if (ids[i].empty()) throw SequenceFilterError("FASTA input contains an empty primary sequence ID.");
+            if (!seen.insert(ids[i]).second) throw SequenceFilterError("Input contains duplicate primary sequence ID: '" + ids[i] + "'.");
+        }
+        if (spans.empty()) throw SequenceFilterError("Assembly input is empty.");
+        if (!hasBases(spans.back())) throw SequenceFilterError("FASTA record '" + ids.back() + "' has no sequence.");
+    }
 
 public:
     // pieceBytes: text bytes a host thread handles at a time (a record's lines are counted / joined by pieces, in parallel).
     // textPieces: do not join the lines at all — a record is the list of its text pieces in the mapped file, with their
     // base counts and N-runs (one pass over the text); the library strips the line ends while it stages the upload
     // (TS_INPUT_TEXT_PIECES).  Only for a mapped plain file; gzip / stdin input is joined by zlib's reader anyway.
+    // strict: assembly record filters are on (see above).
     explicit FastaGroupReader(const std::string &file, size_t groupBytes_ = size_t(256) << 20, size_t pieceBytes_ = size_t(4) << 20,
-                              bool textPieces_ = false)
+                              bool textPieces_ = false, bool strict_ = false)
         : groupBytes(std::max<size_t>(groupBytes_, 1)), pieceBytes(std::min<size_t>(std::max<size_t>(pieceBytes_, 1), size_t(16) << 20)),
-          textPieces(textPieces_) {
+          textPieces(textPieces_), strict(strict_) {
         fd = ::open(file.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("cannot open " + file);
+        if (fd < 0) {
+            if (strict) throw SequenceFilterError("Could not open assembly input '" + file + "'.");
+            throw std::runtime_error("cannot open " + file);
+        }
         struct stat sb;
         unsigned char magic[2] = {0, 0};
         const bool gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
@@ -1738,27 +1794,49 @@ public:
             map = ::mmap(nullptr, mapSize, PROT_READ, MAP_PRIVATE, fd, 0);
             if (map == MAP_FAILED) map = nullptr;
         }
-        if (!map) {                                              // gzip (zlib is one serial stream anyway), FIFOs, empty files
-            ::close(fd); fd = -1;
-            all = readFasta(file);
-            return;
-        }
-        mapped = true;
-        {
+        if (map) {
             const size_t n = mapSize;
             mapping = std::shared_ptr<void>(map, [n](void *p) { ::munmap(p, n); });
+            (void)::madvise(map, mapSize, MADV_SEQUENTIAL);
+            text = static_cast<const char *>(map);
+            textSize = mapSize;
+        } else {
+            ::close(fd); fd = -1;
+            if (!strict) {                                       // gzip (zlib is one serial stream anyway), FIFOs, empty files
+                all = readFasta(file);
+                return;
+            }
+            auto buf = std::make_shared<std::string>();          // plain and gzip alike, through zlib
+            gzFile in = gzopen(file.c_str(), "rb");
+            if (!in) throw SequenceFilterError("Could not open assembly input '" + file + "'.");
+            gzbuffer(in, 1u << 20);
+            size_t used = 0;
+            for (;;) {
+                if (buf->size() - used < (size_t(1) << 20)) buf->resize(std::max<size_t>(buf->size() * 2, size_t(4) << 20));
+                const int r = gzread(in, &(*buf)[used], static_cast<unsigned>(std::min<size_t>(buf->size() - used, size_t(1) << 30)));
+                if (r < 0) { gzclose(in); throw SequenceFilterError("Could not read assembly input '" + file + "'."); }
+                if (r == 0) break;
+                used += static_cast<size_t>(r);
+            }
+            gzclose(in);
+            buf->resize(used);
+            text = buf->data();
+            textSize = used;
+            mapping = buf;
         }
-        (void)::madvise(map, mapSize, MADV_SEQUENTIAL);
-        const char *data = static_cast<const char *>(map), *end = data + mapSize;
+        mapped = true;
+        const char *data = text, *end = data + textSize;
+        // strict: a UTF-8 byte order mark before the first line is not part of it
+        const char *first = data + (strict && textSize >= 3 && std::memcmp(data, "\xef\xbb\xbf", 3) == 0 ? 3 : 0);
         // record starts = '>' at a line start; found by slices of the text in parallel, then put in order
-        const size_t nslice = std::max<size_t>(1, std::min<size_t>(64, mapSize >> 24));
+        const size_t nslice = std::max<size_t>(1, std::min<size_t>(64, textSize >> 24));
         std::vector<std::vector<const char *>> found(nslice);
         detail::onThreads(nslice, [&](size_t k) {
-            const char *lo = data + mapSize / nslice * k, *hi = k + 1 == nslice ? end : data + mapSize / nslice * (k + 1);
+            const char *lo = data + textSize / nslice * k, *hi = k + 1 == nslice ? end : data + textSize / nslice * (k + 1);
             for (const char *p = lo; p < hi;) {
                 const char *gt = static_cast<const char *>(std::memchr(p, '>', static_cast<size_t>(hi - p)));
                 if (!gt) break;
-                if (gt == data || gt[-1] == '\n') found[k].push_back(gt);
+                if (gt == first || (gt > data && gt[-1] == '\n')) found[k].push_back(gt);
                 p = gt + 1;
             }
         });
@@ -1770,6 +1848,7 @@ public:
             const char *nl = static_cast<const char *>(std::memchr(gt, '\n', static_cast<size_t>(lim - gt)));
             spans.push_back(Span{gt + 1, nl ? nl + 1 : lim, lim});
         }
+        if (strict) checkStrict(data, first);
     }
     ~FastaGroupReader() {
         if (map && !mapping) ::munmap(map, mapSize);
@@ -1778,27 +1857,46 @@ public:
     FastaGroupReader(const FastaGroupReader &) = delete;
     FastaGroupReader &operator=(const FastaGroupReader &) = delete;
 
+    // the records' primary IDs (header up to the first whitespace), in input order: the names a SequenceSelector selects from
+    const std::vector<std::string> &primaryIds() {
+        if (ids.size() != records())
+            for (size_t i = ids.size(); i < records(); ++i) ids.push_back(mapped ? idOf(spans[i]) : sequenceFilterId(all[i].header));
+        return ids;
+    }
+    // keep[i] = record i goes on to the scan; before the first next()
+    void keep(std::vector<char> flags) {
+        if (flags.size() != records()) throw std::runtime_error("FastaGroupReader::keep: one flag per record expected");
+        if (nextSpan) throw std::runtime_error("FastaGroupReader::keep: records were read already");
+        kept = std::move(flags);
+        nKept = static_cast<uint64_t>(std::count_if(kept.begin(), kept.end(), [](char c) { return c != 0; }));
+    }
+    uint64_t inputRecords() const { return records(); }
+    uint64_t keptRecords() const { return kept.empty() ? records() : nKept; }
+    bool isStrict() const { return strict; }
+    // text pieces or joined lines (scanFastaToFiles decides once the library says what it takes); before the first next()
+    void setTextPieces(bool on) { textPieces = on; }
+
     // the next group (false at the end of the file)
     bool next(detail::FastaGroup &g) {
         g = detail::FastaGroup{};
+        // the group's records: the next kept ones, as many as fit in groupBytes (at least one)
+        const size_t n = records();
+        while (nextSpan < n && !isKept(nextSpan)) ++nextSpan;
+        if (nextSpan >= n) return false;
+        g.firstRecord = nextSpan;
+        size_t bytes = 0;
+        for (; nextSpan < n; ++nextSpan) {
+            if (!isKept(nextSpan)) continue;
+            const size_t b = mapped ? static_cast<size_t>(spans[nextSpan].stop - spans[nextSpan].body) : all[nextSpan].sequence.size();
+            if (!g.seqPos.empty() && bytes + b > groupBytes) break;
+            bytes += b;
+            g.seqPos.push_back(nextSpan);
+        }
         if (!mapped) {
-            if (nextSpan >= all.size()) return false;
-            g.firstRecord = nextSpan;
-            size_t bytes = 0;
-            while (nextSpan < all.size() && (g.owned.empty() || bytes + all[nextSpan].sequence.size() <= groupBytes)) {
-                bytes += all[nextSpan].sequence.size();
-                g.owned.push_back(std::move(all[nextSpan++]));
-            }
+            for (size_t i : g.seqPos) g.owned.push_back(std::move(all[i]));
             return true;
         }
-        if (nextSpan >= spans.size()) return false;
-        g.firstRecord = nextSpan;
-        size_t first = nextSpan, bytes = 0;
-        while (nextSpan < spans.size() && (nextSpan == first || bytes + static_cast<size_t>(spans[nextSpan].stop - spans[nextSpan].body) <= groupBytes)) {
-            bytes += static_cast<size_t>(spans[nextSpan].stop - spans[nextSpan].body);
-            ++nextSpan;
-        }
-        const size_t nrec = nextSpan - first;
+        const size_t nrec = g.seqPos.size();
         g.records.resize(nrec);
         // pieces of ~4 MB of text, cut at line starts; pass 1 counts every piece's bases, pass 2 copies them to
         // their place in the record's buffer
@@ -1806,9 +1904,9 @@ public:
         std::vector<Piece> pieces;
         const size_t kPiece = pieceBytes;
         for (size_t r = 0; r < nrec; ++r) {
-            const Span &sp = spans[first + r];
+            const Span &sp = spans[g.seqPos[r]];
             const char *he = sp.body > sp.head && sp.body[-1] == '\n' ? sp.body - 1 : sp.body;
-            g.records[r].header = detail::fastaHeaderWord(sp.head, he);
+            g.records[r].header = strict ? ids[g.seqPos[r]] : detail::fastaHeaderWord(sp.head, he);
             for (const char *a = sp.body; a < sp.stop;) {
                 const char *z = sp.stop - a > static_cast<ptrdiff_t>(kPiece) ? a + kPiece : sp.stop;
                 if (z < sp.stop) {
@@ -1871,13 +1969,17 @@ public:
     }
 };
 
-struct ScanFastaTimes { double read_ms = 0, scan_ms = 0, write_ms = 0, wall_ms = 0; uint64_t bases = 0, windows = 0; size_t groups = 0; };
+// library_bases: the bases of the segments handed to the library (N-runs are not; neither are records a filter dropped)
+struct ScanFastaTimes { double read_ms = 0, scan_ms = 0, write_ms = 0, wall_ms = 0; uint64_t bases = 0, windows = 0, library_bases = 0; size_t groups = 0; };
 
 // FASTA file -> the eleven output files + console path report; returns the totals for printSummary.
+// groupReader: a FastaGroupReader of fastaFile the caller made (and, with assembly record filters, selected from with keep())
+// before any output file exists or any device call is made; nullptr = one made here.  Its groupBytes / pieceBytes are its own.
 inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
                                         std::ostream &console, bool manualCuration = false,
                                         size_t groupBytes = size_t(256) << 20, ScanFastaTimes *times = nullptr,
-                                        size_t pieceBytes = size_t(4) << 20, int textPieces = -1) {
+                                        size_t pieceBytes = size_t(4) << 20, int textPieces = -1,
+                                        FastaGroupReader *groupReader = nullptr) {
     // textPieces: -1 = whenever the library takes text input for this parameter set (the tiled kernel's), 0 / 1 = forced
     using Clock = std::chrono::steady_clock;
     auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -1892,7 +1994,10 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
     std::thread reader([&] {
         try {
             const bool text = textPieces < 0 ? teloscope.takesTextPieces() : textPieces != 0;
-            FastaGroupReader rd(fastaFile, groupBytes, pieceBytes, text);
+            std::unique_ptr<FastaGroupReader> own;
+            if (groupReader) groupReader->setTextPieces(text);
+            else own.reset(new FastaGroupReader(fastaFile, groupBytes, pieceBytes, text));
+            FastaGroupReader &rd = groupReader ? *groupReader : *own;
             detail::FastaGroup g;
             for (;;) {
                 const auto t0 = Clock::now();
@@ -1923,8 +2028,11 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
                     views.push_back(r.pieces.empty() && r.size ? RecordView{&r.header, r.data.get(), r.size, nullptr, 0, nullptr}
                                                                : RecordView{&r.header, nullptr, r.size, r.pieces.data(), r.pieces.size(), r.lines.data()});
                 for (const FastaRecord &r : g.owned) views.push_back(RecordView{&r.header, r.sequence.data(), r.sequence.size(), nullptr, 0, nullptr});
+                if (!g.owned.empty()) g.comps = splitPaths(views);
+                for (const PathComponents &pc : g.comps)
+                    for (const auto &sg : pc.segments) T.library_bases += sg.second;
                 Scanned s;
-                s.paths = walkRecordViews(teloscope, views, g.firstRecord, g.owned.empty() ? &g.comps : nullptr);
+                s.paths = walkRecordViews(teloscope, views, g.firstRecord, &g.comps, g.seqPos.empty() ? nullptr : &g.seqPos);
                 s.group = std::move(g);                           // (-m: matchSeq was copied out of the bases already)
                 T.scan_ms += ms(t0, Clock::now());
                 if (trace) std::fprintf(stderr, "trace scan  %7.1f .. %7.1f\n", ms(t_begin, t0), ms(t_begin, Clock::now()));
@@ -1952,6 +2060,10 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
         }
         const auto tf = Clock::now();
         sum = writer.finish();
+        const UserInputTeloscope &ui = teloscope.input();          // (what the caller's selection set, as Input::read does)
+        sum.filterActive = ui.sequenceFilterActive;
+        sum.filterInputCount = ui.filterInputCount;
+        sum.filterSelectedCount = ui.filterSelectedCount;
         if (trace) std::fprintf(stderr, "trace finish %7.1f .. %7.1f\n", ms(t_begin, tf), ms(t_begin, Clock::now()));
     } catch (...) {
         writeError = std::current_exception();

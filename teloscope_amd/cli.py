@@ -4,9 +4,18 @@ UserInputTeloscope it yields.  bench.py and the parity tests describe their work
 Teloscope flag strings ("-c TTAGGG -w 1000 -s 500 -r -g ...") and turn them into the
 library's parameters here, so that both mean exactly what the reference's CLI means by them.
 """
+import os
 import shlex
 
 import numpy as np
+
+
+class SequenceFilterError(ValueError):
+    """An assembly record filter option the reference refuses (its "Error: <message>" text)."""
+
+
+_FILTER_OPTIONS = ("--include-bed", "--exclude-bed", "--include-prefix", "--exclude-prefix")
+
 
 class Options:
     """UserInputTeloscope as main() leaves it (include/input.h:15-64)."""
@@ -35,7 +44,14 @@ class Options:
         self.ultra_fast = True
         self.manual_curation = False
         self.fastq_subset = False
+        self.bam_subset = False
         self.stdin_redirect = None
+        # assembly record filters (include/input.h:21-27): any of the four options turns filtering on
+        self.include_bed_files = []
+        self.exclude_bed_files = []
+        self.include_prefixes = []
+        self.exclude_prefixes = []
+        self.sequence_filter_active = False
 
     def params(self):
         """fields shared by tso_params / ts_params"""
@@ -52,14 +68,56 @@ def _revcom(s):
     return s.translate(str.maketrans("ACGTacgt", "TGCAtgca"))[::-1]
 
 
+def _add_bed_filter_file(o, path, files, option):
+    """--include-bed / --exclude-bed (src/main.cpp:103-124): an existing regular file, kept resolved"""
+    if not path or not os.path.exists(path):
+        raise SequenceFilterError("%s file does not exist: '%s'." % (option, path))
+    if not os.path.isfile(path):
+        raise SequenceFilterError("%s file '%s' is not a regular file." % (option, path))
+    files.append(os.path.realpath(path))
+    o.sequence_filter_active = True
+
+
+def _add_prefix_filters(o, value, prefixes, option):
+    """--include-prefix / --exclude-prefix (src/main.cpp:126-147): comma-separated, trimmed, none empty"""
+    tokens = [t.strip(" \t\r\n") for t in value.split(",")]
+    if not value or any(not t for t in tokens):
+        raise SequenceFilterError("%s contains an empty prefix." % option)
+    prefixes.extend(tokens)
+    o.sequence_filter_active = True
+
+
+def _filter_option(o, option, value):
+    if option == "--include-bed":
+        _add_bed_filter_file(o, value, o.include_bed_files, option)
+    elif option == "--exclude-bed":
+        _add_bed_filter_file(o, value, o.exclude_bed_files, option)
+    elif option == "--include-prefix":
+        _add_prefix_filters(o, value, o.include_prefixes, option)
+    else:
+        _add_prefix_filters(o, value, o.exclude_prefixes, option)
+
+
 def parse_cli(command):
-    """getopt_long loop of src/main.cpp:186-565 for the options used by the manifests."""
+    """getopt_long loop of src/main.cpp:186-565 for the options used by the manifests, and the assembly record filters.
+    A filter option the reference refuses raises SequenceFilterError with the reference's message."""
     o = Options()
     toks = shlex.split(command.replace("<", " < "))
     i = 0
     needs_arg = {"-f", "-o", "-j", "-p", "-s", "-w", "-c", "-t", "-k", "-d", "-l", "-y", "-x"}
     while i < len(toks):
         t = toks[i]
+        if t in _FILTER_OPTIONS or t.split("=", 1)[0] in _FILTER_OPTIONS:
+            if "=" in t:
+                t, value = t.split("=", 1)
+                i += 1
+            elif i + 1 < len(toks):
+                value = toks[i + 1]
+                i += 2
+            else:
+                raise SequenceFilterError("Option %s is missing a required argument" % t)
+            _filter_option(o, t, value)
+            continue
         if t == "<":
             o.stdin_redirect = toks[i + 1]
             i += 2
@@ -100,6 +158,8 @@ def parse_cli(command):
         i += 1
         if t == "--fastq-subset":
             o.fastq_subset = True
+        elif t == "--bam-subset":
+            o.bam_subset = True
         elif t in ("-r", "-g", "-e", "-m", "-i", "-a"):
             o.ultra_fast = False
             if t == "-r":
@@ -123,6 +183,9 @@ def parse_cli(command):
             pass                                   # --cmd, --verbose ...
         elif o.input is None:
             o.input = t                            # first positional
+    if o.sequence_filter_active and (o.fastq_subset or o.bam_subset):      # src/main.cpp:596-600
+        raise SequenceFilterError("--include-bed/--exclude-bed/--include-prefix/--exclude-prefix filter assembly records "
+                                  "and cannot be used in read subset mode.")
     if o.raw_patterns is None or not o.raw_patterns:
         o.raw_patterns = [o.canonical_fwd, o.canonical_rev]   # src/main.cpp:626-633
     return o
