@@ -592,6 +592,89 @@ void         ts_exchange_destroy(ts_exchange *x);
 int          ts_exchange_gather(ts_exchange *x, int dst, const void *d_msg, uint64_t my_bytes, void *const *d_recv,
                                 const uint64_t *msg_bytes, void *stream);
 
+/* ---- BGZF members inflated and checksummed on the device (a wave per member): what the reference's BgzfReader::loadBlock
+ *      does with zlib on one host thread, a member per call (src/bgzf.cpp:57-196: inflate(Z_FINISH), total_out == ISIZE,
+ *      crc32 against the footer).  The caller locates the members (gzip header, BC subfield, footer: host work that reads no
+ *      payload byte) and hands over the compressed bytes and one descriptor per member; only compressed bytes cross PCIe on
+ *      the way in.  A member is accepted exactly when zlib accepts it there: the final deflate block ends in the payload's
+ *      last byte, exactly isize bytes come out, and their CRC32 is crc.  Members without output (isize == 0: the EOF marker,
+ *      legal in mid-stream) are checked like any other. */
+typedef struct ts_bgzf_block {
+    uint64_t src_off;            /* the deflate payload's first byte in `compressed` */
+    uint32_t payload_len;        /* <= 65536 */
+    uint32_t isize;              /* uncompressed size from the footer, <= 65536 */
+    uint32_t crc;                /* CRC32 from the footer */
+    uint32_t reserved;
+    uint64_t dst_off;            /* where the member's bytes go in the output */
+} ts_bgzf_block;
+#define TS_BGZF_OK          0
+#define TS_BGZF_BAD_DEFLATE 1    /* "invalid BGZF deflate payload" */
+#define TS_BGZF_BAD_CRC     2    /* "BGZF checksum mismatch" */
+typedef struct ts_bgzf_status {
+    int32_t  code;               /* TS_BGZF_OK, or what is wrong with the LOWEST member that is not ok */
+    uint32_t reserved;
+    uint64_t block;              /* that member's index; n_blocks when all are ok */
+} ts_bgzf_status;
+/* Host in, host out.  compressed[0, n) holds the payloads, blocks[0, n_blocks) describe them (any order of dst_off; outputs
+ * must not overlap), plain_out[0, plain_cap) receives the members' bytes; bytes of plain_out that no ok member covers are
+ * zero.  Descriptors are checked on the host before anything is launched (src_off + payload_len <= n, payload_len and
+ * isize <= 65536, dst_off + isize <= plain_cap, no overlap): TS_ERR_INVALID_ARG.  A damaged member is not an error of the
+ * call: TS_OK, and *first_bad says which member and why; the other members' bytes are right all the same. */
+int ts_bgzf_inflate(ts_ctx *ctx, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
+                    void *plain_out, uint64_t plain_cap, ts_bgzf_status *first_bad);
+
+/* ---- the resident form, which the BAM route runs on (include/teloscope_mi355x_io.hpp: bamSubsetDevice): a chunk of a BAM's
+ *      uncompressed stream that exists in HBM only.  Replaces, for --bam-subset, BgzfReader::loadBlock (src/bgzf.cpp:57-196)
+ *      and the record loop of subsetBam with decodeSequence (src/bam.cpp:122-259): members are inflated and checksummed,
+ *      records walked and validated, SEQ decoded from 4-bit codes into a read batch's input buffer and passing records
+ *      gathered, all on the device; the record table and the passing records' bytes are what comes back. */
+typedef struct ts_bam_chunk ts_bam_chunk;
+typedef struct ts_bam_record {
+    uint64_t off;                /* of the record's block_size field in the chunk */
+    uint32_t block_size;
+    uint32_t seq_at;             /* SEQ's first byte, relative to off */
+    uint32_t l_seq;
+    uint32_t reserved;
+} ts_bam_record;
+/* error of ts_bam_chunk_walk: the first record that is not valid, in the host route's order of checks */
+#define TS_BAM_OK             0
+#define TS_BAM_BAD_BLOCK_SIZE 1  /* "invalid BAM record block_size": not in 32 .. 256 MiB */
+#define TS_BAM_BAD_LENGTHS    2  /* "invalid BAM record lengths": l_read_name == 0 or l_seq > 0x7fffffff */
+#define TS_BAM_FIELDS_EXCEED  3  /* "BAM record fields exceed block_size" */
+#define TS_BAM_NAME_NOT_NUL   4  /* "BAM read name is not NUL-terminated" */
+/* Room for compressed_cap compressed and plain_cap uncompressed bytes on the context's device; NULL on failure. */
+ts_bam_chunk *ts_bam_chunk_create(ts_ctx *ctx, uint64_t compressed_cap, uint64_t plain_cap);
+void ts_bam_chunk_destroy(ts_bam_chunk *chunk);
+/* The chunk's next contents: the tail [carry_from, size) of what it holds moves to its front (device to device: the head of a
+ * record that continues), then the members are inflated behind it — blocks[i].dst_off counts from the chunk's first byte
+ * and must not lie inside the carried tail.  Descriptors are checked as by ts_bgzf_inflate.  The kernel runs on `stream`;
+ * the caller's buffers are free when the call returns. */
+int ts_bam_chunk_inflate(ts_bam_chunk *chunk, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
+                         uint64_t carry_from, void *stream);
+/* Waits for the device; the lowest member of the last inflate that is not ok (ts_bgzf_status as above). */
+int ts_bam_chunk_status(ts_bam_chunk *chunk, ts_bgzf_status *first_bad);
+/* Bytes the chunk holds. */
+uint64_t ts_bam_chunk_size(const ts_bam_chunk *chunk);
+/* chunk[off, off + n) to host memory (the BAM header, which the host parses; tests).  Waits for the device. */
+int ts_bam_chunk_read(ts_bam_chunk *chunk, uint64_t off, uint64_t n, void *host);
+/* Walks records from `from`: up to cap table entries to recs (host memory), *n of them; *next = the offset of the first
+ * record that was not taken (it does not end inside the chunk: the carry; or the table was full); *error != TS_BAM_OK when
+ * the walk stopped at a record that is not valid, at *error_off.  Waits for the device. */
+int ts_bam_chunk_walk(ts_bam_chunk *chunk, uint64_t from, ts_bam_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
+                      int *error, uint64_t *error_off);
+/* SEQ of recs[i] (l_seq > 0 each) as ASCII bases (=ACMGRSVTWYHKDBN) into segment i of `reads`: an unrestricted tips-only batch
+ * of n segments of l_seq bases made by ts_batch_create on the chunk's context.  The judgement is then the existing
+ * ts_batch_scan + ts_batch_read_pass (+ ts_batch_read_pass_status).  Asynchronous on `stream`. */
+int ts_bam_chunk_decode(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, ts_batch *reads, void *stream);
+/* n bytes of device memory that belong to the chunk (valid until the next call of this function or ts_bam_chunk_destroy):
+ * a place for ts_batch_read_pass to write to for callers that do not allocate device memory themselves.  NULL on failure. */
+void *ts_bam_chunk_pass_buffer(ts_bam_chunk *chunk, uint64_t n);
+/* The records whose pass byte (d_pass[i], device memory, as ts_batch_read_pass writes it) is set, whole (block_size field
+ * included), in input order, to host_out; *bytes and *n_passed say how much.  When *bytes > cap nothing is copied and the
+ * call answers TS_ERR_INVALID_ARG (call again with room for *bytes).  Ordered on `stream`; waits for it. */
+int ts_bam_chunk_gather(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, const void *d_pass, void *host_out,
+                        uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

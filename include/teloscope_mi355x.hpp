@@ -482,6 +482,9 @@ public:
     }
 
     size_t deviceCount() const { return raw.size(); }
+    // the i-th device's context: what a caller needs to judge reads that already are on that device (ts_batch_create on it,
+    // ts_batch_scan + ts_batch_read_pass: bamSubsetDevice)
+    ts_ctx *context(size_t i = 0) const { return raw.at(i); }
 
     std::vector<bool> matchesBatch(const std::vector<std::string> &sequences) {
         std::vector<const char *> ptr(sequences.size());

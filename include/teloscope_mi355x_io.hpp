@@ -1301,6 +1301,210 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
     return stats;
 }
 
+// The device route of --bam-subset (same arguments, statistics, exceptions and output bytes as bamSubset, which stays the
+// default): the compressed BGZF members cross PCIe and the uncompressed BAM stream exists in HBM only.  Per chunk of
+// ~bytesPerBatch uncompressed bytes: the members are located on the host (parseBgzfBlock reads no payload byte), inflated and
+// checksummed on the device (ts_bam_chunk_inflate), the records walked and validated there (ts_bam_chunk_walk: the table
+// comes back), SEQ decoded into a tips-only batch's input buffer (ts_bam_chunk_decode), judged by the scan and the predicate
+// the host route uses (ts_batch_scan + ts_batch_read_pass), and the passing records' bytes gathered (ts_bam_chunk_gather).
+// The BAM header is parsed on the host from the chunk's leading bytes.  Runs on the filter's first context.
+// What a maintainer of the reference would call from runBamSubsetMode (src/bam.cpp:262-316) in place of subsetBam.
+inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
+    BamSubsetStats stats;
+    ts_ctx *ctx = filter.context(0);
+    auto fail = [&](const char *what) -> std::runtime_error {
+        const char *why = ts_last_error(ctx);
+        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
+    };
+    int fd = 0;
+    if (inFile != "-") {
+        fd = ::open(inFile.c_str(), O_RDONLY);
+        if (fd < 0) throw std::runtime_error("cannot open BAM input '" + inFile + "'");
+    }
+    struct Closer { int fd; ~Closer() { if (fd > 0) ::close(fd); } } closer{fd};
+    // the compressed input: a regular file is mapped, a pipe is read to its end
+    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
+    std::vector<unsigned char> piped;
+    const unsigned char *data = nullptr;
+    size_t size = 0;
+    {
+        struct stat st;
+        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
+        }
+        if (mapping.p) { data = static_cast<const unsigned char *>(mapping.p); size = mapping.n; }
+        else {
+            for (;;) {
+                const size_t at = piped.size();
+                piped.resize(at + (8u << 20));
+                const ssize_t r = ::read(fd, piped.data() + at, 8u << 20);
+                if (r < 0) throw std::runtime_error("cannot read BAM input");
+                piped.resize(at + static_cast<size_t>(r));
+                if (r == 0) break;
+            }
+            data = piped.data(); size = piped.size();
+        }
+    }
+    auto le32 = [](const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); };
+    using Clock = std::chrono::steady_clock;
+    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    double msInflate = 0, msWalk = 0, msDecode = 0, msFilter = 0, msGather = 0, msWrite = 0;
+
+    // a chunk holds the unconsumed tail of the one before (at most a record: 4 bytes + 256 MiB) and the new members' output
+    const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 1u << 20);
+    const uint64_t maxCarry = (256ull << 20) + 4, plainCap = maxCarry + chunkBytes, compCap = chunkBytes + (1u << 20);
+    struct ChunkPtr { ts_bam_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, compCap, plainCap)};
+    if (!chunk.p) throw fail("cannot make the device chunk");
+    detail::BgzfWriter writer(out);
+
+    constexpr uint32_t kMaxHeaderText = 1u << 30, kMaxReferenceName = 1u << 20;
+    enum { Magic, Text, Refs, Records } phase = Magic;
+    uint32_t ltext = 0, nref = 0, refsDone = 0;
+    uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
+    std::vector<unsigned char> head;            // host copy of the chunk's leading bytes (header phase only)
+    auto have = [&](uint64_t n) {               // n more bytes from pos on, and on the host
+        if (held - pos < n) return false;
+        if (head.size() < pos + n) {
+            const uint64_t from = head.size(), to = std::min<uint64_t>(held, std::max<uint64_t>(pos + n, from + (1u << 20)));
+            head.resize(static_cast<size_t>(to));
+            if (ts_bam_chunk_read(chunk.p, from, to - from, head.data() + from) != TS_OK) throw fail("cannot read the BAM header from the device");
+        }
+        return true;
+    };
+    auto parseHeader = [&]() -> bool {           // as in bamSubset
+        for (;;) {
+            if (phase == Magic) {
+                if (!have(8)) return false;
+                if (std::memcmp(head.data() + pos, "BAM\1", 4) != 0) throw std::runtime_error("input is not a BAM file");
+                ltext = le32(head.data() + pos + 4);
+                if (ltext > kMaxHeaderText) throw std::runtime_error("invalid BAM header text length");
+                phase = Text;
+            } else if (phase == Text) {
+                if (!have(8 + static_cast<uint64_t>(ltext) + 4)) return false;
+                nref = le32(head.data() + pos + 8 + ltext);
+                if (nref > 0x7fffffffu) throw std::runtime_error("invalid BAM reference count");
+                writer.write(head.data() + pos, 8 + static_cast<size_t>(ltext) + 4);
+                pos += 8 + static_cast<uint64_t>(ltext) + 4;
+                phase = Refs;
+            } else if (phase == Refs) {
+                if (refsDone == nref) { phase = Records; return true; }
+                if (!have(4)) return false;
+                const uint32_t lname = le32(head.data() + pos);
+                if (lname == 0 || lname > kMaxReferenceName) throw std::runtime_error("invalid BAM reference name length");
+                if (!have(4 + static_cast<uint64_t>(lname) + 4)) return false;
+                if (head[pos + 4 + lname - 1] != 0) throw std::runtime_error("BAM reference name is not NUL-terminated");
+                if (le32(head.data() + pos + 4 + lname) > 0x7fffffffu) throw std::runtime_error("invalid BAM reference length");
+                writer.write(head.data() + pos, 4 + static_cast<size_t>(lname) + 4);
+                pos += 4 + static_cast<uint64_t>(lname) + 4;
+                ++refsDone;
+            } else {
+                return true;
+            }
+        }
+    };
+
+    std::vector<ts_bgzf_block> descs;
+    std::vector<ts_bam_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), withSeq;
+    std::vector<uint64_t> lens;
+    std::vector<unsigned char> kept;
+    auto judge = [&](const ts_bam_record *r, size_t n) {      // one sub-batch of records, in input order
+        withSeq.clear(); lens.clear();
+        for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { withSeq.push_back(r[i]); lens.push_back(r[i].l_seq); }
+        stats.totalRecords += n;
+        stats.missingSequenceRecords += n - withSeq.size();
+        if (withSeq.empty()) return;
+        struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
+        if (!batch.p) throw fail("cannot plan the read batch");
+        Clock::time_point t0 = Clock::now();
+        if (ts_bam_chunk_decode(chunk.p, withSeq.data(), withSeq.size(), batch.p, nullptr) != TS_OK) throw fail("SEQ decode failed");
+        void *dPass = ts_bam_chunk_pass_buffer(chunk.p, withSeq.size());
+        if (!dPass) throw fail("cannot allocate the pass bytes");
+        msDecode += since(t0); t0 = Clock::now();
+        if (ts_batch_scan(batch.p, nullptr, nullptr) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK) throw fail("read filter failed");
+        int overflowed = 0;
+        if (ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK) throw fail("read filter failed");
+        if (overflowed) {                                       // regrow + rescan, then judge again (include/teloscan.h)
+            if (ts_batch_sync(batch.p) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK ||
+                ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed) throw fail("read filter failed");
+        }
+        msFilter += since(t0); t0 = Clock::now();
+        uint64_t bytes = 0, nPassed = 0;
+        if (kept.size() < (1u << 20)) kept.resize(1u << 20);
+        int rc = ts_bam_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
+        if (rc == TS_ERR_INVALID_ARG && bytes > kept.size()) {
+            kept.resize(static_cast<size_t>(bytes));
+            rc = ts_bam_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
+        }
+        if (rc != TS_OK) throw fail("gather of the passing records failed");
+        msGather += since(t0); t0 = Clock::now();
+        writer.write(kept.data(), static_cast<size_t>(bytes));
+        stats.passedRecords += nPassed;
+        msWrite += since(t0);
+    };
+
+    size_t at = 0;
+    bool more = true, sawEofMarker = false;
+    while (more) {
+        const uint64_t carry = held - pos;
+        descs.clear();
+        size_t used = 0;
+        uint64_t produced = 0;
+        while (at + used < size) {                              // the members of this chunk (BgzfParallelReader::next's rule)
+            detail::BgzfBlockRef ref{};
+            bool eofm = false;
+            const size_t total = detail::parseBgzfBlock(data + at + used, size - at - used, ref, eofm);
+            if (total == 0) throw std::runtime_error(size - at - used < 12 ? "truncated BGZF header" : "truncated BGZF block");
+            if (produced + ref.isize > chunkBytes || used + total > compCap) break;
+            sawEofMarker = sawEofMarker || eofm;
+            ts_bgzf_block d{};
+            d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
+            d.dst_off = carry + produced;
+            descs.push_back(d);
+            produced += ref.isize;
+            used += total;
+        }
+        if (carry + produced > plainCap) throw std::runtime_error("BAM header is too large for the device route");
+        Clock::time_point t0 = Clock::now();
+        if (ts_bam_chunk_inflate(chunk.p, data + at, used, descs.data(), descs.size(), pos, nullptr) != TS_OK) throw fail("BGZF inflate failed");
+        ts_bgzf_status bad{};
+        if (ts_bam_chunk_status(chunk.p, &bad) != TS_OK) throw fail("BGZF inflate failed");
+        msInflate += since(t0);
+        if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
+        if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
+        at += used;
+        more = used > 0 && at < size;
+        held = carry + produced; pos = 0;
+        head.clear();
+        if (phase == Records || parseHeader()) {
+            head.clear(); head.shrink_to_fit();
+            for (;;) {
+                uint64_t n = 0, next = 0, errorOff = 0;
+                int error = 0;
+                t0 = Clock::now();
+                if (ts_bam_chunk_walk(chunk.p, pos, recs.data(), recs.size(), &n, &next, &error, &errorOff) != TS_OK) throw fail("record walk failed");
+                msWalk += since(t0);
+                if (error == TS_BAM_BAD_BLOCK_SIZE) throw std::runtime_error("invalid BAM record block_size");
+                if (error == TS_BAM_BAD_LENGTHS) throw std::runtime_error("invalid BAM record lengths");
+                if (error == TS_BAM_FIELDS_EXCEED) throw std::runtime_error("BAM record fields exceed block_size");
+                if (error != TS_BAM_OK) throw std::runtime_error("BAM read name is not NUL-terminated");
+                for (size_t a = 0; a < n; a += readsPerBatch) judge(recs.data() + a, std::min<size_t>(readsPerBatch, static_cast<size_t>(n) - a));
+                pos = next;
+                if (n < recs.size()) break;                     // (a full table: more records may follow in this chunk)
+            }
+        }
+    }
+    if (phase != Records) throw std::runtime_error(phase == Refs ? "truncated BAM reference" : "truncated BAM header");
+    if (held != pos) throw std::runtime_error(held - pos < 4 ? "truncated BAM record size" : "truncated BAM record");
+    stats.missingEofBlock = !sawEofMarker;
+    writer.finish();
+    if (std::getenv("TS_TIMING"))
+        std::fprintf(stderr, "bamSubsetDevice: upload + inflate + CRC %.0f ms, walk %.0f ms, decode %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
+                     msInflate, msWalk, msDecode, msFilter, msGather, msWrite);
+    return stats;
+}
+
 inline const char *scaffoldTypeToString(ScaffoldType t) {       // src/tools.cpp
     static const char *names[] = {"t2t", "gapped_t2t", "misassembly", "gapped_misassembly", "incomplete",
                                   "gapped_incomplete", "none", "gapped_none", "discordant", "gapped_discordant"};

@@ -163,6 +163,22 @@ class ShardStatus(C.Structure):
                 ("scale_factor_needed", C.c_uint32), ("msg_bytes", C.c_uint64)]
 
 
+class BgzfBlock(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("payload_len", C.c_uint32), ("isize", C.c_uint32), ("crc", C.c_uint32),
+                ("reserved", C.c_uint32), ("dst_off", C.c_uint64)]
+
+
+class BgzfStatus(C.Structure):
+    _fields_ = [("code", C.c_int32), ("reserved", C.c_uint32), ("block", C.c_uint64)]
+
+
+class BamRecord(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("block_size", C.c_uint32), ("seq_at", C.c_uint32), ("l_seq", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+BGZF_OK, BGZF_BAD_DEFLATE, BGZF_BAD_CRC = 0, 1, 2
+BAM_OK, BAM_BAD_BLOCK_SIZE, BAM_BAD_LENGTHS, BAM_FIELDS_EXCEED, BAM_NAME_NOT_NUL = 0, 1, 2, 3, 4
 SHARD_RETRY_SYNC, SHARD_RETRY_GROW, SHARD_NEED_FULL = 1, 2, 3
 SHARD_OVERFLOW_VISIBLE, SHARD_OVERFLOW_BLOCKS, SHARD_OVERFLOW_SCAN, SHARD_OUT_OF_CONTEXT = 1, 2, 4, 8
 DEVICE_NONE = -2            # TS_DEVICE_NONE: planning-only context
@@ -187,7 +203,8 @@ SYMBOLS = [
     "ts_shard_peek", "ts_shards_finalize", "ts_scan_segments_multi", "ts_batch_read_pass_status", "ts_pack_bases",
     "ts_batch_set_emit", "ts_exchange_unique_id", "ts_exchange_last_error", "ts_exchange_create", "ts_exchange_destroy",
     "ts_exchange_gather", "ts_box_probe", "ts_batch_bind_shard_message", "ts_refresh_env", "ts_streams_concurrent", "ts_batch_wait_scan", "ts_batch_set_timing", "ts_batch_set_record_bits",
-    "ts_terminal_ends",
+    "ts_terminal_ends", "ts_bgzf_inflate", "ts_bam_chunk_create", "ts_bam_chunk_destroy", "ts_bam_chunk_inflate",
+    "ts_bam_chunk_status", "ts_bam_chunk_size", "ts_bam_chunk_read", "ts_bam_chunk_walk", "ts_bam_chunk_decode", "ts_bam_chunk_gather", "ts_bam_chunk_pass_buffer",
 ]
 
 
@@ -333,6 +350,24 @@ def lib():
     L.ts_exchange_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.ts_exchange_destroy.argtypes = [C.c_void_p]
     L.ts_exchange_gather.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BgzfBlock), C.c_size_t, C.c_void_p, C.c_uint64,
+                                  C.POINTER(BgzfStatus)]
+    L.ts_bam_chunk_create.restype = C.c_void_p
+    L.ts_bam_chunk_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+    L.ts_bam_chunk_destroy.argtypes = [C.c_void_p]
+    L.ts_bam_chunk_destroy.restype = None
+    L.ts_bam_chunk_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BgzfBlock), C.c_size_t, C.c_uint64, C.c_void_p]
+    L.ts_bam_chunk_status.argtypes = [C.c_void_p, C.POINTER(BgzfStatus)]
+    L.ts_bam_chunk_size.restype = C.c_uint64
+    L.ts_bam_chunk_size.argtypes = [C.c_void_p]
+    L.ts_bam_chunk_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.ts_bam_chunk_walk.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BamRecord), C.c_uint64, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+    L.ts_bam_chunk_decode.argtypes = [C.c_void_p, C.POINTER(BamRecord), C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ts_bam_chunk_pass_buffer.restype = C.c_void_p
+    L.ts_bam_chunk_pass_buffer.argtypes = [C.c_void_p, C.c_uint64]
+    L.ts_bam_chunk_gather.argtypes = [C.c_void_p, C.POINTER(BamRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     _lib = L
     return L
 

@@ -1,0 +1,33 @@
+"""BGZF members inflated on the device (ts_bgzf_inflate of include/teloscan.h): the caller locates the members, the GPU
+decodes and checksums them, a wave per member.  There is no host decoder behind this."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi as K
+
+BLOCK_DT = np.dtype(K.BgzfBlock)
+
+
+def inflate_blocks(ctx, data, blocks, plain_cap=None):
+    """data: the compressed bytes; blocks: (src_off, payload_len, isize, crc, dst_off) per member, or an array of BLOCK_DT;
+    ctx: a context pointer (Teloscope._ctx.ptr).  -> (plain bytes of plain_cap, (code, block)): code is BGZF_OK, or what is
+    wrong with the lowest member that is not ok, and block is its index (len(blocks) when all are ok)."""
+    if isinstance(blocks, np.ndarray) and blocks.dtype == BLOCK_DT:
+        arr = np.ascontiguousarray(blocks)
+    else:
+        arr = np.zeros(len(blocks), dtype=BLOCK_DT)
+        for i, (src_off, payload_len, isize, crc, dst_off) in enumerate(blocks):
+            arr[i] = (src_off, payload_len, isize, crc, 0, dst_off)
+    if plain_cap is None:
+        plain_cap = int((arr["dst_off"] + arr["isize"]).max()) if len(arr) else 0
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(max(1, plain_cap), dtype=np.uint8)
+    status = K.BgzfStatus()
+    rc = K.lib().ts_bgzf_inflate(ctx, src.ctypes.data if len(src) else None, len(src),
+                                 arr.ctypes.data_as(C.POINTER(K.BgzfBlock)) if len(arr) else None, len(arr),
+                                 out.ctypes.data if plain_cap else None, plain_cap, C.byref(status))
+    if rc != K.TS_OK:
+        msg = K.lib().ts_last_error(ctx)
+        raise K.TeloscanError(rc, msg.decode() if msg else "ts_bgzf_inflate failed")
+    return out[:plain_cap].tobytes(), (int(status.code), int(status.block))

@@ -1,0 +1,286 @@
+// bgzf.cpp — host side of the device BGZF route (include/teloscan.h: ts_bgzf_inflate): descriptor checks, staging, the
+// verdict.  Nothing here inflates: the members are decoded by bgzf.hip's kernel or not at all.
+#include "capi_internal.hpp"
+
+#include <numeric>
+
+namespace {
+
+// src_off + payload_len <= n, sizes <= 64 KB, dst_off + isize <= plain_cap, outputs disjoint
+bool descriptors_ok(const ts_bgzf_block *blocks, size_t n_blocks, uint64_t n, uint64_t plain_cap, std::string &why,
+                    uint64_t dst_floor = 0) {
+    for (size_t i = 0; i < n_blocks; ++i) {
+        const ts_bgzf_block &b = blocks[i];
+        if (b.dst_off < dst_floor) { why = "block " + std::to_string(i) + ": output inside the carried bytes"; return false; }
+        if (b.payload_len > 65536u || b.isize > 65536u) { why = "block " + std::to_string(i) + ": payload_len or isize above 65536"; return false; }
+        if (b.src_off > n || b.payload_len > n - b.src_off) { why = "block " + std::to_string(i) + ": payload outside the compressed bytes"; return false; }
+        if (b.dst_off > plain_cap || b.isize > plain_cap - b.dst_off) { why = "block " + std::to_string(i) + ": output outside plain_out"; return false; }
+    }
+    std::vector<uint32_t> order;
+    for (size_t i = 0; i < n_blocks; ++i) if (blocks[i].isize) order.push_back((uint32_t)i);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return blocks[a].dst_off < blocks[b].dst_off; });
+    for (size_t k = 1; k < order.size(); ++k) {
+        const ts_bgzf_block &a = blocks[order[k - 1]], &b = blocks[order[k]];
+        if (a.dst_off + a.isize > b.dst_off) { why = "blocks " + std::to_string(order[k - 1]) + " and " + std::to_string(order[k]) + ": outputs overlap"; return false; }
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int ts_bgzf_inflate(ts_ctx *ctx, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
+                               void *plain_out, uint64_t plain_cap, ts_bgzf_status *first_bad) {
+    if (!ctx) return TS_ERR_INVALID_ARG;
+    if (!first_bad || (n && !compressed) || (n_blocks && !blocks) || (plain_cap && !plain_out))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bgzf_inflate: null argument");
+    if (n_blocks > 0xffffffffull || n > (1ull << 40) || plain_cap > (1ull << 40))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bgzf_inflate: too large for one call");
+    std::string why;
+    if (!descriptors_ok(blocks, n_blocks, n, plain_cap, why)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bgzf_inflate: " + why);
+    DEVICE_TRY(ctx);
+    first_bad->code = TS_BGZF_OK; first_bad->reserved = 0; first_bad->block = n_blocks;
+    if (n_blocks == 0) { if (plain_cap) memset(plain_out, 0, (size_t)plain_cap); return TS_OK; }
+
+    // the buffers go back to the context's pool on every return path
+    struct Lease {
+        ts_ctx *c; DevBuf b;
+        explicit Lease(ts_ctx *c_) : c(c_) {}
+        ~Lease() { if (b.p) c->pool.give(std::move(b)); }
+    } d_comp(ctx), d_blocks(ctx), d_plain(ctx), d_result(ctx);
+    HIP_TRY(ctx, ctx->pool.take((size_t)n + 16, d_comp.b));                     // (the kernel reads whole aligned dwords)
+    HIP_TRY(ctx, ctx->pool.take(n_blocks * sizeof(ts_bgzf_block), d_blocks.b));
+    HIP_TRY(ctx, ctx->pool.take((size_t)plain_cap + 16, d_plain.b));
+    HIP_TRY(ctx, ctx->pool.take(n_blocks * 4, d_result.b));
+    if (n) HIP_TRY(ctx, hipMemcpy(d_comp.b.p, compressed, (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset((char *)d_comp.b.p + n, 0, 16));
+    HIP_TRY(ctx, hipMemcpy(d_blocks.b.p, blocks, n_blocks * sizeof(ts_bgzf_block), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset(d_plain.b.p, 0, (size_t)plain_cap + 16));
+    HIP_TRY(ctx, hipMemset(d_result.b.p, 0xff, n_blocks * 4));
+    if (ts_k_launch_bgzf_inflate(d_comp.b.p, d_blocks.b.p, (uint32_t)n_blocks, d_plain.b.p, (uint32_t *)d_result.b.p, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_bgzf_inflate: kernel launch failed");
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    std::vector<uint32_t> result(n_blocks);
+    HIP_TRY(ctx, hipMemcpy(result.data(), d_result.b.p, n_blocks * 4, hipMemcpyDeviceToHost));
+    if (plain_cap) HIP_TRY(ctx, hipMemcpy(plain_out, d_plain.b.p, (size_t)plain_cap, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_blocks; ++i) {
+        if (result[i] > TS_BGZF_BAD_CRC) return ctx->fail(TS_ERR_STATE, "ts_bgzf_inflate: block " + std::to_string(i) + " was not judged");
+        if (result[i] != TS_BGZF_OK && first_bad->code == TS_BGZF_OK) { first_bad->code = (int32_t)result[i]; first_bad->block = i; }
+    }
+    // (a member that is not ok may have written some of its bytes: they are not its output)
+    for (size_t i = 0; i < n_blocks; ++i)
+        if (result[i] != TS_BGZF_OK && blocks[i].isize) memset((char *)plain_out + blocks[i].dst_off, 0, blocks[i].isize);
+    return TS_OK;
+}
+
+// ===================================================================== the resident form: a chunk of a BAM on the device
+struct ts_bam_chunk {
+    ts_ctx *ctx = nullptr;
+    uint64_t comp_cap = 0, plain_cap = 0;
+    uint64_t plain_n = 0;               // bytes the chunk holds: the carried tail, then the members' output
+    size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status
+    DevBuf d_comp, d_plain, d_blocks, d_result, d_tmp, d_recs, d_out, d_jobs, d_dst, d_gather, d_pass;
+};
+
+namespace {
+hipError_t grow(DevBuf &b, size_t need) { return b.ensure(need); }
+struct DecodeJobHost { uint64_t src, dst; uint32_t n, pad; };
+constexpr uint32_t kDecodePiece = 2048;
+
+// a record of the table against the chunk: inside it, SEQ inside the record
+bool record_ok(const ts_bam_chunk *ch, const ts_bam_record &r) {
+    if (r.block_size < 32u || r.block_size > (256u << 20)) return false;
+    if (r.off > ch->plain_n || 4ull + r.block_size > ch->plain_n - r.off) return false;
+    if (r.l_seq > 0x7fffffffu) return false;
+    return (uint64_t)r.seq_at + ((uint64_t)r.l_seq + 1) / 2 <= 4ull + r.block_size;
+}
+}  // namespace
+
+extern "C" {
+
+ts_bam_chunk *ts_bam_chunk_create(ts_ctx *ctx, uint64_t compressed_cap, uint64_t plain_cap) {
+    if (!ctx) return nullptr;
+    if (compressed_cap == 0 || plain_cap == 0 || compressed_cap > (1ull << 40) || plain_cap > (1ull << 40)) {
+        ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_create: capacities out of range");
+        return nullptr;
+    }
+    if (ctx->device == kNoDevice) { ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it"); return nullptr; }
+    DeviceGuard guard(ctx->device);
+    if (guard.error() != hipSuccess) { ctx->fail(TS_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.error())); return nullptr; }
+    ts_bam_chunk *ch = new ts_bam_chunk();
+    ch->ctx = ctx; ch->comp_cap = compressed_cap; ch->plain_cap = plain_cap;
+    // (the kernels read whole aligned words: 64 readable bytes behind both buffers)
+    if (ch->d_comp.ensure((size_t)compressed_cap + 64) != hipSuccess || ch->d_plain.ensure((size_t)plain_cap + 64) != hipSuccess ||
+        ch->d_out.ensure(64) != hipSuccess || hipMemset((char *)ch->d_plain.p + plain_cap, 0, 64) != hipSuccess) {
+        ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_create: device allocation failed");
+        delete ch;
+        return nullptr;
+    }
+    return ch;
+}
+
+void ts_bam_chunk_destroy(ts_bam_chunk *ch) {
+    if (!ch) return;
+    DeviceGuard guard(ch->ctx->device);
+    (void)hipDeviceSynchronize();
+    delete ch;
+}
+
+int ts_bam_chunk_inflate(ts_bam_chunk *ch, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
+                         uint64_t carry_from, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if ((n && !compressed) || (n_blocks && !blocks) || n > ch->comp_cap || n_blocks > 0xffffffffull || carry_from > ch->plain_n)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_inflate: null or out-of-range argument");
+    const uint64_t carry = ch->plain_n - carry_from;
+    std::string why;
+    if (!descriptors_ok(blocks, n_blocks, n, ch->plain_cap, why, carry)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_inflate: " + why);
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (carry && carry_from) {                                   // the tail moves to the front (through a buffer where the two overlap)
+        char *p = (char *)ch->d_plain.p;
+        if (carry_from >= carry) HIP_TRY(ctx, hipMemcpyAsync(p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
+        else {
+            HIP_TRY(ctx, grow(ch->d_tmp, (size_t)carry));
+            HIP_TRY(ctx, hipMemcpyAsync(ch->d_tmp.p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(p, ch->d_tmp.p, (size_t)carry, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    uint64_t end = carry;
+    for (size_t i = 0; i < n_blocks; ++i) end = std::max<uint64_t>(end, blocks[i].dst_off + blocks[i].isize);
+    ch->plain_n = end;
+    ch->n_blocks = n_blocks;
+    if (n_blocks) {
+        HIP_TRY(ctx, grow(ch->d_blocks, n_blocks * sizeof(ts_bgzf_block)));
+        HIP_TRY(ctx, grow(ch->d_result, n_blocks * 4));
+        if (n) HIP_TRY(ctx, hipMemcpyAsync(ch->d_comp.p, compressed, (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync((char *)ch->d_comp.p + n, 0, 16, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ch->d_blocks.p, blocks, n_blocks * sizeof(ts_bgzf_block), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync(ch->d_result.p, 0xff, n_blocks * 4, st));
+        // (the descriptors are the caller's memory: they have left it when this returns)
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ts_k_launch_bgzf_inflate(ch->d_comp.p, ch->d_blocks.p, (uint32_t)n_blocks, ch->d_plain.p, (uint32_t *)ch->d_result.p, stream) != 0)
+            return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_inflate: kernel launch failed");
+    }
+    return TS_OK;
+}
+
+int ts_bam_chunk_status(ts_bam_chunk *ch, ts_bgzf_status *first_bad) {
+    if (!ch || !first_bad) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    DEVICE_TRY(ctx);
+    first_bad->code = TS_BGZF_OK; first_bad->reserved = 0; first_bad->block = ch->n_blocks;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (!ch->n_blocks) return TS_OK;
+    std::vector<uint32_t> result(ch->n_blocks);
+    HIP_TRY(ctx, hipMemcpy(result.data(), ch->d_result.p, ch->n_blocks * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ch->n_blocks; ++i) {
+        if (result[i] > TS_BGZF_BAD_CRC) return ctx->fail(TS_ERR_STATE, "ts_bam_chunk_status: block " + std::to_string(i) + " was not judged");
+        if (result[i] != TS_BGZF_OK) { first_bad->code = (int32_t)result[i]; first_bad->block = i; break; }
+    }
+    return TS_OK;
+}
+
+uint64_t ts_bam_chunk_size(const ts_bam_chunk *ch) { return ch ? ch->plain_n : 0; }
+
+int ts_bam_chunk_read(ts_bam_chunk *ch, uint64_t off, uint64_t n, void *host) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if ((n && !host) || off > ch->plain_n || n > ch->plain_n - off) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_read: outside the chunk");
+    DEVICE_TRY(ctx);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (n) HIP_TRY(ctx, hipMemcpy(host, (const char *)ch->d_plain.p + off, (size_t)n, hipMemcpyDeviceToHost));
+    return TS_OK;
+}
+
+int ts_bam_chunk_walk(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
+                      int *error, uint64_t *error_off) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!n || !next || !error || !error_off || (cap && !recs) || from > ch->plain_n || cap > (1ull << 31))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_walk: null or out-of-range argument");
+    DEVICE_TRY(ctx);
+    HIP_TRY(ctx, grow(ch->d_recs, (size_t)std::max<uint64_t>(cap, 1) * sizeof(ts_bam_record)));
+    if (ts_k_launch_bam_walk(ch->d_plain.p, ch->plain_n, from, cap, ch->d_recs.p, ch->d_out.p, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_walk: kernel launch failed");
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    unsigned long long out[4];
+    HIP_TRY(ctx, hipMemcpy(out, ch->d_out.p, sizeof out, hipMemcpyDeviceToHost));
+    if (out[0] > cap || out[1] > ch->plain_n) return ctx->fail(TS_ERR_STATE, "ts_bam_chunk_walk: the walk left the chunk");
+    if (out[0]) HIP_TRY(ctx, hipMemcpy(recs, ch->d_recs.p, (size_t)out[0] * sizeof(ts_bam_record), hipMemcpyDeviceToHost));
+    *n = out[0]; *next = out[1]; *error = (int)out[2]; *error_off = out[3];
+    return TS_OK;
+}
+
+int ts_bam_chunk_decode(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, ts_batch *reads, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!reads || (n && !recs) || reads->ctx != ctx || !reads->tips || !reads->whole() || reads->segs.size() != n)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: needs an unrestricted tips-only batch of this context with one segment per record");
+    std::vector<DecodeJobHost> jobs;
+    for (size_t i = 0; i < n; ++i) {
+        const ts_bam_record &r = recs[i];
+        if (!record_ok(ch, r) || r.l_seq == 0 || reads->segs[i].len != r.l_seq)
+            return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: record " + std::to_string(i) + " does not fit the chunk or its segment");
+        const uint64_t dst = ts_batch_segment_offset(reads, i);
+        for (uint32_t a = 0; a < r.l_seq; a += kDecodePiece)
+            jobs.push_back(DecodeJobHost{r.off + r.seq_at + a / 2, dst + a, std::min(kDecodePiece, r.l_seq - a), 0});
+    }
+    if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: too many bases for one call");
+    DEVICE_TRY(ctx);
+    void *in = ts_batch_input_ptr(reads);
+    if (!in) return ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_decode: no input buffer");
+    if (jobs.empty()) return TS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, grow(ch->d_jobs, jobs.size() * sizeof(DecodeJobHost)));
+    HIP_TRY(ctx, hipMemcpyAsync(ch->d_jobs.p, jobs.data(), jobs.size() * sizeof(DecodeJobHost), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (ts_k_launch_bam_decode(ch->d_plain.p, ch->d_jobs.p, (uint32_t)jobs.size(), in, stream) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_decode: kernel launch failed");
+    return TS_OK;
+}
+
+void *ts_bam_chunk_pass_buffer(ts_bam_chunk *ch, uint64_t n) {
+    if (!ch || n > (1ull << 40)) return nullptr;
+    ts_ctx *ctx = ch->ctx;
+    DeviceGuard guard(ctx->device);
+    if (guard.error() != hipSuccess || hipDeviceSynchronize() != hipSuccess || grow(ch->d_pass, (size_t)n) != hipSuccess) {
+        ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_pass_buffer: device allocation failed");
+        return nullptr;
+    }
+    return ch->d_pass.p;
+}
+
+int ts_bam_chunk_gather(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, const void *d_pass, void *host_out, uint64_t cap,
+                        uint64_t *bytes, uint64_t *n_passed, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!bytes || !n_passed || (n && (!recs || !d_pass)) || (cap && !host_out) || n > 0x7fffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather: null or out-of-range argument");
+    for (size_t i = 0; i < n; ++i)
+        if (!record_ok(ch, recs[i])) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather: record " + std::to_string(i) + " does not fit the chunk");
+    *bytes = 0; *n_passed = 0;
+    if (n == 0) return TS_OK;
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, grow(ch->d_recs, n * sizeof(ts_bam_record)));
+    HIP_TRY(ctx, grow(ch->d_dst, n * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(ch->d_recs.p, recs, n * sizeof(ts_bam_record), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    unsigned long long *totals = (unsigned long long *)ch->d_out.p + 4;
+    if (ts_k_launch_bam_gather_plan(ch->d_recs.p, d_pass, n, ch->d_dst.p, totals, stream) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_gather: kernel launch failed");
+    unsigned long long t[2];
+    HIP_TRY(ctx, hipMemcpyAsync(t, totals, sizeof t, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *bytes = t[0]; *n_passed = t[1];
+    if (t[0] > cap) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather: host_out is too small (*bytes says what is needed)");
+    if (t[0] == 0) return TS_OK;
+    HIP_TRY(ctx, grow(ch->d_gather, (size_t)t[0]));
+    if (ts_k_launch_bam_gather(ch->d_plain.p, ch->d_recs.p, ch->d_dst.p, n, t[0], ch->d_gather.p, stream) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_gather: kernel launch failed");
+    HIP_TRY(ctx, hipMemcpyAsync(host_out, ch->d_gather.p, (size_t)t[0], hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return TS_OK;
+}
+
+}  // extern "C"

@@ -405,6 +405,19 @@ int  ts_k_launch_widen_u16(const uint16_t *src, uint32_t *dst, unsigned long lon
 int  ts_k_launch_compact(const uint32_t *regions, const uint32_t *wave_fill,
                          const unsigned long long *wave_dense_base, uint32_t region_cap,
                          uint32_t nwaves, uint32_t *dense, int rec16, void *stream);
+// bgzf.hip: a wave per BGZF member (blocks: ts_bgzf_block descriptors in device memory, checked by the caller; compressed:
+// 4-byte aligned with 4 readable bytes behind the last payload); result[i] = TS_BGZF_OK / _BAD_DEFLATE / _BAD_CRC
+int  ts_k_launch_bgzf_inflate(const void *compressed, const void *blocks, uint32_t n_blocks, void *plain, uint32_t *result,
+                              void *stream);
+// ... the record walk over an inflated chunk (one wave; out4 = {records, next offset, error code, error offset}; plain is
+// readable 16 bytes beyond plain_n), SEQ -> ASCII (jobs: {src, dst, n, pad} of 24 bytes, a wave each, dst 16-byte aligned,
+// n <= 2048), and the gather of passing records
+int  ts_k_launch_bam_walk(const void *plain, unsigned long long plain_n, unsigned long long from, unsigned long long cap,
+                          void *recs, void *out4, void *stream);
+int  ts_k_launch_bam_decode(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream);
+int  ts_k_launch_bam_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream);
+int  ts_k_launch_bam_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
+                            void *out, void *stream);
 }
 #endif
 
