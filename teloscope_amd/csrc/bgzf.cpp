@@ -227,10 +227,13 @@ int ts_bam_chunk_decode(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, t
     }
     if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: too many bases for one call");
     DEVICE_TRY(ctx);
+    const bool fresh = reads->d_in.p == nullptr;
     void *in = ts_batch_input_ptr(reads);
     if (!in) return ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_decode: no input buffer");
     if (jobs.empty()) return TS_OK;
     hipStream_t st = (hipStream_t)stream;
+    // (a fresh input buffer was just zeroed on the null stream, which a non-blocking `stream` does not wait for)
+    if (fresh && st) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
     HIP_TRY(ctx, grow(ch->d_jobs, jobs.size() * sizeof(DecodeJobHost)));
     HIP_TRY(ctx, hipMemcpyAsync(ch->d_jobs.p, jobs.data(), jobs.size() * sizeof(DecodeJobHost), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -1,6 +1,8 @@
 """The device route of --bam-subset (bamSubsetDevice: BGZF members inflated, records walked, SEQ decoded and passing records
 gathered on the GPU) through tests/cpp/bam_device_cli.cpp: every scenario of tests/test_bam_subset.py with --device, asserting
-what those tests assert and that stdout is byte-equal to the --host run of the same binary on the same file."""
+what those tests assert and that stdout is byte-equal to the --host run of the same binary on the same file.  The stages
+behind the inflate (record walk, SEQ decode, carry, gather) are compared one by one with plain references in
+tests/test_gpu_bam_chunk.py."""
 import os
 import random
 import struct
