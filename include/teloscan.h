@@ -675,6 +675,59 @@ void *ts_bam_chunk_pass_buffer(ts_bam_chunk *chunk, uint64_t n);
 int ts_bam_chunk_gather(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, const void *d_pass, void *host_out,
                         uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
 
+/* ---- FASTQ text in the same resident chunk (include/teloscope_mi355x_io.hpp: fastqSubsetDevice): replaces, for
+ *      --fastq-subset, the line reader and record check of readFastqRecord (src/input.cpp:96-149) and the read / filter /
+ *      echo loop of Input::readFastqSubset (src/input.cpp:737-832).  The text reaches the chunk as plain bytes
+ *      (ts_chunk_upload) or as BGZF members (ts_bam_chunk_inflate); lines are indexed, records framed and validated,
+ *      sequences staged into a read batch's input buffer and passing records gathered on the device.  The chunk object, its
+ *      carry and its inflate are ts_bam_chunk's: ts_chunk is another name for it, and ts_bam_chunk_create / _destroy /
+ *      _inflate / _status / _size / _read / _pass_buffer serve it as they are. */
+typedef struct ts_bam_chunk ts_chunk;
+typedef struct ts_fastq_record {
+    uint64_t off;                /* of the header line's first byte in the chunk */
+    uint32_t seq_at;             /* the sequence line's first byte, relative to off */
+    uint32_t seq_len;            /* bytes of the sequence line without its '\n' (a trailing '\r' included: the filter strips it,
+                                    as it does for the host route, src/input.cpp:113-138) */
+    uint32_t size;               /* from off to the end of the quality line, without its '\n' */
+    uint32_t seq_cr;             /* 1 when the sequence line ends in '\r': the filter judges seq_len - seq_cr bases
+                                    (ReadTelomereFilter::matches drops it, src/read-filter.cpp:38-40) */
+} ts_fastq_record;
+/* error of ts_fastq_chunk_walk: what is wrong with the LOWEST record that is not valid, in the order readFastqRecord checks
+ * (src/input.cpp:113-138) */
+#define TS_FASTQ_OK            0
+#define TS_FASTQ_TRUNCATED     1  /* "truncated FASTQ record": the input ended with fewer than four lines */
+#define TS_FASTQ_BAD_HEADER    2  /* "expected header line starting with '@'" */
+#define TS_FASTQ_BAD_SEPARATOR 3  /* "expected separator line starting with '+'" */
+#define TS_FASTQ_BAD_LENGTHS   4  /* "sequence and quality length differ" */
+/* Room for at least plain_cap uncompressed bytes: the chunk grows (what it holds is kept) — a record larger than the chunk it
+ * was made for (std::getline, src/input.cpp:116-123, reads a line of any length).  Waits for the device. */
+int ts_chunk_reserve(ts_chunk *chunk, uint64_t plain_cap);
+/* The chunk's next contents, plain: the tail [carry_from, size) moves to the front as for ts_bam_chunk_inflate, then
+ * bytes[0, n) (host memory) go behind it; the chunk grows when they do not fit.  What the reference's getline calls read
+ * from the stream it opened (src/input.cpp:116-123, :739), a block at a time.  Ordered on `stream`; the caller's bytes are free
+ * when the call returns. */
+int ts_chunk_upload(ts_chunk *chunk, const void *bytes, uint64_t n, uint64_t carry_from, void *stream);
+/* Lines and records of the whole chunk (at most 4 GiB - 1 bytes), which starts at a record boundary: readFastqRecord's rule
+ * (src/input.cpp:113-138: blank lines in front of a header are skipped, then four lines whatever they hold) as a prefix
+ * scan over the lines.  *n = whole records in the chunk, the first min(*n, cap) of them to recs (host memory); when
+ * *n > cap the call answers TS_ERR_INVALID_ARG (call again with room for *n).  *next = the first byte that was not consumed:
+ * the header of the record that does not end inside the chunk, or of the unfinished line behind the last record (the
+ * carry); with at_end != 0 the input ends with the chunk, its last line may lack the '\n', and *next = size.  *error !=
+ * TS_FASTQ_OK: record *error_record (counted from the chunk's first, the *n records before it are valid and in the table)
+ * at *error_off is not valid.  Waits for the device. */
+int ts_fastq_chunk_walk(ts_chunk *chunk, int at_end, ts_fastq_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
+                        int *error, uint64_t *error_record, uint64_t *error_off);
+/* The bases of recs[i] (seq_len - seq_cr > 0 each) into segment i of `reads`: an unrestricted tips-only batch of n segments
+ * of seq_len - seq_cr bases made by ts_batch_create on the chunk's context; bytes behind a read stay zero.  What the reference hands
+ * to ReadTelomereFilter::matches per record (src/input.cpp:786).  The judgement is then ts_batch_scan + ts_batch_read_pass
+ * (+ ts_batch_read_pass_status).  Asynchronous on `stream`. */
+int ts_fastq_chunk_stage(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, ts_batch *reads, void *stream);
+/* The records whose pass byte (d_pass[i], device memory) is set, their four lines as they are and a '\n' behind each
+ * (appendFastqRecord, src/input.cpp:140-149, written at :798-801), in input order, to host_out; *bytes, *n_passed and cap as for
+ * ts_bam_chunk_gather.  Ordered on `stream`; waits for it. */
+int ts_fastq_chunk_gather(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, const void *d_pass, void *host_out,
+                          uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

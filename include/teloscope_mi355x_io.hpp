@@ -1505,6 +1505,228 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     return stats;
 }
 
+// The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as
+// fastqSubset, which stays the default): the FASTQ text exists in HBM one chunk of ~bytesPerBatch bytes at a time and the host
+// reads none of it.  The text gets there from one of three sources —
+//   1. a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
+//   2. a BGZF regular file (bgzip output): the members are located on the host (parseBgzfBlock reads no payload byte) and
+//      inflated and checksummed on the device (ts_bam_chunk_inflate, as bamSubsetDevice does); from the first member that does
+//      not parse as BGZF on, the rest of the input takes source 3;
+//   3. anything else (plain gzip, stdin, a FIFO, a file that cannot be mapped): through zlib or read(2) in blocks, as
+//      fastqSubset's `fill` reads them, each block uploaded —
+// and behind the source the stages are the same: lines indexed and records framed and validated (ts_fastq_chunk_walk: the table
+// comes back), sequences staged into a tips-only batch's input buffer (ts_fastq_chunk_stage), judged by the scan and the
+// predicate the host route uses (ts_batch_scan + ts_batch_read_pass), and the passing records' bytes gathered
+// (ts_fastq_chunk_gather).  The bytes behind the last whole record stay in the chunk for the next fill; a record larger than a
+// chunk makes the chunk grow.  Runs on the filter's first context.
+// What a maintainer of the reference would call from Input::readFastqSubset (src/input.cpp:737-832) in place of its loop.
+inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                           size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
+    FastqSubsetResult res;
+    ts_ctx *ctx = filter.context(0);
+    auto fail = [&](const char *what) -> std::runtime_error {
+        const char *why = ts_last_error(ctx);
+        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
+    };
+    int fd = 0;
+    if (inFile != "-") {
+        fd = ::open(inFile.c_str(), O_RDONLY);
+        if (fd < 0) throw std::runtime_error("Stream not successful: " + inFile);
+    }
+    struct Closer { int fd; gzFile gz = nullptr; ~Closer() { if (gz) gzclose(gz); else if (fd > 0) ::close(fd); } } closer{fd};
+    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
+    {
+        struct stat st;
+        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
+        }
+    }
+    const unsigned char *data = static_cast<const unsigned char *>(mapping.p);
+    const size_t size = mapping.n;
+    // the BGZF member at p (its total size), or 0: what is there does not parse as a whole BGZF member
+    auto bgzfMember = [](const unsigned char *p, size_t n, detail::BgzfBlockRef &ref, bool &eofm) -> size_t {
+        try { return detail::parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
+    };
+    enum { Plain, Bgzf, Stream } source = Stream;
+    if (data) {
+        detail::BgzfBlockRef ref{};
+        bool eofm = false;
+        if (size >= 2 && data[0] == 0x1f && data[1] == 0x8b) source = bgzfMember(data, size, ref, eofm) ? Bgzf : Stream;
+        else source = Plain;
+    }
+    // source 3 reads the descriptor from `from` on, through zlib where gzip starts there (stdin always, as fastqSubset does).
+    // Behind BGZF members (from > 0) anything that is not gzip ends the input: zlib ignores what trails a gzip stream.
+    const bool deviceInflate = source == Bgzf;
+    bool streamOpen = false, streamDone = false;
+    auto openStream = [&](size_t from) {
+        streamOpen = true;
+        bool gz = fd == 0;
+        if (from > 0) {
+            if (size - from < 2 || data[from] != 0x1f || data[from + 1] != 0x8b) { streamDone = true; return; }
+            if (::lseek(fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error("read error in FASTQ input");
+            gz = true;
+        } else if (!gz) {
+            unsigned char magic[2] = {0, 0};
+            gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+        }
+        if (gz) {
+            closer.gz = gzdopen(fd, "rb");
+            if (!closer.gz) throw std::runtime_error("Stream not successful: " + inFile);
+            gzbuffer(closer.gz, 1u << 20);
+        }
+    };
+    auto get = [&](char *dst, size_t n) -> long {
+        if (closer.gz) return gzread(closer.gz, dst, static_cast<unsigned>(std::min<size_t>(n, 1u << 30)));
+        return static_cast<long>(::read(fd, dst, std::min<size_t>(n, 1u << 30)));
+    };
+    using Clock = std::chrono::steady_clock;
+    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    double msUpload = 0, msIndex = 0, msStage = 0, msFilter = 0, msGather = 0, msWrite = 0;
+
+    const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 64);
+    const uint64_t compCap = source == Bgzf ? chunkBytes + (1u << 20) : 64;
+    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, compCap, chunkBytes)};
+    if (!chunk.p) throw fail("cannot make the device chunk");
+
+    std::vector<ts_fastq_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16)), withSeq;
+    std::vector<uint64_t> lens;
+    std::vector<unsigned char> kept;
+    std::vector<char> block;
+    std::vector<ts_bgzf_block> descs;
+    auto judge = [&](const ts_fastq_record *r, size_t n) {      // one sub-batch of records, in input order
+        withSeq.clear(); lens.clear();
+        for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { withSeq.push_back(r[i]); lens.push_back(r[i].seq_len - r[i].seq_cr); }
+        res.total += n;
+        if (withSeq.empty()) return;                            // (a read without bases is never kept)
+        struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
+        if (!batch.p) throw fail("cannot plan the read batch");
+        Clock::time_point t0 = Clock::now();
+        if (ts_fastq_chunk_stage(chunk.p, withSeq.data(), withSeq.size(), batch.p, nullptr) != TS_OK) throw fail("staging the sequences failed");
+        void *dPass = ts_bam_chunk_pass_buffer(chunk.p, withSeq.size());
+        if (!dPass) throw fail("cannot allocate the pass bytes");
+        msStage += since(t0); t0 = Clock::now();
+        if (ts_batch_scan(batch.p, nullptr, nullptr) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK) throw fail("read filter failed");
+        int overflowed = 0;
+        if (ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK) throw fail("read filter failed");
+        if (overflowed) {                                       // regrow + rescan, then judge again (include/teloscan.h)
+            if (ts_batch_sync(batch.p) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK ||
+                ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed) throw fail("read filter failed");
+        }
+        msFilter += since(t0); t0 = Clock::now();
+        uint64_t bytes = 0, nPassed = 0;
+        if (kept.size() < (1u << 20)) kept.resize(1u << 20);
+        int rc = ts_fastq_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
+        if (rc == TS_ERR_INVALID_ARG && bytes > kept.size()) {
+            kept.resize(static_cast<size_t>(bytes));
+            rc = ts_fastq_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
+        }
+        if (rc != TS_OK) throw fail("gather of the passing records failed");
+        msGather += since(t0); t0 = Clock::now();
+        out.write(reinterpret_cast<const char *>(kept.data()), static_cast<std::streamsize>(bytes));
+        if (!out.good()) throw std::runtime_error("failed while writing FASTQ subset");
+        res.kept += nPassed;
+        msWrite += since(t0);
+    };
+
+    size_t at = 0;                              // next byte of the mapped file (sources 1 and 2)
+    uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
+    bool first = true, atEnd = false;
+    while (!atEnd) {
+        const uint64_t carry = held - pos;
+        // a chunk that held no whole record (a record larger than it) takes as much again
+        const size_t want = static_cast<size_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0));
+        Clock::time_point t0 = Clock::now();
+        if (source == Bgzf) {
+            // members until the chunk has `want` new bytes (BgzfParallelReader::next's rule), in as many inflate calls as the
+            // compressed buffer asks for: the first drops the consumed bytes, the later ones keep what is there
+            uint64_t produced = 0, from = pos;
+            bool foreign = false, full = false;
+            do {
+                descs.clear();
+                size_t used = 0;
+                uint64_t made = 0;
+                while (at + used < size) {
+                    detail::BgzfBlockRef ref{};
+                    bool eofm = false;
+                    const size_t total = bgzfMember(data + at + used, size - at - used, ref, eofm);
+                    if (total == 0) { foreign = true; break; }
+                    if (produced + made > 0 && produced + made + ref.isize > want) { full = true; break; }
+                    if (!descs.empty() && used + total > compCap) break;
+                    ts_bgzf_block d{};
+                    d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
+                    d.dst_off = carry + produced + made;
+                    descs.push_back(d);
+                    made += ref.isize;
+                    used += total;
+                }
+                if (ts_chunk_reserve(chunk.p, carry + produced + made) != TS_OK) throw fail("cannot grow the device chunk");
+                if (ts_bam_chunk_inflate(chunk.p, data + at, used, descs.data(), descs.size(), from, nullptr) != TS_OK) throw fail("BGZF inflate failed");
+                ts_bgzf_status bad{};
+                if (ts_bam_chunk_status(chunk.p, &bad) != TS_OK) throw fail("BGZF inflate failed");
+                if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
+                if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
+                at += used;
+                produced += made;
+                from = 0;
+            } while (!foreign && !full && at < size);
+            if (foreign) { source = Stream; openStream(at); atEnd = streamDone; }
+            else atEnd = at >= size;
+        } else if (source == Plain) {
+            const size_t n = std::min(want, size - at);
+            if (ts_chunk_upload(chunk.p, data + at, n, pos, nullptr) != TS_OK) throw fail("upload of the FASTQ text failed");
+            at += n;
+            atEnd = at >= size;
+        } else {
+            if (!streamOpen) openStream(0);
+            if (block.size() < want) block.resize(want);
+            size_t got = 0;
+            while (!streamDone && got < want) {
+                const long n = get(block.data() + got, want - got);
+                if (n < 0) throw std::runtime_error("read error in FASTQ input");
+                if (n == 0) { streamDone = true; break; }
+                got += static_cast<size_t>(n);
+            }
+            if (ts_chunk_upload(chunk.p, block.data(), got, pos, nullptr) != TS_OK) throw fail("upload of the FASTQ text failed");
+            atEnd = streamDone;
+        }
+        msUpload += since(t0);
+        held = ts_bam_chunk_size(chunk.p); pos = 0;
+        if (first) {
+            if (held == 0) {
+                if (atEnd) throw std::runtime_error("FASTQ input is empty");
+                continue;
+            }
+            unsigned char c = 0;
+            if (ts_bam_chunk_read(chunk.p, 0, 1, &c) != TS_OK) throw fail("cannot read the chunk");
+            if (c != '@') throw std::runtime_error("FASTQ input must start with '@'");
+            first = false;
+        }
+        uint64_t n = 0, next = 0, errorRecord = 0, errorOff = 0;
+        int error = TS_FASTQ_OK;
+        t0 = Clock::now();
+        int rc = ts_fastq_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, &error, &errorRecord, &errorOff);
+        if (rc == TS_ERR_INVALID_ARG && n > recs.size()) {
+            recs.resize(static_cast<size_t>(n));
+            rc = ts_fastq_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, &error, &errorRecord, &errorOff);
+        }
+        if (rc != TS_OK) throw fail("FASTQ walk failed");
+        msIndex += since(t0);
+        for (size_t a = 0; a < n; a += readsPerBatch) judge(recs.data() + a, std::min<size_t>(readsPerBatch, static_cast<size_t>(n) - a));
+        if (error != TS_FASTQ_OK) {
+            const char *msg = error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
+                            : error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
+            throw std::runtime_error("FASTQ record " + std::to_string(res.total + 1) + ": " + msg);
+        }
+        pos = next;
+    }
+    out.flush();
+    if (std::getenv("TS_TIMING"))
+        std::fprintf(stderr, "fastqSubsetDevice: upload%s %.0f ms, index %.0f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
+                     deviceInflate ? " + inflate + CRC" : "", msUpload, msIndex, msStage, msFilter, msGather, msWrite);
+    return res;
+}
+
 inline const char *scaffoldTypeToString(ScaffoldType t) {       // src/tools.cpp
     static const char *names[] = {"t2t", "gapped_t2t", "misassembly", "gapped_misassembly", "incomplete",
                                   "gapped_incomplete", "none", "gapped_none", "discordant", "gapped_discordant"};

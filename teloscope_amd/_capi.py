@@ -177,7 +177,13 @@ class BamRecord(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class FastqRecord(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("seq_at", C.c_uint32), ("seq_len", C.c_uint32), ("size", C.c_uint32),
+                ("seq_cr", C.c_uint32)]
+
+
 BGZF_OK, BGZF_BAD_DEFLATE, BGZF_BAD_CRC = 0, 1, 2
+FASTQ_OK, FASTQ_TRUNCATED, FASTQ_BAD_HEADER, FASTQ_BAD_SEPARATOR, FASTQ_BAD_LENGTHS = 0, 1, 2, 3, 4
 BAM_OK, BAM_BAD_BLOCK_SIZE, BAM_BAD_LENGTHS, BAM_FIELDS_EXCEED, BAM_NAME_NOT_NUL = 0, 1, 2, 3, 4
 SHARD_RETRY_SYNC, SHARD_RETRY_GROW, SHARD_NEED_FULL = 1, 2, 3
 SHARD_OVERFLOW_VISIBLE, SHARD_OVERFLOW_BLOCKS, SHARD_OVERFLOW_SCAN, SHARD_OUT_OF_CONTEXT = 1, 2, 4, 8
@@ -205,6 +211,7 @@ SYMBOLS = [
     "ts_exchange_gather", "ts_box_probe", "ts_batch_bind_shard_message", "ts_refresh_env", "ts_streams_concurrent", "ts_batch_wait_scan", "ts_batch_set_timing", "ts_batch_set_record_bits",
     "ts_terminal_ends", "ts_bgzf_inflate", "ts_bam_chunk_create", "ts_bam_chunk_destroy", "ts_bam_chunk_inflate",
     "ts_bam_chunk_status", "ts_bam_chunk_size", "ts_bam_chunk_read", "ts_bam_chunk_walk", "ts_bam_chunk_decode", "ts_bam_chunk_gather", "ts_bam_chunk_pass_buffer",
+    "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
 ]
 
 
@@ -368,6 +375,13 @@ def lib():
     L.ts_bam_chunk_pass_buffer.argtypes = [C.c_void_p, C.c_uint64]
     L.ts_bam_chunk_gather.argtypes = [C.c_void_p, C.POINTER(BamRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_chunk_reserve.argtypes = [C.c_void_p, C.c_uint64]
+    L.ts_chunk_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.ts_fastq_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.POINTER(FastqRecord), C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ts_fastq_chunk_stage.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ts_fastq_chunk_gather.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     _lib = L
     return L
 

@@ -73,13 +73,22 @@ extern "C" int ts_bgzf_inflate(ts_ctx *ctx, const void *compressed, uint64_t n, 
 }
 
 // ===================================================================== the resident form: a chunk of a BAM on the device
-struct ts_bam_chunk {
-    ts_ctx *ctx = nullptr;
-    uint64_t comp_cap = 0, plain_cap = 0;
-    uint64_t plain_n = 0;               // bytes the chunk holds: the carried tail, then the members' output
-    size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status
-    DevBuf d_comp, d_plain, d_blocks, d_result, d_tmp, d_recs, d_out, d_jobs, d_dst, d_gather, d_pass;
-};
+// (struct ts_bam_chunk: capi_internal.hpp)
+int ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry_out) {
+    ts_ctx *ctx = ch->ctx;
+    const uint64_t carry = ch->plain_n - carry_from;
+    *carry_out = carry;
+    if (carry && carry_from) {                                   // the tail moves to the front (through a buffer where the two overlap)
+        char *p = (char *)ch->d_plain.p;
+        if (carry_from >= carry) HIP_TRY(ctx, hipMemcpyAsync(p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
+        else {
+            HIP_TRY(ctx, ch->d_tmp.ensure((size_t)carry));
+            HIP_TRY(ctx, hipMemcpyAsync(ch->d_tmp.p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(p, ch->d_tmp.p, (size_t)carry, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    return TS_OK;
+}
 
 namespace {
 hipError_t grow(DevBuf &b, size_t need) { return b.ensure(need); }
@@ -136,15 +145,7 @@ int ts_bam_chunk_inflate(ts_bam_chunk *ch, const void *compressed, uint64_t n, c
     if (!descriptors_ok(blocks, n_blocks, n, ch->plain_cap, why, carry)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_inflate: " + why);
     DEVICE_TRY(ctx);
     hipStream_t st = (hipStream_t)stream;
-    if (carry && carry_from) {                                   // the tail moves to the front (through a buffer where the two overlap)
-        char *p = (char *)ch->d_plain.p;
-        if (carry_from >= carry) HIP_TRY(ctx, hipMemcpyAsync(p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
-        else {
-            HIP_TRY(ctx, grow(ch->d_tmp, (size_t)carry));
-            HIP_TRY(ctx, hipMemcpyAsync(ch->d_tmp.p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(p, ch->d_tmp.p, (size_t)carry, hipMemcpyDeviceToDevice, st));
-        }
-    }
+    { uint64_t moved = 0; const int rc = ts_chunk_carry(ch, carry_from, st, &moved); if (rc != TS_OK) return rc; }
     uint64_t end = carry;
     for (size_t i = 0; i < n_blocks; ++i) end = std::max<uint64_t>(end, blocks[i].dst_off + blocks[i].isize);
     ch->plain_n = end;

@@ -370,4 +370,16 @@ ts_fetched *ts_batch_fetch(ts_batch *b, bool with_matches, int slot, int *rc_out
 int  ts_batch_finalize(ts_batch *b, ts_fetched *f, ts_segment_out *out);             // host post-processing; frees f
     // the batch's own input buffer, not zero-filled (every byte read is uploaded)
 
+// bgzf.cpp: a chunk of an uncompressed stream resident on the device (ts_bam_chunk_*; ts_chunk is the same type: fastq.cpp)
+struct ts_bam_chunk {
+    ts_ctx *ctx = nullptr;
+    uint64_t comp_cap = 0, plain_cap = 0;
+    uint64_t plain_n = 0;               // bytes the chunk holds: the carried tail, then the members' output
+    size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status
+    DevBuf d_comp, d_plain, d_blocks, d_result, d_tmp, d_recs, d_out, d_jobs, d_dst, d_gather, d_pass;
+    DevBuf d_lines, d_waves, d_frames;  // the FASTQ walk's line index, per-slice newline counts and framing results (fastq.cpp)
+};
+// the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
+int  ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry);
+
 #endif

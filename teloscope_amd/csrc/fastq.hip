@@ -1,0 +1,345 @@
+// fastq.hip — FASTQ text of a resident chunk (bgzf.cpp's ts_bam_chunk) turned into a record table, a read batch's input and
+// the passing records' bytes, on the device.  One-wave workgroups throughout, like bgzf.hip's.
+//
+//   * line index: a wave per 16 KB of the chunk, 16 bytes per lane per step.  A first pass counts '\n' per slice, one wave
+//     sums the counts, a second pass writes every line's start in order (a prefix sum of the lanes' counts places them),
+//     its first byte and whether a '\r' stands in front of its '\n'.
+//   * record framing: readFastqRecord's rule is an automaton over lines with four states (0 expect header: a blank line
+//     stays, any other line goes to 1; 1, 2, 3 = sequence, separator, quality: one line each, whatever it holds).  A line
+//     is a map of the four states, a byte of four 2-bit fields, and maps compose: a prefix scan of the maps — within the
+//     wave by six shuffle steps, across waves by a scan of the slices' maps — gives every line its state; no wave walks
+//     the records.  A slice of lines also counts its headers for each of the four states it may be entered in, so that the
+//     same scan hands every slice the index of its first record.
+//   * record table: the lane that holds a header (a non-blank line met in state 0) reads its four lines' starts and checks
+//     the record in readFastqRecord's order; the lowest record that fails wins by a 64-bit atomic minimum.
+//   * stage and gather: 16 bytes per lane from an unaligned source — five aligned dwords and v_alignbyte_b32 — to a
+//     16-byte aligned destination.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/teloscan.h"
+#include "fastq_internal.h"
+#include "ts_device.h"
+
+namespace {
+
+// the bytes of w that are '\n', a bit per byte (bits 0..3).  t has bit 7 of every byte that is zero in x (exact per byte: no
+// carry leaves a byte); the multiply moves bit 8 i + 7 to bit 24 + i (the sixteen partial products land on distinct bits)
+__device__ __forceinline__ uint32_t newline_bits(uint32_t w) {
+    const uint32_t x = w ^ 0x0a0a0a0au;
+    const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+    return (((t >> 7) * 0x01020408u) >> 24) & 15u;
+}
+
+// '\n' among the 16 bytes at plain + a (a: a multiple of 16), those at or beyond n left out
+__device__ __forceinline__ uint32_t newline_mask16(const unsigned char *plain, unsigned long long a, unsigned long long n) {
+    if (a >= n) return 0u;
+    const uint4 q = *(const uint4 *)(plain + a);                // (the chunk's buffer is readable 64 bytes beyond its capacity)
+    const uint32_t m = newline_bits(q.x) | newline_bits(q.y) << 4 | newline_bits(q.z) << 8 | newline_bits(q.w) << 12;
+    return n - a >= 16ull ? m : m & ((1u << (uint32_t)(n - a)) - 1u);
+}
+
+__global__ __launch_bounds__(64)
+void ts_fastq_count_kernel(const unsigned char *plain, unsigned long long n, uint32_t *counts) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kFastqSliceBytes + threadIdx.x * 16u;
+    uint32_t c = 0;
+#pragma unroll 8
+    for (uint32_t s = 0; s < kFastqSliceBytes / 1024u; ++s) c += __popc(newline_mask16(plain, base + 1024ull * s, n));
+    c = wave_total(c);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// counts -> exclusive sums in place (one wave, 64 slices per step)
+__global__ __launch_bounds__(64)
+void ts_fastq_count_scan_kernel(const unsigned char *plain, unsigned long long n, uint32_t *counts, uint32_t n_slices,
+                                unsigned long long *out) {
+    uint32_t run = 0;
+    for (uint32_t b = 0; b < n_slices; b += 64u) {
+        const uint32_t i = b + threadIdx.x;
+        const uint32_t c = i < n_slices ? counts[i] : 0u;
+        const uint32_t incl = wave_scan_add(c);
+        if (i < n_slices) counts[i] = run + incl - c;
+        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    if (threadIdx.x == 0) { out[kFqNewlines] = run; out[kFqTail] = n && plain[n - 1] != '\n' ? 1ull : 0ull; }
+}
+
+__global__ __launch_bounds__(64)
+void ts_fastq_index_kernel(const unsigned char *plain, unsigned long long n, const uint32_t *bases, uint32_t newlines, uint32_t tail,
+                           uint32_t *lstart, unsigned char *first, unsigned char *cr) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kFastqSliceBytes + threadIdx.x * 16u;
+    uint32_t run = bases[blockIdx.x];
+    for (uint32_t s = 0; s < kFastqSliceBytes / 1024u; ++s) {
+        const unsigned long long a = base + 1024ull * s;
+        uint32_t m = newline_mask16(plain, a, n);
+        if (ballot64(m != 0u) == 0ull) continue;                // (wave-uniform)
+        const uint32_t c = __popc(m), incl = wave_scan_add(c);
+        uint32_t k = run + incl - c;                            // the first of this lane's '\n' ends line k
+        while (m) {
+            const unsigned long long p = a + (uint32_t)__builtin_ctz(m);
+            m &= m - 1u;
+            if (k < newlines) {                                 // (always: the count pass saw the same bytes)
+                lstart[k + 1] = (uint32_t)(p + 1ull);
+                first[k + 1] = p + 1ull < n ? plain[p + 1ull] : (unsigned char)0;
+                cr[k] = p > 0ull && plain[p - 1ull] == '\r';
+            }
+            ++k;
+        }
+        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        lstart[0] = 0u;
+        first[0] = n ? plain[0] : (unsigned char)0;
+        if (tail) {                                             // the last line has no '\n': it ends at n
+            lstart[newlines + 1] = (uint32_t)(n + 1ull);
+            cr[newlines] = plain[n - 1ull] == '\r';
+        }
+    }
+}
+
+// ---- the framing automaton.  A map: state s goes to (map >> 2 s) & 3.
+constexpr uint32_t kMapIdentity = 0xe4u, kMapBlank = 0x38u, kMapLine = 0x39u;      // {0,1,2,3}, {0,2,3,0}, {1,2,3,0}
+
+__device__ __forceinline__ uint32_t map_then(uint32_t a, uint32_t b) {              // a, then b
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 4u; ++s) r |= ((b >> (2u * ((a >> (2u * s)) & 3u))) & 3u) << (2u * s);
+    return r;
+}
+__device__ __forceinline__ uint32_t wave_scan_maps(uint32_t v) {                    // inclusive, lane order
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
+        if ((int)threadIdx.x >= d) v = map_then(o, v);
+    }
+    return v;
+}
+// the map of the lanes below this one (lane 0: the identity)
+__device__ __forceinline__ uint32_t maps_below(uint32_t incl) {
+    const uint32_t o = (uint32_t)__shfl_up((int)incl, 1);
+    return threadIdx.x == 0 ? kMapIdentity : o;
+}
+// line i of n_lines: 0 = there is none, 1 = blank (logical length 0), 2 = any other
+__device__ __forceinline__ uint32_t line_kind(const uint32_t *lstart, const unsigned char *cr, uint32_t i, uint32_t n_lines) {
+    if (i >= n_lines) return 0u;
+    return lstart[i + 1] - 1u - lstart[i] - (uint32_t)cr[i] == 0u ? 1u : 2u;
+}
+
+__global__ __launch_bounds__(64)
+void ts_fastq_frame_kernel(const uint32_t *lstart, const unsigned char *cr, uint32_t n_lines, FastqFrame *frames) {
+    uint32_t before = kMapIdentity, cnt[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t s = 0; s < kFastqSliceLines; s += 64u) {
+        // (in 64 bits: the last slice of a chunk of nearly 2^32 lines would wrap; n_lines itself is no line)
+        const unsigned long long at = (unsigned long long)blockIdx.x * kFastqSliceLines + s + threadIdx.x;
+        const uint32_t i = at < n_lines ? (uint32_t)at : n_lines;
+        const uint32_t kind = line_kind(lstart, cr, i, n_lines);
+        const uint32_t incl = wave_scan_maps(kind == 0u ? kMapIdentity : kind == 1u ? kMapBlank : kMapLine);
+        const uint32_t pre = map_then(before, maps_below(incl));
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; ++e) cnt[e] += (uint32_t)__popcll(ballot64(kind == 2u && ((pre >> (2u * e)) & 3u) == 0u));
+        before = map_then(before, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63));
+    }
+    if (threadIdx.x == 0) {
+        FastqFrame f;
+        f.map = before; f.cnt[0] = cnt[0]; f.cnt[1] = cnt[1]; f.cnt[2] = cnt[2]; f.cnt[3] = cnt[3]; f.pad[0] = f.pad[1] = f.pad[2] = 0u;
+        frames[blockIdx.x] = f;
+    }
+}
+
+// the slices' maps scanned from state 0 (one wave, 64 slices per step): every slice's entry state and first record
+__global__ __launch_bounds__(64)
+void ts_fastq_frame_scan_kernel(const FastqFrame *frames, uint32_t n_frames, const uint32_t *lstart, uint32_t newlines,
+                                FastqEntry *entries, unsigned long long *out) {
+    uint32_t state = 0, base = 0;
+    for (uint32_t b = 0; b < n_frames; b += 64u) {
+        const uint32_t i = b + threadIdx.x;
+        const bool have = i < n_frames;
+        const uint32_t incl = wave_scan_maps(have ? frames[i].map : kMapIdentity);
+        const uint32_t in = (maps_below(incl) >> (2u * state)) & 3u;
+        const uint32_t c = have ? frames[i].cnt[in] : 0u;
+        const uint32_t sum = wave_scan_add(c);
+        if (have) { FastqEntry e; e.state = in; e.base = base + sum - c; entries[i] = e; }
+        state = ((uint32_t)__builtin_amdgcn_readlane((int)incl, 63) >> (2u * state)) & 3u;
+        base += (uint32_t)__builtin_amdgcn_readlane((int)sum, 63);
+    }
+    if (threadIdx.x == 0) {
+        out[kFqHeaders] = base; out[kFqError] = ~0ull; out[kFqOpen] = 0ull; out[kFqOpenOff] = 0ull; out[kFqLastLine] = lstart[newlines];
+    }
+}
+
+__global__ __launch_bounds__(64)
+void ts_fastq_records_kernel(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                             int at_end, const FastqEntry *entries, ts_fastq_record *recs, unsigned long long *out) {
+    uint32_t state = entries[blockIdx.x].state, base = entries[blockIdx.x].base;
+    for (uint32_t s = 0; s < kFastqSliceLines; s += 64u) {
+        // (in 64 bits: the last slice of a chunk of nearly 2^32 lines would wrap; n_lines itself is no line)
+        const unsigned long long at = (unsigned long long)blockIdx.x * kFastqSliceLines + s + threadIdx.x;
+        const uint32_t i = at < n_lines ? (uint32_t)at : n_lines;
+        const uint32_t kind = line_kind(lstart, cr, i, n_lines);
+        const uint32_t incl = wave_scan_maps(kind == 0u ? kMapIdentity : kind == 1u ? kMapBlank : kMapLine);
+        // (every lane takes part in the shuffle: a lane that sat out would hand its neighbour a zero map)
+        const uint32_t below = maps_below(incl);
+        const bool header = kind == 2u && ((below >> (2u * state)) & 3u) == 0u;
+        const unsigned long long heads = ballot64(header);
+        if (header) {
+            const uint32_t r = base + (uint32_t)__popcll(heads & low_bits(threadIdx.x));
+            const uint32_t s0 = lstart[i];
+            if (n_lines - i < 4u) {                             // the lines ran out: the carry, or a truncated record
+                out[kFqOpenOff] = s0;                           // (only the last header can be here)
+                out[kFqOpen] = 1ull;
+                if (at_end) atomicMin(&out[kFqError], (unsigned long long)r << 3 | TS_FASTQ_TRUNCATED);
+            } else {
+                const uint32_t s1 = lstart[i + 1], s2 = lstart[i + 2], s3 = lstart[i + 3], s4 = lstart[i + 4];
+                ts_fastq_record rec;
+                rec.off = s0; rec.seq_at = s1 - s0; rec.seq_len = s2 - 1u - s1; rec.size = s4 - 1u - s0; rec.seq_cr = cr[i + 1];
+                recs[r] = rec;
+                uint32_t bad = TS_FASTQ_OK;
+                if (first[i] != '@') bad = TS_FASTQ_BAD_HEADER;
+                else if (s3 - 1u - s2 == 0u || first[i + 2] != '+') bad = TS_FASTQ_BAD_SEPARATOR;
+                else if (rec.seq_len - rec.seq_cr != s4 - 1u - s3 - (uint32_t)cr[i + 3]) bad = TS_FASTQ_BAD_LENGTHS;
+                if (bad) atomicMin(&out[kFqError], (unsigned long long)r << 3 | bad);
+            }
+        }
+        state = ((uint32_t)__builtin_amdgcn_readlane((int)incl, 63) >> (2u * state)) & 3u;
+        base += (uint32_t)__popcll(heads);
+    }
+}
+
+// ---- 16 bytes from any address: the five aligned dwords that hold them, shifted into place (reads up to 19 bytes beyond p + 16
+// rounded down to a dword: inside the 64 readable bytes behind the chunk)
+__device__ __forceinline__ uint4 load16_any(const unsigned char *p) {
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t *q = (const uint32_t *)(a & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(a & 3u);
+    uint32_t w[5];
+    __builtin_memcpy(w, __builtin_assume_aligned(q, 4), 20);
+    return make_uint4(__builtin_amdgcn_alignbyte(w[1], w[0], sh), __builtin_amdgcn_alignbyte(w[2], w[1], sh),
+                      __builtin_amdgcn_alignbyte(w[3], w[2], sh), __builtin_amdgcn_alignbyte(w[4], w[3], sh));
+}
+
+// a piece of a sequence line into a read batch's input buffer: a wave per job, 16 bytes per lane per store
+__global__ __launch_bounds__(64)
+void ts_fastq_stage_kernel(const unsigned char *plain, const FastqCopyJob *jobs, uint32_t n_jobs, unsigned char *in) {
+    if (blockIdx.x >= n_jobs) return;
+    const FastqCopyJob job = jobs[blockIdx.x];
+    const unsigned char *src = plain + job.src;
+    unsigned char *dst = in + job.dst;                          // 16-byte aligned
+    for (uint32_t i = threadIdx.x * 16u; i < job.n; i += 1024u) {
+        uint4 v = load16_any(src + i);
+        const uint32_t left = job.n - i;
+        if (left < 16u) {                                       // the bytes behind the read stay zero, as an upload leaves them
+            uint32_t o[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; ++q) {
+                const uint32_t have = left > 4u * q ? left - 4u * q : 0u;
+                o[q] &= have >= 4u ? 0xffffffffu : have == 0u ? 0u : (1u << (8u * have)) - 1u;
+            }
+            v = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+        *(uint4 *)(dst + i) = v;
+    }
+}
+
+// ---- passing records, in input order, each with a '\n' behind it: a prefix sum over size + 1 of the records whose pass byte is
+// set (one wave, 64 records per step; the sibling of bgzf.hip's plan, whose sizes are 4 + block_size), then a wave per record
+__global__ __launch_bounds__(64)
+void ts_fastq_gather_plan_kernel(const ts_fastq_record *recs, const unsigned char *pass, unsigned long long n,
+                                 unsigned long long *dst_off, unsigned long long *totals) {
+    unsigned long long run = 0, kept = 0;
+    for (unsigned long long base = 0; base < n; base += 64ull) {
+        const unsigned long long i = base + threadIdx.x;
+        const bool keep = i < n && pass[i] != 0;
+        const unsigned long long size = keep ? 1ull + recs[i].size : 0ull;
+        // (a step's sizes are summed in two halves: 64 records of up to 4 GiB)
+        const uint32_t incl_lo = wave_scan_add((uint32_t)(size & 0xffffull)), incl_hi = wave_scan_add((uint32_t)(size >> 16));
+        const unsigned long long incl = (unsigned long long)incl_lo + ((unsigned long long)incl_hi << 16);
+        if (i < n) dst_off[i] = keep ? run + incl - size : ~0ull;
+        run += (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)incl_lo, 63) +
+               ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)incl_hi, 63) << 16);
+        kept += (unsigned long long)__popcll(ballot64(keep));
+    }
+    if (threadIdx.x == 0) { totals[0] = run; totals[1] = kept; }
+}
+
+__global__ __launch_bounds__(64)
+void ts_fastq_gather_kernel(const unsigned char *plain, const ts_fastq_record *recs, const unsigned long long *dst_off,
+                            unsigned long long n, unsigned long long cap, unsigned char *out) {
+    const unsigned long long r = blockIdx.x;
+    if (r >= n) return;
+    const unsigned long long to = dst_off[r];
+    if (to == ~0ull) return;
+    const uint32_t size = recs[r].size;
+    if (to > cap || 1ull + size > cap - to) return;             // (the caller has compared the total with cap already)
+    const unsigned char *src = plain + recs[r].off;
+    unsigned char *dst = out + to;
+    // bytes up to the destination's next 16-byte boundary, whole 16-byte stores, the rest, the '\n'
+    uint32_t head = (16u - (uint32_t)(to & 15ull)) & 15u;
+    if (head > size) head = size;
+    const uint32_t body = (size - head) & ~15u, rest = size - head - body;
+    if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+    for (uint32_t i = threadIdx.x * 16u; i < body; i += 1024u) *(uint4 *)(dst + head + i) = load16_any(src + head + i);
+    if (threadIdx.x < rest) dst[head + body + threadIdx.x] = src[head + body + threadIdx.x];
+    if (threadIdx.x == 63) dst[size] = '\n';
+}
+
+}  // namespace
+
+extern "C" {
+
+int ts_k_launch_fastq_count(const void *plain, unsigned long long n, uint32_t *counts, unsigned long long *out, void *stream) {
+    const uint32_t slices = (uint32_t)((n + kFastqSliceBytes - 1) / kFastqSliceBytes);
+    if (slices) hipLaunchKernelGGL(ts_fastq_count_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, counts);
+    hipLaunchKernelGGL(ts_fastq_count_scan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, counts,
+                       slices, out);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_index(const void *plain, unsigned long long n, const uint32_t *bases, uint32_t newlines, uint32_t tail,
+                            uint32_t *lstart, unsigned char *first, unsigned char *cr, void *stream) {
+    const uint32_t slices = (uint32_t)((n + kFastqSliceBytes - 1) / kFastqSliceBytes);
+    if (slices == 0) return 0;
+    hipLaunchKernelGGL(ts_fastq_index_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, bases,
+                       newlines, tail, lstart, first, cr);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_frames(const uint32_t *lstart, const unsigned char *cr, uint32_t n_lines, uint32_t newlines, void *frames,
+                             void *entries, unsigned long long *out, void *stream) {
+    const uint32_t nf = (uint32_t)(((unsigned long long)n_lines + kFastqSliceLines - 1) / kFastqSliceLines);
+    if (nf) hipLaunchKernelGGL(ts_fastq_frame_kernel, dim3(nf), dim3(64), 0, (hipStream_t)stream, lstart, cr, n_lines, (FastqFrame *)frames);
+    hipLaunchKernelGGL(ts_fastq_frame_scan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const FastqFrame *)frames, nf, lstart,
+                       newlines, (FastqEntry *)entries, out);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_records(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                              int at_end, const void *entries, void *recs, unsigned long long *out, void *stream) {
+    const uint32_t nf = (uint32_t)(((unsigned long long)n_lines + kFastqSliceLines - 1) / kFastqSliceLines);
+    if (nf == 0) return 0;
+    hipLaunchKernelGGL(ts_fastq_records_kernel, dim3(nf), dim3(64), 0, (hipStream_t)stream, lstart, first, cr, n_lines, at_end,
+                       (const FastqEntry *)entries, (ts_fastq_record *)recs, out);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_stage(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream) {
+    if (n_jobs == 0) return 0;
+    hipLaunchKernelGGL(ts_fastq_stage_kernel, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain,
+                       (const FastqCopyJob *)jobs, n_jobs, (unsigned char *)in);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream) {
+    hipLaunchKernelGGL(ts_fastq_gather_plan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const ts_fastq_record *)recs,
+                       (const unsigned char *)pass, n, (unsigned long long *)dst_off, (unsigned long long *)totals);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
+                             void *out, void *stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(ts_fastq_gather_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain,
+                       (const ts_fastq_record *)recs, (const unsigned long long *)dst_off, n, cap, (unsigned char *)out);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"
