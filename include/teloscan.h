@@ -141,6 +141,7 @@ typedef struct ts_block {
 #define TS_INPUT_BASES       0
 #define TS_INPUT_TEXT_PIECES 1
 #define TS_INPUT_PACKED2     2
+#define TS_INPUT_DEVICE      3
 typedef struct ts_text_piece {
     const char *text;        /* text_len bytes: n_bases bases and the line ends between / behind them ('\n', and a '\r'
                                 right before one or at the very end of the piece) */
@@ -155,6 +156,13 @@ typedef struct ts_text_piece {
  * quarter of the bytes instead of reading the ASCII a second time, which is what bounds the host entry points once the
  * link carries packed bases.  Results cannot depend on the input format: the device restores the same
  * byte layout ('N' over the runs) that TS_INPUT_BASES uploads.  Tiled kernel's parameter sets only, like the text pieces. */
+/* input_format TS_INPUT_DEVICE: `seq` is a DEVICE pointer, on the context's device, to the segment's `len` bases — raw ASCII in
+ * any case, non-ACGT bytes as they are: exactly the bytes TS_INPUT_BASES would have uploaded, so results are byte-equal to
+ * that format's.  The bases are copied device to device into the scan's input layout (no pinned buffer, no host thread, nothing
+ * over PCIe); any address will do, and the writes that produced them must be complete when the call is made (the copy runs on a
+ * stream of the library's own).  Any parameter set, full and tips-only scans, mixed freely with host segments in one call; not
+ * ts_scan_segments_multi (the pointer belongs to one device).  Stands in for the std::string& that scanSegment borrows
+ * (include/teloscope.h:260) when a front end has produced the bases on the device (the FASTA route's joined records). */
 typedef struct ts_packed_run { uint64_t start, len; } ts_packed_run;
 typedef struct ts_packed_seq {
     const uint8_t       *codes;     /* (len + 3) / 4 bytes */
@@ -162,11 +170,11 @@ typedef struct ts_packed_seq {
     uint64_t             n_runs;
 } ts_packed_seq;
 typedef struct ts_segment_in {
-    const char *seq;        /* borrowed for the duration of the call; need not be NUL-terminated */
+    const char *seq;        /* borrowed for the duration of the call; need not be NUL-terminated (TS_INPUT_DEVICE: device memory) */
     uint64_t    len;
     uint64_t    abs_pos;
     uint8_t     tips_only;
-    uint8_t     input_format;   /* TS_INPUT_BASES / TS_INPUT_TEXT_PIECES / TS_INPUT_PACKED2 (any parameter set the library scans) */
+    uint8_t     input_format;   /* TS_INPUT_BASES / TS_INPUT_TEXT_PIECES / TS_INPUT_PACKED2 / TS_INPUT_DEVICE (any parameter set the library scans) */
     uint8_t     reserved[2];
     uint32_t    n_pieces;       /* TS_INPUT_TEXT_PIECES: entries of the ts_text_piece array (the walk never reads past it;
                                    pieces that hold fewer than `len` bases are TS_ERR_INVALID_ARG) */
@@ -230,8 +238,8 @@ int     ts_uses_fast_path(const ts_ctx *ctx);
  * independent integer instructions at four waves per SIMD — and streams — read + write bytes per ns of a 1 GiB copy —, so that
  * a benchmark line from a box that runs everything a few per cent slower can be told from a slower kernel (bench.py: roofline.box). */
 int     ts_box_probe(ts_ctx *ctx, double *valu_wave_instr_per_ns, double *copy_bytes_per_ns);
-/* 1 if segments of this kind (full scan / tips-only) may come as TS_INPUT_TEXT_PIECES or TS_INPUT_PACKED2: every parameter
- * set the library scans (until ABI 3 the general kernels wanted the bases joined). */
+/* 1 if segments of this kind (full scan / tips-only) may come as TS_INPUT_TEXT_PIECES, TS_INPUT_PACKED2 or TS_INPUT_DEVICE:
+ * every parameter set the library scans (until ABI 3 the general kernels wanted the bases joined). */
 int     ts_takes_text_input(const ts_ctx *ctx, int tips_only);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
  * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
@@ -727,6 +735,61 @@ int ts_fastq_chunk_stage(ts_chunk *chunk, const ts_fastq_record *recs, size_t n,
  * ts_bam_chunk_gather.  Ordered on `stream`; waits for it. */
 int ts_fastq_chunk_gather(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, const void *d_pass, void *host_out,
                           uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+
+/* ---- FASTA text in the same resident chunk: the device form of the assembly front end.  Replaces the reference's FASTA load
+ *      (gfalibs' stream parser behind Input::read, src/input.cpp:655-716: header lines split off, body lines joined into one
+ *      sequence per record) and the cut of a path into segments and gaps at its N-runs (the path components walkPath
+ *      iterates, src/input.cpp:934-1037).  The text reaches the chunk as for FASTQ (ts_chunk_upload, ts_bam_chunk_inflate);
+ *      lines are indexed, records framed, body lines joined into contiguous bases and the runs found, all on the device.
+ *      What comes back is the record table, the header lines and the runs: a few entries per record.  The joined bases stay
+ *      in HBM and are scanned from there (TS_INPUT_DEVICE).
+ *      The rules, which are the host route's (include/teloscope_mi355x_io.hpp: readFasta, FastaGroupReader, splitPath):
+ *        header line   a line whose first byte is '>'; a line starts at byte 0 of the input or right behind a '\n'; a '>'
+ *                      anywhere else is a base.  Bytes in front of the first header line belong to no record.
+ *        name          the header line without its '>', its '\n' and a '\r' right before that (the host cuts it at the first
+ *                      space or tab).
+ *        bases         every byte of the record's body lines except '\n', a '\r' right before a '\n', and a '\r' that is the
+ *                      input's very last byte.  Blank lines give nothing; any other byte, a space included, is a base.  A
+ *                      record may have no bases and still is a record.
+ *        runs          maximal runs of N n X x are gaps, maximal runs of anything else segments; record-relative, never
+ *                      joined across records. */
+typedef struct ts_fasta_record {
+    uint64_t off;                /* of the record's '>' in the chunk */
+    uint32_t text_len;           /* from off to the next record's '>' (or the chunk's end) */
+    uint32_t body_at;            /* the first body line's first byte, relative to off (== text_len: no body line) */
+    uint32_t n_bases;
+    uint32_t name_at;            /* where the record's header line (without '>' and line end) lies in `names` */
+    uint32_t name_len;
+    uint32_t reserved;
+} ts_fasta_record;
+typedef struct ts_fasta_run {
+    uint32_t record;             /* index into the joined records */
+    uint32_t is_gap;             /* 1: a run of N n X x */
+    uint32_t start;              /* record-relative, in bases */
+    uint32_t len;
+} ts_fasta_run;
+/* Lines and records of the whole chunk (at most 4 GiB - 2 bytes), which starts at a line's first byte.  *n = complete records,
+ * the first min(*n, cap) of them to recs (host memory); their header lines, gathered on the device into one buffer, to
+ * names[0, *names_bytes) in ONE copy.  When *n > cap or *names_bytes > names_cap nothing usable is copied and the call answers
+ * TS_ERR_INVALID_ARG (call again with room for *n and *names_bytes).  Without at_end the chunk's last record is never complete
+ * (the next chunk may continue it) and *next is its '>': the carry; a chunk that holds nothing but one unfinished record gives
+ * *n = 0 and *next = 0 and the caller grows the chunk (ts_chunk_reserve), as for FASTQ.  A chunk without any header line holds
+ * no record: *next is the first byte of its last, unfinished line.  With at_end != 0 the input ends with the chunk, the last
+ * line may lack its '\n', every record is complete and *next = size.  Waits for the device. */
+int ts_fasta_chunk_walk(ts_chunk *chunk, int at_end, ts_fasta_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
+                        char *names, uint64_t names_cap, uint64_t *names_bytes);
+/* The bases of recs[0, n) (entries of the last walk's table, with the same at_end) joined into a buffer the chunk owns: record
+ * i's n_bases bases from byte offsets[i] (a multiple of 16; host memory, n entries) of *d_bases (device memory, valid until the
+ * next join or ts_bam_chunk_destroy), zero bytes between records, *total_bytes in all; and the records' runs found,
+ * *n_runs of them (ts_fasta_chunk_runs reads them).  A stream compaction: kept bytes counted per 16 KB of body text, the counts
+ * summed, every byte read once and written once.  Ordered on `stream`; waits for it. */
+int ts_fasta_chunk_join(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, int at_end, const void **d_bases,
+                        uint64_t *offsets, uint64_t *total_bytes, uint64_t *n_runs, void *stream);
+/* The runs of the last join, per record in order, records ascending (a record without bases has none): *n_runs of them, to
+ * runs (host memory) when they fit cap, else TS_ERR_INVALID_ARG (call again with room for *n_runs).  Waits for the device. */
+int ts_fasta_chunk_runs(ts_chunk *chunk, ts_fasta_run *runs, uint64_t cap, uint64_t *n_runs);
+/* joined[off, off + n) of the last join to host memory (tests; the match sequences of -m).  Waits for the device. */
+int ts_fasta_chunk_bases(ts_chunk *chunk, uint64_t off, uint64_t n, void *host);
 
 #ifdef __cplusplus
 }

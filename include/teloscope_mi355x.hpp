@@ -262,6 +262,9 @@ public:
     }
 
     size_t deviceCount() const { return all.size(); }
+    // the first device's context: what a caller needs to produce bases on that device (ts_bam_chunk_create on it, the
+    // ts_fasta_chunk_* stages: scanFastaToFilesDevice) and hand them over as device segments
+    ts_ctx *context() const { return ctx.get(); }
 
     const UserInputTeloscope &input() const { return userInput; }
     // does the library take TS_INPUT_TEXT_PIECES segments for this parameter set (every set it scans)?
@@ -279,6 +282,9 @@ public:
         const ts_text_piece *pieces = nullptr; // FASTA body text as it lies in the file (TS_INPUT_TEXT_PIECES): the
                                                // library skips the line ends on the way to the device
         const TextLines *lines = nullptr;      // per piece, optional: lets bases() jump to a position instead of walking lines
+        const char *device = nullptr;          // the device form (TS_INPUT_DEVICE): the same bases in the first context's device
+                                               // memory, which the scan reads; `data` is then an optional host view that serves
+                                               // bases() (-m) and may be nullptr when nothing asks for a base
         mutable size_t cursorPiece = 0;        // bases() is asked for ascending positions: where the last answer lay
         mutable uint64_t cursorCum = 0;
         Segment(const char *d, size_t n, uint64_t a, bool t) : data(d), size(n), absPos(a), tipsOnly(t) {}
@@ -288,9 +294,9 @@ public:
             : data(nullptr), size(nBases), absPos(a), tipsOnly(t), pieces(p), lines(l), nPieces(np) {}
         ts_segment_in in() const {
             ts_segment_in x{};
-            x.seq = pieces ? reinterpret_cast<const char *>(pieces) : data;
+            x.seq = pieces ? reinterpret_cast<const char *>(pieces) : device ? device : data;
             x.len = size; x.abs_pos = absPos; x.tips_only = static_cast<uint8_t>(tipsOnly);
-            x.input_format = pieces ? TS_INPUT_TEXT_PIECES : TS_INPUT_BASES;
+            x.input_format = pieces ? TS_INPUT_TEXT_PIECES : device ? TS_INPUT_DEVICE : TS_INPUT_BASES;
             x.n_pieces = static_cast<uint32_t>(nPieces);
             return x;
         }

@@ -251,6 +251,8 @@ struct RecordView {
     const ts_text_piece *pieces = nullptr;     // FASTA body text in the file (line ends included), in order
     size_t nPieces = 0;
     const TextLines *lines = nullptr;          // per piece, optional
+    const char *device = nullptr;              // the bases in device memory (joined there: scanFastaToFilesDevice); `data` is then
+                                               // an optional host copy (-m), and the components must come precomputed
 };
 
 namespace detail {
@@ -400,8 +402,10 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
     for (size_t pi = 0; pi < records.size(); ++pi) {
         const RecordView &rv = records[pi];
         if (!rv.pieces) {
-            for (const auto &sg : comps[pi].segments)
-                batch.emplace_back(rv.data + sg.first, static_cast<size_t>(sg.second), sg.first, ui.ultraFastMode);
+            for (const auto &sg : comps[pi].segments) {
+                batch.emplace_back(rv.data ? rv.data + sg.first : nullptr, static_cast<size_t>(sg.second), sg.first, ui.ultraFastMode);
+                if (rv.device) batch.back().device = rv.device + sg.first;
+            }
             continue;
         }
         if (oneSegment(pi)) {
@@ -2502,6 +2506,248 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
     if (scanError) std::rethrow_exception(scanError);
     if (writeError) std::rethrow_exception(writeError);
     T.wall_ms = ms(t_begin, Clock::now());
+    if (times) *times = T;
+    return sum;
+}
+
+// The device route of the assembly scan (same files, console report and AssemblySummary as scanFastaToFiles, which stays the
+// default): the FASTA text exists in HBM one chunk of ~chunkBytes bytes at a time, and without -m the host reads none of it.
+// The text gets there from the three sources of fastqSubsetDevice —
+//   1. a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
+//   2. a BGZF regular file (bgzip output): members located on the host, inflated and checksummed on the device
+//      (ts_bam_chunk_inflate); from the first member that does not parse as BGZF on, the rest of the input takes source 3;
+//   3. anything else (plain gzip, a FIFO, a file that cannot be mapped): through zlib or read(2) in blocks, each block uploaded —
+// (the fill below is a second copy of fastqSubsetDevice's: that one is woven into its FASTQ checks, and it stays untouched)
+// and per chunk: lines indexed, records framed, names gathered (ts_fasta_chunk_walk); body lines joined into contiguous bases and
+// the N-runs found (ts_fasta_chunk_join, ts_fasta_chunk_runs); PathComponents built from the runs, a few entries per record;
+// every segment handed to the scan as a device segment through walkRecordViews, so that blocks, counts and windows come back
+// exactly as for the host route; BedWriter fed.  With -m the joined bases are read back once per chunk (matchSeq needs them).
+// The bytes behind the last complete record stay in the chunk for the next fill; a record larger than a chunk makes it grow.
+// Limits: ONE device (a Teloscope over several throws); no assembly record filters (they stay with the host route); a record
+// whose text does not fit a chunk of chunkLimit bytes (4 GiB - 2, what the walk takes) is refused by name, never cut; the
+// stages run one after the other.  chunkLimit is a test hook (the refusal cannot be reached otherwise without 4 GiB of text):
+// callers leave it alone.  What a maintainer of the reference would call in place of its FASTA load and per-path jobs
+// (src/input.cpp:655-733).
+inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
+                                              std::ostream &console, bool manualCuration = false,
+                                              size_t chunkBytesArg = size_t(256) << 20, ScanFastaTimes *times = nullptr,
+                                              uint64_t chunkLimit = 0xfffffffeull) {
+    using Clock = std::chrono::steady_clock;
+    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto tBegin = Clock::now();
+    if (teloscope.deviceCount() > 1)
+        throw std::runtime_error("scanFastaToFilesDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
+                                 " (the joined bases lie in one device's memory)");
+    const UserInputTeloscope &ui = teloscope.input();
+    ts_ctx *ctx = teloscope.context();
+    auto fail = [&](const char *what) -> std::runtime_error {
+        const char *why = ts_last_error(ctx);
+        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
+    };
+    chunkLimit = std::max<uint64_t>(std::min<uint64_t>(chunkLimit, 0xfffffffeull), 64);
+    const int fd = ::open(fastaFile.c_str(), O_RDONLY);
+    if (fd < 0) throw std::runtime_error("cannot open " + fastaFile);
+    struct Closer { int fd; gzFile gz = nullptr; ~Closer() { if (gz) gzclose(gz); else ::close(fd); } } closer{fd};
+    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
+    {
+        struct stat st;
+        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
+        }
+    }
+    const unsigned char *data = static_cast<const unsigned char *>(mapping.p);
+    const size_t size = mapping.n;
+    auto bgzfMember = [](const unsigned char *p, size_t n, detail::BgzfBlockRef &ref, bool &eofm) -> size_t {
+        try { return detail::parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
+    };
+    enum { Plain, Bgzf, Stream } source = Stream;
+    if (data) {
+        detail::BgzfBlockRef ref{};
+        bool eofm = false;
+        if (size >= 2 && data[0] == 0x1f && data[1] == 0x8b) source = bgzfMember(data, size, ref, eofm) ? Bgzf : Stream;
+        else source = Plain;
+    }
+    const bool deviceInflate = source == Bgzf;
+    // (a fill of BGZF members may exceed what it was asked for by one member: the chunk stays below the walk's limit all the same)
+    if (deviceInflate && chunkLimit > (1u << 17)) chunkLimit -= 65536;
+    bool streamOpen = false, streamDone = false;
+    auto openStream = [&](size_t from) {
+        streamOpen = true;
+        bool gz = false;
+        if (from > 0) {                                         // behind BGZF members anything that is not gzip ends the input
+            if (size - from < 2 || data[from] != 0x1f || data[from + 1] != 0x8b) { streamDone = true; return; }
+            if (::lseek(fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error("read error in " + fastaFile);
+            gz = true;
+        } else {
+            unsigned char magic[2] = {0, 0};
+            gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+        }
+        if (gz) {
+            closer.gz = gzdopen(fd, "rb");
+            if (!closer.gz) throw std::runtime_error("cannot open " + fastaFile);
+            gzbuffer(closer.gz, 1u << 20);
+        }
+    };
+    auto get = [&](char *dst, size_t n) -> long {
+        if (closer.gz) return gzread(closer.gz, dst, static_cast<unsigned>(std::min<size_t>(n, 1u << 30)));
+        return static_cast<long>(::read(fd, dst, std::min<size_t>(n, 1u << 30)));
+    };
+    double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;
+    ScanFastaTimes T;
+
+    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+    const uint64_t compCap = source == Bgzf ? chunkBytes + (1u << 20) : 64;
+    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, compCap, chunkBytes)};
+    if (!chunk.p) throw fail("cannot make the device chunk");
+
+    BedWriter writer(outBase, ui, console, manualCuration);
+    std::vector<ts_fasta_record> recs(4096);
+    std::vector<char> names(size_t(1) << 16), block, hostBases;
+    std::vector<ts_fasta_run> runs(4096);
+    std::vector<uint64_t> offsets;
+    std::vector<ts_bgzf_block> descs;
+    std::vector<std::string> headers;
+    size_t recordsDone = 0;
+
+    size_t at = 0;                              // next byte of the mapped file (sources 1 and 2)
+    uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
+    bool atEnd = false;
+    while (!atEnd) {
+        const uint64_t carry = held - pos;
+        // a chunk that held no whole record (a record larger than it) takes as much again, up to what a chunk may hold
+        if (pos == 0 && carry >= chunkLimit) {
+            char head[257] = {0};
+            const uint64_t hn = std::min<uint64_t>(held, 256);
+            if (hn && ts_bam_chunk_read(chunk.p, 0, hn, head) != TS_OK) throw fail("cannot read the chunk");
+            const char *nl = static_cast<const char *>(std::memchr(head, '\n', static_cast<size_t>(hn)));
+            const std::string name = head[0] == '>' ? detail::fastaHeaderWord(head + 1, nl ? nl : head + hn) : std::string();
+            throw std::runtime_error(head[0] == '>' ? "FASTA record '" + name + "' does not fit a device chunk (" + std::to_string(chunkLimit) + " bytes of text); use the host route"
+                                                    : "a line of more than " + std::to_string(chunkLimit) + " bytes in front of the first FASTA record does not fit a device chunk");
+        }
+        const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0), chunkLimit - carry));
+        Clock::time_point t0 = Clock::now();
+        if (source == Bgzf) {
+            uint64_t produced = 0, from = pos;
+            bool foreign = false, full = false;
+            do {
+                descs.clear();
+                size_t used = 0;
+                uint64_t made = 0;
+                while (at + used < size) {
+                    detail::BgzfBlockRef ref{};
+                    bool eofm = false;
+                    const size_t total = bgzfMember(data + at + used, size - at - used, ref, eofm);
+                    if (total == 0) { foreign = true; break; }
+                    if (produced + made > 0 && produced + made + ref.isize > want) { full = true; break; }
+                    if (!descs.empty() && used + total > compCap) break;
+                    ts_bgzf_block d{};
+                    d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
+                    d.dst_off = carry + produced + made;
+                    descs.push_back(d);
+                    made += ref.isize;
+                    used += total;
+                }
+                if (ts_chunk_reserve(chunk.p, carry + produced + made) != TS_OK) throw fail("cannot grow the device chunk");
+                if (ts_bam_chunk_inflate(chunk.p, data + at, used, descs.data(), descs.size(), from, nullptr) != TS_OK) throw fail("BGZF inflate failed");
+                ts_bgzf_status bad{};
+                if (ts_bam_chunk_status(chunk.p, &bad) != TS_OK) throw fail("BGZF inflate failed");
+                if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
+                if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
+                at += used;
+                produced += made;
+                from = 0;
+            } while (!foreign && !full && at < size);
+            if (foreign) { source = Stream; openStream(at); atEnd = streamDone; }
+            else atEnd = at >= size;
+        } else if (source == Plain) {
+            const size_t n = std::min(want, size - at);
+            if (ts_chunk_upload(chunk.p, data + at, n, pos, nullptr) != TS_OK) throw fail("upload of the FASTA text failed");
+            at += n;
+            atEnd = at >= size;
+        } else {
+            if (!streamOpen) openStream(0);
+            if (block.size() < want) block.resize(want);
+            size_t got = 0;
+            while (!streamDone && got < want) {
+                const long n = get(block.data() + got, want - got);
+                if (n < 0) throw std::runtime_error("read error in " + fastaFile);
+                if (n == 0) { streamDone = true; break; }
+                got += static_cast<size_t>(n);
+            }
+            if (ts_chunk_upload(chunk.p, block.data(), got, pos, nullptr) != TS_OK) throw fail("upload of the FASTA text failed");
+            atEnd = streamDone;
+        }
+        msUpload += since(t0);
+        held = ts_bam_chunk_size(chunk.p); pos = 0;
+        if (held == 0) continue;
+
+        // records and names
+        t0 = Clock::now();
+        uint64_t n = 0, next = 0, nameBytes = 0;
+        int rc = ts_fasta_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
+        if (rc == TS_ERR_INVALID_ARG && (n > recs.size() || nameBytes > names.size())) {
+            if (n > recs.size()) recs.resize(static_cast<size_t>(n));
+            if (nameBytes > names.size()) names.resize(static_cast<size_t>(nameBytes));
+            rc = ts_fasta_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
+        }
+        if (rc != TS_OK) throw fail("FASTA walk failed");
+        msIndex += since(t0);
+        pos = next;
+        if (n == 0) continue;
+
+        // bases and runs
+        t0 = Clock::now();
+        const void *dBases = nullptr;
+        uint64_t total = 0, nRuns = 0;
+        offsets.resize(static_cast<size_t>(n));
+        if (ts_fasta_chunk_join(chunk.p, recs.data(), static_cast<size_t>(n), atEnd ? 1 : 0, &dBases, offsets.data(), &total, &nRuns, nullptr) != TS_OK)
+            throw fail("FASTA join failed");
+        if (nRuns > runs.size()) runs.resize(static_cast<size_t>(nRuns));
+        if (ts_fasta_chunk_runs(chunk.p, runs.data(), runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
+        const bool hostView = ui.outMatches && !ui.ultraFastMode;
+        if (hostView) {                                         // matchSeq is cut out of the bases: one copy per chunk
+            hostBases.resize(static_cast<size_t>(total) + 1);
+            if (ts_fasta_chunk_bases(chunk.p, 0, total, hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
+        }
+        msJoin += since(t0);
+
+        // path components from the runs; every segment a device segment
+        headers.resize(static_cast<size_t>(n));
+        std::vector<PathComponents> comps(static_cast<size_t>(n));
+        std::vector<RecordView> views(static_cast<size_t>(n));
+        for (uint64_t r = 0; r < nRuns; ++r) {
+            const ts_fasta_run &run = runs[static_cast<size_t>(r)];
+            if (run.record >= n) throw std::runtime_error("FASTA runs: a run of a record that was not joined");
+            if (run.is_gap) comps[run.record].gaps.push_back(GapInfo{run.start, run.len});
+            else { comps[run.record].segments.emplace_back(run.start, run.len); T.library_bases += run.len; }
+        }
+        for (size_t i = 0; i < n; ++i) {
+            const ts_fasta_record &r = recs[i];
+            headers[i] = detail::fastaHeaderWord(names.data() + r.name_at, names.data() + r.name_at + r.name_len);
+            views[i] = RecordView{&headers[i], hostView ? hostBases.data() + offsets[i] : nullptr, r.n_bases, nullptr, 0, nullptr,
+                                  static_cast<const char *>(dBases) + offsets[i]};
+        }
+        t0 = Clock::now();
+        std::vector<PathData> paths = walkRecordViews(teloscope, views, recordsDone, &comps);
+        recordsDone += static_cast<size_t>(n);
+        msScan += since(t0);
+        t0 = Clock::now();
+        writer.add(paths);
+        for (const PathData &pd : paths) { T.bases += pd.pathSize; T.windows += pd.windows.size(); }
+        ++T.groups;
+        msWrite += since(t0);
+    }
+    const auto tf = Clock::now();
+    AssemblySummary sum = writer.finish();
+    sum.filterActive = ui.sequenceFilterActive;
+    sum.filterInputCount = ui.filterInputCount;
+    sum.filterSelectedCount = ui.filterSelectedCount;
+    msWrite += since(tf);
+    if (std::getenv("TS_TIMING"))
+        std::fprintf(stderr, "scanFastaToFilesDevice: upload%s %.0f ms, index %.0f ms, join %.0f ms, scan %.0f ms, write %.0f ms\n",
+                     deviceInflate ? " + inflate + CRC" : "", msUpload, msIndex, msJoin, msScan, msWrite);
+    T.read_ms = msUpload + msIndex + msJoin; T.scan_ms = msScan; T.write_ms = msWrite; T.wall_ms = since(tBegin);
     if (times) *times = T;
     return sum;
 }

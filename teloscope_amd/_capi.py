@@ -61,7 +61,7 @@ class SegmentIn(C.Structure):
                 ("tips_only", C.c_uint8), ("input_format", C.c_uint8), ("reserved", C.c_uint8 * 2), ("n_pieces", C.c_uint32)]
 
 
-TS_INPUT_BASES, TS_INPUT_TEXT_PIECES, TS_INPUT_PACKED2 = 0, 1, 2
+TS_INPUT_BASES, TS_INPUT_TEXT_PIECES, TS_INPUT_PACKED2, TS_INPUT_DEVICE = 0, 1, 2, 3
 
 
 class PackedRun(C.Structure):
@@ -182,6 +182,15 @@ class FastqRecord(C.Structure):
                 ("seq_cr", C.c_uint32)]
 
 
+class FastaRecord(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("text_len", C.c_uint32), ("body_at", C.c_uint32), ("n_bases", C.c_uint32),
+                ("name_at", C.c_uint32), ("name_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FastaRun(C.Structure):
+    _fields_ = [("record", C.c_uint32), ("is_gap", C.c_uint32), ("start", C.c_uint32), ("len", C.c_uint32)]
+
+
 BGZF_OK, BGZF_BAD_DEFLATE, BGZF_BAD_CRC = 0, 1, 2
 FASTQ_OK, FASTQ_TRUNCATED, FASTQ_BAD_HEADER, FASTQ_BAD_SEPARATOR, FASTQ_BAD_LENGTHS = 0, 1, 2, 3, 4
 BAM_OK, BAM_BAD_BLOCK_SIZE, BAM_BAD_LENGTHS, BAM_FIELDS_EXCEED, BAM_NAME_NOT_NUL = 0, 1, 2, 3, 4
@@ -212,6 +221,7 @@ SYMBOLS = [
     "ts_terminal_ends", "ts_bgzf_inflate", "ts_bam_chunk_create", "ts_bam_chunk_destroy", "ts_bam_chunk_inflate",
     "ts_bam_chunk_status", "ts_bam_chunk_size", "ts_bam_chunk_read", "ts_bam_chunk_walk", "ts_bam_chunk_decode", "ts_bam_chunk_gather", "ts_bam_chunk_pass_buffer",
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
+    "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
 ]
 
 
@@ -382,6 +392,12 @@ def lib():
     L.ts_fastq_chunk_stage.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p]
     L.ts_fastq_chunk_gather.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_fasta_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.POINTER(FastaRecord), C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.ts_fasta_chunk_join.argtypes = [C.c_void_p, C.POINTER(FastaRecord), C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_fasta_chunk_runs.argtypes = [C.c_void_p, C.POINTER(FastaRun), C.c_uint64, C.POINTER(C.c_uint64)]
+    L.ts_fasta_chunk_bases.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     _lib = L
     return L
 

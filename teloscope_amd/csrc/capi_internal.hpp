@@ -378,6 +378,9 @@ struct ts_bam_chunk {
     size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status
     DevBuf d_comp, d_plain, d_blocks, d_result, d_tmp, d_recs, d_out, d_jobs, d_dst, d_gather, d_pass;
     DevBuf d_lines, d_waves, d_frames;  // the FASTQ walk's line index, per-slice newline counts and framing results (fastq.cpp)
+    // FASTA (fasta.cpp): the walk's header table, record table and names; the join's jobs, their counts, the joined bases and runs
+    DevBuf d_fa_heads, d_fa_recs, d_fa_names, d_fa_jobs, d_fa_counts, d_fa_bases, d_fa_runs, d_fa_out;
+    uint64_t fa_joined = 0, fa_runs = 0;          // bytes of the last join, its runs
 };
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
 int  ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry);

@@ -1,0 +1,45 @@
+// fasta_internal.h — what fasta.cpp (host glue) and fasta.hip (kernels) of the device FASTA route share: the launchers and
+// the layouts both sides count with.  The line index underneath is the FASTQ route's, through its launchers as they are
+// (fastq_internal.h: ts_k_launch_fastq_count / _index); nothing of fastq.hip changes.
+#pragma once
+
+#include <stdint.h>
+
+constexpr uint32_t kFastaSliceLines = 2048;         // lines a wave of the header scan takes
+constexpr uint32_t kFastaSliceBytes = 16384;        // bytes of body text (join) or of joined bases (runs) a wave takes
+// words of the FASTA result block (unsigned long long each)
+enum { kFaHeaders = 0, kFaCrs, kFaNameBytes, kFaLastLine, kFaTotal, kFaRunTotal, kFaWords };
+struct FastaFrame { uint32_t headers, crs, name_bytes, pad; };       // a slice of lines: its header lines, its lines that end in "\r\n",
+                                                                      // the bytes of its headers' names; after the scan: those before it
+struct FastaHead { uint32_t line, crs_before, names_before, pad; };  // a header line: its index, the "\r\n" lines and name bytes before it
+// body text [a, z) of the chunk, a piece of one record that lies inside one 16 KB slice: its kept bytes go to
+// dst_rec + (kept bytes of the record's jobs before this one), and never to or beyond limit; the record's last job also
+// zeroes the bytes from limit to the next multiple of 16, where the next record begins
+struct FastaJoinJob { uint32_t a, z, first, last; unsigned long long dst_rec, limit; };
+// joined bases [a, z) of one record, which begins at rec_begin (a multiple of 16), inside one 16 KB slice of the joined buffer
+struct FastaRunJob { unsigned long long a, z, rec_begin; uint32_t rec, pad; };
+
+extern "C" {
+// header lines, "\r\n" lines and name bytes per slice of kFastaSliceLines -> frames; then (one wave) frames -> exclusive sums in
+// place, out[kFaHeaders / kFaCrs / kFaNameBytes] = the totals, out[kFaLastLine] = lstart[newlines]
+int ts_k_launch_fasta_frames(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                             uint32_t newlines, void *frames, unsigned long long *out, void *stream);
+// heads[r] for every header line in order, and the sentinel heads[n_heads] = {n_lines, all crs, all name bytes}
+int ts_k_launch_fasta_heads(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                            const void *frames, void *heads, uint32_t n_heads, uint32_t crs, uint32_t name_bytes, void *stream);
+// the record table from the heads (a lane per record), then the names gathered (a wave per record)
+int ts_k_launch_fasta_records(const void *plain, unsigned long long size, const uint32_t *lstart, const unsigned char *cr,
+                              const void *heads, uint32_t n_heads, void *recs, void *names, void *stream);
+// kept bytes per join job -> counts[n_jobs]
+int ts_k_launch_fasta_join_count(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
+                                 uint32_t *counts, void *stream);
+// counts[n] -> exclusive sums in place (one wave), *total = their sum
+int ts_k_launch_fasta_scan(uint32_t *counts, uint32_t n, unsigned long long *total, void *stream);
+int ts_k_launch_fasta_join_write(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
+                                 const uint32_t *sums, void *joined, void *stream);
+// run starts per run job -> counts[n_jobs]; after the scan, the runs' {record, is_gap, start}; then every run's length
+int ts_k_launch_fasta_run_count(const void *joined, const void *jobs, uint32_t n_jobs, uint32_t *counts, void *stream);
+int ts_k_launch_fasta_run_write(const void *joined, const void *jobs, uint32_t n_jobs, const uint32_t *sums, void *runs,
+                                unsigned long long n_runs, void *stream);
+int ts_k_launch_fasta_run_lengths(void *runs, unsigned long long n_runs, const void *recs, uint32_t n_recs, void *stream);
+}

@@ -125,7 +125,9 @@ extern "C" int ts_scan_segments_multi(ts_ctx *const *ctxs, size_t n_ctx, const t
         std::memset(&out[i], 0, sizeof out[i]);
         if (counts) counts[i] = ts_segment_counts{0, 0, 0, 0};
         if (segs[i].len && !segs[i].seq) return c0->fail(TS_ERR_INVALID_ARG, "null sequence pointer");
-        if (segs[i].input_format > TS_INPUT_PACKED2) return c0->fail(TS_ERR_INVALID_ARG, "unknown input_format");
+        if (segs[i].input_format == TS_INPUT_DEVICE)
+            return c0->fail(TS_ERR_INVALID_ARG, "ts_scan_segments_multi: TS_INPUT_DEVICE segments lie in one device's memory; scan them through that device's context (ts_scan_segments, ts_scan_segments_blocks)");
+        if (segs[i].input_format > TS_INPUT_DEVICE) return c0->fail(TS_ERR_INVALID_ARG, "unknown input_format");
     }
     if (!n_segs) return TS_OK;
     for (size_t i = 0; i < n_ctx; ++i)

@@ -84,7 +84,8 @@ private:
 
 enum class Mode { Matches, Blocks, ReadPass, Ends };   // Ends: ts_terminal_ends, 8 bytes per segment back
 
-struct Item { const char *seq; uint64_t len, abs_pos; uint8_t format; uint32_t n_pieces; };     // format: TS_INPUT_BASES / TS_INPUT_TEXT_PIECES (seq = ts_text_piece[])
+struct Item { const char *seq; uint64_t len, abs_pos; uint8_t format; uint32_t n_pieces; };     // format: TS_INPUT_BASES / TS_INPUT_TEXT_PIECES (seq = ts_text_piece[]) /
+                                                                                                // TS_INPUT_PACKED2 (seq = ts_packed_seq) / TS_INPUT_DEVICE (seq = device memory)
 
 // Where a call's results go, at the items' indices; null = not asked for.  out: Matches / Blocks; counts: Blocks (optional);
 // pass: ReadPass; ends: Ends (two per item).
@@ -128,7 +129,8 @@ int ensure_streams(ts_ctx *c) {
 
 struct UpPiece { uint64_t off; const char *src; uint64_t len; uint64_t text_len;     // off: byte offset in the input layout; len: bases;
                                                                                      // text_len != 0: src is FASTA text (line ends to skip)
-                 const ts_packed_seq *packed = nullptr; uint64_t packed_first = 0; };  // packed: the bases are codes [packed_first, + len) of *packed
+                 const ts_packed_seq *packed = nullptr; uint64_t packed_first = 0;     // packed: the bases are codes [packed_first, + len) of *packed
+                 bool device = false; };                                               // device: src is memory of the context's device (TS_INPUT_DEVICE)
 
 // the bases of a run of FASTA body text, without its line ends ('\n', and a '\r' right before one or at the very end)
 bool strip_copy(char *dst, const char *text, uint64_t text_len, uint64_t n_bases) {
@@ -243,6 +245,9 @@ constexpr uint32_t kPackRunCap = 1u << 18;                 // invalid runs a pac
 // stream fills pinned memory at ~10 GB/s, a fraction of what the link moves; one copy per read would cost ~10 us each,
 // one pageable 3 GB copy ~0.5 s).  Pieces far apart (the two terminal regions of a long contig in tips-only mode) go
 // separately.  Bytes between pieces are never read as bases (the kernels mask everything past a region's end).
+// Pieces that already lie on the device (TS_INPUT_DEVICE) take no part in any of this: no pinned slot, no host thread — one
+// device-to-device copy each on up_stream, queued BEHIND the host pieces' chunks (a chunk's DMA or unpack kernel also writes the
+// padding between its pieces, where a device piece may lie; the stream's order makes the device piece's bytes the last written).
 // Asynchronous: the DMAs are queued on up_stream.  `pieces` ascend by offset and do not overlap.
 int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, uint64_t lo_all, int &slot, bool used[]) {
     constexpr uint64_t kChunk = 32u << 20, kMaxGap = 64u << 10;
@@ -250,8 +255,11 @@ int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, u
     std::vector<UpPiece> pieces;
     pieces.reserve(pieces_in.size());
     bool any_text = false, any_packed = false;
+    std::vector<UpPiece> on_device;
     for (const UpPiece &pc : pieces_in) {
-        if (pc.text_len) {
+        if (pc.device) {
+            on_device.push_back(pc);
+        } else if (pc.text_len) {
             if (pc.len > kChunk) return c->fail(TS_ERR_INVALID_ARG, "a text piece holds more than 32 MiB of bases");
             pieces.push_back(pc);
             any_text = true;
@@ -551,11 +559,13 @@ int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, u
         i = j;
     }
     if (bad_text.load()) return c->fail(TS_ERR_INVALID_ARG, "a text piece holds fewer bases than it declares");
+    for (const UpPiece &pc : on_device)
+        HIP_TRY(c, hipMemcpyAsync((char *)din + (pc.off - lo_all), pc.src, pc.len, hipMemcpyDeviceToDevice, c->up_stream));
     return TS_OK;
 }
 
 // The upload pieces of one scanned region of an item: its bases [rg_start, rg_start + rg_len), whose first lies at byte
-// layout_off of the input layout, clipped to the layout range [lo, hi) the caller uploads — from whichever of the three
+// layout_off of the input layout, clipped to the layout range [lo, hi) the caller uploads — from whichever of the four
 // input formats the item arrived in.
 int region_pieces(ts_ctx *c, const Item &it, uint64_t seg_len, uint64_t rg_start, uint64_t rg_len, uint64_t layout_off,
                   uint64_t lo, uint64_t hi, std::vector<UpPiece> &pieces) {
@@ -593,7 +603,11 @@ int region_pieces(ts_ctx *c, const Item &it, uint64_t seg_len, uint64_t rg_start
         }
         return TS_OK;
     }
-    if (s1 > s0) pieces.push_back({s0, it.seq + rg_start + (s0 - layout_off), s1 - s0, 0});
+    if (s1 > s0) {
+        UpPiece pc{s0, it.seq + rg_start + (s0 - layout_off), s1 - s0, 0};
+        pc.device = it.format == TS_INPUT_DEVICE;                 // (the same bytes, already in HBM: copied there, never read here)
+        pieces.push_back(pc);
+    }
     return TS_OK;
 }
 
@@ -1480,7 +1494,7 @@ int check_segments(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, Output
         if (o.ends) o.ends[2 * i] = o.ends[2 * i + 1] = 0u;
         if (tips_only && !segs[i].tips_only) return ctx->fail(TS_ERR_INVALID_ARG, "ts_terminal_ends: every segment must be tips_only");
         if (segs[i].len && !segs[i].seq) return ctx->fail(TS_ERR_INVALID_ARG, "null sequence pointer");
-        if (segs[i].input_format > TS_INPUT_PACKED2) return ctx->fail(TS_ERR_INVALID_ARG, "unknown input_format");
+        if (segs[i].input_format > TS_INPUT_DEVICE) return ctx->fail(TS_ERR_INVALID_ARG, "unknown input_format");
     }
     return TS_OK;
 }
