@@ -791,6 +791,62 @@ int ts_fasta_chunk_runs(ts_chunk *chunk, ts_fasta_run *runs, uint64_t cap, uint6
 /* joined[off, off + n) of the last join to host memory (tests; the match sequences of -m).  Waits for the device. */
 int ts_fasta_chunk_bases(ts_chunk *chunk, uint64_t off, uint64_t n, void *host);
 
+/* ---- GFA text in the same resident chunk: the device form of the graph front end (include/teloscope_mi355x_gfa.hpp:
+ *      annotateGfaDevice).  Replaces the line loop of the reference's GFA load (src/input.cpp:625-716): which lines are S, P
+ *      and H records and where an S line's first four tabs lie.  The text reaches the chunk as for FASTQ (ts_chunk_upload,
+ *      ts_bam_chunk_inflate); lines and tabs are indexed on the device, and what comes back is one table entry per segment, one
+ *      per P / H line, and the segments' names and those lines in one buffer.  The sequences stay in HBM and are scanned where
+ *      they lie (TS_INPUT_DEVICE segments at ts_chunk_data + off + f2_at).
+ *      The rules, which are readGfa's (include/teloscope_mi355x_gfa.hpp):
+ *        line      starts at byte 0 of the input or right behind a '\n'; its content excludes the '\n' and one '\r' that is its
+ *                  last byte, also when the input's last line has no '\n'.  A line with empty content is nothing.
+ *        single    content length 1, or second byte '\t'; the type is the first byte.
+ *        segment   a single S line whose content, cut at its first four tabs (at most five fields, the fifth is the rest), has
+ *                  three fields or more.  Which field is the sequence is the caller's decision (the graph's version).
+ *        P / H     every single P and every single H line, whole; the caller cuts their fields.
+ *        foreign   a line with content whose type is not '#' and that is not a single H or S (so P, L, W ... lines are);
+ *                  the lowest one of the chunk is reported by its offset and first field (up to the first tab or the content's
+ *                  end): a GFA 2 input may hold none. */
+typedef struct ts_gfa_segment {
+    uint64_t off;                /* of the S line's first byte in the chunk */
+    uint32_t len;                /* of its content */
+    uint32_t n_fields;           /* 3..5 */
+    uint32_t f1_at, f1_len;      /* fields 1, 2 and 3, relative to off */
+    uint32_t f2_at, f2_len;
+    uint32_t f3_at, f3_len;      /* 0, 0 when n_fields == 3 */
+    uint32_t name_at;            /* where field 1 (f1_len bytes) lies in `text` */
+    uint32_t star;               /* bit 0: field 2 is exactly "*"; bit 1: field 3 is */
+} ts_gfa_segment;
+typedef struct ts_gfa_line {
+    uint64_t off;                /* of the line's first byte in the chunk */
+    uint32_t len;                /* of its content */
+    uint32_t kind;               /* 'P' or 'H' */
+    uint32_t text_at;            /* where the content lies in `text` */
+    uint32_t reserved;
+} ts_gfa_line;
+typedef struct ts_gfa_foreign {
+    uint64_t off;                /* of the lowest foreign line's first byte in the chunk */
+    uint32_t len;                /* of its first field */
+    uint32_t found;              /* 0: the chunk's whole lines hold no foreign line */
+} ts_gfa_foreign;
+/* Lines, tabs and records of the whole chunk (at most 4 GiB - 2 bytes), which starts at a line's first byte.  The segments of
+ * its whole lines in input order to segs, its P / H lines in input order to lines, the segments' names and those lines,
+ * gathered on the device in input order, to text in ONE copy.  When *n_segs > seg_cap, *n_lines > line_cap or *text_bytes >
+ * text_cap nothing is copied and the call answers TS_ERR_INVALID_ARG (call again with room for what the three say).  *next =
+ * the first byte of the unfinished last line (the carry; the chunk's size when it ends in '\n'); with at_end != 0 the input ends
+ * with the chunk, its last line may lack the '\n' and *next = size.  The chunk's bytes are not changed.  Waits for the device. */
+int ts_gfa_chunk_walk(ts_chunk *chunk, int at_end, ts_gfa_segment *segs, uint64_t seg_cap, uint64_t *n_segs, ts_gfa_line *lines,
+                      uint64_t line_cap, uint64_t *n_lines, char *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *next,
+                      ts_gfa_foreign *foreign);
+/* The device address of the chunk's first byte (valid until the chunk grows, is refilled or destroyed): what a TS_INPUT_DEVICE
+ * segment that lies in the chunk is addressed from. */
+const void *ts_chunk_data(const ts_chunk *chunk);
+/* The tail [carry_from, size) of `from` becomes the whole contents of `to` (another chunk of the same context, which grows when
+ * it must), device to device; `from` keeps every byte.  A following ts_chunk_upload(to, ..., 0, ...) or ts_bam_chunk_inflate(to,
+ * ..., 0, ...) appends behind the carried bytes: how an unfinished line moves on while the chunk it began in stays resident.
+ * Ordered on `stream`; waits for it. */
+int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

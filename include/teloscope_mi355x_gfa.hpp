@@ -9,6 +9,9 @@
 // or annotateGfa(teloscope, file, outDir) for all four.  The device reduces a segment to {longest terminal block at its start
 // side, at its end side} (ts_terminal_ends): 8 bytes per segment, whatever the number of blocks.
 //
+// annotateGfaDevice(teloscope, file, outDir) is the device route of the same (not the default): the text lies in device memory,
+// lines and tabs are indexed there (ts_gfa_chunk_walk) and the segments are scanned where they lie; see its comment below.
+//
 // Input lines are written back verbatim (line ends as read) with two exceptions: the header says VN:Z:1.2 (added when the input
 // has none, replacing a VN:Z:2.0), and a GFA 2 segment `S name len seq [tags]` loses its length field.  Other GFA 2 records are
 // refused.  GFA 1.1 W lines are copied through and are not read as paths.
@@ -28,7 +31,9 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -119,6 +124,20 @@ inline void gfaFields(const char *base, const char *b, const char *e, std::vecto
     f.push_back({static_cast<size_t>(p - base), static_cast<size_t>(e - p)});
 }
 
+// a P line's name and components from its fields (three or four of them)
+inline GfaPath gfaCutPath(const char *base, const std::vector<GfaField> &f) {
+    GfaPath p;
+    p.name.assign(base + f[1].off, f[1].len);
+    const char *c = base + f[2].off, *ce = c + f[2].len;
+    while (c < ce) {
+        const char *d = c;
+        while (d < ce && *d != ',' && *d != ';') ++d;
+        if (d - c >= 2) p.comps.emplace_back(std::string(c, static_cast<size_t>(d - c - 1)), d[-1]);
+        c = d + 1;
+    }
+    return p;
+}
+
 // what a chunk of lines holds (parsed side by side, joined in input order)
 struct GfaChunk {
     struct S { size_t line, lineEnd, f1, f1len, f2, f2len, f3, f3len; bool has3; };   // offsets into data
@@ -172,18 +191,7 @@ inline GfaGraph readGfa(const std::string &file) {
                                            f.size() >= 4 ? f[3].len : 0, f.size() >= 4});
                 } else if (type == 'P' && single) {
                     detail::gfaFields(base, b, e, f, 4);
-                    if (f.size() >= 3) {
-                        GfaPath p;
-                        p.name.assign(base + f[1].off, f[1].len);
-                        const char *c = base + f[2].off, *ce = c + f[2].len;
-                        while (c < ce) {
-                            const char *d = c;
-                            while (d < ce && *d != ',' && *d != ';') ++d;
-                            if (d - c >= 2) p.comps.emplace_back(std::string(c, static_cast<size_t>(d - c - 1)), d[-1]);
-                            c = d + 1;
-                        }
-                        ch.paths.push_back(std::move(p));
-                    }
+                    if (f.size() >= 3) ch.paths.push_back(detail::gfaCutPath(base, f));
                 } else if (type == 'H' && single) {
                     detail::gfaFields(base, b, e, f, size_t(-1));
                     for (size_t i = 1; i < f.size(); ++i)
@@ -265,7 +273,9 @@ inline std::vector<GfaEnd> gfaTerminalJobs(const GfaGraph &g, const std::vector<
 // The distinct segments with a sequence that the ends use, in one Teloscope::terminalEnds call (each segment once, scanned
 // where it lies in the input buffer; the library folds case as unmaskSequence does).  Warns on `log` about ends whose
 // segment has no sequence, in the reference's words.
-inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::vector<GfaEnd> &jobs, std::ostream &log = std::cerr) {
+// onDevice: every GfaSegment::seq is an address in the first context's device memory (annotateGfaDevice), scanned from there.
+inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::vector<GfaEnd> &jobs, std::ostream &log = std::cerr,
+                           bool onDevice = false) {
     GfaEnds r;
     r.ends.assign(g.segments.size(), {0u, 0u});
     std::vector<char> want(g.segments.size(), 0);
@@ -279,7 +289,11 @@ inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::v
     std::vector<uint32_t> which;
     std::vector<Teloscope::Segment> segs;
     for (uint32_t i = 0; i < g.segments.size(); ++i)
-        if (want[i]) { which.push_back(i); segs.emplace_back(g.segments[i].seq, g.segments[i].len, 0, true); }
+        if (want[i]) {
+            which.push_back(i);
+            segs.emplace_back(onDevice ? nullptr : g.segments[i].seq, g.segments[i].len, 0, true);
+            if (onDevice) segs.back().device = g.segments[i].seq;
+        }
     r.scanned = which.size();
     if (segs.empty()) return r;
     const std::vector<std::pair<uint32_t, uint32_t>> e = teloscope.terminalEnds(segs);
@@ -287,11 +301,20 @@ inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::v
     return r;
 }
 
+// The input's bytes as the writer sees them: total of them, the last one, and a function that writes bytes [off, off + len) to
+// the output.  writeAnnotatedGfa reads GfaGraph::data; annotateGfaDevice hands over the pieces the text arrived in.
+struct GfaInputBytes {
+    size_t size = 0;
+    char last = 0;                                          // (size > 0)
+    std::function<void(std::ostream &, size_t off, size_t len)> write;
+};
+
 // Writes the annotated graph and its colours file; returns the number of telomere nodes.  ends: per graph segment (GfaEnds).
 // Node rules of walkSegment / walkSegmentForPath (src/input.cpp:835-939): a path end keeps the block on the physical side
 // isFirst == (orient == '+'), edge orientation orient at a start, its flip at an end; a pathless segment gets a node per side
-// that has a block, '+' in the name, edge '+' at the start and '-' at the end.
-inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jobs,
+// that has a block, '+' in the name, edge '+' at the start and '-' at the end.  input: where the input's bytes come from (the form
+// without it reads g.data).
+inline size_t writeAnnotatedGfa(const GfaGraph &g, const GfaInputBytes &input, const std::vector<GfaEnd> &jobs,
                                 const std::vector<std::pair<uint32_t, uint32_t>> &ends,
                                 const std::string &outGfa, const std::string &outColors) {
     struct Node { std::string name; uint32_t seg, len; char edge; };
@@ -315,12 +338,12 @@ inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jo
     if (!g.hasVersion) out << "H\tVN:Z:1.2\n";
     size_t at = 0;
     for (const GfaEdit &ed : g.edits) {
-        out.write(g.data.data() + at, static_cast<std::streamsize>(ed.off - at));
+        input.write(out, at, ed.off - at);
         out << ed.text;
         at = ed.off + ed.len;
     }
-    out.write(g.data.data() + at, static_cast<std::streamsize>(g.data.size() - at));
-    if (!g.data.empty() && g.data.back() != '\n') out << '\n';
+    input.write(out, at, input.size - at);
+    if (input.size && input.last != '\n') out << '\n';
     std::string tail;
     for (const Node &nd : nodes) {
         tail += "S\t" + nd.name + "\t*\tLN:i:6\tRC:i:6000\tTL:i:" + std::to_string(nd.len) + "\n";
@@ -336,6 +359,16 @@ inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jo
     colors.close();
     if (!colors) throw std::runtime_error("could not write " + outColors);
     return nodes.size();
+}
+
+inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jobs,
+                                const std::vector<std::pair<uint32_t, uint32_t>> &ends,
+                                const std::string &outGfa, const std::string &outColors) {
+    GfaInputBytes input;
+    input.size = g.data.size();
+    input.last = g.data.empty() ? 0 : g.data.back();
+    input.write = [&g](std::ostream &o, size_t off, size_t len) { o.write(g.data.data() + off, static_cast<std::streamsize>(len)); };
+    return writeAnnotatedGfa(g, input, jobs, ends, outGfa, outColors);
 }
 
 // With assembly record filters the input must be a GFA 1 graph with P paths or none (src/input.cpp:206-283): throws a
@@ -438,6 +471,327 @@ inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &fil
     const double parseMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     GfaAnnotateStats st = annotateGfa(teloscope, g, &sel, outDir, log);
     st.parseMs += parseMs;
+    return st;
+}
+
+// The device route of annotateGfa(teloscope, file, outDir, log), which stays the default: the same two output files byte for
+// byte, the same warnings on `log`, the same exceptions and the same GfaAnnotateStats, but no host thread looks for a line end
+// or a tab.  The text reaches HBM from the three sources of scanFastaToFilesDevice —
+//   1. a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
+//   2. a BGZF regular file (bgzip output): members located on the host, inflated and checksummed on the device
+//      (ts_bam_chunk_inflate); from the first member that does not parse as BGZF on, the rest of the input takes source 3;
+//   3. anything else (plain gzip, a file that cannot be mapped): through zlib in blocks, each block uploaded —
+// in chunks of ~chunkBytes bytes, and per chunk ts_gfa_chunk_walk gives the segment table, the P / H lines and the names.  Which
+// segments are scanned and which field of an S line is its sequence is known only after the last line (a P or H line may stand
+// anywhere), so every walked chunk STAYS RESIDENT; an unfinished last line moves into the next chunk device to device
+// (ts_chunk_carry_over).  After the last chunk the host builds the graph exactly as readGfa does (names, hash index, paths,
+// version, edits), gfaTerminalJobs picks the ends, and ONE terminalEnds call scans the wanted segments where they lie in the
+// chunks (TS_INPUT_DEVICE, no host view).  The writer takes the input's bytes from the mapping, from the zlib blocks as they were
+// produced, or — BGZF — from the chunks, read back piece by piece.
+// Limits: ONE device (a Teloscope over several throws); no record filters (they stay with the host route); a line of more than
+// 4 GiB - 2 bytes is refused with its byte offset; a text that does not fit the device's free memory is refused with a message
+// that names annotateGfa; the stages run one after the other.  With a GFA 2 input that holds both a foreign record and a segment
+// named twice, the foreign record is reported (readGfa reports whichever comes first by its 16 MB parse blocks).
+inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                          std::ostream &log = std::cerr, size_t chunkBytesArg = size_t(256) << 20) {
+    using Clock = std::chrono::steady_clock;
+    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto tBegin = Clock::now();
+    if (teloscope.deviceCount() > 1)
+        throw std::runtime_error("annotateGfaDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
+                                 " (the graph's text lies in one device's memory)");
+    ts_ctx *ctx = teloscope.context();
+    auto fail = [&](const char *what) -> std::runtime_error {
+        const char *why = ts_last_error(ctx);
+        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
+    };
+    constexpr uint64_t kChunkLimit = 0xfffffffeull;             // what ts_gfa_chunk_walk takes
+    const int fd = ::open(file.c_str(), O_RDONLY);
+    if (fd < 0) throw std::runtime_error("Could not open assembly input '" + file + "'.");
+    struct Closer { int fd; gzFile gz = nullptr; ~Closer() { if (gz) gzclose(gz); else ::close(fd); } } closer{fd};
+    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
+    {
+        struct stat st;
+        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
+        }
+    }
+    const unsigned char *data = static_cast<const unsigned char *>(mapping.p);
+    const size_t size = mapping.n;
+    auto bgzfMember = [](const unsigned char *p, size_t n, detail::BgzfBlockRef &ref, bool &eofm) -> size_t {
+        try { return detail::parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
+    };
+    enum { Plain, Bgzf, Stream } source = Stream;
+    if (data) {
+        detail::BgzfBlockRef ref{};
+        bool eofm = false;
+        if (size >= 2 && data[0] == 0x1f && data[1] == 0x8b) source = bgzfMember(data, size, ref, eofm) ? Bgzf : Stream;
+        else source = Plain;
+    }
+    const bool deviceInflate = source == Bgzf;
+    // (a fill of BGZF members may exceed what it was asked for by one member: the chunk stays below the walk's limit all the same)
+    const uint64_t chunkLimit = deviceInflate ? kChunkLimit - 65536 : kChunkLimit;
+    bool streamOpen = false, streamDone = false;
+    auto openStream = [&](size_t from) {
+        streamOpen = true;
+        if (from > 0) {                                         // behind BGZF members anything that is not gzip ends the input
+            if (size - from < 2 || data[from] != 0x1f || data[from + 1] != 0x8b) { streamDone = true; return; }
+            if (::lseek(fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error("Could not read assembly input '" + file + "'.");
+        }
+        closer.gz = gzdopen(fd, "rb");                          // (zlib reads plain files through the same calls)
+        if (!closer.gz) throw std::runtime_error("Could not open assembly input '" + file + "'.");
+        gzbuffer(closer.gz, 1u << 20);
+    };
+    double msUpload = 0, msIndex = 0, msGraph = 0;
+
+    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+    // (an inflate call takes members of the mapped file: never more compressed bytes than the file has)
+    const uint64_t compCap = source == Bgzf ? std::min<uint64_t>(chunkBytes + (1u << 20), std::max<size_t>(size, 64)) : 64;
+    struct ChunkFree { void operator()(ts_chunk *c) const { ts_bam_chunk_destroy(c); } };
+    std::vector<std::unique_ptr<ts_chunk, ChunkFree>> chunks;   // every one stays until the scan and the write are done
+    uint64_t resident = 0;
+    auto noRoom = [&](const char *what) -> std::runtime_error {
+        const char *why = ts_last_error(ctx);
+        return std::runtime_error(std::string("annotateGfaDevice: ") + what + " with " + std::to_string(resident) +
+                                  " bytes of the graph's text resident (" + (why ? why : "?") +
+                                  "): the text does not fit the device's free memory; use annotateGfa, the host route");
+    };
+    // the input's bytes for the writer, in the pieces they arrived in: host memory, or bytes [at, at + len) of a chunk
+    struct Piece { const char *host; ts_chunk *chunk; uint64_t at, start, len; };
+    std::vector<Piece> pieces;
+    std::vector<std::vector<char>> blocks;                      // zlib's output as it was produced
+    uint64_t total = 0;
+    // what a chunk's walk gave; base: the input offset of the chunk's first byte
+    struct Walked { ts_chunk *chunk; uint64_t base; std::vector<ts_gfa_segment> segs; std::vector<ts_gfa_line> lines; std::vector<char> text; ts_gfa_foreign foreign; };
+    std::vector<Walked> walked;
+    std::vector<ts_bgzf_block> descs;
+
+    size_t at = 0;                              // next byte of the mapped file (sources 1 and 2)
+    ts_chunk *cur = nullptr, *prev = nullptr;
+    uint64_t held = 0, prevNext = 0, base = 0;
+    bool atEnd = false, grow = false;
+    while (!atEnd) {
+        Clock::time_point t0 = Clock::now();
+        uint64_t carry = held;                                  // growing: the whole chunk is one unfinished line
+        if (!grow) carry = prev ? ts_bam_chunk_size(prev) - prevNext : 0;
+        if (carry >= chunkLimit)
+            throw std::runtime_error("the line at byte offset " + std::to_string(base) + " of '" + file + "' has more than " + std::to_string(chunkLimit) +
+                                     " bytes and does not fit a device chunk; use annotateGfa, the host route");
+        // a chunk that held no whole line takes as much again, up to what a chunk may hold
+        const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, grow ? carry : 0), chunkLimit - carry));
+        size_t got = 0;
+        if (source == Stream) {                                 // zlib's next block, kept for the writer
+            if (!streamOpen) openStream(0);
+            blocks.emplace_back(std::min<size_t>(want, size_t(4) << 20));
+            std::vector<char> &block = blocks.back();
+            while (!streamDone && got < want) {
+                if (got == block.size()) block.resize(std::min(want, 2 * block.size()));
+                const int n = gzread(closer.gz, block.data() + got, static_cast<unsigned>(std::min<size_t>(block.size() - got, size_t(1) << 30)));
+                if (n < 0) throw std::runtime_error("Could not read assembly input '" + file + "'.");
+                if (n == 0) { streamDone = true; break; }
+                got += static_cast<size_t>(n);
+            }
+            block.resize(got);
+            block.shrink_to_fit();
+        }
+        if (!grow) {
+            // room for what the fill brings: known for a mapped plain file and a block read, a guess for BGZF members (the chunk grows)
+            const uint64_t room = source == Plain ? std::min<uint64_t>(want, size - at) : source == Stream ? got
+                                                  : std::min<uint64_t>(want, 8 * static_cast<uint64_t>(size - at) + 65536);
+            ts_chunk *made = ts_bam_chunk_create(ctx, compCap, std::max<uint64_t>(carry + room, 64));
+            if (!made) throw noRoom("cannot make a device chunk");
+            chunks.emplace_back(made);
+            cur = made;
+            if (carry && ts_chunk_carry_over(cur, prev, prevNext, nullptr) != TS_OK) throw noRoom("cannot carry a line into the next device chunk");
+        }
+        if (source == Bgzf) {
+            uint64_t produced = 0;
+            bool foreignMember = false, full = false;
+            do {
+                descs.clear();
+                size_t used = 0;
+                uint64_t made = 0;
+                while (at + used < size) {
+                    detail::BgzfBlockRef ref{};
+                    bool eofm = false;
+                    const size_t totalBytes = bgzfMember(data + at + used, size - at - used, ref, eofm);
+                    if (totalBytes == 0) { foreignMember = true; break; }
+                    if (produced + made > 0 && produced + made + ref.isize > want) { full = true; break; }
+                    if (!descs.empty() && used + totalBytes > compCap) break;
+                    ts_bgzf_block d{};
+                    d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
+                    d.dst_off = carry + produced + made;
+                    descs.push_back(d);
+                    made += ref.isize;
+                    used += totalBytes;
+                }
+                if (ts_chunk_reserve(cur, carry + produced + made) != TS_OK) throw noRoom("cannot grow a device chunk");
+                if (ts_bam_chunk_inflate(cur, data + at, used, descs.data(), descs.size(), 0, nullptr) != TS_OK) throw fail("BGZF inflate failed");
+                ts_bgzf_status bad{};
+                if (ts_bam_chunk_status(cur, &bad) != TS_OK) throw fail("BGZF inflate failed");
+                if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
+                if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
+                if (made) pieces.push_back({nullptr, cur, carry + produced, total, made});
+                total += made;
+                at += used;
+                produced += made;
+            } while (!foreignMember && !full && at < size);
+            if (foreignMember) { source = Stream; openStream(at); atEnd = streamDone; }
+            else atEnd = at >= size;
+        } else if (source == Plain) {
+            const size_t n = std::min(want, size - at);
+            if (ts_chunk_upload(cur, data + at, n, 0, nullptr) != TS_OK) throw noRoom("upload of the GFA text failed");
+            at += n;
+            total += n;
+            atEnd = at >= size;
+        } else {
+            const std::vector<char> &block = blocks.back();
+            if (ts_chunk_upload(cur, block.data(), got, 0, nullptr) != TS_OK) throw noRoom("upload of the GFA text failed");
+            if (got) pieces.push_back({block.data(), nullptr, 0, total, got});
+            total += got;
+            atEnd = streamDone;
+        }
+        msUpload += since(t0);
+        resident += ts_bam_chunk_size(cur) - held * (grow ? 1 : 0);
+        held = ts_bam_chunk_size(cur);
+        if (held == 0) continue;
+
+        // segments, P / H lines and names
+        t0 = Clock::now();
+        Walked w;
+        w.chunk = cur; w.base = base;
+        w.segs.resize(4096); w.lines.resize(256); w.text.resize(size_t(1) << 16);
+        uint64_t nSegs = 0, nLines = 0, textBytes = 0, next = 0;
+        int rc = ts_gfa_chunk_walk(cur, atEnd ? 1 : 0, w.segs.data(), w.segs.size(), &nSegs, w.lines.data(), w.lines.size(), &nLines,
+                                   w.text.data(), w.text.size(), &textBytes, &next, &w.foreign);
+        if (rc == TS_ERR_INVALID_ARG && (nSegs > w.segs.size() || nLines > w.lines.size() || textBytes > w.text.size())) {
+            w.segs.resize(static_cast<size_t>(std::max<uint64_t>(nSegs, 1)));
+            w.lines.resize(static_cast<size_t>(std::max<uint64_t>(nLines, 1)));
+            w.text.resize(static_cast<size_t>(std::max<uint64_t>(textBytes, 1)));
+            rc = ts_gfa_chunk_walk(cur, atEnd ? 1 : 0, w.segs.data(), w.segs.size(), &nSegs, w.lines.data(), w.lines.size(), &nLines,
+                                   w.text.data(), w.text.size(), &textBytes, &next, &w.foreign);
+        }
+        if (rc != TS_OK) throw fail("GFA walk failed");
+        msIndex += since(t0);
+        if (!atEnd && next == 0) { grow = true; continue; }     // no whole line yet: the chunk takes more
+        grow = false;
+        w.segs.resize(static_cast<size_t>(nSegs)); w.lines.resize(static_cast<size_t>(nLines)); w.text.resize(static_cast<size_t>(textBytes));
+        w.segs.shrink_to_fit(); w.lines.shrink_to_fit(); w.text.shrink_to_fit();
+        walked.push_back(std::move(w));
+        prev = cur; prevNext = next; base += next;
+    }
+    if (source == Plain && size) pieces.assign(1, Piece{reinterpret_cast<const char *>(data), nullptr, 0, 0, size});
+
+    // the graph, as readGfa builds it
+    Clock::time_point t0 = Clock::now();
+    GfaGraph g;
+    g.file = file;
+    const size_t slash = file.find_last_of('/');
+    g.baseName = slash == std::string::npos ? file : file.substr(slash + 1);
+    std::vector<detail::GfaField> f;
+    std::vector<std::pair<size_t, size_t>> headers;             // H lines carrying VN:Z (once per such field): input offset, length
+    std::vector<char> headerIsV2;
+    size_t nseg = 0;
+    for (const Walked &w : walked) {
+        nseg += w.segs.size();
+        for (const ts_gfa_line &l : w.lines) {
+            const char *b = w.text.data() + l.text_at, *e = b + l.len;
+            if (l.kind == 'P') {
+                detail::gfaFields(b, b, e, f, 4);
+                if (f.size() >= 3) g.paths.push_back(detail::gfaCutPath(b, f));
+            } else {
+                detail::gfaFields(b, b, e, f, size_t(-1));
+                for (size_t i = 1; i < f.size(); ++i)
+                    if (f[i].len >= 5 && std::memcmp(b + f[i].off, "VN:Z:", 5) == 0) {
+                        headers.emplace_back(static_cast<size_t>(w.base + l.off), l.len);
+                        headerIsV2.push_back(std::string(b, l.len).find("VN:Z:2") != std::string::npos);
+                        g.hasVersion = true;
+                        g.version = (f[i].len > 5 && b[f[i].off + 5] == '2') ? 2 : 1;
+                    }
+            }
+        }
+    }
+    if (g.version == 2)
+        for (const Walked &w : walked)
+            if (w.foreign.found) {
+                std::string type(w.foreign.len, '\0');
+                if (w.foreign.len && ts_bam_chunk_read(w.chunk, w.foreign.off, w.foreign.len, &type[0]) != TS_OK) throw fail("cannot read the chunk");
+                throw std::runtime_error("GFA 2 record type '" + type + "' in '" + file +
+                                         "' is not supported: only H and S records of a GFA 2 graph are read.");
+            }
+    for (size_t i = 0; i < headers.size(); ++i)
+        if (headerIsV2[i]) g.edits.push_back({headers[i].first, headers[i].second, "H\tVN:Z:1.2"});
+    g.segments.reserve(nseg);
+    g.index.reserve(nseg);
+    for (const Walked &w : walked) {
+        const char *dev = static_cast<const char *>(ts_chunk_data(w.chunk));
+        for (const ts_gfa_segment &s : w.segs) {
+            GfaSegment seg;
+            seg.name.assign(w.text.data() + s.name_at, s.f1_len);
+            uint64_t so = s.f2_at, sl = s.f2_len;
+            bool star = (s.star & 1u) != 0;
+            if (g.version == 2 && s.n_fields >= 4) {                 // S name len seq [tags]: the length goes
+                so = s.f3_at; sl = s.f3_len; star = (s.star & 2u) != 0;
+                g.edits.push_back({static_cast<size_t>(w.base + s.off + s.f2_at), s.f3_at - s.f2_at, std::string()});
+            }
+            if (!star) { seg.seq = dev + s.off + so; seg.len = sl; }   // (a device address: gfaScanEnds(..., onDevice))
+            if (!g.index.emplace(seg.name, static_cast<uint32_t>(g.segments.size())).second)
+                throw std::runtime_error("segment '" + seg.name + "' is defined twice in '" + file + "'.");
+            g.segments.push_back(std::move(seg));
+        }
+    }
+    std::sort(g.edits.begin(), g.edits.end(), [](const GfaEdit &a, const GfaEdit &b) { return a.off < b.off; });
+    msGraph = since(t0);
+
+    GfaAnnotateStats st;
+    st.parseMs = since(tBegin);
+    const auto t1 = Clock::now();
+    const std::vector<GfaEnd> jobs = gfaTerminalJobs(g);
+    const GfaEnds e = gfaScanEnds(teloscope, g, jobs, log, true);
+    const auto t2 = Clock::now();
+
+    // the input's bytes: host pieces as they lie, chunk pieces read back through a bounce buffer
+    GfaInputBytes input;
+    input.size = static_cast<size_t>(total);
+    std::vector<char> bounce;
+    auto readPiece = [&](const Piece &p, uint64_t off, uint64_t n, char *dst) {
+        if (ts_bam_chunk_read(p.chunk, p.at + off, n, dst) != TS_OK) throw fail("cannot read the chunk");
+    };
+    if (total) {
+        const Piece &p = pieces.back();
+        if (p.host) input.last = p.host[p.len - 1]; else readPiece(p, p.len - 1, 1, &input.last);
+    }
+    input.write = [&](std::ostream &o, size_t off, size_t len) {
+        size_t k = static_cast<size_t>(std::upper_bound(pieces.begin(), pieces.end(), off, [](size_t v, const Piece &p) { return v < p.start; }) - pieces.begin());
+        k = k ? k - 1 : 0;
+        for (; len && k < pieces.size(); ++k) {
+            const Piece &p = pieces[k];
+            if (off >= p.start + p.len) continue;
+            uint64_t in = off - p.start, n = std::min<uint64_t>(len, p.len - in);
+            off += n; len -= n;
+            if (p.host) { o.write(p.host + in, static_cast<std::streamsize>(n)); continue; }
+            for (; n;) {
+                const uint64_t step = std::min<uint64_t>(n, uint64_t(16) << 20);
+                bounce.resize(static_cast<size_t>(std::max<uint64_t>(bounce.size(), step)));
+                readPiece(p, in, step, bounce.data());
+                o.write(bounce.data(), static_cast<std::streamsize>(step));
+                in += step; n -= step;
+            }
+        }
+    };
+    const std::string stem = outDir + "/" + g.baseName + ".telo.annotated";
+    st.nodes = writeAnnotatedGfa(g, input, jobs, e.ends, stem + ".gfa", stem + ".colors.csv");
+    const auto t3 = Clock::now();
+    st.segments = g.segments.size();
+    st.ends = jobs.size();
+    st.scanned = e.scanned;
+    st.noSeq = e.noSeq;
+    st.scanMs = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    st.writeMs = std::chrono::duration<double, std::milli>(t3 - t2).count();
+    if (std::getenv("TS_TIMING"))
+        std::fprintf(stderr, "annotateGfaDevice: upload%s %.0f ms, index %.0f ms, graph (host) %.0f ms, scan %.0f ms, write %.0f ms\n",
+                     deviceInflate ? " + inflate + CRC" : "", msUpload, msIndex, msGraph, st.scanMs, st.writeMs);
     return st;
 }
 

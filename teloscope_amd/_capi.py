@@ -191,6 +191,20 @@ class FastaRun(C.Structure):
     _fields_ = [("record", C.c_uint32), ("is_gap", C.c_uint32), ("start", C.c_uint32), ("len", C.c_uint32)]
 
 
+class GfaSegment(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("n_fields", C.c_uint32), ("f1_at", C.c_uint32), ("f1_len", C.c_uint32),
+                ("f2_at", C.c_uint32), ("f2_len", C.c_uint32), ("f3_at", C.c_uint32), ("f3_len", C.c_uint32),
+                ("name_at", C.c_uint32), ("star", C.c_uint32)]
+
+
+class GfaLine(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("kind", C.c_uint32), ("text_at", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GfaForeign(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("found", C.c_uint32)]
+
+
 BGZF_OK, BGZF_BAD_DEFLATE, BGZF_BAD_CRC = 0, 1, 2
 FASTQ_OK, FASTQ_TRUNCATED, FASTQ_BAD_HEADER, FASTQ_BAD_SEPARATOR, FASTQ_BAD_LENGTHS = 0, 1, 2, 3, 4
 BAM_OK, BAM_BAD_BLOCK_SIZE, BAM_BAD_LENGTHS, BAM_FIELDS_EXCEED, BAM_NAME_NOT_NUL = 0, 1, 2, 3, 4
@@ -222,6 +236,7 @@ SYMBOLS = [
     "ts_bam_chunk_status", "ts_bam_chunk_size", "ts_bam_chunk_read", "ts_bam_chunk_walk", "ts_bam_chunk_decode", "ts_bam_chunk_gather", "ts_bam_chunk_pass_buffer",
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
+    "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over",
 ]
 
 
@@ -398,6 +413,12 @@ def lib():
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     L.ts_fasta_chunk_runs.argtypes = [C.c_void_p, C.POINTER(FastaRun), C.c_uint64, C.POINTER(C.c_uint64)]
     L.ts_fasta_chunk_bases.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.ts_gfa_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.POINTER(GfaSegment), C.c_uint64, C.POINTER(C.c_uint64),
+                                    C.POINTER(GfaLine), C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(GfaForeign)]
+    L.ts_chunk_data.argtypes = [C.c_void_p]
+    L.ts_chunk_data.restype = C.c_void_p
+    L.ts_chunk_carry_over.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = L
     return L
 

@@ -381,6 +381,9 @@ struct ts_bam_chunk {
     // FASTA (fasta.cpp): the walk's header table, record table and names; the join's jobs, their counts, the joined bases and runs
     DevBuf d_fa_heads, d_fa_recs, d_fa_names, d_fa_jobs, d_fa_counts, d_fa_bases, d_fa_runs, d_fa_out;
     uint64_t fa_joined = 0, fa_runs = 0;          // bytes of the last join, its runs
+    // GFA (gfa.cpp): the tab counts per slice and the tabs' offsets, the lines' kind bytes and their per-slice counts, the two
+    // tables and the gathered text
+    DevBuf d_gfa_counts, d_gfa_tabs, d_gfa_kinds, d_gfa_frames, d_gfa_segs, d_gfa_lines, d_gfa_text, d_gfa_out;
 };
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
 int  ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry);

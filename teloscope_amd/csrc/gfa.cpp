@@ -1,0 +1,116 @@
+// gfa.cpp — host side of the device GFA stages (include/teloscan.h: ts_gfa_chunk_walk, ts_chunk_data, ts_chunk_carry_over):
+// argument checks, buffer sizes, launches and the few words that come back.  The chunk is bgzf.cpp's ts_bam_chunk, its line index
+// fastq.hip's; nothing here parses a byte of text.
+#include "capi_internal.hpp"
+#include "fasta_internal.h"
+#include "fastq_internal.h"
+#include "gfa_internal.h"
+
+namespace {
+
+static_assert(sizeof(ts_gfa_segment) == 48 && sizeof(ts_gfa_line) == 24 && sizeof(ts_gfa_foreign) == 16 && sizeof(GfaFrame) == 16, "layouts");
+static_assert(kGfWords * sizeof(unsigned long long) <= 64, "the result block has 64 bytes");
+
+}  // namespace
+
+extern "C" {
+
+const void *ts_chunk_data(const ts_chunk *ch) { return ch ? ch->d_plain.p : nullptr; }
+
+int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void *stream) {
+    if (!to) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = to->ctx;
+    if (!from || from == to || from->ctx != ctx || carry_from > from->plain_n)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_carry_over: needs two chunks of one context and an offset inside the source");
+    const uint64_t n = from->plain_n - carry_from;
+    to->plain_n = 0;                                           // (what the destination held is dropped, not kept by a growth)
+    to->n_blocks = 0;
+    if (n > to->plain_cap) { const int rc = ts_chunk_reserve(to, n); if (rc != TS_OK) return rc; }
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(to->d_plain.p, (const char *)from->d_plain.p + carry_from, (size_t)n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    to->plain_n = n;
+    return TS_OK;
+}
+
+int ts_gfa_chunk_walk(ts_chunk *ch, int at_end, ts_gfa_segment *segs, uint64_t seg_cap, uint64_t *n_segs, ts_gfa_line *lines,
+                      uint64_t line_cap, uint64_t *n_lines_out, char *text, uint64_t text_cap, uint64_t *text_bytes, uint64_t *next,
+                      ts_gfa_foreign *foreign) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!n_segs || !n_lines_out || !text_bytes || !next || !foreign || (seg_cap && !segs) || (line_cap && !lines) || (text_cap && !text) ||
+        seg_cap > (1ull << 31) || line_cap > (1ull << 31))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_gfa_chunk_walk: null or out-of-range argument");
+    if (ch->plain_n >= 0xffffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_gfa_chunk_walk: the chunk holds 4 GiB or more");
+    *n_segs = 0; *n_lines_out = 0; *text_bytes = 0; *next = 0;
+    foreign->off = 0; foreign->len = 0; foreign->found = 0;
+    const uint64_t size = ch->plain_n;
+    if (size == 0) return TS_OK;
+    DEVICE_TRY(ctx);
+    HIP_TRY(ctx, ch->d_gfa_out.ensure(64));
+    unsigned long long *d_out = (unsigned long long *)ch->d_gfa_out.p;
+    unsigned long long out[kGfWords];
+
+    // lines (the FASTQ walk's index) and tabs: '\n' and '\t' per slice, their sums, every line's start and every tab's offset
+    unsigned long long *d_lines_out = (unsigned long long *)ch->d_out.p;
+    const uint64_t slices = ceil_div(size, kFastqSliceBytes);
+    static_assert(kGfaSliceBytes == kFastqSliceBytes, "one slice count serves both indexes");
+    HIP_TRY(ctx, ch->d_waves.ensure((size_t)slices * 4));
+    HIP_TRY(ctx, ch->d_gfa_counts.ensure((size_t)slices * 4));
+    HIP_TRY(ctx, hipMemsetAsync(d_out + kGfForeignLine, 0xff, sizeof(unsigned long long), nullptr));
+    if (ts_k_launch_fastq_count(ch->d_plain.p, size, (uint32_t *)ch->d_waves.p, d_lines_out, nullptr) != 0 ||
+        ts_k_launch_gfa_tab_count(ch->d_plain.p, size, (uint32_t *)ch->d_gfa_counts.p, nullptr) != 0 ||
+        ts_k_launch_fasta_scan((uint32_t *)ch->d_gfa_counts.p, (uint32_t)slices, d_out + kGfTabs, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
+    unsigned long long lines_out[2], n_tabs = 0;
+    HIP_TRY(ctx, hipMemcpy(lines_out, d_lines_out, sizeof lines_out, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&n_tabs, d_out + kGfTabs, sizeof n_tabs, hipMemcpyDeviceToHost));
+    const uint64_t newlines = lines_out[kFqNewlines], tail = lines_out[kFqTail];
+    if (newlines > size || tail > 1 || n_tabs > size) return ctx->fail(TS_ERR_STATE, "ts_gfa_chunk_walk: the line or tab count left the chunk");
+    const uint64_t n_lines = newlines + (at_end ? tail : 0), slots = newlines + 2;
+    HIP_TRY(ctx, ch->d_lines.ensure((size_t)slots * 6));
+    HIP_TRY(ctx, ch->d_gfa_tabs.ensure((size_t)std::max<uint64_t>(n_tabs, 1) * 4));
+    uint32_t *lstart = (uint32_t *)ch->d_lines.p;
+    unsigned char *first = (unsigned char *)ch->d_lines.p + slots * 4, *cr = first + slots;
+    const uint32_t *tabs = (const uint32_t *)ch->d_gfa_tabs.p;
+    if (ts_k_launch_fastq_index(ch->d_plain.p, size, (const uint32_t *)ch->d_waves.p, (uint32_t)newlines, (uint32_t)tail, lstart, first,
+                                cr, nullptr) != 0 ||
+        ts_k_launch_gfa_tabs(ch->d_plain.p, size, (const uint32_t *)ch->d_gfa_counts.p, (uint32_t)n_tabs, (uint32_t *)ch->d_gfa_tabs.p, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
+
+    // kinds: per slice of lines, their sums, the lowest foreign line
+    const uint64_t n_frames = ceil_div(n_lines, kGfaSliceLines);
+    HIP_TRY(ctx, ch->d_gfa_kinds.ensure((size_t)std::max<uint64_t>(n_lines, 1)));
+    HIP_TRY(ctx, ch->d_gfa_frames.ensure((size_t)std::max<uint64_t>(n_frames, 1) * sizeof(GfaFrame)));
+    if (ts_k_launch_gfa_kinds(ch->d_plain.p, lstart, first, cr, (uint32_t)n_lines, (uint32_t)newlines, tabs, (uint32_t)n_tabs,
+                              (unsigned char *)ch->d_gfa_kinds.p, ch->d_gfa_frames.p, d_out, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
+    HIP_TRY(ctx, hipMemcpy(out, d_out, sizeof out, hipMemcpyDeviceToHost));
+    const uint64_t ns = out[kGfSegs], nl = out[kGfLines], nt = out[kGfTextBytes];
+    if (ns > n_lines || nl > n_lines || nt > size || out[kGfLastLine] > size || ns + nl > 0x7fffffffull ||
+        (out[kGfForeignLine] != ~0ull && (out[kGfForeignLine] >= n_lines || out[kGfForeignOff] + out[kGfForeignLen] > size)))
+        return ctx->fail(TS_ERR_STATE, "ts_gfa_chunk_walk: the walk left the chunk");
+    *n_segs = ns; *n_lines_out = nl; *text_bytes = nt;
+    *next = at_end ? size : out[kGfLastLine];
+    if (out[kGfForeignLine] != ~0ull) { foreign->off = out[kGfForeignOff]; foreign->len = (uint32_t)out[kGfForeignLen]; foreign->found = 1; }
+    if (ns > seg_cap || nl > line_cap || nt > text_cap)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_gfa_chunk_walk: a table or the text buffer is too small (*n_segs, *n_lines and *text_bytes say what is needed)");
+    if (ns + nl == 0) return TS_OK;
+
+    // tables and the gathered text
+    HIP_TRY(ctx, ch->d_gfa_segs.ensure((size_t)std::max<uint64_t>(ns, 1) * sizeof(ts_gfa_segment)));
+    HIP_TRY(ctx, ch->d_gfa_lines.ensure((size_t)std::max<uint64_t>(nl, 1) * sizeof(ts_gfa_line)));
+    HIP_TRY(ctx, ch->d_gfa_text.ensure((size_t)std::max<uint64_t>(nt, 1)));
+    if (ts_k_launch_gfa_tables(ch->d_plain.p, lstart, cr, (uint32_t)n_lines, tabs, (uint32_t)n_tabs, (const unsigned char *)ch->d_gfa_kinds.p,
+                               ch->d_gfa_frames.p, ch->d_gfa_segs.p, (uint32_t)ns, ch->d_gfa_lines.p, (uint32_t)nl, nullptr) != 0 ||
+        ts_k_launch_gfa_gather(ch->d_plain.p, size, ch->d_gfa_segs.p, (uint32_t)ns, ch->d_gfa_lines.p, (uint32_t)nl, ch->d_gfa_text.p, nt,
+                               nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
+    if (ns) HIP_TRY(ctx, hipMemcpy(segs, ch->d_gfa_segs.p, (size_t)ns * sizeof(ts_gfa_segment), hipMemcpyDeviceToHost));
+    if (nl) HIP_TRY(ctx, hipMemcpy(lines, ch->d_gfa_lines.p, (size_t)nl * sizeof(ts_gfa_line), hipMemcpyDeviceToHost));
+    if (nt) HIP_TRY(ctx, hipMemcpy(text, ch->d_gfa_text.p, (size_t)nt, hipMemcpyDeviceToHost));
+    return TS_OK;
+}
+
+}  // extern "C"

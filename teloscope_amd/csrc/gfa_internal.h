@@ -1,0 +1,36 @@
+// gfa_internal.h — what gfa.cpp (host glue) and gfa.hip (kernels) of the device GFA route share: the launchers and the layouts
+// both sides count with.  The line index underneath is the FASTQ route's, through its launchers as they are (fastq_internal.h:
+// ts_k_launch_fastq_count / _index), the sums of the tab counts the FASTA route's (fasta_internal.h: ts_k_launch_fasta_scan).
+#pragma once
+
+#include <stdint.h>
+
+constexpr uint32_t kGfaSliceLines = 2048;           // lines a wave of the kind passes takes
+constexpr uint32_t kGfaSliceBytes = 16384;          // bytes of the chunk a wave of the tab index takes
+// words of the GFA result block (unsigned long long each)
+enum { kGfSegs = 0, kGfLines, kGfTextBytes, kGfForeignLine, kGfForeignOff, kGfForeignLen, kGfTabs, kGfLastLine, kGfWords };
+// a line's kind byte: bits 0..1 what the tables keep of it, bit 7 "foreign" (readGfa's rule for a GFA 2 input)
+constexpr uint32_t kGfaNothing = 0, kGfaSegment = 1, kGfaPath = 2, kGfaHeader = 3, kGfaForeign = 0x80;
+// a slice of lines: its segments, its P / H lines and the bytes they gather; after the scan: those before it
+struct GfaFrame { uint32_t segs, lines, text_bytes, pad; };
+
+extern "C" {
+// '\t' per slice of kGfaSliceBytes -> counts[n_slices]
+int ts_k_launch_gfa_tab_count(const void *plain, unsigned long long n, uint32_t *counts, void *stream);
+// every tab's offset in order (sums: the exclusive sums of the counts)
+int ts_k_launch_gfa_tabs(const void *plain, unsigned long long n, const uint32_t *sums, uint32_t n_tabs, uint32_t *tabs, void *stream);
+// every line's kind byte and the counts per slice of kGfaSliceLines -> frames, the lowest foreign line by an atomic minimum on
+// out[kGfForeignLine] (set to ~0 before); then (one wave) frames -> exclusive sums in place, out[kGfSegs / kGfLines / kGfTextBytes]
+// = the totals, out[kGfForeignOff / kGfForeignLen] = the lowest foreign line's offset and first field, out[kGfLastLine] =
+// lstart[newlines]
+int ts_k_launch_gfa_kinds(const void *plain, const uint32_t *lstart, const unsigned char *first, const unsigned char *cr,
+                          uint32_t n_lines, uint32_t newlines, const uint32_t *tabs, uint32_t n_tabs, unsigned char *kinds,
+                          void *frames, unsigned long long *out, void *stream);
+// the segment table and the P / H line table, every entry with its place in the gathered text
+int ts_k_launch_gfa_tables(const void *plain, const uint32_t *lstart, const unsigned char *cr, uint32_t n_lines,
+                           const uint32_t *tabs, uint32_t n_tabs, const unsigned char *kinds, const void *frames, void *segs,
+                           uint32_t n_segs, void *lines, uint32_t n_kept, void *stream);
+// the segments' names and the P / H lines whole into text (a wave per item)
+int ts_k_launch_gfa_gather(const void *plain, unsigned long long size, const void *segs, uint32_t n_segs, const void *lines,
+                           uint32_t n_kept, void *text, unsigned long long text_bytes, void *stream);
+}
