@@ -1,7 +1,14 @@
 """The deflate decoder core and CRC arithmetic of the BGZF kernel (teloscope_amd/csrc/inflate_core.h), compiled for the host by
 g++ under ASan + UBSan (tests/cpp/inflate_core_host.cpp) and compared with zlib: clean blocks of every block type byte for
 byte, damaged blocks verdict for verdict.  The kernel compiles the same functions, so a decoder that walks off a buffer is a
-sanitizer report here and not a fault on a GPU.  No GPU needed."""
+sanitizer report here and not a fault on a GPU.  No GPU needed.
+
+What the decoder is fed: streams of zlib's own encoder (seven settings, five kinds of content, the sizes of SIZES), those
+streams damaged (bit flips, truncations, a trailing byte), the members of the 512-file mutation suite, and the handmade
+streams of tests/deflategen.py, which no encoder here emits: one match at every place of a batch and at every distance
+around the 64 bytes written at a time, chains of matches that copy each other, batches of 64 longest matches, members of
+up to eight blocks of all types in all orders, code-length sets that reach the decode paths behind the lookups, and one
+broken table rule per member.  Third-party encoders (libdeflate, igzip, zopfli) are not among them."""
 import os
 import random
 import struct
@@ -11,6 +18,7 @@ import zlib
 import numpy as np
 import pytest
 
+from tests import deflategen
 from tests.test_bam_subset import bgzf, build_bam, make_reads
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -247,3 +255,31 @@ def test_mutation_suite_512_blocks(host_decoder):
     for w, g in zip(want, got):
         if w[0] != BAD_DEFLATE:
             assert g[1] == w[1]
+
+
+@pytest.mark.parametrize("name", deflategen.ACCEPTED + ("tables_bad", "crc_grid"))
+def test_handmade_streams_get_zlibs_verdict(host_decoder, name):
+    """Every list of tests/deflategen.py (which has asserted each member's class with zlib's decoder): zlib's verdict, and
+    zlib's bytes where it accepts.  The fixture fails on any sanitizer output."""
+    cases, plains = deflategen.cases(name), deflategen.plains(name)
+    want = [zlib_verdict(p, n, c) for _, p, n, c in cases]
+    if name == "tables_bad":
+        assert sum(1 for w in want if w[0] == BAD_DEFLATE) >= 200
+    else:
+        assert all(w[0] == OK for w in want)
+    got = host_decoder([(p, n, c) for _, p, n, c in cases], "handmade_" + name)
+    wrong = [(tag, w[0], g[0]) for (tag, _, _, _), w, g in zip(cases, want, got) if w[0] != g[0]]
+    assert not wrong, wrong[:20]
+    for (tag, _, _, _), w, g in zip(cases, want, got):
+        if w[0] == OK:
+            assert g[1] == w[1] == plains[tag], tag
+
+
+def test_crc_of_short_members(host_decoder):
+    """Stored members of 0..130 bytes with the right CRC32 and with one bit of it wrong."""
+    cases = deflategen.cases("crc_grid")
+    assert [n for _, _, n, _ in cases] == list(range(131))
+    wrong = [(p, n, c ^ (1 << (n % 32))) for _, p, n, c in cases]
+    got = host_decoder([(p, n, c) for _, p, n, c in cases] + wrong, "crc_grid_wrong")
+    assert [v for v, _ in got] == [OK] * 131 + [BAD_CRC] * 131
+    assert [zlib_verdict(*c)[0] for c in wrong] == [BAD_CRC] * 131
