@@ -158,9 +158,12 @@ typedef struct ts_text_piece {
  * byte layout ('N' over the runs) that TS_INPUT_BASES uploads.  Tiled kernel's parameter sets only, like the text pieces. */
 /* input_format TS_INPUT_DEVICE: `seq` is a DEVICE pointer, on the context's device, to the segment's `len` bases — raw ASCII in
  * any case, non-ACGT bytes as they are: exactly the bytes TS_INPUT_BASES would have uploaded, so results are byte-equal to
- * that format's.  The bases are copied device to device into the scan's input layout (no pinned buffer, no host thread, nothing
- * over PCIe); any address will do, and the writes that produced them must be complete when the call is made (the copy runs on a
- * stream of the library's own).  Any parameter set, full and tips-only scans, mixed freely with host segments in one call; not
+ * that format's.  The bases are gathered on the device into the scan's input layout (no pinned buffer, no host thread, nothing
+ * over PCIe): all the device segments of a call by ONE kernel over a job list, a wave per 16 KiB at most — 10^5 small segments
+ * cost one launch, not 10^5 copies; a piece of 8 MiB or more keeps a device-to-device copy of its own (ts_device_input_stats
+ * counts both).  Any address will do — the kernel reads no aligned word that holds no byte of the segment, so the allocation
+ * may end with the segment's last byte — and the writes that produced them must be complete when the call is made (the gather
+ * runs on a stream of the library's own).  Any parameter set, full and tips-only scans, mixed freely with host segments in one call; not
  * ts_scan_segments_multi (the pointer belongs to one device).  Stands in for the std::string& that scanSegment borrows
  * (include/teloscope.h:260) when a front end has produced the bases on the device (the FASTA route's joined records). */
 typedef struct ts_packed_run { uint64_t start, len; } ts_packed_run;
@@ -241,6 +244,12 @@ int     ts_box_probe(ts_ctx *ctx, double *valu_wave_instr_per_ns, double *copy_b
 /* 1 if segments of this kind (full scan / tips-only) may come as TS_INPUT_TEXT_PIECES, TS_INPUT_PACKED2 or TS_INPUT_DEVICE:
  * every parameter set the library scans (until ABI 3 the general kernels wanted the bases joined). */
 int     ts_takes_text_input(const ts_ctx *ctx, int tips_only);
+/* Measurement aid (no counterpart in the reference): what the context has done with TS_INPUT_DEVICE segments since ts_create —
+ * out[0] device pieces seen (a segment scanned fully is one piece per pipeline group it lies in, a long segment's tips are two),
+ * out[1] device-to-device copies issued (pieces of 8 MiB or more), out[2] gather jobs issued (a smaller piece is one job per
+ * 16 KiB), out[3] gather kernel launches (one per pipeline group that holds such a piece).  Cumulative, monotonic and atomic:
+ * concurrent calls are coalesced, so "the last call's" numbers would be nobody's; take the difference around a call. */
+int     ts_device_input_stats(const ts_ctx *ctx, uint64_t out[4]);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
  * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
  * No counterpart in the reference (its options are fixed by main, /root/reference/src/main.cpp:149-184). */

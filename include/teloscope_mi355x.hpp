@@ -18,6 +18,7 @@
 #define TELOSCOPE_MI355X_HPP
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <cstddef>
@@ -271,6 +272,13 @@ public:
     bool takesTextPieces() const { return ts_takes_text_input(ctx.get(), userInput.ultraFastMode ? 1 : 0) != 0; }
     // keeps the calling thread (and the threads it starts) on the CPUs of the device's NUMA node: ts_bind_thread_to_device
     bool bindThreadToDevice() const { return ts_bind_thread_to_device(ctx.get()) != 0; }
+    // what the first device's context has done with device segments since it was made (ts_device_input_stats): pieces seen,
+    // device-to-device copies, gather jobs, gather launches — cumulative; take the difference around a call
+    std::array<uint64_t, 4> deviceInputStats() const {
+        std::array<uint64_t, 4> s{};
+        if (ts_device_input_stats(ctx.get(), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(ctx.get()));
+        return s;
+    }
 
     // one scanSegment call of a batch; the bases are borrowed for the duration of the call (any case:
     // the library folds case itself, as unmaskSequence would have)

@@ -6,11 +6,13 @@ tests/cpp/gfa_device_cli.cpp, on the two seeded graphs of profiles/gfa_annotate_
 
 — each stored as plain text, as BGZF (level 1, 65 280-byte members) and as one gzip stream (level 1).  Per graph and encoding:
 a warm-up of each route, then host and device alternating --reps times in one call, both output files compared every time;
-minimum / median of the whole process's wall time and the device route's TS_TIMING stage line.  Then, in runs of their own, the
-new kernels' times under `rocprofv3 --kernel-trace --stats` (the device route on graph (b), BGZF) and one default bench.py line.
+minimum / median / maximum of the whole process's wall time and the device route's TS_TIMING stage line of every run.  Then,
+in runs of their own, the new kernels' times under `rocprofv3 --kernel-trace --stats` (the device route on graph (b), BGZF, or
+its plain text with --trace-plain) and one default bench.py line.
 Writes DIR/gfa_device_rate.txt; a stage that was not run is listed as "not measured".
 
-  python profiles/gfa_device_rate.py --out DIR [--work DIR] [--scale 1.0] [--reps 3] [--only a|b] [--no-trace] [--no-bench] [--trace-only]
+  python profiles/gfa_device_rate.py --out DIR [--work DIR] [--scale 1.0] [--reps 3] [--only a|b] [--no-trace] [--no-bench]
+                                     [--trace-only [--trace-plain]]
 """
 import argparse
 import glob
@@ -33,7 +35,7 @@ import gfa_annotate_rate as A  # noqa: E402
 
 KERNELS = ("ts_fastq_count_kernel", "ts_fastq_count_scan_kernel", "ts_fastq_index_kernel", "ts_gfa_tab_count_kernel", "ts_fasta_scan_kernel",
            "ts_gfa_tabs_kernel", "ts_gfa_kinds_kernel", "ts_gfa_frame_scan_kernel", "ts_gfa_tables_kernel", "ts_gfa_gather_kernel",
-           "ts_bgzf_inflate")
+           "ts_bgzf_inflate", "ts_gather_pieces_kernel", "ts_scan_tiles", "ts_terminal_ends")
 
 
 def build_cli(work):
@@ -100,8 +102,10 @@ def measure(exe, path, work, reps, log):
         stages.append(stage)
         assert f[:5] == g[:5] and same_outputs(host_dir, dev_dir), "outputs differ on " + path
         stats = (f, g)
-    log("    host   %8.0f / %8.0f ms   (parse %s, scan %s, write %s ms in run %d)" % (min(host), statistics.median(host), stats[0][5], stats[0][6], stats[0][7], reps))
-    log("    device %8.0f / %8.0f ms   (%s)" % (min(dev), statistics.median(dev), stages[0]))
+    log("    host   %8.0f / %8.0f / %8.0f ms   (parse %s, scan %s, write %s ms in run %d)" % (min(host), statistics.median(host), max(host), stats[0][5], stats[0][6], stats[0][7], reps))
+    log("    device %8.0f / %8.0f / %8.0f ms   (%s)" % (min(dev), statistics.median(dev), max(dev), stages[0]))
+    for k, (w, stage) in enumerate(zip(dev[1:], stages[1:]), 2):
+        log("           run %d: %.0f ms   (%s)" % (k, w, stage))
     return stats[0][:5]
 
 
@@ -138,6 +142,7 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--no-bench", action="store_true")
     ap.add_argument("--trace-only", action="store_true", help="graph (b) as BGZF under rocprofv3, nothing else")
+    ap.add_argument("--trace-plain", action="store_true", help="with --trace-only: graph (b) as plain text")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     work = a.work or tempfile.mkdtemp(prefix="gfa_device_rate_")
@@ -154,14 +159,14 @@ def main():
     if a.trace_only:
         plain = os.path.join(work, "graph_b.gfa")
         A.write_graph_b(plain, np.random.default_rng(2), a.scale)
-        traced = encode(plain, work, "graph_b")["bgzip"]
+        traced = plain if a.trace_plain else encode(plain, work, "graph_b")["bgzip"]
         log("Kernel times of the device route, a run of its own under rocprofv3 --kernel-trace --stats (%s, --scale %g):" % (os.path.basename(traced), a.scale))
         kernel_trace(exe, traced, work, log)
         shutil.rmtree(work, ignore_errors=True)
         return
     log("annotateGfaDevice against annotateGfa of the same binary on one MI355X (profiles/gfa_device_rate.py --scale %g --reps %d)." % (a.scale, a.reps))
-    log("Whole-process wall time, minimum / median of %d alternating runs after a warm-up of each route; both output files compared" % a.reps)
-    log("byte for byte after every pair.  Default options.  The device route's stage line is that of run 1.")
+    log("Whole-process wall time, minimum / median / maximum of %d alternating runs after a warm-up of each route; both output files compared" % a.reps)
+    log("byte for byte after every pair.  Default options.  The device route's stage lines are those of runs 1, 2, ...")
     traced = None
     for which, write, seed in (("a", A.write_graph_a, 1), ("b", A.write_graph_b, 2)):
         if a.only not in (None, which):

@@ -236,7 +236,7 @@ SYMBOLS = [
     "ts_bam_chunk_status", "ts_bam_chunk_size", "ts_bam_chunk_read", "ts_bam_chunk_walk", "ts_bam_chunk_decode", "ts_bam_chunk_gather", "ts_bam_chunk_pass_buffer",
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
-    "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over",
+    "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats",
 ]
 
 
@@ -376,6 +376,8 @@ def lib():
     L.ts_scan_segments_multi.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(SegmentIn), C.c_size_t,
                                          C.POINTER(SegmentOut), C.POINTER(SegmentCounts)]
     L.ts_box_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ts_device_input_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_device_input_stats.restype = C.c_int
     L.ts_exchange_unique_id.argtypes = [C.c_void_p]
     L.ts_exchange_last_error.restype = C.c_char_p
     L.ts_exchange_create.restype = C.c_void_p

@@ -734,6 +734,8 @@ void ts_destroy(ts_ctx *ctx) {
             if (ctx->pin_up_ev[i]) (void)hipEventDestroy(ctx->pin_up_ev[i]);
             ctx->d_pack[i].release(); ctx->d_runs[i].release(); ctx->pin_runs[i].release();
         }
+        ctx->pin_jobs.release(); ctx->d_jobs.release();
+        if (ctx->jobs_ev) (void)hipEventDestroy(ctx->jobs_ev);
         for (hipEvent_t e : ctx->gen_ev) if (e) (void)hipEventDestroy(e);
         for (PinBuf &pb : ctx->pin_down) pb.release();
         for (hipStream_t st : {ctx->up_stream, ctx->scan_stream, ctx->down_stream, ctx->side_stream})
@@ -832,6 +834,12 @@ int ts_takes_text_input(const ts_ctx *ctx, int tips_only) {
     // (round 4: the general path stages its groups through the same upload as the tiled path — every format, every set)
     std::string why;
     return ctx && ((tips_only ? ctx->fast_ok : ts_full_scan_supported(ctx, why)) || ctx->generic_ok) ? 1 : 0;
+}
+
+int ts_device_input_stats(const ts_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return TS_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->device_input_stats[i].load(std::memory_order_relaxed);
+    return TS_OK;
 }
 
 // =========================================================================== batches

@@ -156,6 +156,14 @@ struct ts_ctx {
     hipEvent_t pin_up_ev[kUpSlots] = {nullptr, nullptr, nullptr};
     DevBuf d_pack[kUpSlots], d_runs[kUpSlots];   // packed upload: a chunk's 2-bit codes and invalid runs on the device
     PinBuf pin_runs[kUpSlots];
+    // device pieces (TS_INPUT_DEVICE): the job list of upload_pieces' gather launch — staged in pin_jobs (refilled only once
+    // jobs_ev says its previous upload has completed), uploaded to d_jobs (reused under up_stream's order); both grow on demand
+    PinBuf pin_jobs;
+    DevBuf d_jobs;
+    hipEvent_t jobs_ev = nullptr;
+    bool jobs_ev_pending = false;
+    // ts_device_input_stats: device pieces seen, device-to-device copies issued, gather jobs issued, gather launches — since ts_create
+    std::atomic<uint64_t> device_input_stats[4] = {};
     hipEvent_t gen_ev[2] = {nullptr, nullptr};   // TS_TIMING: around the general path's kernels
     PinBuf pin_down[2];
     PinBuf pin_off;                              // general path: a group's tile directory lands here (a pageable landing cost 9 ms per MB-sized copy)

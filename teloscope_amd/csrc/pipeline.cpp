@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "gather_core.h"
 
 namespace {
 
@@ -237,6 +238,58 @@ uint64_t strip_take(char *dst, uint64_t n, const char **pp, const char *end) {
 
 constexpr uint32_t kPackRunCap = 1u << 18;                 // invalid runs a packed chunk may carry (more: the chunk goes as ASCII)
 
+// The device pieces (TS_INPUT_DEVICE) of one upload_pieces call, to the device buffer whose byte lo_all lies at din, on
+// up_stream.  One device-to-device copy per piece costs ~3 us of issue each (400 000 GFA segments: 1.2 s); instead the pieces
+// become a job list — tsgather::Job: source address, offset from din, byte count; a piece longer than a 16 KiB slice is cut
+// into sub-jobs at 16-byte boundaries of the destination, so that no wave's work is unbounded — which is staged in pinned
+// memory, uploaded once and consumed by ONE launch of ts_gather_pieces_kernel (gather.hip), a wave per job.
+// THE RULE, fixed: a piece of kDeviceCopyMin bytes (8 MiB) or more keeps its own device-to-device copy — a blit that long is
+// bound by HBM, not by its issue, and a chromosome-sized record need not become 10^5 jobs; every smaller piece is gathered.
+// ts_device_input_stats counts both.  The pinned list is refilled only after jobs_ev says its previous upload has completed;
+// the device list is reused under the stream's order (growing it frees the old block, which waits for the device).
+constexpr uint64_t kDeviceCopyMin = 8ull << 20;
+int gather_device_pieces(ts_ctx *c, const std::vector<UpPiece> &on_device, void *din, uint64_t lo_all) {
+    if (on_device.empty()) return TS_OK;
+    const uint64_t base = (uint64_t)(uintptr_t)din;
+    uint64_t n_jobs = 0, n_copies = 0;
+    for (const UpPiece &pc : on_device) {
+        if (pc.len >= kDeviceCopyMin) ++n_copies;
+        else n_jobs += tsgather::split_count(base + (pc.off - lo_all), pc.len, tsgather::kSliceBytes);
+    }
+    c->device_input_stats[0].fetch_add(on_device.size(), std::memory_order_relaxed);
+    if (n_copies) {
+        for (const UpPiece &pc : on_device)
+            if (pc.len >= kDeviceCopyMin)
+                HIP_TRY(c, hipMemcpyAsync((char *)din + (pc.off - lo_all), pc.src, pc.len, hipMemcpyDeviceToDevice, c->up_stream));
+        c->device_input_stats[1].fetch_add(n_copies, std::memory_order_relaxed);
+    }
+    if (!n_jobs) return TS_OK;
+    if (n_jobs > 0x7FFFFFFFull) return c->fail(TS_ERR_UNSUPPORTED, "too many device pieces in one group");
+    const size_t bytes = (size_t)n_jobs * sizeof(tsgather::Job);
+    if (!c->jobs_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->jobs_ev, hipEventDisableTiming));
+    if (c->jobs_ev_pending) { HIP_TRY(c, hipEventSynchronize(c->jobs_ev)); c->jobs_ev_pending = false; }
+    if ((c->pin_jobs.bytes < bytes && c->pin_jobs.ensure(bytes + bytes / 2) != hipSuccess) ||
+        (c->d_jobs.bytes < bytes && c->d_jobs.ensure(bytes + bytes / 2) != hipSuccess)) {
+        (void)hipGetLastError();
+        return c->fail(TS_ERR_ALLOC, "cannot allocate the job list of the device pieces' gather");
+    }
+    tsgather::Job *job = (tsgather::Job *)c->pin_jobs.p;
+    for (const UpPiece &pc : on_device) {
+        if (pc.len >= kDeviceCopyMin) continue;
+        tsgather::split_piece((uint64_t)(uintptr_t)pc.src, base + (pc.off - lo_all), pc.len, tsgather::kSliceBytes,
+                              [&](uint64_t src, uint64_t dst, uint32_t n) { *job++ = tsgather::Job{src, dst - base, n, 0u}; });
+    }
+    if ((uint64_t)(job - (tsgather::Job *)c->pin_jobs.p) != n_jobs) return c->fail(TS_ERR_STATE, "device pieces: the job list does not hold what was counted");
+    HIP_TRY(c, hipMemcpyAsync(c->d_jobs.p, c->pin_jobs.p, bytes, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(c, hipEventRecord(c->jobs_ev, c->up_stream));
+    c->jobs_ev_pending = true;
+    if (ts_k_launch_gather_pieces(c->d_jobs.p, (uint32_t)n_jobs, din, c->up_stream) != 0)
+        return c->fail(TS_ERR_HIP, "gather kernel launch failed");
+    c->device_input_stats[2].fetch_add(n_jobs, std::memory_order_relaxed);
+    c->device_input_stats[3].fetch_add(1, std::memory_order_relaxed);
+    return TS_OK;
+}
+
 
 // Uploads pieces of an input layout to the device buffer that holds its bytes from lo_all on (din = address of byte
 // lo_all).  Consecutive pieces that lie close together in the layout (full scans, reads: a few padding bytes apart) are
@@ -245,8 +298,8 @@ constexpr uint32_t kPackRunCap = 1u << 18;                 // invalid runs a pac
 // stream fills pinned memory at ~10 GB/s, a fraction of what the link moves; one copy per read would cost ~10 us each,
 // one pageable 3 GB copy ~0.5 s).  Pieces far apart (the two terminal regions of a long contig in tips-only mode) go
 // separately.  Bytes between pieces are never read as bases (the kernels mask everything past a region's end).
-// Pieces that already lie on the device (TS_INPUT_DEVICE) take no part in any of this: no pinned slot, no host thread — one
-// device-to-device copy each on up_stream, queued BEHIND the host pieces' chunks (a chunk's DMA or unpack kernel also writes the
+// Pieces that already lie on the device (TS_INPUT_DEVICE) take no part in any of this: no pinned slot, no host thread —
+// gather_device_pieces above, queued on up_stream BEHIND the host pieces' chunks (a chunk's DMA or unpack kernel also writes the
 // padding between its pieces, where a device piece may lie; the stream's order makes the device piece's bytes the last written).
 // Asynchronous: the DMAs are queued on up_stream.  `pieces` ascend by offset and do not overlap.
 int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, uint64_t lo_all, int &slot, bool used[]) {
@@ -559,9 +612,7 @@ int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, u
         i = j;
     }
     if (bad_text.load()) return c->fail(TS_ERR_INVALID_ARG, "a text piece holds fewer bases than it declares");
-    for (const UpPiece &pc : on_device)
-        HIP_TRY(c, hipMemcpyAsync((char *)din + (pc.off - lo_all), pc.src, pc.len, hipMemcpyDeviceToDevice, c->up_stream));
-    return TS_OK;
+    return gather_device_pieces(c, on_device, din, lo_all);
 }
 
 // The upload pieces of one scanned region of an item: its bases [rg_start, rg_start + rg_len), whose first lies at byte

@@ -399,6 +399,9 @@ int  ts_k_launch_tile_order_export(const uint32_t *tile_stats, const unsigned lo
 // packed: 4-byte aligned, 8 readable bytes behind the last code.
 int  ts_k_launch_unpack(const void *packed, uint32_t first, void *dst, unsigned long long n, const void *runs, uint32_t nruns,
                         void *runs_base, void *stream);
+// gather.hip: device-resident pieces into the input layout, a wave per job (jobs: tsgather::Job of gather_core.h, device memory;
+// a job's bytes go to base + its dst)
+int  ts_k_launch_gather_pieces(const void *jobs, uint32_t n_jobs, void *base, void *stream);
 // exchange.hip: box calibration (see there)
 int  ts_k_box_probe(void *scratch, unsigned long long bytes, int num_cu, double *issue_per_ns, double *copy_bytes_per_ns, void *stream);
 int  ts_k_launch_widen_u16(const uint16_t *src, uint32_t *dst, unsigned long long n, void *stream);

@@ -192,6 +192,15 @@ class Teloscope:
     def usesFastPath(self):
         return bool(K.lib().ts_uses_fast_path(self._ctx.ptr))
 
+    def device_input_stats(self):
+        """ts_device_input_stats: (device pieces seen, device-to-device copies issued, gather jobs issued, gather launches) of
+        this context since it was made; cumulative, so take the difference around a call."""
+        out = (C.c_uint64 * 4)()
+        rc = K.lib().ts_device_input_stats(self._ctx.ptr, out)
+        if rc != K.TS_OK:
+            raise K.TeloscanError(rc, self._ctx.error())
+        return tuple(int(v) for v in out)
+
     def scanSegments(self, segments, packed=False):
         """Batched scanSegment: segments = [(sequence, absPos, tipsOnly)] -> [SegmentData].
         packed=True hands the bases over as TS_INPUT_PACKED2 (2-bit codes + invalid runs, packed here with ts_pack_bases and
