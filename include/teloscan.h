@@ -82,7 +82,9 @@ typedef struct ts_params {
     uint8_t  fold_case;          /* 1: a/c/g/t match like A/C/G/T (what every reference
                                        caller gets by calling unmaskSequence first);
                                     0: strict scanSegment semantics (lower case = non-ACGT) */
-    uint8_t  reserved0;
+    uint8_t  out_win_repeats;    /* -r : read only by the window tracks' formatter (ts_window_tracks_format, ts_scan_segments_tracks): the
+                                    density, canonical-ratio and strand-ratio tracks exist.  (Was reserved and zero: no other entry
+                                    point looks at it — the covered counts of a window are always produced.) */
     int32_t  device;             /* HIP device ordinal, -1 = current device, TS_DEVICE_NONE = planning only */
     uint32_t reserved1;
 } ts_params;
@@ -319,6 +321,50 @@ typedef struct ts_segment_counts {
 } ts_segment_counts;
 int ts_scan_segments_blocks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out,
                             ts_segment_counts *counts);
+
+/* ---- The five window tracks as text, formatted on the device (no counterpart of its own in the reference: it stands in for the
+ *      window loops of writeBEDFile, src/teloscope.cpp:785-812, whose lines BedWriter::format writes on host threads otherwise).
+ *      A line is  name \t start \t end \t value \n  with value as operator<<(float) prints it (%g, precision 6).  Track order
+ *      everywhere: repeat density, canonical ratio, strand ratio, GC, entropy.  The context decides which tracks exist: the
+ *      first three with out_win_repeats, GC with out_gc, entropy with out_entropy; a track that does not exist comes back as
+ *      text NULL, len 0.  The arrays are the library's until ts_free_track_text().
+ *      A ts_track_text must be ZERO-INITIALISED before its first use.  Both calls REPLACE what the struct holds, they never
+ *      append: a struct that still holds an earlier call's result is reused — its arrays are kept, grown if need be and filled
+ *      again, so a caller that formats chunk after chunk allocates once — and nothing leaks; a struct holding anything else
+ *      (uninitialised memory) is undefined.  After a failed call the struct is empty (freed).  ts_free_track_text() at the end.
+ *      A column value the device formatter cannot print (anything but 0, -1 and the positive floats in [2^-32, 128]: no window
+ *      of a scan has one) makes the call fail with TS_ERR_UNSUPPORTED and a message that names the window; it never yields
+ *      wrong text.  One device: not part of ts_scan_segments_multi. */
+#define TS_N_TRACKS 5
+typedef struct ts_track_text {
+    char    *text[TS_N_TRACKS];      /* not NUL-terminated */
+    uint64_t len[TS_N_TRACKS];
+    uint64_t n_lines;                /* lines per existing track (= windows formatted) */
+    uint64_t capacity[TS_N_TRACKS];  /* the library's */
+} ts_track_text;
+/* One segment of the table ts_window_tracks_format reads: its windows are records [first_window, first_window + n_windows),
+ * window k covers [abs_pos + k * step, abs_pos + k * step + min(window_size, len - k * step)) and carries the name
+ * names[name_off, name_off + name_len).  Segments in ascending first_window order; one without windows is skipped. */
+typedef struct ts_track_segment {
+    uint64_t first_window, n_windows, abs_pos, len, name_off;
+    uint32_t name_len, reserved;
+} ts_track_segment;
+/* The formatting stage by itself, host in, host out: `n` window records of eight uint32 {A, C, G, T, canonical, non-canonical,
+ * forward, reverse covered} (what a scan leaves per window; ts_window's integer fields), the segment table and the names' bytes
+ * -> the text of every track the context has.  Uploads the records and runs the kernels ts_scan_segments_tracks runs; exists so
+ * that records no small scan produces can be formatted.  Stands in for src/teloscope.cpp:785-812. */
+int  ts_window_tracks_format(ts_ctx *ctx, const uint32_t *records, uint64_t n, const ts_track_segment *segs, size_t n_segs,
+                             const char *names, uint64_t names_len, ts_track_text *out);
+void ts_free_track_text(ts_track_text *t);
+/* ts_scan_segments_blocks plus the text: blocks and counts come back as there, but out[i].windows == NULL and
+ * out[i].n_windows == 0 (counts[i].n_windows, if counts is given, carries the count), and `tracks` holds the lines of all
+ * full-scan segments in input order, segs[i]'s under names[i] (NUL-terminated); tips-only segments contribute none.  Every
+ * input format (TS_INPUT_DEVICE included), tiled and general kernels, any number of pipeline groups: each group's lines are
+ * formatted where its window records lie and appended in order, in place of the download of the records and their expansion to
+ * ts_window on host threads.  Calls of this kind are not coalesced with other callers'.  Stands in for scanSegment
+ * (src/teloscope.cpp:537-658) followed by src/teloscope.cpp:785-812. */
+int  ts_scan_segments_tracks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, const char *const *names,
+                             ts_segment_out *out, ts_segment_counts *counts, ts_track_text *tracks);
 
 /* ---- GFA annotation (src/input.cpp:625-716).  For every segment (tips_only must be 1), ends[2*i] / ends[2*i+1]: the
  *      longest terminal block (blockLen) at the start / end side of segs[i], 0 if none (walkSegment's distToStart <= distToEnd

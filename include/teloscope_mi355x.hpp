@@ -132,6 +132,20 @@ inline std::vector<std::pair<std::string, bool>> expandPatternsWithOrientation(
 // bytes long.  width == 0: irregular — positions are found by walking the lines.
 struct TextLines { uint32_t first = 0, width = 0, eol = 0; };
 
+// The lines of the five window tracks as the device formatted them (ts_scan_segments_tracks), in detail::File order: density,
+// canonical ratio, strand ratio, GC, entropy.  Owns the library's arrays; a track the flags switch off is null with length 0.
+struct TrackText {
+    ts_track_text t{};
+    TrackText() = default;
+    TrackText(const TrackText &) = delete;
+    TrackText &operator=(const TrackText &) = delete;
+    ~TrackText() { ts_free_track_text(&t); }
+    const char *data(int track) const { return t.text[track]; }
+    uint64_t size(int track) const { return t.len[track]; }
+    uint64_t lines() const { return t.n_lines; }
+    void clear() { ts_free_track_text(&t); }
+};
+
 namespace detail {
 
 struct CtxDeleter { void operator()(ts_ctx *c) const { ts_destroy(c); } };
@@ -145,6 +159,7 @@ inline ts_params makeParams(const UserInputTeloscope &ui) {
     p.max_block_dist = ui.maxBlockDist; p.min_block_counts = ui.minBlockCounts;
     p.min_block_density = ui.minBlockDensity; p.canonical_size = ui.canonicalSize;
     p.out_gc = ui.outGC; p.out_entropy = ui.outEntropy; p.out_matches = ui.outMatches; p.out_its = ui.outITS;
+    p.out_win_repeats = ui.outWinRepeats;
     p.fold_case = 1;                                   // every reference caller runs unmaskSequence first
     p.device = ui.device;
     return p;
@@ -406,6 +421,26 @@ public:
             for (unsigned i = 0; i < nt; ++i) pool.emplace_back(worker);
             for (std::thread &th : pool) th.join();
         }
+        ts_free_segments(out.data(), out.size());
+        return res;
+    }
+
+    // scanSegmentsNoMatches with the windows left on the device: result[i] has blocks only, counts[i].n_windows says how many
+    // windows segs[i] has, and `text` receives the lines of the five window tracks of all full-scan segments in input order,
+    // segs[i]'s under names[i] — formatted on the device (ts_scan_segments_tracks) in place of WindowData on the host and
+    // BedWriter's formatting threads.  One device.
+    std::vector<SegmentData> scanSegmentsTrackText(const std::vector<Segment> &segs, const std::vector<const char *> &names,
+                                                   std::vector<ts_segment_counts> &counts, TrackText &text) {
+        if (names.size() != segs.size()) throw std::runtime_error("scanSegmentsTrackText: one name per segment");
+        std::vector<ts_segment_in> in(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
+        std::vector<ts_segment_out> out(segs.size());
+        counts.assign(segs.size(), ts_segment_counts{0, 0, 0, 0});
+        // (the call replaces what `text` holds and reuses its arrays)
+        if (ts_scan_segments_tracks(ctx.get(), in.data(), in.size(), names.data(), out.data(), counts.data(), &text.t) != TS_OK)
+            throw std::runtime_error(ts_last_error(ctx.get()));
+        std::vector<SegmentData> res(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) res[i] = convert(out[i], segs[i]);
         ts_free_segments(out.data(), out.size());
         return res;
     }

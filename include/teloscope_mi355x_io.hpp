@@ -69,6 +69,10 @@ struct PathData {                              // include/teloscope.h:151-163
     // not in the reference: canonicalMatches.size() as the report prints it, also when the match
     // vectors were never brought to the host (walkPaths without -m counts on the device)
     uint64_t canonicalMatchCount = 0;
+    // ... and windows.size() when the windows stayed on the device and came back as text (walkRecordViews with a TrackText):
+    // `windows` is empty then
+    uint64_t windowCount = 0;
+    uint64_t nWindows() const { return windows.empty() ? windowCount : windows.size(); }
 };
 
 struct FastaRecord {
@@ -379,14 +383,20 @@ inline std::vector<PathComponents> splitPaths(const std::vector<RecordView> &rec
 
 // walkPath for every record, with one batched scan (result order = record order; seqPos = seqPosBase + index, or
 // (*seqPositions)[index] when given: the records' indices in the whole input, which a record filter leaves with gaps).
+// trackText: when given — and the run has no -m and one device — the windows stay on the device: *trackText receives the lines
+// of the five window tracks of these records in order (Teloscope::scanSegmentsTrackText), every path's `windows` stays empty
+// and its windowCount says how many there were.  Otherwise it is left empty and everything is as without it.
 inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::vector<RecordView> &records, size_t seqPosBase = 0,
                                              const std::vector<PathComponents> *precomputed = nullptr,
-                                             const std::vector<size_t> *seqPositions = nullptr) {
+                                             const std::vector<size_t> *seqPositions = nullptr, TrackText *trackText = nullptr) {
     const UserInputTeloscope &ui = teloscope.input();
     // (the streaming reader finds the N-runs while the freshly joined bases are still in cache)
     const std::vector<PathComponents> split = precomputed ? std::vector<PathComponents>() : splitPaths(records);
     const std::vector<PathComponents> &comps = precomputed ? *precomputed : split;
     std::vector<Teloscope::Segment> batch;
+    const bool textRoute = trackText && !ui.outMatches && teloscope.deviceCount() == 1;
+    if (trackText && !textRoute) trackText->clear();            // (the text route's call replaces the text and reuses its arrays)
+    std::vector<const char *> batchNames;                        // (text route: every segment's record name)
     // text records that N-runs cut into several segments: every segment gets its own piece list (reserved up front, so
     // the lists do not move while the batch points into them)
     auto oneSegment = [&](size_t pi) {
@@ -405,11 +415,13 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
             for (const auto &sg : comps[pi].segments) {
                 batch.emplace_back(rv.data ? rv.data + sg.first : nullptr, static_cast<size_t>(sg.second), sg.first, ui.ultraFastMode);
                 if (rv.device) batch.back().device = rv.device + sg.first;
+                if (textRoute) batchNames.push_back(rv.header->c_str());
             }
             continue;
         }
         if (oneSegment(pi)) {
             batch.emplace_back(rv.pieces, rv.nPieces, rv.size, 0, ui.ultraFastMode, rv.lines);   // its pieces as they are
+            if (textRoute) batchNames.push_back(rv.header->c_str());
             continue;
         }
         // a segment = bases [a, a + n) of the record: the text pieces that hold them, the first one entered at base a
@@ -443,13 +455,15 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
                 at += n; left -= n; c2 += rv.pieces[q].n_bases;
             }
             batch.emplace_back(sp.data(), sp.size(), static_cast<size_t>(sg.second), sg.first, ui.ultraFastMode, sl.data());
+            if (textRoute) batchNames.push_back(rv.header->c_str());
         }
     }
     // without -m nothing downstream reads a match record: blocks and counts come from the device
     std::vector<ts_segment_counts> counts;
     // (with -m: only the two match vectors the writers read are materialised; block calling has happened on the device)
     // (several devices: the batch is cut into one shard per device, and what comes back is the writers' view either way)
-    std::vector<SegmentData> scanned = teloscope.deviceCount() > 1 ? teloscope.scanSegmentsWriterView(batch, counts)
+    std::vector<SegmentData> scanned = textRoute ? teloscope.scanSegmentsTrackText(batch, batchNames, counts, *trackText)
+                                     : teloscope.deviceCount() > 1 ? teloscope.scanSegmentsWriterView(batch, counts)
                                      : ui.outMatches ? teloscope.scanSegments(batch, true)
                                                      : teloscope.scanSegmentsNoMatches(batch, counts);
     const bool haveCounts = teloscope.deviceCount() > 1 || !ui.outMatches;
@@ -466,6 +480,7 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
         if (nseg == 1) {                                        // the common case: the record is one segment — no copies
             SegmentData &sd = scanned[si];
             pd.canonicalMatchCount = haveCounts ? counts[si].n_canonical : sd.canonicalMatches.size();
+            if (textRoute) pd.windowCount = counts[si].n_windows;
             pd.windows = std::move(sd.windows);
             pd.terminalBlocks = std::move(sd.terminalBlocks);
             pd.interstitialBlocks = std::move(sd.interstitialBlocks);
@@ -482,6 +497,7 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
                 append(pd.terminalBlocks, sd.terminalBlocks);
                 append(pd.interstitialBlocks, sd.interstitialBlocks);
                 pd.canonicalMatchCount += haveCounts ? counts[si].n_canonical : sd.canonicalMatches.size();
+                if (textRoute) pd.windowCount += counts[si].n_windows;
                 append(pd.canonicalMatches, sd.canonicalMatches);
                 append(pd.nonCanonicalMatches, sd.nonCanonicalMatches);
             }
@@ -1885,7 +1901,7 @@ class BedWriter {
              uint64_t(static_cast<uint16_t>(pd.gapInfos.size())), '\t', scaffoldTypeToString(pd.scaffoldType), '\t', pd.terminalLabel);
         if (!ui.ultraFastMode)
             line(row, '\t', uint64_t(pd.interstitialBlocks.size()), '\t', pd.canonicalMatchCount, '\t',
-                 uint64_t(pd.windows.size()));
+                 pd.nWindows());
         row += '\n';
         o[REPORT] += row;
         o[CONSOLE] += row;
@@ -1923,9 +1939,23 @@ public:
         if (threads == 0) threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     }
 
-    // formats and writes these paths (which follow, in seqPos order, the ones added before)
-    void add(const std::vector<PathData> &paths) {
+    // formats and writes these paths (which follow, in seqPos order, the ones added before).  text: the lines of these paths'
+    // windows as the device formatted them (walkRecordViews with a TrackText; the paths' `windows` are empty then): each track's
+    // bytes go to its file as they are, large ones on a thread per file as the host-formatted ones do.  Without text — null —
+    // this is add(paths) as it always was.
+    void add(const std::vector<PathData> &paths, const TrackText *text = nullptr) {
         using namespace detail;
+        std::vector<std::thread> textWriters;
+        struct JoinText { std::vector<std::thread> &t; ~JoinText() { for (std::thread &th : t) if (th.joinable()) th.join(); } } joinText{textWriters};
+        if (text) {
+            static_assert(DENSITY == 0 && CANON_RATIO == 1 && STRAND_RATIO == 2 && GC == 3 && ENTROPY == 4, "track order is File order");
+            for (int f = DENSITY; f <= ENTROPY; ++f) {
+                if (!on[f] || !text->size(f)) continue;
+                auto put = [this, text, f] { files[f].write(text->data(f), static_cast<std::streamsize>(text->size(f))); };
+                if (text->size(f) >= (size_t(1) << 20) && threads > 1) textWriters.emplace_back(put);
+                else put();
+            }
+        }
         // work list in output order: per path its row/blocks/gaps/matches, then its windows in runs
         constexpr size_t kRun = 1u << 16;
         std::vector<Task> tasks;
@@ -1978,7 +2008,7 @@ public:
                 if (b.isLongest) { ++sum.totalTelomeres; telomereLengths.push_back(static_cast<float>(b.blockLen)); }
             sum.totalGaps += static_cast<uint16_t>(pd.gapInfos.size());
             if (!ui.ultraFastMode) {
-                sum.totalNWindows += static_cast<uint32_t>(pd.windows.size());
+                sum.totalNWindows += static_cast<uint32_t>(pd.nWindows());
                 sum.totalITS += static_cast<uint32_t>(pd.interstitialBlocks.size());
                 sum.totalCanMatches += static_cast<uint32_t>(pd.canonicalMatchCount);
             }
@@ -2523,6 +2553,8 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
 // every segment handed to the scan as a device segment through walkRecordViews, so that blocks, counts and windows come back
 // exactly as for the host route; BedWriter fed.  With -m the joined bases are read back once per chunk (matchSeq needs them).
 // The bytes behind the last complete record stay in the chunk for the next fill; a record larger than a chunk makes it grow.
+// deviceTracks (off by default): the window tracks' lines are formatted on the device too (ts_scan_segments_tracks) and BedWriter
+// writes them as they come; see below.
 // Limits: ONE device (a Teloscope over several throws); no assembly record filters (they stay with the host route); a record
 // whose text does not fit a chunk of chunkLimit bytes (4 GiB - 2, what the walk takes) is refused by name, never cut; the
 // stages run one after the other.  chunkLimit is a test hook (the refusal cannot be reached otherwise without 4 GiB of text):
@@ -2531,7 +2563,7 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
 inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
                                               std::ostream &console, bool manualCuration = false,
                                               size_t chunkBytesArg = size_t(256) << 20, ScanFastaTimes *times = nullptr,
-                                              uint64_t chunkLimit = 0xfffffffeull) {
+                                              uint64_t chunkLimit = 0xfffffffeull, bool deviceTracks = false) {
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     const auto tBegin = Clock::now();
@@ -2602,6 +2634,12 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
     if (!chunk.p) throw fail("cannot make the device chunk");
 
     BedWriter writer(outBase, ui, console, manualCuration);
+    // deviceTracks: the five window tracks are formatted on the device where the window records lie and come back as text
+    // (opt-in: whether 13 x the records' bytes over PCIe beats the host's formatting threads depends on the box; README has the
+    // measurement).  With -m the flag is ignored and the host formats as ever: the match files and matchSeq dominate such a
+    // run, and the writers' view of the matches comes through another entry point.
+    const bool useTrackText = deviceTracks && !ui.outMatches;
+    TrackText trackText;
     std::vector<ts_fasta_record> recs(4096);
     std::vector<char> names(size_t(1) << 16), block, hostBases;
     std::vector<ts_fasta_run> runs(4096);
@@ -2729,12 +2767,12 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
                                   static_cast<const char *>(dBases) + offsets[i]};
         }
         t0 = Clock::now();
-        std::vector<PathData> paths = walkRecordViews(teloscope, views, recordsDone, &comps);
+        std::vector<PathData> paths = walkRecordViews(teloscope, views, recordsDone, &comps, nullptr, useTrackText ? &trackText : nullptr);
         recordsDone += static_cast<size_t>(n);
         msScan += since(t0);
         t0 = Clock::now();
-        writer.add(paths);
-        for (const PathData &pd : paths) { T.bases += pd.pathSize; T.windows += pd.windows.size(); }
+        writer.add(paths, useTrackText ? &trackText : nullptr);
+        for (const PathData &pd : paths) { T.bases += pd.pathSize; T.windows += pd.nWindows(); }
         ++T.groups;
         msWrite += since(t0);
     }

@@ -31,7 +31,7 @@ class Params(C.Structure):
                 ("min_block_counts", C.c_uint16), ("min_block_density", C.c_float),
                 ("canonical_size", C.c_uint16), ("out_gc", C.c_uint8), ("out_entropy", C.c_uint8),
                 ("out_matches", C.c_uint8), ("out_its", C.c_uint8), ("fold_case", C.c_uint8),
-                ("reserved0", C.c_uint8), ("device", C.c_int32), ("reserved1", C.c_uint32)]
+                ("out_win_repeats", C.c_uint8), ("device", C.c_int32), ("reserved1", C.c_uint32)]
 
 
 class Match(C.Structure):
@@ -127,6 +127,19 @@ class SegmentOut(C.Structure):
 class SegmentCounts(C.Structure):
     _fields_ = [("n_windows", C.c_uint64), ("n_matches", C.c_uint64), ("n_canonical", C.c_uint64),
                 ("n_forward", C.c_uint64)]
+
+
+N_TRACKS = 5
+
+
+class TrackText(C.Structure):
+    _fields_ = [("text", C.c_void_p * N_TRACKS), ("len", C.c_uint64 * N_TRACKS), ("n_lines", C.c_uint64),
+                ("capacity", C.c_uint64 * N_TRACKS)]
+
+
+class TrackSegment(C.Structure):
+    _fields_ = [("first_window", C.c_uint64), ("n_windows", C.c_uint64), ("abs_pos", C.c_uint64), ("len", C.c_uint64),
+                ("name_off", C.c_uint64), ("name_len", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class BatchInfo(C.Structure):
@@ -237,6 +250,7 @@ SYMBOLS = [
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
     "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats",
+    "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
 ]
 
 
@@ -421,6 +435,14 @@ def lib():
     L.ts_chunk_data.argtypes = [C.c_void_p]
     L.ts_chunk_data.restype = C.c_void_p
     L.ts_chunk_carry_over.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.ts_window_tracks_format.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TrackSegment), C.c_size_t, C.c_char_p,
+                                          C.c_uint64, C.POINTER(TrackText)]
+    L.ts_window_tracks_format.restype = C.c_int
+    L.ts_free_track_text.argtypes = [C.POINTER(TrackText)]
+    L.ts_free_track_text.restype = None
+    L.ts_scan_segments_tracks.argtypes = [C.c_void_p, C.POINTER(SegmentIn), C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(SegmentOut),
+                                          C.POINTER(SegmentCounts), C.POINTER(TrackText)]
+    L.ts_scan_segments_tracks.restype = C.c_int
     _lib = L
     return L
 

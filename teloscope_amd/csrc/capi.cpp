@@ -1548,18 +1548,18 @@ struct Fetched {
     const uint32_t *wins = nullptr, *recs = nullptr, *tile_stats = nullptr;
     unsigned long long *tile_off = nullptr;
     uint64_t nrecs = 0;
-    bool with_matches = false;
+    bool with_matches = false, with_windows = true;
 };
 
 // Device work + D2H of a synced whole batch (on its stream), into pinned landing area `pin`.
-int batch_fetch(ts_batch *b, bool with_matches, PinBuf &pin, Fetched &F) {
+int batch_fetch(ts_batch *b, bool with_matches, PinBuf &pin, Fetched &F, bool with_windows = true) {
     ts_ctx *c = b->ctx;
     const size_t nt = b->tiles.size();
     hipStream_t st = (hipStream_t)b->last_stream;
-    F.with_matches = with_matches;
+    F.with_matches = with_matches; F.with_windows = with_windows;
     if (b->msg_windows) return c->fail(TS_ERR_STATE, "the batch's scan packed its window records into a shard message (ts_batch_bind_shard_message): there are no 32-byte records to download");
     { int rc = device_block_call(b, st, F.blocks); if (rc != TS_OK) return rc; }
-    const uint64_t nwin_dl = b->tips ? 0 : b->n_windows;
+    const uint64_t nwin_dl = b->tips || !with_windows ? 0 : b->n_windows;      // (without: they stay on the device, for the track formatter)
     const uint64_t nrecs = with_matches ? b->n_matches : 0;
     F.nrecs = nrecs;
     F.land.reset(new HostLanding(pin, nwin_dl * 32 + (with_matches ? nrecs * 4 + (nt + 1) * 24 : 0) + 1024));
@@ -1662,7 +1662,7 @@ int assemble(ts_ctx *c, const HostView &v, const Decode &decode, ts_segment_out 
         }
     }
     for (size_t si = 0; si < ns; ++si)
-        if (!ts_alloc_segment(out[si], v.tips ? 0 : v.segs[si].n_windows, seg_nm[si])) {
+        if (!ts_alloc_segment(out[si], v.tips || v.no_windows ? 0 : v.segs[si].n_windows, seg_nm[si])) {
             ts_free_segments(out, ns);
             return c->fail(TS_ERR_ALLOC, "out of host memory");
         }
@@ -1673,7 +1673,7 @@ int assemble(ts_ctx *c, const HostView &v, const Decode &decode, ts_segment_out 
     constexpr uint64_t kWinPiece = 1u << 15, kRecPiece = 1u << 17;
     for (size_t si = 0; si < ns; ++si) {
         const HostView::Seg &sg = v.segs[si];
-        if (!v.tips)
+        if (!v.tips && !v.no_windows)
             for (uint64_t a = 0; a < sg.n_windows; a += kWinPiece) pieces.push_back({(uint32_t)si, true, a, std::min<uint64_t>(sg.n_windows, a + kWinPiece)});
         if (seg_nm[si])
             for (uint64_t a = 0, z = 0; a < sg.n_tiles; a = z) {
@@ -1711,6 +1711,7 @@ int assemble(ts_ctx *c, const HostView &v, const Decode &decode, ts_segment_out 
 int batch_finalize(ts_batch *b, const Fetched &F, ts_segment_out *out) {
     HostView v;
     v.tips = b->tips;
+    v.no_windows = !F.with_windows;
     v.wins = F.wins; v.recs = F.recs; v.nrecs = F.nrecs;
     v.blocks = F.blocks.data(); v.n_blocks = F.blocks.size();
     v.segs.reserve(b->segs.size());
@@ -1756,9 +1757,9 @@ int ts_assemble_general(ts_ctx *c, const HostView &v, ts_segment_out *out) {
 // pinned landing area `slot` of the context, then host post-processing (which may run while the next group's
 // fetch uses the other slot)
 struct ts_fetched { Fetched F; };
-ts_fetched *ts_batch_fetch(ts_batch *b, bool with_matches, int slot, int *rc_out) {
+ts_fetched *ts_batch_fetch(ts_batch *b, bool with_matches, int slot, int *rc_out, bool with_windows) {
     ts_fetched *f = new ts_fetched();
-    *rc_out = batch_fetch(b, with_matches, b->ctx->pin_down[slot & 1], f->F);
+    *rc_out = batch_fetch(b, with_matches, b->ctx->pin_down[slot & 1], f->F, with_windows);
     if (*rc_out != TS_OK) { delete f; return nullptr; }
     return f;
 }

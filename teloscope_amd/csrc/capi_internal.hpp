@@ -143,6 +143,8 @@ struct ts_ctx {
     // there, and the pinned staging buffers are allocated there — a DMA out of the other socket's memory, or staging
     // threads on the other socket, cost 15-20 % of the PCIe-inclusive rate on a two-socket host
     std::vector<float> entropy_term;      // ts::entropy_terms(window_size): windows of the full size look their terms up
+    DevBuf d_entropy_term;                // ... and its copy on the device, made by the first call that formats tracks there (tracks.cpp)
+    std::mutex track_mtx;                 // one track-formatting call at a time per context
     std::vector<int> node_cpus;
     void bind_this_thread() const;          // no-op when node_cpus is empty; never widens the thread's current mask
     static constexpr int kUpSlots = 3;
@@ -358,6 +360,7 @@ struct HostView {
     const uint32_t *wins = nullptr, *recs = nullptr;
     uint64_t nrecs = 0;
     bool tips = false;
+    bool no_windows = false;                 // the windows stay on the device (ts_scan_segments_tracks): segments get none
     const TsDevBlock *blocks = nullptr;      // sorted as ts_split_blocks reads them
     size_t n_blocks = 0;
 };
@@ -374,9 +377,18 @@ int  ts_device_block_call_raw(ts_ctx *c, const TsTile *d_tiles, const unsigned l
 void ts_batch_release_input(ts_batch *b);        // returns the batch's input buffer to the context's pool
 void *ts_batch_input_ptr_nozero(ts_batch *b);
 struct ts_fetched;                               // what a download left in host memory, before post-processing
-ts_fetched *ts_batch_fetch(ts_batch *b, bool with_matches, int slot, int *rc_out);   // device work + D2H (pinned slot 0/1)
+ts_fetched *ts_batch_fetch(ts_batch *b, bool with_matches, int slot, int *rc_out, bool with_windows = true);   // device work + D2H (pinned slot 0/1)
 int  ts_batch_finalize(ts_batch *b, ts_fetched *f, ts_segment_out *out);             // host post-processing; frees f
     // the batch's own input buffer, not zero-filled (every byte read is uploaded)
+
+// tracks.cpp: the lines of the window tracks the context has, formatted on the device from `n_records` window records at
+// d_records and appended to *out (zeroed by the caller before the first call).  h_records: the same records on the host, or null
+// (the few the entropy patch list needs are then picked off the device).  Work and copies run on st; synchronous.
+struct ts_track_text;
+struct ts_track_segment;
+void ts_track_text_begin(const ts_ctx *c, ts_track_text *t);    // a caller's struct (zeroed, or an earlier result: reused) made empty
+int  ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_records, uint64_t n_records, const ts_track_segment *segs,
+                      size_t n_segs, const char *names, uint64_t names_len, hipStream_t st, ts_track_text *out);
 
 // bgzf.cpp: a chunk of an uncompressed stream resident on the device (ts_bam_chunk_*; ts_chunk is the same type: fastq.cpp)
 struct ts_bam_chunk {

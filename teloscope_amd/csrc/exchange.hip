@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ts_device.h"
 #include "ts_internal.h"
 
 
@@ -20,18 +21,8 @@ constexpr uint32_t kScanThreads = 64;
 constexpr uint32_t kScanPerThread = 8;
 constexpr uint32_t kScanBlock = kScanThreads * kScanPerThread;      // tiles per workgroup
 
-// wave-wide exclusive prefix sum of one u64 per lane; returns the lane's exclusive prefix, *total = the wave's sum
-__device__ __forceinline__ u64 block_excl_scan(u64 v, u64 *total) {
-    u64 incl = v;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, (int)o), hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), (int)o);
-        if (lane >= o) incl += ((u64)hi << 32) | lo;
-    }
-    const uint32_t tlo = (uint32_t)__shfl((int)(uint32_t)incl, 63), thi = (uint32_t)__shfl((int)(uint32_t)(incl >> 32), 63);
-    *total = ((u64)thi << 32) | tlo;
-    return incl - v;
-}
+// wave-wide exclusive prefix sum of one u64 per lane (ts_device.h); returns the lane's exclusive prefix, *total = the wave's sum
+__device__ __forceinline__ u64 block_excl_scan(u64 v, u64 *total) { return wave_excl_scan_u64(v, total); }
 
 // pass 1: records per workgroup of kScanBlock tiles; also raises the "incomplete" flag when a wave's region
 // overflowed in the scan (its tile counts then promise records that were never stored)

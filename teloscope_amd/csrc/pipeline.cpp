@@ -83,7 +83,8 @@ private:
     int n_;
 };
 
-enum class Mode { Matches, Blocks, ReadPass, Ends };   // Ends: ts_terminal_ends, 8 bytes per segment back
+enum class Mode { Matches, Blocks, ReadPass, Ends, Tracks };   // Ends: ts_terminal_ends, 8 bytes per segment back; Tracks: Blocks
+                                                                // without window records, the window tracks' text instead (ts_scan_segments_tracks)
 
 struct Item { const char *seq; uint64_t len, abs_pos; uint8_t format; uint32_t n_pieces; };     // format: TS_INPUT_BASES / TS_INPUT_TEXT_PIECES (seq = ts_text_piece[]) /
                                                                                                 // TS_INPUT_PACKED2 (seq = ts_packed_seq) / TS_INPUT_DEVICE (seq = device memory)
@@ -95,10 +96,33 @@ struct Outputs {
     ts_segment_counts *counts = nullptr;
     uint8_t *pass = nullptr;
     uint32_t *ends = nullptr;
+    ts_track_text *tracks = nullptr;              // Tracks: every group's lines are appended, in item order (not sliced); names: per item
+    const char *const *names = nullptr;
     Outputs slice(size_t at) const {
-        return {out ? out + at : nullptr, counts ? counts + at : nullptr, pass ? pass + at : nullptr, ends ? ends + 2 * at : nullptr};
+        return {out ? out + at : nullptr, counts ? counts + at : nullptr, pass ? pass + at : nullptr, ends ? ends + 2 * at : nullptr,
+                tracks, names ? names + at : nullptr};
     }
 };
+
+// Tracks: the lines of a group's windows, formatted where the records lie (tracks.cpp), appended to the call's text.  segs: the
+// group's segments with first_window / n_windows / abs_pos / len set; names[i]: segment i's name.
+int group_tracks(ts_ctx *c, const uint32_t *d_windows, uint64_t n_windows, std::vector<ts_track_segment> &segs, const char *const *names,
+                 hipStream_t st, ts_track_text *out) {
+    std::string blob;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        // (consecutive segments of one path share a name: it is stored once)
+        const size_t len = std::strlen(names[i]);
+        if (i && segs[i - 1].name_len == len && std::memcmp(blob.data() + segs[i - 1].name_off, names[i], len) == 0) {
+            segs[i].name_off = segs[i - 1].name_off;
+        } else {
+            segs[i].name_off = blob.size();
+            blob.append(names[i], len);
+        }
+        if (len > 0xFFFFFFFFull) return c->fail(TS_ERR_INVALID_ARG, "ts_scan_segments_tracks: a name of 4 GiB or more");
+        segs[i].name_len = (uint32_t)len;
+    }
+    return ts_tracks_append(c, d_windows, nullptr, n_windows, segs.data(), segs.size(), blob.data(), blob.size(), st, out);
+}
 
 struct Group {
     size_t first = 0, count = 0;                  // items [first, first + count) of the call's item list
@@ -928,8 +952,16 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
                 rc = batch_terminal_ends(gr->b, go.ends, slot, ctx->down_stream);
             } else if (rc == TS_OK) {
                 // device work + D2H of this group while the previous group's records are expanded on the host threads
-                ts_fetched *f = ts_batch_fetch(gr->b, mode == Mode::Matches, slot, &rc);
-                if (rc == TS_OK && mode == Mode::Blocks && go.counts) rc = batch_counts(gr->b, go.counts, tips, ctx->down_stream);
+                ts_fetched *f = ts_batch_fetch(gr->b, mode == Mode::Matches, slot, &rc, mode != Mode::Tracks);
+                if (rc == TS_OK && (mode == Mode::Blocks || mode == Mode::Tracks) && go.counts) rc = batch_counts(gr->b, go.counts, tips, ctx->down_stream);
+                if (rc == TS_OK && mode == Mode::Tracks && go.tracks && !tips) {
+                    std::vector<ts_track_segment> ts(gr->b->segs.size());
+                    for (size_t i = 0; i < ts.size(); ++i) {
+                        const SegPlan &sp = gr->b->segs[i];
+                        ts[i] = ts_track_segment{sp.win_base, sp.n_windows, sp.abs_pos, sp.len, 0, 0, 0};
+                    }
+                    rc = group_tracks(ctx, gr->b->windows_ptr(), gr->b->n_windows, ts, go.names, ctx->down_stream, go.tracks);
+                }
                 gr->t_fetch = ms_between(t0, Clock::now());
                 if (post.joinable()) post.join();
                 if (rc == TS_OK) {
@@ -961,7 +993,7 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
         double p = 0, u = 0, s = 0, d = 0, f = 0, z = 0;
         for (const Group &gr : groups) { p += gr.t_plan; u += gr.t_upload; s += gr.t_scan; d += gr.t_down; f += gr.t_fetch; z += gr.t_final; }
         const char *name = mode == Mode::Matches ? "ts_scan_segments" : mode == Mode::Blocks ? "ts_scan_segments_blocks"
-                         : mode == Mode::Ends ? "ts_terminal_ends" : "ts_filter_reads";
+                         : mode == Mode::Tracks ? "ts_scan_segments_tracks" : mode == Mode::Ends ? "ts_terminal_ends" : "ts_filter_reads";
         fprintf(stderr, "%s: %zu items in %zu groups, wall %.1f ms; stage sums (concurrent): plan %.1f ms, stage+upload %.1f ms, "
                         "scan (incl. waiting for the upload) %.1f ms, download + host post-processing %.1f ms (device work + D2H %.1f ms, host expansion %.1f ms)\n",
                 name, items.size(), groups.size(), ms_between(t_begin, Clock::now()), p, u, s, d, f, z);
@@ -1418,10 +1450,17 @@ int gen_download(GenCall &g, GenGroup &gr) {
         hwin = h.wins_heap.data();
     }
     if (h.nrecs) HIP_TRY(c, hipMemcpyAsync(hrec, gr.d_rec.p, h.nrecs * 4, hipMemcpyDeviceToHost, st));
-    if (gr.nwin_total) HIP_TRY(c, hipMemcpyAsync(hwin, gr.d_win.p, gr.nwin_total * 32, hipMemcpyDeviceToHost, st));
+    const bool text = g.mode == Mode::Tracks;                    // the windows leave as text, formatted where they lie
+    if (gr.nwin_total && !text) HIP_TRY(c, hipMemcpyAsync(hwin, gr.d_win.p, gr.nwin_total * 32, hipMemcpyDeviceToHost, st));
     h.recs = hrec;
-    h.wins = hwin;
+    h.wins = text ? nullptr : hwin;
     HIP_TRY(c, hipStreamSynchronize(st));
+    if (text && g.o.tracks && gr.nwin_total) {
+        std::vector<ts_track_segment> ts(h.G.size());
+        for (size_t i = 0; i < ts.size(); ++i) ts[i] = ts_track_segment{h.G[i].win_base, h.G[i].n_windows, h.G[i].abs_pos, h.G[i].len, 0, 0, 0};
+        const int rc = group_tracks(c, (const uint32_t *)gr.d_win.p, gr.nwin_total, ts, g.o.names + h.first, st, g.o.tracks);
+        if (rc != TS_OK) return rc;
+    }
     if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
     const auto t1 = Clock::now();
     g.t_d2h += ms_between(t0, t1);
@@ -1437,6 +1476,7 @@ int gen_host(GenCall &g, const GenHost &h) {
     HostView v;
     v.tips = g.tips;
     v.wins = h.wins; v.recs = h.recs; v.nrecs = h.nrecs;
+    v.no_windows = g.mode == Mode::Tracks;
     v.blocks = h.blocks.data(); v.n_blocks = h.blocks.size();
     v.segs.reserve(ns);
     for (const GenSeg &sg : h.G) v.segs.push_back({sg.len, sg.abs_pos, sg.win_base, sg.n_windows, sg.first_tile, sg.n_tiles});
@@ -1524,8 +1564,13 @@ Item item_of(const ts_segment_in &s) { return Item{s.seq, s.len, s.abs_pos, s.in
 int route(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &items, Outputs o, bool have_lock) {
     if (items.empty()) return TS_OK;
     std::string why;
-    if (tips ? ctx->fast_ok : ts_full_scan_supported(ctx, why))
+    if (tips ? ctx->fast_ok : ts_full_scan_supported(ctx, why)) {
+        if (mode == Mode::Tracks && !have_lock) {                // (its text is one stream in group order: not merged with other callers)
+            std::lock_guard<std::mutex> api(ctx->api_mtx);
+            return run_pipeline(ctx, mode, tips, items, o);
+        }
         return have_lock ? run_pipeline(ctx, mode, tips, items, o) : submit_pipeline(ctx, mode, tips, items, o);
+    }
     // (an exception — std::bad_alloc while a multi-GB group is planned — must leave as an error code: this is a C boundary)
     try {
         if (have_lock) return scan_general(ctx, mode, tips, items, o);
@@ -1563,7 +1608,10 @@ int scan_segments_impl(ts_ctx *ctx, Mode mode, const ts_segment_in *segs, size_t
         for (size_t i = 0; i < which.size(); ++i) items[i] = item_of(segs[which[i]]);
         std::vector<ts_segment_out> out(which.size());
         std::vector<ts_segment_counts> counts(o.counts ? which.size() : 0);
-        rc = route(ctx, mode, tips, items, Outputs{out.data(), o.counts ? counts.data() : nullptr, nullptr, nullptr}, have_lock);
+        std::vector<const char *> names(o.names ? which.size() : 0);
+        for (size_t i = 0; i < names.size(); ++i) names[i] = o.names[which[i]];
+        rc = route(ctx, mode, tips, items, Outputs{out.data(), o.counts ? counts.data() : nullptr, nullptr, nullptr, tips ? nullptr : o.tracks,
+                                                     names.empty() ? nullptr : names.data()}, have_lock);
         if (rc != TS_OK) { ts_free_segments(out.data(), out.size()); break; }
         for (size_t i = 0; i < which.size(); ++i) {
             o.out[which[i]] = out[i];
@@ -1602,6 +1650,27 @@ int ts_scan_segments_blocks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_seg
                             ts_segment_counts *counts) {
     if (!ctx || (n_segs && (!segs || !out))) return TS_ERR_INVALID_ARG;
     return scan_segments_impl(ctx, Mode::Blocks, segs, n_segs, Outputs{out, counts}, false);
+}
+
+// ts_scan_segments_blocks without the window records: every group's window lines are formatted on the device (tracks.hip) and
+// appended to `tracks` instead; see include/teloscan.h.
+int ts_scan_segments_tracks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, const char *const *names, ts_segment_out *out,
+                            ts_segment_counts *counts, ts_track_text *tracks) {
+    if (!ctx || !tracks || (n_segs && (!segs || !out || !names))) return TS_ERR_INVALID_ARG;
+    ts_track_text_begin(ctx, tracks);
+    for (size_t i = 0; i < n_segs; ++i)
+        if (!names[i]) return ctx->fail(TS_ERR_INVALID_ARG, "ts_scan_segments_tracks: null name");
+    if (ctx->device == kNoDevice) return ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it");
+    Outputs o{out, counts};
+    o.tracks = tracks; o.names = names;
+    int rc = scan_segments_impl(ctx, Mode::Tracks, segs, n_segs, o, false);
+    if (rc == TS_OK) {                                           // (a call without a full-scan segment: the tracks exist, empty)
+        DeviceGuard g(ctx->device);
+        rc = ts_tracks_append(ctx, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, tracks);
+        if (rc != TS_OK) ts_free_segments(out, n_segs);
+    }
+    if (rc != TS_OK) ts_free_track_text(tracks);
+    return rc;
 }
 
 // =========================================================================== ReadTelomereFilter

@@ -24,6 +24,20 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add(v), 63);
 }
 
+// Wave-wide exclusive prefix sum of one 64-bit value per lane (callers: one wave per workgroup, or the lanes of one wave);
+// returns the lane's exclusive prefix, *total = the wave's sum.
+__device__ __forceinline__ unsigned long long wave_excl_scan_u64(unsigned long long v, unsigned long long *total) {
+    unsigned long long incl = v;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, (int)o), hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), (int)o);
+        if (lane >= o) incl += ((unsigned long long)hi << 32) | lo;
+    }
+    const uint32_t tlo = (uint32_t)__shfl((int)(uint32_t)incl, 63), thi = (uint32_t)__shfl((int)(uint32_t)(incl >> 32), 63);
+    *total = ((unsigned long long)thi << 32) | tlo;
+    return incl - v;
+}
+
 // Wave-wide inclusive prefix maximum, the same six DPP steps.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_max(uint32_t v) {

@@ -402,6 +402,30 @@ int  ts_k_launch_unpack(const void *packed, uint32_t first, void *dst, unsigned 
 // gather.hip: device-resident pieces into the input layout, a wave per job (jobs: tsgather::Job of gather_core.h, device memory;
 // a job's bytes go to base + its dst)
 int  ts_k_launch_gather_pieces(const void *jobs, uint32_t n_jobs, void *base, void *stream);
+// tracks.hip: the five window tracks as text (track_format_core.h: tstrack::Segment, tstrack::Patch).  A workgroup formats
+// TS_TRACK_BLOCK windows; block_sums holds 5 x (n_blocks + 1) values — per track the workgroups' bytes, after
+// ts_k_launch_track_count their exclusive prefix sums with the track's total behind them; *bad_window (preset to ~0) the
+// lowest window with a value the formatter cannot print.  ts_k_launch_track_write needs out[t] of block_sums[t][n_blocks]
+// bytes for every track of on_mask; it writes nothing when *bad_window is set.
+#define TS_TRACK_BLOCK 256u
+#define TS_TRACK_MAX_NAME (1u << 24)     // bytes of a segment name: 64 lines of a wave stay far below 2^32 bytes
+struct TsTrackParams {
+    const uint32_t *records;                // eight u32 per window, 16-byte aligned
+    unsigned long long first, n;            // the call formats windows [first, n) of the records, workgroup b those from first + b * TS_TRACK_BLOCK
+    const void *segs;                       // tstrack::Segment[n_segs]: the segments that have windows, first_window ascending
+    const void *names;                      // the bytes the segments' name_off / name_len point into
+    const float *term;                      // ts::entropy_terms(w), or null: every window's entropy is in the patch list
+    const void *patches;                    // tstrack::Patch[n_patches], sorted by window
+    unsigned long long n_patches;
+    unsigned long long *block_sums;
+    unsigned long long *bad_window;
+    void *out[5];
+    uint32_t n_segs, n_blocks, w, step, on_mask;
+};
+int  ts_k_launch_track_count(const TsTrackParams *P, void *stream);
+int  ts_k_launch_track_write(const TsTrackParams *P, void *stream);
+// out[j] = the record of window idx[j] (device memory, all three)
+int  ts_k_launch_track_pick(const uint32_t *records, const unsigned long long *idx, unsigned long long n, uint32_t *out, void *stream);
 // exchange.hip: box calibration (see there)
 int  ts_k_box_probe(void *scratch, unsigned long long bytes, int num_cu, double *issue_per_ns, double *copy_bytes_per_ns, void *stream);
 int  ts_k_launch_widen_u16(const uint16_t *src, uint32_t *dst, unsigned long long n, void *stream);

@@ -81,7 +81,7 @@ class UserInputTeloscope:
                         min_block_density=float(self.minBlockDensity),
                         canonical_size=self.canonicalSize, out_gc=int(self.outGC),
                         out_entropy=int(self.outEntropy), out_matches=int(self.outMatches),
-                        out_its=int(self.outITS), fold_case=int(self.foldCase), device=self.device)
+                        out_its=int(self.outITS), fold_case=int(self.foldCase), out_win_repeats=int(self.outWinRepeats), device=self.device)
 
     def _patterns(self):
         if not self.patternInfo:
