@@ -476,11 +476,8 @@ inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &fil
 
 // The device route of annotateGfa(teloscope, file, outDir, log), which stays the default: the same two output files byte for
 // byte, the same warnings on `log`, the same exceptions and the same GfaAnnotateStats, but no host thread looks for a line end
-// or a tab.  The text reaches HBM from the three sources of scanFastaToFilesDevice —
-//   1. a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
-//   2. a BGZF regular file (bgzip output): members located on the host, inflated and checksummed on the device
-//      (ts_bam_chunk_inflate); from the first member that does not parse as BGZF on, the rest of the input takes source 3;
-//   3. anything else (plain gzip, a file that cannot be mapped): through zlib in blocks, each block uploaded —
+// or a tab.  The text reaches HBM through detail::ChunkFeed (teloscope_mi355x_io.hpp: a plain file, BGZF members inflated on the
+// device, or a stream, here always through zlib, which reads plain bytes through the same calls)
 // in chunks of ~chunkBytes bytes, and per chunk ts_gfa_chunk_walk gives the segment table, the P / H lines and the names.  Which
 // segments are scanned and which field of an S line is its sequence is known only after the last line (a P or H line may stand
 // anywhere), so every walked chunk STAYS RESIDENT; an unfinished last line moves into the next chunk device to device
@@ -501,53 +498,10 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
         throw std::runtime_error("annotateGfaDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
                                  " (the graph's text lies in one device's memory)");
     ts_ctx *ctx = teloscope.context();
-    auto fail = [&](const char *what) -> std::runtime_error {
-        const char *why = ts_last_error(ctx);
-        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
-    };
+    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
     constexpr uint64_t kChunkLimit = 0xfffffffeull;             // what ts_gfa_chunk_walk takes
-    const int fd = ::open(file.c_str(), O_RDONLY);
-    if (fd < 0) throw std::runtime_error("Could not open assembly input '" + file + "'.");
-    struct Closer { int fd; gzFile gz = nullptr; ~Closer() { if (gz) gzclose(gz); else ::close(fd); } } closer{fd};
-    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
-    {
-        struct stat st;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
-        }
-    }
-    const unsigned char *data = static_cast<const unsigned char *>(mapping.p);
-    const size_t size = mapping.n;
-    auto bgzfMember = [](const unsigned char *p, size_t n, detail::BgzfBlockRef &ref, bool &eofm) -> size_t {
-        try { return detail::parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
-    };
-    enum { Plain, Bgzf, Stream } source = Stream;
-    if (data) {
-        detail::BgzfBlockRef ref{};
-        bool eofm = false;
-        if (size >= 2 && data[0] == 0x1f && data[1] == 0x8b) source = bgzfMember(data, size, ref, eofm) ? Bgzf : Stream;
-        else source = Plain;
-    }
-    const bool deviceInflate = source == Bgzf;
-    // (a fill of BGZF members may exceed what it was asked for by one member: the chunk stays below the walk's limit all the same)
-    const uint64_t chunkLimit = deviceInflate ? kChunkLimit - 65536 : kChunkLimit;
-    bool streamOpen = false, streamDone = false;
-    auto openStream = [&](size_t from) {
-        streamOpen = true;
-        if (from > 0) {                                         // behind BGZF members anything that is not gzip ends the input
-            if (size - from < 2 || data[from] != 0x1f || data[from + 1] != 0x8b) { streamDone = true; return; }
-            if (::lseek(fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error("Could not read assembly input '" + file + "'.");
-        }
-        closer.gz = gzdopen(fd, "rb");                          // (zlib reads plain files through the same calls)
-        if (!closer.gz) throw std::runtime_error("Could not open assembly input '" + file + "'.");
-        gzbuffer(closer.gz, 1u << 20);
-    };
     double msUpload = 0, msIndex = 0, msGraph = 0;
 
-    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
-    // (an inflate call takes members of the mapped file: never more compressed bytes than the file has)
-    const uint64_t compCap = source == Bgzf ? std::min<uint64_t>(chunkBytes + (1u << 20), std::max<size_t>(size, 64)) : 64;
     struct ChunkFree { void operator()(ts_chunk *c) const { ts_bam_chunk_destroy(c); } };
     std::vector<std::unique_ptr<ts_chunk, ChunkFree>> chunks;   // every one stays until the scan and the write are done
     uint64_t resident = 0;
@@ -562,13 +516,26 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
     std::vector<Piece> pieces;
     std::vector<std::vector<char>> blocks;                      // zlib's output as it was produced
     uint64_t total = 0;
+    ts_chunk *cur = nullptr, *prev = nullptr;
+    detail::ChunkFeed::Options options;
+    options.cannotOpen = "Could not open assembly input '" + file + "'.";
+    options.cannotRead = "Could not read assembly input '" + file + "'.";
+    options.zlibAlways = true;
+    options.growFailed = "cannot grow a device chunk";
+    options.uploadFailed = "upload of the GFA text failed";
+    options.noRoom = noRoom;
+    options.sink = [&](const char *host, uint64_t chunkAt, uint64_t len) {
+        pieces.push_back({host, host ? nullptr : cur, chunkAt, total, len});
+        total += len;
+    };
+    detail::ChunkFeed feed(ctx, file, options);
+    const uint64_t chunkLimit = feed.chunkLimit(kChunkLimit);
+    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+    const uint64_t compCap = feed.compCap(chunkBytes);
     // what a chunk's walk gave; base: the input offset of the chunk's first byte
     struct Walked { ts_chunk *chunk; uint64_t base; std::vector<ts_gfa_segment> segs; std::vector<ts_gfa_line> lines; std::vector<char> text; ts_gfa_foreign foreign; };
     std::vector<Walked> walked;
-    std::vector<ts_bgzf_block> descs;
 
-    size_t at = 0;                              // next byte of the mapped file (sources 1 and 2)
-    ts_chunk *cur = nullptr, *prev = nullptr;
     uint64_t held = 0, prevNext = 0, base = 0;
     bool atEnd = false, grow = false;
     while (!atEnd) {
@@ -580,78 +547,17 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
                                      " bytes and does not fit a device chunk; use annotateGfa, the host route");
         // a chunk that held no whole line takes as much again, up to what a chunk may hold
         const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, grow ? carry : 0), chunkLimit - carry));
-        size_t got = 0;
-        if (source == Stream) {                                 // zlib's next block, kept for the writer
-            if (!streamOpen) openStream(0);
-            blocks.emplace_back(std::min<size_t>(want, size_t(4) << 20));
-            std::vector<char> &block = blocks.back();
-            while (!streamDone && got < want) {
-                if (got == block.size()) block.resize(std::min(want, 2 * block.size()));
-                const int n = gzread(closer.gz, block.data() + got, static_cast<unsigned>(std::min<size_t>(block.size() - got, size_t(1) << 30)));
-                if (n < 0) throw std::runtime_error("Could not read assembly input '" + file + "'.");
-                if (n == 0) { streamDone = true; break; }
-                got += static_cast<size_t>(n);
-            }
-            block.resize(got);
-            block.shrink_to_fit();
-        }
+        std::vector<char> *keep = nullptr;
+        if (feed.source() == detail::ChunkFeed::Stream) { blocks.emplace_back(); keep = &blocks.back(); }   // zlib's next block, kept for the writer
+        const uint64_t room = feed.read(want, keep);            // (known for a mapped plain file and a block read, a guess for BGZF members)
         if (!grow) {
-            // room for what the fill brings: known for a mapped plain file and a block read, a guess for BGZF members (the chunk grows)
-            const uint64_t room = source == Plain ? std::min<uint64_t>(want, size - at) : source == Stream ? got
-                                                  : std::min<uint64_t>(want, 8 * static_cast<uint64_t>(size - at) + 65536);
             ts_chunk *made = ts_bam_chunk_create(ctx, compCap, std::max<uint64_t>(carry + room, 64));
             if (!made) throw noRoom("cannot make a device chunk");
             chunks.emplace_back(made);
             cur = made;
             if (carry && ts_chunk_carry_over(cur, prev, prevNext, nullptr) != TS_OK) throw noRoom("cannot carry a line into the next device chunk");
         }
-        if (source == Bgzf) {
-            uint64_t produced = 0;
-            bool foreignMember = false, full = false;
-            do {
-                descs.clear();
-                size_t used = 0;
-                uint64_t made = 0;
-                while (at + used < size) {
-                    detail::BgzfBlockRef ref{};
-                    bool eofm = false;
-                    const size_t totalBytes = bgzfMember(data + at + used, size - at - used, ref, eofm);
-                    if (totalBytes == 0) { foreignMember = true; break; }
-                    if (produced + made > 0 && produced + made + ref.isize > want) { full = true; break; }
-                    if (!descs.empty() && used + totalBytes > compCap) break;
-                    ts_bgzf_block d{};
-                    d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
-                    d.dst_off = carry + produced + made;
-                    descs.push_back(d);
-                    made += ref.isize;
-                    used += totalBytes;
-                }
-                if (ts_chunk_reserve(cur, carry + produced + made) != TS_OK) throw noRoom("cannot grow a device chunk");
-                if (ts_bam_chunk_inflate(cur, data + at, used, descs.data(), descs.size(), 0, nullptr) != TS_OK) throw fail("BGZF inflate failed");
-                ts_bgzf_status bad{};
-                if (ts_bam_chunk_status(cur, &bad) != TS_OK) throw fail("BGZF inflate failed");
-                if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
-                if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
-                if (made) pieces.push_back({nullptr, cur, carry + produced, total, made});
-                total += made;
-                at += used;
-                produced += made;
-            } while (!foreignMember && !full && at < size);
-            if (foreignMember) { source = Stream; openStream(at); atEnd = streamDone; }
-            else atEnd = at >= size;
-        } else if (source == Plain) {
-            const size_t n = std::min(want, size - at);
-            if (ts_chunk_upload(cur, data + at, n, 0, nullptr) != TS_OK) throw noRoom("upload of the GFA text failed");
-            at += n;
-            total += n;
-            atEnd = at >= size;
-        } else {
-            const std::vector<char> &block = blocks.back();
-            if (ts_chunk_upload(cur, block.data(), got, 0, nullptr) != TS_OK) throw noRoom("upload of the GFA text failed");
-            if (got) pieces.push_back({block.data(), nullptr, 0, total, got});
-            total += got;
-            atEnd = streamDone;
-        }
+        atEnd = feed.put(cur, 0);
         msUpload += since(t0);
         resident += ts_bam_chunk_size(cur) - held * (grow ? 1 : 0);
         held = ts_bam_chunk_size(cur);
@@ -681,7 +587,6 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
         walked.push_back(std::move(w));
         prev = cur; prevNext = next; base += next;
     }
-    if (source == Plain && size) pieces.assign(1, Piece{reinterpret_cast<const char *>(data), nullptr, 0, 0, size});
 
     // the graph, as readGfa builds it
     Clock::time_point t0 = Clock::now();
@@ -791,7 +696,7 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
     st.writeMs = std::chrono::duration<double, std::milli>(t3 - t2).count();
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "annotateGfaDevice: upload%s %.0f ms, index %.0f ms, graph (host) %.0f ms, scan %.0f ms, write %.0f ms\n",
-                     deviceInflate ? " + inflate + CRC" : "", msUpload, msIndex, msGraph, st.scanMs, st.writeMs);
+                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msGraph, st.scanMs, st.writeMs);
     return st;
 }
 

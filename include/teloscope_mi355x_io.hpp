@@ -1321,56 +1321,297 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
     return stats;
 }
 
+// ---- what the four device routes share: the input's bytes into a device chunk, and the judge step of the two read subsets ----
+namespace detail {
+
+inline std::runtime_error deviceError(ts_ctx *ctx, const char *what) {      // "<what>: <the library's last error>"
+    const char *why = ts_last_error(ctx);
+    return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
+}
+
+// An input's descriptor and, for a regular file that is not empty and can be mapped, its bytes.  `-` is stdin where the route
+// says so; descriptor 0 is never closed from here (gzclose of a stream opened on it closes it, as it always did).
+struct MappedInput {
+    int fd = 0;
+    bool owned = false;
+    gzFile gz = nullptr;
+    const unsigned char *data = nullptr;
+    size_t size = 0;
+    MappedInput(const std::string &file, bool dashIsStdin, const std::string &cannotOpen) {
+        if (!dashIsStdin || file != "-") {
+            fd = ::open(file.c_str(), O_RDONLY);
+            if (fd < 0) throw std::runtime_error(cannotOpen);
+            owned = true;
+        }
+        struct stat st;
+        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { data = static_cast<const unsigned char *>(m); size = static_cast<size_t>(st.st_size); ::madvise(m, size, MADV_SEQUENTIAL); }
+        }
+    }
+    MappedInput(const MappedInput &) = delete;
+    MappedInput &operator=(const MappedInput &) = delete;
+    ~MappedInput() {
+        if (data) ::munmap(const_cast<unsigned char *>(data), size);
+        if (gz) gzclose(gz); else if (owned) ::close(fd);
+    }
+    // what did not map (a pipe, stdin) read to its end
+    void readToEnd(std::vector<unsigned char> &into, const char *cannotRead) const {
+        for (;;) {
+            const size_t at = into.size();
+            into.resize(at + (8u << 20));
+            const ssize_t r = ::read(fd, into.data() + at, 8u << 20);
+            if (r < 0) throw std::runtime_error(cannotRead);
+            into.resize(at + static_cast<size_t>(r));
+            if (r == 0) break;
+        }
+    }
+};
+
+// The BGZF member at p (its total size), or 0: what is there does not parse as a whole BGZF member
+inline size_t bgzfMemberOrNone(const unsigned char *p, size_t n, BgzfBlockRef &ref) {
+    bool eofm = false;
+    try { return parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
+}
+
+// The members of one inflate call, from data[at] on, for a fill that has `produced` of its `want` new bytes already: `used`
+// compressed bytes give `made` bytes at dstBase + produced (descs: src_off from data + at).  The first member of a fill is taken
+// whatever its size; a later one that would pass `want` ends the fill (full); one that would pass compCap ends this call only;
+// what does not parse as a member ends both (foreign).  BgzfParallelReader::next's rule; no device call, no exception.
+struct BgzfPick { size_t used = 0; uint64_t made = 0; bool foreign = false, full = false; };
+inline BgzfPick pickBgzfMembers(const unsigned char *data, size_t size, size_t at, uint64_t dstBase, uint64_t produced, uint64_t want,
+                                uint64_t compCap, std::vector<ts_bgzf_block> &descs) {
+    BgzfPick pick;
+    descs.clear();
+    while (at + pick.used < size) {
+        BgzfBlockRef ref{};
+        const size_t total = bgzfMemberOrNone(data + at + pick.used, size - at - pick.used, ref);
+        if (total == 0) { pick.foreign = true; break; }
+        if (produced + pick.made > 0 && produced + pick.made + ref.isize > want) { pick.full = true; break; }
+        if (!descs.empty() && pick.used + total > compCap) break;
+        ts_bgzf_block d{};
+        d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
+        d.dst_off = dstBase + produced + pick.made;
+        descs.push_back(d);
+        pick.made += ref.isize;
+        pick.used += total;
+    }
+    return pick;
+}
+
+// `used` compressed bytes at src with their members' descriptors: uploaded, inflated and checksummed on the device behind the
+// chunk's bytes from carryFrom on; a payload that is no deflate stream or fails its CRC is the host routes' exception
+inline void inflateMembers(ts_ctx *ctx, ts_chunk *chunk, const unsigned char *src, size_t used, const std::vector<ts_bgzf_block> &descs, uint64_t carryFrom) {
+    if (ts_bam_chunk_inflate(chunk, src, used, descs.data(), descs.size(), carryFrom, nullptr) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
+    ts_bgzf_status bad{};
+    if (ts_bam_chunk_status(chunk, &bad) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
+    if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
+    if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
+}
+
+// Bytes of a text input -> new bytes in a device chunk, for fastqSubsetDevice, scanFastaToFilesDevice and annotateGfaDevice.
+// The text comes from one of three sources —
+//   Plain   a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
+//   Bgzf    a BGZF regular file (bgzip output): the members are located on the host (parseBgzfBlock reads no payload byte) and
+//           inflated and checksummed on the device (ts_bam_chunk_inflate, as bamSubsetDevice does), in as many calls per fill
+//           as the compressed buffer asks for; from the first member that does not parse as BGZF on, the rest of the input is
+//           a Stream.  Behind BGZF members anything that is not gzip ends the input: zlib ignores what trails a gzip stream;
+//   Stream  anything else (plain gzip, stdin, a FIFO, a file that cannot be mapped): read in blocks, each block uploaded;
+//           through zlib where gzip starts there (or always: Options), else read(2) —
+// and a fill is read(want), which says how many bytes come (a Stream is read here), then put(chunk, carryFrom), which brings
+// them behind the chunk's bytes from carryFrom on; fill() is the two in one.
+class ChunkFeed {
+public:
+    enum Source { Plain, Bgzf, Stream };
+    struct Options {
+        std::string cannotOpen, cannotRead;                     // the route's exception texts
+        bool dashIsStdin = false;                               // `-` is stdin, always read through zlib (as fastqSubset does)
+        bool zlibAlways = false;                                // a Stream goes through zlib whatever it begins with
+        const char *growFailed = "cannot grow the device chunk", *uploadFailed = "upload of the text failed";
+        std::function<std::runtime_error(const char *)> noRoom; // the exception of a failed growth or upload; unset: deviceError
+        // told about every run of new bytes: where they lie on the host, or (host == nullptr) their offset in the chunk
+        std::function<void(const char *host, uint64_t chunkAt, uint64_t len)> sink;
+    };
+
+    ChunkFeed(ts_ctx *ctx, const std::string &file, Options options)
+        : ctx_(ctx), opt_(std::move(options)), in_(file, opt_.dashIsStdin, opt_.cannotOpen) {
+        if (in_.data) {
+            BgzfBlockRef ref{};
+            if (in_.size >= 2 && in_.data[0] == 0x1f && in_.data[1] == 0x8b) source_ = bgzfMemberOrNone(in_.data, in_.size, ref) ? Bgzf : Stream;
+            else source_ = Plain;
+        }
+        deviceInflate_ = source_ == Bgzf;
+    }
+
+    Source source() const { return source_; }
+    bool deviceInflate() const { return deviceInflate_; }       // the input began as BGZF
+    // the compressed buffer of a chunk filled with chunkBytes at a time, which the fills then keep to: an inflate call takes
+    // members of the mapped file, never more compressed bytes than the file has
+    uint64_t compCap(size_t chunkBytes) {
+        return compCap_ = source_ == Bgzf ? std::min<uint64_t>(chunkBytes + (1u << 20), std::max<size_t>(in_.size, 64)) : 64;
+    }
+    // a fill of BGZF members may exceed what it was asked for by one member: the chunk stays below the walk's limit all the same
+    uint64_t chunkLimit(uint64_t limit) const { return deviceInflate_ && limit > (1u << 17) ? limit - 65536 : limit; }
+
+    // The next fill: up to `want` bytes (BGZF: whole members, the first whatever its size).  -> how many put() brings: exact for
+    // Plain and Stream, a bound guessed from the compressed size for Bgzf (the chunk grows).  A Stream's block is read here,
+    // into `keep` where the caller wants to own it (it grows as it fills and is cut to what came).
+    uint64_t read(size_t want, std::vector<char> *keep = nullptr) {
+        want_ = want;
+        if (source_ == Plain) return std::min<uint64_t>(want, in_.size - at_);
+        if (source_ == Bgzf) return std::min<uint64_t>(want, 8 * static_cast<uint64_t>(in_.size - at_) + 65536);
+        if (!streamOpen_) openStream(0);
+        std::vector<char> &b = keep ? *keep : block_;
+        const size_t start = keep ? std::min<size_t>(want, size_t(4) << 20) : want;
+        if (b.size() < start) b.resize(start);
+        got_ = 0;
+        while (!streamDone_ && got_ < want) {
+            if (got_ == b.size()) b.resize(std::min(want, 2 * b.size()));
+            const size_t room = std::min<size_t>(std::min(b.size(), want) - got_, size_t(1) << 30);
+            const long n = in_.gz ? gzread(in_.gz, b.data() + got_, static_cast<unsigned>(room)) : static_cast<long>(::read(in_.fd, b.data() + got_, room));
+            if (n < 0) throw std::runtime_error(opt_.cannotRead);
+            if (n == 0) { streamDone_ = true; break; }
+            got_ += static_cast<size_t>(n);
+        }
+        if (keep) { b.resize(got_); b.shrink_to_fit(); }
+        blockData_ = b.data();
+        return got_;
+    }
+
+    // What read() announced, behind the chunk's bytes from carryFrom on (those in front are dropped).  -> the input is at its end
+    bool put(ts_chunk *chunk, uint64_t carryFrom) {
+        auto noRoom = [&](const char *what) { return opt_.noRoom ? opt_.noRoom(what) : deviceError(ctx_, what); };
+        if (source_ == Bgzf) {
+            // the first call drops the consumed bytes, the later ones keep what is there
+            const uint64_t carry = ts_bam_chunk_size(chunk) - carryFrom;
+            uint64_t produced = 0;
+            BgzfPick pick;
+            do {
+                pick = pickBgzfMembers(in_.data, in_.size, at_, carry, produced, want_, compCap_, descs_);
+                if (ts_chunk_reserve(chunk, carry + produced + pick.made) != TS_OK) throw noRoom(opt_.growFailed);
+                inflateMembers(ctx_, chunk, in_.data + at_, pick.used, descs_, carryFrom);
+                if (pick.made && opt_.sink) opt_.sink(nullptr, carry + produced, pick.made);
+                at_ += pick.used;
+                produced += pick.made;
+                carryFrom = 0;
+            } while (!pick.foreign && !pick.full && at_ < in_.size);
+            if (!pick.foreign) return at_ >= in_.size;
+            source_ = Stream;
+            openStream(at_);
+            return streamDone_;
+        }
+        if (source_ == Plain) {
+            const size_t n = std::min(want_, in_.size - at_);
+            if (ts_chunk_upload(chunk, in_.data + at_, n, carryFrom, nullptr) != TS_OK) throw noRoom(opt_.uploadFailed);
+            if (n && opt_.sink) opt_.sink(reinterpret_cast<const char *>(in_.data + at_), 0, n);
+            at_ += n;
+            return at_ >= in_.size;
+        }
+        if (ts_chunk_upload(chunk, blockData_, got_, carryFrom, nullptr) != TS_OK) throw noRoom(opt_.uploadFailed);
+        if (got_ && opt_.sink) opt_.sink(blockData_, 0, got_);
+        return streamDone_;
+    }
+
+    bool fill(ts_chunk *chunk, uint64_t carryFrom, size_t want) { read(want); return put(chunk, carryFrom); }
+
+private:
+    // the descriptor from `from` on; behind BGZF members (from > 0) only gzip is read
+    void openStream(size_t from) {
+        streamOpen_ = true;
+        bool gz = !in_.owned || opt_.zlibAlways;
+        if (from > 0) {
+            if (in_.size - from < 2 || in_.data[from] != 0x1f || in_.data[from + 1] != 0x8b) { streamDone_ = true; return; }
+            if (::lseek(in_.fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error(opt_.cannotRead);
+            gz = true;
+        } else if (!gz) {
+            unsigned char magic[2] = {0, 0};
+            gz = ::pread(in_.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+        }
+        if (gz) {
+            in_.gz = gzdopen(in_.fd, "rb");
+            if (!in_.gz) throw std::runtime_error(opt_.cannotOpen);
+            gzbuffer(in_.gz, 1u << 20);
+        }
+    }
+
+    ts_ctx *ctx_;
+    Options opt_;
+    MappedInput in_;
+    Source source_ = Stream;
+    bool deviceInflate_ = false, streamOpen_ = false, streamDone_ = false;
+    uint64_t compCap_ = 64;
+    size_t at_ = 0, want_ = 0, got_ = 0;                        // next byte of the mapped file; the pending fill
+    const char *blockData_ = nullptr;                               // the Stream block read() filled
+    std::vector<char> block_;
+    std::vector<ts_bgzf_block> descs_;
+};
+
+// The judge step of bamSubsetDevice and fastqSubsetDevice: reads with bases, already picked out of a chunk's table (`lens`, one
+// per read), staged into a tips-only batch's input buffer by stage(batch), judged by the scan and the predicate the host routes
+// use (ts_batch_scan + ts_batch_read_pass, with the regrow-and-rescan of an overflowed batch: include/teloscan.h), the passing
+// records' bytes gathered by gather(dPass, dst, cap, &bytes, &nPassed) into `kept`.
+struct ReadJudge {
+    double msStage = 0, msFilter = 0, msGather = 0;
+    std::vector<unsigned char> kept;
+    uint64_t bytes = 0, nPassed = 0;                            // of the last run: kept[0, bytes) are the passing records
+
+    template <typename Stage, typename Gather>
+    void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather) {
+        using Clock = std::chrono::steady_clock;
+        auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+        struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
+        if (!batch.p) throw deviceError(ctx, "cannot plan the read batch");
+        Clock::time_point t0 = Clock::now();
+        if (stage(batch.p) != TS_OK) throw deviceError(ctx, stageFailed);
+        void *dPass = ts_bam_chunk_pass_buffer(chunk, lens.size());
+        if (!dPass) throw deviceError(ctx, "cannot allocate the pass bytes");
+        msStage += since(t0); t0 = Clock::now();
+        if (ts_batch_scan(batch.p, nullptr, nullptr) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK) throw deviceError(ctx, "read filter failed");
+        int overflowed = 0;
+        if (ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK) throw deviceError(ctx, "read filter failed");
+        if (overflowed) {                                       // regrow + rescan, then judge again
+            if (ts_batch_sync(batch.p) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK ||
+                ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed) throw deviceError(ctx, "read filter failed");
+        }
+        msFilter += since(t0); t0 = Clock::now();
+        bytes = nPassed = 0;
+        if (kept.size() < (1u << 20)) kept.resize(1u << 20);
+        int rc = gather(dPass, kept.data(), kept.size(), &bytes, &nPassed);
+        if (rc == TS_ERR_INVALID_ARG && bytes > kept.size()) {
+            kept.resize(static_cast<size_t>(bytes));
+            rc = gather(dPass, kept.data(), kept.size(), &bytes, &nPassed);
+        }
+        if (rc != TS_OK) throw deviceError(ctx, "gather of the passing records failed");
+        msGather += since(t0);
+    }
+};
+
+}  // namespace detail
+
 // The device route of --bam-subset (same arguments, statistics, exceptions and output bytes as bamSubset, which stays the
-// default): the compressed BGZF members cross PCIe and the uncompressed BAM stream exists in HBM only.  Per chunk of
-// ~bytesPerBatch uncompressed bytes: the members are located on the host (parseBgzfBlock reads no payload byte), inflated and
-// checksummed on the device (ts_bam_chunk_inflate), the records walked and validated there (ts_bam_chunk_walk: the table
-// comes back), SEQ decoded into a tips-only batch's input buffer (ts_bam_chunk_decode), judged by the scan and the predicate
-// the host route uses (ts_batch_scan + ts_batch_read_pass), and the passing records' bytes gathered (ts_bam_chunk_gather).
+// default): the compressed BGZF members cross PCIe and the uncompressed BAM stream exists in HBM only.  The input is
+// detail::MappedInput's (a pipe and stdin are read to their end).  Per chunk of ~bytesPerBatch uncompressed bytes: the members
+// are located on the host (parseBgzfBlock reads no payload byte), inflated and checksummed on the device
+// (detail::inflateMembers), the records walked and validated there (ts_bam_chunk_walk: the table comes back), SEQ decoded into
+// a tips-only batch's input buffer (ts_bam_chunk_decode), judged and the passing records' bytes gathered (detail::ReadJudge
+// with ts_bam_chunk_gather).
 // The BAM header is parsed on the host from the chunk's leading bytes.  Runs on the filter's first context.
 // What a maintainer of the reference would call from runBamSubsetMode (src/bam.cpp:262-316) in place of subsetBam.
 inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                       size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
     BamSubsetStats stats;
     ts_ctx *ctx = filter.context(0);
-    auto fail = [&](const char *what) -> std::runtime_error {
-        const char *why = ts_last_error(ctx);
-        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
-    };
-    int fd = 0;
-    if (inFile != "-") {
-        fd = ::open(inFile.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("cannot open BAM input '" + inFile + "'");
-    }
-    struct Closer { int fd; ~Closer() { if (fd > 0) ::close(fd); } } closer{fd};
+    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
     // the compressed input: a regular file is mapped, a pipe is read to its end
-    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
+    detail::MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
     std::vector<unsigned char> piped;
-    const unsigned char *data = nullptr;
-    size_t size = 0;
-    {
-        struct stat st;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
-        }
-        if (mapping.p) { data = static_cast<const unsigned char *>(mapping.p); size = mapping.n; }
-        else {
-            for (;;) {
-                const size_t at = piped.size();
-                piped.resize(at + (8u << 20));
-                const ssize_t r = ::read(fd, piped.data() + at, 8u << 20);
-                if (r < 0) throw std::runtime_error("cannot read BAM input");
-                piped.resize(at + static_cast<size_t>(r));
-                if (r == 0) break;
-            }
-            data = piped.data(); size = piped.size();
-        }
-    }
+    if (!in.data) in.readToEnd(piped, "cannot read BAM input");
+    const unsigned char *data = in.data ? in.data : piped.data();
+    const size_t size = in.data ? in.size : piped.size();
     auto le32 = [](const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); };
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    double msInflate = 0, msWalk = 0, msDecode = 0, msFilter = 0, msGather = 0, msWrite = 0;
+    double msInflate = 0, msWalk = 0, msWrite = 0;
 
     // a chunk holds the unconsumed tail of the one before (at most a record: 4 bytes + 256 MiB) and the new members' output
     const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 1u << 20);
@@ -1428,39 +1669,21 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     std::vector<ts_bgzf_block> descs;
     std::vector<ts_bam_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), withSeq;
     std::vector<uint64_t> lens;
-    std::vector<unsigned char> kept;
+    detail::ReadJudge judged;
     auto judge = [&](const ts_bam_record *r, size_t n) {      // one sub-batch of records, in input order
         withSeq.clear(); lens.clear();
         for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { withSeq.push_back(r[i]); lens.push_back(r[i].l_seq); }
         stats.totalRecords += n;
         stats.missingSequenceRecords += n - withSeq.size();
         if (withSeq.empty()) return;
-        struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
-        if (!batch.p) throw fail("cannot plan the read batch");
-        Clock::time_point t0 = Clock::now();
-        if (ts_bam_chunk_decode(chunk.p, withSeq.data(), withSeq.size(), batch.p, nullptr) != TS_OK) throw fail("SEQ decode failed");
-        void *dPass = ts_bam_chunk_pass_buffer(chunk.p, withSeq.size());
-        if (!dPass) throw fail("cannot allocate the pass bytes");
-        msDecode += since(t0); t0 = Clock::now();
-        if (ts_batch_scan(batch.p, nullptr, nullptr) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK) throw fail("read filter failed");
-        int overflowed = 0;
-        if (ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK) throw fail("read filter failed");
-        if (overflowed) {                                       // regrow + rescan, then judge again (include/teloscan.h)
-            if (ts_batch_sync(batch.p) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK ||
-                ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed) throw fail("read filter failed");
-        }
-        msFilter += since(t0); t0 = Clock::now();
-        uint64_t bytes = 0, nPassed = 0;
-        if (kept.size() < (1u << 20)) kept.resize(1u << 20);
-        int rc = ts_bam_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
-        if (rc == TS_ERR_INVALID_ARG && bytes > kept.size()) {
-            kept.resize(static_cast<size_t>(bytes));
-            rc = ts_bam_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
-        }
-        if (rc != TS_OK) throw fail("gather of the passing records failed");
-        msGather += since(t0); t0 = Clock::now();
-        writer.write(kept.data(), static_cast<size_t>(bytes));
-        stats.passedRecords += nPassed;
+        judged.run(ctx, chunk.p, lens, "SEQ decode failed",
+                   [&](ts_batch *batch) { return ts_bam_chunk_decode(chunk.p, withSeq.data(), withSeq.size(), batch, nullptr); },
+                   [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                       return ts_bam_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                   });
+        const Clock::time_point t0 = Clock::now();
+        writer.write(judged.kept.data(), static_cast<size_t>(judged.bytes));
+        stats.passedRecords += judged.nPassed;
         msWrite += since(t0);
     };
 
@@ -1471,6 +1694,8 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
         descs.clear();
         size_t used = 0;
         uint64_t produced = 0;
+        // (not pickBgzfMembers: here a member that does not parse is an error, not a change of source, a chunk never takes a member
+        // past chunkBytes, and there is one inflate call per chunk)
         while (at + used < size) {                              // the members of this chunk (BgzfParallelReader::next's rule)
             detail::BgzfBlockRef ref{};
             bool eofm = false;
@@ -1487,12 +1712,8 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
         }
         if (carry + produced > plainCap) throw std::runtime_error("BAM header is too large for the device route");
         Clock::time_point t0 = Clock::now();
-        if (ts_bam_chunk_inflate(chunk.p, data + at, used, descs.data(), descs.size(), pos, nullptr) != TS_OK) throw fail("BGZF inflate failed");
-        ts_bgzf_status bad{};
-        if (ts_bam_chunk_status(chunk.p, &bad) != TS_OK) throw fail("BGZF inflate failed");
+        detail::inflateMembers(ctx, chunk.p, data + at, used, descs, pos);
         msInflate += since(t0);
-        if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
-        if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
         at += used;
         more = used > 0 && at < size;
         held = carry + produced; pos = 0;
@@ -1521,135 +1742,58 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     writer.finish();
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "bamSubsetDevice: upload + inflate + CRC %.0f ms, walk %.0f ms, decode %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
-                     msInflate, msWalk, msDecode, msFilter, msGather, msWrite);
+                     msInflate, msWalk, judged.msStage, judged.msFilter, judged.msGather, msWrite);
     return stats;
 }
 
 // The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as
 // fastqSubset, which stays the default): the FASTQ text exists in HBM one chunk of ~bytesPerBatch bytes at a time and the host
-// reads none of it.  The text gets there from one of three sources —
-//   1. a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
-//   2. a BGZF regular file (bgzip output): the members are located on the host (parseBgzfBlock reads no payload byte) and
-//      inflated and checksummed on the device (ts_bam_chunk_inflate, as bamSubsetDevice does); from the first member that does
-//      not parse as BGZF on, the rest of the input takes source 3;
-//   3. anything else (plain gzip, stdin, a FIFO, a file that cannot be mapped): through zlib or read(2) in blocks, as
-//      fastqSubset's `fill` reads them, each block uploaded —
-// and behind the source the stages are the same: lines indexed and records framed and validated (ts_fastq_chunk_walk: the table
-// comes back), sequences staged into a tips-only batch's input buffer (ts_fastq_chunk_stage), judged by the scan and the
-// predicate the host route uses (ts_batch_scan + ts_batch_read_pass), and the passing records' bytes gathered
-// (ts_fastq_chunk_gather).  The bytes behind the last whole record stay in the chunk for the next fill; a record larger than a
+// reads none of it.  The text gets there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, or a
+// stream through zlib or read(2); `-` is stdin, always through zlib), and behind the source the stages are the same: lines
+// indexed and records framed and validated (ts_fastq_chunk_walk: the table comes back), sequences staged into a tips-only
+// batch's input buffer (ts_fastq_chunk_stage), judged and the passing records' bytes gathered (detail::ReadJudge with
+// ts_fastq_chunk_gather).  The bytes behind the last whole record stay in the chunk for the next fill; a record larger than a
 // chunk makes the chunk grow.  Runs on the filter's first context.
 // What a maintainer of the reference would call from Input::readFastqSubset (src/input.cpp:737-832) in place of its loop.
 inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                            size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
     FastqSubsetResult res;
     ts_ctx *ctx = filter.context(0);
-    auto fail = [&](const char *what) -> std::runtime_error {
-        const char *why = ts_last_error(ctx);
-        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
-    };
-    int fd = 0;
-    if (inFile != "-") {
-        fd = ::open(inFile.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("Stream not successful: " + inFile);
-    }
-    struct Closer { int fd; gzFile gz = nullptr; ~Closer() { if (gz) gzclose(gz); else if (fd > 0) ::close(fd); } } closer{fd};
-    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
-    {
-        struct stat st;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
-        }
-    }
-    const unsigned char *data = static_cast<const unsigned char *>(mapping.p);
-    const size_t size = mapping.n;
-    // the BGZF member at p (its total size), or 0: what is there does not parse as a whole BGZF member
-    auto bgzfMember = [](const unsigned char *p, size_t n, detail::BgzfBlockRef &ref, bool &eofm) -> size_t {
-        try { return detail::parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
-    };
-    enum { Plain, Bgzf, Stream } source = Stream;
-    if (data) {
-        detail::BgzfBlockRef ref{};
-        bool eofm = false;
-        if (size >= 2 && data[0] == 0x1f && data[1] == 0x8b) source = bgzfMember(data, size, ref, eofm) ? Bgzf : Stream;
-        else source = Plain;
-    }
-    // source 3 reads the descriptor from `from` on, through zlib where gzip starts there (stdin always, as fastqSubset does).
-    // Behind BGZF members (from > 0) anything that is not gzip ends the input: zlib ignores what trails a gzip stream.
-    const bool deviceInflate = source == Bgzf;
-    bool streamOpen = false, streamDone = false;
-    auto openStream = [&](size_t from) {
-        streamOpen = true;
-        bool gz = fd == 0;
-        if (from > 0) {
-            if (size - from < 2 || data[from] != 0x1f || data[from + 1] != 0x8b) { streamDone = true; return; }
-            if (::lseek(fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error("read error in FASTQ input");
-            gz = true;
-        } else if (!gz) {
-            unsigned char magic[2] = {0, 0};
-            gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        }
-        if (gz) {
-            closer.gz = gzdopen(fd, "rb");
-            if (!closer.gz) throw std::runtime_error("Stream not successful: " + inFile);
-            gzbuffer(closer.gz, 1u << 20);
-        }
-    };
-    auto get = [&](char *dst, size_t n) -> long {
-        if (closer.gz) return gzread(closer.gz, dst, static_cast<unsigned>(std::min<size_t>(n, 1u << 30)));
-        return static_cast<long>(::read(fd, dst, std::min<size_t>(n, 1u << 30)));
-    };
+    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
+    detail::ChunkFeed::Options options;
+    options.cannotOpen = "Stream not successful: " + inFile;
+    options.cannotRead = "read error in FASTQ input";
+    options.dashIsStdin = true;
+    options.uploadFailed = "upload of the FASTQ text failed";
+    detail::ChunkFeed feed(ctx, inFile, options);
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    double msUpload = 0, msIndex = 0, msStage = 0, msFilter = 0, msGather = 0, msWrite = 0;
+    double msUpload = 0, msIndex = 0, msWrite = 0;
 
     const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 64);
-    const uint64_t compCap = source == Bgzf ? chunkBytes + (1u << 20) : 64;
-    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, compCap, chunkBytes)};
+    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, feed.compCap(chunkBytes), chunkBytes)};
     if (!chunk.p) throw fail("cannot make the device chunk");
 
     std::vector<ts_fastq_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16)), withSeq;
     std::vector<uint64_t> lens;
-    std::vector<unsigned char> kept;
-    std::vector<char> block;
-    std::vector<ts_bgzf_block> descs;
+    detail::ReadJudge judged;
     auto judge = [&](const ts_fastq_record *r, size_t n) {      // one sub-batch of records, in input order
         withSeq.clear(); lens.clear();
         for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { withSeq.push_back(r[i]); lens.push_back(r[i].seq_len - r[i].seq_cr); }
         res.total += n;
         if (withSeq.empty()) return;                            // (a read without bases is never kept)
-        struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
-        if (!batch.p) throw fail("cannot plan the read batch");
-        Clock::time_point t0 = Clock::now();
-        if (ts_fastq_chunk_stage(chunk.p, withSeq.data(), withSeq.size(), batch.p, nullptr) != TS_OK) throw fail("staging the sequences failed");
-        void *dPass = ts_bam_chunk_pass_buffer(chunk.p, withSeq.size());
-        if (!dPass) throw fail("cannot allocate the pass bytes");
-        msStage += since(t0); t0 = Clock::now();
-        if (ts_batch_scan(batch.p, nullptr, nullptr) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK) throw fail("read filter failed");
-        int overflowed = 0;
-        if (ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK) throw fail("read filter failed");
-        if (overflowed) {                                       // regrow + rescan, then judge again (include/teloscan.h)
-            if (ts_batch_sync(batch.p) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK ||
-                ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed) throw fail("read filter failed");
-        }
-        msFilter += since(t0); t0 = Clock::now();
-        uint64_t bytes = 0, nPassed = 0;
-        if (kept.size() < (1u << 20)) kept.resize(1u << 20);
-        int rc = ts_fastq_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
-        if (rc == TS_ERR_INVALID_ARG && bytes > kept.size()) {
-            kept.resize(static_cast<size_t>(bytes));
-            rc = ts_fastq_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, kept.data(), kept.size(), &bytes, &nPassed, nullptr);
-        }
-        if (rc != TS_OK) throw fail("gather of the passing records failed");
-        msGather += since(t0); t0 = Clock::now();
-        out.write(reinterpret_cast<const char *>(kept.data()), static_cast<std::streamsize>(bytes));
+        judged.run(ctx, chunk.p, lens, "staging the sequences failed",
+                   [&](ts_batch *batch) { return ts_fastq_chunk_stage(chunk.p, withSeq.data(), withSeq.size(), batch, nullptr); },
+                   [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                       return ts_fastq_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                   });
+        const Clock::time_point t0 = Clock::now();
+        out.write(reinterpret_cast<const char *>(judged.kept.data()), static_cast<std::streamsize>(judged.bytes));
         if (!out.good()) throw std::runtime_error("failed while writing FASTQ subset");
-        res.kept += nPassed;
+        res.kept += judged.nPassed;
         msWrite += since(t0);
     };
 
-    size_t at = 0;                              // next byte of the mapped file (sources 1 and 2)
     uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
     bool first = true, atEnd = false;
     while (!atEnd) {
@@ -1657,59 +1801,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
         // a chunk that held no whole record (a record larger than it) takes as much again
         const size_t want = static_cast<size_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0));
         Clock::time_point t0 = Clock::now();
-        if (source == Bgzf) {
-            // members until the chunk has `want` new bytes (BgzfParallelReader::next's rule), in as many inflate calls as the
-            // compressed buffer asks for: the first drops the consumed bytes, the later ones keep what is there
-            uint64_t produced = 0, from = pos;
-            bool foreign = false, full = false;
-            do {
-                descs.clear();
-                size_t used = 0;
-                uint64_t made = 0;
-                while (at + used < size) {
-                    detail::BgzfBlockRef ref{};
-                    bool eofm = false;
-                    const size_t total = bgzfMember(data + at + used, size - at - used, ref, eofm);
-                    if (total == 0) { foreign = true; break; }
-                    if (produced + made > 0 && produced + made + ref.isize > want) { full = true; break; }
-                    if (!descs.empty() && used + total > compCap) break;
-                    ts_bgzf_block d{};
-                    d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
-                    d.dst_off = carry + produced + made;
-                    descs.push_back(d);
-                    made += ref.isize;
-                    used += total;
-                }
-                if (ts_chunk_reserve(chunk.p, carry + produced + made) != TS_OK) throw fail("cannot grow the device chunk");
-                if (ts_bam_chunk_inflate(chunk.p, data + at, used, descs.data(), descs.size(), from, nullptr) != TS_OK) throw fail("BGZF inflate failed");
-                ts_bgzf_status bad{};
-                if (ts_bam_chunk_status(chunk.p, &bad) != TS_OK) throw fail("BGZF inflate failed");
-                if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
-                if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
-                at += used;
-                produced += made;
-                from = 0;
-            } while (!foreign && !full && at < size);
-            if (foreign) { source = Stream; openStream(at); atEnd = streamDone; }
-            else atEnd = at >= size;
-        } else if (source == Plain) {
-            const size_t n = std::min(want, size - at);
-            if (ts_chunk_upload(chunk.p, data + at, n, pos, nullptr) != TS_OK) throw fail("upload of the FASTQ text failed");
-            at += n;
-            atEnd = at >= size;
-        } else {
-            if (!streamOpen) openStream(0);
-            if (block.size() < want) block.resize(want);
-            size_t got = 0;
-            while (!streamDone && got < want) {
-                const long n = get(block.data() + got, want - got);
-                if (n < 0) throw std::runtime_error("read error in FASTQ input");
-                if (n == 0) { streamDone = true; break; }
-                got += static_cast<size_t>(n);
-            }
-            if (ts_chunk_upload(chunk.p, block.data(), got, pos, nullptr) != TS_OK) throw fail("upload of the FASTQ text failed");
-            atEnd = streamDone;
-        }
+        atEnd = feed.fill(chunk.p, pos, want);
         msUpload += since(t0);
         held = ts_bam_chunk_size(chunk.p); pos = 0;
         if (first) {
@@ -1743,7 +1835,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
     out.flush();
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "fastqSubsetDevice: upload%s %.0f ms, index %.0f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
-                     deviceInflate ? " + inflate + CRC" : "", msUpload, msIndex, msStage, msFilter, msGather, msWrite);
+                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, judged.msStage, judged.msFilter, judged.msGather, msWrite);
     return res;
 }
 
@@ -2542,13 +2634,8 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
 
 // The device route of the assembly scan (same files, console report and AssemblySummary as scanFastaToFiles, which stays the
 // default): the FASTA text exists in HBM one chunk of ~chunkBytes bytes at a time, and without -m the host reads none of it.
-// The text gets there from the three sources of fastqSubsetDevice —
-//   1. a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
-//   2. a BGZF regular file (bgzip output): members located on the host, inflated and checksummed on the device
-//      (ts_bam_chunk_inflate); from the first member that does not parse as BGZF on, the rest of the input takes source 3;
-//   3. anything else (plain gzip, a FIFO, a file that cannot be mapped): through zlib or read(2) in blocks, each block uploaded —
-// (the fill below is a second copy of fastqSubsetDevice's: that one is woven into its FASTQ checks, and it stays untouched)
-// and per chunk: lines indexed, records framed, names gathered (ts_fasta_chunk_walk); body lines joined into contiguous bases and
+// The text gets there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, or a stream through zlib
+// or read(2)), and per chunk: lines indexed, records framed, names gathered (ts_fasta_chunk_walk); body lines joined into contiguous bases and
 // the N-runs found (ts_fasta_chunk_join, ts_fasta_chunk_runs); PathComponents built from the runs, a few entries per record;
 // every segment handed to the scan as a device segment through walkRecordViews, so that blocks, counts and windows come back
 // exactly as for the host route; BedWriter fed.  With -m the joined bases are read back once per chunk (matchSeq needs them).
@@ -2572,65 +2659,19 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
                                  " (the joined bases lie in one device's memory)");
     const UserInputTeloscope &ui = teloscope.input();
     ts_ctx *ctx = teloscope.context();
-    auto fail = [&](const char *what) -> std::runtime_error {
-        const char *why = ts_last_error(ctx);
-        return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
-    };
+    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
     chunkLimit = std::max<uint64_t>(std::min<uint64_t>(chunkLimit, 0xfffffffeull), 64);
-    const int fd = ::open(fastaFile.c_str(), O_RDONLY);
-    if (fd < 0) throw std::runtime_error("cannot open " + fastaFile);
-    struct Closer { int fd; gzFile gz = nullptr; ~Closer() { if (gz) gzclose(gz); else ::close(fd); } } closer{fd};
-    struct Mapping { void *p = nullptr; size_t n = 0; ~Mapping() { if (p) ::munmap(p, n); } } mapping;
-    {
-        struct stat st;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) { mapping.p = m; mapping.n = static_cast<size_t>(st.st_size); ::madvise(m, mapping.n, MADV_SEQUENTIAL); }
-        }
-    }
-    const unsigned char *data = static_cast<const unsigned char *>(mapping.p);
-    const size_t size = mapping.n;
-    auto bgzfMember = [](const unsigned char *p, size_t n, detail::BgzfBlockRef &ref, bool &eofm) -> size_t {
-        try { return detail::parseBgzfBlock(p, n, ref, eofm); } catch (const std::runtime_error &) { return 0; }
-    };
-    enum { Plain, Bgzf, Stream } source = Stream;
-    if (data) {
-        detail::BgzfBlockRef ref{};
-        bool eofm = false;
-        if (size >= 2 && data[0] == 0x1f && data[1] == 0x8b) source = bgzfMember(data, size, ref, eofm) ? Bgzf : Stream;
-        else source = Plain;
-    }
-    const bool deviceInflate = source == Bgzf;
-    // (a fill of BGZF members may exceed what it was asked for by one member: the chunk stays below the walk's limit all the same)
-    if (deviceInflate && chunkLimit > (1u << 17)) chunkLimit -= 65536;
-    bool streamOpen = false, streamDone = false;
-    auto openStream = [&](size_t from) {
-        streamOpen = true;
-        bool gz = false;
-        if (from > 0) {                                         // behind BGZF members anything that is not gzip ends the input
-            if (size - from < 2 || data[from] != 0x1f || data[from + 1] != 0x8b) { streamDone = true; return; }
-            if (::lseek(fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error("read error in " + fastaFile);
-            gz = true;
-        } else {
-            unsigned char magic[2] = {0, 0};
-            gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        }
-        if (gz) {
-            closer.gz = gzdopen(fd, "rb");
-            if (!closer.gz) throw std::runtime_error("cannot open " + fastaFile);
-            gzbuffer(closer.gz, 1u << 20);
-        }
-    };
-    auto get = [&](char *dst, size_t n) -> long {
-        if (closer.gz) return gzread(closer.gz, dst, static_cast<unsigned>(std::min<size_t>(n, 1u << 30)));
-        return static_cast<long>(::read(fd, dst, std::min<size_t>(n, 1u << 30)));
-    };
+    detail::ChunkFeed::Options options;
+    options.cannotOpen = "cannot open " + fastaFile;
+    options.cannotRead = "read error in " + fastaFile;
+    options.uploadFailed = "upload of the FASTA text failed";
+    detail::ChunkFeed feed(ctx, fastaFile, options);
+    chunkLimit = feed.chunkLimit(chunkLimit);
     double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;
     ScanFastaTimes T;
 
     const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
-    const uint64_t compCap = source == Bgzf ? chunkBytes + (1u << 20) : 64;
-    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, compCap, chunkBytes)};
+    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, feed.compCap(chunkBytes), chunkBytes)};
     if (!chunk.p) throw fail("cannot make the device chunk");
 
     BedWriter writer(outBase, ui, console, manualCuration);
@@ -2641,14 +2682,12 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
     const bool useTrackText = deviceTracks && !ui.outMatches;
     TrackText trackText;
     std::vector<ts_fasta_record> recs(4096);
-    std::vector<char> names(size_t(1) << 16), block, hostBases;
+    std::vector<char> names(size_t(1) << 16), hostBases;
     std::vector<ts_fasta_run> runs(4096);
     std::vector<uint64_t> offsets;
-    std::vector<ts_bgzf_block> descs;
     std::vector<std::string> headers;
     size_t recordsDone = 0;
 
-    size_t at = 0;                              // next byte of the mapped file (sources 1 and 2)
     uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
     bool atEnd = false;
     while (!atEnd) {
@@ -2665,57 +2704,7 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
         }
         const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0), chunkLimit - carry));
         Clock::time_point t0 = Clock::now();
-        if (source == Bgzf) {
-            uint64_t produced = 0, from = pos;
-            bool foreign = false, full = false;
-            do {
-                descs.clear();
-                size_t used = 0;
-                uint64_t made = 0;
-                while (at + used < size) {
-                    detail::BgzfBlockRef ref{};
-                    bool eofm = false;
-                    const size_t total = bgzfMember(data + at + used, size - at - used, ref, eofm);
-                    if (total == 0) { foreign = true; break; }
-                    if (produced + made > 0 && produced + made + ref.isize > want) { full = true; break; }
-                    if (!descs.empty() && used + total > compCap) break;
-                    ts_bgzf_block d{};
-                    d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
-                    d.dst_off = carry + produced + made;
-                    descs.push_back(d);
-                    made += ref.isize;
-                    used += total;
-                }
-                if (ts_chunk_reserve(chunk.p, carry + produced + made) != TS_OK) throw fail("cannot grow the device chunk");
-                if (ts_bam_chunk_inflate(chunk.p, data + at, used, descs.data(), descs.size(), from, nullptr) != TS_OK) throw fail("BGZF inflate failed");
-                ts_bgzf_status bad{};
-                if (ts_bam_chunk_status(chunk.p, &bad) != TS_OK) throw fail("BGZF inflate failed");
-                if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
-                if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
-                at += used;
-                produced += made;
-                from = 0;
-            } while (!foreign && !full && at < size);
-            if (foreign) { source = Stream; openStream(at); atEnd = streamDone; }
-            else atEnd = at >= size;
-        } else if (source == Plain) {
-            const size_t n = std::min(want, size - at);
-            if (ts_chunk_upload(chunk.p, data + at, n, pos, nullptr) != TS_OK) throw fail("upload of the FASTA text failed");
-            at += n;
-            atEnd = at >= size;
-        } else {
-            if (!streamOpen) openStream(0);
-            if (block.size() < want) block.resize(want);
-            size_t got = 0;
-            while (!streamDone && got < want) {
-                const long n = get(block.data() + got, want - got);
-                if (n < 0) throw std::runtime_error("read error in " + fastaFile);
-                if (n == 0) { streamDone = true; break; }
-                got += static_cast<size_t>(n);
-            }
-            if (ts_chunk_upload(chunk.p, block.data(), got, pos, nullptr) != TS_OK) throw fail("upload of the FASTA text failed");
-            atEnd = streamDone;
-        }
+        atEnd = feed.fill(chunk.p, pos, want);
         msUpload += since(t0);
         held = ts_bam_chunk_size(chunk.p); pos = 0;
         if (held == 0) continue;
@@ -2784,7 +2773,7 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
     msWrite += since(tf);
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "scanFastaToFilesDevice: upload%s %.0f ms, index %.0f ms, join %.0f ms, scan %.0f ms, write %.0f ms\n",
-                     deviceInflate ? " + inflate + CRC" : "", msUpload, msIndex, msJoin, msScan, msWrite);
+                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msJoin, msScan, msWrite);
     T.read_ms = msUpload + msIndex + msJoin; T.scan_ms = msScan; T.write_ms = msWrite; T.wall_ms = since(tBegin);
     if (times) *times = T;
     return sum;

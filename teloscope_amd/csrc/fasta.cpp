@@ -44,22 +44,11 @@ int ts_fasta_chunk_walk(ts_chunk *ch, int at_end, ts_fasta_record *recs, uint64_
     static_assert(sizeof out <= 64, "the result block has 64 bytes");
 
     // lines: the FASTQ walk's index ('\n' per slice, their sums, every line's start, first byte and '\r')
-    unsigned long long *d_lines_out = (unsigned long long *)ch->d_out.p;
-    const uint64_t slices = ceil_div(size, kFastqSliceBytes);
-    HIP_TRY(ctx, ch->d_waves.ensure((size_t)slices * 4));
-    if (ts_k_launch_fastq_count(ch->d_plain.p, size, (uint32_t *)ch->d_waves.p, d_lines_out, nullptr) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_walk: kernel launch failed");
-    unsigned long long lines_out[2];
-    HIP_TRY(ctx, hipMemcpy(lines_out, d_lines_out, sizeof lines_out, hipMemcpyDeviceToHost));
-    const uint64_t newlines = lines_out[kFqNewlines], tail = lines_out[kFqTail];
-    if (newlines > size || tail > 1) return ctx->fail(TS_ERR_STATE, "ts_fasta_chunk_walk: the line count left the chunk");
-    const uint64_t n_lines = newlines + (at_end ? tail : 0), slots = newlines + 2;
-    HIP_TRY(ctx, ch->d_lines.ensure((size_t)slots * 6));
-    uint32_t *lstart = (uint32_t *)ch->d_lines.p;
-    unsigned char *first = (unsigned char *)ch->d_lines.p + slots * 4, *cr = first + slots;
-    if (ts_k_launch_fastq_index(ch->d_plain.p, size, (const uint32_t *)ch->d_waves.p, (uint32_t)newlines, (uint32_t)tail, lstart, first,
-                                cr, nullptr) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_walk: kernel launch failed");
+    FastqLineIndex ix;
+    { const int rc = ts_chunk_line_index(ch, at_end, "ts_fasta_chunk_walk", "line", &ix); if (rc != TS_OK) return rc; }
+    const uint64_t newlines = ix.newlines, n_lines = ix.n_lines;
+    uint32_t *lstart = ix.lstart;
+    unsigned char *first = ix.first, *cr = ix.cr;
 
     // header lines: per slice of lines, their sums, every header's place
     const uint64_t n_frames = ceil_div(n_lines, kFastaSliceLines);

@@ -15,6 +15,29 @@ bool record_ok(const ts_bam_chunk *ch, const ts_fastq_record &r) {
 
 }  // namespace
 
+int ts_chunk_line_index(ts_bam_chunk *ch, int at_end, const char *who, const char *counted, FastqLineIndex *ix) {
+    ts_ctx *ctx = ch->ctx;
+    const std::string name = who;
+    const uint64_t size = ch->plain_n;
+    unsigned long long *d_out = (unsigned long long *)ch->d_out.p;
+    HIP_TRY(ctx, ch->d_waves.ensure((size_t)ceil_div(size, kFastqSliceBytes) * 4));
+    if (ts_k_launch_fastq_count(ch->d_plain.p, size, (uint32_t *)ch->d_waves.p, d_out, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, name + ": kernel launch failed");
+    unsigned long long out[2];
+    HIP_TRY(ctx, hipMemcpy(out, d_out, sizeof out, hipMemcpyDeviceToHost));
+    const uint64_t newlines = out[kFqNewlines], tail = out[kFqTail];
+    if (newlines > size || tail > 1) return ctx->fail(TS_ERR_STATE, name + ": the " + counted + " count left the chunk");
+    const uint64_t slots = newlines + 2;
+    HIP_TRY(ctx, ch->d_lines.ensure((size_t)slots * 6));
+    ix->newlines = newlines; ix->tail = tail; ix->n_lines = newlines + (at_end ? tail : 0);
+    ix->lstart = (uint32_t *)ch->d_lines.p;
+    ix->first = (unsigned char *)ch->d_lines.p + slots * 4; ix->cr = ix->first + slots;
+    if (ts_k_launch_fastq_index(ch->d_plain.p, size, (const uint32_t *)ch->d_waves.p, (uint32_t)newlines, (uint32_t)tail, ix->lstart, ix->first,
+                                ix->cr, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, name + ": kernel launch failed");
+    return TS_OK;
+}
+
 extern "C" {
 
 int ts_chunk_reserve(ts_chunk *ch, uint64_t plain_cap) {
@@ -68,20 +91,11 @@ int ts_fastq_chunk_walk(ts_chunk *ch, int at_end, ts_fastq_record *recs, uint64_
     static_assert(sizeof out <= 64, "the chunk's result block has 64 bytes");
 
     // lines: '\n' per slice, their sums, every line's start
-    const uint64_t slices = ceil_div(size, kFastqSliceBytes);
-    HIP_TRY(ctx, ch->d_waves.ensure((size_t)slices * 4));
-    if (ts_k_launch_fastq_count(ch->d_plain.p, size, (uint32_t *)ch->d_waves.p, d_out, nullptr) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_fastq_chunk_walk: kernel launch failed");
-    HIP_TRY(ctx, hipMemcpy(out, d_out, 2 * sizeof out[0], hipMemcpyDeviceToHost));
-    const uint64_t newlines = out[kFqNewlines], tail = out[kFqTail];
-    if (newlines > size || tail > 1) return ctx->fail(TS_ERR_STATE, "ts_fastq_chunk_walk: the line count left the chunk");
-    const uint64_t n_lines = newlines + (at_end ? tail : 0), slots = newlines + 2;
-    HIP_TRY(ctx, ch->d_lines.ensure((size_t)slots * 6));
-    uint32_t *lstart = (uint32_t *)ch->d_lines.p;
-    unsigned char *first = (unsigned char *)ch->d_lines.p + slots * 4, *cr = first + slots;
-    if (ts_k_launch_fastq_index(ch->d_plain.p, size, (const uint32_t *)ch->d_waves.p, (uint32_t)newlines, (uint32_t)tail, lstart, first,
-                                cr, nullptr) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_fastq_chunk_walk: kernel launch failed");
+    FastqLineIndex ix;
+    { const int rc = ts_chunk_line_index(ch, at_end, "ts_fastq_chunk_walk", "line", &ix); if (rc != TS_OK) return rc; }
+    const uint64_t newlines = ix.newlines, n_lines = ix.n_lines;
+    uint32_t *lstart = ix.lstart;
+    unsigned char *first = ix.first, *cr = ix.cr;
 
     // records: the slices' maps and header counts, their scan, the table
     const uint64_t n_frames = ceil_div(n_lines, kFastqSliceLines);

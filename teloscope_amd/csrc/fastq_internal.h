@@ -13,6 +13,14 @@ struct FastqFrame { uint32_t map, cnt[4], pad[3]; };        // a slice of lines:
 struct FastqEntry { uint32_t state, base; };                // a slice's entry state and the index of its first record
 struct FastqCopyJob { unsigned long long src, dst; uint32_t n, pad; };       // n bytes at plain + src -> in + dst (16-byte aligned)
 
+// The line index the FASTQ, FASTA and GFA walks begin with (fastq.cpp), on the null stream: '\n' counted per slice and summed
+// (ts_k_launch_fastq_count; its two words come back through ch->d_out and are checked against the chunk), then every line's
+// start, first byte and '\r' flag into ch->d_lines (ts_k_launch_fastq_index: launched, not waited for).  n_lines counts the
+// unfinished last line with at_end only.  A failure is "<who>: ..." in the context's error; `counted` names what "left the chunk".
+struct ts_bam_chunk;
+struct FastqLineIndex { uint64_t newlines, tail, n_lines; uint32_t *lstart; unsigned char *first, *cr; };
+int ts_chunk_line_index(ts_bam_chunk *ch, int at_end, const char *who, const char *counted, FastqLineIndex *ix);
+
 extern "C" {
 // '\n' per slice of kFastqSliceBytes -> counts[n_slices]; then (one wave) counts -> exclusive sums in place,
 // out[kFqNewlines] = their total, out[kFqTail] = 1 when the last byte is not '\n'

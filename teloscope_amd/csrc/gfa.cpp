@@ -52,31 +52,26 @@ int ts_gfa_chunk_walk(ts_chunk *ch, int at_end, ts_gfa_segment *segs, uint64_t s
     unsigned long long *d_out = (unsigned long long *)ch->d_gfa_out.p;
     unsigned long long out[kGfWords];
 
-    // lines (the FASTQ walk's index) and tabs: '\n' and '\t' per slice, their sums, every line's start and every tab's offset
-    unsigned long long *d_lines_out = (unsigned long long *)ch->d_out.p;
+    // tabs and lines (the FASTQ walk's index): '\t' and '\n' per slice, their sums, every tab's offset and every line's start.
+    // The tab count is under way before the line count's words are waited for.
     const uint64_t slices = ceil_div(size, kFastqSliceBytes);
     static_assert(kGfaSliceBytes == kFastqSliceBytes, "one slice count serves both indexes");
-    HIP_TRY(ctx, ch->d_waves.ensure((size_t)slices * 4));
     HIP_TRY(ctx, ch->d_gfa_counts.ensure((size_t)slices * 4));
     HIP_TRY(ctx, hipMemsetAsync(d_out + kGfForeignLine, 0xff, sizeof(unsigned long long), nullptr));
-    if (ts_k_launch_fastq_count(ch->d_plain.p, size, (uint32_t *)ch->d_waves.p, d_lines_out, nullptr) != 0 ||
-        ts_k_launch_gfa_tab_count(ch->d_plain.p, size, (uint32_t *)ch->d_gfa_counts.p, nullptr) != 0 ||
+    if (ts_k_launch_gfa_tab_count(ch->d_plain.p, size, (uint32_t *)ch->d_gfa_counts.p, nullptr) != 0 ||
         ts_k_launch_fasta_scan((uint32_t *)ch->d_gfa_counts.p, (uint32_t)slices, d_out + kGfTabs, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
-    unsigned long long lines_out[2], n_tabs = 0;
-    HIP_TRY(ctx, hipMemcpy(lines_out, d_lines_out, sizeof lines_out, hipMemcpyDeviceToHost));
+    FastqLineIndex ix;
+    { const int rc = ts_chunk_line_index(ch, at_end, "ts_gfa_chunk_walk", "line or tab", &ix); if (rc != TS_OK) return rc; }
+    unsigned long long n_tabs = 0;
     HIP_TRY(ctx, hipMemcpy(&n_tabs, d_out + kGfTabs, sizeof n_tabs, hipMemcpyDeviceToHost));
-    const uint64_t newlines = lines_out[kFqNewlines], tail = lines_out[kFqTail];
-    if (newlines > size || tail > 1 || n_tabs > size) return ctx->fail(TS_ERR_STATE, "ts_gfa_chunk_walk: the line or tab count left the chunk");
-    const uint64_t n_lines = newlines + (at_end ? tail : 0), slots = newlines + 2;
-    HIP_TRY(ctx, ch->d_lines.ensure((size_t)slots * 6));
+    if (n_tabs > size) return ctx->fail(TS_ERR_STATE, "ts_gfa_chunk_walk: the line or tab count left the chunk");
+    const uint64_t newlines = ix.newlines, n_lines = ix.n_lines;
     HIP_TRY(ctx, ch->d_gfa_tabs.ensure((size_t)std::max<uint64_t>(n_tabs, 1) * 4));
-    uint32_t *lstart = (uint32_t *)ch->d_lines.p;
-    unsigned char *first = (unsigned char *)ch->d_lines.p + slots * 4, *cr = first + slots;
+    uint32_t *lstart = ix.lstart;
+    unsigned char *first = ix.first, *cr = ix.cr;
     const uint32_t *tabs = (const uint32_t *)ch->d_gfa_tabs.p;
-    if (ts_k_launch_fastq_index(ch->d_plain.p, size, (const uint32_t *)ch->d_waves.p, (uint32_t)newlines, (uint32_t)tail, lstart, first,
-                                cr, nullptr) != 0 ||
-        ts_k_launch_gfa_tabs(ch->d_plain.p, size, (const uint32_t *)ch->d_gfa_counts.p, (uint32_t)n_tabs, (uint32_t *)ch->d_gfa_tabs.p, nullptr) != 0)
+    if (ts_k_launch_gfa_tabs(ch->d_plain.p, size, (const uint32_t *)ch->d_gfa_counts.p, (uint32_t)n_tabs, (uint32_t *)ch->d_gfa_tabs.p, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
 
     // kinds: per slice of lines, their sums, the lowest foreign line

@@ -1,7 +1,9 @@
 // Host-only self-test of the FASTA reader and the path splitter of include/teloscope_mi355x_io.hpp (no GPU
 // call is made): the mapped, multi-threaded reader of plain files must return what the zlib stream reader
 // returns for the same text gzip-compressed, and splitPath's 8-bytes-at-a-time scan must equal a per-character
-// walk.  Usage: io_selftest <scratch directory>
+// walk.  And of the device routes' chunk feed: which members of handmade BGZF byte strings one inflate call takes
+// (detail::pickBgzfMembers), and which source a file is read as (detail::ChunkFeed::source).
+// Usage: io_selftest <scratch directory>
 #include "teloscope_mi355x_io.hpp"
 
 #include <cstdlib>
@@ -13,10 +15,119 @@ static void check(bool ok, const char *what) {
     if (!ok) { fprintf(stderr, "io_selftest: FAILED: %s\n", what); std::exit(1); }
 }
 
+// a BGZF member holding `text` (the payload a stored deflate block: nothing here inflates it), the EOF marker, a plain gzip member
+static std::string bgzfMember(const std::string &text) {
+    auto le = [](uint32_t v, int n) { std::string o; for (int i = 0; i < n; ++i) o += static_cast<char>((v >> (8 * i)) & 0xff); return o; };
+    const uint32_t n = static_cast<uint32_t>(text.size());
+    const std::string payload = std::string(1, '\1') + le(n, 2) + le(~n, 2) + text;
+    return std::string("\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", 16) + le(static_cast<uint32_t>(18 + payload.size() + 8 - 1), 2) + payload +
+           le(static_cast<uint32_t>(crc32(crc32(0L, Z_NULL, 0), reinterpret_cast<const Bytef *>(text.data()), n)), 4) + le(n, 4);
+}
+static const std::string kBgzfEof("\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0\x1b\0\x03\0\0\0\0\0\0\0\0\0", 28);
+static std::string gzipMember(const std::string &text, const std::string &dir) {
+    const std::string path = dir + "/member.gz";
+    gzFile g = gzopen(path.c_str(), "wb");
+    check(g != nullptr, "gzopen");
+    gzwrite(g, text.data(), static_cast<unsigned>(text.size()));
+    gzclose(g);
+    std::ifstream f(path, std::ios::binary);
+    return std::string(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+}
+
+// ---- the member selection of the device routes' fill: first member always, `want`, compCap, foreign and truncated members
+static void checkMemberSelection(const std::string &dir) {
+    const size_t isize[4] = {30, 50, 70, 100};
+    std::string m[4], all;
+    for (int i = 0; i < 4; ++i) { m[i] = bgzfMember(std::string(isize[i], "ACGT"[i])); all += m[i]; }
+    std::vector<ts_bgzf_block> descs;
+    auto pick = [&](const std::string &bytes, size_t at, uint64_t dstBase, uint64_t produced, uint64_t want, uint64_t compCap) {
+        return detail::pickBgzfMembers(reinterpret_cast<const unsigned char *>(bytes.data()), bytes.size(), at, dstBase, produced, want, compCap, descs);
+    };
+    const uint64_t roomy = 1u << 20;
+    // want smaller than the first member: it is taken all the same, and the fill is full
+    detail::BgzfPick p = pick(all, 0, 0, 0, 5, roomy);
+    check(descs.size() == 1 && p.used == m[0].size() && p.made == 30 && p.full && !p.foreign, "first member beyond want");
+    check(descs[0].src_off == 18 && descs[0].payload_len == m[0].size() - 26 && descs[0].isize == 30 && descs[0].dst_off == 0, "first member's descriptor");
+    // want on a member boundary, and one byte short of it
+    p = pick(all, 0, 0, 0, 80, roomy);
+    check(descs.size() == 2 && p.used == m[0].size() + m[1].size() && p.made == 80 && p.full && !p.foreign, "want on a member boundary");
+    check(descs[1].src_off == m[0].size() + 18 && descs[1].dst_off == 30, "second member's descriptor");
+    p = pick(all, 0, 0, 0, 79, roomy);
+    check(descs.size() == 1 && p.made == 30 && p.full, "want one byte short of a member boundary");
+    // a compressed buffer for one member: the call ends, the fill does not, and dst_off runs on in the next call
+    p = pick(all, 0, 7, 0, 1000, m[0].size() + 1);
+    check(descs.size() == 1 && p.used == m[0].size() && p.made == 30 && !p.full && !p.foreign && descs[0].dst_off == 7, "compCap of one member, first call");
+    p = pick(all, m[0].size(), 7, 30, 1000, m[0].size() + 1);
+    check(descs.size() == 1 && p.used == m[1].size() && p.made == 50 && !p.full && !p.foreign, "compCap of one member, second call");
+    check(descs[0].dst_off == 7 + 30 && descs[0].src_off == 18 && descs[0].isize == 50, "dst_off runs on, src_off starts again");
+    // (the first member of a call is taken even where it alone exceeds compCap, as the first of a fill exceeds want)
+    p = pick(all, 0, 0, 0, 1000, 10);
+    check(descs.size() == 1 && p.used == m[0].size() && !p.full && !p.foreign, "compCap below one member");
+    // the whole file: neither exit, every dst_off shifted by dstBase
+    p = pick(all, 0, 1000, 0, 1000, roomy);
+    check(descs.size() == 4 && p.used == all.size() && p.made == 250 && !p.full && !p.foreign, "all members");
+    for (uint64_t i = 0, off = 1000; i < 4; off += isize[i++]) check(descs[i].dst_off == off && descs[i].isize == isize[i], "dstBase shifts every dst_off");
+    // a plain gzip member behind two BGZF members: foreign, used stops in front of it, nothing thrown
+    const std::string mixed = m[0] + m[1] + gzipMember("plain gzip text\n", dir);
+    p = pick(mixed, 0, 0, 0, 1000, roomy);
+    check(descs.size() == 2 && p.used == m[0].size() + m[1].size() && p.made == 80 && p.foreign && !p.full, "gzip member behind BGZF members");
+    p = pick(mixed, p.used, 0, 80, 1000, roomy);
+    check(descs.empty() && p.used == 0 && p.made == 0 && p.foreign, "a fill that begins at the foreign member");
+    // a truncated last member, cut in its payload and in its header
+    for (size_t cut : {size_t(5), size_t(11), m[3].size() - 1}) {
+        p = pick(all.substr(0, all.size() - m[3].size() + cut), 0, 0, 0, 1000, roomy);
+        check(descs.size() == 3 && p.used == all.size() - m[3].size() && p.made == 150 && p.foreign && !p.full, "truncated last member");
+    }
+    // the EOF marker (isize 0) in the middle, at the end and in front: a member like any other that brings no byte
+    const std::string marked = kBgzfEof + m[0] + kBgzfEof + m[1] + kBgzfEof;
+    p = pick(marked, 0, 0, 0, 1000, roomy);
+    check(descs.size() == 5 && p.used == marked.size() && p.made == 80 && !p.full && !p.foreign, "EOF markers");
+    check(descs[0].isize == 0 && descs[2].isize == 0 && descs[2].dst_off == 30 && descs[3].dst_off == 30 && descs[4].isize == 0 && descs[4].dst_off == 80, "EOF markers' descriptors");
+    p = pick(marked, 0, 0, 0, 30, roomy);                           // (a marker behind a full fill still fits: it passes nothing)
+    check(descs.size() == 3 && p.made == 30 && p.full, "EOF marker behind the last member that fits");
+    p = pick(marked, 0, 0, 0, 10, roomy);                           // (a marker in front does not use up the first member's allowance)
+    check(descs.size() == 2 && p.made == 30 && p.full, "EOF marker in front of the first member");
+}
+
+// ---- which source a file is read as: mapped plain text, mapped BGZF, or a stream (what does not map, or is gzip but not BGZF)
+static void checkSourceClassification(const std::string &dir) {
+    using Feed = detail::ChunkFeed;
+    Feed::Options options;
+    options.cannotOpen = "cannot open";
+    options.cannotRead = "cannot read";
+    const std::string text = "@r\nACGT\n+\nIIII\n";
+    auto sourceOf = [&](const std::string &name, const std::string &bytes) {
+        { std::ofstream f(dir + "/" + name, std::ios::binary); f << bytes; }
+        return Feed(nullptr, dir + "/" + name, options).source();
+    };
+    check(sourceOf("empty", "") == Feed::Stream, "an empty file is a stream");
+    check(sourceOf("plain", text) == Feed::Plain, "a text file is plain");
+    check(sourceOf("bgzf", bgzfMember(text) + kBgzfEof) == Feed::Bgzf, "a bgzip-shaped file is BGZF");
+    check(sourceOf("gzip", gzipMember(text, dir)) == Feed::Stream, "a plain gzip file is a stream");
+    check(sourceOf("magic", "\x1f\x8b") == Feed::Stream, "two bytes of gzip magic are a stream");
+    {
+        Feed feed(nullptr, dir + "/gzip", options);                     // (a stream is read without a device: through zlib here)
+        std::vector<char> block;
+        check(feed.read(1000, &block) == text.size() && std::string(block.begin(), block.end()) == text && !feed.deviceInflate(), "the gzip stream's text");
+    }
+    bool threw = false;
+    try { Feed(nullptr, dir + "/is_not_there", options); } catch (const std::runtime_error &e) { threw = std::string(e.what()) == "cannot open"; }
+    check(threw, "a missing file is the route's cannot-open exception");
+    const std::string fifo = dir + "/fifo";
+    if (::mkfifo(fifo.c_str(), 0600) == 0) {                            // (quietly left out where the directory takes no FIFO)
+        const int keep = ::open(fifo.c_str(), O_RDWR | O_NONBLOCK);     // a writer, so that the reader's open returns
+        check(keep >= 0, "open the FIFO");
+        check(Feed(nullptr, fifo, options).source() == Feed::Stream, "a FIFO is a stream");
+        ::close(keep);
+    }
+}
+
 int main(int argc, char **argv) {
     check(argc == 2, "usage: io_selftest <scratch directory>");
     const std::string dir = argv[1];
     std::mt19937_64 rng(11);
+    checkMemberSelection(dir);
+    checkSourceClassification(dir);
     // ---- splitPath against a per-character walk
     const char alpha[] = "ACGTNnXxYyOoacgtRWm";
     for (int it = 0; it < 20000; ++it) {
