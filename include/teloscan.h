@@ -902,6 +902,60 @@ const void *ts_chunk_data(const ts_chunk *chunk);
  * Ordered on `stream`; waits for it. */
 int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void *stream);
 
+/* ---- plain gzip (one long deflate stream per member, not BGZF) inflated on the device: replaces gzread in
+ *      detail::ChunkFeed::read (include/teloscope_mi355x_io.hpp) for the text routes.  A window of a member's compressed bytes
+ *      is cut into spans of span_bytes; a wave per span searches its first deflate block start (BFINAL = 0, BTYPE = 2, a
+ *      header that builds three valid codes) and decodes from there without knowing the 32 KiB in front of it (16-bit
+ *      symbols: a byte, or a marker for a byte of those 32 KiB); the host chains the spans whose start is the end of the
+ *      one before (a false candidate is stepped over and its span dropped); the chained spans' last 32 KiB are resolved in
+ *      order, then every symbol becomes a byte at its plain offset and the bytes' CRC32 is taken.  The caller parses member
+ *      headers and trailers (host work that reads no payload byte) and keeps zlib for whatever the chain did not verify: a
+ *      raw inflate primed at end_bit with the last 32 KiB as its dictionary continues at exactly that bit. */
+typedef struct ts_gzip ts_gzip;
+/* why the verified chain ended */
+#define TS_GZIP_WINDOW_END    0  /* the window's bytes ended inside a block: end_bit is the last block boundary in front of it
+                                    (start_bit: the block is larger than the window, which a larger window or zlib answers) */
+#define TS_GZIP_FINAL_BLOCK   1  /* at the end of the member's final block: end_bit is the deflate stream's end */
+#define TS_GZIP_NO_CANDIDATE  2  /* a window of four spans or more that does not begin with a dynamic block and has no candidate
+                                    behind its start (stored blocks: a file that did not compress): nothing was decoded */
+#define TS_GZIP_SPAN_OVERFLOW 3  /* a span's symbols did not fit its room (16 per compressed byte of a span, 512 Ki at least) */
+#define TS_GZIP_BAD_DEFLATE   4  /* what follows end_bit is not deflate, or reaches in front of the member's first byte */
+/* what lies in front of start_bit */
+#define TS_GZIP_HISTORY_EMPTY 0  /* nothing: a member's first window */
+#define TS_GZIP_HISTORY_KEPT  1  /* the bytes the object's last decode produced (and what lay in front of them) */
+#define TS_GZIP_HISTORY_GIVEN 2  /* history[0, history_len), history_len <= 32768: the bytes right in front */
+typedef struct ts_gzip_result {
+    uint64_t end_bit;            /* in the window: where the verified chain ends, a block boundary; start_bit when nothing was verified */
+    uint64_t plain_bytes;        /* produced by this call (they replace what the object held) */
+    uint32_t crc32;              /* of those bytes */
+    int32_t  status;             /* TS_GZIP_WINDOW_END ... TS_GZIP_BAD_DEFLATE */
+    int32_t  member_ended;       /* 1 when status is TS_GZIP_FINAL_BLOCK */
+    uint32_t spans_probed, spans_chained, spans_dropped;
+} ts_gzip_result;
+/* span_bytes: a multiple of 1024 in 1024 .. 1 MiB.  NULL on failure. */
+ts_gzip *ts_gzip_create(ts_ctx *ctx, uint32_t span_bytes);
+void ts_gzip_destroy(ts_gzip *gz);
+/* Decodes compressed[0, n) (host memory, n <= 256 MiB, at most 65535 spans, and 2 bytes per symbol of the spans' room within
+ * 4 GiB) from start_bit on (inside the first span).
+ * Damaged input is not an error of the call: TS_OK, and res->status says where and why the chain ended.  Waits for the
+ * device; the caller's buffers are free when the call returns. */
+int ts_gzip_decode(ts_gzip *gz, const void *compressed, uint64_t n, uint64_t start_bit, int history_mode, const void *history,
+                   uint64_t history_len, ts_gzip_result *res);
+/* Up to `want` of the produced bytes that were not taken yet go behind the chunk's bytes from carry_from on (the tail moves to
+ * the front as for ts_chunk_upload; device to device), *moved of them; what is left stays for the next call. */
+int ts_gzip_take(ts_gzip *gz, ts_chunk *chunk, uint64_t carry_from, uint64_t want, uint64_t *moved);
+/* produced[off, off + n) to host memory (tests).  Waits for the device. */
+int ts_gzip_read(ts_gzip *gz, uint64_t off, uint64_t n, void *host);
+/* The last *len <= 32768 bytes in front of the last decode's end_bit (the dictionary of the raw inflate that takes over there)
+ * to host[0, *len). */
+int ts_gzip_history(ts_gzip *gz, void *host, uint64_t *len);
+/* The caller says that it handed `parts` stretches of the input to zlib (where a chain ended short and a larger window was
+ * not the answer; a member too small to bother the device with): the library cannot see that, and the statistics should. */
+int ts_gzip_note_fallback(ts_gzip *gz, uint64_t parts);
+/* Cumulative since ts_create, like ts_device_input_stats: windows decoded, spans probed, spans chained, spans dropped (a
+ * candidate that was stepped over), plain bytes produced on the device, parts handed to zlib (ts_gzip_note_fallback). */
+int ts_gzip_stats(const ts_ctx *ctx, uint64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

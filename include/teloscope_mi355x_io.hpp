@@ -46,6 +46,7 @@
 
 #include "teloscope_mi355x.hpp"
 #include "teloscope_mi355x_filter.hpp"
+#include "teloscope_mi355x_gzip.hpp"
 
 namespace teloscope_mi355x {
 
@@ -1409,20 +1410,60 @@ inline void inflateMembers(ts_ctx *ctx, ts_chunk *chunk, const unsigned char *sr
     if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
 }
 
+// ts_gzip (include/teloscan.h) as the device GzipReader decodes with
+struct TsGzipDevice : GzipDevice {
+    ts_ctx *ctx;
+    ts_gzip *gz;
+    TsGzipDevice(ts_ctx *ctx_, uint32_t spanBytes) : ctx(ctx_), gz(ts_gzip_create(ctx_, spanBytes)) {
+        if (!gz) throw deviceError(ctx, "cannot make the gzip decoder");
+    }
+    TsGzipDevice(const TsGzipDevice &) = delete;
+    TsGzipDevice &operator=(const TsGzipDevice &) = delete;
+    ~TsGzipDevice() override { ts_gzip_destroy(gz); }
+    GzipWindowResult decode(const unsigned char *window, size_t n, unsigned startBit, int historyMode, const unsigned char *history, size_t historyLen) override {
+        ts_gzip_result r{};
+        if (ts_gzip_decode(gz, window, n, startBit, historyMode, history, historyLen, &r) != TS_OK) throw deviceError(ctx, "gzip decode failed");
+        GzipWindowResult w;
+        w.endBit = r.end_bit; w.plainBytes = r.plain_bytes; w.crc = r.crc32; w.status = r.status;
+        return w;
+    }
+    void noteFallback() override { ts_gzip_note_fallback(gz, 1); }
+    void history(std::vector<unsigned char> &out) override {
+        out.resize(32768);
+        uint64_t len = 0;
+        if (ts_gzip_history(gz, out.data(), &len) != TS_OK) throw deviceError(ctx, "cannot read the gzip history");
+        out.resize(static_cast<size_t>(len));
+    }
+};
+
+// a ChunkFeed::Options default from the environment: the number, or `fallback` where the variable is unset or no number
+inline size_t envSize(const char *name, size_t fallback) {
+    const char *e = std::getenv(name);
+    if (!e || !*e) return fallback;
+    char *end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    return end && *end == 0 ? static_cast<size_t>(v) : fallback;
+}
+
 // Bytes of a text input -> new bytes in a device chunk, for fastqSubsetDevice, scanFastaToFilesDevice and annotateGfaDevice.
-// The text comes from one of three sources —
+// The text comes from one of four sources —
 //   Plain   a plain regular file: mapped, and copied to the device as it lies (ts_chunk_upload);
 //   Bgzf    a BGZF regular file (bgzip output): the members are located on the host (parseBgzfBlock reads no payload byte) and
 //           inflated and checksummed on the device (ts_bam_chunk_inflate, as bamSubsetDevice does), in as many calls per fill
 //           as the compressed buffer asks for; from the first member that does not parse as BGZF on, the rest of the input is
 //           a Stream.  Behind BGZF members anything that is not gzip ends the input: zlib ignores what trails a gzip stream;
-//   Stream  anything else (plain gzip, stdin, a FIFO, a file that cannot be mapped): read in blocks, each block uploaded;
-//           through zlib where gzip starts there (or always: Options), else read(2) —
+//   Gzip    a mapped regular file that begins with a plain gzip member, or such members behind BGZF members, of
+//           Options::gzipMinBytes or more: the deflate stream is decoded on the device a window at a time (ts_gzip_decode),
+//           member headers and trailers are the host's, and zlib continues wherever the device's verified chain of blocks
+//           stops short (GzipReader, teloscope_mi355x_gzip.hpp); its data errors and failed trailer checks are cannotRead,
+//           as gzread's are for a Stream;
+//   Stream  anything else (small plain gzip, stdin, a FIFO, a file that cannot be mapped): read in blocks, each block
+//           uploaded; through zlib where gzip starts there (or always: Options), else read(2) —
 // and a fill is read(want), which says how many bytes come (a Stream is read here), then put(chunk, carryFrom), which brings
 // them behind the chunk's bytes from carryFrom on; fill() is the two in one.
 class ChunkFeed {
 public:
-    enum Source { Plain, Bgzf, Stream };
+    enum Source { Plain, Bgzf, Stream, Gzip };
     struct Options {
         std::string cannotOpen, cannotRead;                     // the route's exception texts
         bool dashIsStdin = false;                               // `-` is stdin, always read through zlib (as fastqSubset does)
@@ -1431,7 +1472,13 @@ public:
         std::function<std::runtime_error(const char *)> noRoom; // the exception of a failed growth or upload; unset: deviceError
         // told about every run of new bytes: where they lie on the host, or (host == nullptr) their offset in the chunk
         std::function<void(const char *host, uint64_t chunkAt, uint64_t len)> sink;
+        // plain gzip on the device; the defaults are the environment's, read when the options are made
+        bool gzipDevice = envSize("TS_GZIP_DEVICE", kGzipDeviceDefault) != 0;       // 0: zlib reads plain gzip, as a Stream
+        size_t gzipSpan = envSize("TS_GZIP_SPAN", 32768);                           // compressed bytes per span (a wave each)
+        size_t gzipMinBytes = envSize("TS_GZIP_MIN_BYTES", size_t(1) << 20);        // fewer compressed bytes: zlib
+        size_t gzipWindow = envSize("TS_GZIP_WINDOW", size_t(8) << 20);             // compressed bytes per device call
     };
+    static constexpr size_t kGzipDeviceDefault = 0;
 
     ChunkFeed(ts_ctx *ctx, const std::string &file, Options options)
         : ctx_(ctx), opt_(std::move(options)), in_(file, opt_.dashIsStdin, opt_.cannotOpen) {
@@ -1441,6 +1488,7 @@ public:
             else source_ = Plain;
         }
         deviceInflate_ = source_ == Bgzf;
+        if (source_ == Stream && in_.data && gzipWanted(0)) { source_ = Gzip; openGzip(0); }
     }
 
     Source source() const { return source_; }
@@ -1460,6 +1508,7 @@ public:
         want_ = want;
         if (source_ == Plain) return std::min<uint64_t>(want, in_.size - at_);
         if (source_ == Bgzf) return std::min<uint64_t>(want, 8 * static_cast<uint64_t>(in_.size - at_) + 65536);
+        if (source_ == Gzip) return std::min<uint64_t>(want, (pendLen_ - pendOff_) + 8 * gzipReader_->bytesLeft() + 65536);
         if (!streamOpen_) openStream(0);
         std::vector<char> &b = keep ? *keep : block_;
         const size_t start = keep ? std::min<size_t>(want, size_t(4) << 20) : want;
@@ -1496,9 +1545,27 @@ public:
                 carryFrom = 0;
             } while (!pick.foreign && !pick.full && at_ < in_.size);
             if (!pick.foreign) return at_ >= in_.size;
+            if (gzipWanted(at_)) { source_ = Gzip; openGzip(at_); return !gzipLoad(); }
             source_ = Stream;
             openStream(at_);
             return streamDone_;
+        }
+        if (source_ == Gzip) {
+            uint64_t got = 0;
+            bool first = true;
+            while (gzipLoad() && got < want_) {
+                const uint64_t n = std::min<uint64_t>(want_ - got, pendLen_ - pendOff_), cf = first ? carryFrom : 0;
+                const uint64_t at = ts_bam_chunk_size(chunk) - cf;
+                if (pendKind_ == GzipReader::OnDevice) {
+                    uint64_t moved = 0;
+                    if (ts_gzip_take(gzipDevice_->gz, chunk, cf, n, &moved) != TS_OK || moved != n) throw noRoom(opt_.growFailed);
+                } else if (ts_chunk_upload(chunk, pendHost_ + pendOff_, n, cf, nullptr) != TS_OK) throw noRoom(opt_.uploadFailed);
+                if (opt_.sink) opt_.sink(nullptr, at, n);
+                pendOff_ += n; got += n;
+                first = false;
+            }
+            if (first && ts_chunk_upload(chunk, nullptr, 0, carryFrom, nullptr) != TS_OK) throw noRoom(opt_.uploadFailed);    // (the carry alone)
+            return !gzipLoad();
         }
         if (source_ == Plain) {
             const size_t n = std::min(want_, in_.size - at_);
@@ -1515,6 +1582,32 @@ public:
     bool fill(ts_chunk *chunk, uint64_t carryFrom, size_t want) { read(want); return put(chunk, carryFrom); }
 
 private:
+    // plain gzip from `from` on goes to the device: asked for, a device to ask, a member there, and enough of it
+    bool gzipWanted(size_t from) const {
+        return opt_.gzipDevice && ctx_ && in_.data && in_.size - from >= std::max<size_t>(opt_.gzipMinBytes, 2) &&
+               in_.data[from] == 0x1f && in_.data[from + 1] == 0x8b;
+    }
+    void openGzip(size_t from) {
+        const size_t span = std::min<size_t>(std::max<size_t>(opt_.gzipSpan / 1024 * 1024, 1024), size_t(1) << 20);
+        gzipDevice_.reset(new TsGzipDevice(ctx_, static_cast<uint32_t>(span)));
+        GzipReader::Tuning tuning;
+        // (the device holds 2 bytes per symbol of every span's room — 16 symbols per compressed byte, 512 Ki at least: 1 GiB here)
+        const size_t spansMost = (size_t(1) << 30) / (2 * std::max<size_t>(16 * span, size_t(512) << 10));
+        tuning.windowBytes = std::min<size_t>(std::max<size_t>(opt_.gzipWindow, span), std::min<size_t>(size_t(1) << 28, spansMost * span));
+        tuning.minBytes = opt_.gzipMinBytes;
+        gzipReader_.reset(new GzipReader(in_.data, in_.size, from, gzipDevice_.get(), tuning));
+    }
+    // a piece with bytes left is at hand -> true; false: the gzip input is at its end.  zlib's verdicts become the route's
+    bool gzipLoad() {
+        while (pendOff_ >= pendLen_) {
+            pendOff_ = pendLen_ = 0;
+            try { pendKind_ = gzipReader_->next(pendLen_, pendHost_); }
+            catch (const GzipError &) { throw std::runtime_error(opt_.cannotRead); }
+            if (pendKind_ == GzipReader::None) return false;
+        }
+        return true;
+    }
+
     // the descriptor from `from` on; behind BGZF members (from > 0) only gzip is read
     void openStream(size_t from) {
         streamOpen_ = true;
@@ -1544,6 +1637,11 @@ private:
     const char *blockData_ = nullptr;                               // the Stream block read() filled
     std::vector<char> block_;
     std::vector<ts_bgzf_block> descs_;
+    std::unique_ptr<TsGzipDevice> gzipDevice_;                      // the Gzip source: the device's decoder, the reader above it
+    std::unique_ptr<GzipReader> gzipReader_;
+    GzipReader::Kind pendKind_ = GzipReader::None;                  // the piece being handed out: where it lies, how far it has gone
+    const char *pendHost_ = nullptr;
+    uint64_t pendLen_ = 0, pendOff_ = 0;
 };
 
 // The judge step of bamSubsetDevice and fastqSubsetDevice: reads with bases, already picked out of a chunk's table (`lens`, one

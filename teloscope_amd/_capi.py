@@ -185,6 +185,12 @@ class BgzfStatus(C.Structure):
     _fields_ = [("code", C.c_int32), ("reserved", C.c_uint32), ("block", C.c_uint64)]
 
 
+class GzipResult(C.Structure):
+    _fields_ = [("end_bit", C.c_uint64), ("plain_bytes", C.c_uint64), ("crc32", C.c_uint32), ("status", C.c_int32),
+                ("member_ended", C.c_int32), ("spans_probed", C.c_uint32), ("spans_chained", C.c_uint32),
+                ("spans_dropped", C.c_uint32)]
+
+
 class BamRecord(C.Structure):
     _fields_ = [("off", C.c_uint64), ("block_size", C.c_uint32), ("seq_at", C.c_uint32), ("l_seq", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -251,6 +257,7 @@ SYMBOLS = [
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
     "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats",
     "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
+    "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
 ]
 
 
@@ -391,6 +398,16 @@ def lib():
                                          C.POINTER(SegmentOut), C.POINTER(SegmentCounts)]
     L.ts_box_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ts_device_input_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_gzip_create.restype = C.c_void_p
+    L.ts_gzip_create.argtypes = [C.c_void_p, C.c_uint32]
+    L.ts_gzip_destroy.restype = None
+    L.ts_gzip_destroy.argtypes = [C.c_void_p]
+    L.ts_gzip_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(GzipResult)]
+    L.ts_gzip_take.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.ts_gzip_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.ts_gzip_history.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_gzip_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_gzip_note_fallback.argtypes = [C.c_void_p, C.c_uint64]
     L.ts_device_input_stats.restype = C.c_int
     L.ts_exchange_unique_id.argtypes = [C.c_void_p]
     L.ts_exchange_last_error.restype = C.c_char_p

@@ -445,6 +445,19 @@ int  ts_k_launch_bam_decode(const void *plain, const void *jobs, uint32_t n_jobs
 int  ts_k_launch_bam_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream);
 int  ts_k_launch_bam_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
                             void *out, void *stream);
+// gzip.hip: a window of one gzip member's deflate stream (window: 16-byte aligned, zero from window_len to the next dword).
+// cand[n_spans] = each span's first candidate block start (span 0: start_bit); then a wave per span decodes 16-bit symbols to
+// sym[s * cap ...] and writes table[s] (24 bytes: start_bit, end_bit, n_out, status, final_seen, reserved; status 0xff = no
+// candidate); then, for the chain the host picked (chain[k]: 24 bytes {span, n_out, hist_avail, reserved, u64 plain_off};
+// hist: (n_chain + 1) * 32 KiB, the first the history in front of the window), the histories, the plain bytes and
+// *bad_span = min(k whose markers reach in front of hist_avail); then CRC32 per slice (16 bytes {u64 off, u32 len, u32 crc})
+int  ts_k_launch_gzip_probe(const void *window, uint32_t window_len, uint32_t start_bit, uint32_t span_bytes, uint32_t n_spans,
+                            uint32_t *cand, void *stream);
+int  ts_k_launch_gzip_decode(const void *window, uint32_t window_len, uint32_t n_spans, const uint32_t *cand, uint32_t cap,
+                             uint32_t hist0_len, void *sym, void *table, void *stream);
+int  ts_k_launch_gzip_resolve(const void *sym, uint32_t cap, const void *chain, uint32_t n_chain, uint32_t max_out, void *hist,
+                              void *plain, unsigned long long plain_n, uint32_t *bad_span, void *stream);
+int  ts_k_launch_gzip_crc(const void *plain, unsigned long long plain_n, void *slices, uint32_t n_slices, void *stream);
 }
 #endif
 
