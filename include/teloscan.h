@@ -902,6 +902,36 @@ const void *ts_chunk_data(const ts_chunk *chunk);
  * Ordered on `stream`; waits for it. */
 int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void *stream);
 
+/* ---- assembly record filters on the two device routes (include/teloscope_mi355x_filter.hpp; scanFastaToFilesDevice and
+ *      annotateGfaDevice with a selector): the few facts the filtered loaders' rules ask about bytes that the host never sees.
+ *      The host stays the judge: these calls say what the text holds, the routes turn that into the reference's messages. */
+/* has_sequence[i] (host memory, n bytes) = 1 when the body lines of recs[i] (entries of the chunk's last walk, any subset) hold
+ * a byte other than '\n' and '\r', else 0: the filtered FASTA loader's "has no sequence" (FastaGroupReader::checkStrict).  Not
+ * n_bases > 0: a body of "\r\r\n" has one base and no sequence.  A wave per 16 KB of body text at most, which stops at the
+ * first such byte it meets.  Ordered on `stream`; waits for it. */
+int ts_fasta_chunk_strict(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, unsigned char *has_sequence, void *stream);
+/* The whole lines of a chunk that ts_gfa_chunk_walk walked last, with the same at_end, against the filtered GFA loader's rules
+ * (validateFilteredGfa, include/teloscope_mi355x_gfa.hpp).  *n_lines = the whole lines in [0, *next) of that walk, blank and
+ * '#' lines included.  flagged = the lines that break a rule, in input order; code = the first rule the line breaks, in the
+ * loader's order:
+ *     1  an "H\t" line that contains "\tVN:Z:2"            5  type C
+ *     2  shorter than 2 bytes, or its second byte no tab   6  an S line whose third field is not empty, all digits and
+ *     3  type O, U, E, G or F                                 followed by a tab
+ *     4  type W                                            7  type not H, S, L, J or P
+ * The loader drops every '\r' of a line before it judges it; the device does not: a line that holds a '\r' anywhere but as the
+ * last byte of its content gets TS_GFA_CHECK_HOST_DECIDES and the caller reads that one line back (ts_bam_chunk_read) and
+ * judges it on the host.  Lines without content and '#' lines are never flagged otherwise.  When *n_flagged > cap nothing is
+ * copied and the call answers TS_ERR_INVALID_ARG (call again with room for *n_flagged).  Waits for the device. */
+#define TS_GFA_CHECK_HOST_DECIDES 255
+typedef struct ts_gfa_flagged {
+    uint64_t off;                /* of the line's first byte in the chunk */
+    uint32_t line;               /* its ordinal among the chunk's lines, from 0 */
+    uint32_t len;                /* of its content (without '\n' and one '\r' in front of it) */
+    uint32_t code;               /* 1..7, or TS_GFA_CHECK_HOST_DECIDES */
+    uint32_t type;               /* the line's first byte */
+} ts_gfa_flagged;
+int ts_gfa_chunk_check(ts_chunk *chunk, int at_end, ts_gfa_flagged *flagged, uint64_t cap, uint64_t *n_flagged, uint64_t *n_lines);
+
 /* ---- plain gzip (one long deflate stream per member, not BGZF) inflated on the device: replaces gzread in
  *      detail::ChunkFeed::read (include/teloscope_mi355x_io.hpp) for the text routes.  A window of a member's compressed bytes
  *      is cut into spans of span_bytes; a wave per span searches its first deflate block start (BFINAL = 0, BTYPE = 2, a

@@ -1,7 +1,9 @@
 // teloscope_mi355x_filter.hpp — assembly record filters (--include-bed / --exclude-bed / --include-prefix / --exclude-prefix;
 // reference: src/main.cpp:103-147, SequenceSelector in src/input.cpp:384-563, docs/parameters.md "Assembly record filters").
-// Host-only, header-only.  Selection decides which FASTA records / GFA paths / GFA segments reach the scan; the device never
-// sees the others.
+// Header-only; the selection itself is host work.  It decides which FASTA records / GFA paths / GFA segments reach the scan.  On
+// the host routes (scanFastaToFiles with a selected FastaGroupReader, annotateGfa) the device never sees the others; on the
+// device routes (scanFastaToFilesDevice and annotateGfaDevice with a selector) their text lies in device memory with the rest,
+// is checked there by the filtered loaders' rules (ts_fasta_chunk_strict, ts_gfa_chunk_check) and is never joined or scanned.
 //
 //     addPrefixFilters(ui, "hap1_chr,hap2_chr", ui.includePrefixes, "--include-prefix");   // option parsing
 //     addBedFilterFile(ui, "primary.ids", ui.includeBedFiles, "--include-bed");

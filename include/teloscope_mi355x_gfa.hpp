@@ -23,7 +23,8 @@
 //   SequenceSelection sel = selectGfa(g, selector);             // candidates: path names, or segment names without paths
 //   ... Teloscope t(ui); annotateGfa(t, g, &sel, outDir);       // ends of selected paths / selected segments only
 //
-// or annotateGfa(teloscope, file, outDir, selector) for all of it.  Every input line, unselected P lines included, is written back.
+// or annotateGfa(teloscope, file, outDir, selector) for all of it (annotateGfaDevice(teloscope, file, outDir, selector) on the
+// device route: the same checks over the text in device memory).  Every input line, unselected P lines included, is written back.
 #pragma once
 
 #include <algorithm>
@@ -371,12 +372,55 @@ inline size_t writeAnnotatedGfa(const GfaGraph &g, const std::vector<GfaEnd> &jo
     return writeAnnotatedGfa(g, input, jobs, ends, outGfa, outColors);
 }
 
+namespace detail {
+
+// One line of a filtered GFA, its '\r' bytes gone, by the filtered loader's rules (src/input.cpp:206-283): 0, or the first rule
+// it breaks, numbered as ts_gfa_chunk_check numbers them (include/teloscan.h)
+inline int filteredGfaLineCode(const std::string &line) {
+    if (line.empty() || line[0] == '#') return 0;
+    if (line.compare(0, 2, "H\t") == 0 && line.find("\tVN:Z:2") != std::string::npos) return 1;
+    if (line.size() < 2 || line[1] != '\t') return 2;
+    const char type = line[0];
+    if (std::strchr("OUEGF", type)) return 3;
+    if (type == 'W') return 4;
+    if (type == 'C') return 5;
+    if (type == 'S') {                                             // S name LEN seq: a GFA 2 segment
+        const size_t t2 = line.find('\t', 2), t3 = t2 == std::string::npos ? t2 : line.find('\t', t2 + 1);
+        if (t3 != std::string::npos && t3 > t2 + 1 &&
+            std::all_of(line.begin() + static_cast<long>(t2) + 1, line.begin() + static_cast<long>(t3),
+                        [](char c) { return c >= '0' && c <= '9'; }))
+            return 6;
+    }
+    if (!std::strchr("HSLJP", type)) return 7;
+    return 0;
+}
+
+// the loader's words for a broken rule (code 1..7) of a line of the given type at line lineNo (from 1)
+inline SequenceFilterError filteredGfaError(int code, char type, uint64_t lineNo) {
+    const std::string gfa2 = "; use GFA1 P paths or a pathless GFA1 graph.", at = " at line " + std::to_string(lineNo);
+    switch (code) {
+    case 1: return SequenceFilterError("Assembly record filters do not support GFA2" + at + gfa2);
+    case 2: return SequenceFilterError("Assembly record filters found a malformed or unsupported GFA record" + at + ".");
+    case 3: return SequenceFilterError(std::string("Assembly record filters do not support GFA2 record type '") + type + "'" + at + gfa2);
+    case 4: return SequenceFilterError("Assembly record filters do not support GFA1 W walks" + at + gfa2);
+    case 5: return SequenceFilterError("Assembly record filters do not support GFA1 C containment records" + at + ".");
+    case 6: return SequenceFilterError("Assembly record filters do not support GFA2 segment records" + at + gfa2);
+    default: return SequenceFilterError(std::string("Assembly record filters do not support GFA record type '") + type + "'" + at + ".");
+    }
+}
+
+// GFA 2 by name: refused before the file is opened
+inline void refuseGfa2Name(const std::string &file) {
+    if (caseInsensitiveSuffix(file, ".gfa2") || caseInsensitiveSuffix(file, ".gfa2.gz"))
+        throw SequenceFilterError("Assembly record filters do not support GFA2; use GFA1 P paths or a pathless GFA1 graph.");
+}
+
+}  // namespace detail
+
 // With assembly record filters the input must be a GFA 1 graph with P paths or none (src/input.cpp:206-283): throws a
 // SequenceFilterError naming the first line that is not, before the graph is read.  Blank and '#' lines are skipped.
 inline void validateFilteredGfa(const std::string &file) {
-    const std::string gfa2 = "; use GFA1 P paths or a pathless GFA1 graph.";
-    if (detail::caseInsensitiveSuffix(file, ".gfa2") || detail::caseInsensitiveSuffix(file, ".gfa2.gz"))
-        throw SequenceFilterError("Assembly record filters do not support GFA2" + gfa2);
+    detail::refuseGfa2Name(file);
     std::string data;
     try {
         data = detail::gfaReadAll(file);
@@ -390,26 +434,8 @@ inline void validateFilteredGfa(const std::string &file) {
         ls = nl == std::string::npos ? data.size() : nl + 1;
         ++lineNo;
         line.erase(std::remove(line.begin(), line.end(), '\r'), line.end());
-        if (line.empty() || line[0] == '#') continue;
-        const std::string at = " at line " + std::to_string(lineNo);
-        if (line.compare(0, 2, "H\t") == 0 && line.find("\tVN:Z:2") != std::string::npos)
-            throw SequenceFilterError("Assembly record filters do not support GFA2" + at + gfa2);
-        if (line.size() < 2 || line[1] != '\t')
-            throw SequenceFilterError("Assembly record filters found a malformed or unsupported GFA record" + at + ".");
-        const char type = line[0];
-        if (std::strchr("OUEGF", type))
-            throw SequenceFilterError(std::string("Assembly record filters do not support GFA2 record type '") + type + "'" + at + gfa2);
-        if (type == 'W') throw SequenceFilterError("Assembly record filters do not support GFA1 W walks" + at + gfa2);
-        if (type == 'C') throw SequenceFilterError("Assembly record filters do not support GFA1 C containment records" + at + ".");
-        if (type == 'S') {                                         // S name LEN seq: a GFA 2 segment
-            const size_t t2 = line.find('\t', 2), t3 = t2 == std::string::npos ? t2 : line.find('\t', t2 + 1);
-            if (t3 != std::string::npos && t3 > t2 + 1 &&
-                std::all_of(line.begin() + static_cast<long>(t2) + 1, line.begin() + static_cast<long>(t3),
-                            [](char c) { return c >= '0' && c <= '9'; }))
-                throw SequenceFilterError("Assembly record filters do not support GFA2 segment records" + at + gfa2);
-        }
-        if (!std::strchr("HSLJP", type))
-            throw SequenceFilterError(std::string("Assembly record filters do not support GFA record type '") + type + "'" + at + ".");
+        const int code = detail::filteredGfaLineCode(line);
+        if (code) throw detail::filteredGfaError(code, line[0], lineNo);
     }
 }
 
@@ -485,15 +511,24 @@ inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &fil
 // version, edits), gfaTerminalJobs picks the ends, and ONE terminalEnds call scans the wanted segments where they lie in the
 // chunks (TS_INPUT_DEVICE, no host view).  The writer takes the input's bytes from the mapping, from the zlib blocks as they were
 // produced, or — BGZF — from the chunks, read back piece by piece.
-// Limits: ONE device (a Teloscope over several throws); no record filters (they stay with the host route); a line of more than
+// Assembly record filters: the form with a selector mirrors annotateGfa(teloscope, file, outDir, selector, log).  With an active
+// selector the .gfa2 / .gfa2.gz name check comes first; ts_gfa_chunk_check judges every chunk's lines by validateFilteredGfa's
+// rules beside the walk (a line with a '\r' inside it is read back and judged by the host's own rule), line numbers running
+// over the chunks; after the last chunk the first offence is thrown with validateFilteredGfa's message, then come the graph
+// build's errors, selectGfa, its line on `log`, and the ends of the selected paths / segments only.  The text is uploaded and
+// indexed once, where the host route reads and walks the file twice.  An inactive selector changes nothing.
+// Limits: ONE device (a Teloscope over several throws); a line of more than
 // 4 GiB - 2 bytes is refused with its byte offset; a text that does not fit the device's free memory is refused with a message
 // that names annotateGfa; the stages run one after the other.  With a GFA 2 input that holds both a foreign record and a segment
 // named twice, the foreign record is reported (readGfa reports whichever comes first by its 16 MB parse blocks).
-inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::string &file, const std::string &outDir,
-                                          std::ostream &log = std::cerr, size_t chunkBytesArg = size_t(256) << 20) {
+namespace detail {
+inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                              const SequenceSelector *selector, std::ostream &log, size_t chunkBytesArg) {
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     const auto tBegin = Clock::now();
+    const bool filtered = selector && selector->active();
+    if (filtered) detail::refuseGfa2Name(file);
     if (teloscope.deviceCount() > 1)
         throw std::runtime_error("annotateGfaDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
                                  " (the graph's text lies in one device's memory)");
@@ -535,6 +570,12 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
     // what a chunk's walk gave; base: the input offset of the chunk's first byte
     struct Walked { ts_chunk *chunk; uint64_t base; std::vector<ts_gfa_segment> segs; std::vector<ts_gfa_line> lines; std::vector<char> text; ts_gfa_foreign foreign; };
     std::vector<Walked> walked;
+
+    // filters: the first line that breaks validateFilteredGfa's rules (code 0: none so far), lines counted over the chunks
+    int offence = 0;
+    char offenceType = 0;
+    uint64_t offenceLine = 0, linesBefore = 0;
+    std::vector<ts_gfa_flagged> flagged(64);
 
     uint64_t held = 0, prevNext = 0, base = 0;
     bool atEnd = false, grow = false;
@@ -582,11 +623,38 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
         msIndex += since(t0);
         if (!atEnd && next == 0) { grow = true; continue; }     // no whole line yet: the chunk takes more
         grow = false;
+        if (filtered && !offence) {                             // the chunk's whole lines by the filtered loader's rules
+            t0 = Clock::now();
+            uint64_t nFlagged = 0, nLines = 0;
+            rc = ts_gfa_chunk_check(cur, atEnd ? 1 : 0, flagged.data(), flagged.size(), &nFlagged, &nLines);
+            if (rc == TS_ERR_INVALID_ARG && nFlagged > flagged.size()) {
+                flagged.resize(static_cast<size_t>(nFlagged));
+                rc = ts_gfa_chunk_check(cur, atEnd ? 1 : 0, flagged.data(), flagged.size(), &nFlagged, &nLines);
+            }
+            if (rc != TS_OK) throw fail("GFA check failed");
+            for (uint64_t k = 0; k < nFlagged && !offence; ++k) {
+                const ts_gfa_flagged &fl = flagged[static_cast<size_t>(k)];
+                int code = static_cast<int>(fl.code);
+                char type = static_cast<char>(fl.type);
+                if (fl.code == TS_GFA_CHECK_HOST_DECIDES) {     // a '\r' inside the line: the host's rule on the line itself
+                    std::string line(fl.len, '\0');
+                    if (fl.len && ts_bam_chunk_read(cur, fl.off, fl.len, &line[0]) != TS_OK) throw fail("cannot read the chunk");
+                    line.erase(std::remove(line.begin(), line.end(), '\r'), line.end());
+                    code = detail::filteredGfaLineCode(line);
+                    type = line.empty() ? 0 : line[0];
+                }
+                if (code) { offence = code; offenceType = type; offenceLine = linesBefore + fl.line + 1; }
+            }
+            linesBefore += nLines;
+            msIndex += since(t0);
+        }
         w.segs.resize(static_cast<size_t>(nSegs)); w.lines.resize(static_cast<size_t>(nLines)); w.text.resize(static_cast<size_t>(textBytes));
         w.segs.shrink_to_fit(); w.lines.shrink_to_fit(); w.text.shrink_to_fit();
         walked.push_back(std::move(w));
         prev = cur; prevNext = next; base += next;
     }
+
+    if (offence) throw detail::filteredGfaError(offence, offenceType, offenceLine);
 
     // the graph, as readGfa builds it
     Clock::time_point t0 = Clock::now();
@@ -649,10 +717,15 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
     std::sort(g.edits.begin(), g.edits.end(), [](const GfaEdit &a, const GfaEdit &b) { return a.off < b.off; });
     msGraph = since(t0);
 
+    SequenceSelection sel;
+    if (filtered) {
+        sel = selectGfa(g, *selector);
+        log << selectionMessage(sel) << "\n";
+    }
     GfaAnnotateStats st;
     st.parseMs = since(tBegin);
     const auto t1 = Clock::now();
-    const std::vector<GfaEnd> jobs = gfaTerminalJobs(g);
+    const std::vector<GfaEnd> jobs = gfaTerminalJobs(g, filtered ? &sel.keep : nullptr);
     const GfaEnds e = gfaScanEnds(teloscope, g, jobs, log, true);
     const auto t2 = Clock::now();
 
@@ -698,6 +771,19 @@ inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::strin
         std::fprintf(stderr, "annotateGfaDevice: upload%s %.0f ms, index %.0f ms, graph (host) %.0f ms, scan %.0f ms, write %.0f ms\n",
                      feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msGraph, st.scanMs, st.writeMs);
     return st;
+}
+}  // namespace detail
+
+inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                          std::ostream &log = std::cerr, size_t chunkBytes = size_t(256) << 20) {
+    return detail::annotateGfaDeviceWith(teloscope, file, outDir, nullptr, log, chunkBytes);
+}
+
+// the same with assembly record filters (see above)
+inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                          const SequenceSelector &selector, std::ostream &log = std::cerr,
+                                          size_t chunkBytes = size_t(256) << 20) {
+    return detail::annotateGfaDeviceWith(teloscope, file, outDir, &selector, log, chunkBytes);
 }
 
 }  // namespace teloscope_mi355x

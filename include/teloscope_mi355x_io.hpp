@@ -32,6 +32,7 @@
 #include <cstring>
 #include <exception>
 #include <fstream>
+#include <iostream>
 #include <ostream>
 #include <sstream>
 #include <string>
@@ -2730,6 +2731,209 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
     return sum;
 }
 
+namespace detail {
+
+// scanFastaToFilesDevice with an active selector (its comment says what happens; the caller has checked the device count).
+inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
+                                                      std::ostream &console, bool manualCuration, size_t chunkBytesArg,
+                                                      ScanFastaTimes *times, uint64_t chunkLimit, bool deviceTracks,
+                                                      const SequenceSelector &selector, std::ostream &log, uint64_t residentLimit) {
+    using Clock = std::chrono::steady_clock;
+    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto tBegin = Clock::now();
+    const UserInputTeloscope &ui = teloscope.input();
+    ts_ctx *ctx = teloscope.context();
+    auto fail = [&](const char *what) { return deviceError(ctx, what); };
+    double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;
+    ScanFastaTimes T;
+
+    struct ChunkFree { void operator()(ts_chunk *c) const { ts_bam_chunk_destroy(c); } };
+    std::vector<std::unique_ptr<ts_chunk, ChunkFree>> chunks;   // every one stays until its kept records are written
+    uint64_t resident = 0;
+    const std::string hostRoute = "with assembly record filters the whole text stays in device memory until the selection is known; "
+                                  "use scanFastaToFiles, the host route";
+    auto noRoom = [&](const char *what) -> std::runtime_error {
+        const char *why = ts_last_error(ctx);
+        return std::runtime_error(std::string("scanFastaToFilesDevice: ") + what + " with " + std::to_string(resident) +
+                                  " bytes of the assembly's text resident (" + (why ? why : "?") +
+                                  "): the text does not fit the device's free memory; " + hostRoute);
+    };
+    ChunkFeed::Options options;
+    options.cannotOpen = "Could not open assembly input '" + fastaFile + "'.";      // (the filtered host loader's words)
+    options.cannotRead = "Could not read assembly input '" + fastaFile + "'.";
+    options.growFailed = "cannot grow a device chunk";
+    options.uploadFailed = "upload of the FASTA text failed";
+    options.noRoom = noRoom;
+    ChunkFeed feed(ctx, fastaFile, options);
+    chunkLimit = feed.chunkLimit(std::max<uint64_t>(std::min<uint64_t>(chunkLimit, 0xfffffffeull), 64));
+    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+    const uint64_t compCap = feed.compCap(chunkBytes);
+    auto makeChunk = [&](uint64_t cap) {
+        ts_chunk *made = ts_bam_chunk_create(ctx, compCap, std::max<uint64_t>(cap, 64));
+        if (!made) throw noRoom("cannot make a device chunk");
+        chunks.emplace_back(made);
+        return made;
+    };
+    auto checkResident = [&]() {
+        if (residentLimit && resident > residentLimit)
+            throw std::runtime_error("scanFastaToFilesDevice: " + std::to_string(resident) + " bytes of the assembly's text are resident and " +
+                                     std::to_string(residentLimit) + " may be: the text does not fit the device's free memory; " + hostRoute);
+    };
+
+    // ---- phase 1: every chunk fed, walked, checked and kept; tables, IDs and the strict facts on the host
+    struct Held { size_t slot; bool atEnd; size_t first; std::vector<ts_fasta_record> recs; };   // first: its first record's input index
+    std::vector<Held> heldChunks;
+    std::vector<std::string> ids;                               // primary IDs of all records, in input order
+    std::vector<char> hasSequence;
+    std::vector<ts_fasta_record> recs(4096);
+    std::vector<char> names(size_t(1) << 16);
+    std::vector<unsigned char> has;
+    bool frontBytes = false, sawRecord = false;                 // bytes that belong to no record in front of the first one
+
+    // the first bytes on their own: a UTF-8 byte order mark is not part of the first line, and is not carried on
+    Clock::time_point t0 = Clock::now();
+    ts_chunk *prev = nullptr, *cur = nullptr;
+    uint64_t prevNext = 0, held = 0;
+    bool atEnd = false, grow = false;
+    {
+        const uint64_t room = feed.read(64);
+        prev = makeChunk(room);
+        atEnd = feed.put(prev, 0);
+        const uint64_t n = ts_bam_chunk_size(prev);
+        unsigned char mark[3] = {0, 0, 0};
+        if (n >= 3 && ts_bam_chunk_read(prev, 0, 3, mark) != TS_OK) throw fail("cannot read the chunk");
+        prevNext = mark[0] == 0xef && mark[1] == 0xbb && mark[2] == 0xbf ? 3 : 0;
+        resident += n;
+        checkResident();
+    }
+    msUpload += since(t0);
+    for (bool firstFill = true; firstFill || !atEnd; firstFill = false) {
+        t0 = Clock::now();
+        const uint64_t carry = grow ? held : ts_bam_chunk_size(prev) - prevNext;
+        if (carry >= chunkLimit)
+            throw std::runtime_error("a FASTA record of '" + fastaFile + "' has more than " + std::to_string(chunkLimit) +
+                                     " bytes of text and does not fit a device chunk; use scanFastaToFiles, the host route");
+        // a chunk that held no whole record takes as much again, up to what a chunk may hold
+        const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, grow ? carry : 0), chunkLimit - carry));
+        const uint64_t room = atEnd ? 0 : feed.read(want);
+        if (!grow) {
+            cur = makeChunk(carry + room);
+            if (carry && ts_chunk_carry_over(cur, prev, prevNext, nullptr) != TS_OK) throw noRoom("cannot carry a record into the next device chunk");
+        }
+        if (!atEnd) atEnd = feed.put(cur, 0);
+        msUpload += since(t0);
+        resident += ts_bam_chunk_size(cur) - (grow ? held : 0);
+        held = ts_bam_chunk_size(cur);
+        checkResident();
+        if (held == 0) continue;
+
+        t0 = Clock::now();
+        uint64_t n = 0, next = 0, nameBytes = 0;
+        int rc = ts_fasta_chunk_walk(cur, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
+        if (rc == TS_ERR_INVALID_ARG && (n > recs.size() || nameBytes > names.size())) {
+            if (n > recs.size()) recs.resize(static_cast<size_t>(n));
+            if (nameBytes > names.size()) names.resize(static_cast<size_t>(nameBytes));
+            rc = ts_fasta_chunk_walk(cur, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
+        }
+        if (rc != TS_OK) throw fail("FASTA walk failed");
+        if (!atEnd && n == 0 && next == 0) { grow = true; msIndex += since(t0); continue; }    // one unfinished record: the chunk takes more
+        grow = false;
+        has.resize(static_cast<size_t>(n));
+        if (n && ts_fasta_chunk_strict(cur, recs.data(), static_cast<size_t>(n), has.data(), nullptr) != TS_OK) throw fail("FASTA strict check failed");
+        msIndex += since(t0);
+        if (!sawRecord && (n ? recs[0].off != 0 : next != 0)) frontBytes = true;
+        sawRecord = sawRecord || n != 0;
+        Held h{chunks.size() - 1, atEnd, ids.size(), std::vector<ts_fasta_record>(recs.begin(), recs.begin() + static_cast<ptrdiff_t>(n))};
+        for (size_t i = 0; i < n; ++i) {
+            ids.push_back(sequenceFilterId(std::string(names.data() + recs[i].name_at, recs[i].name_len)));
+            hasSequence.push_back(static_cast<char>(has[i]));
+        }
+        heldChunks.push_back(std::move(h));
+        prev = cur; prevNext = next;
+    }
+
+    // ---- between the phases: the filtered loader's rules in its order (FastaGroupReader::checkStrict), then the selection
+    if (frontBytes) throw SequenceFilterError("Assembly record filters require FASTA input or a recognized GFA file.");
+    {
+        std::unordered_set<std::string> seen;
+        for (size_t i = 0; i < ids.size(); ++i) {
+            if (i && !hasSequence[i - 1]) throw SequenceFilterError("FASTA record '" + ids[i - 1] + "' has no sequence.");
+            if (ids[i].empty()) throw SequenceFilterError("FASTA input contains an empty primary sequence ID.");
+            if (!seen.insert(ids[i]).second) throw SequenceFilterError("Input contains duplicate primary sequence ID: '" + ids[i] + "'.");
+        }
+        if (ids.empty()) throw SequenceFilterError("Assembly input is empty.");
+        if (!hasSequence.back()) throw SequenceFilterError("FASTA record '" + ids.back() + "' has no sequence.");
+    }
+    const SequenceSelection sel = selector.select(ids, "paths");
+    log << selectionMessage(sel) << "\n";
+
+    // ---- phase 2: the kept records of every chunk joined, scanned and written; the others are never read again
+    BedWriter writer(outBase, ui, console, manualCuration);
+    const bool useTrackText = deviceTracks && !ui.outMatches;
+    TrackText trackText;
+    std::vector<char> hostBases;
+    std::vector<ts_fasta_run> runs(4096);
+    std::vector<uint64_t> offsets;
+    for (Held &h : heldChunks) {
+        ts_chunk *chunk = chunks[h.slot].get();
+        std::vector<ts_fasta_record> kept;
+        std::vector<size_t> seqPos;
+        for (size_t i = 0; i < h.recs.size(); ++i)
+            if (sel.keep[h.first + i]) { kept.push_back(h.recs[i]); seqPos.push_back(h.first + i); }
+        const size_t n = kept.size();
+        if (n) {
+            t0 = Clock::now();
+            const void *dBases = nullptr;
+            uint64_t total = 0, nRuns = 0;
+            offsets.resize(n);
+            if (ts_fasta_chunk_join(chunk, kept.data(), n, h.atEnd ? 1 : 0, &dBases, offsets.data(), &total, &nRuns, nullptr) != TS_OK)
+                throw fail("FASTA join failed");
+            if (nRuns > runs.size()) runs.resize(static_cast<size_t>(nRuns));
+            if (ts_fasta_chunk_runs(chunk, runs.data(), runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
+            const bool hostView = ui.outMatches && !ui.ultraFastMode;
+            if (hostView) {                                     // matchSeq is cut out of the bases: one copy per chunk
+                hostBases.resize(static_cast<size_t>(total) + 1);
+                if (ts_fasta_chunk_bases(chunk, 0, total, hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
+            }
+            msJoin += since(t0);
+            std::vector<PathComponents> comps(n);
+            std::vector<RecordView> views(n);
+            for (uint64_t r = 0; r < nRuns; ++r) {
+                const ts_fasta_run &run = runs[static_cast<size_t>(r)];
+                if (run.record >= n) throw std::runtime_error("FASTA runs: a run of a record that was not joined");
+                if (run.is_gap) comps[run.record].gaps.push_back(GapInfo{run.start, run.len});
+                else { comps[run.record].segments.emplace_back(run.start, run.len); T.library_bases += run.len; }
+            }
+            for (size_t i = 0; i < n; ++i)
+                views[i] = RecordView{&ids[seqPos[i]], hostView ? hostBases.data() + offsets[i] : nullptr, kept[i].n_bases, nullptr, 0, nullptr,
+                                      static_cast<const char *>(dBases) + offsets[i]};
+            t0 = Clock::now();
+            std::vector<PathData> paths = walkRecordViews(teloscope, views, 0, &comps, &seqPos, useTrackText ? &trackText : nullptr);
+            msScan += since(t0);
+            t0 = Clock::now();
+            writer.add(paths, useTrackText ? &trackText : nullptr);
+            for (const PathData &pd : paths) { T.bases += pd.pathSize; T.windows += pd.nWindows(); }
+            ++T.groups;
+            msWrite += since(t0);
+        }
+        chunks[h.slot].reset();                                 // (its text and its joined bases are done with)
+    }
+    const auto tf = Clock::now();
+    AssemblySummary sum = writer.finish();
+    sum.filterActive = true;                                    // (from this selection: the context existed before it was known)
+    sum.filterInputCount = sel.inputCount;
+    sum.filterSelectedCount = sel.selectedCount;
+    msWrite += since(tf);
+    if (std::getenv("TS_TIMING"))
+        std::fprintf(stderr, "scanFastaToFilesDevice (filtered): upload%s %.0f ms, index + check %.0f ms, join %.0f ms, scan %.0f ms, write %.0f ms\n",
+                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msJoin, msScan, msWrite);
+    T.read_ms = msUpload + msIndex + msJoin; T.scan_ms = msScan; T.write_ms = msWrite; T.wall_ms = since(tBegin);
+    if (times) *times = T;
+    return sum;
+}
+
+}  // namespace detail
+
 // The device route of the assembly scan (same files, console report and AssemblySummary as scanFastaToFiles, which stays the
 // default): the FASTA text exists in HBM one chunk of ~chunkBytes bytes at a time, and without -m the host reads none of it.
 // The text gets there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, or a stream through zlib
@@ -2740,7 +2944,15 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
 // The bytes behind the last complete record stay in the chunk for the next fill; a record larger than a chunk makes it grow.
 // deviceTracks (off by default): the window tracks' lines are formatted on the device too (ts_scan_segments_tracks) and BedWriter
 // writes them as they come; see below.
-// Limits: ONE device (a Teloscope over several throws); no assembly record filters (they stay with the host route); a record
+// Assembly record filters (selector given and active; otherwise nothing here changes): two phases.  Phase 1 feeds, walks and
+// checks every chunk (ts_fasta_chunk_strict: which bodies hold a byte that is no line end) and KEEPS it resident, an unfinished
+// record moving on device to device (ts_chunk_carry_over); tables and names stay on the host, a leading UTF-8 byte order mark
+// is dropped, and no join, no scan and no output file exists yet.  Then the host applies FastaGroupReader::checkStrict's rules in
+// its order, cuts the IDs as sequenceFilterId does, selects, and reports the selection on `log`.  Phase 2 joins, scans and
+// writes the kept records chunk by chunk (seqPos = their input indices); an unselected record is never joined or scanned, and
+// the summary's filter counts are this selection's.  The whole text must fit the device's free memory: one that does not (or
+// exceeds residentLimit, a test hook like chunkLimit: 0 = no limit of its own) is refused before any output exists.
+// Limits: ONE device (a Teloscope over several throws); a record
 // whose text does not fit a chunk of chunkLimit bytes (4 GiB - 2, what the walk takes) is refused by name, never cut; the
 // stages run one after the other.  chunkLimit is a test hook (the refusal cannot be reached otherwise without 4 GiB of text):
 // callers leave it alone.  What a maintainer of the reference would call in place of its FASTA load and per-path jobs
@@ -2748,13 +2960,18 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
 inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
                                               std::ostream &console, bool manualCuration = false,
                                               size_t chunkBytesArg = size_t(256) << 20, ScanFastaTimes *times = nullptr,
-                                              uint64_t chunkLimit = 0xfffffffeull, bool deviceTracks = false) {
+                                              uint64_t chunkLimit = 0xfffffffeull, bool deviceTracks = false,
+                                              const SequenceSelector *selector = nullptr, std::ostream &log = std::cerr,
+                                              uint64_t residentLimit = 0) {
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     const auto tBegin = Clock::now();
     if (teloscope.deviceCount() > 1)
         throw std::runtime_error("scanFastaToFilesDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
                                  " (the joined bases lie in one device's memory)");
+    if (selector && selector->active())
+        return detail::scanFastaToFilesDeviceFiltered(teloscope, fastaFile, outBase, console, manualCuration, chunkBytesArg, times, chunkLimit,
+                                                      deviceTracks, *selector, log, residentLimit);
     const UserInputTeloscope &ui = teloscope.input();
     ts_ctx *ctx = teloscope.context();
     auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };

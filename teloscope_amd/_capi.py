@@ -224,6 +224,11 @@ class GfaForeign(C.Structure):
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("found", C.c_uint32)]
 
 
+class GfaFlagged(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("line", C.c_uint32), ("len", C.c_uint32), ("code", C.c_uint32), ("type", C.c_uint32)]
+
+
+GFA_CHECK_HOST_DECIDES = 255
 BGZF_OK, BGZF_BAD_DEFLATE, BGZF_BAD_CRC = 0, 1, 2
 FASTQ_OK, FASTQ_TRUNCATED, FASTQ_BAD_HEADER, FASTQ_BAD_SEPARATOR, FASTQ_BAD_LENGTHS = 0, 1, 2, 3, 4
 BAM_OK, BAM_BAD_BLOCK_SIZE, BAM_BAD_LENGTHS, BAM_FIELDS_EXCEED, BAM_NAME_NOT_NUL = 0, 1, 2, 3, 4
@@ -256,6 +261,7 @@ SYMBOLS = [
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
     "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats",
+    "ts_fasta_chunk_strict", "ts_gfa_chunk_check",
     "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
     "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
 ]
@@ -452,6 +458,9 @@ def lib():
     L.ts_chunk_data.argtypes = [C.c_void_p]
     L.ts_chunk_data.restype = C.c_void_p
     L.ts_chunk_carry_over.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.ts_fasta_chunk_strict.argtypes = [C.c_void_p, C.POINTER(FastaRecord), C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ts_gfa_chunk_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(GfaFlagged), C.c_uint64, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]
     L.ts_window_tracks_format.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TrackSegment), C.c_size_t, C.c_char_p,
                                           C.c_uint64, C.POINTER(TrackText)]
     L.ts_window_tracks_format.restype = C.c_int

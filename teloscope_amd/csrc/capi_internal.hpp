@@ -406,6 +406,13 @@ struct ts_bam_chunk {
     // GFA (gfa.cpp): the tab counts per slice and the tabs' offsets, the lines' kind bytes and their per-slice counts, the two
     // tables and the gathered text
     DevBuf d_gfa_counts, d_gfa_tabs, d_gfa_kinds, d_gfa_frames, d_gfa_segs, d_gfa_lines, d_gfa_text, d_gfa_out;
+    // assembly record filters: a byte per record of the strict FASTA check; of the GFA check the lines' stray-'\r' and code bytes,
+    // the flagged lines per slice, their total and the flagged table.  What the last GFA walk indexed (ts_gfa_chunk_check works on
+    // that line and tab index; another line index over the chunk ends its validity)
+    DevBuf d_fa_strict, d_gfa_stray, d_gfa_codes, d_gfa_ccounts, d_gfa_cout, d_gfa_flagged;
+    bool gfa_walked = false;
+    int gfa_at_end = 0;
+    uint64_t gfa_size = 0, gfa_newlines = 0, gfa_n_lines = 0, gfa_n_tabs = 0;
 };
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
 int  ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry);

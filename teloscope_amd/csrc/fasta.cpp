@@ -8,7 +8,7 @@
 namespace {
 
 static_assert(sizeof(ts_fasta_record) == 32 && sizeof(ts_fasta_run) == 16 && sizeof(FastaFrame) == 16 && sizeof(FastaHead) == 16 &&
-              sizeof(FastaJoinJob) == 32 && sizeof(FastaRunJob) == 32, "layouts");
+              sizeof(FastaJoinJob) == 32 && sizeof(FastaRunJob) == 32 && sizeof(FastaStrictJob) == 16, "layouts");
 
 // a record of the table against the chunk: inside it, the body inside the record, no more bases than body bytes
 bool record_ok(const ts_bam_chunk *ch, const ts_fasta_record &r) {
@@ -167,6 +167,41 @@ int ts_fasta_chunk_join(ts_chunk *ch, const ts_fasta_record *recs, size_t n, int
     HIP_TRY(ctx, hipStreamSynchronize(st));
     ch->fa_runs = runs;
     *n_runs = runs;
+    return TS_OK;
+}
+
+int ts_fasta_chunk_strict(ts_chunk *ch, const ts_fasta_record *recs, size_t n, unsigned char *has_sequence, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if ((n && (!recs || !has_sequence)) || n > 0x7fffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_strict: null or out-of-range argument");
+    if (ch->plain_n >= 0xffffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_strict: the chunk holds 4 GiB or more");
+    if (n == 0) return TS_OK;
+    // the jobs: a record's body text cut at multiples of 16 KB, as the join cuts it
+    std::vector<FastaStrictJob> jobs;
+    for (size_t i = 0; i < n; ++i) {
+        const ts_fasta_record &r = recs[i];
+        if (!record_ok(ch, r)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_strict: record " + std::to_string(i) + " does not fit the chunk");
+        const uint64_t z = r.off + r.text_len;
+        for (uint64_t p = r.off + r.body_at; p < z;) {
+            const uint64_t q = std::min<uint64_t>(z, (p / kFastaSliceBytes + 1) * kFastaSliceBytes);
+            jobs.push_back(FastaStrictJob{(uint32_t)p, (uint32_t)q, (uint32_t)i, 0u});
+            p = q;
+        }
+    }
+    if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_strict: too much text for one call");
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, ch->d_fa_strict.ensure(n));
+    HIP_TRY(ctx, hipMemsetAsync(ch->d_fa_strict.p, 0, n, st));
+    if (!jobs.empty()) {
+        HIP_TRY(ctx, ch->d_fa_jobs.ensure(jobs.size() * sizeof(FastaStrictJob)));
+        HIP_TRY(ctx, hipMemcpyAsync(ch->d_fa_jobs.p, jobs.data(), jobs.size() * sizeof(FastaStrictJob), hipMemcpyHostToDevice, st));
+        if (ts_k_launch_fasta_strict(ch->d_plain.p, ch->plain_n, ch->d_fa_jobs.p, (uint32_t)jobs.size(), (unsigned char *)ch->d_fa_strict.p, stream) != 0)
+            return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_strict: kernel launch failed");
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(has_sequence, ch->d_fa_strict.p, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                    // (the job list was this call's memory: it has left it too)
     return TS_OK;
 }
 

@@ -12,6 +12,8 @@
 //     aligned 16-byte rows, 1 KB at a time.  Every byte is read once and written once; there are no per-line copies.
 //   * runs: the same shape over the joined bytes with another predicate: a run starts where "is a gap letter" differs from
 //     the byte before, or where a record starts.
+//   * strict: the filtered loader's one question about a body (does it hold a byte that is no line end?), the count pass's
+//     jobs with a third predicate and no sum: a byte per record.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -292,9 +294,41 @@ void ts_fasta_run_lengths_kernel(ts_fasta_run *runs, unsigned long long n_runs, 
     runs[i].len = end - start;
 }
 
+// ---- strict
+// a wave per job: does body text [a, z) hold a byte other than '\n' and '\r'?  1 KB per step; the first step that holds one
+// ends the job (most bodies: the first)
+__global__ __launch_bounds__(64)
+void ts_fasta_strict_kernel(const unsigned char *plain, unsigned long long size, const FastaStrictJob *jobs, uint32_t n_jobs,
+                            unsigned char *has) {
+    if (blockIdx.x >= n_jobs) return;
+    const FastaStrictJob job = jobs[blockIdx.x];
+    const unsigned long long a = job.a, z = job.z < size ? job.z : size;
+    for (unsigned long long p0 = a & ~15ull; p0 < z; p0 += 1024ull) {
+        const unsigned long long p = p0 + threadIdx.x * 16u;
+        uint32_t m = 0u;
+        if (p < z && p + 16ull > a) {
+            const uint4 q = *(const uint4 *)(plain + p);       // (the chunk's buffer is readable 64 bytes beyond its capacity)
+            const uint32_t lo = a > p ? (uint32_t)(a - p) : 0u, hi = z - p >= 16ull ? 16u : (uint32_t)(z - p);
+            m = ~(eq_mask16(q, 0x0a0a0a0au) | eq_mask16(q, 0x0d0d0d0du)) & bit_range(lo, hi);
+        }
+        if (ballot64(m != 0u) != 0ull) {                        // (wave-uniform; every job of the record stores the same byte)
+            if (threadIdx.x == 0) has[job.rec] = 1;
+            return;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int ts_k_launch_fasta_strict(const void *plain, unsigned long long size, const void *jobs, uint32_t n_jobs, unsigned char *has,
+                             void *stream) {
+    if (n_jobs == 0) return 0;
+    hipLaunchKernelGGL(ts_fasta_strict_kernel, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, size,
+                       (const FastaStrictJob *)jobs, n_jobs, has);
+    return (int)hipGetLastError();
+}
 
 int ts_k_launch_fasta_frames(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
                              uint32_t newlines, void *frames, unsigned long long *out, void *stream) {

@@ -18,6 +18,8 @@ struct FastaHead { uint32_t line, crs_before, names_before, pad; };  // a header
 struct FastaJoinJob { uint32_t a, z, first, last; unsigned long long dst_rec, limit; };
 // joined bases [a, z) of one record, which begins at rec_begin (a multiple of 16), inside one 16 KB slice of the joined buffer
 struct FastaRunJob { unsigned long long a, z, rec_begin; uint32_t rec, pad; };
+// body text [a, z) of the chunk, a piece of record `rec` of the strict check's table that lies inside one 16 KB slice
+struct FastaStrictJob { uint32_t a, z, rec, pad; };
 
 extern "C" {
 // header lines, "\r\n" lines and name bytes per slice of kFastaSliceLines -> frames; then (one wave) frames -> exclusive sums in
@@ -42,4 +44,7 @@ int ts_k_launch_fasta_run_count(const void *joined, const void *jobs, uint32_t n
 int ts_k_launch_fasta_run_write(const void *joined, const void *jobs, uint32_t n_jobs, const uint32_t *sums, void *runs,
                                 unsigned long long n_runs, void *stream);
 int ts_k_launch_fasta_run_lengths(void *runs, unsigned long long n_runs, const void *recs, uint32_t n_recs, void *stream);
+// has[job.rec] = 1 for every job whose body text holds a byte other than '\n' and '\r' (has: a byte per record, zero before)
+int ts_k_launch_fasta_strict(const void *plain, unsigned long long size, const void *jobs, uint32_t n_jobs, unsigned char *has,
+                             void *stream);
 }

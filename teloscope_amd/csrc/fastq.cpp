@@ -20,6 +20,7 @@ int ts_chunk_line_index(ts_bam_chunk *ch, int at_end, const char *who, const cha
     const std::string name = who;
     const uint64_t size = ch->plain_n;
     unsigned long long *d_out = (unsigned long long *)ch->d_out.p;
+    ch->gfa_walked = false;                                    // (ts_gfa_chunk_check reads the index of the GFA walk that made it)
     HIP_TRY(ctx, ch->d_waves.ensure((size_t)ceil_div(size, kFastqSliceBytes) * 4));
     if (ts_k_launch_fastq_count(ch->d_plain.p, size, (uint32_t *)ch->d_waves.p, d_out, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, name + ": kernel launch failed");

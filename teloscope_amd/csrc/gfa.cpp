@@ -1,4 +1,4 @@
-// gfa.cpp — host side of the device GFA stages (include/teloscan.h: ts_gfa_chunk_walk, ts_chunk_data, ts_chunk_carry_over):
+// gfa.cpp — host side of the device GFA stages (include/teloscan.h: ts_gfa_chunk_walk, ts_gfa_chunk_check, ts_chunk_data, ts_chunk_carry_over):
 // argument checks, buffer sizes, launches and the few words that come back.  The chunk is bgzf.cpp's ts_bam_chunk, its line index
 // fastq.hip's; nothing here parses a byte of text.
 #include "capi_internal.hpp"
@@ -8,7 +8,8 @@
 
 namespace {
 
-static_assert(sizeof(ts_gfa_segment) == 48 && sizeof(ts_gfa_line) == 24 && sizeof(ts_gfa_foreign) == 16 && sizeof(GfaFrame) == 16, "layouts");
+static_assert(sizeof(ts_gfa_segment) == 48 && sizeof(ts_gfa_line) == 24 && sizeof(ts_gfa_foreign) == 16 && sizeof(GfaFrame) == 16 &&
+              sizeof(ts_gfa_flagged) == 24, "layouts");
 static_assert(kGfWords * sizeof(unsigned long long) <= 64, "the result block has 64 bytes");
 
 }  // namespace
@@ -25,6 +26,7 @@ int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void 
     const uint64_t n = from->plain_n - carry_from;
     to->plain_n = 0;                                           // (what the destination held is dropped, not kept by a growth)
     to->n_blocks = 0;
+    to->gfa_walked = false;
     if (n > to->plain_cap) { const int rc = ts_chunk_reserve(to, n); if (rc != TS_OK) return rc; }
     DEVICE_TRY(ctx);
     hipStream_t st = (hipStream_t)stream;
@@ -73,6 +75,9 @@ int ts_gfa_chunk_walk(ts_chunk *ch, int at_end, ts_gfa_segment *segs, uint64_t s
     const uint32_t *tabs = (const uint32_t *)ch->d_gfa_tabs.p;
     if (ts_k_launch_gfa_tabs(ch->d_plain.p, size, (const uint32_t *)ch->d_gfa_counts.p, (uint32_t)n_tabs, (uint32_t *)ch->d_gfa_tabs.p, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_walk: kernel launch failed");
+    // (what ts_gfa_chunk_check works on: both indexes stay where they are until the chunk is indexed again)
+    ch->gfa_walked = true; ch->gfa_at_end = at_end ? 1 : 0; ch->gfa_size = size;
+    ch->gfa_newlines = newlines; ch->gfa_n_lines = n_lines; ch->gfa_n_tabs = n_tabs;
 
     // kinds: per slice of lines, their sums, the lowest foreign line
     const uint64_t n_frames = ceil_div(n_lines, kGfaSliceLines);
@@ -105,6 +110,49 @@ int ts_gfa_chunk_walk(ts_chunk *ch, int at_end, ts_gfa_segment *segs, uint64_t s
     if (ns) HIP_TRY(ctx, hipMemcpy(segs, ch->d_gfa_segs.p, (size_t)ns * sizeof(ts_gfa_segment), hipMemcpyDeviceToHost));
     if (nl) HIP_TRY(ctx, hipMemcpy(lines, ch->d_gfa_lines.p, (size_t)nl * sizeof(ts_gfa_line), hipMemcpyDeviceToHost));
     if (nt) HIP_TRY(ctx, hipMemcpy(text, ch->d_gfa_text.p, (size_t)nt, hipMemcpyDeviceToHost));
+    return TS_OK;
+}
+
+int ts_gfa_chunk_check(ts_chunk *ch, int at_end, ts_gfa_flagged *flagged, uint64_t cap, uint64_t *n_flagged, uint64_t *n_lines_out) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!n_flagged || !n_lines_out || (cap && !flagged) || cap > (1ull << 31))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_gfa_chunk_check: null or out-of-range argument");
+    *n_flagged = 0; *n_lines_out = 0;
+    const uint64_t size = ch->plain_n;
+    if (size == 0) return TS_OK;
+    if (!ch->gfa_walked || ch->gfa_size != size || (ch->gfa_at_end != 0) != (at_end != 0))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_gfa_chunk_check: ts_gfa_chunk_walk has not walked the chunk's bytes with this at_end");
+    const uint64_t n_lines = ch->gfa_n_lines, n_tabs = ch->gfa_n_tabs, slots = ch->gfa_newlines + 2;
+    *n_lines_out = n_lines;
+    if (n_lines == 0) return TS_OK;
+    DEVICE_TRY(ctx);
+    // the walk's indexes, where it left them
+    const uint32_t *lstart = (const uint32_t *)ch->d_lines.p;
+    const unsigned char *first = (const unsigned char *)ch->d_lines.p + slots * 4, *cr = first + slots;
+    const uint32_t *tabs = (const uint32_t *)ch->d_gfa_tabs.p;
+    const uint64_t n_frames = ceil_div(n_lines, kGfaSliceLines);
+    HIP_TRY(ctx, ch->d_gfa_stray.ensure((size_t)n_lines));
+    HIP_TRY(ctx, ch->d_gfa_codes.ensure((size_t)n_lines));
+    HIP_TRY(ctx, ch->d_gfa_ccounts.ensure((size_t)n_frames * 4));
+    HIP_TRY(ctx, ch->d_gfa_cout.ensure(8));
+    HIP_TRY(ctx, hipMemsetAsync(ch->d_gfa_stray.p, 0, (size_t)n_lines, nullptr));
+    if (ts_k_launch_gfa_stray_cr(ch->d_plain.p, size, at_end, lstart, (uint32_t)n_lines, (unsigned char *)ch->d_gfa_stray.p, nullptr) != 0 ||
+        ts_k_launch_gfa_check(ch->d_plain.p, lstart, first, cr, (uint32_t)n_lines, tabs, (uint32_t)n_tabs, (const unsigned char *)ch->d_gfa_stray.p,
+                              (unsigned char *)ch->d_gfa_codes.p, (uint32_t *)ch->d_gfa_ccounts.p, nullptr) != 0 ||
+        ts_k_launch_fasta_scan((uint32_t *)ch->d_gfa_ccounts.p, (uint32_t)n_frames, (unsigned long long *)ch->d_gfa_cout.p, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_check: kernel launch failed");
+    unsigned long long nf = 0;
+    HIP_TRY(ctx, hipMemcpy(&nf, ch->d_gfa_cout.p, sizeof nf, hipMemcpyDeviceToHost));
+    if (nf > n_lines) return ctx->fail(TS_ERR_STATE, "ts_gfa_chunk_check: more flagged lines than lines");
+    *n_flagged = nf;
+    if (nf > cap) return ctx->fail(TS_ERR_INVALID_ARG, "ts_gfa_chunk_check: the table is too small (*n_flagged says what is needed)");
+    if (nf == 0) return TS_OK;
+    HIP_TRY(ctx, ch->d_gfa_flagged.ensure((size_t)nf * sizeof(ts_gfa_flagged)));
+    if (ts_k_launch_gfa_flagged(lstart, first, cr, (uint32_t)n_lines, (const unsigned char *)ch->d_gfa_codes.p, (const uint32_t *)ch->d_gfa_ccounts.p,
+                                ch->d_gfa_flagged.p, (uint32_t)nf, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_gfa_chunk_check: kernel launch failed");
+    HIP_TRY(ctx, hipMemcpy(flagged, ch->d_gfa_flagged.p, (size_t)nf * sizeof(ts_gfa_flagged), hipMemcpyDeviceToHost));
     return TS_OK;
 }
 

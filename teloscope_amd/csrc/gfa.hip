@@ -11,6 +11,9 @@
 //     2 048 lines counts segments, P / H lines and the bytes to gather; one wave sums the counts; a second pass gives every kept
 //     line its index and its place in the gathered text.  The lowest foreign line is taken by a 64-bit atomic minimum.
 //   * gather: a wave per item copies a segment's name or a P / H line into the text buffer.  Sequences are never copied.
+//   * check (assembly record filters): a lane per line judges it by the filtered loader's rules over the same line and tab
+//     indexes; the one thing the indexes do not say, whether a line holds a '\r' that is not its last byte, comes from a pass
+//     over the bytes in the tab count's shape that marks such lines for the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -217,9 +220,147 @@ void ts_gfa_gather_kernel(const unsigned char *plain, unsigned long long size, c
         if (from + i < size && to + i < text_bytes) text[to + i] = plain[from + i];
 }
 
+// ---- the filtered loader's check
+// the bytes of w that equal the byte repeated in c4, a bit per byte (tab_bits for any byte)
+__device__ __forceinline__ uint32_t eq_bits(uint32_t w, uint32_t c4) {
+    const uint32_t x = w ^ c4;
+    const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+    return (((t >> 7) * 0x01020408u) >> 24) & 15u;
+}
+__device__ __forceinline__ uint32_t eq_mask16(uint4 q, uint32_t c4) {
+    return eq_bits(q.x, c4) | eq_bits(q.y, c4) << 4 | eq_bits(q.z, c4) << 8 | eq_bits(q.w, c4) << 12;
+}
+
+// A stray '\r': one that is not the last byte of its line's content, i.e. whose next byte is no '\n' and that is not the input's
+// last byte.  A wave per slice, 16 bytes per lane per step; a step without one is skipped.  The line of a stray '\r' at p is the
+// last one that starts at or before p: a search of lstart[0, n_lines] (lstart[n_lines] is the end of the whole lines), and a
+// '\r' of the unfinished last line finds none.
+__global__ __launch_bounds__(64)
+void ts_gfa_stray_cr_kernel(const unsigned char *plain, unsigned long long n, int at_end, const uint32_t *lstart, uint32_t n_lines,
+                            unsigned char *stray) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kGfaSliceBytes + threadIdx.x * 16u;
+    for (uint32_t s = 0; s < kGfaSliceBytes / 1024u; ++s) {
+        const unsigned long long a = base + 1024ull * s;
+        uint32_t m = 0u;
+        if (a < n) {
+            const uint4 q = *(const uint4 *)(plain + a);        // (the chunk's buffer is readable 64 bytes beyond its capacity)
+            const uint32_t in_chunk = n - a >= 16ull ? 0xffffu : (1u << (uint32_t)(n - a)) - 1u;
+            const uint32_t lf = eq_mask16(q, 0x0a0a0a0au) & in_chunk, cr = eq_mask16(q, 0x0d0d0d0du) & in_chunk;
+            const uint32_t lf_next = (lf >> 1) | (a + 16ull < n && plain[a + 16ull] == '\n' ? 0x8000u : 0u);
+            m = cr & ~lf_next;
+            if (at_end && n - 1ull >= a && n - 1ull < a + 16ull) m &= ~(1u << (uint32_t)(n - 1ull - a));
+        }
+        if (ballot64(m != 0u) == 0ull) continue;                // (wave-uniform)
+        while (m) {
+            const uint32_t p = (uint32_t)a + (uint32_t)__builtin_ctz(m);
+            m &= m - 1u;
+            uint32_t lo = 0u, hi = n_lines + 1u;                // the first entry of lstart[0, n_lines] beyond p
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                if (lstart[mid] <= p) lo = mid + 1u; else hi = mid;
+            }
+            if (lo >= 1u && lo <= n_lines) stray[lo - 1u] = 1;
+        }
+    }
+}
+
+// line i (< n_lines) by validateFilteredGfa's rules: 0, the first rule it breaks (1..7), or 255 where the host decides
+__device__ __forceinline__ uint32_t check_line(const unsigned char *plain, const uint32_t *lstart, const unsigned char *first,
+                                               const unsigned char *cr, const uint32_t *tabs, uint32_t n_tabs,
+                                               const unsigned char *stray, uint32_t i) {
+    if (stray[i]) return TS_GFA_CHECK_HOST_DECIDES;
+    const uint32_t ls = lstart[i], len = lstart[i + 1] - 1u - ls - (uint32_t)cr[i], end = ls + len;
+    const unsigned char type = first[i];
+    if (len == 0u || type == '#') return 0u;
+    const bool tabbed = len >= 2u && plain[ls + 1u] == '\t';
+    if (tabbed && type == 'H') {                                // "\tVN:Z:2" behind any of the line's tabs
+        for (uint32_t k = tab_lower_bound(tabs, n_tabs, ls); k < n_tabs && tabs[k] + 7ull <= end; ++k) {
+            const unsigned char *p = plain + tabs[k];
+            if (p[1] == 'V' && p[2] == 'N' && p[3] == ':' && p[4] == 'Z' && p[5] == ':' && p[6] == '2') return 1u;
+        }
+    }
+    if (!tabbed) return 2u;
+    if (type == 'O' || type == 'U' || type == 'E' || type == 'G' || type == 'F') return 3u;
+    if (type == 'W') return 4u;
+    if (type == 'C') return 5u;
+    if (type == 'S') {                                          // S name LEN seq: the tabs behind the name and behind the third field
+        const uint32_t k = tab_lower_bound(tabs, n_tabs, ls + 2u);
+        if (k + 1u < n_tabs && tabs[k + 1u] < end && tabs[k + 1u] > tabs[k] + 1u) {
+            uint32_t p = tabs[k] + 1u;
+            while (p < tabs[k + 1u] && plain[p] >= '0' && plain[p] <= '9') ++p;
+            if (p == tabs[k + 1u]) return 6u;
+        }
+    }
+    if (type != 'H' && type != 'S' && type != 'L' && type != 'J' && type != 'P') return 7u;
+    return 0u;
+}
+
+__global__ __launch_bounds__(64)
+void ts_gfa_check_kernel(const unsigned char *plain, const uint32_t *lstart, const unsigned char *first, const unsigned char *cr,
+                         uint32_t n_lines, const uint32_t *tabs, uint32_t n_tabs, const unsigned char *stray, unsigned char *codes,
+                         uint32_t *counts) {
+    uint32_t flagged = 0;
+    for (uint32_t s = 0; s < kGfaSliceLines; s += 64u) {
+        const unsigned long long at = (unsigned long long)blockIdx.x * kGfaSliceLines + s + threadIdx.x;
+        if (at >= n_lines) continue;
+        const uint32_t code = check_line(plain, lstart, first, cr, tabs, n_tabs, stray, (uint32_t)at);
+        codes[at] = (unsigned char)code;
+        flagged += code ? 1u : 0u;
+    }
+    flagged = wave_total(flagged);
+    if (threadIdx.x == 0) counts[blockIdx.x] = flagged;
+}
+
+__global__ __launch_bounds__(64)
+void ts_gfa_flagged_kernel(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                           const unsigned char *codes, const uint32_t *sums, ts_gfa_flagged *flagged, uint32_t n_flagged) {
+    uint32_t f0 = sums[blockIdx.x];
+    for (uint32_t s = 0; s < kGfaSliceLines; s += 64u) {
+        const unsigned long long at = (unsigned long long)blockIdx.x * kGfaSliceLines + s + threadIdx.x;
+        const uint32_t i = at < n_lines ? (uint32_t)at : n_lines;
+        const uint32_t code = i < n_lines ? (uint32_t)codes[i] : 0u;
+        const uint32_t is = code ? 1u : 0u, incl = wave_scan_add(is);
+        const uint32_t r = f0 + incl - 1u;
+        if (is && r < n_flagged) {                              // (always: the count pass wrote these codes)
+            ts_gfa_flagged e;
+            e.off = lstart[i]; e.line = i; e.len = lstart[i + 1] - 1u - lstart[i] - (uint32_t)cr[i]; e.code = code; e.type = first[i];
+            flagged[r] = e;
+        }
+        f0 += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int ts_k_launch_gfa_stray_cr(const void *plain, unsigned long long n, int at_end, const uint32_t *lstart, uint32_t n_lines,
+                             unsigned char *stray, void *stream) {
+    const uint32_t slices = (uint32_t)((n + kGfaSliceBytes - 1) / kGfaSliceBytes);
+    if (slices == 0 || n_lines == 0) return 0;
+    hipLaunchKernelGGL(ts_gfa_stray_cr_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, at_end,
+                       lstart, n_lines, stray);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_gfa_check(const void *plain, const uint32_t *lstart, const unsigned char *first, const unsigned char *cr,
+                          uint32_t n_lines, const uint32_t *tabs, uint32_t n_tabs, const unsigned char *stray, unsigned char *codes,
+                          uint32_t *counts, void *stream) {
+    const uint32_t nf = (uint32_t)(((unsigned long long)n_lines + kGfaSliceLines - 1) / kGfaSliceLines);
+    if (nf == 0) return 0;
+    hipLaunchKernelGGL(ts_gfa_check_kernel, dim3(nf), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, lstart, first, cr,
+                       n_lines, tabs, n_tabs, stray, codes, counts);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_gfa_flagged(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                            const unsigned char *codes, const uint32_t *sums, void *flagged, uint32_t n_flagged, void *stream) {
+    const uint32_t nf = (uint32_t)(((unsigned long long)n_lines + kGfaSliceLines - 1) / kGfaSliceLines);
+    if (nf == 0 || n_flagged == 0) return 0;
+    hipLaunchKernelGGL(ts_gfa_flagged_kernel, dim3(nf), dim3(64), 0, (hipStream_t)stream, lstart, first, cr, n_lines, codes, sums,
+                       (ts_gfa_flagged *)flagged, n_flagged);
+    return (int)hipGetLastError();
+}
 
 int ts_k_launch_gfa_tab_count(const void *plain, unsigned long long n, uint32_t *counts, void *stream) {
     const uint32_t slices = (uint32_t)((n + kGfaSliceBytes - 1) / kGfaSliceBytes);

@@ -33,4 +33,15 @@ int ts_k_launch_gfa_tables(const void *plain, const uint32_t *lstart, const unsi
 // the segments' names and the P / H lines whole into text (a wave per item)
 int ts_k_launch_gfa_gather(const void *plain, unsigned long long size, const void *segs, uint32_t n_segs, const void *lines,
                            uint32_t n_kept, void *text, unsigned long long text_bytes, void *stream);
+// the filtered loader's check (ts_gfa_chunk_check).  stray[i] = 1 for every line that holds a '\r' anywhere but as the last byte
+// of its content (stray: a byte per line, zero before): a wave per slice of kGfaSliceBytes, the line found by a search of lstart
+int ts_k_launch_gfa_stray_cr(const void *plain, unsigned long long n, int at_end, const uint32_t *lstart, uint32_t n_lines,
+                             unsigned char *stray, void *stream);
+// every line's code byte (0: nothing to say) and the flagged lines per slice of kGfaSliceLines -> counts
+int ts_k_launch_gfa_check(const void *plain, const uint32_t *lstart, const unsigned char *first, const unsigned char *cr,
+                          uint32_t n_lines, const uint32_t *tabs, uint32_t n_tabs, const unsigned char *stray, unsigned char *codes,
+                          uint32_t *counts, void *stream);
+// the flagged lines in input order (sums: the exclusive sums of the counts)
+int ts_k_launch_gfa_flagged(const uint32_t *lstart, const unsigned char *first, const unsigned char *cr, uint32_t n_lines,
+                            const unsigned char *codes, const uint32_t *sums, void *flagged, uint32_t n_flagged, void *stream);
 }
