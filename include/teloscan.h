@@ -252,6 +252,14 @@ int     ts_takes_text_input(const ts_ctx *ctx, int tips_only);
  * 16 KiB), out[3] gather kernel launches (one per pipeline group that holds such a piece).  Cumulative, monotonic and atomic:
  * concurrent calls are coalesced, so "the last call's" numbers would be nobody's; take the difference around a call. */
 int     ts_device_input_stats(const ts_ctx *ctx, uint64_t out[4]);
+/* Measurement aid (no counterpart in the reference): which way the host-to-device upload of the host entry points went since
+ * ts_create — out[0] chunks sent packed (2-bit codes + invalid runs, restored on the device), out[1] chunks sent as ASCII; of the
+ * packed chunks' blocks of 16384 positions: out[2] packed from one piece of plain bases, out[3] packed straight from one piece of
+ * FASTA text, out[4] copied codes (every piece the block touches arrived as TS_INPUT_PACKED2), out[5] mixed (several pieces, or
+ * padding: spelled out as letters, then packed); out[6] chunks staged by more than one worker thread; out[7] launches of the
+ * unpack kernel for a chunk whose first base is not on a 64-position boundary of the layout.  Cumulative, monotonic and atomic,
+ * like ts_device_input_stats: take the difference around a call. */
+int     ts_upload_stats(const ts_ctx *ctx, uint64_t out[8]);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
  * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
  * No counterpart in the reference (its options are fixed by main, /root/reference/src/main.cpp:149-184). */

@@ -842,6 +842,12 @@ int ts_device_input_stats(const ts_ctx *ctx, uint64_t out[4]) {
     return TS_OK;
 }
 
+int ts_upload_stats(const ts_ctx *ctx, uint64_t out[8]) {
+    if (!ctx || !out) return TS_ERR_INVALID_ARG;
+    for (int i = 0; i < 8; ++i) out[i] = ctx->upload_stats[i].load(std::memory_order_relaxed);
+    return TS_OK;
+}
+
 // =========================================================================== batches
 // Planning is host work only (it also runs on a planning-only context); device state is allocated from the
 // context's pool when the batch first needs it.

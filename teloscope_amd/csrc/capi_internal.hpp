@@ -166,6 +166,8 @@ struct ts_ctx {
     bool jobs_ev_pending = false;
     // ts_device_input_stats: device pieces seen, device-to-device copies issued, gather jobs issued, gather launches — since ts_create
     std::atomic<uint64_t> device_input_stats[4] = {};
+    // ts_upload_stats: which way upload_pieces sent its chunks and packed their 16384-position blocks — since ts_create
+    std::atomic<uint64_t> upload_stats[8] = {};
     // ts_gzip_stats: windows, spans probed, spans chained, spans dropped, plain bytes produced, parts the caller handed to zlib — since ts_create
     std::atomic<uint64_t> gzip_stats[6] = {};
     hipEvent_t gen_ev[2] = {nullptr, nullptr};   // TS_TIMING: around the general path's kernels

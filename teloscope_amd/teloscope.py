@@ -201,6 +201,16 @@ class Teloscope:
             raise K.TeloscanError(rc, self._ctx.error())
         return tuple(int(v) for v in out)
 
+    def upload_stats(self):
+        """ts_upload_stats: (chunks sent packed, chunks sent as ASCII, 16384-blocks packed from one plain piece, from one text
+        piece, copied codes, mixed, chunks staged by several workers, unpack launches off a 64-position boundary) of this context
+        since it was made; cumulative, so take the difference around a call."""
+        out = (C.c_uint64 * 8)()
+        rc = K.lib().ts_upload_stats(self._ctx.ptr, out)
+        if rc != K.TS_OK:
+            raise K.TeloscanError(rc, self._ctx.error())
+        return tuple(int(v) for v in out)
+
     def scanSegments(self, segments, packed=False):
         """Batched scanSegment: segments = [(sequence, absPos, tipsOnly)] -> [SegmentData].
         packed=True hands the bases over as TS_INPUT_PACKED2 (2-bit codes + invalid runs, packed here with ts_pack_bases and
