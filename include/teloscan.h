@@ -261,7 +261,7 @@ int     ts_device_input_stats(const ts_ctx *ctx, uint64_t out[4]);
  * like ts_device_input_stats: take the difference around a call. */
 int     ts_upload_stats(const ts_ctx *ctx, uint64_t out[8]);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
- * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
+ * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32, TS_MATCH_SLICE_BYTES) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
  * No counterpart in the reference (its options are fixed by main, /root/reference/src/main.cpp:149-184). */
 int     ts_refresh_env(ts_ctx *ctx);
 /* HIP puts the streams of a process on a few hardware queues (four unless GPU_MAX_HW_QUEUES says otherwise) and does not say which;
@@ -373,6 +373,55 @@ void ts_free_track_text(ts_track_text *t);
  * (src/teloscope.cpp:537-658) followed by src/teloscope.cpp:785-812. */
 int  ts_scan_segments_tracks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, const char *const *names,
                              ts_segment_out *out, ts_segment_counts *counts, ts_track_text *tracks);
+
+/* ---- The two match files (-m) as text, formatted on the device (no counterpart of its own in the reference: it stands in for
+ *      scanSegment's matchSeq and its routing of a match into canonicalMatches / nonCanonicalMatches, src/teloscope.cpp:466-468,
+ *      485-509, and for the two match loops of writeBEDFile that print those vectors, which BedWriter::format runs on host
+ *      threads otherwise).  A line is  name \t position \t position + match_size \t matchSeq \n  with matchSeq the match's bases,
+ *      a..z upper-cased.  File order everywhere: canonical matches, terminal non-canonical matches.  A full-scan record gives a
+ *      canonical line if it is canonical, a non-canonical line if it is not and isTerminal (src/teloscope.cpp:451-459) holds for
+ *      its position relative to its SEGMENT, and no line otherwise; tips-only segments give none.  Lines come in the order in
+ *      which ts_scan_segments returns `matches`.
+ *      A ts_match_text follows ts_track_text's rules: ZERO-INITIALISED before its first use; a call REPLACES what it holds and
+ *      never appends; an earlier result's arrays are reused and grown; after a failed call the struct is empty (freed);
+ *      ts_free_match_text() at the end.  A context without out_matches yields text NULL, len 0 for both files. */
+#define TS_N_MATCH_FILES 2            /* canonical, terminal non-canonical */
+typedef struct ts_match_text {
+    char    *text[TS_N_MATCH_FILES];      /* not NUL-terminated */
+    uint64_t len[TS_N_MATCH_FILES];
+    uint64_t n_lines[TS_N_MATCH_FILES];
+    uint64_t capacity[TS_N_MATCH_FILES];  /* the library's */
+} ts_match_text;
+void ts_free_match_text(ts_match_text *t);
+/* One segment of the table ts_match_lines_format reads: its matches are records [first_record, first_record + n_records)
+ * (ascending first_record; records between two segments are skipped), its bases are bases[base_off, base_off + len), base 0 at
+ * absolute position abs_pos, its name names[name_off, name_off + name_len).  tips_only != 0: the segment gives no lines. */
+typedef struct ts_match_line_segment {
+    uint64_t first_record, n_records, abs_pos, len, base_off, name_off;
+    uint32_t name_len, tips_only;
+} ts_match_line_segment;
+/* The formatting stage by itself, host in, host out: uploads the records, the table, the names and the bases and runs the
+ * kernels ts_scan_segments_text runs; exists so that records no small scan produces can be formatted (sizes 1 and 63,
+ * positions of ten and more digits).  Canonical is the record's TS_MATCH_CANONICAL flag; terminal is decided from its position
+ * against the segment's len and the context's terminal_limit — the incoming TS_MATCH_TERMINAL bit is not trusted.  A record
+ * outside its segment, or of size 0 or above 63, is TS_ERR_INVALID_ARG.  Stands in for src/teloscope.cpp:466-468, 485-509
+ * and the two match loops of writeBEDFile. */
+int  ts_match_lines_format(ts_ctx *ctx, const ts_match *records, uint64_t n, const ts_match_line_segment *segs, size_t n_segs,
+                           const char *names, uint64_t names_len, const char *bases, uint64_t bases_len, ts_match_text *out);
+/* ts_scan_segments_tracks plus the match lines of all full-scan segments in input order: `tracks` as there, `matches` the two
+ * files' lines, segs[i]'s under names[i].  Either text argument may be NULL, not both.  out[i].matches == NULL and
+ * out[i].windows == NULL; blocks and counts as from ts_scan_segments_blocks.  Every input format (TS_INPUT_DEVICE, text pieces
+ * and packed included), tiled, general and wide kernels, any number of pipeline groups: each group's lines are formatted from
+ * its match records and its input buffer where they lie, so neither a match record nor a base crosses to the host.  One
+ * device: not part of ts_scan_segments_multi; not coalesced with other callers.  Stands in for scanSegment
+ * (src/teloscope.cpp:537-658, its matchSeq and routing :466-468, 485-509) followed by the window loops (:785-812) and the two
+ * match loops of writeBEDFile. */
+int  ts_scan_segments_text(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, const char *const *names,
+                           ts_segment_out *out, ts_segment_counts *counts, ts_track_text *tracks, ts_match_text *matches);
+/* Measurement aid (no counterpart in the reference; it counts what stands in for src/teloscope.cpp:485-509 and the two match
+ * loops of writeBEDFile): out[0] formatting calls (one per pipeline group, or per ts_match_lines_format), out[1] canonical
+ * lines, out[2] non-canonical lines, out[3] text bytes the device formatted since ts_create.  Cumulative, monotonic, atomic. */
+int  ts_match_text_stats(const ts_ctx *ctx, uint64_t out[4]);
 
 /* ---- GFA annotation (src/input.cpp:625-716).  For every segment (tips_only must be 1), ends[2*i] / ends[2*i+1]: the
  *      longest terminal block (blockLen) at the start / end side of segs[i], 0 if none (walkSegment's distToStart <= distToEnd

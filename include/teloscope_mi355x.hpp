@@ -134,16 +134,22 @@ struct TextLines { uint32_t first = 0, width = 0, eol = 0; };
 
 // The lines of the five window tracks as the device formatted them (ts_scan_segments_tracks), in detail::File order: density,
 // canonical ratio, strand ratio, GC, entropy.  Owns the library's arrays; a track the flags switch off is null with length 0.
+// Beside them, under -m, the lines of the two match files (ts_scan_segments_text): canonical matches, terminal non-canonical
+// matches; both null without -m or when the call did not ask for them.
 struct TrackText {
     ts_track_text t{};
+    ts_match_text m{};
     TrackText() = default;
     TrackText(const TrackText &) = delete;
     TrackText &operator=(const TrackText &) = delete;
-    ~TrackText() { ts_free_track_text(&t); }
+    ~TrackText() { clear(); }
     const char *data(int track) const { return t.text[track]; }
     uint64_t size(int track) const { return t.len[track]; }
     uint64_t lines() const { return t.n_lines; }
-    void clear() { ts_free_track_text(&t); }
+    const char *matchData(int file) const { return m.text[file]; }
+    uint64_t matchSize(int file) const { return m.len[file]; }
+    uint64_t matchLines(int file) const { return m.n_lines[file]; }
+    void clear() { ts_free_track_text(&t); ts_free_match_text(&m); }
 };
 
 namespace detail {
@@ -443,6 +449,33 @@ public:
         for (size_t i = 0; i < segs.size(); ++i) res[i] = convert(out[i], segs[i]);
         ts_free_segments(out.data(), out.size());
         return res;
+    }
+
+    // scanSegmentsTrackText under -m: the match lines of all full-scan segments leave as text too (text.m: the canonical and the
+    // terminal non-canonical file, formatted on the device from the match records and the input buffer where they lie —
+    // ts_scan_segments_text), so neither a match record nor a base comes back; result[i] has blocks only, counts[i] the sizes
+    // the match vectors would have had.  One device.
+    std::vector<SegmentData> scanSegmentsText(const std::vector<Segment> &segs, const std::vector<const char *> &names,
+                                              std::vector<ts_segment_counts> &counts, TrackText &text) {
+        if (names.size() != segs.size()) throw std::runtime_error("scanSegmentsText: one name per segment");
+        std::vector<ts_segment_in> in(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
+        std::vector<ts_segment_out> out(segs.size());
+        counts.assign(segs.size(), ts_segment_counts{0, 0, 0, 0});
+        // (the call replaces what `text` holds and reuses its arrays)
+        if (ts_scan_segments_text(ctx.get(), in.data(), in.size(), names.data(), out.data(), counts.data(), &text.t, &text.m) != TS_OK)
+            throw std::runtime_error(ts_last_error(ctx.get()));
+        std::vector<SegmentData> res(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) res[i] = convert(out[i], segs[i]);
+        ts_free_segments(out.data(), out.size());
+        return res;
+    }
+    // what the first device's context has formatted as match lines since it was made (ts_match_text_stats): calls, canonical
+    // lines, non-canonical lines, text bytes — cumulative
+    std::array<uint64_t, 4> matchTextStats() const {
+        std::array<uint64_t, 4> s{};
+        if (ts_match_text_stats(ctx.get(), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(ctx.get()));
+        return s;
     }
 
     // scanSegments for a writer (src/teloscope.cpp:700-868 reads a path's windows, blocks, canonicalMatches and terminal

@@ -385,9 +385,11 @@ inline std::vector<PathComponents> splitPaths(const std::vector<RecordView> &rec
 
 // walkPath for every record, with one batched scan (result order = record order; seqPos = seqPosBase + index, or
 // (*seqPositions)[index] when given: the records' indices in the whole input, which a record filter leaves with gaps).
-// trackText: when given — and the run has no -m and one device — the windows stay on the device: *trackText receives the lines
-// of the five window tracks of these records in order (Teloscope::scanSegmentsTrackText), every path's `windows` stays empty
-// and its windowCount says how many there were.  Otherwise it is left empty and everything is as without it.
+// trackText: when given — and the object has one device — the windows stay on the device: *trackText receives the lines of the
+// five window tracks of these records in order (Teloscope::scanSegmentsTrackText), every path's `windows` stays empty and its
+// windowCount says how many there were; under -m it receives the lines of the two match files as well
+// (Teloscope::scanSegmentsText), the paths' match vectors stay empty and canonicalMatchCount comes from the counts: no match
+// record and no base is read on the host.  Otherwise it is left empty and everything is as without it.
 inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::vector<RecordView> &records, size_t seqPosBase = 0,
                                              const std::vector<PathComponents> *precomputed = nullptr,
                                              const std::vector<size_t> *seqPositions = nullptr, TrackText *trackText = nullptr) {
@@ -396,7 +398,7 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
     const std::vector<PathComponents> split = precomputed ? std::vector<PathComponents>() : splitPaths(records);
     const std::vector<PathComponents> &comps = precomputed ? *precomputed : split;
     std::vector<Teloscope::Segment> batch;
-    const bool textRoute = trackText && !ui.outMatches && teloscope.deviceCount() == 1;
+    const bool textRoute = trackText && teloscope.deviceCount() == 1;
     if (trackText && !textRoute) trackText->clear();            // (the text route's call replaces the text and reuses its arrays)
     std::vector<const char *> batchNames;                        // (text route: every segment's record name)
     // text records that N-runs cut into several segments: every segment gets its own piece list (reserved up front, so
@@ -464,11 +466,12 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
     std::vector<ts_segment_counts> counts;
     // (with -m: only the two match vectors the writers read are materialised; block calling has happened on the device)
     // (several devices: the batch is cut into one shard per device, and what comes back is the writers' view either way)
-    std::vector<SegmentData> scanned = textRoute ? teloscope.scanSegmentsTrackText(batch, batchNames, counts, *trackText)
+    std::vector<SegmentData> scanned = textRoute ? (ui.outMatches ? teloscope.scanSegmentsText(batch, batchNames, counts, *trackText)
+                                                                  : teloscope.scanSegmentsTrackText(batch, batchNames, counts, *trackText))
                                      : teloscope.deviceCount() > 1 ? teloscope.scanSegmentsWriterView(batch, counts)
                                      : ui.outMatches ? teloscope.scanSegments(batch, true)
                                                      : teloscope.scanSegmentsNoMatches(batch, counts);
-    const bool haveCounts = teloscope.deviceCount() > 1 || !ui.outMatches;
+    const bool haveCounts = teloscope.deviceCount() > 1 || !ui.outMatches || textRoute;
 
     std::vector<PathData> paths(records.size());
     size_t si = 0;
@@ -2146,6 +2149,15 @@ public:
                 if (text->size(f) >= (size_t(1) << 20) && threads > 1) textWriters.emplace_back(put);
                 else put();
             }
+            // ... and the match lines, when the device formatted them too (the paths' match vectors are empty then)
+            static_assert(NONCAN_MATCH == CAN_MATCH + 1, "match file order is File order");
+            for (int k = 0; k < TS_N_MATCH_FILES; ++k) {
+                const int f = CAN_MATCH + k;
+                if (!on[f] || !text->matchSize(k)) continue;
+                auto put = [this, text, f, k] { files[f].write(text->matchData(k), static_cast<std::streamsize>(text->matchSize(k))); };
+                if (text->matchSize(k) >= (size_t(1) << 20) && threads > 1) textWriters.emplace_back(put);
+                else put();
+            }
         }
         // work list in output order: per path its row/blocks/gaps/matches, then its windows in runs
         constexpr size_t kRun = 1u << 16;
@@ -2621,7 +2633,9 @@ public:
 };
 
 // library_bases: the bases of the segments handed to the library (N-runs are not; neither are records a filter dropped)
-struct ScanFastaTimes { double read_ms = 0, scan_ms = 0, write_ms = 0, wall_ms = 0; uint64_t bases = 0, windows = 0, library_bases = 0; size_t groups = 0; };
+// bases_read_back: joined bases the device routes copied back to the host (ts_fasta_chunk_bases: -m without deviceTracks)
+struct ScanFastaTimes { double read_ms = 0, scan_ms = 0, write_ms = 0, wall_ms = 0; uint64_t bases = 0, windows = 0, library_bases = 0; size_t groups = 0;
+                        uint64_t bases_read_back = 0; };
 
 // FASTA file -> the eleven output files + console path report; returns the totals for printSummary.
 // groupReader: a FastaGroupReader of fastaFile the caller made (and, with assembly record filters, selected from with keep())
@@ -2869,7 +2883,7 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
 
     // ---- phase 2: the kept records of every chunk joined, scanned and written; the others are never read again
     BedWriter writer(outBase, ui, console, manualCuration);
-    const bool useTrackText = deviceTracks && !ui.outMatches;
+    const bool useTrackText = deviceTracks;                     // (with -m the match lines are formatted on the device too)
     TrackText trackText;
     std::vector<char> hostBases;
     std::vector<ts_fasta_run> runs(4096);
@@ -2890,10 +2904,11 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
                 throw fail("FASTA join failed");
             if (nRuns > runs.size()) runs.resize(static_cast<size_t>(nRuns));
             if (ts_fasta_chunk_runs(chunk, runs.data(), runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
-            const bool hostView = ui.outMatches && !ui.ultraFastMode;
+            const bool hostView = ui.outMatches && !ui.ultraFastMode && !useTrackText;
             if (hostView) {                                     // matchSeq is cut out of the bases: one copy per chunk
                 hostBases.resize(static_cast<size_t>(total) + 1);
                 if (ts_fasta_chunk_bases(chunk, 0, total, hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
+                T.bases_read_back += total;
             }
             msJoin += since(t0);
             std::vector<PathComponents> comps(n);
@@ -2940,10 +2955,12 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
 // or read(2)), and per chunk: lines indexed, records framed, names gathered (ts_fasta_chunk_walk); body lines joined into contiguous bases and
 // the N-runs found (ts_fasta_chunk_join, ts_fasta_chunk_runs); PathComponents built from the runs, a few entries per record;
 // every segment handed to the scan as a device segment through walkRecordViews, so that blocks, counts and windows come back
-// exactly as for the host route; BedWriter fed.  With -m the joined bases are read back once per chunk (matchSeq needs them).
+// exactly as for the host route; BedWriter fed.  With -m and without deviceTracks the joined bases are read back once per chunk
+// (matchSeq needs them).
 // The bytes behind the last complete record stay in the chunk for the next fill; a record larger than a chunk makes it grow.
-// deviceTracks (off by default): the window tracks' lines are formatted on the device too (ts_scan_segments_tracks) and BedWriter
-// writes them as they come; see below.
+// deviceTracks (off by default): the window tracks' lines — and with -m the two match files' — are formatted on the device too
+// (ts_scan_segments_tracks, ts_scan_segments_text) and BedWriter writes them as they come; no base reaches the host then under
+// any flag set; see below.
 // Assembly record filters (selector given and active; otherwise nothing here changes): two phases.  Phase 1 feeds, walks and
 // checks every chunk (ts_fasta_chunk_strict: which bodies hold a byte that is no line end) and KEEPS it resident, an unfinished
 // record moving on device to device (ts_chunk_carry_over); tables and names stay on the host, a leading UTF-8 byte order mark
@@ -2992,9 +3009,9 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
     BedWriter writer(outBase, ui, console, manualCuration);
     // deviceTracks: the five window tracks are formatted on the device where the window records lie and come back as text
     // (opt-in: whether 13 x the records' bytes over PCIe beats the host's formatting threads depends on the box; README has the
-    // measurement).  With -m the flag is ignored and the host formats as ever: the match files and matchSeq dominate such a
-    // run, and the writers' view of the matches comes through another entry point.
-    const bool useTrackText = deviceTracks && !ui.outMatches;
+    // measurement).  With -m the lines of the two match files are formatted there as well (ts_scan_segments_text), from the match
+    // records and the joined bases where they lie: no base is read back and no match record downloaded.
+    const bool useTrackText = deviceTracks;
     TrackText trackText;
     std::vector<ts_fasta_record> recs(4096);
     std::vector<char> names(size_t(1) << 16), hostBases;
@@ -3047,10 +3064,11 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
             throw fail("FASTA join failed");
         if (nRuns > runs.size()) runs.resize(static_cast<size_t>(nRuns));
         if (ts_fasta_chunk_runs(chunk.p, runs.data(), runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
-        const bool hostView = ui.outMatches && !ui.ultraFastMode;
+        const bool hostView = ui.outMatches && !ui.ultraFastMode && !useTrackText;
         if (hostView) {                                         // matchSeq is cut out of the bases: one copy per chunk
             hostBases.resize(static_cast<size_t>(total) + 1);
             if (ts_fasta_chunk_bases(chunk.p, 0, total, hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
+            T.bases_read_back += total;
         }
         msJoin += since(t0);
 

@@ -137,6 +137,19 @@ class TrackText(C.Structure):
                 ("capacity", C.c_uint64 * N_TRACKS)]
 
 
+N_MATCH_FILES = 2                     # TS_N_MATCH_FILES: canonical, terminal non-canonical
+
+
+class MatchText(C.Structure):
+    _fields_ = [("text", C.c_void_p * N_MATCH_FILES), ("len", C.c_uint64 * N_MATCH_FILES), ("n_lines", C.c_uint64 * N_MATCH_FILES),
+                ("capacity", C.c_uint64 * N_MATCH_FILES)]
+
+
+class MatchLineSegment(C.Structure):
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("abs_pos", C.c_uint64), ("len", C.c_uint64),
+                ("base_off", C.c_uint64), ("name_off", C.c_uint64), ("name_len", C.c_uint32), ("tips_only", C.c_uint32)]
+
+
 class TrackSegment(C.Structure):
     _fields_ = [("first_window", C.c_uint64), ("n_windows", C.c_uint64), ("abs_pos", C.c_uint64), ("len", C.c_uint64),
                 ("name_off", C.c_uint64), ("name_len", C.c_uint32), ("reserved", C.c_uint32)]
@@ -263,6 +276,7 @@ SYMBOLS = [
     "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats", "ts_upload_stats",
     "ts_fasta_chunk_strict", "ts_gfa_chunk_check",
     "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
+    "ts_match_lines_format", "ts_free_match_text", "ts_scan_segments_text", "ts_match_text_stats",
     "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
 ]
 
@@ -471,6 +485,16 @@ def lib():
     L.ts_scan_segments_tracks.argtypes = [C.c_void_p, C.POINTER(SegmentIn), C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(SegmentOut),
                                           C.POINTER(SegmentCounts), C.POINTER(TrackText)]
     L.ts_scan_segments_tracks.restype = C.c_int
+    L.ts_match_lines_format.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MatchLineSegment), C.c_size_t, C.c_char_p,
+                                        C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(MatchText)]
+    L.ts_match_lines_format.restype = C.c_int
+    L.ts_free_match_text.argtypes = [C.POINTER(MatchText)]
+    L.ts_free_match_text.restype = None
+    L.ts_scan_segments_text.argtypes = [C.c_void_p, C.POINTER(SegmentIn), C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(SegmentOut),
+                                        C.POINTER(SegmentCounts), C.POINTER(TrackText), C.POINTER(MatchText)]
+    L.ts_scan_segments_text.restype = C.c_int
+    L.ts_match_text_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_match_text_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -92,6 +92,7 @@ void read_env_knobs(ts_ctx *c) {
     k.packed_upload = !is("TS_PACKED_UPLOAD", '0');
     if (const char *e = getenv("TS_PACKED_MIN_BYTES")) k.packed_min_bytes = strtoull(e, nullptr, 10);
     k.rec16 = !is("TS_REC32", '1');
+    if (const char *e = getenv("TS_MATCH_SLICE_BYTES")) k.match_slice_bytes = strtoull(e, nullptr, 10);
     c->knobs = k;
 }
 

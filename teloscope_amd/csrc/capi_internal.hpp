@@ -136,6 +136,7 @@ struct ts_ctx {
         bool timing = false, gen_list = true, packed_upload = true;
         bool rec16 = true;                                    // scans keep 16-bit records where they can (TS_REC32=1: 32-bit)
         uint64_t packed_min_bytes = 1u << 20;                 // small calls are latency, not link time: they go plain
+        uint64_t match_slice_bytes = 256ull << 20;            // match lines (match_text.cpp): text of both files formatted per slice (TS_MATCH_SLICE_BYTES)
     } knobs;
     BufferPool pool;
     // host-buffer entry points (pipeline.cpp): pinned staging rings and their streams
@@ -168,6 +169,8 @@ struct ts_ctx {
     std::atomic<uint64_t> device_input_stats[4] = {};
     // ts_upload_stats: which way upload_pieces sent its chunks and packed their 16384-position blocks — since ts_create
     std::atomic<uint64_t> upload_stats[8] = {};
+    // ts_match_text_stats: formatting calls, canonical lines, non-canonical lines, text bytes — since ts_create
+    std::atomic<uint64_t> match_text_stats[4] = {};
     // ts_gzip_stats: windows, spans probed, spans chained, spans dropped, plain bytes produced, parts the caller handed to zlib — since ts_create
     std::atomic<uint64_t> gzip_stats[6] = {};
     hipEvent_t gen_ev[2] = {nullptr, nullptr};   // TS_TIMING: around the general path's kernels
@@ -393,6 +396,28 @@ struct ts_track_segment;
 void ts_track_text_begin(const ts_ctx *c, ts_track_text *t);    // a caller's struct (zeroed, or an earlier result: reused) made empty
 int  ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_records, uint64_t n_records, const ts_track_segment *segs,
                       size_t n_segs, const char *names, uint64_t names_len, hipStream_t st, ts_track_text *out);
+
+// match_text.cpp: the lines of the two match files (contexts with out_matches; others: nothing happens), formatted on the
+// device from a record stream that lies there and appended to *out.  The stream: `records` in one of match_text.hip's forms,
+// addressed by the directory {tile_off, tile_stats} over `tiles` (TsTile / TsGeneralTile; TS_MATCH_FORM_ARRAY: TsMatchTile and
+// no directory); `bases`: what the segments' base_off points into.  segs[i] is the segment the tiles call i.  Work and copies
+// run on st; synchronous.
+struct ts_match_text;
+struct ts_match_line_segment;
+struct TsMatchSource {
+    uint32_t form = 0;
+    const void *records = nullptr, *tiles = nullptr;
+    const unsigned long long *tile_off = nullptr;
+    const uint32_t *tile_stats = nullptr;
+    size_t n_tiles = 0;
+    const void *bases = nullptr;
+    const uint32_t *wide_len = nullptr;
+    unsigned long long gen_lens = 0;
+    uint32_t k = 0;
+};
+void ts_match_text_begin(const ts_ctx *c, ts_match_text *t);    // a caller's struct (zeroed, or an earlier result: reused) made empty
+int  ts_matches_append(ts_ctx *c, const TsMatchSource &src, const ts_match_line_segment *segs, size_t n_segs, const char *names,
+                       uint64_t names_len, hipStream_t st, ts_match_text *out);
 
 // bgzf.cpp: a chunk of an uncompressed stream resident on the device (ts_bam_chunk_*; ts_chunk is the same type: fastq.cpp)
 struct ts_bam_chunk {

@@ -99,37 +99,58 @@ struct Outputs {
     uint32_t *ends = nullptr;
     ts_track_text *tracks = nullptr;              // Tracks: every group's lines are appended, in item order (not sliced); names: per item
     const char *const *names = nullptr;
+    ts_match_text *matches = nullptr;             // Tracks: the match lines, likewise (ts_scan_segments_text)
     Outputs slice(size_t at) const {
         return {out ? out + at : nullptr, counts ? counts + at : nullptr, pass ? pass + at : nullptr, ends ? ends + 2 * at : nullptr,
-                tracks, names ? names + at : nullptr};
+                tracks, names ? names + at : nullptr, matches};
     }
 };
 
-// Tracks: the lines of a group's windows, formatted where the records lie (tracks.cpp), appended to the call's text.  segs: the
-// group's segments with first_window / n_windows / abs_pos / len set; names[i]: segment i's name.
-int group_tracks(ts_ctx *c, const uint32_t *d_windows, uint64_t n_windows, std::vector<ts_track_segment> &segs, const char *const *names,
-                 hipStream_t st, ts_track_text *out) {
+// The names of a group's segments as the formatters read them: one blob, a name stored once per run of equal ones
+// (consecutive segments of one path share a name); made once per group and shared by the track and the match step.
+struct NameBlob {
     std::string blob;
-    for (size_t i = 0; i < segs.size(); ++i) {
-        // (consecutive segments of one path share a name: it is stored once)
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+};
+int group_names(ts_ctx *c, const char *const *names, size_t n, NameBlob &nb) {
+    nb.off.resize(n); nb.len.resize(n);
+    for (size_t i = 0; i < n; ++i) {
         const size_t len = std::strlen(names[i]);
-        if (i && segs[i - 1].name_len == len && std::memcmp(blob.data() + segs[i - 1].name_off, names[i], len) == 0) {
-            segs[i].name_off = segs[i - 1].name_off;
-        } else {
-            segs[i].name_off = blob.size();
-            blob.append(names[i], len);
-        }
         if (len > 0xFFFFFFFFull) return c->fail(TS_ERR_INVALID_ARG, "ts_scan_segments_tracks: a name of 4 GiB or more");
-        segs[i].name_len = (uint32_t)len;
+        if (i && nb.len[i - 1] == len && std::memcmp(nb.blob.data() + nb.off[i - 1], names[i], len) == 0) {
+            nb.off[i] = nb.off[i - 1];
+        } else {
+            nb.off[i] = nb.blob.size();
+            nb.blob.append(names[i], len);
+        }
+        nb.len[i] = (uint32_t)len;
     }
-    return ts_tracks_append(c, d_windows, nullptr, n_windows, segs.data(), segs.size(), blob.data(), blob.size(), st, out);
+    return TS_OK;
+}
+
+// Tracks: the lines of a group's windows, formatted where the records lie (tracks.cpp), appended to the call's text.  segs: the
+// group's segments with first_window / n_windows / abs_pos / len set; nb: their names.
+int group_tracks(ts_ctx *c, const uint32_t *d_windows, uint64_t n_windows, std::vector<ts_track_segment> &segs, const NameBlob &nb,
+                 hipStream_t st, ts_track_text *out) {
+    for (size_t i = 0; i < segs.size(); ++i) { segs[i].name_off = nb.off[i]; segs[i].name_len = nb.len[i]; }
+    return ts_tracks_append(c, d_windows, nullptr, n_windows, segs.data(), segs.size(), nb.blob.data(), nb.blob.size(), st, out);
+}
+
+// ... and the lines of its match records, formatted from the record stream and the input buffer where they lie
+// (match_text.cpp).  segs: the group's segments with abs_pos / len / base_off set (all of them full scans).
+int group_matches(ts_ctx *c, const TsMatchSource &src, std::vector<ts_match_line_segment> &segs, const NameBlob &nb, hipStream_t st,
+                  ts_match_text *out) {
+    for (size_t i = 0; i < segs.size(); ++i) { segs[i].name_off = nb.off[i]; segs[i].name_len = nb.len[i]; }
+    return ts_matches_append(c, src, segs.data(), segs.size(), nb.blob.data(), nb.blob.size(), st, out);
 }
 
 struct Group {
     size_t first = 0, count = 0;                  // items [first, first + count) of the call's item list
     ts_batch *b = nullptr;
     hipEvent_t uploaded = nullptr;
-    double t_plan = 0, t_upload = 0, t_scan = 0, t_down = 0, t_fetch = 0, t_final = 0;
+    double t_plan = 0, t_upload = 0, t_scan = 0, t_down = 0, t_fetch = 0, t_final = 0, t_text = 0;
+    bool input_kept = false;                      // the download stage reads the input buffer (match lines) and releases it
 };
 
 int ensure_streams(ts_ctx *c) {
@@ -745,6 +766,7 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
     if (ctx->device == kNoDevice) return ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it");
     const auto t_begin = Clock::now();
     const bool timing = ctx->knobs.timing;                       // stage times to stderr
+    const bool match_text = mode == Mode::Tracks && !tips && o.matches && ctx->params.out_matches;   // ts_scan_segments_text under -m
     {
         DeviceGuard g(ctx->device);
         if (g.error() != hipSuccess) return ctx->fail(TS_ERR_HIP, "hipSetDevice failed");
@@ -826,8 +848,9 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
             if (rc == TS_OK && hipStreamWaitEvent(ctx->scan_stream, gr->uploaded, 0) != hipSuccess) rc = ctx->fail(TS_ERR_HIP, "hipStreamWaitEvent failed");
             if (rc == TS_OK) rc = ts_batch_scan(gr->b, nullptr, ctx->scan_stream);
             if (rc == TS_OK) rc = ts_batch_sync(gr->b);          // waits for the scan; regrows + rescans on overflow
-            ts_batch_release_input(gr->b);
-            inputs_in_flight.release();
+            // (match lines are cut out of the input buffer where it lies: the download stage gives it back)
+            gr->input_kept = rc == TS_OK && match_text;
+            if (!gr->input_kept) { ts_batch_release_input(gr->b); inputs_in_flight.release(); }
             gr->t_scan = ms_between(t0, Clock::now());
             if (rc != TS_OK) set_err(rc);
             to_down.push(gr);
@@ -842,7 +865,14 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
         Group *gr;
         std::thread post;                                        // host post-processing of the previous group
         int slot = 0;
+        auto release_kept = [&](Group *g2) {
+            if (!g2->input_kept) return;
+            g2->input_kept = false;
+            ts_batch_release_input(g2->b);
+            inputs_in_flight.release();
+        };
         auto retire = [&](Group *g2, double t_from) {
+            release_kept(g2);
             if (g2->uploaded) (void)hipEventDestroy(g2->uploaded);
             ts_batch_destroy(g2->b);
             g2->b = nullptr;
@@ -861,14 +891,32 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
                 // device work + D2H of this group while the previous group's records are expanded on the host threads
                 ts_fetched *f = ts_batch_fetch(gr->b, mode == Mode::Matches, slot, &rc, mode != Mode::Tracks);
                 if (rc == TS_OK && (mode == Mode::Blocks || mode == Mode::Tracks) && go.counts) rc = batch_counts(gr->b, go.counts, tips, ctx->down_stream);
+                const auto t_text0 = Clock::now();
+                NameBlob nb;
+                if (rc == TS_OK && mode == Mode::Tracks && !tips && (go.tracks || match_text)) rc = group_names(ctx, go.names, gr->b->segs.size(), nb);
                 if (rc == TS_OK && mode == Mode::Tracks && go.tracks && !tips) {
                     std::vector<ts_track_segment> ts(gr->b->segs.size());
                     for (size_t i = 0; i < ts.size(); ++i) {
                         const SegPlan &sp = gr->b->segs[i];
                         ts[i] = ts_track_segment{sp.win_base, sp.n_windows, sp.abs_pos, sp.len, 0, 0, 0};
                     }
-                    rc = group_tracks(ctx, gr->b->windows_ptr(), gr->b->n_windows, ts, go.names, ctx->down_stream, go.tracks);
+                    rc = group_tracks(ctx, gr->b->windows_ptr(), gr->b->n_windows, ts, nb, ctx->down_stream, go.tracks);
                 }
+                if (rc == TS_OK && match_text) {
+                    // the records in the scan's own regions behind its tile directory, the bases in the batch's input buffer
+                    ts_batch *b = gr->b;
+                    std::vector<ts_match_line_segment> ms(b->segs.size());
+                    for (size_t i = 0; i < ms.size(); ++i) ms[i] = ts_match_line_segment{0, 0, b->segs[i].abs_pos, b->segs[i].len, b->segs[i].in_off, 0, 0, 0};
+                    TsMatchSource src;
+                    src.form = b->records16() ? TS_MATCH_FORM_TILED16 : TS_MATCH_FORM_TILED32;
+                    src.records = b->records_ptr(); src.tiles = b->d_tiles.p;
+                    src.tile_off = (const unsigned long long *)b->d_tile_off.p; src.tile_stats = b->stats_ptr();
+                    src.n_tiles = b->tiles.size(); src.bases = b->d_in.p; src.k = ctx->k;
+                    if (!b->d_in.p || !b->whole()) rc = ctx->fail(TS_ERR_STATE, "match lines: the group's input buffer is gone");
+                    else rc = group_matches(ctx, src, ms, nb, ctx->down_stream, go.matches);
+                }
+                release_kept(gr);
+                gr->t_text = ms_between(t_text0, Clock::now());
                 gr->t_fetch = ms_between(t0, Clock::now());
                 if (post.joinable()) post.join();
                 if (rc == TS_OK) {
@@ -897,13 +945,16 @@ int run_pipeline(ts_ctx *ctx, Mode mode, bool tips, const std::vector<Item> &ite
     scanner.join();
     downloader.join();
     if (timing) {
-        double p = 0, u = 0, s = 0, d = 0, f = 0, z = 0;
-        for (const Group &gr : groups) { p += gr.t_plan; u += gr.t_upload; s += gr.t_scan; d += gr.t_down; f += gr.t_fetch; z += gr.t_final; }
+        double p = 0, u = 0, s = 0, d = 0, f = 0, z = 0, x = 0;
+        for (const Group &gr : groups) { p += gr.t_plan; u += gr.t_upload; s += gr.t_scan; d += gr.t_down; f += gr.t_fetch; z += gr.t_final; x += gr.t_text; }
         const char *name = mode == Mode::Matches ? "ts_scan_segments" : mode == Mode::Blocks ? "ts_scan_segments_blocks"
                          : mode == Mode::Tracks ? "ts_scan_segments_tracks" : mode == Mode::Ends ? "ts_terminal_ends" : "ts_filter_reads";
         fprintf(stderr, "%s: %zu items in %zu groups, wall %.1f ms; stage sums (concurrent): plan %.1f ms, stage+upload %.1f ms, "
                         "scan (incl. waiting for the upload) %.1f ms, download + host post-processing %.1f ms (device work + D2H %.1f ms, host expansion %.1f ms)\n",
                 name, items.size(), groups.size(), ms_between(t_begin, Clock::now()), p, u, s, d, f, z);
+        if (mode == Mode::Tracks)
+            fprintf(stderr, "%s: text step (window tracks%s formatted on the device, within the device work above) %.1f ms; bases read back: 0, match records read back: 0\n",
+                    name, match_text ? " and match lines" : "", x);
     }
     return first_err.load();
 }
@@ -1362,10 +1413,29 @@ int gen_download(GenCall &g, GenGroup &gr) {
     h.recs = hrec;
     h.wins = text ? nullptr : hwin;
     HIP_TRY(c, hipStreamSynchronize(st));
+    const bool match_text = text && !g.tips && g.o.matches && g.P.out_matches;
+    NameBlob nb;
+    if (text && !g.tips && (g.o.tracks || match_text)) { const int rc = group_names(c, g.o.names + h.first, h.G.size(), nb); if (rc != TS_OK) return rc; }
     if (text && g.o.tracks && gr.nwin_total) {
         std::vector<ts_track_segment> ts(h.G.size());
         for (size_t i = 0; i < ts.size(); ++i) ts[i] = ts_track_segment{h.G[i].win_base, h.G[i].n_windows, h.G[i].abs_pos, h.G[i].len, 0, 0, 0};
-        const int rc = group_tracks(c, (const uint32_t *)gr.d_win.p, gr.nwin_total, ts, g.o.names + h.first, st, g.o.tracks);
+        const int rc = group_tracks(c, (const uint32_t *)gr.d_win.p, gr.nwin_total, ts, nb, st, g.o.tracks);
+        if (rc != TS_OK) return rc;
+    }
+    if (match_text) {
+        // the stream block calling read — the slots in place, or the dense stream in push order — behind the directory as the
+        // compaction left it (a record moved across a tile border carries its new tile-relative position); the bases in the
+        // group's input layout
+        if (!g.wide && !g.gen_lens) return c->fail(TS_ERR_UNSUPPORTED, "match lines: a pattern set whose lengths the record format does not carry");
+        std::vector<ts_match_line_segment> ms(h.G.size());
+        for (size_t i = 0; i < ms.size(); ++i) ms[i] = ts_match_line_segment{0, 0, h.G[i].abs_pos, h.G[i].len, h.G[i].layout_off, 0, 0, 0};
+        TsMatchSource src;
+        src.form = g.wide ? TS_MATCH_FORM_WIDE : TS_MATCH_FORM_GENERAL;
+        src.records = gr.d_records; src.tiles = gr.d_tiles.p;
+        src.tile_off = (const unsigned long long *)gr.d_off.p; src.tile_stats = (const uint32_t *)gr.d_stats.p;
+        src.n_tiles = h.tiles.size(); src.bases = gr.d_in.p;
+        src.gen_lens = g.gen_lens; src.wide_len = g.wide ? c->wpat.len : nullptr;
+        const int rc = group_matches(c, src, ms, nb, st, g.o.matches);
         if (rc != TS_OK) return rc;
     }
     if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
@@ -1518,7 +1588,7 @@ int scan_segments_impl(ts_ctx *ctx, Mode mode, const ts_segment_in *segs, size_t
         std::vector<const char *> names(o.names ? which.size() : 0);
         for (size_t i = 0; i < names.size(); ++i) names[i] = o.names[which[i]];
         rc = route(ctx, mode, tips, items, Outputs{out.data(), o.counts ? counts.data() : nullptr, nullptr, nullptr, tips ? nullptr : o.tracks,
-                                                     names.empty() ? nullptr : names.data()}, have_lock);
+                                                     names.empty() ? nullptr : names.data(), tips ? nullptr : o.matches}, have_lock);
         if (rc != TS_OK) { ts_free_segments(out.data(), out.size()); break; }
         for (size_t i = 0; i < which.size(); ++i) {
             o.out[which[i]] = out[i];
@@ -1578,6 +1648,33 @@ int ts_scan_segments_tracks(ts_ctx *ctx, const ts_segment_in *segs, size_t n_seg
     }
     if (rc != TS_OK) ts_free_track_text(tracks);
     return rc;
+}
+
+// ts_scan_segments_tracks plus the match lines: every group's match records are formatted where they lie (match_text.hip), from
+// the group's input buffer, and appended to `matches`; see include/teloscan.h.
+int ts_scan_segments_text(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, const char *const *names, ts_segment_out *out,
+                          ts_segment_counts *counts, ts_track_text *tracks, ts_match_text *matches) {
+    if (!ctx || (!tracks && !matches) || (n_segs && (!segs || !out || !names))) return TS_ERR_INVALID_ARG;
+    if (tracks) ts_track_text_begin(ctx, tracks);
+    if (matches) ts_match_text_begin(ctx, matches);
+    auto fail = [&](int rc) {
+        if (tracks) ts_free_track_text(tracks);
+        if (matches) ts_free_match_text(matches);
+        return rc;
+    };
+    for (size_t i = 0; i < n_segs; ++i)
+        if (!names[i]) return fail(ctx->fail(TS_ERR_INVALID_ARG, "ts_scan_segments_text: null name"));
+    if (ctx->device == kNoDevice) return fail(ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it"));
+    Outputs o{out, counts};
+    o.tracks = tracks; o.names = names; o.matches = matches;
+    int rc = scan_segments_impl(ctx, Mode::Tracks, segs, n_segs, o, false);
+    if (rc == TS_OK) {                                           // (a call without a full-scan segment: the texts exist, empty)
+        DeviceGuard g(ctx->device);
+        if (tracks) rc = ts_tracks_append(ctx, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, tracks);
+        if (rc == TS_OK && matches) rc = ts_matches_append(ctx, TsMatchSource{}, nullptr, 0, nullptr, 0, nullptr, matches);
+        if (rc != TS_OK) ts_free_segments(out, n_segs);
+    }
+    return rc == TS_OK ? rc : fail(rc);
 }
 
 // =========================================================================== ReadTelomereFilter

@@ -221,6 +221,12 @@ int ts_k_launch_track_count(const TsTrackParams *P, void *stream) {
     return (int)hipGetLastError();
 }
 
+int ts_k_launch_scan_columns(unsigned long long *sums, uint32_t n_columns, uint32_t n_blocks, void *stream) {
+    if (n_columns == 0) return 0;
+    hipLaunchKernelGGL(ts_track_scan_blocks, dim3(n_columns), dim3(64), 0, (hipStream_t)stream, sums, n_blocks);
+    return (int)hipGetLastError();
+}
+
 int ts_k_launch_track_write(const TsTrackParams *P, void *stream) {
     if (P->n_blocks == 0) return 0;
     hipLaunchKernelGGL(ts_track_write, dim3(P->n_blocks), dim3(kBlock), 0, (hipStream_t)stream, *P);

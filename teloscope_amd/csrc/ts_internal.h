@@ -426,6 +426,38 @@ int  ts_k_launch_track_count(const TsTrackParams *P, void *stream);
 int  ts_k_launch_track_write(const TsTrackParams *P, void *stream);
 // out[j] = the record of window idx[j] (device memory, all three)
 int  ts_k_launch_track_pick(const uint32_t *records, const unsigned long long *idx, unsigned long long n, uint32_t *out, void *stream);
+// ts_track_scan_blocks by itself: n_columns columns of n_blocks + 1 values each — a column's n_blocks sums become their exclusive
+// 64-bit prefix sums, its last entry their total
+int  ts_k_launch_scan_columns(unsigned long long *sums, uint32_t n_columns, uint32_t n_blocks, void *stream);
+// match_text.hip: the two match files as text (match_format_core.h: tsmatch::Segment).  A workgroup of one wave formats one tile
+// of the record stream's directory.  sums holds 4 x (n_tiles + 1) values — per tile the bytes of the canonical and of the
+// non-canonical file and their line counts; after ts_k_launch_match_count their exclusive prefix sums with the totals behind
+// them.  ts_k_launch_match_write(P, n) formats tiles [tile_first, tile_first + n): file f's lines of tile t start at
+// out[f] + sums[f][t] - slice_base[f].
+#define TS_MATCH_STAGE_BYTES 8192u
+#define TS_MATCH_FORM_TILED16 0u        // the tiled kernel's regions, 16-bit records: tiles = TsTile[], {tile_off, tile_stats} the batch's directory
+#define TS_MATCH_FORM_TILED32 1u        // ... 32-bit records
+#define TS_MATCH_FORM_GENERAL 2u        // the general kernels' stream (shift 5, 3-bit length index into gen_lens): tiles = TsGeneralTile[]
+#define TS_MATCH_FORM_WIDE    3u        // the wide form's (shift 8, 6-bit index into wide_len)
+#define TS_MATCH_FORM_ARRAY   4u        // ts_match[]: tiles = TsMatchTile[], no directory
+struct TsMatchTile { unsigned long long first; uint32_t count, seg; };   // records [first, first + count) belong to segment seg
+struct TsMatchTextParams {
+    const void *records;
+    const void *tiles;
+    const unsigned long long *tile_off;     // per tile: index of its first record
+    const uint32_t *tile_stats;             // per tile four words, the first its record count
+    const void *segs;                       // tsmatch::Segment[n_segs]; a tiled segment's base_off is its in_off of the input layout
+    const void *names;
+    const void *bases;                      // the input layout (or the caller's bases): base_off + segment-relative position
+    const uint32_t *wide_len;
+    unsigned long long gen_lens;
+    unsigned long long *sums;
+    void *out[2];
+    unsigned long long slice_base[2];
+    uint32_t form, n_tiles, tile_first, n_segs, k, terminal_limit;
+};
+int  ts_k_launch_match_count(const TsMatchTextParams *P, void *stream);
+int  ts_k_launch_match_write(const TsMatchTextParams *P, uint32_t n, void *stream);
 // exchange.hip: box calibration (see there)
 int  ts_k_box_probe(void *scratch, unsigned long long bytes, int num_cu, double *issue_per_ns, double *copy_bytes_per_ns, void *stream);
 int  ts_k_launch_widen_u16(const uint16_t *src, uint32_t *dst, unsigned long long n, void *stream);
