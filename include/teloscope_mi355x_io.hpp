@@ -2747,6 +2747,112 @@ inline AssemblySummary scanFastaToFiles(Teloscope &teloscope, const std::string 
 
 namespace detail {
 
+// The device FASTA route's chunk sizes: chunkLimit clamped to what the walk takes (4 GiB - 2) and to what the feed leaves of
+// it; -> the bytes a fill asks for.
+inline size_t clampFastaChunk(const ChunkFeed &feed, size_t chunkBytesArg, uint64_t &chunkLimit) {
+    chunkLimit = feed.chunkLimit(std::max<uint64_t>(std::min<uint64_t>(chunkLimit, 0xfffffffeull), 64));
+    return static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+}
+
+// ts_fasta_chunk_walk over a chunk: n records in recs, their names in names (both grown, once, to what the walk asks for), the
+// first byte behind the last complete record in next.
+inline void walkFastaChunk(ts_ctx *ctx, ts_chunk *chunk, bool atEnd, std::vector<ts_fasta_record> &recs, std::vector<char> &names,
+                           uint64_t &n, uint64_t &next) {
+    for (bool grown = false;; grown = true) {
+        uint64_t nameBytes = 0;
+        const int rc = ts_fasta_chunk_walk(chunk, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
+        if (rc == TS_OK) return;
+        if (grown || rc != TS_ERR_INVALID_ARG || (n <= recs.size() && nameBytes <= names.size())) throw deviceError(ctx, "FASTA walk failed");
+        if (n > recs.size()) recs.resize(static_cast<size_t>(n));
+        if (nameBytes > names.size()) names.resize(static_cast<size_t>(nameBytes));
+    }
+}
+
+// What both bodies of scanFastaToFilesDevice do with the records of a walked chunk, and their common end: the stage times, the
+// output files (made by open(), not before: a refusal in front of it leaves no file behind) and the summary.
+class FastaChunkStage {
+    using Clock = std::chrono::steady_clock;
+    static double since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+    const Clock::time_point tBegin_ = Clock::now();
+    Teloscope &teloscope_;
+    // deviceTracks: the five window tracks are formatted on the device where the window records lie and come back as text
+    // (opt-in: whether 13 x the records' bytes over PCIe beats the host's formatting threads depends on the box; README has the
+    // measurement).  With -m the lines of the two match files are formatted there as well (ts_scan_segments_text), from the match
+    // records and the joined bases where they lie: no base is read back and no match record downloaded.
+    const bool useTrackText_;
+    TrackText trackText_;
+    std::unique_ptr<BedWriter> writer_;
+    std::vector<char> hostBases_;
+    std::vector<ts_fasta_run> runs_ = std::vector<ts_fasta_run>(4096);
+    std::vector<uint64_t> offsets_;
+    ScanFastaTimes T_;
+public:
+    double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;      // (the first two: the caller's stages)
+    FastaChunkStage(Teloscope &teloscope, bool deviceTracks) : teloscope_(teloscope), useTrackText_(deviceTracks) {}
+    void open(const std::string &outBase, std::ostream &console, bool manualCuration) {
+        writer_.reset(new BedWriter(outBase, teloscope_.input(), console, manualCuration));
+    }
+
+    // Records recs[0, n) of the chunk: joined, their runs read (and their bases, where matchSeq needs them), scanned as device
+    // segments, written.  header(i): record i's header, a string that outlives the call; seqPos: null = firstRecord, + 1, ...
+    template <class Header>
+    void add(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, bool atEnd, const Header &header, size_t firstRecord,
+             const std::vector<size_t> *seqPos) {
+        const UserInputTeloscope &ui = teloscope_.input();
+        auto fail = [&](const char *what) { return deviceError(teloscope_.context(), what); };
+        auto t0 = Clock::now();
+        const void *dBases = nullptr;
+        uint64_t total = 0, nRuns = 0;
+        offsets_.resize(n);
+        if (ts_fasta_chunk_join(chunk, recs, n, atEnd ? 1 : 0, &dBases, offsets_.data(), &total, &nRuns, nullptr) != TS_OK) throw fail("FASTA join failed");
+        if (nRuns > runs_.size()) runs_.resize(static_cast<size_t>(nRuns));
+        if (ts_fasta_chunk_runs(chunk, runs_.data(), runs_.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
+        const bool hostView = ui.outMatches && !ui.ultraFastMode && !useTrackText_;
+        if (hostView) {                                         // matchSeq is cut out of the bases: one copy per chunk
+            hostBases_.resize(static_cast<size_t>(total) + 1);
+            if (ts_fasta_chunk_bases(chunk, 0, total, hostBases_.data()) != TS_OK) throw fail("reading the joined bases failed");
+            T_.bases_read_back += total;
+        }
+        msJoin += since(t0);
+        std::vector<PathComponents> comps(n);
+        std::vector<RecordView> views(n);
+        for (uint64_t r = 0; r < nRuns; ++r) {
+            const ts_fasta_run &run = runs_[static_cast<size_t>(r)];
+            if (run.record >= n) throw std::runtime_error("FASTA runs: a run of a record that was not joined");
+            if (run.is_gap) comps[run.record].gaps.push_back(GapInfo{run.start, run.len});
+            else { comps[run.record].segments.emplace_back(run.start, run.len); T_.library_bases += run.len; }
+        }
+        for (size_t i = 0; i < n; ++i)
+            views[i] = RecordView{header(i), hostView ? hostBases_.data() + offsets_[i] : nullptr, recs[i].n_bases, nullptr, 0, nullptr,
+                                  static_cast<const char *>(dBases) + offsets_[i]};
+        TrackText *text = useTrackText_ ? &trackText_ : nullptr;
+        t0 = Clock::now();
+        std::vector<PathData> paths = walkRecordViews(teloscope_, views, firstRecord, &comps, seqPos, text);
+        msScan += since(t0);
+        t0 = Clock::now();
+        writer_->add(paths, text);
+        for (const PathData &pd : paths) { T_.bases += pd.pathSize; T_.windows += pd.nWindows(); }
+        ++T_.groups;
+        msWrite += since(t0);
+    }
+
+    // The files finished, the TS_TIMING line, *times; the summary with the filter facts the caller knows.
+    AssemblySummary finish(bool filterActive, uint64_t filterInputCount, uint64_t filterSelectedCount, bool filtered, const ChunkFeed &feed,
+                           ScanFastaTimes *times) {
+        const auto tf = Clock::now();
+        AssemblySummary sum = writer_->finish();
+        sum.filterActive = filterActive; sum.filterInputCount = filterInputCount; sum.filterSelectedCount = filterSelectedCount;
+        msWrite += since(tf);
+        if (std::getenv("TS_TIMING"))
+            std::fprintf(stderr, "scanFastaToFilesDevice%s: upload%s %.0f ms, index%s %.0f ms, join %.0f ms, scan %.0f ms, write %.0f ms\n",
+                         filtered ? " (filtered)" : "", feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, filtered ? " + check" : "",
+                         msIndex, msJoin, msScan, msWrite);
+        T_.read_ms = msUpload + msIndex + msJoin; T_.scan_ms = msScan; T_.write_ms = msWrite; T_.wall_ms = since(tBegin_);
+        if (times) *times = T_;
+        return sum;
+    }
+};
+
 // scanFastaToFilesDevice with an active selector (its comment says what happens; the caller has checked the device count).
 inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
                                                       std::ostream &console, bool manualCuration, size_t chunkBytesArg,
@@ -2754,12 +2860,10 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
                                                       const SequenceSelector &selector, std::ostream &log, uint64_t residentLimit) {
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    const auto tBegin = Clock::now();
-    const UserInputTeloscope &ui = teloscope.input();
     ts_ctx *ctx = teloscope.context();
     auto fail = [&](const char *what) { return deviceError(ctx, what); };
-    double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;
-    ScanFastaTimes T;
+    FastaChunkStage stage(teloscope, deviceTracks);
+    double &msUpload = stage.msUpload, &msIndex = stage.msIndex;
 
     struct ChunkFree { void operator()(ts_chunk *c) const { ts_bam_chunk_destroy(c); } };
     std::vector<std::unique_ptr<ts_chunk, ChunkFree>> chunks;   // every one stays until its kept records are written
@@ -2779,8 +2883,7 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
     options.uploadFailed = "upload of the FASTA text failed";
     options.noRoom = noRoom;
     ChunkFeed feed(ctx, fastaFile, options);
-    chunkLimit = feed.chunkLimit(std::max<uint64_t>(std::min<uint64_t>(chunkLimit, 0xfffffffeull), 64));
-    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+    const size_t chunkBytes = clampFastaChunk(feed, chunkBytesArg, chunkLimit);
     const uint64_t compCap = feed.compCap(chunkBytes);
     auto makeChunk = [&](uint64_t cap) {
         ts_chunk *made = ts_bam_chunk_create(ctx, compCap, std::max<uint64_t>(cap, 64));
@@ -2842,14 +2945,8 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
         if (held == 0) continue;
 
         t0 = Clock::now();
-        uint64_t n = 0, next = 0, nameBytes = 0;
-        int rc = ts_fasta_chunk_walk(cur, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
-        if (rc == TS_ERR_INVALID_ARG && (n > recs.size() || nameBytes > names.size())) {
-            if (n > recs.size()) recs.resize(static_cast<size_t>(n));
-            if (nameBytes > names.size()) names.resize(static_cast<size_t>(nameBytes));
-            rc = ts_fasta_chunk_walk(cur, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
-        }
-        if (rc != TS_OK) throw fail("FASTA walk failed");
+        uint64_t n = 0, next = 0;
+        walkFastaChunk(ctx, cur, atEnd, recs, names, n, next);
         if (!atEnd && n == 0 && next == 0) { grow = true; msIndex += since(t0); continue; }    // one unfinished record: the chunk takes more
         grow = false;
         has.resize(static_cast<size_t>(n));
@@ -2882,69 +2979,18 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
     log << selectionMessage(sel) << "\n";
 
     // ---- phase 2: the kept records of every chunk joined, scanned and written; the others are never read again
-    BedWriter writer(outBase, ui, console, manualCuration);
-    const bool useTrackText = deviceTracks;                     // (with -m the match lines are formatted on the device too)
-    TrackText trackText;
-    std::vector<char> hostBases;
-    std::vector<ts_fasta_run> runs(4096);
-    std::vector<uint64_t> offsets;
+    stage.open(outBase, console, manualCuration);
     for (Held &h : heldChunks) {
-        ts_chunk *chunk = chunks[h.slot].get();
         std::vector<ts_fasta_record> kept;
         std::vector<size_t> seqPos;
         for (size_t i = 0; i < h.recs.size(); ++i)
             if (sel.keep[h.first + i]) { kept.push_back(h.recs[i]); seqPos.push_back(h.first + i); }
-        const size_t n = kept.size();
-        if (n) {
-            t0 = Clock::now();
-            const void *dBases = nullptr;
-            uint64_t total = 0, nRuns = 0;
-            offsets.resize(n);
-            if (ts_fasta_chunk_join(chunk, kept.data(), n, h.atEnd ? 1 : 0, &dBases, offsets.data(), &total, &nRuns, nullptr) != TS_OK)
-                throw fail("FASTA join failed");
-            if (nRuns > runs.size()) runs.resize(static_cast<size_t>(nRuns));
-            if (ts_fasta_chunk_runs(chunk, runs.data(), runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
-            const bool hostView = ui.outMatches && !ui.ultraFastMode && !useTrackText;
-            if (hostView) {                                     // matchSeq is cut out of the bases: one copy per chunk
-                hostBases.resize(static_cast<size_t>(total) + 1);
-                if (ts_fasta_chunk_bases(chunk, 0, total, hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
-                T.bases_read_back += total;
-            }
-            msJoin += since(t0);
-            std::vector<PathComponents> comps(n);
-            std::vector<RecordView> views(n);
-            for (uint64_t r = 0; r < nRuns; ++r) {
-                const ts_fasta_run &run = runs[static_cast<size_t>(r)];
-                if (run.record >= n) throw std::runtime_error("FASTA runs: a run of a record that was not joined");
-                if (run.is_gap) comps[run.record].gaps.push_back(GapInfo{run.start, run.len});
-                else { comps[run.record].segments.emplace_back(run.start, run.len); T.library_bases += run.len; }
-            }
-            for (size_t i = 0; i < n; ++i)
-                views[i] = RecordView{&ids[seqPos[i]], hostView ? hostBases.data() + offsets[i] : nullptr, kept[i].n_bases, nullptr, 0, nullptr,
-                                      static_cast<const char *>(dBases) + offsets[i]};
-            t0 = Clock::now();
-            std::vector<PathData> paths = walkRecordViews(teloscope, views, 0, &comps, &seqPos, useTrackText ? &trackText : nullptr);
-            msScan += since(t0);
-            t0 = Clock::now();
-            writer.add(paths, useTrackText ? &trackText : nullptr);
-            for (const PathData &pd : paths) { T.bases += pd.pathSize; T.windows += pd.nWindows(); }
-            ++T.groups;
-            msWrite += since(t0);
-        }
+        if (!kept.empty())
+            stage.add(chunks[h.slot].get(), kept.data(), kept.size(), h.atEnd, [&](size_t i) { return &ids[seqPos[i]]; }, 0, &seqPos);
         chunks[h.slot].reset();                                 // (its text and its joined bases are done with)
     }
-    const auto tf = Clock::now();
-    AssemblySummary sum = writer.finish();
-    sum.filterActive = true;                                    // (from this selection: the context existed before it was known)
-    sum.filterInputCount = sel.inputCount;
-    sum.filterSelectedCount = sel.selectedCount;
-    msWrite += since(tf);
-    if (std::getenv("TS_TIMING"))
-        std::fprintf(stderr, "scanFastaToFilesDevice (filtered): upload%s %.0f ms, index + check %.0f ms, join %.0f ms, scan %.0f ms, write %.0f ms\n",
-                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msJoin, msScan, msWrite);
-    T.read_ms = msUpload + msIndex + msJoin; T.scan_ms = msScan; T.write_ms = msWrite; T.wall_ms = since(tBegin);
-    if (times) *times = T;
-    return sum;
+    // (the filter facts are this selection's: the context existed before it was known)
+    return stage.finish(true, sel.inputCount, sel.selectedCount, true, feed, times);
 }
 
 }  // namespace detail
@@ -2982,41 +3028,27 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
                                               uint64_t residentLimit = 0) {
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    const auto tBegin = Clock::now();
     if (teloscope.deviceCount() > 1)
         throw std::runtime_error("scanFastaToFilesDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
                                  " (the joined bases lie in one device's memory)");
     if (selector && selector->active())
         return detail::scanFastaToFilesDeviceFiltered(teloscope, fastaFile, outBase, console, manualCuration, chunkBytesArg, times, chunkLimit,
                                                       deviceTracks, *selector, log, residentLimit);
-    const UserInputTeloscope &ui = teloscope.input();
+    detail::FastaChunkStage stage(teloscope, deviceTracks);
     ts_ctx *ctx = teloscope.context();
     auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
-    chunkLimit = std::max<uint64_t>(std::min<uint64_t>(chunkLimit, 0xfffffffeull), 64);
     detail::ChunkFeed::Options options;
     options.cannotOpen = "cannot open " + fastaFile;
     options.cannotRead = "read error in " + fastaFile;
     options.uploadFailed = "upload of the FASTA text failed";
     detail::ChunkFeed feed(ctx, fastaFile, options);
-    chunkLimit = feed.chunkLimit(chunkLimit);
-    double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;
-    ScanFastaTimes T;
-
-    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
+    const size_t chunkBytes = detail::clampFastaChunk(feed, chunkBytesArg, chunkLimit);
     struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, feed.compCap(chunkBytes), chunkBytes)};
     if (!chunk.p) throw fail("cannot make the device chunk");
 
-    BedWriter writer(outBase, ui, console, manualCuration);
-    // deviceTracks: the five window tracks are formatted on the device where the window records lie and come back as text
-    // (opt-in: whether 13 x the records' bytes over PCIe beats the host's formatting threads depends on the box; README has the
-    // measurement).  With -m the lines of the two match files are formatted there as well (ts_scan_segments_text), from the match
-    // records and the joined bases where they lie: no base is read back and no match record downloaded.
-    const bool useTrackText = deviceTracks;
-    TrackText trackText;
+    stage.open(outBase, console, manualCuration);
     std::vector<ts_fasta_record> recs(4096);
-    std::vector<char> names(size_t(1) << 16), hostBases;
-    std::vector<ts_fasta_run> runs(4096);
-    std::vector<uint64_t> offsets;
+    std::vector<char> names(size_t(1) << 16);
     std::vector<std::string> headers;
     size_t recordsDone = 0;
 
@@ -3037,79 +3069,28 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
         const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0), chunkLimit - carry));
         Clock::time_point t0 = Clock::now();
         atEnd = feed.fill(chunk.p, pos, want);
-        msUpload += since(t0);
+        stage.msUpload += since(t0);
         held = ts_bam_chunk_size(chunk.p); pos = 0;
         if (held == 0) continue;
 
         // records and names
         t0 = Clock::now();
-        uint64_t n = 0, next = 0, nameBytes = 0;
-        int rc = ts_fasta_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
-        if (rc == TS_ERR_INVALID_ARG && (n > recs.size() || nameBytes > names.size())) {
-            if (n > recs.size()) recs.resize(static_cast<size_t>(n));
-            if (nameBytes > names.size()) names.resize(static_cast<size_t>(nameBytes));
-            rc = ts_fasta_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, names.data(), names.size(), &nameBytes);
-        }
-        if (rc != TS_OK) throw fail("FASTA walk failed");
-        msIndex += since(t0);
+        uint64_t n = 0, next = 0;
+        detail::walkFastaChunk(ctx, chunk.p, atEnd, recs, names, n, next);
+        stage.msIndex += since(t0);
         pos = next;
         if (n == 0) continue;
 
-        // bases and runs
-        t0 = Clock::now();
-        const void *dBases = nullptr;
-        uint64_t total = 0, nRuns = 0;
-        offsets.resize(static_cast<size_t>(n));
-        if (ts_fasta_chunk_join(chunk.p, recs.data(), static_cast<size_t>(n), atEnd ? 1 : 0, &dBases, offsets.data(), &total, &nRuns, nullptr) != TS_OK)
-            throw fail("FASTA join failed");
-        if (nRuns > runs.size()) runs.resize(static_cast<size_t>(nRuns));
-        if (ts_fasta_chunk_runs(chunk.p, runs.data(), runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
-        const bool hostView = ui.outMatches && !ui.ultraFastMode && !useTrackText;
-        if (hostView) {                                         // matchSeq is cut out of the bases: one copy per chunk
-            hostBases.resize(static_cast<size_t>(total) + 1);
-            if (ts_fasta_chunk_bases(chunk.p, 0, total, hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
-            T.bases_read_back += total;
-        }
-        msJoin += since(t0);
-
-        // path components from the runs; every segment a device segment
+        // bases, runs, scan and output
         headers.resize(static_cast<size_t>(n));
-        std::vector<PathComponents> comps(static_cast<size_t>(n));
-        std::vector<RecordView> views(static_cast<size_t>(n));
-        for (uint64_t r = 0; r < nRuns; ++r) {
-            const ts_fasta_run &run = runs[static_cast<size_t>(r)];
-            if (run.record >= n) throw std::runtime_error("FASTA runs: a run of a record that was not joined");
-            if (run.is_gap) comps[run.record].gaps.push_back(GapInfo{run.start, run.len});
-            else { comps[run.record].segments.emplace_back(run.start, run.len); T.library_bases += run.len; }
-        }
-        for (size_t i = 0; i < n; ++i) {
-            const ts_fasta_record &r = recs[i];
-            headers[i] = detail::fastaHeaderWord(names.data() + r.name_at, names.data() + r.name_at + r.name_len);
-            views[i] = RecordView{&headers[i], hostView ? hostBases.data() + offsets[i] : nullptr, r.n_bases, nullptr, 0, nullptr,
-                                  static_cast<const char *>(dBases) + offsets[i]};
-        }
-        t0 = Clock::now();
-        std::vector<PathData> paths = walkRecordViews(teloscope, views, recordsDone, &comps, nullptr, useTrackText ? &trackText : nullptr);
+        stage.add(chunk.p, recs.data(), static_cast<size_t>(n), atEnd, [&](size_t i) {
+            headers[i] = detail::fastaHeaderWord(names.data() + recs[i].name_at, names.data() + recs[i].name_at + recs[i].name_len);
+            return &headers[i];
+        }, recordsDone, nullptr);
         recordsDone += static_cast<size_t>(n);
-        msScan += since(t0);
-        t0 = Clock::now();
-        writer.add(paths, useTrackText ? &trackText : nullptr);
-        for (const PathData &pd : paths) { T.bases += pd.pathSize; T.windows += pd.nWindows(); }
-        ++T.groups;
-        msWrite += since(t0);
     }
-    const auto tf = Clock::now();
-    AssemblySummary sum = writer.finish();
-    sum.filterActive = ui.sequenceFilterActive;
-    sum.filterInputCount = ui.filterInputCount;
-    sum.filterSelectedCount = ui.filterSelectedCount;
-    msWrite += since(tf);
-    if (std::getenv("TS_TIMING"))
-        std::fprintf(stderr, "scanFastaToFilesDevice: upload%s %.0f ms, index %.0f ms, join %.0f ms, scan %.0f ms, write %.0f ms\n",
-                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msJoin, msScan, msWrite);
-    T.read_ms = msUpload + msIndex + msJoin; T.scan_ms = msScan; T.write_ms = msWrite; T.wall_ms = since(tBegin);
-    if (times) *times = T;
-    return sum;
+    const UserInputTeloscope &ui = teloscope.input();
+    return stage.finish(ui.sequenceFilterActive, ui.filterInputCount, ui.filterSelectedCount, false, feed, times);
 }
 
 }  // namespace teloscope_mi355x

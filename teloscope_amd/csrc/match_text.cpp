@@ -7,14 +7,10 @@
 // block per file; one copy per file appends it to the caller's text.  When the two files together exceed the slice limit
 // (256 MB; TS_MATCH_SLICE_BYTES) the byte columns of the prefix sums come down and the tiles go through in runs that stay
 // below it, so that the device block stays bounded whatever the group holds.
-#include "capi_internal.hpp"
+#include "text_out.hpp"
 #include "match_format_core.h"
 
-#include "../../include/teloscan.h"
-
-#include <chrono>
 #include <cstdio>
-#include <cstdlib>
 
 static_assert(sizeof(ts_match_line_segment) == sizeof(tsmatch::Segment) && offsetof(ts_match_line_segment, name_len) == offsetof(tsmatch::Segment, name_len) &&
               offsetof(ts_match_line_segment, base_off) == offsetof(tsmatch::Segment, base_off) &&
@@ -27,48 +23,27 @@ namespace {
 
 constexpr uint32_t kArrayTile = 512;                // records per pseudo-tile of a ts_match array
 
-struct Pooled {                                     // device blocks of one call, back to the pool at its end
-    ts_ctx *c;
-    DevBuf segs, names, sums, text;
-    explicit Pooled(ts_ctx *c_) : c(c_) {}
-    ~Pooled() { for (DevBuf *d : {&segs, &names, &sums, &text}) c->pool.give(std::move(*d)); }
-};
-
-bool grow(ts_match_text *out, int f, uint64_t more) {
-    const uint64_t need = out->len[f] + more + 1;
-    if (out->text[f] && need <= out->capacity[f]) return true;
-    const uint64_t cap = std::max<uint64_t>(need, out->capacity[f] + out->capacity[f] / 2);
-    char *p = (char *)std::realloc(out->text[f], cap);
-    if (!p) return false;
-    out->text[f] = p; out->capacity[f] = cap;
-    return true;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
 }  // namespace
 
 int ts_matches_append(ts_ctx *c, const TsMatchSource &src, const ts_match_line_segment *segs, size_t n_segs, const char *names,
                       uint64_t names_len, hipStream_t st, ts_match_text *out) {
     const ts_params &P = c->params;
     if (!P.out_matches) return TS_OK;
+    const TextFiles files = text_files(out);
     for (int f = 0; f < TS_N_MATCH_FILES; ++f)
-        if (!grow(out, f, 0)) return c->fail(TS_ERR_ALLOC, "out of host memory");
+        if (!files.grow(f, 0)) return c->fail(TS_ERR_ALLOC, "out of host memory");
     if (!src.n_tiles || !n_segs) return TS_OK;
     if (src.n_tiles >= 0x7FFFFFFFull || n_segs > 0xFFFFFFFFull) return c->fail(TS_ERR_UNSUPPORTED, "match lines: too many tiles or segments in one call");
     for (size_t i = 0; i < n_segs; ++i) {
         const ts_match_line_segment &s = segs[i];
-        if (s.name_off > names_len || s.name_len > names_len - s.name_off)
-            return c->fail(TS_ERR_INVALID_ARG, "match lines: segment " + std::to_string(i) + ": its name lies outside the names");
-        // (a wave's 64 line lengths are summed in 32 bits on the device)
-        if (s.name_len > TS_TRACK_MAX_NAME)
-            return c->fail(TS_ERR_UNSUPPORTED, "match lines: segment " + std::to_string(i) + ": a name of more than 16 MiB (2^24 bytes) is not formatted on the device");
-        if (s.abs_pos + s.len < s.abs_pos) return c->fail(TS_ERR_INVALID_ARG, "match lines: segment " + std::to_string(i) + ": abs_pos + len exceeds 64 bits");
+        const int rc = text_check_segment(c, "match lines", i, s.name_off, s.name_len, names_len, s.abs_pos, s.len);
+        if (rc != TS_OK) return rc;
     }
 
     std::lock_guard<std::mutex> lock(c->track_mtx);
     const auto t_begin = std::chrono::steady_clock::now();
-    Pooled D(c);
+    struct { DevBuf segs, names, sums, text; } D;
+    PoolReturn give_back{c, {&D.segs, &D.names, &D.sums, &D.text}};
     const uint32_t nt = (uint32_t)src.n_tiles;
     const size_t col = (size_t)nt + 1;
     HIP_TRY(c, c->pool.take(n_segs * sizeof(tsmatch::Segment), D.segs));
@@ -98,7 +73,7 @@ int ts_matches_append(ts_ctx *c, const TsMatchSource &src, const ts_match_line_s
             pre[f].resize(col);
             HIP_TRY(c, hipMemcpy(pre[f].data(), K.sums + (size_t)f * col, col * 8, hipMemcpyDeviceToHost));
         }
-    double ms_write = 0, ms_copy = 0;
+    TextTimes ms;
     uint32_t n_slices = 0;
     for (uint32_t a = 0; a < nt && total[0] + total[1];) {
         uint32_t z = nt;
@@ -108,23 +83,11 @@ int ts_matches_append(ts_ctx *c, const TsMatchSource &src, const ts_match_line_s
         }
         const unsigned long long base[2] = {sliced ? pre[0][a] : 0ull, sliced ? pre[1][a] : 0ull};
         const unsigned long long bytes[2] = {sliced ? pre[0][z] - base[0] : total[0], sliced ? pre[1][z] - base[1] : total[1]};
-        auto t0 = std::chrono::steady_clock::now();
         if (bytes[0] + bytes[1]) {
-            const uint64_t off1 = (bytes[0] + 255u) & ~255ull, need = off1 + ((bytes[1] + 255u) & ~255ull);
-            if (D.text.bytes < need) { c->pool.give(std::move(D.text)); HIP_TRY(c, c->pool.take(need, D.text)); }
-            K.out[0] = D.text.p; K.out[1] = (char *)D.text.p + off1;
             K.slice_base[0] = base[0]; K.slice_base[1] = base[1];
             K.tile_first = a;
-            if (ts_k_launch_match_write(&K, z - a, st) != 0) return c->fail(TS_ERR_HIP, "match lines: write launch failed");
-            if (c->knobs.timing) { HIP_TRY(c, hipStreamSynchronize(st)); ms_write += ms_since(t0); t0 = std::chrono::steady_clock::now(); }
-            for (int f = 0; f < TS_N_MATCH_FILES; ++f) {
-                if (!bytes[f]) continue;
-                if (!grow(out, f, bytes[f])) return c->fail(TS_ERR_ALLOC, "out of host memory");
-                HIP_TRY(c, hipMemcpyAsync(out->text[f] + out->len[f], K.out[f], bytes[f], hipMemcpyDeviceToHost, st));
-                out->len[f] += bytes[f];
-            }
-            HIP_TRY(c, hipStreamSynchronize(st));
-            ms_copy += ms_since(t0);
+            const int rc = text_slice_out(c, "match lines", st, D.text, files, bytes, K.out, ms, [&] { return ts_k_launch_match_write(&K, z - a, st); });
+            if (rc != TS_OK) return rc;
             ++n_slices;
         }
         a = z;
@@ -135,17 +98,14 @@ int ts_matches_append(ts_ctx *c, const TsMatchSource &src, const ts_match_line_s
     if (c->knobs.timing)
         fprintf(stderr, "match lines: %llu canonical + %llu non-canonical lines of %u tiles, %llu bytes in %u slices, %.1f ms (tables up + count %.1f ms, "
                         "write kernel %.1f ms, text D2H %.1f ms); records and bases read where they lie: 0 bytes of either read back\n",
-                total[2], total[3], nt, total[0] + total[1], n_slices, ms_since(t_begin), ms_count, ms_write, ms_copy);
+                total[2], total[3], nt, total[0] + total[1], n_slices, ms_since(t_begin), ms_count, ms.write, ms.copy);
     return TS_OK;
 }
 
-// A caller's struct at the start of a call: zero-initialised, or an earlier call's result, whose arrays are kept and filled
-// again; a context without -m has no match files: freed.
+// A caller's struct at the start of a call (TextFiles::begin); a context without -m has no match files: freed.
 void ts_match_text_begin(const ts_ctx *c, ts_match_text *t) {
-    for (int f = 0; f < TS_N_MATCH_FILES; ++f) {
-        if (!c->params.out_matches || !t->text[f]) { std::free(t->text[f]); t->text[f] = nullptr; t->capacity[f] = 0; }
-        t->len[f] = 0; t->n_lines[f] = 0;
-    }
+    text_files(t).begin(c->params.out_matches ? 3u : 0u);
+    t->n_lines[0] = t->n_lines[1] = 0;
 }
 
 extern "C" {
@@ -190,7 +150,7 @@ int ts_match_lines_format(ts_ctx *ctx, const ts_match *records, uint64_t n, cons
     }
     hipStream_t st = c->down_stream;
     DevBuf d_rec, d_tiles, d_bases;
-    struct Return { ts_ctx *c; DevBuf &a, &b, &d; ~Return() { for (DevBuf *x : {&a, &b, &d}) c->pool.give(std::move(*x)); } } give_back{c, d_rec, d_tiles, d_bases};
+    PoolReturn give_back{c, {&d_rec, &d_tiles, &d_bases}};
     {
         std::lock_guard<std::mutex> dl(c->down_mtx);
         auto up = [&]() -> int {
@@ -216,8 +176,8 @@ int ts_match_lines_format(ts_ctx *ctx, const ts_match *records, uint64_t n, cons
 
 void ts_free_match_text(ts_match_text *t) {
     if (!t) return;
-    for (int f = 0; f < TS_N_MATCH_FILES; ++f) std::free(t->text[f]);
-    std::memset(t, 0, sizeof *t);
+    text_files(t).free_all();
+    t->n_lines[0] = t->n_lines[1] = 0;
 }
 
 int ts_match_text_stats(const ts_ctx *ctx, uint64_t out[4]) {

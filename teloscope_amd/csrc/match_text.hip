@@ -10,9 +10,8 @@
 //   (the scan)       tracks.hip's ts_track_scan_blocks over the four columns: exclusive 64-bit prefix sums, the totals behind them.
 //                    No atomics: the text's order is the stream's order;
 //   ts_match_write   the same lanes compute the same lengths again, scan them for their place, stage the wave's lines of one file
-//                    in LDS — shifted by the destination's offset within 16 bytes — and store aligned 16-byte pieces; only the
-//                    bytes in front of the first and behind the last 16-byte boundary go out singly.  64 lines that exceed the
-//                    staging area (names beyond ~40 bytes with long matches) are written bytewise.
+//                    in LDS and copy them out in aligned 16-byte pieces, as tracks.hip does (ts_text_emit.h says how).  64 lines
+//                    that exceed the staging area (names beyond ~40 bytes with long matches) are written bytewise.
 //
 // A workgroup is a single wave because a tile's records are consumed in a loop whose trip count differs from tile to tile:
 // the barriers between staging and copy-out are then a wave's own, and waves never wait for a longer neighbour.
@@ -28,29 +27,12 @@
 #include "match_format_core.h"
 #include "ts_device.h"
 #include "ts_internal.h"
+#include "ts_text_emit.h"
 
 namespace {
 
 typedef unsigned long long u64;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 using tsmatch::kFiles;
-
-constexpr uint32_t kStageBytes = TS_MATCH_STAGE_BYTES;      // staged text per wave and file
-constexpr uint32_t kStageVecs = kStageBytes / 16u + 1u;     // (+ the shift of up to 15 bytes)
-
-#define TS_GLOBAL __attribute__((address_space(1)))
-struct GlobalBytes {
-    const TS_GLOBAL unsigned char *p;
-    __device__ __forceinline__ uint32_t byte(u64 i) const { return p[i]; }
-};
-struct StageSink {
-    unsigned char *p;
-    __device__ __forceinline__ void put(uint32_t at, uint32_t byte) const { p[at] = (unsigned char)byte; }
-};
-struct GlobalSink {
-    TS_GLOBAL unsigned char *p;
-    __device__ __forceinline__ void put(uint32_t at, uint32_t byte) const { p[at] = (unsigned char)byte; }
-};
 
 // A tile as the formatter sees it: `count` records from index `first` of the stream, of segment `seg`, their offsets relative to
 // segment position `rel0`.
@@ -169,7 +151,6 @@ void ts_match_write(const TsMatchTextParams P) {
     if (sg.tips_only) return;
     const u64 col = (u64)P.n_tiles + 1u;
     u64 off[kFiles] = {P.sums[t] - P.slice_base[0], P.sums[col + t] - P.slice_base[1]};
-    unsigned char *lds = (unsigned char *)&stage[0];
     for (uint32_t i0 = 0; i0 < T.count; i0 += 64u) {
         const Line L = load_line<F>(P, sg, T, i0 + lane);
 #pragma unroll
@@ -179,22 +160,9 @@ void ts_match_write(const TsMatchTextParams P) {
             const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             if (!n) continue;
             TS_GLOBAL unsigned char *dst = (TS_GLOBAL unsigned char *)P.out[f] + off[f];    // the first byte of these lines
-            const bool staged = n <= kStageBytes;
-            const uint32_t shift = (uint32_t)((uintptr_t)dst & 15u);
-            if (len) {
-                if (staged) put_line(StageSink{lds}, shift + excl, P, sg, L.m);
-                else put_line(GlobalSink{dst}, excl, P, sg, L.m);
-            }
-            __syncthreads();
-            if (staged) {
-                uint32_t head = (16u - shift) & 15u;
-                if (head > n) head = n;
-                const uint32_t body = (n - head) & ~15u, rest = n - head - body;
-                if (lane < head) dst[lane] = lds[shift + lane];
-                if (lane >= 16u && lane - 16u < rest) dst[head + body + lane - 16u] = lds[shift + head + body + lane - 16u];
-                const uint32_t v0 = (shift + head) / 16u;        // (shift + head is 0 or 16 when there is a body)
-                for (uint32_t v = lane; v < body / 16u; v += 64u) *(TS_GLOBAL u32x4 *)(dst + head + 16u * v) = stage[v0 + v];
-            }
+            if (len) wave_put(stage, dst, n, excl, [&](const auto &s, uint32_t at) { put_line(s, at, P, sg, L.m); });
+            __syncthreads();                                     // (a single wave, and n is the same in all its lanes)
+            wave_copy_out(stage, dst, n, lane);
             __syncthreads();                                     // (the next lines reuse the staging area)
             off[f] += n;
         }

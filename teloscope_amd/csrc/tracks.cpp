@@ -10,14 +10,10 @@
 // once per context); every other window — the trailing windows of a segment, or all of them when the window is too long for a
 // table — gets the host's ts::shannon_entropy_memo of its record, as float bits in a sorted patch list.  The host has the
 // records at hand (ts_window_tracks_format) or picks the few it needs off the device (ts_track_pick).
-#include "capi_internal.hpp"
+#include "text_out.hpp"
 #include "track_format_core.h"
 
-#include "../../include/teloscan.h"
-
-#include <chrono>
 #include <cstdio>
-#include <cstdlib>
 
 static_assert(sizeof(ts_track_segment) == sizeof(tstrack::Segment) && offsetof(ts_track_segment, name_len) == offsetof(tstrack::Segment, name_len) &&
               offsetof(ts_track_segment, abs_pos) == offsetof(tstrack::Segment, abs_pos), "ts_track_segment is tstrack::Segment");
@@ -31,38 +27,19 @@ uint32_t track_mask(const ts_params &P) {
     return (P.out_win_repeats ? 7u : 0u) | (P.out_gc ? 1u << tstrack::GC : 0u) | (P.out_entropy ? 1u << tstrack::ENTROPY : 0u);
 }
 
-struct Pooled {                                     // device blocks of one call, back to the pool at its end
-    ts_ctx *c;
-    DevBuf segs, names, idx, picked, patches, sums, text;
-    explicit Pooled(ts_ctx *c_) : c(c_) {}
-    ~Pooled() { for (DevBuf *d : {&segs, &names, &idx, &picked, &patches, &sums, &text}) c->pool.give(std::move(*d)); }
-};
-
-bool grow(ts_track_text *out, int t, uint64_t more) {
-    const uint64_t need = out->len[t] + more + 1;
-    if (out->text[t] && need <= out->capacity[t]) return true;
-    const uint64_t cap = std::max<uint64_t>(need, out->capacity[t] + out->capacity[t] / 2);
-    char *p = (char *)std::realloc(out->text[t], cap);
-    if (!p) return false;
-    out->text[t] = p; out->capacity[t] = cap;
-    return true;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
 }  // namespace
 
 int ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_records, uint64_t n_records, const ts_track_segment *segs_in,
                      size_t n_segs_in, const char *names, uint64_t names_len, hipStream_t st, ts_track_text *out) {
     const ts_params &P = c->params;
     const uint32_t mask = track_mask(P), w = P.window_size, step = P.step;
+    const TextFiles files = text_files(out);
     for (int t = 0; t < TS_N_TRACKS; ++t)
-        if ((mask >> t & 1u) && !grow(out, t, 0)) return c->fail(TS_ERR_ALLOC, "out of host memory");
+        if ((mask >> t & 1u) && !files.grow(t, 0)) return c->fail(TS_ERR_ALLOC, "out of host memory");
     if (!mask || !n_records || !n_segs_in) return TS_OK;
     if (!w || !step) return c->fail(TS_ERR_INVALID_ARG, "window tracks: the context has no window size or step");
 
-    // the segments that have windows, checked: ascending, inside the record array, every window inside its segment, the name
-    // inside the names
+    // the segments that have windows, checked: ascending, inside the record array, every window inside its segment
     std::vector<tstrack::Segment> segs;
     uint64_t next = 0, lines = 0;
     for (size_t i = 0; i < n_segs_in; ++i) {
@@ -72,12 +49,8 @@ int ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_rec
             return c->fail(TS_ERR_INVALID_ARG, "window tracks: segment " + std::to_string(i) + ": its windows overlap the previous segment's or exceed the records");
         if ((unsigned __int128)(s.n_windows - 1) * step >= s.len)
             return c->fail(TS_ERR_INVALID_ARG, "window tracks: segment " + std::to_string(i) + ": more windows than its length holds");
-        if (s.name_off > names_len || s.name_len > names_len - s.name_off)
-            return c->fail(TS_ERR_INVALID_ARG, "window tracks: segment " + std::to_string(i) + ": its name lies outside the names");
-        // (line lengths and a wave's 64 of them are 32-bit on the device: a name is at most 16 MiB, reported, not misprinted)
-        if (s.name_len > TS_TRACK_MAX_NAME)
-            return c->fail(TS_ERR_UNSUPPORTED, "window tracks: segment " + std::to_string(i) + ": a name of more than 16 MiB (2^24 bytes) is not formatted on the device");
-        if (s.abs_pos + s.len < s.abs_pos) return c->fail(TS_ERR_INVALID_ARG, "window tracks: segment " + std::to_string(i) + ": abs_pos + len exceeds 64 bits");
+        const int rc = text_check_segment(c, "window tracks", i, s.name_off, s.name_len, names_len, s.abs_pos, s.len);
+        if (rc != TS_OK) return rc;
         segs.push_back(tstrack::Segment{s.first_window, s.n_windows, s.abs_pos, s.len, s.name_off, s.name_len, 0u});
         next = s.first_window + s.n_windows;
         lines += s.n_windows;
@@ -87,7 +60,8 @@ int ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_rec
 
     std::lock_guard<std::mutex> lock(c->track_mtx);
     const auto t_begin = std::chrono::steady_clock::now();
-    Pooled D(c);
+    struct { DevBuf segs, names, idx, picked, patches, sums, text; } D;
+    PoolReturn give_back{c, {&D.segs, &D.names, &D.idx, &D.picked, &D.patches, &D.sums, &D.text}};
     const bool table = P.out_entropy && c->entropy_term.size() == (size_t)w + 1;
     if (table && !c->d_entropy_term.p) {
         HIP_TRY(c, c->d_entropy_term.ensure(c->entropy_term.size() * 4));
@@ -142,7 +116,8 @@ int ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_rec
     HIP_TRY(c, c->pool.take(sums_bytes + 8, D.sums));
     unsigned long long *const d_bad = (unsigned long long *)((char *)D.sums.p + sums_bytes);
 
-    double ms_count = 0, ms_write = 0, ms_copy = 0;
+    double ms_count = 0;
+    TextTimes ms;
     for (uint64_t a = first; a < last; a += kSliceWindows) {
         const uint64_t z = std::min(last, a + kSliceWindows);
         auto t0 = std::chrono::steady_clock::now();
@@ -168,38 +143,19 @@ int ts_tracks_append(ts_ctx *c, const uint32_t *d_records, const uint32_t *h_rec
                                                    std::string(names + s.name_off, s.name_len) +
                                                    "'): a column value lies outside what the device formatter prints (0, -1, 2^-32 .. 128), or a count exceeds the window");
         }
-        t0 = std::chrono::steady_clock::now();
-        uint64_t off[TS_N_TRACKS], bytes = 0;
-        for (int t = 0; t < TS_N_TRACKS; ++t) { off[t] = bytes; bytes += (total[t] + 255u) & ~255ull; }
-        if (D.text.bytes < bytes) { c->pool.give(std::move(D.text)); HIP_TRY(c, c->pool.take(bytes, D.text)); }
-        for (int t = 0; t < TS_N_TRACKS; ++t) K.out[t] = (char *)D.text.p + off[t];
-        if (ts_k_launch_track_write(&K, st) != 0) return c->fail(TS_ERR_HIP, "window tracks: write launch failed");
-        if (c->knobs.timing) { HIP_TRY(c, hipStreamSynchronize(st)); ms_write += ms_since(t0); t0 = std::chrono::steady_clock::now(); }
-        for (int t = 0; t < TS_N_TRACKS; ++t) {
-            if (!(mask >> t & 1u) || !total[t]) continue;
-            if (!grow(out, t, total[t])) return c->fail(TS_ERR_ALLOC, "out of host memory");
-            HIP_TRY(c, hipMemcpyAsync(out->text[t] + out->len[t], K.out[t], total[t], hipMemcpyDeviceToHost, st));
-            out->len[t] += total[t];
-        }
-        HIP_TRY(c, hipStreamSynchronize(st));
-        ms_copy += ms_since(t0);
+        const int rc = text_slice_out(c, "window tracks", st, D.text, files, total, K.out, ms, [&] { return ts_k_launch_track_write(&K, st); });
+        if (rc != TS_OK) return rc;
     }
     out->n_lines += lines;
     if (c->knobs.timing)
         fprintf(stderr, "window tracks: %llu windows of %zu segments, %zu patched, %.1f ms (tables up + count %.1f ms, write kernel %.1f ms, text D2H %.1f ms)\n",
-                (unsigned long long)lines, segs.size(), patches.size(), ms_since(t_begin), ms_count, ms_write, ms_copy);
+                (unsigned long long)lines, segs.size(), patches.size(), ms_since(t_begin), ms_count, ms.write, ms.copy);
     return TS_OK;
 }
 
-// A caller's struct at the start of a call: zero-initialised, or an earlier call's result, whose arrays are kept and filled
-// again (a route that formats chunk after chunk neither frees nor faults in ~100 MB per chunk); a track this context does not
-// have is freed.
+// A caller's struct at the start of a call (TextFiles::begin); a track this context does not have is freed.
 void ts_track_text_begin(const ts_ctx *c, ts_track_text *t) {
-    const uint32_t mask = track_mask(c->params);
-    for (int i = 0; i < TS_N_TRACKS; ++i) {
-        if (!(mask >> i & 1u) || !t->text[i]) { std::free(t->text[i]); t->text[i] = nullptr; t->capacity[i] = 0; }
-        t->len[i] = 0;
-    }
+    text_files(t).begin(track_mask(c->params));
     t->n_lines = 0;
 }
 
@@ -215,7 +171,7 @@ int ts_window_tracks_format(ts_ctx *ctx, const uint32_t *records, uint64_t n, co
     if (rc != TS_OK) return rc;
     hipStream_t st = c->down_stream;
     DevBuf d_rec;
-    struct Return { ts_ctx *c; DevBuf &a; ~Return() { c->pool.give(std::move(a)); } } give_back{c, d_rec};
+    PoolReturn give_back{c, {&d_rec}};
     if (n) {
         std::lock_guard<std::mutex> dl(c->down_mtx);
         HIP_TRY(c, c->pool.take(n * 32, d_rec));
@@ -231,8 +187,8 @@ int ts_window_tracks_format(ts_ctx *ctx, const uint32_t *records, uint64_t n, co
 
 void ts_free_track_text(ts_track_text *t) {
     if (!t) return;
-    for (int i = 0; i < TS_N_TRACKS; ++i) std::free(t->text[i]);
-    std::memset(t, 0, sizeof *t);
+    text_files(t).free_all();
+    t->n_lines = 0;
 }
 
 }  // extern "C"

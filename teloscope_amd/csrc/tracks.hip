@@ -10,44 +10,24 @@
 //   ts_track_write        the same lane per window computes the same lengths again, once, (a record is 32 bytes, its five offsets
 //                         would be 40), scans them for its place and writes its lines.
 //
-// Stores.  A lane's line starts at whatever byte the lines before it end on, so lanes that stored their own lines would issue
-// byte stores at unaligned addresses, ~70 per line.  Instead a wave stages the text of its 64 lines of one track in LDS — shifted
-// by the destination's offset within a 16-byte line, so that 16-byte pieces of the staging area are 16-byte pieces of the file —
-// and copies it out with aligned 16-byte stores, lane l the l-th, (l + 64)-th, ... of them; only the bytes in front of the first
-// and behind the last 16-byte boundary go out singly (the neighbouring waves store the rest of those lines at the same time: no
-// read-modify-write).  A wave whose 64 lines of a track exceed the staging area (names beyond ~70 bytes) writes them bytewise.
+// Stores: a wave stages its 64 lines of one track in LDS and copies them out in aligned 16-byte pieces; ts_text_emit.h says how
+// (match_text.hip writes its lines the same way).  A wave's 64 lines exceed the staging area with names beyond ~70 bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "track_format_core.h"
 #include "ts_device.h"
 #include "ts_internal.h"
+#include "ts_text_emit.h"
 
 namespace {
 
 typedef unsigned long long u64;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 using tstrack::kTracks;
 
 constexpr uint32_t kBlock = TS_TRACK_BLOCK;                 // windows (threads) per workgroup
 constexpr uint32_t kWaves = kBlock / 64u;
-constexpr uint32_t kStageBytes = 8192u;                     // staged text per wave and track
-constexpr uint32_t kStageVecs = kStageBytes / 16u + 1u;     // (+ the shift of up to 15 bytes)
 constexpr uint32_t kSumsPerThread = 8u;                     // ts_track_scan_blocks: consecutive sums per lane
-
-#define TS_GLOBAL __attribute__((address_space(1)))
-struct GlobalNames {
-    const TS_GLOBAL unsigned char *p;
-    __device__ __forceinline__ uint32_t byte(u64 i) const { return p[i]; }
-};
-struct StageSink {                                          // a wave's staging area (the pointer comes straight from a __shared__ array)
-    unsigned char *p;
-    __device__ __forceinline__ void put(uint32_t at, uint32_t byte) const { p[at] = (unsigned char)byte; }
-};
-struct GlobalSink {
-    TS_GLOBAL unsigned char *p;
-    __device__ __forceinline__ void put(uint32_t at, uint32_t byte) const { p[at] = (unsigned char)byte; }
-};
 
 // What a lane knows about its window before it formats a value.
 struct Window {
@@ -98,7 +78,7 @@ __device__ __forceinline__ uint32_t line_len(const Window &W, uint32_t t, tstrac
 
 template <class S>
 __device__ __forceinline__ void put_line(const S &s, uint32_t at, const TsTrackParams &P, const Window &W, const tstrack::FloatDec &d) {
-    const GlobalNames names{(const TS_GLOBAL unsigned char *)P.names};
+    const GlobalBytes names{(const TS_GLOBAL unsigned char *)P.names};
     tstrack::put_prefix(s, at, names, W.name_off, W.name_len, W.start, W.end);
     tstrack::put_float(s, at + W.prefix, d);
     s.put(at + W.prefix + tstrack::float_len(d), '\n');
@@ -177,26 +157,10 @@ void ts_track_write(const TsTrackParams P) {
         u64 off = P.block_sums[(u64)t * (P.n_blocks + 1u) + blockIdx.x];
         for (uint32_t w = 0; w < wave; ++w) off += tot[t][w];
         TS_GLOBAL unsigned char *dst = (TS_GLOBAL unsigned char *)P.out[t] + off;    // the wave's first byte
-        const uint32_t n = wave_bytes[t];
-        const bool staged = n <= kStageBytes;                    // (uniform over the wave)
-        const uint32_t shift = (uint32_t)((uintptr_t)dst & 15u);
         const tstrack::FloatDec d = dec[t];
-        const uint32_t len = lens[t];
-        unsigned char *lds = (unsigned char *)&stage[wave][0];
-        if (len) {
-            if (staged) put_line(StageSink{lds}, shift + excl[t], P, W, d);
-            else put_line(GlobalSink{dst}, excl[t], P, W, d);
-        }
-        __syncthreads();
-        if (staged && n) {
-            uint32_t head = (16u - shift) & 15u;
-            if (head > n) head = n;
-            const uint32_t body = (n - head) & ~15u, rest = n - head - body;
-            if (lane < head) dst[lane] = lds[shift + lane];
-            if (lane >= 16u && lane - 16u < rest) dst[head + body + lane - 16u] = lds[shift + head + body + lane - 16u];
-            const uint32_t v0 = (shift + head) / 16u;            // (shift + head is 0 or 16 when there is a body)
-            for (uint32_t v = lane; v < body / 16u; v += 64u) *(TS_GLOBAL u32x4 *)(dst + head + 16u * v) = stage[wave][v0 + v];
-        }
+        if (lens[t]) wave_put(stage[wave], dst, wave_bytes[t], excl[t], [&](const auto &s, uint32_t at) { put_line(s, at, P, W, d); });
+        __syncthreads();                                         // (outside every condition a wave could differ in: a wave without bytes waits too)
+        wave_copy_out(stage[wave], dst, wave_bytes[t], lane);
         __syncthreads();                                         // (the next track reuses the staging area)
     }
 }

@@ -434,7 +434,6 @@ int  ts_k_launch_scan_columns(unsigned long long *sums, uint32_t n_columns, uint
 // non-canonical file and their line counts; after ts_k_launch_match_count their exclusive prefix sums with the totals behind
 // them.  ts_k_launch_match_write(P, n) formats tiles [tile_first, tile_first + n): file f's lines of tile t start at
 // out[f] + sums[f][t] - slice_base[f].
-#define TS_MATCH_STAGE_BYTES 8192u
 #define TS_MATCH_FORM_TILED16 0u        // the tiled kernel's regions, 16-bit records: tiles = TsTile[], {tile_off, tile_stats} the batch's directory
 #define TS_MATCH_FORM_TILED32 1u        // ... 32-bit records
 #define TS_MATCH_FORM_GENERAL 2u        // the general kernels' stream (shift 5, 3-bit length index into gen_lens): tiles = TsGeneralTile[]

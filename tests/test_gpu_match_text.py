@@ -137,3 +137,27 @@ def test_what_the_entry_point_refuses(tel):
             M.device_format(tel, recs, table, bases)
         assert e.value.code == K.TS_ERR_INVALID_ARG, what
     check(tel, records, segs, bases)                                    # the context is fine afterwards
+
+
+def test_runs_of_64_lines_start_at_every_residue_mod_16(tel):
+    """17 segments of 65 records with names of 1 to 16 bytes: a segment is one pseudo-tile, whose records a wave takes in runs of
+    64, and the lines of such a run start on every residue modulo 16 of their file (a file's block starts 256-byte aligned) —
+    checked on the reference text before the device is asked — so the copy-out (text_store_core.h) meets every shift."""
+    records, segs, bases = M.counted_case([65] * 17)
+    # (the name lengths in an order in which the 51 run starts do reach every residue: in ascending order they miss one)
+    name_lens = [1, 5, 16, 7, 10, 14, 11, 6, 9, 2, 15, 3, 4, 8, 12, 13, 7]
+    segs = [sg[:5] + (bytes(97 + (i + k) % 26 for k in range(name_lens[i])),) + sg[6:] for i, sg in enumerate(segs)]
+    assert {len(sg[5]) for sg in segs} == set(range(1, 17))
+    want, _ = M.format_matches(records, segs, bases, M.CASE_LIMIT)
+    at, residues, pieces = [0, 0], set(), [[], []]
+    for sg in segs:
+        for i0 in range(0, sg[1], 64):
+            run, _ = M.format_matches(records, [(sg[0] + i0, min(64, sg[1] - i0)) + sg[2:]], bases, M.CASE_LIMIT)
+            for f in range(M.N_FILES):
+                if run[f]:
+                    residues.add(at[f] % 16)
+                    pieces[f].append(run[f])
+                    at[f] += len(run[f])
+    assert [b"".join(p) for p in pieces] == want                       # (the runs are the text, cut where the waves cut it)
+    assert residues == set(range(16))
+    check(tel, records, segs, bases)

@@ -268,3 +268,24 @@ def test_value_outside_the_domain_fails_the_call(tel_1000):
         T.device_format(tel_1000, records, big)
     assert e.value.code == K.TS_ERR_UNSUPPORTED and "16 MiB" in str(e.value)
     check(tel_1000, random_records(np.random.default_rng(2), seg_sizes(10 * s, w, s)), segs, w, s, (1, 1, 1))    # the context still works
+
+
+def test_wave_starts_at_every_residue_mod_16(tel_1000):
+    """Names of 1 to 16 bytes over 17 segments of 65 windows: the 64 lines of a wave start on every residue modulo 16 of their
+    file — which the reference text says before the device is asked (a track's block starts 256-byte aligned, so a wave's first
+    byte has its line's offset modulo 16) — so the head, body and tail stores of the copy-out (text_store_core.h) meet every
+    shift of the staging area."""
+    w, s = 1000, 500
+    lens = [65 * s] * 17
+    segs = layout(lens, s, names=[bytes(97 + (i + k) % 26 for k in range(1 + i % 16)) for i in range(17)])
+    assert [sg[1] for sg in segs] == [65] * 17 and {len(sg[4]) for sg in segs} == set(range(1, 17))
+    records = random_records(np.random.default_rng(16), [x for ln in lens for x in seg_sizes(ln, w, s)])
+    want = T.format_tracks(records, segs, w, s, 1, 1, 1)
+    residues = set()
+    for text in want:
+        lines = text.split(b"\n")[:-1]
+        assert len(lines) == 17 * 65
+        starts = np.concatenate([[0], np.cumsum([len(ln) + 1 for ln in lines])])
+        residues |= {int(starts[k]) % 16 for k in range(0, len(lines), 64)}
+    assert residues == set(range(16))
+    check(tel_1000, records, segs, w, s, (1, 1, 1), want)
