@@ -260,6 +260,13 @@ int     ts_device_input_stats(const ts_ctx *ctx, uint64_t out[4]);
  * unpack kernel for a chunk whose first base is not on a 64-position boundary of the layout.  Cumulative, monotonic and atomic,
  * like ts_device_input_stats: take the difference around a call. */
 int     ts_upload_stats(const ts_ctx *ctx, uint64_t out[8]);
+/* Measurement aid (no counterpart in the reference): what the context's GENERAL TIPS BATCHES (see the batch section below) have
+ * done since ts_create — out[0] scans enqueued on them, rescans included, out[1] segments ts_batch_read_pass judged on them,
+ * out[2] rescans ts_batch_sync made after a tile overflowed its slot or a candidate list spilled, out[3] bytes these calls
+ * copied device to host: the fused pass's flag word, four bytes per ts_batch_read_pass_status and per round of ts_batch_sync —
+ * no record and no block is ever downloaded.  Cumulative, monotonic and atomic, like ts_device_input_stats: take the difference
+ * around a call. */
+int     ts_read_batch_stats(const ts_ctx *ctx, uint64_t out[4]);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
  * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32, TS_MATCH_SLICE_BYTES) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
  * No counterpart in the reference (its options are fixed by main, /root/reference/src/main.cpp:149-184). */
@@ -448,7 +455,21 @@ typedef struct ts_batch_info {
 } ts_batch_info;
 
 /* Plans a batch of n_segs segments of the given lengths (all tips_only or all full scan).
- * match_capacity 0 = default (bases/4). */
+ * match_capacity 0 = default (bases/4).
+ *
+ * GENERAL TIPS BATCHES.  With tips_only = 1 the call succeeds on every context for which ts_takes_text_input(ctx, 1) is 1.  On
+ * a context whose tips-only scans go to the general kernels (mixed pattern lengths, patterns of 9 bases or more, up to 63 lengths
+ * of up to 63 bases) it returns a general tips batch: the same input layout (ts_batch_segment_offset, TS_IN_PAD zero bytes
+ * behind the last segment), so ts_batch_input_ptr, ts_batch_upload, ts_fastq_chunk_stage, ts_bam_chunk_decode and a caller's
+ * own d_input fill it unchanged; ts_batch_scan enqueues the general kernels' fused tips pass, ts_batch_read_pass the read
+ * predicate over its records (same stream), ts_batch_read_pass_status says whether a tile overflowed its record slot or a
+ * candidate list spilled, and ts_batch_sync then regrows the slots (or changes the pass's form) and rescans — the protocol of a
+ * tiled read batch.  ts_batch_get_info fills the segments, bases, input bytes, tiles and slot capacity (the rest is 0), and
+ * ts_batch_destroy frees it.  match_capacity is ignored.  EVERY OTHER ts_batch_* call (restrict, partition, the shard calls,
+ * bind, export, adopt, the downloads, the summary, get_tiles / range_info, set_emit, set_record_bits, set_timing, wait_scan) and
+ * ts_shards_finalize answers TS_ERR_UNSUPPORTED with the call named in ts_last_error; the three pointer calls return NULL and
+ * ts_batch_wire16_ok 0.  Full-scan batches (tips_only = 0) of such sets stay refused: the host entry points scan them.  The
+ * reference has no batches at all (one job per read, src/input.cpp:753-812). */
 ts_batch *ts_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t *abs_pos,
                           size_t n_segs, int tips_only, uint64_t match_capacity);
 void      ts_batch_destroy(ts_batch *b);
@@ -686,6 +707,9 @@ int ts_batch_read_pass(ts_batch *b, void *d_pass, void *stream);
  * *overflowed = 1 if any pass since the last call was skipped for that reason (then: ts_batch_sync, which regrows and
  * rescans, and ts_batch_read_pass again).  Waits for the device. */
 int ts_batch_read_pass_status(ts_batch *b, int *overflowed);
+/* (On a general tips batch — see ts_batch_create — the pass is always enqueued; after an overflow or a spill its bytes mean
+ * nothing, *overflowed says so on every call until ts_batch_sync has rescanned, and ts_batch_read_pass wants the stream of the
+ * scan.) */
 int ts_filter_reads_multi(ts_ctx *const *ctxs, size_t n_ctx, const char *const *seqs, const uint64_t *lens,
                           size_t n_reads, uint8_t *pass);
 

@@ -273,7 +273,7 @@ SYMBOLS = [
     "ts_bam_chunk_status", "ts_bam_chunk_size", "ts_bam_chunk_read", "ts_bam_chunk_walk", "ts_bam_chunk_decode", "ts_bam_chunk_gather", "ts_bam_chunk_pass_buffer",
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
-    "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats", "ts_upload_stats",
+    "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats", "ts_upload_stats", "ts_read_batch_stats",
     "ts_fasta_chunk_strict", "ts_gfa_chunk_check",
     "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
     "ts_match_lines_format", "ts_free_match_text", "ts_scan_segments_text", "ts_match_text_stats",
@@ -419,6 +419,7 @@ def lib():
     L.ts_box_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ts_device_input_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ts_upload_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_read_batch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ts_gzip_create.restype = C.c_void_p
     L.ts_gzip_create.argtypes = [C.c_void_p, C.c_uint32]
     L.ts_gzip_destroy.restype = None
@@ -431,6 +432,7 @@ def lib():
     L.ts_gzip_note_fallback.argtypes = [C.c_void_p, C.c_uint64]
     L.ts_device_input_stats.restype = C.c_int
     L.ts_upload_stats.restype = C.c_int
+    L.ts_read_batch_stats.restype = C.c_int
     L.ts_exchange_unique_id.argtypes = [C.c_void_p]
     L.ts_exchange_last_error.restype = C.c_char_p
     L.ts_exchange_create.restype = C.c_void_p

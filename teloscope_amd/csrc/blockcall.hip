@@ -111,9 +111,12 @@ __device__ __forceinline__ void emit_block(const TsBlockCallParams &Q, TsDevBloc
 // record: a telomere is one chain of thousands of matches.  Lane 0 writes the blocks.
 // (forced inline: as a function of its own it took the kernel's parameters by reference — the whole parameter block went to scratch,
 // every pointer out of it became a flat address, and the eight rows it fetches ahead were waited for behind the first scratch reload)
-template <int MODE>
+// PASS (ts_terminal_pass, a general read batch's predicate): a block that would be emitted sets pass[seg] instead — no block
+// buffer, no counter; the instantiations without it are the code they were.
+template <int MODE, bool PASS = false>
 __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, const SegView &V, uint32_t seg, u64 n, u64 abs_pos,
-                                  bool from_start, uint32_t &seq, uint32_t lane, bool &out_of_context) {
+                                  bool from_start, uint32_t &seq, uint32_t lane, bool &out_of_context,
+                                  unsigned char *pass = nullptr) {
     u64 boundary = from_start ? 0 : n;                     // segment-relative
     const uint32_t wlen_lane = (MODE == 1 && Q.wide) ? Q.wide_len[lane] : 0u;     // (the table holds 64 entries)
     Chain ch; bool open = false;
@@ -128,8 +131,11 @@ __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, co
             cur.has_valid_or = from_start ? (left <= right) : (left >= right);
             boundary = from_start ? cur.start + cur.block_len : cur.start;
             if (lane == 0) {
-                TsDevBlock out = cur;
-                emit_block(Q, out, seg, from_start ? 0u : 1u, seq, abs_pos);
+                if constexpr (PASS) pass[seg] = 1;
+                else {
+                    TsDevBlock out = cur;
+                    emit_block(Q, out, seg, from_start ? 0u : 1u, seq, abs_pos);
+                }
             }
             ++seq;
         }
@@ -422,6 +428,48 @@ void ts_terminal_blocks(const TsBlockCallParams Q, const TsShardSegIn *segs, uin
                 atomicOr(&seg_out[si].flags, (walk ? TS_SEG_F_REV_WALKED : 0u) | (ooc ? TS_SEG_F_CONTEXT : 0u));
             }
         }
+    }
+}
+
+// ---- the read predicate over the general kernels' records (a general tips batch: ts_batch_read_pass)
+//
+// ts_slot_counts: the records lie where the fused pass wrote them, tile t's in its slot of slot_cap entries.  One wave per tile
+// counts its canonical and forward records into words 1 and 2 of the tile directory (the walks' ">= 2 matches" gates read them).
+// A tile that overflowed its slot has a count above slot_cap and records that were never written: its count is cut to the slot,
+// so that no walk reads behind it — the pass bytes of such a scan mean nothing, the fused pass's flag word says so, and the
+// rescan writes every count anew.
+__global__ __launch_bounds__(kSideWg)
+void ts_slot_counts(const uint32_t *records, uint32_t slot_cap, uint32_t ntiles, uint32_t *tile_stats) {
+    const uint32_t t = blockIdx.x, lane = threadIdx.x & 63u;
+    if (t >= ntiles) return;
+    const uint32_t cnt = tile_stats[4ull * t];
+    const uint32_t n = cnt < slot_cap ? cnt : slot_cap;
+    const uint32_t *src = records + (u64)t * slot_cap;
+    uint32_t ncan = 0, nfwd = 0;
+    for (uint32_t i = lane; i < n; i += 64u) {
+        const uint32_t r = src[i];
+        nfwd += r & 1u; ncan += (r >> 1) & 1u;             // (general and wide records: forward is bit 0, canonical bit 1)
+    }
+    ncan = wave_total(ncan); nfwd = wave_total(nfwd);
+    if (lane == 0u) { tile_stats[4ull * t] = n; tile_stats[4ull * t + 1u] = ncan; tile_stats[4ull * t + 2u] = nfwd; }
+}
+
+// ts_terminal_pass: the two terminal walks of ts_terminal_blocks, one wave each, in their PASS form — pass[segment] = 1 where a
+// walk closes a terminal block (ReadTelomereFilter::matches is !terminalBlocks.empty()); pass is zero at launch.
+template <int MODE>
+__global__ __launch_bounds__(kSideWg)
+void ts_terminal_pass(const TsBlockCallParams Q, const TsShardSegIn *segs, uint32_t nseg, unsigned char *pass) {
+    const uint32_t si = blockIdx.x >> 1;
+    if (si >= nseg) return;
+    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x & 1u;
+    const TsShardSegIn S = segs[si];
+    const SegView V = seg_view(Q, S);
+    uint32_t seq = 0;
+    bool ooc = false;
+    if (wave == 0) {
+        if (view_has_two(Q, V, 1, false, lane)) terminal_direction<MODE, true>(Q, V, si, S.len, S.abs_pos, true, seq, lane, ooc, pass);
+    } else {
+        if (view_has_two(Q, V, 2, true, lane)) terminal_direction<MODE, true>(Q, V, si, S.len, S.abs_pos, false, seq, lane, ooc, pass);
     }
 }
 
@@ -1022,6 +1070,24 @@ int ts_k_launch_terminal(const TsBlockCallParams *Q, const TsShardSegIn *segs, u
         hipLaunchKernelGGL(ts_terminal_blocks<1>, dim3(2u * nseg), dim3(kSideWg), 0, (hipStream_t)stream, *Q, segs, nseg, bounds, seg_out);
     else
         hipLaunchKernelGGL(ts_terminal_blocks<0>, dim3(2u * nseg), dim3(kSideWg), 0, (hipStream_t)stream, *Q, segs, nseg, bounds, seg_out);
+    return (int)hipGetLastError();
+}
+
+// The read predicate of a general tips batch: Q.matches = the fused pass's slots (ntiles x slot_cap records), Q.tile_off[t] =
+// t * slot_cap, Q.tile_stats = the directory the pass left (completed here), segs = every segment with all its tiles; one byte
+// per segment to pass.  Everything on `stream`, nothing comes back to the host.
+int ts_k_launch_read_pass_general(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
+                                  uint32_t *tile_stats, unsigned char *pass, void *stream) {
+    if (nseg == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(pass, 0, nseg, st);
+    if (e != hipSuccess) return (int)e;
+    if (ntiles == 0) return 0;
+    hipLaunchKernelGGL(ts_slot_counts, dim3(ntiles), dim3(kSideWg), 0, st, Q->matches, slot_cap, ntiles, tile_stats);
+    if (Q->wide)
+        hipLaunchKernelGGL(ts_terminal_pass<1>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, pass);
+    else
+        hipLaunchKernelGGL(ts_terminal_pass<0>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, pass);
     return (int)hipGetLastError();
 }
 

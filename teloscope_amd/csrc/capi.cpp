@@ -857,6 +857,11 @@ ts_batch *ts_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t 
     if (!ctx) return nullptr;
     if (n_segs && !seg_lens) { ctx->fail(TS_ERR_INVALID_ARG, "ts_batch_create: null seg_lens"); return nullptr; }
     std::string why;
+    // tips-only scans of a set the tiled kernel does not take: a general tips batch (general_batch.cpp)
+    if (tips_only && !ctx->fast_ok && ctx->generic_ok) {
+        try { return ts_general_batch_create(ctx, seg_lens, abs_pos, n_segs); }
+        catch (const std::exception &e) { ctx->fail(TS_ERR_ALLOC, std::string("ts_batch_create: ") + e.what()); return nullptr; }
+    }
     if (tips_only ? !ctx->fast_ok : !ts_full_scan_supported(ctx, why)) {
         ctx->fail(TS_ERR_UNSUPPORTED, "unsupported parameter set: " + (tips_only ? ctx->why_not : why));
         return nullptr;
@@ -926,6 +931,7 @@ void ts_batch_destroy(ts_batch *b) {
     ts_ctx *c = b->ctx;
     if (c->device != kNoDevice) {
         DeviceGuard g(c->device);
+        if (b->gen) ts_general_batch_release(b);
         for (DevBuf *d : {&b->d_in, &b->d_tiles, &b->d_windows, &b->d_matches, &b->d_tile_off, &b->d_stats, &b->d_fill, &b->d_tickets,
                           &b->d_segtab, &b->d_dense, &b->d_dense_base, &b->d_scan_tmp, &b->d_readtab, &b->d_shard_segs,
                           &b->d_shard_bounds, &b->d_shard_tmp, &b->d_shard_cand, &b->d_vis, &b->d_chain, &b->d_zone})
@@ -943,6 +949,7 @@ uint64_t ts_batch_segment_offset(const ts_batch *b, size_t i) {
 }
 
 int ts_batch_get_tiles(const ts_batch *b, uint64_t first, uint64_t n, ts_tile_info *out) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_get_tiles");
     if (!b || (n && !out) || first > b->tiles.size() || n > b->tiles.size() - first) return TS_ERR_INVALID_ARG;
     for (uint64_t i = 0; i < n; ++i) {
         const TsTile &T = b->tiles[first + i];
@@ -956,12 +963,14 @@ int ts_batch_get_tiles(const ts_batch *b, uint64_t first, uint64_t n, ts_tile_in
 }
 
 int ts_batch_range_info(const ts_batch *b, uint64_t tile_begin, uint64_t tile_end, ts_range_info *out) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_range_info");
     if (!b || !out || tile_begin > tile_end || tile_end > b->tiles.size()) return TS_ERR_INVALID_ARG;
     range_cover(b, tile_begin, tile_end, *out);
     return TS_OK;
 }
 
 int ts_batch_partition(const ts_batch *b, uint32_t n_parts, uint32_t part, uint64_t *tile_begin, uint64_t *tile_end) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_partition");
     if (!b || !n_parts || part >= n_parts || !tile_begin || !tile_end) return TS_ERR_INVALID_ARG;
     // consecutive ranges of equal owned bases (tiles are near-equal work), the boundaries moved — by at most the
     // terminal zone + context of a segment — so that none falls near a segment's end (shard.cpp)
@@ -973,6 +982,7 @@ int ts_batch_partition(const ts_batch *b, uint32_t n_parts, uint32_t part, uint6
 }
 
 int ts_batch_restrict(ts_batch *b, uint64_t tile_begin, uint64_t tile_end) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_restrict");
     if (!b || tile_begin > tile_end || tile_end > b->tiles.size()) return TS_ERR_INVALID_ARG;
     if (b->allocated || b->scanned) return b->ctx->fail(TS_ERR_STATE, "ts_batch_restrict after the batch was used on the device");
     set_range(b, tile_begin, tile_end);
@@ -981,6 +991,7 @@ int ts_batch_restrict(ts_batch *b, uint64_t tile_begin, uint64_t tile_end) {
 
 int ts_batch_set_emit(ts_batch *b, int on) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_refuse(b, "ts_batch_set_emit");
     if (b->dense) return b->ctx->fail(TS_ERR_STATE, "ts_batch_set_emit on a batch that adopted results");
     if (b->tips) return TS_OK;                           // (a tips-only batch ignores it)
     b->kp.emit = on ? 1u : 0u;
@@ -989,6 +1000,7 @@ int ts_batch_set_emit(ts_batch *b, int on) {
 
 int ts_batch_bind_results(ts_batch *b, void *d_windows, void *d_tile_stats) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_refuse(b, "ts_batch_bind_results");
     if (b->allocated || b->scanned) return b->ctx->fail(TS_ERR_STATE, "ts_batch_bind_results after the batch was used on the device");
     b->ext_windows = (uint32_t *)d_windows;
     b->ext_stats = (uint32_t *)d_tile_stats;
@@ -1028,6 +1040,7 @@ int ts_batch_upload(ts_batch *b, size_t i, const char *seq) {
 
 int ts_batch_scan(ts_batch *b, const void *d_input, void *stream) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_scan(b, d_input, stream);
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
     if (b->dense) return c->fail(TS_ERR_STATE, "ts_batch_scan on a batch that adopted results");
@@ -1100,11 +1113,13 @@ int ts_batch_scan(ts_batch *b, const void *d_input, void *stream) {
 
 int ts_batch_set_timing(ts_batch *b, uint32_t every) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_refuse(b, "ts_batch_set_timing");
     b->time_every = every;
     return TS_OK;
 }
 
 int ts_batch_set_record_bits(ts_batch *b, int bits) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_set_record_bits");
     if (!b || (bits != 16 && bits != 32)) return TS_ERR_INVALID_ARG;
     ts_ctx *c = b->ctx;
     if (b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_set_record_bits: before the first scan");
@@ -1118,6 +1133,7 @@ int ts_batch_set_record_bits(ts_batch *b, int bits) {
 
 int ts_batch_wait_scan(ts_batch *b, void *stream) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_refuse(b, "ts_batch_wait_scan");
     ts_ctx *c = b->ctx;
     if (!b->scanned || b->dense || b->scan_seq == 0) return c->fail(TS_ERR_STATE, "ts_batch_wait_scan needs a scanned batch");
     if (stream == b->last_stream) return TS_OK;                 // (the same stream: in order already)
@@ -1129,6 +1145,7 @@ int ts_batch_wait_scan(ts_batch *b, void *stream) {
 
 int ts_batch_sync(ts_batch *b) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_sync(b);
     ts_ctx *c = b->ctx;
     if (b->dense && b->synced) return TS_OK;
     if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_sync before ts_batch_scan");
@@ -1196,8 +1213,8 @@ int ts_batch_get_info(const ts_batch *b, ts_batch_info *info) {
     info->total_bases = b->total_bases;
     info->input_bytes = b->input_bytes;
     info->n_windows = b->n_windows;
-    info->n_tiles = b->tiles.size();
-    info->match_capacity = b->match_cap;
+    info->n_tiles = b->gen ? b->gen->tiles.size() : b->tiles.size();
+    info->match_capacity = b->gen ? (uint64_t)b->gen->tiles.size() * b->gen->slot_cap : b->match_cap;
     info->n_matches = b->synced ? b->n_matches : 0;
     // of the range the batch executes (the whole plan unless restricted), by SURVEY 8(d): a window scan reads 1 B per base and
     // writes 32 B per window and 4 B per match; a tips-only / read batch reads 1 B per scanned base and what leaves it is one
@@ -1210,11 +1227,14 @@ int ts_batch_get_info(const ts_batch *b, ts_batch_info *info) {
     return TS_OK;
 }
 
-const void *ts_batch_windows_ptr(const ts_batch *b) { return b ? b->windows_ptr() : nullptr; }
-const void *ts_batch_matches_ptr(const ts_batch *b) { return b && !b->records16() ? b->records_ptr() : nullptr; }   // (16-bit regions: no raw view; a dense stream is 32-bit)
-const void *ts_batch_tile_stats_ptr(const ts_batch *b) { return b ? b->stats_ptr() : nullptr; }
+// (a general tips batch has none of the three: null, and the call named in ts_last_error)
+static bool general_no_view(const ts_batch *b, const char *call) { if (b && b->gen) (void)ts_general_batch_refuse(b, call); return b && b->gen; }
+const void *ts_batch_windows_ptr(const ts_batch *b) { return b && !general_no_view(b, "ts_batch_windows_ptr") ? b->windows_ptr() : nullptr; }
+const void *ts_batch_matches_ptr(const ts_batch *b) { return b && !general_no_view(b, "ts_batch_matches_ptr") && !b->records16() ? b->records_ptr() : nullptr; }   // (16-bit regions: no raw view; a dense stream is 32-bit)
+const void *ts_batch_tile_stats_ptr(const ts_batch *b) { return b && !general_no_view(b, "ts_batch_tile_stats_ptr") ? b->stats_ptr() : nullptr; }
 
 int ts_batch_export(ts_batch *b, void *d_dense, uint64_t dense_capacity, void *d_total, void *stream) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_export");
     if (!b || !d_dense || !d_total) return TS_ERR_INVALID_ARG;
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
@@ -1232,7 +1252,7 @@ int ts_batch_export(ts_batch *b, void *d_dense, uint64_t dense_capacity, void *d
 }
 
 int ts_batch_wire16_ok(const ts_batch *b) {
-    if (!b) return 0;
+    if (!b || b->gen) return 0;
     const ts_ctx *c = b->ctx;
     // records: (position << 2 | flags) with position < nch * TS_CHUNK + 64 <= 2^14; tile counts <= a tile's bases;
     // window fields: nucleotide counts <= w, covered bases = k x matches <= k x w
@@ -1250,6 +1270,7 @@ int ts_wire_widen_u16(ts_ctx *ctx, const void *d_src_u16, void *d_dst_u32, uint6
 }
 
 int ts_batch_adopt(ts_batch *b, void *d_windows, void *d_tile_stats, const void *d_dense, uint64_t n_matches, void *stream) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_adopt");
     if (!b || !d_tile_stats || (n_matches && !d_dense) || (!b->tips && b->n_windows && !d_windows)) return TS_ERR_INVALID_ARG;
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
@@ -1279,6 +1300,7 @@ int ts_batch_adopt(ts_batch *b, void *d_windows, void *d_tile_stats, const void 
 }
 
 int ts_batch_segment_summary(ts_batch *b, void *d_out, void *stream) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_segment_summary");
     if (!b || !d_out) return TS_ERR_INVALID_ARG;
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
@@ -1783,11 +1805,15 @@ extern "C" {
 // device, like ts_batch_download_blocks — so the only host work per record is its expansion to MatchInfo.
 int ts_batch_download(ts_batch *b, const char *const *host_seqs, ts_segment_out *out) {
     (void)host_seqs;
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_download");
     return download_impl(b, out, true);
 }
 
 // --------------------------------------------------------------- device block calling (row f1)
-int ts_batch_download_blocks(ts_batch *b, ts_segment_out *out) { return download_impl(b, out, false); }
+int ts_batch_download_blocks(ts_batch *b, ts_segment_out *out) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_download_blocks");
+    return download_impl(b, out, false);
+}
 
 void ts_free_segments(ts_segment_out *out, size_t n_segs) {
     if (!out) return;

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -173,6 +174,9 @@ struct ts_ctx {
     std::atomic<uint64_t> match_text_stats[4] = {};
     // ts_gzip_stats: windows, spans probed, spans chained, spans dropped, plain bytes produced, parts the caller handed to zlib — since ts_create
     std::atomic<uint64_t> gzip_stats[6] = {};
+    // ts_read_batch_stats: scans enqueued on general tips batches, segments their read pass judged, rescans after an overflow or
+    // spill, bytes those calls copied device to host — since ts_create
+    std::atomic<uint64_t> read_batch_stats[4] = {};
     hipEvent_t gen_ev[2] = {nullptr, nullptr};   // TS_TIMING: around the general path's kernels
     PinBuf pin_down[2];
     PinBuf pin_off;                              // general path: a group's tile directory lands here (a pageable landing cost 9 ms per MB-sized copy)
@@ -219,12 +223,30 @@ struct ShardLayout {
     uint64_t n_windows;
 };
 
+// What a GENERAL TIPS BATCH holds beside the segments and the input layout of a ts_batch (general_batch.cpp): a tips-only batch
+// of a context whose tips scans go to the general kernels.  Its tiles are TsGeneralTile over the regions scanSegment picks,
+// the records stay in the fused pass's per-tile slots, and the read predicate walks them there.
+struct TsGeneralBatch {
+    std::vector<TsGeneralTile> tiles;
+    TsGenericGeom Q{};
+    unsigned long long gen_lens = 0;
+    bool wide = false, use_list = false;
+    uint32_t slot_unit = 0;             // positions of the largest tile, a multiple of 4: what a slot is a multiple of
+    uint32_t slot_cap = 0, slot_max = 0;
+    // tile list, {segment lengths, zeros, zeros, flag word}, slots, tile directory, slot offsets, the predicate's TsTile list and
+    // segment table: all but the slots uploaded or sized once per batch
+    DevBuf d_tiles, d_tab, d_slots, d_stats, d_off, d_bct, d_segin;
+    bool uploaded = false;
+    size_t tab_flag = 0;                // byte offset of the fused pass's flag word in d_tab
+};
+
 // A batch is a PLAN over all its segments (tiles, window records, input layout) plus the device state of
 // the tile range [tile_lo, tile_hi) it executes: the whole plan by default, one rank's shard after
 // ts_batch_restrict, or — on the rank that assembles — results produced elsewhere (ts_batch_adopt).
 struct ts_batch {
     ts_ctx *ctx = nullptr;
     bool tips = false;
+    std::unique_ptr<TsGeneralBatch> gen;    // non-null: a general tips batch — `tiles` stays empty, only the calls general_batch.cpp serves work
     std::vector<SegPlan> segs;
     std::vector<TsTile> tiles;      // the whole plan
     TsScanParams kp{};
@@ -373,6 +395,43 @@ struct HostView {
 };
 // SegmentData from the general kernels' records (pipeline.cpp's general path) to out[0, v.segs.size()); frees it on failure
 int  ts_assemble_general(ts_ctx *c, const HostView &v, ts_segment_out *out);
+
+// ---- the general kernels' per-context launch geometry: the host entry points' general path (pipeline.cpp) and general tips
+// batches (general_batch.cpp) launch the same passes
+inline TsGenericGeom ts_general_geom(const ts_ctx *c) {
+    const ts_params &P = c->params;
+    const uint32_t s = P.step, w = P.window_size;
+    TsGenericGeom Q{};
+    Q.s = s; Q.w = w; Q.longest = c->longest; Q.nuc_on = (P.out_gc || P.out_entropy) ? 1u : 0u; Q.fold = P.fold_case;
+    Q.s_magic = s >= 2u ? (uint32_t)((1ull << 32) / s + 1ull) : 0u;
+    Q.cw = w / s; Q.rw = w - Q.cw * s;
+    return Q;
+}
+// the pattern lengths as block calling reads them (TsBlockCallParams.gen_lens); the wide form: non-zero = "general format"
+inline unsigned long long ts_general_gen_lens(const ts_ctx *c) {
+    if (c->gen_wide) return 1ull;
+    unsigned long long v = 0;
+    for (uint32_t li = 0; li < c->gpat.nlen && li < 8u; ++li) v |= (unsigned long long)(c->gpat.len[li] & 63u) << (6u * li);
+    if (c->gpat.nlen && c->gpat.len[c->gpat.nlen - 1] > 63u) v = 0;
+    return v;
+}
+// may a scan start in the list form of the fused pass?  (every tips-only scan that passes this does; a spilled candidate list
+// sends it to the strided form)
+inline bool ts_general_list_form_ok(const ts_ctx *c) {
+    return !c->gen_wide && c->knobs.gen_list && c->params.step >= 2u && c->params.window_size < (1u << 28);
+}
+// a tile's slot, in units of the positions it holds: what a scan starts with, and what cannot overflow
+inline uint32_t ts_general_slot_start(const ts_ctx *c, uint32_t unit) { return c->gen_wide ? unit * std::min<uint32_t>(4u, std::max<uint32_t>(1u, c->wpat.nlen)) : unit; }
+inline uint32_t ts_general_slot_max(const ts_ctx *c, uint32_t unit) { return unit * std::max<uint32_t>(1u, c->gen_wide ? c->wpat.nlen : c->gpat.nlen); }
+
+// general_batch.cpp: what the ts_batch_* entry points hand a general tips batch (b->gen != nullptr) to
+ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t *abs_pos, size_t n_segs);
+void ts_general_batch_release(ts_batch *b);      // its device blocks back to the pool (ts_batch_destroy)
+int  ts_general_batch_scan(ts_batch *b, const void *d_input, void *stream);
+int  ts_general_batch_read_pass(ts_batch *b, void *d_pass, void *stream);
+int  ts_general_batch_status(ts_batch *b, int *overflowed);
+int  ts_general_batch_sync(ts_batch *b);
+int  ts_general_batch_refuse(const ts_batch *b, const char *call);     // TS_ERR_UNSUPPORTED, the call named in ts_last_error
 
 int  ts_batch_ensure_device(ts_batch *b);        // allocates the range's device state (idempotent)
 // block calling on the device over a resident match stream + tile directory (a batch's, or the general kernels' dense stream)

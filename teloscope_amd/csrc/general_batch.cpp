@@ -1,0 +1,269 @@
+// general_batch.cpp — general tips batches: the device-resident read batch of pattern sets the tiled kernel does not take
+// (mixed lengths, patterns of 9 bases or more, the wide form's up to 63 lengths of up to 63 bases).
+//
+// ts_batch_create(ctx, ..., tips_only = 1, ...) returns one on a context whose tips scans go to the general kernels.  It has the
+// input layout of a tiled batch — whole segments back to back, each 16-byte aligned, TS_IN_PAD zero bytes behind the last — so
+// that ts_batch_upload, ts_fastq_chunk_stage, ts_bam_chunk_decode and a caller's own d_input fill it as they fill any batch.
+// Its tiles are TsGeneralTile over the regions scanSegment picks (the whole segment up to 2 x terminal limit, else the two tips);
+// ts_batch_scan enqueues the fused tips pass of generic.hip and the slot offsets, ts_batch_read_pass the predicate over the
+// records where that pass left them (blockcall.hip: ts_terminal_pass).  Only the fused pass's flag word ever comes back to the
+// host: ts_batch_read_pass_status reads it, ts_batch_sync regrows the slots (or leaves the list form) and rescans.
+#include "capi_internal.hpp"
+
+namespace {
+
+const char kWayOut[] = "; the host routes (fastqSubset / bamSubset, ts_filter_reads) scan such a set in groups of bounded size";
+
+// a block of the context's pool, or the batch's own error: an allocation that fails names the way out
+int take(ts_ctx *c, size_t bytes, DevBuf &d, const char *what, const TsGeneralBatch &g) {
+    if (c->pool.take(bytes, d) == hipSuccess) return TS_OK;
+    (void)hipGetLastError();
+    return c->fail(TS_ERR_ALLOC, "general read batch: cannot allocate " + std::to_string(bytes) + " bytes of device memory for " + what +
+                                 " (" + std::to_string(g.tiles.size()) + " tiles, a slot of " + std::to_string(g.slot_cap) + " records each)" + kWayOut);
+}
+
+size_t slot_bytes(const TsGeneralBatch &g) { return std::max<size_t>(g.tiles.size(), 1) * (size_t)g.slot_cap * 4; }
+
+// Device state, once per batch: the tile list, the per-segment table of the fused pass {lengths, window bases, window counts:
+// the last two zero for tips} with the flag word behind it, the predicate's tile list and segment table; and the buffers every
+// scan writes.
+int ensure_device(ts_batch *b) {
+    ts_ctx *c = b->ctx;
+    TsGeneralBatch &g = *b->gen;
+    if (g.uploaded) return TS_OK;
+    const size_t ns = b->segs.size(), nt = g.tiles.size();
+    g.tab_flag = 3 * ns * 8;
+    int rc;
+    if ((rc = take(c, std::max<size_t>(nt, 1) * sizeof(TsGeneralTile), g.d_tiles, "the tile list", g)) != TS_OK) return rc;
+    if ((rc = take(c, g.tab_flag + 16, g.d_tab, "the segment table", g)) != TS_OK) return rc;
+    if ((rc = take(c, (nt + 1) * 16, g.d_stats, "the tile directory", g)) != TS_OK) return rc;
+    if ((rc = take(c, (nt + 1) * 8, g.d_off, "the slot offsets", g)) != TS_OK) return rc;
+    if ((rc = take(c, std::max<size_t>(nt, 1) * sizeof(TsTile), g.d_bct, "the predicate's tile list", g)) != TS_OK) return rc;
+    if ((rc = take(c, std::max<size_t>(ns, 1) * sizeof(TsShardSegIn), g.d_segin, "the predicate's segment table", g)) != TS_OK) return rc;
+    if ((rc = take(c, slot_bytes(g), g.d_slots, "the record slots", g)) != TS_OK) return rc;
+    std::vector<unsigned long long> tab(3 * ns + 2, 0ull);
+    std::vector<TsShardSegIn> segin(ns);
+    for (size_t i = 0; i < ns; ++i) {
+        const SegPlan &sp = b->segs[i];
+        tab[i] = sp.len;
+        TsShardSegIn &S = segin[i];
+        S = TsShardSegIn{};
+        S.in_off = sp.in_off; S.len = sp.len; S.abs_pos = sp.abs_pos;
+        S.t0 = S.o0 = sp.first_tile; S.t1 = S.o1 = sp.first_tile + sp.n_tiles;
+        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
+        S.lo_rel = 0; S.hi_rel = sp.len; S.seg = (uint32_t)i;
+    }
+    // (the walks take a tile's segment-relative position from in_off - the segment's: the layout's own offsets serve)
+    std::vector<TsTile> bct(nt);
+    for (size_t t = 0; t < nt; ++t) {
+        TsTile &T = bct[t];
+        T = TsTile{};
+        T.in_off = g.tiles[t].in_off; T.own_len = T.nrel = g.tiles[t].n; T.seg = g.tiles[t].seg;
+    }
+    if (nt) HIP_TRY(c, hipMemcpy(g.d_tiles.p, g.tiles.data(), nt * sizeof(TsGeneralTile), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(g.d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    if (nt) HIP_TRY(c, hipMemcpy(g.d_bct.p, bct.data(), nt * sizeof(TsTile), hipMemcpyHostToDevice));
+    if (ns) HIP_TRY(c, hipMemcpy(g.d_segin.p, segin.data(), ns * sizeof(TsShardSegIn), hipMemcpyHostToDevice));
+    g.uploaded = true;
+    return TS_OK;
+}
+
+// the fused pass's flag word (bit 0: a tile overflowed its slot, bit 1: a candidate list spilled), once the batch's stream is done
+int read_flag(ts_batch *b, uint32_t &flag) {
+    ts_ctx *c = b->ctx;
+    hipStream_t st = (hipStream_t)b->last_stream;
+    flag = 0;
+    HIP_TRY(c, hipMemcpyAsync(&flag, (char *)b->gen->d_tab.p + b->gen->tab_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->read_batch_stats[3].fetch_add(4, std::memory_order_relaxed);
+    return TS_OK;
+}
+
+}  // namespace
+
+ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t *abs_pos, size_t n_segs) {
+    std::unique_ptr<ts_batch> b(new ts_batch());
+    b->ctx = ctx;
+    b->tips = true;
+    b->gen.reset(new TsGeneralBatch());
+    TsGeneralBatch &g = *b->gen;
+    g.wide = ctx->gen_wide;
+    g.Q = ts_general_geom(ctx);
+    g.gen_lens = ts_general_gen_lens(ctx);
+    const uint32_t s = std::max<uint32_t>(ctx->params.step, 1u), tl = ctx->params.terminal_limit;
+    const uint32_t halo = g.wide ? (uint32_t)TS_WIDE_HALO : 32u;
+    uint64_t off = 0, scanned = 0;
+    uint32_t largest = 0;
+    bool aligned = true;
+    b->segs.resize(n_segs);
+    for (size_t i = 0; i < n_segs; ++i) {
+        SegPlan &sp = b->segs[i];
+        sp.len = seg_lens[i];
+        sp.abs_pos = abs_pos ? abs_pos[i] : 0;
+        sp.in_off = off;
+        off += (sp.len + 15) & ~15ull;
+        sp.first_tile = (uint32_t)g.tiles.size();
+        auto add_region = [&](uint64_t start, uint64_t len) {
+            Region rg{start, len, (uint32_t)g.tiles.size(), 0, TS_GENERAL_TILE};
+            uint64_t kq = start / s, kr = start - kq * s;                    // P0 = kq s + kr, walked from tile to tile
+            for (uint64_t a = 0; a < len; a += TS_GENERAL_TILE) {
+                TsGeneralTile T{};
+                T.in_off = sp.in_off + start + a;
+                T.seg_rel = start + a;
+                T.k_p0 = kq; T.r_p0 = (uint32_t)kr;
+                T.n = (uint32_t)std::min<uint64_t>(TS_GENERAL_TILE, len - a);
+                T.avail = (uint32_t)std::min<uint64_t>(len - a, (uint64_t)T.n + halo);
+                T.seg = (uint32_t)i;
+                g.tiles.push_back(T);
+                largest = std::max(largest, T.n);
+                aligned = aligned && (T.in_off & 15ull) == 0;
+                kr += TS_GENERAL_TILE;
+                if (kr >= s) { const uint64_t d = kr / s; kq += d; kr -= d * s; }
+            }
+            rg.n_tiles = (uint32_t)g.tiles.size() - rg.first_tile;
+            sp.regions.push_back(rg);
+            scanned += len;
+        };
+        // regions exactly as scanSegment picks them (src/teloscope.cpp:576-583; uint32 product)
+        const uint32_t twice = 2u * tl;
+        if (sp.len > twice) { add_region(0, tl); add_region(sp.len - tl, tl); }
+        else if (sp.len) add_region(0, sp.len);
+        sp.n_tiles = (uint32_t)g.tiles.size() - sp.first_tile;
+        b->total_bases += sp.len;
+        if (g.tiles.size() >= 0x7FFFFFFFull) {
+            ctx->fail(TS_ERR_UNSUPPORTED, "too many tiles in one batch");
+            return nullptr;
+        }
+    }
+    b->input_bytes = off + TS_IN_PAD;
+    b->in_lo = 0; b->in_hi = b->input_bytes;
+    b->range_bases = scanned;
+    // a slot per tile, sized by the largest tile of THIS batch (reads of 150 bases need no slot of 4096 records): one record per
+    // position to begin with (the wide form: four), a record per position and length when that overflowed
+    g.slot_unit = std::max<uint32_t>(4u, (largest + 3u) & ~3u);
+    g.slot_cap = ts_general_slot_start(ctx, g.slot_unit);
+    g.slot_max = ts_general_slot_max(ctx, g.slot_unit);
+    // the list form loads a tile's bases 16 aligned bytes at a time: a second tip that starts off a 16-byte boundary (a segment
+    // longer than 2 x terminal limit; never a read of a read filter) sends the batch to the strided form
+    g.use_list = ts_general_list_form_ok(ctx) && aligned;
+    return b.release();
+}
+
+void ts_general_batch_release(ts_batch *b) {
+    TsGeneralBatch &g = *b->gen;
+    for (DevBuf *d : {&g.d_tiles, &g.d_tab, &g.d_slots, &g.d_stats, &g.d_off, &g.d_bct, &g.d_segin}) b->ctx->pool.give(std::move(*d));
+    g.uploaded = false;
+}
+
+int ts_general_batch_refuse(const ts_batch *b, const char *call) {
+    return b->ctx->fail(TS_ERR_UNSUPPORTED, std::string(call) + ": not served by a general tips batch (the tips-only batch of a pattern set "
+                                            "the general kernels scan); it takes ts_batch_segment_offset, _input_ptr, _upload, _scan, "
+                                            "_read_pass, _read_pass_status, _sync, _get_info and _destroy");
+}
+
+// The fused tips pass (list or strided form, or the wide form) and the slot offsets, on `stream`; no host synchronisation beyond
+// the first call's uploads.  Tips scans are in position order: the records stay in their slots.
+int ts_general_batch_scan(ts_batch *b, const void *d_input, void *stream) {
+    ts_ctx *c = b->ctx;
+    DEVICE_TRY(c);
+    TsGeneralBatch &g = *b->gen;
+    if (!d_input) d_input = ts_batch_input_ptr(b);
+    if (!d_input) return c->fail(TS_ERR_ALLOC, std::string("general read batch: cannot allocate the device input buffer") + kWayOut);
+    { const int rc = ensure_device(b); if (rc != TS_OK) return rc; }
+    if (!g.d_slots.p) { const int rc = take(c, slot_bytes(g), g.d_slots, "the record slots", g); if (rc != TS_OK) return rc; }   // (a regrow that failed)
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ns = b->segs.size(), nt = g.tiles.size();
+    b->last_input = d_input;
+    b->last_stream = stream;
+    b->scanned = true;
+    b->synced = false;
+    char *const dt = (char *)g.d_tab.p;
+    const unsigned long long *const tab_len = (const unsigned long long *)dt, *const tab_win = tab_len + ns, *const tab_nwin = tab_len + 2 * ns;
+    uint32_t *const d_flag = (uint32_t *)(dt + g.tab_flag);
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        HIP_TRY(c, hipMemsetAsync(d_flag, 0, 16, st));
+        if (g.wide) {
+            if (ts_k_launch_general_wide((const unsigned char *)d_input, (const TsGeneralTile *)g.d_tiles.p, (uint32_t)nt, tab_len, tab_win, tab_nwin,
+                                         &c->wpat, &g.Q, 1, g.slot_cap, (uint32_t *)g.d_stats.p, (uint32_t *)g.d_slots.p, nullptr, d_flag, st) != 0)
+                return c->fail(TS_ERR_HIP, "general wide kernel launch failed");
+        } else if (ts_k_launch_general_fused((const unsigned char *)d_input, (const TsGeneralTile *)g.d_tiles.p, (uint32_t)nt, tab_len, tab_win, tab_nwin,
+                                             &c->gpat, &g.Q, 1, g.slot_cap, (uint32_t *)g.d_stats.p, (uint32_t *)g.d_slots.p, nullptr, d_flag,
+                                             g.use_list ? 1 : 0, c->num_cu, st) != 0)
+            return c->fail(TS_ERR_HIP, "general fused kernel launch failed");
+        if (ts_k_launch_general_slot_offsets((unsigned long long *)g.d_off.p, (uint32_t)nt, g.slot_cap, st) != 0)
+            return c->fail(TS_ERR_HIP, "slot-offset kernel launch failed");
+    }
+    c->read_batch_stats[0].fetch_add(1, std::memory_order_relaxed);
+    return TS_OK;
+}
+
+// ReadTelomereFilter::matches (src/read-filter.cpp:37-45, reduced to !terminalBlocks.empty()) per segment: the terminal walks of
+// device block calling in their pass form, over the slots.  One byte per segment to d_pass, on the scan's stream.
+int ts_general_batch_read_pass(ts_batch *b, void *d_pass, void *stream) {
+    ts_ctx *c = b->ctx;
+    DEVICE_TRY(c);
+    TsGeneralBatch &g = *b->gen;
+    if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_read_pass needs a scanned, unrestricted tips-only batch");
+    if (stream != b->last_stream) return c->fail(TS_ERR_STATE, "ts_batch_read_pass on a general tips batch: pass the stream of its scan");
+    const ts_params &P = c->params;
+    TsBlockCallParams Q{};
+    Q.tiles = (const TsTile *)g.d_bct.p;
+    Q.tile_off = (const unsigned long long *)g.d_off.p;
+    Q.tile_stats = (const uint32_t *)g.d_stats.p;
+    Q.matches = (const uint32_t *)g.d_slots.p;
+    Q.terminal_limit = P.terminal_limit; Q.max_match_dist = P.max_match_dist;
+    Q.min_block_len = P.min_block_len; Q.max_block_dist = P.max_block_dist;
+    Q.min_block_counts = P.min_block_counts; Q.min_block_density = P.min_block_density;
+    Q.k = c->k;
+    Q.gen_lens = g.gen_lens;
+    Q.wide = g.wide ? 1u : 0u; Q.wide_len = g.wide ? c->wpat.len : nullptr;
+    if (ts_k_launch_read_pass_general(&Q, (const TsShardSegIn *)g.d_segin.p, (uint32_t)b->segs.size(), (uint32_t)g.tiles.size(), g.slot_cap,
+                                      (uint32_t *)g.d_stats.p, (unsigned char *)d_pass, stream) != 0)
+        return c->fail(TS_ERR_HIP, "general read-pass kernel launch failed");
+    c->read_batch_stats[1].fetch_add(b->segs.size(), std::memory_order_relaxed);
+    return TS_OK;
+}
+
+int ts_general_batch_status(ts_batch *b, int *overflowed) {
+    ts_ctx *c = b->ctx;
+    DEVICE_TRY(c);
+    *overflowed = 0;
+    if (!b->scanned) return TS_OK;                                // nothing was ever enqueued
+    uint32_t flag = 0;
+    { const int rc = read_flag(b, flag); if (rc != TS_OK) return rc; }
+    *overflowed = flag ? 1 : 0;
+    return TS_OK;
+}
+
+// Waits for the scan; after an overflow or a spill grows the slots as the host path's fused stage does (a record per position
+// and length, the wide form by fours) or leaves the list form, and rescans until the flag word stays clear.
+int ts_general_batch_sync(ts_batch *b) {
+    ts_ctx *c = b->ctx;
+    if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_sync before ts_batch_scan");
+    DEVICE_TRY(c);
+    TsGeneralBatch &g = *b->gen;
+    for (int attempt = 0;; ++attempt) {
+        uint32_t flag = 0;
+        { const int rc = read_flag(b, flag); if (rc != TS_OK) return rc; }
+        if (!flag) { b->synced = true; return TS_OK; }
+        if (attempt > (g.wide ? 4 : 1) || (g.slot_cap >= g.slot_max && !(flag & 2u)))
+            return c->fail(TS_ERR_STATE, "general read batch: a tile overflowed a slot that holds every match it can have");
+        if (flag & 2u) g.use_list = false;                        // a candidate list spilled: the strided form takes the batch
+        else {
+            g.slot_cap = g.wide ? std::min<uint32_t>(g.slot_max, g.slot_cap * 4u) : g.slot_max;
+            c->pool.give(std::move(g.d_slots));
+            const int rc = take(c, slot_bytes(g), g.d_slots, "the regrown record slots", g);
+            if (rc != TS_OK) return rc;
+        }
+        c->read_batch_stats[2].fetch_add(1, std::memory_order_relaxed);
+        const int rc = ts_general_batch_scan(b, b->last_input, b->last_stream);
+        if (rc != TS_OK) return rc;
+    }
+}
+
+extern "C" int ts_read_batch_stats(const ts_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return TS_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->read_batch_stats[i].load(std::memory_order_relaxed);
+    return TS_OK;
+}

@@ -1141,9 +1141,7 @@ struct GenCall {
         : c(c_), P(c_->params), mode(m), tips(t), blocks_only(m != Mode::Matches), wide(c_->gen_wide), items(it), o(out),
           timing(c_->knobs.timing) {
         const uint32_t s = P.step, w = P.window_size;
-        Q.s = s; Q.w = w; Q.longest = c->longest; Q.nuc_on = (P.out_gc || P.out_entropy) ? 1u : 0u; Q.fold = P.fold_case;
-        Q.s_magic = s >= 2u ? (uint32_t)((1ull << 32) / s + 1ull) : 0u;
-        Q.cw = w / s; Q.rw = w - Q.cw * s;
+        Q = ts_general_geom(c);
         // the wide form (sets beyond 8 lengths / 32 bases): its own kernel, a 64-base halo, records with six bits of length index;
         // smaller groups, because a tile's slot may have to grow to a record per position AND length
         target = wide ? std::min<uint64_t>(group_target_bytes(), 256ull << 20) : group_target_bytes();   // (16 - 64 KB of slot per tile: 4 - 17 GB per group)
@@ -1159,10 +1157,8 @@ struct GenCall {
                           : (c->gpat.nlen ? c->gpat.len[c->gpat.nlen - 1] - c->gpat.len[0] : 0u);
         position_order = tips || w == s || len_spread <= 1u;                   // position order IS push order
         push_compact = !position_order;                                         // the device orders the stream
-        for (uint32_t li = 0; li < c->gpat.nlen && li < 8u; ++li) gen_lens |= (unsigned long long)(c->gpat.len[li] & 63u) << (6u * li);
-        if (c->gpat.nlen && c->gpat.len[c->gpat.nlen - 1] > 63u) gen_lens = 0;
-        if (wide) gen_lens = 1ull;                                              // (wide records: the lengths come from wpat.len; non-zero = "general format")
-        slot_cap_call = wide ? TS_GENERAL_TILE * std::min<uint32_t>(4u, std::max<uint32_t>(1u, c->wpat.nlen)) : TS_GENERAL_TILE;
+        gen_lens = ts_general_gen_lens(c);                                      // (wide records: the lengths come from wpat.len; non-zero = "general format")
+        slot_cap_call = ts_general_slot_start(c, TS_GENERAL_TILE);
     }
     ~GenCall() { if (host_job.joinable()) host_job.join(); }
 };
@@ -1252,8 +1248,7 @@ int gen_fused(GenCall &g, GenGroup &gr) {
     // the list form of the fused pass (per-candidate work on full wavefronts) when a tile adds to few enough window
     // records for the accumulators it keeps in LDS; a tile dense enough to overflow a wave's candidate list sends the
     // group through the position-strided form instead
-    bool use_list = !g.wide && c->knobs.gen_list && s >= 2u && w < (1u << 28) &&
-                    (g.tips || ((uint64_t)TS_GENERAL_TILE + w) / s + 3 <= ts_k_general_list_max_records());
+    bool use_list = ts_general_list_form_ok(c) && (g.tips || ((uint64_t)TS_GENERAL_TILE + w) / s + 3 <= ts_k_general_list_max_records());
     HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)gr.slot_cap * 4, gr.d_slots));
     HIP_TRY(c, c->pool.take((nt + 1) * 16, gr.d_stats));
     HIP_TRY(c, c->pool.take((nt + 1) * 8, gr.d_off));
@@ -1304,7 +1299,7 @@ int gen_fused(GenCall &g, GenGroup &gr) {
         if (g.timing) { g.t_dbg[0] += ms_between(t1, te0); g.t_dbg[1] += ms_between(te0, te1); g.t_dbg[2] += ms_between(te1, Clock::now()); }
         if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
         if (!flag) break;
-        const uint32_t slot_max = TS_GENERAL_TILE * std::max<uint32_t>(1u, g.wide ? c->wpat.nlen : c->gpat.nlen);
+        const uint32_t slot_max = ts_general_slot_max(c, TS_GENERAL_TILE);
         if (attempt > (g.wide ? 4 : 1) || (gr.slot_cap >= slot_max && !(flag & 2u)))
             return c->fail(TS_ERR_STATE, "general path: a tile overflowed a slot that holds every match it can have");
         if (flag & 2u) { use_list = false; continue; }            // a candidate list spilled: the strided form takes this group
@@ -1713,6 +1708,7 @@ int ts_terminal_ends(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, uint
 // the pass byte of every read to d_pass, asynchronously on the same stream.
 int ts_batch_read_pass(ts_batch *b, void *d_pass, void *stream) {
     if (!b || !d_pass) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_read_pass(b, d_pass, stream);
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
     if (!b->tips || !b->whole() || !b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_read_pass needs a scanned, unrestricted tips-only batch");
@@ -1721,6 +1717,7 @@ int ts_batch_read_pass(ts_batch *b, void *d_pass, void *stream) {
 
 int ts_batch_read_pass_status(ts_batch *b, int *overflowed) {
     if (!b || !overflowed) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_status(b, overflowed);
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
     *overflowed = 0;

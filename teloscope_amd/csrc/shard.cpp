@@ -214,12 +214,14 @@ void ts_shard_boundaries(const ts_batch *b, uint32_t n_parts, std::vector<uint64
 extern "C" {
 
 int ts_batch_shard_info(const ts_batch *b, uint32_t n_parts, uint32_t part, uint32_t scale, ts_shard_info *out) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_shard_info");
     if (!b || !out || !n_parts || part >= n_parts) return TS_ERR_INVALID_ARG;
     fill_shard_info(b, n_parts, part, scale, *out);
     return TS_OK;
 }
 
 int ts_batch_restrict_shard(ts_batch *b, uint32_t n_parts, uint32_t part, uint32_t scale) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_restrict_shard");
     if (!b || !n_parts || part >= n_parts) return TS_ERR_INVALID_ARG;
     if (b->allocated || b->scanned) return b->ctx->fail(TS_ERR_STATE, "ts_batch_restrict_shard after the batch was used on the device");
     const ShardRange r = shard_range(b, n_parts, part);
@@ -234,6 +236,7 @@ int ts_batch_restrict_shard(ts_batch *b, uint32_t n_parts, uint32_t part, uint32
 }
 
 int ts_batch_set_shard_scale(ts_batch *b, uint32_t scale) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_set_shard_scale");
     if (!b || !b->shard_parts || !scale) return TS_ERR_INVALID_ARG;
     b->shard_scale = scale;
     b->shard_L = shard_layout(b, b->shard_r, scale);
@@ -243,6 +246,7 @@ int ts_batch_set_shard_scale(ts_batch *b, uint32_t scale) {
 
 int ts_batch_bind_shard_message(ts_batch *b, void *d_msg, uint64_t msg_bytes) {
     if (!b) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_refuse(b, "ts_batch_bind_shard_message");
     ts_ctx *c = b->ctx;
     if (!b->shard_parts) return c->fail(TS_ERR_STATE, "ts_batch_bind_shard_message needs ts_batch_restrict_shard first");
     if (d_msg && msg_bytes < b->shard_L.bytes) return c->fail(TS_ERR_INVALID_ARG, "ts_batch_bind_shard_message: message buffer smaller than ts_batch_shard_info says");
@@ -251,6 +255,7 @@ int ts_batch_bind_shard_message(ts_batch *b, void *d_msg, uint64_t msg_bytes) {
 }
 
 int ts_batch_pack_shard(ts_batch *b, void *d_msg, uint64_t msg_bytes, void *stream) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_pack_shard");
     if (!b || !d_msg) return TS_ERR_INVALID_ARG;
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
@@ -447,6 +452,7 @@ inline uint32_t visible_rec(const PartView &pv, uint64_t i) {
 
 extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, const uint64_t *msg_bytes, uint32_t n_parts,
                                   ts_segment_out *out, ts_segment_counts *counts) {
+    if (b && b->gen) return ts_general_batch_refuse(b, "ts_shards_finalize");
     if (!b || !msgs || !msg_bytes || !n_parts || !out) return TS_ERR_INVALID_ARG;
     ts_ctx *c = b->ctx;
     const ts_params &P = c->params;

@@ -364,6 +364,11 @@ int  ts_k_launch_block_call(const TsBlockCallParams *Q, const TsShardSegIn *segs
 // the terminal walks alone (they answer scanSegment's ">= 2 matches" gates from the tile directory themselves)
 int  ts_k_launch_terminal(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t seg_base, uint32_t ntiles,
                           unsigned long long *bounds, TsShardSeg *seg_out, void *stream);
+// the read predicate over the general kernels' records where the fused pass left them (a general tips batch): Q->matches = the
+// slots (ntiles x slot_cap records), Q->tile_off[t] = t * slot_cap, tile_stats = the pass's directory (counts cut to the slot,
+// canonical / forward counts added); pass[i] = 1 where segment i has a terminal block, else 0
+int  ts_k_launch_read_pass_general(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
+                                   uint32_t *tile_stats, unsigned char *pass, void *stream);
 // per-segment totals into sums (5 x u64 per segment) or into the segments' entries of a shard's message (seg_out)
 int  ts_k_launch_segment_sums(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t seg_base, uint32_t ntiles,
                               unsigned long long *sums, TsShardSeg *seg_out, int prezeroed, void *stream);
