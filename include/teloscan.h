@@ -267,6 +267,14 @@ int     ts_upload_stats(const ts_ctx *ctx, uint64_t out[8]);
  * no record and no block is ever downloaded.  Cumulative, monotonic and atomic, like ts_device_input_stats: take the difference
  * around a call. */
 int     ts_read_batch_stats(const ts_ctx *ctx, uint64_t out[4]);
+/* Measurement aid (no counterpart in the reference): which way the per-side maxima of ts_terminal_ends and
+ * ts_batch_terminal_ends were reduced since ts_create — out[0] segments reduced on the device by the tiled kernel's ENDS walk,
+ * out[1] segments reduced on the device by the general kernels' ENDS walk (both calls count here), out[2] segments reduced on
+ * the host from downloaded blocks (a tiled group whose scan overflowed a record region; a general group the walk does not take),
+ * out[3] bytes of per-side maxima and flag words these calls copied device to host (what the blocks route downloads besides
+ * is not in it: out[2] says how many segments took that route).  Cumulative, monotonic and atomic, like ts_device_input_stats:
+ * take the difference around a call. */
+int     ts_terminal_ends_stats(const ts_ctx *ctx, uint64_t out[4]);
 /* The host entry points read a handful of measurement / test knobs from the environment (TS_TIMING, TS_PACKED_UPLOAD,
  * TS_PACKED_MIN_BYTES, TS_GEN_LIST, TS_REC32, TS_MATCH_SLICE_BYTES) ONCE, when the context is made — never per call.  This reads them again (tests and A/B scripts that flip one between two calls on one context).
  * No counterpart in the reference (its options are fixed by main, /root/reference/src/main.cpp:149-184). */
@@ -433,7 +441,9 @@ int  ts_match_text_stats(const ts_ctx *ctx, uint64_t out[4]);
 /* ---- GFA annotation (src/input.cpp:625-716).  For every segment (tips_only must be 1), ends[2*i] / ends[2*i+1]: the
  *      longest terminal block (blockLen) at the start / end side of segs[i], 0 if none (walkSegment's distToStart <= distToEnd
  *      rule, src/input.cpp:835-881; positions relative to abs_pos).  Host in, host out, any context; the same numbers as
- *      ts_scan_segments_blocks' terminal blocks reduced per side, but only 8 bytes per segment leave the device. */
+ *      ts_scan_segments_blocks' terminal blocks reduced per side, but only 8 bytes per segment leave the device — under
+ *      every pattern set: the tiled kernel's records are reduced by the read predicate's walks, the general kernels' by the
+ *      terminal walks of device block calling (ts_terminal_ends_stats says which way a call went). */
 int ts_terminal_ends(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, uint32_t *ends);
 
 /* ---- device-resident batches: the same scan with inputs and outputs kept in HBM.
@@ -464,10 +474,15 @@ typedef struct ts_batch_info {
  * own d_input fill it unchanged; ts_batch_scan enqueues the general kernels' fused tips pass, ts_batch_read_pass the read
  * predicate over its records (same stream), ts_batch_read_pass_status says whether a tile overflowed its record slot or a
  * candidate list spilled, and ts_batch_sync then regrows the slots (or changes the pass's form) and rescans — the protocol of a
- * tiled read batch.  ts_batch_get_info fills the segments, bases, input bytes, tiles and slot capacity (the rest is 0), and
- * ts_batch_destroy frees it.  match_capacity is ignored.  EVERY OTHER ts_batch_* call (restrict, partition, the shard calls,
- * bind, export, adopt, the downloads, the summary, get_tiles / range_info, set_emit, set_record_bits, set_timing, wait_scan) and
- * ts_shards_finalize answers TS_ERR_UNSUPPORTED with the call named in ts_last_error; the three pointer calls return NULL and
+ * tiled read batch.  The other tips-only results are served too: ts_batch_terminal_ends writes the longest terminal block
+ * per side of every segment to device memory (same stream, same overflow protocol as the pass), ts_batch_download_blocks calls
+ * the terminal blocks on the device over the records where they lie and returns them as ts_scan_segments_blocks returns the
+ * same tips-only segments (no windows, no matches, no interstitial blocks; it syncs first when the batch is not synced), and
+ * ts_batch_segment_summary writes {0, n_matches, n_canonical, n_forward} per segment, the numbers ts_scan_segments_blocks hands
+ * back as ts_segment_counts (scan's stream; it syncs first likewise).  ts_batch_get_info fills the segments, bases, input
+ * bytes, tiles and slot capacity (the rest is 0), and ts_batch_destroy frees it.  match_capacity is ignored.  EVERY OTHER
+ * ts_batch_* call (restrict, partition, the shard calls, bind, export, adopt, ts_batch_download, get_tiles / range_info,
+ * set_emit, set_record_bits, set_timing, wait_scan) and ts_shards_finalize answers TS_ERR_UNSUPPORTED with the call named in ts_last_error; the three pointer calls return NULL and
  * ts_batch_wire16_ok 0.  Full-scan batches (tips_only = 0) of such sets stay refused: the host entry points scan them.  The
  * reference has no batches at all (one job per read, src/input.cpp:753-812). */
 ts_batch *ts_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t *abs_pos,
@@ -710,6 +725,15 @@ int ts_batch_read_pass_status(ts_batch *b, int *overflowed);
 /* (On a general tips batch — see ts_batch_create — the pass is always enqueued; after an overflow or a spill its bytes mean
  * nothing, *overflowed says so on every call until ts_batch_sync has rescanned, and ts_batch_read_pass wants the stream of the
  * scan.) */
+/* The GFA annotation's numbers for segment ends that already are in HBM: on a scanned tips-only batch, tiled or general, writes
+ * d_ends[2*i] / d_ends[2*i+1] (uint32 each, device memory, 8 bytes per segment) = the longest terminal block at the start / end
+ * side of segment i, 0 where there is none — what ts_terminal_ends returns for the same segments — asynchronously on `stream`.
+ * Stands in for walkSegment / walkSegmentForPath's per-segment reduction (src/input.cpp:835-939) over scanSegment's terminal
+ * blocks.  A full-scan batch answers TS_ERR_INVALID_ARG.  Overflow follows ts_batch_read_pass' protocol exactly:
+ * ts_batch_read_pass_status reports it, the caller then calls ts_batch_sync and ts_batch_terminal_ends again; after an
+ * overflow a tiled batch's d_ends keeps what it held and a general tips batch's holds memory-safe, meaningless numbers.  On a
+ * general tips batch `stream` is the stream of the scan. */
+int ts_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream);
 int ts_filter_reads_multi(ts_ctx *const *ctxs, size_t n_ctx, const char *const *seqs, const uint64_t *lens,
                           size_t n_reads, uint8_t *pass);
 

@@ -301,6 +301,15 @@ public:
         return s;
     }
 
+    // which way the first device's context reduced the per-side maxima of terminalEnds since it was made (ts_terminal_ends_stats):
+    // segments by the tiled ENDS walk, by the general ENDS walk, on the host from downloaded blocks, bytes of maxima and flag
+    // words copied device to host — cumulative; take the difference around a call
+    std::array<uint64_t, 4> terminalEndsStats() const {
+        std::array<uint64_t, 4> s{};
+        if (ts_terminal_ends_stats(ctx.get(), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(ctx.get()));
+        return s;
+    }
+
     // one scanSegment call of a batch; the bases are borrowed for the duration of the call (any case:
     // the library folds case itself, as unmaskSequence would have)
     struct Segment {

@@ -274,7 +274,7 @@ SYMBOLS = [
     "ts_chunk_reserve", "ts_chunk_upload", "ts_fastq_chunk_walk", "ts_fastq_chunk_stage", "ts_fastq_chunk_gather",
     "ts_fasta_chunk_walk", "ts_fasta_chunk_join", "ts_fasta_chunk_runs", "ts_fasta_chunk_bases",
     "ts_gfa_chunk_walk", "ts_chunk_data", "ts_chunk_carry_over", "ts_device_input_stats", "ts_upload_stats", "ts_read_batch_stats",
-    "ts_fasta_chunk_strict", "ts_gfa_chunk_check",
+    "ts_fasta_chunk_strict", "ts_gfa_chunk_check", "ts_terminal_ends_stats", "ts_batch_terminal_ends",
     "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
     "ts_match_lines_format", "ts_free_match_text", "ts_scan_segments_text", "ts_match_text_stats",
     "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
@@ -433,6 +433,10 @@ def lib():
     L.ts_device_input_stats.restype = C.c_int
     L.ts_upload_stats.restype = C.c_int
     L.ts_read_batch_stats.restype = C.c_int
+    L.ts_terminal_ends_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ts_terminal_ends_stats.restype = C.c_int
+    L.ts_batch_terminal_ends.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ts_batch_terminal_ends.restype = C.c_int
     L.ts_exchange_unique_id.argtypes = [C.c_void_p]
     L.ts_exchange_last_error.restype = C.c_char_p
     L.ts_exchange_create.restype = C.c_void_p

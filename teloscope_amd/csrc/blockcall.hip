@@ -113,10 +113,14 @@ __device__ __forceinline__ void emit_block(const TsBlockCallParams &Q, TsDevBloc
 // every pointer out of it became a flat address, and the eight rows it fetches ahead were waited for behind the first scratch reload)
 // PASS (ts_terminal_pass, a general read batch's predicate): a block that would be emitted sets pass[seg] instead — no block
 // buffer, no counter; the instantiations without it are the code they were.
-template <int MODE, bool PASS = false>
+// ENDS (ts_terminal_ends_walk, ts_terminal_ends over the general kernels' records): such a block's length is folded into the maximum
+// of the side it lies at, ends[2 seg + side] — walkSegment's rule (src/input.cpp:849-853), as reduce_terminal_ends applies it to the
+// emitted blocks: the start side when the block is at most as far from the start as from the end, a tie included.  Which walk found
+// the block does not decide its side.  Again nothing else changes: the other instantiations are the code they were.
+template <int MODE, bool PASS = false, bool ENDS = false>
 __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, const SegView &V, uint32_t seg, u64 n, u64 abs_pos,
                                   bool from_start, uint32_t &seq, uint32_t lane, bool &out_of_context,
-                                  unsigned char *pass = nullptr) {
+                                  unsigned char *pass = nullptr, uint32_t *ends = nullptr) {
     u64 boundary = from_start ? 0 : n;                     // segment-relative
     const uint32_t wlen_lane = (MODE == 1 && Q.wide) ? Q.wide_len[lane] : 0u;     // (the table holds 64 entries)
     Chain ch; bool open = false;
@@ -132,7 +136,10 @@ __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, co
             boundary = from_start ? cur.start + cur.block_len : cur.start;
             if (lane == 0) {
                 if constexpr (PASS) pass[seg] = 1;
-                else {
+                else if constexpr (ENDS) {
+                    const u64 to_end = n - (rel_start + cur.block_len);            // (unsigned, as the host's reduction computes it)
+                    atomicMax(&ends[2ull * seg + (rel_start <= to_end ? 0u : 1u)], cur.block_len);
+                } else {
                     TsDevBlock out = cur;
                     emit_block(Q, out, seg, from_start ? 0u : 1u, seq, abs_pos);
                 }
@@ -470,6 +477,32 @@ void ts_terminal_pass(const TsBlockCallParams Q, const TsShardSegIn *segs, uint3
         if (view_has_two(Q, V, 1, false, lane)) terminal_direction<MODE, true>(Q, V, si, S.len, S.abs_pos, true, seq, lane, ooc, pass);
     } else {
         if (view_has_two(Q, V, 2, true, lane)) terminal_direction<MODE, true>(Q, V, si, S.len, S.abs_pos, false, seq, lane, ooc, pass);
+    }
+}
+
+// ts_terminal_ends_walk: the same two walks, one wave each, in their ENDS form — ends[2 segment] / ends[2 segment + 1] = the longest
+// terminal block at the segment's start / end side, 0 where there is none; ends is zero at launch.  A block of the forward walk
+// can lie at the end side and one of the reverse walk at the start side (both happen in segments of at most twice the terminal
+// limit, where each walk's zone reaches past the middle), so both waves may write either word.  They combine with a vector
+// atomicMax: every block of at least -l, from either walk, is folded into its side's word exactly once, the words start at zero,
+// and a maximum over a fixed set of values is the same in whatever order they arrive — the result does not depend on which wave
+// runs first, nor on how the atomics of the two interleave.  (One wave walking both directions and storing once would need no
+// atomics, but it would walk the two lists one after the other: the walks are chains of memory latencies, and the two waves
+// halve that chain.  A segment has a handful of blocks: the atomics are as few.)
+template <int MODE>
+__global__ __launch_bounds__(kSideWg)
+void ts_terminal_ends_walk(const TsBlockCallParams Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t *ends) {
+    const uint32_t si = blockIdx.x >> 1;
+    if (si >= nseg) return;
+    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x & 1u;
+    const TsShardSegIn S = segs[si];
+    const SegView V = seg_view(Q, S);
+    uint32_t seq = 0;
+    bool ooc = false;
+    if (wave == 0) {
+        if (view_has_two(Q, V, 1, false, lane)) terminal_direction<MODE, false, true>(Q, V, si, S.len, S.abs_pos, true, seq, lane, ooc, nullptr, ends);
+    } else {
+        if (view_has_two(Q, V, 2, true, lane)) terminal_direction<MODE, false, true>(Q, V, si, S.len, S.abs_pos, false, seq, lane, ooc, nullptr, ends);
     }
 }
 
@@ -1088,6 +1121,31 @@ int ts_k_launch_read_pass_general(const TsBlockCallParams *Q, const TsShardSegIn
         hipLaunchKernelGGL(ts_terminal_pass<1>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, pass);
     else
         hipLaunchKernelGGL(ts_terminal_pass<0>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, pass);
+    return (int)hipGetLastError();
+}
+
+// The canonical / forward counts of a general tips batch's directory by themselves (block calling over its slots reads them).
+int ts_k_launch_slot_counts(const uint32_t *records, uint32_t slot_cap, uint32_t ntiles, uint32_t *tile_stats, void *stream) {
+    if (ntiles == 0) return 0;
+    hipLaunchKernelGGL(ts_slot_counts, dim3(ntiles), dim3(kSideWg), 0, (hipStream_t)stream, records, slot_cap, ntiles, tile_stats);
+    return (int)hipGetLastError();
+}
+
+// The per-side maxima over the general kernels' records in their slots: the arguments of the read predicate above, two u32 per
+// segment to ends (zeroed here: the walks fold into it).  tile_stats == nullptr: the directory already holds the canonical /
+// forward counts (the host entry points' groups: ts_k_launch_general_block_inputs wrote them with the tile list).
+int ts_k_launch_terminal_ends_general(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
+                                      uint32_t *tile_stats, uint32_t *ends, void *stream) {
+    if (nseg == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ends, 0, (size_t)nseg * 8, st);
+    if (e != hipSuccess) return (int)e;
+    if (ntiles == 0) return 0;
+    if (tile_stats) hipLaunchKernelGGL(ts_slot_counts, dim3(ntiles), dim3(kSideWg), 0, st, Q->matches, slot_cap, ntiles, tile_stats);
+    if (Q->wide)
+        hipLaunchKernelGGL(ts_terminal_ends_walk<1>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, ends);
+    else
+        hipLaunchKernelGGL(ts_terminal_ends_walk<0>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, ends);
     return (int)hipGetLastError();
 }
 

@@ -1300,8 +1300,8 @@ int ts_batch_adopt(ts_batch *b, void *d_windows, void *d_tile_stats, const void 
 }
 
 int ts_batch_segment_summary(ts_batch *b, void *d_out, void *stream) {
-    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_segment_summary");
     if (!b || !d_out) return TS_ERR_INVALID_ARG;
+    if (b->gen) return ts_general_batch_segment_summary(b, d_out, stream);
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
     if (!b->whole()) return c->fail(TS_ERR_STATE, "ts_batch_segment_summary needs an unrestricted batch");
@@ -1811,7 +1811,11 @@ int ts_batch_download(ts_batch *b, const char *const *host_seqs, ts_segment_out 
 
 // --------------------------------------------------------------- device block calling (row f1)
 int ts_batch_download_blocks(ts_batch *b, ts_segment_out *out) {
-    if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_download_blocks");
+    if (b && b->gen) {
+        if (!out) return TS_ERR_INVALID_ARG;
+        try { return ts_general_batch_download_blocks(b, out); }
+        catch (const std::exception &e) { return b->ctx->fail(TS_ERR_ALLOC, std::string("ts_batch_download_blocks: ") + e.what()); }
+    }
     return download_impl(b, out, false);
 }
 

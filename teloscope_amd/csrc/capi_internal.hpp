@@ -177,6 +177,9 @@ struct ts_ctx {
     // ts_read_batch_stats: scans enqueued on general tips batches, segments their read pass judged, rescans after an overflow or
     // spill, bytes those calls copied device to host — since ts_create
     std::atomic<uint64_t> read_batch_stats[4] = {};
+    // ts_terminal_ends_stats: segments reduced per side by the tiled ENDS walk, by the general ENDS walk, on the host from
+    // downloaded blocks; bytes of per-side maxima and flag words copied device to host — since ts_create
+    std::atomic<uint64_t> terminal_ends_stats[4] = {};
     hipEvent_t gen_ev[2] = {nullptr, nullptr};   // TS_TIMING: around the general path's kernels
     PinBuf pin_down[2];
     PinBuf pin_off;                              // general path: a group's tile directory lands here (a pageable landing cost 9 ms per MB-sized copy)
@@ -236,6 +239,7 @@ struct TsGeneralBatch {
     // tile list, {segment lengths, zeros, zeros, flag word}, slots, tile directory, slot offsets, the predicate's TsTile list and
     // segment table: all but the slots uploaded or sized once per batch
     DevBuf d_tiles, d_tab, d_slots, d_stats, d_off, d_bct, d_segin;
+    DevBuf d_sumtab;                    // ts_batch_segment_summary's table (first tile per segment), made on its first call
     bool uploaded = false;
     size_t tab_flag = 0;                // byte offset of the fused pass's flag word in d_tab
 };
@@ -415,6 +419,18 @@ inline unsigned long long ts_general_gen_lens(const ts_ctx *c) {
     if (c->gpat.nlen && c->gpat.len[c->gpat.nlen - 1] > 63u) v = 0;
     return v;
 }
+// what blockcall.hip's terminal walks read of the context (the record stream and its directory are the caller's to set)
+inline TsBlockCallParams ts_general_walk_params(const ts_ctx *c, unsigned long long gen_lens, bool wide) {
+    const ts_params &P = c->params;
+    TsBlockCallParams Q{};
+    Q.terminal_limit = P.terminal_limit; Q.max_match_dist = P.max_match_dist;
+    Q.min_block_len = P.min_block_len; Q.max_block_dist = P.max_block_dist;
+    Q.min_block_counts = P.min_block_counts; Q.min_block_density = P.min_block_density;
+    Q.k = c->k;
+    Q.gen_lens = gen_lens;
+    Q.wide = wide ? 1u : 0u; Q.wide_len = wide ? c->wpat.len : nullptr;
+    return Q;
+}
 // may a scan start in the list form of the fused pass?  (every tips-only scan that passes this does; a spilled candidate list
 // sends it to the strided form)
 inline bool ts_general_list_form_ok(const ts_ctx *c) {
@@ -429,6 +445,9 @@ ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const u
 void ts_general_batch_release(ts_batch *b);      // its device blocks back to the pool (ts_batch_destroy)
 int  ts_general_batch_scan(ts_batch *b, const void *d_input, void *stream);
 int  ts_general_batch_read_pass(ts_batch *b, void *d_pass, void *stream);
+int  ts_general_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream);
+int  ts_general_batch_download_blocks(ts_batch *b, ts_segment_out *out);
+int  ts_general_batch_segment_summary(ts_batch *b, void *d_out, void *stream);
 int  ts_general_batch_status(ts_batch *b, int *overflowed);
 int  ts_general_batch_sync(ts_batch *b);
 int  ts_general_batch_refuse(const ts_batch *b, const char *call);     // TS_ERR_UNSUPPORTED, the call named in ts_last_error

@@ -6,8 +6,10 @@
 // that ts_batch_upload, ts_fastq_chunk_stage, ts_bam_chunk_decode and a caller's own d_input fill it as they fill any batch.
 // Its tiles are TsGeneralTile over the regions scanSegment picks (the whole segment up to 2 x terminal limit, else the two tips);
 // ts_batch_scan enqueues the fused tips pass of generic.hip and the slot offsets, ts_batch_read_pass the predicate over the
-// records where that pass left them (blockcall.hip: ts_terminal_pass).  Only the fused pass's flag word ever comes back to the
-// host: ts_batch_read_pass_status reads it, ts_batch_sync regrows the slots (or leaves the list form) and rescans.
+// records where that pass left them (blockcall.hip: ts_terminal_pass), ts_batch_terminal_ends the same walks in their ENDS form
+// (ts_terminal_ends_walk).  For those calls only the fused pass's flag word ever comes back to the host:
+// ts_batch_read_pass_status reads it, ts_batch_sync regrows the slots (or leaves the list form) and rescans.
+// ts_batch_download_blocks calls the terminal blocks over the same slots and ts_batch_segment_summary adds up the tile directory.
 #include "capi_internal.hpp"
 
 namespace {
@@ -23,6 +25,21 @@ int take(ts_ctx *c, size_t bytes, DevBuf &d, const char *what, const TsGeneralBa
 }
 
 size_t slot_bytes(const TsGeneralBatch &g) { return std::max<size_t>(g.tiles.size(), 1) * (size_t)g.slot_cap * 4; }
+
+// the walks' per-segment table: every segment with all its tiles, both ends its own
+std::vector<TsShardSegIn> segment_table(const ts_batch *b) {
+    std::vector<TsShardSegIn> segin(b->segs.size());
+    for (size_t i = 0; i < segin.size(); ++i) {
+        const SegPlan &sp = b->segs[i];
+        TsShardSegIn &S = segin[i];
+        S = TsShardSegIn{};
+        S.in_off = sp.in_off; S.len = sp.len; S.abs_pos = sp.abs_pos;
+        S.t0 = S.o0 = sp.first_tile; S.t1 = S.o1 = sp.first_tile + sp.n_tiles;
+        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
+        S.lo_rel = 0; S.hi_rel = sp.len; S.seg = (uint32_t)i;
+    }
+    return segin;
+}
 
 // Device state, once per batch: the tile list, the per-segment table of the fused pass {lengths, window bases, window counts:
 // the last two zero for tips} with the flag word behind it, the predicate's tile list and segment table; and the buffers every
@@ -42,17 +59,8 @@ int ensure_device(ts_batch *b) {
     if ((rc = take(c, std::max<size_t>(ns, 1) * sizeof(TsShardSegIn), g.d_segin, "the predicate's segment table", g)) != TS_OK) return rc;
     if ((rc = take(c, slot_bytes(g), g.d_slots, "the record slots", g)) != TS_OK) return rc;
     std::vector<unsigned long long> tab(3 * ns + 2, 0ull);
-    std::vector<TsShardSegIn> segin(ns);
-    for (size_t i = 0; i < ns; ++i) {
-        const SegPlan &sp = b->segs[i];
-        tab[i] = sp.len;
-        TsShardSegIn &S = segin[i];
-        S = TsShardSegIn{};
-        S.in_off = sp.in_off; S.len = sp.len; S.abs_pos = sp.abs_pos;
-        S.t0 = S.o0 = sp.first_tile; S.t1 = S.o1 = sp.first_tile + sp.n_tiles;
-        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-        S.lo_rel = 0; S.hi_rel = sp.len; S.seg = (uint32_t)i;
-    }
+    const std::vector<TsShardSegIn> segin = segment_table(b);
+    for (size_t i = 0; i < ns; ++i) tab[i] = b->segs[i].len;
     // (the walks take a tile's segment-relative position from in_off - the segment's: the layout's own offsets serve)
     std::vector<TsTile> bct(nt);
     for (size_t t = 0; t < nt; ++t) {
@@ -77,6 +85,17 @@ int read_flag(ts_batch *b, uint32_t &flag) {
     HIP_TRY(c, hipStreamSynchronize(st));
     c->read_batch_stats[3].fetch_add(4, std::memory_order_relaxed);
     return TS_OK;
+}
+
+// what the terminal walks read of the batch: the slots through the directory, the context's block parameters
+TsBlockCallParams walk_params(const ts_batch *b) {
+    const TsGeneralBatch &g = *b->gen;
+    TsBlockCallParams Q = ts_general_walk_params(b->ctx, g.gen_lens, g.wide);
+    Q.tiles = (const TsTile *)g.d_bct.p;
+    Q.tile_off = (const unsigned long long *)g.d_off.p;
+    Q.tile_stats = (const uint32_t *)g.d_stats.p;
+    Q.matches = (const uint32_t *)g.d_slots.p;
+    return Q;
 }
 
 }  // namespace
@@ -151,14 +170,15 @@ ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const u
 
 void ts_general_batch_release(ts_batch *b) {
     TsGeneralBatch &g = *b->gen;
-    for (DevBuf *d : {&g.d_tiles, &g.d_tab, &g.d_slots, &g.d_stats, &g.d_off, &g.d_bct, &g.d_segin}) b->ctx->pool.give(std::move(*d));
+    for (DevBuf *d : {&g.d_tiles, &g.d_tab, &g.d_slots, &g.d_stats, &g.d_off, &g.d_bct, &g.d_segin, &g.d_sumtab}) b->ctx->pool.give(std::move(*d));
     g.uploaded = false;
 }
 
 int ts_general_batch_refuse(const ts_batch *b, const char *call) {
     return b->ctx->fail(TS_ERR_UNSUPPORTED, std::string(call) + ": not served by a general tips batch (the tips-only batch of a pattern set "
                                             "the general kernels scan); it takes ts_batch_segment_offset, _input_ptr, _upload, _scan, "
-                                            "_read_pass, _read_pass_status, _sync, _get_info and _destroy");
+                                            "_read_pass, _terminal_ends, _read_pass_status, _sync, _download_blocks, "
+                                            "_segment_summary, _get_info and _destroy");
 }
 
 // The fused tips pass (list or strided form, or the wide form) and the slot offsets, on `stream`; no host synchronisation beyond
@@ -206,22 +226,78 @@ int ts_general_batch_read_pass(ts_batch *b, void *d_pass, void *stream) {
     TsGeneralBatch &g = *b->gen;
     if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_read_pass needs a scanned, unrestricted tips-only batch");
     if (stream != b->last_stream) return c->fail(TS_ERR_STATE, "ts_batch_read_pass on a general tips batch: pass the stream of its scan");
-    const ts_params &P = c->params;
-    TsBlockCallParams Q{};
-    Q.tiles = (const TsTile *)g.d_bct.p;
-    Q.tile_off = (const unsigned long long *)g.d_off.p;
-    Q.tile_stats = (const uint32_t *)g.d_stats.p;
-    Q.matches = (const uint32_t *)g.d_slots.p;
-    Q.terminal_limit = P.terminal_limit; Q.max_match_dist = P.max_match_dist;
-    Q.min_block_len = P.min_block_len; Q.max_block_dist = P.max_block_dist;
-    Q.min_block_counts = P.min_block_counts; Q.min_block_density = P.min_block_density;
-    Q.k = c->k;
-    Q.gen_lens = g.gen_lens;
-    Q.wide = g.wide ? 1u : 0u; Q.wide_len = g.wide ? c->wpat.len : nullptr;
+    const TsBlockCallParams Q = walk_params(b);
     if (ts_k_launch_read_pass_general(&Q, (const TsShardSegIn *)g.d_segin.p, (uint32_t)b->segs.size(), (uint32_t)g.tiles.size(), g.slot_cap,
                                       (uint32_t *)g.d_stats.p, (unsigned char *)d_pass, stream) != 0)
         return c->fail(TS_ERR_HIP, "general read-pass kernel launch failed");
     c->read_batch_stats[1].fetch_add(b->segs.size(), std::memory_order_relaxed);
+    return TS_OK;
+}
+
+// walkSegment's per-side maxima (src/input.cpp:835-881) per segment: the same walks in their ENDS form.  Two u32 per segment to
+// d_ends, on the scan's stream; after an overflow they mean nothing, as the pass bytes do.
+int ts_general_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream) {
+    ts_ctx *c = b->ctx;
+    DEVICE_TRY(c);
+    TsGeneralBatch &g = *b->gen;
+    if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_terminal_ends needs a scanned, unrestricted tips-only batch");
+    if (stream != b->last_stream) return c->fail(TS_ERR_STATE, "ts_batch_terminal_ends on a general tips batch: pass the stream of its scan");
+    const TsBlockCallParams Q = walk_params(b);
+    if (ts_k_launch_terminal_ends_general(&Q, (const TsShardSegIn *)g.d_segin.p, (uint32_t)b->segs.size(), (uint32_t)g.tiles.size(), g.slot_cap,
+                                          (uint32_t *)g.d_stats.p, (uint32_t *)d_ends, stream) != 0)
+        return c->fail(TS_ERR_HIP, "general terminal-ends kernel launch failed");
+    c->terminal_ends_stats[1].fetch_add(b->segs.size(), std::memory_order_relaxed);
+    return TS_OK;
+}
+
+// The terminal blocks of every segment, called on the device over the slots in place (a tips scan is in position order: the
+// host route's in-place case, pipeline.cpp: gen_blocks) and assembled as that route assembles them: no windows, no matches, no
+// interstitial blocks.
+int ts_general_batch_download_blocks(ts_batch *b, ts_segment_out *out) {
+    ts_ctx *c = b->ctx;
+    DEVICE_TRY(c);
+    TsGeneralBatch &g = *b->gen;
+    if (!b->synced) { const int rc = ts_batch_sync(b); if (rc != TS_OK) return rc; }
+    hipStream_t st = (hipStream_t)b->last_stream;
+    const size_t ns = b->segs.size(), nt = g.tiles.size();
+    if (ts_k_launch_slot_counts((const uint32_t *)g.d_slots.p, g.slot_cap, (uint32_t)nt, (uint32_t *)g.d_stats.p, st) != 0)
+        return c->fail(TS_ERR_HIP, "slot-count kernel launch failed");
+    std::vector<TsDevBlock> blocks;
+    const int rc = ts_device_block_call_raw(c, (const TsTile *)g.d_bct.p, (const unsigned long long *)g.d_off.p, (const uint32_t *)g.d_stats.p,
+                                            (const uint32_t *)g.d_slots.p, 0, segment_table(b), nt, true, g.gen_lens, nullptr, nullptr, st,
+                                            blocks, nullptr, 0, g.wide ? c->wpat.len : nullptr, false);
+    if (rc != TS_OK) return rc;
+    HostView v;
+    v.tips = true;
+    v.blocks = blocks.data(); v.n_blocks = blocks.size();
+    v.segs.reserve(ns);
+    for (const SegPlan &sp : b->segs) v.segs.push_back({sp.len, sp.abs_pos, 0, 0, sp.first_tile, sp.n_tiles});
+    return ts_assemble_general(c, v, out);
+}
+
+// {0, matches, canonical, forward} per segment, four u64 each, to d_out on the scan's stream: the tile directory added up (the
+// tiled batches' summary kernel; a tips scan has no windows).
+int ts_general_batch_segment_summary(ts_batch *b, void *d_out, void *stream) {
+    ts_ctx *c = b->ctx;
+    DEVICE_TRY(c);
+    TsGeneralBatch &g = *b->gen;
+    if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_segment_summary needs a scanned batch");
+    if (!b->synced) { const int rc = ts_batch_sync(b); if (rc != TS_OK) return rc; }
+    if (stream != b->last_stream) return c->fail(TS_ERR_STATE, "ts_batch_segment_summary on a general tips batch: pass the stream of its scan");
+    const size_t ns = b->segs.size(), nt = g.tiles.size();
+    const size_t bytes_first = ((ns + 1) * 4 + 15) & ~(size_t)15;
+    if (!g.d_sumtab.p) {
+        std::vector<char> tab(bytes_first + ns * 8 + 16, 0);              // first tile per segment (and the end), then zero windows each
+        for (size_t i = 0; i < ns; ++i) ((uint32_t *)tab.data())[i] = b->segs[i].first_tile;
+        ((uint32_t *)tab.data())[ns] = (uint32_t)nt;
+        { const int rc = take(c, tab.size(), g.d_sumtab, "the summary's segment table", g); if (rc != TS_OK) return rc; }
+        HIP_TRY(c, hipMemcpy(g.d_sumtab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    }
+    if (ts_k_launch_slot_counts((const uint32_t *)g.d_slots.p, g.slot_cap, (uint32_t)nt, (uint32_t *)g.d_stats.p, stream) != 0)
+        return c->fail(TS_ERR_HIP, "slot-count kernel launch failed");
+    if (ts_k_launch_summary((const uint32_t *)g.d_stats.p, (const uint32_t *)g.d_sumtab.p, (const uint64_t *)((char *)g.d_sumtab.p + bytes_first),
+                            (uint32_t)ns, (unsigned long long *)d_out, stream) != 0)
+        return c->fail(TS_ERR_HIP, "summary kernel launch failed");
     return TS_OK;
 }
 
@@ -260,6 +336,12 @@ int ts_general_batch_sync(ts_batch *b) {
         const int rc = ts_general_batch_scan(b, b->last_input, b->last_stream);
         if (rc != TS_OK) return rc;
     }
+}
+
+extern "C" int ts_terminal_ends_stats(const ts_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return TS_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->terminal_ends_stats[i].load(std::memory_order_relaxed);
+    return TS_OK;
 }
 
 extern "C" int ts_read_batch_stats(const ts_ctx *ctx, uint64_t out[4]) {

@@ -732,6 +732,8 @@ int batch_terminal_ends(ts_batch *b, uint32_t *ends_out, int slot, hipStream_t s
     HIP_TRY(c, hipMemcpyAsync(ends_out, d_ends.p, ns * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(&flag, flag_at, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
+    c->terminal_ends_stats[3].fetch_add(ns * 8 + 4, std::memory_order_relaxed);
+    c->terminal_ends_stats[flag ? 2 : 0].fetch_add(ns, std::memory_order_relaxed);
     if (!flag) return TS_OK;
     HIP_TRY(c, hipMemsetAsync(flag_at, 0, 4, st));
     ts_fetched *f = ts_batch_fetch(b, false, slot, &rc);
@@ -1119,6 +1121,10 @@ struct GenCall {
     uint64_t target;                                      // bytes of regions per group
     uint32_t len_spread;
     bool position_order, push_compact;
+    // ts_terminal_ends over records that stay in their slots: the walks' ENDS form reduces them on the device (gen_ends) — no
+    // directory, no block and no sum is downloaded, and the group has no host stage.  A stream the device would have to put in
+    // push order first keeps the blocks path (no tips scan is one: the flag is the fallback's door, not a switch).
+    bool ends_device;
     unsigned long long gen_lens = 0;
     // a tile's slot at the start of a group: what the groups before needed (a telomeric tile under a many-length set holds more
     // than a record per position; finding that out again for every group ran half the groups of a call twice)
@@ -1157,6 +1163,7 @@ struct GenCall {
                           : (c->gpat.nlen ? c->gpat.len[c->gpat.nlen - 1] - c->gpat.len[0] : 0u);
         position_order = tips || w == s || len_spread <= 1u;                   // position order IS push order
         push_compact = !position_order;                                         // the device orders the stream
+        ends_device = m == Mode::Ends && t && !push_compact;
         gen_lens = ts_general_gen_lens(c);                                      // (wide records: the lengths come from wpat.len; non-zero = "general format")
         slot_cap_call = ts_general_slot_start(c, TS_GENERAL_TILE);
     }
@@ -1291,11 +1298,13 @@ int gen_fused(GenCall &g, GenGroup &gr) {
         if (nt && c->pin_off.ensure(std::max<size_t>((nt + 1) * 8 + 64, 1u << 20)) == hipSuccess) land = (unsigned long long *)c->pin_off.p;
         else (void)hipGetLastError();
         uint32_t *flag_land = land ? (uint32_t *)(land + nt + 1) : &flag;
-        if (nt) HIP_TRY(c, hipMemcpyAsync(land ? land : tile_off.data(), gr.d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
+        // (the ENDS walk reads the records in their slots: the dense stream's offsets have no reader on the host)
+        if (nt && !g.ends_device) HIP_TRY(c, hipMemcpyAsync(land ? land : tile_off.data(), gr.d_off.p, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipMemcpyAsync(flag_land, d_flag, 4, hipMemcpyDeviceToHost, st));
+        if (g.mode == Mode::Ends) c->terminal_ends_stats[3].fetch_add(4, std::memory_order_relaxed);
         const auto te1 = Clock::now();
         HIP_TRY(c, hipStreamSynchronize(st));
-        if (land) { std::memcpy(tile_off.data(), land, (nt + 1) * 8); flag = *flag_land; }
+        if (land) { if (!g.ends_device) std::memcpy(tile_off.data(), land, (nt + 1) * 8); flag = *flag_land; }
         if (g.timing) { g.t_dbg[0] += ms_between(t1, te0); g.t_dbg[1] += ms_between(te0, te1); g.t_dbg[2] += ms_between(te1, Clock::now()); }
         if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
         if (!flag) break;
@@ -1312,6 +1321,75 @@ int gen_fused(GenCall &g, GenGroup &gr) {
     ++(use_list ? g.n_list : g.n_strided);
     gr.nrec = tile_off[nt];
     g.t_fused += ms_between(t1, Clock::now());
+    return TS_OK;
+}
+
+// The walks' per-segment table of a group, and per segment the base its tiles' positions are relative to: the group's layout
+// holds the regions back to back, so a tile's segment-relative position is not its layout offset minus the segment's —
+// ts_k_launch_general_block_inputs writes tiles whose in_off is base + that position instead.
+void gen_segment_table(const GenHost &h, std::vector<unsigned long long> &sbase, std::vector<TsShardSegIn> &segtab) {
+    const size_t ns = h.G.size();
+    sbase.assign(std::max<size_t>(ns, 1), 0ull);
+    segtab.resize(ns);
+    unsigned long long X = 0;
+    for (size_t i = 0; i < ns; ++i) {
+        sbase[i] = X;
+        TsShardSegIn &S = segtab[i];
+        S = TsShardSegIn{};
+        S.in_off = X; S.len = h.G[i].len; S.abs_pos = h.G[i].abs_pos;
+        S.t0 = S.o0 = (uint32_t)h.G[i].first_tile; S.t1 = S.o1 = (uint32_t)(h.G[i].first_tile + h.G[i].n_tiles);
+        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
+        S.lo_rel = 0; S.hi_rel = h.G[i].len; S.seg = (uint32_t)i;
+        X += h.G[i].len + 64;
+    }
+}
+
+// ts_terminal_ends of a group on the device: the directory pointed at the slots, the tiles as blockcall.hip addresses them with
+// the canonical / forward counts (one kernel makes both: what ts_slot_counts counts for a batch, whose tile list is made once),
+// then the terminal walks in their ENDS form (ts_terminal_ends_walk) and 8 bytes per segment to the caller's array.
+int gen_ends(GenCall &g, GenGroup &gr) {
+    ts_ctx *c = g.c;
+    GenHost &h = *gr.gh;
+    const size_t ns = h.G.size(), nt = h.tiles.size();
+    hipStream_t st = c->scan_stream;
+    const auto t0 = Clock::now();
+    DevBuf d_bct, d_tab, d_ends;
+    struct Return { ts_ctx *c; DevBuf &a, &b2, &d; ~Return() { for (DevBuf *x : {&a, &b2, &d}) c->pool.give(std::move(*x)); } } give_back{c, d_bct, d_tab, d_ends};
+    std::vector<unsigned long long> sbase;
+    std::vector<TsShardSegIn> segtab;
+    gen_segment_table(h, sbase, segtab);
+    const size_t off_segs = (sbase.size() * 8 + 63) & ~(size_t)63;
+    HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * sizeof(TsTile), d_bct));
+    HIP_TRY(c, c->pool.take(off_segs + std::max<size_t>(ns, 1) * sizeof(TsShardSegIn), d_tab));
+    HIP_TRY(c, c->pool.take(ns * 8 + 16, d_ends));
+    HIP_TRY(c, hipMemcpyAsync(d_tab.p, sbase.data(), sbase.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync((char *)d_tab.p + off_segs, segtab.data(), ns * sizeof(TsShardSegIn), hipMemcpyHostToDevice, st));
+    TsBlockCallParams Q = ts_general_walk_params(c, g.gen_lens, g.wide);
+    Q.tiles = (const TsTile *)d_bct.p;
+    Q.tile_off = (const unsigned long long *)gr.d_off.p;
+    Q.tile_stats = (const uint32_t *)gr.d_stats.p;
+    Q.matches = (const uint32_t *)gr.d_slots.p;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[0], st));
+        if (ts_k_launch_general_slot_offsets((unsigned long long *)gr.d_off.p, (uint32_t)nt, gr.slot_cap, st) != 0)
+            return c->fail(TS_ERR_HIP, "slot-offset kernel launch failed");
+        if (ts_k_launch_general_block_inputs((const TsGeneralTile *)gr.d_tiles.p, (const unsigned long long *)gr.d_off.p, (const uint32_t *)gr.d_slots.p,
+                                             (const unsigned long long *)d_tab.p, (uint32_t)nt, (TsTile *)d_bct.p, (uint32_t *)gr.d_stats.p, 0, st) != 0)
+            return c->fail(TS_ERR_HIP, "general block-input kernel launch failed");
+        if (ts_k_launch_terminal_ends_general(&Q, (const TsShardSegIn *)((char *)d_tab.p + off_segs), (uint32_t)ns, (uint32_t)nt, gr.slot_cap,
+                                              nullptr, (uint32_t *)d_ends.p, st) != 0)
+            return c->fail(TS_ERR_HIP, "general terminal-ends kernel launch failed");
+        if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
+    }
+    HIP_TRY(c, hipMemcpyAsync(g.o.ends + 2 * h.first, d_ends.p, ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));                        // (sbase and segtab are locals)
+    c->terminal_ends_stats[1].fetch_add(ns, std::memory_order_relaxed);
+    c->terminal_ends_stats[3].fetch_add(ns * 8, std::memory_order_relaxed);
+    if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
+    const auto t1 = Clock::now();
+    g.t_blk += ms_between(t0, t1);
+    g.t_dev += ms_between(gr.t_dev0, t1);
     return TS_OK;
 }
 
@@ -1354,19 +1432,9 @@ int gen_blocks(GenCall &g, GenGroup &gr) {
     struct Return { ts_ctx *c; DevBuf &a, &b2; ~Return() { c->pool.give(std::move(a)); c->pool.give(std::move(b2)); } } give_back{c, d_bct, d_sbase};
     HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * sizeof(TsTile), d_bct));
     HIP_TRY(c, c->pool.take(std::max<size_t>(ns, 1) * 8, d_sbase));
-    std::vector<unsigned long long> sbase(std::max<size_t>(ns, 1), 0ull);
-    std::vector<TsShardSegIn> segtab(ns);
-    unsigned long long X = 0;
-    for (size_t i = 0; i < ns; ++i) {
-        sbase[i] = X;
-        TsShardSegIn &S = segtab[i];
-        S = TsShardSegIn{};
-        S.in_off = X; S.len = h.G[i].len; S.abs_pos = h.G[i].abs_pos;
-        S.t0 = S.o0 = (uint32_t)h.G[i].first_tile; S.t1 = S.o1 = (uint32_t)(h.G[i].first_tile + h.G[i].n_tiles);
-        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-        S.lo_rel = 0; S.hi_rel = h.G[i].len; S.seg = (uint32_t)i;
-        X += h.G[i].len + 64;
-    }
+    std::vector<unsigned long long> sbase;
+    std::vector<TsShardSegIn> segtab;
+    gen_segment_table(h, sbase, segtab);
     HIP_TRY(c, hipMemcpyAsync(d_sbase.p, sbase.data(), sbase.size() * 8, hipMemcpyHostToDevice, st));
     if (ts_k_launch_general_block_inputs((const TsGeneralTile *)gr.d_tiles.p, (const unsigned long long *)gr.d_off.p, gr.d_records,
                                          (const unsigned long long *)d_sbase.p, (uint32_t)nt, (TsTile *)d_bct.p, (uint32_t *)gr.d_stats.p,
@@ -1466,6 +1534,7 @@ int gen_host(GenCall &g, const GenHost &h) {
         if (o.pass) o.pass[i] = out[i].n_terminal_blocks != 0;
         if (o.ends) reduce_terminal_ends(out[i], h.G[i].len, h.G[i].abs_pos, o.ends + 2 * i);
     }
+    if (o.ends) g.c->terminal_ends_stats[2].fetch_add(ns, std::memory_order_relaxed);
     ts_free_segments(tmp.data(), tmp.size());
     return TS_OK;
 }
@@ -1495,6 +1564,16 @@ int scan_general(ts_ctx *c, Mode mode, bool tips, const std::vector<Item> &items
             });
         }
         int rc = gen_fused(g, *cur);
+        if (rc == TS_OK && g.ends_device) {
+            // the group's answer is on the host already: nothing to download, no host stage
+            rc = gen_ends(g, *cur);
+            if (rc != TS_OK) return rc;
+            const auto t_w = Clock::now();
+            if (pf.joinable()) pf.join();
+            g.t_wait_next += ms_between(t_w, Clock::now());
+            cur = std::move(nxt);
+            continue;
+        }
         if (rc == TS_OK) rc = gen_blocks(g, *cur);
         if (rc == TS_OK) rc = gen_download(g, *cur);
         if (rc != TS_OK) return rc;
@@ -1693,7 +1772,9 @@ int ts_filter_reads(ts_ctx *ctx, const char *const *seqs, const uint64_t *lens, 
 // =========================================================================== GFA annotation: per-end terminal lengths
 // ends[2i] / ends[2i+1]: the longest terminal block at the start / end side of segs[i] (walkSegment's rule,
 // src/input.cpp:835-881).  Tiled sets: a tips-only batch, the scan, the predicate's walks in their ENDS form
-// (predicate.hip) and 8 bytes per segment back.  Other sets: the general kernels' blocks, reduced on the host.
+// (predicate.hip) and 8 bytes per segment back.  Other sets: the general kernels' fused pass per group, then the terminal walks of
+// device block calling in their ENDS form over the records in their slots (blockcall.hip: ts_terminal_ends_walk) and the same 8
+// bytes per segment back; the blocks route (called on the device, reduced on the host) remains behind it.
 int ts_terminal_ends(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, uint32_t *ends) {
     if (!ctx || (n_segs && (!segs || !ends))) return TS_ERR_INVALID_ARG;
     const Outputs o{nullptr, nullptr, nullptr, ends};
@@ -1713,6 +1794,21 @@ int ts_batch_read_pass(ts_batch *b, void *d_pass, void *stream) {
     DEVICE_TRY(c);
     if (!b->tips || !b->whole() || !b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_read_pass needs a scanned, unrestricted tips-only batch");
     return batch_read_pass_device(b, (unsigned char *)d_pass, (hipStream_t)stream);
+}
+
+// walkSegment's per-side maxima over a device-resident tips-only batch: two u32 per segment to d_ends (device), asynchronously.
+// A tiled batch: the predicate's walks in their ENDS form, as ts_terminal_ends runs them per group; a general tips batch: the
+// terminal walks of device block calling in theirs.
+int ts_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream) {
+    if (!b || !d_ends) return TS_ERR_INVALID_ARG;
+    ts_ctx *c = b->ctx;
+    if (!b->tips) return c->fail(TS_ERR_INVALID_ARG, "ts_batch_terminal_ends needs a tips-only batch");
+    if (b->gen) return ts_general_batch_terminal_ends(b, d_ends, stream);
+    DEVICE_TRY(c);
+    if (!b->whole() || !b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_terminal_ends needs a scanned, unrestricted tips-only batch");
+    const int rc = batch_read_pass_device(b, nullptr, (hipStream_t)stream, (uint32_t *)d_ends);
+    if (rc == TS_OK) c->terminal_ends_stats[0].fetch_add(b->segs.size(), std::memory_order_relaxed);
+    return rc;
 }
 
 int ts_batch_read_pass_status(ts_batch *b, int *overflowed) {

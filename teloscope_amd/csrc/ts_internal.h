@@ -369,6 +369,12 @@ int  ts_k_launch_terminal(const TsBlockCallParams *Q, const TsShardSegIn *segs, 
 // canonical / forward counts added); pass[i] = 1 where segment i has a terminal block, else 0
 int  ts_k_launch_read_pass_general(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
                                    uint32_t *tile_stats, unsigned char *pass, void *stream);
+// the same walks in their ENDS form (ts_terminal_ends_walk): ends[2 i] / ends[2 i + 1] = the longest terminal block at the start /
+// end side of segment i (zeroed here).  tile_stats == nullptr: the directory's canonical / forward counts are already there
+int  ts_k_launch_terminal_ends_general(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
+                                       uint32_t *tile_stats, uint32_t *ends, void *stream);
+// the directory's counts alone (ts_slot_counts), for block calling over a general tips batch's slots
+int  ts_k_launch_slot_counts(const uint32_t *records, uint32_t slot_cap, uint32_t ntiles, uint32_t *tile_stats, void *stream);
 // per-segment totals into sums (5 x u64 per segment) or into the segments' entries of a shard's message (seg_out)
 int  ts_k_launch_segment_sums(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t seg_base, uint32_t ntiles,
                               unsigned long long *sums, TsShardSeg *seg_out, int prezeroed, void *stream);

@@ -201,6 +201,16 @@ class Teloscope:
             raise K.TeloscanError(rc, self._ctx.error())
         return tuple(int(v) for v in out)
 
+    def terminal_ends_stats(self):
+        """ts_terminal_ends_stats: (segments reduced per side by the tiled ENDS walk, by the general ENDS walk, on the host from
+        downloaded blocks, bytes of maxima and flag words copied device to host) of this context since it was made; cumulative,
+        so take the difference around a call."""
+        out = (C.c_uint64 * 4)()
+        rc = K.lib().ts_terminal_ends_stats(self._ctx.ptr, out)
+        if rc != K.TS_OK:
+            raise K.TeloscanError(rc, self._ctx.error())
+        return tuple(int(v) for v in out)
+
     def upload_stats(self):
         """ts_upload_stats: (chunks sent packed, chunks sent as ASCII, 16384-blocks packed from one plain piece, from one text
         piece, copied codes, mixed, chunks staged by several workers, unpack launches off a 64-position boundary) of this context
