@@ -830,6 +830,22 @@ int ts_bam_chunk_read(ts_bam_chunk *chunk, uint64_t off, uint64_t n, void *host)
  * the walk stopped at a record that is not valid, at *error_off.  Waits for the device. */
 int ts_bam_chunk_walk(ts_bam_chunk *chunk, uint64_t from, ts_bam_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
                       int *error, uint64_t *error_off);
+/* The same table by a parallel index: the contract of ts_bam_chunk_walk, word for word (recs, *n, *next, *error and *error_off
+ * are what that call gives for the same chunk, `from` and cap), for chunks of many short records, where the one-wave walk is
+ * the slowest stage.  The chunk is cut at absolute multiples of a span size; a wave per span finds up to `candidates` offsets
+ * from which the record rule survives to the span's end, the spans are chained from `from` (a span whose entry is no
+ * candidate is settled by the serial rule), and a wave per span writes its records.  The result never depends on the
+ * candidates, only the time does.  Replaces the record loop of subsetBam (src/bam.cpp:188-259), as ts_bam_chunk_walk does.
+ * Waits for the device. */
+int ts_bam_chunk_index(ts_bam_chunk *chunk, uint64_t from, ts_bam_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
+                       int *error, uint64_t *error_off);
+/* The index's span size (a power of two, 64 .. 2^30; 262144 unless set) and candidates kept per span (1 .. 8; 4 unless set), for
+ * tests and A/B runs of the stage that replaces src/bam.cpp:188-259; anything else: TS_ERR_INVALID_ARG, nothing changes. */
+int ts_bam_chunk_set_index_geometry(ts_bam_chunk *chunk, uint32_t span_bytes, uint32_t candidates);
+/* Cumulative since ts_create, monotonic and atomic, like ts_device_input_stats: calls of ts_bam_chunk_index (the stage that
+ * replaces src/bam.cpp:188-259), spans its chain entered, spans whose entry was a candidate row, spans settled by the serial
+ * rule, records the index wrote, bytes of candidate rows copied device to host. */
+int ts_bam_index_stats(const ts_ctx *ctx, uint64_t out[6]);
 /* SEQ of recs[i] (l_seq > 0 each) as ASCII bases (=ACMGRSVTWYHKDBN) into segment i of `reads`: an unrestricted tips-only batch
  * of n segments of l_seq bases made by ts_batch_create on the chunk's context.  The judgement is then the existing
  * ts_batch_scan + ts_batch_read_pass (+ ts_batch_read_pass_status).  Asynchronous on `stream`. */

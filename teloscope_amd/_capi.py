@@ -278,6 +278,7 @@ SYMBOLS = [
     "ts_window_tracks_format", "ts_free_track_text", "ts_scan_segments_tracks",
     "ts_match_lines_format", "ts_free_match_text", "ts_scan_segments_text", "ts_match_text_stats",
     "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
+    "ts_bam_chunk_index", "ts_bam_chunk_set_index_geometry", "ts_bam_index_stats",
 ]
 
 
@@ -456,6 +457,9 @@ def lib():
     L.ts_bam_chunk_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.ts_bam_chunk_walk.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BamRecord), C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+    L.ts_bam_chunk_index.argtypes = L.ts_bam_chunk_walk.argtypes
+    L.ts_bam_chunk_set_index_geometry.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    L.ts_bam_index_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ts_bam_chunk_decode.argtypes = [C.c_void_p, C.POINTER(BamRecord), C.c_size_t, C.c_void_p, C.c_void_p]
     L.ts_bam_chunk_pass_buffer.restype = C.c_void_p
     L.ts_bam_chunk_pass_buffer.argtypes = [C.c_void_p, C.c_uint64]

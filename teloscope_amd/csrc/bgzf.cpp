@@ -1,6 +1,7 @@
 // bgzf.cpp — host side of the device BGZF route (include/teloscan.h: ts_bgzf_inflate): descriptor checks, staging, the
 // verdict.  Nothing here inflates: the members are decoded by bgzf.hip's kernel or not at all.
 #include "capi_internal.hpp"
+#include "bam_walk_core.h"
 
 #include <numeric>
 
@@ -209,6 +210,90 @@ int ts_bam_chunk_walk(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uint
     if (out[0] > cap || out[1] > ch->plain_n) return ctx->fail(TS_ERR_STATE, "ts_bam_chunk_walk: the walk left the chunk");
     if (out[0]) HIP_TRY(ctx, hipMemcpy(recs, ch->d_recs.p, (size_t)out[0] * sizeof(ts_bam_record), hipMemcpyDeviceToHost));
     *n = out[0]; *next = out[1]; *error = (int)out[2]; *error_off = out[3];
+    return TS_OK;
+}
+
+int ts_bam_chunk_set_index_geometry(ts_bam_chunk *ch, uint32_t span_bytes, uint32_t candidates) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    if (span_bytes < tsbam::kMinSpan || span_bytes > tsbam::kMaxSpan || (span_bytes & (span_bytes - 1u)) != 0u || candidates < 1u ||
+        candidates > tsbam::kMaxCandidates)
+        return ch->ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_set_index_geometry: span_bytes is a power of two of 64 .. 2^30, candidates 1 .. 8");
+    uint32_t lg = 0;
+    while ((1u << lg) < span_bytes) ++lg;
+    ch->index_span_log2 = lg;
+    ch->index_candidates = candidates;
+    return TS_OK;
+}
+
+// The parallel form of ts_bam_chunk_walk (bam_walk_core.h): candidates per span on the device, the chain here from the
+// downloaded rows, the table written on the device by a wave per entered span.
+int ts_bam_chunk_index(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uint64_t cap, uint64_t *n, uint64_t *next,
+                       int *error, uint64_t *error_off) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!n || !next || !error || !error_off || (cap && !recs) || from > ch->plain_n || cap > (1ull << 31))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_index: null or out-of-range argument");
+    DEVICE_TRY(ctx);
+    const uint32_t lg = ch->index_span_log2, K = ch->index_candidates;
+    const uint64_t size = ch->plain_n;
+    ctx->bam_index_stats[0].fetch_add(1, std::memory_order_relaxed);
+    *n = 0; *next = from; *error = TS_BAM_OK; *error_off = 0;
+    if (cap == 0 || size - from < 4) return TS_OK;
+    const uint64_t first = from >> lg, n_spans = ((size - 1) >> lg) - first + 1;
+    if (n_spans > (1ull << 26)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_index: the span size is too small for this chunk");
+    const size_t row_bytes = (size_t)n_spans * K * sizeof(tsbam::Row);
+    HIP_TRY(ctx, grow(ch->d_idx_rows, row_bytes));
+    if (ts_k_launch_bam_index_candidates(ch->d_plain.p, size, from, lg, K, first, (uint32_t)n_spans, ch->d_idx_rows.p, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_index: kernel launch failed");
+    ch->h_idx_rows.resize(row_bytes);
+    HIP_TRY(ctx, hipMemcpy(ch->h_idx_rows.data(), ch->d_idx_rows.p, row_bytes, hipMemcpyDeviceToHost));     // (waits for the kernel)
+    const tsbam::Row *rows = (const tsbam::Row *)ch->h_idx_rows.data();
+    std::vector<tsbam::Task> tasks;
+    hipError_t bad = hipSuccess;
+    int launch_failed = 0;
+    const tsbam::ChainResult c = tsbam::chain(
+        size, from, cap, lg, K, [&](uint64_t k) { return rows + (size_t)(k - first) * K; },
+        [&](uint64_t entry, uint64_t span_end) {
+            tsbam::SpanResult s;
+            s.exit = entry; s.records = 0; s.stop = tsbam::kShort;      // (after a failure: the chain ends here)
+            unsigned long long out[3] = {0, 0, 0};
+            if (bad != hipSuccess || launch_failed) return s;
+            if (ts_k_launch_bam_index_settle(ch->d_plain.p, size, entry, span_end, ch->d_out.p, nullptr) != 0) { launch_failed = 1; return s; }
+            bad = hipMemcpy(out, ch->d_out.p, sizeof out, hipMemcpyDeviceToHost);
+            if (bad != hipSuccess) return s;
+            s.exit = out[0]; s.records = out[1]; s.stop = (uint32_t)out[2];
+            return s;
+        },
+        [&](const tsbam::Task &t) { tasks.push_back(t); });
+    if (launch_failed) return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_index: kernel launch failed");
+    HIP_TRY(ctx, bad);
+    ctx->bam_index_stats[1].fetch_add(c.entered, std::memory_order_relaxed);
+    ctx->bam_index_stats[2].fetch_add(c.hits, std::memory_order_relaxed);
+    ctx->bam_index_stats[3].fetch_add(c.settled, std::memory_order_relaxed);
+    ctx->bam_index_stats[5].fetch_add(row_bytes, std::memory_order_relaxed);
+    if (c.n > cap || c.next > size) return ctx->fail(TS_ERR_STATE, "ts_bam_chunk_index: the chain left the chunk");
+    unsigned long long next_at = c.next;
+    if (c.n) {
+        // (the write pass is told c.n, not cap: it stores nothing beyond what the chain counted, whatever it meets)
+        HIP_TRY(ctx, grow(ch->d_recs, (size_t)c.n * sizeof(ts_bam_record)));
+        HIP_TRY(ctx, grow(ch->d_idx_tasks, tasks.size() * sizeof(tsbam::Task)));
+        HIP_TRY(ctx, hipMemcpy(ch->d_idx_tasks.p, tasks.data(), tasks.size() * sizeof(tsbam::Task), hipMemcpyHostToDevice));
+        if (ts_k_launch_bam_index_write(ch->d_plain.p, size, ch->d_idx_tasks.p, (uint32_t)tasks.size(), lg, c.n, ch->d_recs.p, ch->d_out.p, nullptr) != 0)
+            return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_index: kernel launch failed");
+        HIP_TRY(ctx, hipMemcpy(recs, ch->d_recs.p, (size_t)c.n * sizeof(ts_bam_record), hipMemcpyDeviceToHost));
+        if (c.next_in_span) {
+            HIP_TRY(ctx, hipMemcpy(&next_at, ch->d_out.p, sizeof next_at, hipMemcpyDeviceToHost));
+            if (next_at > size) return ctx->fail(TS_ERR_STATE, "ts_bam_chunk_index: the walk left the chunk");
+        }
+    }
+    ctx->bam_index_stats[4].fetch_add(c.n, std::memory_order_relaxed);
+    *n = c.n; *next = next_at; *error = (int)c.error; *error_off = c.error_off;
+    return TS_OK;
+}
+
+int ts_bam_index_stats(const ts_ctx *ctx, uint64_t out[6]) {
+    if (!ctx || !out) return TS_ERR_INVALID_ARG;
+    for (int i = 0; i < 6; ++i) out[i] = ctx->bam_index_stats[i].load(std::memory_order_relaxed);
     return TS_OK;
 }
 

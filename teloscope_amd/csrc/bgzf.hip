@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/teloscan.h"
+#include "bam_walk_core.h"
 #include "inflate_core.h"
 #include "ts_device.h"
 #include "ts_internal.h"
@@ -237,6 +238,126 @@ void ts_bam_walk_kernel(const unsigned char *plain, unsigned long long plain_n, 
     if (threadIdx.x == 0) { out[0] = n; out[1] = pos; out[2] = err; out[3] = err ? pos : 0ull; }
 }
 
+// ---- the parallel record index (ts_bam_chunk_index; the scheme and its rule: bam_walk_core.h).  The chunk is cut into spans;
+// a wave per span finds the span's candidates, the host chains them from `from` (bgzf.cpp; a span it cannot chain is settled
+// by ts_bam_index_settle_kernel), and a wave per entered span walks it again from its verified entry and stores the table.
+// Three ways to the bytes: per-lane reads of an LDS window (the candidate test's first record: 64 offsets side by side),
+// per-lane reads of memory (the rest of a candidate's walk: each lane is somewhere else), and the serial walk's wave-uniform
+// LDS window (settle and write).  Every read is bounded by plain_n inside tsbam::record_at; the staging loads are whole aligned
+// 16-byte words that begin below plain_n (the chunk's buffer is readable 16 bytes beyond it).
+constexpr uint32_t kCandWindow = 4096, kCandStage = kCandWindow + 304;      // offsets per staged window; its bytes (+ a header region)
+
+struct LdsBytes {                                               // [wlo, ...) staged in LDS, read per lane
+    const unsigned char *win;
+    unsigned long long wlo;
+    __device__ __forceinline__ uint32_t byte(unsigned long long p) const { return win[p - wlo]; }
+    __device__ __forceinline__ uint32_t le32(unsigned long long p) const { return byte(p) | byte(p + 1) << 8 | byte(p + 2) << 16 | byte(p + 3) << 24; }
+    __device__ __forceinline__ void stage(unsigned long long, unsigned long long) const {}
+};
+
+struct GlobalBytes {                                            // the chunk in memory, read per lane
+    const unsigned char *plain;
+    __device__ __forceinline__ uint32_t byte(unsigned long long p) const { return plain[p]; }
+    __device__ __forceinline__ uint32_t le32(unsigned long long p) const { uint32_t v; __builtin_memcpy(&v, plain + p, 4); return v; }
+    __device__ __forceinline__ void stage(unsigned long long, unsigned long long) const {}
+};
+
+// The serial walk's staging for a wave that walks one span: 16 KB windows, 1 KB behind a jump of more than 8 KB, and never
+// beyond the header region of the span's last possible record.  All lanes run the walk; every value read is wave-uniform.
+struct WaveWindow {
+    uint4 *win4;
+    const unsigned char *plain;
+    unsigned long long span_end, wlo, whi, prev;
+    __device__ __forceinline__ uint32_t byte(unsigned long long p) const {
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)((const unsigned char *)win4)[p - wlo]);
+    }
+    __device__ __forceinline__ uint32_t le32(unsigned long long p) const { return byte(p) | byte(p + 1) << 8 | byte(p + 2) << 16 | byte(p + 3) << 24; }
+    __device__ __forceinline__ void stage(unsigned long long pos, unsigned long long n) {
+        const unsigned long long want = n - pos < tsbam::kHeader ? n : pos + tsbam::kHeader;
+        if (pos < wlo || want > whi) {                          // (wave-uniform)
+            uint32_t bytes = whi != 0ull && pos - prev > kWalkWindow / 2 ? 1024u : kWalkWindow;
+            __syncthreads();
+            wlo = pos & ~15ull;
+            const unsigned long long need = (span_end + tsbam::kHeader - wlo + 15ull) & ~15ull;     // (pos < span_end)
+            if (need < bytes) bytes = (uint32_t)need;
+            whi = wlo + bytes;
+            for (uint32_t k = threadIdx.x; k < bytes / 16u; k += 64u) {
+                const unsigned long long a = wlo + 16ull * k;
+                win4[k] = a < n ? *(const uint4 *)(plain + a) : make_uint4(0u, 0u, 0u, 0u);
+            }
+            __syncthreads();
+        }
+        prev = pos;
+    }
+};
+
+__global__ __launch_bounds__(64)
+void ts_bam_index_candidates_kernel(const unsigned char *plain, unsigned long long plain_n, unsigned long long from, uint32_t span_log2,
+                                    uint32_t K, unsigned long long first_span, tsbam::Row *rows) {
+    __shared__ uint4 win4[kCandStage / 16];
+    const unsigned long long k = first_span + blockIdx.x, span_lo = k << span_log2, span_end = span_lo + (1ull << span_log2);
+    tsbam::Row *mine = rows + (unsigned long long)blockIdx.x * K;
+    uint64_t lo, hi;
+    tsbam::scan_range(plain_n, from, span_log2, k, lo, hi);
+    uint32_t found = 0;
+    GlobalBytes g{plain};
+    for (unsigned long long w = lo & ~15ull; w < hi && found < K; w += kCandWindow) {
+        const unsigned long long wend = w + kCandWindow < hi ? w + kCandWindow : hi;
+        const uint32_t bytes = (uint32_t)((wend - w + tsbam::kHeader + 15ull) & ~15ull);            // <= kCandStage
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < bytes / 16u; i += 64u) {
+            const unsigned long long a = w + 16ull * i;
+            win4[i] = a < plain_n ? *(const uint4 *)(plain + a) : make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();
+        LdsBytes l{(const unsigned char *)win4, w};
+        for (unsigned long long b = w; b < wend && found < K; b += 64ull) {     // 64 offsets, ascending with the lane
+            const unsigned long long p = b + threadIdx.x;
+            tsbam::Row row;
+            bool ok = false;
+            if (p >= lo && p < wend) ok = tsbam::candidate(l, g, plain_n, p, span_lo, span_end, row);
+            const unsigned long long mask = ballot64(ok);
+            const uint32_t slot = found + (uint32_t)__popcll(mask & ((1ull << threadIdx.x) - 1ull));
+            if (ok && slot < K) mine[slot] = row;
+            found += (uint32_t)__popcll(mask);
+        }
+    }
+    if (threadIdx.x >= found && threadIdx.x < K) {
+        tsbam::Row none;
+        none.entry = tsbam::kNoRow; none.exit = 0u; none.records = 0u; none.stop = 0u;
+        mine[threadIdx.x] = none;
+    }
+}
+
+__global__ __launch_bounds__(64)
+void ts_bam_index_settle_kernel(const unsigned char *plain, unsigned long long plain_n, unsigned long long entry,
+                                unsigned long long span_end, unsigned long long *out) {
+    __shared__ uint4 win4[kWalkWindow / 16];
+    WaveWindow a{win4, plain, span_end, 0ull, 0ull, 0ull};
+    const tsbam::SpanResult s = tsbam::span_walk(a, plain_n, entry, span_end, ~0ull, tsbam::NoEmit());
+    if (threadIdx.x == 0) { out[0] = s.exit; out[1] = s.records; out[2] = s.stop; }
+}
+
+__global__ __launch_bounds__(64)
+void ts_bam_index_write_kernel(const unsigned char *plain, unsigned long long plain_n, const tsbam::Task *tasks, uint32_t n_tasks,
+                               uint32_t span_log2, unsigned long long cap, ts_bam_record *recs, unsigned long long *out) {
+    __shared__ uint4 win4[kWalkWindow / 16];
+    if (blockIdx.x >= n_tasks) return;
+    const unsigned long long entry = tasks[blockIdx.x].entry, base = tasks[blockIdx.x].base;
+    if (base >= cap) return;
+    const unsigned long long span_end = ((entry >> span_log2) + 1ull) << span_log2;
+    WaveWindow a{win4, plain, span_end, 0ull, 0ull, 0ull};
+    const tsbam::SpanResult s = tsbam::span_walk(a, plain_n, entry, span_end, cap - base,
+                                                 [&](unsigned long long i, unsigned long long pos, const tsbam::Record &r) {
+        if (threadIdx.x == 0) {
+            ts_bam_record o;
+            o.off = pos; o.block_size = r.block_size; o.seq_at = r.seq_at; o.l_seq = r.l_seq; o.reserved = 0u;
+            recs[base + i] = o;
+        }
+    });
+    if (s.stop == tsbam::kTableFull && threadIdx.x == 0) out[0] = s.exit;      // the offset of record `cap`
+}
+
 // ---- SEQ nibbles -> ASCII bases into a read batch's input buffer: a wave per <= 2 KB of a read, 16 output bytes per lane per
 // store.  The 16 letters sit in four registers; v_perm_b32 picks from eight bytes at a time.
 struct DecodeJob { unsigned long long src, dst; uint32_t n, pad; };         // packed bytes at plain + src -> n bases at in + dst
@@ -318,6 +439,29 @@ int ts_k_launch_bam_walk(const void *plain, unsigned long long plain_n, unsigned
                          void *recs, void *out4, void *stream) {
     hipLaunchKernelGGL(ts_bam_walk_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, plain_n, from,
                        cap, (ts_bam_record *)recs, (unsigned long long *)out4);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_bam_index_candidates(const void *plain, unsigned long long plain_n, unsigned long long from, uint32_t span_log2,
+                                     uint32_t K, unsigned long long first_span, uint32_t n_spans, void *rows, void *stream) {
+    if (n_spans == 0) return 0;
+    hipLaunchKernelGGL(ts_bam_index_candidates_kernel, dim3(n_spans), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain,
+                       plain_n, from, span_log2, K, first_span, (tsbam::Row *)rows);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_bam_index_settle(const void *plain, unsigned long long plain_n, unsigned long long entry, unsigned long long span_end,
+                                 void *out3, void *stream) {
+    hipLaunchKernelGGL(ts_bam_index_settle_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, plain_n,
+                       entry, span_end, (unsigned long long *)out3);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_bam_index_write(const void *plain, unsigned long long plain_n, const void *tasks, uint32_t n_tasks, uint32_t span_log2,
+                                unsigned long long cap, void *recs, void *out1, void *stream) {
+    if (n_tasks == 0) return 0;
+    hipLaunchKernelGGL(ts_bam_index_write_kernel, dim3(n_tasks), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, plain_n,
+                       (const tsbam::Task *)tasks, n_tasks, span_log2, cap, (ts_bam_record *)recs, (unsigned long long *)out1);
     return (int)hipGetLastError();
 }
 

@@ -174,6 +174,9 @@ struct ts_ctx {
     std::atomic<uint64_t> match_text_stats[4] = {};
     // ts_gzip_stats: windows, spans probed, spans chained, spans dropped, plain bytes produced, parts the caller handed to zlib — since ts_create
     std::atomic<uint64_t> gzip_stats[6] = {};
+    // ts_bam_index_stats: calls, spans the chain entered, spans whose entry was a candidate row, spans settled by the serial
+    // rule, records the index wrote, bytes of rows copied device to host — since ts_create
+    std::atomic<uint64_t> bam_index_stats[6] = {};
     // ts_read_batch_stats: scans enqueued on general tips batches, segments their read pass judged, rescans after an overflow or
     // spill, bytes those calls copied device to host — since ts_create
     std::atomic<uint64_t> read_batch_stats[4] = {};
@@ -504,6 +507,11 @@ struct ts_bam_chunk {
     uint64_t plain_n = 0;               // bytes the chunk holds: the carried tail, then the members' output
     size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status
     DevBuf d_comp, d_plain, d_blocks, d_result, d_tmp, d_recs, d_out, d_jobs, d_dst, d_gather, d_pass;
+    // the parallel record index (ts_bam_chunk_index): its span size (log2) and candidates per span, the candidate rows, the tasks
+    // of the write pass, and the host copy of the rows
+    uint32_t index_span_log2 = 18, index_candidates = 4;
+    DevBuf d_idx_rows, d_idx_tasks;
+    std::vector<unsigned char> h_idx_rows;
     DevBuf d_lines, d_waves, d_frames;  // the FASTQ walk's line index, per-slice newline counts and framing results (fastq.cpp)
     // FASTA (fasta.cpp): the walk's header table, record table and names; the join's jobs, their counts, the joined bases and runs
     DevBuf d_fa_heads, d_fa_recs, d_fa_names, d_fa_jobs, d_fa_counts, d_fa_bases, d_fa_runs, d_fa_out;

@@ -483,6 +483,15 @@ int  ts_k_launch_bgzf_inflate(const void *compressed, const void *blocks, uint32
 // n <= 2048), and the gather of passing records
 int  ts_k_launch_bam_walk(const void *plain, unsigned long long plain_n, unsigned long long from, unsigned long long cap,
                           void *recs, void *out4, void *stream);
+// ... the parallel record index (bam_walk_core.h): a wave per span [first_span, first_span + n_spans) writes its K candidate rows
+// (tsbam::Row); one wave settles a span by the serial rule (out3 = {exit, records, stop}); a wave per task (tsbam::Task) walks
+// its span from the verified entry and stores records below cap (out1[0] = the offset of record `cap` where a span holds it)
+int  ts_k_launch_bam_index_candidates(const void *plain, unsigned long long plain_n, unsigned long long from, uint32_t span_log2,
+                                      uint32_t K, unsigned long long first_span, uint32_t n_spans, void *rows, void *stream);
+int  ts_k_launch_bam_index_settle(const void *plain, unsigned long long plain_n, unsigned long long entry, unsigned long long span_end,
+                                  void *out3, void *stream);
+int  ts_k_launch_bam_index_write(const void *plain, unsigned long long plain_n, const void *tasks, uint32_t n_tasks, uint32_t span_log2,
+                                 unsigned long long cap, void *recs, void *out1, void *stream);
 int  ts_k_launch_bam_decode(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream);
 int  ts_k_launch_bam_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream);
 int  ts_k_launch_bam_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
