@@ -1130,6 +1130,54 @@ public:
         if (!out.good()) throw std::runtime_error("failed while writing BAM subset");
     }
 };
+// The BAM header in front of the records — magic, text, reference list — validated like copyBamHeader (src/bam.cpp:75-120:
+// text <= 1 GiB, names 1 .. 1 MiB and NUL-terminated, no negative counts or lengths) and copied verbatim to the writer.  The
+// bytes are the caller's: have(n) says whether n bytes lie at its cursor, bytes(off) points at them, and the cursor is moved
+// past what was copied.  A step that lacks bytes makes parse() return false; it is called again when more bytes have come.
+class BamHeaderParser {
+    static constexpr uint32_t kMaxHeaderText = 1u << 30, kMaxReferenceName = 1u << 20;
+    enum { Magic, Text, Refs, Records } phase = Magic;
+    uint32_t ltext = 0, nref = 0, refsDone = 0;
+    static uint32_t le32(const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); }
+public:
+    bool done() const { return phase == Records; }
+    // the input has ended: what an unfinished header is called
+    void requireDone() const { if (phase != Records) throw std::runtime_error(phase == Refs ? "truncated BAM reference" : "truncated BAM header"); }
+    template <typename Have, typename Bytes, typename Cursor>
+    bool parse(Have &&have, Bytes &&bytes, Cursor &pos, BgzfWriter &writer) {      // true when the header is complete
+        for (;;) {
+            if (phase == Magic) {
+                if (!have(8)) return false;
+                if (std::memcmp(bytes(0), "BAM\1", 4) != 0) throw std::runtime_error("input is not a BAM file");
+                ltext = le32(bytes(4));
+                if (ltext > kMaxHeaderText) throw std::runtime_error("invalid BAM header text length");
+                phase = Text;
+            } else if (phase == Text) {
+                const size_t n = 8 + static_cast<size_t>(ltext) + 4;
+                if (!have(n)) return false;
+                nref = le32(bytes(8 + static_cast<size_t>(ltext)));
+                if (nref > 0x7fffffffu) throw std::runtime_error("invalid BAM reference count");
+                writer.write(bytes(0), n);
+                pos += n;
+                phase = Refs;
+            } else if (phase == Refs) {
+                if (refsDone == nref) { phase = Records; return true; }
+                if (!have(4)) return false;
+                const uint32_t lname = le32(bytes(0));
+                if (lname == 0 || lname > kMaxReferenceName) throw std::runtime_error("invalid BAM reference name length");
+                const size_t n = 4 + static_cast<size_t>(lname) + 4;
+                if (!have(n)) return false;
+                if (*bytes(4 + static_cast<size_t>(lname) - 1) != 0) throw std::runtime_error("BAM reference name is not NUL-terminated");
+                if (le32(bytes(4 + static_cast<size_t>(lname))) > 0x7fffffffu) throw std::runtime_error("invalid BAM reference length");
+                writer.write(bytes(0), n);
+                pos += n;
+                ++refsDone;
+            } else {
+                return true;
+            }
+        }
+    }
+};
 }  // namespace detail
 
 inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
@@ -1176,44 +1224,10 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
     const unsigned char *plain = nullptr;       // the bytes being parsed: [plain + pos, plain + plainSize)
     size_t plainSize = 0, pos = 0;
     std::vector<unsigned char> carry, joined;   // unconsumed tail of the last chunk; (rare) a tail larger than the headroom + the next chunk
-    // header: magic, text, reference list — validated like copyBamHeader (src/bam.cpp:75-120: text <= 1 GiB, names
-    // 1 .. 1 MiB and NUL-terminated, no negative counts or lengths) and copied verbatim.  A step of the parse that lacks
-    // bytes returns false and is retried when the next chunk has been inflated.
-    constexpr uint32_t kMaxHeaderText = 1u << 30, kMaxReferenceName = 1u << 20;
-    enum { Magic, Text, Refs, Records } phase = Magic;
-    uint32_t ltext = 0, nref = 0, refsDone = 0;
+    // header: a step of the parse that lacks bytes returns false and is retried when the next chunk has been inflated
+    detail::BamHeaderParser header;
     auto have = [&](size_t n) { return plainSize - pos >= n; };
-    auto parseHeader = [&]() -> bool {                      // true when the header is complete
-        for (;;) {
-            if (phase == Magic) {
-                if (!have(8)) return false;
-                if (std::memcmp(plain + pos, "BAM\1", 4) != 0) throw std::runtime_error("input is not a BAM file");
-                ltext = le32(plain + pos + 4);
-                if (ltext > kMaxHeaderText) throw std::runtime_error("invalid BAM header text length");
-                phase = Text;
-            } else if (phase == Text) {
-                if (!have(8 + static_cast<size_t>(ltext) + 4)) return false;
-                nref = le32(plain + pos + 8 + ltext);
-                if (nref > 0x7fffffffu) throw std::runtime_error("invalid BAM reference count");
-                writer.write(plain + pos, 8 + static_cast<size_t>(ltext) + 4);
-                pos += 8 + static_cast<size_t>(ltext) + 4;
-                phase = Refs;
-            } else if (phase == Refs) {
-                if (refsDone == nref) { phase = Records; return true; }
-                if (!have(4)) return false;
-                const uint32_t lname = le32(plain + pos);
-                if (lname == 0 || lname > kMaxReferenceName) throw std::runtime_error("invalid BAM reference name length");
-                if (!have(4 + static_cast<size_t>(lname) + 4)) return false;
-                if (plain[pos + 4 + lname - 1] != 0) throw std::runtime_error("BAM reference name is not NUL-terminated");
-                if (le32(plain + pos + 4 + lname) > 0x7fffffffu) throw std::runtime_error("invalid BAM reference length");
-                writer.write(plain + pos, 4 + static_cast<size_t>(lname) + 4);
-                pos += 4 + static_cast<size_t>(lname) + 4;
-                ++refsDone;
-            } else {
-                return true;
-            }
-        }
-    };
+    auto bytesAt = [&](size_t off) { return plain + pos + off; };
 
     struct Rec { size_t rawOff, rawLen, seqAt; uint32_t seqLen; size_t seqOff; };
     std::vector<Rec> recs;
@@ -1293,7 +1307,7 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
             plain = joined.data(); plainSize = joined.size();
         }
         pos = 0;
-        if (phase == Records || parseHeader()) {
+        if (header.done() || header.parse(have, bytesAt, pos, writer)) {
             while (have(4)) {
                 const int32_t blockSize = static_cast<int32_t>(le32(plain + pos));
                 if (blockSize < 32 || static_cast<uint32_t>(blockSize) > (256u << 20)) throw std::runtime_error("invalid BAM record block_size");   // BAM_MAX_RECORD_SIZE, src/bam.cpp:29
@@ -1314,7 +1328,7 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
         msRecords += std::chrono::duration<double, std::milli>(Clock::now() - t1).count();
         if (more) spare.push(c);
     }
-    if (phase != Records) throw std::runtime_error(phase == Refs ? "truncated BAM reference" : "truncated BAM header");
+    header.requireDone();
     if (!carry.empty()) throw std::runtime_error(carry.size() < 4 ? "truncated BAM record size" : "truncated BAM record");
     spare.close();
     if (inflater.joinable()) inflater.join();
@@ -1717,7 +1731,6 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     if (!in.data) in.readToEnd(piped, "cannot read BAM input");
     const unsigned char *data = in.data ? in.data : piped.data();
     const size_t size = in.data ? in.size : piped.size();
-    auto le32 = [](const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); };
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     double msInflate = 0, msWalk = 0, msWrite = 0;
@@ -1729,9 +1742,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     if (!chunk.p) throw fail("cannot make the device chunk");
     detail::BgzfWriter writer(out);
 
-    constexpr uint32_t kMaxHeaderText = 1u << 30, kMaxReferenceName = 1u << 20;
-    enum { Magic, Text, Refs, Records } phase = Magic;
-    uint32_t ltext = 0, nref = 0, refsDone = 0;
+    detail::BamHeaderParser header;
     uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
     std::vector<unsigned char> head;            // host copy of the chunk's leading bytes (header phase only)
     auto have = [&](uint64_t n) {               // n more bytes from pos on, and on the host
@@ -1743,37 +1754,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
         }
         return true;
     };
-    auto parseHeader = [&]() -> bool {           // as in bamSubset
-        for (;;) {
-            if (phase == Magic) {
-                if (!have(8)) return false;
-                if (std::memcmp(head.data() + pos, "BAM\1", 4) != 0) throw std::runtime_error("input is not a BAM file");
-                ltext = le32(head.data() + pos + 4);
-                if (ltext > kMaxHeaderText) throw std::runtime_error("invalid BAM header text length");
-                phase = Text;
-            } else if (phase == Text) {
-                if (!have(8 + static_cast<uint64_t>(ltext) + 4)) return false;
-                nref = le32(head.data() + pos + 8 + ltext);
-                if (nref > 0x7fffffffu) throw std::runtime_error("invalid BAM reference count");
-                writer.write(head.data() + pos, 8 + static_cast<size_t>(ltext) + 4);
-                pos += 8 + static_cast<uint64_t>(ltext) + 4;
-                phase = Refs;
-            } else if (phase == Refs) {
-                if (refsDone == nref) { phase = Records; return true; }
-                if (!have(4)) return false;
-                const uint32_t lname = le32(head.data() + pos);
-                if (lname == 0 || lname > kMaxReferenceName) throw std::runtime_error("invalid BAM reference name length");
-                if (!have(4 + static_cast<uint64_t>(lname) + 4)) return false;
-                if (head[pos + 4 + lname - 1] != 0) throw std::runtime_error("BAM reference name is not NUL-terminated");
-                if (le32(head.data() + pos + 4 + lname) > 0x7fffffffu) throw std::runtime_error("invalid BAM reference length");
-                writer.write(head.data() + pos, 4 + static_cast<size_t>(lname) + 4);
-                pos += 4 + static_cast<uint64_t>(lname) + 4;
-                ++refsDone;
-            } else {
-                return true;
-            }
-        }
-    };
+    auto bytesAt = [&](uint64_t off) { return head.data() + pos + off; };
 
     std::vector<ts_bgzf_block> descs;
     std::vector<ts_bam_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), withSeq;
@@ -1827,7 +1808,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
         more = used > 0 && at < size;
         held = carry + produced; pos = 0;
         head.clear();
-        if (phase == Records || parseHeader()) {
+        if (header.done() || header.parse(have, bytesAt, pos, writer)) {
             head.clear(); head.shrink_to_fit();
             for (;;) {
                 uint64_t n = 0, next = 0, errorOff = 0;
@@ -1846,7 +1827,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
             }
         }
     }
-    if (phase != Records) throw std::runtime_error(phase == Refs ? "truncated BAM reference" : "truncated BAM header");
+    header.requireDone();
     if (held != pos) throw std::runtime_error(held - pos < 4 ? "truncated BAM record size" : "truncated BAM record");
     stats.missingEofBlock = !sawEofMarker;
     writer.finish();

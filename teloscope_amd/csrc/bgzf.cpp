@@ -1,6 +1,6 @@
 // bgzf.cpp — host side of the device BGZF route (include/teloscan.h: ts_bgzf_inflate): descriptor checks, staging, the
 // verdict.  Nothing here inflates: the members are decoded by bgzf.hip's kernel or not at all.
-#include "capi_internal.hpp"
+#include "chunk_internal.h"
 #include "bam_walk_core.h"
 
 #include <numeric>
@@ -74,25 +74,8 @@ extern "C" int ts_bgzf_inflate(ts_ctx *ctx, const void *compressed, uint64_t n, 
 }
 
 // ===================================================================== the resident form: a chunk of a BAM on the device
-// (struct ts_bam_chunk: capi_internal.hpp)
-int ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry_out) {
-    ts_ctx *ctx = ch->ctx;
-    const uint64_t carry = ch->plain_n - carry_from;
-    *carry_out = carry;
-    if (carry && carry_from) {                                   // the tail moves to the front (through a buffer where the two overlap)
-        char *p = (char *)ch->d_plain.p;
-        if (carry_from >= carry) HIP_TRY(ctx, hipMemcpyAsync(p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
-        else {
-            HIP_TRY(ctx, ch->d_tmp.ensure((size_t)carry));
-            HIP_TRY(ctx, hipMemcpyAsync(ch->d_tmp.p, p + carry_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(p, ch->d_tmp.p, (size_t)carry, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    return TS_OK;
-}
-
+// (struct ts_bam_chunk: chunk_internal.h; the object itself: chunk.cpp)
 namespace {
-hipError_t grow(DevBuf &b, size_t need) { return b.ensure(need); }
 struct DecodeJobHost { uint64_t src, dst; uint32_t n, pad; };
 constexpr uint32_t kDecodePiece = 2048;
 
@@ -106,34 +89,6 @@ bool record_ok(const ts_bam_chunk *ch, const ts_bam_record &r) {
 }  // namespace
 
 extern "C" {
-
-ts_bam_chunk *ts_bam_chunk_create(ts_ctx *ctx, uint64_t compressed_cap, uint64_t plain_cap) {
-    if (!ctx) return nullptr;
-    if (compressed_cap == 0 || plain_cap == 0 || compressed_cap > (1ull << 40) || plain_cap > (1ull << 40)) {
-        ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_create: capacities out of range");
-        return nullptr;
-    }
-    if (ctx->device == kNoDevice) { ctx->fail(TS_ERR_NO_DEVICE, "planning-only context: no HIP device behind it"); return nullptr; }
-    DeviceGuard guard(ctx->device);
-    if (guard.error() != hipSuccess) { ctx->fail(TS_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.error())); return nullptr; }
-    ts_bam_chunk *ch = new ts_bam_chunk();
-    ch->ctx = ctx; ch->comp_cap = compressed_cap; ch->plain_cap = plain_cap;
-    // (the kernels read whole aligned words: 64 readable bytes behind both buffers)
-    if (ch->d_comp.ensure((size_t)compressed_cap + 64) != hipSuccess || ch->d_plain.ensure((size_t)plain_cap + 64) != hipSuccess ||
-        ch->d_out.ensure(64) != hipSuccess || hipMemset((char *)ch->d_plain.p + plain_cap, 0, 64) != hipSuccess) {
-        ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_create: device allocation failed");
-        delete ch;
-        return nullptr;
-    }
-    return ch;
-}
-
-void ts_bam_chunk_destroy(ts_bam_chunk *ch) {
-    if (!ch) return;
-    DeviceGuard guard(ch->ctx->device);
-    (void)hipDeviceSynchronize();
-    delete ch;
-}
 
 int ts_bam_chunk_inflate(ts_bam_chunk *ch, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
                          uint64_t carry_from, void *stream) {
@@ -152,15 +107,15 @@ int ts_bam_chunk_inflate(ts_bam_chunk *ch, const void *compressed, uint64_t n, c
     ch->plain_n = end;
     ch->n_blocks = n_blocks;
     if (n_blocks) {
-        HIP_TRY(ctx, grow(ch->d_blocks, n_blocks * sizeof(ts_bgzf_block)));
-        HIP_TRY(ctx, grow(ch->d_result, n_blocks * 4));
+        HIP_TRY(ctx, ch->bam.d_blocks.ensure(n_blocks * sizeof(ts_bgzf_block)));
+        HIP_TRY(ctx, ch->bam.d_result.ensure(n_blocks * 4));
         if (n) HIP_TRY(ctx, hipMemcpyAsync(ch->d_comp.p, compressed, (size_t)n, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemsetAsync((char *)ch->d_comp.p + n, 0, 16, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ch->d_blocks.p, blocks, n_blocks * sizeof(ts_bgzf_block), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemsetAsync(ch->d_result.p, 0xff, n_blocks * 4, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ch->bam.d_blocks.p, blocks, n_blocks * sizeof(ts_bgzf_block), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync(ch->bam.d_result.p, 0xff, n_blocks * 4, st));
         // (the descriptors are the caller's memory: they have left it when this returns)
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (ts_k_launch_bgzf_inflate(ch->d_comp.p, ch->d_blocks.p, (uint32_t)n_blocks, ch->d_plain.p, (uint32_t *)ch->d_result.p, stream) != 0)
+        if (ts_k_launch_bgzf_inflate(ch->d_comp.p, ch->bam.d_blocks.p, (uint32_t)n_blocks, ch->d_plain.p, (uint32_t *)ch->bam.d_result.p, stream) != 0)
             return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_inflate: kernel launch failed");
     }
     return TS_OK;
@@ -174,23 +129,11 @@ int ts_bam_chunk_status(ts_bam_chunk *ch, ts_bgzf_status *first_bad) {
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (!ch->n_blocks) return TS_OK;
     std::vector<uint32_t> result(ch->n_blocks);
-    HIP_TRY(ctx, hipMemcpy(result.data(), ch->d_result.p, ch->n_blocks * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(result.data(), ch->bam.d_result.p, ch->n_blocks * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < ch->n_blocks; ++i) {
         if (result[i] > TS_BGZF_BAD_CRC) return ctx->fail(TS_ERR_STATE, "ts_bam_chunk_status: block " + std::to_string(i) + " was not judged");
         if (result[i] != TS_BGZF_OK) { first_bad->code = (int32_t)result[i]; first_bad->block = i; break; }
     }
-    return TS_OK;
-}
-
-uint64_t ts_bam_chunk_size(const ts_bam_chunk *ch) { return ch ? ch->plain_n : 0; }
-
-int ts_bam_chunk_read(ts_bam_chunk *ch, uint64_t off, uint64_t n, void *host) {
-    if (!ch) return TS_ERR_INVALID_ARG;
-    ts_ctx *ctx = ch->ctx;
-    if ((n && !host) || off > ch->plain_n || n > ch->plain_n - off) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_read: outside the chunk");
-    DEVICE_TRY(ctx);
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (n) HIP_TRY(ctx, hipMemcpy(host, (const char *)ch->d_plain.p + off, (size_t)n, hipMemcpyDeviceToHost));
     return TS_OK;
 }
 
@@ -201,7 +144,7 @@ int ts_bam_chunk_walk(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uint
     if (!n || !next || !error || !error_off || (cap && !recs) || from > ch->plain_n || cap > (1ull << 31))
         return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_walk: null or out-of-range argument");
     DEVICE_TRY(ctx);
-    HIP_TRY(ctx, grow(ch->d_recs, (size_t)std::max<uint64_t>(cap, 1) * sizeof(ts_bam_record)));
+    HIP_TRY(ctx, ch->d_recs.ensure((size_t)std::max<uint64_t>(cap, 1) * sizeof(ts_bam_record)));
     if (ts_k_launch_bam_walk(ch->d_plain.p, ch->plain_n, from, cap, ch->d_recs.p, ch->d_out.p, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_walk: kernel launch failed");
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -220,8 +163,8 @@ int ts_bam_chunk_set_index_geometry(ts_bam_chunk *ch, uint32_t span_bytes, uint3
         return ch->ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_set_index_geometry: span_bytes is a power of two of 64 .. 2^30, candidates 1 .. 8");
     uint32_t lg = 0;
     while ((1u << lg) < span_bytes) ++lg;
-    ch->index_span_log2 = lg;
-    ch->index_candidates = candidates;
+    ch->bam.index_span_log2 = lg;
+    ch->bam.index_candidates = candidates;
     return TS_OK;
 }
 
@@ -234,7 +177,7 @@ int ts_bam_chunk_index(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uin
     if (!n || !next || !error || !error_off || (cap && !recs) || from > ch->plain_n || cap > (1ull << 31))
         return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_index: null or out-of-range argument");
     DEVICE_TRY(ctx);
-    const uint32_t lg = ch->index_span_log2, K = ch->index_candidates;
+    const uint32_t lg = ch->bam.index_span_log2, K = ch->bam.index_candidates;
     const uint64_t size = ch->plain_n;
     ctx->bam_index_stats[0].fetch_add(1, std::memory_order_relaxed);
     *n = 0; *next = from; *error = TS_BAM_OK; *error_off = 0;
@@ -242,12 +185,12 @@ int ts_bam_chunk_index(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uin
     const uint64_t first = from >> lg, n_spans = ((size - 1) >> lg) - first + 1;
     if (n_spans > (1ull << 26)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_index: the span size is too small for this chunk");
     const size_t row_bytes = (size_t)n_spans * K * sizeof(tsbam::Row);
-    HIP_TRY(ctx, grow(ch->d_idx_rows, row_bytes));
-    if (ts_k_launch_bam_index_candidates(ch->d_plain.p, size, from, lg, K, first, (uint32_t)n_spans, ch->d_idx_rows.p, nullptr) != 0)
+    HIP_TRY(ctx, ch->bam.d_idx_rows.ensure(row_bytes));
+    if (ts_k_launch_bam_index_candidates(ch->d_plain.p, size, from, lg, K, first, (uint32_t)n_spans, ch->bam.d_idx_rows.p, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_index: kernel launch failed");
-    ch->h_idx_rows.resize(row_bytes);
-    HIP_TRY(ctx, hipMemcpy(ch->h_idx_rows.data(), ch->d_idx_rows.p, row_bytes, hipMemcpyDeviceToHost));     // (waits for the kernel)
-    const tsbam::Row *rows = (const tsbam::Row *)ch->h_idx_rows.data();
+    ch->bam.h_idx_rows.resize(row_bytes);
+    HIP_TRY(ctx, hipMemcpy(ch->bam.h_idx_rows.data(), ch->bam.d_idx_rows.p, row_bytes, hipMemcpyDeviceToHost));     // (waits for the kernel)
+    const tsbam::Row *rows = (const tsbam::Row *)ch->bam.h_idx_rows.data();
     std::vector<tsbam::Task> tasks;
     hipError_t bad = hipSuccess;
     int launch_failed = 0;
@@ -275,10 +218,10 @@ int ts_bam_chunk_index(ts_bam_chunk *ch, uint64_t from, ts_bam_record *recs, uin
     unsigned long long next_at = c.next;
     if (c.n) {
         // (the write pass is told c.n, not cap: it stores nothing beyond what the chain counted, whatever it meets)
-        HIP_TRY(ctx, grow(ch->d_recs, (size_t)c.n * sizeof(ts_bam_record)));
-        HIP_TRY(ctx, grow(ch->d_idx_tasks, tasks.size() * sizeof(tsbam::Task)));
-        HIP_TRY(ctx, hipMemcpy(ch->d_idx_tasks.p, tasks.data(), tasks.size() * sizeof(tsbam::Task), hipMemcpyHostToDevice));
-        if (ts_k_launch_bam_index_write(ch->d_plain.p, size, ch->d_idx_tasks.p, (uint32_t)tasks.size(), lg, c.n, ch->d_recs.p, ch->d_out.p, nullptr) != 0)
+        HIP_TRY(ctx, ch->d_recs.ensure((size_t)c.n * sizeof(ts_bam_record)));
+        HIP_TRY(ctx, ch->bam.d_idx_tasks.ensure(tasks.size() * sizeof(tsbam::Task)));
+        HIP_TRY(ctx, hipMemcpy(ch->bam.d_idx_tasks.p, tasks.data(), tasks.size() * sizeof(tsbam::Task), hipMemcpyHostToDevice));
+        if (ts_k_launch_bam_index_write(ch->d_plain.p, size, ch->bam.d_idx_tasks.p, (uint32_t)tasks.size(), lg, c.n, ch->d_recs.p, ch->d_out.p, nullptr) != 0)
             return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_index: kernel launch failed");
         HIP_TRY(ctx, hipMemcpy(recs, ch->d_recs.p, (size_t)c.n * sizeof(ts_bam_record), hipMemcpyDeviceToHost));
         if (c.next_in_span) {
@@ -320,23 +263,12 @@ int ts_bam_chunk_decode(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, t
     hipStream_t st = (hipStream_t)stream;
     // (a fresh input buffer was just zeroed on the null stream, which a non-blocking `stream` does not wait for)
     if (fresh && st) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-    HIP_TRY(ctx, grow(ch->d_jobs, jobs.size() * sizeof(DecodeJobHost)));
-    HIP_TRY(ctx, hipMemcpyAsync(ch->d_jobs.p, jobs.data(), jobs.size() * sizeof(DecodeJobHost), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, ch->bam.d_jobs.ensure(jobs.size() * sizeof(DecodeJobHost)));
+    HIP_TRY(ctx, hipMemcpyAsync(ch->bam.d_jobs.p, jobs.data(), jobs.size() * sizeof(DecodeJobHost), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (ts_k_launch_bam_decode(ch->d_plain.p, ch->d_jobs.p, (uint32_t)jobs.size(), in, stream) != 0)
+    if (ts_k_launch_bam_decode(ch->d_plain.p, ch->bam.d_jobs.p, (uint32_t)jobs.size(), in, stream) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_decode: kernel launch failed");
     return TS_OK;
-}
-
-void *ts_bam_chunk_pass_buffer(ts_bam_chunk *ch, uint64_t n) {
-    if (!ch || n > (1ull << 40)) return nullptr;
-    ts_ctx *ctx = ch->ctx;
-    DeviceGuard guard(ctx->device);
-    if (guard.error() != hipSuccess || hipDeviceSynchronize() != hipSuccess || grow(ch->d_pass, (size_t)n) != hipSuccess) {
-        ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_pass_buffer: device allocation failed");
-        return nullptr;
-    }
-    return ch->d_pass.p;
 }
 
 int ts_bam_chunk_gather(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, const void *d_pass, void *host_out, uint64_t cap,
@@ -347,29 +279,8 @@ int ts_bam_chunk_gather(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, c
         return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather: null or out-of-range argument");
     for (size_t i = 0; i < n; ++i)
         if (!record_ok(ch, recs[i])) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather: record " + std::to_string(i) + " does not fit the chunk");
-    *bytes = 0; *n_passed = 0;
-    if (n == 0) return TS_OK;
-    DEVICE_TRY(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(ctx, grow(ch->d_recs, n * sizeof(ts_bam_record)));
-    HIP_TRY(ctx, grow(ch->d_dst, n * 8));
-    HIP_TRY(ctx, hipMemcpyAsync(ch->d_recs.p, recs, n * sizeof(ts_bam_record), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    unsigned long long *totals = (unsigned long long *)ch->d_out.p + 4;
-    if (ts_k_launch_bam_gather_plan(ch->d_recs.p, d_pass, n, ch->d_dst.p, totals, stream) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_gather: kernel launch failed");
-    unsigned long long t[2];
-    HIP_TRY(ctx, hipMemcpyAsync(t, totals, sizeof t, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    *bytes = t[0]; *n_passed = t[1];
-    if (t[0] > cap) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather: host_out is too small (*bytes says what is needed)");
-    if (t[0] == 0) return TS_OK;
-    HIP_TRY(ctx, grow(ch->d_gather, (size_t)t[0]));
-    if (ts_k_launch_bam_gather(ch->d_plain.p, ch->d_recs.p, ch->d_dst.p, n, t[0], ch->d_gather.p, stream) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_gather: kernel launch failed");
-    HIP_TRY(ctx, hipMemcpyAsync(host_out, ch->d_gather.p, (size_t)t[0], hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return TS_OK;
+    return ts_chunk_gather(ch, "ts_bam_chunk_gather", recs, sizeof(ts_bam_record), n, d_pass, host_out, cap, bytes, n_passed, stream,
+                           ts_k_launch_chunk_gather_plan_bam, ts_k_launch_bam_gather);
 }
 
 }  // extern "C"

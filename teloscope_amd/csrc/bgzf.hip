@@ -21,6 +21,7 @@
 
 #include "../../include/teloscan.h"
 #include "bam_walk_core.h"
+#include "chunk_device.h"
 #include "inflate_core.h"
 #include "ts_device.h"
 #include "ts_internal.h"
@@ -388,38 +389,15 @@ void ts_bam_decode_seq_kernel(const unsigned char *plain, const DecodeJob *jobs,
             o[2 * h] = nibbles_to_letters(__builtin_amdgcn_perm(lo, hi, 0x05010400u));
             o[2 * h + 1] = nibbles_to_letters(__builtin_amdgcn_perm(lo, hi, 0x07030602u));
         }
-        if (bases < 16u) {                                      // the bytes behind the read stay zero, as an upload leaves them
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t left = bases > 4u * q ? bases - 4u * q : 0u;
-                o[q] &= left >= 4u ? 0xffffffffu : left == 0u ? 0u : (1u << (8u * left)) - 1u;
-            }
-        }
+        if (bases < 16u) zero_tail16(o, bases);                 // the bytes behind the read stay zero, as an upload leaves them
         *(uint4 *)(dst + i) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
 
-// ---- passing records, in input order, into one contiguous buffer: a prefix sum over 4 + block_size of the records whose pass
-// byte is set (one wave, 64 records per step), then a wave per passing record copies it.
-__global__ __launch_bounds__(64)
-void ts_bam_gather_plan_kernel(const ts_bam_record *recs, const unsigned char *pass, unsigned long long n,
-                               unsigned long long *dst_off, unsigned long long *totals) {
-    unsigned long long run = 0, kept = 0;
-    for (unsigned long long base = 0; base < n; base += 64ull) {
-        const unsigned long long i = base + threadIdx.x;
-        const bool keep = i < n && pass[i] != 0;
-        const uint32_t size = keep ? 4u + recs[i].block_size : 0u;
-        // (a step's sizes are summed in two halves of 32 bits: 64 records of up to 256 MiB)
-        const uint32_t incl_lo = wave_scan_add(size & 0xffffu), incl_hi = wave_scan_add(size >> 16);
-        const unsigned long long incl = (unsigned long long)incl_lo + ((unsigned long long)incl_hi << 16);
-        if (i < n) dst_off[i] = keep ? run + incl - size : ~0ull;
-        run += (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)incl_lo, 63) +
-               ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)incl_hi, 63) << 16);
-        kept += (unsigned long long)__popcll(ballot64(keep));
-    }
-    if (threadIdx.x == 0) { totals[0] = run; totals[1] = kept; }
-}
-
+// ---- passing records, in input order, into one contiguous buffer, at the places chunk.hip's plan gave them: a wave per passing
+// record copies it as the FASTQ gather does (chunk_device.h: copy_record16).  The copy reads up to 19 bytes beyond a record's
+// last byte (load16_any's five aligned dwords) and stores none: they lie inside the 64 readable bytes every chunk's plain buffer
+// has behind its capacity (chunk.cpp: ts_bam_chunk_create, ts_chunk_reserve), and `out` is written in [to, to + size) only.
 __global__ __launch_bounds__(64)
 void ts_bam_gather_kernel(const unsigned char *plain, const ts_bam_record *recs, const unsigned long long *dst_off,
                           unsigned long long n, unsigned long long cap, unsigned char *out) {
@@ -427,10 +405,9 @@ void ts_bam_gather_kernel(const unsigned char *plain, const ts_bam_record *recs,
     if (i >= n) return;
     const unsigned long long to = dst_off[i];
     if (to == ~0ull) return;
-    const unsigned long long size = 4ull + recs[i].block_size;
+    const uint32_t size = 4u + recs[i].block_size;              // (block_size <= 256 MiB: the host checked the table)
     if (to > cap || size > cap - to) return;                    // (the caller has compared the total with cap already)
-    const unsigned char *src = plain + recs[i].off;
-    for (unsigned long long j = threadIdx.x; j < size; j += 64ull) out[to + j] = src[j];
+    copy_record16(out + to, plain + recs[i].off, size, to);
 }
 
 }  // namespace
@@ -469,12 +446,6 @@ int ts_k_launch_bam_decode(const void *plain, const void *jobs, uint32_t n_jobs,
     if (n_jobs == 0) return 0;
     hipLaunchKernelGGL(ts_bam_decode_seq_kernel, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain,
                        (const DecodeJob *)jobs, n_jobs, (unsigned char *)in);
-    return (int)hipGetLastError();
-}
-
-int ts_k_launch_bam_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream) {
-    hipLaunchKernelGGL(ts_bam_gather_plan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const ts_bam_record *)recs,
-                       (const unsigned char *)pass, n, (unsigned long long *)dst_off, (unsigned long long *)totals);
     return (int)hipGetLastError();
 }
 

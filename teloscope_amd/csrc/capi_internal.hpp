@@ -500,34 +500,6 @@ void ts_match_text_begin(const ts_ctx *c, ts_match_text *t);    // a caller's st
 int  ts_matches_append(ts_ctx *c, const TsMatchSource &src, const ts_match_line_segment *segs, size_t n_segs, const char *names,
                        uint64_t names_len, hipStream_t st, ts_match_text *out);
 
-// bgzf.cpp: a chunk of an uncompressed stream resident on the device (ts_bam_chunk_*; ts_chunk is the same type: fastq.cpp)
-struct ts_bam_chunk {
-    ts_ctx *ctx = nullptr;
-    uint64_t comp_cap = 0, plain_cap = 0;
-    uint64_t plain_n = 0;               // bytes the chunk holds: the carried tail, then the members' output
-    size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status
-    DevBuf d_comp, d_plain, d_blocks, d_result, d_tmp, d_recs, d_out, d_jobs, d_dst, d_gather, d_pass;
-    // the parallel record index (ts_bam_chunk_index): its span size (log2) and candidates per span, the candidate rows, the tasks
-    // of the write pass, and the host copy of the rows
-    uint32_t index_span_log2 = 18, index_candidates = 4;
-    DevBuf d_idx_rows, d_idx_tasks;
-    std::vector<unsigned char> h_idx_rows;
-    DevBuf d_lines, d_waves, d_frames;  // the FASTQ walk's line index, per-slice newline counts and framing results (fastq.cpp)
-    // FASTA (fasta.cpp): the walk's header table, record table and names; the join's jobs, their counts, the joined bases and runs
-    DevBuf d_fa_heads, d_fa_recs, d_fa_names, d_fa_jobs, d_fa_counts, d_fa_bases, d_fa_runs, d_fa_out;
-    uint64_t fa_joined = 0, fa_runs = 0;          // bytes of the last join, its runs
-    // GFA (gfa.cpp): the tab counts per slice and the tabs' offsets, the lines' kind bytes and their per-slice counts, the two
-    // tables and the gathered text
-    DevBuf d_gfa_counts, d_gfa_tabs, d_gfa_kinds, d_gfa_frames, d_gfa_segs, d_gfa_lines, d_gfa_text, d_gfa_out;
-    // assembly record filters: a byte per record of the strict FASTA check; of the GFA check the lines' stray-'\r' and code bytes,
-    // the flagged lines per slice, their total and the flagged table.  What the last GFA walk indexed (ts_gfa_chunk_check works on
-    // that line and tab index; another line index over the chunk ends its validity)
-    DevBuf d_fa_strict, d_gfa_stray, d_gfa_codes, d_gfa_ccounts, d_gfa_cout, d_gfa_flagged;
-    bool gfa_walked = false;
-    int gfa_at_end = 0;
-    uint64_t gfa_size = 0, gfa_newlines = 0, gfa_n_lines = 0, gfa_n_tabs = 0;
-};
-// the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
-int  ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry);
+// (struct ts_bam_chunk, the chunk of the device routes: chunk_internal.h)
 
 #endif

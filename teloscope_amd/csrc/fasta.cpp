@@ -1,9 +1,9 @@
 // fasta.cpp — host side of the device FASTA stages (include/teloscan.h: ts_fasta_chunk_*): argument checks, buffer sizes, the
 // job lists of the join and the run search (a job per 16 KB of a record: arithmetic on the record table), launches and the few
-// words that come back.  The chunk is bgzf.cpp's ts_bam_chunk, its line index fastq.hip's; nothing here parses a byte of text.
-#include "capi_internal.hpp"
+// words that come back.  The chunk and its line index are the chunk layer's (chunk_internal.h); nothing here parses a byte of
+// text.
+#include "chunk_internal.h"
 #include "fasta_internal.h"
-#include "fastq_internal.h"
 
 namespace {
 
@@ -17,9 +17,9 @@ bool record_ok(const ts_bam_chunk *ch, const ts_fasta_record &r) {
 }
 
 int ensure_out(ts_bam_chunk *ch) {
-    if (ch->d_fa_out.p) return TS_OK;
+    if (ch->fasta.d_out.p) return TS_OK;
     ts_ctx *ctx = ch->ctx;
-    HIP_TRY(ctx, ch->d_fa_out.ensure(64));
+    HIP_TRY(ctx, ch->fasta.d_out.ensure(64));
     return TS_OK;
 }
 
@@ -39,12 +39,12 @@ int ts_fasta_chunk_walk(ts_chunk *ch, int at_end, ts_fasta_record *recs, uint64_
     if (size == 0) return TS_OK;
     DEVICE_TRY(ctx);
     { const int rc = ensure_out(ch); if (rc != TS_OK) return rc; }
-    unsigned long long *d_out = (unsigned long long *)ch->d_fa_out.p;
+    unsigned long long *d_out = (unsigned long long *)ch->fasta.d_out.p;
     unsigned long long out[kFaWords];
     static_assert(sizeof out <= 64, "the result block has 64 bytes");
 
-    // lines: the FASTQ walk's index ('\n' per slice, their sums, every line's start, first byte and '\r')
-    FastqLineIndex ix;
+    // lines: the chunk's line index ('\n' per slice, their sums, every line's start, first byte and '\r')
+    LineIndex ix;
     { const int rc = ts_chunk_line_index(ch, at_end, "ts_fasta_chunk_walk", "line", &ix); if (rc != TS_OK) return rc; }
     const uint64_t newlines = ix.newlines, n_lines = ix.n_lines;
     uint32_t *lstart = ix.lstart;
@@ -52,8 +52,8 @@ int ts_fasta_chunk_walk(ts_chunk *ch, int at_end, ts_fasta_record *recs, uint64_
 
     // header lines: per slice of lines, their sums, every header's place
     const uint64_t n_frames = ceil_div(n_lines, kFastaSliceLines);
-    HIP_TRY(ctx, ch->d_frames.ensure((size_t)std::max<uint64_t>(n_frames, 1) * sizeof(FastaFrame)));
-    if (ts_k_launch_fasta_frames(lstart, first, cr, (uint32_t)n_lines, (uint32_t)newlines, ch->d_frames.p, d_out, nullptr) != 0)
+    HIP_TRY(ctx, ch->fasta.d_frames.ensure((size_t)std::max<uint64_t>(n_frames, 1) * sizeof(FastaFrame)));
+    if (ts_k_launch_fasta_frames(lstart, first, cr, (uint32_t)n_lines, (uint32_t)newlines, ch->fasta.d_frames.p, d_out, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_walk: kernel launch failed");
     HIP_TRY(ctx, hipMemcpy(out, d_out, sizeof out, hipMemcpyDeviceToHost));
     const uint64_t heads = out[kFaHeaders], all_names = out[kFaNameBytes];
@@ -63,13 +63,13 @@ int ts_fasta_chunk_walk(ts_chunk *ch, int at_end, ts_fasta_record *recs, uint64_
         *next = at_end ? size : out[kFaLastLine];
         return TS_OK;
     }
-    HIP_TRY(ctx, ch->d_fa_heads.ensure((size_t)(heads + 1) * sizeof(FastaHead)));
-    HIP_TRY(ctx, ch->d_fa_recs.ensure((size_t)heads * sizeof(ts_fasta_record)));
-    HIP_TRY(ctx, ch->d_fa_names.ensure((size_t)std::max<uint64_t>(all_names, 1)));
-    if (ts_k_launch_fasta_heads(lstart, first, cr, (uint32_t)n_lines, ch->d_frames.p, ch->d_fa_heads.p, (uint32_t)heads,
+    HIP_TRY(ctx, ch->fasta.d_heads.ensure((size_t)(heads + 1) * sizeof(FastaHead)));
+    HIP_TRY(ctx, ch->fasta.d_recs.ensure((size_t)heads * sizeof(ts_fasta_record)));
+    HIP_TRY(ctx, ch->fasta.d_names.ensure((size_t)std::max<uint64_t>(all_names, 1)));
+    if (ts_k_launch_fasta_heads(lstart, first, cr, (uint32_t)n_lines, ch->fasta.d_frames.p, ch->fasta.d_heads.p, (uint32_t)heads,
                                 (uint32_t)out[kFaCrs], (uint32_t)all_names, nullptr) != 0 ||
-        ts_k_launch_fasta_records(ch->d_plain.p, size, lstart, cr, ch->d_fa_heads.p, (uint32_t)heads, ch->d_fa_recs.p,
-                                  ch->d_fa_names.p, nullptr) != 0)
+        ts_k_launch_fasta_records(ch->d_plain.p, size, lstart, cr, ch->fasta.d_heads.p, (uint32_t)heads, ch->fasta.d_recs.p,
+                                  ch->fasta.d_names.p, nullptr) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_walk: kernel launch failed");
 
     // without at_end the last record is open: the next chunk may continue it
@@ -78,7 +78,7 @@ int ts_fasta_chunk_walk(ts_chunk *ch, int at_end, ts_fasta_record *recs, uint64_
     *next = size;
     if (whole < heads) {
         ts_fasta_record open;
-        HIP_TRY(ctx, hipMemcpy(&open, (const ts_fasta_record *)ch->d_fa_recs.p + whole, sizeof open, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(&open, (const ts_fasta_record *)ch->fasta.d_recs.p + whole, sizeof open, hipMemcpyDeviceToHost));
         if (open.off > size || open.name_at > all_names) return ctx->fail(TS_ERR_STATE, "ts_fasta_chunk_walk: the walk left the chunk");
         *next = open.off;
         name_bytes = open.name_at;
@@ -87,8 +87,8 @@ int ts_fasta_chunk_walk(ts_chunk *ch, int at_end, ts_fasta_record *recs, uint64_
     *names_bytes = name_bytes;
     if (whole > cap || name_bytes > names_cap)
         return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_walk: the table or the names buffer is too small (*n and *names_bytes say what is needed)");
-    if (whole) HIP_TRY(ctx, hipMemcpy(recs, ch->d_fa_recs.p, (size_t)whole * sizeof(ts_fasta_record), hipMemcpyDeviceToHost));
-    if (name_bytes) HIP_TRY(ctx, hipMemcpy(names, ch->d_fa_names.p, (size_t)name_bytes, hipMemcpyDeviceToHost));
+    if (whole) HIP_TRY(ctx, hipMemcpy(recs, ch->fasta.d_recs.p, (size_t)whole * sizeof(ts_fasta_record), hipMemcpyDeviceToHost));
+    if (name_bytes) HIP_TRY(ctx, hipMemcpy(names, ch->fasta.d_names.p, (size_t)name_bytes, hipMemcpyDeviceToHost));
     return TS_OK;
 }
 
@@ -100,7 +100,7 @@ int ts_fasta_chunk_join(ts_chunk *ch, const ts_fasta_record *recs, size_t n, int
         return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_join: null or out-of-range argument");
     if (ch->plain_n >= 0xffffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_join: the chunk holds 4 GiB or more");
     *d_bases = nullptr; *total_bytes = 0; *n_runs = 0;
-    ch->fa_joined = 0; ch->fa_runs = 0;
+    ch->fasta.joined = 0; ch->fasta.runs = 0;
     const uint64_t size = ch->plain_n;
     // where every record goes, and the jobs: a record's body text and its joined bases, each cut at multiples of 16 KB
     std::vector<FastaJoinJob> jobs;
@@ -128,29 +128,29 @@ int ts_fasta_chunk_join(ts_chunk *ch, const ts_fasta_record *recs, size_t n, int
     DEVICE_TRY(ctx);
     { const int rc = ensure_out(ch); if (rc != TS_OK) return rc; }
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long *d_totals = (unsigned long long *)ch->d_fa_out.p + kFaTotal;      // {kept bytes, runs}
-    HIP_TRY(ctx, ch->d_fa_bases.ensure((size_t)total + 64));
-    HIP_TRY(ctx, hipMemsetAsync((char *)ch->d_fa_bases.p + total, 0, 64, st));           // (readable, and zero, behind the last record)
-    *d_bases = ch->d_fa_bases.p;
+    unsigned long long *d_totals = (unsigned long long *)ch->fasta.d_out.p + kFaTotal;      // {kept bytes, runs}
+    HIP_TRY(ctx, ch->fasta.d_bases.ensure((size_t)total + 64));
+    HIP_TRY(ctx, hipMemsetAsync((char *)ch->fasta.d_bases.p + total, 0, 64, st));           // (readable, and zero, behind the last record)
+    *d_bases = ch->fasta.d_bases.p;
     *total_bytes = total;
-    ch->fa_joined = total;
+    ch->fasta.joined = total;
     if (n == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); return TS_OK; }
     // both job lists and the table go up together; both count passes and their sums run before the one wait for the totals
     const size_t n_jobs = jobs.size(), n_rjobs = run_jobs.size();
-    HIP_TRY(ctx, ch->d_fa_recs.ensure(n * sizeof(ts_fasta_record)));
-    HIP_TRY(ctx, ch->d_fa_jobs.ensure(std::max<size_t>(1, n_jobs * sizeof(FastaJoinJob) + n_rjobs * sizeof(FastaRunJob))));
-    HIP_TRY(ctx, ch->d_fa_counts.ensure(std::max<size_t>(1, n_jobs + n_rjobs) * 4));
-    void *d_jobs = ch->d_fa_jobs.p, *d_rjobs = (char *)ch->d_fa_jobs.p + n_jobs * sizeof(FastaJoinJob);
-    uint32_t *counts = (uint32_t *)ch->d_fa_counts.p, *rcounts = counts + n_jobs;
-    HIP_TRY(ctx, hipMemcpyAsync(ch->d_fa_recs.p, recs, n * sizeof(ts_fasta_record), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, ch->fasta.d_recs.ensure(n * sizeof(ts_fasta_record)));
+    HIP_TRY(ctx, ch->fasta.d_jobs.ensure(std::max<size_t>(1, n_jobs * sizeof(FastaJoinJob) + n_rjobs * sizeof(FastaRunJob))));
+    HIP_TRY(ctx, ch->fasta.d_counts.ensure(std::max<size_t>(1, n_jobs + n_rjobs) * 4));
+    void *d_jobs = ch->fasta.d_jobs.p, *d_rjobs = (char *)ch->fasta.d_jobs.p + n_jobs * sizeof(FastaJoinJob);
+    uint32_t *counts = (uint32_t *)ch->fasta.d_counts.p, *rcounts = counts + n_jobs;
+    HIP_TRY(ctx, hipMemcpyAsync(ch->fasta.d_recs.p, recs, n * sizeof(ts_fasta_record), hipMemcpyHostToDevice, st));
     if (n_jobs) HIP_TRY(ctx, hipMemcpyAsync(d_jobs, jobs.data(), n_jobs * sizeof(FastaJoinJob), hipMemcpyHostToDevice, st));
     if (n_rjobs) HIP_TRY(ctx, hipMemcpyAsync(d_rjobs, run_jobs.data(), n_rjobs * sizeof(FastaRunJob), hipMemcpyHostToDevice, st));
     // join: count, sum, write; runs: count, sum
     if (ts_k_launch_fasta_join_count(ch->d_plain.p, size, at_end, d_jobs, (uint32_t)n_jobs, counts, stream) != 0 ||
-        ts_k_launch_fasta_scan(counts, (uint32_t)n_jobs, d_totals, stream) != 0 ||
-        ts_k_launch_fasta_join_write(ch->d_plain.p, size, at_end, d_jobs, (uint32_t)n_jobs, counts, ch->d_fa_bases.p, stream) != 0 ||
-        ts_k_launch_fasta_run_count(ch->d_fa_bases.p, d_rjobs, (uint32_t)n_rjobs, rcounts, stream) != 0 ||
-        ts_k_launch_fasta_scan(rcounts, (uint32_t)n_rjobs, d_totals + 1, stream) != 0)
+        ts_k_launch_chunk_scan(counts, (uint32_t)n_jobs, d_totals, stream) != 0 ||
+        ts_k_launch_fasta_join_write(ch->d_plain.p, size, at_end, d_jobs, (uint32_t)n_jobs, counts, ch->fasta.d_bases.p, stream) != 0 ||
+        ts_k_launch_fasta_run_count(ch->fasta.d_bases.p, d_rjobs, (uint32_t)n_rjobs, rcounts, stream) != 0 ||
+        ts_k_launch_chunk_scan(rcounts, (uint32_t)n_rjobs, d_totals + 1, stream) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_join: kernel launch failed");
     unsigned long long totals[2] = {0, 0}, bases = 0;
     HIP_TRY(ctx, hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, st));
@@ -160,12 +160,12 @@ int ts_fasta_chunk_join(ts_chunk *ch, const ts_fasta_record *recs, size_t n, int
     if (kept != bases) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_join: the records are not the chunk's (their text holds " + std::to_string(kept) + " bases, the table says " + std::to_string(bases) + ")");
     if (runs > total) return ctx->fail(TS_ERR_STATE, "ts_fasta_chunk_join: more runs than bases");
     // runs: write, lengths
-    HIP_TRY(ctx, ch->d_fa_runs.ensure((size_t)std::max<unsigned long long>(runs, 1) * sizeof(ts_fasta_run)));
-    if (ts_k_launch_fasta_run_write(ch->d_fa_bases.p, d_rjobs, (uint32_t)n_rjobs, rcounts, ch->d_fa_runs.p, runs, stream) != 0 ||
-        ts_k_launch_fasta_run_lengths(ch->d_fa_runs.p, runs, ch->d_fa_recs.p, (uint32_t)n, stream) != 0)
+    HIP_TRY(ctx, ch->fasta.d_runs.ensure((size_t)std::max<unsigned long long>(runs, 1) * sizeof(ts_fasta_run)));
+    if (ts_k_launch_fasta_run_write(ch->fasta.d_bases.p, d_rjobs, (uint32_t)n_rjobs, rcounts, ch->fasta.d_runs.p, runs, stream) != 0 ||
+        ts_k_launch_fasta_run_lengths(ch->fasta.d_runs.p, runs, ch->fasta.d_recs.p, (uint32_t)n, stream) != 0)
         return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_join: kernel launch failed");
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    ch->fa_runs = runs;
+    ch->fasta.runs = runs;
     *n_runs = runs;
     return TS_OK;
 }
@@ -192,15 +192,15 @@ int ts_fasta_chunk_strict(ts_chunk *ch, const ts_fasta_record *recs, size_t n, u
     if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_strict: too much text for one call");
     DEVICE_TRY(ctx);
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(ctx, ch->d_fa_strict.ensure(n));
-    HIP_TRY(ctx, hipMemsetAsync(ch->d_fa_strict.p, 0, n, st));
+    HIP_TRY(ctx, ch->fasta.d_strict.ensure(n));
+    HIP_TRY(ctx, hipMemsetAsync(ch->fasta.d_strict.p, 0, n, st));
     if (!jobs.empty()) {
-        HIP_TRY(ctx, ch->d_fa_jobs.ensure(jobs.size() * sizeof(FastaStrictJob)));
-        HIP_TRY(ctx, hipMemcpyAsync(ch->d_fa_jobs.p, jobs.data(), jobs.size() * sizeof(FastaStrictJob), hipMemcpyHostToDevice, st));
-        if (ts_k_launch_fasta_strict(ch->d_plain.p, ch->plain_n, ch->d_fa_jobs.p, (uint32_t)jobs.size(), (unsigned char *)ch->d_fa_strict.p, stream) != 0)
+        HIP_TRY(ctx, ch->fasta.d_jobs.ensure(jobs.size() * sizeof(FastaStrictJob)));
+        HIP_TRY(ctx, hipMemcpyAsync(ch->fasta.d_jobs.p, jobs.data(), jobs.size() * sizeof(FastaStrictJob), hipMemcpyHostToDevice, st));
+        if (ts_k_launch_fasta_strict(ch->d_plain.p, ch->plain_n, ch->fasta.d_jobs.p, (uint32_t)jobs.size(), (unsigned char *)ch->fasta.d_strict.p, stream) != 0)
             return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_strict: kernel launch failed");
     }
-    HIP_TRY(ctx, hipMemcpyAsync(has_sequence, ch->d_fa_strict.p, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(has_sequence, ch->fasta.d_strict.p, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                    // (the job list was this call's memory: it has left it too)
     return TS_OK;
 }
@@ -209,21 +209,21 @@ int ts_fasta_chunk_runs(ts_chunk *ch, ts_fasta_run *runs, uint64_t cap, uint64_t
     if (!ch) return TS_ERR_INVALID_ARG;
     ts_ctx *ctx = ch->ctx;
     if (!n_runs || (cap && !runs)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_runs: null argument");
-    *n_runs = ch->fa_runs;
-    if (ch->fa_runs > cap) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_runs: the table is too small (*n_runs says what is needed)");
-    if (ch->fa_runs == 0) return TS_OK;
+    *n_runs = ch->fasta.runs;
+    if (ch->fasta.runs > cap) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_runs: the table is too small (*n_runs says what is needed)");
+    if (ch->fasta.runs == 0) return TS_OK;
     DEVICE_TRY(ctx);                                           // (the join waited for its stream: a blocking copy is all it takes)
-    HIP_TRY(ctx, hipMemcpy(runs, ch->d_fa_runs.p, (size_t)ch->fa_runs * sizeof(ts_fasta_run), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(runs, ch->fasta.d_runs.p, (size_t)ch->fasta.runs * sizeof(ts_fasta_run), hipMemcpyDeviceToHost));
     return TS_OK;
 }
 
 int ts_fasta_chunk_bases(ts_chunk *ch, uint64_t off, uint64_t n, void *host) {
     if (!ch) return TS_ERR_INVALID_ARG;
     ts_ctx *ctx = ch->ctx;
-    if ((n && !host) || off > ch->fa_joined || n > ch->fa_joined - off) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_bases: outside the joined bases");
+    if ((n && !host) || off > ch->fasta.joined || n > ch->fasta.joined - off) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_bases: outside the joined bases");
     if (n == 0) return TS_OK;
     DEVICE_TRY(ctx);
-    HIP_TRY(ctx, hipMemcpy(host, (const char *)ch->d_fa_bases.p + off, (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(host, (const char *)ch->fasta.d_bases.p + off, (size_t)n, hipMemcpyDeviceToHost));
     return TS_OK;
 }
 

@@ -1,6 +1,6 @@
-// fasta.hip — FASTA text of a resident chunk (bgzf.cpp's ts_bam_chunk) turned into a record table, the records' header lines,
-// their bases joined into one buffer and the runs of gap letters, on the device.  One-wave workgroups throughout, like
-// fastq.hip's, whose line index (count, count-scan, index) runs in front of everything here, unchanged.
+// fasta.hip — FASTA text of a resident chunk (chunk_internal.h) turned into a record table, the records' header lines, their
+// bases joined into one buffer and the runs of gap letters, on the device.  One-wave workgroups throughout, like fastq.hip's.
+// The chunk layer's line index (chunk.hip) runs in front of everything here; the sums of the counts are its scan.
 //
 //   * records: a header line is a line whose first byte is '>'.  A wave per 2 048 lines counts the header lines, the lines
 //     that end in "\r\n" and the bytes of the headers' names; one wave sums the counts; a second pass gives every header line
@@ -18,21 +18,12 @@
 #include <stdint.h>
 
 #include "../../include/teloscan.h"
+#include "chunk_device.h"
 #include "fasta_internal.h"
 #include "ts_device.h"
 
 namespace {
 
-// the bytes of w that equal the byte repeated in c4, a bit per byte (bits 0..3).  t has bit 7 of every byte that is zero in x
-// (exact per byte: no carry leaves a byte); the multiply moves bit 8 i + 7 to bit 24 + i
-__device__ __forceinline__ uint32_t eq_bits(uint32_t w, uint32_t c4) {
-    const uint32_t x = w ^ c4;
-    const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
-    return (((t >> 7) * 0x01020408u) >> 24) & 15u;
-}
-__device__ __forceinline__ uint32_t eq_mask16(uint4 q, uint32_t c4) {
-    return eq_bits(q.x, c4) | eq_bits(q.y, c4) << 4 | eq_bits(q.z, c4) << 8 | eq_bits(q.w, c4) << 12;
-}
 // bits [lo, hi) of a 16-bit mask (0 <= lo, hi <= 16)
 __device__ __forceinline__ uint32_t bit_range(uint32_t lo, uint32_t hi) { return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u; }
 
@@ -145,7 +136,7 @@ __device__ __forceinline__ uint32_t keep_mask16(const unsigned char *plain, unsi
     if (p >= z || p + 16ull <= a) return 0u;
     q = *(const uint4 *)(plain + p);                           // (the chunk's buffer is readable 64 bytes beyond its capacity)
     const uint32_t in_chunk = size - p >= 16ull ? 0xffffu : (1u << (uint32_t)(size - p)) - 1u;
-    const uint32_t lf = eq_mask16(q, 0x0a0a0a0au) & in_chunk, cr = eq_mask16(q, 0x0d0d0d0du);
+    const uint32_t lf = byte_eq_mask16(q, 0x0a0a0a0au) & in_chunk, cr = byte_eq_mask16(q, 0x0d0d0d0du);
     const uint32_t lf_next = (lf >> 1) | (p + 16ull < size && plain[p + 16ull] == '\n' ? 0x8000u : 0u);
     uint32_t drop = lf | (cr & lf_next);
     if (at_end && size - 1ull >= p && size - 1ull < p + 16ull) drop |= cr & (1u << (uint32_t)(size - 1ull - p));
@@ -166,20 +157,6 @@ void ts_fasta_join_count_kernel(const unsigned char *plain, unsigned long long s
     }
     c = wave_total(c);
     if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// counts -> exclusive sums in place (one wave, 64 per step)
-__global__ __launch_bounds__(64)
-void ts_fasta_scan_kernel(uint32_t *counts, uint32_t n, unsigned long long *total) {
-    unsigned long long run = 0;
-    for (uint32_t b = 0; b < n; b += 64u) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t c = i < n ? counts[i] : 0u;
-        const uint32_t incl = wave_scan_add(c);
-        if (i < n) counts[i] = (uint32_t)run + incl - c;        // (a chunk holds less than 4 GiB: the sums fit)
-        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    }
-    if (threadIdx.x == 0) *total = run;
 }
 
 // rows [0, upto) of the staged bytes to out + base (base: a multiple of 16), a 16-byte row per lane; bytes below `lo` (what the
@@ -232,7 +209,7 @@ void ts_fasta_join_write_kernel(const unsigned char *plain, unsigned long long s
 // gap letters (N n X x) among the 16 joined bytes at p, as a mask
 __device__ __forceinline__ uint32_t gap_mask16(uint4 q) {
     const uint4 f = make_uint4(q.x | 0x20202020u, q.y | 0x20202020u, q.z | 0x20202020u, q.w | 0x20202020u);
-    return eq_mask16(f, 0x6e6e6e6eu) | eq_mask16(f, 0x78787878u);
+    return byte_eq_mask16(f, 0x6e6e6e6eu) | byte_eq_mask16(f, 0x78787878u);
 }
 __device__ __forceinline__ bool is_gap(unsigned char c) { c |= 0x20; return c == 'n' || c == 'x'; }
 // the run starts among the 16 joined bytes at p (a multiple of 16, inside [a, z) rounded to 16); g = their gap mask
@@ -309,7 +286,7 @@ void ts_fasta_strict_kernel(const unsigned char *plain, unsigned long long size,
         if (p < z && p + 16ull > a) {
             const uint4 q = *(const uint4 *)(plain + p);       // (the chunk's buffer is readable 64 bytes beyond its capacity)
             const uint32_t lo = a > p ? (uint32_t)(a - p) : 0u, hi = z - p >= 16ull ? 16u : (uint32_t)(z - p);
-            m = ~(eq_mask16(q, 0x0a0a0a0au) | eq_mask16(q, 0x0d0d0d0du)) & bit_range(lo, hi);
+            m = ~(byte_eq_mask16(q, 0x0a0a0a0au) | byte_eq_mask16(q, 0x0d0d0d0du)) & bit_range(lo, hi);
         }
         if (ballot64(m != 0u) != 0ull) {                        // (wave-uniform; every job of the record stores the same byte)
             if (threadIdx.x == 0) has[job.rec] = 1;
@@ -362,11 +339,6 @@ int ts_k_launch_fasta_join_count(const void *plain, unsigned long long size, int
     if (n_jobs == 0) return 0;
     hipLaunchKernelGGL(ts_fasta_join_count_kernel, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, size,
                        at_end, (const FastaJoinJob *)jobs, n_jobs, counts);
-    return (int)hipGetLastError();
-}
-
-int ts_k_launch_fasta_scan(uint32_t *counts, uint32_t n, unsigned long long *total, void *stream) {
-    hipLaunchKernelGGL(ts_fasta_scan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counts, n, total);
     return (int)hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // fasta_internal.h — what fasta.cpp (host glue) and fasta.hip (kernels) of the device FASTA route share: the launchers and
-// the layouts both sides count with.  The line index underneath is the FASTQ route's, through its launchers as they are
-// (fastq_internal.h: ts_k_launch_fastq_count / _index); nothing of fastq.hip changes.
+// the layouts both sides count with.  The line index underneath and the sums of the join's and the runs' counts are the chunk
+// layer's (chunk_internal.h).
 #pragma once
 
 #include <stdint.h>
@@ -35,8 +35,6 @@ int ts_k_launch_fasta_records(const void *plain, unsigned long long size, const 
 // kept bytes per join job -> counts[n_jobs]
 int ts_k_launch_fasta_join_count(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
                                  uint32_t *counts, void *stream);
-// counts[n] -> exclusive sums in place (one wave), *total = their sum
-int ts_k_launch_fasta_scan(uint32_t *counts, uint32_t n, unsigned long long *total, void *stream);
 int ts_k_launch_fasta_join_write(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
                                  const uint32_t *sums, void *joined, void *stream);
 // run starts per run job -> counts[n_jobs]; after the scan, the runs' {record, is_gap, start}; then every run's length

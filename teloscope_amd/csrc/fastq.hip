@@ -1,9 +1,7 @@
-// fastq.hip — FASTQ text of a resident chunk (bgzf.cpp's ts_bam_chunk) turned into a record table, a read batch's input and
-// the passing records' bytes, on the device.  One-wave workgroups throughout, like bgzf.hip's.
+// fastq.hip — FASTQ text of a resident chunk (chunk_internal.h) turned into a record table, a read batch's input and the
+// passing records' bytes, on the device.  One-wave workgroups throughout, like bgzf.hip's.  The chunk layer's line index
+// (chunk.hip: every line's start, its first byte and whether a '\r' stands in front of its '\n') runs in front of everything here.
 //
-//   * line index: a wave per 16 KB of the chunk, 16 bytes per lane per step.  A first pass counts '\n' per slice, one wave
-//     sums the counts, a second pass writes every line's start in order (a prefix sum of the lanes' counts places them),
-//     its first byte and whether a '\r' stands in front of its '\n'.
 //   * record framing: readFastqRecord's rule is an automaton over lines with four states (0 expect header: a blank line
 //     stays, any other line goes to 1; 1, 2, 3 = sequence, separator, quality: one line each, whatever it holds).  A line
 //     is a map of the four states, a byte of four 2-bit fields, and maps compose: a prefix scan of the maps — within the
@@ -12,90 +10,17 @@
 //     same scan hands every slice the index of its first record.
 //   * record table: the lane that holds a header (a non-blank line met in state 0) reads its four lines' starts and checks
 //     the record in readFastqRecord's order; the lowest record that fails wins by a 64-bit atomic minimum.
-//   * stage and gather: 16 bytes per lane from an unaligned source — five aligned dwords and v_alignbyte_b32 — to a
-//     16-byte aligned destination.
+//   * stage and gather: 16 bytes per lane from an unaligned source — five aligned dwords and v_alignbyte_b32
+//     (chunk_device.h) — to a 16-byte aligned destination.  The gather's places come from chunk.hip's plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/teloscan.h"
+#include "chunk_device.h"
 #include "fastq_internal.h"
 #include "ts_device.h"
 
 namespace {
-
-// the bytes of w that are '\n', a bit per byte (bits 0..3).  t has bit 7 of every byte that is zero in x (exact per byte: no
-// carry leaves a byte); the multiply moves bit 8 i + 7 to bit 24 + i (the sixteen partial products land on distinct bits)
-__device__ __forceinline__ uint32_t newline_bits(uint32_t w) {
-    const uint32_t x = w ^ 0x0a0a0a0au;
-    const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
-    return (((t >> 7) * 0x01020408u) >> 24) & 15u;
-}
-
-// '\n' among the 16 bytes at plain + a (a: a multiple of 16), those at or beyond n left out
-__device__ __forceinline__ uint32_t newline_mask16(const unsigned char *plain, unsigned long long a, unsigned long long n) {
-    if (a >= n) return 0u;
-    const uint4 q = *(const uint4 *)(plain + a);                // (the chunk's buffer is readable 64 bytes beyond its capacity)
-    const uint32_t m = newline_bits(q.x) | newline_bits(q.y) << 4 | newline_bits(q.z) << 8 | newline_bits(q.w) << 12;
-    return n - a >= 16ull ? m : m & ((1u << (uint32_t)(n - a)) - 1u);
-}
-
-__global__ __launch_bounds__(64)
-void ts_fastq_count_kernel(const unsigned char *plain, unsigned long long n, uint32_t *counts) {
-    const unsigned long long base = (unsigned long long)blockIdx.x * kFastqSliceBytes + threadIdx.x * 16u;
-    uint32_t c = 0;
-#pragma unroll 8
-    for (uint32_t s = 0; s < kFastqSliceBytes / 1024u; ++s) c += __popc(newline_mask16(plain, base + 1024ull * s, n));
-    c = wave_total(c);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// counts -> exclusive sums in place (one wave, 64 slices per step)
-__global__ __launch_bounds__(64)
-void ts_fastq_count_scan_kernel(const unsigned char *plain, unsigned long long n, uint32_t *counts, uint32_t n_slices,
-                                unsigned long long *out) {
-    uint32_t run = 0;
-    for (uint32_t b = 0; b < n_slices; b += 64u) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t c = i < n_slices ? counts[i] : 0u;
-        const uint32_t incl = wave_scan_add(c);
-        if (i < n_slices) counts[i] = run + incl - c;
-        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    }
-    if (threadIdx.x == 0) { out[kFqNewlines] = run; out[kFqTail] = n && plain[n - 1] != '\n' ? 1ull : 0ull; }
-}
-
-__global__ __launch_bounds__(64)
-void ts_fastq_index_kernel(const unsigned char *plain, unsigned long long n, const uint32_t *bases, uint32_t newlines, uint32_t tail,
-                           uint32_t *lstart, unsigned char *first, unsigned char *cr) {
-    const unsigned long long base = (unsigned long long)blockIdx.x * kFastqSliceBytes + threadIdx.x * 16u;
-    uint32_t run = bases[blockIdx.x];
-    for (uint32_t s = 0; s < kFastqSliceBytes / 1024u; ++s) {
-        const unsigned long long a = base + 1024ull * s;
-        uint32_t m = newline_mask16(plain, a, n);
-        if (ballot64(m != 0u) == 0ull) continue;                // (wave-uniform)
-        const uint32_t c = __popc(m), incl = wave_scan_add(c);
-        uint32_t k = run + incl - c;                            // the first of this lane's '\n' ends line k
-        while (m) {
-            const unsigned long long p = a + (uint32_t)__builtin_ctz(m);
-            m &= m - 1u;
-            if (k < newlines) {                                 // (always: the count pass saw the same bytes)
-                lstart[k + 1] = (uint32_t)(p + 1ull);
-                first[k + 1] = p + 1ull < n ? plain[p + 1ull] : (unsigned char)0;
-                cr[k] = p > 0ull && plain[p - 1ull] == '\r';
-            }
-            ++k;
-        }
-        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        lstart[0] = 0u;
-        first[0] = n ? plain[0] : (unsigned char)0;
-        if (tail) {                                             // the last line has no '\n': it ends at n
-            lstart[newlines + 1] = (uint32_t)(n + 1ull);
-            cr[newlines] = plain[n - 1ull] == '\r';
-        }
-    }
-}
 
 // ---- the framing automaton.  A map: state s goes to (map >> 2 s) & 3.
 constexpr uint32_t kMapIdentity = 0xe4u, kMapBlank = 0x38u, kMapLine = 0x39u;      // {0,1,2,3}, {0,2,3,0}, {1,2,3,0}
@@ -205,18 +130,6 @@ void ts_fastq_records_kernel(const uint32_t *lstart, const unsigned char *first,
     }
 }
 
-// ---- 16 bytes from any address: the five aligned dwords that hold them, shifted into place (reads up to 19 bytes beyond p + 16
-// rounded down to a dword: inside the 64 readable bytes behind the chunk)
-__device__ __forceinline__ uint4 load16_any(const unsigned char *p) {
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t *q = (const uint32_t *)(a & ~(uintptr_t)3);
-    const uint32_t sh = (uint32_t)(a & 3u);
-    uint32_t w[5];
-    __builtin_memcpy(w, __builtin_assume_aligned(q, 4), 20);
-    return make_uint4(__builtin_amdgcn_alignbyte(w[1], w[0], sh), __builtin_amdgcn_alignbyte(w[2], w[1], sh),
-                      __builtin_amdgcn_alignbyte(w[3], w[2], sh), __builtin_amdgcn_alignbyte(w[4], w[3], sh));
-}
-
 // a piece of a sequence line into a read batch's input buffer: a wave per job, 16 bytes per lane per store
 __global__ __launch_bounds__(64)
 void ts_fastq_stage_kernel(const unsigned char *plain, const FastqCopyJob *jobs, uint32_t n_jobs, unsigned char *in) {
@@ -229,38 +142,14 @@ void ts_fastq_stage_kernel(const unsigned char *plain, const FastqCopyJob *jobs,
         const uint32_t left = job.n - i;
         if (left < 16u) {                                       // the bytes behind the read stay zero, as an upload leaves them
             uint32_t o[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (uint32_t q = 0; q < 4u; ++q) {
-                const uint32_t have = left > 4u * q ? left - 4u * q : 0u;
-                o[q] &= have >= 4u ? 0xffffffffu : have == 0u ? 0u : (1u << (8u * have)) - 1u;
-            }
+            zero_tail16(o, left);
             v = make_uint4(o[0], o[1], o[2], o[3]);
         }
         *(uint4 *)(dst + i) = v;
     }
 }
 
-// ---- passing records, in input order, each with a '\n' behind it: a prefix sum over size + 1 of the records whose pass byte is
-// set (one wave, 64 records per step; the sibling of bgzf.hip's plan, whose sizes are 4 + block_size), then a wave per record
-__global__ __launch_bounds__(64)
-void ts_fastq_gather_plan_kernel(const ts_fastq_record *recs, const unsigned char *pass, unsigned long long n,
-                                 unsigned long long *dst_off, unsigned long long *totals) {
-    unsigned long long run = 0, kept = 0;
-    for (unsigned long long base = 0; base < n; base += 64ull) {
-        const unsigned long long i = base + threadIdx.x;
-        const bool keep = i < n && pass[i] != 0;
-        const unsigned long long size = keep ? 1ull + recs[i].size : 0ull;
-        // (a step's sizes are summed in two halves: 64 records of up to 4 GiB)
-        const uint32_t incl_lo = wave_scan_add((uint32_t)(size & 0xffffull)), incl_hi = wave_scan_add((uint32_t)(size >> 16));
-        const unsigned long long incl = (unsigned long long)incl_lo + ((unsigned long long)incl_hi << 16);
-        if (i < n) dst_off[i] = keep ? run + incl - size : ~0ull;
-        run += (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)incl_lo, 63) +
-               ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)incl_hi, 63) << 16);
-        kept += (unsigned long long)__popcll(ballot64(keep));
-    }
-    if (threadIdx.x == 0) { totals[0] = run; totals[1] = kept; }
-}
-
+// ---- passing records, in input order, each with a '\n' behind it, to the places chunk.hip's plan gave them: a wave per record
 __global__ __launch_bounds__(64)
 void ts_fastq_gather_kernel(const unsigned char *plain, const ts_fastq_record *recs, const unsigned long long *dst_off,
                             unsigned long long n, unsigned long long cap, unsigned char *out) {
@@ -272,36 +161,13 @@ void ts_fastq_gather_kernel(const unsigned char *plain, const ts_fastq_record *r
     if (to > cap || 1ull + size > cap - to) return;             // (the caller has compared the total with cap already)
     const unsigned char *src = plain + recs[r].off;
     unsigned char *dst = out + to;
-    // bytes up to the destination's next 16-byte boundary, whole 16-byte stores, the rest, the '\n'
-    uint32_t head = (16u - (uint32_t)(to & 15ull)) & 15u;
-    if (head > size) head = size;
-    const uint32_t body = (size - head) & ~15u, rest = size - head - body;
-    if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
-    for (uint32_t i = threadIdx.x * 16u; i < body; i += 1024u) *(uint4 *)(dst + head + i) = load16_any(src + head + i);
-    if (threadIdx.x < rest) dst[head + body + threadIdx.x] = src[head + body + threadIdx.x];
+    copy_record16(dst, src, size, to);
     if (threadIdx.x == 63) dst[size] = '\n';
 }
 
 }  // namespace
 
 extern "C" {
-
-int ts_k_launch_fastq_count(const void *plain, unsigned long long n, uint32_t *counts, unsigned long long *out, void *stream) {
-    const uint32_t slices = (uint32_t)((n + kFastqSliceBytes - 1) / kFastqSliceBytes);
-    if (slices) hipLaunchKernelGGL(ts_fastq_count_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, counts);
-    hipLaunchKernelGGL(ts_fastq_count_scan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, counts,
-                       slices, out);
-    return (int)hipGetLastError();
-}
-
-int ts_k_launch_fastq_index(const void *plain, unsigned long long n, const uint32_t *bases, uint32_t newlines, uint32_t tail,
-                            uint32_t *lstart, unsigned char *first, unsigned char *cr, void *stream) {
-    const uint32_t slices = (uint32_t)((n + kFastqSliceBytes - 1) / kFastqSliceBytes);
-    if (slices == 0) return 0;
-    hipLaunchKernelGGL(ts_fastq_index_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, bases,
-                       newlines, tail, lstart, first, cr);
-    return (int)hipGetLastError();
-}
 
 int ts_k_launch_fastq_frames(const uint32_t *lstart, const unsigned char *cr, uint32_t n_lines, uint32_t newlines, void *frames,
                              void *entries, unsigned long long *out, void *stream) {
@@ -325,12 +191,6 @@ int ts_k_launch_fastq_stage(const void *plain, const void *jobs, uint32_t n_jobs
     if (n_jobs == 0) return 0;
     hipLaunchKernelGGL(ts_fastq_stage_kernel, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain,
                        (const FastqCopyJob *)jobs, n_jobs, (unsigned char *)in);
-    return (int)hipGetLastError();
-}
-
-int ts_k_launch_fastq_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream) {
-    hipLaunchKernelGGL(ts_fastq_gather_plan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const ts_fastq_record *)recs,
-                       (const unsigned char *)pass, n, (unsigned long long *)dst_off, (unsigned long long *)totals);
     return (int)hipGetLastError();
 }
 

@@ -1,11 +1,9 @@
-// gfa.hip — GFA text of a resident chunk (bgzf.cpp's ts_bam_chunk) turned into a segment table, a table of its P and H lines and
-// one buffer of the segments' names and those lines, on the device.  One-wave workgroups throughout, like fasta.hip's; fastq.hip's
-// line index (count, count-scan, index) runs in front of everything here, unchanged.
+// gfa.hip — GFA text of a resident chunk (chunk_internal.h) turned into a segment table, a table of its P and H lines and one
+// buffer of the segments' names and those lines, on the device.  One-wave workgroups throughout, like fasta.hip's.  The chunk
+// layer's line index and tab index (chunk.hip: the byte count, the scan and the byte index for '\n' and for '\t') run in front of
+// everything here: the one step that touches every byte is spread over the bytes, so an S line of hundreds of megabases costs
+// what its bytes cost, and no thread walks it.
 //
-//   * tab index: the one step that touches every byte.  A wave per 16 KB of the chunk, 16 bytes per lane per step: a first pass
-//     counts '\t' per slice, one wave sums the counts (fasta.hip's scan), a second pass writes every tab's offset in order (a DPP
-//     prefix sum of the lanes' counts places them; a step without a tab is skipped on a ballot).  The work is spread over the
-//     bytes: an S line of hundreds of megabases costs what its bytes cost, and no thread walks it.
 //   * line kinds: a lane per line.  Kind, second byte and content length come from the line index; an S line finds its first tabs
 //     by a lower bound of its start in the tab offsets (a binary search of ~25 steps, whatever the line's length).  A wave per
 //     2 048 lines counts segments, P / H lines and the bytes to gather; one wave sums the counts; a second pass gives every kept
@@ -18,56 +16,11 @@
 #include <stdint.h>
 
 #include "../../include/teloscan.h"
+#include "chunk_device.h"
 #include "gfa_internal.h"
 #include "ts_device.h"
 
 namespace {
-
-// the bytes of w that are '\t', a bit per byte (bits 0..3).  t has bit 7 of every byte that is zero in x (exact per byte: no carry
-// leaves a byte); the multiply moves bit 8 i + 7 to bit 24 + i
-__device__ __forceinline__ uint32_t tab_bits(uint32_t w) {
-    const uint32_t x = w ^ 0x09090909u;
-    const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
-    return (((t >> 7) * 0x01020408u) >> 24) & 15u;
-}
-
-// '\t' among the 16 bytes at plain + a (a: a multiple of 16), those at or beyond n left out
-__device__ __forceinline__ uint32_t tab_mask16(const unsigned char *plain, unsigned long long a, unsigned long long n) {
-    if (a >= n) return 0u;
-    const uint4 q = *(const uint4 *)(plain + a);                // (the chunk's buffer is readable 64 bytes beyond its capacity)
-    const uint32_t m = tab_bits(q.x) | tab_bits(q.y) << 4 | tab_bits(q.z) << 8 | tab_bits(q.w) << 12;
-    return n - a >= 16ull ? m : m & ((1u << (uint32_t)(n - a)) - 1u);
-}
-
-__global__ __launch_bounds__(64)
-void ts_gfa_tab_count_kernel(const unsigned char *plain, unsigned long long n, uint32_t *counts) {
-    const unsigned long long base = (unsigned long long)blockIdx.x * kGfaSliceBytes + threadIdx.x * 16u;
-    uint32_t c = 0;
-#pragma unroll 8
-    for (uint32_t s = 0; s < kGfaSliceBytes / 1024u; ++s) c += __popc(tab_mask16(plain, base + 1024ull * s, n));
-    c = wave_total(c);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-__global__ __launch_bounds__(64)
-void ts_gfa_tabs_kernel(const unsigned char *plain, unsigned long long n, const uint32_t *sums, uint32_t n_tabs, uint32_t *tabs) {
-    const unsigned long long base = (unsigned long long)blockIdx.x * kGfaSliceBytes + threadIdx.x * 16u;
-    uint32_t run = sums[blockIdx.x];
-    for (uint32_t s = 0; s < kGfaSliceBytes / 1024u; ++s) {
-        const unsigned long long a = base + 1024ull * s;
-        uint32_t m = tab_mask16(plain, a, n);
-        if (ballot64(m != 0u) == 0ull) continue;                // (wave-uniform)
-        const uint32_t c = __popc(m), incl = wave_scan_add(c);
-        uint32_t k = run + incl - c;
-        while (m) {
-            const uint32_t p = (uint32_t)a + (uint32_t)__builtin_ctz(m);
-            m &= m - 1u;
-            if (k < n_tabs) tabs[k] = p;                        // (always: the count pass saw the same bytes)
-            ++k;
-        }
-        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    }
-}
 
 // the first tab at or behind byte pos, as an index into tabs (n_tabs: there is none)
 __device__ __forceinline__ uint32_t tab_lower_bound(const uint32_t *tabs, uint32_t n_tabs, uint32_t pos) {
@@ -221,16 +174,6 @@ void ts_gfa_gather_kernel(const unsigned char *plain, unsigned long long size, c
 }
 
 // ---- the filtered loader's check
-// the bytes of w that equal the byte repeated in c4, a bit per byte (tab_bits for any byte)
-__device__ __forceinline__ uint32_t eq_bits(uint32_t w, uint32_t c4) {
-    const uint32_t x = w ^ c4;
-    const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
-    return (((t >> 7) * 0x01020408u) >> 24) & 15u;
-}
-__device__ __forceinline__ uint32_t eq_mask16(uint4 q, uint32_t c4) {
-    return eq_bits(q.x, c4) | eq_bits(q.y, c4) << 4 | eq_bits(q.z, c4) << 8 | eq_bits(q.w, c4) << 12;
-}
-
 // A stray '\r': one that is not the last byte of its line's content, i.e. whose next byte is no '\n' and that is not the input's
 // last byte.  A wave per slice, 16 bytes per lane per step; a step without one is skipped.  The line of a stray '\r' at p is the
 // last one that starts at or before p: a search of lstart[0, n_lines] (lstart[n_lines] is the end of the whole lines), and a
@@ -238,14 +181,14 @@ __device__ __forceinline__ uint32_t eq_mask16(uint4 q, uint32_t c4) {
 __global__ __launch_bounds__(64)
 void ts_gfa_stray_cr_kernel(const unsigned char *plain, unsigned long long n, int at_end, const uint32_t *lstart, uint32_t n_lines,
                             unsigned char *stray) {
-    const unsigned long long base = (unsigned long long)blockIdx.x * kGfaSliceBytes + threadIdx.x * 16u;
-    for (uint32_t s = 0; s < kGfaSliceBytes / 1024u; ++s) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kChunkSliceBytes + threadIdx.x * 16u;
+    for (uint32_t s = 0; s < kChunkSliceBytes / 1024u; ++s) {
         const unsigned long long a = base + 1024ull * s;
         uint32_t m = 0u;
         if (a < n) {
             const uint4 q = *(const uint4 *)(plain + a);        // (the chunk's buffer is readable 64 bytes beyond its capacity)
             const uint32_t in_chunk = n - a >= 16ull ? 0xffffu : (1u << (uint32_t)(n - a)) - 1u;
-            const uint32_t lf = eq_mask16(q, 0x0a0a0a0au) & in_chunk, cr = eq_mask16(q, 0x0d0d0d0du) & in_chunk;
+            const uint32_t lf = byte_eq_mask16(q, 0x0a0a0a0au) & in_chunk, cr = byte_eq_mask16(q, 0x0d0d0d0du) & in_chunk;
             const uint32_t lf_next = (lf >> 1) | (a + 16ull < n && plain[a + 16ull] == '\n' ? 0x8000u : 0u);
             m = cr & ~lf_next;
             if (at_end && n - 1ull >= a && n - 1ull < a + 16ull) m &= ~(1u << (uint32_t)(n - 1ull - a));
@@ -336,7 +279,7 @@ extern "C" {
 
 int ts_k_launch_gfa_stray_cr(const void *plain, unsigned long long n, int at_end, const uint32_t *lstart, uint32_t n_lines,
                              unsigned char *stray, void *stream) {
-    const uint32_t slices = (uint32_t)((n + kGfaSliceBytes - 1) / kGfaSliceBytes);
+    const uint32_t slices = (uint32_t)((n + kChunkSliceBytes - 1) / kChunkSliceBytes);
     if (slices == 0 || n_lines == 0) return 0;
     hipLaunchKernelGGL(ts_gfa_stray_cr_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, at_end,
                        lstart, n_lines, stray);
@@ -359,20 +302,6 @@ int ts_k_launch_gfa_flagged(const uint32_t *lstart, const unsigned char *first, 
     if (nf == 0 || n_flagged == 0) return 0;
     hipLaunchKernelGGL(ts_gfa_flagged_kernel, dim3(nf), dim3(64), 0, (hipStream_t)stream, lstart, first, cr, n_lines, codes, sums,
                        (ts_gfa_flagged *)flagged, n_flagged);
-    return (int)hipGetLastError();
-}
-
-int ts_k_launch_gfa_tab_count(const void *plain, unsigned long long n, uint32_t *counts, void *stream) {
-    const uint32_t slices = (uint32_t)((n + kGfaSliceBytes - 1) / kGfaSliceBytes);
-    if (slices == 0) return 0;
-    hipLaunchKernelGGL(ts_gfa_tab_count_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, counts);
-    return (int)hipGetLastError();
-}
-
-int ts_k_launch_gfa_tabs(const void *plain, unsigned long long n, const uint32_t *sums, uint32_t n_tabs, uint32_t *tabs, void *stream) {
-    const uint32_t slices = (uint32_t)((n + kGfaSliceBytes - 1) / kGfaSliceBytes);
-    if (slices == 0 || n_tabs == 0) return 0;
-    hipLaunchKernelGGL(ts_gfa_tabs_kernel, dim3(slices), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, n, sums, n_tabs, tabs);
     return (int)hipGetLastError();
 }
 

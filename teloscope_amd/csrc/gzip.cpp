@@ -1,7 +1,7 @@
 // gzip.cpp — host side of the device route for plain gzip (include/teloscan.h: ts_gzip_decode): staging, the stitch of the span
 // table into a chain, the verdict.  Nothing here inflates: the spans are decoded by gzip.hip's kernels or not at all, and what
 // their chain does not verify is the caller's to hand to zlib.
-#include "capi_internal.hpp"
+#include "chunk_internal.h"
 #include "gzip_core.h"
 
 namespace {

@@ -480,7 +480,7 @@ int  ts_k_launch_bgzf_inflate(const void *compressed, const void *blocks, uint32
                               void *stream);
 // ... the record walk over an inflated chunk (one wave; out4 = {records, next offset, error code, error offset}; plain is
 // readable 16 bytes beyond plain_n), SEQ -> ASCII (jobs: {src, dst, n, pad} of 24 bytes, a wave each, dst 16-byte aligned,
-// n <= 2048), and the gather of passing records
+// n <= 2048), and the copy of passing records to the places chunk.hip's gather plan gave them
 int  ts_k_launch_bam_walk(const void *plain, unsigned long long plain_n, unsigned long long from, unsigned long long cap,
                           void *recs, void *out4, void *stream);
 // ... the parallel record index (bam_walk_core.h): a wave per span [first_span, first_span + n_spans) writes its K candidate rows
@@ -493,7 +493,6 @@ int  ts_k_launch_bam_index_settle(const void *plain, unsigned long long plain_n,
 int  ts_k_launch_bam_index_write(const void *plain, unsigned long long plain_n, const void *tasks, uint32_t n_tasks, uint32_t span_log2,
                                  unsigned long long cap, void *recs, void *out1, void *stream);
 int  ts_k_launch_bam_decode(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream);
-int  ts_k_launch_bam_gather_plan(const void *recs, const void *pass, unsigned long long n, void *dst_off, void *totals, void *stream);
 int  ts_k_launch_bam_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
                             void *out, void *stream);
 // gzip.hip: a window of one gzip member's deflate stream (window: 16-byte aligned, zero from window_len to the next dword).
