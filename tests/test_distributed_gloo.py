@@ -5,8 +5,10 @@ a planning-only context) and the result on rank 0 must equal the single-process 
 Without a GPU the tile results cannot come from the HIP kernels, so each rank computes the raw arrays of ITS
 tile range — window records, tile directory entries, packed match records in tile order — from the CPU oracle,
 in exactly the layout ts_scan_tiles + ts_batch_export leave on a device.  What is under test is the plan
-split, the exchange and the reassembly, not the scan (tests/test_gpu_parity.py does that on the GPU, and
-test_sharded_scan_equals_whole_scan there runs this same exchange over real kernel output)."""
+split, the exchange and the reassembly, not the scan (tests/test_gpu_parity.py does that on the GPU;
+test_sharded_scan_equals_whole_scan_and_oracle in tests/test_gpu_shards_fullsize.py assembles real kernel output the way
+this exchange does, and tests/test_gpu_wire16.py — test_full_exchange_over_the_u16_wire_equals_the_oracle — sends it
+through the u16 wire's device side, ts_widen_u16, which the CPU branch of _widen_u16 here never reaches)."""
 import os
 import socket
 import sys

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests import harness as H
-from tests import seqgen
+from tests import seqgen, shardpack, shardwidths
 from tests.backends import OracleBackend, assert_visible_view_equal
 
 pytestmark = pytest.mark.gpu
@@ -142,11 +142,37 @@ def test_visible_record_regions_that_overflow_are_regrown(monkeypatch):
     plan.close()
 
 
+def _sorted_blocks(msg, at, n):
+    key = ("seg", "kind", "seq", "start")                        # (the kernels append blocks in completion order)
+    return np.sort(np.frombuffer(msg[at:at + n * 64].tobytes(), dtype=shardpack.DEVBLOCK_DT), order=key)
+
+
+def _assert_messages_equal_oracle_packing(plan, opts, msgs, exp, ctx, scale=1, wants=None):
+    """Byte level: every part's message against tests/shardpack.py's rendering of the oracle's results in the same layout
+    (`wants`, where the caller holds several sets of messages against one rendering) — header, segment entries, the
+    windows / tilevis / visible sections byte for byte, the blocks as a set.  Returns the parts' section offsets."""
+    from teloscope_amd.distributed import shard_info
+    offs = []
+    for p in range(plan.world):
+        want = wants[p] if wants is not None else shardpack.pack_shard(plan, opts, p, exp, scale=scale)
+        got = msgs[p]
+        hg, hw = shardpack.read_header(got), shardpack.read_header(want)
+        assert hg == hw, (ctx, p, hg, hw)
+        nseg, nown, nwin = int(hg["n_segs"]), int(hg["own_end"] - hg["own_begin"]), int(hg["n_windows"])
+        off = shardpack.sections(shard_info(plan, p, scale), nseg, nown, nwin)
+        assert np.array_equal(shardpack.read_segs(got), shardpack.read_segs(want)), (ctx, p)
+        for name, n in (("windows", nwin * int(hg["window_bytes"])), ("tilevis", nown * 2), ("visible", int(hg["n_visible"]) * int(hg["visible_bytes"]))):
+            assert np.array_equal(got[off[name]:off[name] + n], want[off[name]:off[name] + n]), (ctx, p, name)
+        nb = int(hg["n_blocks"])
+        assert np.array_equal(_sorted_blocks(got, off["blocks"], nb), _sorted_blocks(want, off["blocks"], nb)), (ctx, p)
+        offs.append(off)
+    return offs
+
+
 def test_kernel_messages_equal_the_messages_packed_from_oracle_results():
     """Byte level: what the kernels pack (header, per-segment entries, bit-packed windows, per-tile counts, visible records,
     blocks) against tests/shardpack.py's rendering of the oracle's results in the same layout."""
     import torch
-    from tests import shardpack
     from teloscope_amd.distributed import ShardPlan
     dev = torch.device("cuda", 0)
     for cli in (HEADLINE + " -t 3000", "-r -i -w 700 -s 700 -t 1000"):
@@ -160,23 +186,61 @@ def test_kernel_messages_equal_the_messages_packed_from_oracle_results():
         for world in (1, 3, 4):
             plan = ShardPlan(tel, lens, abs_pos=abs_pos, world=world)
             msgs, _ = _pack_all_parts(plan, _fill(plan, seqs, dev), dev)
-            for p in range(world):
-                want = shardpack.pack_shard(plan, opts, p, exp)
-                got = msgs[p]
-                hg, hw = shardpack.read_header(got), shardpack.read_header(want)
-                assert hg == hw, (cli, world, p, hg, hw)
-                nseg, nown, nwin = int(hg["n_segs"]), int(hg["own_end"] - hg["own_begin"]), int(hg["n_windows"])
-                from teloscope_amd.distributed import shard_info
-                off = shardpack.sections(shard_info(plan, p), nseg, nown, nwin)
-                assert np.array_equal(shardpack.read_segs(got), shardpack.read_segs(want)), (cli, world, p)
-                for name, n in (("windows", nwin * int(hg["window_bytes"])), ("tilevis", nown * 2), ("visible", int(hg["n_visible"]) * int(hg["visible_bytes"]))):
-                    assert np.array_equal(got[off[name]:off[name] + n], want[off[name]:off[name] + n]), (cli, world, p, name)
-                nb = int(hg["n_blocks"])
-                bg = np.frombuffer(got[off["blocks"]:off["blocks"] + nb * 64].tobytes(), dtype=shardpack.DEVBLOCK_DT)
-                bw = np.frombuffer(want[off["blocks"]:off["blocks"] + nb * 64].tobytes(), dtype=shardpack.DEVBLOCK_DT)
-                key = ("seg", "kind", "seq", "start")            # (the kernels append blocks in completion order)
-                assert np.array_equal(np.sort(bg, order=key), np.sort(bw, order=key)), (cli, world, p)
+            _assert_messages_equal_oracle_packing(plan, opts, msgs, exp, (cli, world))
             plan.close()
+
+
+@pytest.mark.parametrize("entry", shardwidths.WIDTH_GRID + shardwidths.SEAM_GRID, ids=shardwidths.entry_id)
+def test_kernel_messages_at_every_field_width(entry, monkeypatch):
+    """The message's window records at every field width 3 .. 16 and record size 2 .. 14 bytes (tests/shardwidths.py), with
+    every field of the homopolymer's windows at the largest value its width holds, from both device packers — the scan
+    kernel's own tail (a bound message and an emitting scan: the constant layout at 10 bits x 7 fields, the generic `put`
+    everywhere else, the 8 + 4 + single-byte store ladder) and ts_shard_pack_windows (TS_SHARD_BIND=0, or a scan that does
+    not emit) — for one part and two: each message equals the oracle's results packed by tests/shardpack.py byte for byte,
+    nothing is stored behind the last window's record, the merge equals the oracle, and the packers agree with each other."""
+    import torch
+    import teloscope_amd as ta
+    from teloscope_amd.distributed import ShardPlan, finalize_shards, free_segments
+    dev = torch.device("cuda", 0)
+    cli = shardwidths.cli(entry)
+    opts, seqs, abs_pos, exp = shardwidths.reference(cli)
+    _, tel = _teloscope(cli)
+    lens = [len(s) for s in seqs]
+    for world in (1, 2):
+        plan = ShardPlan(tel, lens, abs_pos=abs_pos, world=world)
+        buf = _fill(plan, seqs, dev)
+        wants = [shardpack.pack_shard(plan, opts, p, exp, scale=shardwidths.SCALE) for p in range(world)]
+        packed = {}
+        for bind in (None, "0"):
+            if bind is None:
+                monkeypatch.delenv("TS_SHARD_BIND", raising=False)
+            else:
+                monkeypatch.setenv("TS_SHARD_BIND", bind)
+            for emit in (True, False):
+                ctx = (cli, "world %d" % world, "bind %s" % bind, "emit %d" % emit)
+                msgs, stats = _pack_all_parts(plan, buf, dev, scale=shardwidths.SCALE, emit=emit)
+                assert not any(st.flags for st in stats), (ctx, [hex(st.flags) for st in stats])
+                offs = _assert_messages_equal_oracle_packing(plan, opts, msgs, exp, ctx, scale=shardwidths.SCALE, wants=wants)
+                for p, (m, off) in enumerate(zip(msgs, offs)):
+                    h = shardpack.read_header(m)
+                    assert int(h["window_bytes"]) == shardwidths.window_bytes(entry), ctx
+                    end = off["windows"] + int(h["n_windows"]) * int(h["window_bytes"])
+                    # the message buffer is zero-filled: a store ladder that runs past the last record shows up here
+                    assert not m[end:off["tilevis"]].any(), (ctx, p, m[end:off["tilevis"]])
+                rc, out, cnt = finalize_shards(plan, msgs)
+                assert rc == 0, (ctx, rc, tel._ctx.error())
+                for i in range(len(lens)):
+                    assert_visible_view_equal(ta.SegmentData(out[i], False), exp[i], False, cnt[i], "%s segment %d" % (ctx, i))
+                free_segments(plan, out)
+                packed[(bind, emit)] = (msgs, offs)
+        first, offs = packed[(None, True)]
+        for key, (msgs, _) in packed.items():
+            for p in range(world):
+                a, b, nb = first[p], msgs[p], int(shardpack.read_header(first[p])["n_blocks"])
+                assert shardpack.read_header(a) == shardpack.read_header(b), (cli, world, key, p)
+                assert np.array_equal(a[128:offs[p]["blocks"]], b[128:offs[p]["blocks"]]), (cli, world, key, p)
+                assert np.array_equal(_sorted_blocks(a, offs[p]["blocks"], nb), _sorted_blocks(b, offs[p]["blocks"], nb)), (cli, world, key, p)
+        plan.close()
 
 
 @pytest.mark.parametrize("cli", [HEADLINE + " -t 3000", "-r -g -e -m -i", "-r -i -w 700 -s 700 -t 1000 -k 120"])

@@ -39,20 +39,9 @@ def _scan_parts(plan, buf, dev):
     """Every part of the plan scanned on its own restricted batch (as a rank would), the parts' arrays
     concatenated in rank order (what the gather does): (windows, stats, dense[:n], counts)."""
     import torch
-    from teloscope_amd.distributed import HipShard
-    stream = torch.cuda.current_stream()
-    sptr = C.c_void_p(stream.cuda_stream)
-    ws, ss, ds, counts = [], [], [], []
-    for p in range(plan.world):
-        r = plan.ranges[p]
-        local = buf[r.input_begin:r.input_end].clone()         # a rank holds only the bytes its range reads
-        hs = HipShard(plan, p, dev, slots=1)
-        hs.scan(local.data_ptr(), sptr, 0)
-        n = hs.finish(local.data_ptr(), sptr, 0)
-        ws.append(hs.windows[0].clone()); ss.append(hs.stats[0].clone()); ds.append(hs.dense[0][:n].clone())
-        counts.append(n)
-        hs.close()
-    return torch.cat(ws), torch.cat(ss), torch.cat(ds), counts
+    from tests import shardwidths
+    parts, counts = shardwidths.scan_parts(plan, buf, dev)
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), counts
 
 
 @pytest.mark.parametrize("cli", [HEADLINE, "-r -g -e -m -i", "-c CCCTAAA -w 2000 -s 1000 -r -g -e -m -i", "", "-t 3000"])

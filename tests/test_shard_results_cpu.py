@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from tests import seqgen, shardpack
+from tests import seqgen, shardpack, shardwidths
 from tests.backends import OracleBackend, assert_visible_view_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,6 +119,58 @@ def test_messages_merge_to_the_oracle(cli):
             assert_visible_view_equal(ta.SegmentData(out[i], opts.ultra_fast), exp[i], opts.ultra_fast, cnt[i], "world %d segment %d" % (world, i))
         free_segments(plan, out)
         plan.close()
+
+
+@pytest.mark.parametrize("entry", shardwidths.WIDTH_GRID + shardwidths.SEAM_GRID, ids=shardwidths.entry_id)
+def test_messages_of_every_field_width_merge_to_the_oracle(entry):
+    """The message's bit-packed window records at every field width 3 .. 16 and every record size 2 .. 14 bytes, both field
+    counts, 2- and 4-byte visible records (tests/shardwidths.py): messages packed from oracle results must merge
+    (ts_shards_finalize: the unsigned __int128 unpacker) to the oracle, with every field of the homopolymer's windows at
+    the largest value its width holds.  NEED_FULL and RETRY_GROW are failures here."""
+    import teloscope_amd as ta
+    from teloscope_amd.distributed import finalize_shards, free_segments, shard_info
+    w = entry[0]
+    cli = shardwidths.cli(entry)
+    opts, seqs, abs_pos, exp = shardwidths.reference(cli)
+    lens = [len(s) for s in seqs]
+    nuc = shardwidths.nuc_on(entry)
+    # the fields really are at their maximum: a window of w A's, and w - 5 canonical matches in it (non-canonical ones in
+    # the entries that put the other count across bit 64)
+    wins = exp[0]["windows"]
+    assert len(wins) >= 4
+    counted = "non_canonical_covered" if entry in shardwidths.SEAM_GRID else "canonical_covered"
+    assert int(wins[counted].max()) == (w - 5) * 6 and int(wins["fwd_covered"].max()) == (w - 5) * 6
+    if nuc:
+        assert int(wins["nucleotide_counts"].max()) == w
+    for world in (1, 2):
+        _, tel, plan = _plan(cli, world, lens, abs_pos)
+        for p in range(world):
+            si = shard_info(plan, p, shardwidths.SCALE)
+            assert int(si.window_bytes) == -(-(7 if nuc else 3) * int(w).bit_length() // 8) == shardwidths.window_bytes(entry)
+            assert int(si.visible_bytes) == (2 if plan.wire16_ok else 4)
+        msgs = [shardpack.pack_shard(plan, opts, p, exp, scale=shardwidths.SCALE) for p in range(world)]
+        if world == 2:
+            h = shardpack.read_header(msgs[1])
+            assert int(h["ext_begin"]) != int(h["own_begin"]), "the boundary did not fall inside the chromosome"
+        rc, out, cnt = finalize_shards(plan, msgs)
+        assert rc == 0, (world, rc, tel._ctx.error())
+        for i in range(len(lens)):
+            assert_visible_view_equal(ta.SegmentData(out[i], False), exp[i], False, cnt[i], "%s world %d segment %d" % (cli, world, i))
+        free_segments(plan, out)
+        plan.close()
+
+
+def test_the_width_grid_has_visible_records_of_both_sizes():
+    """2-byte visible records, and the 4-byte ones a plan takes when a tile exceeds 2^14 positions or k x w > 65535."""
+    from teloscope_amd.distributed import shard_info
+    seen = {}
+    for entry in shardwidths.WIDTH_GRID:
+        w = entry[0]
+        _, tel, plan = _plan(shardwidths.cli(entry), 1, [3 * w + w // 2 + 5, max(300_000, 12 * w + 17)], [0, 11])
+        seen[entry] = int(shard_info(plan, 0, shardwidths.SCALE).visible_bytes)
+        plan.close()
+    assert set(seen.values()) == {2, 4}, seen
+    assert seen[(10922, 5461, "-r -g")] == 2 and seen[(10923, 10923, "-r -g")] == 4 and seen[(16384, 16384, "-r -g")] == 4
 
 
 def test_merge_reports_what_it_cannot_merge():
