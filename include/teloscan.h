@@ -1017,11 +1017,36 @@ int ts_gfa_chunk_walk(ts_chunk *chunk, int at_end, ts_gfa_segment *segs, uint64_
 /* The device address of the chunk's first byte (valid until the chunk grows, is refilled or destroyed): what a TS_INPUT_DEVICE
  * segment that lies in the chunk is addressed from. */
 const void *ts_chunk_data(const ts_chunk *chunk);
-/* The tail [carry_from, size) of `from` becomes the whole contents of `to` (another chunk of the same context, which grows when
- * it must), device to device; `from` keeps every byte.  A following ts_chunk_upload(to, ..., 0, ...) or ts_bam_chunk_inflate(to,
- * ..., 0, ...) appends behind the carried bytes: how an unfinished line moves on while the chunk it began in stays resident.
- * Ordered on `stream`; waits for it. */
+/* The tail [carry_from, size) of `from` becomes the whole contents of `to` (another chunk, which grows when it must); `from`
+ * keeps every byte.  The two may belong to different contexts: device to device where both contexts are on one GPU, a peer copy
+ * where the destination's GPU can reach the source's memory, through host memory otherwise (the caller sees to it that nothing
+ * changes `from` meanwhile).  A following ts_chunk_upload(to, ..., 0, ...), ts_bam_chunk_inflate(to, ..., 0, ...) or
+ * ts_chunk_commit(to, ...) appends behind the carried bytes: how an unfinished line or record moves on while the chunk it began
+ * in stays resident.  Ordered on `stream` of the destination's context; waits for it. */
 int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void *stream);
+
+/* ---- a chunk's staging region, for read routes that deal the chunks of one input to several contexts (include/
+ *      teloscope_mi355x_io.hpp: fastqSubsetDevice and bamSubsetDevice on a ReadTelomereFilter of several contexts).  Chunk k + 1
+ *      lives on another context than chunk k, and the front of its contents, the unfinished record of chunk k, is known only when
+ *      chunk k has been walked; its new bytes need not wait for that.  They are staged beside the chunk's contents, and committed
+ *      behind the carry once it is there: contents = carry ++ staged.  Stands in for the same reference loops as ts_chunk_upload
+ *      and ts_bam_chunk_inflate (the getline calls of readFastqRecord, src/input.cpp:116-123; BgzfReader::loadBlock,
+ *      src/bgzf.cpp:57-196), which read one stream front to back and have no such seam. */
+/* bytes[0, n) (host memory) behind what is staged; the region grows when they do not fit.  The chunk's contents are not touched.
+ * Ordered on `stream`; the caller's bytes are free when the call returns. */
+int ts_chunk_stage_upload(ts_chunk *chunk, const void *bytes, uint64_t n, void *stream);
+/* BGZF members inflated and checksummed into the staging region: ts_bam_chunk_inflate without a carry, blocks[i].dst_off
+ * counting from the region's first byte and not below what is staged already; staged = the highest dst_off + isize.  The members
+ * are judged by ts_bam_chunk_status, as after ts_bam_chunk_inflate.  The kernel runs on `stream`; the caller's buffers are free
+ * when the call returns. */
+int ts_chunk_stage_inflate(ts_chunk *chunk, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
+                           void *stream);
+/* Bytes staged and not committed yet. */
+uint64_t ts_chunk_staged(const ts_chunk *chunk);
+/* The staged bytes go behind the chunk's contents (device to device; the chunk grows when it must) and the region is empty
+ * again.  The contents before it are typically a carry placed by ts_chunk_carry_over, or nothing: the chunk's first byte stays
+ * at the 16-byte aligned address every walk, stage and gather kernel reads from.  Ordered on `stream`; waits for it. */
+int ts_chunk_commit(ts_chunk *chunk, void *stream);
 
 /* ---- assembly record filters on the two device routes (include/teloscope_mi355x_filter.hpp; scanFastaToFilesDevice and
  *      annotateGfaDevice with a selector): the few facts the filtered loaders' rules ask about bytes that the host never sees.

@@ -48,6 +48,7 @@
 #include "teloscope_mi355x.hpp"
 #include "teloscope_mi355x_filter.hpp"
 #include "teloscope_mi355x_gzip.hpp"
+#include "teloscope_mi355x_ring.hpp"
 
 namespace teloscope_mi355x {
 
@@ -1418,14 +1419,20 @@ inline BgzfPick pickBgzfMembers(const unsigned char *data, size_t size, size_t a
     return pick;
 }
 
-// `used` compressed bytes at src with their members' descriptors: uploaded, inflated and checksummed on the device behind the
-// chunk's bytes from carryFrom on; a payload that is no deflate stream or fails its CRC is the host routes' exception
-inline void inflateMembers(ts_ctx *ctx, ts_chunk *chunk, const unsigned char *src, size_t used, const std::vector<ts_bgzf_block> &descs, uint64_t carryFrom) {
-    if (ts_bam_chunk_inflate(chunk, src, used, descs.data(), descs.size(), carryFrom, nullptr) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
+// the members of the chunk's last inflate, into its contents or its staging region, judged: a payload that is no deflate stream
+// or fails its CRC is the host routes' exception
+inline void membersVerdict(ts_ctx *ctx, ts_chunk *chunk) {
     ts_bgzf_status bad{};
     if (ts_bam_chunk_status(chunk, &bad) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
     if (bad.code == TS_BGZF_BAD_DEFLATE) throw std::runtime_error("invalid BGZF deflate payload");
     if (bad.code != TS_BGZF_OK) throw std::runtime_error("BGZF checksum mismatch");
+}
+
+// `used` compressed bytes at src with their members' descriptors: uploaded, inflated and checksummed on the device behind the
+// chunk's bytes from carryFrom on
+inline void inflateMembers(ts_ctx *ctx, ts_chunk *chunk, const unsigned char *src, size_t used, const std::vector<ts_bgzf_block> &descs, uint64_t carryFrom) {
+    if (ts_bam_chunk_inflate(chunk, src, used, descs.data(), descs.size(), carryFrom, nullptr) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
+    membersVerdict(ctx, chunk);
 }
 
 // ts_gzip (include/teloscan.h) as the device GzipReader decodes with
@@ -1599,6 +1606,57 @@ public:
 
     bool fill(ts_chunk *chunk, uint64_t carryFrom, size_t want) { read(want); return put(chunk, carryFrom); }
 
+    // The same fill in two halves for a route that deals its chunks to several contexts (detail::ChunkRing): take() is the
+    // reader's, one call at a time in chunk order, and touches no device; stage() brings what was taken into the staging region
+    // of a chunk of any context (ts_chunk_stage_upload, ts_chunk_stage_inflate) and may run for several fills at once.  The
+    // Gzip source is bound to the context it was made on: such a feed is made with Options::gzipDevice off, and plain gzip is a
+    // Stream.  Options::sink is not told about these fills.
+    struct Fill {
+        const char *host = nullptr;                             // Plain and Stream: the bytes (a Stream's lie in `block`)
+        uint64_t n = 0;                                         // new bytes in all
+        std::vector<char> block;
+        struct Call { size_t at = 0, used = 0; std::vector<ts_bgzf_block> descs; };
+        std::vector<Call> calls;                                // Bgzf: the members of each inflate call, dst_off from the fill's start
+        bool atEnd = false;                                     // the input is at its end
+    };
+    void take(size_t want, Fill &f) {
+        f.host = nullptr; f.n = 0; f.calls.clear(); f.atEnd = false;
+        if (source_ == Gzip) throw std::logic_error("ChunkFeed::take: the Gzip source serves one context");
+        if (source_ == Bgzf) {
+            BgzfPick pick;
+            do {
+                f.calls.emplace_back();
+                Fill::Call &c = f.calls.back();
+                pick = pickBgzfMembers(in_.data, in_.size, at_, 0, f.n, want, compCap_, c.descs);
+                c.at = at_; c.used = pick.used;
+                at_ += pick.used;
+                f.n += pick.made;
+            } while (!pick.foreign && !pick.full && at_ < in_.size);
+            if (!pick.foreign) { f.atEnd = at_ >= in_.size; return; }
+            source_ = Stream;
+            openStream(at_);
+            f.atEnd = streamDone_;
+            return;
+        }
+        if (source_ == Plain) {
+            f.n = std::min<uint64_t>(want, in_.size - at_);
+            f.host = reinterpret_cast<const char *>(in_.data + at_);
+            at_ += static_cast<size_t>(f.n);
+            f.atEnd = at_ >= in_.size;
+            return;
+        }
+        f.n = read(want, &f.block);
+        f.host = f.block.data();
+        f.atEnd = streamDone_;
+    }
+    void stage(ts_ctx *ctx, ts_chunk *chunk, const Fill &f) const {
+        for (const Fill::Call &c : f.calls) {
+            if (ts_chunk_stage_inflate(chunk, in_.data + c.at, c.used, c.descs.data(), c.descs.size(), nullptr) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
+            membersVerdict(ctx, chunk);
+        }
+        if (f.calls.empty() && ts_chunk_stage_upload(chunk, f.host, f.n, nullptr) != TS_OK) throw opt_.noRoom ? opt_.noRoom(opt_.uploadFailed) : deviceError(ctx, opt_.uploadFailed);
+    }
+
 private:
     // plain gzip from `from` on goes to the device: asked for, a device to ask, a member there, and enough of it
     bool gzipWanted(size_t from) const {
@@ -1711,7 +1769,10 @@ struct ReadJudge {
 // (detail::inflateMembers), the records walked and validated there (ts_bam_chunk_walk or ts_bam_chunk_index: the table comes back), SEQ decoded into
 // a tips-only batch's input buffer (ts_bam_chunk_decode), judged and the passing records' bytes gathered (detail::ReadJudge
 // with ts_bam_chunk_gather).
-// The BAM header is parsed on the host from the chunk's leading bytes.  Runs on the filter's first context.
+// The BAM header is parsed on the host from the chunk's leading bytes.  A filter of one context runs the loop below; a filter of
+// several contexts (ordinals may repeat) deals the chunks to all of them, chunk k to context k mod N, once context 0 has the
+// header behind it (detail::BamRing, below), with the same statistics, exceptions and output bytes.  perDevice, where given,
+// receives one entry per context.
 // What a maintainer of the reference would call from runBamSubsetMode (src/bam.cpp:262-316) in place of subsetBam.
 // `walk` chooses how a chunk's records are framed: Serial is ts_bam_chunk_walk, one wave that follows the records one after the
 // other; Index is ts_bam_chunk_index, which finds record chains in all spans of the chunk at once and links them.  Both give
@@ -1719,9 +1780,24 @@ struct ReadJudge {
 // walk stage measured 6.8 ms against 98.4 ms on a HiFi BAM and 11 ms against 1 112 ms on a BAM of 150-base reads
 // (profiles/bam/bam_index_rate.txt).
 enum class BamRecordWalk { Serial, Index };
+// One context's share of a device read route: chunks it took, reads with bases it judged, uncompressed bytes it received, and the
+// milliseconds its thread spent in the source (reading, upload, inflate and CRC), waiting for the chunk before its own to be
+// framed (several contexts only: the serial section as this context sees it), placing the carry and committing the staged bytes
+// behind it (several contexts only), framing records (index or walk), and in ReadJudge's stage, filter and gather.
+struct ReadRouteDeviceStats {
+    uint64_t chunks = 0, recordsJudged = 0, bytesReceived = 0;
+    double msSource = 0, msCarryWait = 0, msCommit = 0, msWalk = 0, msStage = 0, msFilter = 0, msGather = 0;
+};
+namespace detail {
+inline BamSubsetStats bamSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                   size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice);
+inline FastqSubsetResult fastqSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                        size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice);
+}  // namespace detail
 inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                       size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
-                                      BamRecordWalk walk = BamRecordWalk::Index) {
+                                      BamRecordWalk walk = BamRecordWalk::Index, std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    if (filter.deviceCount() > 1) return detail::bamSubsetDeviceRing(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice);
     BamSubsetStats stats;
     ts_ctx *ctx = filter.context(0);
     auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
@@ -1734,6 +1810,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     double msInflate = 0, msWalk = 0, msWrite = 0;
+    ReadRouteDeviceStats one;
 
     // a chunk holds the unconsumed tail of the one before (at most a record: 4 bytes + 256 MiB) and the new members' output
     const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 1u << 20);
@@ -1766,6 +1843,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
         stats.totalRecords += n;
         stats.missingSequenceRecords += n - withSeq.size();
         if (withSeq.empty()) return;
+        one.recordsJudged += withSeq.size();
         judged.run(ctx, chunk.p, lens, "SEQ decode failed",
                    [&](ts_batch *batch) { return ts_bam_chunk_decode(chunk.p, withSeq.data(), withSeq.size(), batch, nullptr); },
                    [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
@@ -1805,6 +1883,7 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
         detail::inflateMembers(ctx, chunk.p, data + at, used, descs, pos);
         msInflate += since(t0);
         at += used;
+        ++one.chunks; one.bytesReceived += produced;
         more = used > 0 && at < size;
         held = carry + produced; pos = 0;
         head.clear();
@@ -1834,6 +1913,10 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "bamSubsetDevice: upload + inflate + CRC %.0f ms, walk (%s) %.1f ms, decode %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
                      msInflate, walk == BamRecordWalk::Index ? "index" : "serial", msWalk, judged.msStage, judged.msFilter, judged.msGather, msWrite);
+    if (perDevice) {
+        one.msSource = msInflate; one.msWalk = msWalk; one.msStage = judged.msStage; one.msFilter = judged.msFilter; one.msGather = judged.msGather;
+        perDevice->assign(1, one);
+    }
     return stats;
 }
 
@@ -1844,10 +1927,15 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
 // indexed and records framed and validated (ts_fastq_chunk_walk: the table comes back), sequences staged into a tips-only
 // batch's input buffer (ts_fastq_chunk_stage), judged and the passing records' bytes gathered (detail::ReadJudge with
 // ts_fastq_chunk_gather).  The bytes behind the last whole record stay in the chunk for the next fill; a record larger than a
-// chunk makes the chunk grow.  Runs on the filter's first context.
+// chunk makes the chunk grow.  A filter of one context runs the loop below; a filter of several contexts (ordinals may repeat)
+// deals the chunks to all of them, chunk k to context k mod N (detail::FastqRing, below), with the same result, exceptions and
+// output bytes; there plain gzip is read through zlib, because the opt-in device gzip source (ChunkFeed::Gzip) is bound to one
+// context.  perDevice, where given, receives one entry per context.
 // What a maintainer of the reference would call from Input::readFastqSubset (src/input.cpp:737-832) in place of its loop.
 inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                           size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
+                                           size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
+                                           std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    if (filter.deviceCount() > 1) return detail::fastqSubsetDeviceRing(inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice);
     FastqSubsetResult res;
     ts_ctx *ctx = filter.context(0);
     auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
@@ -1860,6 +1948,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
     double msUpload = 0, msIndex = 0, msWrite = 0;
+    ReadRouteDeviceStats one;
 
     const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 64);
     struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, feed.compCap(chunkBytes), chunkBytes)};
@@ -1873,6 +1962,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
         for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { withSeq.push_back(r[i]); lens.push_back(r[i].seq_len - r[i].seq_cr); }
         res.total += n;
         if (withSeq.empty()) return;                            // (a read without bases is never kept)
+        one.recordsJudged += withSeq.size();
         judged.run(ctx, chunk.p, lens, "staging the sequences failed",
                    [&](ts_batch *batch) { return ts_fastq_chunk_stage(chunk.p, withSeq.data(), withSeq.size(), batch, nullptr); },
                    [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
@@ -1894,6 +1984,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
         Clock::time_point t0 = Clock::now();
         atEnd = feed.fill(chunk.p, pos, want);
         msUpload += since(t0);
+        ++one.chunks; one.bytesReceived += ts_bam_chunk_size(chunk.p) - carry;
         held = ts_bam_chunk_size(chunk.p); pos = 0;
         if (first) {
             if (held == 0) {
@@ -1927,8 +2018,419 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "fastqSubsetDevice: upload%s %.0f ms, index %.0f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
                      feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, judged.msStage, judged.msFilter, judged.msGather, msWrite);
+    if (perDevice) {
+        one.msSource = msUpload; one.msWalk = msIndex; one.msStage = judged.msStage; one.msFilter = judged.msFilter; one.msGather = judged.msGather;
+        perDevice->assign(1, one);
+    }
     return res;
 }
+
+// ---- the two read routes on a filter of several contexts: the chunks of the input dealt to all of them (detail::ChunkRing) ----
+namespace detail {
+
+// What a context of a ring route owns: its chunk (contents and staging region), its judge and pass buffer, the passing records
+// of the chunk it is working on, and its figures.
+struct RingWorker {
+    ts_ctx *ctx = nullptr;
+    ts_chunk *chunk = nullptr;
+    ReadJudge judged;
+    std::vector<uint64_t> lens;
+    std::vector<unsigned char> out;                             // the chunk's passing records, in input order
+    std::vector<size_t> cuts;                                   // where each sub-batch's records end in `out`: the writer's pieces
+    uint64_t passed = 0;
+    ReadRouteDeviceStats st;
+    RingWorker() = default;
+    RingWorker(const RingWorker &) = delete;
+    RingWorker &operator=(const RingWorker &) = delete;
+    ~RingWorker() { ts_bam_chunk_destroy(chunk); }
+    void fresh() { out.clear(); cuts.clear(); passed = 0; }
+    void keep() {
+        out.insert(out.end(), judged.kept.begin(), judged.kept.begin() + static_cast<std::ptrdiff_t>(judged.bytes));
+        cuts.push_back(out.size());
+        passed += judged.nPassed;
+    }
+    // the pieces in the order and sizes the loop on one context writes them
+    template <typename Write>
+    void pieces(Write &&write) const {
+        size_t from = 0;
+        for (size_t to : cuts) { write(out.data() + from, to - from); from = to; }
+    }
+};
+
+inline double ringSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// The unfinished record of the chunk framed before goes to the front of `to`, the staged bytes behind it.  `from` is another
+// context's chunk (ts_chunk_carry_over: on one GPU, between peers, or through the host), `to` itself (the chunk's own tail moves
+// to its front), or nothing (the first chunk of the input).
+inline void ringCommit(RingWorker &to, const RingWorker *from, uint64_t carryFrom) {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    if (from == &to) { if (ts_chunk_upload(to.chunk, nullptr, 0, carryFrom, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot carry a record into the next device chunk"); }
+    else if (from && ts_chunk_carry_over(to.chunk, from->chunk, carryFrom, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot carry a record into the next device chunk");
+    if (ts_chunk_commit(to.chunk, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot grow the device chunk");
+    to.st.msCommit += ringSince(t0);
+}
+
+template <typename Worker, typename Ring>
+inline void ringFigures(const char *route, const std::vector<std::unique_ptr<Worker>> &workers, const Ring *ring, double msWrite,
+                        std::vector<ReadRouteDeviceStats> *perDevice) {
+    if (perDevice) perDevice->clear();
+    for (size_t w = 0; w < workers.size(); ++w) {
+        ReadRouteDeviceStats s = workers[w]->st;
+        s.msStage = workers[w]->judged.msStage; s.msFilter = workers[w]->judged.msFilter; s.msGather = workers[w]->judged.msGather;
+        if (ring) s.msCarryWait = ring->frameWaitMs(w);
+        if (perDevice) perDevice->push_back(s);
+        if (std::getenv("TS_TIMING"))
+            std::fprintf(stderr, "%s: context %zu of %zu: %llu chunks, %llu reads judged, %llu bytes; source %.0f ms, carry wait %.1f ms, carry + commit %.1f ms, "
+                         "walk %.1f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms\n", route, w, workers.size(), (unsigned long long)s.chunks,
+                         (unsigned long long)s.recordsJudged, (unsigned long long)s.bytesReceived, s.msSource, s.msCarryWait, s.msCommit, s.msWalk, s.msStage,
+                         s.msFilter, s.msGather);
+    }
+    if (std::getenv("TS_TIMING")) std::fprintf(stderr, "%s: write %.0f ms\n", route, msWrite);
+}
+
+// fastqSubsetDevice's stages as the steps of a ChunkRing.  A chunk's new bytes are staged while the chunks before it are still
+// being framed; frame() is the serial section: carry, commit, ts_fastq_chunk_walk.  A chunk that holds no whole record hands all
+// of its contents on, and the next chunk is that much larger.  A record that is not valid ends the framing; its chunk's valid
+// records are still judged and written before emit() throws, as the loop on one context does.
+class FastqRing {
+public:
+    struct Worker : RingWorker {
+        ChunkFeed::Fill fill;
+        std::vector<ts_fastq_record> recs, withSeq;
+        uint64_t n = 0;                                         // whole records of the chunk
+        int error = TS_FASTQ_OK;
+    };
+    FastqSubsetResult res;
+    double msWrite = 0;
+    std::vector<std::unique_ptr<Worker>> workers;
+
+    FastqRing(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes)
+        : feed_(feed), out_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
+        const uint64_t compCap = feed.compCap(chunkBytes);
+        for (size_t w = 0; w < filter.deviceCount(); ++w) {
+            workers.emplace_back(new Worker());
+            Worker &k = *workers.back();
+            k.ctx = filter.context(w);
+            k.chunk = ts_bam_chunk_create(k.ctx, compCap, chunkBytes);
+            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
+            k.recs.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16));
+        }
+    }
+
+    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
+    RingTake take(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        feed_.take(chunkBytes_, k.fill);
+        k.st.msSource += ringSince(t0);
+        return k.fill.atEnd ? RingTake::Last : RingTake::More;
+    }
+    void stage(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        feed_.stage(k.ctx, k.chunk, k.fill);
+        k.st.msSource += ringSince(t0);
+        ++k.st.chunks; k.st.bytesReceived += k.fill.n;
+    }
+    bool frame(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        ringCommit(k, prev_, prevNext_);
+        prev_ = &k; prevNext_ = 0;
+        k.n = 0; k.error = TS_FASTQ_OK;
+        const int atEnd = k.fill.atEnd ? 1 : 0;
+        if (first_) {
+            if (ts_bam_chunk_size(k.chunk) == 0) {
+                if (atEnd) throw std::runtime_error("FASTQ input is empty");
+                return true;
+            }
+            unsigned char c = 0;
+            if (ts_bam_chunk_read(k.chunk, 0, 1, &c) != TS_OK) throw deviceError(k.ctx, "cannot read the chunk");
+            if (c != '@') throw std::runtime_error("FASTQ input must start with '@'");
+            first_ = false;
+        }
+        uint64_t errorRecord = 0, errorOff = 0;
+        const Clock::time_point t0 = Clock::now();
+        int rc = ts_fastq_chunk_walk(k.chunk, atEnd, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
+        if (rc == TS_ERR_INVALID_ARG && k.n > k.recs.size()) {
+            k.recs.resize(static_cast<size_t>(k.n));
+            rc = ts_fastq_chunk_walk(k.chunk, atEnd, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
+        }
+        if (rc != TS_OK) throw deviceError(k.ctx, "FASTQ walk failed");
+        k.st.msWalk += ringSince(t0);
+        return k.error == TS_FASTQ_OK;
+    }
+    void judge(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        k.fresh();
+        for (size_t a = 0; a < k.n; a += readsPerBatch_) {      // sub-batches of records, in input order
+            const ts_fastq_record *r = k.recs.data() + a;
+            const size_t n = std::min<size_t>(readsPerBatch_, static_cast<size_t>(k.n) - a);
+            k.withSeq.clear(); k.lens.clear();
+            for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].seq_len - r[i].seq_cr); }
+            if (k.withSeq.empty()) continue;                    // (a read without bases is never kept)
+            k.st.recordsJudged += k.withSeq.size();
+            k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
+                         [&](ts_batch *batch) { return ts_fastq_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
+                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                             return ts_fastq_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                         });
+            k.keep();
+        }
+    }
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        k.pieces([&](const unsigned char *p, size_t n) {
+            out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+            if (!out_.good()) throw std::runtime_error("failed while writing FASTQ subset");
+        });
+        res.kept += k.passed; res.total += k.n;
+        msWrite += ringSince(t0);
+        if (k.error != TS_FASTQ_OK) {
+            const char *msg = k.error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : k.error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
+                            : k.error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
+            throw std::runtime_error("FASTQ record " + std::to_string(res.total + 1) + ": " + msg);
+        }
+    }
+
+private:
+    using Clock = std::chrono::steady_clock;
+    ChunkFeed &feed_;
+    std::ostream &out_;
+    size_t readsPerBatch_, chunkBytes_;
+    // the serial section's state: the chunk framed last and where its unfinished record begins; nothing framed yet held a byte
+    const RingWorker *prev_ = nullptr;
+    uint64_t prevNext_ = 0;
+    bool first_ = true;
+};
+
+inline FastqSubsetResult fastqSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                               size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice) {
+    ChunkFeed::Options options;
+    options.cannotOpen = "Stream not successful: " + inFile;
+    options.cannotRead = "read error in FASTQ input";
+    options.dashIsStdin = true;
+    options.uploadFailed = "upload of the FASTQ text failed";
+    options.gzipDevice = false;                                 // (bound to one context: plain gzip is read through zlib here)
+    ChunkFeed feed(filter.context(0), inFile, options);
+    FastqRing steps(filter, feed, out, readsPerBatch, std::max<size_t>(bytesPerBatch, 64));
+    ChunkRing<FastqRing> ring(filter.deviceCount(), 0, steps);
+    ring.run();
+    out.flush();
+    ringFigures(feed.deviceInflate() ? "fastqSubsetDevice (upload + inflate + CRC)" : "fastqSubsetDevice", steps.workers, &ring, steps.msWrite, perDevice);
+    return steps.res;
+}
+
+// bamSubsetDevice's stages as the steps of a ChunkRing.  The chunks hold the members the loop on one context gives them (as many
+// as inflate to bytesPerBatch), so the tables, and what is written before a record that is not valid, are that loop's.  Context 0
+// takes chunks alone until the header is behind it (headerPhase); from the next chunk on the ring deals them.
+class BamRing {
+public:
+    struct Worker : RingWorker {
+        std::vector<ts_bgzf_block> descs;                       // the chunk's members: where they lie, how much they give
+        size_t at = 0, used = 0;
+        uint64_t produced = 0;
+        std::vector<ts_bam_record> table, recs, withSeq;        // a walk's table; the chunk's records
+        const char *error = nullptr;                            // the record the framing stopped at is not valid
+    };
+    BamSubsetStats stats;
+    double msWrite = 0;
+    std::vector<std::unique_ptr<Worker>> workers;
+
+    BamRing(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk)
+        : data_(data), size_(size), writer_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes), walk_(walk),
+          plainCap_((256ull << 20) + 4 + chunkBytes), compCap_(chunkBytes + (1u << 20)) {
+        for (size_t w = 0; w < filter.deviceCount(); ++w) {
+            workers.emplace_back(new Worker());
+            Worker &k = *workers.back();
+            k.ctx = filter.context(w);
+            // (context 0's chunk holds a header of any size the route accepts; the others grow when a carry asks for it)
+            k.chunk = ts_bam_chunk_create(k.ctx, compCap_, w == 0 ? plainCap_ : chunkBytes + (1u << 20));
+            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
+            k.table.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2));
+        }
+    }
+
+    // Chunks 0 .. h on context 0, as the loop on one context runs them, until the header is complete and chunk h's records are
+    // written.  -> h + 1, the ring's first chunk (0 where the input ended before)
+    uint64_t headerPhase() {
+        Worker &k = *workers[0];
+        uint64_t chunks = 0, pos = 0;
+        std::vector<unsigned char> head;                        // host copy of the chunk's leading bytes
+        auto have = [&](uint64_t n) {                           // n more bytes from pos on, and on the host
+            if (held_ - pos < n) return false;
+            if (head.size() < pos + n) {
+                const uint64_t from = head.size(), to = std::min<uint64_t>(held_, std::max<uint64_t>(pos + n, from + (1u << 20)));
+                head.resize(static_cast<size_t>(to));
+                if (ts_bam_chunk_read(k.chunk, from, to - from, head.data() + from) != TS_OK) throw deviceError(k.ctx, "cannot read the BAM header from the device");
+            }
+            return true;
+        };
+        auto bytesAt = [&](uint64_t off) { return head.data() + pos + off; };
+        while (more_ && !header_.done()) {
+            const uint64_t carry = held_ - pos;
+            pick(k, carry);
+            if (carry + k.produced > plainCap_) throw std::runtime_error("BAM header is too large for the device route");
+            const Clock::time_point t0 = Clock::now();
+            inflateMembers(k.ctx, k.chunk, data_ + k.at, k.used, k.descs, pos);
+            k.st.msSource += ringSince(t0);
+            ++k.st.chunks; k.st.bytesReceived += k.produced;
+            ++chunks;
+            held_ = carry + k.produced; pos = 0;
+            head.clear();
+            k.recs.clear(); k.error = nullptr;
+            if (header_.parse(have, bytesAt, pos, writer_)) {
+                walkRecords(k, pos);
+                judge(0, 0);
+                emit(0, 0);
+            } else {
+                prev_ = &k; prevNext_ = pos;
+            }
+        }
+        return more_ && header_.done() ? chunks : 0;
+    }
+
+    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
+    RingTake take(size_t w, uint64_t) {
+        if (!more_) return RingTake::None;
+        pick(*workers[w], 0);
+        return more_ ? RingTake::More : RingTake::Last;
+    }
+    void stage(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        if (ts_chunk_stage_inflate(k.chunk, data_ + k.at, k.used, k.descs.data(), k.descs.size(), nullptr) != TS_OK) throw deviceError(k.ctx, "BGZF inflate failed");
+        membersVerdict(k.ctx, k.chunk);
+        k.st.msSource += ringSince(t0);
+        ++k.st.chunks; k.st.bytesReceived += k.produced;
+    }
+    bool frame(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        ringCommit(k, prev_, prevNext_);
+        held_ = ts_bam_chunk_size(k.chunk);
+        k.recs.clear(); k.error = nullptr;
+        walkRecords(k, 0);
+        return !k.error;
+    }
+    void judge(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        k.fresh();
+        for (size_t a = 0; a < k.recs.size(); a += readsPerBatch_) {        // sub-batches of records, in input order
+            const ts_bam_record *r = k.recs.data() + a;
+            const size_t n = std::min<size_t>(readsPerBatch_, k.recs.size() - a);
+            k.withSeq.clear(); k.lens.clear();
+            for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].l_seq); }
+            if (k.withSeq.empty()) continue;
+            k.st.recordsJudged += k.withSeq.size();
+            k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
+                         [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
+                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                             return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                         });
+            k.keep();
+        }
+    }
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        k.pieces([&](const unsigned char *p, size_t n) { writer_.write(p, n); });
+        uint64_t withBases = 0;
+        for (const ts_bam_record &r : k.recs) withBases += r.l_seq ? 1 : 0;
+        stats.totalRecords += k.recs.size();
+        stats.missingSequenceRecords += k.recs.size() - withBases;
+        stats.passedRecords += k.passed;
+        msWrite += ringSince(t0);
+        if (k.error) throw std::runtime_error(k.error);
+    }
+    // the input has ended: what is left of it is no header and no record
+    void finish() {
+        header_.requireDone();
+        if (held_ != prevNext_) throw std::runtime_error(held_ - prevNext_ < 4 ? "truncated BAM record size" : "truncated BAM record");
+        stats.missingEofBlock = !sawEofMarker_;
+        writer_.finish();
+    }
+
+private:
+    using Clock = std::chrono::steady_clock;
+    // The members of the next chunk, their output from dstBase on (BgzfParallelReader::next's rule, as the loop on one context
+    // applies it: a member that does not parse is an error, a chunk never takes a member past chunkBytes).  The reader's: one
+    // call at a time, no device call.
+    void pick(Worker &k, uint64_t dstBase) {
+        k.descs.clear();
+        k.at = at_; k.used = 0; k.produced = 0;
+        while (at_ + k.used < size_) {
+            BgzfBlockRef ref{};
+            bool eofm = false;
+            const size_t total = parseBgzfBlock(data_ + at_ + k.used, size_ - at_ - k.used, ref, eofm);
+            if (total == 0) throw std::runtime_error(size_ - at_ - k.used < 12 ? "truncated BGZF header" : "truncated BGZF block");
+            if (k.produced + ref.isize > chunkBytes_ || k.used + total > compCap_) break;
+            sawEofMarker_ = sawEofMarker_ || eofm;
+            ts_bgzf_block d{};
+            d.src_off = static_cast<uint64_t>(ref.payload - (data_ + at_)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
+            d.dst_off = dstBase + k.produced;
+            k.descs.push_back(d);
+            k.produced += ref.isize;
+            k.used += total;
+        }
+        at_ += k.used;
+        more_ = k.used > 0 && at_ < size_;
+    }
+    // The chunk's records from `from` on, a table at a time, into k.recs; the serial section's state moves on to this chunk.  A
+    // record that is not valid drops its table, as the loop on one context throws before judging it.
+    void walkRecords(Worker &k, uint64_t from) {
+        const Clock::time_point t0 = Clock::now();
+        uint64_t pos = from;
+        for (;;) {
+            uint64_t n = 0, next = 0, errorOff = 0;
+            int error = 0;
+            if ((walk_ == BamRecordWalk::Index ? ts_bam_chunk_index : ts_bam_chunk_walk)(k.chunk, pos, k.table.data(), k.table.size(), &n, &next, &error, &errorOff) != TS_OK)
+                throw deviceError(k.ctx, "record walk failed");
+            if (error != TS_BAM_OK) {
+                k.error = error == TS_BAM_BAD_BLOCK_SIZE ? "invalid BAM record block_size" : error == TS_BAM_BAD_LENGTHS ? "invalid BAM record lengths"
+                        : error == TS_BAM_FIELDS_EXCEED ? "BAM record fields exceed block_size" : "BAM read name is not NUL-terminated";
+                break;
+            }
+            k.recs.insert(k.recs.end(), k.table.begin(), k.table.begin() + static_cast<std::ptrdiff_t>(n));
+            pos = next;
+            if (n < k.table.size()) break;                      // (a full table: more records may follow in this chunk)
+        }
+        k.st.msWalk += ringSince(t0);
+        prev_ = &k; prevNext_ = pos;
+    }
+
+    const unsigned char *data_;
+    size_t size_;
+    BgzfWriter writer_;
+    BamHeaderParser header_;
+    size_t readsPerBatch_, chunkBytes_;
+    BamRecordWalk walk_;
+    uint64_t plainCap_, compCap_;
+    // the reader's state: the next member, whether one may follow, the EOF marker seen
+    size_t at_ = 0;
+    bool more_ = true, sawEofMarker_ = false;
+    // the serial section's state: the chunk framed last, its size and where its unfinished record begins
+    const RingWorker *prev_ = nullptr;
+    uint64_t prevNext_ = 0, held_ = 0;
+};
+
+inline BamSubsetStats bamSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                          size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice) {
+    MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
+    std::vector<unsigned char> piped;
+    if (!in.data) in.readToEnd(piped, "cannot read BAM input");
+    BamRing steps(filter, in.data ? in.data : piped.data(), in.data ? in.size : piped.size(), out, readsPerBatch, std::max<size_t>(bytesPerBatch, 1u << 20), walk);
+    const uint64_t firstChunk = steps.headerPhase();
+    std::unique_ptr<ChunkRing<BamRing>> ring;
+    if (firstChunk) {
+        ring.reset(new ChunkRing<BamRing>(filter.deviceCount(), firstChunk, steps));
+        ring->run();
+    }
+    steps.finish();
+    ringFigures(walk == BamRecordWalk::Index ? "bamSubsetDevice (index)" : "bamSubsetDevice (serial)", steps.workers, ring.get(), steps.msWrite, perDevice);
+    return steps.stats;
+}
+
+}  // namespace detail
 
 inline const char *scaffoldTypeToString(ScaffoldType t) {       // src/tools.cpp
     static const char *names[] = {"t2t", "gapped_t2t", "misassembly", "gapped_misassembly", "incomplete",

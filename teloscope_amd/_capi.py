@@ -279,6 +279,7 @@ SYMBOLS = [
     "ts_match_lines_format", "ts_free_match_text", "ts_scan_segments_text", "ts_match_text_stats",
     "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
     "ts_bam_chunk_index", "ts_bam_chunk_set_index_geometry", "ts_bam_index_stats",
+    "ts_chunk_stage_upload", "ts_chunk_stage_inflate", "ts_chunk_staged", "ts_chunk_commit",
 ]
 
 
@@ -484,6 +485,11 @@ def lib():
     L.ts_chunk_data.argtypes = [C.c_void_p]
     L.ts_chunk_data.restype = C.c_void_p
     L.ts_chunk_carry_over.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.ts_chunk_stage_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.ts_chunk_stage_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BgzfBlock), C.c_size_t, C.c_void_p]
+    L.ts_chunk_staged.argtypes = [C.c_void_p]
+    L.ts_chunk_staged.restype = C.c_uint64
+    L.ts_chunk_commit.argtypes = [C.c_void_p, C.c_void_p]
     L.ts_fasta_chunk_strict.argtypes = [C.c_void_p, C.POINTER(FastaRecord), C.c_size_t, C.c_void_p, C.c_void_p]
     L.ts_gfa_chunk_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(GfaFlagged), C.c_uint64, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64)]

@@ -121,6 +121,36 @@ int ts_bam_chunk_inflate(ts_bam_chunk *ch, const void *compressed, uint64_t n, c
     return TS_OK;
 }
 
+int ts_chunk_stage_inflate(ts_bam_chunk *ch, const void *compressed, uint64_t n, const ts_bgzf_block *blocks, size_t n_blocks,
+                           void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if ((n && !compressed) || (n_blocks && !blocks) || n > ch->comp_cap || n_blocks > 0xffffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_stage_inflate: null or out-of-range argument");
+    uint64_t end = ch->stage_n;
+    for (size_t i = 0; i < n_blocks; ++i)
+        if (blocks[i].dst_off < (1ull << 40) && blocks[i].isize <= 65536u) end =std::max<uint64_t>(end, blocks[i].dst_off + blocks[i].isize);
+    { const int rc = ts_chunk_stage_reserve(ch, end); if (rc != TS_OK) return rc; }
+    std::string why;
+    if (!descriptors_ok(blocks, n_blocks, n, ch->stage_cap, why, ch->stage_n)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_stage_inflate: " + why);
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    ch->stage_n = end;
+    ch->n_blocks = n_blocks;
+    if (n_blocks) {
+        HIP_TRY(ctx, ch->bam.d_blocks.ensure(n_blocks * sizeof(ts_bgzf_block)));
+        HIP_TRY(ctx, ch->bam.d_result.ensure(n_blocks * 4));
+        if (n) HIP_TRY(ctx, hipMemcpyAsync(ch->d_comp.p, compressed, (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync((char *)ch->d_comp.p + n, 0, 16, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ch->bam.d_blocks.p, blocks, n_blocks * sizeof(ts_bgzf_block), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync(ch->bam.d_result.p, 0xff, n_blocks * 4, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));                // (the descriptors are the caller's memory, as for ts_bam_chunk_inflate)
+        if (ts_k_launch_bgzf_inflate(ch->d_comp.p, ch->bam.d_blocks.p, (uint32_t)n_blocks, ch->d_stage.p, (uint32_t *)ch->bam.d_result.p, stream) != 0)
+            return ctx->fail(TS_ERR_HIP, "ts_chunk_stage_inflate: kernel launch failed");
+    }
+    return TS_OK;
+}
+
 int ts_bam_chunk_status(ts_bam_chunk *ch, ts_bgzf_status *first_bad) {
     if (!ch || !first_bad) return TS_ERR_INVALID_ARG;
     ts_ctx *ctx = ch->ctx;

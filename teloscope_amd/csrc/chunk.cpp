@@ -19,6 +19,21 @@ int ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64
     return TS_OK;
 }
 
+int ts_chunk_stage_reserve(ts_bam_chunk *ch, uint64_t stage_cap) {
+    ts_ctx *ctx = ch->ctx;
+    if (stage_cap > (1ull << 40)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_stage: capacity out of range");
+    if (stage_cap <= ch->stage_cap && ch->d_stage.p) return TS_OK;
+    DEVICE_TRY(ctx);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(stage_cap, 64), ch->stage_cap + ch->stage_cap / 2);
+    DevBuf grown;
+    if (grown.ensure((size_t)cap + 64) != hipSuccess) return ctx->fail(TS_ERR_ALLOC, "ts_chunk_stage: device allocation failed");
+    if (ch->stage_n) HIP_TRY(ctx, hipMemcpy(grown.p, ch->d_stage.p, (size_t)ch->stage_n, hipMemcpyDeviceToDevice));
+    ch->d_stage = std::move(grown);
+    ch->stage_cap = cap;
+    return TS_OK;
+}
+
 int ts_chunk_line_index(ts_bam_chunk *ch, int at_end, const char *who, const char *counted, LineIndex *ix) {
     ts_ctx *ctx = ch->ctx;
     ts_bam_chunk::Lines &L = ch->lines;
@@ -169,8 +184,8 @@ int ts_chunk_upload(ts_chunk *ch, const void *bytes, uint64_t n, uint64_t carry_
 int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void *stream) {
     if (!to) return TS_ERR_INVALID_ARG;
     ts_ctx *ctx = to->ctx;
-    if (!from || from == to || from->ctx != ctx || carry_from > from->plain_n)
-        return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_carry_over: needs two chunks of one context and an offset inside the source");
+    if (!from || from == to || from->ctx->device == kNoDevice || carry_from > from->plain_n)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_carry_over: needs two chunks on devices and an offset inside the source");
     const uint64_t n = from->plain_n - carry_from;
     to->plain_n = 0;                                           // (what the destination held is dropped, not kept by a growth)
     to->n_blocks = 0;
@@ -178,9 +193,58 @@ int ts_chunk_carry_over(ts_chunk *to, ts_chunk *from, uint64_t carry_from, void 
     if (n > to->plain_cap) { const int rc = ts_chunk_reserve(to, n); if (rc != TS_OK) return rc; }
     DEVICE_TRY(ctx);
     hipStream_t st = (hipStream_t)stream;
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(to->d_plain.p, (const char *)from->d_plain.p + carry_from, (size_t)n, hipMemcpyDeviceToDevice, st));
+    const char *src = (const char *)from->d_plain.p + carry_from;
+    const int dev_to = ctx->device, dev_from = from->ctx->device;
+    if (n && dev_from == dev_to) {                             // one GPU, whichever contexts: device to device
+        HIP_TRY(ctx, hipMemcpyAsync(to->d_plain.p, src, (size_t)n, hipMemcpyDeviceToDevice, st));
+    } else if (n) {
+        // two GPUs: what the source's device still has in flight for these bytes is waited for there, then a peer copy where the
+        // destination's device can reach the source's memory, else the bytes bounce through host memory
+        { DeviceGuard other(dev_from); HIP_TRY(ctx, other.error()); HIP_TRY(ctx, hipDeviceSynchronize()); }
+        int peer = 0;
+        HIP_TRY(ctx, hipDeviceCanAccessPeer(&peer, dev_to, dev_from));
+        if (peer) HIP_TRY(ctx, hipMemcpyPeerAsync(to->d_plain.p, dev_to, src, dev_from, (size_t)n, st));
+        else {
+            std::vector<char> bounce((size_t)n);
+            HIP_TRY(ctx, hipMemcpy(bounce.data(), src, (size_t)n, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpyAsync(to->d_plain.p, bounce.data(), (size_t)n, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));            // (the bounce buffer ends with this scope)
+        }
+    }
     HIP_TRY(ctx, hipStreamSynchronize(st));
     to->plain_n = n;
+    return TS_OK;
+}
+
+int ts_chunk_stage_upload(ts_chunk *ch, const void *bytes, uint64_t n, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if ((n && !bytes) || n > (1ull << 40)) return ctx->fail(TS_ERR_INVALID_ARG, "ts_chunk_stage_upload: null or out-of-range argument");
+    { const int rc = ts_chunk_stage_reserve(ch, ch->stage_n + n); if (rc != TS_OK) return rc; }
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync((char *)ch->d_stage.p + ch->stage_n, bytes, (size_t)n, hipMemcpyHostToDevice, st));
+    ch->stage_n += n;
+    ch->n_blocks = 0;
+    HIP_TRY(ctx, hipStreamSynchronize(st));                    // (the bytes are the caller's memory: they have left it when this returns)
+    return TS_OK;
+}
+
+uint64_t ts_chunk_staged(const ts_chunk *ch) { return ch ? ch->stage_n : 0; }
+
+int ts_chunk_commit(ts_chunk *ch, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    const uint64_t n = ch->stage_n;
+    if (ch->plain_n + n > ch->plain_cap) { const int rc = ts_chunk_reserve(ch, ch->plain_n + n); if (rc != TS_OK) return rc; }
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    // (the chunk's first byte stays where every kernel expects it; the staged bytes land wherever the carry ends)
+    if (n) HIP_TRY(ctx, hipMemcpyAsync((char *)ch->d_plain.p + ch->plain_n, ch->d_stage.p, (size_t)n, hipMemcpyDeviceToDevice, st));
+    ch->plain_n += n;
+    ch->stage_n = 0;
+    ch->lines.valid = false;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     return TS_OK;
 }
 

@@ -24,6 +24,10 @@ struct ts_bam_chunk {
     // the compressed and the plain bytes (both readable 64 bytes beyond their capacity), the carry's bounce buffer, a result block
     // of 64 bytes, the caller's pass bytes; the record table of a walk or a gather, the passing records' places and bytes
     DevBuf d_comp, d_plain, d_tmp, d_out, d_pass, d_recs, d_dst, d_gather;
+    // the staging region (ts_chunk_stage_upload / ts_chunk_stage_inflate): new bytes that wait for the carry they go behind
+    // (ts_chunk_commit); readable 64 bytes beyond stage_cap, as d_plain is
+    DevBuf d_stage;
+    uint64_t stage_cap = 0, stage_n = 0;
     // the line index (ts_chunk_line_index) and the record of what it indexed: `ix` describes the chunk's bytes as long as `valid`
     // holds, plain_n == size and the caller's at_end is the one it was made with; every index made has another generation
     struct Lines {
@@ -61,6 +65,9 @@ struct ts_bam_chunk {
 
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
 int  ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry);
+
+// room for stage_cap staged bytes (what is staged is kept); waits for the device when the region grows
+int  ts_chunk_stage_reserve(ts_bam_chunk *ch, uint64_t stage_cap);
 
 // The line index of the chunk's bytes, on the null stream: '\n' counted per slice and summed (its two words come back through
 // ch->d_out and are checked against the chunk), then every line's start, first byte and '\r' flag into ch->lines.d_lines
