@@ -1724,6 +1724,9 @@ private:
 // per read), staged into a tips-only batch's input buffer by stage(batch), judged by the scan and the predicate the host routes
 // use (ts_batch_scan + ts_batch_read_pass, with the regrow-and-rescan of an overflowed batch: include/teloscan.h), the passing
 // records' bytes gathered by gather(dPass, dst, cap, &bytes, &nPassed) into `kept`.
+using Clock = std::chrono::steady_clock;
+inline double since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }    // ms
+
 struct ReadJudge {
     double msStage = 0, msFilter = 0, msGather = 0;
     std::vector<unsigned char> kept;
@@ -1731,8 +1734,6 @@ struct ReadJudge {
 
     template <typename Stage, typename Gather>
     void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather) {
-        using Clock = std::chrono::steady_clock;
-        auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
         struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
         if (!batch.p) throw deviceError(ctx, "cannot plan the read batch");
         Clock::time_point t0 = Clock::now();
@@ -1762,294 +1763,60 @@ struct ReadJudge {
 
 }  // namespace detail
 
-// The device route of --bam-subset (same arguments, statistics, exceptions and output bytes as bamSubset, which stays the
-// default): the compressed BGZF members cross PCIe and the uncompressed BAM stream exists in HBM only.  The input is
-// detail::MappedInput's (a pipe and stdin are read to their end).  Per chunk of ~bytesPerBatch uncompressed bytes: the members
-// are located on the host (parseBgzfBlock reads no payload byte), inflated and checksummed on the device
-// (detail::inflateMembers), the records walked and validated there (ts_bam_chunk_walk or ts_bam_chunk_index: the table comes back), SEQ decoded into
-// a tips-only batch's input buffer (ts_bam_chunk_decode), judged and the passing records' bytes gathered (detail::ReadJudge
-// with ts_bam_chunk_gather).
-// The BAM header is parsed on the host from the chunk's leading bytes.  A filter of one context runs the loop below; a filter of
-// several contexts (ordinals may repeat) deals the chunks to all of them, chunk k to context k mod N, once context 0 has the
-// header behind it (detail::BamRing, below), with the same statistics, exceptions and output bytes.  perDevice, where given,
-// receives one entry per context.
-// What a maintainer of the reference would call from runBamSubsetMode (src/bam.cpp:262-316) in place of subsetBam.
-// `walk` chooses how a chunk's records are framed: Serial is ts_bam_chunk_walk, one wave that follows the records one after the
-// other; Index is ts_bam_chunk_index, which finds record chains in all spans of the chunk at once and links them.  Both give
-// the same table, so the output bytes do not depend on it; the TS_TIMING line names the one that ran.  Index is the default: its
-// walk stage measured 6.8 ms against 98.4 ms on a HiFi BAM and 11 ms against 1 112 ms on a BAM of 150-base reads
+// ---- the two device read routes, bamSubsetDevice and fastqSubsetDevice: one set of chunk steps each, for a filter of any number
+// of contexts ----
+// A route's steps (detail::BamChunkSteps, detail::FastqChunkSteps) have two ways to bring a chunk's bytes in; everything behind
+// the fill (framing, judging, emitting, the exception texts, the figures) exists once and serves both.
+//   In place  the new bytes go straight behind the unfinished record in the context's own chunk, and the chunk is framed, judged
+//             and emitted on the caller's thread, each sub-batch's passing bytes straight from the judge to the output: no
+//             staging region, no commit, no carry between chunks, no thread.  A filter of one context takes its whole input so;
+//             on several contexts the BAM route takes its chunks so on context 0 until the header is behind it.
+//   Dealt     detail::ChunkRing (teloscope_mi355x_ring.hpp) deals chunk k to context k mod N (ordinals may repeat), a thread per
+//             context: the new bytes are staged beside the chunk while the chunks before it are still being framed, frame()
+//             carries the unfinished record over and commits the staged bytes behind it, and judge() keeps the passing bytes
+//             until emit() has its turn.
+// The result, the statistics, the exceptions and the output bytes, those written before a failure included, do not depend on the
+// number of contexts (tests/test_gpu_read_routes_multi.py).
+
+// `walk` of bamSubsetDevice chooses how a chunk's records are framed: Serial is ts_bam_chunk_walk, one wave that follows the
+// records one after the other; Index is ts_bam_chunk_index, which finds record chains in all spans of the chunk at once and links
+// them.  Both give the same table, so the output bytes do not depend on it; the TS_TIMING lines name the one that ran.  Index is
+// the default: its walk stage measured 6.8 ms against 98.4 ms on a HiFi BAM and 11 ms against 1 112 ms on a BAM of 150-base reads
 // (profiles/bam/bam_index_rate.txt).
 enum class BamRecordWalk { Serial, Index };
 // One context's share of a device read route: chunks it took, reads with bases it judged, uncompressed bytes it received, and the
 // milliseconds its thread spent in the source (reading, upload, inflate and CRC), waiting for the chunk before its own to be
-// framed (several contexts only: the serial section as this context sees it), placing the carry and committing the staged bytes
-// behind it (several contexts only), framing records (index or walk), and in ReadJudge's stage, filter and gather.
+// framed (dealt chunks only: the serial section as this context sees it), placing the carry and committing the staged bytes
+// behind it (dealt chunks only), framing records (index or walk), and in ReadJudge's stage, filter and gather.
 struct ReadRouteDeviceStats {
     uint64_t chunks = 0, recordsJudged = 0, bytesReceived = 0;
     double msSource = 0, msCarryWait = 0, msCommit = 0, msWalk = 0, msStage = 0, msFilter = 0, msGather = 0;
 };
-namespace detail {
-inline BamSubsetStats bamSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
-                                   size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice);
-inline FastqSubsetResult fastqSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
-                                        size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice);
-}  // namespace detail
-inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
-                                      BamRecordWalk walk = BamRecordWalk::Index, std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
-    if (filter.deviceCount() > 1) return detail::bamSubsetDeviceRing(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice);
-    BamSubsetStats stats;
-    ts_ctx *ctx = filter.context(0);
-    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
-    // the compressed input: a regular file is mapped, a pipe is read to its end
-    detail::MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
-    std::vector<unsigned char> piped;
-    if (!in.data) in.readToEnd(piped, "cannot read BAM input");
-    const unsigned char *data = in.data ? in.data : piped.data();
-    const size_t size = in.data ? in.size : piped.size();
-    using Clock = std::chrono::steady_clock;
-    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    double msInflate = 0, msWalk = 0, msWrite = 0;
-    ReadRouteDeviceStats one;
 
-    // a chunk holds the unconsumed tail of the one before (at most a record: 4 bytes + 256 MiB) and the new members' output
-    const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 1u << 20);
-    const uint64_t maxCarry = (256ull << 20) + 4, plainCap = maxCarry + chunkBytes, compCap = chunkBytes + (1u << 20);
-    struct ChunkPtr { ts_bam_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, compCap, plainCap)};
-    if (!chunk.p) throw fail("cannot make the device chunk");
-    detail::BgzfWriter writer(out);
-
-    detail::BamHeaderParser header;
-    uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
-    std::vector<unsigned char> head;            // host copy of the chunk's leading bytes (header phase only)
-    auto have = [&](uint64_t n) {               // n more bytes from pos on, and on the host
-        if (held - pos < n) return false;
-        if (head.size() < pos + n) {
-            const uint64_t from = head.size(), to = std::min<uint64_t>(held, std::max<uint64_t>(pos + n, from + (1u << 20)));
-            head.resize(static_cast<size_t>(to));
-            if (ts_bam_chunk_read(chunk.p, from, to - from, head.data() + from) != TS_OK) throw fail("cannot read the BAM header from the device");
-        }
-        return true;
-    };
-    auto bytesAt = [&](uint64_t off) { return head.data() + pos + off; };
-
-    std::vector<ts_bgzf_block> descs;
-    std::vector<ts_bam_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), withSeq;
-    std::vector<uint64_t> lens;
-    detail::ReadJudge judged;
-    auto judge = [&](const ts_bam_record *r, size_t n) {      // one sub-batch of records, in input order
-        withSeq.clear(); lens.clear();
-        for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { withSeq.push_back(r[i]); lens.push_back(r[i].l_seq); }
-        stats.totalRecords += n;
-        stats.missingSequenceRecords += n - withSeq.size();
-        if (withSeq.empty()) return;
-        one.recordsJudged += withSeq.size();
-        judged.run(ctx, chunk.p, lens, "SEQ decode failed",
-                   [&](ts_batch *batch) { return ts_bam_chunk_decode(chunk.p, withSeq.data(), withSeq.size(), batch, nullptr); },
-                   [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                       return ts_bam_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
-                   });
-        const Clock::time_point t0 = Clock::now();
-        writer.write(judged.kept.data(), static_cast<size_t>(judged.bytes));
-        stats.passedRecords += judged.nPassed;
-        msWrite += since(t0);
-    };
-
-    size_t at = 0;
-    bool more = true, sawEofMarker = false;
-    while (more) {
-        const uint64_t carry = held - pos;
-        descs.clear();
-        size_t used = 0;
-        uint64_t produced = 0;
-        // (not pickBgzfMembers: here a member that does not parse is an error, not a change of source, a chunk never takes a member
-        // past chunkBytes, and there is one inflate call per chunk)
-        while (at + used < size) {                              // the members of this chunk (BgzfParallelReader::next's rule)
-            detail::BgzfBlockRef ref{};
-            bool eofm = false;
-            const size_t total = detail::parseBgzfBlock(data + at + used, size - at - used, ref, eofm);
-            if (total == 0) throw std::runtime_error(size - at - used < 12 ? "truncated BGZF header" : "truncated BGZF block");
-            if (produced + ref.isize > chunkBytes || used + total > compCap) break;
-            sawEofMarker = sawEofMarker || eofm;
-            ts_bgzf_block d{};
-            d.src_off = static_cast<uint64_t>(ref.payload - (data + at)); d.payload_len = ref.payloadLen; d.isize = ref.isize; d.crc = ref.crc;
-            d.dst_off = carry + produced;
-            descs.push_back(d);
-            produced += ref.isize;
-            used += total;
-        }
-        if (carry + produced > plainCap) throw std::runtime_error("BAM header is too large for the device route");
-        Clock::time_point t0 = Clock::now();
-        detail::inflateMembers(ctx, chunk.p, data + at, used, descs, pos);
-        msInflate += since(t0);
-        at += used;
-        ++one.chunks; one.bytesReceived += produced;
-        more = used > 0 && at < size;
-        held = carry + produced; pos = 0;
-        head.clear();
-        if (header.done() || header.parse(have, bytesAt, pos, writer)) {
-            head.clear(); head.shrink_to_fit();
-            for (;;) {
-                uint64_t n = 0, next = 0, errorOff = 0;
-                int error = 0;
-                t0 = Clock::now();
-                if ((walk == BamRecordWalk::Index ? ts_bam_chunk_index : ts_bam_chunk_walk)(chunk.p, pos, recs.data(), recs.size(), &n, &next, &error, &errorOff) != TS_OK)
-                    throw fail("record walk failed");
-                msWalk += since(t0);
-                if (error == TS_BAM_BAD_BLOCK_SIZE) throw std::runtime_error("invalid BAM record block_size");
-                if (error == TS_BAM_BAD_LENGTHS) throw std::runtime_error("invalid BAM record lengths");
-                if (error == TS_BAM_FIELDS_EXCEED) throw std::runtime_error("BAM record fields exceed block_size");
-                if (error != TS_BAM_OK) throw std::runtime_error("BAM read name is not NUL-terminated");
-                for (size_t a = 0; a < n; a += readsPerBatch) judge(recs.data() + a, std::min<size_t>(readsPerBatch, static_cast<size_t>(n) - a));
-                pos = next;
-                if (n < recs.size()) break;                     // (a full table: more records may follow in this chunk)
-            }
-        }
-    }
-    header.requireDone();
-    if (held != pos) throw std::runtime_error(held - pos < 4 ? "truncated BAM record size" : "truncated BAM record");
-    stats.missingEofBlock = !sawEofMarker;
-    writer.finish();
-    if (std::getenv("TS_TIMING"))
-        std::fprintf(stderr, "bamSubsetDevice: upload + inflate + CRC %.0f ms, walk (%s) %.1f ms, decode %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
-                     msInflate, walk == BamRecordWalk::Index ? "index" : "serial", msWalk, judged.msStage, judged.msFilter, judged.msGather, msWrite);
-    if (perDevice) {
-        one.msSource = msInflate; one.msWalk = msWalk; one.msStage = judged.msStage; one.msFilter = judged.msFilter; one.msGather = judged.msGather;
-        perDevice->assign(1, one);
-    }
-    return stats;
-}
-
-// The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as
-// fastqSubset, which stays the default): the FASTQ text exists in HBM one chunk of ~bytesPerBatch bytes at a time and the host
-// reads none of it.  The text gets there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, or a
-// stream through zlib or read(2); `-` is stdin, always through zlib), and behind the source the stages are the same: lines
-// indexed and records framed and validated (ts_fastq_chunk_walk: the table comes back), sequences staged into a tips-only
-// batch's input buffer (ts_fastq_chunk_stage), judged and the passing records' bytes gathered (detail::ReadJudge with
-// ts_fastq_chunk_gather).  The bytes behind the last whole record stay in the chunk for the next fill; a record larger than a
-// chunk makes the chunk grow.  A filter of one context runs the loop below; a filter of several contexts (ordinals may repeat)
-// deals the chunks to all of them, chunk k to context k mod N (detail::FastqRing, below), with the same result, exceptions and
-// output bytes; there plain gzip is read through zlib, because the opt-in device gzip source (ChunkFeed::Gzip) is bound to one
-// context.  perDevice, where given, receives one entry per context.
-// What a maintainer of the reference would call from Input::readFastqSubset (src/input.cpp:737-832) in place of its loop.
-inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                           size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
-                                           std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
-    if (filter.deviceCount() > 1) return detail::fastqSubsetDeviceRing(inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice);
-    FastqSubsetResult res;
-    ts_ctx *ctx = filter.context(0);
-    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
-    detail::ChunkFeed::Options options;
-    options.cannotOpen = "Stream not successful: " + inFile;
-    options.cannotRead = "read error in FASTQ input";
-    options.dashIsStdin = true;
-    options.uploadFailed = "upload of the FASTQ text failed";
-    detail::ChunkFeed feed(ctx, inFile, options);
-    using Clock = std::chrono::steady_clock;
-    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    double msUpload = 0, msIndex = 0, msWrite = 0;
-    ReadRouteDeviceStats one;
-
-    const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 64);
-    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, feed.compCap(chunkBytes), chunkBytes)};
-    if (!chunk.p) throw fail("cannot make the device chunk");
-
-    std::vector<ts_fastq_record> recs(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16)), withSeq;
-    std::vector<uint64_t> lens;
-    detail::ReadJudge judged;
-    auto judge = [&](const ts_fastq_record *r, size_t n) {      // one sub-batch of records, in input order
-        withSeq.clear(); lens.clear();
-        for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { withSeq.push_back(r[i]); lens.push_back(r[i].seq_len - r[i].seq_cr); }
-        res.total += n;
-        if (withSeq.empty()) return;                            // (a read without bases is never kept)
-        one.recordsJudged += withSeq.size();
-        judged.run(ctx, chunk.p, lens, "staging the sequences failed",
-                   [&](ts_batch *batch) { return ts_fastq_chunk_stage(chunk.p, withSeq.data(), withSeq.size(), batch, nullptr); },
-                   [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                       return ts_fastq_chunk_gather(chunk.p, withSeq.data(), withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
-                   });
-        const Clock::time_point t0 = Clock::now();
-        out.write(reinterpret_cast<const char *>(judged.kept.data()), static_cast<std::streamsize>(judged.bytes));
-        if (!out.good()) throw std::runtime_error("failed while writing FASTQ subset");
-        res.kept += judged.nPassed;
-        msWrite += since(t0);
-    };
-
-    uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
-    bool first = true, atEnd = false;
-    while (!atEnd) {
-        const uint64_t carry = held - pos;
-        // a chunk that held no whole record (a record larger than it) takes as much again
-        const size_t want = static_cast<size_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0));
-        Clock::time_point t0 = Clock::now();
-        atEnd = feed.fill(chunk.p, pos, want);
-        msUpload += since(t0);
-        ++one.chunks; one.bytesReceived += ts_bam_chunk_size(chunk.p) - carry;
-        held = ts_bam_chunk_size(chunk.p); pos = 0;
-        if (first) {
-            if (held == 0) {
-                if (atEnd) throw std::runtime_error("FASTQ input is empty");
-                continue;
-            }
-            unsigned char c = 0;
-            if (ts_bam_chunk_read(chunk.p, 0, 1, &c) != TS_OK) throw fail("cannot read the chunk");
-            if (c != '@') throw std::runtime_error("FASTQ input must start with '@'");
-            first = false;
-        }
-        uint64_t n = 0, next = 0, errorRecord = 0, errorOff = 0;
-        int error = TS_FASTQ_OK;
-        t0 = Clock::now();
-        int rc = ts_fastq_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, &error, &errorRecord, &errorOff);
-        if (rc == TS_ERR_INVALID_ARG && n > recs.size()) {
-            recs.resize(static_cast<size_t>(n));
-            rc = ts_fastq_chunk_walk(chunk.p, atEnd ? 1 : 0, recs.data(), recs.size(), &n, &next, &error, &errorRecord, &errorOff);
-        }
-        if (rc != TS_OK) throw fail("FASTQ walk failed");
-        msIndex += since(t0);
-        for (size_t a = 0; a < n; a += readsPerBatch) judge(recs.data() + a, std::min<size_t>(readsPerBatch, static_cast<size_t>(n) - a));
-        if (error != TS_FASTQ_OK) {
-            const char *msg = error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
-                            : error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
-            throw std::runtime_error("FASTQ record " + std::to_string(res.total + 1) + ": " + msg);
-        }
-        pos = next;
-    }
-    out.flush();
-    if (std::getenv("TS_TIMING"))
-        std::fprintf(stderr, "fastqSubsetDevice: upload%s %.0f ms, index %.0f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms, write %.0f ms\n",
-                     feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, judged.msStage, judged.msFilter, judged.msGather, msWrite);
-    if (perDevice) {
-        one.msSource = msUpload; one.msWalk = msIndex; one.msStage = judged.msStage; one.msFilter = judged.msFilter; one.msGather = judged.msGather;
-        perDevice->assign(1, one);
-    }
-    return res;
-}
-
-// ---- the two read routes on a filter of several contexts: the chunks of the input dealt to all of them (detail::ChunkRing) ----
 namespace detail {
 
-// What a context of a ring route owns: its chunk (contents and staging region), its judge and pass buffer, the passing records
-// of the chunk it is working on, and its figures.
-struct RingWorker {
+// What a context of a read route owns: its chunk (contents and, once a chunk is dealt to it, a staging region), its judge and
+// pass buffer, the passing records of the dealt chunk it is working on, and its figures.
+struct ChunkWorker {
     ts_ctx *ctx = nullptr;
     ts_chunk *chunk = nullptr;
     ReadJudge judged;
     std::vector<uint64_t> lens;
-    std::vector<unsigned char> out;                             // the chunk's passing records, in input order
+    std::vector<unsigned char> out;                             // a dealt chunk's passing records, in input order
     std::vector<size_t> cuts;                                   // where each sub-batch's records end in `out`: the writer's pieces
-    uint64_t passed = 0;
+    uint64_t passed = 0;                                        // the chunk's passing records, however it came in
     ReadRouteDeviceStats st;
-    RingWorker() = default;
-    RingWorker(const RingWorker &) = delete;
-    RingWorker &operator=(const RingWorker &) = delete;
-    ~RingWorker() { ts_bam_chunk_destroy(chunk); }
+    ChunkWorker() = default;
+    ChunkWorker(const ChunkWorker &) = delete;
+    ChunkWorker &operator=(const ChunkWorker &) = delete;
+    ~ChunkWorker() { ts_bam_chunk_destroy(chunk); }
     void fresh() { out.clear(); cuts.clear(); passed = 0; }
+    // a dealt chunk's sub-batch waits here for the chunk's turn to emit
     void keep() {
         out.insert(out.end(), judged.kept.begin(), judged.kept.begin() + static_cast<std::ptrdiff_t>(judged.bytes));
         cuts.push_back(out.size());
-        passed += judged.nPassed;
     }
-    // the pieces in the order and sizes the loop on one context writes them
+    // the kept pieces in the order and sizes an in-place chunk writes them (of which it keeps none)
     template <typename Write>
     void pieces(Write &&write) const {
         size_t from = 0;
@@ -2057,22 +1824,22 @@ struct RingWorker {
     }
 };
 
-inline double ringSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
-// The unfinished record of the chunk framed before goes to the front of `to`, the staged bytes behind it.  `from` is another
-// context's chunk (ts_chunk_carry_over: on one GPU, between peers, or through the host), `to` itself (the chunk's own tail moves
-// to its front), or nothing (the first chunk of the input).
-inline void ringCommit(RingWorker &to, const RingWorker *from, uint64_t carryFrom) {
-    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+// A dealt chunk comes together: the unfinished record of the chunk framed before goes to the front of `to`, the staged bytes
+// behind it.  `from` is another context's chunk (ts_chunk_carry_over: on one GPU, between peers, or through the host), `to`
+// itself (the chunk's own tail moves to its front), or nothing (the first chunk of the input).
+inline void ringCommit(ChunkWorker &to, const ChunkWorker *from, uint64_t carryFrom) {
+    const Clock::time_point t0 = Clock::now();
     if (from == &to) { if (ts_chunk_upload(to.chunk, nullptr, 0, carryFrom, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot carry a record into the next device chunk"); }
     else if (from && ts_chunk_carry_over(to.chunk, from->chunk, carryFrom, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot carry a record into the next device chunk");
     if (ts_chunk_commit(to.chunk, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot grow the device chunk");
-    to.st.msCommit += ringSince(t0);
+    to.st.msCommit += since(t0);
 }
 
+// A route's figures, to perDevice and, under TS_TIMING, to stderr: a line per context and the write line, each beginning with
+// `route`.  `ring` is the ring that dealt the chunks, or nothing (every chunk came in place: no context waited for another).
 template <typename Worker, typename Ring>
-inline void ringFigures(const char *route, const std::vector<std::unique_ptr<Worker>> &workers, const Ring *ring, double msWrite,
-                        std::vector<ReadRouteDeviceStats> *perDevice) {
+inline void routeFigures(const char *route, const std::vector<std::unique_ptr<Worker>> &workers, const Ring *ring, double msWrite,
+                         std::vector<ReadRouteDeviceStats> *perDevice) {
     if (perDevice) perDevice->clear();
     for (size_t w = 0; w < workers.size(); ++w) {
         ReadRouteDeviceStats s = workers[w]->st;
@@ -2088,14 +1855,15 @@ inline void ringFigures(const char *route, const std::vector<std::unique_ptr<Wor
     if (std::getenv("TS_TIMING")) std::fprintf(stderr, "%s: write %.0f ms\n", route, msWrite);
 }
 
-// fastqSubsetDevice's stages as the steps of a ChunkRing.  A chunk's new bytes are staged while the chunks before it are still
-// being framed; frame() is the serial section: carry, commit, ts_fastq_chunk_walk.  A chunk that holds no whole record hands all
-// of its contents on, and the next chunk is that much larger.  A record that is not valid ends the framing; its chunk's valid
-// records are still judged and written before emit() throws, as the loop on one context does.
-class FastqRing {
+// fastqSubsetDevice's stages.  The first chunk must begin with '@'; ts_fastq_chunk_walk frames and validates the records, and the
+// bytes behind the last whole one go in front of the next chunk.  A record that is not valid ends the framing; its chunk's valid
+// records are still judged and written before emit() throws.  A chunk that holds no whole record (a record larger than it)
+// passes all of its contents on: in place the next fill takes as much again, so the chunk doubles; a dealt chunk takes
+// chunkBytes more.
+class FastqChunkSteps {
 public:
-    struct Worker : RingWorker {
-        ChunkFeed::Fill fill;
+    struct Worker : ChunkWorker {
+        ChunkFeed::Fill fill;                                   // a dealt chunk's new bytes
         std::vector<ts_fastq_record> recs, withSeq;
         uint64_t n = 0;                                         // whole records of the chunk
         int error = TS_FASTQ_OK;
@@ -2104,7 +1872,7 @@ public:
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    FastqRing(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes)
+    FastqChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes)
         : feed_(feed), out_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
         const uint64_t compCap = feed.compCap(chunkBytes);
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
@@ -2117,27 +1885,62 @@ public:
         }
     }
 
+    // The whole input as in-place chunks of context 0, on the caller's thread: any source of the feed, ChunkFeed::Gzip included
+    void runInPlace() {
+        Worker &k = *workers[0];
+        for (bool atEnd = false; !atEnd;) {
+            const uint64_t carry = ts_bam_chunk_size(k.chunk) - prevNext_;
+            // a chunk that held no whole record takes as much again
+            const size_t want = static_cast<size_t>(std::max<uint64_t>(chunkBytes_, prevNext_ == 0 ? carry : 0));
+            const Clock::time_point t0 = Clock::now();
+            atEnd = feed_.fill(k.chunk, prevNext_, want);
+            k.st.msSource += since(t0);
+            ++k.st.chunks; k.st.bytesReceived += ts_bam_chunk_size(k.chunk) - carry;
+            frameRecords(k, atEnd);
+            judgeRecords(k, false);
+            emit(0, 0);
+        }
+    }
+
+    // the ring's steps: a dealt chunk
     void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
     RingTake take(size_t w, uint64_t) {
         Worker &k = *workers[w];
         const Clock::time_point t0 = Clock::now();
         feed_.take(chunkBytes_, k.fill);
-        k.st.msSource += ringSince(t0);
+        k.st.msSource += since(t0);
         return k.fill.atEnd ? RingTake::Last : RingTake::More;
     }
     void stage(size_t w, uint64_t) {
         Worker &k = *workers[w];
         const Clock::time_point t0 = Clock::now();
         feed_.stage(k.ctx, k.chunk, k.fill);
-        k.st.msSource += ringSince(t0);
+        k.st.msSource += since(t0);
         ++k.st.chunks; k.st.bytesReceived += k.fill.n;
     }
-    bool frame(size_t w, uint64_t) {
+    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, ts_fastq_chunk_walk
         Worker &k = *workers[w];
         ringCommit(k, prev_, prevNext_);
+        return frameRecords(k, k.fill.atEnd);
+    }
+    void judge(size_t w, uint64_t) { judgeRecords(*workers[w], true); }
+    // the chunk's turn to write: what it kept (nothing, where it came in place), its totals, and the record that is not valid
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
+        res.kept += k.passed; res.total += k.n;
+        if (k.error != TS_FASTQ_OK) {
+            const char *msg = k.error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : k.error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
+                            : k.error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
+            throw std::runtime_error("FASTQ record " + std::to_string(res.total + 1) + ": " + msg);
+        }
+    }
+
+private:
+    // The records of a chunk that has its bytes; the framing's state moves on to it.  -> every record up to the chunk's end is valid
+    bool frameRecords(Worker &k, bool atEnd) {
         prev_ = &k; prevNext_ = 0;
         k.n = 0; k.error = TS_FASTQ_OK;
-        const int atEnd = k.fill.atEnd ? 1 : 0;
         if (first_) {
             if (ts_bam_chunk_size(k.chunk) == 0) {
                 if (atEnd) throw std::runtime_error("FASTQ input is empty");
@@ -2150,19 +1953,20 @@ public:
         }
         uint64_t errorRecord = 0, errorOff = 0;
         const Clock::time_point t0 = Clock::now();
-        int rc = ts_fastq_chunk_walk(k.chunk, atEnd, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
+        int rc = ts_fastq_chunk_walk(k.chunk, atEnd ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
         if (rc == TS_ERR_INVALID_ARG && k.n > k.recs.size()) {
             k.recs.resize(static_cast<size_t>(k.n));
-            rc = ts_fastq_chunk_walk(k.chunk, atEnd, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
+            rc = ts_fastq_chunk_walk(k.chunk, atEnd ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
         }
         if (rc != TS_OK) throw deviceError(k.ctx, "FASTQ walk failed");
-        k.st.msWalk += ringSince(t0);
+        k.st.msWalk += since(t0);
         return k.error == TS_FASTQ_OK;
     }
-    void judge(size_t w, uint64_t) {
-        Worker &k = *workers[w];
+    // The chunk's records in sub-batches, in input order.  A dealt chunk keeps a sub-batch's passing bytes until its turn to emit;
+    // an in-place chunk has the turn, and they go from the judge straight to the output.
+    void judgeRecords(Worker &k, bool dealt) {
         k.fresh();
-        for (size_t a = 0; a < k.n; a += readsPerBatch_) {      // sub-batches of records, in input order
+        for (size_t a = 0; a < k.n; a += readsPerBatch_) {
             const ts_fastq_record *r = k.recs.data() + a;
             const size_t n = std::min<size_t>(readsPerBatch_, static_cast<size_t>(k.n) - a);
             k.withSeq.clear(); k.lens.clear();
@@ -2174,89 +1978,67 @@ public:
                          [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
                              return ts_fastq_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
                          });
-            k.keep();
+            k.passed += k.judged.nPassed;
+            if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
         }
     }
-    void emit(size_t w, uint64_t) {
-        Worker &k = *workers[w];
+    void write(const unsigned char *p, size_t n) {
         const Clock::time_point t0 = Clock::now();
-        k.pieces([&](const unsigned char *p, size_t n) {
-            out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
-            if (!out_.good()) throw std::runtime_error("failed while writing FASTQ subset");
-        });
-        res.kept += k.passed; res.total += k.n;
-        msWrite += ringSince(t0);
-        if (k.error != TS_FASTQ_OK) {
-            const char *msg = k.error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : k.error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
-                            : k.error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
-            throw std::runtime_error("FASTQ record " + std::to_string(res.total + 1) + ": " + msg);
-        }
+        out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+        if (!out_.good()) throw std::runtime_error("failed while writing FASTQ subset");
+        msWrite += since(t0);
     }
 
-private:
-    using Clock = std::chrono::steady_clock;
     ChunkFeed &feed_;
     std::ostream &out_;
     size_t readsPerBatch_, chunkBytes_;
-    // the serial section's state: the chunk framed last and where its unfinished record begins; nothing framed yet held a byte
-    const RingWorker *prev_ = nullptr;
+    // the framing's state: the chunk framed last and where its unfinished record begins; nothing framed yet held a byte
+    const ChunkWorker *prev_ = nullptr;
     uint64_t prevNext_ = 0;
     bool first_ = true;
 };
 
-inline FastqSubsetResult fastqSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
-                                               size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice) {
-    ChunkFeed::Options options;
-    options.cannotOpen = "Stream not successful: " + inFile;
-    options.cannotRead = "read error in FASTQ input";
-    options.dashIsStdin = true;
-    options.uploadFailed = "upload of the FASTQ text failed";
-    options.gzipDevice = false;                                 // (bound to one context: plain gzip is read through zlib here)
-    ChunkFeed feed(filter.context(0), inFile, options);
-    FastqRing steps(filter, feed, out, readsPerBatch, std::max<size_t>(bytesPerBatch, 64));
-    ChunkRing<FastqRing> ring(filter.deviceCount(), 0, steps);
-    ring.run();
-    out.flush();
-    ringFigures(feed.deviceInflate() ? "fastqSubsetDevice (upload + inflate + CRC)" : "fastqSubsetDevice", steps.workers, &ring, steps.msWrite, perDevice);
-    return steps.res;
-}
-
-// bamSubsetDevice's stages as the steps of a ChunkRing.  The chunks hold the members the loop on one context gives them (as many
-// as inflate to bytesPerBatch), so the tables, and what is written before a record that is not valid, are that loop's.  Context 0
-// takes chunks alone until the header is behind it (headerPhase); from the next chunk on the ring deals them.
-class BamRing {
+// bamSubsetDevice's stages.  A chunk holds as many BGZF members as inflate to chunkBytes (pick), whichever way it comes in, so
+// the tables, and what is written before a record that is not valid, do not depend on the number of contexts.  The header is
+// parsed on the host from the leading bytes of context 0's in-place chunks.
+class BamChunkSteps {
 public:
-    struct Worker : RingWorker {
+    struct Worker : ChunkWorker {
         std::vector<ts_bgzf_block> descs;                       // the chunk's members: where they lie, how much they give
         size_t at = 0, used = 0;
         uint64_t produced = 0;
-        std::vector<ts_bam_record> table, recs, withSeq;        // a walk's table; the chunk's records
+        std::vector<ts_bam_record> recs, withSeq;               // the chunk's records, one walk's table behind the other
+        uint64_t n = 0, withBases = 0;                          // how many there are; how many of those judged so far had bases
+        std::vector<size_t> tables;                             // where each table ends in recs
         const char *error = nullptr;                            // the record the framing stopped at is not valid
     };
     BamSubsetStats stats;
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    BamRing(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk)
-        : data_(data), size_(size), writer_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes), walk_(walk),
+    BamChunkSteps(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk)
+        : data_(data), size_(size), writer_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
+          table_(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), walk_(walk),
           plainCap_((256ull << 20) + 4 + chunkBytes), compCap_(chunkBytes + (1u << 20)) {
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
             workers.emplace_back(new Worker());
             Worker &k = *workers.back();
             k.ctx = filter.context(w);
-            // (context 0's chunk holds a header of any size the route accepts; the others grow when a carry asks for it)
+            // (a chunk holds the unconsumed tail of the one before, at most a record: 4 bytes + 256 MiB, and the new members'
+            // output.  Context 0's holds a header of any size the route accepts; the others grow when a carry asks for it)
             k.chunk = ts_bam_chunk_create(k.ctx, compCap_, w == 0 ? plainCap_ : chunkBytes + (1u << 20));
             if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
-            k.table.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2));
+            k.recs.resize(table_);
         }
     }
 
-    // Chunks 0 .. h on context 0, as the loop on one context runs them, until the header is complete and chunk h's records are
-    // written.  -> h + 1, the ring's first chunk (0 where the input ended before)
-    uint64_t headerPhase() {
+    // In-place chunks of context 0, on the caller's thread: the whole input where the filter has one context, else the chunks up
+    // to the one that completes the header, its records included.  -> the first chunk for a ring to deal (0: the input has ended)
+    uint64_t runInPlace() {
         Worker &k = *workers[0];
-        uint64_t chunks = 0, pos = 0;
-        std::vector<unsigned char> head;                        // host copy of the chunk's leading bytes
+        const bool alone = workers.size() == 1;
+        uint64_t pos = 0;                                       // the chunk's first byte not consumed yet
+        std::vector<unsigned char> head;                        // host copy of the chunk's leading bytes (until the header is done)
         auto have = [&](uint64_t n) {                           // n more bytes from pos on, and on the host
             if (held_ - pos < n) return false;
             if (head.size() < pos + n) {
@@ -2267,29 +2049,30 @@ public:
             return true;
         };
         auto bytesAt = [&](uint64_t off) { return head.data() + pos + off; };
-        while (more_ && !header_.done()) {
+        while (more_ && (alone || !header_.done())) {
             const uint64_t carry = held_ - pos;
             pick(k, carry);
             if (carry + k.produced > plainCap_) throw std::runtime_error("BAM header is too large for the device route");
             const Clock::time_point t0 = Clock::now();
             inflateMembers(k.ctx, k.chunk, data_ + k.at, k.used, k.descs, pos);
-            k.st.msSource += ringSince(t0);
+            k.st.msSource += since(t0);
             ++k.st.chunks; k.st.bytesReceived += k.produced;
-            ++chunks;
             held_ = carry + k.produced; pos = 0;
             head.clear();
-            k.recs.clear(); k.error = nullptr;
-            if (header_.parse(have, bytesAt, pos, writer_)) {
+            if (header_.done() || header_.parse(have, bytesAt, pos, writer_)) {
+                head.clear(); head.shrink_to_fit();
                 walkRecords(k, pos);
-                judge(0, 0);
+                judgeRecords(k, false);
                 emit(0, 0);
+                pos = prevNext_;
             } else {
                 prev_ = &k; prevNext_ = pos;
             }
         }
-        return more_ && header_.done() ? chunks : 0;
+        return more_ ? k.st.chunks : 0;
     }
 
+    // the ring's steps: a dealt chunk
     void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
     RingTake take(size_t w, uint64_t) {
         if (!more_) return RingTake::None;
@@ -2301,45 +2084,24 @@ public:
         const Clock::time_point t0 = Clock::now();
         if (ts_chunk_stage_inflate(k.chunk, data_ + k.at, k.used, k.descs.data(), k.descs.size(), nullptr) != TS_OK) throw deviceError(k.ctx, "BGZF inflate failed");
         membersVerdict(k.ctx, k.chunk);
-        k.st.msSource += ringSince(t0);
+        k.st.msSource += since(t0);
         ++k.st.chunks; k.st.bytesReceived += k.produced;
     }
-    bool frame(size_t w, uint64_t) {
+    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, the record walk
         Worker &k = *workers[w];
         ringCommit(k, prev_, prevNext_);
         held_ = ts_bam_chunk_size(k.chunk);
-        k.recs.clear(); k.error = nullptr;
         walkRecords(k, 0);
         return !k.error;
     }
-    void judge(size_t w, uint64_t) {
-        Worker &k = *workers[w];
-        k.fresh();
-        for (size_t a = 0; a < k.recs.size(); a += readsPerBatch_) {        // sub-batches of records, in input order
-            const ts_bam_record *r = k.recs.data() + a;
-            const size_t n = std::min<size_t>(readsPerBatch_, k.recs.size() - a);
-            k.withSeq.clear(); k.lens.clear();
-            for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].l_seq); }
-            if (k.withSeq.empty()) continue;
-            k.st.recordsJudged += k.withSeq.size();
-            k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
-                         [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
-                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                             return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
-                         });
-            k.keep();
-        }
-    }
+    void judge(size_t w, uint64_t) { judgeRecords(*workers[w], true); }
+    // the chunk's turn to write: what it kept (nothing, where it came in place), its totals, and the record that is not valid
     void emit(size_t w, uint64_t) {
         Worker &k = *workers[w];
-        const Clock::time_point t0 = Clock::now();
-        k.pieces([&](const unsigned char *p, size_t n) { writer_.write(p, n); });
-        uint64_t withBases = 0;
-        for (const ts_bam_record &r : k.recs) withBases += r.l_seq ? 1 : 0;
-        stats.totalRecords += k.recs.size();
-        stats.missingSequenceRecords += k.recs.size() - withBases;
+        k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
+        stats.totalRecords += k.n;
+        stats.missingSequenceRecords += k.n - k.withBases;
         stats.passedRecords += k.passed;
-        msWrite += ringSince(t0);
         if (k.error) throw std::runtime_error(k.error);
     }
     // the input has ended: what is left of it is no header and no record
@@ -2351,10 +2113,9 @@ public:
     }
 
 private:
-    using Clock = std::chrono::steady_clock;
-    // The members of the next chunk, their output from dstBase on (BgzfParallelReader::next's rule, as the loop on one context
-    // applies it: a member that does not parse is an error, a chunk never takes a member past chunkBytes).  The reader's: one
-    // call at a time, no device call.
+    // The members of the next chunk, their output from dstBase on (BgzfParallelReader::next's rule).  Not pickBgzfMembers: here a
+    // member that does not parse is an error, not a change of source, a chunk never takes a member past chunkBytes, and there is
+    // one inflate call per chunk.  The reader's: one call at a time, no device call.
     void pick(Worker &k, uint64_t dstBase) {
         k.descs.clear();
         k.at = at_; k.used = 0; k.produced = 0;
@@ -2375,62 +2136,148 @@ private:
         at_ += k.used;
         more_ = k.used > 0 && at_ < size_;
     }
-    // The chunk's records from `from` on, a table at a time, into k.recs; the serial section's state moves on to this chunk.  A
-    // record that is not valid drops its table, as the loop on one context throws before judging it.
+    // The chunk's records from `from` on into k.recs, a table of table_ records at a time; the framing's state moves on to this
+    // chunk.  Where a table's walk meets a record that is not valid, the table is dropped and the framing ends: the tables before
+    // it are judged and written, then emit() throws.
     void walkRecords(Worker &k, uint64_t from) {
         const Clock::time_point t0 = Clock::now();
+        k.n = 0; k.tables.clear(); k.error = nullptr;
         uint64_t pos = from;
         for (;;) {
+            if (k.recs.size() < k.n + table_) k.recs.resize(static_cast<size_t>(k.n) + table_);
             uint64_t n = 0, next = 0, errorOff = 0;
             int error = 0;
-            if ((walk_ == BamRecordWalk::Index ? ts_bam_chunk_index : ts_bam_chunk_walk)(k.chunk, pos, k.table.data(), k.table.size(), &n, &next, &error, &errorOff) != TS_OK)
+            if ((walk_ == BamRecordWalk::Index ? ts_bam_chunk_index : ts_bam_chunk_walk)(k.chunk, pos, k.recs.data() + k.n, table_, &n, &next, &error, &errorOff) != TS_OK)
                 throw deviceError(k.ctx, "record walk failed");
             if (error != TS_BAM_OK) {
                 k.error = error == TS_BAM_BAD_BLOCK_SIZE ? "invalid BAM record block_size" : error == TS_BAM_BAD_LENGTHS ? "invalid BAM record lengths"
                         : error == TS_BAM_FIELDS_EXCEED ? "BAM record fields exceed block_size" : "BAM read name is not NUL-terminated";
                 break;
             }
-            k.recs.insert(k.recs.end(), k.table.begin(), k.table.begin() + static_cast<std::ptrdiff_t>(n));
+            k.n += n;
+            k.tables.push_back(static_cast<size_t>(k.n));
             pos = next;
-            if (n < k.table.size()) break;                      // (a full table: more records may follow in this chunk)
+            if (n < table_) break;                              // (a full table: more records may follow in this chunk)
         }
-        k.st.msWalk += ringSince(t0);
+        k.st.msWalk += since(t0);
         prev_ = &k; prevNext_ = pos;
+    }
+    // The chunk's records in sub-batches, in input order.  A sub-batch never spans two tables of the walk, for any number of
+    // contexts: each table is cut into sub-batches of readsPerBatch on its own.  A dealt chunk keeps a sub-batch's passing bytes
+    // until its turn to emit; an in-place chunk has the turn, and they go from the judge straight to the writer.
+    void judgeRecords(Worker &k, bool dealt) {
+        k.fresh();
+        k.withBases = 0;
+        size_t from = 0;
+        for (size_t end : k.tables) {
+            for (size_t a = from; a < end; a += readsPerBatch_) {
+                const ts_bam_record *r = k.recs.data() + a;
+                const size_t n = std::min<size_t>(readsPerBatch_, end - a);
+                k.withSeq.clear(); k.lens.clear();
+                for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].l_seq); }
+                if (k.withSeq.empty()) continue;
+                k.withBases += k.withSeq.size();
+                k.st.recordsJudged += k.withSeq.size();
+                k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
+                             [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
+                             [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                                 return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                             });
+                k.passed += k.judged.nPassed;
+                if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
+            }
+            from = end;
+        }
+    }
+    void write(const unsigned char *p, size_t n) {
+        const Clock::time_point t0 = Clock::now();
+        writer_.write(p, n);
+        msWrite += since(t0);
     }
 
     const unsigned char *data_;
     size_t size_;
     BgzfWriter writer_;
     BamHeaderParser header_;
-    size_t readsPerBatch_, chunkBytes_;
+    size_t readsPerBatch_, chunkBytes_, table_;
     BamRecordWalk walk_;
     uint64_t plainCap_, compCap_;
     // the reader's state: the next member, whether one may follow, the EOF marker seen
     size_t at_ = 0;
     bool more_ = true, sawEofMarker_ = false;
-    // the serial section's state: the chunk framed last, its size and where its unfinished record begins
-    const RingWorker *prev_ = nullptr;
+    // the framing's state: the chunk framed last, its size and where its unfinished record begins
+    const ChunkWorker *prev_ = nullptr;
     uint64_t prevNext_ = 0, held_ = 0;
 };
 
-inline BamSubsetStats bamSubsetDeviceRing(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
-                                          size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice) {
-    MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
+}  // namespace detail
+
+// The device route of --bam-subset (same arguments, statistics, exceptions and output bytes as bamSubset, which stays the
+// default): the compressed BGZF members cross PCIe and the uncompressed BAM stream exists in HBM only.  The input is
+// detail::MappedInput's (a pipe and stdin are read to their end).  Per chunk of ~bytesPerBatch uncompressed bytes: the members
+// are located on the host (parseBgzfBlock reads no payload byte), inflated and checksummed on the device
+// (detail::inflateMembers, ts_chunk_stage_inflate), the records walked and validated there (ts_bam_chunk_walk or
+// ts_bam_chunk_index, see BamRecordWalk: the table comes back), SEQ decoded into a tips-only batch's input buffer
+// (ts_bam_chunk_decode), judged and the passing records' bytes gathered (detail::ReadJudge with ts_bam_chunk_gather).
+// The BAM header is parsed on the host from the chunk's leading bytes.  The stages are detail::BamChunkSteps for every filter: a
+// filter of one context takes every chunk in place, on the caller's thread and with no staging region; a filter of several
+// contexts does so on context 0 until the header is behind it, and from the next chunk on the ring deals the chunks to all of
+// them.  perDevice, where given, receives one entry per context.
+// What a maintainer of the reference would call from runBamSubsetMode (src/bam.cpp:262-316) in place of subsetBam.
+inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
+                                      BamRecordWalk walk = BamRecordWalk::Index, std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    // the compressed input: a regular file is mapped, a pipe is read to its end
+    detail::MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
     std::vector<unsigned char> piped;
     if (!in.data) in.readToEnd(piped, "cannot read BAM input");
-    BamRing steps(filter, in.data ? in.data : piped.data(), in.data ? in.size : piped.size(), out, readsPerBatch, std::max<size_t>(bytesPerBatch, 1u << 20), walk);
-    const uint64_t firstChunk = steps.headerPhase();
-    std::unique_ptr<ChunkRing<BamRing>> ring;
-    if (firstChunk) {
-        ring.reset(new ChunkRing<BamRing>(filter.deviceCount(), firstChunk, steps));
+    detail::BamChunkSteps steps(filter, in.data ? in.data : piped.data(), in.data ? in.size : piped.size(), out, readsPerBatch,
+                                std::max<size_t>(bytesPerBatch, 1u << 20), walk);
+    std::unique_ptr<detail::ChunkRing<detail::BamChunkSteps>> ring;
+    if (const uint64_t firstChunk = steps.runInPlace()) {
+        ring.reset(new detail::ChunkRing<detail::BamChunkSteps>(filter.deviceCount(), firstChunk, steps));
         ring->run();
     }
     steps.finish();
-    ringFigures(walk == BamRecordWalk::Index ? "bamSubsetDevice (index)" : "bamSubsetDevice (serial)", steps.workers, ring.get(), steps.msWrite, perDevice);
+    detail::routeFigures(walk == BamRecordWalk::Index ? "bamSubsetDevice (index)" : "bamSubsetDevice (serial)", steps.workers, ring.get(), steps.msWrite, perDevice);
     return steps.stats;
 }
 
-}  // namespace detail
+// The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as
+// fastqSubset, which stays the default): the FASTQ text exists in HBM one chunk of ~bytesPerBatch bytes at a time and the host
+// reads none of it.  The text gets there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, or a
+// stream through zlib or read(2); `-` is stdin, always through zlib), and behind the source the stages are the same: lines
+// indexed and records framed and validated (ts_fastq_chunk_walk: the table comes back), sequences staged into a tips-only
+// batch's input buffer (ts_fastq_chunk_stage), judged and the passing records' bytes gathered (detail::ReadJudge with
+// ts_fastq_chunk_gather).  The bytes behind the last whole record stay in the chunk for the next fill; a record larger than a
+// chunk makes the chunk grow.  The stages are detail::FastqChunkSteps for every filter: a filter of one context takes every chunk
+// in place, on the caller's thread and with no staging region; on a filter of several contexts the ring deals the chunks to all
+// of them, and there plain gzip is read through zlib, because the opt-in device gzip source (ChunkFeed::Gzip) is bound to one
+// context.  perDevice, where given, receives one entry per context.
+// What a maintainer of the reference would call from Input::readFastqSubset (src/input.cpp:737-832) in place of its loop.
+inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                           size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
+                                           std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    const bool dealt = filter.deviceCount() > 1;
+    detail::ChunkFeed::Options options;
+    options.cannotOpen = "Stream not successful: " + inFile;
+    options.cannotRead = "read error in FASTQ input";
+    options.dashIsStdin = true;
+    options.uploadFailed = "upload of the FASTQ text failed";
+    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
+    detail::ChunkFeed feed(filter.context(0), inFile, options);
+    detail::FastqChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(bytesPerBatch, 64));
+    std::unique_ptr<detail::ChunkRing<detail::FastqChunkSteps>> ring;
+    if (dealt) {
+        ring.reset(new detail::ChunkRing<detail::FastqChunkSteps>(filter.deviceCount(), 0, steps));
+        ring->run();
+    } else {
+        steps.runInPlace();
+    }
+    out.flush();
+    detail::routeFigures(feed.deviceInflate() ? "fastqSubsetDevice (upload + inflate + CRC)" : "fastqSubsetDevice", steps.workers, ring.get(), steps.msWrite, perDevice);
+    return steps.res;
+}
 
 inline const char *scaffoldTypeToString(ScaffoldType t) {       // src/tools.cpp
     static const char *names[] = {"t2t", "gapped_t2t", "misassembly", "gapped_misassembly", "incomplete",

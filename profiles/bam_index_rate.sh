@@ -86,7 +86,7 @@ ab() {      # label, input
     for r in 1 2 3; do
         for w in serial index; do
             run $w "$1 run $r" $2
-            sed -n 's/.*walk ([a-z]*) \([0-9.]*\) ms.*/\1/p' $TMP/run_$w.log >> $TMP/walk_$w.txt
+            sed -n 's/^bamSubsetDevice ([a-z]*): context 0 of 1: .* walk \([0-9.]*\) ms.*/\1/p' $TMP/run_$w.log >> $TMP/walk_$w.txt
         done
         cmp $TMP/kept_serial.bam $TMP/kept_index.bam; echo "kept bytes equal"
     done

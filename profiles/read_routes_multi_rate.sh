@@ -4,11 +4,13 @@
 # configurations alternate in every round, each a process of its own under its own time limit:
 #   parent   $PARENT's fastq_device_cli / bam_device_cli --device   (a built checkout of the parent commit: include/, tests/cpp/
 #            and teloscope_amd/libteloscan.so; without it the parent runs are left out and the output says so)
-#   one      this tree, tests/cpp/read_routes_multi_cli.cpp --device --devices 0     (the loop on one context: the parent's code)
-#   two      this tree, --device --devices 0,0                                        (the ring: chunks dealt to two contexts)
-# One warm-up of each, then three rounds with TS_TIMING=1 (the stage line of one context, one line per context of two), the kept
-# bytes of the three compared in every round; minimum and median of the three at the end.  `one` must lie within the spread of
-# `parent`: it runs the same code.  Two contexts on one card share its PCIe link, its copy engines and its CUs: what they show is
+#   one      this tree, tests/cpp/read_routes_multi_cli.cpp --device --devices 0     (the routes' chunk steps, every chunk in place)
+#   two      this tree, --device --devices 0,0                                        (the same steps, chunks dealt to two contexts)
+# One warm-up of each, then three rounds with TS_TIMING=1 (a line per context and the write line), the kept bytes of the three
+# compared in every round; minimum and median of the three at the end.  `one` must lie within the spread of `parent`, stage by
+# stage: in place it does what the parent's loop did.  TELOMERIC (default 0.005) is the fraction of reads that get a telomeric
+# stretch; at 1 every read passes, the bytes written are as large as the chunks, and a stray host copy of them would show in the
+# gather and write figures.  Two contexts on one card share its PCIe link, its copy engines and its CUs: what they show is
 # the overlap the ring buys on one card and the carry wait, not a figure for several GPUs.  Then `two` once more on the bgzipped
 # FASTQ under rocprofv3 --kernel-trace --memory-copy-trace --stats (a run of its own, no counters): the commit's copy is a
 # device-to-device copy, not a kernel.  Run on the GPU box.
@@ -20,6 +22,7 @@ NBAM=${2:-120000}
 OUT=${3:-profiles/reads/read_routes_multi_rate.txt}
 PARENT=${PARENT:-ab_old/parent}
 CHUNK=${CHUNK:-268435456}
+TELOMERIC=${TELOMERIC:-0.005}
 TMP=${TMPDIR:-/tmp}
 FQ=$TMP/reads_multi_rate.fq
 BAM=$TMP/reads_multi_rate.bam
@@ -29,7 +32,7 @@ mkdir -p "$(dirname "$OUT")"
 exec > >(tee "$OUT") 2>&1
 
 generate() {
-python3 - $NFQ $NBAM "$FQ" "$BAM" <<'PY'
+python3 - $NFQ $NBAM "$FQ" "$BAM" $TELOMERIC <<'PY'
 import numpy as np, struct, sys, zlib, time
 from concurrent.futures import ThreadPoolExecutor
 sys.path.insert(0, '.')
@@ -50,7 +53,7 @@ def reads(n):                                                               # th
     lens = np.clip(rng.normal(15000, 3000, size=n), 1000, 40000).astype(np.int64)
     pool = seqgen.random_dna(rng, int(lens.sum()))
     offs = np.concatenate(([0], np.cumsum(lens)))
-    for i in np.flatnonzero(rng.random(n) < 0.005):
+    for i in np.flatnonzero(rng.random(n) < float(sys.argv[5])):
         ln = int(rng.integers(300, 8000))
         t = seqgen.mutate(rng, seqgen.repeat_array("TTAGGG", ln // 6 + 1), 0.01)[:min(ln, lens[i])]
         pool[offs[i]:offs[i] + len(t)] = t

@@ -1,9 +1,12 @@
 """fastqSubsetDevice and bamSubsetDevice on a ReadTelomereFilter of several contexts (the input's chunks dealt to all of them:
-include/teloscope_mi355x_ring.hpp and the ring routes of include/teloscope_mi355x_io.hpp) through
+include/teloscope_mi355x_ring.hpp and the routes' chunk steps of include/teloscope_mi355x_io.hpp) through
 tests/cpp/read_routes_multi_cli.cpp: 2 and 3 contexts on this one GPU against 1 context and against the host route of the same
 binary — equal verdicts, byte-equal output, equal result structs, equal messages and equal bytes written before a failure — and
-the per-context figures, which say that every context worked.  Most runs go through the CLI's list mode: one process and one
-filter per configuration for all files of a test.  The carry between two contexts is also checked call by call."""
+the per-context figures, which say that every context worked.  One set of steps serves every count (one context fills each chunk
+in place, on the caller's thread and with no staging region; on several the ring deals the chunks), so 1 against N contexts
+compares two ways in of one code: the independent side is the host route, and the figures of one context are held against the
+chunks the parent commit's loop cut.  Most runs go through the CLI's list mode: one process and one filter per configuration for
+all files of a test.  The carry between two contexts is also checked call by call."""
 import ctypes as C
 import gzip
 import json
@@ -124,12 +127,15 @@ def test_malformed_fastq_fails_alike(mcli, tmp_path):
     extra = ["-x", "0", "-l", "6", "--chunk-bytes", "257", "--reads-per-batch", "2"]
     one = run_each(mcli, tmp_path, "one", "--fastq-subset", entries, "--device", "0", extra)
     three = run_each(mcli, tmp_path, "three", "--fastq-subset", entries, "--device", "0,0,0", extra)
+    host = run_each(mcli, tmp_path, "host", "--fastq-subset", entries, "--host", None, extra[:4])
     expected = dict(F.error_cases())
     for (name, _, _), (case, text) in zip(entries, sorted(cases.items())):
         assert one[name][0] == "err" and three[name] == one[name], (case, three[name][:2], one[name][:2])
         if case in expected:
             _, kind, at = expected[case]
             assert three[name][1] == "FASTQ record %d: %s\n" % (at + 1, F.MESSAGES[kind]), case
+        else:                                                       # (one and several contexts share their steps: the host route's message)
+            assert host[name][0] == "err" and three[name][1] == host[name][1], (case, three[name][1], host[name][1])
     assert any(len(v[2]) > 0 for v in three.values())              # (something was written before some of the failures)
 
 
@@ -252,6 +258,40 @@ def test_every_context_works(mcli, tmp_path, two_kb, devices):
         assert sum(c["recordsJudged"] for c in ctxs) == 3000 and js["result"]["totalRecords"] == 3001
         assert js["result"]["missingSequenceRecords"] == 1
         assert max(chunks) - min(chunks) <= 1, chunks
+
+
+# What the build of the commit before the one set of chunk steps (2b8e572, whose one context ran a loop of its own) reports as
+# `chunks` on one context for the inputs of test_one_context_pays_nothing_for_the_ring, same flags.
+PARENT_CHUNKS = {"plain": 31, "bgzf": 42, "gzip": 31, "index": 9, "serial": 9}
+
+
+def test_one_context_pays_nothing_for_the_ring(mcli, tmp_path, two_kb):
+    """The figures of one context: every chunk comes in place (no staging region, no commit, no wait for a turn), in the chunks
+    the loop of the parent commit cut."""
+    def one_context(mode, path, extra, judged, received, chunks):
+        r, js = run_one(mcli, mode, path, "--device", "0", extra)
+        assert r.returncode == 0, r.stderr[-300:]
+        assert len(js["contexts"]) == 1, js
+        c = js["contexts"][0]
+        print(path.name, extra[-1], c)
+        assert c["msCommit"] == 0.0 and c["msCarryWait"] == 0.0, c
+        assert c["recordsJudged"] == judged and c["bytesReceived"] == received, c
+        assert c["chunks"] == chunks, c
+        return js
+
+    text = F.reads_text(83, 300)
+    for kind, data in (("plain", text), ("bgzf", bgzf(text, 3000)), ("gzip", gzip.compress(text, 6))):
+        p = tmp_path / ("reads." + kind)
+        p.write_bytes(data)
+        js = one_context("--fastq-subset", p, FLAGS + ["--chunk-bytes", "4096"], with_bases(text), len(text), PARENT_CHUNKS[kind])
+        assert js["result"]["total"] == 300
+    header, records, bam = two_kb
+    p = tmp_path / "reads.bam"
+    p.write_bytes(bam)
+    for walk in ("index", "serial"):
+        js = one_context("--bam-subset", p, ["--chunk-bytes", str(1 << 20), "--walk", walk], 3000, len(header) + sum(map(len, records)),
+                         PARENT_CHUNKS[walk])
+        assert js["result"]["totalRecords"] == 3001
 
 
 def test_general_pattern_set_on_two_contexts(mcli, tmp_path):
