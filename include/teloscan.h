@@ -859,6 +859,32 @@ void *ts_bam_chunk_pass_buffer(ts_bam_chunk *chunk, uint64_t n);
 int ts_bam_chunk_gather(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, const void *d_pass, void *host_out,
                         uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
 
+/* ---- BGZF members WRITTEN on the device (a wave per member): what the reference's BgzfWriter does with zlib on the host, a
+ *      member per payload (src/bgzf.cpp:227-276: deflateInit2(Z_DEFAULT_COMPRESSION, -15), crc32, the footer).  A payload of at
+ *      most 65 280 bytes becomes one raw deflate block — dynamic Huffman codes over greedy LZ77 matches, or stored where that is
+ *      no shorter, so a payload never grows by more than five bytes — framed by the 18-byte BGZF header and the CRC32 / ISIZE
+ *      footer.  zlib inflates every member to its payload; the compressed bytes are this encoder's, not zlib's, and are a
+ *      function of the payload alone.  Nothing here is on by default: bamSubsetDevice writes through these calls only under
+ *      BamOutputDeflate::Device (include/teloscope_mi355x_io.hpp). */
+/* Host in, host out (tests and tools: blocks no BAM produces; the counterpart of ts_bgzf_inflate for src/bgzf.cpp:227-276).
+ * plain[0, n) is cut into consecutive payloads of payload_bytes (1 .. 65280, else TS_ERR_INVALID_ARG; the last may be shorter),
+ * each becomes one complete member, in order and contiguous in out; *bytes and *n_members say how much (n == 0: none).  No EOF
+ * marker is appended.  When *bytes > cap nothing is copied and the call answers TS_ERR_INVALID_ARG (call again with room for
+ * *bytes). */
+int ts_bgzf_deflate(ts_ctx *ctx, const void *plain, uint64_t n, uint32_t payload_bytes, void *out, uint64_t cap, uint64_t *bytes,
+                    uint64_t *n_members);
+/* ts_bam_chunk_gather with the passing records gathered into a device buffer of the chunk's, deflated there in payloads of
+ * payload_bytes and downloaded as BGZF members (replaces zlib in BgzfWriter::write / flush, src/bgzf.cpp:227-276): the same
+ * records in the same order.  *bytes = the members' bytes in host_out, *plain_bytes = what ts_bam_chunk_gather would have
+ * returned in *bytes; when nothing passes there is no member and *bytes == 0.  When *bytes > cap nothing is copied:
+ * TS_ERR_INVALID_ARG.  Ordered on `stream`; waits for it. */
+int ts_bam_chunk_gather_bgzf(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, const void *d_pass, uint32_t payload_bytes,
+                             void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, uint64_t *plain_bytes, void *stream);
+/* Cumulative since ts_create, monotonic and atomic, like ts_bam_index_stats: device deflate calls that passed their argument
+ * checks (the stage that replaces zlib in src/bgzf.cpp:227-276; a gather with nothing passing makes none), members they
+ * delivered, plain bytes that went in, member bytes that came out. */
+int ts_bgzf_deflate_stats(const ts_ctx *ctx, uint64_t out[4]);
+
 /* ---- FASTQ text in the same resident chunk (include/teloscope_mi355x_io.hpp: fastqSubsetDevice): replaces, for
  *      --fastq-subset, the line reader and record check of readFastqRecord (src/input.cpp:96-149) and the read / filter /
  *      echo loop of Input::readFastqSubset (src/input.cpp:737-832).  The text reaches the chunk as plain bytes

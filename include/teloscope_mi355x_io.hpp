@@ -891,7 +891,12 @@ inline FastqSubsetResult fastqSubset(const std::string &inFile, std::ostream &ou
 // written as BGZF blocks of <= 0xff00 payload bytes (raw deflate + the BC field + CRC32/ISIZE) closed by the EOF marker.
 // (Round 2 until here read the input with zlib's gz* API on one thread: 0.14 Gbases/s on a HiFi BAM;
 // profiles/r02/bam_subset_rate.txt.)
-struct BamSubsetStats { uint64_t totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0; bool missingEofBlock = false; };
+// (deflatePlainBytes / deflateMemberBytes / msDeflate: what bamSubsetDevice compressed on the device under BamOutputDeflate::Device —
+// record bytes in, BGZF member bytes out, milliseconds its contexts spent in ts_bam_chunk_gather_bgzf; zero everywhere else)
+struct BamSubsetStats {
+    uint64_t totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0; bool missingEofBlock = false;
+    uint64_t deflatePlainBytes = 0, deflateMemberBytes = 0; double msDeflate = 0;
+};
 
 namespace detail {
 // the host-side helpers of this header: a bounded queue between pipeline stages, and a dynamic parallel-for
@@ -1122,6 +1127,13 @@ public:
     void write(const unsigned char *data, size_t n) {
         pending.insert(pending.end(), data, data + n);
         if (pending.size() >= kBlocksPerFlush * kPayload) flush(pending.size() / kPayload * kPayload);      // whole blocks only
+    }
+    // what is pending becomes members now (the last one may be short)
+    void flushPending() { flush(pending.size()); }
+    // finished BGZF members, verbatim, behind whatever was pending (which is flushed first)
+    void writeMembers(const unsigned char *members, size_t n) {
+        flushPending();
+        out.write(reinterpret_cast<const char *>(members), static_cast<std::streamsize>(n));
     }
     void finish() {
         flush(pending.size());
@@ -1734,6 +1746,12 @@ struct ReadJudge {
 
     template <typename Stage, typename Gather>
     void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather) {
+        run(ctx, chunk, lens, stageFailed, stage, gather, [](void *) { return uint64_t(0); });
+    }
+    // ... with room(dPass): the bytes `kept` must hold before gather is called (0: as it is), for a gather whose refused call is
+    // not cheap
+    template <typename Stage, typename Gather, typename Room>
+    void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather, Room &&room) {
         struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
         if (!batch.p) throw deviceError(ctx, "cannot plan the read batch");
         Clock::time_point t0 = Clock::now();
@@ -1751,6 +1769,8 @@ struct ReadJudge {
         msFilter += since(t0); t0 = Clock::now();
         bytes = nPassed = 0;
         if (kept.size() < (1u << 20)) kept.resize(1u << 20);
+        const uint64_t want = room(dPass);
+        if (want > kept.size()) kept.resize(static_cast<size_t>(want));
         int rc = gather(dPass, kept.data(), kept.size(), &bytes, &nPassed);
         if (rc == TS_ERR_INVALID_ARG && bytes > kept.size()) {
             kept.resize(static_cast<size_t>(bytes));
@@ -1784,6 +1804,13 @@ struct ReadJudge {
 // the default: its walk stage measured 6.8 ms against 98.4 ms on a HiFi BAM and 11 ms against 1 112 ms on a BAM of 150-base reads
 // (profiles/bam/bam_index_rate.txt).
 enum class BamRecordWalk { Serial, Index };
+// `deflate` of bamSubsetDevice chooses who compresses the passing records.  Host: detail::BgzfWriter, zlib level 6 on the host
+// threads inside the writer's turn, as bamSubset does (the default; nothing about it changes).  Device: every sub-batch's passing
+// records are gathered, cut into payloads of 65 280 bytes, deflated and framed on the device (ts_bam_chunk_gather_bgzf) and come
+// back as finished members, which the writer appends verbatim; the header still goes through zlib, into members of its own.  The
+// output is then a valid BGZF file that inflates to exactly what Host's inflates to; its compressed bytes are the device
+// encoder's, and do not depend on the number of contexts (they do on readsPerBatch and bytesPerBatch, which cut the sub-batches).
+enum class BamOutputDeflate { Host, Device };
 // One context's share of a device read route: chunks it took, reads with bases it judged, uncompressed bytes it received, and the
 // milliseconds its thread spent in the source (reading, upload, inflate and CRC), waiting for the chunk before its own to be
 // framed (dealt chunks only: the serial section as this context sees it), placing the carry and committing the staged bytes
@@ -1791,6 +1818,10 @@ enum class BamRecordWalk { Serial, Index };
 struct ReadRouteDeviceStats {
     uint64_t chunks = 0, recordsJudged = 0, bytesReceived = 0;
     double msSource = 0, msCarryWait = 0, msCommit = 0, msWalk = 0, msStage = 0, msFilter = 0, msGather = 0;
+    // BamOutputDeflate::Device only: milliseconds in ts_bam_chunk_gather_bgzf (part of msGather: gather, deflate kernels, the
+    // members' download), record bytes that went into it and member bytes that came out
+    double msDeflate = 0;
+    uint64_t deflatePlainBytes = 0, deflateMemberBytes = 0;
 };
 
 namespace detail {
@@ -1846,11 +1877,16 @@ inline void routeFigures(const char *route, const std::vector<std::unique_ptr<Wo
         s.msStage = workers[w]->judged.msStage; s.msFilter = workers[w]->judged.msFilter; s.msGather = workers[w]->judged.msGather;
         if (ring) s.msCarryWait = ring->frameWaitMs(w);
         if (perDevice) perDevice->push_back(s);
-        if (std::getenv("TS_TIMING"))
+        if (std::getenv("TS_TIMING")) {
+            char deflate[160] = "";                             // (a route that deflated on the device says so behind the gather)
+            if (s.deflatePlainBytes)
+                std::snprintf(deflate, sizeof deflate, ", of which device deflate %.0f ms (%llu record bytes -> %llu member bytes)", s.msDeflate,
+                              (unsigned long long)s.deflatePlainBytes, (unsigned long long)s.deflateMemberBytes);
             std::fprintf(stderr, "%s: context %zu of %zu: %llu chunks, %llu reads judged, %llu bytes; source %.0f ms, carry wait %.1f ms, carry + commit %.1f ms, "
-                         "walk %.1f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms\n", route, w, workers.size(), (unsigned long long)s.chunks,
+                         "walk %.1f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms%s\n", route, w, workers.size(), (unsigned long long)s.chunks,
                          (unsigned long long)s.recordsJudged, (unsigned long long)s.bytesReceived, s.msSource, s.msCarryWait, s.msCommit, s.msWalk, s.msStage,
-                         s.msFilter, s.msGather);
+                         s.msFilter, s.msGather, deflate);
+        }
     }
     if (std::getenv("TS_TIMING")) std::fprintf(stderr, "%s: write %.0f ms\n", route, msWrite);
 }
@@ -2016,9 +2052,10 @@ public:
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    BamChunkSteps(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk)
+    BamChunkSteps(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk,
+                  BamOutputDeflate deflate = BamOutputDeflate::Host)
         : data_(data), size_(size), writer_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
-          table_(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), walk_(walk),
+          table_(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), walk_(walk), deflate_(deflate),
           plainCap_((256ull << 20) + 4 + chunkBytes), compCap_(chunkBytes + (1u << 20)) {
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
             workers.emplace_back(new Worker());
@@ -2164,7 +2201,9 @@ private:
     }
     // The chunk's records in sub-batches, in input order.  A sub-batch never spans two tables of the walk, for any number of
     // contexts: each table is cut into sub-batches of readsPerBatch on its own.  A dealt chunk keeps a sub-batch's passing bytes
-    // until its turn to emit; an in-place chunk has the turn, and they go from the judge straight to the writer.
+    // until its turn to emit; an in-place chunk has the turn, and they go from the judge straight to the writer.  Under
+    // BamOutputDeflate::Device the bytes are finished BGZF members (ts_bam_chunk_gather_bgzf, payloads of 0xff00): a dealt chunk's
+    // compression runs here, on every context at once, and emit() only writes.
     void judgeRecords(Worker &k, bool dealt) {
         k.fresh();
         k.withBases = 0;
@@ -2181,7 +2220,24 @@ private:
                 k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
                              [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
                              [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                                 return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                                 if (deflate_ == BamOutputDeflate::Host)
+                                     return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                                 const Clock::time_point t0 = Clock::now();
+                                 uint64_t plainBytes = 0;
+                                 const int rc = ts_bam_chunk_gather_bgzf(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, 0xff00u, dst, cap, bytes, nPassed,
+                                                                         &plainBytes, nullptr);
+                                 k.st.msDeflate += since(t0);
+                                 if (rc == TS_OK) { k.st.deflatePlainBytes += plainBytes; k.st.deflateMemberBytes += *bytes; }
+                                 return rc;
+                             },
+                             // (a refused ts_bam_chunk_gather_bgzf has deflated already: the plain gather's plan, which a call
+                             // without room stops at, says how many record bytes pass, and a member adds 31 bytes at the most)
+                             [&](void *dPass) -> uint64_t {
+                                 if (deflate_ == BamOutputDeflate::Host) return 0;
+                                 uint64_t plain = 0, passed = 0;
+                                 const int rc = ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, nullptr, 0, &plain, &passed, nullptr);
+                                 if (rc != TS_OK && !(rc == TS_ERR_INVALID_ARG && plain > 0)) throw deviceError(k.ctx, "gather of the passing records failed");
+                                 return plain + 31u * ((plain + 0xff00u - 1) / 0xff00u);
                              });
                 k.passed += k.judged.nPassed;
                 if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
@@ -2189,9 +2245,11 @@ private:
             from = end;
         }
     }
+    // a sub-batch's passing records to the writer: plain bytes for zlib, or (Device) finished members
     void write(const unsigned char *p, size_t n) {
         const Clock::time_point t0 = Clock::now();
-        writer_.write(p, n);
+        if (deflate_ == BamOutputDeflate::Host) writer_.write(p, n);
+        else if (n) writer_.writeMembers(p, n);
         msWrite += since(t0);
     }
 
@@ -2201,6 +2259,7 @@ private:
     BamHeaderParser header_;
     size_t readsPerBatch_, chunkBytes_, table_;
     BamRecordWalk walk_;
+    BamOutputDeflate deflate_;
     uint64_t plainCap_, compCap_;
     // the reader's state: the next member, whether one may follow, the EOF marker seen
     size_t at_ = 0;
@@ -2222,17 +2281,20 @@ private:
 // The BAM header is parsed on the host from the chunk's leading bytes.  The stages are detail::BamChunkSteps for every filter: a
 // filter of one context takes every chunk in place, on the caller's thread and with no staging region; a filter of several
 // contexts does so on context 0 until the header is behind it, and from the next chunk on the ring deals the chunks to all of
-// them.  perDevice, where given, receives one entry per context.
+// them.  perDevice, where given, receives one entry per context.  `deflate` (BamOutputDeflate, above) moves the output's
+// compression to the device as well; Host is the default and leaves every byte as it was.
 // What a maintainer of the reference would call from runBamSubsetMode (src/bam.cpp:262-316) in place of subsetBam.
-inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
-                                      BamRecordWalk walk = BamRecordWalk::Index, std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+namespace detail {
+// (the route itself, behind bamSubsetDevice's two forms below)
+inline BamSubsetStats bamSubsetDeviceRun(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                         size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice,
+                                         BamOutputDeflate deflate) {
     // the compressed input: a regular file is mapped, a pipe is read to its end
     detail::MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
     std::vector<unsigned char> piped;
     if (!in.data) in.readToEnd(piped, "cannot read BAM input");
     detail::BamChunkSteps steps(filter, in.data ? in.data : piped.data(), in.data ? in.size : piped.size(), out, readsPerBatch,
-                                std::max<size_t>(bytesPerBatch, 1u << 20), walk);
+                                std::max<size_t>(bytesPerBatch, 1u << 20), walk, deflate);
     std::unique_ptr<detail::ChunkRing<detail::BamChunkSteps>> ring;
     if (const uint64_t firstChunk = steps.runInPlace()) {
         ring.reset(new detail::ChunkRing<detail::BamChunkSteps>(filter.deviceCount(), firstChunk, steps));
@@ -2240,7 +2302,23 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
     }
     steps.finish();
     detail::routeFigures(walk == BamRecordWalk::Index ? "bamSubsetDevice (index)" : "bamSubsetDevice (serial)", steps.workers, ring.get(), steps.msWrite, perDevice);
+    for (const auto &k : steps.workers) {
+        steps.stats.deflatePlainBytes += k->st.deflatePlainBytes; steps.stats.deflateMemberBytes += k->st.deflateMemberBytes;
+        steps.stats.msDeflate += k->st.msDeflate;
+    }
     return steps.stats;
+}
+}  // namespace detail
+inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
+                                      BamRecordWalk walk = BamRecordWalk::Index, std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, BamOutputDeflate::Host);
+}
+// ... and with the trailing `deflate` given (an overload, so that the form above stays exactly what it was)
+inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                      size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice,
+                                      BamOutputDeflate deflate) {
+    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, deflate);
 }
 
 // The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as

@@ -280,6 +280,7 @@ SYMBOLS = [
     "ts_gzip_create", "ts_gzip_destroy", "ts_gzip_decode", "ts_gzip_take", "ts_gzip_read", "ts_gzip_history", "ts_gzip_note_fallback", "ts_gzip_stats",
     "ts_bam_chunk_index", "ts_bam_chunk_set_index_geometry", "ts_bam_index_stats",
     "ts_chunk_stage_upload", "ts_chunk_stage_inflate", "ts_chunk_staged", "ts_chunk_commit",
+    "ts_bgzf_deflate", "ts_bam_chunk_gather_bgzf", "ts_bgzf_deflate_stats",
 ]
 
 
@@ -466,6 +467,11 @@ def lib():
     L.ts_bam_chunk_pass_buffer.argtypes = [C.c_void_p, C.c_uint64]
     L.ts_bam_chunk_gather.argtypes = [C.c_void_p, C.POINTER(BamRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64)]
+    L.ts_bam_chunk_gather_bgzf.argtypes = [C.c_void_p, C.POINTER(BamRecord), C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_bgzf_deflate_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ts_chunk_reserve.argtypes = [C.c_void_p, C.c_uint64]
     L.ts_chunk_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.ts_fastq_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.POINTER(FastqRecord), C.c_uint64, C.POINTER(C.c_uint64),

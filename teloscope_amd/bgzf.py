@@ -1,5 +1,6 @@
 """BGZF members inflated on the device (ts_bgzf_inflate of include/teloscan.h): the caller locates the members, the GPU
-decodes and checksums them, a wave per member.  There is no host decoder behind this."""
+decodes and checksums them, a wave per member.  There is no host decoder behind this.  deflate_blocks is the other direction
+(ts_bgzf_deflate): plain bytes in, complete members out, compressed by a wave per member; no zlib behind it either."""
 import ctypes as C
 
 import numpy as np
@@ -31,3 +32,18 @@ def inflate_blocks(ctx, data, blocks, plain_cap=None):
         msg = K.lib().ts_last_error(ctx)
         raise K.TeloscanError(rc, msg.decode() if msg else "ts_bgzf_inflate failed")
     return out[:plain_cap].tobytes(), (int(status.code), int(status.block))
+
+
+def deflate_blocks(ctx, data, payload_bytes=0xFF00):
+    """data: plain bytes, cut into consecutive payloads of payload_bytes (1 .. 65280); ctx: a context pointer.  -> the BGZF
+    members, one per payload, concatenated (no EOF marker; b"" for no data)."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    members = -(-len(src) // payload_bytes) if 0 < payload_bytes <= 0xFF00 else 0
+    out = np.zeros(max(1, len(src) + 31 * members), dtype=np.uint8)      # (a payload grows by 5 bytes at most, plus 26 of framing)
+    nbytes, count = C.c_uint64(0), C.c_uint64(0)
+    rc = K.lib().ts_bgzf_deflate(ctx, src.ctypes.data if len(src) else None, len(src), payload_bytes, out.ctypes.data, len(out),
+                                 C.byref(nbytes), C.byref(count))
+    if rc != K.TS_OK:
+        msg = K.lib().ts_last_error(ctx)
+        raise K.TeloscanError(rc, msg.decode() if msg else "ts_bgzf_deflate failed")
+    return out[:nbytes.value].tobytes()

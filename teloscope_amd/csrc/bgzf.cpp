@@ -313,4 +313,25 @@ int ts_bam_chunk_gather(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, c
                            ts_k_launch_chunk_gather_plan_bam, ts_k_launch_bam_gather);
 }
 
+// ts_bam_chunk_gather with the passing records left on the device, deflated there (deflate.cpp, deflate.hip) and downloaded as
+// BGZF members: what the reference's BgzfWriter makes of them with zlib (src/bgzf.cpp:227-276).
+int ts_bam_chunk_gather_bgzf(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, const void *d_pass, uint32_t payload_bytes,
+                             void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, uint64_t *plain_bytes, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!bytes || !n_passed || !plain_bytes || (n && (!recs || !d_pass)) || (cap && !host_out) || n > 0x7fffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather_bgzf: null or out-of-range argument");
+    *bytes = 0; *n_passed = 0; *plain_bytes = 0;
+    if (payload_bytes == 0 || payload_bytes > 0xff00u)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather_bgzf: payload_bytes is 1 .. 65280");
+    for (size_t i = 0; i < n; ++i)
+        if (!record_ok(ch, recs[i])) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_gather_bgzf: record " + std::to_string(i) + " does not fit the chunk");
+    const int rc = ts_chunk_gather_device(ch, "ts_bam_chunk_gather_bgzf", recs, sizeof(ts_bam_record), n, d_pass, ~0ull, plain_bytes, n_passed,
+                                          stream, ts_k_launch_chunk_gather_plan_bam, ts_k_launch_bam_gather);
+    if (rc != TS_OK || *plain_bytes == 0) return rc;
+    uint64_t members = 0;
+    return ts_deflate_members(ctx, "ts_bam_chunk_gather_bgzf", ch->d_gather.p, *plain_bytes, payload_bytes, ch->bam.deflate, host_out, cap,
+                              bytes, &members, stream);
+}
+
 }  // extern "C"

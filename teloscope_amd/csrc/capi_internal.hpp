@@ -177,6 +177,8 @@ struct ts_ctx {
     // ts_bam_index_stats: calls, spans the chain entered, spans whose entry was a candidate row, spans settled by the serial
     // rule, records the index wrote, bytes of rows copied device to host — since ts_create
     std::atomic<uint64_t> bam_index_stats[6] = {};
+    // ts_bgzf_deflate_stats: device deflate calls, members they wrote, plain bytes in, member bytes out — since ts_create
+    std::atomic<uint64_t> bgzf_deflate_stats[4] = {};
     // ts_read_batch_stats: scans enqueued on general tips batches, segments their read pass judged, rescans after an overflow or
     // spill, bytes those calls copied device to host — since ts_create
     std::atomic<uint64_t> read_batch_stats[4] = {};

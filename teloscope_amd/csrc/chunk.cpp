@@ -62,9 +62,9 @@ int ts_chunk_line_index(ts_bam_chunk *ch, int at_end, const char *who, const cha
     return TS_OK;
 }
 
-int ts_chunk_gather(ts_bam_chunk *ch, const char *who, const void *recs, size_t rec_bytes, size_t n, const void *d_pass,
-                    void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream, ts_chunk_plan_launch plan,
-                    ts_chunk_copy_launch copy) {
+int ts_chunk_gather_device(ts_bam_chunk *ch, const char *who, const void *recs, size_t rec_bytes, size_t n, const void *d_pass,
+                           uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream, ts_chunk_plan_launch plan,
+                           ts_chunk_copy_launch copy) {
     ts_ctx *ctx = ch->ctx;
     const std::string name = who;
     *bytes = 0; *n_passed = 0;
@@ -86,7 +86,18 @@ int ts_chunk_gather(ts_bam_chunk *ch, const char *who, const void *recs, size_t 
     HIP_TRY(ctx, ch->d_gather.ensure((size_t)t[0]));
     if (copy(ch->d_plain.p, ch->d_recs.p, ch->d_dst.p, n, t[0], ch->d_gather.p, stream) != 0)
         return ctx->fail(TS_ERR_HIP, name + ": kernel launch failed");
-    HIP_TRY(ctx, hipMemcpyAsync(host_out, ch->d_gather.p, (size_t)t[0], hipMemcpyDeviceToHost, st));
+    return TS_OK;
+}
+
+int ts_chunk_gather(ts_bam_chunk *ch, const char *who, const void *recs, size_t rec_bytes, size_t n, const void *d_pass,
+                    void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream, ts_chunk_plan_launch plan,
+                    ts_chunk_copy_launch copy) {
+    ts_ctx *ctx = ch->ctx;
+    const int rc = ts_chunk_gather_device(ch, who, recs, rec_bytes, n, d_pass, cap, bytes, n_passed, stream, plan, copy);
+    if (rc != TS_OK || *bytes == 0) return rc;
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, hipMemcpyAsync(host_out, ch->d_gather.p, (size_t)*bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return TS_OK;
 }

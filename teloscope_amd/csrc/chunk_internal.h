@@ -15,6 +15,10 @@ enum { kChunkNewlines = 0, kChunkTail, kChunkLineWords };
 // the unfinished last line (tail = 1: the last byte is no '\n') with at_end only.
 struct LineIndex { uint64_t newlines, tail, n_lines; uint32_t *lstart; unsigned char *first, *cr; };
 
+// the buffers of one device deflate (deflate.cpp: ts_deflate_members) — the members' slots, their sizes and offsets (the total
+// behind the offsets), the packed members
+struct DeflateBufs { DevBuf slots, sizes, offs, packed; };
+
 struct ts_bam_chunk {
     // ---- what every route uses
     ts_ctx *ctx = nullptr;
@@ -45,6 +49,7 @@ struct ts_bam_chunk {
         uint32_t index_span_log2 = 18, index_candidates = 4;
         DevBuf d_idx_rows, d_idx_tasks;
         std::vector<unsigned char> h_idx_rows;
+        DeflateBufs deflate;                // ts_bam_chunk_gather_bgzf's buffers (deflate.cpp)
     } bam;
     // ---- FASTQ (fastq.cpp): the framing results and the stage's jobs
     struct Fastq { DevBuf d_frames, d_jobs; } fastq;
@@ -89,6 +94,18 @@ typedef int (*ts_chunk_copy_launch)(const void *plain, const void *recs, const v
 int  ts_chunk_gather(ts_bam_chunk *ch, const char *who, const void *recs, size_t rec_bytes, size_t n, const void *d_pass,
                      void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream, ts_chunk_plan_launch plan,
                      ts_chunk_copy_launch copy);
+// ... up to the copy kernel: the passing records' bytes stay in ch->d_gather (launched on `stream`, not waited for); cap bounds
+// *bytes as above
+int  ts_chunk_gather_device(ts_bam_chunk *ch, const char *who, const void *recs, size_t rec_bytes, size_t n, const void *d_pass,
+                            uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream, ts_chunk_plan_launch plan,
+                            ts_chunk_copy_launch copy);
+
+// ---- deflate.cpp
+// d_plain[0, n) (device memory of ctx's device) cut into payloads of payload_bytes (1 .. 0xff00), each deflated into one BGZF
+// member on the device (deflate.hip), the members packed and downloaded to host_out: *bytes of them, *n_members.  When *bytes >
+// cap nothing is copied: TS_ERR_INVALID_ARG.  Ordered on `stream`; waits for it.  Counts into ctx->bgzf_deflate_stats.
+int  ts_deflate_members(ts_ctx *ctx, const char *who, const void *d_plain, uint64_t n, uint32_t payload_bytes, DeflateBufs &bufs,
+                        void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_members, void *stream);
 
 // ---- chunk.hip
 extern "C" {

@@ -495,6 +495,14 @@ int  ts_k_launch_bam_index_write(const void *plain, unsigned long long plain_n, 
 int  ts_k_launch_bam_decode(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream);
 int  ts_k_launch_bam_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
                             void *out, void *stream);
+// deflate.hip: a wave per BGZF member written — plain[0, n) (device memory) cut into payloads of payload_bytes (1 .. 0xff00), member
+// i framed in slots + i * stride (zeroed by the caller; stride >= payload_bytes + 33, a multiple of 4; header at byte 2), sizes[i]
+// = its length (zeroed by the caller); then offs[i] = the exclusive sums of the sizes, total[0] their sum and total[1] the count of zero sizes (one wave) ...
+int  ts_k_launch_bgzf_deflate(const void *plain, unsigned long long n, uint32_t payload_bytes, uint32_t n_members, void *slots,
+                              uint32_t stride, uint32_t *sizes, unsigned long long *offs, unsigned long long *total, void *stream);
+// ... and the members copied to packed + offs[i] (packed: 16-byte aligned, cap bytes; slots readable 64 bytes beyond the last)
+int  ts_k_launch_deflate_pack(const void *slots, uint32_t stride, const uint32_t *sizes, const unsigned long long *offs,
+                              uint32_t n_members, unsigned long long cap, void *packed, void *stream);
 // gzip.hip: a window of one gzip member's deflate stream (window: 16-byte aligned, zero from window_len to the next dword).
 // cand[n_spans] = each span's first candidate block start (span 0: start_bit); then a wave per span decodes 16-bit symbols to
 // sym[s * cap ...] and writes table[s] (24 bytes: start_bit, end_bit, n_out, status, final_seen, reserved; status 0xff = no
