@@ -211,6 +211,12 @@ inline ts_block fromBlock(const TelomereBlock &t) {
 
 }  // namespace detail
 
+// What the two assembly device routes (scanFastaToFilesDevice, annotateGfaDevice) do with a Teloscope made over several devices.
+// OneContext, the default: they run on one device and refuse such an object, as they always have — a caller who made it for the
+// host route's shards does not get a thread, a chunk and a share of the text's memory per device without asking.  EveryContext:
+// the routes deal the input's chunks to all of its contexts.  The host routes and the scan methods do not read it.
+enum class DeviceRoutes : uint8_t { OneContext, EveryContext };
+
 class Teloscope {                              // include/teloscope.h:166-300 (scan path only)
 public:
     struct Segment;
@@ -222,6 +228,8 @@ private:
     // downloads its shard over its own PCIe link
     std::vector<detail::CtxPtr> more;
     std::vector<ts_ctx *> all;
+    std::vector<int> ordinals;                  // all[i]'s HIP ordinal as it was asked for (-1 = the current device)
+    DeviceRoutes routes = DeviceRoutes::OneContext;
 
     // writerViewOnly: fill only what writeBEDFile reads (src/teloscope.cpp:700-868) — windows, blocks,
     // canonicalMatches and nonCanonicalMatches; the other three match vectors (all / fwd / rev, which only block
@@ -268,8 +276,9 @@ private:
 
 public:
     // devices: HIP ordinals, one context each (an ordinal may repeat: several contexts share that GPU);
-    // empty = one context on userInput.device
-    explicit Teloscope(UserInputTeloscope ui, const std::vector<int> &devices = {}) : userInput(std::move(ui)) {
+    // empty = one context on userInput.device.  deviceRoutes: see DeviceRoutes
+    explicit Teloscope(UserInputTeloscope ui, const std::vector<int> &devices = {}, DeviceRoutes deviceRoutes = DeviceRoutes::OneContext)
+        : userInput(std::move(ui)), routes(deviceRoutes) {
         std::vector<ts_pattern> pats = detail::makePatterns(userInput);
         const std::vector<int> devs = devices.empty() ? std::vector<int>{userInput.device} : devices;
         for (size_t i = 0; i < devs.size(); ++i) {
@@ -279,34 +288,43 @@ public:
             detail::CtxPtr c(ts_create(&p, pats.data(), pats.size()));
             if (!c) throw std::runtime_error(ts_last_error(nullptr));
             all.push_back(c.get());
+            ordinals.push_back(devs[i]);
             if (i == 0) ctx = std::move(c); else more.push_back(std::move(c));
         }
     }
 
     size_t deviceCount() const { return all.size(); }
-    // the first device's context: what a caller needs to produce bases on that device (ts_bam_chunk_create on it, the
-    // ts_fasta_chunk_* stages: scanFastaToFilesDevice) and hand them over as device segments
-    ts_ctx *context() const { return ctx.get(); }
+    // may the assembly device routes deal their chunks to every context of this object? (the constructor's deviceRoutes)
+    bool deviceRoutesUseEveryContext() const { return routes == DeviceRoutes::EveryContext; }
+    // the i-th context (the first device's by default): what a caller needs to produce bases on that device (ts_bam_chunk_create
+    // on it, the ts_fasta_chunk_* stages: scanFastaToFilesDevice) and hand them over as device segments to a scan ON THAT
+    // CONTEXT.  Every scan method below but scanSegmentsWriterView takes the context to run on as its last argument (0, the
+    // first, by default); calls on different contexts may run at the same time, on a thread each.
+    ts_ctx *context(size_t i = 0) const { return all.at(i); }
+    // the HIP ordinal context i was made on, as the constructor was given it (-1: the device current at that time)
+    int deviceOrdinal(size_t i = 0) const { return ordinals.at(i); }
 
     const UserInputTeloscope &input() const { return userInput; }
     // does the library take TS_INPUT_TEXT_PIECES segments for this parameter set (every set it scans)?
     bool takesTextPieces() const { return ts_takes_text_input(ctx.get(), userInput.ultraFastMode ? 1 : 0) != 0; }
     // keeps the calling thread (and the threads it starts) on the CPUs of the device's NUMA node: ts_bind_thread_to_device
     bool bindThreadToDevice() const { return ts_bind_thread_to_device(ctx.get()) != 0; }
-    // what the first device's context has done with device segments since it was made (ts_device_input_stats): pieces seen,
+    // what a context (the first by default) has done with device segments since it was made (ts_device_input_stats): pieces seen,
     // device-to-device copies, gather jobs, gather launches — cumulative; take the difference around a call
-    std::array<uint64_t, 4> deviceInputStats() const {
+    std::array<uint64_t, 4> deviceInputStats() const { return deviceInputStats(0); }
+    std::array<uint64_t, 4> deviceInputStats(size_t context) const {
         std::array<uint64_t, 4> s{};
-        if (ts_device_input_stats(ctx.get(), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_device_input_stats(all.at(context), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(all.at(context)));
         return s;
     }
 
-    // which way the first device's context reduced the per-side maxima of terminalEnds since it was made (ts_terminal_ends_stats):
+    // which way a context (the first by default) reduced the per-side maxima of terminalEnds since it was made (ts_terminal_ends_stats):
     // segments by the tiled ENDS walk, by the general ENDS walk, on the host from downloaded blocks, bytes of maxima and flag
     // words copied device to host — cumulative; take the difference around a call
-    std::array<uint64_t, 4> terminalEndsStats() const {
+    std::array<uint64_t, 4> terminalEndsStats() const { return terminalEndsStats(0); }
+    std::array<uint64_t, 4> terminalEndsStats(size_t context) const {
         std::array<uint64_t, 4> s{};
-        if (ts_terminal_ends_stats(ctx.get(), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_terminal_ends_stats(all.at(context), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(all.at(context)));
         return s;
     }
 
@@ -320,9 +338,9 @@ public:
         const ts_text_piece *pieces = nullptr; // FASTA body text as it lies in the file (TS_INPUT_TEXT_PIECES): the
                                                // library skips the line ends on the way to the device
         const TextLines *lines = nullptr;      // per piece, optional: lets bases() jump to a position instead of walking lines
-        const char *device = nullptr;          // the device form (TS_INPUT_DEVICE): the same bases in the first context's device
-                                               // memory, which the scan reads; `data` is then an optional host view that serves
-                                               // bases() (-m) and may be nullptr when nothing asks for a base
+        const char *device = nullptr;          // the device form (TS_INPUT_DEVICE): the same bases in the device memory of the
+                                               // context the call is made on, which the scan reads; `data` is then an optional
+                                               // host view that serves bases() (-m) and may be nullptr when nothing asks for a base
         mutable size_t cursorPiece = 0;        // bases() is asked for ascending positions: where the last answer lay
         mutable uint64_t cursorCum = 0;
         Segment(const char *d, size_t n, uint64_t a, bool t) : data(d), size(n), absPos(a), tipsOnly(t) {}
@@ -380,13 +398,14 @@ public:
     };
 
     // batched scanSegment: result[i] is what scanSegment(*segs[i].sequence, absPos, tipsOnly) returns
-    // (writerViewOnly: see convert())
-    std::vector<SegmentData> scanSegments(const std::vector<Segment> &segs, bool writerViewOnly = false) {
+    // (writerViewOnly: see convert()); on context `context`, like every method below that takes one
+    std::vector<SegmentData> scanSegments(const std::vector<Segment> &segs, bool writerViewOnly = false, size_t context = 0) {
+        ts_ctx *const on = all.at(context);
         std::vector<ts_segment_in> in(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
         std::vector<ts_segment_out> out(segs.size());
-        if (ts_scan_segments(ctx.get(), in.data(), in.size(), out.data()) != TS_OK)
-            throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_scan_segments(on, in.data(), in.size(), out.data()) != TS_OK)
+            throw std::runtime_error(ts_last_error(on));
         // SegmentData's five MatchInfo vectors (56-byte records holding a std::string) are the costly part
         // of the mirror: segments are converted on up to 16 host threads, largest first
         std::vector<SegmentData> res(segs.size());
@@ -415,13 +434,14 @@ public:
     // scanSegments for callers that do not read the match vectors (every run without -m): scan, block
     // calling and counting on the device (ts_scan_segments_blocks).  result[i] has windows and blocks;
     // counts[i] = the sizes the match vectors would have had.
-    std::vector<SegmentData> scanSegmentsNoMatches(const std::vector<Segment> &segs, std::vector<ts_segment_counts> &counts) {
+    std::vector<SegmentData> scanSegmentsNoMatches(const std::vector<Segment> &segs, std::vector<ts_segment_counts> &counts, size_t context = 0) {
+        ts_ctx *const on = all.at(context);
         std::vector<ts_segment_in> in(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
         std::vector<ts_segment_out> out(segs.size());
         counts.assign(segs.size(), ts_segment_counts{0, 0, 0, 0});
-        if (ts_scan_segments_blocks(ctx.get(), in.data(), in.size(), out.data(), counts.data()) != TS_OK)
-            throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_scan_segments_blocks(on, in.data(), in.size(), out.data(), counts.data()) != TS_OK)
+            throw std::runtime_error(ts_last_error(on));
         // (window records of a long contig are millions: segments are converted on up to 16 host threads)
         std::vector<SegmentData> res(segs.size());
         std::atomic<size_t> next{0};
@@ -443,17 +463,18 @@ public:
     // scanSegmentsNoMatches with the windows left on the device: result[i] has blocks only, counts[i].n_windows says how many
     // windows segs[i] has, and `text` receives the lines of the five window tracks of all full-scan segments in input order,
     // segs[i]'s under names[i] — formatted on the device (ts_scan_segments_tracks) in place of WindowData on the host and
-    // BedWriter's formatting threads.  One device.
+    // BedWriter's formatting threads.  One context: the one given.
     std::vector<SegmentData> scanSegmentsTrackText(const std::vector<Segment> &segs, const std::vector<const char *> &names,
-                                                   std::vector<ts_segment_counts> &counts, TrackText &text) {
+                                                   std::vector<ts_segment_counts> &counts, TrackText &text, size_t context = 0) {
+        ts_ctx *const on = all.at(context);
         if (names.size() != segs.size()) throw std::runtime_error("scanSegmentsTrackText: one name per segment");
         std::vector<ts_segment_in> in(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
         std::vector<ts_segment_out> out(segs.size());
         counts.assign(segs.size(), ts_segment_counts{0, 0, 0, 0});
         // (the call replaces what `text` holds and reuses its arrays)
-        if (ts_scan_segments_tracks(ctx.get(), in.data(), in.size(), names.data(), out.data(), counts.data(), &text.t) != TS_OK)
-            throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_scan_segments_tracks(on, in.data(), in.size(), names.data(), out.data(), counts.data(), &text.t) != TS_OK)
+            throw std::runtime_error(ts_last_error(on));
         std::vector<SegmentData> res(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) res[i] = convert(out[i], segs[i]);
         ts_free_segments(out.data(), out.size());
@@ -463,27 +484,29 @@ public:
     // scanSegmentsTrackText under -m: the match lines of all full-scan segments leave as text too (text.m: the canonical and the
     // terminal non-canonical file, formatted on the device from the match records and the input buffer where they lie —
     // ts_scan_segments_text), so neither a match record nor a base comes back; result[i] has blocks only, counts[i] the sizes
-    // the match vectors would have had.  One device.
+    // the match vectors would have had.  One context: the one given.
     std::vector<SegmentData> scanSegmentsText(const std::vector<Segment> &segs, const std::vector<const char *> &names,
-                                              std::vector<ts_segment_counts> &counts, TrackText &text) {
+                                              std::vector<ts_segment_counts> &counts, TrackText &text, size_t context = 0) {
+        ts_ctx *const on = all.at(context);
         if (names.size() != segs.size()) throw std::runtime_error("scanSegmentsText: one name per segment");
         std::vector<ts_segment_in> in(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
         std::vector<ts_segment_out> out(segs.size());
         counts.assign(segs.size(), ts_segment_counts{0, 0, 0, 0});
         // (the call replaces what `text` holds and reuses its arrays)
-        if (ts_scan_segments_text(ctx.get(), in.data(), in.size(), names.data(), out.data(), counts.data(), &text.t, &text.m) != TS_OK)
-            throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_scan_segments_text(on, in.data(), in.size(), names.data(), out.data(), counts.data(), &text.t, &text.m) != TS_OK)
+            throw std::runtime_error(ts_last_error(on));
         std::vector<SegmentData> res(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) res[i] = convert(out[i], segs[i]);
         ts_free_segments(out.data(), out.size());
         return res;
     }
-    // what the first device's context has formatted as match lines since it was made (ts_match_text_stats): calls, canonical
+    // what a context (the first by default) has formatted as match lines since it was made (ts_match_text_stats): calls, canonical
     // lines, non-canonical lines, text bytes — cumulative
-    std::array<uint64_t, 4> matchTextStats() const {
+    std::array<uint64_t, 4> matchTextStats() const { return matchTextStats(0); }
+    std::array<uint64_t, 4> matchTextStats(size_t context) const {
         std::array<uint64_t, 4> s{};
-        if (ts_match_text_stats(ctx.get(), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_match_text_stats(all.at(context), s.data()) != TS_OK) throw std::runtime_error(ts_last_error(all.at(context)));
         return s;
     }
 
@@ -491,6 +514,7 @@ public:
     // nonCanonicalMatches, nothing else), over ALL the object's devices: ts_scan_segments_multi cuts the batch into one
     // shard per device; block calling happens on the devices and only that view comes back.  result[i] has windows,
     // blocks and those two match vectors (the other three stay empty); counts[i] = the sizes the match vectors had.
+    // Host segments only: a device segment's address belongs to one context, and is scanned by a call on that context.
     std::vector<SegmentData> scanSegmentsWriterView(const std::vector<Segment> &segs, std::vector<ts_segment_counts> &counts) {
         std::vector<ts_segment_in> in(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) in[i] = segs[i].in();
@@ -517,12 +541,13 @@ public:
 
     // The GFA annotation's numbers (ts_terminal_ends): for every segment (tipsOnly is implied), {longest terminal block at
     // the start side, at the end side} of scanSegment(seq, absPos, true) — walkSegment's rule, src/input.cpp:849-853; 0 = none
-    std::vector<std::pair<uint32_t, uint32_t>> terminalEnds(const std::vector<Segment> &segs) {
+    std::vector<std::pair<uint32_t, uint32_t>> terminalEnds(const std::vector<Segment> &segs, size_t context = 0) {
+        ts_ctx *const on = all.at(context);
         std::vector<ts_segment_in> in(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) { in[i] = segs[i].in(); in[i].tips_only = 1; }
         std::vector<uint32_t> ends(2 * segs.size());
-        if (ts_terminal_ends(ctx.get(), in.data(), in.size(), ends.data()) != TS_OK)
-            throw std::runtime_error(ts_last_error(ctx.get()));
+        if (ts_terminal_ends(on, in.data(), in.size(), ends.data()) != TS_OK)
+            throw std::runtime_error(ts_last_error(on));
         std::vector<std::pair<uint32_t, uint32_t>> res(segs.size());
         for (size_t i = 0; i < segs.size(); ++i) res[i] = {ends[2 * i], ends[2 * i + 1]};
         return res;

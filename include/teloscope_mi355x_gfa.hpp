@@ -9,7 +9,8 @@
 // or annotateGfa(teloscope, file, outDir) for all four.  The device reduces a segment to {longest terminal block at its start
 // side, at its end side} (ts_terminal_ends): 8 bytes per segment, whatever the number of blocks.
 //
-// annotateGfaDevice(teloscope, file, outDir) is the device route of the same (not the default): the text lies in device memory,
+// annotateGfaDevice(teloscope, file, outDir) is the device route of the same (not the default; on every context of a
+// Teloscope made with DeviceRoutes::EveryContext): the text lies in device memory,
 // lines and tabs are indexed there (ts_gfa_chunk_walk) and the segments are scanned where they lie; see its comment below.
 //
 // Input lines are written back verbatim (line ends as read) with two exceptions: the header says VN:Z:1.2 (added when the input
@@ -28,6 +29,7 @@
 #pragma once
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -38,6 +40,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <tuple>
 #include <unordered_map>
 #include <utility>
@@ -274,9 +277,15 @@ inline std::vector<GfaEnd> gfaTerminalJobs(const GfaGraph &g, const std::vector<
 // The distinct segments with a sequence that the ends use, in one Teloscope::terminalEnds call (each segment once, scanned
 // where it lies in the input buffer; the library folds case as unmaskSequence does).  Warns on `log` about ends whose
 // segment has no sequence, in the reference's words.
-// onDevice: every GfaSegment::seq is an address in the first context's device memory (annotateGfaDevice), scanned from there.
+// onDevice: every GfaSegment::seq is an address in device memory (annotateGfaDevice), scanned from there: the first context's, or
+// — segContext given, one entry per graph segment — that of context segContext[i] of the Teloscope.  The wanted segments are then
+// grouped by their context and ONE terminalEnds call per context that owns any runs, a thread per context, each on its own
+// device and bound to the CPUs of its NUMA node (ts_bind_thread_to_device), as the ring's threads are; the results go back in
+// segment order.  scannedBases and scanMs, where given, receive per context the bases it scanned and the milliseconds its own
+// call took (0 for a context that owns none of the wanted segments).
 inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::vector<GfaEnd> &jobs, std::ostream &log = std::cerr,
-                           bool onDevice = false) {
+                           bool onDevice = false, const std::vector<uint32_t> *segContext = nullptr,
+                           std::vector<uint64_t> *scannedBases = nullptr, std::vector<double> *scanMs = nullptr) {
     GfaEnds r;
     r.ends.assign(g.segments.size(), {0u, 0u});
     std::vector<char> want(g.segments.size(), 0);
@@ -287,18 +296,42 @@ inline GfaEnds gfaScanEnds(Teloscope &teloscope, const GfaGraph &g, const std::v
     if (r.noSeq)
         log << "Warning: " << r.noSeq << " of " << jobs.size()
             << " GFA segment(s) had no sequence (*); skipped for telomere annotation.\n";
-    std::vector<uint32_t> which;
-    std::vector<Teloscope::Segment> segs;
+    const size_t nctx = onDevice && segContext ? teloscope.deviceCount() : 1;
+    std::vector<std::vector<uint32_t>> which(nctx);
+    std::vector<std::vector<Teloscope::Segment>> segs(nctx);
+    if (scannedBases) scannedBases->assign(nctx, 0);
+    if (scanMs) scanMs->assign(nctx, 0.0);
     for (uint32_t i = 0; i < g.segments.size(); ++i)
         if (want[i]) {
-            which.push_back(i);
-            segs.emplace_back(onDevice ? nullptr : g.segments[i].seq, g.segments[i].len, 0, true);
-            if (onDevice) segs.back().device = g.segments[i].seq;
+            const size_t c = nctx > 1 ? (*segContext)[i] : 0;
+            which[c].push_back(i);
+            segs[c].emplace_back(onDevice ? nullptr : g.segments[i].seq, g.segments[i].len, 0, true);
+            if (onDevice) segs[c].back().device = g.segments[i].seq;
+            if (scannedBases) (*scannedBases)[c] += g.segments[i].len;
+            ++r.scanned;
         }
-    r.scanned = which.size();
-    if (segs.empty()) return r;
-    const std::vector<std::pair<uint32_t, uint32_t>> e = teloscope.terminalEnds(segs);
-    for (size_t k = 0; k < which.size(); ++k) r.ends[which[k]] = e[k];
+    if (!r.scanned) return r;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> e(nctx);
+    std::vector<std::exception_ptr> errors(nctx);
+    auto scan = [&](size_t c, bool ownThread) {
+        const auto t0 = std::chrono::steady_clock::now();
+        try {
+            if (ownThread) ts_bind_thread_to_device(teloscope.context(c));
+            e[c] = teloscope.terminalEnds(segs[c], c);
+        } catch (...) { errors[c] = std::current_exception(); }
+        if (scanMs) (*scanMs)[c] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    size_t busy = 0, only = 0;
+    for (size_t c = 0; c < nctx; ++c) if (!segs[c].empty()) { ++busy; only = c; }
+    if (busy == 1) scan(only, false);
+    else {
+        std::vector<std::thread> threads;
+        for (size_t c = 0; c < nctx; ++c) if (!segs[c].empty()) threads.emplace_back(scan, c, true);
+        for (std::thread &t : threads) t.join();
+    }
+    for (size_t c = 0; c < nctx; ++c) if (errors[c]) std::rethrow_exception(errors[c]);
+    for (size_t c = 0; c < nctx; ++c)
+        for (size_t k = 0; k < which[c].size(); ++k) r.ends[which[c][k]] = e[c][k];
     return r;
 }
 
@@ -509,7 +542,7 @@ inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &fil
 // anywhere), so every walked chunk STAYS RESIDENT; an unfinished last line moves into the next chunk device to device
 // (ts_chunk_carry_over).  After the last chunk the host builds the graph exactly as readGfa does (names, hash index, paths,
 // version, edits), gfaTerminalJobs picks the ends, and ONE terminalEnds call scans the wanted segments where they lie in the
-// chunks (TS_INPUT_DEVICE, no host view).  The writer takes the input's bytes from the mapping, from the zlib blocks as they were
+// chunks (TS_INPUT_DEVICE, no host view; one call per context where the Teloscope has several: below).  The writer takes the input's bytes from the mapping, from the zlib blocks as they were
 // produced, or — BGZF — from the chunks, read back piece by piece.
 // Assembly record filters: the form with a selector mirrors annotateGfa(teloscope, file, outDir, selector, log).  With an active
 // selector the .gfa2 / .gfa2.gz name check comes first; ts_gfa_chunk_check judges every chunk's lines by validateFilteredGfa's
@@ -517,97 +550,207 @@ inline GfaAnnotateStats annotateGfa(Teloscope &teloscope, const std::string &fil
 // over the chunks; after the last chunk the first offence is thrown with validateFilteredGfa's message, then come the graph
 // build's errors, selectGfa, its line on `log`, and the ends of the selected paths / segments only.  The text is uploaded and
 // indexed once, where the host route reads and walks the file twice.  An inactive selector changes nothing.
-// Limits: ONE device (a Teloscope over several throws); a line of more than
-// 4 GiB - 2 bytes is refused with its byte offset; a text that does not fit the device's free memory is refused with a message
-// that names annotateGfa; the stages run one after the other.  With a GFA 2 input that holds both a foreign record and a segment
+// Several contexts (a Teloscope made over a device list with DeviceRoutes::EveryContext — without it such an object is refused
+// as before, "runs on one device"; with and without a selector): detail::ChunkRing deals chunk k to
+// context k mod N, a thread per context; the new bytes are staged while the chunks before are framed, and the serial section
+// carries the unfinished last line over (across contexts), commits, walks, checks and appends the tables in chunk order
+// (detail::GfaChunkSteps, for every count: one context fills each chunk in place on the caller's thread).  Every chunk stays
+// resident on the context that took it, so N devices hold the text between them; the wanted segments are grouped by the context
+// that owns their line and ONE terminalEnds call per context runs, a thread each; the writer reads BGZF pieces back from
+// whichever context's chunk holds them.  Files, warnings, exceptions and their order, and GfaAnnotateStats do not depend on N
+// (tests/test_gpu_assembly_routes_multi.py).  perDevice, where given, receives one entry per context (AssemblyRouteDeviceStats,
+// teloscope_mi355x_io.hpp); TS_TIMING=1 prints a line per context beside the line of totals.
+// Limits: a line of more than
+// 4 GiB - 2 bytes is refused with its byte offset; a text that does not fit the devices' free memory is refused with a message
+// that names annotateGfa, the context that could not allocate and the bytes resident over all contexts; on one context the
+// stages run one after the other.  With a GFA 2 input that holds both a foreign record and a segment
 // named twice, the foreign record is reported (readGfa reports whichever comes first by its 16 MB parse blocks).
 namespace detail {
-inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::string &file, const std::string &outDir,
-                                              const SequenceSelector *selector, std::ostream &log, size_t chunkBytesArg) {
-    using Clock = std::chrono::steady_clock;
-    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    const auto tBegin = Clock::now();
-    const bool filtered = selector && selector->active();
-    if (filtered) detail::refuseGfa2Name(file);
-    if (teloscope.deviceCount() > 1)
-        throw std::runtime_error("annotateGfaDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
-                                 " (the graph's text lies in one device's memory)");
-    ts_ctx *ctx = teloscope.context();
-    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
-    constexpr uint64_t kChunkLimit = 0xfffffffeull;             // what ts_gfa_chunk_walk takes
-    double msUpload = 0, msIndex = 0, msGraph = 0;
 
-    struct ChunkFree { void operator()(ts_chunk *c) const { ts_bam_chunk_destroy(c); } };
-    std::vector<std::unique_ptr<ts_chunk, ChunkFree>> chunks;   // every one stays until the scan and the write are done
-    uint64_t resident = 0;
-    auto noRoom = [&](const char *what) -> std::runtime_error {
-        const char *why = ts_last_error(ctx);
-        return std::runtime_error(std::string("annotateGfaDevice: ") + what + " with " + std::to_string(resident) +
-                                  " bytes of the graph's text resident (" + (why ? why : "?") +
-                                  "): the text does not fit the device's free memory; use annotateGfa, the host route");
-    };
+// annotateGfaDevice's chunk stages, for a Teloscope of any number of contexts.  Every walked chunk stays resident on the context
+// that took it, so each chunk is a ts_chunk of its own; the two ways its bytes come in are the read routes'
+// (teloscope_mi355x_io.hpp): in place on one context, on the caller's thread, a chunk that holds no whole line growing where it
+// is; dealt by detail::ChunkRing on several, chunk k to context k mod N, the new bytes staged while the chunks before it are
+// framed.  The serial section places the unfinished last line of chunk k - 1 in front (ts_chunk_carry_over, across contexts),
+// commits the staged bytes, walks (ts_gfa_chunk_walk), checks (ts_gfa_chunk_check, with an active selector; line numbers run over
+// the chunks) and appends the tables to the host's, in chunk order.  A dealt chunk that holds no whole line hands all of its
+// bytes on and is given up once they have moved; judge and emit are empty.
+class GfaChunkSteps {
+public:
     // the input's bytes for the writer, in the pieces they arrived in: host memory, or bytes [at, at + len) of a chunk
     struct Piece { const char *host; ts_chunk *chunk; uint64_t at, start, len; };
+    // what a chunk's walk gave; base: the input offset of the chunk's first byte; context: whose memory the chunk lies in
+    struct Walked { ts_chunk *chunk; size_t context; uint64_t base; std::vector<ts_gfa_segment> segs; std::vector<ts_gfa_line> lines; std::vector<char> text; ts_gfa_foreign foreign; };
+    struct Held {
+        ts_chunk *chunk = nullptr;
+        std::atomic<bool> spent{false};                         // all of its bytes moved on: its owner gives it up
+        explicit Held(ts_chunk *c) : chunk(c) {}
+        Held(const Held &) = delete;
+        Held &operator=(const Held &) = delete;
+        ~Held() { ts_bam_chunk_destroy(chunk); }
+    };
+    struct Worker {
+        size_t index = 0;
+        ts_ctx *ctx = nullptr;
+        std::vector<std::unique_ptr<Held>> chunks;              // every one stays until the scan and the write are done
+        Held *cur = nullptr;
+        ChunkFeed::Fill fill;                                   // a dealt chunk's new bytes
+        std::vector<ts_gfa_flagged> flagged = std::vector<ts_gfa_flagged>(64);
+        AssemblyRouteDeviceStats st;
+    };
+    static constexpr uint64_t kChunkLimit = 0xfffffffeull;      // what ts_gfa_chunk_walk takes
+
+    std::vector<std::unique_ptr<Worker>> workers;
     std::vector<Piece> pieces;
     std::vector<std::vector<char>> blocks;                      // zlib's output as it was produced
     uint64_t total = 0;
-    ts_chunk *cur = nullptr, *prev = nullptr;
-    detail::ChunkFeed::Options options;
-    options.cannotOpen = "Could not open assembly input '" + file + "'.";
-    options.cannotRead = "Could not read assembly input '" + file + "'.";
-    options.zlibAlways = true;
-    options.growFailed = "cannot grow a device chunk";
-    options.uploadFailed = "upload of the GFA text failed";
-    options.noRoom = noRoom;
-    options.sink = [&](const char *host, uint64_t chunkAt, uint64_t len) {
-        pieces.push_back({host, host ? nullptr : cur, chunkAt, total, len});
-        total += len;
-    };
-    detail::ChunkFeed feed(ctx, file, options);
-    const uint64_t chunkLimit = feed.chunkLimit(kChunkLimit);
-    const size_t chunkBytes = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit));
-    const uint64_t compCap = feed.compCap(chunkBytes);
-    // what a chunk's walk gave; base: the input offset of the chunk's first byte
-    struct Walked { ts_chunk *chunk; uint64_t base; std::vector<ts_gfa_segment> segs; std::vector<ts_gfa_line> lines; std::vector<char> text; ts_gfa_foreign foreign; };
     std::vector<Walked> walked;
-
     // filters: the first line that breaks validateFilteredGfa's rules (code 0: none so far), lines counted over the chunks
     int offence = 0;
     char offenceType = 0;
-    uint64_t offenceLine = 0, linesBefore = 0;
-    std::vector<ts_gfa_flagged> flagged(64);
+    uint64_t offenceLine = 0;
+    std::unique_ptr<ChunkFeed> feed;
 
-    uint64_t held = 0, prevNext = 0, base = 0;
-    bool atEnd = false, grow = false;
-    while (!atEnd) {
-        Clock::time_point t0 = Clock::now();
-        uint64_t carry = held;                                  // growing: the whole chunk is one unfinished line
-        if (!grow) carry = prev ? ts_bam_chunk_size(prev) - prevNext : 0;
-        if (carry >= chunkLimit)
-            throw std::runtime_error("the line at byte offset " + std::to_string(base) + " of '" + file + "' has more than " + std::to_string(chunkLimit) +
-                                     " bytes and does not fit a device chunk; use annotateGfa, the host route");
-        // a chunk that held no whole line takes as much again, up to what a chunk may hold
-        const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, grow ? carry : 0), chunkLimit - carry));
-        std::vector<char> *keep = nullptr;
-        if (feed.source() == detail::ChunkFeed::Stream) { blocks.emplace_back(); keep = &blocks.back(); }   // zlib's next block, kept for the writer
-        const uint64_t room = feed.read(want, keep);            // (known for a mapped plain file and a block read, a guess for BGZF members)
-        if (!grow) {
-            ts_chunk *made = ts_bam_chunk_create(ctx, compCap, std::max<uint64_t>(carry + room, 64));
-            if (!made) throw noRoom("cannot make a device chunk");
-            chunks.emplace_back(made);
-            cur = made;
-            if (carry && ts_chunk_carry_over(cur, prev, prevNext, nullptr) != TS_OK) throw noRoom("cannot carry a line into the next device chunk");
+    GfaChunkSteps(Teloscope &teloscope, const std::string &file, bool filtered, size_t chunkBytesArg) : file_(file), filtered_(filtered) {
+        for (size_t w = 0; w < teloscope.deviceCount(); ++w) {
+            workers.emplace_back(new Worker());
+            workers.back()->index = w;
+            workers.back()->ctx = teloscope.context(w);
+            workers.back()->st.device = teloscope.deviceOrdinal(w);
         }
-        atEnd = feed.put(cur, 0);
-        msUpload += since(t0);
-        resident += ts_bam_chunk_size(cur) - held * (grow ? 1 : 0);
-        held = ts_bam_chunk_size(cur);
-        if (held == 0) continue;
+        ChunkFeed::Options options;
+        options.cannotOpen = "Could not open assembly input '" + file + "'.";
+        options.cannotRead = "Could not read assembly input '" + file + "'.";
+        options.zlibAlways = true;
+        options.growFailed = "cannot grow a device chunk";
+        options.uploadFailed = "upload of the GFA text failed";
+        options.noRoom = [this](const char *what) { return noRoom(*workers[0], what); };         // (the in-place fills: context 0's)
+        options.sink = [this](const char *host, uint64_t chunkAt, uint64_t len) {
+            pieces.push_back({host, host ? nullptr : workers[0]->cur->chunk, chunkAt, total, len});
+            total += len;
+        };
+        if (workers.size() > 1) options.gzipDevice = false;      // (bound to one context: plain gzip is read through zlib)
+        feed.reset(new ChunkFeed(workers[0]->ctx, file, options));
+        chunkLimit_ = feed->chunkLimit(kChunkLimit);
+        chunkBytes_ = static_cast<size_t>(std::min<uint64_t>(std::max<size_t>(chunkBytesArg, 64), chunkLimit_));
+        compCap_ = feed->compCap(chunkBytes_);
+    }
 
-        // segments, P / H lines and names
-        t0 = Clock::now();
+    // "does not fit the device's free memory": the context that could not allocate, and what is resident over all of them
+    std::runtime_error noRoom(const Worker &k, const char *what) const {
+        const char *why = ts_last_error(k.ctx);
+        return std::runtime_error(std::string("annotateGfaDevice: ") + what + " on context " + std::to_string(k.index) + " of " + std::to_string(workers.size()) +
+                                  " (device " + std::to_string(k.st.device) + ") with " + std::to_string(resident_.load()) +
+                                  " bytes of the graph's text resident over all contexts (" + (why ? why : "?") +
+                                  "): the text does not fit the device's free memory; use annotateGfa, the host route");
+    }
+
+    // The whole input as in-place chunks of context 0, on the caller's thread: any source of the feed
+    void runInPlace() {
+        Worker &k = *workers[0];
+        uint64_t held = 0;
+        bool atEnd = false, grow = false;
+        while (!atEnd) {
+            const Clock::time_point t0 = Clock::now();
+            uint64_t carry = held;                              // growing: the whole chunk is one unfinished line
+            if (!grow) carry = prev_ ? prevSize_ - prevNext_ : 0;
+            if (carry >= chunkLimit_) throw lineTooLong();
+            // a chunk that held no whole line takes as much again, up to what a chunk may hold
+            const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes_, grow ? carry : 0), chunkLimit_ - carry));
+            std::vector<char> *keep = nullptr;
+            if (feed->source() == ChunkFeed::Stream) { blocks.emplace_back(); keep = &blocks.back(); }   // zlib's next block, kept for the writer
+            const uint64_t room = feed->read(want, keep);       // (known for a mapped plain file and a block read, a guess for BGZF members)
+            if (!grow) {
+                make(k, carry + room);
+                if (carry && ts_chunk_carry_over(k.cur->chunk, prev_->chunk, prevNext_, nullptr) != TS_OK) throw noRoom(k, "cannot carry a line into the next device chunk");
+                ++k.st.chunks;
+            }
+            atEnd = feed->put(k.cur->chunk, 0);
+            k.st.msFill += since(t0);
+            const uint64_t now = ts_bam_chunk_size(k.cur->chunk);
+            resident_ += now - (grow ? held : 0);
+            k.st.bytesReceived += now - carry;
+            held = now;
+            if (held == 0) continue;
+            grow = !walk(k, atEnd, held);                       // no whole line yet: the chunk takes more
+        }
+    }
+
+    // the ring's steps: a dealt chunk
+    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
+    RingTake take(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        feed->take(chunkBytes_, k.fill);
+        return k.fill.atEnd ? RingTake::Last : RingTake::More;
+    }
+    void stage(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        k.chunks.erase(std::remove_if(k.chunks.begin(), k.chunks.end(), [](const std::unique_ptr<Held> &h) { return h->spent.load(); }), k.chunks.end());
+        make(k, k.fill.n);
+        const std::function<std::runtime_error(const char *)> refuse = [&](const char *what) { return noRoom(k, what); };
+        feed->stage(k.ctx, k.cur->chunk, k.fill, &refuse);
+        resident_ += k.fill.n;
+        k.st.msStage += since(t0);
+        ++k.st.chunks; k.st.bytesReceived += k.fill.n;
+    }
+    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, walk, check, the tables appended
+        Worker &k = *workers[w];
+        const uint64_t carry = prev_ ? prevSize_ - prevNext_ : 0;
+        if (carry >= chunkLimit_) throw lineTooLong();
+        const Clock::time_point t0 = Clock::now();
+        if (prev_ && ts_chunk_carry_over(k.cur->chunk, prev_->chunk, prevNext_, nullptr) != TS_OK) throw noRoom(k, "cannot carry a line into the next device chunk");
+        if (prev_ && prevWhole_) {                              // all of that chunk's bytes are here now, at the same offsets
+            // (the pieces of the unfinished line, which begins at input offset base_, are the list's last ones)
+            for (size_t i = pieces.size(); i-- > 0 && pieces[i].start + pieces[i].len > base_;)
+                if (pieces[i].chunk == prev_->chunk) pieces[i].chunk = k.cur->chunk;
+            resident_ -= prevSize_;
+            prev_->spent.store(true);
+        }
+        if (ts_chunk_commit(k.cur->chunk, nullptr) != TS_OK) throw noRoom(k, "cannot grow a device chunk");
+        k.st.msCommit += since(t0);
+        resident_ += carry;
+        // the new bytes for the writer: where they lie on the host, or behind the carry in the chunk
+        if (k.fill.n) {
+            if (k.fill.calls.empty()) {
+                pieces.push_back({k.fill.host, nullptr, 0, total, k.fill.n});
+                if (!k.fill.block.empty()) blocks.push_back(std::move(k.fill.block));    // (its bytes stay where they are)
+            } else {
+                pieces.push_back({nullptr, k.cur->chunk, carry, total, k.fill.n});
+            }
+            total += k.fill.n;
+        }
+        const uint64_t held = ts_bam_chunk_size(k.cur->chunk);
+        if (held == 0 || !walk(k, k.fill.atEnd, held)) { prev_ = k.cur; prevNext_ = 0; prevSize_ = held; prevWhole_ = true; }
+        return true;
+    }
+    void judge(size_t, uint64_t) {}                             // (every chunk stays resident on its own context: the scan comes
+    void emit(size_t, uint64_t) {}                              // after the last one)
+
+    std::runtime_error chunkError(const Worker &k, const char *what) const { return deviceError(k.ctx, what); }
+
+private:
+    using Clock = std::chrono::steady_clock;
+    static double since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+    void make(Worker &k, uint64_t room) {
+        ts_chunk *made = ts_bam_chunk_create(k.ctx, compCap_, std::max<uint64_t>(room, 64));
+        if (!made) throw noRoom(k, "cannot make a device chunk");
+        k.chunks.emplace_back(new Held(made));
+        k.cur = k.chunks.back().get();
+    }
+    std::runtime_error lineTooLong() const {
+        return std::runtime_error("the line at byte offset " + std::to_string(base_) + " of '" + file_ + "' has more than " + std::to_string(chunkLimit_) +
+                                  " bytes and does not fit a device chunk; use annotateGfa, the host route");
+    }
+    // Segments, P / H lines and names of k's current chunk, which has its `held` bytes; with an active selector its whole lines
+    // by the filtered loader's rules; the tables appended and the framing's state moved on.  -> false: the chunk holds no whole
+    // line yet, and nothing was appended
+    bool walk(Worker &k, bool atEnd, uint64_t held) {
+        ts_chunk *cur = k.cur->chunk;
+        Clock::time_point t0 = Clock::now();
         Walked w;
-        w.chunk = cur; w.base = base;
+        w.chunk = cur; w.context = k.index; w.base = base_;
         w.segs.resize(4096); w.lines.resize(256); w.text.resize(size_t(1) << 16);
         uint64_t nSegs = 0, nLines = 0, textBytes = 0, next = 0;
         int rc = ts_gfa_chunk_walk(cur, atEnd ? 1 : 0, w.segs.data(), w.segs.size(), &nSegs, w.lines.data(), w.lines.size(), &nLines,
@@ -619,40 +762,87 @@ inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::s
             rc = ts_gfa_chunk_walk(cur, atEnd ? 1 : 0, w.segs.data(), w.segs.size(), &nSegs, w.lines.data(), w.lines.size(), &nLines,
                                    w.text.data(), w.text.size(), &textBytes, &next, &w.foreign);
         }
-        if (rc != TS_OK) throw fail("GFA walk failed");
-        msIndex += since(t0);
-        if (!atEnd && next == 0) { grow = true; continue; }     // no whole line yet: the chunk takes more
-        grow = false;
-        if (filtered && !offence) {                             // the chunk's whole lines by the filtered loader's rules
+        if (rc != TS_OK) throw chunkError(k, "GFA walk failed");
+        k.st.msIndex += since(t0);
+        if (!atEnd && next == 0) return false;
+        if (filtered_ && !offence) {                            // the chunk's whole lines by the filtered loader's rules
             t0 = Clock::now();
-            uint64_t nFlagged = 0, nLines = 0;
-            rc = ts_gfa_chunk_check(cur, atEnd ? 1 : 0, flagged.data(), flagged.size(), &nFlagged, &nLines);
-            if (rc == TS_ERR_INVALID_ARG && nFlagged > flagged.size()) {
-                flagged.resize(static_cast<size_t>(nFlagged));
-                rc = ts_gfa_chunk_check(cur, atEnd ? 1 : 0, flagged.data(), flagged.size(), &nFlagged, &nLines);
+            uint64_t nFlagged = 0, nChecked = 0;
+            rc = ts_gfa_chunk_check(cur, atEnd ? 1 : 0, k.flagged.data(), k.flagged.size(), &nFlagged, &nChecked);
+            if (rc == TS_ERR_INVALID_ARG && nFlagged > k.flagged.size()) {
+                k.flagged.resize(static_cast<size_t>(nFlagged));
+                rc = ts_gfa_chunk_check(cur, atEnd ? 1 : 0, k.flagged.data(), k.flagged.size(), &nFlagged, &nChecked);
             }
-            if (rc != TS_OK) throw fail("GFA check failed");
-            for (uint64_t k = 0; k < nFlagged && !offence; ++k) {
-                const ts_gfa_flagged &fl = flagged[static_cast<size_t>(k)];
+            if (rc != TS_OK) throw chunkError(k, "GFA check failed");
+            for (uint64_t i = 0; i < nFlagged && !offence; ++i) {
+                const ts_gfa_flagged &fl = k.flagged[static_cast<size_t>(i)];
                 int code = static_cast<int>(fl.code);
                 char type = static_cast<char>(fl.type);
                 if (fl.code == TS_GFA_CHECK_HOST_DECIDES) {     // a '\r' inside the line: the host's rule on the line itself
                     std::string line(fl.len, '\0');
-                    if (fl.len && ts_bam_chunk_read(cur, fl.off, fl.len, &line[0]) != TS_OK) throw fail("cannot read the chunk");
+                    if (fl.len && ts_bam_chunk_read(cur, fl.off, fl.len, &line[0]) != TS_OK) throw chunkError(k, "cannot read the chunk");
                     line.erase(std::remove(line.begin(), line.end(), '\r'), line.end());
-                    code = detail::filteredGfaLineCode(line);
+                    code = filteredGfaLineCode(line);
                     type = line.empty() ? 0 : line[0];
                 }
-                if (code) { offence = code; offenceType = type; offenceLine = linesBefore + fl.line + 1; }
+                if (code) { offence = code; offenceType = type; offenceLine = linesBefore_ + fl.line + 1; }
             }
-            linesBefore += nLines;
-            msIndex += since(t0);
+            linesBefore_ += nChecked;
+            k.st.msIndex += since(t0);
         }
         w.segs.resize(static_cast<size_t>(nSegs)); w.lines.resize(static_cast<size_t>(nLines)); w.text.resize(static_cast<size_t>(textBytes));
         w.segs.shrink_to_fit(); w.lines.shrink_to_fit(); w.text.shrink_to_fit();
+        k.st.records += nSegs;
         walked.push_back(std::move(w));
-        prev = cur; prevNext = next; base += next;
+        prev_ = k.cur; prevNext_ = next; prevSize_ = held; prevWhole_ = false;
+        base_ += next;
+        return true;
     }
+
+    std::string file_;
+    bool filtered_;
+    uint64_t chunkLimit_ = kChunkLimit, compCap_ = 64;
+    size_t chunkBytes_ = 64;
+    std::atomic<uint64_t> resident_{0};
+    // the framing's state: the chunk framed last, its size, where its unfinished line begins and whether that is all it holds; the
+    // input offset of the next chunk's first byte; the lines checked so far
+    Held *prev_ = nullptr;
+    uint64_t prevNext_ = 0, prevSize_ = 0, base_ = 0, linesBefore_ = 0;
+    bool prevWhole_ = false;
+};
+
+inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::string &file, const std::string &outDir,
+                                              const SequenceSelector *selector, std::ostream &log, size_t chunkBytesArg,
+                                              std::vector<AssemblyRouteDeviceStats> *perDevice = nullptr) {
+    using Clock = std::chrono::steady_clock;
+    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+    const auto tBegin = Clock::now();
+    const bool filtered = selector && selector->active();
+    if (filtered) detail::refuseGfa2Name(file);
+    if (teloscope.deviceCount() > 1 && !teloscope.deviceRoutesUseEveryContext())
+        throw std::runtime_error("annotateGfaDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
+                                 " (the graph's text lies in one device's memory); one made with DeviceRoutes::EveryContext has the route "
+                                 "deal its chunks to all of them");
+    double msGraph = 0;
+
+    GfaChunkSteps steps(teloscope, file, filtered, chunkBytesArg);
+    std::unique_ptr<ChunkRing<GfaChunkSteps>> ring;
+    if (teloscope.deviceCount() > 1) {
+        ring.reset(new ChunkRing<GfaChunkSteps>(teloscope.deviceCount(), 0, steps));
+        ring->run();
+    } else {
+        steps.runInPlace();
+    }
+    using Walked = GfaChunkSteps::Walked;
+    using Piece = GfaChunkSteps::Piece;
+    const std::vector<Walked> &walked = steps.walked;
+    const std::vector<Piece> &pieces = steps.pieces;
+    const uint64_t total = steps.total;
+    const int offence = steps.offence;
+    const char offenceType = steps.offenceType;
+    const uint64_t offenceLine = steps.offenceLine;
+    ChunkFeed &feed = *steps.feed;
+    auto fail = [&](const char *what) { return detail::deviceError(teloscope.context(0), what); };
 
     if (offence) throw detail::filteredGfaError(offence, offenceType, offenceLine);
 
@@ -689,7 +879,8 @@ inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::s
         for (const Walked &w : walked)
             if (w.foreign.found) {
                 std::string type(w.foreign.len, '\0');
-                if (w.foreign.len && ts_bam_chunk_read(w.chunk, w.foreign.off, w.foreign.len, &type[0]) != TS_OK) throw fail("cannot read the chunk");
+                if (w.foreign.len && ts_bam_chunk_read(w.chunk, w.foreign.off, w.foreign.len, &type[0]) != TS_OK)
+                    throw detail::deviceError(teloscope.context(w.context), "cannot read the chunk");
                 throw std::runtime_error("GFA 2 record type '" + type + "' in '" + file +
                                          "' is not supported: only H and S records of a GFA 2 graph are read.");
             }
@@ -697,6 +888,8 @@ inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::s
         if (headerIsV2[i]) g.edits.push_back({headers[i].first, headers[i].second, "H\tVN:Z:1.2"});
     g.segments.reserve(nseg);
     g.index.reserve(nseg);
+    std::vector<uint32_t> segContext;                           // whose memory each segment's line lies in (a line lies in one chunk)
+    segContext.reserve(nseg);
     for (const Walked &w : walked) {
         const char *dev = static_cast<const char *>(ts_chunk_data(w.chunk));
         for (const ts_gfa_segment &s : w.segs) {
@@ -712,6 +905,7 @@ inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::s
             if (!g.index.emplace(seg.name, static_cast<uint32_t>(g.segments.size())).second)
                 throw std::runtime_error("segment '" + seg.name + "' is defined twice in '" + file + "'.");
             g.segments.push_back(std::move(seg));
+            segContext.push_back(static_cast<uint32_t>(w.context));
         }
     }
     std::sort(g.edits.begin(), g.edits.end(), [](const GfaEdit &a, const GfaEdit &b) { return a.off < b.off; });
@@ -726,8 +920,14 @@ inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::s
     st.parseMs = since(tBegin);
     const auto t1 = Clock::now();
     const std::vector<GfaEnd> jobs = gfaTerminalJobs(g, filtered ? &sel.keep : nullptr);
-    const GfaEnds e = gfaScanEnds(teloscope, g, jobs, log, true);
+    std::vector<uint64_t> scannedBases;
+    std::vector<double> scanMs;
+    const GfaEnds e = gfaScanEnds(teloscope, g, jobs, log, true, &segContext, &scannedBases, &scanMs);
     const auto t2 = Clock::now();
+    for (size_t w = 0; w < steps.workers.size(); ++w) {
+        steps.workers[w]->st.basesScanned = w < scannedBases.size() ? scannedBases[w] : 0;
+        steps.workers[w]->st.msScan = w < scanMs.size() ? scanMs[w] : 0;          // (its own call; the contexts scan side by side)
+    }
 
     // the input's bytes: host pieces as they lie, chunk pieces read back through a bounce buffer
     GfaInputBytes input;
@@ -767,23 +967,28 @@ inline GfaAnnotateStats annotateGfaDeviceWith(Teloscope &teloscope, const std::s
     st.noSeq = e.noSeq;
     st.scanMs = std::chrono::duration<double, std::milli>(t2 - t1).count();
     st.writeMs = std::chrono::duration<double, std::milli>(t3 - t2).count();
+    double msUpload = 0, msIndex = 0;
+    for (const auto &k : steps.workers) { msUpload += k->st.msFill + k->st.msStage + k->st.msCommit; msIndex += k->st.msIndex; }
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "annotateGfaDevice: upload%s %.0f ms, index %.0f ms, graph (host) %.0f ms, scan %.0f ms, write %.0f ms\n",
                      feed.deviceInflate() ? " + inflate + CRC" : "", msUpload, msIndex, msGraph, st.scanMs, st.writeMs);
+    assemblyRouteFigures("annotateGfaDevice", steps.workers, ring.get(), perDevice);
     return st;
 }
 }  // namespace detail
 
 inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::string &file, const std::string &outDir,
-                                          std::ostream &log = std::cerr, size_t chunkBytes = size_t(256) << 20) {
-    return detail::annotateGfaDeviceWith(teloscope, file, outDir, nullptr, log, chunkBytes);
+                                          std::ostream &log = std::cerr, size_t chunkBytes = size_t(256) << 20,
+                                          std::vector<AssemblyRouteDeviceStats> *perDevice = nullptr) {
+    return detail::annotateGfaDeviceWith(teloscope, file, outDir, nullptr, log, chunkBytes, perDevice);
 }
 
 // the same with assembly record filters (see above)
 inline GfaAnnotateStats annotateGfaDevice(Teloscope &teloscope, const std::string &file, const std::string &outDir,
                                           const SequenceSelector &selector, std::ostream &log = std::cerr,
-                                          size_t chunkBytes = size_t(256) << 20) {
-    return detail::annotateGfaDeviceWith(teloscope, file, outDir, &selector, log, chunkBytes);
+                                          size_t chunkBytes = size_t(256) << 20,
+                                          std::vector<AssemblyRouteDeviceStats> *perDevice = nullptr) {
+    return detail::annotateGfaDeviceWith(teloscope, file, outDir, &selector, log, chunkBytes, perDevice);
 }
 
 }  // namespace teloscope_mi355x

@@ -386,20 +386,28 @@ inline std::vector<PathComponents> splitPaths(const std::vector<RecordView> &rec
 
 // walkPath for every record, with one batched scan (result order = record order; seqPos = seqPosBase + index, or
 // (*seqPositions)[index] when given: the records' indices in the whole input, which a record filter leaves with gaps).
-// trackText: when given — and the object has one device — the windows stay on the device: *trackText receives the lines of the
+// context: the context the one batched scan runs on (Teloscope::context(i)).  -1, the default: host records go over all of the
+// object's contexts (scanSegmentsWriterView) when it has several, and records with a device form, whose address belongs to one
+// context, are scanned on the first.  A caller that produced the bases on context i passes i.
+// trackText: when given — and the scan runs on one context — the windows stay on the device: *trackText receives the lines of the
 // five window tracks of these records in order (Teloscope::scanSegmentsTrackText), every path's `windows` stays empty and its
 // windowCount says how many there were; under -m it receives the lines of the two match files as well
 // (Teloscope::scanSegmentsText), the paths' match vectors stay empty and canonicalMatchCount comes from the counts: no match
 // record and no base is read on the host.  Otherwise it is left empty and everything is as without it.
 inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::vector<RecordView> &records, size_t seqPosBase = 0,
                                              const std::vector<PathComponents> *precomputed = nullptr,
-                                             const std::vector<size_t> *seqPositions = nullptr, TrackText *trackText = nullptr) {
+                                             const std::vector<size_t> *seqPositions = nullptr, TrackText *trackText = nullptr,
+                                             int context = -1) {
     const UserInputTeloscope &ui = teloscope.input();
+    bool deviceForm = false;
+    for (const RecordView &rv : records) deviceForm = deviceForm || rv.device != nullptr;
+    const bool multi = teloscope.deviceCount() > 1 && context < 0 && !deviceForm;    // all contexts: host segments only
+    const size_t on = context < 0 ? 0 : static_cast<size_t>(context);
     // (the streaming reader finds the N-runs while the freshly joined bases are still in cache)
     const std::vector<PathComponents> split = precomputed ? std::vector<PathComponents>() : splitPaths(records);
     const std::vector<PathComponents> &comps = precomputed ? *precomputed : split;
     std::vector<Teloscope::Segment> batch;
-    const bool textRoute = trackText && teloscope.deviceCount() == 1;
+    const bool textRoute = trackText && !multi;
     if (trackText && !textRoute) trackText->clear();            // (the text route's call replaces the text and reuses its arrays)
     std::vector<const char *> batchNames;                        // (text route: every segment's record name)
     // text records that N-runs cut into several segments: every segment gets its own piece list (reserved up front, so
@@ -467,12 +475,12 @@ inline std::vector<PathData> walkRecordViews(Teloscope &teloscope, const std::ve
     std::vector<ts_segment_counts> counts;
     // (with -m: only the two match vectors the writers read are materialised; block calling has happened on the device)
     // (several devices: the batch is cut into one shard per device, and what comes back is the writers' view either way)
-    std::vector<SegmentData> scanned = textRoute ? (ui.outMatches ? teloscope.scanSegmentsText(batch, batchNames, counts, *trackText)
-                                                                  : teloscope.scanSegmentsTrackText(batch, batchNames, counts, *trackText))
-                                     : teloscope.deviceCount() > 1 ? teloscope.scanSegmentsWriterView(batch, counts)
-                                     : ui.outMatches ? teloscope.scanSegments(batch, true)
-                                                     : teloscope.scanSegmentsNoMatches(batch, counts);
-    const bool haveCounts = teloscope.deviceCount() > 1 || !ui.outMatches || textRoute;
+    std::vector<SegmentData> scanned = textRoute ? (ui.outMatches ? teloscope.scanSegmentsText(batch, batchNames, counts, *trackText, on)
+                                                                  : teloscope.scanSegmentsTrackText(batch, batchNames, counts, *trackText, on))
+                                     : multi ? teloscope.scanSegmentsWriterView(batch, counts)
+                                     : ui.outMatches ? teloscope.scanSegments(batch, true, on)
+                                                     : teloscope.scanSegmentsNoMatches(batch, counts, on);
+    const bool haveCounts = multi || !ui.outMatches || textRoute;
 
     std::vector<PathData> paths(records.size());
     size_t si = 0;
@@ -1661,12 +1669,14 @@ public:
         f.host = f.block.data();
         f.atEnd = streamDone_;
     }
-    void stage(ts_ctx *ctx, ts_chunk *chunk, const Fill &f) const {
+    // (noRoom: the exception of a failed upload in place of Options::noRoom's, for a route whose message names the context)
+    void stage(ts_ctx *ctx, ts_chunk *chunk, const Fill &f, const std::function<std::runtime_error(const char *)> *noRoom = nullptr) const {
         for (const Fill::Call &c : f.calls) {
             if (ts_chunk_stage_inflate(chunk, in_.data + c.at, c.used, c.descs.data(), c.descs.size(), nullptr) != TS_OK) throw deviceError(ctx, "BGZF inflate failed");
             membersVerdict(ctx, chunk);
         }
-        if (f.calls.empty() && ts_chunk_stage_upload(chunk, f.host, f.n, nullptr) != TS_OK) throw opt_.noRoom ? opt_.noRoom(opt_.uploadFailed) : deviceError(ctx, opt_.uploadFailed);
+        if (f.calls.empty() && ts_chunk_stage_upload(chunk, f.host, f.n, nullptr) != TS_OK)
+            throw noRoom ? (*noRoom)(opt_.uploadFailed) : opt_.noRoom ? opt_.noRoom(opt_.uploadFailed) : deviceError(ctx, opt_.uploadFailed);
     }
 
 private:
@@ -1858,7 +1868,8 @@ struct ChunkWorker {
 // A dealt chunk comes together: the unfinished record of the chunk framed before goes to the front of `to`, the staged bytes
 // behind it.  `from` is another context's chunk (ts_chunk_carry_over: on one GPU, between peers, or through the host), `to`
 // itself (the chunk's own tail moves to its front), or nothing (the first chunk of the input).
-inline void ringCommit(ChunkWorker &to, const ChunkWorker *from, uint64_t carryFrom) {
+template <typename To, typename From>
+inline void ringCommit(To &to, const From *from, uint64_t carryFrom) {
     const Clock::time_point t0 = Clock::now();
     if (from == &to) { if (ts_chunk_upload(to.chunk, nullptr, 0, carryFrom, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot carry a record into the next device chunk"); }
     else if (from && ts_chunk_carry_over(to.chunk, from->chunk, carryFrom, nullptr) != TS_OK) throw deviceError(to.ctx, "cannot carry a record into the next device chunk");
@@ -3196,12 +3207,23 @@ class FastaChunkStage {
     // measurement).  With -m the lines of the two match files are formatted there as well (ts_scan_segments_text), from the match
     // records and the joined bases where they lie: no base is read back and no match record downloaded.
     const bool useTrackText_;
-    TrackText trackText_;
     std::unique_ptr<BedWriter> writer_;
-    std::vector<char> hostBases_;
-    std::vector<ts_fasta_run> runs_ = std::vector<ts_fasta_run>(4096);
-    std::vector<uint64_t> offsets_;
     ScanFastaTimes T_;
+public:
+    // What the judging of a chunk's records needs and leaves, one per context that judges (judge() fills it, any number of them
+    // at once; emit() hands it to the writer, one at a time in chunk order): the host view of the bases, the runs, the window and
+    // match text, the paths, and the chunk's share of the figures.
+    struct Judged {
+        TrackText trackText;
+        std::vector<char> hostBases;
+        std::vector<ts_fasta_run> runs = std::vector<ts_fasta_run>(4096);
+        std::vector<uint64_t> offsets;
+        std::vector<PathData> paths;
+        uint64_t libraryBases = 0, basesReadBack = 0;
+        double msJoin = 0, msScan = 0;
+    };
+private:
+    Judged own_;                                                // add()'s
 public:
     double msUpload = 0, msIndex = 0, msJoin = 0, msScan = 0, msWrite = 0;      // (the first two: the caller's stages)
     FastaChunkStage(Teloscope &teloscope, bool deviceTracks) : teloscope_(teloscope), useTrackText_(deviceTracks) {}
@@ -3214,41 +3236,56 @@ public:
     template <class Header>
     void add(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, bool atEnd, const Header &header, size_t firstRecord,
              const std::vector<size_t> *seqPos) {
+        judge(own_, 0, chunk, recs, n, atEnd, header, firstRecord, seqPos);
+        emit(own_);
+    }
+
+    // add() up to the writer, on context `context` of the Teloscope, which is the chunk's: everything lands in `j`, and nothing
+    // of the stage itself is written, so that several contexts may judge a chunk each at the same time.
+    template <class Header>
+    void judge(Judged &j, size_t context, ts_chunk *chunk, const ts_fasta_record *recs, size_t n, bool atEnd, const Header &header,
+               size_t firstRecord, const std::vector<size_t> *seqPos) const {
         const UserInputTeloscope &ui = teloscope_.input();
-        auto fail = [&](const char *what) { return deviceError(teloscope_.context(), what); };
+        auto fail = [&](const char *what) { return deviceError(teloscope_.context(context), what); };
         auto t0 = Clock::now();
         const void *dBases = nullptr;
         uint64_t total = 0, nRuns = 0;
-        offsets_.resize(n);
-        if (ts_fasta_chunk_join(chunk, recs, n, atEnd ? 1 : 0, &dBases, offsets_.data(), &total, &nRuns, nullptr) != TS_OK) throw fail("FASTA join failed");
-        if (nRuns > runs_.size()) runs_.resize(static_cast<size_t>(nRuns));
-        if (ts_fasta_chunk_runs(chunk, runs_.data(), runs_.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
+        j.libraryBases = j.basesReadBack = 0;
+        j.offsets.resize(n);
+        if (ts_fasta_chunk_join(chunk, recs, n, atEnd ? 1 : 0, &dBases, j.offsets.data(), &total, &nRuns, nullptr) != TS_OK) throw fail("FASTA join failed");
+        if (nRuns > j.runs.size()) j.runs.resize(static_cast<size_t>(nRuns));
+        if (ts_fasta_chunk_runs(chunk, j.runs.data(), j.runs.size(), &nRuns) != TS_OK) throw fail("reading the runs failed");
         const bool hostView = ui.outMatches && !ui.ultraFastMode && !useTrackText_;
         if (hostView) {                                         // matchSeq is cut out of the bases: one copy per chunk
-            hostBases_.resize(static_cast<size_t>(total) + 1);
-            if (ts_fasta_chunk_bases(chunk, 0, total, hostBases_.data()) != TS_OK) throw fail("reading the joined bases failed");
-            T_.bases_read_back += total;
+            j.hostBases.resize(static_cast<size_t>(total) + 1);
+            if (ts_fasta_chunk_bases(chunk, 0, total, j.hostBases.data()) != TS_OK) throw fail("reading the joined bases failed");
+            j.basesReadBack = total;
         }
-        msJoin += since(t0);
+        j.msJoin = since(t0);
         std::vector<PathComponents> comps(n);
         std::vector<RecordView> views(n);
         for (uint64_t r = 0; r < nRuns; ++r) {
-            const ts_fasta_run &run = runs_[static_cast<size_t>(r)];
+            const ts_fasta_run &run = j.runs[static_cast<size_t>(r)];
             if (run.record >= n) throw std::runtime_error("FASTA runs: a run of a record that was not joined");
             if (run.is_gap) comps[run.record].gaps.push_back(GapInfo{run.start, run.len});
-            else { comps[run.record].segments.emplace_back(run.start, run.len); T_.library_bases += run.len; }
+            else { comps[run.record].segments.emplace_back(run.start, run.len); j.libraryBases += run.len; }
         }
         for (size_t i = 0; i < n; ++i)
-            views[i] = RecordView{header(i), hostView ? hostBases_.data() + offsets_[i] : nullptr, recs[i].n_bases, nullptr, 0, nullptr,
-                                  static_cast<const char *>(dBases) + offsets_[i]};
-        TrackText *text = useTrackText_ ? &trackText_ : nullptr;
+            views[i] = RecordView{header(i), hostView ? j.hostBases.data() + j.offsets[i] : nullptr, recs[i].n_bases, nullptr, 0, nullptr,
+                                  static_cast<const char *>(dBases) + j.offsets[i]};
         t0 = Clock::now();
-        std::vector<PathData> paths = walkRecordViews(teloscope_, views, firstRecord, &comps, seqPos, text);
-        msScan += since(t0);
-        t0 = Clock::now();
-        writer_->add(paths, text);
-        for (const PathData &pd : paths) { T_.bases += pd.pathSize; T_.windows += pd.nWindows(); }
+        j.paths = walkRecordViews(teloscope_, views, firstRecord, &comps, seqPos, useTrackText_ ? &j.trackText : nullptr, static_cast<int>(context));
+        j.msScan = since(t0);
+    }
+    // ... and the writer's part, in the order of the input: the judged paths written, the deterministic counters moved on
+    void emit(Judged &j) {
+        const auto t0 = Clock::now();
+        writer_->add(j.paths, useTrackText_ ? &j.trackText : nullptr);
+        for (const PathData &pd : j.paths) { T_.bases += pd.pathSize; T_.windows += pd.nWindows(); }
+        T_.library_bases += j.libraryBases; T_.bases_read_back += j.basesReadBack;
+        msJoin += j.msJoin; msScan += j.msScan;
         ++T_.groups;
+        j.paths.clear();
         msWrite += since(t0);
     }
 
@@ -3411,6 +3448,198 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
 
 }  // namespace detail
 
+// One context's share of an assembly device route (scanFastaToFilesDevice; annotateGfaDevice in teloscope_mi355x_gfa.hpp): the
+// HIP ordinal it was made on, chunks it took, records framed in them (FASTA records; GFA segments), bases it scanned (of the
+// segments handed to the library), uncompressed bytes it received, and the milliseconds its thread spent filling a chunk in
+// place (one context: upload or inflate straight behind the carry), staging a dealt chunk's bytes (several contexts), waiting
+// for the chunk before its own to be framed (dealt chunks only: the serial section as this context sees it), placing the carry
+// and committing the staged bytes behind it (dealt chunks only), indexing (the walk, and the GFA check), joining and scanning.
+struct AssemblyRouteDeviceStats {
+    int device = -1;
+    uint64_t chunks = 0, records = 0, basesScanned = 0, bytesReceived = 0;
+    double msFill = 0, msStage = 0, msFrameWait = 0, msCommit = 0, msIndex = 0, msJoin = 0, msScan = 0;
+};
+
+namespace detail {
+
+// A route's per-context figures, to perDevice and, under TS_TIMING, to stderr: one line per context, each beginning with `route`.
+// `ring` is the ring that dealt the chunks, or nothing (every chunk came in place: no context waited for another).
+template <typename Worker, typename Ring>
+inline void assemblyRouteFigures(const char *route, const std::vector<std::unique_ptr<Worker>> &workers, const Ring *ring,
+                                 std::vector<AssemblyRouteDeviceStats> *perDevice) {
+    if (perDevice) perDevice->clear();
+    for (size_t w = 0; w < workers.size(); ++w) {
+        AssemblyRouteDeviceStats s = workers[w]->st;
+        if (ring) s.msFrameWait = ring->frameWaitMs(w);
+        if (perDevice) perDevice->push_back(s);
+        if (std::getenv("TS_TIMING"))
+            std::fprintf(stderr, "%s: context %zu of %zu (device %d): %llu chunks, %llu records, %llu bases scanned, %llu bytes; fill %.0f ms, stage %.0f ms, "
+                         "frame wait %.1f ms, carry + commit %.1f ms, index %.1f ms, join %.0f ms, scan %.0f ms\n", route, w, workers.size(), s.device,
+                         (unsigned long long)s.chunks, (unsigned long long)s.records, (unsigned long long)s.basesScanned, (unsigned long long)s.bytesReceived,
+                         s.msFill, s.msStage, s.msFrameWait, s.msCommit, s.msIndex, s.msJoin, s.msScan);
+    }
+}
+
+// scanFastaToFilesDevice's stages (the unfiltered form), for a Teloscope of any number of contexts; the two ways a chunk's bytes
+// come in are the read routes' (above): in place on one context, dealt by detail::ChunkRing on several.  Everything behind the
+// fill exists once: ts_fasta_chunk_walk frames the records, the bytes behind the last complete one go in front of the next chunk,
+// FastaChunkStage::judge joins and scans on the chunk's own context, FastaChunkStage::emit writes in chunk order.  A chunk that
+// holds nothing but one unfinished record passes all of its contents on, and the next fill brings chunkBytes more, in place (up
+// to chunkLimit) and dealt alike: the reader of dealt chunks runs ahead of the framing and cannot know that a chunk will grow, so
+// growth by a fixed step is the one rule both can follow, and with it the chunks hold the same bytes, and BedWriter gets the
+// same groups, for every number of contexts (ScanFastaTimes::groups and bases_read_back do not depend on it).  One exception:
+// with a carry of more than chunkLimit - chunkBytes bytes the fill in place stops at chunkLimit, where a dealt chunk brings its
+// chunkBytes regardless, so behind a record that comes that close to the limit the cuts, and with them `groups`, may differ; the
+// files do not.  The price of the fixed step: a record of r chunks is walked r times (r <= chunkLimit / chunkBytes, 16 at the
+// defaults), where growth by doubling walked it log r times.  Either way a
+// record that is not complete within chunkLimit bytes of text is refused by name, with the same words.
+class FastaChunkSteps {
+public:
+    struct Worker {
+        size_t index = 0;
+        ts_ctx *ctx = nullptr;
+        ts_chunk *chunk = nullptr;
+        ChunkFeed::Fill fill;                                   // a dealt chunk's new bytes
+        std::vector<ts_fasta_record> recs = std::vector<ts_fasta_record>(4096);
+        std::vector<char> names = std::vector<char>(size_t(1) << 16);
+        std::vector<std::string> headers;
+        uint64_t n = 0;                                         // complete records of the chunk
+        size_t firstRecord = 0;                                 // the first one's index in the input: the report's `pos` column
+        bool atEnd = false;
+        FastaChunkStage::Judged judged;
+        AssemblyRouteDeviceStats st;
+        Worker() = default;
+        Worker(const Worker &) = delete;
+        Worker &operator=(const Worker &) = delete;
+        ~Worker() { ts_bam_chunk_destroy(chunk); }
+    };
+    std::vector<std::unique_ptr<Worker>> workers;
+
+    FastaChunkSteps(Teloscope &teloscope, ChunkFeed &feed, FastaChunkStage &stage, size_t chunkBytes, uint64_t chunkLimit)
+        : feed_(feed), stage_(stage), chunkBytes_(chunkBytes), chunkLimit_(chunkLimit) {
+        const uint64_t compCap = feed.compCap(chunkBytes);
+        for (size_t w = 0; w < teloscope.deviceCount(); ++w) {
+            workers.emplace_back(new Worker());
+            Worker &k = *workers.back();
+            k.index = w;
+            k.ctx = teloscope.context(w);
+            k.st.device = teloscope.deviceOrdinal(w);
+            k.chunk = ts_bam_chunk_create(k.ctx, compCap, chunkBytes);
+            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
+        }
+    }
+
+    // The whole input as in-place chunks of context 0, on the caller's thread: any source of the feed, ChunkFeed::Gzip included
+    void runInPlace() {
+        Worker &k = *workers[0];
+        uint64_t held = 0, pos = 0;                             // bytes in the chunk; the first one not consumed yet
+        for (bool atEnd = false; !atEnd;) {
+            const uint64_t carry = held - pos;
+            // a chunk that held no whole record (a record larger than it) takes chunkBytes more, up to what a chunk may hold
+            if (pos == 0 && carry >= chunkLimit_) throw doesNotFit(k, 0, held);
+            const size_t want = static_cast<size_t>(std::min<uint64_t>(chunkBytes_, chunkLimit_ - carry));
+            const Clock::time_point t0 = Clock::now();
+            atEnd = feed_.fill(k.chunk, pos, want);
+            k.st.msFill += since(t0);
+            held = ts_bam_chunk_size(k.chunk); pos = 0;
+            ++k.st.chunks; k.st.bytesReceived += held - carry;
+            k.atEnd = atEnd;
+            if (held == 0) continue;
+            pos = walk(k);
+            if (k.n == 0) continue;
+            judge(0, 0);
+            emit(0, 0);
+        }
+    }
+
+    // the ring's steps: a dealt chunk
+    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
+    RingTake take(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        feed_.take(chunkBytes_, k.fill);                        // (a Stream is read here: the reader's time, in nobody's figures)
+        return k.fill.atEnd ? RingTake::Last : RingTake::More;
+    }
+    void stage(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        feed_.stage(k.ctx, k.chunk, k.fill);
+        k.st.msStage += since(t0);
+        ++k.st.chunks; k.st.bytesReceived += k.fill.n;
+    }
+    // the serial section: the unfinished record of the chunk before in front, the staged bytes behind it, the records framed
+    bool frame(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const uint64_t carry = prevSize_ - prevNext_;
+        // (refused before the carry is copied, so that a copy of that size cannot fail first; the name is read where it lies)
+        if (prev_ && carry >= chunkLimit_) throw doesNotFit(*prev_, prevNext_, carry);
+        const Clock::time_point t0 = Clock::now();
+        if (prev_ && ts_chunk_carry_over(k.chunk, prev_->chunk, prevNext_, nullptr) != TS_OK) throw deviceError(k.ctx, "cannot carry a record into the next device chunk");
+        if (ts_chunk_commit(k.chunk, nullptr) != TS_OK) throw deviceError(k.ctx, "cannot grow the device chunk");
+        k.st.msCommit += since(t0);
+        k.atEnd = k.fill.atEnd;
+        k.n = 0;
+        prev_ = &k; prevNext_ = 0; prevSize_ = ts_bam_chunk_size(k.chunk);
+        if (prevSize_ == 0) return true;
+        prevNext_ = walk(k);
+        // (a chunk filled in place never holds chunkLimit bytes or more of one record: the same records are refused here)
+        for (uint64_t i = 0; i < k.n; ++i)
+            if (k.recs[i].text_len > chunkLimit_ || (k.recs[i].text_len == chunkLimit_ && !(k.atEnd && i + 1 == k.n)))
+                throw doesNotFit(k, k.recs[i].off, k.recs[i].text_len);
+        return true;
+    }
+    void judge(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        if (k.n == 0) return;
+        const size_t n = static_cast<size_t>(k.n);
+        k.headers.resize(n);
+        stage_.judge(k.judged, w, k.chunk, k.recs.data(), n, k.atEnd, [&](size_t i) {
+            k.headers[i] = fastaHeaderWord(k.names.data() + k.recs[i].name_at, k.names.data() + k.recs[i].name_at + k.recs[i].name_len);
+            return &k.headers[i];
+        }, k.firstRecord, nullptr);
+        k.st.msJoin += k.judged.msJoin; k.st.msScan += k.judged.msScan;
+        k.st.basesScanned += k.judged.libraryBases;
+    }
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        if (k.n) stage_.emit(k.judged);
+    }
+
+private:
+    // The records of a chunk that has its bytes; the running record count moves on.  -> the first byte behind the last complete one
+    uint64_t walk(Worker &k) {
+        const Clock::time_point t0 = Clock::now();
+        uint64_t next = 0;
+        walkFastaChunk(k.ctx, k.chunk, k.atEnd, k.recs, k.names, k.n, next);
+        const double ms = since(t0);
+        k.st.msIndex += ms; stage_.msIndex += ms;
+        k.firstRecord = recordsDone_;
+        recordsDone_ += static_cast<size_t>(k.n);
+        k.st.records += k.n;
+        return next;
+    }
+    // the refusal of the record (or of the line in front of the first record) that begins at `off` of k's chunk, `len` bytes of it there
+    std::runtime_error doesNotFit(const Worker &k, uint64_t off, uint64_t len) const {
+        char head[257] = {0};
+        const uint64_t hn = std::min<uint64_t>(len, 256);
+        if (hn && ts_bam_chunk_read(k.chunk, off, hn, head) != TS_OK) return deviceError(k.ctx, "cannot read the chunk");
+        const char *nl = static_cast<const char *>(std::memchr(head, '\n', static_cast<size_t>(hn)));
+        const std::string name = head[0] == '>' ? fastaHeaderWord(head + 1, nl ? nl : head + hn) : std::string();
+        return std::runtime_error(head[0] == '>' ? "FASTA record '" + name + "' does not fit a device chunk (" + std::to_string(chunkLimit_) + " bytes of text); use the host route"
+                                                 : "a line of more than " + std::to_string(chunkLimit_) + " bytes in front of the first FASTA record does not fit a device chunk");
+    }
+
+    ChunkFeed &feed_;
+    FastaChunkStage &stage_;
+    size_t chunkBytes_;
+    uint64_t chunkLimit_;
+    // the framing's state: the chunk framed last, its size and where its unfinished record begins; the records framed so far
+    const Worker *prev_ = nullptr;
+    uint64_t prevNext_ = 0, prevSize_ = 0;
+    size_t recordsDone_ = 0;
+};
+
+}  // namespace detail
+
 // The device route of the assembly scan (same files, console report and AssemblySummary as scanFastaToFiles, which stays the
 // default): the FASTA text exists in HBM one chunk of ~chunkBytes bytes at a time, and without -m the host reads none of it.
 // The text gets there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, or a stream through zlib
@@ -3431,9 +3660,22 @@ inline AssemblySummary scanFastaToFilesDeviceFiltered(Teloscope &teloscope, cons
 // writes the kept records chunk by chunk (seqPos = their input indices); an unselected record is never joined or scanned, and
 // the summary's filter counts are this selection's.  The whole text must fit the device's free memory: one that does not (or
 // exceeds residentLimit, a test hook like chunkLimit: 0 = no limit of its own) is refused before any output exists.
-// Limits: ONE device (a Teloscope over several throws); a record
-// whose text does not fit a chunk of chunkLimit bytes (4 GiB - 2, what the walk takes) is refused by name, never cut; the
-// stages run one after the other.  chunkLimit is a test hook (the refusal cannot be reached otherwise without 4 GiB of text):
+// Several contexts (a Teloscope made over a device list with DeviceRoutes::EveryContext — without it such an object is refused as
+// before, "runs on one device"; the unfiltered form): detail::ChunkRing deals chunk k to context k mod N,
+// a thread per context.  The new bytes are staged beside the chunk (ts_chunk_stage_upload, ts_chunk_stage_inflate) while the
+// chunks before it are framed; in the serial section the unfinished record of chunk k - 1 moves in front (ts_chunk_carry_over,
+// across contexts), the staged bytes are committed behind it and the records are framed, which gives the chunk its first record
+// number; join, runs, the host view of the bases and the scan then run on the chunk's own context, any number of chunks at once,
+// and BedWriter takes the chunks in order.  The stages are detail::FastaChunkSteps for every count: one context fills every
+// chunk in place, on the caller's thread and with no staging region, exactly as before.  Files, console report, summary, the
+// deterministic fields of ScanFastaTimes and the exceptions do not depend on the number of contexts
+// (tests/test_gpu_assembly_routes_multi.py); plain gzip goes through zlib there, because the opt-in device gzip source
+// (ChunkFeed::Gzip) is bound to one context.  perDevice, where given, receives one entry per context; TS_TIMING=1 prints a line
+// per context beside the line of totals.
+// Limits: the FILTERED form runs on ONE device (its two phases keep the whole text resident on it: a Teloscope over several
+// throws, before any output file exists); a record
+// whose text does not fit a chunk of chunkLimit bytes (4 GiB - 2, what the walk takes) is refused by name, never cut; on one
+// context the stages run one after the other.  chunkLimit is a test hook (the refusal cannot be reached otherwise without 4 GiB of text):
 // callers leave it alone.  What a maintainer of the reference would call in place of its FASTA load and per-path jobs
 // (src/input.cpp:655-733).
 inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::string &fastaFile, const std::string &outBase,
@@ -3441,72 +3683,44 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
                                               size_t chunkBytesArg = size_t(256) << 20, ScanFastaTimes *times = nullptr,
                                               uint64_t chunkLimit = 0xfffffffeull, bool deviceTracks = false,
                                               const SequenceSelector *selector = nullptr, std::ostream &log = std::cerr,
-                                              uint64_t residentLimit = 0) {
-    using Clock = std::chrono::steady_clock;
-    auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    if (teloscope.deviceCount() > 1)
+                                              uint64_t residentLimit = 0, std::vector<AssemblyRouteDeviceStats> *perDevice = nullptr) {
+    const bool dealt = teloscope.deviceCount() > 1;
+    if (dealt && !teloscope.deviceRoutesUseEveryContext())
         throw std::runtime_error("scanFastaToFilesDevice runs on one device: this Teloscope was made over " + std::to_string(teloscope.deviceCount()) +
-                                 " (the joined bases lie in one device's memory)");
-    if (selector && selector->active())
+                                 " (the joined bases lie in one device's memory); one made with DeviceRoutes::EveryContext has the route "
+                                 "deal its chunks to all of them");
+    if (selector && selector->active()) {
+        if (dealt)
+            throw std::runtime_error("scanFastaToFilesDevice with assembly record filters runs on one device: this Teloscope was made over " +
+                                     std::to_string(teloscope.deviceCount()) + " (the filtered device route keeps the whole text in one device's memory "
+                                     "until the selection is known; without a selector the route uses every context)");
+        if (perDevice) perDevice->clear();
         return detail::scanFastaToFilesDeviceFiltered(teloscope, fastaFile, outBase, console, manualCuration, chunkBytesArg, times, chunkLimit,
                                                       deviceTracks, *selector, log, residentLimit);
+    }
     detail::FastaChunkStage stage(teloscope, deviceTracks);
-    ts_ctx *ctx = teloscope.context();
-    auto fail = [&](const char *what) { return detail::deviceError(ctx, what); };
     detail::ChunkFeed::Options options;
     options.cannotOpen = "cannot open " + fastaFile;
     options.cannotRead = "read error in " + fastaFile;
     options.uploadFailed = "upload of the FASTA text failed";
-    detail::ChunkFeed feed(ctx, fastaFile, options);
+    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
+    detail::ChunkFeed feed(teloscope.context(0), fastaFile, options);
     const size_t chunkBytes = detail::clampFastaChunk(feed, chunkBytesArg, chunkLimit);
-    struct ChunkPtr { ts_chunk *p; ~ChunkPtr() { ts_bam_chunk_destroy(p); } } chunk{ts_bam_chunk_create(ctx, feed.compCap(chunkBytes), chunkBytes)};
-    if (!chunk.p) throw fail("cannot make the device chunk");
+    detail::FastaChunkSteps steps(teloscope, feed, stage, chunkBytes, chunkLimit);
 
     stage.open(outBase, console, manualCuration);
-    std::vector<ts_fasta_record> recs(4096);
-    std::vector<char> names(size_t(1) << 16);
-    std::vector<std::string> headers;
-    size_t recordsDone = 0;
-
-    uint64_t held = 0, pos = 0;                 // bytes in the chunk; the first one not consumed yet
-    bool atEnd = false;
-    while (!atEnd) {
-        const uint64_t carry = held - pos;
-        // a chunk that held no whole record (a record larger than it) takes as much again, up to what a chunk may hold
-        if (pos == 0 && carry >= chunkLimit) {
-            char head[257] = {0};
-            const uint64_t hn = std::min<uint64_t>(held, 256);
-            if (hn && ts_bam_chunk_read(chunk.p, 0, hn, head) != TS_OK) throw fail("cannot read the chunk");
-            const char *nl = static_cast<const char *>(std::memchr(head, '\n', static_cast<size_t>(hn)));
-            const std::string name = head[0] == '>' ? detail::fastaHeaderWord(head + 1, nl ? nl : head + hn) : std::string();
-            throw std::runtime_error(head[0] == '>' ? "FASTA record '" + name + "' does not fit a device chunk (" + std::to_string(chunkLimit) + " bytes of text); use the host route"
-                                                    : "a line of more than " + std::to_string(chunkLimit) + " bytes in front of the first FASTA record does not fit a device chunk");
-        }
-        const size_t want = static_cast<size_t>(std::min<uint64_t>(std::max<uint64_t>(chunkBytes, pos == 0 ? carry : 0), chunkLimit - carry));
-        Clock::time_point t0 = Clock::now();
-        atEnd = feed.fill(chunk.p, pos, want);
-        stage.msUpload += since(t0);
-        held = ts_bam_chunk_size(chunk.p); pos = 0;
-        if (held == 0) continue;
-
-        // records and names
-        t0 = Clock::now();
-        uint64_t n = 0, next = 0;
-        detail::walkFastaChunk(ctx, chunk.p, atEnd, recs, names, n, next);
-        stage.msIndex += since(t0);
-        pos = next;
-        if (n == 0) continue;
-
-        // bases, runs, scan and output
-        headers.resize(static_cast<size_t>(n));
-        stage.add(chunk.p, recs.data(), static_cast<size_t>(n), atEnd, [&](size_t i) {
-            headers[i] = detail::fastaHeaderWord(names.data() + recs[i].name_at, names.data() + recs[i].name_at + recs[i].name_len);
-            return &headers[i];
-        }, recordsDone, nullptr);
-        recordsDone += static_cast<size_t>(n);
+    std::unique_ptr<detail::ChunkRing<detail::FastaChunkSteps>> ring;
+    if (dealt) {
+        ring.reset(new detail::ChunkRing<detail::FastaChunkSteps>(teloscope.deviceCount(), 0, steps));
+        ring->run();
+    } else {
+        steps.runInPlace();
     }
+    for (const auto &k : steps.workers) stage.msUpload += k->st.msFill + k->st.msStage + k->st.msCommit;
     const UserInputTeloscope &ui = teloscope.input();
-    return stage.finish(ui.sequenceFilterActive, ui.filterInputCount, ui.filterSelectedCount, false, feed, times);
+    const AssemblySummary sum = stage.finish(ui.sequenceFilterActive, ui.filterInputCount, ui.filterSelectedCount, false, feed, times);
+    detail::assemblyRouteFigures("scanFastaToFilesDevice", steps.workers, ring.get(), perDevice);
+    return sum;
 }
 
 }  // namespace teloscope_mi355x
