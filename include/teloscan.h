@@ -938,6 +938,64 @@ int ts_fastq_chunk_stage(ts_chunk *chunk, const ts_fastq_record *recs, size_t n,
 int ts_fastq_chunk_gather(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, const void *d_pass, void *host_out,
                           uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
 
+/* ---- SAM text in the same resident chunk (include/teloscope_mi355x_io.hpp: samSubset, samSubsetDevice): the third front end of
+ *      the read filter, which the reference names and does not have (docs/algorithm.md: "BAM I/O is isolated from scoring so a
+ *      future SAM parser or optional CRAM backend can reuse the same filter").  The text reaches the chunk as for FASTQ
+ *      (ts_chunk_upload, ts_bam_chunk_inflate, the staging calls).  The rule is this project's own, and every route follows it:
+ *        - A line starts at byte 0 or right behind a '\n'.  Its content excludes the '\n' and one '\r' that is its last byte.
+ *          The input's last line may lack the '\n'.
+ *        - A line whose first byte is '@' is a header line.  Every other line, an empty one included, is an alignment line.
+ *        - Header lines are allowed only before the first alignment line of the input.  They are written out verbatim and in
+ *          order, line ends as read, before any record.
+ *        - An alignment line is cut at its tabs.  Field 10 is SEQ.  Field 11 is QUAL: from tab 10 to tab 11, or to the
+ *          content's end.
+ *        - Checks, in this order; the lowest offending line of the input wins:
+ *            TS_SAM_HEADER_AFTER_RECORD  a '@' line after an alignment line      "header line after the first alignment record"
+ *            TS_SAM_TOO_FEW_FIELDS       fewer than 10 tabs inside the line      "fewer than 11 fields"
+ *            TS_SAM_EMPTY_SEQ            SEQ has length 0                        "empty SEQ field"
+ *            TS_SAM_BAD_LENGTHS          SEQ is not "*", QUAL is not "*", and
+ *                                        their lengths differ                    "SEQ and QUAL length differ"
+ *          A route throws "SAM line <n>: <message>", n counted from 1 over the whole input, after the valid records before
+ *          the bad line have been judged and written.  An empty input is "SAM input is empty"; a header-only input is valid.
+ *        - SEQ exactly "*": the record has no sequence, is never kept, and is counted as missing (what bamSubset does for
+ *          l_seq == 0).  Every other record is judged on its SEQ bytes as they lie: the filter folds case, and '=', '.', 'N'
+ *          and the IUPAC letters are not ACGT.
+ *        - A passing record's line is written verbatim: content, its '\r' if any, and a '\n' (which the input's last line
+ *          gets when it lacked one).  Order is kept. */
+typedef struct ts_sam_record {
+    uint64_t off;                /* of the alignment line's first byte in the chunk */
+    uint32_t seq_at;             /* SEQ's first byte, relative to off */
+    uint32_t seq_len;            /* bytes of SEQ */
+    uint32_t size;               /* the content's length with a trailing '\r': what the gather copies in front of its '\n' */
+    uint32_t flags;              /* bit 0: SEQ is "*" */
+} ts_sam_record;
+#define TS_SAM_OK                  0
+#define TS_SAM_HEADER_AFTER_RECORD 1
+#define TS_SAM_TOO_FEW_FIELDS      2
+#define TS_SAM_EMPTY_SEQ           3
+#define TS_SAM_BAD_LENGTHS         4
+/* Lines and records of the whole chunk (at most 4 GiB - 1 bytes), which starts at a line's first byte.  in_header != 0: the
+ * input's header may still go on, and header lines are accepted up to the chunk's first alignment line; *n_header_lines counts
+ * them and *header_end is that alignment line's offset, or *next when every whole line is a header.  in_header == 0: both are
+ * 0 and any '@' line is TS_SAM_HEADER_AFTER_RECORD.  *n = alignment lines among the whole lines, the first min(*n, cap) of them
+ * to recs (host memory); when *n > cap the call answers TS_ERR_INVALID_ARG (call again with room for *n).  *n_lines = whole
+ * lines consumed, headers included.  *next = the first byte that was not consumed: the unfinished last line (the carry); with
+ * at_end != 0 the input ends with the chunk, its last line may lack the '\n', and *next = size.  *error != TS_SAM_OK: line
+ * *error_line of the chunk (counted from 0) at *error_off fails that check; *n and *n_lines then count what lies before it, and
+ * *next = *error_off.  Waits for the device. */
+int ts_sam_chunk_walk(ts_chunk *chunk, int at_end, int in_header, ts_sam_record *recs, uint64_t cap, uint64_t *n,
+                      uint64_t *n_header_lines, uint64_t *header_end, uint64_t *n_lines, uint64_t *next, int *error,
+                      uint64_t *error_line, uint64_t *error_off);
+/* ts_fastq_chunk_stage for SAM: the seq_len bytes of recs[i]'s SEQ (flags bit 0 clear, seq_len > 0 each) into segment i of
+ * `reads`, an unrestricted tips-only batch of n segments of seq_len bases on the chunk's context; bytes behind a read stay
+ * zero.  Asynchronous on `stream`. */
+int ts_sam_chunk_stage(ts_chunk *chunk, const ts_sam_record *recs, size_t n, ts_batch *reads, void *stream);
+/* ts_fastq_chunk_gather for SAM: the records whose pass byte (d_pass[i], device memory) is set, `size` bytes and a '\n'
+ * behind each, in input order, to host_out; *bytes, *n_passed and cap as for ts_bam_chunk_gather.  Ordered on `stream`; waits
+ * for it. */
+int ts_sam_chunk_gather(ts_chunk *chunk, const ts_sam_record *recs, size_t n, const void *d_pass, void *host_out,
+                        uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+
 /* ---- FASTA text in the same resident chunk: the device form of the assembly front end.  Replaces the reference's FASTA load
  *      (gfalibs' stream parser behind Input::read, src/input.cpp:655-716: header lines split off, body lines joined into one
  *      sequence per record) and the cut of a path into segments and gaps at its N-runs (the path components walkPath

@@ -2368,6 +2368,353 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
     return steps.res;
 }
 
+// ---------------------------------------------------------------------------------------------
+// --sam-subset: the read filter over SAM text, the front end the reference names and does not have (docs/algorithm.md: "BAM I/O
+// is isolated from scoring so a future SAM parser or optional CRAM backend can reuse the same filter").  The rule — lines, header
+// lines, fields, the four checks, "*" sequences and what is written — is stated once in include/teloscan.h above
+// ts_sam_chunk_walk; both routes below follow it, and their output bytes, statistics and exception texts are the same.
+struct SamSubsetStats { uint64_t headerLines = 0, totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0; };
+
+namespace detail {
+inline const char *samErrorText(int error) {
+    return error == TS_SAM_HEADER_AFTER_RECORD ? "header line after the first alignment record" : error == TS_SAM_TOO_FEW_FIELDS ? "fewer than 11 fields"
+         : error == TS_SAM_EMPTY_SEQ ? "empty SEQ field" : "SEQ and QUAL length differ";
+}
+inline std::runtime_error samLineError(uint64_t line, int error) {
+    return std::runtime_error("SAM line " + std::to_string(line) + ": " + samErrorText(error));
+}
+
+// The host form of ts_sam_chunk_walk, with its meanings: text[0, size) starts at a line's first byte; the whole lines' header
+// extent and record table, the carry, and the lowest line that fails a check, by a sequential pass over the lines.
+struct SamWalk {
+    std::vector<ts_sam_record> recs;
+    uint64_t headerLines = 0, headerEnd = 0, lines = 0, next = 0, errorLine = 0, errorOff = 0;
+    int error = TS_SAM_OK;
+};
+inline void samWalkHost(const char *text, size_t size, bool atEnd, bool inHeader, SamWalk &w) {
+    w.recs.clear();
+    w.headerLines = w.headerEnd = w.lines = w.next = w.errorLine = w.errorOff = 0;
+    w.error = TS_SAM_OK;
+    const char *p = text, *const end = text + size;
+    bool header = inHeader;
+    auto closeHeader = [&]() { if (header) { header = false; w.headerEnd = static_cast<uint64_t>(p - text); } };
+    while (p < end) {
+        const char *nl = static_cast<const char *>(std::memchr(p, '\n', static_cast<size_t>(end - p)));
+        if (!nl && !atEnd) break;                               // the unfinished last line: the carry
+        const char *lineEnd = nl ? nl : end, *next = nl ? nl + 1 : end;
+        const char *e = lineEnd > p && lineEnd[-1] == '\r' ? lineEnd - 1 : lineEnd;     // the content's end
+        int bad = TS_SAM_OK;
+        if (p < lineEnd && *p == '@') {
+            if (header) ++w.headerLines; else bad = TS_SAM_HEADER_AFTER_RECORD;
+        } else {
+            closeHeader();
+            const char *tab[11];
+            int tabs = 0;
+            for (const char *q = p; tabs < 11 && (q = static_cast<const char *>(std::memchr(q, '\t', static_cast<size_t>(e - q)))) != nullptr; ++q) tab[tabs++] = q;
+            ts_sam_record r{};
+            r.off = static_cast<uint64_t>(p - text); r.size = static_cast<uint32_t>(lineEnd - p);
+            if (tabs < 10) bad = TS_SAM_TOO_FEW_FIELDS;
+            else {
+                const char *seq = tab[8] + 1, *qual = tab[9] + 1, *qualEnd = tabs > 10 ? tab[10] : e;
+                const size_t seqLen = static_cast<size_t>(tab[9] - seq), qualLen = static_cast<size_t>(qualEnd - qual);
+                const bool seqStar = seqLen == 1 && *seq == '*', qualStar = qualLen == 1 && *qual == '*';
+                r.seq_at = static_cast<uint32_t>(seq - p); r.seq_len = static_cast<uint32_t>(seqLen); r.flags = seqStar ? 1u : 0u;
+                if (seqLen == 0) bad = TS_SAM_EMPTY_SEQ;
+                else if (!seqStar && !qualStar && seqLen != qualLen) bad = TS_SAM_BAD_LENGTHS;
+            }
+            if (bad == TS_SAM_OK) w.recs.push_back(r);
+        }
+        if (bad != TS_SAM_OK) {
+            w.error = bad; w.errorLine = w.lines; w.errorOff = static_cast<uint64_t>(p - text);
+            break;
+        }
+        ++w.lines;
+        p = next;
+    }
+    w.next = static_cast<uint64_t>(p - text);
+    if (header && inHeader) w.headerEnd = w.next;               // every whole line is a header line
+}
+}  // namespace detail
+
+// The host route: lines and fields are found on the host, a block of input at a time, and the sequences are judged in batches of
+// up to readsPerBatch through the filter, as fastqSubset does.  Input may be plain or gzip (both through zlib, which passes plain
+// bytes on as they are); `-` is stdin.
+inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
+    detail::FilterWarmUp warmUp(filter);
+    struct Source { gzFile gz = nullptr; ~Source() { if (gz) gzclose(gz); } } src;
+    if (inFile == "-") src.gz = gzdopen(0, "rb");
+    else {
+        const int fd = ::open(inFile.c_str(), O_RDONLY);
+        if (fd < 0) throw std::runtime_error("Stream not successful: " + inFile);
+        src.gz = gzdopen(fd, "rb");
+        if (!src.gz) ::close(fd);
+    }
+    if (!src.gz) throw std::runtime_error("Stream not successful: " + inFile);
+    gzbuffer(src.gz, 1u << 20);
+    const size_t blockBytes = std::max<size_t>(bytesPerBatch, 64);
+    readsPerBatch = std::max<size_t>(readsPerBatch, 1);
+
+    SamSubsetStats stats;
+    std::vector<const char *> ptr;
+    std::vector<uint64_t> len;
+    std::vector<const ts_sam_record *> judged;
+    std::vector<uint8_t> pass;
+    std::string text;
+    auto write = [&](const char *p, size_t n) {
+        out.write(p, static_cast<std::streamsize>(n));
+        if (!out.good()) throw std::runtime_error("failed while writing SAM subset");
+    };
+    std::vector<char> buf;
+    size_t have = 0;                                            // buf[0, have): the unfinished line of the block before
+    bool eof = false, any = false, inHeader = true;
+    uint64_t lines = 0;
+    detail::SamWalk walk;
+    while (!eof) {
+        if (buf.size() < have + blockBytes) buf.resize(have + blockBytes);
+        size_t got = 0;
+        while (got < blockBytes) {
+            const int r = gzread(src.gz, buf.data() + have + got, static_cast<unsigned>(std::min<size_t>(blockBytes - got, 1u << 30)));
+            if (r < 0) throw std::runtime_error("read error in SAM input");
+            if (r == 0) { eof = true; break; }
+            got += static_cast<size_t>(r);
+        }
+        const size_t size = have + got;
+        any = any || size > 0;
+        if (eof && !any) throw std::runtime_error("SAM input is empty");
+        detail::samWalkHost(buf.data(), size, eof, inHeader, walk);
+        write(buf.data(), static_cast<size_t>(walk.headerEnd));
+        stats.headerLines += walk.headerLines; stats.totalRecords += walk.recs.size();
+        if (walk.headerLines < walk.lines || walk.error != TS_SAM_OK) inHeader = false;
+        // the block's records in batches (they point into the block), the kept lines echoed
+        for (size_t a = 0; a < walk.recs.size(); a += readsPerBatch) {
+            const size_t n = std::min(readsPerBatch, walk.recs.size() - a);
+            ptr.clear(); len.clear(); judged.clear();
+            for (size_t i = a; i < a + n; ++i) {
+                const ts_sam_record &r = walk.recs[i];
+                if (r.flags & 1u) { ++stats.missingSequenceRecords; continue; }      // (SEQ is "*": never kept)
+                ptr.push_back(buf.data() + r.off + r.seq_at); len.push_back(r.seq_len); judged.push_back(&r);
+            }
+            if (judged.empty()) continue;
+            pass.resize(judged.size());
+            warmUp.join();
+            filter.matchesPointers(ptr.data(), len.data(), judged.size(), pass.data());
+            text.clear();
+            for (size_t i = 0; i < judged.size(); ++i) {
+                if (!pass[i]) continue;
+                text.append(buf.data() + judged[i]->off, judged[i]->size);
+                text.push_back('\n');
+                ++stats.passedRecords;
+            }
+            write(text.data(), text.size());
+        }
+        if (walk.error != TS_SAM_OK) { out.flush(); throw detail::samLineError(lines + walk.errorLine + 1, walk.error); }
+        lines += walk.lines;
+        have = size - static_cast<size_t>(walk.next);
+        if (have) std::memmove(buf.data(), buf.data() + walk.next, have);
+    }
+    out.flush();
+    return stats;
+}
+
+namespace detail {
+
+// samSubsetDevice's stages, modelled on FastqChunkSteps.  ts_sam_chunk_walk frames the chunk's lines — the header lines in front
+// of it while the input's header goes on, then the records — and the unfinished last line goes in front of the next chunk.  A
+// line that fails a check ends the framing; its chunk's header lines and valid records are still written before emit() throws.  A
+// chunk that holds no whole line passes all of its contents on and grows as the FASTQ steps' chunks do.  Whether the input is
+// still in its header, and how many lines lie behind, is the framing's state: it moves on in the serial section only.
+class SamChunkSteps {
+public:
+    struct Worker : ChunkWorker {
+        ChunkFeed::Fill fill;                                   // a dealt chunk's new bytes
+        std::vector<ts_sam_record> recs, withSeq;
+        std::vector<char> header;                               // the chunk's header lines as read, until they are written
+        uint64_t n = 0, headerLines = 0, missing = 0;           // records and header lines of the chunk; its records without sequence
+        int error = TS_SAM_OK;
+        uint64_t errorLine = 0;                                 // of the whole input, counted from 1
+    };
+    SamSubsetStats stats;
+    double msWrite = 0;
+    std::vector<std::unique_ptr<Worker>> workers;
+
+    SamChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes)
+        : feed_(feed), out_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
+        const uint64_t compCap = feed.compCap(chunkBytes);
+        for (size_t w = 0; w < filter.deviceCount(); ++w) {
+            workers.emplace_back(new Worker());
+            Worker &k = *workers.back();
+            k.ctx = filter.context(w);
+            k.chunk = ts_bam_chunk_create(k.ctx, compCap, chunkBytes);
+            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
+            k.recs.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16));
+        }
+    }
+
+    // The whole input as in-place chunks of context 0, on the caller's thread: any source of the feed, ChunkFeed::Gzip included
+    void runInPlace() {
+        Worker &k = *workers[0];
+        for (bool atEnd = false; !atEnd;) {
+            const uint64_t carry = ts_bam_chunk_size(k.chunk) - prevNext_;
+            // a chunk that held no whole line takes as much again
+            const size_t want = static_cast<size_t>(std::max<uint64_t>(chunkBytes_, prevNext_ == 0 ? carry : 0));
+            const Clock::time_point t0 = Clock::now();
+            atEnd = feed_.fill(k.chunk, prevNext_, want);
+            k.st.msSource += since(t0);
+            ++k.st.chunks; k.st.bytesReceived += ts_bam_chunk_size(k.chunk) - carry;
+            frameLines(k, atEnd);
+            judgeRecords(k, false);
+            emit(0, 0);
+        }
+    }
+
+    // the ring's steps: a dealt chunk
+    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
+    RingTake take(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        feed_.take(chunkBytes_, k.fill);
+        k.st.msSource += since(t0);
+        return k.fill.atEnd ? RingTake::Last : RingTake::More;
+    }
+    void stage(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        const Clock::time_point t0 = Clock::now();
+        feed_.stage(k.ctx, k.chunk, k.fill);
+        k.st.msSource += since(t0);
+        ++k.st.chunks; k.st.bytesReceived += k.fill.n;
+    }
+    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, ts_sam_chunk_walk, the header state
+        Worker &k = *workers[w];
+        ringCommit(k, prev_, prevNext_);
+        return frameLines(k, k.fill.atEnd);
+    }
+    void judge(size_t w, uint64_t) { judgeRecords(*workers[w], true); }
+    // the chunk's turn to write: its header lines and what it kept (nothing, where it came in place), its totals, and the line
+    // that is not valid
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        writeHeader(k);
+        k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
+        stats.headerLines += k.headerLines; stats.totalRecords += k.n; stats.passedRecords += k.passed; stats.missingSequenceRecords += k.missing;
+        if (k.error != TS_SAM_OK) { out_.flush(); throw samLineError(k.errorLine, k.error); }
+    }
+
+private:
+    // The lines of a chunk that has its bytes; the framing's state moves on to it.  -> every line up to the chunk's end is valid
+    bool frameLines(Worker &k, bool atEnd) {
+        prev_ = &k; prevNext_ = 0;
+        k.n = k.headerLines = k.missing = 0; k.error = TS_SAM_OK; k.header.clear();
+        if (first_) {
+            if (ts_bam_chunk_size(k.chunk) == 0) {
+                if (atEnd) throw std::runtime_error("SAM input is empty");
+                return true;
+            }
+            first_ = false;
+        }
+        uint64_t headerEnd = 0, nLines = 0, errorLine = 0, errorOff = 0;
+        const Clock::time_point t0 = Clock::now();
+        auto walk = [&]() {
+            return ts_sam_chunk_walk(k.chunk, atEnd ? 1 : 0, inHeader_ ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &k.headerLines, &headerEnd, &nLines,
+                                     &prevNext_, &k.error, &errorLine, &errorOff);
+        };
+        int rc = walk();
+        if (rc == TS_ERR_INVALID_ARG && k.n > k.recs.size()) {
+            k.recs.resize(static_cast<size_t>(k.n));
+            rc = walk();
+        }
+        if (rc != TS_OK) throw deviceError(k.ctx, "SAM walk failed");
+        if (headerEnd) {
+            k.header.resize(static_cast<size_t>(headerEnd));
+            if (ts_bam_chunk_read(k.chunk, 0, headerEnd, k.header.data()) != TS_OK) throw deviceError(k.ctx, "cannot read the chunk");
+        }
+        k.st.msWalk += since(t0);
+        k.errorLine = lines_ + errorLine + 1;
+        lines_ += nLines;
+        if (k.headerLines < nLines || k.error != TS_SAM_OK) inHeader_ = false;
+        return k.error == TS_SAM_OK;
+    }
+    // The chunk's records in sub-batches, in input order.  A dealt chunk keeps a sub-batch's passing bytes until its turn to emit;
+    // an in-place chunk has the turn: its header lines, then the passing bytes, go straight to the output.
+    void judgeRecords(Worker &k, bool dealt) {
+        k.fresh();
+        if (!dealt) writeHeader(k);
+        for (size_t a = 0; a < k.n; a += readsPerBatch_) {
+            const ts_sam_record *r = k.recs.data() + a;
+            const size_t n = std::min<size_t>(readsPerBatch_, static_cast<size_t>(k.n) - a);
+            k.withSeq.clear(); k.lens.clear();
+            for (size_t i = 0; i < n; ++i) {
+                if (r[i].flags & 1u) { ++k.missing; continue; }     // (SEQ is "*": never kept)
+                k.withSeq.push_back(r[i]); k.lens.push_back(r[i].seq_len);
+            }
+            if (k.withSeq.empty()) continue;
+            k.st.recordsJudged += k.withSeq.size();
+            k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
+                         [&](ts_batch *batch) { return ts_sam_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
+                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                             return ts_sam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+                         });
+            k.passed += k.judged.nPassed;
+            if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
+        }
+    }
+    void writeHeader(Worker &k) {
+        if (k.header.empty()) return;
+        write(reinterpret_cast<const unsigned char *>(k.header.data()), k.header.size());
+        k.header.clear();
+    }
+    void write(const unsigned char *p, size_t n) {
+        const Clock::time_point t0 = Clock::now();
+        out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+        if (!out_.good()) throw std::runtime_error("failed while writing SAM subset");
+        msWrite += since(t0);
+    }
+
+    ChunkFeed &feed_;
+    std::ostream &out_;
+    size_t readsPerBatch_, chunkBytes_;
+    // the framing's state: the chunk framed last and where its unfinished line begins; nothing framed yet held a byte; the input
+    // is still in its header; whole lines behind
+    const ChunkWorker *prev_ = nullptr;
+    uint64_t prevNext_ = 0;
+    bool first_ = true, inHeader_ = true;
+    uint64_t lines_ = 0;
+};
+
+}  // namespace detail
+
+// The device route of --sam-subset (same arguments, result, exceptions and output bytes as samSubset): the SAM text exists in HBM
+// one chunk of ~chunkBytes bytes at a time and the host reads none of it but the header lines, which it writes.  The text gets
+// there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, a stream through zlib or read(2), plain gzip
+// on the device under TS_GZIP_DEVICE=1; `-` is stdin, always through zlib); behind the source the lines and tabs are indexed and the
+// lines cut and checked (ts_sam_chunk_walk: the table comes back), the sequences staged into a tips-only batch's input buffer
+// (ts_sam_chunk_stage), judged and the passing lines gathered (detail::ReadJudge with ts_sam_chunk_gather).  A filter of one
+// context takes every chunk in place; on a filter of several contexts the ring deals the chunks to all of them, and there plain
+// gzip is read through zlib, as for fastqSubsetDevice.  perDevice, where given, receives one entry per context.
+inline SamSubsetStats samSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                      size_t readsPerBatch = 1u << 20, size_t chunkBytes = 256u << 20,
+                                      std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    const bool dealt = filter.deviceCount() > 1;
+    detail::ChunkFeed::Options options;
+    options.cannotOpen = "Stream not successful: " + inFile;
+    options.cannotRead = "read error in SAM input";
+    options.dashIsStdin = true;
+    options.uploadFailed = "upload of the SAM text failed";
+    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
+    detail::ChunkFeed feed(filter.context(0), inFile, options);
+    detail::SamChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64));
+    std::unique_ptr<detail::ChunkRing<detail::SamChunkSteps>> ring;
+    if (dealt) {
+        ring.reset(new detail::ChunkRing<detail::SamChunkSteps>(filter.deviceCount(), 0, steps));
+        ring->run();
+    } else {
+        steps.runInPlace();
+    }
+    out.flush();
+    detail::routeFigures(feed.deviceInflate() ? "samSubsetDevice (upload + inflate + CRC)" : "samSubsetDevice", steps.workers, ring.get(), steps.msWrite, perDevice);
+    return steps.stats;
+}
+
 inline const char *scaffoldTypeToString(ScaffoldType t) {       // src/tools.cpp
     static const char *names[] = {"t2t", "gapped_t2t", "misassembly", "gapped_misassembly", "incomplete",
                                   "gapped_incomplete", "none", "gapped_none", "discordant", "gapped_discordant"};

@@ -214,6 +214,11 @@ class FastqRecord(C.Structure):
                 ("seq_cr", C.c_uint32)]
 
 
+class SamRecord(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("seq_at", C.c_uint32), ("seq_len", C.c_uint32), ("size", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 class FastaRecord(C.Structure):
     _fields_ = [("off", C.c_uint64), ("text_len", C.c_uint32), ("body_at", C.c_uint32), ("n_bases", C.c_uint32),
                 ("name_at", C.c_uint32), ("name_len", C.c_uint32), ("reserved", C.c_uint32)]
@@ -244,6 +249,7 @@ class GfaFlagged(C.Structure):
 GFA_CHECK_HOST_DECIDES = 255
 BGZF_OK, BGZF_BAD_DEFLATE, BGZF_BAD_CRC = 0, 1, 2
 FASTQ_OK, FASTQ_TRUNCATED, FASTQ_BAD_HEADER, FASTQ_BAD_SEPARATOR, FASTQ_BAD_LENGTHS = 0, 1, 2, 3, 4
+SAM_OK, SAM_HEADER_AFTER_RECORD, SAM_TOO_FEW_FIELDS, SAM_EMPTY_SEQ, SAM_BAD_LENGTHS = 0, 1, 2, 3, 4
 BAM_OK, BAM_BAD_BLOCK_SIZE, BAM_BAD_LENGTHS, BAM_FIELDS_EXCEED, BAM_NAME_NOT_NUL = 0, 1, 2, 3, 4
 SHARD_RETRY_SYNC, SHARD_RETRY_GROW, SHARD_NEED_FULL = 1, 2, 3
 SHARD_OVERFLOW_VISIBLE, SHARD_OVERFLOW_BLOCKS, SHARD_OVERFLOW_SCAN, SHARD_OUT_OF_CONTEXT = 1, 2, 4, 8
@@ -281,6 +287,7 @@ SYMBOLS = [
     "ts_bam_chunk_index", "ts_bam_chunk_set_index_geometry", "ts_bam_index_stats",
     "ts_chunk_stage_upload", "ts_chunk_stage_inflate", "ts_chunk_staged", "ts_chunk_commit",
     "ts_bgzf_deflate", "ts_bam_chunk_gather_bgzf", "ts_bgzf_deflate_stats",
+    "ts_sam_chunk_walk", "ts_sam_chunk_stage", "ts_sam_chunk_gather",
 ]
 
 
@@ -479,6 +486,11 @@ def lib():
     L.ts_fastq_chunk_stage.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p]
     L.ts_fastq_chunk_gather.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_sam_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SamRecord), C.c_uint64] + [C.POINTER(C.c_uint64)] * 5 + \
+        [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ts_sam_chunk_stage.argtypes = [C.c_void_p, C.POINTER(SamRecord), C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ts_sam_chunk_gather.argtypes = [C.c_void_p, C.POINTER(SamRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     L.ts_fasta_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.POINTER(FastaRecord), C.c_uint64, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.ts_fasta_chunk_join.argtypes = [C.c_void_p, C.POINTER(FastaRecord), C.c_size_t, C.c_int, C.POINTER(C.c_void_p),

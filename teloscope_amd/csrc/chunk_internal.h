@@ -1,7 +1,7 @@
-// chunk_internal.h — the chunk layer under the BAM, FASTQ, FASTA and GFA device stages: a chunk of an uncompressed stream
+// chunk_internal.h — the chunk layer under the BAM, FASTQ, SAM, FASTA and GFA device stages: a chunk of an uncompressed stream
 // resident on the device (struct ts_bam_chunk: the public header names the type; ts_chunk is the same type), the line index the
-// three text walks begin with, the gather both record routes end with, and the launchers of the kernels the routes share
-// (chunk.hip).  chunk.cpp owns the object and the functions declared here; a route file (bgzf.cpp, fastq.cpp, fasta.cpp,
+// four text walks begin with, the gather the record routes end with, and the launchers of the kernels the routes share
+// (chunk.hip).  chunk.cpp owns the object and the functions declared here; a route file (bgzf.cpp, fastq.cpp, sam.cpp, fasta.cpp,
 // gfa.cpp) touches the common part and its own group.
 #pragma once
 
@@ -66,6 +66,9 @@ struct ts_bam_chunk {
         DevBuf d_counts, d_tabs, d_kinds, d_frames, d_segs, d_lines, d_text, d_out, d_stray, d_codes, d_ccounts, d_cout, d_flagged;
         uint64_t lines_generation = 0, n_tabs = 0;
     } gfa;
+    // ---- SAM (sam.cpp): the tab counts per slice and the tabs' offsets, the alignment lines per slice of lines, the walk's
+    // result block of 64 bytes; the stage's jobs
+    struct Sam { DevBuf d_counts, d_tabs, d_frames, d_out, d_jobs; } sam;
 };
 
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
