@@ -996,6 +996,67 @@ int ts_sam_chunk_stage(ts_chunk *chunk, const ts_sam_record *recs, size_t n, ts_
 int ts_sam_chunk_gather(ts_chunk *chunk, const ts_sam_record *recs, size_t n, const void *d_pass, void *host_out,
                         uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
 
+/* ---- The read block report: the telomere blocks of the kept reads as text, a BED beside a read subset (--fastq-subset,
+ *      --bam-subset, --sam-subset; include/teloscope_mi355x_io.hpp: the trailing `blocks` stream of fastqSubset, bamSubset,
+ *      samSubset and their device forms), formatted where a sub-batch's reads were judged.  The reference has no such output; the
+ *      rule is this project's own, stated here and nowhere else, and every caller follows it.  It mirrors the terminal loop of the
+ *      reference's writeBEDFile (src/teloscope.cpp, the lines of _terminal_telomeres.bed) with pathSize replaced by the read's
+ *      length and the scaffold / contig word dropped:
+ *        - For every kept record, in output order, one line per terminal block of its read.  The blocks are those of the read
+ *          scanned as ONE tips-only segment at abs_pos 0 under the read filter's parameters, in the order in which
+ *          ts_scan_segments_blocks returns terminal_blocks (the forward list's walk from the start, then the reverse list's walk
+ *          from the end, each in push order).
+ *        - A line is
+ *            name \t start \t end \t block_len \t label \t forward_count \t reverse_count \t canonical_count \t
+ *            non_canonical_count \t read_len \n
+ *          with end = start + block_len and label the block's block_label as that call returns it.  Always '\n', never '\r'.
+ *        - read_len is the number of bases judged: seq_len - seq_cr for FASTQ, SEQ's length for SAM, l_seq for BAM.
+ *        - name is, for FASTQ, the header line's bytes behind '@' up to the first space, tab or the line's end, a '\r' in front of
+ *          the line's '\n' not counted to the line (the name may be empty); for SAM the bytes in front of the first tab; for BAM
+ *          read_name without its NUL.
+ *        - A record that is not kept has no line; a kept record has at least one (matches() is !terminalBlocks.empty(),
+ *          src/read-filter.cpp:37-45).  Secondary and supplementary BAM records are records like any other. */
+/* One row of a batch's ordered blocks: the segment (read) of the batch and its block, start relative to the segment's abs_pos. */
+typedef struct ts_read_block {
+    uint32_t segment;
+    uint32_t reserved;
+    ts_block block;
+} ts_read_block;
+/* On a scanned tips-only batch, tiled or general (a full-scan batch answers TS_ERR_INVALID_ARG): runs the terminal walks and
+ * leaves, in device memory of the batch, the terminal blocks of all segments ordered by (segment, walk, push order) — the order
+ * of ts_scan_segments_blocks' terminal_blocks — and the index of every segment's first block (n + 1 entries).  The walks run
+ * twice: a counting form says how many blocks each walk closes, exchange.hip's sums turn the counts into places, and a placing
+ * form writes every block at its walk's base plus its push order; nothing is sorted on the host, no block leaves the device, and
+ * the rows are the same bytes from launch to launch.  Asynchronous on `stream` (a general tips batch: the stream of its scan).
+ * Overflow follows ts_batch_read_pass' protocol exactly: ts_batch_read_pass_status reports it, the caller then calls
+ * ts_batch_sync and ts_batch_call_read_blocks again; after an overflow a tiled batch holds no rows and a general tips batch's are
+ * memory-safe and meaningless.  Stands in for getTerminalBlocks (src/teloscope.cpp:29-176) as scanSegment calls it per read. */
+int ts_batch_call_read_blocks(ts_batch *b, void *stream);
+/* The rows of the last ts_batch_call_read_blocks to host memory, for tests and tools: *n of them; when *n > cap nothing is copied
+ * and the call answers TS_ERR_INVALID_ARG (call again with room for *n).  Waits for the device. */
+int ts_batch_read_blocks(ts_batch *b, ts_read_block *out, uint64_t cap, uint64_t *n);
+/* The report's lines of a sub-batch, formatted on the device from the rows where they lie and the names where the chunk holds
+ * them.  recs / n are the arrays given to the matching stage / decode call (ts_fastq_chunk_stage, ts_sam_chunk_stage,
+ * ts_bam_chunk_decode), `reads` that batch after ts_batch_call_read_blocks (and after ts_batch_read_pass_status said that nothing
+ * overflowed).  The lines, in row order, to host_out; *bytes and *n_lines say how much; cap and *bytes behave as for
+ * ts_fastq_chunk_gather (*bytes > cap: nothing is copied, TS_ERR_INVALID_ARG).  Ordered on `stream`; waits for it. */
+int ts_fastq_chunk_block_lines(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
+                               uint64_t *bytes, uint64_t *n_lines, void *stream);
+int ts_sam_chunk_block_lines(ts_chunk *chunk, const ts_sam_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
+                             uint64_t *bytes, uint64_t *n_lines, void *stream);
+int ts_bam_chunk_block_lines(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
+                             uint64_t *bytes, uint64_t *n_lines, void *stream);
+/* The formatting stage alone, host in, host out: rows[0, n_rows) (segment: an index into the three per-segment arrays, which
+ * must cover it), segment s's name names[name_off[s], name_off[s] + name_len[s]) and read length read_len[s].  Uploads them and
+ * runs the kernels the chunk calls run; exists so that values no small read produces can be formatted (positions of twenty
+ * digits, names of hundreds of bytes).  cap and *bytes as above. */
+int ts_read_block_lines_format(ts_ctx *ctx, const ts_read_block *rows, uint64_t n_rows, const uint64_t *name_off,
+                               const uint32_t *name_len, const uint32_t *read_len, const char *names, uint64_t names_len, void *out,
+                               uint64_t cap, uint64_t *bytes);
+/* Measurement aid: out[0] formatting calls that reached the device (a *_block_lines call or ts_read_block_lines_format), out[1]
+ * lines, out[2] text bytes the device formatted since ts_create.  Cumulative, monotonic, atomic, like ts_match_text_stats. */
+int ts_read_block_text_stats(const ts_ctx *ctx, uint64_t out[3]);
+
 /* ---- FASTA text in the same resident chunk: the device form of the assembly front end.  Replaces the reference's FASTA load
  *      (gfalibs' stream parser behind Input::read, src/input.cpp:655-716: header lines split off, body lines joined into one
  *      sequence per record) and the cut of a path into segments and gaps at its N-runs (the path components walkPath

@@ -49,6 +49,7 @@
 #include "teloscope_mi355x_filter.hpp"
 #include "teloscope_mi355x_gzip.hpp"
 #include "teloscope_mi355x_ring.hpp"
+#include "../teloscope_amd/csrc/read_block_format_core.h"
 
 namespace teloscope_mi355x {
 
@@ -535,7 +536,7 @@ inline std::vector<PathData> walkPaths(Teloscope &teloscope, const std::vector<F
 // kept verbatim, '\r' included) from a plain or gzip file ("-" = stdin) and filtered in batches of up
 // to readsPerBatch reads / basesPerBatch bases — a GPU batch, not the reference's 2048-record one.
 // Malformed input throws std::runtime_error with the reference's message.
-struct FastqSubsetResult { uint64_t kept = 0, total = 0; };
+struct FastqSubsetResult { uint64_t kept = 0, total = 0, blockLines = 0; };     // blockLines: lines of the read block report, if one was asked for
 
 namespace detail {
 inline size_t logicalLineLength(const char *b, const char *e) { return (e > b && e[-1] == '\r') ? static_cast<size_t>(e - b) - 1 : static_cast<size_t>(e - b); }
@@ -655,9 +656,59 @@ public:
 };
 }  // namespace detail
 
+namespace detail {
+// The read block report of the host routes (the rule: include/teloscan.h, "The read block report"; the output is this project's
+// own, its columns those of the terminal loop of the reference's writeBEDFile, src/teloscope.cpp).  A route adds the reads it keeps
+// of a batch, in output order; flush() scans them once more as tips-only segments at abs_pos 0 on the filter's context
+// (ts_scan_segments_blocks: the blocks the filter's bit was made from), formats a line per terminal block with the core header the
+// device formatter compiles, and writes them.  Without a stream nothing is kept and nothing runs.
+class ReadBlockReport {
+public:
+    uint64_t lines = 0;
+    ReadBlockReport(std::ostream *os, const char *failed) : os_(os), failed_(failed) {}
+    bool on() const { return os_ != nullptr; }
+    void add(const char *name, uint32_t nameLen, const char *seq, uint64_t len) { if (os_) kept_.push_back(Kept{name, nameLen, seq, len}); }
+    void flush(ts_ctx *ctx) {
+        if (!os_ || kept_.empty()) return;
+        segs_.assign(kept_.size(), ts_segment_in{});
+        outs_.assign(kept_.size(), ts_segment_out{});
+        for (size_t i = 0; i < kept_.size(); ++i) { segs_[i].seq = kept_[i].seq; segs_[i].len = kept_[i].len; segs_[i].tips_only = 1; }
+        if (ts_scan_segments_blocks(ctx, segs_.data(), segs_.size(), outs_.data(), nullptr) != TS_OK) throw std::runtime_error(std::string("block calling of the kept reads failed: ") + ts_last_error(ctx));
+        text_.clear();
+        for (size_t i = 0; i < kept_.size(); ++i)
+            for (uint64_t j = 0; j < outs_[i].n_terminal_blocks; ++j) {
+                const ts_block &b = outs_[i].terminal_blocks[j];
+                const tsrb::Fields f{b.start, b.block_len, b.forward_count, b.reverse_count, b.canonical_count, b.non_canonical_count,
+                                     static_cast<uint32_t>(kept_[i].len), static_cast<uint32_t>(static_cast<unsigned char>(b.block_label))};
+                const size_t at = text_.size();
+                text_.resize(at + tsrb::line_len(kept_[i].nameLen, f));
+                Sink sink{&text_[at]};
+                tsrb::put_line(sink, 0u, Bytes{kept_[i].name}, 0, kept_[i].nameLen, f);
+                ++lines;
+            }
+        ts_free_segments(outs_.data(), outs_.size());
+        kept_.clear();
+        os_->write(text_.data(), static_cast<std::streamsize>(text_.size()));
+        if (!os_->good()) throw std::runtime_error(failed_);
+    }
+    struct Bytes { const char *p; uint32_t byte(uint64_t i) const { return static_cast<unsigned char>(p[i]); } };
+
+private:
+    struct Kept { const char *name; uint32_t nameLen; const char *seq; uint64_t len; };
+    struct Sink { char *p; void put(uint32_t at, uint32_t byte) { p[at] = static_cast<char>(byte); } };
+    std::ostream *os_;
+    const char *failed_;
+    std::vector<Kept> kept_;
+    std::vector<ts_segment_in> segs_;
+    std::vector<ts_segment_out> outs_;
+    std::string text_;
+};
+}  // namespace detail
+
 inline FastqSubsetResult fastqSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 512u << 20) {
+                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 512u << 20, std::ostream *blocks = nullptr) {
     detail::FilterWarmUp warmUp(filter);
+    detail::ReadBlockReport report(blocks, "failed while writing the FASTQ subset's block report");
     // The input is read in large blocks into one arena and parsed in place: a batch's sequences are
     // handed to the filter as pointers into the arena and a kept record is echoed as the byte range of
     // its four lines — no per-line copies.
@@ -764,10 +815,15 @@ inline FastqSubsetResult fastqSubset(const std::string &inFile, std::ostream &ou
             text.append(batch[i].begin, batch[i].end);
             text.push_back('\n');
             ++res.kept;
+            if (report.on())
+                report.add(batch[i].begin + 1, tsrb::fastq_name_len(detail::ReadBlockReport::Bytes{batch[i].begin}, 0, static_cast<uint32_t>(batch[i].seq - batch[i].begin)),
+                           batch[i].seq, detail::logicalLineLength(batch[i].seq, batch[i].seq + batch[i].seqLen));
         }
         res.total += batch.size();
         out.write(text.data(), static_cast<std::streamsize>(text.size()));
         if (!out.good()) throw std::runtime_error("failed while writing FASTQ subset");
+        report.flush(filter.context(0));
+        res.blockLines = report.lines;
     };
     // Parses whole records out of [p, end) — several GPU batches if the range holds more than readsPerBatch reads or
     // bytesPerBatch record bytes — filters them and echoes the kept ones; returns the end of the last whole record.
@@ -904,6 +960,7 @@ inline FastqSubsetResult fastqSubset(const std::string &inFile, std::ostream &ou
 struct BamSubsetStats {
     uint64_t totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0; bool missingEofBlock = false;
     uint64_t deflatePlainBytes = 0, deflateMemberBytes = 0; double msDeflate = 0;
+    uint64_t blockLines = 0;                    // lines of the read block report, if one was asked for
 };
 
 namespace detail {
@@ -1202,9 +1259,10 @@ public:
 }  // namespace detail
 
 inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
+                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
     BamSubsetStats stats;
     detail::FilterWarmUp warmUp(filter);
+    detail::ReadBlockReport report(blocks, "failed while writing the BAM subset's block report");
     int fd = 0;
     if (inFile != "-") {
         fd = ::open(inFile.c_str(), O_RDONLY);
@@ -1304,8 +1362,16 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
                 const Rec &r = recs[i];
                 ++stats.totalRecords;
                 if (!r.seqLen) { ++stats.missingSequenceRecords; continue; }
-                if (pass[k++]) { writer.write(plain + r.rawOff, r.rawLen); ++stats.passedRecords; }
+                if (pass[k++]) {
+                    writer.write(plain + r.rawOff, r.rawLen); ++stats.passedRecords;
+                    if (report.on()) {
+                        const char *rec = reinterpret_cast<const char *>(plain + r.rawOff);
+                        report.add(rec + tsrb::kBamNameAt, tsrb::bam_name_len(detail::ReadBlockReport::Bytes{rec}, 0), seqs.get() + r.seqOff, r.seqLen);
+                    }
+                }
             }
+            report.flush(filter.context(0));
+            stats.blockLines = report.lines;
         }
         recs.clear();
     };
@@ -1750,9 +1816,16 @@ using Clock = std::chrono::steady_clock;
 inline double since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }    // ms
 
 struct ReadJudge {
-    double msStage = 0, msFilter = 0, msGather = 0;
+    double msStage = 0, msFilter = 0, msGather = 0, msBlocks = 0;
     std::vector<unsigned char> kept;
     uint64_t bytes = 0, nPassed = 0;                            // of the last run: kept[0, bytes) are the passing records
+    // The read block report (include/teloscan.h), where a route was given a stream for it: blockLines(batch, dst, cap, &bytes,
+    // &lines) is the route's ts_*_chunk_block_lines call.  Between filter and gather the judged batch's blocks are called
+    // (ts_batch_call_read_blocks) and the lines of the kept reads formatted and downloaded: blockText[0, blockBytes), nBlockLines
+    // of them.  Empty: no call, no kernel, no allocation.
+    std::function<int(ts_batch *, unsigned char *, uint64_t, uint64_t *, uint64_t *)> blockLines;
+    std::vector<unsigned char> blockText;
+    uint64_t blockBytes = 0, nBlockLines = 0;
 
     template <typename Stage, typename Gather>
     void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather) {
@@ -1777,6 +1850,19 @@ struct ReadJudge {
                 ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed) throw deviceError(ctx, "read filter failed");
         }
         msFilter += since(t0); t0 = Clock::now();
+        blockBytes = nBlockLines = 0;
+        if (blockLines) {
+            if (ts_batch_call_read_blocks(batch.p, nullptr) != TS_OK || ts_batch_read_pass_status(batch.p, &overflowed) != TS_OK || overflowed)
+                throw deviceError(ctx, "block calling of the kept reads failed");
+            if (blockText.size() < (1u << 16)) blockText.resize(1u << 16);
+            int rc = blockLines(batch.p, blockText.data(), blockText.size(), &blockBytes, &nBlockLines);
+            if (rc == TS_ERR_INVALID_ARG && blockBytes > blockText.size()) {
+                blockText.resize(static_cast<size_t>(blockBytes));
+                rc = blockLines(batch.p, blockText.data(), blockText.size(), &blockBytes, &nBlockLines);
+            }
+            if (rc != TS_OK) throw deviceError(ctx, "formatting the block report failed");
+            msBlocks += since(t0); t0 = Clock::now();
+        }
         bytes = nPassed = 0;
         if (kept.size() < (1u << 20)) kept.resize(1u << 20);
         const uint64_t want = room(dPass);
@@ -1828,6 +1914,7 @@ enum class BamOutputDeflate { Host, Device };
 struct ReadRouteDeviceStats {
     uint64_t chunks = 0, recordsJudged = 0, bytesReceived = 0;
     double msSource = 0, msCarryWait = 0, msCommit = 0, msWalk = 0, msStage = 0, msFilter = 0, msGather = 0;
+    double msBlocks = 0;                                        // in ReadJudge's block report step (0 without a `blocks` stream)
     // BamOutputDeflate::Device only: milliseconds in ts_bam_chunk_gather_bgzf (part of msGather: gather, deflate kernels, the
     // members' download), record bytes that went into it and member bytes that came out
     double msDeflate = 0;
@@ -1846,16 +1933,25 @@ struct ChunkWorker {
     std::vector<unsigned char> out;                             // a dealt chunk's passing records, in input order
     std::vector<size_t> cuts;                                   // where each sub-batch's records end in `out`: the writer's pieces
     uint64_t passed = 0;                                        // the chunk's passing records, however it came in
+    std::vector<unsigned char> blockOut;                        // a dealt chunk's lines of the read block report, in input order
+    uint64_t blockLines = 0;                                    // the chunk's report lines, however it came in
     ReadRouteDeviceStats st;
     ChunkWorker() = default;
     ChunkWorker(const ChunkWorker &) = delete;
     ChunkWorker &operator=(const ChunkWorker &) = delete;
     ~ChunkWorker() { ts_bam_chunk_destroy(chunk); }
-    void fresh() { out.clear(); cuts.clear(); passed = 0; }
+    void fresh() { out.clear(); cuts.clear(); passed = 0; blockOut.clear(); blockLines = 0; }
     // a dealt chunk's sub-batch waits here for the chunk's turn to emit
     void keep() {
         out.insert(out.end(), judged.kept.begin(), judged.kept.begin() + static_cast<std::ptrdiff_t>(judged.bytes));
         cuts.push_back(out.size());
+        blockOut.insert(blockOut.end(), judged.blockText.begin(), judged.blockText.begin() + static_cast<std::ptrdiff_t>(judged.blockBytes));
+    }
+    // report lines to the route's `blocks` stream (nothing without one)
+    static void writeBlocks(std::ostream *os, const unsigned char *p, size_t n) {
+        if (!os || !n) return;
+        os->write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+        if (!os->good()) throw std::runtime_error("failed while writing the block report");
     }
     // the kept pieces in the order and sizes an in-place chunk writes them (of which it keeps none)
     template <typename Write>
@@ -1886,6 +1982,7 @@ inline void routeFigures(const char *route, const std::vector<std::unique_ptr<Wo
     for (size_t w = 0; w < workers.size(); ++w) {
         ReadRouteDeviceStats s = workers[w]->st;
         s.msStage = workers[w]->judged.msStage; s.msFilter = workers[w]->judged.msFilter; s.msGather = workers[w]->judged.msGather;
+        s.msBlocks = workers[w]->judged.msBlocks;
         if (ring) s.msCarryWait = ring->frameWaitMs(w);
         if (perDevice) perDevice->push_back(s);
         if (std::getenv("TS_TIMING")) {
@@ -1893,10 +1990,12 @@ inline void routeFigures(const char *route, const std::vector<std::unique_ptr<Wo
             if (s.deflatePlainBytes)
                 std::snprintf(deflate, sizeof deflate, ", of which device deflate %.0f ms (%llu record bytes -> %llu member bytes)", s.msDeflate,
                               (unsigned long long)s.deflatePlainBytes, (unsigned long long)s.deflateMemberBytes);
+            char report[64] = "";                               // (a route that wrote the block report says what it cost)
+            if (workers[w]->judged.blockLines) std::snprintf(report, sizeof report, ", block report %.0f ms", s.msBlocks);
             std::fprintf(stderr, "%s: context %zu of %zu: %llu chunks, %llu reads judged, %llu bytes; source %.0f ms, carry wait %.1f ms, carry + commit %.1f ms, "
-                         "walk %.1f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms%s\n", route, w, workers.size(), (unsigned long long)s.chunks,
+                         "walk %.1f ms, stage %.0f ms, filter %.0f ms, gather %.0f ms%s%s\n", route, w, workers.size(), (unsigned long long)s.chunks,
                          (unsigned long long)s.recordsJudged, (unsigned long long)s.bytesReceived, s.msSource, s.msCarryWait, s.msCommit, s.msWalk, s.msStage,
-                         s.msFilter, s.msGather, deflate);
+                         s.msFilter, s.msGather, deflate, report);
         }
     }
     if (std::getenv("TS_TIMING")) std::fprintf(stderr, "%s: write %.0f ms\n", route, msWrite);
@@ -1919,8 +2018,8 @@ public:
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    FastqChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes)
-        : feed_(feed), out_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
+    FastqChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
+        : feed_(feed), out_(out), blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
         const uint64_t compCap = feed.compCap(chunkBytes);
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
             workers.emplace_back(new Worker());
@@ -1975,7 +2074,8 @@ public:
     void emit(size_t w, uint64_t) {
         Worker &k = *workers[w];
         k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
-        res.kept += k.passed; res.total += k.n;
+        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
+        res.kept += k.passed; res.total += k.n; res.blockLines += k.blockLines;
         if (k.error != TS_FASTQ_OK) {
             const char *msg = k.error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : k.error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
                             : k.error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
@@ -2020,13 +2120,19 @@ private:
             for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].seq_len - r[i].seq_cr); }
             if (k.withSeq.empty()) continue;                    // (a read without bases is never kept)
             k.st.recordsJudged += k.withSeq.size();
+            if (blocks_ && !k.judged.blockLines)
+                k.judged.blockLines = [&k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+                    return ts_fastq_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+                };
             k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
                          [&](ts_batch *batch) { return ts_fastq_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
                          [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
                              return ts_fastq_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
                          });
             k.passed += k.judged.nPassed;
-            if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
+            k.blockLines += k.judged.nBlockLines;
+            if (dealt) k.keep();
+            else { write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
         }
     }
     void write(const unsigned char *p, size_t n) {
@@ -2038,6 +2144,7 @@ private:
 
     ChunkFeed &feed_;
     std::ostream &out_;
+    std::ostream *blocks_;                                      // the read block report's stream, or nothing
     size_t readsPerBatch_, chunkBytes_;
     // the framing's state: the chunk framed last and where its unfinished record begins; nothing framed yet held a byte
     const ChunkWorker *prev_ = nullptr;
@@ -2064,8 +2171,8 @@ public:
     std::vector<std::unique_ptr<Worker>> workers;
 
     BamChunkSteps(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk,
-                  BamOutputDeflate deflate = BamOutputDeflate::Host)
-        : data_(data), size_(size), writer_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
+                  BamOutputDeflate deflate = BamOutputDeflate::Host, std::ostream *blocks = nullptr)
+        : data_(data), size_(size), writer_(out), blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
           table_(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), walk_(walk), deflate_(deflate),
           plainCap_((256ull << 20) + 4 + chunkBytes), compCap_(chunkBytes + (1u << 20)) {
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
@@ -2147,6 +2254,8 @@ public:
     void emit(size_t w, uint64_t) {
         Worker &k = *workers[w];
         k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
+        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
+        stats.blockLines += k.blockLines;
         stats.totalRecords += k.n;
         stats.missingSequenceRecords += k.n - k.withBases;
         stats.passedRecords += k.passed;
@@ -2228,6 +2337,10 @@ private:
                 if (k.withSeq.empty()) continue;
                 k.withBases += k.withSeq.size();
                 k.st.recordsJudged += k.withSeq.size();
+                if (blocks_ && !k.judged.blockLines)
+                    k.judged.blockLines = [&k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+                        return ts_bam_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+                    };
                 k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
                              [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
                              [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
@@ -2251,7 +2364,9 @@ private:
                                  return plain + 31u * ((plain + 0xff00u - 1) / 0xff00u);
                              });
                 k.passed += k.judged.nPassed;
-                if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
+                k.blockLines += k.judged.nBlockLines;
+            if (dealt) k.keep();
+            else { write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
             }
             from = end;
         }
@@ -2267,6 +2382,7 @@ private:
     const unsigned char *data_;
     size_t size_;
     BgzfWriter writer_;
+    std::ostream *blocks_;                                      // the read block report's stream, or nothing
     BamHeaderParser header_;
     size_t readsPerBatch_, chunkBytes_, table_;
     BamRecordWalk walk_;
@@ -2299,13 +2415,13 @@ namespace detail {
 // (the route itself, behind bamSubsetDevice's two forms below)
 inline BamSubsetStats bamSubsetDeviceRun(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
                                          size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice,
-                                         BamOutputDeflate deflate) {
+                                         BamOutputDeflate deflate, std::ostream *blocks) {
     // the compressed input: a regular file is mapped, a pipe is read to its end
     detail::MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
     std::vector<unsigned char> piped;
     if (!in.data) in.readToEnd(piped, "cannot read BAM input");
     detail::BamChunkSteps steps(filter, in.data ? in.data : piped.data(), in.data ? in.size : piped.size(), out, readsPerBatch,
-                                std::max<size_t>(bytesPerBatch, 1u << 20), walk, deflate);
+                                std::max<size_t>(bytesPerBatch, 1u << 20), walk, deflate, blocks);
     std::unique_ptr<detail::ChunkRing<detail::BamChunkSteps>> ring;
     if (const uint64_t firstChunk = steps.runInPlace()) {
         ring.reset(new detail::ChunkRing<detail::BamChunkSteps>(filter.deviceCount(), firstChunk, steps));
@@ -2323,13 +2439,13 @@ inline BamSubsetStats bamSubsetDeviceRun(const std::string &inFile, std::ostream
 inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                       size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
                                       BamRecordWalk walk = BamRecordWalk::Index, std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
-    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, BamOutputDeflate::Host);
+    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, BamOutputDeflate::Host, nullptr);
 }
 // ... and with the trailing `deflate` given (an overload, so that the form above stays exactly what it was)
 inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
                                       size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice,
-                                      BamOutputDeflate deflate) {
-    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, deflate);
+                                      BamOutputDeflate deflate, std::ostream *blocks = nullptr) {
+    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, deflate, blocks);
 }
 
 // The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as
@@ -2344,9 +2460,16 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
 // of them, and there plain gzip is read through zlib, because the opt-in device gzip source (ChunkFeed::Gzip) is bound to one
 // context.  perDevice, where given, receives one entry per context.
 // What a maintainer of the reference would call from Input::readFastqSubset (src/input.cpp:737-832) in place of its loop.
+// (two forms, as for bamSubsetDevice: the one without `blocks` stays exactly what it was; the one with it writes the read block report)
+inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                           size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks);
 inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                            size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20,
                                            std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    return fastqSubsetDevice(inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice, nullptr);
+}
+inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                           size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks) {
     const bool dealt = filter.deviceCount() > 1;
     detail::ChunkFeed::Options options;
     options.cannotOpen = "Stream not successful: " + inFile;
@@ -2355,7 +2478,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
     options.uploadFailed = "upload of the FASTQ text failed";
     if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
     detail::ChunkFeed feed(filter.context(0), inFile, options);
-    detail::FastqChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(bytesPerBatch, 64));
+    detail::FastqChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(bytesPerBatch, 64), blocks);
     std::unique_ptr<detail::ChunkRing<detail::FastqChunkSteps>> ring;
     if (dealt) {
         ring.reset(new detail::ChunkRing<detail::FastqChunkSteps>(filter.deviceCount(), 0, steps));
@@ -2373,7 +2496,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
 // is isolated from scoring so a future SAM parser or optional CRAM backend can reuse the same filter").  The rule — lines, header
 // lines, fields, the four checks, "*" sequences and what is written — is stated once in include/teloscan.h above
 // ts_sam_chunk_walk; both routes below follow it, and their output bytes, statistics and exception texts are the same.
-struct SamSubsetStats { uint64_t headerLines = 0, totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0; };
+struct SamSubsetStats { uint64_t headerLines = 0, totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0, blockLines = 0; };   // blockLines: of the read block report
 
 namespace detail {
 inline const char *samErrorText(int error) {
@@ -2440,8 +2563,9 @@ inline void samWalkHost(const char *text, size_t size, bool atEnd, bool inHeader
 // up to readsPerBatch through the filter, as fastqSubset does.  Input may be plain or gzip (both through zlib, which passes plain
 // bytes on as they are); `-` is stdin.
 inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20) {
+                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
     detail::FilterWarmUp warmUp(filter);
+    detail::ReadBlockReport report(blocks, "failed while writing the SAM subset's block report");
     struct Source { gzFile gz = nullptr; ~Source() { if (gz) gzclose(gz); } } src;
     if (inFile == "-") src.gz = gzdopen(0, "rb");
     else {
@@ -2505,8 +2629,14 @@ inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, Re
                 text.append(buf.data() + judged[i]->off, judged[i]->size);
                 text.push_back('\n');
                 ++stats.passedRecords;
+                if (report.on()) {
+                    const char *line = buf.data() + judged[i]->off;
+                    report.add(line, tsrb::sam_name_len(detail::ReadBlockReport::Bytes{line}, 0, judged[i]->seq_at), ptr[i], len[i]);
+                }
             }
             write(text.data(), text.size());
+            report.flush(filter.context(0));
+            stats.blockLines = report.lines;
         }
         if (walk.error != TS_SAM_OK) { out.flush(); throw detail::samLineError(lines + walk.errorLine + 1, walk.error); }
         lines += walk.lines;
@@ -2538,8 +2668,8 @@ public:
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    SamChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes)
-        : feed_(feed), out_(out), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
+    SamChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
+        : feed_(feed), out_(out), blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
         const uint64_t compCap = feed.compCap(chunkBytes);
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
             workers.emplace_back(new Worker());
@@ -2596,6 +2726,8 @@ public:
         Worker &k = *workers[w];
         writeHeader(k);
         k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
+        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
+        stats.blockLines += k.blockLines;
         stats.headerLines += k.headerLines; stats.totalRecords += k.n; stats.passedRecords += k.passed; stats.missingSequenceRecords += k.missing;
         if (k.error != TS_SAM_OK) { out_.flush(); throw samLineError(k.errorLine, k.error); }
     }
@@ -2649,13 +2781,19 @@ private:
             }
             if (k.withSeq.empty()) continue;
             k.st.recordsJudged += k.withSeq.size();
+            if (blocks_ && !k.judged.blockLines)
+                k.judged.blockLines = [&k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+                    return ts_sam_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+                };
             k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
                          [&](ts_batch *batch) { return ts_sam_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
                          [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
                              return ts_sam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
                          });
             k.passed += k.judged.nPassed;
-            if (dealt) k.keep(); else write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes));
+            k.blockLines += k.judged.nBlockLines;
+            if (dealt) k.keep();
+            else { write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
         }
     }
     void writeHeader(Worker &k) {
@@ -2672,6 +2810,7 @@ private:
 
     ChunkFeed &feed_;
     std::ostream &out_;
+    std::ostream *blocks_;                                      // the read block report's stream, or nothing
     size_t readsPerBatch_, chunkBytes_;
     // the framing's state: the chunk framed last and where its unfinished line begins; nothing framed yet held a byte; the input
     // is still in its header; whole lines behind
@@ -2693,7 +2832,7 @@ private:
 // gzip is read through zlib, as for fastqSubsetDevice.  perDevice, where given, receives one entry per context.
 inline SamSubsetStats samSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                       size_t readsPerBatch = 1u << 20, size_t chunkBytes = 256u << 20,
-                                      std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+                                      std::vector<ReadRouteDeviceStats> *perDevice = nullptr, std::ostream *blocks = nullptr) {
     const bool dealt = filter.deviceCount() > 1;
     detail::ChunkFeed::Options options;
     options.cannotOpen = "Stream not successful: " + inFile;
@@ -2702,7 +2841,7 @@ inline SamSubsetStats samSubsetDevice(const std::string &inFile, std::ostream &o
     options.uploadFailed = "upload of the SAM text failed";
     if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
     detail::ChunkFeed feed(filter.context(0), inFile, options);
-    detail::SamChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64));
+    detail::SamChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64), blocks);
     std::unique_ptr<detail::ChunkRing<detail::SamChunkSteps>> ring;
     if (dealt) {
         ring.reset(new detail::ChunkRing<detail::SamChunkSteps>(filter.deviceCount(), 0, steps));

@@ -56,6 +56,10 @@ class Block(C.Structure):
                 ("is_longest", C.c_uint8), ("block_label", C.c_char), ("reserved", C.c_uint8)]
 
 
+class ReadBlock(C.Structure):
+    _fields_ = [("segment", C.c_uint32), ("reserved", C.c_uint32), ("block", Block)]
+
+
 class SegmentIn(C.Structure):
     _fields_ = [("seq", C.c_char_p), ("len", C.c_uint64), ("abs_pos", C.c_uint64),
                 ("tips_only", C.c_uint8), ("input_format", C.c_uint8), ("reserved", C.c_uint8 * 2), ("n_pieces", C.c_uint32)]
@@ -258,6 +262,7 @@ MATCH_DT = np.dtype(Match)
 TILE_DT = np.dtype(TileInfo)
 WINDOW_DT = np.dtype(Window)
 BLOCK_DT = np.dtype(Block)
+READ_BLOCK_DT = np.dtype(ReadBlock)
 
 # every symbol include/teloscan.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -288,6 +293,8 @@ SYMBOLS = [
     "ts_chunk_stage_upload", "ts_chunk_stage_inflate", "ts_chunk_staged", "ts_chunk_commit",
     "ts_bgzf_deflate", "ts_bam_chunk_gather_bgzf", "ts_bgzf_deflate_stats",
     "ts_sam_chunk_walk", "ts_sam_chunk_stage", "ts_sam_chunk_gather",
+    "ts_batch_call_read_blocks", "ts_batch_read_blocks", "ts_fastq_chunk_block_lines", "ts_sam_chunk_block_lines",
+    "ts_bam_chunk_block_lines", "ts_read_block_lines_format", "ts_read_block_text_stats",
 ]
 
 
@@ -529,6 +536,15 @@ def lib():
     L.ts_scan_segments_text.restype = C.c_int
     L.ts_match_text_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ts_match_text_stats.restype = C.c_int
+    L.ts_batch_call_read_blocks.argtypes = [C.c_void_p, C.c_void_p]
+    L.ts_batch_read_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    for name, rec in (("ts_fastq_chunk_block_lines", FastqRecord), ("ts_sam_chunk_block_lines", SamRecord),
+                      ("ts_bam_chunk_block_lines", BamRecord)):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(rec), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_read_block_lines_format.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
+                                             C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.ts_read_block_text_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 

@@ -117,10 +117,14 @@ __device__ __forceinline__ void emit_block(const TsBlockCallParams &Q, TsDevBloc
 // of the side it lies at, ends[2 seg + side] — walkSegment's rule (src/input.cpp:849-853), as reduce_terminal_ends applies it to the
 // emitted blocks: the start side when the block is at most as far from the start as from the end, a tie included.  Which walk found
 // the block does not decide its side.  Again nothing else changes: the other instantiations are the code they were.
-template <int MODE, bool PASS = false, bool ENDS = false>
+// READ (ts_terminal_read_blocks, ts_batch_call_read_blocks): 1 counts — no block is written, the walk's seq says how many it closes
+// —, 2 places — block seq of the walk goes to rows[row_base + seq], a place that the counts of all walks fixed beforehand, so the
+// rows are ordered by (segment, walk, push order) without an atomic.  Once more the other instantiations are the code they were.
+template <int MODE, bool PASS = false, bool ENDS = false, int READ = 0>
 __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, const SegView &V, uint32_t seg, u64 n, u64 abs_pos,
                                   bool from_start, uint32_t &seq, uint32_t lane, bool &out_of_context,
-                                  unsigned char *pass = nullptr, uint32_t *ends = nullptr) {
+                                  unsigned char *pass = nullptr, uint32_t *ends = nullptr,
+                                  TsReadBlockRow *rows = nullptr, u64 row_base = 0, u64 row_cap = 0) {
     u64 boundary = from_start ? 0 : n;                     // segment-relative
     const uint32_t wlen_lane = (MODE == 1 && Q.wide) ? Q.wide_len[lane] : 0u;     // (the table holds 64 entries)
     Chain ch; bool open = false;
@@ -135,7 +139,19 @@ __device__ __forceinline__ u64 terminal_direction(const TsBlockCallParams &Q, co
             cur.has_valid_or = from_start ? (left <= right) : (left >= right);
             boundary = from_start ? cur.start + cur.block_len : cur.start;
             if (lane == 0) {
-                if constexpr (PASS) pass[seg] = 1;
+                if constexpr (READ == 1) {
+                } else if constexpr (READ == 2) {
+                    if (row_base + seq < row_cap) {
+                        TsReadBlockRow r;
+                        r.seg = seg; r.reserved0 = 0u; r.start = cur.start + abs_pos;
+                        r.block_len = cur.block_len; r.block_counts = cur.block_counts; r.forward_count = cur.forward_count;
+                        r.reverse_count = cur.reverse_count; r.canonical_count = cur.canonical_count;
+                        r.non_canonical_count = cur.non_canonical_count; r.total_covered = cur.total_covered;
+                        r.fwd_covered = cur.fwd_covered; r.can_covered = cur.can_covered;
+                        r.has_valid_or = cur.has_valid_or; r.is_longest = cur.is_longest; r.block_label = cur.block_label; r.reserved = 0;
+                        rows[row_base + seq] = r;
+                    }
+                } else if constexpr (PASS) pass[seg] = 1;
                 else if constexpr (ENDS) {
                     const u64 to_end = n - (rel_start + cur.block_len);            // (unsigned, as the host's reduction computes it)
                     atomicMax(&ends[2ull * seg + (rel_start <= to_end ? 0u : 1u)], cur.block_len);
@@ -504,6 +520,47 @@ void ts_terminal_ends_walk(const TsBlockCallParams Q, const TsShardSegIn *segs, 
     } else {
         if (view_has_two(Q, V, 2, true, lane)) terminal_direction<MODE, false, true>(Q, V, si, S.len, S.abs_pos, false, seq, lane, ooc, nullptr, ends);
     }
+}
+
+// ts_terminal_read_blocks: the same two walks, one wave each, in their READ forms.  Counting (READ 1): word 0 of counts entry
+// 2 segment + walk = the blocks the walk closes (16 bytes per entry, a tile directory's layout: exchange.hip's sums place them).
+// Placing (READ 2): the walk's blocks to rows[places[2 segment + walk] + push order]; the forward walk's wave also notes where
+// its segment's rows begin, the last segment's reverse wave the total.  *overflow (a tiled batch: the scan overflowed a wave's
+// region, ts_read_blocks_guard) — no walk runs: the counts stay zero, as the caller left them, and there are no rows.
+template <int MODE, int READ>
+__global__ __launch_bounds__(kSideWg)
+void ts_terminal_read_blocks(const TsBlockCallParams Q, const TsShardSegIn *segs, uint32_t nseg, const uint32_t *overflow,
+                             uint32_t *counts, const u64 *places, u64 *first, TsReadBlockRow *rows, u64 row_cap) {
+    const uint32_t si = blockIdx.x >> 1;
+    if (si >= nseg) return;
+    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x & 1u;
+    if (READ == 2 && first && lane == 0u) {
+        if (wave == 0u) first[si] = places[2ull * si];
+        else if (si + 1u == nseg) first[nseg] = places[2ull * nseg];
+    }
+    if (overflow && *overflow) return;
+    const TsShardSegIn S = segs[si];
+    const SegView V = seg_view(Q, S);
+    uint32_t seq = 0;
+    bool ooc = false;
+    const u64 base = READ == 2 ? places[2ull * si + wave] : 0ull;
+    if (wave == 0) {
+        if (view_has_two(Q, V, 1, false, lane))
+            terminal_direction<MODE, false, false, READ>(Q, V, si, S.len, S.abs_pos, true, seq, lane, ooc, nullptr, nullptr, rows, base, row_cap);
+    } else {
+        if (view_has_two(Q, V, 2, true, lane))
+            terminal_direction<MODE, false, false, READ>(Q, V, si, S.len, S.abs_pos, false, seq, lane, ooc, nullptr, nullptr, rows, base, row_cap);
+    }
+    if (READ == 1 && lane == 0u) counts[4ull * (2ull * si + wave)] = seq;
+}
+
+// Raises *flag (sticky) when a wave of the scan needed more records than its region holds (predicate.hip's guard, for the walks
+// above: the directory then promises records that were never stored).
+__global__ void ts_read_blocks_guard(const uint32_t *wave_fill, uint32_t region_cap, uint32_t nwaves, uint32_t *flag) {
+    bool over = false;
+    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < nwaves; w += gridDim.x * blockDim.x)
+        over |= wave_fill[w] > region_cap;
+    if (over) atomicOr(flag, 1u);
 }
 
 // computeBlockLabel, include/teloscope.h:217-222
@@ -1146,6 +1203,49 @@ int ts_k_launch_terminal_ends_general(const TsBlockCallParams *Q, const TsShardS
         hipLaunchKernelGGL(ts_terminal_ends_walk<1>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, ends);
     else
         hipLaunchKernelGGL(ts_terminal_ends_walk<0>, dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, ends);
+    return (int)hipGetLastError();
+}
+
+// The ordered rows of ts_batch_call_read_blocks (ts_internal.h says what the arguments hold): guard or slot counts, the counting
+// walks, exchange.hip's three-pass sums over the 2 nseg counts, the placing walks.  Everything on `stream`, nothing comes back.
+int ts_k_launch_read_blocks_place(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, const uint32_t *overflow,
+                                  const unsigned long long *places, TsReadBlockRow *rows, unsigned long long row_cap, void *stream) {
+    if (nseg == 0) return 0;
+    if (Q->wide)
+        hipLaunchKernelGGL((ts_terminal_read_blocks<1, 2>), dim3(2u * nseg), dim3(kSideWg), 0, (hipStream_t)stream, *Q, segs, nseg, overflow,
+                           (uint32_t *)nullptr, (const u64 *)places, (u64 *)nullptr, rows, (u64)row_cap);
+    else
+        hipLaunchKernelGGL((ts_terminal_read_blocks<0, 2>), dim3(2u * nseg), dim3(kSideWg), 0, (hipStream_t)stream, *Q, segs, nseg, overflow,
+                           (uint32_t *)nullptr, (const u64 *)places, (u64 *)nullptr, rows, (u64)row_cap);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_read_blocks(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
+                            uint32_t *tile_stats, const uint32_t *wave_fill, uint32_t region_cap, uint32_t nwaves, uint32_t *overflow,
+                            uint32_t *counts, unsigned long long *places, unsigned long long *first, void *tmp, TsReadBlockRow *rows,
+                            unsigned long long row_cap, void *stream) {
+    if (nseg == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)nseg * 32, st);
+    if (e != hipSuccess) return (int)e;
+    if (wave_fill) hipLaunchKernelGGL(ts_read_blocks_guard, dim3(8), dim3(256), 0, st, wave_fill, region_cap, nwaves, overflow);
+    if (slot_cap && ntiles) hipLaunchKernelGGL(ts_slot_counts, dim3(ntiles), dim3(kSideWg), 0, st, Q->matches, slot_cap, ntiles, tile_stats);
+    const uint32_t *const flag = wave_fill ? overflow : nullptr;
+    // (a batch without tiles: every segment's view is empty and no walk reads a record)
+    if (Q->wide)
+        hipLaunchKernelGGL((ts_terminal_read_blocks<1, 1>), dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, flag, counts,
+                           (const u64 *)nullptr, (u64 *)nullptr, (TsReadBlockRow *)nullptr, (u64)0);
+    else
+        hipLaunchKernelGGL((ts_terminal_read_blocks<0, 1>), dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, flag, counts,
+                           (const u64 *)nullptr, (u64 *)nullptr, (TsReadBlockRow *)nullptr, (u64)0);
+    const int rc = ts_k_launch_tile_offsets(counts, 2u * nseg, places, tmp, stream);
+    if (rc != 0) return rc;
+    if (Q->wide)
+        hipLaunchKernelGGL((ts_terminal_read_blocks<1, 2>), dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, flag,
+                           (uint32_t *)nullptr, (const u64 *)places, (u64 *)first, rows, (u64)row_cap);
+    else
+        hipLaunchKernelGGL((ts_terminal_read_blocks<0, 2>), dim3(2u * nseg), dim3(kSideWg), 0, st, *Q, segs, nseg, flag,
+                           (uint32_t *)nullptr, (const u64 *)places, (u64 *)first, rows, (u64)row_cap);
     return (int)hipGetLastError();
 }
 

@@ -934,7 +934,8 @@ void ts_batch_destroy(ts_batch *b) {
         if (b->gen) ts_general_batch_release(b);
         for (DevBuf *d : {&b->d_in, &b->d_tiles, &b->d_windows, &b->d_matches, &b->d_tile_off, &b->d_stats, &b->d_fill, &b->d_tickets,
                           &b->d_segtab, &b->d_dense, &b->d_dense_base, &b->d_scan_tmp, &b->d_readtab, &b->d_shard_segs,
-                          &b->d_shard_bounds, &b->d_shard_tmp, &b->d_shard_cand, &b->d_vis, &b->d_chain, &b->d_zone})
+                          &b->d_shard_bounds, &b->d_shard_tmp, &b->d_shard_cand, &b->d_vis, &b->d_chain, &b->d_zone, &b->rb.d_tab, &b->rb.d_rows,
+                          &b->rb.d_segin})
             c->pool.give(std::move(*d));
         for (hipEvent_t e : b->evs)
             if (e) (void)hipEventDestroy(e);
@@ -1054,6 +1055,7 @@ int ts_batch_scan(ts_batch *b, const void *d_input, void *stream) {
     b->last_stream = stream;
     b->scanned = true;
     b->synced = false;
+    b->rb.called = false;
 
     // The device sees the range's slice of every array; tile descriptors carry offsets of the WHOLE plan
     // (in_off into the input layout, win_out into the window array), so those two base pointers are shifted

@@ -172,6 +172,8 @@ struct ts_ctx {
     std::atomic<uint64_t> upload_stats[8] = {};
     // ts_match_text_stats: formatting calls, canonical lines, non-canonical lines, text bytes — since ts_create
     std::atomic<uint64_t> match_text_stats[4] = {};
+    // ts_read_block_text_stats: formatting calls that reached the device, lines, text bytes — since ts_create
+    std::atomic<uint64_t> read_block_text_stats[3] = {};
     // ts_gzip_stats: windows, spans probed, spans chained, spans dropped, plain bytes produced, parts the caller handed to zlib — since ts_create
     std::atomic<uint64_t> gzip_stats[6] = {};
     // ts_bam_index_stats: calls, spans the chain entered, spans whose entry was a candidate row, spans settled by the serial
@@ -249,6 +251,22 @@ struct TsGeneralBatch {
     size_t tab_flag = 0;                // byte offset of the fused pass's flag word in d_tab
 };
 
+// What ts_batch_call_read_blocks leaves in a tips batch, tiled or general: the walks' tables — 2 n x 16 bytes of counts, 2 n + 1
+// places, n + 1 first-row indices, the sums' scratch — the rows (room for row_cap of them), and, for a tiled batch, the walks'
+// segment table (a general tips batch has its own).  `called`: the rows describe the batch's latest scan.
+struct ReadBlocksTab {
+    size_t places, first, tmp, bytes;
+    explicit ReadBlocksTab(size_t ns) : places(ns * 32), first(places + (((2 * ns + 1) * 8 + 15) & ~(size_t)15)), tmp(first + (((ns + 1) * 8 + 15) & ~(size_t)15)),
+                                        bytes(tmp + (size_t)ts_k_scan_tmp_bytes((uint32_t)(2 * ns)) + 16) {}
+};
+struct ReadBlocksState {
+    DevBuf d_tab, d_rows, d_segin;
+    uint64_t row_cap = 0;
+    bool called = false;                // the rows describe the batch's latest scan
+    bool clean = false;                 // ... and ts_batch_read_pass_status has said since that nothing overflowed
+    void *stream = nullptr;
+};
+
 // A batch is a PLAN over all its segments (tiles, window records, input layout) plus the device state of
 // the tile range [tile_lo, tile_hi) it executes: the whole plan by default, one rank's shard after
 // ts_batch_restrict, or — on the rank that assembles — results produced elsewhere (ts_batch_adopt).
@@ -296,6 +314,7 @@ struct ts_batch {
     uint32_t *ext_windows = nullptr, *ext_stats = nullptr;
     const uint32_t *ext_dense = nullptr;
     uint32_t total_waves = 0, region_cap = 0;
+    ReadBlocksState rb;                     // ts_batch_call_read_blocks
     bool all_terminal = false;              // (set with d_readtab) no segment longer than the terminal limit
     bool dealt_tiles = false;               // tiles dealt round-robin instead of taken on demand (see ts_batch_scan)
     uint64_t ticket_seq = 0;                // launches with on-demand tiles so far: parity = the ticket counter in use
@@ -453,10 +472,15 @@ int  ts_general_batch_read_pass(ts_batch *b, void *d_pass, void *stream);
 int  ts_general_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream);
 int  ts_general_batch_download_blocks(ts_batch *b, ts_segment_out *out);
 int  ts_general_batch_segment_summary(ts_batch *b, void *d_out, void *stream);
+int  ts_general_batch_call_read_blocks(ts_batch *b, void *stream);
+int  ts_general_batch_place_read_blocks(ts_batch *b);            // the placing walks again, into b->rb.d_rows as it is now
 int  ts_general_batch_status(ts_batch *b, int *overflowed);
 int  ts_general_batch_sync(ts_batch *b);
 int  ts_general_batch_refuse(const ts_batch *b, const char *call);     // TS_ERR_UNSUPPORTED, the call named in ts_last_error
 
+// pipeline.cpp: after ts_batch_call_read_blocks — waits for its stream, *n_rows = the rows it called; when they are more than the
+// buffer held, the buffer is grown and the placing walks run again (same places, same rows).  Then b->rb.d_rows holds them all.
+int  ts_batch_settle_read_blocks(ts_batch *b, uint64_t *n_rows);
 int  ts_batch_ensure_device(ts_batch *b);        // allocates the range's device state (idempotent)
 // block calling on the device over a resident match stream + tile directory (a batch's, or the general kernels' dense stream)
 int  ts_device_block_call_raw(ts_ctx *c, const TsTile *d_tiles, const unsigned long long *d_tile_off, const uint32_t *d_stats,

@@ -69,6 +69,9 @@ struct ts_bam_chunk {
     // ---- SAM (sam.cpp): the tab counts per slice and the tabs' offsets, the alignment lines per slice of lines, the walk's
     // result block of 64 bytes; the stage's jobs
     struct Sam { DevBuf d_counts, d_tabs, d_frames, d_out, d_jobs; } sam;
+    // ---- the read block report (read_blocks.cpp): the record table of a *_block_lines call, the segments' name entries, the
+    // workgroups' sums and the text
+    struct Blocks { DevBuf d_recs, d_segs, d_sums, d_text; } blocks;
 };
 
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length

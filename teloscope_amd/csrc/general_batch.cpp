@@ -197,6 +197,7 @@ int ts_general_batch_scan(ts_batch *b, const void *d_input, void *stream) {
     b->last_stream = stream;
     b->scanned = true;
     b->synced = false;
+    b->rb.called = false;
     char *const dt = (char *)g.d_tab.p;
     const unsigned long long *const tab_len = (const unsigned long long *)dt, *const tab_win = tab_len + ns, *const tab_nwin = tab_len + 2 * ns;
     uint32_t *const d_flag = (uint32_t *)(dt + g.tab_flag);
@@ -247,6 +248,41 @@ int ts_general_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream) {
                                           (uint32_t *)g.d_stats.p, (uint32_t *)d_ends, stream) != 0)
         return c->fail(TS_ERR_HIP, "general terminal-ends kernel launch failed");
     c->terminal_ends_stats[1].fetch_add(b->segs.size(), std::memory_order_relaxed);
+    return TS_OK;
+}
+
+// The terminal blocks of every segment as ordered rows in the batch's device memory (ts_batch_call_read_blocks, which made the
+// tables and the rows' room): the same walks in their counting and placing forms, on the scan's stream.  After an overflow or a
+// spill the rows mean nothing, as the pass bytes do; the walks stay inside the slots and the rows' room.
+int ts_general_batch_call_read_blocks(ts_batch *b, void *stream) {
+    ts_ctx *c = b->ctx;
+    TsGeneralBatch &g = *b->gen;
+    ReadBlocksState &R = b->rb;
+    if (!b->scanned) return c->fail(TS_ERR_STATE, "ts_batch_call_read_blocks needs a scanned, unrestricted tips-only batch");
+    if (stream != b->last_stream) return c->fail(TS_ERR_STATE, "ts_batch_call_read_blocks on a general tips batch: pass the stream of its scan");
+    R.called = false;
+    const size_t ns = b->segs.size();
+    if (ns) {
+        const TsBlockCallParams Q = walk_params(b);
+        const ReadBlocksTab T(ns);
+        char *const dt = (char *)R.d_tab.p;
+        if (ts_k_launch_read_blocks(&Q, (const TsShardSegIn *)g.d_segin.p, (uint32_t)ns, (uint32_t)g.tiles.size(), g.slot_cap, (uint32_t *)g.d_stats.p,
+                                    nullptr, 0u, 0u, nullptr, (uint32_t *)dt, (unsigned long long *)(dt + T.places),
+                                    (unsigned long long *)(dt + T.first), dt + T.tmp, (TsReadBlockRow *)R.d_rows.p, R.row_cap, stream) != 0)
+            return c->fail(TS_ERR_HIP, "general read-block kernel launch failed");
+    }
+    R.called = true; R.stream = stream;
+    return TS_OK;
+}
+
+int ts_general_batch_place_read_blocks(ts_batch *b) {
+    ts_ctx *c = b->ctx;
+    const ReadBlocksState &R = b->rb;
+    const TsBlockCallParams Q = walk_params(b);
+    if (ts_k_launch_read_blocks_place(&Q, (const TsShardSegIn *)b->gen->d_segin.p, (uint32_t)b->segs.size(), nullptr,
+                                      (const unsigned long long *)((char *)R.d_tab.p + ReadBlocksTab(b->segs.size()).places),
+                                      (TsReadBlockRow *)R.d_rows.p, R.row_cap, R.stream) != 0)
+        return c->fail(TS_ERR_HIP, "general read-block kernel launch failed");
     return TS_OK;
 }
 

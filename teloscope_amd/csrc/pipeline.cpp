@@ -640,15 +640,10 @@ struct ReadTab {
                                   count((long_list + ns * 4 + 15) & ~(size_t)15), flag(count + 16), bytes(flag + 16) {}
 };
 
-// The terminal-block predicate of a scanned tips batch on the device: one byte per read
-// (ReadTelomereFilter::matches, src/read-filter.cpp:37-45, reduced to !terminalBlocks.empty()), written to
-// d_pass (device).  The per-read table the kernel walks is built once per batch.
-// d_ends (instead of a predicate): the same walks reduced to the longest terminal block per side, two u32 per segment
-// (ts_terminal_ends); the overflow flag is then left for the caller to read.
-int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, uint32_t *d_ends = nullptr) {
+// the per-read table of a tips batch (ReadTab), built and uploaded once per batch
+int ensure_readtab(ts_batch *b, hipStream_t st) {
     ts_ctx *c = b->ctx;
     const size_t ns = b->segs.size();
-    if (!ns) return TS_OK;
     const ReadTab T(ns);
     if (!b->d_readtab.p) {
         std::vector<char> tab(T.bytes);
@@ -664,6 +659,20 @@ int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, u
         HIP_TRY(c, hipMemcpyAsync(b->d_readtab.p, tab.data(), T.bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipStreamSynchronize(st));                    // (tab is a local)
     }
+    return TS_OK;
+}
+
+// The terminal-block predicate of a scanned tips batch on the device: one byte per read
+// (ReadTelomereFilter::matches, src/read-filter.cpp:37-45, reduced to !terminalBlocks.empty()), written to
+// d_pass (device).  The per-read table the kernel walks is built once per batch.
+// d_ends (instead of a predicate): the same walks reduced to the longest terminal block per side, two u32 per segment
+// (ts_terminal_ends); the overflow flag is then left for the caller to read.
+int batch_read_pass_device(ts_batch *b, unsigned char *d_pass, hipStream_t st, uint32_t *d_ends = nullptr) {
+    ts_ctx *c = b->ctx;
+    const size_t ns = b->segs.size();
+    if (!ns) return TS_OK;
+    const ReadTab T(ns);
+    { const int rc = ensure_readtab(b, st); if (rc != TS_OK) return rc; }
     char *const dt = (char *)b->d_readtab.p;
     TsPredParams Q{};
     Q.terminal_limit = c->params.terminal_limit;
@@ -1687,6 +1696,70 @@ int ts_pipeline_upload_batch(ts_batch *b, const ts_segment_in *segs, int *slot, 
     return upload_batch(b, items.data(), *slot, used);
 }
 
+// ---- ts_batch_call_read_blocks' helpers (the entry points are below, with ts_batch_read_pass)
+namespace {
+
+// what the terminal walks of blockcall.hip read of a tiled tips batch (device_block_call's view, capi.cpp)
+TsBlockCallParams tiled_walk_params(const ts_batch *b) {
+    const ts_ctx *c = b->ctx;
+    const ts_params &P = c->params;
+    TsBlockCallParams Q{};
+    Q.tiles = (const TsTile *)b->d_tiles.p;
+    Q.tile_off = (const unsigned long long *)b->d_tile_off.p;
+    Q.tile_stats = b->stats_ptr();
+    Q.matches = b->records_ptr();
+    Q.terminal_limit = P.terminal_limit; Q.max_match_dist = P.max_match_dist;
+    Q.min_block_len = P.min_block_len; Q.max_block_dist = P.max_block_dist;
+    Q.min_block_counts = P.min_block_counts; Q.min_block_density = P.min_block_density;
+    Q.k = c->k;
+    Q.rec16 = b->records16() ? 1u : 0u;
+    return Q;
+}
+
+// the rows' room: what the batch held before, or a few blocks per read to begin with
+int ensure_read_block_rows(ts_batch *b, uint64_t rows) {
+    ts_ctx *c = b->ctx;
+    ReadBlocksState &R = b->rb;
+    if (R.d_rows.p && R.row_cap >= rows) return TS_OK;
+    c->pool.give(std::move(R.d_rows));
+    R.row_cap = 0;
+    HIP_TRY(c, c->pool.take((size_t)rows * sizeof(TsReadBlockRow), R.d_rows));
+    R.row_cap = rows;
+    return TS_OK;
+}
+
+}  // namespace
+
+int ts_batch_settle_read_blocks(ts_batch *b, uint64_t *n_rows) {
+    ts_ctx *c = b->ctx;
+    ReadBlocksState &R = b->rb;
+    *n_rows = 0;
+    if (!R.called) return c->fail(TS_ERR_STATE, "the batch's read blocks were not called since its last scan (ts_batch_call_read_blocks)");
+    if (!R.clean) return c->fail(TS_ERR_STATE, "the batch's read blocks: ts_batch_read_pass_status has not said since the call that nothing overflowed");
+    const size_t ns = b->segs.size();
+    if (!ns) return TS_OK;
+    hipStream_t st = (hipStream_t)R.stream;
+    const ReadBlocksTab T(ns);
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, (char *)R.d_tab.p + T.first + ns * 8, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (total > R.row_cap) {
+        { const int rc = ensure_read_block_rows(b, total + total / 4); if (rc != TS_OK) return rc; }
+        if (b->gen) { const int rc = ts_general_batch_place_read_blocks(b); if (rc != TS_OK) return rc; }
+        else {
+            const TsBlockCallParams Q = tiled_walk_params(b);
+            const uint32_t *const flag = b->dense ? nullptr : (const uint32_t *)((char *)b->d_readtab.p + ReadTab(ns).flag);
+            if (ts_k_launch_read_blocks_place(&Q, (const TsShardSegIn *)R.d_segin.p, (uint32_t)ns, flag,
+                                              (const unsigned long long *)((char *)R.d_tab.p + T.places), (TsReadBlockRow *)R.d_rows.p,
+                                              R.row_cap, R.stream) != 0)
+                return c->fail(TS_ERR_HIP, "read-block kernel launch failed");
+        }
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    *n_rows = total;
+    return TS_OK;
+}
+
 // =========================================================================== scanSegment, batched
 extern "C" {
 
@@ -1811,9 +1884,74 @@ int ts_batch_terminal_ends(ts_batch *b, void *d_ends, void *stream) {
     return rc;
 }
 
+// The terminal blocks of a device-resident tips-only batch as ordered rows in its own device memory (blockcall.hip's walks in
+// their counting and placing forms); asynchronous.  A tiled batch here, a general tips batch in general_batch.cpp.
+int ts_batch_call_read_blocks(ts_batch *b, void *stream) {
+    if (!b) return TS_ERR_INVALID_ARG;
+    ts_ctx *c = b->ctx;
+    if (!b->tips) return c->fail(TS_ERR_INVALID_ARG, "ts_batch_call_read_blocks needs a tips-only batch");
+    DEVICE_TRY(c);
+    ReadBlocksState &R = b->rb;
+    const size_t ns = b->segs.size();
+    if (ns >= 0x3FFFFFFFull) return c->fail(TS_ERR_UNSUPPORTED, "ts_batch_call_read_blocks: too many segments in one batch");
+    if (!b->scanned || (!b->gen && !b->whole())) return c->fail(TS_ERR_STATE, "ts_batch_call_read_blocks needs a scanned, unrestricted tips-only batch");
+    if (b->gen && stream != b->last_stream) return c->fail(TS_ERR_STATE, "ts_batch_call_read_blocks on a general tips batch: pass the stream of its scan");
+    R.called = R.clean = false;
+    if (!R.d_tab.p) HIP_TRY(c, c->pool.take(ReadBlocksTab(ns).bytes, R.d_tab));
+    { const int rc = ensure_read_block_rows(b, std::max<uint64_t>(R.row_cap, 2 * (uint64_t)ns + 1024)); if (rc != TS_OK) return rc; }
+    if (b->gen) return ts_general_batch_call_read_blocks(b, stream);
+    if (!ns) { R.called = true; R.stream = stream; return TS_OK; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int rc = ensure_readtab(b, st); if (rc != TS_OK) return rc; }
+    if (!R.d_segin.p) {
+        std::vector<TsShardSegIn> tab(ns);
+        for (size_t i = 0; i < ns; ++i) {
+            TsShardSegIn &S = tab[i];
+            S = TsShardSegIn{};
+            S.in_off = b->segs[i].in_off; S.len = b->segs[i].len; S.abs_pos = b->segs[i].abs_pos;
+            S.t0 = S.o0 = b->segs[i].first_tile;
+            S.t1 = S.o1 = b->segs[i].first_tile + b->segs[i].n_tiles;
+            S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
+            S.lo_rel = 0; S.hi_rel = b->segs[i].len;
+            S.seg = (uint32_t)i;
+        }
+        HIP_TRY(c, c->pool.take(ns * sizeof(TsShardSegIn), R.d_segin));
+        HIP_TRY(c, hipMemcpyAsync(R.d_segin.p, tab.data(), ns * sizeof(TsShardSegIn), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipStreamSynchronize(st));                    // (tab is a local)
+    }
+    const TsBlockCallParams Q = tiled_walk_params(b);
+    const ReadBlocksTab T(ns);
+    char *const dt = (char *)R.d_tab.p;
+    uint32_t *const flag = (uint32_t *)((char *)b->d_readtab.p + ReadTab(ns).flag);
+    if (ts_k_launch_read_blocks(&Q, (const TsShardSegIn *)R.d_segin.p, (uint32_t)ns, (uint32_t)b->tiles.size(), 0u, nullptr,
+                                b->dense ? nullptr : (const uint32_t *)b->d_fill.p, b->region_cap, b->total_waves, flag, (uint32_t *)dt,
+                                (unsigned long long *)(dt + T.places), (unsigned long long *)(dt + T.first), dt + T.tmp,
+                                (TsReadBlockRow *)R.d_rows.p, R.row_cap, stream) != 0)
+        return c->fail(TS_ERR_HIP, "read-block kernel launch failed");
+    R.called = true; R.stream = stream;
+    return TS_OK;
+}
+
+int ts_batch_read_blocks(ts_batch *b, ts_read_block *out, uint64_t cap, uint64_t *n) {
+    if (!b || !n || (cap && !out)) return TS_ERR_INVALID_ARG;
+    ts_ctx *c = b->ctx;
+    static_assert(sizeof(ts_read_block) == sizeof(TsReadBlockRow) && offsetof(ts_read_block, block) == offsetof(TsReadBlockRow, start) &&
+                  offsetof(ts_block, block_label) + offsetof(ts_read_block, block) == offsetof(TsReadBlockRow, block_label),
+                  "a TsReadBlockRow is a ts_read_block");
+    DEVICE_TRY(c);
+    { const int rc = ts_batch_settle_read_blocks(b, n); if (rc != TS_OK) return rc; }
+    if (*n > cap) return c->fail(TS_ERR_INVALID_ARG, "ts_batch_read_blocks: out is too small (*n says what is needed)");
+    if (*n) HIP_TRY(c, hipMemcpy(out, b->rb.d_rows.p, (size_t)*n * sizeof(ts_read_block), hipMemcpyDeviceToHost));
+    return TS_OK;
+}
+
 int ts_batch_read_pass_status(ts_batch *b, int *overflowed) {
     if (!b || !overflowed) return TS_ERR_INVALID_ARG;
-    if (b->gen) return ts_general_batch_status(b, overflowed);
+    if (b->gen) {
+        const int rc = ts_general_batch_status(b, overflowed);
+        if (rc == TS_OK && !*overflowed) b->rb.clean = true;     // (rows called since the scan may be read)
+        return rc;
+    }
     ts_ctx *c = b->ctx;
     DEVICE_TRY(c);
     *overflowed = 0;
@@ -1824,6 +1962,7 @@ int ts_batch_read_pass_status(ts_batch *b, int *overflowed) {
     HIP_TRY(c, hipMemcpy(&flag, flag_at, 4, hipMemcpyDeviceToHost));
     if (flag) HIP_TRY(c, hipMemset(flag_at, 0, 4));
     *overflowed = flag ? 1 : 0;
+    if (!flag) b->rb.clean = true;                                // (rows called since the scan may be read)
     return TS_OK;
 }
 

@@ -129,6 +129,18 @@ struct TsDevBlock {                     // ts_block (include/teloscan.h) + bookk
     uint32_t pad;
 };
 
+// One row of a batch's ordered terminal blocks (ts_batch_call_read_blocks): ts_read_block of include/teloscan.h, 56 bytes — the
+// segment, then the block as a TsDevBlock begins
+struct TsReadBlockRow {
+    uint32_t seg, reserved0;
+    unsigned long long start;
+    uint32_t block_len, block_counts, forward_count, reverse_count, canonical_count, non_canonical_count;
+    uint32_t total_covered, fwd_covered, can_covered;
+    uint8_t  has_valid_or, is_longest;
+    char     block_label;
+    uint8_t  reserved;
+};
+
 struct TsBlockCallParams {
     const TsTile *tiles;
     const unsigned long long *tile_off;
@@ -373,6 +385,20 @@ int  ts_k_launch_read_pass_general(const TsBlockCallParams *Q, const TsShardSegI
 // end side of segment i (zeroed here).  tile_stats == nullptr: the directory's canonical / forward counts are already there
 int  ts_k_launch_terminal_ends_general(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
                                        uint32_t *tile_stats, uint32_t *ends, void *stream);
+// The same walks in their counting and placing forms (ts_batch_call_read_blocks): the terminal blocks of every segment as rows in
+// device memory, ordered by (segment, walk, push order).  tab: 2 nseg x 16 bytes of counts (word 0 of entry 2 i + w: the blocks
+// walk w of segment i closes), places: 2 nseg + 1 x u64 (their exclusive sums, the total behind them), first: nseg + 1 x u64 (the
+// index of every segment's first row, the total behind them), tmp: ts_k_scan_tmp_bytes(2 nseg) bytes.  rows: room for row_cap rows;
+// a row beyond it is not written (first[nseg] > row_cap says so: ts_k_launch_read_blocks_place places again into a larger
+// buffer from the same places).  wave_fill != nullptr (a tiled batch): *overflow is raised when a wave's region overflowed in the
+// scan, and then no walk runs and there are no rows; slot_cap != 0 (a general tips batch): the directory's counts are completed
+// first, as for the read pass.
+int  ts_k_launch_read_blocks(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, uint32_t ntiles, uint32_t slot_cap,
+                             uint32_t *tile_stats, const uint32_t *wave_fill, uint32_t region_cap, uint32_t nwaves, uint32_t *overflow,
+                             uint32_t *counts, unsigned long long *places, unsigned long long *first, void *tmp, TsReadBlockRow *rows,
+                             unsigned long long row_cap, void *stream);
+int  ts_k_launch_read_blocks_place(const TsBlockCallParams *Q, const TsShardSegIn *segs, uint32_t nseg, const uint32_t *overflow,
+                                   const unsigned long long *places, TsReadBlockRow *rows, unsigned long long row_cap, void *stream);
 // the directory's counts alone (ts_slot_counts), for block calling over a general tips batch's slots
 int  ts_k_launch_slot_counts(const uint32_t *records, uint32_t slot_cap, uint32_t ntiles, uint32_t *tile_stats, void *stream);
 // per-segment totals into sums (5 x u64 per segment) or into the segments' entries of a shard's message (seg_out)
@@ -440,6 +466,27 @@ int  ts_k_launch_track_pick(const uint32_t *records, const unsigned long long *i
 // ts_track_scan_blocks by itself: n_columns columns of n_blocks + 1 values each — a column's n_blocks sums become their exclusive
 // 64-bit prefix sums, its last entry their total
 int  ts_k_launch_scan_columns(unsigned long long *sums, uint32_t n_columns, uint32_t n_blocks, void *stream);
+// read_blocks.hip: the read block report as text (read_block_format_core.h).  A segment's entry says where its read's name lies in
+// `names` (the chunk, or an uploaded buffer) and how many bases were judged; a workgroup of one wave formats 64 rows.  sums holds
+// two columns of n_blocks + 1 values: after ts_k_launch_read_block_count the exclusive prefix sums of the workgroups' bytes and of
+// their line counts, each column's total behind it.
+struct TsReadBlockSeg { unsigned long long name_off; uint32_t name_len, read_len; };
+struct TsReadBlockTextParams {
+    const TsReadBlockRow *rows;
+    const TsReadBlockSeg *segs;
+    const void *names;
+    unsigned long long *sums;
+    void *out;
+    unsigned long long n_rows;
+    uint32_t n_segs;
+};
+#define TS_READ_BLOCK_FASTQ 0u
+#define TS_READ_BLOCK_SAM   1u
+#define TS_READ_BLOCK_BAM   2u
+// segs[i] from entry i of a chunk's record table (ts_fastq_record / ts_sam_record / ts_bam_record by `kind`, device memory)
+int  ts_k_launch_read_block_names(const void *recs, uint32_t n, uint32_t kind, const void *chunk, TsReadBlockSeg *segs, void *stream);
+int  ts_k_launch_read_block_count(const TsReadBlockTextParams *P, uint32_t n_blocks, void *stream);
+int  ts_k_launch_read_block_write(const TsReadBlockTextParams *P, uint32_t n_blocks, void *stream);
 // match_text.hip: the two match files as text (match_format_core.h: tsmatch::Segment).  A workgroup of one wave formats one tile
 // of the record stream's directory.  sums holds 4 x (n_tiles + 1) values — per tile the bytes of the canonical and of the
 // non-canonical file and their line counts; after ts_k_launch_match_count their exclusive prefix sums with the totals behind
