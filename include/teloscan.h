@@ -1057,6 +1057,47 @@ int ts_read_block_lines_format(ts_ctx *ctx, const ts_read_block *rows, uint64_t 
  * lines, out[2] text bytes the device formatted since ts_create.  Cumulative, monotonic, atomic, like ts_match_text_stats. */
 int ts_read_block_text_stats(const ts_ctx *ctx, uint64_t out[3]);
 
+/* ---- FASTQ out of the BAM and SAM subsets: the kept records of --bam-subset and --sam-subset as FASTQ text instead of the
+ *      format they were read in (include/teloscope_mi355x_io.hpp: bamSubsetFastq, samSubsetFastq and their device forms), formatted
+ *      where a sub-batch's reads were judged, in place of the verbatim gather (ts_bam_chunk_gather, ts_sam_chunk_gather).  The
+ *      reference writes a subset in the format it read (subsetBam, src/bam.cpp:188-259) and FASTQ only from FASTQ
+ *      (appendFastqRecord, src/input.cpp:140-149; docs/algorithm.md: "the output can be piped straight into a mapper"); it has
+ *      no conversion.  The rule is this project's own, stated here and nowhere else, and every route follows it:
+ *        - For every kept record, in output order, four lines that always end in '\n' and never in '\r':
+ *            '@' name '\n'  bases '\n'  '+' '\n'  quals '\n'
+ *        - name is the read block report's name for the same front end: for BAM read_name without its NUL, for SAM the bytes
+ *          in front of the first tab.  It may be empty.  No /1 or /2 suffix is ever added.
+ *        - L is the number of bases judged: l_seq for BAM, SEQ's length for SAM.  A kept record has L >= 1.
+ *        - Stored bases b[0..L): for BAM "=ACMGRSVTWYHKDBN"[code]; for SAM SEQ's bytes as they lie, with no case folding.
+ *        - Stored quals q[0..L): for BAM min(byte, 93) + 33, and QUAL is missing when its first byte is 0xFF; for SAM QUAL's
+ *          bytes as they lie, and QUAL is missing when field 11 is exactly "*" (for L == 1 too).  Missing QUAL is written as
+ *          L times '!'.
+ *        - FLAG: for BAM the little-endian 16-bit word 18 bytes behind the record's block_size field; for SAM the decimal
+ *          value of the leading digits of field 2, of which at most nine are read; no leading digit means 0.
+ *        - reverse is true when the caller asked for the read's own strand (TS_FASTQ_OUT_RESTORE_STRAND) and FLAG & 0x10 is
+ *          set.  Without reverse bases = b and quals = q; with it bases[j] = comp(b[L-1-j]) and quals[j] = q[L-1-j].
+ *        - comp: for BAM the letter of the 4-bit code with its four bits reversed (A<->T, C<->G, M<->K, R<->Y, V<->B, H<->D;
+ *          '=', S, W and N stay); for SAM the same pairs on letters of either case, case kept, U and u go to A and a, and
+ *          every other byte is unchanged.
+ *        - The judgement does not change: the filter judges the stored SEQ, and a record is kept exactly when the verbatim
+ *          subset keeps it.  Secondary and supplementary records are records like any other: a caller who wants primaries
+ *          only filters upstream.
+ *        - A read block report written beside this output stays in stored-SEQ coordinates, whatever the orientation of the text.
+ *        - No BAM header, EOF member or SAM header line is written. */
+#define TS_FASTQ_OUT_RESTORE_STRAND 1u
+/* ts_bam_chunk_gather / ts_sam_chunk_gather with the text above in place of the records' own bytes: recs, n and d_pass are those
+ * calls' arguments, `flags` is 0 or TS_FASTQ_OUT_RESTORE_STRAND (any other bit: TS_ERR_INVALID_ARG).  The text of the records
+ * whose pass byte is set, in input order, to host_out; *bytes and *n_passed say how much.  When *bytes > cap nothing is copied
+ * and the call answers TS_ERR_INVALID_ARG (call again with room for *bytes).  A lane per record sizes its text, prefix sums place
+ * it and cut it into pieces, a wave per piece writes 16 bytes per lane and store.  Ordered on `stream`; waits for it. */
+int ts_bam_chunk_gather_fastq(ts_bam_chunk *chunk, const ts_bam_record *recs, size_t n, const void *d_pass, uint32_t flags,
+                              void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+int ts_sam_chunk_gather_fastq(ts_chunk *chunk, const ts_sam_record *recs, size_t n, const void *d_pass, uint32_t flags,
+                              void *host_out, uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+/* Measurement aid: out[0] FASTQ-out gathers that formatted text on the device, out[1] records, out[2] text bytes since
+ * ts_create.  Cumulative, monotonic, atomic, like ts_read_block_text_stats. */
+int ts_read_fastq_text_stats(const ts_ctx *ctx, uint64_t out[3]);
+
 /* ---- FASTA text in the same resident chunk: the device form of the assembly front end.  Replaces the reference's FASTA load
  *      (gfalibs' stream parser behind Input::read, src/input.cpp:655-716: header lines split off, body lines joined into one
  *      sequence per record) and the cut of a path into segments and gaps at its N-runs (the path components walkPath

@@ -50,6 +50,7 @@
 #include "teloscope_mi355x_gzip.hpp"
 #include "teloscope_mi355x_ring.hpp"
 #include "../teloscope_amd/csrc/read_block_format_core.h"
+#include "../teloscope_amd/csrc/read_fastq_format_core.h"
 
 namespace teloscope_mi355x {
 
@@ -1148,10 +1149,34 @@ public:
 };
 }  // namespace detail
 
+// FASTQ out of the BAM and SAM subsets (the rule: include/teloscan.h, "FASTQ out of the BAM and SAM subsets"): what
+// bamSubsetFastq, samSubsetFastq and their device forms write in place of the kept records' own bytes.  restoreStrand: a record
+// whose FLAG has 0x10 set is written reverse-complemented, its quals reversed (TS_FASTQ_OUT_RESTORE_STRAND) — the read as the
+// sequencer gave it; false writes SEQ and QUAL as stored.
+struct ReadFastqOutput { bool restoreStrand = true; };
+
 namespace detail {
+inline uint32_t fastqOutFlags(const ReadFastqOutput &f) { return f.restoreStrand ? TS_FASTQ_OUT_RESTORE_STRAND : 0u; }
+// a located record's text behind `text`: the host routes' formatter, every byte from the core header the device compiles
+inline void appendFastqText(std::string &text, const char *bytes, const tsfq::Rec &r) {
+    const size_t at = text.size(), n = static_cast<size_t>(tsfq::record_len(r));
+    text.resize(at + n);
+    const ReadBlockReport::Bytes b{bytes};
+    // (the lines one after the other: out_byte's bytes, without its search for the line a byte lies in)
+    char *p = &text[at];
+    *p++ = '@';
+    std::memcpy(p, bytes + r.name_off, r.name_len); p += r.name_len;
+    *p++ = '\n';
+    for (uint32_t j = 0; j < r.len; ++j) *p++ = static_cast<char>(tsfq::base_at(b, r, j));
+    *p++ = '\n'; *p++ = '+'; *p++ = '\n';
+    for (uint32_t j = 0; j < r.len; ++j) *p++ = static_cast<char>(tsfq::qual_at(b, r, j));
+    *p++ = '\n';
+}
+
 class BgzfWriter {
     static constexpr size_t kPayload = 0xff00, kSlot = 65536, kBlocksPerFlush = 64;
     std::ostream &out;
+    bool discard = false;                       // nothing is kept and nothing written: a route whose output is not BAM
     std::vector<unsigned char> pending, comp;
     std::vector<size_t> sizes;
     static size_t block(const unsigned char *data, size_t n, unsigned char *slot) {         // one BGZF block into its 64 KB slot
@@ -1188,8 +1213,9 @@ class BgzfWriter {
         pending.erase(pending.begin(), pending.begin() + static_cast<std::ptrdiff_t>(bytes));
     }
 public:
-    explicit BgzfWriter(std::ostream &o) : out(o) {}
+    explicit BgzfWriter(std::ostream &o, bool discardAll = false) : out(o), discard(discardAll) {}
     void write(const unsigned char *data, size_t n) {
+        if (discard) return;
         pending.insert(pending.end(), data, data + n);
         if (pending.size() >= kBlocksPerFlush * kPayload) flush(pending.size() / kPayload * kPayload);      // whole blocks only
     }
@@ -1201,6 +1227,7 @@ public:
         out.write(reinterpret_cast<const char *>(members), static_cast<std::streamsize>(n));
     }
     void finish() {
+        if (discard) return;
         flush(pending.size());
         static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         out.write(reinterpret_cast<const char *>(eof), sizeof eof);
@@ -1258,11 +1285,15 @@ public:
 };
 }  // namespace detail
 
-inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+namespace detail {
+// (the route itself, behind bamSubset and bamSubsetFastq: with `fastq` the kept records leave as FASTQ text, and no header, member
+// or EOF marker is written)
+inline BamSubsetStats bamSubsetHost(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                    size_t bytesPerBatch, std::ostream *blocks, const ReadFastqOutput *fastq) {
     BamSubsetStats stats;
     detail::FilterWarmUp warmUp(filter);
     detail::ReadBlockReport report(blocks, "failed while writing the BAM subset's block report");
+    std::string fastqText;
     int fd = 0;
     if (inFile != "-") {
         fd = ::open(inFile.c_str(), O_RDONLY);
@@ -1272,7 +1303,7 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
     detail::BgzfParallelReader reader(fd);
     auto le32 = [](const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); };
 
-    detail::BgzfWriter writer(out);
+    detail::BgzfWriter writer(out, fastq != nullptr);
     // Uncompressed bytes arrive in chunks of ~bytesPerBatch, inflated by a reader thread (which spreads the blocks over the
     // host threads) into one of two buffers while the other one is parsed and filtered.  What a chunk leaves unconsumed —
     // the head of a record that continues in the next chunk — is carried into the headroom in front of the next one.
@@ -1363,12 +1394,22 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
                 ++stats.totalRecords;
                 if (!r.seqLen) { ++stats.missingSequenceRecords; continue; }
                 if (pass[k++]) {
-                    writer.write(plain + r.rawOff, r.rawLen); ++stats.passedRecords;
+                    if (fastq) {
+                        const ReadBlockReport::Bytes b{reinterpret_cast<const char *>(plain)};
+                        appendFastqText(fastqText, b.p, tsfq::bam_locate(b, r.rawOff, static_cast<uint32_t>(r.rawLen - 4), static_cast<uint32_t>(r.seqAt - r.rawOff),
+                                                                         r.seqLen, fastqOutFlags(*fastq)));
+                    } else writer.write(plain + r.rawOff, r.rawLen);
+                    ++stats.passedRecords;
                     if (report.on()) {
                         const char *rec = reinterpret_cast<const char *>(plain + r.rawOff);
                         report.add(rec + tsrb::kBamNameAt, tsrb::bam_name_len(detail::ReadBlockReport::Bytes{rec}, 0), seqs.get() + r.seqOff, r.seqLen);
                     }
                 }
+            }
+            if (fastq) {
+                out.write(fastqText.data(), static_cast<std::streamsize>(fastqText.size()));
+                fastqText.clear();
+                if (!out.good()) throw std::runtime_error("failed while writing BAM subset");
             }
             report.flush(filter.context(0));
             stats.blockLines = report.lines;
@@ -1421,10 +1462,23 @@ inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, Re
     if (inflater.joinable()) inflater.join();
     stats.missingEofBlock = !reader.sawEofMarker;
     writer.finish();
+    if (fastq) { out.flush(); if (!out.good()) throw std::runtime_error("failed while writing BAM subset"); }
     if (std::getenv("TS_TIMING"))
         std::fprintf(stderr, "bamSubset: locate + inflate %.0f ms (reader thread), records (walk, decode, filter, write) %.0f ms of which decode %.0f ms, filter %.0f ms\n",
                      msInflate, msRecords, msDecode, msFilter);
     return stats;
+}
+}  // namespace detail
+inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+    return detail::bamSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, nullptr);
+}
+// --bam-subset with FASTQ out (the rule: include/teloscan.h, "FASTQ out of the BAM and SAM subsets"): bamSubset's arguments,
+// statistics and exceptions, and the kept records as four FASTQ lines each in place of a BAM.  The valid records in front of a bad
+// one are written first, as bamSubset writes them.
+inline BamSubsetStats bamSubsetFastq(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, const ReadFastqOutput &fastq = ReadFastqOutput(),
+                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+    return detail::bamSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, &fastq);
 }
 
 // ---- what the four device routes share: the input's bytes into a device chunk, and the judge step of the two read subsets ----
@@ -2171,8 +2225,9 @@ public:
     std::vector<std::unique_ptr<Worker>> workers;
 
     BamChunkSteps(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk,
-                  BamOutputDeflate deflate = BamOutputDeflate::Host, std::ostream *blocks = nullptr)
-        : data_(data), size_(size), writer_(out), blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
+                  BamOutputDeflate deflate = BamOutputDeflate::Host, std::ostream *blocks = nullptr, const ReadFastqOutput *fastq = nullptr)
+        : data_(data), size_(size), writer_(out, fastq != nullptr), text_(out), fastq_(fastq != nullptr), fastqFlags_(fastq ? fastqOutFlags(*fastq) : 0u),
+          blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
           table_(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), walk_(walk), deflate_(deflate),
           plainCap_((256ull << 20) + 4 + chunkBytes), compCap_(chunkBytes + (1u << 20)) {
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
@@ -2267,6 +2322,7 @@ public:
         if (held_ != prevNext_) throw std::runtime_error(held_ - prevNext_ < 4 ? "truncated BAM record size" : "truncated BAM record");
         stats.missingEofBlock = !sawEofMarker_;
         writer_.finish();
+        if (fastq_) { text_.flush(); if (!text_.good()) throw std::runtime_error("failed while writing BAM subset"); }
     }
 
 private:
@@ -2344,6 +2400,8 @@ private:
                 k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
                              [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
                              [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                                 if (fastq_)
+                                     return ts_bam_chunk_gather_fastq(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, fastqFlags_, dst, cap, bytes, nPassed, nullptr);
                                  if (deflate_ == BamOutputDeflate::Host)
                                      return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
                                  const Clock::time_point t0 = Clock::now();
@@ -2357,7 +2415,7 @@ private:
                              // (a refused ts_bam_chunk_gather_bgzf has deflated already: the plain gather's plan, which a call
                              // without room stops at, says how many record bytes pass, and a member adds 31 bytes at the most)
                              [&](void *dPass) -> uint64_t {
-                                 if (deflate_ == BamOutputDeflate::Host) return 0;
+                                 if (fastq_ || deflate_ == BamOutputDeflate::Host) return 0;
                                  uint64_t plain = 0, passed = 0;
                                  const int rc = ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, nullptr, 0, &plain, &passed, nullptr);
                                  if (rc != TS_OK && !(rc == TS_ERR_INVALID_ARG && plain > 0)) throw deviceError(k.ctx, "gather of the passing records failed");
@@ -2374,7 +2432,10 @@ private:
     // a sub-batch's passing records to the writer: plain bytes for zlib, or (Device) finished members
     void write(const unsigned char *p, size_t n) {
         const Clock::time_point t0 = Clock::now();
-        if (deflate_ == BamOutputDeflate::Host) writer_.write(p, n);
+        if (fastq_) {                                           // FASTQ text: as it is
+            text_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+            if (!text_.good()) throw std::runtime_error("failed while writing BAM subset");
+        } else if (deflate_ == BamOutputDeflate::Host) writer_.write(p, n);
         else if (n) writer_.writeMembers(p, n);
         msWrite += since(t0);
     }
@@ -2382,6 +2443,9 @@ private:
     const unsigned char *data_;
     size_t size_;
     BgzfWriter writer_;
+    std::ostream &text_;                                        // the output itself, for FASTQ text (writer_ then keeps nothing)
+    bool fastq_;
+    uint32_t fastqFlags_;
     std::ostream *blocks_;                                      // the read block report's stream, or nothing
     BamHeaderParser header_;
     size_t readsPerBatch_, chunkBytes_, table_;
@@ -2415,13 +2479,13 @@ namespace detail {
 // (the route itself, behind bamSubsetDevice's two forms below)
 inline BamSubsetStats bamSubsetDeviceRun(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
                                          size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice,
-                                         BamOutputDeflate deflate, std::ostream *blocks) {
+                                         BamOutputDeflate deflate, std::ostream *blocks, const ReadFastqOutput *fastq = nullptr) {
     // the compressed input: a regular file is mapped, a pipe is read to its end
     detail::MappedInput in(inFile, true, "cannot open BAM input '" + inFile + "'");
     std::vector<unsigned char> piped;
     if (!in.data) in.readToEnd(piped, "cannot read BAM input");
     detail::BamChunkSteps steps(filter, in.data ? in.data : piped.data(), in.data ? in.size : piped.size(), out, readsPerBatch,
-                                std::max<size_t>(bytesPerBatch, 1u << 20), walk, deflate, blocks);
+                                std::max<size_t>(bytesPerBatch, 1u << 20), walk, deflate, blocks, fastq);
     std::unique_ptr<detail::ChunkRing<detail::BamChunkSteps>> ring;
     if (const uint64_t firstChunk = steps.runInPlace()) {
         ring.reset(new detail::ChunkRing<detail::BamChunkSteps>(filter.deviceCount(), firstChunk, steps));
@@ -2446,6 +2510,16 @@ inline BamSubsetStats bamSubsetDevice(const std::string &inFile, std::ostream &o
                                       size_t bytesPerBatch, BamRecordWalk walk, std::vector<ReadRouteDeviceStats> *perDevice,
                                       BamOutputDeflate deflate, std::ostream *blocks = nullptr) {
     return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, deflate, blocks);
+}
+// The device route of --bam-subset with FASTQ out (same arguments, statistics, exceptions and output bytes as bamSubsetFastq):
+// bamSubsetDevice's chunk steps on every context of the filter, with ts_bam_chunk_gather_fastq as detail::ReadJudge's gather — the
+// kept records' text is formatted where the chunk lies and only the text comes back.  The bytes do not depend on the number of
+// contexts, readsPerBatch, bytesPerBatch or the walk.  The TS_TIMING lines are bamSubsetDevice's.
+inline BamSubsetStats bamSubsetFastqDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                           const ReadFastqOutput &fastq = ReadFastqOutput(), size_t readsPerBatch = 1u << 20,
+                                           size_t bytesPerBatch = 256u << 20, BamRecordWalk walk = BamRecordWalk::Index,
+                                           std::vector<ReadRouteDeviceStats> *perDevice = nullptr, std::ostream *blocks = nullptr) {
+    return detail::bamSubsetDeviceRun(inFile, out, filter, readsPerBatch, bytesPerBatch, walk, perDevice, BamOutputDeflate::Host, blocks, &fastq);
 }
 
 // The device route of --fastq-subset (same arguments, result, exceptions and, for well-formed input, output bytes as
@@ -2559,11 +2633,11 @@ inline void samWalkHost(const char *text, size_t size, bool atEnd, bool inHeader
 }
 }  // namespace detail
 
-// The host route: lines and fields are found on the host, a block of input at a time, and the sequences are judged in batches of
-// up to readsPerBatch through the filter, as fastqSubset does.  Input may be plain or gzip (both through zlib, which passes plain
-// bytes on as they are); `-` is stdin.
-inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+namespace detail {
+// (the route itself, behind samSubset and samSubsetFastq: with `fastq` the kept records leave as FASTQ text and no header line is
+// written)
+inline SamSubsetStats samSubsetHost(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
+                                    size_t bytesPerBatch, std::ostream *blocks, const ReadFastqOutput *fastq) {
     detail::FilterWarmUp warmUp(filter);
     detail::ReadBlockReport report(blocks, "failed while writing the SAM subset's block report");
     struct Source { gzFile gz = nullptr; ~Source() { if (gz) gzclose(gz); } } src;
@@ -2607,7 +2681,7 @@ inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, Re
         any = any || size > 0;
         if (eof && !any) throw std::runtime_error("SAM input is empty");
         detail::samWalkHost(buf.data(), size, eof, inHeader, walk);
-        write(buf.data(), static_cast<size_t>(walk.headerEnd));
+        if (!fastq) write(buf.data(), static_cast<size_t>(walk.headerEnd));
         stats.headerLines += walk.headerLines; stats.totalRecords += walk.recs.size();
         if (walk.headerLines < walk.lines || walk.error != TS_SAM_OK) inHeader = false;
         // the block's records in batches (they point into the block), the kept lines echoed
@@ -2626,8 +2700,13 @@ inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, Re
             text.clear();
             for (size_t i = 0; i < judged.size(); ++i) {
                 if (!pass[i]) continue;
-                text.append(buf.data() + judged[i]->off, judged[i]->size);
-                text.push_back('\n');
+                if (fastq) {
+                    const ts_sam_record &r = *judged[i];
+                    appendFastqText(text, buf.data(), tsfq::sam_locate(ReadBlockReport::Bytes{buf.data()}, r.off, r.seq_at, r.seq_len, r.size, fastqOutFlags(*fastq)));
+                } else {
+                    text.append(buf.data() + judged[i]->off, judged[i]->size);
+                    text.push_back('\n');
+                }
                 ++stats.passedRecords;
                 if (report.on()) {
                     const char *line = buf.data() + judged[i]->off;
@@ -2645,6 +2724,20 @@ inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, Re
     }
     out.flush();
     return stats;
+}
+}  // namespace detail
+// The host route: lines and fields are found on the host, a block of input at a time, and the sequences are judged in batches of
+// up to readsPerBatch through the filter, as fastqSubset does.  Input may be plain or gzip (both through zlib, which passes plain
+// bytes on as they are); `-` is stdin.
+inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+    return detail::samSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, nullptr);
+}
+// --sam-subset with FASTQ out (the rule: include/teloscan.h, "FASTQ out of the BAM and SAM subsets"): samSubset's arguments,
+// statistics and exceptions, and the kept records as four FASTQ lines each; header lines are counted and not written.
+inline SamSubsetStats samSubsetFastq(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, const ReadFastqOutput &fastq = ReadFastqOutput(),
+                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+    return detail::samSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, &fastq);
 }
 
 namespace detail {
@@ -2668,8 +2761,10 @@ public:
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    SamChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
-        : feed_(feed), out_(out), blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
+    SamChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr,
+                  const ReadFastqOutput *fastq = nullptr)
+        : feed_(feed), out_(out), blocks_(blocks), fastq_(fastq != nullptr), fastqFlags_(fastq ? fastqOutFlags(*fastq) : 0u),
+          readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
         const uint64_t compCap = feed.compCap(chunkBytes);
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
             workers.emplace_back(new Worker());
@@ -2756,7 +2851,7 @@ private:
             rc = walk();
         }
         if (rc != TS_OK) throw deviceError(k.ctx, "SAM walk failed");
-        if (headerEnd) {
+        if (headerEnd && !fastq_) {                             // (FASTQ out writes no header line)
             k.header.resize(static_cast<size_t>(headerEnd));
             if (ts_bam_chunk_read(k.chunk, 0, headerEnd, k.header.data()) != TS_OK) throw deviceError(k.ctx, "cannot read the chunk");
         }
@@ -2788,6 +2883,8 @@ private:
             k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
                          [&](ts_batch *batch) { return ts_sam_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
                          [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+                             if (fastq_)
+                                 return ts_sam_chunk_gather_fastq(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, fastqFlags_, dst, cap, bytes, nPassed, nullptr);
                              return ts_sam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
                          });
             k.passed += k.judged.nPassed;
@@ -2811,6 +2908,8 @@ private:
     ChunkFeed &feed_;
     std::ostream &out_;
     std::ostream *blocks_;                                      // the read block report's stream, or nothing
+    bool fastq_;                                                // the kept records leave as FASTQ text (ts_sam_chunk_gather_fastq)
+    uint32_t fastqFlags_;
     size_t readsPerBatch_, chunkBytes_;
     // the framing's state: the chunk framed last and where its unfinished line begins; nothing framed yet held a byte; the input
     // is still in its header; whole lines behind
@@ -2822,6 +2921,31 @@ private:
 
 }  // namespace detail
 
+namespace detail {
+// (the route itself, behind samSubsetDevice and samSubsetFastqDevice)
+inline SamSubsetStats samSubsetDeviceRun(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch, size_t chunkBytes,
+                                         std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks, const ReadFastqOutput *fastq) {
+    const bool dealt = filter.deviceCount() > 1;
+    detail::ChunkFeed::Options options;
+    options.cannotOpen = "Stream not successful: " + inFile;
+    options.cannotRead = "read error in SAM input";
+    options.dashIsStdin = true;
+    options.uploadFailed = "upload of the SAM text failed";
+    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
+    detail::ChunkFeed feed(filter.context(0), inFile, options);
+    detail::SamChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64), blocks, fastq);
+    std::unique_ptr<detail::ChunkRing<detail::SamChunkSteps>> ring;
+    if (dealt) {
+        ring.reset(new detail::ChunkRing<detail::SamChunkSteps>(filter.deviceCount(), 0, steps));
+        ring->run();
+    } else {
+        steps.runInPlace();
+    }
+    out.flush();
+    detail::routeFigures(feed.deviceInflate() ? "samSubsetDevice (upload + inflate + CRC)" : "samSubsetDevice", steps.workers, ring.get(), steps.msWrite, perDevice);
+    return steps.stats;
+}
+}  // namespace detail
 // The device route of --sam-subset (same arguments, result, exceptions and output bytes as samSubset): the SAM text exists in HBM
 // one chunk of ~chunkBytes bytes at a time and the host reads none of it but the header lines, which it writes.  The text gets
 // there through detail::ChunkFeed (a plain file, BGZF members inflated on the device, a stream through zlib or read(2), plain gzip
@@ -2833,25 +2957,16 @@ private:
 inline SamSubsetStats samSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                       size_t readsPerBatch = 1u << 20, size_t chunkBytes = 256u << 20,
                                       std::vector<ReadRouteDeviceStats> *perDevice = nullptr, std::ostream *blocks = nullptr) {
-    const bool dealt = filter.deviceCount() > 1;
-    detail::ChunkFeed::Options options;
-    options.cannotOpen = "Stream not successful: " + inFile;
-    options.cannotRead = "read error in SAM input";
-    options.dashIsStdin = true;
-    options.uploadFailed = "upload of the SAM text failed";
-    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
-    detail::ChunkFeed feed(filter.context(0), inFile, options);
-    detail::SamChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64), blocks);
-    std::unique_ptr<detail::ChunkRing<detail::SamChunkSteps>> ring;
-    if (dealt) {
-        ring.reset(new detail::ChunkRing<detail::SamChunkSteps>(filter.deviceCount(), 0, steps));
-        ring->run();
-    } else {
-        steps.runInPlace();
-    }
-    out.flush();
-    detail::routeFigures(feed.deviceInflate() ? "samSubsetDevice (upload + inflate + CRC)" : "samSubsetDevice", steps.workers, ring.get(), steps.msWrite, perDevice);
-    return steps.stats;
+    return detail::samSubsetDeviceRun(inFile, out, filter, readsPerBatch, chunkBytes, perDevice, blocks, nullptr);
+}
+// The device route of --sam-subset with FASTQ out (same arguments, statistics, exceptions and output bytes as samSubsetFastq):
+// samSubsetDevice's chunk steps on every context of the filter, with ts_sam_chunk_gather_fastq as detail::ReadJudge's gather; the
+// header lines are counted and stay on the device.  The bytes do not depend on the number of contexts, readsPerBatch or chunkBytes.
+// The TS_TIMING lines are samSubsetDevice's.
+inline SamSubsetStats samSubsetFastqDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                           const ReadFastqOutput &fastq = ReadFastqOutput(), size_t readsPerBatch = 1u << 20, size_t chunkBytes = 256u << 20,
+                                           std::vector<ReadRouteDeviceStats> *perDevice = nullptr, std::ostream *blocks = nullptr) {
+    return detail::samSubsetDeviceRun(inFile, out, filter, readsPerBatch, chunkBytes, perDevice, blocks, &fastq);
 }
 
 inline const char *scaffoldTypeToString(ScaffoldType t) {       // src/tools.cpp

@@ -295,6 +295,7 @@ SYMBOLS = [
     "ts_sam_chunk_walk", "ts_sam_chunk_stage", "ts_sam_chunk_gather",
     "ts_batch_call_read_blocks", "ts_batch_read_blocks", "ts_fastq_chunk_block_lines", "ts_sam_chunk_block_lines",
     "ts_bam_chunk_block_lines", "ts_read_block_lines_format", "ts_read_block_text_stats",
+    "ts_bam_chunk_gather_fastq", "ts_sam_chunk_gather_fastq", "ts_read_fastq_text_stats",
 ]
 
 
@@ -545,6 +546,10 @@ def lib():
     L.ts_read_block_lines_format.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
                                              C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.ts_read_block_text_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    for name, rec in (("ts_bam_chunk_gather_fastq", BamRecord), ("ts_sam_chunk_gather_fastq", SamRecord)):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(rec), C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_read_fastq_text_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 

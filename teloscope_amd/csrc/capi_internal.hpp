@@ -174,6 +174,8 @@ struct ts_ctx {
     std::atomic<uint64_t> match_text_stats[4] = {};
     // ts_read_block_text_stats: formatting calls that reached the device, lines, text bytes — since ts_create
     std::atomic<uint64_t> read_block_text_stats[3] = {};
+    // ts_read_fastq_text_stats: FASTQ-out gathers that formatted text on the device, records, text bytes — since ts_create
+    std::atomic<uint64_t> read_fastq_text_stats[3] = {};
     // ts_gzip_stats: windows, spans probed, spans chained, spans dropped, plain bytes produced, parts the caller handed to zlib — since ts_create
     std::atomic<uint64_t> gzip_stats[6] = {};
     // ts_bam_index_stats: calls, spans the chain entered, spans whose entry was a candidate row, spans settled by the serial

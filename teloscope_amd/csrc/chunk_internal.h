@@ -72,6 +72,9 @@ struct ts_bam_chunk {
     // ---- the read block report (read_blocks.cpp): the record table of a *_block_lines call, the segments' name entries, the
     // workgroups' sums and the text
     struct Blocks { DevBuf d_recs, d_segs, d_sums, d_text; } blocks;
+    // ---- FASTQ out of a BAM or SAM chunk (read_fastq.cpp): the kept records' table entries, their text's sizes, their first
+    // jobs and the jobs
+    struct FastqOut { DevBuf d_table, d_sizes, d_job_base, d_jobs; } fastq_out;
 };
 
 // the tail [carry_from, plain_n) of the chunk's bytes to its front, on st (through d_tmp where the two overlap); -> the tail's length
