@@ -1881,12 +1881,7 @@ struct ReadJudge {
     std::vector<unsigned char> blockText;
     uint64_t blockBytes = 0, nBlockLines = 0;
 
-    template <typename Stage, typename Gather>
-    void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather) {
-        run(ctx, chunk, lens, stageFailed, stage, gather, [](void *) { return uint64_t(0); });
-    }
-    // ... with room(dPass): the bytes `kept` must hold before gather is called (0: as it is), for a gather whose refused call is
-    // not cheap
+    // room(dPass): the bytes `kept` must hold before gather is called (0: as it is), for a gather whose refused call is not cheap
     template <typename Stage, typename Gather, typename Room>
     void run(ts_ctx *ctx, ts_chunk *chunk, const std::vector<uint64_t> &lens, const char *stageFailed, Stage &&stage, Gather &&gather, Room &&room) {
         struct BatchPtr { ts_batch *p; ~BatchPtr() { ts_batch_destroy(p); } } batch{ts_batch_create(ctx, lens.data(), nullptr, lens.size(), 1, 0)};
@@ -1933,10 +1928,11 @@ struct ReadJudge {
 
 }  // namespace detail
 
-// ---- the two device read routes, bamSubsetDevice and fastqSubsetDevice: one set of chunk steps each, for a filter of any number
-// of contexts ----
-// A route's steps (detail::BamChunkSteps, detail::FastqChunkSteps) have two ways to bring a chunk's bytes in; everything behind
-// the fill (framing, judging, emitting, the exception texts, the figures) exists once and serves both.
+// ---- the three device read routes, bamSubsetDevice, fastqSubsetDevice and samSubsetDevice: one set of chunk steps each, for a
+// filter of any number of contexts ----
+// A route's steps (detail::BamChunkSteps, detail::FastqChunkSteps, detail::SamChunkSteps) have two ways to bring a chunk's bytes
+// in; everything behind the fill (framing, judging, emitting, the exception texts, the figures) exists once and serves both.
+// What the formats do alike exists once under the three (detail::ReadChunkSteps, and detail::TextChunkSteps for the two of text).
 //   In place  the new bytes go straight behind the unfinished record in the context's own chunk, and the chunk is framed, judged
 //             and emitted on the caller's thread, each sub-batch's passing bytes straight from the judge to the output: no
 //             staging region, no commit, no carry between chunks, no thread.  A filter of one context takes its whole input so;
@@ -1986,7 +1982,7 @@ struct ChunkWorker {
     std::vector<uint64_t> lens;
     std::vector<unsigned char> out;                             // a dealt chunk's passing records, in input order
     std::vector<size_t> cuts;                                   // where each sub-batch's records end in `out`: the writer's pieces
-    uint64_t passed = 0;                                        // the chunk's passing records, however it came in
+    uint64_t withBases = 0, passed = 0;                         // the chunk's records that had bases, and its passing ones, however it came in
     std::vector<unsigned char> blockOut;                        // a dealt chunk's lines of the read block report, in input order
     uint64_t blockLines = 0;                                    // the chunk's report lines, however it came in
     ReadRouteDeviceStats st;
@@ -1994,7 +1990,7 @@ struct ChunkWorker {
     ChunkWorker(const ChunkWorker &) = delete;
     ChunkWorker &operator=(const ChunkWorker &) = delete;
     ~ChunkWorker() { ts_bam_chunk_destroy(chunk); }
-    void fresh() { out.clear(); cuts.clear(); passed = 0; blockOut.clear(); blockLines = 0; }
+    void fresh() { out.clear(); cuts.clear(); withBases = passed = 0; blockOut.clear(); blockLines = 0; }
     // a dealt chunk's sub-batch waits here for the chunk's turn to emit
     void keep() {
         out.insert(out.end(), judged.kept.begin(), judged.kept.begin() + static_cast<std::ptrdiff_t>(judged.bytes));
@@ -2055,39 +2051,78 @@ inline void routeFigures(const char *route, const std::vector<std::unique_ptr<Wo
     if (std::getenv("TS_TIMING")) std::fprintf(stderr, "%s: write %.0f ms\n", route, msWrite);
 }
 
-// fastqSubsetDevice's stages.  The first chunk must begin with '@'; ts_fastq_chunk_walk frames and validates the records, and the
-// bytes behind the last whole one go in front of the next chunk.  A record that is not valid ends the framing; its chunk's valid
-// records are still judged and written before emit() throws.  A chunk that holds no whole record (a record larger than it)
-// passes all of its contents on: in place the next fill takes as much again, so the chunk doubles; a dealt chunk takes
-// chunkBytes more.
-class FastqChunkSteps {
+// ... of a record route: the chunk's record table as the walk left it, and the records of the sub-batch under way that have bases
+template <typename Rec>
+struct RecordWorker : ChunkWorker {
+    std::vector<Rec> recs, withSeq;
+    uint64_t n = 0;                                             // records of the chunk
+};
+
+// What the steps of the three device read routes share: the sub-batch judge loop and the head of emit().  Route (FastqChunkSteps,
+// SamChunkSteps, BamChunkSteps) derives from it and says what its format does differently:
+//   static uint64_t bases(const Rec &)      the record's bases; 0: it has none, is not judged and never kept
+//   static constexpr const char *stageFailed
+//   int stageReads(Worker &, ts_batch *)    the sequences of k.withSeq into the batch's input buffer
+//   int gatherKept(Worker &, void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed)
+//   int blockLines(Worker &, ts_batch *, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines)
+//   void write(const unsigned char *, size_t)       passing bytes to the route's output
+// and gatherRoom(Worker &, void *dPass) where its gather needs one (ReadJudge::run).
+template <typename Route, typename Worker>
+class ReadChunkSteps {
 public:
-    struct Worker : ChunkWorker {
-        ChunkFeed::Fill fill;                                   // a dealt chunk's new bytes
-        std::vector<ts_fastq_record> recs, withSeq;
-        uint64_t n = 0;                                         // whole records of the chunk
-        int error = TS_FASTQ_OK;
-    };
-    FastqSubsetResult res;
     double msWrite = 0;
     std::vector<std::unique_ptr<Worker>> workers;
 
-    FastqChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
-        : feed_(feed), out_(out), blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
-        const uint64_t compCap = feed.compCap(chunkBytes);
-        for (size_t w = 0; w < filter.deviceCount(); ++w) {
-            workers.emplace_back(new Worker());
-            Worker &k = *workers.back();
-            k.ctx = filter.context(w);
-            k.chunk = ts_bam_chunk_create(k.ctx, compCap, chunkBytes);
-            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
-            k.recs.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16));
+protected:
+    ReadChunkSteps(std::ostream *blocks, size_t readsPerBatch) : blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)) {}
+    Route &route() { return static_cast<Route &>(*this); }
+    uint64_t gatherRoom(Worker &, void *) { return 0; }
+    // Records [from, to) of the chunk's table in sub-batches of readsPerBatch, in input order.  A dealt chunk keeps a sub-batch's
+    // passing bytes until its turn to emit; an in-place chunk has the turn, and they go from the judge straight to the output.
+    void judgeRecords(Worker &k, size_t from, size_t to, bool dealt) {
+        Route &r = route();
+        for (size_t a = from; a < to; a += readsPerBatch_) {
+            const auto *rec = k.recs.data() + a;
+            const size_t n = std::min<size_t>(readsPerBatch_, to - a);
+            k.withSeq.clear(); k.lens.clear();
+            for (size_t i = 0; i < n; ++i) if (const uint64_t bases = Route::bases(rec[i])) { k.withSeq.push_back(rec[i]); k.lens.push_back(bases); }
+            if (k.withSeq.empty()) continue;                    // (a read without bases is never kept)
+            k.withBases += k.withSeq.size();
+            k.st.recordsJudged += k.withSeq.size();
+            if (blocks_ && !k.judged.blockLines)
+                k.judged.blockLines = [&r, &k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+                    return r.blockLines(k, batch, dst, cap, bytes, lines);
+                };
+            k.judged.run(k.ctx, k.chunk, k.lens, Route::stageFailed, [&](ts_batch *batch) { return r.stageReads(k, batch); },
+                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) { return r.gatherKept(k, dPass, dst, cap, bytes, nPassed); },
+                         [&](void *dPass) { return r.gatherRoom(k, dPass); });
+            k.passed += k.judged.nPassed;
+            k.blockLines += k.judged.nBlockLines;
+            if (dealt) k.keep();
+            else { r.write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
         }
     }
+    // the head of a chunk's turn to write: what it kept (nothing, where it came in place)
+    void emitKept(const Worker &k) {
+        k.pieces([&](const unsigned char *p, size_t n) { route().write(p, n); });
+        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
+    }
 
+    std::ostream *blocks_;                                      // the read block report's stream, or nothing
+    size_t readsPerBatch_;
+};
+
+// The steps of the two text routes, fastqSubsetDevice and samSubsetDevice, up to the format's framing: a chunk of chunkBytes per
+// context, fed by one ChunkFeed.  Route adds frameChunk(Worker &, atEnd) (-> every record up to the chunk's end is valid; where
+// the chunk's unfinished record begins goes to prevNext_), emit(w, chunk) and, where it judges with more than the loop,
+// judgeChunk.  A chunk that holds no whole record (a record larger than it) passes all of its contents on: in place the next
+// fill takes as much again, so the chunk doubles; a dealt chunk takes chunkBytes more.
+template <typename Route, typename Worker>
+class TextChunkSteps : public ReadChunkSteps<Route, Worker> {
+public:
     // The whole input as in-place chunks of context 0, on the caller's thread: any source of the feed, ChunkFeed::Gzip included
     void runInPlace() {
-        Worker &k = *workers[0];
+        Worker &k = *this->workers[0];
         for (bool atEnd = false; !atEnd;) {
             const uint64_t carry = ts_bam_chunk_size(k.chunk) - prevNext_;
             // a chunk that held no whole record takes as much again
@@ -2096,51 +2131,110 @@ public:
             atEnd = feed_.fill(k.chunk, prevNext_, want);
             k.st.msSource += since(t0);
             ++k.st.chunks; k.st.bytesReceived += ts_bam_chunk_size(k.chunk) - carry;
-            frameRecords(k, atEnd);
-            judgeRecords(k, false);
-            emit(0, 0);
+            frameNext(k, atEnd);
+            this->route().judgeChunk(k, false);
+            this->route().emit(0, 0);
         }
     }
 
     // the ring's steps: a dealt chunk
-    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
+    void begin(size_t w) { ts_bind_thread_to_device(this->workers[w]->ctx); }
     RingTake take(size_t w, uint64_t) {
-        Worker &k = *workers[w];
+        Worker &k = *this->workers[w];
         const Clock::time_point t0 = Clock::now();
         feed_.take(chunkBytes_, k.fill);
         k.st.msSource += since(t0);
         return k.fill.atEnd ? RingTake::Last : RingTake::More;
     }
     void stage(size_t w, uint64_t) {
-        Worker &k = *workers[w];
+        Worker &k = *this->workers[w];
         const Clock::time_point t0 = Clock::now();
         feed_.stage(k.ctx, k.chunk, k.fill);
         k.st.msSource += since(t0);
         ++k.st.chunks; k.st.bytesReceived += k.fill.n;
     }
-    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, ts_fastq_chunk_walk
-        Worker &k = *workers[w];
+    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, the format's framing
+        Worker &k = *this->workers[w];
         ringCommit(k, prev_, prevNext_);
-        return frameRecords(k, k.fill.atEnd);
+        return frameNext(k, k.fill.atEnd);
     }
-    void judge(size_t w, uint64_t) { judgeRecords(*workers[w], true); }
-    // the chunk's turn to write: what it kept (nothing, where it came in place), its totals, and the record that is not valid
+    void judge(size_t w, uint64_t) { this->route().judgeChunk(*this->workers[w], true); }
+
+    void judgeChunk(Worker &k, bool dealt) { k.fresh(); this->judgeRecords(k, 0, static_cast<size_t>(k.n), dealt); }
+    void write(const unsigned char *p, size_t n) {
+        const Clock::time_point t0 = Clock::now();
+        out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+        if (!out_.good()) throw std::runtime_error(writeFailed_);
+        this->msWrite += since(t0);
+    }
+
+protected:
+    TextChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks, const char *writeFailed)
+        : ReadChunkSteps<Route, Worker>(blocks, readsPerBatch), feed_(feed), out_(out), chunkBytes_(chunkBytes), writeFailed_(writeFailed) {
+        const uint64_t compCap = feed.compCap(chunkBytes);
+        for (size_t w = 0; w < filter.deviceCount(); ++w) {
+            this->workers.emplace_back(new Worker());
+            Worker &k = *this->workers.back();
+            k.ctx = filter.context(w);
+            k.chunk = ts_bam_chunk_create(k.ctx, compCap, chunkBytes);
+            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
+            k.recs.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16));
+        }
+    }
+    // The records of a chunk that has its bytes; the framing's state moves on to it
+    bool frameNext(Worker &k, bool atEnd) {
+        prev_ = &k; prevNext_ = 0;
+        return this->route().frameChunk(k, atEnd);
+    }
+
+    ChunkFeed &feed_;
+    std::ostream &out_;
+    size_t chunkBytes_;
+    const char *writeFailed_;
+    // the framing's state: the chunk framed last and where its unfinished record begins; nothing framed yet held a byte
+    const ChunkWorker *prev_ = nullptr;
+    uint64_t prevNext_ = 0;
+    bool first_ = true;
+};
+
+// fastqSubsetDevice's stages: TextChunkSteps with the FASTQ framing.  The first chunk must begin with '@'; ts_fastq_chunk_walk
+// frames and validates the records, and the bytes behind the last whole one go in front of the next chunk.  A record that is not
+// valid ends the framing; its chunk's valid records are still judged and written before emit() throws.
+struct FastqWorker : RecordWorker<ts_fastq_record> {
+    ChunkFeed::Fill fill;                                       // a dealt chunk's new bytes
+    int error = TS_FASTQ_OK;
+};
+class FastqChunkSteps : public TextChunkSteps<FastqChunkSteps, FastqWorker> {
+public:
+    using Worker = FastqWorker;
+    FastqSubsetResult result;
+
+    FastqChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
+        : TextChunkSteps(filter, feed, out, readsPerBatch, chunkBytes, blocks, "failed while writing FASTQ subset") {}
+
+    // the chunk's turn to write: what it kept, its totals, and the record that is not valid
     void emit(size_t w, uint64_t) {
         Worker &k = *workers[w];
-        k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
-        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
-        res.kept += k.passed; res.total += k.n; res.blockLines += k.blockLines;
+        emitKept(k);
+        result.kept += k.passed; result.total += k.n; result.blockLines += k.blockLines;
         if (k.error != TS_FASTQ_OK) {
             const char *msg = k.error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : k.error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
                             : k.error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
-            throw std::runtime_error("FASTQ record " + std::to_string(res.total + 1) + ": " + msg);
+            throw std::runtime_error("FASTQ record " + std::to_string(result.total + 1) + ": " + msg);
         }
     }
 
-private:
-    // The records of a chunk that has its bytes; the framing's state moves on to it.  -> every record up to the chunk's end is valid
-    bool frameRecords(Worker &k, bool atEnd) {
-        prev_ = &k; prevNext_ = 0;
+    // the format's part of the shared steps
+    static uint64_t bases(const ts_fastq_record &r) { return r.seq_len > r.seq_cr ? r.seq_len - r.seq_cr : 0; }
+    static constexpr const char *stageFailed = "staging the sequences failed";
+    int stageReads(Worker &k, ts_batch *batch) { return ts_fastq_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); }
+    int gatherKept(Worker &k, void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+        return ts_fastq_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+    }
+    int blockLines(Worker &k, ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+        return ts_fastq_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+    }
+    bool frameChunk(Worker &k, bool atEnd) {
         k.n = 0; k.error = TS_FASTQ_OK;
         if (first_) {
             if (ts_bam_chunk_size(k.chunk) == 0) {
@@ -2163,71 +2257,55 @@ private:
         k.st.msWalk += since(t0);
         return k.error == TS_FASTQ_OK;
     }
-    // The chunk's records in sub-batches, in input order.  A dealt chunk keeps a sub-batch's passing bytes until its turn to emit;
-    // an in-place chunk has the turn, and they go from the judge straight to the output.
-    void judgeRecords(Worker &k, bool dealt) {
-        k.fresh();
-        for (size_t a = 0; a < k.n; a += readsPerBatch_) {
-            const ts_fastq_record *r = k.recs.data() + a;
-            const size_t n = std::min<size_t>(readsPerBatch_, static_cast<size_t>(k.n) - a);
-            k.withSeq.clear(); k.lens.clear();
-            for (size_t i = 0; i < n; ++i) if (r[i].seq_len > r[i].seq_cr) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].seq_len - r[i].seq_cr); }
-            if (k.withSeq.empty()) continue;                    // (a read without bases is never kept)
-            k.st.recordsJudged += k.withSeq.size();
-            if (blocks_ && !k.judged.blockLines)
-                k.judged.blockLines = [&k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
-                    return ts_fastq_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
-                };
-            k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
-                         [&](ts_batch *batch) { return ts_fastq_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
-                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                             return ts_fastq_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
-                         });
-            k.passed += k.judged.nPassed;
-            k.blockLines += k.judged.nBlockLines;
-            if (dealt) k.keep();
-            else { write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
-        }
-    }
-    void write(const unsigned char *p, size_t n) {
-        const Clock::time_point t0 = Clock::now();
-        out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
-        if (!out_.good()) throw std::runtime_error("failed while writing FASTQ subset");
-        msWrite += since(t0);
-    }
-
-    ChunkFeed &feed_;
-    std::ostream &out_;
-    std::ostream *blocks_;                                      // the read block report's stream, or nothing
-    size_t readsPerBatch_, chunkBytes_;
-    // the framing's state: the chunk framed last and where its unfinished record begins; nothing framed yet held a byte
-    const ChunkWorker *prev_ = nullptr;
-    uint64_t prevNext_ = 0;
-    bool first_ = true;
 };
+
+// The driver of the two text routes, behind fastqSubsetDevice and samSubsetDeviceRun: the feed with the route's exception texts
+// (`format` is the name they give the input), Steps over it with `more` behind the common arguments, the chunks dealt by the ring
+// on several contexts or taken in place on one, and the figures under `route`.
+template <typename Steps, typename... More>
+inline auto textSubsetDeviceRun(const char *format, const std::string &route, const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                size_t readsPerBatch, size_t chunkBytes, std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks, More... more) {
+    const bool dealt = filter.deviceCount() > 1;
+    const std::string uploadFailed = std::string("upload of the ") + format + " text failed";
+    ChunkFeed::Options options;
+    options.cannotOpen = "Stream not successful: " + inFile;
+    options.cannotRead = std::string("read error in ") + format + " input";
+    options.dashIsStdin = true;
+    options.uploadFailed = uploadFailed.c_str();
+    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
+    ChunkFeed feed(filter.context(0), inFile, options);
+    Steps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64), blocks, more...);
+    std::unique_ptr<ChunkRing<Steps>> ring;
+    if (dealt) {
+        ring.reset(new ChunkRing<Steps>(filter.deviceCount(), 0, steps));
+        ring->run();
+    } else {
+        steps.runInPlace();
+    }
+    out.flush();
+    routeFigures((feed.deviceInflate() ? route + " (upload + inflate + CRC)" : route).c_str(), steps.workers, ring.get(), steps.msWrite, perDevice);
+    return steps.result;
+}
 
 // bamSubsetDevice's stages.  A chunk holds as many BGZF members as inflate to chunkBytes (pick), whichever way it comes in, so
 // the tables, and what is written before a record that is not valid, do not depend on the number of contexts.  The header is
 // parsed on the host from the leading bytes of context 0's in-place chunks.
-class BamChunkSteps {
+struct BamWorker : RecordWorker<ts_bam_record> {                // (recs: one walk's table behind the other)
+    std::vector<ts_bgzf_block> descs;                           // the chunk's members: where they lie, how much they give
+    size_t at = 0, used = 0;
+    uint64_t produced = 0;
+    std::vector<size_t> tables;                                 // where each table ends in recs
+    const char *error = nullptr;                                // the record the framing stopped at is not valid
+};
+class BamChunkSteps : public ReadChunkSteps<BamChunkSteps, BamWorker> {
 public:
-    struct Worker : ChunkWorker {
-        std::vector<ts_bgzf_block> descs;                       // the chunk's members: where they lie, how much they give
-        size_t at = 0, used = 0;
-        uint64_t produced = 0;
-        std::vector<ts_bam_record> recs, withSeq;               // the chunk's records, one walk's table behind the other
-        uint64_t n = 0, withBases = 0;                          // how many there are; how many of those judged so far had bases
-        std::vector<size_t> tables;                             // where each table ends in recs
-        const char *error = nullptr;                            // the record the framing stopped at is not valid
-    };
+    using Worker = BamWorker;
     BamSubsetStats stats;
-    double msWrite = 0;
-    std::vector<std::unique_ptr<Worker>> workers;
 
     BamChunkSteps(ReadTelomereFilter &filter, const unsigned char *data, size_t size, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, BamRecordWalk walk,
                   BamOutputDeflate deflate = BamOutputDeflate::Host, std::ostream *blocks = nullptr, const ReadFastqOutput *fastq = nullptr)
-        : data_(data), size_(size), writer_(out, fastq != nullptr), text_(out), fastq_(fastq != nullptr), fastqFlags_(fastq ? fastqOutFlags(*fastq) : 0u),
-          blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes),
+        : ReadChunkSteps(blocks, readsPerBatch), data_(data), size_(size), writer_(out, fastq != nullptr), text_(out), fastq_(fastq != nullptr),
+          fastqFlags_(fastq ? fastqOutFlags(*fastq) : 0u), chunkBytes_(chunkBytes),
           table_(std::min<size_t>(size_t(1) << 20, chunkBytes / 36 + 2)), walk_(walk), deflate_(deflate),
           plainCap_((256ull << 20) + 4 + chunkBytes), compCap_(chunkBytes + (1u << 20)) {
         for (size_t w = 0; w < filter.deviceCount(); ++w) {
@@ -2272,7 +2350,7 @@ public:
             if (header_.done() || header_.parse(have, bytesAt, pos, writer_)) {
                 head.clear(); head.shrink_to_fit();
                 walkRecords(k, pos);
-                judgeRecords(k, false);
+                judgeChunk(k, false);
                 emit(0, 0);
                 pos = prevNext_;
             } else {
@@ -2304,12 +2382,11 @@ public:
         walkRecords(k, 0);
         return !k.error;
     }
-    void judge(size_t w, uint64_t) { judgeRecords(*workers[w], true); }
-    // the chunk's turn to write: what it kept (nothing, where it came in place), its totals, and the record that is not valid
+    void judge(size_t w, uint64_t) { judgeChunk(*workers[w], true); }
+    // the chunk's turn to write: what it kept, its totals, and the record that is not valid
     void emit(size_t w, uint64_t) {
         Worker &k = *workers[w];
-        k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
-        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
+        emitKept(k);
         stats.blockLines += k.blockLines;
         stats.totalRecords += k.n;
         stats.missingSequenceRecords += k.n - k.withBases;
@@ -2323,6 +2400,53 @@ public:
         stats.missingEofBlock = !sawEofMarker_;
         writer_.finish();
         if (fastq_) { text_.flush(); if (!text_.good()) throw std::runtime_error("failed while writing BAM subset"); }
+    }
+
+    // The chunk's records in sub-batches, in input order.  A sub-batch never spans two tables of the walk, for any number of
+    // contexts: each table is cut into sub-batches of readsPerBatch on its own.  Under BamOutputDeflate::Device the passing bytes
+    // are finished BGZF members (ts_bam_chunk_gather_bgzf, payloads of 0xff00): a dealt chunk's compression runs here, on every
+    // context at once, and emit() only writes.
+    void judgeChunk(Worker &k, bool dealt) {
+        k.fresh();
+        size_t from = 0;
+        for (size_t end : k.tables) { judgeRecords(k, from, end, dealt); from = end; }
+    }
+
+    // the format's part of the shared steps
+    static uint64_t bases(const ts_bam_record &r) { return r.l_seq; }
+    static constexpr const char *stageFailed = "SEQ decode failed";
+    int stageReads(Worker &k, ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); }
+    int gatherKept(Worker &k, void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+        if (fastq_) return ts_bam_chunk_gather_fastq(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, fastqFlags_, dst, cap, bytes, nPassed, nullptr);
+        if (deflate_ == BamOutputDeflate::Host) return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+        const Clock::time_point t0 = Clock::now();
+        uint64_t plainBytes = 0;
+        const int rc = ts_bam_chunk_gather_bgzf(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, 0xff00u, dst, cap, bytes, nPassed, &plainBytes, nullptr);
+        k.st.msDeflate += since(t0);
+        if (rc == TS_OK) { k.st.deflatePlainBytes += plainBytes; k.st.deflateMemberBytes += *bytes; }
+        return rc;
+    }
+    // (a refused ts_bam_chunk_gather_bgzf has deflated already: the plain gather's plan, which a call without room stops at, says
+    // how many record bytes pass, and a member adds 31 bytes at the most)
+    uint64_t gatherRoom(Worker &k, void *dPass) {
+        if (fastq_ || deflate_ == BamOutputDeflate::Host) return 0;
+        uint64_t plain = 0, passed = 0;
+        const int rc = ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, nullptr, 0, &plain, &passed, nullptr);
+        if (rc != TS_OK && !(rc == TS_ERR_INVALID_ARG && plain > 0)) throw deviceError(k.ctx, "gather of the passing records failed");
+        return plain + 31u * ((plain + 0xff00u - 1) / 0xff00u);
+    }
+    int blockLines(Worker &k, ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+        return ts_bam_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+    }
+    // a sub-batch's passing records to the writer: plain bytes for zlib, or (Device) finished members
+    void write(const unsigned char *p, size_t n) {
+        const Clock::time_point t0 = Clock::now();
+        if (fastq_) {                                           // FASTQ text: as it is
+            text_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
+            if (!text_.good()) throw std::runtime_error("failed while writing BAM subset");
+        } else if (deflate_ == BamOutputDeflate::Host) writer_.write(p, n);
+        else if (n) writer_.writeMembers(p, n);
+        msWrite += since(t0);
     }
 
 private:
@@ -2375,80 +2499,14 @@ private:
         k.st.msWalk += since(t0);
         prev_ = &k; prevNext_ = pos;
     }
-    // The chunk's records in sub-batches, in input order.  A sub-batch never spans two tables of the walk, for any number of
-    // contexts: each table is cut into sub-batches of readsPerBatch on its own.  A dealt chunk keeps a sub-batch's passing bytes
-    // until its turn to emit; an in-place chunk has the turn, and they go from the judge straight to the writer.  Under
-    // BamOutputDeflate::Device the bytes are finished BGZF members (ts_bam_chunk_gather_bgzf, payloads of 0xff00): a dealt chunk's
-    // compression runs here, on every context at once, and emit() only writes.
-    void judgeRecords(Worker &k, bool dealt) {
-        k.fresh();
-        k.withBases = 0;
-        size_t from = 0;
-        for (size_t end : k.tables) {
-            for (size_t a = from; a < end; a += readsPerBatch_) {
-                const ts_bam_record *r = k.recs.data() + a;
-                const size_t n = std::min<size_t>(readsPerBatch_, end - a);
-                k.withSeq.clear(); k.lens.clear();
-                for (size_t i = 0; i < n; ++i) if (r[i].l_seq) { k.withSeq.push_back(r[i]); k.lens.push_back(r[i].l_seq); }
-                if (k.withSeq.empty()) continue;
-                k.withBases += k.withSeq.size();
-                k.st.recordsJudged += k.withSeq.size();
-                if (blocks_ && !k.judged.blockLines)
-                    k.judged.blockLines = [&k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
-                        return ts_bam_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
-                    };
-                k.judged.run(k.ctx, k.chunk, k.lens, "SEQ decode failed",
-                             [&](ts_batch *batch) { return ts_bam_chunk_decode(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
-                             [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                                 if (fastq_)
-                                     return ts_bam_chunk_gather_fastq(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, fastqFlags_, dst, cap, bytes, nPassed, nullptr);
-                                 if (deflate_ == BamOutputDeflate::Host)
-                                     return ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
-                                 const Clock::time_point t0 = Clock::now();
-                                 uint64_t plainBytes = 0;
-                                 const int rc = ts_bam_chunk_gather_bgzf(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, 0xff00u, dst, cap, bytes, nPassed,
-                                                                         &plainBytes, nullptr);
-                                 k.st.msDeflate += since(t0);
-                                 if (rc == TS_OK) { k.st.deflatePlainBytes += plainBytes; k.st.deflateMemberBytes += *bytes; }
-                                 return rc;
-                             },
-                             // (a refused ts_bam_chunk_gather_bgzf has deflated already: the plain gather's plan, which a call
-                             // without room stops at, says how many record bytes pass, and a member adds 31 bytes at the most)
-                             [&](void *dPass) -> uint64_t {
-                                 if (fastq_ || deflate_ == BamOutputDeflate::Host) return 0;
-                                 uint64_t plain = 0, passed = 0;
-                                 const int rc = ts_bam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, nullptr, 0, &plain, &passed, nullptr);
-                                 if (rc != TS_OK && !(rc == TS_ERR_INVALID_ARG && plain > 0)) throw deviceError(k.ctx, "gather of the passing records failed");
-                                 return plain + 31u * ((plain + 0xff00u - 1) / 0xff00u);
-                             });
-                k.passed += k.judged.nPassed;
-                k.blockLines += k.judged.nBlockLines;
-            if (dealt) k.keep();
-            else { write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
-            }
-            from = end;
-        }
-    }
-    // a sub-batch's passing records to the writer: plain bytes for zlib, or (Device) finished members
-    void write(const unsigned char *p, size_t n) {
-        const Clock::time_point t0 = Clock::now();
-        if (fastq_) {                                           // FASTQ text: as it is
-            text_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
-            if (!text_.good()) throw std::runtime_error("failed while writing BAM subset");
-        } else if (deflate_ == BamOutputDeflate::Host) writer_.write(p, n);
-        else if (n) writer_.writeMembers(p, n);
-        msWrite += since(t0);
-    }
-
     const unsigned char *data_;
     size_t size_;
     BgzfWriter writer_;
     std::ostream &text_;                                        // the output itself, for FASTQ text (writer_ then keeps nothing)
     bool fastq_;
     uint32_t fastqFlags_;
-    std::ostream *blocks_;                                      // the read block report's stream, or nothing
     BamHeaderParser header_;
-    size_t readsPerBatch_, chunkBytes_, table_;
+    size_t chunkBytes_, table_;
     BamRecordWalk walk_;
     BamOutputDeflate deflate_;
     uint64_t plainCap_, compCap_;
@@ -2544,25 +2602,7 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
 }
 inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
                                            size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks) {
-    const bool dealt = filter.deviceCount() > 1;
-    detail::ChunkFeed::Options options;
-    options.cannotOpen = "Stream not successful: " + inFile;
-    options.cannotRead = "read error in FASTQ input";
-    options.dashIsStdin = true;
-    options.uploadFailed = "upload of the FASTQ text failed";
-    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
-    detail::ChunkFeed feed(filter.context(0), inFile, options);
-    detail::FastqChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(bytesPerBatch, 64), blocks);
-    std::unique_ptr<detail::ChunkRing<detail::FastqChunkSteps>> ring;
-    if (dealt) {
-        ring.reset(new detail::ChunkRing<detail::FastqChunkSteps>(filter.deviceCount(), 0, steps));
-        ring->run();
-    } else {
-        steps.runInPlace();
-    }
-    out.flush();
-    detail::routeFigures(feed.deviceInflate() ? "fastqSubsetDevice (upload + inflate + CRC)" : "fastqSubsetDevice", steps.workers, ring.get(), steps.msWrite, perDevice);
-    return steps.res;
+    return detail::textSubsetDeviceRun<detail::FastqChunkSteps>("FASTQ", "fastqSubsetDevice", inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice, blocks);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2742,96 +2782,57 @@ inline SamSubsetStats samSubsetFastq(const std::string &inFile, std::ostream &ou
 
 namespace detail {
 
-// samSubsetDevice's stages, modelled on FastqChunkSteps.  ts_sam_chunk_walk frames the chunk's lines — the header lines in front
-// of it while the input's header goes on, then the records — and the unfinished last line goes in front of the next chunk.  A
-// line that fails a check ends the framing; its chunk's header lines and valid records are still written before emit() throws.  A
-// chunk that holds no whole line passes all of its contents on and grows as the FASTQ steps' chunks do.  Whether the input is
-// still in its header, and how many lines lie behind, is the framing's state: it moves on in the serial section only.
-class SamChunkSteps {
+// samSubsetDevice's stages: TextChunkSteps with the SAM framing.  ts_sam_chunk_walk frames the chunk's lines — the header lines in
+// front of it while the input's header goes on, then the records — and the unfinished last line goes in front of the next chunk.  A
+// line that fails a check ends the framing; its chunk's header lines and valid records are still written before emit() throws.
+// Whether the input is still in its header, and how many lines lie behind, is the framing's state: it moves on in the serial
+// section only.
+struct SamWorker : RecordWorker<ts_sam_record> {
+    ChunkFeed::Fill fill;                                       // a dealt chunk's new bytes
+    std::vector<char> header;                                   // the chunk's header lines as read, until they are written
+    uint64_t headerLines = 0;
+    int error = TS_SAM_OK;
+    uint64_t errorLine = 0;                                     // of the whole input, counted from 1
+};
+class SamChunkSteps : public TextChunkSteps<SamChunkSteps, SamWorker> {
 public:
-    struct Worker : ChunkWorker {
-        ChunkFeed::Fill fill;                                   // a dealt chunk's new bytes
-        std::vector<ts_sam_record> recs, withSeq;
-        std::vector<char> header;                               // the chunk's header lines as read, until they are written
-        uint64_t n = 0, headerLines = 0, missing = 0;           // records and header lines of the chunk; its records without sequence
-        int error = TS_SAM_OK;
-        uint64_t errorLine = 0;                                 // of the whole input, counted from 1
-    };
-    SamSubsetStats stats;
-    double msWrite = 0;
-    std::vector<std::unique_ptr<Worker>> workers;
+    using Worker = SamWorker;
+    SamSubsetStats result;
 
     SamChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr,
                   const ReadFastqOutput *fastq = nullptr)
-        : feed_(feed), out_(out), blocks_(blocks), fastq_(fastq != nullptr), fastqFlags_(fastq ? fastqOutFlags(*fastq) : 0u),
-          readsPerBatch_(std::max<size_t>(readsPerBatch, 1)), chunkBytes_(chunkBytes) {
-        const uint64_t compCap = feed.compCap(chunkBytes);
-        for (size_t w = 0; w < filter.deviceCount(); ++w) {
-            workers.emplace_back(new Worker());
-            Worker &k = *workers.back();
-            k.ctx = filter.context(w);
-            k.chunk = ts_bam_chunk_create(k.ctx, compCap, chunkBytes);
-            if (!k.chunk) throw deviceError(k.ctx, "cannot make the device chunk");
-            k.recs.resize(std::min<size_t>(size_t(1) << 20, chunkBytes / 64 + 16));
-        }
-    }
+        : TextChunkSteps(filter, feed, out, readsPerBatch, chunkBytes, blocks, "failed while writing SAM subset"), fastq_(fastq != nullptr),
+          fastqFlags_(fastq ? fastqOutFlags(*fastq) : 0u) {}
 
-    // The whole input as in-place chunks of context 0, on the caller's thread: any source of the feed, ChunkFeed::Gzip included
-    void runInPlace() {
-        Worker &k = *workers[0];
-        for (bool atEnd = false; !atEnd;) {
-            const uint64_t carry = ts_bam_chunk_size(k.chunk) - prevNext_;
-            // a chunk that held no whole line takes as much again
-            const size_t want = static_cast<size_t>(std::max<uint64_t>(chunkBytes_, prevNext_ == 0 ? carry : 0));
-            const Clock::time_point t0 = Clock::now();
-            atEnd = feed_.fill(k.chunk, prevNext_, want);
-            k.st.msSource += since(t0);
-            ++k.st.chunks; k.st.bytesReceived += ts_bam_chunk_size(k.chunk) - carry;
-            frameLines(k, atEnd);
-            judgeRecords(k, false);
-            emit(0, 0);
-        }
+    // an in-place chunk has the turn to write: its header lines, then the passing bytes, go straight to the output
+    void judgeChunk(Worker &k, bool dealt) {
+        if (!dealt) writeHeader(k);
+        TextChunkSteps::judgeChunk(k, dealt);
     }
-
-    // the ring's steps: a dealt chunk
-    void begin(size_t w) { ts_bind_thread_to_device(workers[w]->ctx); }
-    RingTake take(size_t w, uint64_t) {
-        Worker &k = *workers[w];
-        const Clock::time_point t0 = Clock::now();
-        feed_.take(chunkBytes_, k.fill);
-        k.st.msSource += since(t0);
-        return k.fill.atEnd ? RingTake::Last : RingTake::More;
-    }
-    void stage(size_t w, uint64_t) {
-        Worker &k = *workers[w];
-        const Clock::time_point t0 = Clock::now();
-        feed_.stage(k.ctx, k.chunk, k.fill);
-        k.st.msSource += since(t0);
-        ++k.st.chunks; k.st.bytesReceived += k.fill.n;
-    }
-    bool frame(size_t w, uint64_t) {                            // the serial section: carry, commit, ts_sam_chunk_walk, the header state
-        Worker &k = *workers[w];
-        ringCommit(k, prev_, prevNext_);
-        return frameLines(k, k.fill.atEnd);
-    }
-    void judge(size_t w, uint64_t) { judgeRecords(*workers[w], true); }
     // the chunk's turn to write: its header lines and what it kept (nothing, where it came in place), its totals, and the line
     // that is not valid
     void emit(size_t w, uint64_t) {
         Worker &k = *workers[w];
         writeHeader(k);
-        k.pieces([&](const unsigned char *p, size_t n) { write(p, n); });
-        ChunkWorker::writeBlocks(blocks_, k.blockOut.data(), k.blockOut.size());
-        stats.blockLines += k.blockLines;
-        stats.headerLines += k.headerLines; stats.totalRecords += k.n; stats.passedRecords += k.passed; stats.missingSequenceRecords += k.missing;
+        emitKept(k);
+        result.blockLines += k.blockLines;
+        result.headerLines += k.headerLines; result.totalRecords += k.n; result.passedRecords += k.passed; result.missingSequenceRecords += k.n - k.withBases;
         if (k.error != TS_SAM_OK) { out_.flush(); throw samLineError(k.errorLine, k.error); }
     }
 
-private:
-    // The lines of a chunk that has its bytes; the framing's state moves on to it.  -> every line up to the chunk's end is valid
-    bool frameLines(Worker &k, bool atEnd) {
-        prev_ = &k; prevNext_ = 0;
-        k.n = k.headerLines = k.missing = 0; k.error = TS_SAM_OK; k.header.clear();
+    // the format's part of the shared steps
+    static uint64_t bases(const ts_sam_record &r) { return (r.flags & 1u) ? 0 : r.seq_len; }      // (SEQ is "*": never kept)
+    static constexpr const char *stageFailed = "staging the sequences failed";
+    int stageReads(Worker &k, ts_batch *batch) { return ts_sam_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); }
+    int gatherKept(Worker &k, void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+        if (fastq_) return ts_sam_chunk_gather_fastq(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, fastqFlags_, dst, cap, bytes, nPassed, nullptr);
+        return ts_sam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+    }
+    int blockLines(Worker &k, ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+        return ts_sam_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+    }
+    bool frameChunk(Worker &k, bool atEnd) {
+        k.n = k.headerLines = 0; k.error = TS_SAM_OK; k.header.clear();
         if (first_) {
             if (ts_bam_chunk_size(k.chunk) == 0) {
                 if (atEnd) throw std::runtime_error("SAM input is empty");
@@ -2861,89 +2862,25 @@ private:
         if (k.headerLines < nLines || k.error != TS_SAM_OK) inHeader_ = false;
         return k.error == TS_SAM_OK;
     }
-    // The chunk's records in sub-batches, in input order.  A dealt chunk keeps a sub-batch's passing bytes until its turn to emit;
-    // an in-place chunk has the turn: its header lines, then the passing bytes, go straight to the output.
-    void judgeRecords(Worker &k, bool dealt) {
-        k.fresh();
-        if (!dealt) writeHeader(k);
-        for (size_t a = 0; a < k.n; a += readsPerBatch_) {
-            const ts_sam_record *r = k.recs.data() + a;
-            const size_t n = std::min<size_t>(readsPerBatch_, static_cast<size_t>(k.n) - a);
-            k.withSeq.clear(); k.lens.clear();
-            for (size_t i = 0; i < n; ++i) {
-                if (r[i].flags & 1u) { ++k.missing; continue; }     // (SEQ is "*": never kept)
-                k.withSeq.push_back(r[i]); k.lens.push_back(r[i].seq_len);
-            }
-            if (k.withSeq.empty()) continue;
-            k.st.recordsJudged += k.withSeq.size();
-            if (blocks_ && !k.judged.blockLines)
-                k.judged.blockLines = [&k](ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
-                    return ts_sam_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
-                };
-            k.judged.run(k.ctx, k.chunk, k.lens, "staging the sequences failed",
-                         [&](ts_batch *batch) { return ts_sam_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, nullptr); },
-                         [&](void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
-                             if (fastq_)
-                                 return ts_sam_chunk_gather_fastq(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, fastqFlags_, dst, cap, bytes, nPassed, nullptr);
-                             return ts_sam_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
-                         });
-            k.passed += k.judged.nPassed;
-            k.blockLines += k.judged.nBlockLines;
-            if (dealt) k.keep();
-            else { write(k.judged.kept.data(), static_cast<size_t>(k.judged.bytes)); ChunkWorker::writeBlocks(blocks_, k.judged.blockText.data(), static_cast<size_t>(k.judged.blockBytes)); }
-        }
-    }
+
+private:
     void writeHeader(Worker &k) {
         if (k.header.empty()) return;
         write(reinterpret_cast<const unsigned char *>(k.header.data()), k.header.size());
         k.header.clear();
     }
-    void write(const unsigned char *p, size_t n) {
-        const Clock::time_point t0 = Clock::now();
-        out_.write(reinterpret_cast<const char *>(p), static_cast<std::streamsize>(n));
-        if (!out_.good()) throw std::runtime_error("failed while writing SAM subset");
-        msWrite += since(t0);
-    }
 
-    ChunkFeed &feed_;
-    std::ostream &out_;
-    std::ostream *blocks_;                                      // the read block report's stream, or nothing
     bool fastq_;                                                // the kept records leave as FASTQ text (ts_sam_chunk_gather_fastq)
     uint32_t fastqFlags_;
-    size_t readsPerBatch_, chunkBytes_;
-    // the framing's state: the chunk framed last and where its unfinished line begins; nothing framed yet held a byte; the input
-    // is still in its header; whole lines behind
-    const ChunkWorker *prev_ = nullptr;
-    uint64_t prevNext_ = 0;
-    bool first_ = true, inHeader_ = true;
+    // more of the framing's state: the input is still in its header; whole lines behind
+    bool inHeader_ = true;
     uint64_t lines_ = 0;
 };
 
-}  // namespace detail
-
-namespace detail {
 // (the route itself, behind samSubsetDevice and samSubsetFastqDevice)
 inline SamSubsetStats samSubsetDeviceRun(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch, size_t chunkBytes,
                                          std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks, const ReadFastqOutput *fastq) {
-    const bool dealt = filter.deviceCount() > 1;
-    detail::ChunkFeed::Options options;
-    options.cannotOpen = "Stream not successful: " + inFile;
-    options.cannotRead = "read error in SAM input";
-    options.dashIsStdin = true;
-    options.uploadFailed = "upload of the SAM text failed";
-    if (dealt) options.gzipDevice = false;                      // (bound to one context: plain gzip is read through zlib)
-    detail::ChunkFeed feed(filter.context(0), inFile, options);
-    detail::SamChunkSteps steps(filter, feed, out, readsPerBatch, std::max<size_t>(chunkBytes, 64), blocks, fastq);
-    std::unique_ptr<detail::ChunkRing<detail::SamChunkSteps>> ring;
-    if (dealt) {
-        ring.reset(new detail::ChunkRing<detail::SamChunkSteps>(filter.deviceCount(), 0, steps));
-        ring->run();
-    } else {
-        steps.runInPlace();
-    }
-    out.flush();
-    detail::routeFigures(feed.deviceInflate() ? "samSubsetDevice (upload + inflate + CRC)" : "samSubsetDevice", steps.workers, ring.get(), steps.msWrite, perDevice);
-    return steps.stats;
+    return textSubsetDeviceRun<SamChunkSteps>("SAM", "samSubsetDevice", inFile, out, filter, readsPerBatch, chunkBytes, perDevice, blocks, fastq);
 }
 }  // namespace detail
 // The device route of --sam-subset (same arguments, result, exceptions and output bytes as samSubset): the SAM text exists in HBM
@@ -4173,10 +4110,7 @@ public:
         const uint64_t carry = prevSize_ - prevNext_;
         // (refused before the carry is copied, so that a copy of that size cannot fail first; the name is read where it lies)
         if (prev_ && carry >= chunkLimit_) throw doesNotFit(*prev_, prevNext_, carry);
-        const Clock::time_point t0 = Clock::now();
-        if (prev_ && ts_chunk_carry_over(k.chunk, prev_->chunk, prevNext_, nullptr) != TS_OK) throw deviceError(k.ctx, "cannot carry a record into the next device chunk");
-        if (ts_chunk_commit(k.chunk, nullptr) != TS_OK) throw deviceError(k.ctx, "cannot grow the device chunk");
-        k.st.msCommit += since(t0);
+        ringCommit(k, prev_, prevNext_);
         k.atEnd = k.fill.atEnd;
         k.n = 0;
         prev_ = &k; prevNext_ = 0; prevSize_ = ts_bam_chunk_size(k.chunk);

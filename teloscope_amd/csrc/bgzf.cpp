@@ -76,7 +76,6 @@ extern "C" int ts_bgzf_inflate(ts_ctx *ctx, const void *compressed, uint64_t n, 
 // ===================================================================== the resident form: a chunk of a BAM on the device
 // (struct ts_bam_chunk: chunk_internal.h; the object itself: chunk.cpp)
 namespace {
-struct DecodeJobHost { uint64_t src, dst; uint32_t n, pad; };
 constexpr uint32_t kDecodePiece = 2048;
 
 // a record of the table against the chunk: inside it, SEQ inside the record
@@ -272,33 +271,13 @@ int ts_bam_index_stats(const ts_ctx *ctx, uint64_t out[6]) {
 
 int ts_bam_chunk_decode(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, ts_batch *reads, void *stream) {
     if (!ch) return TS_ERR_INVALID_ARG;
-    ts_ctx *ctx = ch->ctx;
-    if (!reads || (n && !recs) || reads->ctx != ctx || !reads->tips || !reads->whole() || reads->segs.size() != n)
-        return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: needs an unrestricted tips-only batch of this context with one segment per record");
-    std::vector<DecodeJobHost> jobs;
-    for (size_t i = 0; i < n; ++i) {
-        const ts_bam_record &r = recs[i];
-        if (!record_ok(ch, r) || r.l_seq == 0 || reads->segs[i].len != r.l_seq)
-            return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: record " + std::to_string(i) + " does not fit the chunk or its segment");
-        const uint64_t dst = ts_batch_segment_offset(reads, i);
-        for (uint32_t a = 0; a < r.l_seq; a += kDecodePiece)
-            jobs.push_back(DecodeJobHost{r.off + r.seq_at + a / 2, dst + a, std::min(kDecodePiece, r.l_seq - a), 0});
-    }
-    if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_bam_chunk_decode: too many bases for one call");
-    DEVICE_TRY(ctx);
-    const bool fresh = reads->d_in.p == nullptr;
-    void *in = ts_batch_input_ptr(reads);
-    if (!in) return ctx->fail(TS_ERR_ALLOC, "ts_bam_chunk_decode: no input buffer");
-    if (jobs.empty()) return TS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // (a fresh input buffer was just zeroed on the null stream, which a non-blocking `stream` does not wait for)
-    if (fresh && st) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-    HIP_TRY(ctx, ch->bam.d_jobs.ensure(jobs.size() * sizeof(DecodeJobHost)));
-    HIP_TRY(ctx, hipMemcpyAsync(ch->bam.d_jobs.p, jobs.data(), jobs.size() * sizeof(DecodeJobHost), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (ts_k_launch_bam_decode(ch->d_plain.p, ch->bam.d_jobs.p, (uint32_t)jobs.size(), in, stream) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_bam_chunk_decode: kernel launch failed");
-    return TS_OK;
+    // (a job's kDecodePiece bases are packed two to a byte)
+    return ts_chunk_stage_records(ch, "ts_bam_chunk_decode", recs, n, reads, stream, kDecodePiece, kDecodePiece / 2,
+                                  [](const ts_bam_chunk *c, const void *table, size_t i, uint64_t *src, uint32_t *len) {
+                                      const ts_bam_record &r = ((const ts_bam_record *)table)[i];
+                                      *src = (uint64_t)r.off + r.seq_at; *len = r.l_seq;
+                                      return record_ok(c, r);
+                                  }, ts_k_launch_bam_decode);
 }
 
 int ts_bam_chunk_gather(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, const void *d_pass, void *host_out, uint64_t cap,

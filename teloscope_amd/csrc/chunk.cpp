@@ -1,6 +1,6 @@
 // chunk.cpp — the chunk object of the device routes (chunk_internal.h; include/teloscan.h: ts_bam_chunk_create / _destroy / _size /
 // _read / _pass_buffer, ts_chunk_*): its buffers, how bytes get into it and are carried from one chunk to the next, the line index
-// of the three text walks and the gather of the two record routes.  What a route makes of the bytes is the route's file.
+// of the three text walks, the stage and the gather of the record routes.  What a route makes of the bytes is the route's file.
 #include "chunk_internal.h"
 
 int ts_chunk_carry(ts_bam_chunk *ch, uint64_t carry_from, hipStream_t st, uint64_t *carry_out) {
@@ -99,6 +99,37 @@ int ts_chunk_gather(ts_bam_chunk *ch, const char *who, const void *recs, size_t 
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(ctx, hipMemcpyAsync(host_out, ch->d_gather.p, (size_t)*bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    return TS_OK;
+}
+
+int ts_chunk_stage_records(ts_bam_chunk *ch, const char *who, const void *recs, size_t n, ts_batch *reads, void *stream, uint32_t piece,
+                           uint32_t src_step, ts_chunk_stage_record record, ts_chunk_stage_launch launch) {
+    ts_ctx *ctx = ch->ctx;
+    const std::string name = who;
+    if (!reads || (n && !recs) || reads->ctx != ctx || !reads->tips || !reads->whole() || reads->segs.size() != n)
+        return ctx->fail(TS_ERR_INVALID_ARG, name + ": needs an unrestricted tips-only batch of this context with one segment per record");
+    std::vector<ChunkStageJob> jobs;
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t src = 0;
+        uint32_t len = 0;
+        if (!record(ch, recs, i, &src, &len) || len == 0 || reads->segs[i].len != len)
+            return ctx->fail(TS_ERR_INVALID_ARG, name + ": record " + std::to_string(i) + " does not fit the chunk or its segment");
+        const uint64_t dst = ts_batch_segment_offset(reads, i);
+        for (uint32_t a = 0; a < len; a += piece, src += src_step) jobs.push_back(ChunkStageJob{src, dst + a, std::min(piece, len - a), 0});
+    }
+    if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, name + ": too many bases for one call");
+    DEVICE_TRY(ctx);
+    const bool fresh = reads->d_in.p == nullptr;
+    void *in = ts_batch_input_ptr(reads);
+    if (!in) return ctx->fail(TS_ERR_ALLOC, name + ": no input buffer");
+    if (jobs.empty()) return TS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // (a fresh input buffer was just zeroed on the null stream, which a non-blocking `stream` does not wait for)
+    if (fresh && st) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+    HIP_TRY(ctx, ch->d_jobs.ensure(jobs.size() * sizeof(ChunkStageJob)));
+    HIP_TRY(ctx, hipMemcpyAsync(ch->d_jobs.p, jobs.data(), jobs.size() * sizeof(ChunkStageJob), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (launch(ch->d_plain.p, ch->d_jobs.p, (uint32_t)jobs.size(), in, stream) != 0) return ctx->fail(TS_ERR_HIP, name + ": kernel launch failed");
     return TS_OK;
 }
 

@@ -26,8 +26,9 @@ struct ts_bam_chunk {
     uint64_t plain_n = 0;               // bytes the chunk holds: the carried tail, then the members' output or the uploaded bytes
     size_t n_blocks = 0;                // members of the last inflate, judged by ts_bam_chunk_status (0: the bytes came another way)
     // the compressed and the plain bytes (both readable 64 bytes beyond their capacity), the carry's bounce buffer, a result block
-    // of 64 bytes, the caller's pass bytes; the record table of a walk or a gather, the passing records' places and bytes
-    DevBuf d_comp, d_plain, d_tmp, d_out, d_pass, d_recs, d_dst, d_gather;
+    // of 64 bytes, the caller's pass bytes; the record table of a walk or a gather, the passing records' places and bytes; the
+    // jobs of a stage (ts_chunk_stage_records)
+    DevBuf d_comp, d_plain, d_tmp, d_out, d_pass, d_recs, d_dst, d_gather, d_jobs;
     // the staging region (ts_chunk_stage_upload / ts_chunk_stage_inflate): new bytes that wait for the carry they go behind
     // (ts_chunk_commit); readable 64 bytes beyond stage_cap, as d_plain is
     DevBuf d_stage;
@@ -41,18 +42,18 @@ struct ts_bam_chunk {
         int at_end = 0;
         uint64_t size = 0, generation = 0;
     } lines;
-    // ---- BAM (bgzf.cpp): the members' descriptors and verdicts, the decode's jobs; the parallel record index
+    // ---- BAM (bgzf.cpp): the members' descriptors and verdicts; the parallel record index
     // (ts_bam_chunk_index): its span size (log2) and candidates per span, the candidate rows, the tasks of the write pass, and the
     // host copy of the rows
     struct Bam {
-        DevBuf d_blocks, d_result, d_jobs;
+        DevBuf d_blocks, d_result;
         uint32_t index_span_log2 = 18, index_candidates = 4;
         DevBuf d_idx_rows, d_idx_tasks;
         std::vector<unsigned char> h_idx_rows;
         DeflateBufs deflate;                // ts_bam_chunk_gather_bgzf's buffers (deflate.cpp)
     } bam;
-    // ---- FASTQ (fastq.cpp): the framing results and the stage's jobs
-    struct Fastq { DevBuf d_frames, d_jobs; } fastq;
+    // ---- FASTQ (fastq.cpp): the framing results
+    struct Fastq { DevBuf d_frames; } fastq;
     // ---- FASTA (fasta.cpp): the header counts per slice, the walk's header table, record table and names; the join's jobs, their
     // counts, the joined bases and runs; a byte per record of the strict check
     struct Fasta {
@@ -67,8 +68,8 @@ struct ts_bam_chunk {
         uint64_t lines_generation = 0, n_tabs = 0;
     } gfa;
     // ---- SAM (sam.cpp): the tab counts per slice and the tabs' offsets, the alignment lines per slice of lines, the walk's
-    // result block of 64 bytes; the stage's jobs
-    struct Sam { DevBuf d_counts, d_tabs, d_frames, d_out, d_jobs; } sam;
+    // result block of 64 bytes
+    struct Sam { DevBuf d_counts, d_tabs, d_frames, d_out; } sam;
     // ---- the read block report (read_blocks.cpp): the record table of a *_block_lines call, the segments' name entries, the
     // workgroups' sums and the text
     struct Blocks { DevBuf d_recs, d_segs, d_sums, d_text; } blocks;
@@ -108,6 +109,17 @@ int  ts_chunk_gather(ts_bam_chunk *ch, const char *who, const void *recs, size_t
 int  ts_chunk_gather_device(ts_bam_chunk *ch, const char *who, const void *recs, size_t rec_bytes, size_t n, const void *d_pass,
                             uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream, ts_chunk_plan_launch plan,
                             ts_chunk_copy_launch copy);
+
+// The host half of ts_fastq_chunk_stage, ts_sam_chunk_stage and ts_bam_chunk_decode behind their null check: `reads` must be an
+// unrestricted tips-only batch of the chunk's context with one segment per record; record(ch, recs, i, &src, &len) holds record i
+// against the chunk by the route's rule and says where its len bases begin in the chunk; every record becomes jobs of `piece` bases
+// whose sources lie src_step bytes apart; the jobs go up into ch->d_jobs and `launch` is called on `stream` (not waited for).
+// Failures are "<who>: ...".
+struct ChunkStageJob { unsigned long long src, dst; uint32_t n, pad; };     // n bases from plain + src -> in + dst (16-byte aligned)
+typedef bool (*ts_chunk_stage_record)(const ts_bam_chunk *ch, const void *recs, size_t i, uint64_t *src, uint32_t *len);
+typedef int (*ts_chunk_stage_launch)(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream);
+int  ts_chunk_stage_records(ts_bam_chunk *ch, const char *who, const void *recs, size_t n, ts_batch *reads, void *stream, uint32_t piece,
+                            uint32_t src_step, ts_chunk_stage_record record, ts_chunk_stage_launch launch);
 
 // ---- deflate.cpp
 // d_plain[0, n) (device memory of ctx's device) cut into payloads of payload_bytes (1 .. 0xff00), each deflated into one BGZF

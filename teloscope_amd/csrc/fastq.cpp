@@ -81,34 +81,12 @@ int ts_fastq_chunk_walk(ts_chunk *ch, int at_end, ts_fastq_record *recs, uint64_
 
 int ts_fastq_chunk_stage(ts_chunk *ch, const ts_fastq_record *recs, size_t n, ts_batch *reads, void *stream) {
     if (!ch) return TS_ERR_INVALID_ARG;
-    ts_ctx *ctx = ch->ctx;
-    if (!reads || (n && !recs) || reads->ctx != ctx || !reads->tips || !reads->whole() || reads->segs.size() != n)
-        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_stage: needs an unrestricted tips-only batch of this context with one segment per record");
-    std::vector<FastqCopyJob> jobs;
-    for (size_t i = 0; i < n; ++i) {
-        const ts_fastq_record &r = recs[i];
-        const uint32_t bases = r.seq_len - r.seq_cr;
-        if (!record_ok(ch, r) || bases == 0 || reads->segs[i].len != bases)
-            return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_stage: record " + std::to_string(i) + " does not fit the chunk or its segment");
-        const uint64_t dst = ts_batch_segment_offset(reads, i);
-        for (uint32_t a = 0; a < bases; a += kFastqStagePiece)
-            jobs.push_back(FastqCopyJob{r.off + r.seq_at + a, dst + a, std::min(kFastqStagePiece, bases - a), 0});
-    }
-    if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_stage: too many bases for one call");
-    DEVICE_TRY(ctx);
-    const bool fresh = reads->d_in.p == nullptr;
-    void *in = ts_batch_input_ptr(reads);
-    if (!in) return ctx->fail(TS_ERR_ALLOC, "ts_fastq_chunk_stage: no input buffer");
-    if (jobs.empty()) return TS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // (a fresh input buffer was just zeroed on the null stream, which a non-blocking `stream` does not wait for)
-    if (fresh && st) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-    HIP_TRY(ctx, ch->fastq.d_jobs.ensure(jobs.size() * sizeof(FastqCopyJob)));
-    HIP_TRY(ctx, hipMemcpyAsync(ch->fastq.d_jobs.p, jobs.data(), jobs.size() * sizeof(FastqCopyJob), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (ts_k_launch_fastq_stage(ch->d_plain.p, ch->fastq.d_jobs.p, (uint32_t)jobs.size(), in, stream) != 0)
-        return ctx->fail(TS_ERR_HIP, "ts_fastq_chunk_stage: kernel launch failed");
-    return TS_OK;
+    return ts_chunk_stage_records(ch, "ts_fastq_chunk_stage", recs, n, reads, stream, kFastqStagePiece, kFastqStagePiece,
+                                  [](const ts_bam_chunk *c, const void *table, size_t i, uint64_t *src, uint32_t *len) {
+                                      const ts_fastq_record &r = ((const ts_fastq_record *)table)[i];
+                                      *src = (uint64_t)r.off + r.seq_at; *len = r.seq_len - r.seq_cr;
+                                      return record_ok(c, r);
+                                  }, ts_k_launch_fastq_stage);
 }
 
 int ts_fastq_chunk_gather(ts_chunk *ch, const ts_fastq_record *recs, size_t n, const void *d_pass, void *host_out, uint64_t cap,

@@ -12,7 +12,7 @@ constexpr uint32_t kFastqStagePiece = 8192;         // bytes of a sequence a wav
 enum { kFqHeaders = kChunkLineWords, kFqError, kFqOpen, kFqOpenOff, kFqLastLine, kFqWords };
 struct FastqFrame { uint32_t map, cnt[4], pad[3]; };        // a slice of lines: its transition map, its headers per entry state
 struct FastqEntry { uint32_t state, base; };                // a slice's entry state and the index of its first record
-struct FastqCopyJob { unsigned long long src, dst; uint32_t n, pad; };       // n bytes at plain + src -> in + dst (16-byte aligned)
+using FastqCopyJob = ChunkStageJob;                         // the stage kernel's job: n bytes at plain + src -> in + dst
 
 extern "C" {
 // the framing automaton over n_lines lines: frames per slice of kFastqSliceLines, their scan (entry states and record bases,

@@ -2,8 +2,9 @@
 // several contexts, through the host route (samSubset: lines and fields found on the host) or the device route (samSubsetDevice:
 // lines and tabs indexed, lines cut and checked, sequences staged and passing lines gathered on the GPU), so that the two can be
 // compared on the same input by the same binary.
-// Usage: sam_device_cli --sam-subset [--device|--host] [--devices 0,0,0] [--chunk-bytes N] [--reads-per-batch N]
+// Usage: sam_device_cli --sam-subset [--device|--host] [--devices 0,0,0] [--chunk-bytes N] [--reads-per-batch N] [--figures]
 //                       [-c -p -x -l -y -k -d -t ...] [file|-]          (no file: stdin)
+//        --figures: the device route's per-context figures on stderr, a JSON line per context, before the closing line
 //        sam_device_cli --sam-subset ... --each LIST   every file named in LIST through one filter: <file>.out and <file>.ok (the
 //                                                      statistics), or <file>.err with the message and <file>.partial with what was
 //                                                      written before it; a line "<file" puts the file on descriptor 0 and runs
@@ -42,7 +43,7 @@ static int dumpRecords(const std::string &path) {
 int main(int argc, char **argv) {
     UserInputTeloscope ui;
     std::string input, canonical, each, dump;
-    bool samSubsetMode = false, device = true;
+    bool samSubsetMode = false, device = true, perContext = false;
     size_t readsPerBatch = 1u << 20, chunkBytes = 0;
     std::vector<int> devices;
     std::vector<std::string> rawPatterns;
@@ -60,6 +61,7 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = true;
         else if (a == "--host") device = false;
         else if (a == "--each") each = val();
+        else if (a == "--figures") perContext = true;
         else if (a == "--devices") list(val(), [&](const std::string &x) { devices.push_back(std::stoi(x)); });
         else if (a == "--reads-per-batch") readsPerBatch = static_cast<size_t>(std::stoull(val()));
         else if (a == "--chunk-bytes") chunkBytes = static_cast<size_t>(std::stoull(val()));
@@ -84,8 +86,9 @@ int main(int argc, char **argv) {
         ReadTelomereFilter filter(ui, devices);                 // (no device: throws — there is no host scan behind either route)
         filter.bindThreadToDevice();
         const size_t chunk = chunkBytes ? chunkBytes : size_t(256) << 20;
+        std::vector<ReadRouteDeviceStats> per;
         auto subset = [&](const std::string &path, std::ostream &out) {
-            return device ? samSubsetDevice(path, out, filter, readsPerBatch, chunk) : samSubset(path, out, filter, readsPerBatch, chunk);
+            return device ? samSubsetDevice(path, out, filter, readsPerBatch, chunk, perContext ? &per : nullptr) : samSubset(path, out, filter, readsPerBatch, chunk);
         };
         auto figures = [](const SamSubsetStats &s) {
             char line[200];
@@ -119,6 +122,9 @@ int main(int argc, char **argv) {
         }
         const SamSubsetStats s = subset(input, std::cout);
         std::cout.flush();
+        for (const ReadRouteDeviceStats &c : per)
+            fprintf(stderr, "{\"chunks\": %llu, \"recordsJudged\": %llu, \"bytesReceived\": %llu, \"msCommit\": %.3f, \"msCarryWait\": %.3f}\n",
+                    (unsigned long long)c.chunks, (unsigned long long)c.recordsJudged, (unsigned long long)c.bytesReceived, c.msCommit, c.msCarryWait);
         fprintf(stderr, "%s\n", figures(s).c_str());
         return 0;
     } catch (const std::exception &e) {

@@ -4,6 +4,7 @@ was written before it — and both against the rule's plain-Python restatement (
 oracle's read filter.  Inputs go through --each, many files per process, so a test opens a handful of processes; every process
 is one bounded step.  The stages are compared one by one in tests/test_gpu_sam_chunk.py."""
 import gzip
+import json
 import os
 import subprocess
 
@@ -196,6 +197,37 @@ def test_context_counts(dcli, tmp_path, chunk):
         got = run_each(dcli, tmp_path, list(files.values()), route + args, timeout=300)
         for key, entry in files.items():
             assert got[entry] == want[key], (who, key, got[entry][0], got[entry][2], want[key][2])
+
+
+# What sam_device_cli of the commit before the shared chunk steps (173634d, with nothing but the --figures switch added) reports
+# as `chunks` on one context for the input and flags of test_per_context_figures.
+PARENT_CHUNKS = 53
+
+
+def test_per_context_figures(dcli, tmp_path):
+    """--figures on one, two and three contexts: together the contexts judged every record that has a sequence and received every
+    byte of the text, each of them judged something and the chunks are dealt evenly; one context takes every chunk in place (no
+    commit, no wait for a turn), in the chunks the parent commit cut."""
+    text = S.generated(41, 150, 30, 1500)
+    recs = S.ref_walk(text, True, True)[0]
+    with_seq = sum(1 for r in recs if not r[4] & S.SEQ_IS_STAR)
+    assert 0 < with_seq < len(recs)
+    p = tmp_path / "reads.sam"
+    p.write_bytes(text)
+    for devices in ("0", "0,0", "0,0,0"):
+        r = subprocess.run([dcli, "--sam-subset", "--device", "--devices", devices, "--figures", "-l", "42", "--chunk-bytes", "4096",
+                            "--reads-per-batch", "37", str(p)], stdin=subprocess.DEVNULL, capture_output=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-300:]
+        ctxs = [json.loads(line) for line in r.stderr.decode().splitlines() if line.startswith("{")]
+        print(devices, ctxs)
+        assert len(ctxs) == devices.count(",") + 1
+        assert sum(c["recordsJudged"] for c in ctxs) == with_seq and sum(c["bytesReceived"] for c in ctxs) == len(text)
+        assert all(c["recordsJudged"] > 0 for c in ctxs), ctxs
+        chunks = [c["chunks"] for c in ctxs]
+        assert max(chunks) - min(chunks) <= 1, chunks
+        if len(ctxs) == 1:
+            assert ctxs[0]["msCommit"] == 0.0 and ctxs[0]["msCarryWait"] == 0.0, ctxs
+            assert chunks == [PARENT_CHUNKS]
 
 
 def test_plain_gzip_inflated_on_the_device(dcli, tmp_path, monkeypatch):
