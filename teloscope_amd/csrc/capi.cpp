@@ -26,6 +26,7 @@
 #include <sys/mman.h>
 
 #include "capi_internal.hpp"
+#include "general_plan_core.h"
 
 namespace {
 
@@ -894,20 +895,13 @@ ts_batch *ts_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t 
         sp.in_off = off;
         off += (sp.len + 15) & ~15ull;
         sp.first_tile = (uint32_t)b->tiles.size();
-        if (b->tips) {
-            const uint32_t twice = 2u * tl;             // uint32 product, as src/teloscope.cpp:576
-            if (sp.len > twice) {
-                add_region_tiles(b, sp, (uint32_t)i, 0, tl, tile_bases, 1, false);
-                add_region_tiles(b, sp, (uint32_t)i, sp.len - tl, tl, tile_bases, 1, false);
-            } else if (sp.len > 0) {
-                add_region_tiles(b, sp, (uint32_t)i, 0, sp.len, tile_bases, 1, false);
-            }
-        } else {
+        if (!b->tips) {
             sp.win_base = wins;
             sp.n_windows = ceil_div(sp.len, ctx->params.step);
             wins += sp.n_windows;
-            if (sp.len > 0) add_region_tiles(b, sp, (uint32_t)i, 0, sp.len, tile_bases, wpt, true);
         }
+        for (const tsplan::Span &r : tsplan::scanned_regions(sp.len, b->tips, tl))
+            add_region_tiles(b, sp, (uint32_t)i, r.start, r.len, tile_bases, b->tips ? 1 : wpt, !b->tips);
         sp.n_tiles = (uint32_t)b->tiles.size() - sp.first_tile;
         b->total_bases += sp.len;
     }
@@ -1552,13 +1546,8 @@ int device_block_call(ts_batch *b, hipStream_t st, std::vector<TsDevBlock> &bloc
     // segment table of the kernels (a whole batch: every segment with all its tiles, both ends its own)
     std::vector<TsShardSegIn> tab(ns);
     for (size_t i = 0; i < ns; ++i) {
-        TsShardSegIn &S = tab[i];
-        S.in_off = b->segs[i].in_off; S.len = b->segs[i].len; S.abs_pos = b->segs[i].abs_pos;
-        S.t0 = S.o0 = b->segs[i].first_tile;
-        S.t1 = S.o1 = b->segs[i].first_tile + b->segs[i].n_tiles;
-        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-        S.lo_rel = 0; S.hi_rel = b->segs[i].len;
-        S.seg = (uint32_t)i;
+        const SegPlan &sp = b->segs[i];
+        tab[i] = tsplan::whole_segment_entry(sp.in_off, sp.len, sp.abs_pos, sp.first_tile, sp.n_tiles, (uint32_t)i);
     }
     // (with the scan's chain summaries the interstitial search screens the tiles and walks only the listed ones)
     const bool from_scan = b->chain_valid() && !b->tips;

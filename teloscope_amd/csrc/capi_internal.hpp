@@ -427,7 +427,7 @@ struct HostView {
 int  ts_assemble_general(ts_ctx *c, const HostView &v, ts_segment_out *out);
 
 // ---- the general kernels' per-context launch geometry: the host entry points' general path (pipeline.cpp) and general tips
-// batches (general_batch.cpp) launch the same passes
+// batches (general_batch.cpp) launch the same passes, here; what they plan for them is in general_plan_core.h
 inline TsGenericGeom ts_general_geom(const ts_ctx *c) {
     const ts_params &P = c->params;
     const uint32_t s = P.step, w = P.window_size;
@@ -465,6 +465,33 @@ inline bool ts_general_list_form_ok(const ts_ctx *c) {
 // a tile's slot, in units of the positions it holds: what a scan starts with, and what cannot overflow
 inline uint32_t ts_general_slot_start(const ts_ctx *c, uint32_t unit) { return c->gen_wide ? unit * std::min<uint32_t>(4u, std::max<uint32_t>(1u, c->wpat.nlen)) : unit; }
 inline uint32_t ts_general_slot_max(const ts_ctx *c, uint32_t unit) { return unit * std::max<uint32_t>(1u, c->gen_wide ? c->wpat.nlen : c->gpat.nlen); }
+// The fused pass on `st`: the wide form on a context of the wide form, else the list form (use_list) or the strided one.  The
+// three tables are per segment (lengths, window bases, window counts); d_flag is the pass's flag word, cleared by the caller,
+// who holds c->mtx.  d_win: the window records, nullptr for tips.
+inline int ts_general_launch_fused(ts_ctx *c, const void *d_in, const TsGeneralTile *d_tiles, uint32_t nt, const unsigned long long *tab_len,
+                                   const unsigned long long *tab_win, const unsigned long long *tab_nwin, uint32_t *d_flag, bool tips, uint32_t slot_cap,
+                                   uint32_t *d_stats, uint32_t *d_slots, uint32_t *d_win, bool use_list, const TsGenericGeom &Q, hipStream_t st) {
+    if (c->gen_wide) {
+        if (ts_k_launch_general_wide((const unsigned char *)d_in, d_tiles, nt, tab_len, tab_win, tab_nwin, &c->wpat, &Q, tips ? 1 : 0, slot_cap,
+                                     d_stats, d_slots, d_win, d_flag, st) != 0)
+            return c->fail(TS_ERR_HIP, "general wide kernel launch failed");
+    } else if (ts_k_launch_general_fused((const unsigned char *)d_in, d_tiles, nt, tab_len, tab_win, tab_nwin, &c->gpat, &Q, tips ? 1 : 0, slot_cap,
+                                         d_stats, d_slots, d_win, d_flag, use_list ? 1 : 0, c->num_cu, st) != 0)
+        return c->fail(TS_ERR_HIP, "general fused kernel launch failed");
+    return TS_OK;
+}
+// What a driver does once a scan has raised its flag word (bit 0: a tile overflowed its slot, bit 1: a candidate list spilled)
+// in scan number `attempt` (from 0): give up at the third scan that raises it (the wide form: the sixth), or when the slot
+// already holds every match a tile can have and nothing spilled; after a spill take the strided form and keep the slots; else
+// grow the slots to slot_max — the wide form by fours: a slot for every position AND length, 63 of them, is 1 MB per tile —
+// which sets slot_cap.
+enum class TsGeneralRescan { Fail, Strided, Grown };
+inline TsGeneralRescan ts_general_after_flag(uint32_t flag, int attempt, bool wide, uint32_t &slot_cap, uint32_t slot_max) {
+    if (attempt > (wide ? 4 : 1) || (slot_cap >= slot_max && !(flag & 2u))) return TsGeneralRescan::Fail;
+    if (flag & 2u) return TsGeneralRescan::Strided;
+    slot_cap = wide ? std::min<uint32_t>(slot_max, slot_cap * 4u) : slot_max;
+    return TsGeneralRescan::Grown;
+}
 
 // general_batch.cpp: what the ts_batch_* entry points hand a general tips batch (b->gen != nullptr) to
 ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t *abs_pos, size_t n_segs);

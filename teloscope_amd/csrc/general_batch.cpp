@@ -11,6 +11,7 @@
 // ts_batch_read_pass_status reads it, ts_batch_sync regrows the slots (or leaves the list form) and rescans.
 // ts_batch_download_blocks calls the terminal blocks over the same slots and ts_batch_segment_summary adds up the tile directory.
 #include "capi_internal.hpp"
+#include "general_plan_core.h"
 
 namespace {
 
@@ -31,12 +32,7 @@ std::vector<TsShardSegIn> segment_table(const ts_batch *b) {
     std::vector<TsShardSegIn> segin(b->segs.size());
     for (size_t i = 0; i < segin.size(); ++i) {
         const SegPlan &sp = b->segs[i];
-        TsShardSegIn &S = segin[i];
-        S = TsShardSegIn{};
-        S.in_off = sp.in_off; S.len = sp.len; S.abs_pos = sp.abs_pos;
-        S.t0 = S.o0 = sp.first_tile; S.t1 = S.o1 = sp.first_tile + sp.n_tiles;
-        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-        S.lo_rel = 0; S.hi_rel = sp.len; S.seg = (uint32_t)i;
+        segin[i] = tsplan::whole_segment_entry(sp.in_off, sp.len, sp.abs_pos, sp.first_tile, sp.n_tiles, (uint32_t)i);
     }
     return segin;
 }
@@ -112,8 +108,6 @@ ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const u
     const uint32_t s = std::max<uint32_t>(ctx->params.step, 1u), tl = ctx->params.terminal_limit;
     const uint32_t halo = g.wide ? (uint32_t)TS_WIDE_HALO : 32u;
     uint64_t off = 0, scanned = 0;
-    uint32_t largest = 0;
-    bool aligned = true;
     b->segs.resize(n_segs);
     for (size_t i = 0; i < n_segs; ++i) {
         SegPlan &sp = b->segs[i];
@@ -122,31 +116,13 @@ ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const u
         sp.in_off = off;
         off += (sp.len + 15) & ~15ull;
         sp.first_tile = (uint32_t)g.tiles.size();
-        auto add_region = [&](uint64_t start, uint64_t len) {
-            Region rg{start, len, (uint32_t)g.tiles.size(), 0, TS_GENERAL_TILE};
-            uint64_t kq = start / s, kr = start - kq * s;                    // P0 = kq s + kr, walked from tile to tile
-            for (uint64_t a = 0; a < len; a += TS_GENERAL_TILE) {
-                TsGeneralTile T{};
-                T.in_off = sp.in_off + start + a;
-                T.seg_rel = start + a;
-                T.k_p0 = kq; T.r_p0 = (uint32_t)kr;
-                T.n = (uint32_t)std::min<uint64_t>(TS_GENERAL_TILE, len - a);
-                T.avail = (uint32_t)std::min<uint64_t>(len - a, (uint64_t)T.n + halo);
-                T.seg = (uint32_t)i;
-                g.tiles.push_back(T);
-                largest = std::max(largest, T.n);
-                aligned = aligned && (T.in_off & 15ull) == 0;
-                kr += TS_GENERAL_TILE;
-                if (kr >= s) { const uint64_t d = kr / s; kq += d; kr -= d * s; }
-            }
+        for (const tsplan::Span &r : tsplan::scanned_regions(sp.len, true, tl)) {
+            Region rg{r.start, r.len, (uint32_t)g.tiles.size(), 0, TS_GENERAL_TILE};
+            tsplan::append_region_tiles(g.tiles, sp.in_off + r.start, r.start, r.len, (uint32_t)i, s, halo);
             rg.n_tiles = (uint32_t)g.tiles.size() - rg.first_tile;
             sp.regions.push_back(rg);
-            scanned += len;
-        };
-        // regions exactly as scanSegment picks them (src/teloscope.cpp:576-583; uint32 product)
-        const uint32_t twice = 2u * tl;
-        if (sp.len > twice) { add_region(0, tl); add_region(sp.len - tl, tl); }
-        else if (sp.len) add_region(0, sp.len);
+            scanned += r.len;
+        }
         sp.n_tiles = (uint32_t)g.tiles.size() - sp.first_tile;
         b->total_bases += sp.len;
         if (g.tiles.size() >= 0x7FFFFFFFull) {
@@ -157,6 +133,12 @@ ts_batch *ts_general_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const u
     b->input_bytes = off + TS_IN_PAD;
     b->in_lo = 0; b->in_hi = b->input_bytes;
     b->range_bases = scanned;
+    uint32_t largest = 0;
+    bool aligned = true;
+    for (const TsGeneralTile &T : g.tiles) {
+        largest = std::max(largest, T.n);
+        aligned = aligned && (T.in_off & 15ull) == 0;
+    }
     // a slot per tile, sized by the largest tile of THIS batch (reads of 150 bases need no slot of 4096 records): one record per
     // position to begin with (the wide form: four), a record per position and length when that overflowed
     g.slot_unit = std::max<uint32_t>(4u, (largest + 3u) & ~3u);
@@ -204,14 +186,9 @@ int ts_general_batch_scan(ts_batch *b, const void *d_input, void *stream) {
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         HIP_TRY(c, hipMemsetAsync(d_flag, 0, 16, st));
-        if (g.wide) {
-            if (ts_k_launch_general_wide((const unsigned char *)d_input, (const TsGeneralTile *)g.d_tiles.p, (uint32_t)nt, tab_len, tab_win, tab_nwin,
-                                         &c->wpat, &g.Q, 1, g.slot_cap, (uint32_t *)g.d_stats.p, (uint32_t *)g.d_slots.p, nullptr, d_flag, st) != 0)
-                return c->fail(TS_ERR_HIP, "general wide kernel launch failed");
-        } else if (ts_k_launch_general_fused((const unsigned char *)d_input, (const TsGeneralTile *)g.d_tiles.p, (uint32_t)nt, tab_len, tab_win, tab_nwin,
-                                             &c->gpat, &g.Q, 1, g.slot_cap, (uint32_t *)g.d_stats.p, (uint32_t *)g.d_slots.p, nullptr, d_flag,
-                                             g.use_list ? 1 : 0, c->num_cu, st) != 0)
-            return c->fail(TS_ERR_HIP, "general fused kernel launch failed");
+        const int rc = ts_general_launch_fused(c, d_input, (const TsGeneralTile *)g.d_tiles.p, (uint32_t)nt, tab_len, tab_win, tab_nwin, d_flag, true,
+                                               g.slot_cap, (uint32_t *)g.d_stats.p, (uint32_t *)g.d_slots.p, nullptr, g.use_list, g.Q, st);
+        if (rc != TS_OK) return rc;
         if (ts_k_launch_general_slot_offsets((unsigned long long *)g.d_off.p, (uint32_t)nt, g.slot_cap, st) != 0)
             return c->fail(TS_ERR_HIP, "slot-offset kernel launch failed");
     }
@@ -359,11 +336,11 @@ int ts_general_batch_sync(ts_batch *b) {
         uint32_t flag = 0;
         { const int rc = read_flag(b, flag); if (rc != TS_OK) return rc; }
         if (!flag) { b->synced = true; return TS_OK; }
-        if (attempt > (g.wide ? 4 : 1) || (g.slot_cap >= g.slot_max && !(flag & 2u)))
+        const TsGeneralRescan next = ts_general_after_flag(flag, attempt, g.wide, g.slot_cap, g.slot_max);
+        if (next == TsGeneralRescan::Fail)
             return c->fail(TS_ERR_STATE, "general read batch: a tile overflowed a slot that holds every match it can have");
-        if (flag & 2u) g.use_list = false;                        // a candidate list spilled: the strided form takes the batch
+        if (next == TsGeneralRescan::Strided) g.use_list = false;        // a candidate list spilled: the strided form takes the batch
         else {
-            g.slot_cap = g.wide ? std::min<uint32_t>(g.slot_max, g.slot_cap * 4u) : g.slot_max;
             c->pool.give(std::move(g.d_slots));
             const int rc = take(c, slot_bytes(g), g.d_slots, "the regrown record slots", g);
             if (rc != TS_OK) return rc;

@@ -36,6 +36,7 @@
 
 #include "capi_internal.hpp"
 #include "gather_core.h"
+#include "general_plan_core.h"
 #include "text_core.h"
 
 namespace {
@@ -1195,34 +1196,14 @@ int gen_prepare(GenCall &g, GenGroup &gr) {
     while (g.next_item < g.items.size() && (G.empty() || off < g.target)) {
         const Item &it = g.items[g.next_item];
         GenSeg sl{it.len, it.abs_pos, off, {}};
-        // regions exactly as scanSegment picks them (src/teloscope.cpp:576-583; uint32 product)
-        if (g.tips) {
-            const uint32_t twice = 2u * P.terminal_limit;
-            if (it.len > twice) { sl.regions.push_back({0, P.terminal_limit, 0}); sl.regions.push_back({it.len - P.terminal_limit, P.terminal_limit, 0}); }
-            else if (it.len) sl.regions.push_back({0, it.len, 0});
-        } else if (it.len) {
-            sl.regions.push_back({0, it.len, 0});
-            sl.n_windows = ceil_div(it.len, s);
-        }
+        if (!g.tips) sl.n_windows = ceil_div(it.len, s);
         sl.first_tile = tiles.size();
-        for (GenRegion &rg : sl.regions) {
-            rg.layout_off = off;
-            const int rc = region_pieces(c, it, it.len, rg.seg_start, rg.len, off, 0, ~0ull, pieces);
+        for (const tsplan::Span &r : tsplan::scanned_regions(it.len, g.tips, P.terminal_limit)) {
+            sl.regions.push_back({r.start, r.len, off});
+            const int rc = region_pieces(c, it, it.len, r.start, r.len, off, 0, ~0ull, pieces);
             if (rc != TS_OK) return rc;
-            uint64_t kq = rg.seg_start / s, kr = rg.seg_start - kq * s;          // P0 = kq s + kr, walked from tile to tile
-            for (uint64_t a = 0; a < rg.len; a += TS_GENERAL_TILE) {
-                TsGeneralTile T{};
-                T.in_off = off + a;
-                T.seg_rel = rg.seg_start + a;
-                T.k_p0 = kq; T.r_p0 = (uint32_t)kr;
-                T.n = (uint32_t)std::min<uint64_t>(TS_GENERAL_TILE, rg.len - a);
-                T.avail = (uint32_t)std::min<uint64_t>(rg.len - a, (uint64_t)T.n + (g.wide ? (uint32_t)TS_WIDE_HALO : 32u));
-                T.seg = (uint32_t)G.size();
-                tiles.push_back(T);
-                kr += TS_GENERAL_TILE;
-                if (kr >= s) { const uint64_t d = kr / s; kq += d; kr -= d * s; }
-            }
-            off += (rg.len + 15) & ~15ull;
+            tsplan::append_region_tiles(tiles, off, r.start, r.len, (uint32_t)G.size(), s, g.wide ? (uint32_t)TS_WIDE_HALO : 32u);
+            off += (r.len + 15) & ~15ull;
         }
         sl.n_tiles = tiles.size() - sl.first_tile;
         sl.win_base = nwin_total;
@@ -1287,16 +1268,10 @@ int gen_fused(GenCall &g, GenGroup &gr) {
             if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[0], st));
             HIP_TRY(c, hipMemsetAsync(d_flag, 0, 16, st));
             if (gr.nwin_total) HIP_TRY(c, hipMemsetAsync(gr.d_win.p, 0, gr.nwin_total * 32, st));
-            if (g.wide) {
-                if (ts_k_launch_general_wide((const unsigned char *)gr.d_in.p, (const TsGeneralTile *)gr.d_tiles.p, (uint32_t)nt,
-                                             tab_len, tab_win, tab_nwin, &c->wpat, &g.Q, g.tips ? 1 : 0, gr.slot_cap, (uint32_t *)gr.d_stats.p,
-                                             (uint32_t *)gr.d_slots.p, (uint32_t *)gr.d_win.p, d_flag, st) != 0)
-                    return c->fail(TS_ERR_HIP, "general wide kernel launch failed");
-            } else
-            if (ts_k_launch_general_fused((const unsigned char *)gr.d_in.p, (const TsGeneralTile *)gr.d_tiles.p, (uint32_t)nt,
-                                          tab_len, tab_win, tab_nwin, &c->gpat, &g.Q, g.tips ? 1 : 0, gr.slot_cap, (uint32_t *)gr.d_stats.p,
-                                          (uint32_t *)gr.d_slots.p, (uint32_t *)gr.d_win.p, d_flag, use_list ? 1 : 0, c->num_cu, st) != 0)
-                return c->fail(TS_ERR_HIP, "general fused kernel launch failed");
+            const int rc = ts_general_launch_fused(c, gr.d_in.p, (const TsGeneralTile *)gr.d_tiles.p, (uint32_t)nt, tab_len, tab_win, tab_nwin, d_flag,
+                                                   g.tips, gr.slot_cap, (uint32_t *)gr.d_stats.p, (uint32_t *)gr.d_slots.p, (uint32_t *)gr.d_win.p,
+                                                   use_list, g.Q, st);
+            if (rc != TS_OK) return rc;
             if (ts_k_launch_tile_offsets((const uint32_t *)gr.d_stats.p, (uint32_t)nt, (unsigned long long *)gr.d_off.p, gr.d_tmp.p, st) != 0)
                 return c->fail(TS_ERR_HIP, "tile-offset kernel launch failed");
             if (g.timing) HIP_TRY(c, hipEventRecord(c->gen_ev[1], st));
@@ -1317,12 +1292,10 @@ int gen_fused(GenCall &g, GenGroup &gr) {
         if (g.timing) { g.t_dbg[0] += ms_between(t1, te0); g.t_dbg[1] += ms_between(te0, te1); g.t_dbg[2] += ms_between(te1, Clock::now()); }
         if (g.timing) { float ms = 0; if (hipEventElapsedTime(&ms, c->gen_ev[0], c->gen_ev[1]) == hipSuccess) g.t_kern += ms; }
         if (!flag) break;
-        const uint32_t slot_max = ts_general_slot_max(c, TS_GENERAL_TILE);
-        if (attempt > (g.wide ? 4 : 1) || (gr.slot_cap >= slot_max && !(flag & 2u)))
+        const TsGeneralRescan next = ts_general_after_flag(flag, attempt, g.wide, gr.slot_cap, ts_general_slot_max(c, TS_GENERAL_TILE));
+        if (next == TsGeneralRescan::Fail)
             return c->fail(TS_ERR_STATE, "general path: a tile overflowed a slot that holds every match it can have");
-        if (flag & 2u) { use_list = false; continue; }            // a candidate list spilled: the strided form takes this group
-        // (the wide form grows by fours: a slot for every position AND length — 63 of them — is 1 MB per tile)
-        gr.slot_cap = g.wide ? std::min<uint32_t>(slot_max, gr.slot_cap * 4u) : slot_max;
+        if (next == TsGeneralRescan::Strided) { use_list = false; continue; }   // a candidate list spilled: the strided form takes this group
         g.slot_cap_call = gr.slot_cap;
         c->pool.give(std::move(gr.d_slots));
         HIP_TRY(c, c->pool.take(std::max<size_t>(nt, 1) * (size_t)gr.slot_cap * 4, gr.d_slots));
@@ -1343,12 +1316,7 @@ void gen_segment_table(const GenHost &h, std::vector<unsigned long long> &sbase,
     unsigned long long X = 0;
     for (size_t i = 0; i < ns; ++i) {
         sbase[i] = X;
-        TsShardSegIn &S = segtab[i];
-        S = TsShardSegIn{};
-        S.in_off = X; S.len = h.G[i].len; S.abs_pos = h.G[i].abs_pos;
-        S.t0 = S.o0 = (uint32_t)h.G[i].first_tile; S.t1 = S.o1 = (uint32_t)(h.G[i].first_tile + h.G[i].n_tiles);
-        S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-        S.lo_rel = 0; S.hi_rel = h.G[i].len; S.seg = (uint32_t)i;
+        segtab[i] = tsplan::whole_segment_entry(X, h.G[i].len, h.G[i].abs_pos, (uint32_t)h.G[i].first_tile, (uint32_t)h.G[i].n_tiles, (uint32_t)i);
         X += h.G[i].len + 64;
     }
 }
@@ -1906,14 +1874,8 @@ int ts_batch_call_read_blocks(ts_batch *b, void *stream) {
     if (!R.d_segin.p) {
         std::vector<TsShardSegIn> tab(ns);
         for (size_t i = 0; i < ns; ++i) {
-            TsShardSegIn &S = tab[i];
-            S = TsShardSegIn{};
-            S.in_off = b->segs[i].in_off; S.len = b->segs[i].len; S.abs_pos = b->segs[i].abs_pos;
-            S.t0 = S.o0 = b->segs[i].first_tile;
-            S.t1 = S.o1 = b->segs[i].first_tile + b->segs[i].n_tiles;
-            S.flags = TS_SEG_F_HAS_START | TS_SEG_F_HAS_END;
-            S.lo_rel = 0; S.hi_rel = b->segs[i].len;
-            S.seg = (uint32_t)i;
+            const SegPlan &sp = b->segs[i];
+            tab[i] = tsplan::whole_segment_entry(sp.in_off, sp.len, sp.abs_pos, sp.first_tile, sp.n_tiles, (uint32_t)i);
         }
         HIP_TRY(c, c->pool.take(ns * sizeof(TsShardSegIn), R.d_segin));
         HIP_TRY(c, hipMemcpyAsync(R.d_segin.p, tab.data(), ns * sizeof(TsShardSegIn), hipMemcpyHostToDevice, st));
