@@ -17,13 +17,11 @@
 // and one job per chunk of a 2048-record FASTQ batch (src/input.cpp:753-812); a group is the GPU-sized
 // equivalent of such a job, and results come back in input order whatever the grouping.
 #include <hip/hip_runtime.h>
-#include <immintrin.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +36,7 @@
 #include "gather_core.h"
 #include "general_plan_core.h"
 #include "text_core.h"
+#include "upload_stage_core.h"
 
 namespace {
 
@@ -175,14 +174,9 @@ int ensure_streams(ts_ctx *c) {
     return rc;
 }
 
-struct UpPiece { uint64_t off; const char *src; uint64_t len; uint64_t text_len;     // off: byte offset in the input layout; len: bases;
-                                                                                     // text_len != 0: src is FASTA text (line ends to skip)
-                 const ts_packed_seq *packed = nullptr; uint64_t packed_first = 0;     // packed: the bases are codes [packed_first, + len) of *packed
-                 bool device = false; };                                               // device: src is memory of the context's device (TS_INPUT_DEVICE)
-
-// (the walks over FASTA body text — strip_copy, text_locate, strip_take — and the staging workers' range cuts: text_core.h)
-using tstext::strip_copy;
-using tstext::strip_take;
+// (a call's pieces, their chunks and everything the staging workers write into a pinned slot: upload_stage_core.h; the walks over
+// FASTA body text under it: text_core.h)
+using tsstage::UpPiece;
 using tstext::text_locate;
 
 constexpr uint32_t kPackRunCap = 1u << 18;                 // invalid runs a packed chunk may carry (more: the chunk goes as ASCII)
@@ -251,84 +245,24 @@ int gather_device_pieces(ts_ctx *c, const std::vector<UpPiece> &on_device, void 
 // gather_device_pieces above, queued on up_stream BEHIND the host pieces' chunks (a chunk's DMA or unpack kernel also writes the
 // padding between its pieces, where a device piece may lie; the stream's order makes the device piece's bytes the last written).
 // Asynchronous: the DMAs are queued on up_stream.  `pieces` ascend by offset and do not overlap.
+// This function drives: the knobs, the slots and their events, the choice between the packed and the ASCII route per chunk, the DMAs
+// and the unpack launch, the counters and the timing line.  What a chunk is and every byte that lands in its slot: upload_stage_core.h.
 int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, uint64_t lo_all, int &slot, bool used[]) {
-    constexpr uint64_t kChunk = 32u << 20, kMaxGap = 64u << 10;
-    constexpr uint64_t kChunkPacked = 4 * kChunk;            // a packed chunk fills the same 32 MB pinned slot with 128 MB of layout
-    std::vector<UpPiece> pieces;
-    pieces.reserve(pieces_in.size());
-    bool any_text = false, any_packed = false;
-    std::vector<UpPiece> on_device;
-    for (const UpPiece &pc : pieces_in) {
-        if (pc.device) {
-            on_device.push_back(pc);
-        } else if (pc.text_len) {
-            if (pc.len > kChunk) return c->fail(TS_ERR_INVALID_ARG, "a text piece holds more than 32 MiB of bases");
-            pieces.push_back(pc);
-            any_text = true;
-        } else if (pc.packed) {
-            for (uint64_t a = 0; a < pc.len; a += kChunk) {
-                UpPiece q = pc;
-                q.off = pc.off + a; q.len = std::min<uint64_t>(kChunk, pc.len - a); q.packed_first = pc.packed_first + a;
-                pieces.push_back(q);
-            }
-            any_packed = true;
-        } else {
-            for (uint64_t a = 0; a < pc.len; a += kChunk) pieces.push_back({pc.off + a, pc.src + a, std::min<uint64_t>(kChunk, pc.len - a), 0});
-        }
-    }
+    using tsstage::kChunk;
+    using tsstage::kChunkPacked;
+    tsstage::CallPieces call;
+    if (tsstage::normalise_pieces(pieces_in, kChunk, call) == tsstage::Refused::TextPieceTooLong)
+        return c->fail(TS_ERR_INVALID_ARG, "a text piece holds more than 32 MiB of bases");
+    const UpPiece *pieces = call.host.data();
+    const size_t n_pieces = call.host.size();
+    const bool any_packed = call.any_packed;
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    unsigned nthr = std::min(8u, std::max(1u, hw / 2u));
-    // The staging threads live for the whole call, not for one 32 MB chunk (a chunk is staged in ~0.6 ms: spawning and
-    // joining eight threads for each cost a tenth of the upload): job(t) runs on worker t, the caller is worker 0.
-    struct StagePool {
-        std::mutex m;
-        std::condition_variable cv_go, cv_done;
-        std::function<void(unsigned)> job;
-        uint64_t generation = 0;
-        unsigned active = 0, pending = 0;
-        bool quit = false;
-        std::vector<std::thread> threads;
-        explicit StagePool(unsigned n) {
-            for (unsigned t = 1; t < n; ++t)
-                threads.emplace_back([this, t] {
-                    uint64_t seen = 0;
-                    for (;;) {
-                        std::function<void(unsigned)> f;
-                        {
-                            std::unique_lock<std::mutex> g(m);
-                            cv_go.wait(g, [&] { return quit || generation != seen; });
-                            if (quit) return;
-                            seen = generation;
-                            if (t >= active) continue;
-                            f = job;
-                        }
-                        f(t);
-                        { std::lock_guard<std::mutex> g(m); if (--pending == 0) cv_done.notify_one(); }
-                    }
-                });
-        }
-        void run(unsigned n, const std::function<void(unsigned)> &f) {       // f(0 .. n-1), n <= workers
-            if (n <= 1 || threads.empty()) { for (unsigned t = 0; t < n; ++t) f(t); return; }
-            { std::lock_guard<std::mutex> g(m); job = f; active = n; pending = n - 1; ++generation; }
-            cv_go.notify_all();
-            f(0);
-            std::unique_lock<std::mutex> g(m);
-            cv_done.wait(g, [&] { return pending == 0; });
-        }
-        ~StagePool() {
-            { std::lock_guard<std::mutex> g(m); quit = true; }
-            cv_go.notify_all();
-            for (std::thread &th : threads) th.join();
-        }
-    };
-    uint64_t total_bytes = 0;
-    for (const UpPiece &pc : pieces) total_bytes += pc.len;
-    StagePool stage_pool(total_bytes >= (8u << 20) ? nthr : 1u);
+    const unsigned nthr = std::min(8u, std::max(1u, hw / 2u));
+    tsstage::StagePool stage_pool(call.total_bytes >= (8u << 20) ? nthr : 1u);
     const bool pooled = !stage_pool.threads.empty();          // (without threads a chunk's ranges run one after the other on the caller)
     std::atomic<int> bad_text{0};
     const bool fold = c->params.fold_case != 0;
-    const uint64_t packed_min = c->knobs.packed_min_bytes;
-    bool use_packed = (c->knobs.packed_upload && total_bytes >= packed_min) || any_packed;      // (bases that arrive packed leave packed)
+    bool use_packed = (c->knobs.packed_upload && call.total_bytes >= c->knobs.packed_min_bytes) || any_packed;   // (bases that arrive packed leave packed)
     if (use_packed && !c->d_pack[0].p) {                       // the device side of the ring, once per context
         for (int q = 0; q < ts_ctx::kUpSlots && use_packed; ++q) {
             if (c->d_pack[q].ensure((kChunkPacked >> 2) + 4096) != hipSuccess || c->d_runs[q].ensure((size_t)kPackRunCap * 8) != hipSuccess ||
@@ -341,231 +275,66 @@ int upload_pieces(ts_ctx *c, const std::vector<UpPiece> &pieces_in, void *din, u
     size_t n_chunks = 0;
     struct Report { const bool on; double &w, &p, &i; size_t &n; ~Report() { if (on && n) fprintf(stderr, "  upload_pieces: %zu chunks, waiting for a free slot %.2f ms, packing %.2f ms, runs + DMA + unpack enqueue %.2f ms\n", n, w, p, i); } }
         report{stage_timing, t_wait, t_pack, t_issue, n_chunks};
-    size_t i = 0;
-    while (i < pieces.size()) {
+    for (size_t i = 0; i < n_pieces;) {
         const uint64_t c0 = pieces[i].off;
-        size_t j = i + 1;
-        uint64_t bytes = pieces[i].len;
-        const uint64_t chunk_limit = use_packed ? kChunkPacked : kChunk;
-        while (j < pieces.size() && pieces[j].off + pieces[j].len - c0 <= chunk_limit &&
-               pieces[j].off - (pieces[j - 1].off + pieces[j - 1].len) <= kMaxGap) { bytes += pieces[j].len; ++j; }
+        const tsstage::Extent ext = tsstage::chunk_extent(pieces, n_pieces, i, use_packed ? kChunkPacked : kChunk, tsstage::kMaxGap);
+        const size_t j = ext.end;
+        const uint64_t bytes = ext.bytes, hi_pos = pieces[j - 1].off + pieces[j - 1].len;
         const auto tw0 = Clock::now();
         if (used[slot]) HIP_TRY(c, hipEventSynchronize(c->pin_up_ev[slot]));
         if (stage_timing) t_wait += ms_between(tw0, Clock::now());
         ++n_chunks;
         char *dst = (char *)c->pin_up[slot].p;
         const unsigned nt = bytes >= (4u << 20) ? nthr : 1u;
-        const uint64_t hi_pos = pieces[j - 1].off + pieces[j - 1].len;
-        // ---- packed: the chunk leaves as 2-bit codes + invalid runs (pack.cpp), a quarter of the bytes; unpack.hip
-        // restores the byte layout on the device.  Worker t packs the layout range [t, t + 1) x share of the chunk
-        // (ranges end at multiples of 4096 positions: no two workers write the same byte), pulling its bases out of the
-        // pieces that overlap it — plain pieces in place, FASTA text through a small buffer that the line ends are
-        // stripped into — and 'A' into the padding between pieces, which nobody reads.
-        if (use_packed && (bytes >= 4096 || any_packed)) {
-            const uint64_t c0a = c0 & ~63ull;
-            const uint64_t P = hi_pos - c0a;                                  // chunk positions, incl. the lead before c0
-            std::vector<ts::PackRuns> wr(nt);
-            std::atomic<int> short_text{0};
-            struct BlockKinds { uint64_t plain = 0, text = 0, copied = 0, mixed = 0; };     // (ts_upload_stats: one entry per worker, written once per range)
-            std::vector<BlockKinds> kinds(nt);
-            // the workers' ranges: equal shares that snap to where a FASTA text piece begins (text_core.h: range_cuts)
-            std::vector<tstext::CutPiece> cut_pieces;
-            if (nt > 1u) {
-                cut_pieces.reserve(j - i);
-                for (size_t q = i; q < j; ++q) cut_pieces.push_back({pieces[q].off - c0a, pieces[q].text_len != 0});
-            }
-            const std::vector<uint64_t> cut = tstext::range_cuts(P, nt, cut_pieces.data(), cut_pieces.size());
-            auto pack_range = [&](unsigned t) {
-                const uint64_t a0 = cut[t], z0 = cut[t + 1];
-                if (a0 >= z0) return;
-                constexpr uint64_t BK = 16384;
-                alignas(64) unsigned char buf[BK];
-                ts::PackRuns &R = wr[t];
-                BlockKinds seen;
-                size_t k = i;
-                while (k < j && pieces[k].off + pieces[k].len <= c0a + a0) ++k;      // first piece that reaches into the range
-                const char *tcur = nullptr, *tend = nullptr;                         // text cursor inside pieces[tk]
-                size_t tk = (size_t)-1;
-                for (uint64_t a = a0; a < z0; a += BK) {
-                    const uint64_t z = std::min(z0, a + BK), la = c0a + a, lz = c0a + z;   // layout range of the block
-                    while (k < j && pieces[k].off + pieces[k].len <= la) ++k;
-                    // wholly inside one plain piece: packed from where it lies
-                    if (k < j && !pieces[k].text_len && !pieces[k].packed && pieces[k].off <= la && pieces[k].off + pieces[k].len >= lz) {
-                        ts::pack_bases((const unsigned char *)pieces[k].src + (la - pieces[k].off), z - a, (unsigned char *)dst + (a >> 2), fold, (uint32_t)a, R);
-                        ++seen.plain;
-                        continue;
-                    }
-                    // wholly inside one FASTA text piece: packed straight from the text (ts::pack_text: 32 text bytes at a time, the line
-                    // ends' slots taken out of the codes) — the stripped copy in between made text in half as fast as joined bases
-                    if (k < j && pieces[k].text_len && !pieces[k].packed && pieces[k].off <= la && pieces[k].off + pieces[k].len >= lz) {
-                        const UpPiece &pc = pieces[k];
-                        if (tk != k) {                                               // enter this text piece (at base la - pc.off)
-                            tk = k;
-                            tend = pc.src + pc.text_len;
-                            tcur = la > pc.off ? text_locate(pc.src, pc.text_len, la - pc.off) : pc.src;
-                        }
-                        if (ts::pack_text(&tcur, tend, z - a, (unsigned char *)dst + (a >> 2), fold, (uint32_t)a, R) != z - a) short_text.store(1);
-                        ++seen.text;
-                        continue;
-                    }
-                    // bases that arrive packed (TS_INPUT_PACKED2): when every piece the block touches is such, their codes are
-                    // copied — whole bytes where source and destination agree on the phase within a byte (full scans: segments
-                    // start on 16-byte boundaries of the layout), else shifted — and their invalid runs translated; a block
-                    // that mixes packed and ASCII pieces (the seam between two segments of different formats) takes the
-                    // ASCII path below with the codes spelled out as letters
-                    {
-                        bool all_packed = true, any_here = false;
-                        for (size_t q = k; q < j && pieces[q].off < lz; ++q) {
-                            if (pieces[q].off + pieces[q].len <= la) continue;
-                            any_here = true;
-                            if (!pieces[q].packed) all_packed = false;
-                        }
-                        if (any_here && all_packed) {
-                            unsigned char *out = (unsigned char *)dst + (a >> 2);              // a is a multiple of 4 (blocks of 16384 from a multiple of 4096)
-                            std::memset(out, 0, (z - a + 3) >> 2);
-                            for (size_t q = k; q < j && pieces[q].off < lz; ++q) {
-                                const UpPiece &pc = pieces[q];
-                                const uint64_t s0 = std::max(pc.off, la), s1 = std::min(pc.off + pc.len, lz);
-                                if (s1 <= s0) continue;
-                                const uint64_t d0 = s0 - la, n = s1 - s0, i0 = pc.packed_first + (s0 - pc.off);   // block position, bases, source base index
-                                const uint8_t *codes = pc.packed->codes;
-                                if (((d0 ^ i0) & 3u) == 0u) {
-                                    uint64_t x = 0;
-                                    for (; x < n && ((d0 + x) & 3u); ++x)                                        // up to the first whole byte
-                                        out[(d0 + x) >> 2] |= (unsigned char)(((codes[(i0 + x) >> 2] >> (2u * ((i0 + x) & 3u))) & 3u) << (2u * ((d0 + x) & 3u)));
-                                    const uint64_t whole = (n - x) >> 2;
-                                    std::memcpy(out + ((d0 + x) >> 2), codes + ((i0 + x) >> 2), whole);
-                                    for (x += whole * 4; x < n; ++x)
-                                        out[(d0 + x) >> 2] |= (unsigned char)(((codes[(i0 + x) >> 2] >> (2u * ((i0 + x) & 3u))) & 3u) << (2u * ((d0 + x) & 3u)));
-                                } else {
-                                    for (uint64_t x = 0; x < n; ++x)
-                                        out[(d0 + x) >> 2] |= (unsigned char)(((codes[(i0 + x) >> 2] >> (2u * ((i0 + x) & 3u))) & 3u) << (2u * ((d0 + x) & 3u)));
-                                }
-                                // the piece's invalid runs that reach into [i0, i0 + n): chunk positions; the codes under them are zeroed
-                                // (what pack_bases leaves there: the unpack kernel writes 'N' over them anyway)
-                                const ts_packed_run *pr = pc.packed->runs;
-                                const uint64_t nr = pr ? pc.packed->n_runs : 0;
-                                size_t r0 = (size_t)(std::upper_bound(pr, pr + nr, i0, [](uint64_t v, const ts_packed_run &r) { return v < r.start + r.len; }) - pr);
-                                for (; r0 < nr && pr[r0].start < i0 + n; ++r0) {
-                                    const uint64_t ra = std::max<uint64_t>(pr[r0].start, i0), rz = std::min<uint64_t>(pr[r0].start + pr[r0].len, i0 + n);
-                                    if (rz <= ra) continue;
-                                    R.finish();
-                                    const uint32_t cs = (uint32_t)(a + d0 + (ra - i0));
-                                    if (!R.runs.empty() && R.runs.back().start + R.runs.back().len == cs) R.runs.back().len += (uint32_t)(rz - ra);
-                                    else R.runs.push_back({cs, (uint32_t)(rz - ra)});
-                                }
-                            }
-                            ++seen.copied;
-                            continue;
-                        }
-                    }
-                    ++seen.mixed;
-                    std::memset(buf, 'A', z - a);
-                    for (size_t q = k; q < j && pieces[q].off < lz; ++q) {
-                        const UpPiece &pc = pieces[q];
-                        const uint64_t s0 = std::max(pc.off, la), s1 = std::min(pc.off + pc.len, lz);
-                        if (s1 <= s0) continue;
-                        if (pc.packed) {                                                             // (a mixed block: letters, 'N' under the runs)
-                            const uint64_t i0 = pc.packed_first + (s0 - pc.off);
-                            for (uint64_t x = 0; x < s1 - s0; ++x)
-                                buf[s0 - la + x] = "ACTG"[(pc.packed->codes[(i0 + x) >> 2] >> (2u * ((i0 + x) & 3u))) & 3u];
-                            const ts_packed_run *pr = pc.packed->runs;
-                            for (uint64_t r = 0; pr && r < pc.packed->n_runs; ++r) {
-                                const uint64_t ra = std::max<uint64_t>(pr[r].start, i0), rz = std::min<uint64_t>(pr[r].start + pr[r].len, i0 + (s1 - s0));
-                                for (uint64_t y = ra; y < rz; ++y) buf[s0 - la + (y - i0)] = 'N';
-                            }
-                            continue;
-                        }
-                        if (!pc.text_len) { std::memcpy(buf + (s0 - la), pc.src + (s0 - pc.off), s1 - s0); continue; }
-                        if (tk != q) {                                               // enter this text piece (at base s0 - pc.off)
-                            tk = q;
-                            tend = pc.src + pc.text_len;
-                            tcur = s0 > pc.off ? text_locate(pc.src, pc.text_len, s0 - pc.off) : pc.src;
-                        }
-                        if (strip_take((char *)buf + (s0 - la), s1 - s0, &tcur, tend) != s1 - s0) short_text.store(1);
-                    }
-                    ts::pack_bases(buf, z - a, (unsigned char *)dst + (a >> 2), fold, (uint32_t)a, R);
-                }
-                R.finish();
-                kinds[t] = seen;
-            };
+        const bool packed = use_packed && (bytes >= 4096 || any_packed);
+        uint64_t add[8] = {0, 1, 0, 0, 0, 0, nt > 1u && pooled ? 1u : 0u, 0};      // (ts_upload_stats; an ASCII chunk's, a packed one fills its own in)
+        Clock::time_point tp1;
+        if (packed) {
+            // the chunk leaves as 2-bit codes + invalid runs, a quarter of the bytes; unpack.hip restores the byte layout on the device
+            tsstage::PackedChunk pk(pieces, i, j, nt);
+            auto pack = [&](unsigned t) { if (!pk.pack(t, dst, fold)) bad_text.store(1); };
             const auto tp0 = Clock::now();
-            if (nt == 1u) pack_range(0); else stage_pool.run(nt, pack_range);
-            const auto tp1 = Clock::now();
+            if (nt == 1u) pack(0); else stage_pool.run(nt, pack);
+            tp1 = Clock::now();
             if (stage_timing) t_pack += ms_between(tp0, tp1);
-            if (short_text.load()) bad_text.store(1);
-            size_t nruns = 0;
-            for (const ts::PackRuns &R : wr) nruns += R.runs.size();
-            if (nruns <= kPackRunCap) {
-                ts::InvalidRun *hr = (ts::InvalidRun *)c->pin_runs[slot].p;
-                size_t at = 0;
-                for (const ts::PackRuns &R : wr) { if (!R.runs.empty()) std::memcpy(hr + at, R.runs.data(), R.runs.size() * sizeof(ts::InvalidRun)); at += R.runs.size(); }
-                const uint64_t pbytes = (((P + 3) >> 2) + 3) & ~3ull;
-                if (pbytes + 8 > c->pin_up[slot].bytes || pbytes + 8 > c->d_pack[slot].bytes)
-                    return c->fail(TS_ERR_STATE, "packed upload: a chunk does not fit its staging slot");
-                std::memset(dst + ((P + 3) >> 2), 0, pbytes - ((P + 3) >> 2) + 8);     // (the kernel reads one dword past the last code)
-                HIP_TRY(c, hipMemcpyAsync(c->d_pack[slot].p, dst, pbytes + 8, hipMemcpyHostToDevice, c->up_stream));
-                if (nruns) HIP_TRY(c, hipMemcpyAsync(c->d_runs[slot].p, hr, nruns * sizeof(ts::InvalidRun), hipMemcpyHostToDevice, c->up_stream));
-                if (ts_k_launch_unpack(c->d_pack[slot].p, (uint32_t)(c0 - c0a), (char *)din + (c0 - lo_all), hi_pos - c0, c->d_runs[slot].p, (uint32_t)nruns,
-                                       (char *)din + (c0 - lo_all) - (c0 - c0a), c->up_stream) != 0)
-                    return c->fail(TS_ERR_HIP, "unpack kernel launch failed");
-                HIP_TRY(c, hipEventRecord(c->pin_up_ev[slot], c->up_stream));
-                {
-                    BlockKinds sum;
-                    unsigned workers = 0;
-                    for (unsigned t = 0; t < nt; ++t) {
-                        sum.plain += kinds[t].plain; sum.text += kinds[t].text; sum.copied += kinds[t].copied; sum.mixed += kinds[t].mixed;
-                        if (cut[t + 1] > cut[t]) ++workers;
-                    }
-                    const uint64_t add[8] = {1, 0, sum.plain, sum.text, sum.copied, sum.mixed, workers > 1u && pooled ? 1u : 0u, c0 != c0a ? 1u : 0u};
-                    for (int q = 0; q < 8; ++q) if (add[q]) c->upload_stats[q].fetch_add(add[q], std::memory_order_relaxed);
-                }
-                if (stage_timing) t_issue += ms_between(tp1, Clock::now());
-                used[slot] = true;
-                slot = (slot + 1) % ts_ctx::kUpSlots;
-                i = j;
+            const size_t nruns = pk.n_runs();
+            if (nruns > kPackRunCap) {
+                // a chunk with more invalid runs than the list holds is not sequence data: the rest of the call goes the plain way
+                if (any_packed) return c->fail(TS_ERR_INVALID_ARG, "packed input with more invalid runs per 128 Mi bases than the upload carries (2^18)");
+                use_packed = false;
                 continue;
             }
-            // a chunk with more invalid runs than the list holds is not sequence data: the rest of the call goes the plain way
-            if (any_packed) return c->fail(TS_ERR_INVALID_ARG, "packed input with more invalid runs per 128 Mi bases than the upload carries (2^18)");
-            use_packed = false;
-            continue;
+            const uint64_t pbytes = tsstage::packed_bytes(pk.P);
+            if (pbytes + 8 > c->pin_up[slot].bytes || pbytes + 8 > c->d_pack[slot].bytes)
+                return c->fail(TS_ERR_STATE, "packed upload: a chunk does not fit its staging slot");
+            ts::InvalidRun *hr = (ts::InvalidRun *)c->pin_runs[slot].p;
+            pk.finish(dst, hr, pooled, add);
+            HIP_TRY(c, hipMemcpyAsync(c->d_pack[slot].p, dst, pbytes + 8, hipMemcpyHostToDevice, c->up_stream));
+            if (nruns) HIP_TRY(c, hipMemcpyAsync(c->d_runs[slot].p, hr, nruns * sizeof(ts::InvalidRun), hipMemcpyHostToDevice, c->up_stream));
+            if (ts_k_launch_unpack(c->d_pack[slot].p, (uint32_t)(c0 - pk.c0a), (char *)din + (c0 - lo_all), hi_pos - c0, c->d_runs[slot].p, (uint32_t)nruns,
+                                   (char *)din + (c0 - lo_all) - (c0 - pk.c0a), c->up_stream) != 0)
+                return c->fail(TS_ERR_HIP, "unpack kernel launch failed");
+        } else {
+            // the chunk leaves as it is: the pieces mirrored in the slot, one DMA
+            if (nt == 1u) {
+                if (!tsstage::ascii_single(pieces, i, j, c0, dst)) bad_text.store(1);
+            } else if (call.any_text) {
+                std::atomic<size_t> next{i};
+                stage_pool.run(nt, [&](unsigned) { if (!tsstage::ascii_whole_pieces(pieces, j, c0, dst, next)) bad_text.store(1); });
+            } else {
+                stage_pool.run(nt, [&](unsigned t) { tsstage::ascii_share(pieces, i, j, c0, dst, bytes, nt, t); });
+            }
+            HIP_TRY(c, hipMemcpyAsync((char *)din + (c0 - lo_all), dst, hi_pos - c0, hipMemcpyHostToDevice, c->up_stream));
         }
-        auto copy_part = [&](size_t k) {
-            const UpPiece &pc = pieces[k];
-            if (pc.text_len) { if (!strip_copy(dst + (pc.off - c0), pc.src, pc.text_len, pc.len)) bad_text.store(1); }
-            else std::memcpy(dst + (pc.off - c0), pc.src, pc.len);
-        };
-        if (nt == 1u) {
-            for (size_t k = i; k < j; ++k) copy_part(k);
-        } else if (any_text) {                                   // whole parts, handed out dynamically
-            std::atomic<size_t> next{i};
-            stage_pool.run(nt, [&](unsigned) { for (size_t k; (k = next.fetch_add(1)) < j;) copy_part(k); });
-        } else {                                                 // worker t copies the bytes [t, t+1) * share of the concatenated parts
-            const size_t share = (bytes + nt - 1) / nt;
-            stage_pool.run(nt, [&](unsigned t) {
-                const size_t lo = (size_t)t * share, hi = std::min<size_t>(bytes, lo + share);
-                size_t at = 0;
-                for (size_t k = i; k < j; ++k) {
-                    const UpPiece &pc = pieces[k];
-                    const size_t a = std::max(lo, at), z = std::min<size_t>(hi, at + pc.len);
-                    if (z > a) std::memcpy(dst + (pc.off - c0) + (a - at), pc.src + (a - at), z - a);
-                    at += pc.len;
-                    if (at >= hi) break;
-                }
-            });
-        }
-        const uint64_t hi = pieces[j - 1].off + pieces[j - 1].len;
-        HIP_TRY(c, hipMemcpyAsync((char *)din + (c0 - lo_all), dst, hi - c0, hipMemcpyHostToDevice, c->up_stream));
         HIP_TRY(c, hipEventRecord(c->pin_up_ev[slot], c->up_stream));
-        c->upload_stats[1].fetch_add(1, std::memory_order_relaxed);
-        if (nt > 1u && pooled) c->upload_stats[6].fetch_add(1, std::memory_order_relaxed);
+        for (int q = 0; q < 8; ++q) if (add[q]) c->upload_stats[q].fetch_add(add[q], std::memory_order_relaxed);
+        if (packed && stage_timing) t_issue += ms_between(tp1, Clock::now());
         used[slot] = true;
         slot = (slot + 1) % ts_ctx::kUpSlots;
         i = j;
     }
     if (bad_text.load()) return c->fail(TS_ERR_INVALID_ARG, "a text piece holds fewer bases than it declares");
-    return gather_device_pieces(c, on_device, din, lo_all);
+    return gather_device_pieces(c, call.on_device, din, lo_all);
 }
 
 // The upload pieces of one scanned region of an item: its bases [rg_start, rg_start + rg_len), whose first lies at byte

@@ -1,6 +1,6 @@
-// text_core.h — the walks over FASTA body text of the host upload (pipeline.cpp: upload_pieces, region_pieces) and the staging
-// workers' range cuts of a packed chunk, one source for the library and for a host test program (tests/cpp/text_pack_host.cpp,
-// built by g++ under ASan + UBSan).  Host only: no HIP include, no allocation beyond the cuts' vector.
+// text_core.h — the walks over FASTA body text of the host upload (upload_stage_core.h: the staging of a chunk; pipeline.cpp:
+// region_pieces) and the staging workers' range cuts of a packed chunk, one source for the library and for a host test program
+// (tests/cpp/text_pack_host.cpp, built by g++ under ASan + UBSan).  Host only: no HIP include, no allocation beyond the cuts' vector.
 //
 // A byte of body text is a base unless it is (part of) a line end: a line feed, or a carriage return right before one or at the
 // very end of the text.  ts::pack_text (pack.cpp) reads text by the same rule.
