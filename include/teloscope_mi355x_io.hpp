@@ -49,8 +49,7 @@
 #include "teloscope_mi355x_filter.hpp"
 #include "teloscope_mi355x_gzip.hpp"
 #include "teloscope_mi355x_ring.hpp"
-#include "../teloscope_amd/csrc/read_block_format_core.h"
-#include "../teloscope_amd/csrc/read_fastq_format_core.h"
+#include "teloscope_mi355x_reads_host.hpp"
 
 namespace teloscope_mi355x {
 
@@ -530,442 +529,8 @@ inline std::vector<PathData> walkPaths(Teloscope &teloscope, const std::vector<F
     return walkRecordViews(teloscope, views, 0);
 }
 
-// ---------------------------------------------------------------------------------------------
-// --fastq-subset (Input::readFastqSubset, src/input.cpp:737-832): echo the reads that carry a terminal
-// telomere block, in input order, byte for byte.  Records are read by the 4-line rules of
-// readFastqRecord (src/input.cpp:113-138: blank lines before a header are skipped, line contents are
-// kept verbatim, '\r' included) from a plain or gzip file ("-" = stdin) and filtered in batches of up
-// to readsPerBatch reads / basesPerBatch bases — a GPU batch, not the reference's 2048-record one.
-// Malformed input throws std::runtime_error with the reference's message.
-struct FastqSubsetResult { uint64_t kept = 0, total = 0, blockLines = 0; };     // blockLines: lines of the read block report, if one was asked for
-
 namespace detail {
-inline size_t logicalLineLength(const char *b, const char *e) { return (e > b && e[-1] == '\r') ? static_cast<size_t>(e - b) - 1 : static_cast<size_t>(e - b); }
-
-struct FastqRec { const char *begin, *seq, *end; uint64_t seqLen; bool needNewline; };
-
-// Parses the records that START in [p, limit) of a complete FASTQ text ending at `end` (the last line may lack its
-// '\n'), by readFastqRecord's rules (src/input.cpp:113-138).  Returns where it stopped — the start of the first record
-// at or beyond `limit`, or `end` — or nullptr at the first thing that is not a well-formed record (the caller then
-// re-parses sequentially to report it the way the reference does).
-inline const char *parseFastqPiece(const char *p, const char *limit, const char *end, std::vector<FastqRec> &out) {
-    auto nextLine = [&](const char *from, const char *&lb, const char *&le, const char *&next) -> bool {
-        if (from >= end) return false;
-        const char *nl = static_cast<const char *>(std::memchr(from, '\n', static_cast<size_t>(end - from)));
-        lb = from; le = nl ? nl : end; next = nl ? nl + 1 : end;
-        return true;
-    };
-    while (p < limit) {
-        const char *hb, *he, *nx;
-        if (!nextLine(p, hb, he, nx)) break;
-        if (logicalLineLength(hb, he) == 0) { p = nx; continue; }             // blank line before a header
-        const char *sb, *se, *pb, *pe, *qb, *qe, *n2, *n3, *n4;
-        if (!(nextLine(nx, sb, se, n2) && nextLine(n2, pb, pe, n3) && nextLine(n3, qb, qe, n4))) return nullptr;
-        if (he == hb || *hb != '@' || pe == pb || *pb != '+' || logicalLineLength(sb, se) != logicalLineLength(qb, qe)) return nullptr;
-        out.push_back(FastqRec{hb, sb, qe, static_cast<uint64_t>(se - sb), true});
-        p = n4;
-    }
-    return p;
-}
-
-// All records of a mapped FASTQ text, found by the host threads: the text is cut into pieces; a piece starts at the first
-// line that looks like a header ('@' first, the line after next begins with '+', the next line does not begin with '@' — a
-// quality line may begin with '@', but then the line after it is a header), every piece is parsed on its own, and the
-// pieces are accepted only if each parse lands exactly on the next piece's start.  false = not provably well-formed this
-// way: parse sequentially instead.
-inline bool splitFastqRecords(const char *data, size_t size, std::vector<FastqRec> &records, size_t pieceBytes = size_t(32) << 20) {
-    const char *end = data + size;
-    const size_t np = std::max<size_t>(1, std::min<size_t>(256, size / std::max<size_t>(pieceBytes, 1)));
-    if (np < 2) return false;
-    std::vector<const char *> start(np + 1, nullptr);
-    start[0] = data; start[np] = end;
-    std::atomic<bool> bad{false};
-    auto lineAfter = [&](const char *q) -> const char * {                    // start of the line after the one holding q
-        const char *nl = static_cast<const char *>(std::memchr(q, '\n', static_cast<size_t>(end - q)));
-        return nl ? nl + 1 : end;
-    };
-    {
-        std::atomic<size_t> next{1};
-        auto worker = [&]() {
-            for (size_t i; (i = next.fetch_add(1)) < np;) {
-                const char *q = lineAfter(data + size / np * i - 1);          // a line start at or after the cut
-                int tries = 0;
-                for (; q < end && tries < 64; ++tries) {
-                    const char *l1 = lineAfter(q), *l2 = l1 < end ? lineAfter(l1) : end;
-                    if (*q == '@' && l1 < end && *l1 != '@' && l2 < end && *l2 == '+') break;
-                    q = l1;
-                }
-                if (q < end && tries == 64) { bad.store(true); return; }       // 64 lines without a header: not FASTQ-shaped
-                start[i] = q < end ? q : end;                                     // (no record starts behind this cut)
-            }
-        };
-        const unsigned nt = static_cast<unsigned>(std::min<size_t>({size_t(16), np, size_t(std::max(1u, std::thread::hardware_concurrency()))}));
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < nt; ++t) pool.emplace_back(worker);
-        for (std::thread &th : pool) th.join();
-    }
-    if (bad.load()) return false;
-    for (size_t i = 1; i <= np; ++i) if (start[i] < start[i - 1]) return false;
-    std::vector<std::vector<FastqRec>> parts(np);
-    {
-        std::atomic<size_t> next{0};
-        auto worker = [&]() {
-            for (size_t i; (i = next.fetch_add(1)) < np;) {
-                if (start[i] == start[i + 1]) continue;
-                parts[i].reserve(static_cast<size_t>(start[i + 1] - start[i]) / 20000 + 16);
-                const char *stop = parseFastqPiece(start[i], start[i + 1], end, parts[i]);
-                if (stop != start[i + 1]) { bad.store(true); return; }
-            }
-        };
-        const unsigned nt = static_cast<unsigned>(std::min<size_t>({size_t(16), np, size_t(std::max(1u, std::thread::hardware_concurrency()))}));
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < nt; ++t) pool.emplace_back(worker);
-        for (std::thread &th : pool) th.join();
-    }
-    if (bad.load()) return false;
-    size_t total = 0;
-    for (const auto &v : parts) total += v.size();
-    records.clear();
-    records.reserve(total);
-    for (const auto &v : parts) records.insert(records.end(), v.begin(), v.end());
-    return true;
-}
-}  // namespace detail
-
-namespace detail {
-// The library's first call in a process pays for its streams, its kernels' code, the device pool and the pinned staging (about
-// 75 ms, whatever the size of the call).  The subset tools make it here, on one dummy read and a thread of its own, while their
-// first block of input is still being read and parsed; joined before the first real batch.
-class FilterWarmUp {
-    std::thread th;
-public:
-    explicit FilterWarmUp(ReadTelomereFilter &filter) {
-        th = std::thread([&filter] {
-            try {
-                const std::string seq(4096, 'A');
-                const char *p = seq.data();
-                uint64_t l = seq.size();
-                uint8_t pass = 0;
-                filter.matchesPointers(&p, &l, 1, &pass);
-            } catch (...) {}
-        });
-    }
-    void join() { if (th.joinable()) th.join(); }
-    ~FilterWarmUp() { join(); }
-    FilterWarmUp(const FilterWarmUp &) = delete;
-    FilterWarmUp &operator=(const FilterWarmUp &) = delete;
-};
-}  // namespace detail
-
-namespace detail {
-// The read block report of the host routes (the rule: include/teloscan.h, "The read block report"; the output is this project's
-// own, its columns those of the terminal loop of the reference's writeBEDFile, src/teloscope.cpp).  A route adds the reads it keeps
-// of a batch, in output order; flush() scans them once more as tips-only segments at abs_pos 0 on the filter's context
-// (ts_scan_segments_blocks: the blocks the filter's bit was made from), formats a line per terminal block with the core header the
-// device formatter compiles, and writes them.  Without a stream nothing is kept and nothing runs.
-class ReadBlockReport {
-public:
-    uint64_t lines = 0;
-    ReadBlockReport(std::ostream *os, const char *failed) : os_(os), failed_(failed) {}
-    bool on() const { return os_ != nullptr; }
-    void add(const char *name, uint32_t nameLen, const char *seq, uint64_t len) { if (os_) kept_.push_back(Kept{name, nameLen, seq, len}); }
-    void flush(ts_ctx *ctx) {
-        if (!os_ || kept_.empty()) return;
-        segs_.assign(kept_.size(), ts_segment_in{});
-        outs_.assign(kept_.size(), ts_segment_out{});
-        for (size_t i = 0; i < kept_.size(); ++i) { segs_[i].seq = kept_[i].seq; segs_[i].len = kept_[i].len; segs_[i].tips_only = 1; }
-        if (ts_scan_segments_blocks(ctx, segs_.data(), segs_.size(), outs_.data(), nullptr) != TS_OK) throw std::runtime_error(std::string("block calling of the kept reads failed: ") + ts_last_error(ctx));
-        text_.clear();
-        for (size_t i = 0; i < kept_.size(); ++i)
-            for (uint64_t j = 0; j < outs_[i].n_terminal_blocks; ++j) {
-                const ts_block &b = outs_[i].terminal_blocks[j];
-                const tsrb::Fields f{b.start, b.block_len, b.forward_count, b.reverse_count, b.canonical_count, b.non_canonical_count,
-                                     static_cast<uint32_t>(kept_[i].len), static_cast<uint32_t>(static_cast<unsigned char>(b.block_label))};
-                const size_t at = text_.size();
-                text_.resize(at + tsrb::line_len(kept_[i].nameLen, f));
-                Sink sink{&text_[at]};
-                tsrb::put_line(sink, 0u, Bytes{kept_[i].name}, 0, kept_[i].nameLen, f);
-                ++lines;
-            }
-        ts_free_segments(outs_.data(), outs_.size());
-        kept_.clear();
-        os_->write(text_.data(), static_cast<std::streamsize>(text_.size()));
-        if (!os_->good()) throw std::runtime_error(failed_);
-    }
-    struct Bytes { const char *p; uint32_t byte(uint64_t i) const { return static_cast<unsigned char>(p[i]); } };
-
-private:
-    struct Kept { const char *name; uint32_t nameLen; const char *seq; uint64_t len; };
-    struct Sink { char *p; void put(uint32_t at, uint32_t byte) { p[at] = static_cast<char>(byte); } };
-    std::ostream *os_;
-    const char *failed_;
-    std::vector<Kept> kept_;
-    std::vector<ts_segment_in> segs_;
-    std::vector<ts_segment_out> outs_;
-    std::string text_;
-};
-}  // namespace detail
-
-inline FastqSubsetResult fastqSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 512u << 20, std::ostream *blocks = nullptr) {
-    detail::FilterWarmUp warmUp(filter);
-    detail::ReadBlockReport report(blocks, "failed while writing the FASTQ subset's block report");
-    // The input is read in large blocks into one arena and parsed in place: a batch's sequences are
-    // handed to the filter as pointers into the arena and a kept record is echoed as the byte range of
-    // its four lines — no per-line copies.
-    // (a plain file is read with pread(2) straight into the block; gzip input and stdin go through zlib)
-    struct Source {
-        gzFile gz = nullptr;
-        int fd = -1;
-        ~Source() { if (gz) gzclose(gz); if (fd >= 0) ::close(fd); }
-        long get(char *dst, size_t n) {
-            if (gz) return gzread(gz, dst, static_cast<unsigned>(std::min<size_t>(n, 1u << 30)));
-            return static_cast<long>(::read(fd, dst, std::min<size_t>(n, 1u << 30)));
-        }
-    } src;
-    if (inFile != "-") {
-        src.fd = ::open(inFile.c_str(), O_RDONLY);
-        if (src.fd < 0) throw std::runtime_error("Stream not successful: " + inFile);
-        unsigned char magic[2] = {0, 0};
-        const bool gz = ::pread(src.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        if (gz) { src.gz = gzdopen(src.fd, "rb"); src.fd = -1; }
-    } else {
-        src.gz = gzdopen(0, "rb");
-    }
-    if (!src.gz && src.fd < 0) throw std::runtime_error("Stream not successful: " + inFile);
-    if (src.gz) gzbuffer(src.gz, 1u << 20);
-    const bool seekable = !src.gz && ::lseek(src.fd, 0, SEEK_CUR) != static_cast<off_t>(-1);   // a FIFO is read in order
-    // Two blocks in turn: while one is parsed and filtered on the GPU, a reader thread fills the other (a plain
-    // file by up to eight concurrent pread(2) streams, gzip / stdin through zlib).  A block's data starts at `head`
-    // bytes into its buffer, so that the partial record left over from the previous block can be put in front
-    // of it without moving the block.
-    const size_t blockBytes = std::max<size_t>(bytesPerBatch, 64);
-    struct Block {
-        std::vector<char> buf;
-        size_t begin = 0, end = 0;         // valid bytes [begin, end)
-        bool last = false;                 // the input ended inside (or right before) this block
-    } blk[2];
-    size_t head = std::min<size_t>(blockBytes, 1u << 20);
-    uint64_t fileOff = 0;                  // next byte of a plain file
-    auto fill = [&](Block &b) {            // reads up to blockBytes bytes to b.buf[head ..)
-        if (b.buf.size() < head + blockBytes) b.buf.resize(head + blockBytes);
-        char *dst = b.buf.data() + head;
-        size_t got = 0;
-        b.last = false;
-        if (seekable) {
-            // slices of the block are read concurrently; a short slice means the file ends there
-            const unsigned nth = blockBytes >= (64u << 20) ? std::min(8u, std::max(2u, std::thread::hardware_concurrency() / 2u)) : 1u;
-            const size_t share = (blockBytes + nth - 1) / nth;
-            std::vector<size_t> done(nth, 0);
-            std::vector<int> bad(nth, 0);
-            auto readSlice = [&](unsigned t) {
-                const size_t lo = std::min(blockBytes, t * share), hi = std::min(blockBytes, lo + share);
-                size_t n = 0;
-                while (lo + n < hi) {
-                    const ssize_t r = ::pread(src.fd, dst + lo + n, std::min<size_t>(hi - lo - n, 1u << 30), static_cast<off_t>(fileOff + lo + n));
-                    if (r < 0) { bad[t] = 1; break; }
-                    if (r == 0) break;
-                    n += static_cast<size_t>(r);
-                }
-                done[t] = n;
-            };
-            if (nth == 1) readSlice(0);
-            else {
-                std::vector<std::thread> pool;
-                for (unsigned t = 0; t < nth; ++t) pool.emplace_back(readSlice, t);
-                for (std::thread &th : pool) th.join();
-            }
-            for (unsigned t = 0; t < nth; ++t) {
-                if (bad[t]) throw std::runtime_error("read error in FASTQ input");
-                const size_t lo = std::min(blockBytes, t * share), hi = std::min(blockBytes, lo + share);
-                got += done[t];
-                if (done[t] < hi - lo) { b.last = true; break; }      // end of file inside this slice
-            }
-            fileOff += got;
-        } else {
-            while (got < blockBytes) {
-                const long n = src.get(dst + got, blockBytes - got);
-                if (n < 0) throw std::runtime_error("read error in FASTQ input");
-                if (n == 0) { b.last = true; break; }
-                got += static_cast<size_t>(n);
-            }
-        }
-        b.begin = head;
-        b.end = head + got;
-    };
-    bool first = true;
-    FastqSubsetResult res;
-    uint64_t recordNumber = 0;
-    auto fail = [&](const char *msg) { throw std::runtime_error("FASTQ record " + std::to_string(recordNumber + 1) + ": " + msg); };
-    using Rec = detail::FastqRec;
-    std::vector<Rec> batch;
-    std::vector<const char *> ptr;
-    std::vector<uint64_t> len;
-    std::vector<uint8_t> pass;
-    std::string text;
-    // filters `batch` on the GPU and echoes the kept records
-    auto runBatch = [&]() {
-        if (batch.empty()) return;
-        ptr.resize(batch.size()); len.resize(batch.size()); pass.resize(batch.size());
-        for (size_t i = 0; i < batch.size(); ++i) { ptr[i] = batch[i].seq; len[i] = batch[i].seqLen; }
-        warmUp.join();
-        filter.matchesPointers(ptr.data(), len.data(), batch.size(), pass.data());
-        text.clear();
-        for (size_t i = 0; i < batch.size(); ++i) {
-            if (!pass[i]) continue;
-            text.append(batch[i].begin, batch[i].end);
-            text.push_back('\n');
-            ++res.kept;
-            if (report.on())
-                report.add(batch[i].begin + 1, tsrb::fastq_name_len(detail::ReadBlockReport::Bytes{batch[i].begin}, 0, static_cast<uint32_t>(batch[i].seq - batch[i].begin)),
-                           batch[i].seq, detail::logicalLineLength(batch[i].seq, batch[i].seq + batch[i].seqLen));
-        }
-        res.total += batch.size();
-        out.write(text.data(), static_cast<std::streamsize>(text.size()));
-        if (!out.good()) throw std::runtime_error("failed while writing FASTQ subset");
-        report.flush(filter.context(0));
-        res.blockLines = report.lines;
-    };
-    // Parses whole records out of [p, end) — several GPU batches if the range holds more than readsPerBatch reads or
-    // bytesPerBatch record bytes — filters them and echoes the kept ones; returns the end of the last whole record.
-    auto processRange = [&](const char *p, const char *const end, const bool eof) -> const char * {
-        const char *consumed = p;
-        // parse whole records out of the block; several GPU batches if it holds more than readsPerBatch reads
-        bool more = true;
-        while (more) {
-            batch.clear();
-            more = false;
-            size_t batchBytes = 0;
-            while (p < end) {
-                if (batch.size() >= readsPerBatch || batchBytes >= bytesPerBatch) { more = true; break; }
-                // a line = [p, nl); at end of input the last line may lack its '\n'
-                auto nextLine = [&](const char *from, const char *&lb, const char *&le, const char *&next) -> bool {
-                    if (from >= end) return false;
-                    const char *nl = static_cast<const char *>(std::memchr(from, '\n', static_cast<size_t>(end - from)));
-                    if (!nl && !eof) return false;                 // incomplete line: wait for more input
-                    lb = from; le = nl ? nl : end; next = nl ? nl + 1 : end;
-                    return true;
-                };
-                const char *hb, *he, *nx;
-                if (!nextLine(p, hb, he, nx)) break;
-                if (detail::logicalLineLength(hb, he) == 0) { p = nx; consumed = p; continue; }   // blank line before a header
-                const char *sb, *se, *pb, *pe, *qb, *qe, *n2, *n3, *n4;
-                const bool l2 = nextLine(nx, sb, se, n2), l3 = l2 && nextLine(n2, pb, pe, n3), l4 = l3 && nextLine(n3, qb, qe, n4);
-                if (!l4) {
-                    if (eof) fail("truncated FASTQ record");
-                    break;                                          // the record continues in the next block
-                }
-                if (he == hb || *hb != '@') fail("expected header line starting with '@'");
-                if (pe == pb || *pb != '+') fail("expected separator line starting with '+'");
-                if (detail::logicalLineLength(sb, se) != detail::logicalLineLength(qb, qe)) fail("sequence and quality length differ");
-                ++recordNumber;
-                batch.push_back(Rec{hb, sb, qe, static_cast<uint64_t>(se - sb), true});
-                batchBytes += static_cast<size_t>(n4 - hb);
-                p = n4;
-                consumed = p;
-            }
-            runBatch();
-        }
-        return consumed;
-    };
-    if (seekable) {
-        // A regular file is mapped and parsed where the page cache holds it: the only copy of a sequence is the one
-        // into the pinned upload ring.
-        struct stat sb;
-        if (::fstat(src.fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
-            const size_t size = static_cast<size_t>(sb.st_size);
-            void *map = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, src.fd, 0);
-            if (map != MAP_FAILED) {
-                (void)::madvise(map, size, MADV_SEQUENTIAL);
-                struct Unmap { void *p; size_t n; ~Unmap() { ::munmap(p, n); } } unmap{map, size};
-                const char *data = static_cast<const char *>(map);
-                if (data[0] != '@') throw std::runtime_error("FASTQ input must start with '@'");
-                // a large file's records are located by all host threads at once (one thread walks 3 GB of text in
-                // ~0.5 s); anything that is not provably well-formed that way takes the sequential parser, which
-                // reports errors the way the reference does
-                std::vector<Rec> all;
-                if (size >= (size_t(64) << 20) && detail::splitFastqRecords(data, size, all)) {
-                    size_t i = 0;
-                    while (i < all.size()) {
-                        batch.clear();
-                        size_t batchBytes = 0;
-                        while (i < all.size() && batch.size() < readsPerBatch && batchBytes < bytesPerBatch) {
-                            batchBytes += static_cast<size_t>(all[i].end - all[i].begin) + 1;
-                            batch.push_back(all[i++]);
-                        }
-                        runBatch();
-                    }
-                    out.flush();
-                    return res;
-                }
-                (void)processRange(data, data + size, true);
-                out.flush();
-                return res;
-            }
-        }
-    }
-    int cur = 0;
-    fill(blk[0]);
-    for (;;) {
-        Block &B = blk[cur], &N = blk[cur ^ 1];
-        const bool eof = B.last;
-        // the next block is read while this one is parsed and filtered
-        std::exception_ptr readError;
-        std::thread reader;
-        if (!eof) reader = std::thread([&] { try { fill(N); } catch (...) { readError = std::current_exception(); } });
-        struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{reader};
-        if (first) {
-            if (B.end == B.begin) throw std::runtime_error("FASTQ input is empty");
-            if (B.buf[B.begin] != '@') throw std::runtime_error("FASTQ input must start with '@'");
-            first = false;
-        }
-        const char *const end = B.buf.data() + B.end;
-        const char *const consumed = processRange(B.buf.data() + B.begin, end, eof);
-        if (eof) break;
-        reader.join();
-        if (readError) std::rethrow_exception(readError);
-        // what was not consumed (a partial record) goes in front of the next block's data
-        const size_t left = static_cast<size_t>(end - consumed);
-        if (left > N.begin) {                                   // more than the headroom (a record larger than a block)
-            const size_t have = N.end - N.begin;
-            std::vector<char> grown(left + std::max(blockBytes, have) + head);
-            std::memcpy(grown.data() + left, N.buf.data() + N.begin, have);
-            N.buf.swap(grown);
-            N.begin = left; N.end = left + have;
-            head = std::max(head, left);                        // later blocks leave that much room
-        }
-        if (left) std::memcpy(N.buf.data() + N.begin - left, consumed, left);
-        N.begin -= left;
-        cur ^= 1;
-    }
-    out.flush();
-    return res;
-}
-
-// ---------------------------------------------------------------------------------------------
-// --bam-subset (subsetBam, src/bam.cpp:188-259): copy the header and the alignment records whose read
-// carries a terminal telomere block, byte for byte, into a new BAM.
-//
-// BGZF is a series of independent gzip members of at most 64 KB, each carrying its own size ("BC" extra subfield), so the
-// input is not read as one stream: a few hundred MB of blocks are LOCATED by walking their headers (validated like
-// BgzfReader::loadBlock, src/bgzf.cpp:57-196: FEXTRA set, reserved flag bits clear, exactly one BC subfield of length 2,
-// block and uncompressed sizes <= 64 KB, optional file name / comment / header checksum), INFLATED by all host threads
-// straight into their places of one buffer (raw inflate must use the whole payload and yield exactly ISIZE bytes, CRC32
-// checked), the records in it are walked and validated, and their sequences (4-bit codes "=ACMGRSVTWYHKDBN") are decoded
-// by all host threads into one arena that the GPU filters in batches of up to readsPerBatch records.  The output is
-// written as BGZF blocks of <= 0xff00 payload bytes (raw deflate + the BC field + CRC32/ISIZE) closed by the EOF marker.
-// (Round 2 until here read the input with zlib's gz* API on one thread: 0.14 Gbases/s on a HiFi BAM;
-// profiles/r02/bam_subset_rate.txt.)
-// (deflatePlainBytes / deflateMemberBytes / msDeflate: what bamSubsetDevice compressed on the device under BamOutputDeflate::Device —
-// record bytes in, BGZF member bytes out, milliseconds its contexts spent in ts_bam_chunk_gather_bgzf; zero everywhere else)
-struct BamSubsetStats {
-    uint64_t totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0; bool missingEofBlock = false;
-    uint64_t deflatePlainBytes = 0, deflateMemberBytes = 0; double msDeflate = 0;
-    uint64_t blockLines = 0;                    // lines of the read block report, if one was asked for
-};
-
-namespace detail {
-// the host-side helpers of this header: a bounded queue between pipeline stages, and a dynamic parallel-for
+// a bounded queue between the stages of scanFastaToFiles (the dynamic parallel-for, onThreads: teloscope_mi355x_reads_host.hpp)
 template <typename T>
 class BoundedQueue {
 public:
@@ -993,493 +558,7 @@ private:
     size_t cap_;
     bool closed_ = false;
 };
-
-template <typename F>
-inline void onThreads(size_t n, F &&f) {                        // f(i) for i in [0, n), dynamic, on up to 16 host threads
-    const unsigned nt = static_cast<unsigned>(std::min<size_t>({size_t(16), n, size_t(std::max(1u, std::thread::hardware_concurrency()))}));
-    if (nt <= 1) { for (size_t i = 0; i < n; ++i) f(i); return; }
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < nt; ++t) pool.emplace_back([&] { for (size_t i; (i = next.fetch_add(1)) < n;) f(i); });
-    for (std::thread &th : pool) th.join();
-}
-
-struct BgzfBlockRef { const unsigned char *payload; uint32_t payloadLen, isize, crc; size_t outOff; };
-
-// The BGZF block that starts at p, of which n bytes are at hand: its total size, or 0 when it is not complete within n
-// bytes (more input is needed).  Throws on anything that is not a BGZF block.
-inline size_t parseBgzfBlock(const unsigned char *p, size_t n, BgzfBlockRef &ref, bool &eofMarker) {
-    static const unsigned char kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto u16 = [](const unsigned char *q) { return static_cast<uint32_t>(q[0]) | (static_cast<uint32_t>(q[1]) << 8); };
-    auto u32 = [&](const unsigned char *q) { return u16(q) | (u16(q + 2) << 16); };
-    if (n < 12) return 0;
-    if (p[0] != 31 || p[1] != 139 || p[2] != 8) throw std::runtime_error("input is not BGZF-compressed BAM (not a BAM file)");
-    const unsigned flags = p[3];
-    if ((flags & 0x04) == 0 || (flags & 0xe0) != 0) throw std::runtime_error("invalid BGZF gzip flags");
-    const size_t xlen = u16(p + 10);
-    if (n < 12 + xlen) return 0;
-    bool found = false;
-    size_t total = 0;
-    for (size_t pos = 12; pos < 12 + xlen;) {
-        if (12 + xlen - pos < 4) throw std::runtime_error("malformed BGZF extra field");
-        const size_t slen = u16(p + pos + 2), end = pos + 4 + slen;
-        if (end > 12 + xlen) throw std::runtime_error("malformed BGZF extra subfield");
-        if (p[pos] == 'B' && p[pos + 1] == 'C') {
-            if (slen != 2 || found) throw std::runtime_error("invalid BGZF BC subfield");
-            total = static_cast<size_t>(u16(p + pos + 4)) + 1;
-            found = true;
-        }
-        pos = end;
-    }
-    if (!found) throw std::runtime_error("BGZF block is missing the BC subfield");
-    if (total > 65536 || total < 12 + xlen + 8) throw std::runtime_error("invalid BGZF block size");
-    if (n < total) return 0;
-    size_t at = 12 + xlen;
-    const size_t footer = total - 8;
-    auto skipText = [&](const char *what) {
-        while (at < footer && p[at] != 0) ++at;
-        if (at == footer) throw std::runtime_error(std::string("unterminated BGZF ") + what);
-        ++at;
-    };
-    if (flags & 0x08) skipText("filename");
-    if (flags & 0x10) skipText("comment");
-    if (flags & 0x02) {
-        if (footer - at < 2) throw std::runtime_error("truncated BGZF header checksum");
-        const uLong crc = crc32(crc32(0L, Z_NULL, 0), p, static_cast<uInt>(at));
-        if (static_cast<uint32_t>(crc & 0xffffu) != u16(p + at)) throw std::runtime_error("BGZF header checksum mismatch");
-        at += 2;
-    }
-    ref.payload = p + at;
-    ref.payloadLen = static_cast<uint32_t>(footer - at);
-    ref.crc = u32(p + footer);
-    ref.isize = u32(p + footer + 4);
-    if (ref.isize > 65536) throw std::runtime_error("BGZF uncompressed block is too large");
-    eofMarker = total == sizeof kEof && std::memcmp(p, kEof, sizeof kEof) == 0;
-    return total;
-}
-
-inline void inflateBgzfBlock(const BgzfBlockRef &b, unsigned char *dst) {
-    z_stream zs{};
-    unsigned char dummy = 0;
-    zs.next_in = const_cast<unsigned char *>(b.payload); zs.avail_in = b.payloadLen;
-    zs.next_out = b.isize ? dst : &dummy; zs.avail_out = b.isize ? b.isize : 1;
-    if (inflateInit2(&zs, -15) != Z_OK) throw std::runtime_error("could not initialize BGZF decompressor");
-    const int rc = inflate(&zs, Z_FINISH);
-    const bool whole = rc == Z_STREAM_END && zs.total_out == b.isize && zs.total_in == b.payloadLen;
-    inflateEnd(&zs);
-    if (!whole) throw std::runtime_error("invalid BGZF deflate payload");
-    const uLong crc = crc32(crc32(0L, Z_NULL, 0), b.isize ? dst : Z_NULL, b.isize);
-    if (static_cast<uint32_t>(crc) != b.crc) throw std::runtime_error("BGZF checksum mismatch");
-}
-
-// Uncompressed bytes of a BGZF file or stream, a few hundred MB per call, inflated by all host threads.
-class BgzfParallelReader {
-    int fd_;
-    const unsigned char *map_ = nullptr;        // a regular file is mapped ...
-    size_t mapSize_ = 0, mapPos_ = 0;
-    std::vector<unsigned char> buf_;            // ... a pipe is read into a buffer (the incomplete block at its end is kept)
-    bool streamEof_ = false;
-    std::vector<BgzfBlockRef> blocks_;
-public:
-    bool sawEofMarker = false;
-    explicit BgzfParallelReader(int fd) : fd_(fd) {
-        struct stat st;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) {
-                map_ = static_cast<const unsigned char *>(m); mapSize_ = static_cast<size_t>(st.st_size);
-                ::madvise(m, mapSize_, MADV_SEQUENTIAL);
-            }
-        }
-    }
-    ~BgzfParallelReader() { if (map_) ::munmap(const_cast<unsigned char *>(map_), mapSize_); }
-    BgzfParallelReader(const BgzfParallelReader &) = delete;
-    BgzfParallelReader &operator=(const BgzfParallelReader &) = delete;
-
-    // Inflates the next whole blocks into dst[0 .. cap) (cap >= 64 KB): the number of bytes produced; `more` = false when
-    // the input is exhausted.
-    size_t next(unsigned char *dst, size_t cap, bool &more) {
-        const unsigned char *w;
-        size_t wn;
-        bool atEnd;
-        if (map_) { w = map_ + mapPos_; wn = mapSize_ - mapPos_; atEnd = true; }
-        else {
-            while (!streamEof_ && buf_.size() < cap) {             // compressed bytes: never more than the uncompressed room
-                const size_t at = buf_.size();
-                buf_.resize(at + (8u << 20));
-                const ssize_t r = ::read(fd_, buf_.data() + at, 8u << 20);
-                if (r < 0) throw std::runtime_error("cannot read BAM input");
-                buf_.resize(at + static_cast<size_t>(r));
-                if (r == 0) streamEof_ = true;
-            }
-            w = buf_.data(); wn = buf_.size(); atEnd = streamEof_;
-        }
-        blocks_.clear();
-        size_t used = 0, produced = 0;
-        while (used < wn) {
-            BgzfBlockRef ref{};
-            bool eofm = false;
-            const size_t total = parseBgzfBlock(w + used, wn - used, ref, eofm);
-            if (total == 0) {
-                if (atEnd) throw std::runtime_error(wn - used < 12 ? "truncated BGZF header" : "truncated BGZF block");
-                break;
-            }
-            if (produced + ref.isize > cap) break;
-            sawEofMarker = sawEofMarker || eofm;
-            ref.outOff = produced;
-            produced += ref.isize;
-            blocks_.push_back(ref);
-            used += total;
-        }
-        if (!blocks_.empty()) {
-            const size_t per = 32, tasks = (blocks_.size() + per - 1) / per;
-            std::mutex em;
-            std::exception_ptr err;
-            onThreads(tasks, [&](size_t t) {
-                try {
-                    for (size_t i = t * per; i < std::min(blocks_.size(), (t + 1) * per); ++i) inflateBgzfBlock(blocks_[i], dst + blocks_[i].outOff);
-                } catch (...) { std::lock_guard<std::mutex> g(em); if (!err) err = std::current_exception(); }
-            });
-            if (err) std::rethrow_exception(err);
-        }
-        if (map_) mapPos_ += used; else buf_.erase(buf_.begin(), buf_.begin() + static_cast<std::ptrdiff_t>(used));
-        more = used > 0 && (map_ ? mapPos_ < mapSize_ : !(streamEof_ && buf_.empty()));
-        return produced;
-    }
-};
 }  // namespace detail
-
-// FASTQ out of the BAM and SAM subsets (the rule: include/teloscan.h, "FASTQ out of the BAM and SAM subsets"): what
-// bamSubsetFastq, samSubsetFastq and their device forms write in place of the kept records' own bytes.  restoreStrand: a record
-// whose FLAG has 0x10 set is written reverse-complemented, its quals reversed (TS_FASTQ_OUT_RESTORE_STRAND) — the read as the
-// sequencer gave it; false writes SEQ and QUAL as stored.
-struct ReadFastqOutput { bool restoreStrand = true; };
-
-namespace detail {
-inline uint32_t fastqOutFlags(const ReadFastqOutput &f) { return f.restoreStrand ? TS_FASTQ_OUT_RESTORE_STRAND : 0u; }
-// a located record's text behind `text`: the host routes' formatter, every byte from the core header the device compiles
-inline void appendFastqText(std::string &text, const char *bytes, const tsfq::Rec &r) {
-    const size_t at = text.size(), n = static_cast<size_t>(tsfq::record_len(r));
-    text.resize(at + n);
-    const ReadBlockReport::Bytes b{bytes};
-    // (the lines one after the other: out_byte's bytes, without its search for the line a byte lies in)
-    char *p = &text[at];
-    *p++ = '@';
-    std::memcpy(p, bytes + r.name_off, r.name_len); p += r.name_len;
-    *p++ = '\n';
-    for (uint32_t j = 0; j < r.len; ++j) *p++ = static_cast<char>(tsfq::base_at(b, r, j));
-    *p++ = '\n'; *p++ = '+'; *p++ = '\n';
-    for (uint32_t j = 0; j < r.len; ++j) *p++ = static_cast<char>(tsfq::qual_at(b, r, j));
-    *p++ = '\n';
-}
-
-class BgzfWriter {
-    static constexpr size_t kPayload = 0xff00, kSlot = 65536, kBlocksPerFlush = 64;
-    std::ostream &out;
-    bool discard = false;                       // nothing is kept and nothing written: a route whose output is not BAM
-    std::vector<unsigned char> pending, comp;
-    std::vector<size_t> sizes;
-    static size_t block(const unsigned char *data, size_t n, unsigned char *slot) {         // one BGZF block into its 64 KB slot
-        z_stream zs{};
-        if (deflateInit2(&zs, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw std::runtime_error("deflateInit2 failed");
-        zs.next_in = const_cast<unsigned char *>(data); zs.avail_in = static_cast<unsigned>(n);
-        zs.next_out = slot + 18; zs.avail_out = kSlot - 18 - 8;
-        const int rc = deflate(&zs, Z_FINISH);
-        deflateEnd(&zs);
-        if (rc != Z_STREAM_END) throw std::runtime_error("BGZF block does not fit");
-        const size_t clen = zs.total_out, total = 18 + clen + 8;
-        static const unsigned char head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-        std::memcpy(slot, head, 16);
-        slot[16] = static_cast<unsigned char>((total - 1) & 0xff); slot[17] = static_cast<unsigned char>((total - 1) >> 8);
-        const uint32_t crc = static_cast<uint32_t>(crc32(crc32(0L, Z_NULL, 0), data, static_cast<unsigned>(n)));
-        unsigned char *tail = slot + 18 + clen;
-        for (int i = 0; i < 4; ++i) { tail[i] = static_cast<unsigned char>(crc >> (8 * i)); tail[4 + i] = static_cast<unsigned char>(static_cast<uint32_t>(n) >> (8 * i)); }
-        return total;
-    }
-    // the first `bytes` pending bytes leave as blocks of kPayload (the last one may be shorter), deflated by all host threads
-    void flush(size_t bytes) {
-        const size_t nb = (bytes + kPayload - 1) / kPayload;
-        if (!nb) return;
-        comp.resize(nb * kSlot);
-        sizes.assign(nb, 0);
-        std::mutex em;
-        std::exception_ptr err;
-        onThreads(nb, [&](size_t i) {
-            try { sizes[i] = block(pending.data() + i * kPayload, std::min(kPayload, bytes - i * kPayload), comp.data() + i * kSlot); }
-            catch (...) { std::lock_guard<std::mutex> g(em); if (!err) err = std::current_exception(); }
-        });
-        if (err) std::rethrow_exception(err);
-        for (size_t i = 0; i < nb; ++i) out.write(reinterpret_cast<const char *>(comp.data() + i * kSlot), static_cast<std::streamsize>(sizes[i]));
-        pending.erase(pending.begin(), pending.begin() + static_cast<std::ptrdiff_t>(bytes));
-    }
-public:
-    explicit BgzfWriter(std::ostream &o, bool discardAll = false) : out(o), discard(discardAll) {}
-    void write(const unsigned char *data, size_t n) {
-        if (discard) return;
-        pending.insert(pending.end(), data, data + n);
-        if (pending.size() >= kBlocksPerFlush * kPayload) flush(pending.size() / kPayload * kPayload);      // whole blocks only
-    }
-    // what is pending becomes members now (the last one may be short)
-    void flushPending() { flush(pending.size()); }
-    // finished BGZF members, verbatim, behind whatever was pending (which is flushed first)
-    void writeMembers(const unsigned char *members, size_t n) {
-        flushPending();
-        out.write(reinterpret_cast<const char *>(members), static_cast<std::streamsize>(n));
-    }
-    void finish() {
-        if (discard) return;
-        flush(pending.size());
-        static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        out.write(reinterpret_cast<const char *>(eof), sizeof eof);
-        out.flush();
-        if (!out.good()) throw std::runtime_error("failed while writing BAM subset");
-    }
-};
-// The BAM header in front of the records — magic, text, reference list — validated like copyBamHeader (src/bam.cpp:75-120:
-// text <= 1 GiB, names 1 .. 1 MiB and NUL-terminated, no negative counts or lengths) and copied verbatim to the writer.  The
-// bytes are the caller's: have(n) says whether n bytes lie at its cursor, bytes(off) points at them, and the cursor is moved
-// past what was copied.  A step that lacks bytes makes parse() return false; it is called again when more bytes have come.
-class BamHeaderParser {
-    static constexpr uint32_t kMaxHeaderText = 1u << 30, kMaxReferenceName = 1u << 20;
-    enum { Magic, Text, Refs, Records } phase = Magic;
-    uint32_t ltext = 0, nref = 0, refsDone = 0;
-    static uint32_t le32(const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); }
-public:
-    bool done() const { return phase == Records; }
-    // the input has ended: what an unfinished header is called
-    void requireDone() const { if (phase != Records) throw std::runtime_error(phase == Refs ? "truncated BAM reference" : "truncated BAM header"); }
-    template <typename Have, typename Bytes, typename Cursor>
-    bool parse(Have &&have, Bytes &&bytes, Cursor &pos, BgzfWriter &writer) {      // true when the header is complete
-        for (;;) {
-            if (phase == Magic) {
-                if (!have(8)) return false;
-                if (std::memcmp(bytes(0), "BAM\1", 4) != 0) throw std::runtime_error("input is not a BAM file");
-                ltext = le32(bytes(4));
-                if (ltext > kMaxHeaderText) throw std::runtime_error("invalid BAM header text length");
-                phase = Text;
-            } else if (phase == Text) {
-                const size_t n = 8 + static_cast<size_t>(ltext) + 4;
-                if (!have(n)) return false;
-                nref = le32(bytes(8 + static_cast<size_t>(ltext)));
-                if (nref > 0x7fffffffu) throw std::runtime_error("invalid BAM reference count");
-                writer.write(bytes(0), n);
-                pos += n;
-                phase = Refs;
-            } else if (phase == Refs) {
-                if (refsDone == nref) { phase = Records; return true; }
-                if (!have(4)) return false;
-                const uint32_t lname = le32(bytes(0));
-                if (lname == 0 || lname > kMaxReferenceName) throw std::runtime_error("invalid BAM reference name length");
-                const size_t n = 4 + static_cast<size_t>(lname) + 4;
-                if (!have(n)) return false;
-                if (*bytes(4 + static_cast<size_t>(lname) - 1) != 0) throw std::runtime_error("BAM reference name is not NUL-terminated");
-                if (le32(bytes(4 + static_cast<size_t>(lname))) > 0x7fffffffu) throw std::runtime_error("invalid BAM reference length");
-                writer.write(bytes(0), n);
-                pos += n;
-                ++refsDone;
-            } else {
-                return true;
-            }
-        }
-    }
-};
-}  // namespace detail
-
-namespace detail {
-// (the route itself, behind bamSubset and bamSubsetFastq: with `fastq` the kept records leave as FASTQ text, and no header, member
-// or EOF marker is written)
-inline BamSubsetStats bamSubsetHost(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
-                                    size_t bytesPerBatch, std::ostream *blocks, const ReadFastqOutput *fastq) {
-    BamSubsetStats stats;
-    detail::FilterWarmUp warmUp(filter);
-    detail::ReadBlockReport report(blocks, "failed while writing the BAM subset's block report");
-    std::string fastqText;
-    int fd = 0;
-    if (inFile != "-") {
-        fd = ::open(inFile.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("cannot open BAM input '" + inFile + "'");
-    }
-    struct Closer { int fd; ~Closer() { if (fd > 0) ::close(fd); } } closer{fd};
-    detail::BgzfParallelReader reader(fd);
-    auto le32 = [](const unsigned char *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) | (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24); };
-
-    detail::BgzfWriter writer(out, fastq != nullptr);
-    // Uncompressed bytes arrive in chunks of ~bytesPerBatch, inflated by a reader thread (which spreads the blocks over the
-    // host threads) into one of two buffers while the other one is parsed and filtered.  What a chunk leaves unconsumed —
-    // the head of a record that continues in the next chunk — is carried into the headroom in front of the next one.
-    constexpr size_t kHeadroom = 1u << 20;
-    const size_t chunkBytes = std::max<size_t>(bytesPerBatch, 1u << 20);
-    struct Chunk { std::unique_ptr<unsigned char[]> buf; size_t n = 0; bool more = false; std::exception_ptr err; };
-    Chunk chunks[2];
-    for (Chunk &c : chunks) c.buf.reset(new unsigned char[kHeadroom + chunkBytes]);
-    detail::BoundedQueue<Chunk *> ready(2), spare(2);
-    spare.push(&chunks[0]); spare.push(&chunks[1]);
-    double msInflate = 0;
-    using Clock = std::chrono::steady_clock;
-    std::thread inflater([&] {
-        Chunk *c;
-        while (spare.pop(c)) {
-            const Clock::time_point t0 = Clock::now();
-            try { c->err = nullptr; c->n = reader.next(c->buf.get() + kHeadroom, chunkBytes, c->more); }
-            catch (...) { c->err = std::current_exception(); c->n = 0; c->more = false; }
-            msInflate += std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-            const bool last = !c->more;
-            ready.push(c);
-            if (last) break;
-        }
-        ready.close();
-    });
-    struct Joiner { std::thread &t; detail::BoundedQueue<Chunk *> &q; ~Joiner() { q.close(); if (t.joinable()) t.join(); } } joiner{inflater, spare};
-
-    const unsigned char *plain = nullptr;       // the bytes being parsed: [plain + pos, plain + plainSize)
-    size_t plainSize = 0, pos = 0;
-    std::vector<unsigned char> carry, joined;   // unconsumed tail of the last chunk; (rare) a tail larger than the headroom + the next chunk
-    // header: a step of the parse that lacks bytes returns false and is retried when the next chunk has been inflated
-    detail::BamHeaderParser header;
-    auto have = [&](size_t n) { return plainSize - pos >= n; };
-    auto bytesAt = [&](size_t off) { return plain + pos + off; };
-
-    struct Rec { size_t rawOff, rawLen, seqAt; uint32_t seqLen; size_t seqOff; };
-    std::vector<Rec> recs;
-    std::unique_ptr<char[]> seqs;               // the chunk's decoded sequences, back to back
-    size_t seqsCap = 0;
-    std::vector<const char *> ptr;
-    std::vector<uint64_t> len;
-    std::vector<uint8_t> pass;
-    double msDecode = 0, msFilter = 0, msRecords = 0;
-    // two bases per packed byte
-    static const std::array<uint16_t, 256> pairs = [] {
-        std::array<uint16_t, 256> t{};
-        const char *bases = "=ACMGRSVTWYHKDBN";
-        for (unsigned v = 0; v < 256; ++v) {
-            const unsigned char two[2] = {static_cast<unsigned char>(bases[v >> 4]), static_cast<unsigned char>(bases[v & 15])};
-            uint16_t w;
-            std::memcpy(&w, two, 2);
-            t[v] = w;
-        }
-        return t;
-    }();
-    auto processRecords = [&]() {
-        if (recs.empty()) return;
-        size_t total = 0;
-        for (Rec &r : recs) { r.seqOff = total; total += (static_cast<size_t>(r.seqLen) + 1) & ~size_t(1); }      // even lengths: whole pairs are stored
-        if (total > seqsCap) { seqsCap = total + total / 8; seqs.reset(new char[seqsCap]); }
-        // decode on all host threads: tasks of ~2 MB of bases
-        std::vector<size_t> cut{0};
-        for (size_t i = 0, acc = 0; i < recs.size(); ++i) { acc += recs[i].seqLen; if (acc >= (2u << 20)) { cut.push_back(i + 1); acc = 0; } }
-        if (cut.back() != recs.size()) cut.push_back(recs.size());
-        const Clock::time_point td = Clock::now();
-        detail::onThreads(cut.size() - 1, [&](size_t t) {
-            for (size_t i = cut[t]; i < cut[t + 1]; ++i) {
-                const Rec &r = recs[i];
-                const unsigned char *packed = plain + r.seqAt;
-                char *dst = seqs.get() + r.seqOff;
-                for (size_t j = 0, n = (static_cast<size_t>(r.seqLen) + 1) / 2; j < n; ++j) std::memcpy(dst + 2 * j, &pairs[packed[j]], 2);
-            }
-        });
-        msDecode += std::chrono::duration<double, std::milli>(Clock::now() - td).count();
-        for (size_t a = 0; a < recs.size(); a += readsPerBatch) {
-            const size_t z = std::min(recs.size(), a + readsPerBatch);
-            ptr.clear(); len.clear();
-            for (size_t i = a; i < z; ++i)
-                if (recs[i].seqLen) { ptr.push_back(seqs.get() + recs[i].seqOff); len.push_back(recs[i].seqLen); }
-            pass.assign(ptr.size(), 0);
-            const Clock::time_point tf = Clock::now();
-            warmUp.join();
-            if (!ptr.empty()) filter.matchesPointers(ptr.data(), len.data(), ptr.size(), pass.data());
-            msFilter += std::chrono::duration<double, std::milli>(Clock::now() - tf).count();
-            size_t k = 0;
-            for (size_t i = a; i < z; ++i) {
-                const Rec &r = recs[i];
-                ++stats.totalRecords;
-                if (!r.seqLen) { ++stats.missingSequenceRecords; continue; }
-                if (pass[k++]) {
-                    if (fastq) {
-                        const ReadBlockReport::Bytes b{reinterpret_cast<const char *>(plain)};
-                        appendFastqText(fastqText, b.p, tsfq::bam_locate(b, r.rawOff, static_cast<uint32_t>(r.rawLen - 4), static_cast<uint32_t>(r.seqAt - r.rawOff),
-                                                                         r.seqLen, fastqOutFlags(*fastq)));
-                    } else writer.write(plain + r.rawOff, r.rawLen);
-                    ++stats.passedRecords;
-                    if (report.on()) {
-                        const char *rec = reinterpret_cast<const char *>(plain + r.rawOff);
-                        report.add(rec + tsrb::kBamNameAt, tsrb::bam_name_len(detail::ReadBlockReport::Bytes{rec}, 0), seqs.get() + r.seqOff, r.seqLen);
-                    }
-                }
-            }
-            if (fastq) {
-                out.write(fastqText.data(), static_cast<std::streamsize>(fastqText.size()));
-                fastqText.clear();
-                if (!out.good()) throw std::runtime_error("failed while writing BAM subset");
-            }
-            report.flush(filter.context(0));
-            stats.blockLines = report.lines;
-        }
-        recs.clear();
-    };
-
-    bool more = true;
-    while (more) {
-        Chunk *c = nullptr;
-        if (!ready.pop(c)) break;
-        if (c->err) std::rethrow_exception(c->err);
-        more = c->more;
-        const Clock::time_point t1 = Clock::now();
-        // the unconsumed tail of the chunk before goes in front of this one
-        if (carry.size() <= kHeadroom) {
-            unsigned char *start = c->buf.get() + kHeadroom - carry.size();
-            if (!carry.empty()) std::memcpy(start, carry.data(), carry.size());
-            plain = start; plainSize = carry.size() + c->n;
-        } else {                                            // a record of many MB that spans chunks
-            joined.assign(carry.begin(), carry.end());
-            joined.insert(joined.end(), c->buf.get() + kHeadroom, c->buf.get() + kHeadroom + c->n);
-            plain = joined.data(); plainSize = joined.size();
-        }
-        pos = 0;
-        if (header.done() || header.parse(have, bytesAt, pos, writer)) {
-            while (have(4)) {
-                const int32_t blockSize = static_cast<int32_t>(le32(plain + pos));
-                if (blockSize < 32 || static_cast<uint32_t>(blockSize) > (256u << 20)) throw std::runtime_error("invalid BAM record block_size");   // BAM_MAX_RECORD_SIZE, src/bam.cpp:29
-                if (!have(4 + static_cast<size_t>(blockSize))) break;
-                const unsigned char *core = plain + pos + 4;
-                const uint32_t lname = core[8], ncigar = static_cast<uint32_t>(core[12]) | (static_cast<uint32_t>(core[13]) << 8), lseq = le32(core + 16);
-                const uint64_t seqAt = 32ull + lname + 4ull * ncigar;
-                if (lname == 0 || lseq > 0x7fffffffu) throw std::runtime_error("invalid BAM record lengths");          // decodeSequence, src/bam.cpp:122-163
-                if (seqAt + (static_cast<uint64_t>(lseq) + 1) / 2 + lseq > static_cast<uint64_t>(blockSize))
-                    throw std::runtime_error("BAM record fields exceed block_size");
-                if (core[32 + lname - 1] != 0) throw std::runtime_error("BAM read name is not NUL-terminated");
-                recs.push_back(Rec{pos, 4 + static_cast<size_t>(blockSize), pos + 4 + static_cast<size_t>(seqAt), lseq, 0});
-                pos += 4 + static_cast<size_t>(blockSize);
-            }
-            processRecords();                   // (record offsets point into `plain`: used before the chunk goes back)
-        }
-        carry.assign(plain + pos, plain + plainSize);
-        msRecords += std::chrono::duration<double, std::milli>(Clock::now() - t1).count();
-        if (more) spare.push(c);
-    }
-    header.requireDone();
-    if (!carry.empty()) throw std::runtime_error(carry.size() < 4 ? "truncated BAM record size" : "truncated BAM record");
-    spare.close();
-    if (inflater.joinable()) inflater.join();
-    stats.missingEofBlock = !reader.sawEofMarker;
-    writer.finish();
-    if (fastq) { out.flush(); if (!out.good()) throw std::runtime_error("failed while writing BAM subset"); }
-    if (std::getenv("TS_TIMING"))
-        std::fprintf(stderr, "bamSubset: locate + inflate %.0f ms (reader thread), records (walk, decode, filter, write) %.0f ms of which decode %.0f ms, filter %.0f ms\n",
-                     msInflate, msRecords, msDecode, msFilter);
-    return stats;
-}
-}  // namespace detail
-inline BamSubsetStats bamSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
-    return detail::bamSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, nullptr);
-}
-// --bam-subset with FASTQ out (the rule: include/teloscan.h, "FASTQ out of the BAM and SAM subsets"): bamSubset's arguments,
-// statistics and exceptions, and the kept records as four FASTQ lines each in place of a BAM.  The valid records in front of a bad
-// one are written first, as bamSubset writes them.
-inline BamSubsetStats bamSubsetFastq(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, const ReadFastqOutput &fastq = ReadFastqOutput(),
-                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
-    return detail::bamSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, &fastq);
-}
 
 // ---- what the four device routes share: the input's bytes into a device chunk, and the judge step of the two read subsets ----
 namespace detail {
@@ -1488,45 +567,6 @@ inline std::runtime_error deviceError(ts_ctx *ctx, const char *what) {      // "
     const char *why = ts_last_error(ctx);
     return std::runtime_error(std::string(what) + ": " + (why ? why : "?"));
 }
-
-// An input's descriptor and, for a regular file that is not empty and can be mapped, its bytes.  `-` is stdin where the route
-// says so; descriptor 0 is never closed from here (gzclose of a stream opened on it closes it, as it always did).
-struct MappedInput {
-    int fd = 0;
-    bool owned = false;
-    gzFile gz = nullptr;
-    const unsigned char *data = nullptr;
-    size_t size = 0;
-    MappedInput(const std::string &file, bool dashIsStdin, const std::string &cannotOpen) {
-        if (!dashIsStdin || file != "-") {
-            fd = ::open(file.c_str(), O_RDONLY);
-            if (fd < 0) throw std::runtime_error(cannotOpen);
-            owned = true;
-        }
-        struct stat st;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-            void *m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) { data = static_cast<const unsigned char *>(m); size = static_cast<size_t>(st.st_size); ::madvise(m, size, MADV_SEQUENTIAL); }
-        }
-    }
-    MappedInput(const MappedInput &) = delete;
-    MappedInput &operator=(const MappedInput &) = delete;
-    ~MappedInput() {
-        if (data) ::munmap(const_cast<unsigned char *>(data), size);
-        if (gz) gzclose(gz); else if (owned) ::close(fd);
-    }
-    // what did not map (a pipe, stdin) read to its end
-    void readToEnd(std::vector<unsigned char> &into, const char *cannotRead) const {
-        for (;;) {
-            const size_t at = into.size();
-            into.resize(at + (8u << 20));
-            const ssize_t r = ::read(fd, into.data() + at, 8u << 20);
-            if (r < 0) throw std::runtime_error(cannotRead);
-            into.resize(at + static_cast<size_t>(r));
-            if (r == 0) break;
-        }
-    }
-};
 
 // The BGZF member at p (its total size), or 0: what is there does not parse as a whole BGZF member
 inline size_t bgzfMemberOrNone(const unsigned char *p, size_t n, BgzfBlockRef &ref) {
@@ -1682,7 +722,7 @@ public:
         while (!streamDone_ && got_ < want) {
             if (got_ == b.size()) b.resize(std::min(want, 2 * b.size()));
             const size_t room = std::min<size_t>(std::min(b.size(), want) - got_, size_t(1) << 30);
-            const long n = in_.gz ? gzread(in_.gz, b.data() + got_, static_cast<unsigned>(room)) : static_cast<long>(::read(in_.fd, b.data() + got_, room));
+            const long n = in_.get(b.data() + got_, room);
             if (n < 0) throw std::runtime_error(opt_.cannotRead);
             if (n == 0) { streamDone_ = true; break; }
             got_ += static_cast<size_t>(n);
@@ -1834,15 +874,8 @@ private:
             if (in_.size - from < 2 || in_.data[from] != 0x1f || in_.data[from + 1] != 0x8b) { streamDone_ = true; return; }
             if (::lseek(in_.fd, static_cast<off_t>(from), SEEK_SET) == static_cast<off_t>(-1)) throw std::runtime_error(opt_.cannotRead);
             gz = true;
-        } else if (!gz) {
-            unsigned char magic[2] = {0, 0};
-            gz = ::pread(in_.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
         }
-        if (gz) {
-            in_.gz = gzdopen(in_.fd, "rb");
-            if (!in_.gz) throw std::runtime_error(opt_.cannotOpen);
-            gzbuffer(in_.gz, 1u << 20);
-        }
+        in_.openZlib(gz, opt_.cannotOpen);                     // (not always: where gzip begins the file)
     }
 
     ts_ctx *ctx_;
@@ -1866,9 +899,6 @@ private:
 // per read), staged into a tips-only batch's input buffer by stage(batch), judged by the scan and the predicate the host routes
 // use (ts_batch_scan + ts_batch_read_pass, with the regrow-and-rescan of an overflowed batch: include/teloscan.h), the passing
 // records' bytes gathered by gather(dPass, dst, cap, &bytes, &nPassed) into `kept`.
-using Clock = std::chrono::steady_clock;
-inline double since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }    // ms
-
 struct ReadJudge {
     double msStage = 0, msFilter = 0, msGather = 0, msBlocks = 0;
     std::vector<unsigned char> kept;
@@ -2603,181 +1633,6 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
 inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
                                            size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks) {
     return detail::textSubsetDeviceRun<detail::FastqChunkSteps>("FASTQ", "fastqSubsetDevice", inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice, blocks);
-}
-
-// ---------------------------------------------------------------------------------------------
-// --sam-subset: the read filter over SAM text, the front end the reference names and does not have (docs/algorithm.md: "BAM I/O
-// is isolated from scoring so a future SAM parser or optional CRAM backend can reuse the same filter").  The rule — lines, header
-// lines, fields, the four checks, "*" sequences and what is written — is stated once in include/teloscan.h above
-// ts_sam_chunk_walk; both routes below follow it, and their output bytes, statistics and exception texts are the same.
-struct SamSubsetStats { uint64_t headerLines = 0, totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0, blockLines = 0; };   // blockLines: of the read block report
-
-namespace detail {
-inline const char *samErrorText(int error) {
-    return error == TS_SAM_HEADER_AFTER_RECORD ? "header line after the first alignment record" : error == TS_SAM_TOO_FEW_FIELDS ? "fewer than 11 fields"
-         : error == TS_SAM_EMPTY_SEQ ? "empty SEQ field" : "SEQ and QUAL length differ";
-}
-inline std::runtime_error samLineError(uint64_t line, int error) {
-    return std::runtime_error("SAM line " + std::to_string(line) + ": " + samErrorText(error));
-}
-
-// The host form of ts_sam_chunk_walk, with its meanings: text[0, size) starts at a line's first byte; the whole lines' header
-// extent and record table, the carry, and the lowest line that fails a check, by a sequential pass over the lines.
-struct SamWalk {
-    std::vector<ts_sam_record> recs;
-    uint64_t headerLines = 0, headerEnd = 0, lines = 0, next = 0, errorLine = 0, errorOff = 0;
-    int error = TS_SAM_OK;
-};
-inline void samWalkHost(const char *text, size_t size, bool atEnd, bool inHeader, SamWalk &w) {
-    w.recs.clear();
-    w.headerLines = w.headerEnd = w.lines = w.next = w.errorLine = w.errorOff = 0;
-    w.error = TS_SAM_OK;
-    const char *p = text, *const end = text + size;
-    bool header = inHeader;
-    auto closeHeader = [&]() { if (header) { header = false; w.headerEnd = static_cast<uint64_t>(p - text); } };
-    while (p < end) {
-        const char *nl = static_cast<const char *>(std::memchr(p, '\n', static_cast<size_t>(end - p)));
-        if (!nl && !atEnd) break;                               // the unfinished last line: the carry
-        const char *lineEnd = nl ? nl : end, *next = nl ? nl + 1 : end;
-        const char *e = lineEnd > p && lineEnd[-1] == '\r' ? lineEnd - 1 : lineEnd;     // the content's end
-        int bad = TS_SAM_OK;
-        if (p < lineEnd && *p == '@') {
-            if (header) ++w.headerLines; else bad = TS_SAM_HEADER_AFTER_RECORD;
-        } else {
-            closeHeader();
-            const char *tab[11];
-            int tabs = 0;
-            for (const char *q = p; tabs < 11 && (q = static_cast<const char *>(std::memchr(q, '\t', static_cast<size_t>(e - q)))) != nullptr; ++q) tab[tabs++] = q;
-            ts_sam_record r{};
-            r.off = static_cast<uint64_t>(p - text); r.size = static_cast<uint32_t>(lineEnd - p);
-            if (tabs < 10) bad = TS_SAM_TOO_FEW_FIELDS;
-            else {
-                const char *seq = tab[8] + 1, *qual = tab[9] + 1, *qualEnd = tabs > 10 ? tab[10] : e;
-                const size_t seqLen = static_cast<size_t>(tab[9] - seq), qualLen = static_cast<size_t>(qualEnd - qual);
-                const bool seqStar = seqLen == 1 && *seq == '*', qualStar = qualLen == 1 && *qual == '*';
-                r.seq_at = static_cast<uint32_t>(seq - p); r.seq_len = static_cast<uint32_t>(seqLen); r.flags = seqStar ? 1u : 0u;
-                if (seqLen == 0) bad = TS_SAM_EMPTY_SEQ;
-                else if (!seqStar && !qualStar && seqLen != qualLen) bad = TS_SAM_BAD_LENGTHS;
-            }
-            if (bad == TS_SAM_OK) w.recs.push_back(r);
-        }
-        if (bad != TS_SAM_OK) {
-            w.error = bad; w.errorLine = w.lines; w.errorOff = static_cast<uint64_t>(p - text);
-            break;
-        }
-        ++w.lines;
-        p = next;
-    }
-    w.next = static_cast<uint64_t>(p - text);
-    if (header && inHeader) w.headerEnd = w.next;               // every whole line is a header line
-}
-}  // namespace detail
-
-namespace detail {
-// (the route itself, behind samSubset and samSubsetFastq: with `fastq` the kept records leave as FASTQ text and no header line is
-// written)
-inline SamSubsetStats samSubsetHost(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
-                                    size_t bytesPerBatch, std::ostream *blocks, const ReadFastqOutput *fastq) {
-    detail::FilterWarmUp warmUp(filter);
-    detail::ReadBlockReport report(blocks, "failed while writing the SAM subset's block report");
-    struct Source { gzFile gz = nullptr; ~Source() { if (gz) gzclose(gz); } } src;
-    if (inFile == "-") src.gz = gzdopen(0, "rb");
-    else {
-        const int fd = ::open(inFile.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("Stream not successful: " + inFile);
-        src.gz = gzdopen(fd, "rb");
-        if (!src.gz) ::close(fd);
-    }
-    if (!src.gz) throw std::runtime_error("Stream not successful: " + inFile);
-    gzbuffer(src.gz, 1u << 20);
-    const size_t blockBytes = std::max<size_t>(bytesPerBatch, 64);
-    readsPerBatch = std::max<size_t>(readsPerBatch, 1);
-
-    SamSubsetStats stats;
-    std::vector<const char *> ptr;
-    std::vector<uint64_t> len;
-    std::vector<const ts_sam_record *> judged;
-    std::vector<uint8_t> pass;
-    std::string text;
-    auto write = [&](const char *p, size_t n) {
-        out.write(p, static_cast<std::streamsize>(n));
-        if (!out.good()) throw std::runtime_error("failed while writing SAM subset");
-    };
-    std::vector<char> buf;
-    size_t have = 0;                                            // buf[0, have): the unfinished line of the block before
-    bool eof = false, any = false, inHeader = true;
-    uint64_t lines = 0;
-    detail::SamWalk walk;
-    while (!eof) {
-        if (buf.size() < have + blockBytes) buf.resize(have + blockBytes);
-        size_t got = 0;
-        while (got < blockBytes) {
-            const int r = gzread(src.gz, buf.data() + have + got, static_cast<unsigned>(std::min<size_t>(blockBytes - got, 1u << 30)));
-            if (r < 0) throw std::runtime_error("read error in SAM input");
-            if (r == 0) { eof = true; break; }
-            got += static_cast<size_t>(r);
-        }
-        const size_t size = have + got;
-        any = any || size > 0;
-        if (eof && !any) throw std::runtime_error("SAM input is empty");
-        detail::samWalkHost(buf.data(), size, eof, inHeader, walk);
-        if (!fastq) write(buf.data(), static_cast<size_t>(walk.headerEnd));
-        stats.headerLines += walk.headerLines; stats.totalRecords += walk.recs.size();
-        if (walk.headerLines < walk.lines || walk.error != TS_SAM_OK) inHeader = false;
-        // the block's records in batches (they point into the block), the kept lines echoed
-        for (size_t a = 0; a < walk.recs.size(); a += readsPerBatch) {
-            const size_t n = std::min(readsPerBatch, walk.recs.size() - a);
-            ptr.clear(); len.clear(); judged.clear();
-            for (size_t i = a; i < a + n; ++i) {
-                const ts_sam_record &r = walk.recs[i];
-                if (r.flags & 1u) { ++stats.missingSequenceRecords; continue; }      // (SEQ is "*": never kept)
-                ptr.push_back(buf.data() + r.off + r.seq_at); len.push_back(r.seq_len); judged.push_back(&r);
-            }
-            if (judged.empty()) continue;
-            pass.resize(judged.size());
-            warmUp.join();
-            filter.matchesPointers(ptr.data(), len.data(), judged.size(), pass.data());
-            text.clear();
-            for (size_t i = 0; i < judged.size(); ++i) {
-                if (!pass[i]) continue;
-                if (fastq) {
-                    const ts_sam_record &r = *judged[i];
-                    appendFastqText(text, buf.data(), tsfq::sam_locate(ReadBlockReport::Bytes{buf.data()}, r.off, r.seq_at, r.seq_len, r.size, fastqOutFlags(*fastq)));
-                } else {
-                    text.append(buf.data() + judged[i]->off, judged[i]->size);
-                    text.push_back('\n');
-                }
-                ++stats.passedRecords;
-                if (report.on()) {
-                    const char *line = buf.data() + judged[i]->off;
-                    report.add(line, tsrb::sam_name_len(detail::ReadBlockReport::Bytes{line}, 0, judged[i]->seq_at), ptr[i], len[i]);
-                }
-            }
-            write(text.data(), text.size());
-            report.flush(filter.context(0));
-            stats.blockLines = report.lines;
-        }
-        if (walk.error != TS_SAM_OK) { out.flush(); throw detail::samLineError(lines + walk.errorLine + 1, walk.error); }
-        lines += walk.lines;
-        have = size - static_cast<size_t>(walk.next);
-        if (have) std::memmove(buf.data(), buf.data() + walk.next, have);
-    }
-    out.flush();
-    return stats;
-}
-}  // namespace detail
-// The host route: lines and fields are found on the host, a block of input at a time, and the sequences are judged in batches of
-// up to readsPerBatch through the filter, as fastqSubset does.  Input may be plain or gzip (both through zlib, which passes plain
-// bytes on as they are); `-` is stdin.
-inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
-                                size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
-    return detail::samSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, nullptr);
-}
-// --sam-subset with FASTQ out (the rule: include/teloscan.h, "FASTQ out of the BAM and SAM subsets"): samSubset's arguments,
-// statistics and exceptions, and the kept records as four FASTQ lines each; header lines are counted and not written.
-inline SamSubsetStats samSubsetFastq(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, const ReadFastqOutput &fastq = ReadFastqOutput(),
-                                     size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
-    return detail::samSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, &fastq);
 }
 
 namespace detail {
