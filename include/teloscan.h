@@ -997,8 +997,8 @@ int ts_sam_chunk_gather(ts_chunk *chunk, const ts_sam_record *recs, size_t n, co
                         uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
 
 /* ---- The read block report: the telomere blocks of the kept reads as text, a BED beside a read subset (--fastq-subset,
- *      --bam-subset, --sam-subset; include/teloscope_mi355x_io.hpp: the trailing `blocks` stream of fastqSubset, bamSubset,
- *      samSubset and their device forms), formatted where a sub-batch's reads were judged.  The reference has no such output; the
+ *      --bam-subset, --sam-subset, the FASTA read subset; include/teloscope_mi355x_io.hpp: the trailing `blocks` stream of
+ *      fastqSubset, bamSubset, samSubset, fastaSubset and their device forms), formatted where a sub-batch's reads were judged.  The reference has no such output; the
  *      rule is this project's own, stated here and nowhere else, and every caller follows it.  It mirrors the terminal loop of the
  *      reference's writeBEDFile (src/teloscope.cpp, the lines of _terminal_telomeres.bed) with pathSize replaced by the read's
  *      length and the scaffold / contig word dropped:
@@ -1010,10 +1010,11 @@ int ts_sam_chunk_gather(ts_chunk *chunk, const ts_sam_record *recs, size_t n, co
  *            name \t start \t end \t block_len \t label \t forward_count \t reverse_count \t canonical_count \t
  *            non_canonical_count \t read_len \n
  *          with end = start + block_len and label the block's block_label as that call returns it.  Always '\n', never '\r'.
- *        - read_len is the number of bases judged: seq_len - seq_cr for FASTQ, SEQ's length for SAM, l_seq for BAM.
+ *        - read_len is the number of bases judged: seq_len - seq_cr for FASTQ, SEQ's length for SAM, l_seq for BAM, n_bases for
+ *          FASTA reads.
  *        - name is, for FASTQ, the header line's bytes behind '@' up to the first space, tab or the line's end, a '\r' in front of
- *          the line's '\n' not counted to the line (the name may be empty); for SAM the bytes in front of the first tab; for BAM
- *          read_name without its NUL.
+ *          the line's '\n' not counted to the line (the name may be empty); for FASTA reads the same with '>' in place of '@';
+ *          for SAM the bytes in front of the first tab; for BAM read_name without its NUL.
  *        - A record that is not kept has no line; a kept record has at least one (matches() is !terminalBlocks.empty(),
  *          src/read-filter.cpp:37-45).  Secondary and supplementary BAM records are records like any other. */
 /* One row of a batch's ordered blocks: the segment (read) of the batch and its block, start relative to the segment's abs_pos. */
@@ -1039,7 +1040,8 @@ int ts_batch_read_blocks(ts_batch *b, ts_read_block *out, uint64_t cap, uint64_t
  * them.  recs / n are the arrays given to the matching stage / decode call (ts_fastq_chunk_stage, ts_sam_chunk_stage,
  * ts_bam_chunk_decode), `reads` that batch after ts_batch_call_read_blocks (and after ts_batch_read_pass_status said that nothing
  * overflowed).  The lines, in row order, to host_out; *bytes and *n_lines say how much; cap and *bytes behave as for
- * ts_fastq_chunk_gather (*bytes > cap: nothing is copied, TS_ERR_INVALID_ARG).  Ordered on `stream`; waits for it. */
+ * ts_fastq_chunk_gather (*bytes > cap: nothing is copied, TS_ERR_INVALID_ARG).  Ordered on `stream`; waits for it.
+ * (ts_fasta_chunk_block_lines, for FASTA reads, is declared with that front end's stage and gather below.) */
 int ts_fastq_chunk_block_lines(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
                                uint64_t *bytes, uint64_t *n_lines, void *stream);
 int ts_sam_chunk_block_lines(ts_chunk *chunk, const ts_sam_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
@@ -1152,6 +1154,36 @@ int ts_fasta_chunk_join(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, 
 int ts_fasta_chunk_runs(ts_chunk *chunk, ts_fasta_run *runs, uint64_t cap, uint64_t *n_runs);
 /* joined[off, off + n) of the last join to host memory (tests; the match sequences of -m).  Waits for the device. */
 int ts_fasta_chunk_bases(ts_chunk *chunk, uint64_t off, uint64_t n, void *host);
+
+/* ---- FASTA reads in the same resident chunk (include/teloscope_mi355x_io.hpp: fastaSubset, fastaSubsetDevice): the fourth front
+ *      end of the read filter, for reads that come without qualities (corrected reads, seqtk seq -A, samtools fasta, unitigs and
+ *      contigs).  The reference has no such mode (its --fastq-subset answers "FASTQ input must start with '@'"); the rule is this
+ *      project's own, stated here and nowhere else, and every route follows it:
+ *        - Lines, header lines, names and bases are those of the FASTA section above ("header line", "name", "bases"), exactly.
+ *        - An input of 0 bytes is "FASTA input is empty"; a first byte that is not '>' is "FASTA input must start with '>'".
+ *          There is no other input error.
+ *        - A record with 0 bases is never kept and is counted as missing (what samSubset does for SEQ "*").  Every other record
+ *          is judged on its joined bases as one read: the filter folds case, and any byte that is not A, C, G or T matches nothing.
+ *        - A kept record is written verbatim, in input order: every byte from its '>' up to the next record's '>', line ends and
+ *          blank lines as read.  The input's last record gets a '\n' when its last byte is not one.
+ *        - What the read block report names a read of this front end, and its read_len, are stated in that report's section above.
+ *        - Limits are ts_fasta_record's: text_len and n_bases have 32 bits.  The device route refuses a larger record by naming
+ *          the host route. */
+/* ts_fastq_chunk_stage for FASTA reads: the bases of recs[i] (any n entries of the last walk's table with n_bases > 0, walked
+ * with the same at_end) into segment i of `reads`, an unrestricted tips-only batch, tiled or general, of n segments of n_bases
+ * bases on the chunk's context; segment i starts at ts_batch_segment_offset(reads, i), and bytes behind a read stay zero.  A
+ * stream compaction of body text into the batch's layout with ts_fasta_chunk_join's keep rule (one source): body text is cut at
+ * multiples of 16 KB, a record that lies in one piece is read once and written once, the pieces of a larger record are counted
+ * and a segmented exclusive sum per record places them; aligned 16-byte stores.  No runs are searched.  Asynchronous on `stream`. */
+int ts_fasta_chunk_stage(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, int at_end, ts_batch *reads, void *stream);
+/* ts_fastq_chunk_gather for FASTA reads: the records whose pass byte (d_pass[i], device memory) is set, their text_len bytes as
+ * they are and a '\n' behind a text that does not end in one (only the input's last record can), in input order, to host_out;
+ * *bytes, *n_passed and cap as for ts_bam_chunk_gather.  Ordered on `stream`; waits for it. */
+int ts_fasta_chunk_gather(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, const void *d_pass, void *host_out,
+                          uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
+/* ts_fastq_chunk_block_lines for FASTA reads: recs / n are the arrays given to ts_fasta_chunk_stage. */
+int ts_fasta_chunk_block_lines(ts_chunk *chunk, const ts_fasta_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
+                               uint64_t *bytes, uint64_t *n_lines, void *stream);
 
 /* ---- GFA text in the same resident chunk: the device form of the graph front end (include/teloscope_mi355x_gfa.hpp:
  *      annotateGfaDevice).  Replaces the line loop of the reference's GFA load (src/input.cpp:625-716): which lines are S, P

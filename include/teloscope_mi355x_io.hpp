@@ -3113,6 +3113,84 @@ inline AssemblySummary scanFastaToFilesDevice(Teloscope &teloscope, const std::s
     return sum;
 }
 
+namespace detail {
+
+// fastaSubsetDevice's stages: TextChunkSteps with the assembly route's framing (ts_fasta_chunk_walk) and the read routes' judge.
+// The first chunk must begin with '>'; the chunk's last record is unfinished unless the input ends with it, and goes in front of
+// the next chunk.  There is no record that is not valid.  The stage reads a '\r' at the chunk's end by the walk's at_end, so a
+// worker remembers it.
+struct FastaReadWorker : RecordWorker<ts_fasta_record> {
+    ChunkFeed::Fill fill;                                       // a dealt chunk's new bytes
+    std::vector<char> names;                                    // the walk's header lines: the call's room for them, not read here
+    bool atEnd = false;
+};
+class FastaReadChunkSteps : public TextChunkSteps<FastaReadChunkSteps, FastaReadWorker> {
+public:
+    using Worker = FastaReadWorker;
+    FastaSubsetStats result;
+
+    FastaReadChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
+        : TextChunkSteps(filter, feed, out, readsPerBatch, chunkBytes, blocks, "failed while writing FASTA subset") {}
+
+    // the chunk's turn to write: what it kept (nothing, where it came in place) and its totals
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        emitKept(k);
+        result.blockLines += k.blockLines;
+        result.totalRecords += k.n; result.passedRecords += k.passed; result.missingSequenceRecords += k.n - k.withBases;
+    }
+
+    // the format's part of the shared steps
+    static uint64_t bases(const ts_fasta_record &r) { return r.n_bases; }          // (none: never kept)
+    static constexpr const char *stageFailed = "staging the sequences failed";
+    int stageReads(Worker &k, ts_batch *batch) { return ts_fasta_chunk_stage(k.chunk, k.withSeq.data(), k.withSeq.size(), k.atEnd ? 1 : 0, batch, nullptr); }
+    int gatherKept(Worker &k, void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+        return ts_fasta_chunk_gather(k.chunk, k.withSeq.data(), k.withSeq.size(), dPass, dst, cap, bytes, nPassed, nullptr);
+    }
+    int blockLines(Worker &k, ts_batch *batch, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *lines) {
+        return ts_fasta_chunk_block_lines(k.chunk, k.withSeq.data(), k.withSeq.size(), batch, dst, cap, bytes, lines, nullptr);
+    }
+    bool frameChunk(Worker &k, bool atEnd) {
+        k.n = 0; k.atEnd = atEnd;
+        const uint64_t size = ts_bam_chunk_size(k.chunk);
+        if (first_) {
+            if (size == 0) {
+                if (atEnd) throw std::runtime_error("FASTA input is empty");
+                return true;
+            }
+            unsigned char c = 0;
+            if (ts_bam_chunk_read(k.chunk, 0, 1, &c) != TS_OK) throw deviceError(k.ctx, "cannot read the chunk");
+            if (c != '>') throw std::runtime_error("FASTA input must start with '>'");
+            first_ = false;
+        }
+        // (ts_fasta_record counts a record's text and bases in 32 bits, and the walk takes a chunk below 4 GiB: a chunk reaches
+        // that size only by growing around one record)
+        if (size >= 0xffffffffull)
+            throw std::runtime_error("fastaSubsetDevice: a record of 4 GiB or more of FASTA text does not fit the device route; the host route (fastaSubset) takes it");
+        const Clock::time_point t0 = Clock::now();
+        if (k.names.empty()) k.names.resize(static_cast<size_t>(size / 16 + 64));  // (reads: names are a few percent of the text; the walk says when it needs more)
+        walkFastaChunk(k.ctx, k.chunk, atEnd, k.recs, k.names, k.n, prevNext_);
+        k.st.msWalk += since(t0);
+        return true;
+    }
+};
+}  // namespace detail
+// The device route of the FASTA read subset (same arguments, result, exceptions and output bytes as fastaSubset): the FASTA text
+// exists in HBM one chunk of ~chunkBytes bytes at a time and the host reads none of it but its first byte.  The text gets there
+// through detail::ChunkFeed as for fastqSubsetDevice (a plain file, BGZF members inflated on the device, a stream through zlib or
+// read(2), plain gzip on the device under TS_GZIP_DEVICE=1; `-` is stdin); behind the source the records are framed as the
+// assembly route frames them (ts_fasta_chunk_walk: the table comes back), their body lines joined straight into a tips-only
+// batch's input buffer (ts_fasta_chunk_stage), judged, and the passing records gathered as they were read (detail::ReadJudge with
+// ts_fasta_chunk_gather).  A record larger than a chunk makes the chunk grow; one of 4 GiB or more is refused by naming the host
+// route.  A filter of one context takes every chunk in place; on several the ring deals the chunks to all of them.  perDevice,
+// where given, receives one entry per context.
+inline FastaSubsetStats fastaSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                          size_t readsPerBatch = 1u << 20, size_t chunkBytes = 256u << 20, std::ostream *blocks = nullptr,
+                                          std::vector<ReadRouteDeviceStats> *perDevice = nullptr) {
+    return detail::textSubsetDeviceRun<detail::FastaReadChunkSteps>("FASTA", "fastaSubsetDevice", inFile, out, filter, readsPerBatch,
+                                                                    std::min<size_t>(chunkBytes, size_t(1) << 31), perDevice, blocks);
+}
+
 }  // namespace teloscope_mi355x
 
 #endif

@@ -1,5 +1,5 @@
-// teloscope_mi355x_reads_host.hpp — the host routes of the three read subsets, fastqSubset, bamSubset / bamSubsetFastq and
-// samSubset / samSubsetFastq: the defaults of the product and what every device read route is compared with.  A route opens its
+// teloscope_mi355x_reads_host.hpp — the host routes of the four read subsets, fastqSubset, bamSubset / bamSubsetFastq,
+// samSubset / samSubsetFastq and fastaSubset: the defaults of the product and what every device read route is compared with.  A route opens its
 // input (detail::MappedInput), reads it a block at a time with the next block filled behind it (detail::BlockReader), finds the
 // records of a block by its format's rule, and hands them in batches to one judge-and-echo step (detail::HostReadJudge).  The
 // route bodies are templates over the judge — anything with matchesPointers(seqs, lens, n, pass) and context(i) — so that all
@@ -1082,6 +1082,132 @@ inline SamSubsetStats samSubset(const std::string &inFile, std::ostream &out, Re
 inline SamSubsetStats samSubsetFastq(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, const ReadFastqOutput &fastq = ReadFastqOutput(),
                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
     return detail::samSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks, &fastq);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The FASTA read subset: the read filter over reads that come as FASTA text (corrected reads, seqtk seq -A, samtools fasta,
+// unitigs and contigs), which the reference has no mode for.  The rule — framing, the two input errors, records without bases,
+// what is written, the block report's name — is stated once in include/teloscan.h above ts_fasta_chunk_stage; the host route
+// below and the device route (fastaSubsetDevice) follow it, and their output bytes, statistics and exception texts are the same.
+struct FastaSubsetStats { uint64_t totalRecords = 0, passedRecords = 0, missingSequenceRecords = 0, blockLines = 0; };   // blockLines: of the read block report
+
+namespace detail {
+// The host form of ts_fasta_chunk_walk, with its meanings and without its 32-bit limits: text[0, size) starts at a line's first
+// byte; the complete records in order and the carry (`next`: the unfinished record's '>'; without a header line the unfinished
+// last line).  Bytes in front of the first header line belong to no record.
+struct FastaReadRecord { uint64_t off, textLen, bodyAt, nBases, nameLen; };     // ts_fasta_record's fields; nameLen: the header line behind '>', without its end
+struct FastaReadWalk {
+    std::vector<FastaReadRecord> recs;
+    uint64_t next = 0;
+};
+inline void fastaWalkHost(const char *text, size_t size, bool atEnd, FastaReadWalk &w) {
+    w.recs.clear();
+    const char *p = text, *const end = text + size;
+    while (p < end) {
+        const char *nl = static_cast<const char *>(std::memchr(p, '\n', static_cast<size_t>(end - p)));
+        if (!nl && !atEnd) break;                               // the unfinished last line
+        const char *lineEnd = nl ? nl : end, *next = nl ? nl + 1 : end;
+        // (a '\r' in front of the '\n'; without one the line ends the input, and the '\r' is its very last byte)
+        const char *e = lineEnd > p && lineEnd[-1] == '\r' ? lineEnd - 1 : lineEnd;
+        if (*p == '>') {
+            if (!w.recs.empty()) w.recs.back().textLen = static_cast<uint64_t>(p - text) - w.recs.back().off;
+            w.recs.push_back(FastaReadRecord{static_cast<uint64_t>(p - text), 0, static_cast<uint64_t>(next - p), 0, static_cast<uint64_t>(e - p) - 1});
+        } else if (!w.recs.empty()) {
+            w.recs.back().nBases += static_cast<uint64_t>(e - p);
+        }
+        p = next;
+    }
+    w.next = atEnd ? size : static_cast<uint64_t>(p - text);
+    if (w.recs.empty()) return;
+    if (atEnd) { w.recs.back().textLen = size - w.recs.back().off; return; }
+    w.next = w.recs.back().off;                                 // the last record is open: the next block may continue it
+    w.recs.pop_back();
+}
+// a complete record's bases to dst (room for nBases): its body lines without '\n' and the '\r' the walk left out
+inline char *fastaReadBases(const char *p, const char *end, char *dst) {
+    while (p < end) {
+        const char *nl = static_cast<const char *>(std::memchr(p, '\n', static_cast<size_t>(end - p)));
+        const char *stop = nl ? nl : end;
+        const size_t n = static_cast<size_t>((stop > p && stop[-1] == '\r' ? stop - 1 : stop) - p);
+        std::memcpy(dst, p, n);
+        dst += n;
+        p = nl ? nl + 1 : end;
+    }
+    return dst;
+}
+
+// (the route itself)  Shaped like samSubsetHost: a block at a time with the next one read behind it, the block's last record
+// carried unless the input ends with it, a block without a complete record grown; per sub-batch the records' bases are joined
+// into one buffer, judged, and the kept records echoed as they were read.
+template <typename Filter>
+inline FastaSubsetStats fastaSubsetHost(const std::string &inFile, std::ostream &out, Filter &filter, size_t readsPerBatch, size_t bytesPerBatch,
+                                        std::ostream *blocks) {
+    HostReadJudge<Filter> judge(filter, blocks, "failed while writing the FASTA subset's block report");
+    MappedInput in(inFile, true, "Stream not successful: " + inFile, false);
+    in.openZlib(true, "Stream not successful: " + inFile);
+    const size_t blockBytes = std::max<size_t>(bytesPerBatch, 64);
+    BlockReader reader([&](char *dst, size_t cap, bool &last) { return in.fill(dst, cap, last, "read error in FASTA input"); }, blockBytes,
+                       std::min<size_t>(blockBytes, 1u << 20));
+    readsPerBatch = std::max<size_t>(readsPerBatch, 1);
+
+    FastaSubsetStats stats;
+    std::string text, bases;
+    std::vector<size_t> at;                                     // where each record's bases begin in `bases`
+    auto write = [&](const char *p, size_t n) {
+        out.write(p, static_cast<std::streamsize>(n));
+        if (!out.good()) throw std::runtime_error("failed while writing FASTA subset");
+    };
+    FastaReadWalk walk;
+    size_t left = 0;
+    for (bool first = true, last = false; !last;) {
+        const BlockReader::Block b = reader.next(left);         // (the unfinished record of the block before in front of it)
+        last = b.last;
+        const size_t size = static_cast<size_t>(b.end - b.begin);
+        if (first && size) {
+            if (*b.begin != '>') throw std::runtime_error("FASTA input must start with '>'");
+            first = false;
+        }
+        if (first && last) throw std::runtime_error("FASTA input is empty");
+        fastaWalkHost(b.begin, size, last, walk);
+        stats.totalRecords += walk.recs.size();
+        for (size_t a = 0; a < walk.recs.size(); a += readsPerBatch) {
+            const size_t n = std::min(readsPerBatch, walk.recs.size() - a);
+            // the sub-batch's bases, one read behind the other
+            at.assign(n + 1, 0);
+            for (size_t i = 0; i < n; ++i) at[i + 1] = at[i] + static_cast<size_t>(walk.recs[a + i].nBases);
+            bases.resize(at[n]);
+            for (size_t i = 0; i < n; ++i) {
+                const FastaReadRecord &r = walk.recs[a + i];
+                if (r.nBases) fastaReadBases(b.begin + r.off + r.bodyAt, b.begin + r.off + r.textLen, &bases[at[i]]);
+            }
+            text.clear();
+            stats.passedRecords += judge.run(n,
+                [&](size_t i, const char *&seq, uint64_t &len) {
+                    if (walk.recs[a + i].nBases == 0) { ++stats.missingSequenceRecords; return false; }     // (no bases: never kept)
+                    seq = bases.data() + at[i]; len = walk.recs[a + i].nBases;
+                    return true;
+                },
+                [&](size_t i, const char *seq, uint64_t len) {
+                    const FastaReadRecord &r = walk.recs[a + i];
+                    text.append(b.begin + r.off, static_cast<size_t>(r.textLen));
+                    if (text.back() != '\n') text.push_back('\n');              // (only the input's last record can lack it)
+                    if (judge.report.on())
+                        judge.report.add(b.begin + r.off + 1, tsrb::fasta_name_len(ReadBlockReport::Bytes{b.begin + r.off}, 0, static_cast<uint32_t>(r.nameLen)), seq, len);
+                },
+                [&]() { write(text.data(), text.size()); });
+            stats.blockLines = judge.report.lines;
+        }
+        left = size - static_cast<size_t>(walk.next);
+    }
+    out.flush();
+    return stats;
+}
+}  // namespace detail
+// The host route: records are framed on the host, a block of input at a time, their body lines joined and judged in batches of up
+// to readsPerBatch through the filter.  Input may be plain or gzip (both through zlib); `-` is stdin.
+inline FastaSubsetStats fastaSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                    size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 256u << 20, std::ostream *blocks = nullptr) {
+    return detail::fastaSubsetHost(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks);
 }
 
 }  // namespace teloscope_mi355x

@@ -296,6 +296,7 @@ SYMBOLS = [
     "ts_batch_call_read_blocks", "ts_batch_read_blocks", "ts_fastq_chunk_block_lines", "ts_sam_chunk_block_lines",
     "ts_bam_chunk_block_lines", "ts_read_block_lines_format", "ts_read_block_text_stats",
     "ts_bam_chunk_gather_fastq", "ts_sam_chunk_gather_fastq", "ts_read_fastq_text_stats",
+    "ts_fasta_chunk_stage", "ts_fasta_chunk_gather", "ts_fasta_chunk_block_lines",
 ]
 
 
@@ -539,8 +540,11 @@ def lib():
     L.ts_match_text_stats.restype = C.c_int
     L.ts_batch_call_read_blocks.argtypes = [C.c_void_p, C.c_void_p]
     L.ts_batch_read_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.ts_fasta_chunk_stage.argtypes = [C.c_void_p, C.POINTER(FastaRecord), C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    L.ts_fasta_chunk_gather.argtypes = [C.c_void_p, C.POINTER(FastaRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     for name, rec in (("ts_fastq_chunk_block_lines", FastqRecord), ("ts_sam_chunk_block_lines", SamRecord),
-                      ("ts_bam_chunk_block_lines", BamRecord)):
+                      ("ts_bam_chunk_block_lines", BamRecord), ("ts_fasta_chunk_block_lines", FastaRecord)):
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(rec), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
     L.ts_read_block_lines_format.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,

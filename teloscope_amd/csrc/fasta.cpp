@@ -1,9 +1,10 @@
 // fasta.cpp — host side of the device FASTA stages (include/teloscan.h: ts_fasta_chunk_*): argument checks, buffer sizes, the
-// job lists of the join and the run search (a job per 16 KB of a record: arithmetic on the record table), launches and the few
-// words that come back.  The chunk and its line index are the chunk layer's (chunk_internal.h); nothing here parses a byte of
-// text.
+// job lists of the join, the read stage and the run search (a job per 16 KB of a record: arithmetic on the record table), launches
+// and the few words that come back.  The read route's gather is the FASTQ route's kernel and chunk.hip's plan over the records'
+// spans.  The chunk and its line index are the chunk layer's (chunk_internal.h); nothing here parses a byte of text.
 #include "chunk_internal.h"
 #include "fasta_internal.h"
+#include "fastq_internal.h"
 
 namespace {
 
@@ -168,6 +169,80 @@ int ts_fasta_chunk_join(ts_chunk *ch, const ts_fasta_record *recs, size_t n, int
     ch->fasta.runs = runs;
     *n_runs = runs;
     return TS_OK;
+}
+
+int ts_fasta_chunk_stage(ts_chunk *ch, const ts_fasta_record *recs, size_t n, int at_end, ts_batch *reads, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!reads || (n && !recs) || reads->ctx != ctx || !reads->tips || !reads->whole() || reads->segs.size() != n)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_stage: needs an unrestricted tips-only batch of this context with one segment per record");
+    if (ch->plain_n >= 0xffffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_stage: the chunk holds 4 GiB or more");
+    // the jobs: a record's body text cut at multiples of 16 KB, as the join cuts it, with the record's segment as its place; the
+    // records of two jobs or more, whose jobs are counted and summed
+    std::vector<FastaJoinJob> jobs;
+    std::vector<FastaStageSpan> spans;
+    for (size_t i = 0; i < n; ++i) {
+        const ts_fasta_record &r = recs[i];
+        if (!record_ok(ch, r) || r.n_bases == 0 || reads->segs[i].len != r.n_bases)
+            return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_stage: record " + std::to_string(i) + " does not fit the chunk or its segment");
+        const uint64_t dst = ts_batch_segment_offset(reads, i), z = r.off + r.text_len, first = jobs.size();
+        for (uint64_t p = r.off + r.body_at; p < z;) {
+            const uint64_t q = std::min<uint64_t>(z, (p / kFastaSliceBytes + 1) * kFastaSliceBytes);
+            jobs.push_back(FastaJoinJob{(uint32_t)p, (uint32_t)q, (uint32_t)first, 0u, dst, dst + r.n_bases});
+            p = q;
+        }
+        jobs.back().last = 1u;                                  // (n_bases > 0: the record has a job) it zeroes the bytes behind the read
+        if (jobs.size() - first > 1) spans.push_back(FastaStageSpan{(uint32_t)first, (uint32_t)(jobs.size() - first)});
+        if (jobs.size() > 0x7fffffffull) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_stage: too many bases for one call");
+    }
+    DEVICE_TRY(ctx);
+    const bool fresh = reads->d_in.p == nullptr;
+    void *in = ts_batch_input_ptr(reads);
+    if (!in) return ctx->fail(TS_ERR_ALLOC, "ts_fasta_chunk_stage: no input buffer");
+    if (jobs.empty()) return TS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // (a fresh input buffer was just zeroed on the null stream, which a non-blocking `stream` does not wait for)
+    if (fresh && st) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+    const size_t job_bytes = jobs.size() * sizeof(FastaJoinJob);
+    HIP_TRY(ctx, ch->fasta.d_jobs.ensure(job_bytes + std::max<size_t>(1, spans.size()) * sizeof(FastaStageSpan)));
+    HIP_TRY(ctx, ch->fasta.d_counts.ensure(jobs.size() * 4));
+    void *d_spans = (char *)ch->fasta.d_jobs.p + job_bytes;
+    HIP_TRY(ctx, hipMemcpyAsync(ch->fasta.d_jobs.p, jobs.data(), job_bytes, hipMemcpyHostToDevice, st));
+    if (!spans.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_spans, spans.data(), spans.size() * sizeof(FastaStageSpan), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                    // (the lists are this call's memory)
+    if (ts_k_launch_fasta_stage(ch->d_plain.p, ch->plain_n, at_end ? 1 : 0, ch->fasta.d_jobs.p, (uint32_t)jobs.size(), d_spans, (uint32_t)spans.size(),
+                                (uint32_t *)ch->fasta.d_counts.p, in, stream) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_fasta_chunk_stage: kernel launch failed");
+    return TS_OK;
+}
+
+int ts_fasta_chunk_gather(ts_chunk *ch, const ts_fasta_record *recs, size_t n, const void *d_pass, void *host_out, uint64_t cap,
+                          uint64_t *bytes, uint64_t *n_passed, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!bytes || !n_passed || (n && (!recs || !d_pass)) || (cap && !host_out) || n > 0x7fffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_gather: null or out-of-range argument");
+    // a record's text ends with the '\n' in front of the next record's '>'; only the text that ends the chunk may lack it
+    bool final_lf = true, looked = false;
+    for (size_t i = 0; i < n; ++i) {
+        if (!record_ok(ch, recs[i]) || recs[i].text_len == 0)
+            return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_gather: record " + std::to_string(i) + " does not fit the chunk");
+        if (recs[i].off + recs[i].text_len == ch->plain_n && !looked) {
+            unsigned char c = 0;
+            looked = true;
+            DEVICE_TRY(ctx);
+            HIP_TRY(ctx, hipMemcpy(&c, (const char *)ch->d_plain.p + ch->plain_n - 1, 1, hipMemcpyDeviceToHost));
+            final_lf = c == '\n';
+        }
+    }
+    // the span gather of the FASTQ and SAM routes: `size` bytes from `off` and a '\n' behind them
+    std::vector<ts_fastq_record> spans(n);
+    for (size_t i = 0; i < n; ++i) {
+        const bool ends_chunk = recs[i].off + recs[i].text_len == ch->plain_n;
+        spans[i] = ts_fastq_record{recs[i].off, 0u, 0u, recs[i].text_len - (ends_chunk && !final_lf ? 0u : 1u), 0u};
+    }
+    return ts_chunk_gather(ch, "ts_fasta_chunk_gather", spans.data(), sizeof(ts_fastq_record), n, d_pass, host_out, cap, bytes, n_passed, stream,
+                           ts_k_launch_chunk_gather_plan_fastq, ts_k_launch_fastq_gather);
 }
 
 int ts_fasta_chunk_strict(ts_chunk *ch, const ts_fasta_record *recs, size_t n, unsigned char *has_sequence, void *stream) {

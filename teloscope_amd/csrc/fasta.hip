@@ -10,6 +10,9 @@
 //     bytes (not '\n', not a '\r' in front of one or at the input's very end), one wave sums the counts, and the write pass
 //     takes 16 source bytes per lane, places the wave's kept bytes in LDS by a DPP prefix sum of the lanes' counts and stores
 //     aligned 16-byte rows, 1 KB at a time.  Every byte is read once and written once; there are no per-line copies.
+//   * stage: the join's masks and write pass with a read batch's segments as the places (ts_fasta_chunk_stage).  A record inside
+//     one slice is one job and is read once, without a count; the jobs of a record that crosses a slice are counted and summed
+//     per record, a wave per record.
 //   * runs: the same shape over the joined bytes with another predicate: a run starts where "is a gap letter" differs from
 //     the byte before, or where a record starts.
 //   * strict: the filtered loader's one question about a body (does it hold a byte that is no line end?), the count pass's
@@ -144,18 +147,22 @@ __device__ __forceinline__ uint32_t keep_mask16(const unsigned char *plain, unsi
     return ~drop & bit_range(lo, hi);
 }
 
-__global__ __launch_bounds__(64)
-void ts_fasta_join_count_kernel(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob *jobs,
-                                uint32_t n_jobs, uint32_t *counts) {
-    if (blockIdx.x >= n_jobs) return;
-    const FastaJoinJob job = jobs[blockIdx.x];
+// the kept bytes of a job's body text (the wave's total, in every lane)
+__device__ __forceinline__ uint32_t job_kept(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob &job) {
     const unsigned long long a = job.a, z = job.z < size ? job.z : size;
     uint32_t c = 0;
     for (unsigned long long p0 = a & ~15ull; p0 < z; p0 += 1024ull) {
         uint4 q;
         c += __popc(keep_mask16(plain, p0 + threadIdx.x * 16u, a, z, size, at_end, q));
     }
-    c = wave_total(c);
+    return wave_total(c);
+}
+
+__global__ __launch_bounds__(64)
+void ts_fasta_join_count_kernel(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob *jobs,
+                                uint32_t n_jobs, uint32_t *counts) {
+    if (blockIdx.x >= n_jobs) return;
+    const uint32_t c = job_kept(plain, size, at_end, jobs[blockIdx.x]);
     if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
@@ -170,15 +177,12 @@ __device__ __forceinline__ void flush_rows(const unsigned char *buf, unsigned ch
     for (uint32_t k = s; k < b1; ++k) if (base + k < limit) out[base + k] = buf[k];
 }
 
-__global__ __launch_bounds__(64)
-void ts_fasta_join_write_kernel(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob *jobs,
-                                uint32_t n_jobs, const uint32_t *sums, unsigned char *joined) {
-    __shared__ __attribute__((aligned(16))) unsigned char buf[2048];
-    if (blockIdx.x >= n_jobs) return;
-    const FastaJoinJob job = jobs[blockIdx.x];
+// a job's kept bytes to out + dst and on, through buf (2 048 bytes of LDS, 16-byte aligned): the write pass of the join and of
+// the read stage
+__device__ __forceinline__ void job_write(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob &job,
+                                          unsigned long long dst, unsigned char *out, unsigned char *buf) {
     const unsigned long long a = job.a, z = job.z < size ? job.z : size;
-    const unsigned long long dst = job.dst_rec + (sums[blockIdx.x] - sums[job.first]);
-    uint32_t lo = (uint32_t)(dst & 15ull), fill = lo;          // buf[k] goes to joined[base + k]
+    uint32_t lo = (uint32_t)(dst & 15ull), fill = lo;          // buf[k] goes to out[base + k]
     unsigned long long base = dst - lo;
     for (unsigned long long p0 = a & ~15ull; p0 < z; p0 += 1024ull) {
         uint4 q;
@@ -192,7 +196,7 @@ void ts_fasta_join_write_kernel(const unsigned char *plain, unsigned long long s
         fill += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         __syncthreads();
         if (fill >= 1024u) {                                    // (wave-uniform)
-            flush_rows(buf, joined, base, lo, 1024u, job.limit);
+            flush_rows(buf, out, base, lo, 1024u, job.limit);
             const uint4 rest = *(const uint4 *)(buf + 1024u + threadIdx.x * 16u);
             __syncthreads();
             *(uint4 *)(buf + threadIdx.x * 16u) = rest;
@@ -200,9 +204,56 @@ void ts_fasta_join_write_kernel(const unsigned char *plain, unsigned long long s
             base += 1024ull; fill -= 1024u; lo = 0u;
         }
     }
-    flush_rows(buf, joined, base, lo, fill, job.limit);
+    flush_rows(buf, out, base, lo, fill, job.limit);
     // the bytes between this record and the next one's 16-byte aligned start are zero, whatever the buffer held before
-    if (job.last && threadIdx.x < (uint32_t)(-job.limit & 15ull)) joined[job.limit + threadIdx.x] = 0;
+    if (job.last && threadIdx.x < (uint32_t)(-job.limit & 15ull)) out[job.limit + threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(64)
+void ts_fasta_join_write_kernel(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob *jobs,
+                                uint32_t n_jobs, const uint32_t *sums, unsigned char *joined) {
+    __shared__ __attribute__((aligned(16))) unsigned char buf[2048];
+    if (blockIdx.x >= n_jobs) return;
+    const FastaJoinJob job = jobs[blockIdx.x];
+    job_write(plain, size, at_end, job, job.dst_rec + (sums[blockIdx.x] - sums[job.first]), joined, buf);
+}
+
+// ---- stage (ts_fasta_chunk_stage): the join's jobs with a read batch's segments as their places.  Reads are many and short: a
+// record that lies inside one slice is one job, needs no count and no sum, and its text is read once; only the jobs of a record
+// that crosses a slice are counted, and their sums are taken per record, a wave each, not over the whole list.
+__global__ __launch_bounds__(64)
+void ts_fasta_stage_count_kernel(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob *jobs,
+                                 uint32_t n_jobs, uint32_t *counts) {
+    if (blockIdx.x >= n_jobs) return;
+    const FastaJoinJob job = jobs[blockIdx.x];
+    if (job.first == blockIdx.x && job.last) return;           // (the record's only job: it goes to the segment's start)
+    const uint32_t c = job_kept(plain, size, at_end, job);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// a wave per record of several jobs: its jobs' counts -> the counts before each, in place (64 jobs per step)
+__global__ __launch_bounds__(64)
+void ts_fasta_stage_scan_kernel(const FastaStageSpan *spans, uint32_t n_spans, uint32_t *counts) {
+    if (blockIdx.x >= n_spans) return;
+    const FastaStageSpan s = spans[blockIdx.x];
+    uint32_t before = 0;
+    for (uint32_t b = 0; b < s.n; b += 64u) {
+        const uint32_t i = b + threadIdx.x;
+        const uint32_t c = i < s.n ? counts[s.first + i] : 0u;
+        const uint32_t incl = wave_scan_add(c);
+        if (i < s.n) counts[s.first + i] = before + incl - c;
+        before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+}
+
+__global__ __launch_bounds__(64)
+void ts_fasta_stage_write_kernel(const unsigned char *plain, unsigned long long size, int at_end, const FastaJoinJob *jobs,
+                                 uint32_t n_jobs, const uint32_t *sums, unsigned char *in) {
+    __shared__ __attribute__((aligned(16))) unsigned char buf[2048];
+    if (blockIdx.x >= n_jobs) return;
+    const FastaJoinJob job = jobs[blockIdx.x];
+    const uint32_t before = job.first == blockIdx.x ? 0u : sums[blockIdx.x];
+    job_write(plain, size, at_end, job, job.dst_rec + before, in, buf);
 }
 
 // ---- runs
@@ -347,6 +398,20 @@ int ts_k_launch_fasta_join_write(const void *plain, unsigned long long size, int
     if (n_jobs == 0) return 0;
     hipLaunchKernelGGL(ts_fasta_join_write_kernel, dim3(n_jobs), dim3(64), 0, (hipStream_t)stream, (const unsigned char *)plain, size,
                        at_end, (const FastaJoinJob *)jobs, n_jobs, sums, (unsigned char *)joined);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fasta_stage(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
+                            const void *spans, uint32_t n_spans, uint32_t *counts, void *in, void *stream) {
+    if (n_jobs == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_spans) {
+        hipLaunchKernelGGL(ts_fasta_stage_count_kernel, dim3(n_jobs), dim3(64), 0, st, (const unsigned char *)plain, size, at_end,
+                           (const FastaJoinJob *)jobs, n_jobs, counts);
+        hipLaunchKernelGGL(ts_fasta_stage_scan_kernel, dim3(n_spans), dim3(64), 0, st, (const FastaStageSpan *)spans, n_spans, counts);
+    }
+    hipLaunchKernelGGL(ts_fasta_stage_write_kernel, dim3(n_jobs), dim3(64), 0, st, (const unsigned char *)plain, size, at_end,
+                       (const FastaJoinJob *)jobs, n_jobs, counts, (unsigned char *)in);
     return (int)hipGetLastError();
 }
 

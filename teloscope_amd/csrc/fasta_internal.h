@@ -16,6 +16,8 @@ struct FastaHead { uint32_t line, crs_before, names_before, pad; };  // a header
 // dst_rec + (kept bytes of the record's jobs before this one), and never to or beyond limit; the record's last job also
 // zeroes the bytes from limit to the next multiple of 16, where the next record begins
 struct FastaJoinJob { uint32_t a, z, first, last; unsigned long long dst_rec, limit; };
+// the jobs [first, first + n) of the stage's list are one record's, n >= 2: what its segmented sum runs over
+struct FastaStageSpan { uint32_t first, n; };
 // joined bases [a, z) of one record, which begins at rec_begin (a multiple of 16), inside one 16 KB slice of the joined buffer
 struct FastaRunJob { unsigned long long a, z, rec_begin; uint32_t rec, pad; };
 // body text [a, z) of the chunk, a piece of record `rec` of the strict check's table that lies inside one 16 KB slice
@@ -37,6 +39,11 @@ int ts_k_launch_fasta_join_count(const void *plain, unsigned long long size, int
                                  uint32_t *counts, void *stream);
 int ts_k_launch_fasta_join_write(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
                                  const uint32_t *sums, void *joined, void *stream);
+// The read stage: the jobs are the join's, dst_rec / limit a segment of a read batch's input buffer `in`; spans names the records
+// of two jobs or more.  Their jobs are counted into counts[n_jobs], summed per record in place, and every job's kept bytes are
+// written (a record's only job without a count).  Launched on `stream`, not waited for.
+int ts_k_launch_fasta_stage(const void *plain, unsigned long long size, int at_end, const void *jobs, uint32_t n_jobs,
+                            const void *spans, uint32_t n_spans, uint32_t *counts, void *in, void *stream);
 // run starts per run job -> counts[n_jobs]; after the scan, the runs' {record, is_gap, start}; then every run's length
 int ts_k_launch_fasta_run_count(const void *joined, const void *jobs, uint32_t n_jobs, uint32_t *counts, void *stream);
 int ts_k_launch_fasta_run_write(const void *joined, const void *jobs, uint32_t n_jobs, const uint32_t *sums, void *runs,

@@ -36,6 +36,20 @@ TS_THD uint32_t fastq_name_len(const B &bytes, uint64_t off, uint32_t seq_at) {
 }
 TS_THD uint64_t fastq_name_off(uint64_t off) { return off + 1u; }
 
+// FASTA (the read subset): the header line starts at `off` with '>', and line_len bytes of it lie behind the '>' and in front of
+// the line's end (ts_fasta_record's name_len: a '\r' in front of the '\n' is not among them); the name ends at the first space or
+// tab, or with the line.  Its first byte is fastq_name_off's.
+template <class B>
+TS_THD uint32_t fasta_name_len(const B &bytes, uint64_t off, uint32_t line_len) {
+    uint32_t i = 0;
+    while (i < line_len) {
+        const uint32_t c = bytes.byte(off + 1u + i);
+        if (c == ' ' || c == '\t') break;
+        ++i;
+    }
+    return i;
+}
+
 // SAM: the bytes of the alignment line in front of its first tab (a record of the table has ten tabs or more in front of SEQ, so the
 // search ends before seq_at).
 template <class B>

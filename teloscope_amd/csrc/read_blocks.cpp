@@ -1,5 +1,5 @@
 // read_blocks.cpp — host side of the read block report's device formatter (read_blocks.hip): ts_fastq_chunk_block_lines,
-// ts_sam_chunk_block_lines, ts_bam_chunk_block_lines, ts_read_block_lines_format and ts_read_block_text_stats.  The rule of the
+// ts_sam_chunk_block_lines, ts_fasta_chunk_block_lines, ts_bam_chunk_block_lines, ts_read_block_lines_format and ts_read_block_text_stats.  The rule of the
 // report is include/teloscan.h's; its bytes are read_block_format_core.h's.
 //
 // Per call: the rows lie where ts_batch_call_read_blocks left them (or go up), a name entry per segment is made from the chunk's
@@ -8,10 +8,12 @@
 #include "chunk_internal.h"
 #include "read_block_format_core.h"
 
-static_assert(sizeof(TsReadBlockSeg) == 16 && sizeof(ts_fastq_record) == 24 && sizeof(ts_sam_record) == 24 && sizeof(ts_bam_record) == 24, "layouts");
+static_assert(sizeof(TsReadBlockSeg) == 16 && sizeof(ts_fastq_record) == 24 && sizeof(ts_sam_record) == 24 && sizeof(ts_bam_record) == 24 &&
+              sizeof(ts_fasta_record) == 32, "layouts");
 static_assert(offsetof(ts_fastq_record, seq_at) == 8 && offsetof(ts_fastq_record, seq_len) == 12 && offsetof(ts_fastq_record, seq_cr) == 20 &&
               offsetof(ts_sam_record, seq_at) == 8 && offsetof(ts_sam_record, seq_len) == 12 && offsetof(ts_bam_record, block_size) == 8 &&
-              offsetof(ts_bam_record, l_seq) == 16, "read_blocks.hip reads the record tables by these offsets");
+              offsetof(ts_bam_record, l_seq) == 16 && offsetof(ts_fasta_record, n_bases) == 16 && offsetof(ts_fasta_record, name_len) == 24,
+              "read_blocks.hip reads the record tables by these offsets");
 
 namespace {
 
@@ -109,6 +111,23 @@ int ts_sam_chunk_block_lines(ts_chunk *ch, const ts_sam_record *recs, size_t n, 
             return ctx->fail(TS_ERR_UNSUPPORTED, "ts_sam_chunk_block_lines: record " + std::to_string(i) + ": more than 16 MiB (2^24 bytes) in front of SEQ are not formatted on the device");
     }
     return chunk_block_lines(ch, "ts_sam_chunk_block_lines", recs, sizeof *recs, n, TS_READ_BLOCK_SAM, reads, host_out, cap, bytes, n_lines, stream);
+}
+
+int ts_fasta_chunk_block_lines(ts_chunk *ch, const ts_fasta_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,
+                               uint64_t *bytes, uint64_t *n_lines, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!reads || !bytes || !n_lines || (n && !recs) || (cap && !host_out) || n > 0x7fffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_block_lines: null or out-of-range argument");
+    for (size_t i = 0; i < n; ++i) {
+        const ts_fasta_record &r = recs[i];
+        // ('>' and the header line's name_len bytes lie inside the record's text)
+        if (r.off > ch->plain_n || r.text_len > ch->plain_n - r.off || r.name_len >= r.text_len)
+            return ctx->fail(TS_ERR_INVALID_ARG, "ts_fasta_chunk_block_lines: record " + std::to_string(i) + " does not fit the chunk");
+        if (r.name_len > TS_TRACK_MAX_NAME)
+            return ctx->fail(TS_ERR_UNSUPPORTED, "ts_fasta_chunk_block_lines: record " + std::to_string(i) + ": a header line of more than 16 MiB (2^24 bytes) is not formatted on the device");
+    }
+    return chunk_block_lines(ch, "ts_fasta_chunk_block_lines", recs, sizeof *recs, n, TS_READ_BLOCK_FASTA, reads, host_out, cap, bytes, n_lines, stream);
 }
 
 int ts_bam_chunk_block_lines(ts_bam_chunk *ch, const ts_bam_record *recs, size_t n, ts_batch *reads, void *host_out, uint64_t cap,

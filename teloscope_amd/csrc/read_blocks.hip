@@ -32,10 +32,12 @@ __device__ __forceinline__ tsrb::Fields fields_of(const TsReadBlockRow &r, uint3
                         (uint32_t)(unsigned char)r.block_label};
 }
 
-// the record tables' entries, as include/teloscan.h lays them out (ts_fastq_record, ts_sam_record: 24 bytes; ts_bam_record: 24)
+// the record tables' entries, as include/teloscan.h lays them out (ts_fastq_record, ts_sam_record: 24 bytes; ts_bam_record: 24;
+// ts_fasta_record: 32)
 struct RecFastq { u64 off; uint32_t seq_at, seq_len, size, seq_cr; };
 struct RecSam { u64 off; uint32_t seq_at, seq_len, size, flags; };
 struct RecBam { u64 off; uint32_t block_size, seq_at, l_seq, reserved; };
+struct RecFasta { u64 off; uint32_t text_len, body_at, n_bases, name_at, name_len, reserved; };    // (ts_fasta_record: 32 bytes)
 
 __global__ __launch_bounds__(64)
 void ts_read_block_names(const void *recs, uint32_t n, uint32_t kind, const unsigned char *chunk, TsReadBlockSeg *segs) {
@@ -49,6 +51,9 @@ void ts_read_block_names(const void *recs, uint32_t n, uint32_t kind, const unsi
     } else if (kind == TS_READ_BLOCK_SAM) {
         const RecSam r = ((const RecSam *)recs)[i];
         s.name_off = r.off; s.name_len = tsrb::sam_name_len(bytes, r.off, r.seq_at); s.read_len = r.seq_len;
+    } else if (kind == TS_READ_BLOCK_FASTA) {
+        const RecFasta r = ((const RecFasta *)recs)[i];
+        s.name_off = tsrb::fastq_name_off(r.off); s.name_len = tsrb::fasta_name_len(bytes, r.off, r.name_len); s.read_len = r.n_bases;
     } else {
         const RecBam r = ((const RecBam *)recs)[i];
         // (a walked record's name ends inside it; the cut keeps any other table's reads inside the record too)

@@ -483,6 +483,7 @@ struct TsReadBlockTextParams {
 #define TS_READ_BLOCK_FASTQ 0u
 #define TS_READ_BLOCK_SAM   1u
 #define TS_READ_BLOCK_BAM   2u
+#define TS_READ_BLOCK_FASTA 3u
 // segs[i] from entry i of a chunk's record table (ts_fastq_record / ts_sam_record / ts_bam_record by `kind`, device memory)
 int  ts_k_launch_read_block_names(const void *recs, uint32_t n, uint32_t kind, const void *chunk, TsReadBlockSeg *segs, void *stream);
 int  ts_k_launch_read_block_count(const TsReadBlockTextParams *P, uint32_t n_blocks, void *stream);
