@@ -76,13 +76,7 @@ void BufferPool::clear() {
 
 namespace {
 
-constexpr uint32_t kMaxLds = 160u * 1024u;
 constexpr uint64_t kEventRing = 64;            // scans whose HIP-event times a batch remembers
-constexpr uint32_t kMaxBlocksPerTile = 448;
-constexpr uint32_t kMaxChunks = 8;             // tiles up to ~16 k positions per wave
-constexpr uint32_t kTipsChunks = 8;            // tips-only / read batches: ~16 k positions per tile (15 kb reads, TS_GEOMETRY sweeps: six chunks until round 4;
-                                               // eight since the stage's entries are 16 bits — profiles/r05/reads_tilings.txt)
-
 // The measurement / test knobs of the host entry points (ts_ctx::Knobs), from the environment: at ts_create and ts_refresh_env,
 // never per call.
 void read_env_knobs(ts_ctx *c) {
@@ -137,182 +131,30 @@ std::vector<int> device_node_cpus(int dev) {
 // groups of workgroups that share a ticket counter
 constexpr uint32_t kTicketGroups = std::min<uint32_t>(32, TS_MAX_TICKET_GROUPS);
 
-// Chooses waves per workgroup, chunks per tile and windows per tile so that the match table plus
-// one LDS slice per wave fit in 160 KB; false if even one wave cannot hold one window.
-
-bool plan_geometry(const ts_ctx *c, bool tips, TsScanParams &kp, uint32_t &wpt, std::string &why) {
+// What the tiled plan (tiled_plan_core.h) depends on: the context's parameters and tables, and the planner's knobs — read from the
+// environment here, once per plan (tests change TS_GEOMETRY between the batches of one process).
+tsplan::PlanInputs plan_inputs(const ts_ctx *c) {
     const ts_params &P = c->params;
-    const uint32_t k = c->k;
-    kp.k = k;
-    kp.table_rows = c->table_rows;
-    kp.fc_bytes = c->fc_bytes;
-    kp.fc_byte_table = c->fc_byte_table ? 1u : 0u;
-    kp.pair_byte_table = c->pair_byte_table ? 1u : 0u;
-    kp.fold_mask = P.fold_case ? 0xDFDFDFDFu : 0xFFFFFFFFu;
-    kp.emit = 0;                         // (ts_batch_set_emit)
-    kp.kdist = P.max_match_dist;
-    if (tips) {
-        kp.halo_blocks = 0;
-        kp.straddle_fix = 0; kp.windows_on = 0; kp.nuc_on = 0; kp.block_sums = 0; kp.acc_blocks = 0;
-    } else {
-        const uint32_t s = P.step, w = P.window_size;
-        kp.s = s; kp.w = w;
-        kp.s_inv = (65536u + s - 1u) / s;
-        kp.halo_blocks = (w + s - 1) / s - 1;            // window i reaches into step blocks i .. i + ceil(w/s) - 1
-        kp.straddle_fix = (w == s) ? 1u : 0u;
-        kp.windows_on = 1;
-        kp.nuc_on = (P.out_gc || P.out_entropy) ? 1u : 0u;
-        kp.block_sums = (w % s == 0) ? 1u : 0u;
-        kp.acc_blocks = (kp.block_sums && !ts_env_flag("TS_ACC_PER_WINDOW")) ? 1u : 0u;      // (TS_ACC_PER_WINDOW=1: A/B)
-    }
-    // Search (waves per workgroup, chunks per tile) for the best modelled throughput:
-    //   owned bases per tile x occupancy factor / instructions per tile.
-    // Instructions: ~470 per 2016-position chunk (decode, probes, planes, per-match pass: the weights of round 1's kernel), ~170 per
-    // pass of the window loop (64 window fields per pass), ~100 fixed per tile.  Occupancy factors are
-    // measured (profiles/r01/geometry_sweep.txt): against 16 waves per CU the kernel loses 12 % at 12
-    // waves and 31 % at 8; more than 16 is not reachable (two workgroups per CU did not co-reside).
-    // Round 2: built for 80 VGPRs, two workgroups of 10 waves do share a CU (20 waves; each has its own table copy and half of
-    // the LDS, so tiles are shorter): against 16 x 8 chunks, 2 x 10 x 6 chunks measures -3.2 % on configs[1], -1.2 % with the
-    // default flags (-8 % and 0 on another box: see `sparse` below); with k = 7 (a table of 20 KB per copy) only
-    // 5 chunks and a small record stage fit and it loses 37 %.  So: considered only for window scans with byte tables, at least
-    // 6 chunks, a record stage of 256 and all accumulator copies; its factor is what those measurements give under the
-    // instruction model below.  (Read batches: +4 % on one box, -1 % on another, where the predicate kernel that runs beside
-    // the scan finds fewer free registers; they stay on one workgroup.)
-    // What the extra waves hide is the latency chains of the per-match work: the gain needs matches.  On random sequence a
-    // position matches with probability patterns / 4^k: 3 % for configs[1] (-2.7 % at 1 Gb) and for a k = 5 motif with one
-    // mismatch (-3 %); 0.9 % with the default flags and 0.05 % with -x 0 (both +-1 %): those stay on 16 waves
-    // (profiles/r02/planner_check.txt).
-    const bool sparse = (double)c->patterns.size() < 0.015 * (double)(1ull << (2 * k));
-    static const struct { uint32_t waves, wgs; double factor; } kOccupancy[] = {
-        {16, 1, 1.0}, {10, 2, 1.06}, {12, 1, 0.88}, {8, 1, 0.69}, {4, 1, 0.43}, {2, 1, 0.22}, {1, 1, 0.11}};
-    uint32_t nch_min = 1;
-    if (!tips) nch_min = (uint32_t)ceil_div((uint64_t)(1 + kp.halo_blocks) * kp.s + 63, TS_CHUNK);
-    // TS_GEOMETRY="waves,chunks" pins the search to one point (0 = any): a test knob for the contract that the
-    // output does not depend on the tiling ("independent of GPU count and tile size")
-    uint32_t pin_waves = 0, pin_nch = 0;
-    uint32_t pin_stage = 0, pin_wgs = 0;               // (4th field: workgroups per CU, for measurements such as 2 x 12 waves)
-    if (const char *g = getenv("TS_GEOMETRY")) sscanf(g, "%u,%u,%u,%u", &pin_waves, &pin_nch, &pin_stage, &pin_wgs);
-    const uint32_t nch_max = tips ? std::max(kTipsChunks, pin_nch) : std::max(nch_min, std::max(kMaxChunks, pin_nch));
-    double best = 0.0;
-    TsScanParams best_kp{};
-    uint32_t best_wpt = 0;
-    for (const auto &occ : kOccupancy) {
-        if (pin_waves && occ.waves != pin_waves) continue;
-        const uint32_t wgs = (pin_waves && pin_wgs >= 1 && pin_wgs <= 4) ? pin_wgs : occ.wgs;
-        const uint32_t kMaxLds = ::kMaxLds / wgs;
-        for (uint32_t nch = nch_min; nch <= nch_max; ++nch) {
-            if (nch * TS_CHUNK + 64u > 65535u) break;        // the match queue holds 16-bit plane coordinates
-            if (pin_nch && nch != pin_nch) continue;
-            TsScanParams cand = kp;
-            cand.waves_per_wg = occ.waves;
-            cand.wgs_per_cu = wgs;
-            cand.nch = nch;
-            cand.stage_u16 = ((uint64_t)nch * TS_CHUNK + 64u <= (1u << 14) && !ts_env_flag("TS_STAGE_U32")) ? 1u : 0u;      // (position << 2 | flags) in 16 bits: the stage's entries (TS_STAGE_U32=1: A/B)
-            const uint32_t span_max = nch * TS_CHUNK - 63u;
-            uint32_t cwpt;
-            if (tips) {
-                const uint32_t tb = span_max & ~15u;            // one pseudo block per tile
-                cand.s = cand.w = tb;
-                cand.s_inv = (65536u + tb - 1u) / tb;
-                cand.max_windows = 1;
-                cwpt = 1;
-            } else {
-                const uint32_t nblk = span_max / cand.s;
-                cwpt = nblk > cand.halo_blocks ? std::min<uint32_t>(nblk - cand.halo_blocks, kMaxBlocksPerTile) : 0u;
-                cand.max_windows = cwpt;
-            }
-            // staging room for match records: what is left of the CU's LDS, 64 .. 1024 records per wave
-            cand.stage_cap = 128;
-            cand.acc_copies = 4;             // (8 copies measured no better than 4; the LDS goes to the record stage)
-            while (cand.acc_copies > 1 && (uint32_t)ts_k_lds_bytes(&cand) > kMaxLds) cand.acc_copies >>= 1;
-            if (cwpt < 1 || (uint32_t)ts_k_lds_bytes(&cand) > kMaxLds) continue;
-            {
-                const uint32_t spare = (kMaxLds - (uint32_t)ts_k_lds_bytes(&cand)) / occ.waves / (cand.stage_u16 ? 2u : 4u);
-                cand.stage_cap = std::min<uint32_t>(pin_stage ? pin_stage : 1024u, 128u + (spare & ~15u));
-                while ((uint32_t)ts_k_lds_bytes(&cand) > kMaxLds) cand.stage_cap -= 16;
-            }
-            // (the kernels for the 2-bit tables of k >= 7 need 97 VGPRs: built for 80 they spill)
-            if (wgs > 1 && !(kp.pair_byte_table && kp.fc_byte_table)) continue;      // not built: it would spill (kernels.hip: scan_variant)
-            if (wgs > 1 && !pin_waves && (tips || sparse || !(kp.pair_byte_table && kp.fc_byte_table) || nch < 6 || cand.stage_cap < 256 || cand.acc_copies < 4)) continue;
-            const double passes = tips ? 0.0 : (double)ceil_div((uint64_t)cwpt * 4, 64);
-            // fewer accumulator copies serialise the window adds of a pass: 8 chunks with 2 copies measured 2.5 %
-            // slower than 7 chunks with 4 on the headline configuration, where the model alone says 1 % faster
-            const double copies = cand.acc_copies >= 4 ? 1.0 : cand.acc_copies == 2 ? 0.96 : 0.92;
-            // a stage that holds a tile of random sequence whole (its matches at the pattern set's density, + 15 % + most of a pass) lets
-            // the records leave once, at the tile's end; a smaller one flushes from inside the chunk loop, where a store sits in
-            // the memory queue ahead of the chunk loads that are waited for next
-            const double tile_records = (double)c->patterns.size() / (double)(1ull << (2 * std::min<uint32_t>(k, 16))) * (double)cwpt * cand.s;
-            const double whole = (double)cand.stage_cap >= 1.15 * tile_records + 48.0 ? 1.0 : 0.93;
-            const double score = (double)cwpt * cand.s * occ.factor * copies * whole / (470.0 * nch + 170.0 * passes + 100.0);
-            if (score > best) { best = score; best_kp = cand; best_wpt = cwpt; }
-        }
-    }
-    if (best > 0.0) {
-        kp = best_kp; wpt = best_wpt;
-        {   // the exact 22-bit magic of the step, where it exists for every position of a tile (see kernels.hip: the per-match pass)
-            const uint64_t s64 = std::max<uint32_t>(kp.s, 1), magic = ((1ull << 22) + s64 - 1) / s64, err = magic * s64 - (1ull << 22);
-            const uint64_t max_u = (uint64_t)kp.nch * TS_CHUNK + 64u;
-            kp.s_magic22 = (uint32_t)magic;
-            kp.div_exact = (!tips && magic < (1u << 24) && max_u < (1u << 24) && max_u * magic < (1ull << 32) && max_u * err < (1ull << 22)) ? 1u : 0u;
-        }
-        kp.vis_wide = ((uint64_t)kp.nch * TS_CHUNK + 64u <= (1u << 14)) ? 0u : 1u;      // (position << 2 | flags) in 16 bits?
-        return true;
-    }
-    why = "window/step geometry does not fit the 160 KB LDS of a CU";
-    return false;
+    tsplan::PlanInputs in;
+    in.step = P.step; in.window_size = P.window_size;
+    in.terminal_limit = P.terminal_limit; in.max_match_dist = P.max_match_dist;
+    in.fold_case = P.fold_case != 0;
+    in.nuc = P.out_gc || P.out_entropy;
+    in.k = c->k;
+    in.n_patterns = c->patterns.size();
+    for (const ts::Pattern &p : c->patterns) in.n_canonical += p.is_canonical ? 1 : 0;
+    in.table_rows = c->table_rows; in.fc_bytes = c->fc_bytes;
+    in.fc_byte_table = c->fc_byte_table; in.pair_byte_table = c->pair_byte_table;
+    if (const char *g = getenv("TS_GEOMETRY")) sscanf(g, "%u,%u,%u,%u", &in.pin_waves, &in.pin_nch, &in.pin_stage, &in.pin_wgs);
+    in.acc_per_window = ts_env_flag("TS_ACC_PER_WINDOW");
+    in.stage_u32 = ts_env_flag("TS_STAGE_U32");
+    return in;
 }
 
-void add_region_tiles(ts_batch *b, SegPlan &sp, uint32_t seg_index, uint64_t start, uint64_t len,
-                      uint64_t tile_bases, uint64_t windows_per_tile, bool windows) {
-    Region rg{start, len, (uint32_t)b->tiles.size(), 0, tile_bases};
-    const uint64_t nt = ceil_div(len, tile_bases);
-    for (uint64_t j = 0; j < nt; ++j) {
-        TsTile t{};
-        const uint64_t u0 = j * tile_bases;
-        const uint64_t rem = len - u0;
-        t.in_off = sp.in_off + start + u0;
-        t.nrel = (uint32_t)std::min<uint64_t>(rem, 1u << 30);
-        if (windows) {
-            const uint64_t wins_left = sp.n_windows - j * windows_per_tile;
-            t.nwin = (uint32_t)std::min<uint64_t>(wins_left, windows_per_tile);
-            t.win_out = sp.win_base + j * windows_per_tile;
-        } else {
-            t.nwin = 1;
-            t.win_out = 0;
-        }
-        t.own_len = (uint32_t)std::min<uint64_t>(rem, tile_bases);
-        t.seg = seg_index;
-        b->tiles.push_back(t);
-    }
-    rg.n_tiles = (uint32_t)nt;
-    sp.regions.push_back(rg);
-}
-
-// the first tile at or after `t` whose segment differs from tile t's is found by the callers; here: the range
-// [lo, hi) of tiles -> what it covers (window records, bytes of the input layout, owned bases)
-void range_cover(const ts_batch *b, uint64_t lo, uint64_t hi, ts_range_info &r) {
-    r = ts_range_info{};
-    r.tile_begin = lo; r.tile_end = hi;
-    if (lo >= hi) return;
-    const TsTile &first = b->tiles[lo];
-    r.window_begin = b->tips ? 0 : first.win_out;
-    r.window_end = r.window_begin;
-    r.input_begin = first.in_off & ~15ull;
-    uint64_t in_end = 0;
-    for (uint64_t t = lo; t < hi; ++t) {
-        const TsTile &T = b->tiles[t];
-        r.bases += T.own_len;
-        if (!b->tips) r.window_end = std::max<uint64_t>(r.window_end, T.win_out + T.nwin);
-        // what ts_scan_tiles loads for this tile: nch chunks of TS_CHUNK positions from the 16-byte-aligned
-        // address at or below its first base, each lane 32 bytes (the last lane reaches 32 bytes past a chunk)
-        const uint32_t sh = (uint32_t)(T.in_off & 15ull);
-        const uint64_t span = (uint64_t)(T.nwin + b->kp.halo_blocks) * b->kp.s;
-        const uint64_t need = sh + std::min<uint64_t>(T.nrel, span + 16u);
-        uint64_t nch = (need + 16u + TS_CHUNK - 1u) / TS_CHUNK;
-        nch = std::min<uint64_t>(std::max<uint64_t>(nch, 1), b->kp.nch);
-        in_end = std::max<uint64_t>(in_end, (T.in_off - sh) + nch * TS_CHUNK + 64u);
-    }
-    r.input_end = std::min<uint64_t>(in_end, b->input_bytes);
+// TS_VIS_CAP, read whenever a range's launch is sized
+uint64_t vis_cap_override() {
+    if (const char *e = getenv("TS_VIS_CAP")) { const long v = atol(e); if (v > 0) return (uint64_t)v; }
+    return 0;
 }
 
 }  // namespace
@@ -329,29 +171,16 @@ void ts_ctx::bind_this_thread() const {
 }
 
 // The buffers of a batch that emits (ts_batch_set_emit): per-wave regions of visible records, the per-tile chain summaries
-// and, planned here, every tile's terminal-zone word.  Idempotent.
+// and every tile's terminal-zone word as the plan states it (tsplan::zone_words).  Idempotent.
 static int ensure_emit_buffers(ts_batch *b) {
     ts_ctx *c = b->ctx;
     if (!b->kp.emit || b->d_chain.p) return TS_OK;
     const size_t nt = (size_t)b->range_tiles();
-    {
-        HIP_TRY(c, c->pool.take(std::max<uint64_t>((uint64_t)b->vis_cap * b->total_waves, 4) * (b->kp.vis_wide ? 4 : 2) + 16, b->d_vis));
-        HIP_TRY(c, c->pool.take((nt + 1) * 16, b->d_chain));
-        HIP_TRY(c, c->pool.take((nt + 1) * 4, b->d_zone));
-        // terminal zone of a segment (isTerminal, src/teloscope.cpp:451-459): rel <= t || rel >= N - t, the whole of a
-        // segment no longer than t; per tile as two 16-bit thresholds on the tile-relative position
-        std::vector<uint32_t> zone(nt + 1, TS_ZONE_NONE);
-        const uint64_t tl = c->params.terminal_limit;
-        for (size_t i = 0; i < nt; ++i) {
-            const TsTile &T = b->tiles[b->tile_lo + i];
-            const SegPlan &sp = b->segs[T.seg];
-            const uint64_t rel0 = T.in_off - sp.in_off;
-            uint64_t zlo = rel0 <= tl ? tl + 1 - rel0 : 0, zhi = 0;
-            if (sp.len > tl) zhi = sp.len - tl > rel0 ? sp.len - tl - rel0 : 0;
-            zone[i] = (uint32_t)std::min<uint64_t>(zlo, 0xFFFF) | ((uint32_t)std::min<uint64_t>(zhi, 0xFFFF) << 16);
-        }
-        HIP_TRY(c, hipMemcpy(b->d_zone.p, zone.data(), (nt + 1) * 4, hipMemcpyHostToDevice));
-    }
+    HIP_TRY(c, c->pool.take(std::max<uint64_t>((uint64_t)b->vis_cap * b->total_waves, 4) * (b->kp.vis_wide ? 4 : 2) + 16, b->d_vis));
+    HIP_TRY(c, c->pool.take((nt + 1) * 16, b->d_chain));
+    HIP_TRY(c, c->pool.take((nt + 1) * 4, b->d_zone));
+    const std::vector<uint32_t> zone = tsplan::zone_words(*b);
+    HIP_TRY(c, hipMemcpy(b->d_zone.p, zone.data(), (nt + 1) * 4, hipMemcpyHostToDevice));
     return TS_OK;
 }
 
@@ -382,78 +211,6 @@ int ts_batch_ensure_device(ts_batch *b) {
 void ts_batch_release_input(ts_batch *b) {
     if (b && b->d_in.p) b->ctx->pool.give(std::move(b->d_in));
 }
-
-namespace {
-
-// Sizes the launch (one or two persistent workgroups per CU, whose waves take tiles or are dealt them) and the per-wave
-// record regions for the batch's tile range.  Every wave appends to its own region of the match buffer;
-// small ranges get the worst case (every base a match), large ones bases/4 spread evenly, grown on overflow
-// by ts_batch_sync (worst case for wave w = the owned bases of the tiles it is dealt: t = w, w + waves, ...).
-void size_launch(ts_batch *b) {
-    const uint32_t wpw = b->kp.waves_per_wg;
-    const uint64_t nt = b->range_tiles();
-    const int ncu = b->ctx->num_cu > 0 ? b->ctx->num_cu : 256;
-    b->grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ceil_div(nt, wpw), 1), (uint64_t)ncu * std::max<uint32_t>(b->kp.wgs_per_cu, 1));
-    b->total_waves = b->grid * wpw;
-    uint64_t worst = 256;
-    {
-        std::vector<uint64_t> per_wave(b->total_waves, 0);
-        for (uint64_t t = 0; t < nt; ++t) per_wave[t % b->total_waves] += b->tiles[b->tile_lo + t].own_len;
-        for (uint64_t v : per_wave) worst = std::max(worst, v);
-    }
-    const uint64_t want = b->match_cap_request ? b->match_cap_request : b->range_bases / 4 + 4096;
-    uint64_t cap = ceil_div(want, b->total_waves);
-    // Tiles are taken on demand by the waves (see ts_scan_tiles); dealt round-robin to small ranges, whose regions are
-    // sized for the worst case of the tiles a wave is dealt, and to the rescans after an overflow.
-    b->dealt_tiles = b->range_bases <= (64ull << 20) && !b->match_cap_request;
-    if (b->dealt_tiles) cap = worst;
-    cap = std::min<uint64_t>(std::max<uint64_t>(cap, 256), worst);
-    b->region_cap = (uint32_t)((cap + 3) & ~3ull);
-    b->match_cap = (uint64_t)b->region_cap * b->total_waves;
-    // visible records (kp.emit): canonical matches at their density on random sequence, every match of a terminal zone
-    // (a few per cent of its bases; every k-th base inside a telomere), twice the even share per wave, grown on overflow
-    b->vis_cap = 0;
-    if (!b->tips) {
-        const ts_ctx *c = b->ctx;
-        uint64_t zone_bases = 0;
-        const uint64_t tl = c->params.terminal_limit;
-        for (uint64_t t = 0; t < nt; ++t) {
-            const TsTile &T = b->tiles[b->tile_lo + t];
-            const SegPlan &sp = b->segs[T.seg];
-            const uint64_t rel0 = T.in_off - sp.in_off, rel1 = rel0 + T.own_len;
-            if (rel0 <= tl || sp.len <= tl || rel1 > sp.len - tl) zone_bases += T.own_len;
-        }
-        uint64_t ncanon = 0;
-        for (const ts::Pattern &p : c->patterns) ncanon += p.is_canonical ? 1 : 0;
-        const double d_canon = (double)std::max<uint64_t>(ncanon, 1) / (double)(1ull << (2 * std::min<uint32_t>(c->k, 16)));
-        const uint64_t vwant = (uint64_t)((double)b->range_bases * d_canon * 1.5) + zone_bases / 8;
-        // (which wave scans which tile is decided at run time: a wave may take several of the few tiles that lie in a telomere,
-        // where every k-th base is a visible record — room for a dozen of those per wave, so that an overflow, which costs a
-        // rescan with dealt tiles, stays an event for inputs that are telomere through and through)
-        const uint64_t tile_bases = (uint64_t)b->wpt * std::max<uint32_t>(b->kp.s, 1);
-        uint64_t vcap = 2 * ceil_div(vwant, b->total_waves) + 12 * ceil_div(tile_bases, std::max<uint32_t>(c->k, 1)) + 2048;
-        if (b->dealt_tiles && !b->match_cap_request) vcap = worst;          // small ranges: the worst case, like the record regions
-        vcap = std::min<uint64_t>(vcap, std::max<uint64_t>(worst, 256));
-        if (const char *e = getenv("TS_VIS_CAP")) { const long v = atol(e); if (v > 0) vcap = (uint64_t)v; }   // (tests: force the overflow -> regrow -> rescan path)
-        b->vis_cap = (uint32_t)((vcap + 7) & ~7ull);
-    }
-}
-
-void set_range(ts_batch *b, uint64_t lo, uint64_t hi) {
-    ts_range_info r;
-    range_cover(b, lo, hi, r);
-    b->tile_lo = lo; b->tile_hi = hi;
-    b->win_lo = r.window_begin; b->win_hi = r.window_end;
-    b->in_lo = r.input_begin; b->in_hi = r.input_end;
-    b->range_bases = r.bases;
-    if (lo == 0 && hi == b->tiles.size()) {          // the whole plan: every byte of the layout, every window
-        b->in_lo = 0; b->in_hi = b->input_bytes;
-        b->win_lo = 0; b->win_hi = b->n_windows;
-    }
-    size_launch(b);
-}
-
-}  // namespace
 
 // =========================================================================== misc entry points
 extern "C" {
@@ -682,12 +439,11 @@ static ts_ctx *create_impl(const ts_params *params, const ts_pattern *patterns, 
             if (built) {
                 TsScanParams kp{};
                 uint32_t wpt = 0;
-                std::string why;
                 // (windows the tiled kernel does not take — see full_scan_supported — go to the general kernels)
                 const uint32_t s_ = c->params.step, w_ = c->params.window_size, ov = w_ - s_;
                 const bool win_tiled = !read_filter && kmin <= w_ && (ov == 0 || kmin <= std::min(s_, ov)) && w_ <= 32768u;
                 const bool tips = !win_tiled;
-                const bool fits = plan_geometry(c, tips, kp, wpt, why) && kp.waves_per_wg == 16u && (tips || kp.nch >= 5u);
+                const bool fits = tsplan::plan_geometry(plan_inputs(c), tips, kp, wpt) && kp.waves_per_wg == 16u && (tips || kp.nch >= 5u);
                 if (!fits) built = false;
             }
         }
@@ -870,53 +626,28 @@ ts_batch *ts_batch_create(ts_ctx *ctx, const uint64_t *seg_lens, const uint64_t 
 
     ts_batch *b = new ts_batch();
     b->ctx = ctx;
-    b->tips = tips_only != 0;
-    uint32_t wpt = 1;
-    if (!plan_geometry(ctx, b->tips, b->kp, wpt, why)) {
-        ctx->fail(TS_ERR_UNSUPPORTED, "unsupported parameter set: " + why);
+    b->in = plan_inputs(ctx);
+    const bool tips = tips_only != 0;
+    const uint32_t tl = ctx->params.terminal_limit;
+    const tsplan::PlanStatus st = tsplan::plan_batch(*b, tips, seg_lens, abs_pos, n_segs, [=](uint64_t len) { return tsplan::scanned_regions(len, tips, tl); },
+                                                     match_capacity, ctx->num_cu, vis_cap_override());
+    if (st == tsplan::PlanStatus::no_fit) {
+        ctx->fail(TS_ERR_UNSUPPORTED, "unsupported parameter set: window/step geometry does not fit the 160 KB LDS of a CU");
         delete b;
         return nullptr;
     }
-    b->wpt = wpt;
     if (getenv("TS_TIMING"))
         fprintf(stderr, "ts_batch_create: %s scan, k=%u (%s pair table), %u x %u waves per CU, %u chunks and %u windows per tile, LDS %d B per workgroup "
                         "(match queue %u, record stage %u, %u accumulator copies)\n", b->tips ? "tips-only" : "window", ctx->k,
                 ctx->pair_byte_table ? "byte" : "2-bit",
-                b->kp.wgs_per_cu, b->kp.waves_per_wg, b->kp.nch, wpt, ts_k_lds_bytes(&b->kp), (unsigned)TS_LIST, b->kp.stage_cap, b->kp.acc_copies);
-    const uint64_t tile_bases = (uint64_t)wpt * b->kp.s;
-    const uint32_t tl = ctx->params.terminal_limit;
-
-    uint64_t off = 0, wins = 0;
-    b->segs.resize(n_segs);
-    for (size_t i = 0; i < n_segs; ++i) {
-        SegPlan &sp = b->segs[i];
-        sp.len = seg_lens[i];
-        sp.abs_pos = abs_pos ? abs_pos[i] : 0;
-        sp.in_off = off;
-        off += (sp.len + 15) & ~15ull;
-        sp.first_tile = (uint32_t)b->tiles.size();
-        if (!b->tips) {
-            sp.win_base = wins;
-            sp.n_windows = ceil_div(sp.len, ctx->params.step);
-            wins += sp.n_windows;
-        }
-        for (const tsplan::Span &r : tsplan::scanned_regions(sp.len, b->tips, tl))
-            add_region_tiles(b, sp, (uint32_t)i, r.start, r.len, tile_bases, b->tips ? 1 : wpt, !b->tips);
-        sp.n_tiles = (uint32_t)b->tiles.size() - sp.first_tile;
-        b->total_bases += sp.len;
-    }
-    b->input_bytes = off + TS_IN_PAD;
-    b->n_windows = wins;
-    b->match_cap_request = match_capacity;
-    if (b->tiles.size() >= 0x7FFFFFFFull) {
+                b->kp.wgs_per_cu, b->kp.waves_per_wg, b->kp.nch, b->wpt, (int)b->lds_bytes, (unsigned)TS_LIST, b->kp.stage_cap, b->kp.acc_copies);
+    if (st == tsplan::PlanStatus::too_many_tiles) {
         ctx->fail(TS_ERR_UNSUPPORTED, "too many tiles in one batch");
         delete b;
         return nullptr;
     }
-    b->lds_bytes = (uint32_t)ts_k_lds_bytes(&b->kp);
     // records leave as the stage holds them: 16 bits each where tile positions fit 14 bits (TS_REC32=1 / ts_batch_set_record_bits: 32)
     b->kp.rec16 = (b->kp.stage_u16 && ctx->knobs.rec16) ? 1u : 0u;
-    set_range(b, 0, b->tiles.size());
     return b;
 }
 
@@ -960,17 +691,16 @@ int ts_batch_get_tiles(const ts_batch *b, uint64_t first, uint64_t n, ts_tile_in
 int ts_batch_range_info(const ts_batch *b, uint64_t tile_begin, uint64_t tile_end, ts_range_info *out) {
     if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_range_info");
     if (!b || !out || tile_begin > tile_end || tile_end > b->tiles.size()) return TS_ERR_INVALID_ARG;
-    range_cover(b, tile_begin, tile_end, *out);
+    const tsplan::RangeCover r = tsplan::range_cover(*b, tile_begin, tile_end);
+    *out = ts_range_info{tile_begin, tile_end, r.window_begin, r.window_end, r.input_begin, r.input_end, r.bases};
     return TS_OK;
 }
 
 int ts_batch_partition(const ts_batch *b, uint32_t n_parts, uint32_t part, uint64_t *tile_begin, uint64_t *tile_end) {
     if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_partition");
     if (!b || !n_parts || part >= n_parts || !tile_begin || !tile_end) return TS_ERR_INVALID_ARG;
-    // consecutive ranges of equal owned bases (tiles are near-equal work), the boundaries moved — by at most the
-    // terminal zone + context of a segment — so that none falls near a segment's end (shard.cpp)
     std::vector<uint64_t> cut;
-    ts_shard_boundaries(b, n_parts, cut);
+    tsplan::shard_boundaries(*b, n_parts, cut);
     *tile_begin = cut[part];
     *tile_end = cut[part + 1];
     return TS_OK;
@@ -980,7 +710,7 @@ int ts_batch_restrict(ts_batch *b, uint64_t tile_begin, uint64_t tile_end) {
     if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_restrict");
     if (!b || tile_begin > tile_end || tile_end > b->tiles.size()) return TS_ERR_INVALID_ARG;
     if (b->allocated || b->scanned) return b->ctx->fail(TS_ERR_STATE, "ts_batch_restrict after the batch was used on the device");
-    set_range(b, tile_begin, tile_end);
+    tsplan::set_range(*b, tile_begin, tile_end, b->ctx->num_cu, vis_cap_override());
     return TS_OK;
 }
 
@@ -1182,7 +912,7 @@ int ts_batch_sync(ts_batch *b) {
         // dealt round-robin (the counts of one such scan are those of the next)
         b->dealt_tiles = true;
         if (worst > b->region_cap) {
-            b->region_cap = (uint32_t)(((uint64_t)worst + worst / 8 + 64 + 3) & ~3ull);
+            b->region_cap = tsplan::regrown_region_cap(worst);
             b->match_cap = (uint64_t)b->region_cap * b->total_waves;
             if (b->d_matches.bytes < b->match_cap * 4 + 16) {
                 c->pool.give(std::move(b->d_matches));
@@ -1190,7 +920,7 @@ int ts_batch_sync(ts_batch *b) {
             }
         }
         if (worst_vis > b->vis_cap) {
-            b->vis_cap = (uint32_t)(((uint64_t)worst_vis + worst_vis / 8 + 64 + 7) & ~7ull);
+            b->vis_cap = tsplan::regrown_vis_cap(worst_vis);
             const size_t need = (size_t)b->vis_cap * b->total_waves * (b->kp.vis_wide ? 4 : 2) + 16;
             if (b->d_vis.bytes < need) {
                 c->pool.give(std::move(b->d_vis));
@@ -1248,13 +978,7 @@ int ts_batch_export(ts_batch *b, void *d_dense, uint64_t dense_capacity, void *d
 }
 
 int ts_batch_wire16_ok(const ts_batch *b) {
-    if (!b || b->gen) return 0;
-    const ts_ctx *c = b->ctx;
-    // records: (position << 2 | flags) with position < nch * TS_CHUNK + 64 <= 2^14; tile counts <= a tile's bases;
-    // window fields: nucleotide counts <= w, covered bases = k x matches <= k x w
-    const bool records = (uint64_t)b->kp.nch * TS_CHUNK + 64u <= (1u << 14);
-    const bool windows = b->tips || (uint64_t)c->k * c->params.window_size <= 65535u;
-    return records && windows ? 1 : 0;
+    return b && !b->gen && tsplan::wire16_ok(*b) ? 1 : 0;
 }
 
 int ts_wire_widen_u16(ts_ctx *ctx, const void *d_src_u16, void *d_dst_u32, uint64_t n, void *stream) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "host.hpp"
+#include "tiled_plan_core.h"
 #include "ts_internal.h"
 
 // A planning-only context (ts_params.device == TS_DEVICE_NONE) never touches HIP: it plans batches
@@ -208,32 +209,11 @@ struct ts_ctx {
     int fail(int code, const std::string &msg) const { std::lock_guard<std::mutex> g(err_mtx); error = msg; return code; }
 };
 
-struct Region {                     // one scanned interval of a segment
-    uint64_t start, len;            // relative to the segment
-    uint32_t first_tile, n_tiles;
-    uint64_t tile_bases;            // owned bases per tile
-};
-
-struct SegPlan {
-    uint64_t len = 0, abs_pos = 0;
-    uint64_t in_off = 0;            // byte offset in the (whole-batch) input layout
-    uint64_t win_base = 0, n_windows = 0;
-    uint32_t first_tile = 0, n_tiles = 0;
-    std::vector<Region> regions;
-};
-
-// A shard of a plan (shard.cpp): the tiles it owns, the tiles it scans (owned + context), the segments with an owned tile
-struct ShardRange {
-    uint64_t own_lo, own_hi, ext_lo, ext_hi;
-    uint64_t seg_begin, n_segs;
-};
-// ... and the layout of its result message
-struct ShardLayout {
-    uint64_t off_segs, off_windows, off_tilevis, off_visible, off_blocks, bytes;
-    uint64_t visible_capacity;
-    uint32_t block_capacity, window_bytes, visible_bytes, field_bits;
-    uint64_t n_windows;
-};
+// The plan of a tiled batch and of its shards: tiled_plan_core.h
+using tsplan::Region;
+using tsplan::SegPlan;
+using tsplan::ShardRange;
+using tsplan::ShardLayout;
 
 // What a GENERAL TIPS BATCH holds beside the segments and the input layout of a ts_batch (general_batch.cpp): a tips-only batch
 // of a context whose tips scans go to the general kernels.  Its tiles are TsGeneralTile over the regions scanSegment picks,
@@ -269,22 +249,13 @@ struct ReadBlocksState {
     void *stream = nullptr;
 };
 
-// A batch is a PLAN over all its segments (tiles, window records, input layout) plus the device state of
-// the tile range [tile_lo, tile_hi) it executes: the whole plan by default, one rank's shard after
-// ts_batch_restrict, or — on the rank that assembles — results produced elsewhere (ts_batch_adopt).
-struct ts_batch {
+// A batch is a PLAN over all its segments (tsplan::TiledPlan: tiles, window records, input layout, the tile range
+// [tile_lo, tile_hi) it executes and that range's launch sizes) plus the device state of that range: the whole plan by default,
+// one rank's shard after ts_batch_restrict, or — on the rank that assembles — results produced elsewhere (ts_batch_adopt).
+struct ts_batch : tsplan::TiledPlan {
     ts_ctx *ctx = nullptr;
-    bool tips = false;
     std::unique_ptr<TsGeneralBatch> gen;    // non-null: a general tips batch — `tiles` stays empty, only the calls general_batch.cpp serves work
-    std::vector<SegPlan> segs;
-    std::vector<TsTile> tiles;      // the whole plan
-    TsScanParams kp{};
-    uint32_t wpt = 1;               // windows per tile
-    uint32_t grid = 0, lds_bytes = 0;
-    uint64_t total_bases = 0, input_bytes = 0, n_windows = 0, match_cap = 0, match_cap_request = 0;
     uint64_t n_matches = 0;
-    // executed range and what it covers
-    uint64_t tile_lo = 0, tile_hi = 0, win_lo = 0, win_hi = 0, in_lo = 0, in_hi = 0, range_bases = 0;
     bool allocated = false;
     double last_ms = 0.0;
     bool scanned = false, synced = false;
@@ -295,7 +266,6 @@ struct ts_batch {
     // what the scan hands to block calling and to a shard's message (kp.emit): per-wave regions of visible records, the
     // per-tile chain summaries (TsTileChain) and, planned on the host, the terminal-zone word of every tile
     DevBuf d_vis, d_chain, d_zone;
-    uint32_t vis_cap = 0;           // visible records per wave region
     bool emitted = false;           // the latest scan ran the emitting build: tile_stats word 3, d_chain and d_vis describe it
     bool chain_valid() const { return emitted && !dense && d_chain.p != nullptr; }
     // a shard (ts_batch_restrict_shard): the range the batch executes is its OWNED tiles [own_lo, own_hi) plus context tiles
@@ -315,10 +285,8 @@ struct ts_batch {
     // caller-owned result buffers (ts_batch_bind_results / ts_batch_adopt); null = the batch's own
     uint32_t *ext_windows = nullptr, *ext_stats = nullptr;
     const uint32_t *ext_dense = nullptr;
-    uint32_t total_waves = 0, region_cap = 0;
     ReadBlocksState rb;                     // ts_batch_call_read_blocks
     bool all_terminal = false;              // (set with d_readtab) no segment longer than the terminal limit
-    bool dealt_tiles = false;               // tiles dealt round-robin instead of taken on demand (see ts_batch_scan)
     uint64_t ticket_seq = 0;                // launches with on-demand tiles so far: parity = the ticket counter in use
     std::vector<uint32_t> wave_fill;
     std::vector<hipEvent_t> evs;                 // ring of {start, stop} pairs, one per enqueued scan
@@ -334,8 +302,6 @@ struct ts_batch {
     const uint32_t *records_ptr() const { return dense ? (ext_dense ? ext_dense : (const uint32_t *)d_dense.p) : (const uint32_t *)d_matches.p; }
     // records that may be read behind records_ptr(): the per-wave regions, or the dense stream
     unsigned long long records_limit() const { return dense ? n_matches : (unsigned long long)region_cap * total_waves; }
-    uint64_t range_tiles() const { return tile_hi - tile_lo; }
-    bool whole() const { return tile_lo == 0 && tile_hi == tiles.size(); }
 };
 
 #define HIP_TRY(ctx, expr)                                                                   \
@@ -351,11 +317,6 @@ struct ts_batch {
     DeviceGuard _dev_guard((ctx)->device);                                                    \
     if (_dev_guard.error() != hipSuccess)                                                     \
         return (ctx)->fail(TS_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_dev_guard.error()))
-
-inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
-
-// shard.cpp: boundaries of the split of a plan into n_parts consecutive tile ranges (n_parts + 1 values)
-void ts_shard_boundaries(const ts_batch *b, uint32_t n_parts, std::vector<uint64_t> &out);
 
 // pipeline.cpp: per-context pieces of the host pipeline, for multi.cpp
 int  ts_scan_segments_unlocked(ts_ctx *ctx, const ts_segment_in *segs, size_t n_segs, ts_segment_out *out);   // ts_scan_segments for a caller that holds api_mtx
@@ -381,10 +342,6 @@ void ts_parallel_for(size_t n, unsigned max_threads, F &&f) {
         pool.emplace_back([&] { for (size_t i; (i = next.fetch_add(1)) < n;) f(i); });
     for (std::thread &th : pool) th.join();
 }
-
-// isTerminal (src/teloscope.cpp:451-459) of a segment-relative position; term_end = ts_terminal_end(segment length, limit)
-inline uint64_t ts_terminal_end(uint64_t seg_len, uint64_t terminal_limit) { return seg_len > terminal_limit ? seg_len - terminal_limit : 0; }
-inline bool ts_is_terminal(uint64_t rel, uint64_t terminal_limit, uint64_t term_end) { return rel <= terminal_limit || rel >= term_end; }
 
 // Window kwin of a segment from its eight counts {A, C, G, T, canonical, non-canonical, forward, reverse covered}: the float
 // metrics are evaluated on the host from the integer counts, as the reference does

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "scan_lds_core.h"
 #include "ts_device.h"
 #include "ts_internal.h"
 
@@ -230,8 +231,6 @@ __device__ __forceinline__ void window_tile_part(const uint32_t *codes2, const u
 constexpr uint32_t kCodeWords = (kTile + kHalo) / 16u + 4u;          // 2-bit plane, dwords (+ slack: three are read per position)
 constexpr uint32_t kInvalWords = (kTile + kHalo) / 32u + 3u;         // validity plane
 constexpr uint32_t kCumWords = 260;                                  // per-dword nucleotide prefix sums of a tile (256 + the end sentinel)
-
-__host__ __device__ inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
 
 // LDS of ts_general_fused (byte offsets; lp: patterns whose lists are copied in, 0: none):
 //   mask u32[kTile] | pcode u64[lp] | bitmap u32[8][128] | part u32[8] | codes2 | inval | pflag u8[lp]

@@ -13,7 +13,7 @@
 // are dealt round-robin instead where per-wave record counts must be reproducible), and every wave appends its packed
 // match records to its own region of the output (a per-tile directory {offset, count} makes
 // the stream addressable in position order).  Latency is hidden by the 16 waves per CU — or 20, as two workgroups of
-// ten, where the pattern set is dense enough to need them (the WAVES_EU = 6 build below; plan_geometry in capi.cpp decides) —
+// ten, where the pattern set is dense enough to need them (the WAVES_EU = 6 build below; plan_geometry in tiled_plan_core.h decides) —
 // and by wave priorities: the phases that are chains of dependent LDS / memory operations run above the dense per-chunk work.
 //
 // Per tile:
@@ -33,6 +33,7 @@
 
 #include <type_traits>
 
+#include "scan_lds_core.h"
 #include "ts_device.h"
 #include "ts_internal.h"
 
@@ -60,55 +61,6 @@ typedef LDS uint32_t lds_u32;
 // an LDS byte address (the dynamic-LDS base is 0) as a pointer
 __device__ __forceinline__ lds_u16 *lds_at16(uint32_t addr) { return (lds_u16 *)(uintptr_t)addr; }
 __device__ __forceinline__ lds_u8 *lds_at8(uint32_t addr) { return (lds_u8 *)(uintptr_t)addr; }
-
-__host__ __device__ inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
-
-// LDS: [match table][wave 0 queue][wave 1 queue]...[wave 0 slice][wave 1 slice]...; a slice = codes | rec | wacc | stage
-//   codes   2-bit codes of the tile, two dwords per 32 positions (+ one look-ahead dword pair); the per-match pass
-//           reads k-mers from it and the window phase counts the nucleotides of every step block in it
-//   queue   (its own region) ring of TS_LIST u16 plane coordinates of match positions, appended to by every
-//           chunk in position order and consumed 64 at a time, so that the per-match work runs
-//           on full wavefronts
-//   rec     nucleotide counts {A, C, G, T}, 4 x u32 per step block of the tile (windows + halo) when w is a
-//           multiple of s (a window is the sum of w / s rows), else per window
-//   wacc    the match fields of the tile's window records while they accumulate: one u64 per step block (w a multiple of s:
-//           a window's fields are then the sum of its blocks' minus the matches that run over the end of its last block,
-//           which have a row of their own — ONE add per match instead of one per window that contains it) or per window
-//           = four 16-bit counters {canonical, non-canonical, forward, reverse}, bumped by ONE
-//           ds_add_u64 per (match, window); kept in acc_copies lane-interleaved copies so that the
-//           matches of a pass, which mostly fall into the same few windows, do not serialise on one
-//           address
-//   stage   packed match records waiting to leave in whole coalesced rows at the tile's end (kept out of the
-//           chunk loads' counted vmcnt waits), 16 bits each when tile positions allow (P.stage_u16), + one spare slot per lane
-//           for predicated-off writes
-//   park    eight dwords of per-wave state of the emitting build that only the end of a tile touches (finish_records): kept here,
-//           not in scalar registers, so that the chunk loop of the emitting build is the plain build's
-struct SliceLayout { uint32_t codes, rec, wacc, stage, park, bytes; };
-
-__host__ __device__ inline SliceLayout slice_layout(const TsScanParams &P) {
-    SliceLayout s;
-    uint32_t o = 0;
-    s.codes = o; o += align16((P.nch * 63u + 1u) * 8u);
-    s.rec = o; o += (P.windows_on && P.nuc_on) ? align16((P.max_windows + P.halo_blocks) * 16u) : 0u;
-    // (per step block when w is a multiple of s: rows for the tile's windows + halo in every copy, then one row per block for
-    //  the matches that run over their block's end; else per window)
-    s.wacc = o; o += P.windows_on ? align16((P.max_windows + (P.acc_blocks ? P.halo_blocks : 0u)) * 8u * (P.acc_copies + (P.acc_blocks ? 1u : 0u))) : 0u;
-    s.stage = o; o += (P.stage_cap + 64u) * (P.stage_u16 ? 2u : 4u);
-    s.park = o; o += 32u;                                     // (whether or not this batch emits: one geometry)
-    s.bytes = o;
-    return s;
-}
-
-// The match queues of all waves sit together behind the table, each aligned to its own size, so that a
-// queue slot's LDS address is (byte offset & mask) | base: one v_and_or instead of mask, shift and add.
-__host__ __device__ inline uint32_t queue_region(const TsScanParams &P) {
-    const uint32_t a = TS_LIST * 2u;
-    return (P.table_rows * 4u + P.fc_bytes + a - 1u) & ~(a - 1u);
-}
-
-__host__ __device__ inline uint32_t lds_total(const TsScanParams &P) {
-    return queue_region(P) + P.waves_per_wg * (TS_LIST * 2u + slice_layout(P).bytes);
-}
 
 // ---------------------------------------------------------------------------------------
 // Two register budgets.  WAVES_EU = 4: one workgroup of up to 16 waves per CU (4 per SIMD; the allocator takes 81 VGPRs).
@@ -1016,11 +968,6 @@ __global__ void ts_compact_regions(const uint32_t *regions, const uint32_t *wave
     else { const uint32_t *src = regions + (u64)w * region_cap; for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i]; }
 }
 
-}  // namespace
-
-int ts_k_lds_bytes(const TsScanParams *p) { return (int)lds_total(*p); }
-
-namespace {
 // The 80-VGPR build (two workgroups per CU) exists for the byte tables only: the probe path of the 2-bit tables (k >= 7)
 // needs 97 registers and would spill to scratch there, so it is not instantiated and plan_geometry never asks for it.
 template <bool EMIT>
@@ -1047,7 +994,7 @@ int ts_k_prepare(uint32_t lds_bytes) {
                          (const void *)ts_scan_tiles<true, true, 4, true, true>, (const void *)ts_scan_tiles<true, true, 6, true, true>};
     // the limit is a property of the function, not of a launch: batches of different geometries share it, so it is
     // raised to the CU's whole LDS rather than set to the size one batch asked for
-    const int limit = (int)(lds_bytes > 160u * 1024u ? lds_bytes : 160u * 1024u);
+    const int limit = (int)(lds_bytes > TS_CU_LDS_BYTES ? lds_bytes : TS_CU_LDS_BYTES);
     for (const void *fn : fns) {
         int e = (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
         if (e) return e;

@@ -32,73 +32,6 @@
 
 namespace {
 
-uint32_t bit_width_u32(uint32_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b ? b : 1u; }
-
-struct ShardGeom { uint64_t tile_bases; uint32_t ctx, zone, margin; };
-
-// context tiles: enough that a record beyond them cannot chain (gap <= -k) to one in an owned tile across an empty
-// context, and at least two; zone tiles: those holding positions [0, terminal_limit]
-ShardGeom shard_geom(const ts_batch *b) {
-    ShardGeom g{};
-    const ts_params &P = b->ctx->params;
-    g.tile_bases = std::max<uint64_t>((uint64_t)b->wpt * b->kp.s, 1);
-    if (b->tips) { g.ctx = 0; g.zone = 0; g.margin = 0; return g; }
-    g.ctx = (uint32_t)std::max<uint64_t>(2, ceil_div((uint64_t)P.max_match_dist + b->ctx->k + 1, g.tile_bases) + 1);
-    g.zone = (uint32_t)std::min<uint64_t>(ceil_div((uint64_t)P.terminal_limit + 1, g.tile_bases), 0x3FFFFFFFull);
-    g.margin = g.zone + g.ctx;
-    return g;
-}
-
-// Boundaries of the split into n_parts: part p owns tiles [out[p], out[p + 1]).
-void shard_boundaries(const ts_batch *b, uint32_t n_parts, std::vector<uint64_t> &out) {
-    const ShardGeom g = shard_geom(b);
-    const uint64_t nt = b->tiles.size();
-    out.assign((size_t)n_parts + 1, nt);
-    out[0] = 0;
-    uint64_t total = 0;
-    for (const TsTile &T : b->tiles) total += T.own_len;
-    // where equal bases would cut: the first tile whose preceding owned bases reach q / n_parts of the total
-    uint64_t acc = 0, t = 0;
-    for (uint32_t q = 1; q < n_parts; ++q) {
-        const unsigned __int128 target = (unsigned __int128)total * q;
-        for (; t < nt; ++t) {
-            if ((unsigned __int128)acc * n_parts >= target) break;
-            acc += b->tiles[t].own_len;
-        }
-        uint64_t cut = t;
-        if (cut > 0 && cut < nt) {
-            const SegPlan &sp = b->segs[b->tiles[cut].seg];
-            const uint64_t f = sp.first_tile, e = f + sp.n_tiles;
-            if (cut != f) {
-                uint64_t lo, hi;                                     // the allowed positions either side of the cut
-                if (b->tips || e - f < 2ull * g.margin) { lo = f; hi = e; }
-                else if (cut - f < g.margin) { lo = f; hi = f + g.margin; }
-                else if (e - cut < g.margin) { lo = e - g.margin; hi = e; }
-                else { lo = hi = cut; }
-                cut = (cut - lo <= hi - cut) ? lo : hi;
-            }
-        }
-        out[q] = std::max(cut, out[q - 1]);
-    }
-}
-
-ShardRange shard_range(const ts_batch *b, uint32_t n_parts, uint32_t part) {
-    std::vector<uint64_t> cut;
-    shard_boundaries(b, n_parts, cut);
-    const ShardGeom g = shard_geom(b);
-    ShardRange r{};
-    r.own_lo = cut[part]; r.own_hi = cut[part + 1];
-    r.ext_lo = r.own_lo; r.ext_hi = r.own_hi;
-    if (r.own_hi > r.own_lo) {
-        const uint64_t nt = b->tiles.size();
-        if (r.own_lo > 0 && b->segs[b->tiles[r.own_lo].seg].first_tile != r.own_lo) r.ext_lo = r.own_lo - g.ctx;
-        if (r.own_hi < nt && b->segs[b->tiles[r.own_hi].seg].first_tile != r.own_hi) r.ext_hi = r.own_hi + g.ctx;
-        r.seg_begin = b->tiles[r.own_lo].seg;
-        r.n_segs = b->tiles[r.own_hi - 1].seg - r.seg_begin + 1;
-    }
-    return r;
-}
-
 // The context's side stream, on a hardware queue of its own where that can be had.  HIP maps the streams of a process onto a few
 // hardware queues (four by default) and does not say which; kernels of two streams on one queue run one after the other.  A side
 // stream on the SCAN stream's queue puts the terminal walks of step i (a latency chain: ~60-90 us) in front of the scan of step
@@ -139,58 +72,9 @@ int side_stream_for(ts_ctx *c, void *scan_stream, void *pack_stream) {
     return TS_OK;
 }
 
-uint64_t align16u(uint64_t v) { return (v + 15ull) & ~15ull; }
-
-// Sizes of a shard's message.  The variable sections (visible records, blocks) get capacities estimated from the plan —
-// canonical patterns per 4^k positions on random sequence, every position of a terminal zone, a block or two per segment —
-// times `scale`; a message that overflows says so in its header and the caller packs again with a larger scale.
-ShardLayout shard_layout(const ts_batch *b, const ShardRange &r, uint32_t scale) {
-    const ts_ctx *c = b->ctx;
-    const ts_params &P = c->params;
-    ShardLayout L{};
-    if (scale == 0) scale = 1;
-    {
-        uint64_t w0 = 0, w1 = 0;
-        if (!b->tips && r.own_hi > r.own_lo) {
-            w0 = b->tiles[r.own_lo].win_out;
-            const TsTile &last = b->tiles[r.own_hi - 1];
-            w1 = last.win_out + last.nwin;
-        }
-        L.n_windows = w1 - w0;
-    }
-    const bool nuc = P.out_gc || P.out_entropy;
-    L.field_bits = bit_width_u32(P.window_size);
-    L.window_bytes = b->tips ? 0u : (uint32_t)(((nuc ? 7u : 3u) * L.field_bits + 7u) / 8u);
-    L.visible_bytes = ts_batch_wire16_ok(b) ? 2u : 4u;
-    uint64_t own_bases = 0, zone_bases = 0;
-    for (uint64_t t = r.own_lo; t < r.own_hi; ++t) {
-        const TsTile &T = b->tiles[t];
-        own_bases += T.own_len;
-        const SegPlan &sp = b->segs[T.seg];
-        const uint64_t rel0 = T.in_off - sp.in_off, rel1 = rel0 + T.own_len;
-        const uint64_t hi_begin = sp.len > P.terminal_limit ? sp.len - P.terminal_limit : 0;
-        if (rel0 <= P.terminal_limit || rel1 > hi_begin) zone_bases += T.own_len;
-    }
-    uint64_t ncanon = 0;
-    for (const ts::Pattern &p : c->patterns) ncanon += p.is_canonical ? 1 : 0;
-    const double d_canon = (double)std::max<uint64_t>(ncanon, 1) / (double)(1ull << (2 * std::min<uint32_t>(c->k, 16)));
-    uint64_t vis = b->tips ? 0 : (uint64_t)((double)own_bases * d_canon * 1.5) + zone_bases / 8 + 65536;   // (every match of a terminal zone is visible: ~3 % of its bases, more inside a telomere)
-    vis = std::min<uint64_t>(vis * scale, own_bases + 16);
-    L.visible_capacity = (vis + 7ull) & ~7ull;
-    L.block_capacity = (uint32_t)std::min<uint64_t>((16ull * r.n_segs + 256ull) * scale, 1u << 24);
-    uint64_t o = sizeof(TsShardHeader);
-    L.off_segs = o; o = align16u(o + r.n_segs * sizeof(TsShardSeg));
-    L.off_windows = o; o = align16u(o + L.n_windows * L.window_bytes);
-    L.off_tilevis = o; o = align16u(o + (r.own_hi - r.own_lo) * 2ull);
-    L.off_visible = o; o = align16u(o + L.visible_capacity * L.visible_bytes);
-    L.off_blocks = o; o = align16u(o + (uint64_t)L.block_capacity * sizeof(TsDevBlock));
-    L.bytes = o;
-    return L;
-}
-
 void fill_shard_info(const ts_batch *b, uint32_t n_parts, uint32_t part, uint32_t scale, ts_shard_info &o) {
-    const ShardRange r = shard_range(b, n_parts, part);
-    const ShardLayout L = shard_layout(b, r, scale);
+    const ShardRange r = tsplan::shard_range(*b, n_parts, part);
+    const ShardLayout L = tsplan::shard_layout(*b, r, scale);
     std::memset(&o, 0, sizeof o);
     o.n_parts = n_parts; o.part = part;
     o.own_begin = r.own_lo; o.own_end = r.own_hi; o.ext_begin = r.ext_lo; o.ext_end = r.ext_hi;
@@ -204,12 +88,10 @@ void fill_shard_info(const ts_batch *b, uint32_t n_parts, uint32_t part, uint32_
     o.msg_bytes = L.bytes;
     o.visible_capacity = L.visible_capacity; o.block_capacity = L.block_capacity;
     o.window_bytes = L.window_bytes; o.visible_bytes = L.visible_bytes;
-    o.context_tiles = shard_geom(b).ctx;
+    o.context_tiles = tsplan::shard_geom(*b).ctx;
 }
 
 }  // namespace
-
-void ts_shard_boundaries(const ts_batch *b, uint32_t n_parts, std::vector<uint64_t> &out) { shard_boundaries(b, n_parts, out); }
 
 extern "C" {
 
@@ -224,14 +106,14 @@ int ts_batch_restrict_shard(ts_batch *b, uint32_t n_parts, uint32_t part, uint32
     if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_restrict_shard");
     if (!b || !n_parts || part >= n_parts) return TS_ERR_INVALID_ARG;
     if (b->allocated || b->scanned) return b->ctx->fail(TS_ERR_STATE, "ts_batch_restrict_shard after the batch was used on the device");
-    const ShardRange r = shard_range(b, n_parts, part);
+    const ShardRange r = tsplan::shard_range(*b, n_parts, part);
     int rc = ts_batch_restrict(b, r.ext_lo, r.ext_hi);
     if (rc != TS_OK) return rc;
     (void)ts_batch_set_emit(b, 1);                       // the pack takes the visible records and the chain summaries from the scan
     b->shard_parts = n_parts; b->shard_part = part; b->shard_scale = scale ? scale : 1;
     b->own_lo = r.own_lo; b->own_hi = r.own_hi;
     b->shard_r = r;
-    b->shard_L = shard_layout(b, r, b->shard_scale);
+    b->shard_L = tsplan::shard_layout(*b, r, b->shard_scale);
     return TS_OK;
 }
 
@@ -239,7 +121,7 @@ int ts_batch_set_shard_scale(ts_batch *b, uint32_t scale) {
     if (b && b->gen) return ts_general_batch_refuse(b, "ts_batch_set_shard_scale");
     if (!b || !b->shard_parts || !scale) return TS_ERR_INVALID_ARG;
     b->shard_scale = scale;
-    b->shard_L = shard_layout(b, b->shard_r, scale);
+    b->shard_L = tsplan::shard_layout(*b, b->shard_r, scale);
     b->bound_msg = nullptr;                               // (a message of the new size is bound anew)
     return TS_OK;
 }
@@ -472,10 +354,10 @@ extern "C" int ts_shards_finalize(const ts_batch *b, const void *const *msgs, co
         const TsShardHeader &H = *pv.H;
         if (H.magic != TS_SHARD_MAGIC || H.version != TS_SHARD_VERSION || H.n_parts != n_parts || H.part != p)
             return c->fail(TS_ERR_INVALID_ARG, "ts_shards_finalize: message " + std::to_string(p) + " is not part " + std::to_string(p) + " of " + std::to_string(n_parts));
-        pv.r = shard_range(b, n_parts, p);
+        pv.r = tsplan::shard_range(*b, n_parts, p);
         // the scale the sender laid its sections out with travels in the header (reserved[1]); what it implies is checked below
         const uint32_t scale = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(H.reserved[1], 1), 1u << 24);
-        pv.L = shard_layout(b, pv.r, scale);
+        pv.L = tsplan::shard_layout(*b, pv.r, scale);
         if (pv.L.visible_capacity != H.visible_capacity || pv.L.block_capacity != H.block_capacity)
             return c->fail(TS_ERR_INVALID_ARG, "ts_shards_finalize: message " + std::to_string(p) + " was packed with capacities that do not match its scale");
         if (H.own_begin != pv.r.own_lo || H.own_end != pv.r.own_hi || H.ext_begin != pv.r.ext_lo || H.ext_end != pv.r.ext_hi ||

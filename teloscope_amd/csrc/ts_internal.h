@@ -178,7 +178,7 @@ struct TsBlockCallParams {
 // "visible" = the match records a writer reads: canonicalMatches, and nonCanonicalMatches of the terminal zone
 // (src/teloscope.cpp:486-496, writers :700-868); everything else the match stream holds is consumed by block calling,
 // which has happened on the device.  Section offsets are a pure function of the plan, the split and the capacity scale
-// (shard_layout, shard.cpp), so sender and receiver agree on them without talking.
+// (shard_layout, tiled_plan_core.h), so sender and receiver agree on them without talking.
 #define TS_SHARD_MAGIC   0x44485354u    // "TSHD"
 #define TS_SHARD_VERSION 1u
 #define TS_SHARD_F_VISIBLE_OVERFLOW 0x1u    // more visible records than the section holds (n_visible says how many)
@@ -311,7 +311,6 @@ struct TsLaunchInfo {
 #ifdef __cplusplus
 extern "C++" {
 // Implemented in kernels.hip (compiled by hipcc).  All return a hipError_t as int.
-int  ts_k_lds_bytes(const TsScanParams *p);
 int  ts_k_prepare(uint32_t lds_bytes);                       // raises the dynamic-LDS limit
 int  ts_k_launch_scan(const TsScanParams *p, uint32_t grid, uint32_t lds_bytes, void *stream);
 int  ts_k_launch_summary(const uint32_t *tile_stats, const uint32_t *seg_first_tile,

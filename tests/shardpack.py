@@ -44,7 +44,7 @@ def _align16(x):
 
 
 def sections(info, n_segs, n_own_tiles, n_windows):
-    """Byte offsets of a message's sections (shard_layout, shard.cpp)."""
+    """Byte offsets of a message's sections (shard_layout, tiled_plan_core.h)."""
     o = 128
     off = {"segs": o}
     o = _align16(o + n_segs * 64)

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: one grid of window sizes at which the two multi-GPU wire formats are pinned — the shard message's
-bit-packed window records (shard.cpp: shard_layout; field_bits = bit_width(w), 7 fields with -g / -e and 3 without,
+bit-packed window records (tiled_plan_core.h: shard_layout; field_bits = bit_width(w), 7 fields with -g / -e and 3 without,
 window_bytes = ceil(fields x field_bits / 8)) and the full exchange's u16 wire (ts_batch_wire16_ok).
 
 Every entry scans with `-c AAAAAA -x 0 -t 50`, so that a run of A matches at every position: a window of w A's holds
