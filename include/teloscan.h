@@ -938,6 +938,43 @@ int ts_fastq_chunk_stage(ts_chunk *chunk, const ts_fastq_record *recs, size_t n,
 int ts_fastq_chunk_gather(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, const void *d_pass, void *host_out,
                           uint64_t cap, uint64_t *bytes, uint64_t *n_passed, void *stream);
 
+/* ---- Interleaved paired FASTQ (include/teloscope_mi355x_io.hpp: fastqSubsetPaired, fastqSubsetPairedDevice): the read subset of
+ *      an input whose records come in pairs, first mate then second, as `samtools fastq`, `seqtk mergepe` and the -p modes of the
+ *      short-read mappers write and read them.  The reference has no paired mode; the rule is this project's own, stated here and
+ *      nowhere else, and every route follows it:
+ *        - Records are those of the FASTQ record rule above (blank lines in front of a header are skipped, a record is four
+ *          lines), numbered from 0 over the whole input.  Records 2 j and 2 j + 1 are pair j: its first and its second mate.
+ *        - A record's name is the read block report's FASTQ name: the bytes behind '@' up to the first space, tab or the line's
+ *          end, a '\r' in front of the '\n' not counted.  Its mate name is that name without its last two bytes when they are
+ *          "/1" or "/2", and the name itself otherwise.  The suffix is removed once, and whichever mate carries it: "/3", "/12"
+ *          and "/1/" are no suffixes, and a name of exactly "/1" has the empty mate name.
+ *        - A pair is well formed when its two mate names are byte-equal; two empty names are.
+ *        - Every record with bases is judged exactly as the unpaired route judges it.  A pair is kept when at least one of its
+ *          mates passes; both records of a kept pair are written verbatim, first mate first, by ts_fastq_chunk_gather's rule
+ *          (the four lines as they are, a '\n' behind each).  A mate without bases is written with its pair.  Pair order is
+ *          input order.
+ *        - Errors; the lowest offending place of the input wins.  The record errors keep their texts and numbers, "FASTQ record
+ *          <n>: ..." with n counted as the unpaired route counts it, and so do "FASTQ input is empty" and "FASTQ input must
+ *          start with '@'".  "FASTQ records <2j+1> and <2j+2> do not have the same name" (1-based record numbers) is thrown for
+ *          the lowest pair that is not well formed; "FASTQ input ends with an unpaired record" when the input is otherwise valid
+ *          and holds an odd number of records.  A record error at record r wins over the name error of a pair that contains r
+ *          or lies behind it; the name error of a pair wholly in front of r wins over the record error.
+ *        - Before the exception every whole, well-formed pair in front of the offending place has been judged and, if kept,
+ *          written; a single valid record in front of a bad record is never written.  The bytes written before a failure do not
+ *          depend on chunk size, sub-batch size or the number of contexts.
+ *        - Statistics: total = records read, kept = records written (an even number).  The block report keeps its rule; a record
+ *          written only for its mate has no line. */
+/* Whether recs[2 j] and recs[2 j + 1] (records of the chunk, as ts_fastq_chunk_walk gives them; n even, else TS_ERR_INVALID_ARG)
+ * are mates, for every j, a lane per pair, the names read where the chunk holds them: *mismatch = the lowest j that is no well-
+ * formed pair, or UINT64_MAX.  n == 0 is valid and launches nothing.  Waits for the device. */
+int ts_fastq_chunk_mates(ts_chunk *chunk, const ts_fastq_record *recs, size_t n, uint64_t *mismatch);
+/* The pair's verdict for both of its records: read_of[i] (host memory) is record i's index in d_pass (device memory, as
+ * ts_batch_read_pass writes it), or 0xFFFFFFFF when the record had no bases and was not staged; d_pair_pass[2 j] and
+ * d_pair_pass[2 j + 1] (device memory, n bytes, not aliasing d_pass: the two halves of one ts_bam_chunk_pass_buffer) both become
+ * 1 when either mate's own pass byte is set, else 0 — a d_pass for ts_fastq_chunk_gather(chunk, recs, n, ...) over all n records.
+ * n even, else TS_ERR_INVALID_ARG.  Asynchronous on `stream`. */
+int ts_fastq_chunk_pair_pass(ts_chunk *chunk, size_t n, const uint32_t *read_of, const void *d_pass, void *d_pair_pass, void *stream);
+
 /* ---- SAM text in the same resident chunk (include/teloscope_mi355x_io.hpp: samSubset, samSubsetDevice): the third front end of
  *      the read filter, which the reference names and does not have (docs/algorithm.md: "BAM I/O is isolated from scoring so a
  *      future SAM parser or optional CRAM backend can reuse the same filter").  The text reaches the chunk as for FASTQ
@@ -1016,7 +1053,8 @@ int ts_sam_chunk_gather(ts_chunk *chunk, const ts_sam_record *recs, size_t n, co
  *          the line's '\n' not counted to the line (the name may be empty); for FASTA reads the same with '>' in place of '@';
  *          for SAM the bytes in front of the first tab; for BAM read_name without its NUL.
  *        - A record that is not kept has no line; a kept record has at least one (matches() is !terminalBlocks.empty(),
- *          src/read-filter.cpp:37-45).  Secondary and supplementary BAM records are records like any other. */
+ *          src/read-filter.cpp:37-45).  The one amendment: a record of an interleaved pair ("Interleaved paired FASTQ" above)
+ *          that is written only for its mate has no blocks and no line.  Secondary and supplementary BAM records are records like any other. */
 /* One row of a batch's ordered blocks: the segment (read) of the batch and its block, start relative to the segment's abs_pos. */
 typedef struct ts_read_block {
     uint32_t segment;

@@ -910,6 +910,11 @@ struct ReadJudge {
     std::function<int(ts_batch *, unsigned char *, uint64_t, uint64_t *, uint64_t *)> blockLines;
     std::vector<unsigned char> blockText;
     uint64_t blockBytes = 0, nBlockLines = 0;
+    // A step between filter and gather for a route that keeps records by more than their own pass byte (fastqSubsetPairedDevice:
+    // a pair is kept when either mate passes): passRoom more bytes are asked of the chunk's pass buffer behind the reads' own, and
+    // passStep(dPass) answers the pass bytes the gather reads (nothing: it failed).  Empty: no call, no kernel, no allocation.
+    std::function<void *(void *)> passStep;
+    uint64_t passRoom = 0;
 
     // room(dPass): the bytes `kept` must hold before gather is called (0: as it is), for a gather whose refused call is not cheap
     template <typename Stage, typename Gather, typename Room>
@@ -918,7 +923,7 @@ struct ReadJudge {
         if (!batch.p) throw deviceError(ctx, "cannot plan the read batch");
         Clock::time_point t0 = Clock::now();
         if (stage(batch.p) != TS_OK) throw deviceError(ctx, stageFailed);
-        void *dPass = ts_bam_chunk_pass_buffer(chunk, lens.size());
+        void *dPass = ts_bam_chunk_pass_buffer(chunk, lens.size() + passRoom);
         if (!dPass) throw deviceError(ctx, "cannot allocate the pass bytes");
         msStage += since(t0); t0 = Clock::now();
         if (ts_batch_scan(batch.p, nullptr, nullptr) != TS_OK || ts_batch_read_pass(batch.p, dPass, nullptr) != TS_OK) throw deviceError(ctx, "read filter failed");
@@ -942,6 +947,7 @@ struct ReadJudge {
             if (rc != TS_OK) throw deviceError(ctx, "formatting the block report failed");
             msBlocks += since(t0); t0 = Clock::now();
         }
+        if (passStep && !(dPass = passStep(dPass))) throw deviceError(ctx, "the pass bytes of the records failed");
         bytes = nPassed = 0;
         if (kept.size() < (1u << 20)) kept.resize(1u << 20);
         const uint64_t want = room(dPass);
@@ -1107,6 +1113,10 @@ protected:
     ReadChunkSteps(std::ostream *blocks, size_t readsPerBatch) : blocks_(blocks), readsPerBatch_(std::max<size_t>(readsPerBatch, 1)) {}
     Route &route() { return static_cast<Route &>(*this); }
     uint64_t gatherRoom(Worker &, void *) { return 0; }
+    // a sub-batch begins with n records at rec; its record i was placed among the reads to judge, or has no bases (a route that
+    // needs to know: FastqPairChunkSteps)
+    template <typename Rec> void subBatch(Worker &, const Rec *, size_t) {}
+    void placed(Worker &, size_t, bool) {}
     // Records [from, to) of the chunk's table in sub-batches of readsPerBatch, in input order.  A dealt chunk keeps a sub-batch's
     // passing bytes until its turn to emit; an in-place chunk has the turn, and they go from the judge straight to the output.
     void judgeRecords(Worker &k, size_t from, size_t to, bool dealt) {
@@ -1115,7 +1125,12 @@ protected:
             const auto *rec = k.recs.data() + a;
             const size_t n = std::min<size_t>(readsPerBatch_, to - a);
             k.withSeq.clear(); k.lens.clear();
-            for (size_t i = 0; i < n; ++i) if (const uint64_t bases = Route::bases(rec[i])) { k.withSeq.push_back(rec[i]); k.lens.push_back(bases); }
+            r.subBatch(k, rec, n);
+            for (size_t i = 0; i < n; ++i) {
+                const uint64_t bases = Route::bases(rec[i]);
+                if (bases) { k.withSeq.push_back(rec[i]); k.lens.push_back(bases); }
+                r.placed(k, i, bases != 0);
+            }
             if (k.withSeq.empty()) continue;                    // (a read without bases is never kept)
             k.withBases += k.withSeq.size();
             k.st.recordsJudged += k.withSeq.size();
@@ -1234,24 +1249,27 @@ struct FastqWorker : RecordWorker<ts_fastq_record> {
     ChunkFeed::Fill fill;                                       // a dealt chunk's new bytes
     int error = TS_FASTQ_OK;
 };
-class FastqChunkSteps : public TextChunkSteps<FastqChunkSteps, FastqWorker> {
+// (Route: FastqChunkSteps itself, or FastqPairChunkSteps, which frames pairs over the same steps)
+template <typename Route, typename WorkerT = FastqWorker>
+class FastqChunkStepsOf : public TextChunkSteps<Route, WorkerT> {
 public:
-    using Worker = FastqWorker;
+    using Worker = WorkerT;
     FastqSubsetResult result;
 
-    FastqChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
-        : TextChunkSteps(filter, feed, out, readsPerBatch, chunkBytes, blocks, "failed while writing FASTQ subset") {}
+    FastqChunkStepsOf(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
+        : TextChunkSteps<Route, WorkerT>(filter, feed, out, readsPerBatch, chunkBytes, blocks, "failed while writing FASTQ subset") {}
 
     // the chunk's turn to write: what it kept, its totals, and the record that is not valid
     void emit(size_t w, uint64_t) {
-        Worker &k = *workers[w];
-        emitKept(k);
+        Worker &k = *this->workers[w];
+        this->emitKept(k);
         result.kept += k.passed; result.total += k.n; result.blockLines += k.blockLines;
-        if (k.error != TS_FASTQ_OK) {
-            const char *msg = k.error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : k.error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
-                            : k.error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
-            throw std::runtime_error("FASTQ record " + std::to_string(result.total + 1) + ": " + msg);
-        }
+        if (k.error != TS_FASTQ_OK) throw recordError(k.error, result.total + 1);
+    }
+    static std::runtime_error recordError(int error, uint64_t number) {
+        const char *msg = error == TS_FASTQ_TRUNCATED ? "truncated FASTQ record" : error == TS_FASTQ_BAD_HEADER ? "expected header line starting with '@'"
+                        : error == TS_FASTQ_BAD_SEPARATOR ? "expected separator line starting with '+'" : "sequence and quality length differ";
+        return std::runtime_error("FASTQ record " + std::to_string(number) + ": " + msg);
     }
 
     // the format's part of the shared steps
@@ -1266,7 +1284,7 @@ public:
     }
     bool frameChunk(Worker &k, bool atEnd) {
         k.n = 0; k.error = TS_FASTQ_OK;
-        if (first_) {
+        if (this->first_) {
             if (ts_bam_chunk_size(k.chunk) == 0) {
                 if (atEnd) throw std::runtime_error("FASTQ input is empty");
                 return true;
@@ -1274,18 +1292,87 @@ public:
             unsigned char c = 0;
             if (ts_bam_chunk_read(k.chunk, 0, 1, &c) != TS_OK) throw deviceError(k.ctx, "cannot read the chunk");
             if (c != '@') throw std::runtime_error("FASTQ input must start with '@'");
-            first_ = false;
+            this->first_ = false;
         }
         uint64_t errorRecord = 0, errorOff = 0;
         const Clock::time_point t0 = Clock::now();
-        int rc = ts_fastq_chunk_walk(k.chunk, atEnd ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
+        int rc = ts_fastq_chunk_walk(k.chunk, atEnd ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &this->prevNext_, &k.error, &errorRecord, &errorOff);
         if (rc == TS_ERR_INVALID_ARG && k.n > k.recs.size()) {
             k.recs.resize(static_cast<size_t>(k.n));
-            rc = ts_fastq_chunk_walk(k.chunk, atEnd ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &prevNext_, &k.error, &errorRecord, &errorOff);
+            rc = ts_fastq_chunk_walk(k.chunk, atEnd ? 1 : 0, k.recs.data(), k.recs.size(), &k.n, &this->prevNext_, &k.error, &errorRecord, &errorOff);
         }
         if (rc != TS_OK) throw deviceError(k.ctx, "FASTQ walk failed");
         k.st.msWalk += since(t0);
         return k.error == TS_FASTQ_OK;
+    }
+};
+class FastqChunkSteps : public FastqChunkStepsOf<FastqChunkSteps> {
+public:
+    using FastqChunkStepsOf::FastqChunkStepsOf;
+};
+
+// fastqSubsetPairedDevice's stages (the rule: include/teloscan.h, "Interleaved paired FASTQ"): FastqChunkSteps with pairs.  The
+// framing hands on whole pairs only: a chunk that is not the input's last gives up the first mate at its end, so that the next
+// chunk begins at an even record; ts_fastq_chunk_mates compares the names of its pairs, and the lowest pair that is not well
+// formed ends the framing.  A sub-batch is whole pairs; between filter and gather ts_fastq_chunk_pair_pass gives both mates the
+// pair's verdict, and the gather runs over all of the sub-batch's records.
+struct FastqPairWorker : FastqWorker {
+    std::vector<uint32_t> readOf;                               // of the sub-batch under way: a record's place in withSeq, or ~0
+    const ts_fastq_record *sub = nullptr;                       // the sub-batch's records, with and without bases
+    size_t subN = 0;
+    bool mismatch = false, unpaired = false;                    // the pair behind the chunk's records is not well formed; the input ends with a first mate
+    uint64_t dropped = 0;                                       // valid records in front of a record that is not: a first mate, never written
+};
+class FastqPairChunkSteps : public FastqChunkStepsOf<FastqPairChunkSteps, FastqPairWorker> {
+public:
+    using Base = FastqChunkStepsOf<FastqPairChunkSteps, FastqPairWorker>;
+    FastqPairChunkSteps(ReadTelomereFilter &filter, ChunkFeed &feed, std::ostream &out, size_t readsPerBatch, size_t chunkBytes, std::ostream *blocks = nullptr)
+        : Base(filter, feed, out, std::max<size_t>(readsPerBatch + (readsPerBatch & 1u), 2), chunkBytes, blocks) {}
+
+    void emit(size_t w, uint64_t) {
+        Worker &k = *workers[w];
+        emitKept(k);
+        result.kept += k.passed; result.total += k.n; result.blockLines += k.blockLines;
+        if (k.mismatch)
+            throw std::runtime_error("FASTQ records " + std::to_string(result.total + 1) + " and " + std::to_string(result.total + 2) + " do not have the same name");
+        if (k.error != TS_FASTQ_OK) throw recordError(k.error, result.total + k.dropped + 1);
+        if (k.unpaired) throw std::runtime_error("FASTQ input ends with an unpaired record");
+    }
+
+    bool frameChunk(Worker &k, bool atEnd) {
+        k.mismatch = k.unpaired = false; k.dropped = 0;
+        Base::frameChunk(k, atEnd);
+        if (k.n & 1u) {
+            k.n -= 1;
+            if (k.error != TS_FASTQ_OK) k.dropped = 1;          // (the record error stands, with its true number)
+            else if (atEnd) k.unpaired = true;                  // (raised at emit, behind the chunk's whole pairs)
+            else prevNext_ = k.n ? k.recs[k.n].off : 0;         // (no whole pair: the chunk passes all of its contents on, and grows)
+        }
+        uint64_t bad = UINT64_MAX;
+        const Clock::time_point t0 = Clock::now();
+        if (ts_fastq_chunk_mates(k.chunk, k.recs.data(), static_cast<size_t>(k.n), &bad) != TS_OK) throw deviceError(k.ctx, "FASTQ mate names failed");
+        k.st.msWalk += since(t0);
+        if (bad != UINT64_MAX) {
+            k.n = 2 * bad; k.error = TS_FASTQ_OK; k.dropped = 0; k.unpaired = false; k.mismatch = true;
+            return false;
+        }
+        return k.error == TS_FASTQ_OK && !k.unpaired;
+    }
+
+    // the sub-batch's records and where each lies among its reads; the step that pairs the pass bytes
+    void subBatch(Worker &k, const ts_fastq_record *rec, size_t n) {
+        k.sub = rec; k.subN = n;
+        k.readOf.assign(n, 0xffffffffu);
+        k.judged.passRoom = n + 16;
+        if (!k.judged.passStep)
+            k.judged.passStep = [&k](void *dPass) -> void * {
+                void *dPair = static_cast<unsigned char *>(dPass) + ((k.lens.size() + 15) & ~size_t(15));
+                return ts_fastq_chunk_pair_pass(k.chunk, k.subN, k.readOf.data(), dPass, dPair, nullptr) == TS_OK ? dPair : nullptr;
+            };
+    }
+    void placed(Worker &k, size_t i, bool staged) { if (staged) k.readOf[i] = static_cast<uint32_t>(k.withSeq.size() - 1); }
+    int gatherKept(Worker &k, void *dPass, unsigned char *dst, uint64_t cap, uint64_t *bytes, uint64_t *nPassed) {
+        return ts_fastq_chunk_gather(k.chunk, k.sub, k.subN, dPass, dst, cap, bytes, nPassed, nullptr);
     }
 };
 
@@ -1633,6 +1720,17 @@ inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostre
 inline FastqSubsetResult fastqSubsetDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch,
                                            size_t bytesPerBatch, std::vector<ReadRouteDeviceStats> *perDevice, std::ostream *blocks) {
     return detail::textSubsetDeviceRun<detail::FastqChunkSteps>("FASTQ", "fastqSubsetDevice", inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice, blocks);
+}
+
+// fastqSubsetPaired on the device: fastqSubsetDevice's route, arguments and sources, over interleaved pairs (the rule:
+// include/teloscan.h, "Interleaved paired FASTQ").  A chunk hands on whole pairs, their names are compared where the chunk holds
+// them (ts_fastq_chunk_mates), every record with bases is judged as fastqSubsetDevice judges it, and both records of a pair are
+// gathered when either passes (ts_fastq_chunk_pair_pass).  readsPerBatch is rounded up to an even number.  Output, statistics,
+// block report and exceptions are fastqSubsetPaired's, on any number of contexts.
+inline FastqSubsetResult fastqSubsetPairedDevice(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter, size_t readsPerBatch = 1u << 20,
+                                                 size_t bytesPerBatch = size_t(256) << 20, std::vector<ReadRouteDeviceStats> *perDevice = nullptr,
+                                                 std::ostream *blocks = nullptr) {
+    return detail::textSubsetDeviceRun<detail::FastqPairChunkSteps>("FASTQ", "fastqSubsetPairedDevice", inFile, out, filter, readsPerBatch, bytesPerBatch, perDevice, blocks);
 }
 
 namespace detail {

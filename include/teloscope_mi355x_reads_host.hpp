@@ -35,6 +35,7 @@
 
 #include "teloscope_mi355x.hpp"
 #include "../teloscope_amd/csrc/read_block_format_core.h"
+#include "../teloscope_amd/csrc/fastq_pair_core.h"
 #include "../teloscope_amd/csrc/read_fastq_format_core.h"
 
 namespace teloscope_mi355x {
@@ -421,6 +422,42 @@ inline bool splitFastqRecords(const char *data, size_t size, std::vector<FastqRe
     return true;
 }
 
+// What fastqSubset and fastqSubsetPaired do alike with their input and with a kept record.  The input: `-` is stdin; gzip and stdin
+// go through zlib and are never mapped; a regular file that can be mapped is.  blocks() reads what is not mapped in blocks of
+// ~bytesPerBatch: parse(begin, end, last) consumes whole units (records, or pairs) and answers where it stopped; the rest goes in
+// front of the next block.
+struct FastqHostInput {
+    MappedInput in;
+    bool zlib;
+    explicit FastqHostInput(const std::string &inFile) : in(inFile, true, "Stream not successful: " + inFile, false) {
+        zlib = in.openZlib(!in.owned, "Stream not successful: " + inFile);
+        if (!zlib) in.mapFile();
+    }
+    template <typename Parse>
+    void blocks(size_t bytesPerBatch, Parse &&parse) {
+        const size_t blockBytes = std::max<size_t>(bytesPerBatch, 64);
+        BlockReader reader([&](char *dst, size_t cap, bool &last) { return in.fill(dst, cap, last, "read error in FASTQ input"); }, blockBytes,
+                           std::min<size_t>(blockBytes, 1u << 20));
+        size_t left = 0;
+        for (bool first = true;; first = false) {
+            const BlockReader::Block b = reader.next(left);
+            if (first && b.end == b.begin) throw std::runtime_error("FASTQ input is empty");
+            if (first && *b.begin != '@') throw std::runtime_error("FASTQ input must start with '@'");
+            left = static_cast<size_t>(b.end - parse(b.begin, b.end, b.last));
+            if (b.last) break;
+        }
+    }
+};
+// a kept record's four lines and a '\n' behind `text`; a passing record's read to the block report
+inline void fastqEcho(std::string &text, const FastqRec &r) {
+    text.append(r.begin, r.end);
+    text.push_back('\n');
+}
+inline void fastqReportRead(ReadBlockReport &report, const FastqRec &r, const char *seq, uint64_t len) {
+    if (report.on())
+        report.add(r.begin + 1, tsrb::fastq_name_len(ReadBlockReport::Bytes{r.begin}, 0, static_cast<uint32_t>(seq - r.begin)), seq, logicalLineLength(seq, seq + len));
+}
+
 // (the route itself, behind fastqSubset)  A regular file is mapped and parsed where the page cache holds it — the only copy of a
 // sequence is the one into the pinned upload ring; gzip, stdin, a FIFO and a file that cannot be mapped are read in blocks.  Either
 // way a batch's sequences are handed to the filter as pointers into the text and a kept record is echoed as the byte range of
@@ -429,9 +466,9 @@ template <typename Filter>
 inline FastqSubsetResult fastqSubsetWith(const std::string &inFile, std::ostream &out, Filter &filter, size_t readsPerBatch, size_t bytesPerBatch,
                                          std::ostream *blocks) {
     HostReadJudge<Filter> judge(filter, blocks, "failed while writing the FASTQ subset's block report");
-    MappedInput in(inFile, true, "Stream not successful: " + inFile, false);
-    const bool zlib = in.openZlib(!in.owned, "Stream not successful: " + inFile);
-    if (!zlib) in.mapFile();                                    // (gzip and stdin are never mapped)
+    FastqHostInput input(inFile);
+    MappedInput &in = input.in;
+    const bool zlib = input.zlib;
     FastqSubsetResult res;
     std::vector<FastqRec> batch;
     std::string text;
@@ -441,12 +478,8 @@ inline FastqSubsetResult fastqSubsetWith(const std::string &inFile, std::ostream
         res.kept += judge.run(batch.size(),
             [&](size_t i, const char *&seq, uint64_t &len) { seq = batch[i].seq; len = batch[i].seqLen; return true; },
             [&](size_t i, const char *seq, uint64_t len) {
-                const FastqRec &r = batch[i];
-                text.append(r.begin, r.end);
-                text.push_back('\n');
-                if (judge.report.on())
-                    judge.report.add(r.begin + 1, tsrb::fastq_name_len(ReadBlockReport::Bytes{r.begin}, 0, static_cast<uint32_t>(seq - r.begin)), seq,
-                                     logicalLineLength(seq, seq + len));
+                fastqEcho(text, batch[i]);
+                fastqReportRead(judge.report, batch[i], seq, len);
             },
             [&]() {
                 out.write(text.data(), static_cast<std::streamsize>(text.size()));
@@ -494,17 +527,7 @@ inline FastqSubsetResult fastqSubsetWith(const std::string &inFile, std::ostream
         out.flush();
         return res;
     }
-    const size_t blockBytes = std::max<size_t>(bytesPerBatch, 64);
-    BlockReader reader([&](char *dst, size_t cap, bool &last) { return in.fill(dst, cap, last, "read error in FASTQ input"); }, blockBytes,
-                       std::min<size_t>(blockBytes, 1u << 20));
-    size_t left = 0;
-    for (bool first = true;; first = false) {
-        const BlockReader::Block b = reader.next(left);
-        if (first && b.end == b.begin) throw std::runtime_error("FASTQ input is empty");
-        if (first && *b.begin != '@') throw std::runtime_error("FASTQ input must start with '@'");
-        left = static_cast<size_t>(b.end - parseRange(b.begin, b.end, b.last));       // (a partial record: in front of the next block)
-        if (b.last) break;
-    }
+    input.blocks(bytesPerBatch, parseRange);                    // (a partial record: in front of the next block)
     out.flush();
     return res;
 }
@@ -513,6 +536,94 @@ inline FastqSubsetResult fastqSubsetWith(const std::string &inFile, std::ostream
 inline FastqSubsetResult fastqSubset(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
                                      size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 512u << 20, std::ostream *blocks = nullptr) {
     return detail::fastqSubsetWith(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The read subset of interleaved paired FASTQ (the rule: include/teloscan.h, "Interleaved paired FASTQ"; the reference has no
+// paired mode): records 2 j and 2 j + 1 are a pair, a pair whose mate names differ is an error, and a pair is kept, both records
+// verbatim, when at least one mate passes the filter.  Input, record rule, judge and block report are fastqSubset's.  A batch is
+// whole pairs, up to readsPerBatch records (rounded up to an even number) or bytesPerBatch bytes; with the block reader the
+// unfinished pair goes in front of the next block.  Before an exception every whole, well-formed pair in front of the offending
+// place has been judged and, if kept, written.
+namespace detail {
+template <typename Filter>
+inline FastqSubsetResult fastqSubsetPairedWith(const std::string &inFile, std::ostream &out, Filter &filter, size_t readsPerBatch, size_t bytesPerBatch,
+                                               std::ostream *blocks) {
+    HostReadJudge<Filter> judge(filter, blocks, "failed while writing the FASTQ subset's block report");
+    FastqHostInput input(inFile);
+    readsPerBatch = std::max<size_t>(readsPerBatch + (readsPerBatch & 1u), 2);
+    FastqSubsetResult res;
+    std::vector<FastqRec> batch;                                // whole pairs
+    std::vector<uint8_t> pass;
+    std::string text;
+    // judges `batch` and echoes the kept pairs
+    auto runBatch = [&]() {
+        text.clear();
+        pass.assign(batch.size(), 0);
+        uint64_t written = 0;
+        judge.run(batch.size(),
+            [&](size_t i, const char *&seq, uint64_t &len) { seq = batch[i].seq; len = batch[i].seqLen; return true; },
+            [&](size_t i, const char *seq, uint64_t len) { pass[i] = 1; fastqReportRead(judge.report, batch[i], seq, len); },
+            [&]() {
+                for (size_t j = 0; j + 1 < batch.size(); j += 2)
+                    if (pass[j] || pass[j + 1]) { fastqEcho(text, batch[j]); fastqEcho(text, batch[j + 1]); written += 2; }
+                out.write(text.data(), static_cast<std::streamsize>(text.size()));
+                if (!out.good()) throw std::runtime_error("failed while writing FASTQ subset");
+            });
+        res.kept += written;
+        res.total += batch.size();
+        res.blockLines = judge.report.lines;
+        batch.clear();
+    };
+    auto fail = [&](const std::string &message) {               // what stands in front of the offending place first
+        runBatch();
+        throw std::runtime_error(message);
+    };
+    // Whole pairs out of [p, end); returns where the first pair that does not end inside the text begins.
+    uint64_t recordNumber = 0;                                  // records of the whole pairs so far
+    auto parseRange = [&](const char *p, const char *const end, const bool eof) -> const char * {
+        size_t batchBytes = 0;
+        for (;;) {
+            FastqRec mate[2];
+            const char *q = p, *pairStart = nullptr;
+            int have = 0;
+            bool needMore = false;
+            while (have < 2 && q < end) {
+                const char *next = q;
+                const FastqStep step = fastqRecordAt(q, end, eof, mate[have], next);
+                if (step == FastqStep::NeedMore) { needMore = true; break; }
+                if (step > FastqStep::NeedMore) fail("FASTQ record " + std::to_string(recordNumber + static_cast<uint64_t>(have) + 1) + ": " + fastqStepText(step));
+                if (step == FastqStep::Record && have++ == 0) pairStart = q;
+                q = next;
+            }
+            if (have < 2) {
+                if (!needMore && eof && have == 1) fail("FASTQ input ends with an unpaired record");
+                if (batch.size()) runBatch();
+                return have ? pairStart : q;                    // (blank lines behind the last pair are consumed)
+            }
+            const ReadBlockReport::Bytes a{mate[0].begin}, b{mate[1].begin};
+            if (!tspair::mates(a, 0, static_cast<uint32_t>(mate[0].seq - mate[0].begin), b, 0, static_cast<uint32_t>(mate[1].seq - mate[1].begin)))
+                fail("FASTQ records " + std::to_string(recordNumber + 1) + " and " + std::to_string(recordNumber + 2) + " do not have the same name");
+            recordNumber += 2;
+            batch.push_back(mate[0]); batch.push_back(mate[1]);
+            batchBytes += static_cast<size_t>(q - p);
+            p = q;
+            if (batch.size() >= readsPerBatch || batchBytes >= bytesPerBatch) { runBatch(); batchBytes = 0; }
+        }
+    };
+    if (!input.zlib && input.in.data) {
+        const char *data = reinterpret_cast<const char *>(input.in.data);
+        if (data[0] != '@') throw std::runtime_error("FASTQ input must start with '@'");
+        (void)parseRange(data, data + input.in.size, true);
+    } else input.blocks(bytesPerBatch, parseRange);
+    out.flush();
+    return res;
+}
+}  // namespace detail
+
+inline FastqSubsetResult fastqSubsetPaired(const std::string &inFile, std::ostream &out, ReadTelomereFilter &filter,
+                                           size_t readsPerBatch = 1u << 20, size_t bytesPerBatch = 512u << 20, std::ostream *blocks = nullptr) {
+    return detail::fastqSubsetPairedWith(inFile, out, filter, readsPerBatch, bytesPerBatch, blocks);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -297,6 +297,7 @@ SYMBOLS = [
     "ts_bam_chunk_block_lines", "ts_read_block_lines_format", "ts_read_block_text_stats",
     "ts_bam_chunk_gather_fastq", "ts_sam_chunk_gather_fastq", "ts_read_fastq_text_stats",
     "ts_fasta_chunk_stage", "ts_fasta_chunk_gather", "ts_fasta_chunk_block_lines",
+    "ts_fastq_chunk_mates", "ts_fastq_chunk_pair_pass",
 ]
 
 
@@ -495,6 +496,8 @@ def lib():
     L.ts_fastq_chunk_stage.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p]
     L.ts_fastq_chunk_gather.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.ts_fastq_chunk_mates.argtypes = [C.c_void_p, C.POINTER(FastqRecord), C.c_size_t, C.POINTER(C.c_uint64)]
+    L.ts_fastq_chunk_pair_pass.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p]
     L.ts_sam_chunk_walk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SamRecord), C.c_uint64] + [C.POINTER(C.c_uint64)] * 5 + \
         [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.ts_sam_chunk_stage.argtypes = [C.c_void_p, C.POINTER(SamRecord), C.c_size_t, C.c_void_p, C.c_void_p]

@@ -52,8 +52,8 @@ struct ts_bam_chunk {
         std::vector<unsigned char> h_idx_rows;
         DeflateBufs deflate;                // ts_bam_chunk_gather_bgzf's buffers (deflate.cpp)
     } bam;
-    // ---- FASTQ (fastq.cpp): the framing results
-    struct Fastq { DevBuf d_frames; } fastq;
+    // ---- FASTQ (fastq.cpp): the framing results; of the paired route, where a sub-batch's records lie among its judged reads
+    struct Fastq { DevBuf d_frames, d_read_of; } fastq;
     // ---- FASTA (fasta.cpp): the header counts per slice, the walk's header table, record table and names; the join's jobs, their
     // counts, the joined bases and runs; a byte per record of the strict check
     struct Fasta {

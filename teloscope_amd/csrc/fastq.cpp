@@ -101,4 +101,47 @@ int ts_fastq_chunk_gather(ts_chunk *ch, const ts_fastq_record *recs, size_t n, c
                            ts_k_launch_chunk_gather_plan_fastq, ts_k_launch_fastq_gather);
 }
 
+int ts_fastq_chunk_mates(ts_chunk *ch, const ts_fastq_record *recs, size_t n, uint64_t *mismatch) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if (!mismatch || (n && !recs) || (n & 1u) || n > 0x7fffffffull)
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_mates: null or out-of-range argument, or an odd number of records");
+    *mismatch = UINT64_MAX;
+    if (n == 0) return TS_OK;
+    // (the header line lies inside the record: every byte the kernel reads of it is the chunk's)
+    for (size_t i = 0; i < n; ++i)
+        if (!record_ok(ch, recs[i]) || recs[i].seq_at < 2) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_mates: record " + std::to_string(i) + " does not fit the chunk");
+    DEVICE_TRY(ctx);
+    unsigned long long *d_lowest = (unsigned long long *)ch->d_out.p;
+    unsigned long long lowest = ~0ull;
+    HIP_TRY(ctx, ch->d_recs.ensure(n * sizeof(ts_fastq_record)));
+    HIP_TRY(ctx, hipMemcpy(ch->d_recs.p, recs, n * sizeof(ts_fastq_record), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_lowest, &lowest, sizeof lowest, hipMemcpyHostToDevice));
+    if (ts_k_launch_fastq_mates(ch->d_plain.p, ch->plain_n, ch->d_recs.p, n / 2, d_lowest, nullptr) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_fastq_chunk_mates: kernel launch failed");
+    HIP_TRY(ctx, hipMemcpy(&lowest, d_lowest, sizeof lowest, hipMemcpyDeviceToHost));
+    if (lowest != ~0ull && lowest >= n / 2) return ctx->fail(TS_ERR_STATE, "ts_fastq_chunk_mates: the pair lies behind the records");
+    *mismatch = lowest;
+    return TS_OK;
+}
+
+int ts_fastq_chunk_pair_pass(ts_chunk *ch, size_t n, const uint32_t *read_of, const void *d_pass, void *d_pair_pass, void *stream) {
+    if (!ch) return TS_ERR_INVALID_ARG;
+    ts_ctx *ctx = ch->ctx;
+    if ((n && (!read_of || !d_pass || !d_pair_pass)) || (n & 1u) || n > 0x7fffffffull || (n && d_pass == d_pair_pass))
+        return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_pair_pass: null, aliased or out-of-range argument, or an odd number of records");
+    if (n == 0) return TS_OK;
+    // (a record's index in d_pass lies in front of the judged reads' number, which is at most n)
+    for (size_t i = 0; i < n; ++i)
+        if (read_of[i] != 0xffffffffu && read_of[i] >= n) return ctx->fail(TS_ERR_INVALID_ARG, "ts_fastq_chunk_pair_pass: record " + std::to_string(i) + " points behind the judged reads");
+    DEVICE_TRY(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, ch->fastq.d_read_of.ensure(n * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ch->fastq.d_read_of.p, read_of, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                    // (read_of is the caller's memory: it has left it when this returns)
+    if (ts_k_launch_fastq_pair_pass(ch->fastq.d_read_of.p, d_pass, n / 2, d_pair_pass, stream) != 0)
+        return ctx->fail(TS_ERR_HIP, "ts_fastq_chunk_pair_pass: kernel launch failed");
+    return TS_OK;
+}
+
 }  // extern "C"

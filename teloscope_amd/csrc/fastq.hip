@@ -12,12 +12,15 @@
 //     the record in readFastqRecord's order; the lowest record that fails wins by a 64-bit atomic minimum.
 //   * stage and gather: 16 bytes per lane from an unaligned source — five aligned dwords and v_alignbyte_b32
 //     (chunk_device.h) — to a 16-byte aligned destination.  The gather's places come from chunk.hip's plan.
+//   * interleaved pairs: a lane per pair compares the two mate names by fastq_pair_core.h's rule, read through aligned dwords,
+//     and the lowest pair that fails wins by a 64-bit atomic minimum; a byte kernel gives both mates the pair's verdict.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/teloscan.h"
 #include "chunk_device.h"
 #include "fastq_internal.h"
+#include "fastq_pair_core.h"
 #include "ts_device.h"
 
 namespace {
@@ -165,9 +168,74 @@ void ts_fastq_gather_kernel(const unsigned char *plain, const ts_fastq_record *r
     if (threadIdx.x == 63) dst[size] = '\n';
 }
 
+// ---- interleaved pairs (include/teloscan.h: "Interleaved paired FASTQ"): records 2 j and 2 j + 1 of the table are pair j
+// The chunk's bytes for one lane, through the aligned dword that holds them, kept until another is asked for (a name is read in
+// order).  The chunk's last dword, where the chunk ends inside it, is put together from the bytes that are the chunk's: no load
+// touches a byte outside [0, n).
+struct MateBytes {
+    const unsigned char *plain;                                 // (dword aligned: the chunk's allocation)
+    unsigned long long n;
+    mutable unsigned long long at;
+    mutable uint32_t w;
+    __device__ __forceinline__ uint32_t byte(unsigned long long i) const {
+        if (i >= n) return 0u;
+        const unsigned long long a = i & ~3ull;
+        if (a != at) {
+            at = a;
+            if (n - a >= 4ull) w = *(const uint32_t *)__builtin_assume_aligned(plain + a, 4);
+            else {
+                w = 0u;
+                for (uint32_t k = 0; a + k < n; ++k) w |= (uint32_t)plain[a + k] << (8u * k);
+            }
+        }
+        return (w >> (8u * (uint32_t)(i & 3ull))) & 255u;
+    }
+};
+
+// a lane per pair: the lowest pair whose records are not mates, by a 64-bit atomic minimum (one atomic per wave)
+__global__ __launch_bounds__(64)
+void ts_fastq_mates_kernel(const unsigned char *plain, unsigned long long n_bytes, const ts_fastq_record *recs, unsigned long long n_pairs,
+                           unsigned long long *lowest) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * 64u + threadIdx.x;
+    bool bad = false;
+    if (j < n_pairs) {
+        const ts_fastq_record a = recs[2 * j], b = recs[2 * j + 1];
+        const MateBytes ra{plain, n_bytes, ~0ull, 0u}, rb{plain, n_bytes, ~0ull, 0u};
+        bad = !tspair::mates(ra, a.off, a.seq_at, rb, b.off, b.seq_at);
+    }
+    const unsigned long long wrong = ballot64(bad);
+    if (wrong && threadIdx.x == (uint32_t)__builtin_ctzll(wrong)) atomicMin(lowest, j);
+}
+
+// a lane per pair: both records' bytes of pair_pass are 1 when either mate's own pass byte is set (read_of: a record's index in
+// pass, ~0 when it was not judged)
+__global__ __launch_bounds__(64)
+void ts_fastq_pair_pass_kernel(const uint32_t *read_of, const unsigned char *pass, unsigned long long n_pairs, unsigned char *pair_pass) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * 64u + threadIdx.x;
+    if (j >= n_pairs) return;
+    const uint32_t a = read_of[2 * j], b = read_of[2 * j + 1];
+    const bool keep = (a != 0xffffffffu && pass[a] != 0) || (b != 0xffffffffu && pass[b] != 0);
+    pair_pass[2 * j] = pair_pass[2 * j + 1] = keep ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ts_k_launch_fastq_mates(const void *plain, unsigned long long n_bytes, const void *recs, unsigned long long n_pairs,
+                            unsigned long long *lowest, void *stream) {
+    if (n_pairs == 0) return 0;
+    hipLaunchKernelGGL(ts_fastq_mates_kernel, dim3((unsigned)((n_pairs + 63u) / 64u)), dim3(64), 0, (hipStream_t)stream,
+                       (const unsigned char *)plain, n_bytes, (const ts_fastq_record *)recs, n_pairs, lowest);
+    return (int)hipGetLastError();
+}
+
+int ts_k_launch_fastq_pair_pass(const void *read_of, const void *pass, unsigned long long n_pairs, void *pair_pass, void *stream) {
+    if (n_pairs == 0) return 0;
+    hipLaunchKernelGGL(ts_fastq_pair_pass_kernel, dim3((unsigned)((n_pairs + 63u) / 64u)), dim3(64), 0, (hipStream_t)stream,
+                       (const uint32_t *)read_of, (const unsigned char *)pass, n_pairs, (unsigned char *)pair_pass);
+    return (int)hipGetLastError();
+}
 
 int ts_k_launch_fastq_frames(const uint32_t *lstart, const unsigned char *cr, uint32_t n_lines, uint32_t newlines, void *frames,
                              void *entries, unsigned long long *out, void *stream) {

@@ -24,4 +24,9 @@ int ts_k_launch_fastq_records(const uint32_t *lstart, const unsigned char *first
 int ts_k_launch_fastq_stage(const void *plain, const void *jobs, uint32_t n_jobs, void *in, void *stream);
 int ts_k_launch_fastq_gather(const void *plain, const void *recs, const void *dst_off, unsigned long long n, unsigned long long cap,
                              void *out, void *stream);
+// interleaved pairs: *lowest = min(*lowest, the lowest j < n_pairs for which recs[2 j] and recs[2 j + 1] are not mates); both bytes
+// of a pair in pair_pass from the mates' own pass bytes
+int ts_k_launch_fastq_mates(const void *plain, unsigned long long n_bytes, const void *recs, unsigned long long n_pairs,
+                            unsigned long long *lowest, void *stream);
+int ts_k_launch_fastq_pair_pass(const void *read_of, const void *pass, unsigned long long n_pairs, void *pair_pass, void *stream);
 }
